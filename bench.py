@@ -14,9 +14,17 @@ environment is all that is used).
     python bench.py --gpus 1 --steps 10 --warmup 3
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
-The default single-GPU run appends `extra`: BASELINE configs[2]'s shape (128 HD pairs,
-SIFT(2048) + BF-L2) and the consecutive-frame stream (configs[4] stand-in), each with its
-own roofline and cpu_baseline (--no-extra skips them).
+A plain run does only what the headline needs: it renders the inputs, warms up, times
+--steps steps and prints the result line (pairs/s, ms_per_step, median rotation error,
+per-stage device times of the timed steps).  --dump-outputs DIR also writes the pose
+records of the last timed step as .npy files (dump_outputs).
+
+--full adds what takes work of its own: the roofline (live VALU / HBM calibration kernels
++ the committed PMC counters), cpu_baseline (the oracle on a sample of the same batch, also
+a GPU == CPU check), and on the default single-GPU workload `extra`: BASELINE configs[2]'s
+shape (128 HD pairs, SIFT(2048) + BF-L2) and the consecutive-frame stream (configs[4]
+stand-in), each with its own roofline and cpu_baseline, and the drop-in's operating points
+(--no-calibrate / --no-cpu-baseline / --no-extra leave parts of it out).
 """
 import argparse
 import json
@@ -35,6 +43,7 @@ HBM_PEAK_GBS = 8000.0   # MI355X HBM3E spec peak (MI355X_MICROARCH.md); ~6290 me
 VALU_PEAK_WAVE_INSTS = 256 * 4 * 2.4e9 / 2
 # dense int8 MFMA peak: 2x the bf16 rate per clock (MI355X_MICROARCH.md 'Matrix cores'), bf16 dense ~2.5 PFLOP/s
 MFMA_I8_PEAK_TOPS = 5000.0
+DUMP_LIMIT_BYTES = 64 << 20      # --dump-outputs: at most this much in all
 COUNTERS = os.path.join(ROOT, "profiles", "r03_counters.json")
 if not os.path.exists(COUNTERS):
     COUNTERS = os.path.join(ROOT, "profiles", "r02_counters.json")
@@ -171,10 +180,14 @@ def parse():
     ap.add_argument("--max-matches", type=int, default=500)
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--height", type=int, default=480)
-    ap.add_argument("--cpu-sample", type=int, default=1024, help="pairs of the batch the CPU oracle is timed on (about 10 s on a 16-core share)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extra", action="store_true", help="skip the configs[2] / stream lines appended to the default single-GPU run")
-    ap.add_argument("--no-calibrate", action="store_true", help="skip the live VALU / HBM calibration kernels")
+    ap.add_argument("--full", action="store_true",
+                    help="also the roofline, cpu_baseline and (default single-GPU workload) `extra`; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write the pose records of the last timed step to DIR/<name>.npy (float64)")
+    ap.add_argument("--cpu-sample", type=int, default=1024, help="pairs of the batch the CPU oracle is timed on with --full (about 10 s on a 16-core share)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without cpu_baseline")
+    ap.add_argument("--no-extra", action="store_true", help="--full without the configs[2] / stream / drop-in lines of the default single-GPU run")
+    ap.add_argument("--no-calibrate", action="store_true", help="--full without the live VALU / HBM calibration kernels")
     ap.add_argument("--gen-workers", type=int, default=0)
     ap.add_argument("--config", type=int, default=2, choices=[2, 3],
                     help="BASELINE configs[]: 2 = 1024 VGA pairs ORB(1000)+Hamming (the metric's config, default); "
@@ -239,8 +252,23 @@ def generate(args, method, rank, world, workers):
     return dict(K=K, i1=i1, i2=i2, Rgt=Rgt, tgt=tgt, first_pair=rank * B, distinct=U)
 
 
-def run_workload(args, method, sub, data, rank, world, device, comm_kind):
-    """times args.steps steps of one workload on this rank's GPU; returns the JSON object (rank 0) or None"""
+def dump_outputs(out_dir, rec):
+    """The pose records of every pair of one step (all ranks, in pair order) as DIR/{R,t,inliers,n_matches,status,pair}.npy,
+    float64: what a caller of the timed path receives.  Above DUMP_LIMIT_BYTES, a fixed seeded sample of the pairs."""
+    rec = rec[np.argsort(rec["pair"], kind="stable")]
+    per_pair = 8 * (9 + 3 + 4)
+    if len(rec) * per_pair > DUMP_LIMIT_BYTES:
+        rec = rec[np.sort(np.random.default_rng(0).choice(len(rec), DUMP_LIMIT_BYTES // per_pair, replace=False))]
+    n = len(rec)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in (("R", rec["R"].reshape(n, 3, 3)), ("t", rec["t"].reshape(n, 3, 1)), ("inliers", rec["inliers"]),
+                    ("n_matches", rec["n_matches"]), ("status", rec["status"]), ("pair", rec["pair"])):
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.asarray(a, np.float64))
+
+
+def run_workload(args, method, sub, data, rank, world, device, comm_kind, dump_dir=""):
+    """times args.steps steps of one workload on this rank's GPU; returns the JSON object (rank 0) or None.
+    dump_dir: where rank 0 writes the outputs of the last timed step (dump_outputs)."""
     from relative_pose_estimation_amd import _capi, geometry, sharding
     W, H, B = args.width, args.height, args.batch
     K, i1, i2, Rgt, tgt = data["K"], data["i1"], data["i2"], data["Rgt"], data["tgt"]
@@ -337,6 +365,8 @@ def run_workload(args, method, sub, data, rank, world, device, comm_kind):
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
     assert len(rec) == world * B and sorted(rec["pair"].tolist()) == list(range(world * B)), "pose gather incomplete"
+    if dump_dir and rank == 0:
+        dump_outputs(dump_dir, rec)
 
     R, t, inl, nm, st = local
     ok = st == 0
@@ -356,64 +386,65 @@ def run_workload(args, method, sub, data, rank, world, device, comm_kind):
 
     out = None
     if rank == 0:
-        names = SIFT_STAGE_KERNEL if method == "SIFT" else STAGE_KERNEL
-        wkey = f"{method}_{W}x{H}_{args.nfeatures}_{int(Bl)}" + ("_stream" if args.stream else "")
-        ctr = counters_for(wkey)
-        calib = {}
+        if args.full:
+            names = SIFT_STAGE_KERNEL if method == "SIFT" else STAGE_KERNEL
+            wkey = f"{method}_{W}x{H}_{args.nfeatures}_{int(Bl)}" + ("_stream" if args.stream else "")
+            ctr = counters_for(wkey)
+            calib = {}
 
-        def issue_rate(kind):
-            if args.no_calibrate:
-                return None
-            if kind not in calib:
-                calib[kind] = eng.calibrate_valu(kind, 8)
-            return calib[kind]
+            def issue_rate(kind):
+                if args.no_calibrate:
+                    return None
+                if kind not in calib:
+                    calib[kind] = eng.calibrate_valu(kind, 8)
+                return calib[kind]
 
-        def roof(stage):
-            """both roofs of one stage's kernel: HBM (algorithmic bytes / spec peak) and VALU issue (SQ_INSTS_VALU of the
-            committed PMC pass / measured issue rate of the instruction kind its inner loop is made of)"""
-            ms = stage_ms[stage]
-            b = stage_bytes(stage, W, H, pyr_px, args.nfeatures, args.max_matches, method) * Bl
-            ach = b / (ms * 1e-3) / 1e9
-            r = {"kernel": names.get(stage, stage), "stage": stage, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                 "frac": ach / HBM_PEAK_GBS, "traffic": kernel_counter(ctr, names.get(stage, stage).split(" ")[0].replace("_*_kernel", "_"), "hbm_bytes_per_launch"),
-                 "algorithmic_bytes_per_launch": b, "avg_launch_ms": ms}
-            insts = kernel_counter(ctr, names.get(stage, stage).split(" ")[0].replace("_*_kernel", "_"), "valu_insts_per_launch")
-            rate = issue_rate(STAGE_CALIB_KIND.get(stage, 5))
-            if insts is not None:
-                v = {"insts": insts, "insts_per_s": insts / (ms * 1e-3), "spec_peak_insts_per_s": VALU_PEAK_WAVE_INSTS,
-                     "frac_of_spec": insts / (ms * 1e-3) / VALU_PEAK_WAVE_INSTS}
-                if rate is not None:
-                    v.update({"measured_peak_insts_per_s": rate[1], "calibration_instruction": rate[0], "frac": insts / (ms * 1e-3) / rate[1]})
+            def roof(stage):
+                """both roofs of one stage's kernel: HBM (algorithmic bytes / spec peak) and VALU issue (SQ_INSTS_VALU of the
+                committed PMC pass / measured issue rate of the instruction kind its inner loop is made of)"""
+                ms = stage_ms[stage]
+                b = stage_bytes(stage, W, H, pyr_px, args.nfeatures, args.max_matches, method) * Bl
+                ach = b / (ms * 1e-3) / 1e9
+                r = {"kernel": names.get(stage, stage), "stage": stage, "achieved": ach, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                     "frac": ach / HBM_PEAK_GBS, "traffic": kernel_counter(ctr, names.get(stage, stage).split(" ")[0].replace("_*_kernel", "_"), "hbm_bytes_per_launch"),
+                     "algorithmic_bytes_per_launch": b, "avg_launch_ms": ms}
+                insts = kernel_counter(ctr, names.get(stage, stage).split(" ")[0].replace("_*_kernel", "_"), "valu_insts_per_launch")
+                rate = issue_rate(STAGE_CALIB_KIND.get(stage, 5))
+                if insts is not None:
+                    v = {"insts": insts, "insts_per_s": insts / (ms * 1e-3), "spec_peak_insts_per_s": VALU_PEAK_WAVE_INSTS,
+                         "frac_of_spec": insts / (ms * 1e-3) / VALU_PEAK_WAVE_INSTS}
+                    if rate is not None:
+                        v.update({"measured_peak_insts_per_s": rate[1], "calibration_instruction": rate[0], "frac": insts / (ms * 1e-3) / rate[1]})
+                    else:
+                        v["frac"] = v["frac_of_spec"]
+                    r["valu"] = v
+                    r["bound"] = "valu" if v["frac"] > r["frac"] else "hbm"
                 else:
-                    v["frac"] = v["frac_of_spec"]
-                r["valu"] = v
-                r["bound"] = "valu" if v["frac"] > r["frac"] else "hbm"
-            else:
-                r["bound"] = "hbm"
-            return r
+                    r["bound"] = "hbm"
+                return r
 
-        dom = max(stage_ms, key=stage_ms.get)
-        rl = roof(dom)
-        rl["matcher"] = roof("match")              # the stage north_star attaches a roofline target to: always reported
-        if method == "ORB":
-            # the crossCheck Hamming matcher runs its O(N^2) part on the matrix cores: d = |q| + |t| - 2 q.t over 256 0/1 bytes,
-            # 32x32 tiles of v_mfma_i32_32x32x32_i8 (8 per tile); N1 = N2 = nfeatures is the algorithmic problem size
-            ops = 2.0 * 256 * args.nfeatures * args.nfeatures * Bl
-            tops = ops / (stage_ms["match"] * 1e-3) / 1e12
-            rl["matcher"]["mfma"] = {"ops": ops, "achieved": tops, "peak": MFMA_I8_PEAK_TOPS, "unit": "TOP/s (int8, dense)", "frac": tops / MFMA_I8_PEAK_TOPS}
-            if rl["matcher"]["mfma"]["frac"] > max(rl["matcher"]["frac"], rl["matcher"].get("valu", {}).get("frac", 0.0)):
-                rl["matcher"]["bound"] = "mfma"
-        else:
-            # the L2 matcher: |a-b|^2 = |a'|^2 + |b'|^2 - 2 a'.b' with a' = a - 128 as int8, 4 x v_mfma_i32_32x32x32_i8 per 32 x 32
-            # tile (K = 128), two crossCheck passes; the stage time includes the norms and the select kernels
-            ops = 2 * 2.0 * 128 * args.nfeatures * args.nfeatures * Bl
-            tops = ops / (stage_ms["match"] * 1e-3) / 1e12
-            rl["matcher"]["mfma"] = {"ops": ops, "achieved": tops, "peak": MFMA_I8_PEAK_TOPS, "unit": "TOP/s (int8, dense)", "frac": tops / MFMA_I8_PEAK_TOPS}
-        if not args.no_calibrate:
-            try:
-                rl["hbm_measured_gbs"] = eng.calibrate_hbm() / 1e9
-            except _capi.RpeError:
-                rl["hbm_measured_gbs"] = None
+            dom = max(stage_ms, key=stage_ms.get)
+            rl = roof(dom)
+            rl["matcher"] = roof("match")              # the stage north_star attaches a roofline target to: always reported
+            if method == "ORB":
+                # the crossCheck Hamming matcher runs its O(N^2) part on the matrix cores: d = |q| + |t| - 2 q.t over 256 0/1 bytes,
+                # 32x32 tiles of v_mfma_i32_32x32x32_i8 (8 per tile); N1 = N2 = nfeatures is the algorithmic problem size
+                ops = 2.0 * 256 * args.nfeatures * args.nfeatures * Bl
+                tops = ops / (stage_ms["match"] * 1e-3) / 1e12
+                rl["matcher"]["mfma"] = {"ops": ops, "achieved": tops, "peak": MFMA_I8_PEAK_TOPS, "unit": "TOP/s (int8, dense)", "frac": tops / MFMA_I8_PEAK_TOPS}
+                if rl["matcher"]["mfma"]["frac"] > max(rl["matcher"]["frac"], rl["matcher"].get("valu", {}).get("frac", 0.0)):
+                    rl["matcher"]["bound"] = "mfma"
+            else:
+                # the L2 matcher: |a-b|^2 = |a'|^2 + |b'|^2 - 2 a'.b' with a' = a - 128 as int8, 4 x v_mfma_i32_32x32x32_i8 per 32 x 32
+                # tile (K = 128), two crossCheck passes; the stage time includes the norms and the select kernels
+                ops = 2 * 2.0 * 128 * args.nfeatures * args.nfeatures * Bl
+                tops = ops / (stage_ms["match"] * 1e-3) / 1e12
+                rl["matcher"]["mfma"] = {"ops": ops, "achieved": tops, "peak": MFMA_I8_PEAK_TOPS, "unit": "TOP/s (int8, dense)", "frac": tops / MFMA_I8_PEAK_TOPS}
+            if not args.no_calibrate:
+                try:
+                    rl["hbm_measured_gbs"] = eng.calibrate_hbm() / 1e9
+                except _capi.RpeError:
+                    rl["hbm_measured_gbs"] = None
         out = {
             "metric": "image-pairs/s end-to-end (640x480 pairs), median rotation-angle error alongside",
             "value": world * B * args.steps / elapsed,
@@ -440,9 +471,10 @@ def run_workload(args, method, sub, data, rank, world, device, comm_kind):
             "median_translation_dir_error_deg": float(np.median(terrs)) if len(terrs) else None,
             "pairs_ok": int(ok.sum()),
             "stage_ms_per_launch": {k: round(v, 4) for k, v in stage_ms.items()},
-            "roofline": rl,
         }
-        if not args.no_cpu_baseline and world == 1:
+        if args.full:
+            out["roofline"] = rl
+        if args.full and not args.no_cpu_baseline and world == 1:
             res, cb = cpu_baseline(i1, i2, K, args.nfeatures, args.max_matches, args.cpu_sample, method)
             n = len(res)
             cerr = [geometry.rotation_error(res["R"][i].reshape(3, 3), Rgt[i]) for i in range(n) if res["status"][i] == 0]
@@ -595,13 +627,15 @@ def main():
         self_launch(args)
     if args.gpus != world:
         raise SystemExit(f"--gpus {args.gpus} but WORLD_SIZE={world}: launch with --nproc-per-node {args.gpus} (or without a launcher)")
+    if args.steps < 1:
+        raise SystemExit("--steps must be >= 1")
     method, sub = resolve(args)
     cores = os.cpu_count() or 1
     workers = args.gen_workers or max(1, min(16, cores // max(1, world)))
 
-    # ---- all synthetic data first (the generator forks): headline + the two extra workloads of the default run
+    # ---- all synthetic data first (the generator forks): headline + the two extra workloads of the default --full run
     data = generate(args, method, rank, world, workers)
-    want_extra = (world == 1 and not args.no_extra and args.config == 2 and not args.stream and args.streams == 1 and
+    want_extra = (args.full and world == 1 and not args.no_extra and args.config == 2 and not args.stream and args.streams == 1 and
                   args.batch == 1024 and (args.width, args.height, args.nfeatures) == (640, 480, 1000))
     extras = []
     if want_extra:
@@ -628,7 +662,7 @@ def main():
     from relative_pose_estimation_amd import _capi
     ndev = _capi.load().rpe_device_count()
     device = local_rank % max(ndev, 1)
-    out = run_workload(args, method, sub, data, rank, world, device, args.dist_backend)
+    out = run_workload(args, method, sub, data, rank, world, device, args.dist_backend, args.dump_outputs)
     if rank == 0 and extras:
         out["extra"] = {}
         for name, a, m, s, d in extras:

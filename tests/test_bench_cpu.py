@@ -35,3 +35,48 @@ def test_algorithmic_bytes():
     assert bench.stage_bytes("pyramid", 1920, 1080, 0, 2048, 500, "SIFT") == 2 * (1920 * 1080 + 24 * px)
     with pytest.raises(KeyError):
         bench.stage_bytes("nope", 640, 480, P, 1000, 500)
+
+
+def test_plain_run_options(monkeypatch):
+    """a plain run is the headline alone; --full and --dump-outputs are opt-in; --steps below 1 is refused before any work"""
+    import subprocess
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "5", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (5, 2, False, "")
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out"
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "0"], env=env, capture_output=True, text=True)
+    assert p.returncode != 0 and "--steps must be >= 1" in p.stderr and p.stdout == ""
+
+
+def test_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs writes every pair's pose record in pair order as float64, and a fixed sample above the size limit"""
+    import numpy as np
+    import bench
+    from relative_pose_estimation_amd import sharding
+    rng = np.random.default_rng(1)
+    n = 40
+    R, t = rng.standard_normal((n, 3, 3)), rng.standard_normal((n, 3, 1))
+    inl, st, nm = rng.integers(0, 500, n), rng.integers(0, 5, n), rng.integers(0, 500, n)
+    rec = sharding.pack_records(R, t, inl, st, nm)
+    names = ("R", "t", "inliers", "n_matches", "status", "pair")
+
+    def load(d):
+        return {k: np.load(os.path.join(d, f"{k}.npy")) for k in names}
+
+    bench.dump_outputs(str(tmp_path / "all"), rec[::-1])          # gathered records need not arrive in pair order
+    got = load(tmp_path / "all")
+    assert all(v.dtype == np.float64 for v in got.values())
+    for k, v in zip(names, (R, t, inl, nm, st, np.arange(n))):
+        assert np.array_equal(got[k], v), k
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 10 * 128)
+    bench.dump_outputs(str(tmp_path / "s1"), rec)
+    bench.dump_outputs(str(tmp_path / "s2"), rec[::-1])
+    s1, s2 = load(tmp_path / "s1"), load(tmp_path / "s2")
+    assert sum(v.nbytes for v in s1.values()) <= 10 * 128
+    assert all(np.array_equal(s1[k], s2[k]) for k in names)
+    pair = s1["pair"].astype(int)
+    assert len(pair) == 10 and np.all(np.diff(pair) > 0) and np.array_equal(s1["R"], R[pair]) and np.array_equal(s1["status"], st[pair])

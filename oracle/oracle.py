@@ -249,6 +249,11 @@ def set_stl(name="libstdc++"):
     set_variant(1, STL[name])
 
 
+def set_sift_order(cv2_order=None):
+    """Keypoint order of the SIFT pose pipeline (estimate_pose_batch(method="SIFT")) under a cap; see sift_detect_and_compute."""
+    lib().orc_debug_set_sift_order(SIFT_ORDER[cv2_order])
+
+
 def estimate_pose_batch(imgs1, imgs2, K, nfeatures=4000, max_matches=500, nthreads=1, method="ORB", return_points=False):
     imgs1 = np.ascontiguousarray(imgs1, np.uint8); imgs2 = np.ascontiguousarray(imgs2, np.uint8)
     K = np.ascontiguousarray(K, np.float64)
@@ -279,14 +284,21 @@ def pose_from_points_batch(pts, n_matches, K, nthreads=1):
 SIFT_KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"), ("octave", "<i4")])
 
 
-def sift_detect_and_compute(img, nfeatures=0, seed_cap=None, cap=None, return_flags=False):
+SIFT_ORDER = {None: 0, "libstdc++": 1, "msvc": 2}
+
+
+def sift_detect_and_compute(img, nfeatures=0, seed_cap=None, cap=None, return_flags=False, cv2_order=None):
+    """cv2_order=None: the HIP path's order (retainBest's set sorted by KeyPoint_LessThan).  cv2_order="libstdc++" / "msvc":
+    cv2's own order under a cap -- sorted and deduplicated first, then std::nth_element + std::partition of that C++
+    runtime, not sorted again.  A test-infrastructure switch; without a cap both orders are the sorted one."""
     img = np.ascontiguousarray(img, np.uint8)
     H, W = img.shape
     seed_cap = seed_cap or max(16384, 4 * W * H // 16)      # the HIP path's workspace rule
     cap = cap or (nfeatures + 64 if nfeatures > 0 else 4 * seed_cap)
     kps = np.zeros(cap, SIFT_KP_DTYPE); desc = np.zeros((cap, 128), np.float32)
     flags = C.c_uint32(0)
-    n = lib().orc_sift_detect_and_compute_ex(_p(img), W, H, int(nfeatures), int(seed_cap), _p(kps), _p(desc), cap, C.byref(flags))
+    n = lib().orc_sift_detect_and_compute_order(_p(img), W, H, int(nfeatures), int(seed_cap), _p(kps), _p(desc), cap,
+                                                C.byref(flags), SIFT_ORDER[cv2_order])
     if return_flags:
         return kps[:n].copy(), desc[:n].copy(), int(flags.value)
     return kps[:n].copy(), desc[:n].copy()

@@ -389,6 +389,13 @@ static int kp_less(const sift_kp *a, const sift_kp *b)   /* KeyPoint_LessThan (k
 }
 static int kp_cmp(const void *a, const void *b) { return kp_less((const sift_kp *)a, (const sift_kp *)b) ? -1 : kp_less((const sift_kp *)b, (const sift_kp *)a) ? 1 : 0; }
 
+/* Keypoint order under a cap (test infrastructure, not a product switch).  ORC_SIFT_ORDER_SORTED (default) is the HIP
+ * path's convention: retainBest's set, then sorted by KeyPoint_LessThan.  ORC_SIFT_ORDER_CV2_* is cv2's own order:
+ * SIFT_Impl::detectAndCompute sorts and removes duplicates first (removeDuplicatedSorted), then retainBest(nfeatures)
+ * -- std::nth_element + std::partition of the named C++ runtime -- and nothing sorts again.  The set is the same. */
+static int g_sift_order = ORC_SIFT_ORDER_SORTED;
+void orc_debug_set_sift_order(int order) { g_sift_order = order; }
+
 /* nfeatures <= 0: no cap.  seed_cap: max seeds per image (raster order).  Returns count (<= cap). */
 int orc_sift_detect_and_compute(const uint8_t *img, int W, int H, int nfeatures, int seed_cap,
                                 orc_sift_keypoint *kps, float *desc, int cap)
@@ -398,6 +405,12 @@ int orc_sift_detect_and_compute(const uint8_t *img, int W, int H, int nfeatures,
 
 int orc_sift_detect_and_compute_ex(const uint8_t *img, int W, int H, int nfeatures, int seed_cap,
                                    orc_sift_keypoint *kps, float *desc, int cap, uint32_t *flags)
+{
+    return orc_sift_detect_and_compute_order(img, W, H, nfeatures, seed_cap, kps, desc, cap, flags, g_sift_order);
+}
+
+int orc_sift_detect_and_compute_order(const uint8_t *img, int W, int H, int nfeatures, int seed_cap,
+                                      orc_sift_keypoint *kps, float *desc, int cap, uint32_t *flags, int order)
 {
     uint32_t ovf = 0;
     sift_geo g;
@@ -456,8 +469,23 @@ int orc_sift_detect_and_compute_ex(const uint8_t *img, int W, int H, int nfeatur
                 }
         free(claimed);
     }
+    if (order != ORC_SIFT_ORDER_SORTED) {
+        /* removeDuplicatedSorted (exact duplicates were dropped above), then retainBest in the runtime's order */
+        qsort(tmp, (size_t)nk, sizeof(sift_kp), kp_cmp);
+        if (nfeatures > 0 && nk > nfeatures) {
+            ovf |= ORC_OVF_SIFT_CAP;
+            float *rs = (float *)malloc(sizeof(float) * (size_t)nk);
+            int32_t *ids = (int32_t *)malloc(sizeof(int32_t) * (size_t)nk);
+            sift_kp *kept = (sift_kp *)malloc(sizeof(sift_kp) * (size_t)nk);
+            for (int i = 0; i < nk; ++i) { rs[i] = tmp[i].response; ids[i] = i; }
+            int m = order == ORC_SIFT_ORDER_CV2_MSVC ? orc_retain_best_msvc(rs, ids, nk, nfeatures) : orc_retain_best(rs, ids, nk, nfeatures);
+            for (int i = 0; i < m; ++i) kept[i] = tmp[ids[i]];
+            memcpy(tmp, kept, sizeof(sift_kp) * (size_t)m);
+            nk = m; free(kept); free(ids); free(rs);
+        }
+    }
     /* retainBest(nfeatures): all keypoints with response >= the n-th best */
-    if (nfeatures > 0 && nk > nfeatures) {
+    else if (nfeatures > 0 && nk > nfeatures) {
         ovf |= ORC_OVF_SIFT_CAP;          /* the cap bites: the reference's SIFT_create() keeps all nk */
         float *rs = (float *)malloc(sizeof(float) * (size_t)nk);
         for (int i = 0; i < nk; ++i) rs[i] = tmp[i].response;
@@ -467,7 +495,7 @@ int orc_sift_detect_and_compute_ex(const uint8_t *img, int W, int H, int nfeatur
         for (int i = 0; i < nk; ++i) if (tmp[i].response >= th) tmp[m++] = tmp[i];
         nk = m; free(rs);
     }
-    qsort(tmp, (size_t)nk, sizeof(sift_kp), kp_cmp);
+    if (order == ORC_SIFT_ORDER_SORTED) qsort(tmp, (size_t)nk, sizeof(sift_kp), kp_cmp);
     if (nk > cap) { nk = cap; ovf |= ORC_OVF_SIFT_KEYPOINTS; }
     if (flags) *flags = ovf;
     for (int i = 0; i < nk; ++i) {

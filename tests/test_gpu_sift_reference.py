@@ -1,0 +1,122 @@
+"""The HIP SIFT kernels against the independent float64 model of cv2's SIFT (tests/sift_reference.py), one stage at a
+time, each stage fed the kernels' own upstream output (Engine.sift_debug_gauss, sift_detect_and_compute).  The same rows
+run on the CPU oracle in tests/test_sift_reference_cpu.py; tolerances and their derivations: tests/sift_stage_checks.py."""
+import numpy as np
+import pytest
+
+import sift_reference as ref
+import sift_stage_checks as chk
+
+pytestmark = pytest.mark.gpu
+
+
+def _engine(W, H, nfeatures, batch=1):
+    from relative_pose_estimation_amd import _capi
+    return _capi.Engine(W, H, max_batch=batch, nfeatures=nfeatures, max_matches=300, feature_method=_capi.FEATURE_SIFT,
+                        norm_type=_capi.NORM_L2)
+
+
+def _frames(W, H, cfg, n=1):
+    from relative_pose_estimation_amd import synthetic, geometry
+    i1, i2, _, _ = synthetic.make_batch(n, geometry.default_camera_matrix(W, H), W, H, cfg=cfg)
+    return np.concatenate([i1, i2])
+
+
+def _run(e, imgs):
+    kps, desc, cnt = e.sift_detect_and_compute(imgs)
+    H, W = imgs.shape[1:]
+    out = []
+    for n in range(len(imgs)):
+        pyr = ref.split_pyramid(e.sift_debug_gauss(n), W, H)
+        out.append((pyr, kps[n, :cnt[n]].copy(), desc[n, :cnt[n]].copy()))
+    return out
+
+
+def _all_stages(name, img, pyr, k, d, sample=None):
+    st = {"pyramid": chk.check_pyramid(img, pyr)}
+    st["keypoints"] = chk.check_keypoints(pyr, k, sample=sample)
+    st["orientation"] = chk.check_orientations(pyr, k, sample=sample)
+    st["descriptor"] = chk.check_descriptors(pyr, k, d, sample=sample)
+    print(f"{name}: {st}")
+    return st
+
+
+@pytest.mark.parametrize("W,H", [(320, 240), (211, 157), (96, 130), (400, 97)])
+def test_stages_small_frames(W, H):
+    """cfg-6 frames; at 96x130 and 400x97 the deep octaves fall below 2 * border and are skipped"""
+    imgs = _frames(W, H, 6)
+    e = _engine(W, H, 0, len(imgs))
+    for n, (pyr, k, d) in enumerate(_run(e, imgs)):
+        _all_stages(f"{W}x{H}[{n}]", imgs[n], pyr, k, d)
+    e.close()
+
+
+def test_stages_drawn_images():
+    """blobs on the border and in the corners, gradients along 0 / 360 degrees, L-corners, a blob of the last octaves,
+    a flat image (no keypoint), a saturated block (dx = dy = 0)"""
+    drawn = chk.drawn_images()
+    names = list(drawn)
+    imgs = np.stack([drawn[n] for n in names])
+    e = _engine(imgs.shape[2], imgs.shape[1], 0, len(imgs))
+    for name, img, (pyr, k, d) in zip(names, imgs, _run(e, imgs)):
+        _all_stages(name, img, pyr, k, d)
+        if name == "flat":
+            assert len(k) == 0
+        if name == "large_blob":
+            assert len(k) and np.all(ref.locate(k)[0] >= 3)
+        if name == "wrap_blobs":
+            assert np.sum(np.minimum(k["angle"], 360 - k["angle"]) < 12) >= 2
+    e.close()
+
+
+@pytest.mark.parametrize("nfeatures", [150, 300])
+def test_post_processing_small(nfeatures):
+    """the capped set equals the model's retainBest of the uncapped list; the kernels' capped order is sorted"""
+    imgs = _frames(320, 240, 6)[:1]
+    eu = _engine(320, 240, 0)
+    ku = _run(eu, imgs)[0][1]
+    eu.close()
+    ec = _engine(320, 240, nfeatures)
+    kc = _run(ec, imgs)[0][1]
+    ec.close()
+    chk.check_post(ku, ku, 0)
+    chk.check_post(ku, kc, nfeatures)
+
+
+@pytest.fixture(scope="module")
+def hd():
+    img = _frames(1920, 1080, 5)[:1]
+    e = _engine(1920, 1080, 0)
+    out = _run(e, img)[0]
+    e.close()
+    return img[0], out
+
+
+def test_stages_hd_uncapped(hd):
+    """a textured 1920x1080 frame: the large octaves go through sift_blur_fused<R> and the select path.  Levels in full,
+    keypoint fields, orientations and descriptors on ~500 sampled octave-0 keypoints (NumPy time)."""
+    img, (pyr, k, d) = hd
+    _all_stages("hd", img, pyr, k, d, sample=500)
+
+
+def test_cap_2048_hd(hd):
+    """nfeatures = 2048 on the HD frame: the same set as the model's retainBest of the uncapped list, and the keypoints,
+    orientations and descriptors of the capped run pass the model's rows too"""
+    img, (pyr_u, ku, _) = hd
+    e = _engine(1920, 1080, 2048)
+    pyr, kc, dc = _run(e, img[None])[0]
+    e.close()
+    assert len(ku) > 2048
+    chk.check_post(ku, kc, 2048)
+    print("cap 2048:", chk.check_orientations(pyr, kc, sample=600), chk.check_descriptors(pyr, kc, dc, sample=300))
+
+
+def test_marching_pyramid_hd(monkeypatch):
+    """RPE_SIFT_MARCH=1 (sift_march_kernel for the large octaves): the pyramid stage on the HD frame"""
+    img = _frames(1920, 1080, 5)[:1]
+    monkeypatch.setenv("RPE_SIFT_MARCH", "1")
+    e = _engine(1920, 1080, 0)
+    monkeypatch.delenv("RPE_SIFT_MARCH")
+    pyr, _, _ = _run(e, img)[0]
+    e.close()
+    print("march pyramid max |err|:", chk.check_pyramid(img[0], pyr))

@@ -243,16 +243,23 @@ void rpe_launch_pyramid(rpe_handle *h, int n_img)
 // Tile = 64x64 output pixels; scores are needed on 66x66, pixels on 72x72 (halo 3+1
 // rows, 4 columns => dword aligned).  ~5 KB of loads in flight per workgroup.
 //  phase 1: every dword group (4 px) of the 66x72 score area: OpenCV's pair test on the
-//           4 compass + 4 diagonal ring pixels with class bits (darker=1 / brighter=2):
-//           a 9-arc contains one pixel of every opposite pair, so
-//           (c0|c8)&(c4|c12)&(c2|c10)&(c6|c14) != 0 is necessary; survivors are appended
-//           to an LDS list with one wave-aggregated LDS atomic per wave.
-//  phase 2: list processed densely: 16 ring differences, window-9 min/max via
-//           min3/max3, score = max(A,B)-1 (0 if not a corner) into the LDS score tile.
-//  phase 3: strict 3x3 maximum on the LDS score tile, 31-px border filter
-//           (KeyPointsFilter::runByImageBorder), per-tile keypoint list to HBM.
+//           4 compass + 4 diagonal ring pixels, darker and brighter side apart:
+//           a 9-arc contains one pixel of every opposite pair, so a darker (brighter) arc needs
+//           every pair to hold a pixel below v - thr (above v + thr).  Survivors are appended
+//           to an LDS list with one wave-aggregated LDS atomic per wave: candidates with a darker
+//           arc possible from the front, brighter-only ones from the back.
+//  phase 2: the list in one contiguous slice per wave: the score of the possible side(s) only,
+//           window-9 min/max via min3/max3 on the raw ring values, score - 1 into the LDS score
+//           tile; the corners (score > thr) are compacted to the front of the wave's slice.
+//  phase 3: strict 3x3 maximum on the LDS score tile over the corners only, 31-px border
+//           filter (KeyPointsFilter::runByImageBorder), per-tile keypoint list to HBM.
 __device__ __forceinline__ int imin3(int a, int b, int c) { return min(a, min(b, c)); }
 __device__ __forceinline__ int imax3(int a, int b, int c) { return max(a, max(b, c)); }
+// one v_max3_u32 / v_min3_u32 per window of 3: left to itself the compiler shares two-input partial results between
+// neighbouring windows (max(r[k+1], r[k+2]) ...) and spends ~48 instructions on a side's windows of 3 and 9 and the
+// reduction instead of 16 + 16 + 8
+__device__ __forceinline__ int vmax3u(int a, int b, int c) { int d; asm("v_max3_u32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c)); return d; }
+__device__ __forceinline__ int vmin3u(int a, int b, int c) { int d; asm("v_min3_u32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c)); return d; }
 typedef short short2_t __attribute__((ext_vector_type(2)));
 // Bresenham circle of radius 3 (fast.cpp), compile-time offsets
 static constexpr int CIRC_DX[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1};
@@ -263,6 +270,7 @@ static constexpr int CIRC_DY[16] = {3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1, 0
 #define FAST_THREADS (FAST_TH * 4)
 #define FAST_NRP (FAST_THREADS / 18)  // rows of the 18-dword tile row that one pass of the lanes covers (14 or 7)
 #define FAST_LANES (FAST_NRP * 18)
+#define FAST_NCAND (FS_ROWS * 72)    // candidate list capacity: one entry per score-area pixel at most
 // Output: one compact list per tile of the keypoints that survive NMS and the border filter, packed
 // score << 24 | y << 12 | x (level coordinates).  A strict 3x3
 // maximum cannot have an 8-neighbour that is one too, so a 64x64 tile holds at most 32*32 = 1024 of them:
@@ -279,7 +287,7 @@ __global__ __launch_bounds__(FAST_THREADS) void fast_nms_kernel(const uint8_t *_
     __shared__ __attribute__((aligned(16))) unsigned s_in[S_IN_DW];                // pixels  y0-4 .. y0+FAST_TH+3, x0-4 .. x0+67 (sized for the phase-3 aliases too)
     __shared__ __attribute__((aligned(16))) unsigned s_sc[FS_ROWS * 18];   // scores  y0-1 .. y0+64, x0-4 .. x0+67
     unsigned *s_out = s_in;                                               // phase 3: the tile's keypoint list [1024]
-    __shared__ unsigned short s_cand[FS_ROWS * 72];
+    __shared__ unsigned short s_cand[FAST_NCAND];
     __shared__ int s_ncand, s_nout;
     const int tid = threadIdx.x, lane = tid & 63;
     const int ti = xcd_tile(blockIdx.x, ntiles);
@@ -324,9 +332,9 @@ __global__ __launch_bounds__(FAST_THREADS) void fast_nms_kernel(const uint8_t *_
     // ---- phase 1 (packed 16-bit SWAR: even / odd pixels of the dword group in one VGPR each)
     // lane -> fixed dword column c (18 per row) and rows r0, r0+14, ... : the x-validity mask is
     // computed once per tile and the candidate bits of the 5 rows are appended in one go
-    const unsigned T1 = (unsigned)(thr + 1) * 0x00010001u, T0 = (unsigned)thr * 0x00010001u;
+    const unsigned T0 = (unsigned)thr * 0x00010001u;
     const int c = tid % 18, r0 = tid / 18;
-    unsigned cand_bits = 0;
+    unsigned dark_bits = 0, brt_bits = 0;
     if (tid < FAST_LANES) {
         const int cl = max(c - 1, 0), cr = min(c + 1, 17);
         const int pxb = x0 - 4 + 4 * c;
@@ -335,9 +343,9 @@ __global__ __launch_bounds__(FAST_THREADS) void fast_nms_kernel(const uint8_t *_
         if (pxb < xlo) vmask &= 0xFu << min(xlo - pxb, 4);
         if (pxb + 3 > xhi) vmask &= 0xFu >> min(pxb + 3 - xhi, 4);
         vmask &= 0xFu;
-        // candidate flags of the 5 rows share one dword: pixel px of row it -> bit 8 px + it (the four sign bytes of a row
-        // are gathered by one v_perm and dropped into place by a shift and a v_and_or: 5 instructions per row instead of
-        // 14 for the compact 4-bit form; the x-validity mask is applied once, spread to bytes)
+        // candidate flags of the 5 rows share one dword per side: pixel px of row it -> bit 8 px + it (the four sign bytes of
+        // a row are gathered by one v_perm and dropped into place by a shift and a v_and_or: 3 instructions per row and side
+        // instead of 14 for the compact 4-bit form; the x-validity mask is applied once, spread to bytes)
         const unsigned vmask5 = ((vmask * 0x00204081u) & 0x01010101u) * 0x1Fu;
         const unsigned *pC = s_in + (r0 + 3) * 18 + c, *pL = s_in + (r0 + 3) * 18 + cl, *pR = s_in + (r0 + 3) * 18 + cr;
 #pragma unroll
@@ -352,7 +360,7 @@ __global__ __launch_bounds__(FAST_THREADS) void fast_nms_kernel(const uint8_t *_
             const unsigned upl = pL[ro - 36], upc = pC[ro - 36], upr = pR[ro - 36];
             const unsigned dnl = pL[ro + 36], dnc = pC[ro + 36], dnr = pR[ro + 36];
             const unsigned bot = pC[ro + 54], top = pC[ro - 54];
-            unsigned z[2];
+            unsigned zd[2], zb[2];
 #pragma unroll
             for (int par = 0; par < 2; ++par) {
                 // v_perm_b32 picks bytes (sh+par, sh+par+2) of {hi:lo} into the low bytes of two 16-bit lanes
@@ -375,82 +383,131 @@ __global__ __launch_bounds__(FAST_THREADS) void fast_nms_kernel(const uint8_t *_
                                                               __builtin_elementwise_max(__builtin_elementwise_min(r[4], r[5]), __builtin_elementwise_min(r[6], r[7])));
                 const short2_t hi = __builtin_elementwise_min(__builtin_elementwise_min(__builtin_elementwise_max(r[0], r[1]), __builtin_elementwise_max(r[2], r[3])),
                                                               __builtin_elementwise_min(__builtin_elementwise_max(r[4], r[5]), __builtin_elementwise_max(r[6], r[7])));
-                // darker arc possible:   ce - lo > thr  <=>  (ce - lo) - (thr+1) >= 0
+                // darker arc possible:   ce - lo > thr  <=>  (lo - ce) + thr < 0
                 // brighter arc possible: hi - ce > thr  <=>  (ce - hi) + thr < 0
-                const unsigned u = __builtin_bit_cast(unsigned, (ce - lo) - __builtin_bit_cast(short2_t, T1));
-                const unsigned q = __builtin_bit_cast(unsigned, (ce - hi) + __builtin_bit_cast(short2_t, T0));
-                z[par] = ~u | q;                                   // bit 15 / 31: candidate flag of the even / odd pixel pair
+                // bit 15 / 31: the side's flag of the even / odd pixel pair
+                zd[par] = __builtin_bit_cast(unsigned, (lo - ce) + __builtin_bit_cast(short2_t, T0));
+                zb[par] = __builtin_bit_cast(unsigned, (ce - hi) + __builtin_bit_cast(short2_t, T0));
             }
-            const unsigned x4 = __builtin_amdgcn_perm(z[1], z[0], 0x07030501u);      // bytes (px0, px1, px2, px3), flag = bit 7
-            cand_bits |= (x4 >> (7 - it)) & (0x01010101u << it);
+            const unsigned xd = __builtin_amdgcn_perm(zd[1], zd[0], 0x07030501u);    // bytes (px0, px1, px2, px3), flag = bit 7
+            const unsigned xb = __builtin_amdgcn_perm(zb[1], zb[0], 0x07030501u);
+            dark_bits |= (xd >> (7 - it)) & (0x01010101u << it);
+            brt_bits |= (xb >> (7 - it)) & (0x01010101u << it);
         }
-        cand_bits &= vmask5;
+        dark_bits &= vmask5;
+        brt_bits &= vmask5;
     }
-    {   // one append per tile: wave prefix sum of the per-lane counts, one LDS atomic per wave
-        const int n = __popc(cand_bits);
+    {   // one append per tile: wave prefix sum of the per-lane counts (front | back << 16), one LDS atomic per wave.
+        // List entry (ry << 7) | bx | side bits: 0x4000 darker arc possible, 0x8000 brighter arc possible.  Entries with
+        // the darker side go to the front (0.1 % of them have both bits), brighter-only ones to the back, so the lanes of a
+        // phase-2 round almost always share one side.  Both lists together hold at most one entry per score-area pixel.
+        const unsigned bo_bits = brt_bits & ~dark_bits;
+        const int n = __popc(dark_bits) | (__popc(bo_bits) << 16);
         const int inc = wave_inclusive_sum(n);
         const int total = __shfl(inc, 63);
         if (total) {
             int base = 0;
             if (lane == 63) base = atomicAdd(&s_ncand, total);
-            int pos = __shfl(base, 63) + inc - n;
-            unsigned bits = cand_bits;
+            const int pre = __shfl(base, 63) + inc - n;
+            // one loop per side: choosing the side per bit inside one loop cost 20 instructions per trip instead of ~10,
+            // more than the trips it saves
+            int posF = pre & 0xFFFF, posB = FAST_NCAND - 1 - (pre >> 16);
+            unsigned bits = dark_bits;
             while (bits) {
                 const int bpos = __ffs((int)bits) - 1;
                 bits &= bits - 1;
-                s_cand[pos++] = (unsigned short)(((r0 + FAST_NRP * (bpos & 7)) << 7) | (4 * c + (bpos >> 3)));
+                s_cand[posF++] = (unsigned short)(((r0 + FAST_NRP * (bpos & 7)) << 7) | (4 * c + (bpos >> 3)) | 0x4000 | (((brt_bits >> bpos) & 1u) << 15));
+            }
+            bits = bo_bits;
+            while (bits) {
+                const int bpos = __ffs((int)bits) - 1;
+                bits &= bits - 1;
+                s_cand[posB--] = (unsigned short)(((r0 + FAST_NRP * (bpos & 7)) << 7) | (4 * c + (bpos >> 3)) | 0x8000);
             }
         }
     }
     __syncthreads();
-    // ---- phase 2
+    // ---- phase 2: virtual list index j in [0, nF + nB) -> s_cand[j] (front), s_cand[j + gap] (back).  Wave wv takes the
+    // slice [jb, je) in rounds of 64 and compacts the corners of the slice to s_cand[cb ..] (cb = the slice's first
+    // physical index).  A corner's physical write index never passes the read index of the round (the gap between the
+    // lists is free), and the slices do not overlap, so no other lane's unread entry is overwritten.
     const int ncand = s_ncand;
+    const int nF = ncand & 0xFFFF, nB = ncand >> 16, nc = nF + nB, gap = FAST_NCAND - nc;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int slice = ((nc + FAST_THREADS - 1) / FAST_THREADS) * 64;
+    const int jb = min(wv * slice, nc), je = min(jb + slice, nc);
+    const int cb = jb < nF ? jb : jb + gap;
+    int ncorner = 0;
     const uint8_t *sb = (const uint8_t *)s_in;
-    for (int i = tid; i < ncand; i += FAST_THREADS) {
-        const int cc = s_cand[i];
-        const int bx = cc & 127, ry = cc >> 7;
-        const uint8_t *p = sb + (ry + 3) * 72 + bx;
-        const int v = p[0];
-        int d[16];
+    for (int j0 = jb; j0 < je; j0 += 64) {                              // wave-uniform trip count
+        const int j = j0 + lane;
+        bool corner = false;
+        int cc = 0;
+        if (j < je) {
+            cc = s_cand[j < nF ? j : j + gap];
+            const int bx = cc & 127, ry = (cc >> 7) & 127;
+            const uint8_t *p = sb + (ry + 3) * 72 + bx;
+            const int v = p[0];
+            int r[16];
 #pragma unroll
-        for (int k = 0; k < 16; ++k) d[k] = v - (int)p[CIRC_DY[k] * 72 + CIRC_DX[k]];
-        int m3[16], x3[16];
+            for (int k = 0; k < 16; ++k) r[k] = p[CIRC_DY[k] * 72 + CIRC_DX[k]];
+            // with d = v - r: the darker score A = max_k min_arc9(k) d = v - min_k max_arc9(k) r, the brighter one
+            // -Bm = -min_k max_arc9(k) d = max_k min_arc9(k) r - v; a side that phase 1 ruled out has a score <= thr
+            // (necessary condition above), so max(A, -Bm) > thr iff the possible side's score is, and then it is that score
+            int s = 0;
+            if (cc & 0x4000) {
+                int x3[16];
 #pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            m3[k] = imin3(d[k], d[(k + 1) & 15], d[(k + 2) & 15]);
-            x3[k] = imax3(d[k], d[(k + 1) & 15], d[(k + 2) & 15]);
+                for (int k = 0; k < 16; ++k) x3[k] = vmax3u(r[k], r[(k + 1) & 15], r[(k + 2) & 15]);
+                int x9[16];
+#pragma unroll
+                for (int k = 0; k < 16; ++k) x9[k] = vmax3u(x3[k], x3[(k + 3) & 15], x3[(k + 6) & 15]);
+                const int m = min(vmin3u(vmin3u(x9[0], x9[1], x9[2]), vmin3u(x9[3], x9[4], x9[5]), vmin3u(x9[6], x9[7], x9[8])),
+                                  vmin3u(vmin3u(x9[9], x9[10], x9[11]), vmin3u(x9[12], x9[13], x9[14]), x9[15]));
+                s = v - m;
+            }
+            if (cc & 0x8000) {
+                int m3[16];
+#pragma unroll
+                for (int k = 0; k < 16; ++k) m3[k] = vmin3u(r[k], r[(k + 1) & 15], r[(k + 2) & 15]);
+                int m9[16];
+#pragma unroll
+                for (int k = 0; k < 16; ++k) m9[k] = vmin3u(m3[k], m3[(k + 3) & 15], m3[(k + 6) & 15]);
+                const int m = max(vmax3u(vmax3u(m9[0], m9[1], m9[2]), vmax3u(m9[3], m9[4], m9[5]), vmax3u(m9[6], m9[7], m9[8])),
+                                  vmax3u(vmax3u(m9[9], m9[10], m9[11]), vmax3u(m9[12], m9[13], m9[14]), m9[15]));
+                s = max(s, m - v);
+            }
+            if (s > thr) {
+                ((uint8_t *)s_sc)[ry * 72 + bx] = (uint8_t)(s - 1);
+                corner = true;
+            }
         }
-        int A = -1000, Bm = 1000;
-#pragma unroll
-        for (int k = 0; k < 16; ++k) {
-            A = max(A, imin3(m3[k], m3[(k + 3) & 15], m3[(k + 6) & 15]));
-            Bm = min(Bm, imax3(x3[k], x3[(k + 3) & 15], x3[(k + 6) & 15]));
-        }
-        const int s = max(A, -Bm);
-        if (s > thr) ((uint8_t *)s_sc)[ry * 72 + bx] = (uint8_t)(s - 1);
+        const unsigned long long km = __ballot(corner);
+        if (corner) s_cand[cb + ncorner + __popcll(km & ((1ull << lane) - 1ull))] = (unsigned short)cc;
+        ncorner += __popcll(km);
     }
     __syncthreads();
-    // ---- phase 3: NMS + border filter over the candidate list (only pixels that went through
-    // phase 2 can hold a score); survivors are appended to the tile's list, one LDS atomic per wave and round.
+    // ---- phase 3: NMS + border filter over the wave's own corners (only a corner can be a maximum: a pixel without a
+    // score holds 0); survivors are appended to the tile's list, one LDS atomic per wave and round.
     // The pixel tile is dead now (the barrier above ended phase 2): its LDS holds the list.
     const uint8_t *sc = (const uint8_t *)s_sc;
-    for (int i0 = 0; i0 < ncand; i0 += FAST_THREADS) {                  // block-uniform trip count: the ballot sees whole waves
-        const int i = i0 + tid;
+    for (int i0 = 0; i0 < ncorner; i0 += 64) {                          // wave-uniform trip count: the ballot sees whole waves
+        const int i = i0 + lane;
         bool keep = false;
         unsigned ent = 0;
-        if (i < ncand) {
-            const int cc = s_cand[i];
-            const int bx = cc & 127, ry = cc >> 7;
+        if (i < ncorner) {
+            const int cc = s_cand[cb + i];
+            const int bx = cc & 127, ry = (cc >> 7) & 127;
             const int px = x0 - 4 + bx, py = y0 - 1 + ry;
             // branch-free: the eight neighbour reads go out together (as a short-circuit chain they were nine dependent LDS
-            // round trips with an exec-mask save / restore each); reads of halo candidates past the score tile land in
+            // round trips with an exec-mask save / restore each); reads of halo corners past the score tile land in
             // other LDS arrays of this kernel and are discarded by `inside`
             const bool inside = (unsigned)(bx - 4) < 64u & (unsigned)(ry - 1) < (unsigned)FAST_TH &                 // halo pixels are not outputs
                                 (unsigned)(px - RPE_EDGE) < (unsigned)(w - 2 * RPE_EDGE) & (unsigned)(py - RPE_EDGE) < (unsigned)(hgt - 2 * RPE_EDGE);
             const uint8_t *q = sc + ry * 72 + bx;
             const int v = q[0];
             const int nmax = imax3(imax3(q[-1], q[1], q[-73]), imax3(q[-72], q[-71], q[71]), max((int)q[72], (int)q[73]));
-            if (inside & (v != 0) & (v > nmax)) {
+            if (inside & (v > nmax)) {
                 keep = true;
                 ent = ((unsigned)v << 24) | ((unsigned)py << 12) | (unsigned)px;
             }

@@ -213,6 +213,15 @@ int rpe_lsd_detect(const uint8_t *h_gray, int width, int height, float *h_lines,
  * pose_estimator.py:606-607,628-629): pts[B*max_matches*2] f32 */
 int rpe_fetch_matched_points(rpe_handle *h, int B, float *pts1, float *pts2);
 
+/* Per-match results of the last rpe_estimate_batch / rpe_estimate_batch_device / rpe_enqueue_batch_device /
+ * rpe_estimate_stream / rpe_enqueue_stream_device call, pair p at offset p*max_matches (points: *3).
+ * ransac_mask: findEssentialMat's inlier mask (pose_estimator.py:522-527); pose_mask: recoverPose's cheirality
+ * mask of the returned (R, t), distanceThresh 50 (:533), sum == inliers[p]; points: triangulated point of every
+ * match, camera-1 frame, |t| = 1 scale.  Zero past n_matches[p] and for pairs whose status is not OK.
+ * Any output may be NULL.  RPE_ERR_INVALID after a chunked host batch, after a stage-API call, or for
+ * B > pairs of the last batch. */
+int rpe_fetch_structure(rpe_handle *h, int B, uint8_t *ransac_mask, uint8_t *pose_mask, double *points);
+
 /* ---------------------------------------------------------- stage entry */
 /* replaces extractor.detectAndCompute(image, None) (pose_estimator.py:108)
  * for n_images images (n_images <= 2*max_batch).  kps[n_images*cap],

@@ -31,7 +31,7 @@ EXPORTS = [
     "rpe_default_config", "rpe_create", "rpe_destroy", "rpe_last_error", "rpe_device_count",
     "rpe_keypoint_capacity", "rpe_device_malloc", "rpe_device_free", "rpe_memcpy_h2d", "rpe_memcpy_d2h",
     "rpe_synchronize", "rpe_host_alloc", "rpe_host_free", "rpe_host_register", "rpe_host_unregister", "rpe_estimate_batch", "rpe_estimate_batch_device", "rpe_enqueue_batch_device",
-    "rpe_fetch_results", "rpe_fetch_matched_points", "rpe_orb_detect_and_compute", "rpe_orb_debug_fetch",
+    "rpe_fetch_results", "rpe_fetch_matched_points", "rpe_fetch_structure", "rpe_orb_detect_and_compute", "rpe_orb_debug_fetch",
     "rpe_orb_pyramid_pixels", "rpe_match_hamming", "rpe_find_essential", "rpe_recover_pose",
     "rpe_set_profiling", "rpe_get_stage_ms", "rpe_stage_name",
     "rpe_sift_detect_and_compute", "rpe_sift_debug_gauss", "rpe_match_l2",
@@ -96,6 +96,7 @@ def load():
     lib.rpe_enqueue_batch_device.argtypes = [vp, vp, vp, C.c_int, vp]; lib.rpe_enqueue_batch_device.restype = C.c_int
     lib.rpe_fetch_results.argtypes = [vp, C.c_int, vp, vp, i32p, i32p, i32p]; lib.rpe_fetch_results.restype = C.c_int
     lib.rpe_fetch_matched_points.argtypes = [vp, C.c_int, vp, vp]; lib.rpe_fetch_matched_points.restype = C.c_int
+    lib.rpe_fetch_structure.argtypes = [vp, C.c_int, vp, vp, vp]; lib.rpe_fetch_structure.restype = C.c_int
     lib.rpe_orb_detect_and_compute.argtypes = [vp, vp, C.c_int, vp, vp, i32p]
     lib.rpe_orb_detect_and_compute.restype = C.c_int
     lib.rpe_orb_debug_fetch.argtypes = [vp, C.c_int, C.c_int, vp]; lib.rpe_orb_debug_fetch.restype = C.c_int
@@ -306,6 +307,17 @@ class Engine:
         p1 = np.zeros((B, self.max_matches, 2), np.float32); p2 = np.zeros_like(p1)
         self._chk(self.lib.rpe_fetch_matched_points(self.h, B, _p(p1), _p(p2)))
         return p1, p2
+
+    def fetch_structure(self, B):
+        """Per-match results of the last batch / stream (rpe_fetch_structure): (ransac_mask bool[B, mm],
+        pose_mask bool[B, mm], points f64[B, mm, 3]).  ransac_mask is findEssentialMat's inlier mask, pose_mask
+        recoverPose's cheirality mask of the returned pose (sums to the inlier count), points the triangulated point
+        of every match in the camera-1 frame on the |t| = 1 scale.  Zero past each pair's match count and for pairs
+        whose status is not OK."""
+        mm = self.max_matches
+        rm = np.zeros((B, mm), np.uint8); pm = np.zeros((B, mm), np.uint8); pts = np.zeros((B, mm, 3))
+        self._chk(self.lib.rpe_fetch_structure(self.h, B, _p(rm), _p(pm), _p(pts)))
+        return rm.astype(bool), pm.astype(bool), pts
 
     # ---- stage API
     def orb_detect_and_compute(self, imgs):

@@ -849,18 +849,21 @@ __global__ __launch_bounds__(256) void ransac_update_kernel(RpeRansacState *__re
 }
 
 // ------------------------------------------------------------------- mask
+// status (may be null): pairs of a batch whose status is not RPE_PAIR_OK get an all-zero mask
 __global__ __launch_bounds__(256) void ransac_mask_kernel(const double2 *__restrict__ n1, const double2 *__restrict__ n2,
                                                            const RpeRansacState *__restrict__ st, const double *__restrict__ K,
-                                                           double threshold, uint8_t *__restrict__ mask, int max_matches)
+                                                           double threshold, const int *__restrict__ status,
+                                                           uint8_t *__restrict__ mask, int max_matches)
 {
     const int pair = blockIdx.x, tid = threadIdx.x;
     const RpeRansacState s = st[pair];
     const double fx = K[0], fy = K[4];
     const double thr = threshold / ((fx + fy) / 2);
     const float thr2 = (float)(thr * thr);
+    const bool ok = !status || status[pair] == RPE_PAIR_OK;
     for (int i = tid; i < max_matches; i += 256) {
         uint8_t v = 0;
-        if (i < s.M && s.found) {
+        if (ok && i < s.M && s.found) {
             if (s.M == 5) v = 1;
             else {
                 double2 a = n1[(long long)pair * max_matches + i], b = n2[(long long)pair * max_matches + i];
@@ -919,7 +922,7 @@ void rpe_launch_ransac(rpe_handle *h, int B, bool want_mask)
     }
     if (want_mask)
         hipLaunchKernelGGL(ransac_mask_kernel, dim3(B), dim3(256), 0, h->stream,
-                           n1, n2, h->d_rstate, h->d_K, h->cfg.ransac_threshold, h->d_mask, mm);
+                           n1, n2, h->d_rstate, h->d_K, h->cfg.ransac_threshold, (const int *)nullptr, h->d_mask, mm);
 }
 
 // ------------------------------------------------------------ recoverPose
@@ -1005,8 +1008,10 @@ __device__ static void decompose_essential(const double *E, double *R1, double *
     t[0] = U[2]; t[1] = U[5]; t[2] = U[8];
 }
 
-// triangulate.cpp DLT with P0 = [I|0], P = [R|t]; cheirality test of recoverPose (dist 50)
-__device__ static int cheirality_one(const double *R, const double *t, double x1, double y1, double x2, double y2)
+// triangulate.cpp DLT with P0 = [I|0], P = [R|t]; cheirality test of recoverPose (dist 50).  P receives the point
+// (X/W, Y/W, Z/W) in the camera-1 frame, whatever the test says.  recover_pose_kernel and pose_structure_kernel both call
+// this one helper, so the structure's mask sums to the inlier count exactly.
+__device__ static int triangulate_one(const double *R, const double *t, double x1, double y1, double x2, double y2, double *P)
 {
     double A[16], V[16];
     A[0] = -1.; A[1] = 0.;  A[2] = x1; A[3] = 0.;
@@ -1027,6 +1032,7 @@ __device__ static int cheirality_one(const double *R, const double *t, double x1
     }
     int good = (Z * W) > 0.;
     X /= W; Y /= W; Z /= W;
+    P[0] = X; P[1] = Y; P[2] = Z;
     good = good && (Z < 50.);
     double z2 = ((R[6] * X + R[7] * Y) + R[8] * Z) + t[2];
     good = good && (z2 > 0.) && (z2 < 50.);
@@ -1067,10 +1073,11 @@ __global__ __launch_bounds__(256) void recover_pose_kernel(const double *__restr
         float2 a = pts1[(long long)pair * max_matches + i], b = pts2[(long long)pair * max_matches + i];
         double x1 = ((double)a.x - cx) / fx, y1 = ((double)a.y - cy) / fy;
         double x2 = ((double)b.x - cx) / fx, y2 = ((double)b.y - cy) / fy;
-        g1 += cheirality_one(R1, tt, x1, y1, x2, y2);
-        g2 += cheirality_one(R2, tt, x1, y1, x2, y2);
-        g3 += cheirality_one(R1, tn, x1, y1, x2, y2);
-        g4 += cheirality_one(R2, tn, x1, y1, x2, y2);
+        double P[3];
+        g1 += triangulate_one(R1, tt, x1, y1, x2, y2, P);
+        g2 += triangulate_one(R2, tt, x1, y1, x2, y2, P);
+        g3 += triangulate_one(R1, tn, x1, y1, x2, y2, P);
+        g4 += triangulate_one(R2, tn, x1, y1, x2, y2, P);
     }
     g1 = wave_sum(g1); g2 = wave_sum(g2); g3 = wave_sum(g3); g4 = wave_sum(g4);
     if ((tid & 63) == 0) { atomicAdd(&s_g[0], g1); atomicAdd(&s_g[1], g2); atomicAdd(&s_g[2], g3); atomicAdd(&s_g[3], g4); }
@@ -1087,6 +1094,49 @@ __global__ __launch_bounds__(256) void recover_pose_kernel(const double *__restr
         inliers[pair] = g;
         if (status) status[pair] = RPE_PAIR_OK;
     }
+}
+
+// Per-match results of the pose recover_pose_kernel returned (recoverPose's mask and triangulatedPoints, distanceThresh
+// 50): one block per pair, one candidate per match.  Entries past the pair's match count and every entry of a pair whose
+// status is not OK are zero.
+__global__ __launch_bounds__(256) void pose_structure_kernel(const float2 *__restrict__ pts1, const float2 *__restrict__ pts2,
+                                                              const int *__restrict__ m_n, const int *__restrict__ status,
+                                                              const double *__restrict__ K, const double *__restrict__ Rall,
+                                                              const double *__restrict__ tall, uint8_t *__restrict__ pose_mask,
+                                                              double *__restrict__ points, int max_matches)
+{
+    const int pair = blockIdx.x, tid = threadIdx.x;
+    const int M = status[pair] == RPE_PAIR_OK ? min(m_n[pair], max_matches) : 0;
+    double R[9], t[3];
+#pragma unroll
+    for (int e = 0; e < 9; ++e) R[e] = Rall[pair * 9 + e];
+#pragma unroll
+    for (int e = 0; e < 3; ++e) t[e] = tall[pair * 3 + e];
+    const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
+    for (int i = tid; i < max_matches; i += 256) {
+        const long long o = (long long)pair * max_matches + i;
+        double P[3] = {0., 0., 0.};
+        int g = 0;
+        if (i < M) {
+            float2 a = pts1[o], b = pts2[o];
+            double x1 = ((double)a.x - cx) / fx, y1 = ((double)a.y - cy) / fy;
+            double x2 = ((double)b.x - cx) / fx, y2 = ((double)b.y - cy) / fy;
+            g = triangulate_one(R, t, x1, y1, x2, y2, P);
+        }
+        pose_mask[o] = (uint8_t)g;
+        points[o * 3] = P[0]; points[o * 3 + 1] = P[1]; points[o * 3 + 2] = P[2];
+    }
+}
+
+// Only rpe_fetch_structure launches these, after a batch: d_n1 / d_n2 / d_rstate still hold the batch's normalised points
+// and RANSAC state, d_R / d_t / d_status its results.
+void rpe_launch_structure(rpe_handle *h, int B)
+{
+    const int mm = h->cfg.max_matches;
+    hipLaunchKernelGGL(ransac_mask_kernel, dim3(B), dim3(256), 0, h->stream,
+                       h->d_n1, h->d_n2, h->d_rstate, h->d_K, h->cfg.ransac_threshold, (const int *)h->d_status, h->d_mask, mm);
+    hipLaunchKernelGGL(pose_structure_kernel, dim3(B), dim3(256), 0, h->stream,
+                       h->d_pts1, h->d_pts2, h->d_m_n, h->d_status, h->d_K, h->d_R, h->d_t, h->d_pose_mask, h->d_points, mm);
 }
 
 void rpe_launch_pose(rpe_handle *h, int B, bool fused)

@@ -399,7 +399,7 @@ extern "C" void rpe_destroy(rpe_handle *h)
                     h->d_hist, h->d_cand_xy, h->d_cand_resp, h->d_cand_count, h->d_kp_xy, h->d_kp_resp, h->d_kp_angle,
                     h->d_kp_pt, h->d_kp_cs, h->d_kp_count, h->d_desc, h->d_m_q, h->d_m_t, h->d_m_d, h->d_resblk, h->d_pts1, h->d_pts2,
                     h->d_subsets, h->d_nit_denom, h->d_nit_round, h->d_rstate, h->d_n1, h->d_n2, h->d_found, h->d_models, h->d_hyp, h->d_counts,
-                    h->d_nmodels, h->d_mask, h->d_E, h->d_K, h->d_m_best, h->d_m_best2, h->d_m_norm, h->d_hm_best, h->d_hm_row, h->d_ovf, h->d_corner, h->d_corner_count, h->d_kp_lvl_count};
+                    h->d_nmodels, h->d_mask, h->d_pose_mask, h->d_points, h->d_E, h->d_K, h->d_m_best, h->d_m_best2, h->d_m_norm, h->d_hm_best, h->d_hm_row, h->d_ovf, h->d_corner, h->d_corner_count, h->d_kp_lvl_count};
     for (void *p : ptrs) if (p) hipFree(p);
     if (h->h_resblk) hipHostFree(h->h_resblk);
     for (void *p : h->user_allocs) hipFree(p);
@@ -551,6 +551,7 @@ static int run_pairs(rpe_handle *h, const uint8_t *d_a, const uint8_t *d_b, int 
     h->img2_base = img2_base;
     h->last_pairs = pairs; h->last_img2_base = img2_base;
     h->last_chunked = false;
+    h->structure_valid = false;
     int rc;
     if (h->cfg.feature_method == RPE_FEATURE_SIFT) {
         if ((rc = rpe_sift_run(h, d_a, d_b, na, nb)) != RPE_OK) return rc;             // records PYRAMID .. DESCRIBE
@@ -566,6 +567,7 @@ static int run_pairs(rpe_handle *h, const uint8_t *d_a, const uint8_t *d_b, int 
     rpe_launch_pose(h, pairs, true);
     if (h->profiling) { hipEventRecord(h->ev[RPE_STAGE_COUNT], h->stream); h->ev_valid = true; }
     HIPCHK(h, hipGetLastError());
+    h->structure_valid = true;
     return RPE_OK;
 }
 
@@ -585,7 +587,7 @@ extern "C" int rpe_enqueue_batch_device(rpe_handle *h, const uint8_t *d_imgs1, c
         return run_pairs(h, d_imgs1, d_imgs2, B, B, B, B);
     for (auto &g : h->graphs)
         if (g.a == d_imgs1 && g.b == d_imgs2 && g.B == B) {
-            h->last_pairs = B; h->last_img2_base = B; h->last_chunked = false;
+            h->last_pairs = B; h->last_img2_base = B; h->last_chunked = false; h->structure_valid = true;
             h->lay.in_na = B; h->level0_slots = 2 * B;
             const bool direct = h->lay.lv[0].pitch == h->cfg.width && (((uintptr_t)d_imgs1 | (uintptr_t)d_imgs2) & 15) == 0;
             h->lay.in_a = direct ? d_imgs1 : nullptr; h->lay.in_b = direct ? d_imgs2 : nullptr;
@@ -820,6 +822,7 @@ extern "C" int rpe_estimate_batch(rpe_handle *h, const uint8_t *h_imgs1, const u
     h->ovf_pairs.assign((size_t)B, 0u);
     for (int p2 = 0; p2 < B; ++p2) h->ovf_pairs[(size_t)p2] = ov[(size_t)p2] | ov[MB + (size_t)p2];
     h->last_chunked = true;
+    h->structure_valid = false;
     return RPE_OK;
 }
 
@@ -834,6 +837,25 @@ extern "C" int rpe_fetch_matched_points(rpe_handle *h, int B, float *pts1, float
     return RPE_OK;
 }
 
+extern "C" int rpe_fetch_structure(rpe_handle *h, int B, uint8_t *ransac_mask, uint8_t *pose_mask, double *points)
+{
+    if (!h || B < 1 || B > h->cfg.max_batch) return RPE_ERR_INVALID;
+    if (h->last_chunked) { h->err = "rpe_fetch_structure: the last host batch ran in chunks: per-match results are kept for unchunked and device-resident batches only"; return RPE_ERR_INVALID; }
+    if (!h->structure_valid) { h->err = "rpe_fetch_structure: no batch or stream since the last stage-API call (it overwrote the per-match buffers)"; return RPE_ERR_INVALID; }
+    if (B > h->last_pairs) { h->err = "rpe_fetch_structure: more pairs than the last batch had"; return RPE_ERR_INVALID; }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const size_t cap = (size_t)h->cfg.max_batch * h->cfg.max_matches, n = (size_t)B * h->cfg.max_matches;
+    if (!h->d_pose_mask) HIPCHK(h, hipMalloc((void **)&h->d_pose_mask, cap));
+    if (!h->d_points) HIPCHK(h, hipMalloc((void **)&h->d_points, cap * 3 * sizeof(double)));
+    rpe_launch_structure(h, B);
+    HIPCHK(h, hipGetLastError());
+    if (ransac_mask) HIPCHK(h, hipMemcpyAsync(ransac_mask, h->d_mask, n, hipMemcpyDeviceToHost, h->stream));
+    if (pose_mask) HIPCHK(h, hipMemcpyAsync(pose_mask, h->d_pose_mask, n, hipMemcpyDeviceToHost, h->stream));
+    if (points) HIPCHK(h, hipMemcpyAsync(points, h->d_points, n * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return RPE_OK;
+}
+
 // ---------------------------------------------------------------- stage API
 extern "C" int rpe_orb_detect_and_compute(rpe_handle *h, const uint8_t *h_imgs, int n_images,
                                           rpe_keypoint *kps, uint8_t *desc, int32_t *counts)
@@ -842,6 +864,7 @@ extern "C" int rpe_orb_detect_and_compute(rpe_handle *h, const uint8_t *h_imgs, 
     if (h->cfg.feature_method != RPE_FEATURE_ORB) { h->err = "handle was not created for ORB"; return RPE_ERR_INVALID; }
     if (n_images > h->n_img_cap) { h->err = "n_images exceeds 2*max_batch"; return RPE_ERR_CAPACITY; }
     HIPCHK(h, hipSetDevice(h->cfg.device));
+    h->structure_valid = false;                 // overwrites buffers rpe_fetch_structure reads
     const size_t img = (size_t)h->cfg.width * h->cfg.height;
     const int na = n_images < h->cfg.max_batch ? n_images : h->cfg.max_batch, nb = n_images - na;
     HIPCHK(h, hipMemcpyAsync(h->d_stage1, h_imgs, img * na, hipMemcpyHostToDevice, h->stream));
@@ -935,6 +958,7 @@ extern "C" int rpe_match_hamming(rpe_handle *h, const uint8_t *h_desc1, const in
     if (!h || !h_desc1 || !h_desc2 || !n1 || !n2 || B < 1) return RPE_ERR_INVALID;
     if (B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return RPE_ERR_CAPACITY; }
     HIPCHK(h, hipSetDevice(h->cfg.device));
+    h->structure_valid = false;                 // overwrites buffers rpe_fetch_structure reads
     const size_t per = (size_t)h->lay.kcap * 32, mm = h->cfg.max_matches;
     for (int i = 0; i < B; ++i) if (n1[i] < 0 || n2[i] < 0 || n1[i] > h->lay.kcap || n2[i] > h->lay.kcap) {
         h->err = "descriptor count exceeds keypoint capacity"; return RPE_ERR_INVALID;
@@ -969,6 +993,7 @@ extern "C" int rpe_find_essential(rpe_handle *h, const float *h_pts1, const floa
     if (!h || !h_pts1 || !h_pts2 || !m || !K || B < 1) return RPE_ERR_INVALID;
     if (B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return RPE_ERR_CAPACITY; }
     HIPCHK(h, hipSetDevice(h->cfg.device));
+    h->structure_valid = false;                 // overwrites buffers rpe_fetch_structure reads
     int rc = upload_points(h, h_pts1, h_pts2, m, B);
     if (rc) return rc;
     if ((rc = set_K(h, K)) != RPE_OK) return rc;
@@ -993,6 +1018,7 @@ extern "C" int rpe_recover_pose(rpe_handle *h, const double *h_E, const float *h
     if (!h || !h_E || !h_pts1 || !h_pts2 || !m || !K || B < 1) return RPE_ERR_INVALID;
     if (B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return RPE_ERR_CAPACITY; }
     HIPCHK(h, hipSetDevice(h->cfg.device));
+    h->structure_valid = false;                 // overwrites buffers rpe_fetch_structure reads
     int rc = upload_points(h, h_pts1, h_pts2, m, B);
     if (rc) return rc;
     if ((rc = set_K(h, K)) != RPE_OK) return rc;
@@ -1171,6 +1197,7 @@ extern "C" int rpe_sift_detect_and_compute(rpe_handle *h, const uint8_t *h_imgs,
     if (h->cfg.feature_method != RPE_FEATURE_SIFT) { h->err = "handle was not created for SIFT"; return RPE_ERR_INVALID; }
     if (n_images > h->n_img_cap) { h->err = "n_images exceeds 2*max_batch"; return RPE_ERR_CAPACITY; }
     HIPCHK(h, hipSetDevice(h->cfg.device));
+    h->structure_valid = false;                 // overwrites buffers rpe_fetch_structure reads
     const size_t img = (size_t)h->cfg.width * h->cfg.height;
     const int na = n_images < h->cfg.max_batch ? n_images : h->cfg.max_batch, nb = n_images - na;
     HIPCHK(h, hipMemcpyAsync(h->d_stage1, h_imgs, img * na, hipMemcpyHostToDevice, h->stream));
@@ -1214,6 +1241,7 @@ extern "C" int rpe_match_l2(rpe_handle *h, const float *h_desc1, const int32_t *
     if (h->cfg.norm_type != RPE_NORM_L2) { h->err = "handle was not created for NORM_L2"; return RPE_ERR_INVALID; }
     if (B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return RPE_ERR_CAPACITY; }
     HIPCHK(h, hipSetDevice(h->cfg.device));
+    h->structure_valid = false;                 // overwrites buffers rpe_fetch_structure reads
     const size_t dim = (size_t)h->desc_bytes;               // 128 (SIFT) or 32 (ORB descriptors under NORM_L2)
     const size_t per = (size_t)h->lay.kcap * dim, mm = h->cfg.max_matches;
     std::vector<uint8_t> u(2 * per * B, 0);

@@ -189,6 +189,9 @@ struct rpe_handle {
     int *d_nmodels = nullptr;             // [pair][MAXCHUNK]
     int *d_counts = nullptr;              // [pair][MAXCHUNK][10] inlier counts of the current chunk
     uint8_t *d_mask = nullptr;            // [pair][max_matches]
+    uint8_t *d_pose_mask = nullptr;       // [pair][max_matches] rpe_fetch_structure only (created on first use)
+    double *d_points = nullptr;           // [pair][max_matches][3] rpe_fetch_structure only (created on first use)
+    bool structure_valid = false;         // d_pts*, d_n*, d_rstate, d_R / d_t still describe the last batch / stream (run_pairs)
     // results
     double *d_R = nullptr, *d_t = nullptr, *d_E = nullptr;
     int *d_inliers = nullptr, *d_status = nullptr;
@@ -224,6 +227,7 @@ int rpe_sift_fetch_gauss(rpe_handle *h, int index, float *out);
 long long rpe_sift_gauss_floats(rpe_handle *h);
 void rpe_launch_ransac(rpe_handle *h, int B, bool want_mask);
 void rpe_launch_pose(rpe_handle *h, int B, bool set_status);
+void rpe_launch_structure(rpe_handle *h, int B);
 
 // per-stage hipEvents on the handle's stream (rpe_set_profiling / rpe_get_stage_ms)
 #define MARK(h, stage) do { if ((h)->profiling) hipEventRecord((h)->ev[stage], (h)->stream); } while (0)

@@ -4,7 +4,8 @@ Mirrors reference src/core/pose_estimator.py: same constructor signature and
 defaults (:19-32), estimate(img1, img2, R_prev=None) -> (R, t) (:487-569),
 estimate_with_debug(...) -> dict with the reference's keys (:571-688, dict
 :624-633), same exception types and messages (:96, :129, :508-509, :514-515,
-:529-530).  Added: estimate_batch() for many pairs per call.
+:529-530).  Added: estimate_batch() for many pairs per call; estimate_with_structure() / last_structure() for the
+per-match inlier masks and triangulated points.
 
 Scope: the feature -> match -> essential -> pose path on the GPU: ORB or SIFT features, Hamming or L2 matcher
 (every combination cv2 can run: ORB + Hamming, ORB + L2, SIFT + L2; SIFT + Hamming constructs, as in the reference,
@@ -145,6 +146,21 @@ class PoseEstimator:
         where a fixed-size GPU workspace truncated a list cv2 would have kept whole (status stays OK)."""
         return self._last_engine.fetch_overflow(self._last_pairs)
 
+    def last_structure(self):
+        """Per-match results of the pairs of the last estimate_batch / estimate_sequence call: one dict per pair with
+        arrays trimmed to the pair's match count -- 'ransac_mask' (n,) bool, findEssentialMat's inlier mask;
+        'pose_mask' (n,) bool, recoverPose's cheirality mask of the returned pose (its sum is the pair's inlier count);
+        'points3d' (n, 3), the triangulated point of every match in the camera-1 frame on the |t| = 1 scale.  All zero
+        for pairs whose status is not OK.  Raises RpeError after a chunked host batch, which keeps no per-match
+        results."""
+        eng, B = self._last_engine, self._last_pairs
+        rm, pm, pts = eng.fetch_structure(B)
+        out = []
+        for p in range(B):
+            n = int(self._last_n_matches[p])
+            out.append({'ransac_mask': rm[p, :n].copy(), 'pose_mask': pm[p, :n].copy(), 'points3d': pts[p, :n].copy()})
+        return out
+
     def estimate_sequence(self, frames):
         """Relative poses of consecutive frames (frame i -> i+1): the pair loop of the reference's
         BatchProcessor.process_sequence (batch_processor.py:71-109) with features extracted once
@@ -200,6 +216,34 @@ class PoseEstimator:
                 info['R'] = R_rel
                 info['vp_used'] = True
         return info
+
+    def estimate_with_structure(self, img1, img2):
+        """estimate_with_debug's pose, matches and inlier count plus the per-match results the pose rests on:
+        'ransac_mask' (n,) bool = findEssentialMat's inlier mask (pose_estimator.py:522-527), 'pose_mask' (n,) bool =
+        recoverPose's cheirality mask (:533, distanceThresh 50; its sum is 'inliers') and 'points3d' (n, 3) =
+        recoverPose's triangulatedPoints dehomogenised: the point of every match in the camera-1 frame, |t| = 1 scale
+        (points behind a camera included).  Raises what estimate raises.  VP refinement is never applied: the
+        structure belongs to the five-point pose, and a refined R would not be the pose the masks and points
+        describe."""
+        img1 = self._gray(img1); img2 = self._gray(img2)
+        eng = self._engine(img1.shape[0], img1.shape[1], 1)
+        R, t, inl, nm, st = eng.estimate_batch(img1[None], img2[None], self.K)
+        self._last_n_matches, self._last_engine, self._last_pairs = nm, eng, 1
+        self._raise_for(int(st[0]), int(nm[0]))
+        p1, p2 = eng.fetch_matched_points(1)
+        rm, pm, pts = eng.fetch_structure(1)
+        n = int(nm[0])
+        return {
+            'R': R[0],
+            't': t[0],
+            'num_matches': n,
+            'pts1': p1[0, :n].copy(),
+            'pts2': p2[0, :n].copy(),
+            'inliers': int(inl[0]),
+            'ransac_mask': rm[0, :n].copy(),
+            'pose_mask': pm[0, :n].copy(),
+            'points3d': pts[0, :n].copy(),
+        }
 
     def close(self):
         for e in self._engines.values():

@@ -222,6 +222,28 @@ int rpe_fetch_matched_points(rpe_handle *h, int B, float *pts1, float *pts2);
  * B > pairs of the last batch. */
 int rpe_fetch_structure(rpe_handle *h, int B, uint8_t *ransac_mask, uint8_t *pose_mask, double *points);
 
+/* per-pair outcome of a refinement (info[4 * p]) */
+enum {
+    RPE_REFINE_OK = 0,        /* refined pose returned */
+    RPE_REFINE_SKIPPED = 1,   /* pair status not OK, or fewer than 6 RANSAC inliers: input pose returned */
+    RPE_REFINE_REJECTED = 2   /* refined pose lost cheirality inliers or was not finite: input pose returned */
+};
+
+/* Non-linear refinement of the poses of the last batch / stream (same validity rules as rpe_fetch_structure):
+ * Levenberg-Marquardt on the Sampson error of E = [t]x R over findEssentialMat's inliers, starting from
+ * recoverPose's (R, t); 5 parameters (rotation increment, step of t on the unit sphere), at most max_iters
+ * (1 ... 100) iterations, the cost never increases.  NOT in the reference.  Does not modify the batch's own
+ * results: rpe_fetch_results / rpe_fetch_structure / rpe_gather_poses afterwards still return the unrefined pose.
+ * Bit-deterministic run to run like every other call (no floating-point atomics).
+ * Outputs (host, any may be NULL): R[B*9], t[B*3], inliers[B] (cheirality count of the returned pose),
+ * info[B*4] = {RPE_REFINE_* code, iterations run, residuals used, accepted steps},
+ * rms[B*2] = {before, after} root-mean-square Sampson distance in pixels (the scale of
+ * rpe_config.ransac_threshold) of the input and of the returned pose over the residuals used.
+ * RPE_ERR_INVALID after a chunked host batch, after a stage-API call, for B > pairs of the last batch and for
+ * max_iters outside 1 ... 100. */
+int rpe_refine_poses(rpe_handle *h, int B, int max_iters, double *R, double *t, int32_t *inliers,
+                     int32_t *info, double *rms);
+
 /* ---------------------------------------------------------- stage entry */
 /* replaces extractor.detectAndCompute(image, None) (pose_estimator.py:108)
  * for n_images images (n_images <= 2*max_batch).  kps[n_images*cap],
@@ -270,6 +292,14 @@ int rpe_find_essential(rpe_handle *h, const float *h_pts1, const float *h_pts2, 
 int rpe_recover_pose(rpe_handle *h, const double *h_E, const float *h_pts1, const float *h_pts2,
                      const int32_t *m, int B, const double K[9],
                      double *R, double *t, int32_t *inliers);
+
+/* stage form of rpe_refine_poses, for callers that hold their own matches: pts as in rpe_recover_pose,
+ * mask[B*max_matches] (non-zero = use) selects the residuals, (R0[B*9], t0[B*3], |t0| = 1) is the start; inliers
+ * counts the cheirality inliers of the returned pose over all m[p] matches.  Overwrites the per-match buffers like
+ * every stage call (rpe_fetch_structure / rpe_refine_poses are refused afterwards). */
+int rpe_refine_pose_points(rpe_handle *h, const double *h_R0, const double *h_t0, const float *h_pts1,
+                           const float *h_pts2, const uint8_t *h_mask, const int32_t *m, int B, const double K[9],
+                           int max_iters, double *R, double *t, int32_t *inliers, int32_t *info, double *rms);
 
 /* ------------------------------------------------------------ profiling */
 /* Per-stage device time of the last hot-path call, from hipEvents recorded

@@ -26,12 +26,13 @@ MAX_MATCHES_LIMIT = 8064          # rpe_config.max_matches upper bound
 CALIB_KINDS = 16
 STAGE_COUNT = 12
 ORDER_BGR, ORDER_RGB = 0, 1
+REFINE_OK, REFINE_SKIPPED, REFINE_REJECTED = 0, 1, 2   # info[:, 0] of refine_poses (include/rpe_amd.h RPE_REFINE_*)
 
 EXPORTS = [
     "rpe_default_config", "rpe_create", "rpe_destroy", "rpe_last_error", "rpe_device_count",
     "rpe_keypoint_capacity", "rpe_device_malloc", "rpe_device_free", "rpe_memcpy_h2d", "rpe_memcpy_d2h",
     "rpe_synchronize", "rpe_host_alloc", "rpe_host_free", "rpe_host_register", "rpe_host_unregister", "rpe_estimate_batch", "rpe_estimate_batch_device", "rpe_enqueue_batch_device",
-    "rpe_fetch_results", "rpe_fetch_matched_points", "rpe_fetch_structure", "rpe_orb_detect_and_compute", "rpe_orb_debug_fetch",
+    "rpe_fetch_results", "rpe_fetch_matched_points", "rpe_fetch_structure", "rpe_refine_poses", "rpe_refine_pose_points", "rpe_orb_detect_and_compute", "rpe_orb_debug_fetch",
     "rpe_orb_pyramid_pixels", "rpe_match_hamming", "rpe_find_essential", "rpe_recover_pose",
     "rpe_set_profiling", "rpe_get_stage_ms", "rpe_stage_name",
     "rpe_sift_detect_and_compute", "rpe_sift_debug_gauss", "rpe_match_l2",
@@ -97,6 +98,9 @@ def load():
     lib.rpe_fetch_results.argtypes = [vp, C.c_int, vp, vp, i32p, i32p, i32p]; lib.rpe_fetch_results.restype = C.c_int
     lib.rpe_fetch_matched_points.argtypes = [vp, C.c_int, vp, vp]; lib.rpe_fetch_matched_points.restype = C.c_int
     lib.rpe_fetch_structure.argtypes = [vp, C.c_int, vp, vp, vp]; lib.rpe_fetch_structure.restype = C.c_int
+    lib.rpe_refine_poses.argtypes = [vp, C.c_int, C.c_int, vp, vp, i32p, i32p, vp]; lib.rpe_refine_poses.restype = C.c_int
+    lib.rpe_refine_pose_points.argtypes = [vp, vp, vp, vp, vp, vp, i32p, C.c_int, vp, C.c_int, vp, vp, i32p, i32p, vp]
+    lib.rpe_refine_pose_points.restype = C.c_int
     lib.rpe_orb_detect_and_compute.argtypes = [vp, vp, C.c_int, vp, vp, i32p]
     lib.rpe_orb_detect_and_compute.restype = C.c_int
     lib.rpe_orb_debug_fetch.argtypes = [vp, C.c_int, C.c_int, vp]; lib.rpe_orb_debug_fetch.restype = C.c_int
@@ -319,6 +323,16 @@ class Engine:
         self._chk(self.lib.rpe_fetch_structure(self.h, B, _p(rm), _p(pm), _p(pts)))
         return rm.astype(bool), pm.astype(bool), pts
 
+    def refine_poses(self, B, max_iters=10):
+        """Non-linear refinement of the poses of the last batch / stream (rpe_refine_poses; not in the reference):
+        Levenberg-Marquardt on the Sampson error over findEssentialMat's inliers, started from the batch's (R, t).
+        Returns (R[B,3,3], t[B,3,1], inliers[B], info[B,4], rms[B,2]): info = (REFINE_* code, iterations run, residuals
+        used, accepted steps), rms = (before, after) in pixels.  The batch's own results are not modified."""
+        R = np.zeros((B, 3, 3)); t = np.zeros((B, 3, 1)); inl = np.zeros(B, np.int32)
+        info = np.zeros((B, 4), np.int32); rms = np.zeros((B, 2))
+        self._chk(self.lib.rpe_refine_poses(self.h, B, max_iters, _p(R), _p(t), _p(inl), _p(info), _p(rms)))
+        return R, t, inl, info, rms
+
     # ---- stage API
     def orb_detect_and_compute(self, imgs):
         imgs = np.ascontiguousarray(imgs, np.uint8)
@@ -393,6 +407,21 @@ class Engine:
         R = np.zeros((B, 3, 3)); t = np.zeros((B, 3, 1)); inl = np.zeros(B, np.int32)
         self._chk(self.lib.rpe_recover_pose(self.h, _p(E), _p(p1), _p(p2), _p(m), B, _p(K), _p(R), _p(t), _p(inl)))
         return R, t, inl
+
+    def refine_pose_points(self, R0, t0, pts1, pts2, masks, K, max_iters=10):
+        """Stage form of refine_poses: per pair the start (R0, t0), the matched points and a mask (one entry per match)
+        selecting the residuals.  Same outputs as refine_poses."""
+        p1, p2, m = self._pack_points(pts1, pts2)
+        B = len(m); K = np.ascontiguousarray(K, np.float64)
+        R0 = np.ascontiguousarray(np.asarray(R0, np.float64).reshape(B, 9)); t0 = np.ascontiguousarray(np.asarray(t0, np.float64).reshape(B, 3))
+        mk = np.zeros((B, self.max_matches), np.uint8)
+        for i in range(B):
+            mk[i, :m[i]] = np.asarray(masks[i]).astype(bool)[:m[i]]
+        R = np.zeros((B, 3, 3)); t = np.zeros((B, 3, 1)); inl = np.zeros(B, np.int32)
+        info = np.zeros((B, 4), np.int32); rms = np.zeros((B, 2))
+        self._chk(self.lib.rpe_refine_pose_points(self.h, _p(R0), _p(t0), _p(p1), _p(p2), _p(mk), _p(m), B, _p(K), max_iters,
+                                                  _p(R), _p(t), _p(inl), _p(info), _p(rms)))
+        return R, t, inl, info, rms
 
     # ---- roofline calibration
     def calibrate_valu(self, kind, waves_per_simd):

@@ -33,7 +33,11 @@ class BatchProcessor:
         return self.images_dir / f"{frame_idx:06d}.png"
 
     # ---- stream over already decoded frames (gray uint8 [F,H,W] or colour [F,H,W,3])
-    def process_frames(self, frame_indices, frames, order=_capi.ORDER_RGB):
+    def process_frames(self, frame_indices, frames, order=_capi.ORDER_RGB, refine=False):
+        """refine=True (not in the reference) adds, beside the unchanged columns, the same columns for the pose refined
+        on the GPU over findEssentialMat's inliers (PoseEstimator.last_refined): 'R_refined', 't_refined',
+        'roll_refined', 'pitch_refined', 'yaw_refined', and per pair 'refine_code' (_capi.REFINE_*), 'rms_before',
+        'rms_after' (Sampson distance in pixels).  The VP post-step is not applied to the refined columns."""
         frame_indices = [int(f) for f in frame_indices]
         if len(frame_indices) < 2:
             raise ValueError("Need at least 2 frames to process")
@@ -54,9 +58,12 @@ class BatchProcessor:
         try:
             eng.enqueue_stream_device(d_gray, F, est.K)
             R_rel, t_rel, inl, nm, st = eng.fetch_results(F - 1)
+            if refine:
+                R_ref, t_ref, _, rinfo, rms = eng.refine_poses(F - 1)
         finally:
             eng.device_free(d_gray)
         out = {"frames": [], "roll": [], "pitch": [], "yaw": [], "R": [], "t": []}
+        ref = {"roll_refined": [], "pitch_refined": [], "yaw_refined": [], "R_refined": [], "t_refined": []}
         for i in range(F - 1):
             est._raise_for(int(st[i]), int(nm[i]))
             gt = self.gt_loader.get_pose(frame_indices[i])
@@ -69,17 +76,27 @@ class BatchProcessor:
             out["frames"].append(frame_indices[i + 1])
             out["roll"].append(roll); out["pitch"].append(pitch); out["yaw"].append(yaw)
             out["R"].append(R_new_world); out["t"].append(t_rel[i])
+            if refine:
+                R_ref_world = R_prev_world @ R_ref[i]
+                yaw, pitch, roll = rotation_to_euler(R_ref_world, convention=self.euler_convention)
+                ref["roll_refined"].append(roll); ref["pitch_refined"].append(pitch); ref["yaw_refined"].append(yaw)
+                ref["R_refined"].append(R_ref_world); ref["t_refined"].append(t_ref[i])
         for k in ("roll", "pitch", "yaw"):
             out[k] = np.array(out[k])
         out["inliers"] = inl
+        if refine:
+            for k in ("roll_refined", "pitch_refined", "yaw_refined"):
+                ref[k] = np.array(ref[k])
+            out.update(ref)
+            out["refine_code"] = rinfo[:, 0].copy(); out["rms_before"] = rms[:, 0].copy(); out["rms_after"] = rms[:, 1].copy()
         return out
 
-    def process_sequence(self, frame_indices):
+    def process_sequence(self, frame_indices, refine=False):
         frame_indices = [int(f) for f in frame_indices]
         if len(frame_indices) < 2:
             raise ValueError("Need at least 2 frames to process")
         rgb = np.stack([image_loader.decode_rgb(str(self.get_image_path(f))) for f in frame_indices])
-        return self.process_frames(frame_indices, rgb, order=_capi.ORDER_RGB)
+        return self.process_frames(frame_indices, rgb, order=_capi.ORDER_RGB, refine=refine)
 
-    def process_at_interval(self, step=15):
-        return self.process_sequence(self.gt_loader.get_frame_indices(step=step))
+    def process_at_interval(self, step=15, refine=False):
+        return self.process_sequence(self.gt_loader.get_frame_indices(step=step), refine=refine)

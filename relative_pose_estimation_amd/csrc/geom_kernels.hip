@@ -1146,3 +1146,377 @@ void rpe_launch_pose(rpe_handle *h, int B, bool fused)
                        fused ? h->d_kp_count : (const int *)nullptr, h->img2_base ? h->img2_base : B, h->d_K,
                        h->d_R, h->d_t, h->d_inliers, h->d_status, h->cfg.max_matches);
 }
+
+// ------------------------------------------------------------ pose refinement
+// rpe_refine_poses / rpe_refine_pose_points (NOT in the reference): Levenberg-Marquardt on the essential manifold over
+// findEssentialMat's inliers, started from recoverPose's (R, t).  One 256-thread workgroup per pair, f64 throughout.
+//   parameters  R <- exp([w]x) R (Rodrigues), t <- normalise(t + a b1 + b b2), (b1, b2) = tangent basis of the sphere at t
+//   residual    signed Sampson distance of E = [t]x R in pixels (scale (fx + fy) / 2, as the RANSAC threshold)
+//   step        (J'J + lambda diag(J'J)) d = -J'r by 5x5 Cholesky (every lane, identical operands), trial cost in a
+//               second pass, accepted only on a strict decrease (lambda / 10), rejected otherwise (lambda * 10)
+//   sums        lane partials in strided order -> xor butterfly inside the wave -> the four waves added in wave order
+//               through LDS: no floating-point atomics, bit-deterministic
+//   points      the inliers are compacted in match order once: into LDS (max_matches <= REFINE_LDS_MATCHES: 32 B per
+//               match, 64 KB at the cut, two workgroups per CU) or, above the cut, as 16-bit indices into d_n1 / d_n2
+//               (both forms walk the same list in the same order: same sums)
+//   fallback    the refined pose is returned only if it is finite and keeps at least the cheirality inliers of the
+//               input pose (triangulate_one over all matches, as recover_pose_kernel counts them)
+#define REFINE_LAMBDA0 1e-3          // initial damping
+#define REFINE_REL_TOL 1e-6          // stop when an accepted step lowers the cost by no more than this fraction
+#define REFINE_STEP_TOL 1e-9         // ... or its 5-vector is no longer than this
+#define REFINE_SMALL_ANGLE 1e-4      // Rodrigues: series for sin(th)/th and (1 - cos th)/th^2 below this angle
+#define REFINE_MIN_RESIDUALS 6       // 5 degrees of freedom
+#define REFINE_LDS_MATCHES 2048      // staging cut (max_matches)
+#define REFINE_NSUM 21               // 15 J'J + 5 J'r + 1 r'r
+
+__device__ __forceinline__ double wave_sum_f64(double v)
+{
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
+    return v;
+}
+
+// all 256 threads return the same N totals: ((wave 0 + wave 1) + wave 2) + wave 3
+template <int N>
+__device__ __forceinline__ void block_sum_f64(double (&v)[N], double *s_red, int tid)
+{
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = wave_sum_f64(v[k]);
+    __syncthreads();                                   // readers of the previous reduction are done
+    if ((tid & 63) == 0) {
+#pragma unroll
+        for (int k = 0; k < N; ++k) s_red[(tid >> 6) * N + k] = v[k];
+    }
+    __syncthreads();
+#pragma unroll
+    for (int k = 0; k < N; ++k) v[k] = ((s_red[k] + s_red[N + k]) + s_red[2 * N + k]) + s_red[3 * N + k];
+}
+
+__device__ __forceinline__ void cross3(const double *a, const double *b, double *c)
+{
+    c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// Sampson residual of one match in pixels; optionally its 5 derivatives (w0 w1 w2 | b1 b2)
+template <bool JAC>
+__device__ __forceinline__ double refine_residual(const double *R, const double *t, const double *b1, const double *b2, double scale,
+                                                  double x1, double y1, double x2, double y2, double *J)
+{
+    double a[3], l[3], c[3];
+#pragma unroll
+    for (int i = 0; i < 3; ++i) a[i] = (R[3 * i] * x1 + R[3 * i + 1] * y1) + R[3 * i + 2];      // R x1
+    cross3(t, a, l);                                                                              // E x1
+    const double X2[3] = {x2, y2, 1.};
+    cross3(X2, t, c);                                                                             // E' x2 = R' (x2 x t)
+    const double m0 = (R[0] * c[0] + R[3] * c[1]) + R[6] * c[2], m1 = (R[1] * c[0] + R[4] * c[1]) + R[7] * c[2];
+    const double C = (x2 * l[0] + y2 * l[1]) + l[2];
+    const double D = ((l[0] * l[0] + l[1] * l[1]) + m0 * m0) + m1 * m1;
+    const double inv = scale / sqrt(D);
+    if (JAC) {
+        const double rc0[3] = {R[0], R[3], R[6]}, rc1[3] = {R[1], R[4], R[7]};
+        const double ta = (t[0] * a[0] + t[1] * a[1]) + t[2] * a[2], q = C / D;
+        double dC[3], dm0[3], dm1[3];
+        cross3(a, c, dC); cross3(rc0, c, dm0); cross3(rc1, c, dm1);
+#pragma unroll
+        for (int j = 0; j < 3; ++j) {
+            const double dl0 = (j == 0 ? ta : 0.) - a[0] * t[j], dl1 = (j == 1 ? ta : 0.) - a[1] * t[j];
+            const double g = ((l[0] * dl0 + l[1] * dl1) + m0 * dm0[j]) + m1 * dm1[j];
+            J[j] = inv * (dC[j] - q * g);
+        }
+        double aX[3], r0X[3], r1X[3];
+        cross3(a, X2, aX); cross3(rc0, X2, r0X); cross3(rc1, X2, r1X);
+#pragma unroll
+        for (int k = 0; k < 2; ++k) {
+            const double b[3] = {k ? b2[0] : b1[0], k ? b2[1] : b1[1], k ? b2[2] : b1[2]};
+            const double dCk = (b[0] * aX[0] + b[1] * aX[1]) + b[2] * aX[2];
+            const double dl0 = b[1] * a[2] - b[2] * a[1], dl1 = b[2] * a[0] - b[0] * a[2];
+            const double e0 = (b[0] * r0X[0] + b[1] * r0X[1]) + b[2] * r0X[2], e1 = (b[0] * r1X[0] + b[1] * r1X[1]) + b[2] * r1X[2];
+            const double g = ((l[0] * dl0 + l[1] * dl1) + m0 * e0) + m1 * e1;
+            J[3 + k] = inv * (dCk - q * g);
+        }
+    }
+    return C * inv;
+}
+
+// tangent basis of the unit sphere at t: b1 = normalise(t x e_k), k = axis of smallest |t_k| (lowest on ties), b2 = t x b1
+__device__ __forceinline__ void refine_basis(const double *t, double *b1, double *b2)
+{
+    int k = 0;                                       // static indices only
+    double m = fabs(t[0]);
+    if (fabs(t[1]) < m) { k = 1; m = fabs(t[1]); }
+    if (fabs(t[2]) < m) k = 2;
+    const double e[3] = {k == 0 ? 1. : 0., k == 1 ? 1. : 0., k == 2 ? 1. : 0.};
+    cross3(t, e, b1);
+    const double n = sqrt((b1[0] * b1[0] + b1[1] * b1[1]) + b1[2] * b1[2]);
+    b1[0] /= n; b1[1] /= n; b1[2] /= n;
+    cross3(t, b1, b2);
+}
+
+// Rn = exp([w]x) R
+__device__ __forceinline__ void refine_rotate(const double *w, const double *R, double *Rn)
+{
+    const double th2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2], th = sqrt(th2);
+    double A, B;
+    if (th < REFINE_SMALL_ANGLE) { A = 1. - th2 / 6.; B = 0.5 - th2 / 24.; }
+    else { const double sh = sin(0.5 * th); A = sin(th) / th; B = 2. * (sh * sh) / th2; }
+    // exp = I + A [w]x + B [w]x^2,  [w]x^2 = w w' - th2 I
+    double X[9];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) X[i * 3 + j] = B * (w[i] * w[j]) + (i == j ? 1. - B * th2 : 0.);
+    X[1] -= A * w[2]; X[2] += A * w[1];
+    X[3] += A * w[2]; X[5] -= A * w[0];
+    X[6] -= A * w[1]; X[7] += A * w[0];
+#pragma unroll
+    for (int i = 0; i < 3; ++i)
+#pragma unroll
+        for (int j = 0; j < 3; ++j) Rn[i * 3 + j] = (X[i * 3] * R[j] + X[i * 3 + 1] * R[3 + j]) + X[i * 3 + 2] * R[6 + j];
+}
+
+// (H + lambda diag H) d = -g, H given as its upper triangle (row-major, 15 entries); false when not positive definite
+__device__ __forceinline__ bool refine_solve(const double *H, const double *g, double lambda, double *d)
+{
+    double L[5][5];
+    int q = 0;
+#pragma unroll
+    for (int i = 0; i < 5; ++i)
+#pragma unroll
+        for (int j = i; j < 5; ++j, ++q) { L[i][j] = H[q]; L[j][i] = H[q]; }
+#pragma unroll
+    for (int i = 0; i < 5; ++i) L[i][i] = L[i][i] + lambda * L[i][i];
+    bool ok = true;
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+        double s = L[j][j];
+#pragma unroll
+        for (int k = 0; k < j; ++k) s -= L[j][k] * L[j][k];
+        if (!(s > 0.) || !isfinite(s)) ok = false;
+        const double dj = sqrt(s);
+        L[j][j] = dj;
+#pragma unroll
+        for (int i = j + 1; i < 5; ++i) {
+            double v = L[i][j];
+#pragma unroll
+            for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
+            L[i][j] = v / dj;
+        }
+    }
+    double y[5];
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        double v = -g[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) v -= L[i][k] * y[k];
+        y[i] = v / L[i][i];
+    }
+#pragma unroll
+    for (int i = 4; i >= 0; --i) {
+        double v = y[i];
+#pragma unroll
+        for (int k = i + 1; k < 5; ++k) v -= L[k][i] * d[k];
+        d[i] = v / L[i][i];
+    }
+    return ok;
+}
+
+// status / inl_in may be null (stage form): every pair is then refined and the input pose's cheirality inliers are counted here
+template <bool LDS>
+__global__ __launch_bounds__(256) void pose_refine_kernel(const double2 *__restrict__ n1, const double2 *__restrict__ n2,
+                                                           const uint8_t *__restrict__ mask, const int *__restrict__ m_n,
+                                                           const int *__restrict__ status, const int *__restrict__ inl_in,
+                                                           const double *__restrict__ K, const double *__restrict__ Rin,
+                                                           const double *__restrict__ tin, double *__restrict__ Rout,
+                                                           double *__restrict__ tout, int *__restrict__ inl_out,
+                                                           int *__restrict__ info, double *__restrict__ rms,
+                                                           int max_matches, int max_iters)
+{
+    extern __shared__ double2 s_dyn[];            // LDS: [2][max_matches] compacted inlier points; else u16 [max_matches] inlier indices
+    __shared__ double s_red[4 * REFINE_NSUM];
+    __shared__ int s_wc[4], s_g[2];
+    const int pair = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int M = min(m_n[pair], max_matches);
+    const bool st_ok = !status || status[pair] == RPE_PAIR_OK;
+    const double2 *gp1 = n1 + (long long)pair * max_matches, *gp2 = n2 + (long long)pair * max_matches;
+    const uint8_t *mk = mask + (long long)pair * max_matches;
+    double2 *l1 = s_dyn, *l2 = s_dyn + max_matches;
+    unsigned short *s_idx = (unsigned short *)s_dyn;
+    if (tid < 2) s_g[tid] = 0;
+    // ---- ordered compaction of the inliers
+    int n = 0;
+    for (int i0 = 0; i0 < (st_ok ? M : 0); i0 += 256) {
+        const int i = i0 + tid;
+        const bool f = i < M && mk[i] != 0;
+        const unsigned long long bal = __ballot(f);
+        if (lane == 0) s_wc[wv] = __popcll(bal);
+        __syncthreads();
+        int off = n, tot = 0;
+#pragma unroll
+        for (int w = 0; w < 4; ++w) { const int c = s_wc[w]; if (w < wv) off += c; tot += c; }
+        if (f) {
+            const int pos = off + __popcll(bal & ((1ull << lane) - 1ull));
+            if (LDS) { l1[pos] = gp1[i]; l2[pos] = gp2[i]; }
+            else s_idx[pos] = (unsigned short)i;
+        }
+        n += tot;
+        __syncthreads();
+    }
+    double R[9], t[3];
+#pragma unroll
+    for (int e = 0; e < 9; ++e) R[e] = Rin[pair * 9 + e];
+#pragma unroll
+    for (int e = 0; e < 3; ++e) t[e] = tin[pair * 3 + e];
+    const double scale = (K[0] + K[4]) / 2;
+    auto fetch = [&](int j, double2 &a, double2 &b) {
+        if (LDS) { a = l1[j]; b = l2[j]; }
+        else { const int i = s_idx[j]; a = gp1[i]; b = gp2[i]; }
+    };
+    double H[15], g[5], b1[3], b2[3];
+    double cost = 0., cost0 = 0., lambda = REFINE_LAMBDA0;
+    int iters = 0, acc = 0;
+    bool finite = true;
+    auto linearise = [&](double &rtr) {
+        refine_basis(t, b1, b2);
+        double s[REFINE_NSUM];
+#pragma unroll
+        for (int k = 0; k < REFINE_NSUM; ++k) s[k] = 0.;
+        for (int j = tid; j < n; j += 256) {
+            double2 a, b; fetch(j, a, b);
+            double J[5];
+            const double r = refine_residual<true>(R, t, b1, b2, scale, a.x, a.y, b.x, b.y, J);
+            int q = 0;
+#pragma unroll
+            for (int u = 0; u < 5; ++u)
+#pragma unroll
+                for (int v = u; v < 5; ++v, ++q) s[q] += J[u] * J[v];
+#pragma unroll
+            for (int u = 0; u < 5; ++u) s[15 + u] += J[u] * r;
+            s[20] += r * r;
+        }
+        block_sum_f64<REFINE_NSUM>(s, s_red, tid);
+#pragma unroll
+        for (int k = 0; k < 15; ++k) H[k] = s[k];
+#pragma unroll
+        for (int k = 0; k < 5; ++k) g[k] = s[15 + k];
+        rtr = s[20];
+    };
+    const bool skip = !st_ok || n < REFINE_MIN_RESIDUALS;
+    if (n > 0) {
+        linearise(cost0);
+        cost = cost0;
+        finite = isfinite(cost0);
+    }
+    if (!skip && finite) {
+        bool need_lin = false;
+        for (int it = 0; it < max_iters; ++it) {
+            if (need_lin) { double dummy; linearise(dummy); need_lin = false; }
+            ++iters;
+            double d[5];
+            if (!refine_solve(H, g, lambda, d)) { lambda = lambda * 10.; continue; }
+            double Rn[9], tn[3];
+            refine_rotate(d, R, Rn);
+#pragma unroll
+            for (int e = 0; e < 3; ++e) tn[e] = (t[e] + d[3] * b1[e]) + d[4] * b2[e];
+            const double nt = sqrt((tn[0] * tn[0] + tn[1] * tn[1]) + tn[2] * tn[2]);
+            tn[0] /= nt; tn[1] /= nt; tn[2] /= nt;
+            double c1[1] = {0.};
+            for (int j = tid; j < n; j += 256) {
+                double2 a, b; fetch(j, a, b);
+                const double r = refine_residual<false>(Rn, tn, b1, b2, scale, a.x, a.y, b.x, b.y, nullptr);
+                c1[0] += r * r;
+            }
+            block_sum_f64<1>(c1, s_red, tid);
+            if (isfinite(c1[0]) && c1[0] < cost) {
+                const double dec = cost - c1[0], prev = cost;
+                const double dn = sqrt((((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) + d[3] * d[3]) + d[4] * d[4]);
+#pragma unroll
+                for (int e = 0; e < 9; ++e) R[e] = Rn[e];
+#pragma unroll
+                for (int e = 0; e < 3; ++e) t[e] = tn[e];
+                cost = c1[0]; lambda = lambda / 10.; ++acc; need_lin = true;
+                if (dec <= REFINE_REL_TOL * prev || dn <= REFINE_STEP_TOL) break;
+            } else {
+                lambda = lambda * 10.;
+            }
+        }
+#pragma unroll
+        for (int e = 0; e < 9; ++e) finite = finite && isfinite(R[e]);
+#pragma unroll
+        for (int e = 0; e < 3; ++e) finite = finite && isfinite(t[e]);
+    }
+    // ---- cheirality inliers over ALL matches: of the refined pose, and of the input pose where the caller has no count
+    const bool moved = !skip && finite && acc > 0;
+    const bool need_org = st_ok && inl_in == nullptr;
+    if (moved || need_org) {
+        double R0[9], t0[3];
+#pragma unroll
+        for (int e = 0; e < 9; ++e) R0[e] = Rin[pair * 9 + e];
+#pragma unroll
+        for (int e = 0; e < 3; ++e) t0[e] = tin[pair * 3 + e];
+        int gr = 0, go = 0;
+        for (int i = tid; i < M; i += 256) {
+            const double2 a = gp1[i], b = gp2[i];
+            double P[3];
+            if (moved) gr += triangulate_one(R, t, a.x, a.y, b.x, b.y, P);
+            if (need_org) go += triangulate_one(R0, t0, a.x, a.y, b.x, b.y, P);
+        }
+        gr = wave_sum(gr); go = wave_sum(go);
+        __syncthreads();
+        if (lane == 0) { atomicAdd(&s_g[0], gr); atomicAdd(&s_g[1], go); }
+    }
+    __syncthreads();
+    const int g_org = inl_in ? inl_in[pair] : s_g[1];
+    const int g_ref = moved ? s_g[0] : g_org;
+    int code = RPE_REFINE_OK;
+    if (skip) code = RPE_REFINE_SKIPPED;
+    else if (!finite || g_ref < g_org) code = RPE_REFINE_REJECTED;
+    const bool take = code == RPE_REFINE_OK && moved;
+    if (tid < 9) Rout[pair * 9 + tid] = take ? R[tid] : Rin[pair * 9 + tid];
+    if (tid < 3) tout[pair * 3 + tid] = take ? t[tid] : tin[pair * 3 + tid];
+    if (tid == 0) {
+        inl_out[pair] = take ? g_ref : g_org;
+        info[pair * 4] = code; info[pair * 4 + 1] = iters; info[pair * 4 + 2] = n; info[pair * 4 + 3] = acc;
+        const double before = n > 0 ? sqrt(cost0 / n) : 0.;
+        rms[pair * 2] = before;
+        rms[pair * 2 + 1] = take ? sqrt(cost / n) : before;
+    }
+}
+
+// normalised points of a stage call (the batch path leaves them in d_n1 / d_n2): same expression as ransac_prepare_kernel
+__global__ __launch_bounds__(256) void refine_normalise_kernel(const float2 *__restrict__ pts1, const float2 *__restrict__ pts2,
+                                                                const int *__restrict__ m_n, const double *__restrict__ K,
+                                                                double2 *__restrict__ n1, double2 *__restrict__ n2, int max_matches)
+{
+    const int pair = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    const int M = min(m_n[pair], max_matches);
+    const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
+    if (i < M) {
+        long long o = (long long)pair * max_matches + i;
+        float2 a = pts1[o], b = pts2[o];
+        n1[o] = make_double2(((double)a.x - cx) / fx, ((double)a.y - cy) / fy);
+        n2[o] = make_double2(((double)b.x - cx) / fx, ((double)b.y - cy) / fy);
+    }
+}
+
+// after a batch / stream (from_batch): inliers = ransac_mask_kernel's mask of the winning model, start = d_R / d_t.
+// stage form: d_mask, d_ref_R0 / d_ref_t0 and d_pts* were uploaded by the caller.
+void rpe_launch_refine(rpe_handle *h, int B, int max_iters, bool from_batch)
+{
+    const int mm = h->cfg.max_matches;
+    if (from_batch)
+        hipLaunchKernelGGL(ransac_mask_kernel, dim3(B), dim3(256), 0, h->stream,
+                           h->d_n1, h->d_n2, h->d_rstate, h->d_K, h->cfg.ransac_threshold, (const int *)h->d_status, h->d_mask, mm);
+    else
+        hipLaunchKernelGGL(refine_normalise_kernel, dim3((mm + 255) / 256, B), dim3(256), 0, h->stream,
+                           h->d_pts1, h->d_pts2, h->d_m_n, h->d_K, h->d_n1, h->d_n2, mm);
+    const double *Rin = from_batch ? h->d_R : h->d_ref_R0, *tin = from_batch ? h->d_t : h->d_ref_t0;
+    const int *status = from_batch ? h->d_status : nullptr, *inl = from_batch ? h->d_inliers : nullptr;
+    if (mm <= REFINE_LDS_MATCHES)
+        hipLaunchKernelGGL(pose_refine_kernel<true>, dim3(B), dim3(256), sizeof(double2) * 2 * (size_t)mm, h->stream,
+                           h->d_n1, h->d_n2, h->d_mask, h->d_m_n, status, inl, h->d_K, Rin, tin,
+                           h->d_ref_R, h->d_ref_t, h->d_ref_inl, h->d_ref_info, h->d_ref_rms, mm, max_iters);
+    else
+        hipLaunchKernelGGL(pose_refine_kernel<false>, dim3(B), dim3(256), sizeof(unsigned short) * (size_t)mm, h->stream,
+                           h->d_n1, h->d_n2, h->d_mask, h->d_m_n, status, inl, h->d_K, Rin, tin,
+                           h->d_ref_R, h->d_ref_t, h->d_ref_inl, h->d_ref_info, h->d_ref_rms, mm, max_iters);
+}

@@ -399,7 +399,7 @@ extern "C" void rpe_destroy(rpe_handle *h)
                     h->d_hist, h->d_cand_xy, h->d_cand_resp, h->d_cand_count, h->d_kp_xy, h->d_kp_resp, h->d_kp_angle,
                     h->d_kp_pt, h->d_kp_cs, h->d_kp_count, h->d_desc, h->d_m_q, h->d_m_t, h->d_m_d, h->d_resblk, h->d_pts1, h->d_pts2,
                     h->d_subsets, h->d_nit_denom, h->d_nit_round, h->d_rstate, h->d_n1, h->d_n2, h->d_found, h->d_models, h->d_hyp, h->d_counts,
-                    h->d_nmodels, h->d_mask, h->d_pose_mask, h->d_points, h->d_E, h->d_K, h->d_m_best, h->d_m_best2, h->d_m_norm, h->d_hm_best, h->d_hm_row, h->d_ovf, h->d_corner, h->d_corner_count, h->d_kp_lvl_count};
+                    h->d_nmodels, h->d_mask, h->d_pose_mask, h->d_points, h->d_ref_R, h->d_ref_t, h->d_ref_rms, h->d_ref_R0, h->d_ref_t0, h->d_ref_inl, h->d_ref_info, h->d_E, h->d_K, h->d_m_best, h->d_m_best2, h->d_m_norm, h->d_hm_best, h->d_hm_row, h->d_ovf, h->d_corner, h->d_corner_count, h->d_kp_lvl_count};
     for (void *p : ptrs) if (p) hipFree(p);
     if (h->h_resblk) hipHostFree(h->h_resblk);
     for (void *p : h->user_allocs) hipFree(p);
@@ -856,6 +856,48 @@ extern "C" int rpe_fetch_structure(rpe_handle *h, int B, uint8_t *ransac_mask, u
     return RPE_OK;
 }
 
+// refined poses: device buffers on first use, launch, fetch
+static int refine_alloc(rpe_handle *h)
+{
+    const size_t MB = (size_t)h->cfg.max_batch;
+    if (!h->d_ref_R) HIPCHK(h, hipMalloc((void **)&h->d_ref_R, MB * 9 * sizeof(double)));
+    if (!h->d_ref_t) HIPCHK(h, hipMalloc((void **)&h->d_ref_t, MB * 3 * sizeof(double)));
+    if (!h->d_ref_rms) HIPCHK(h, hipMalloc((void **)&h->d_ref_rms, MB * 2 * sizeof(double)));
+    if (!h->d_ref_R0) HIPCHK(h, hipMalloc((void **)&h->d_ref_R0, MB * 9 * sizeof(double)));
+    if (!h->d_ref_t0) HIPCHK(h, hipMalloc((void **)&h->d_ref_t0, MB * 3 * sizeof(double)));
+    if (!h->d_ref_inl) HIPCHK(h, hipMalloc((void **)&h->d_ref_inl, MB * sizeof(int)));
+    if (!h->d_ref_info) HIPCHK(h, hipMalloc((void **)&h->d_ref_info, MB * 4 * sizeof(int)));
+    return RPE_OK;
+}
+
+static int refine_run(rpe_handle *h, int B, int max_iters, bool from_batch, double *R, double *t, int32_t *inliers,
+                      int32_t *info, double *rms)
+{
+    rpe_launch_refine(h, B, max_iters, from_batch);
+    HIPCHK(h, hipGetLastError());
+    if (R) HIPCHK(h, hipMemcpyAsync(R, h->d_ref_R, sizeof(double) * 9 * B, hipMemcpyDeviceToHost, h->stream));
+    if (t) HIPCHK(h, hipMemcpyAsync(t, h->d_ref_t, sizeof(double) * 3 * B, hipMemcpyDeviceToHost, h->stream));
+    if (inliers) HIPCHK(h, hipMemcpyAsync(inliers, h->d_ref_inl, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
+    if (info) HIPCHK(h, hipMemcpyAsync(info, h->d_ref_info, sizeof(int) * 4 * B, hipMemcpyDeviceToHost, h->stream));
+    if (rms) HIPCHK(h, hipMemcpyAsync(rms, h->d_ref_rms, sizeof(double) * 2 * B, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return RPE_OK;
+}
+
+extern "C" int rpe_refine_poses(rpe_handle *h, int B, int max_iters, double *R, double *t, int32_t *inliers,
+                                int32_t *info, double *rms)
+{
+    if (!h || B < 1 || B > h->cfg.max_batch) return RPE_ERR_INVALID;
+    if (max_iters < 1 || max_iters > 100) { h->err = "rpe_refine_poses: max_iters must be 1 ... 100"; return RPE_ERR_INVALID; }
+    if (h->last_chunked) { h->err = "rpe_refine_poses: the last host batch ran in chunks: per-match results are kept for unchunked and device-resident batches only"; return RPE_ERR_INVALID; }
+    if (!h->structure_valid) { h->err = "rpe_refine_poses: no batch or stream since the last stage-API call (it overwrote the per-match buffers)"; return RPE_ERR_INVALID; }
+    if (B > h->last_pairs) { h->err = "rpe_refine_poses: more pairs than the last batch had"; return RPE_ERR_INVALID; }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    int rc = refine_alloc(h);
+    if (rc) return rc;
+    return refine_run(h, B, max_iters, true, R, t, inliers, info, rms);
+}
+
 // ---------------------------------------------------------------- stage API
 extern "C" int rpe_orb_detect_and_compute(rpe_handle *h, const uint8_t *h_imgs, int n_images,
                                           rpe_keypoint *kps, uint8_t *desc, int32_t *counts)
@@ -1026,6 +1068,25 @@ extern "C" int rpe_recover_pose(rpe_handle *h, const double *h_E, const float *h
     rpe_launch_pose(h, B, false);
     HIPCHK(h, hipGetLastError());
     return rpe_fetch_results(h, B, R, t, inliers, nullptr, nullptr);
+}
+
+extern "C" int rpe_refine_pose_points(rpe_handle *h, const double *h_R0, const double *h_t0, const float *h_pts1,
+                                      const float *h_pts2, const uint8_t *h_mask, const int32_t *m, int B, const double K[9],
+                                      int max_iters, double *R, double *t, int32_t *inliers, int32_t *info, double *rms)
+{
+    if (!h || !h_R0 || !h_t0 || !h_pts1 || !h_pts2 || !h_mask || !m || !K || B < 1) return RPE_ERR_INVALID;
+    if (B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return RPE_ERR_CAPACITY; }
+    if (max_iters < 1 || max_iters > 100) { h->err = "rpe_refine_pose_points: max_iters must be 1 ... 100"; return RPE_ERR_INVALID; }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    h->structure_valid = false;                 // overwrites buffers rpe_fetch_structure reads
+    int rc = upload_points(h, h_pts1, h_pts2, m, B);
+    if (rc) return rc;
+    if ((rc = set_K(h, K)) != RPE_OK) return rc;
+    if ((rc = refine_alloc(h)) != RPE_OK) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->d_mask, h_mask, (size_t)h->cfg.max_matches * B, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_ref_R0, h_R0, sizeof(double) * 9 * B, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_ref_t0, h_t0, sizeof(double) * 3 * B, hipMemcpyHostToDevice, h->stream));
+    return refine_run(h, B, max_iters, false, R, t, inliers, info, rms);
 }
 
 // ---------------------------------------------------------------- profiling

@@ -191,6 +191,10 @@ struct rpe_handle {
     uint8_t *d_mask = nullptr;            // [pair][max_matches]
     uint8_t *d_pose_mask = nullptr;       // [pair][max_matches] rpe_fetch_structure only (created on first use)
     double *d_points = nullptr;           // [pair][max_matches][3] rpe_fetch_structure only (created on first use)
+    // rpe_refine_poses / rpe_refine_pose_points only (created on first use): refined pose, cheirality count, info[4], rms[2]
+    // per pair; start pose of the stage form
+    double *d_ref_R = nullptr, *d_ref_t = nullptr, *d_ref_rms = nullptr, *d_ref_R0 = nullptr, *d_ref_t0 = nullptr;
+    int *d_ref_inl = nullptr, *d_ref_info = nullptr;
     bool structure_valid = false;         // d_pts*, d_n*, d_rstate, d_R / d_t still describe the last batch / stream (run_pairs)
     // results
     double *d_R = nullptr, *d_t = nullptr, *d_E = nullptr;
@@ -228,6 +232,7 @@ long long rpe_sift_gauss_floats(rpe_handle *h);
 void rpe_launch_ransac(rpe_handle *h, int B, bool want_mask);
 void rpe_launch_pose(rpe_handle *h, int B, bool set_status);
 void rpe_launch_structure(rpe_handle *h, int B);
+void rpe_launch_refine(rpe_handle *h, int B, int max_iters, bool from_batch);
 
 // per-stage hipEvents on the handle's stream (rpe_set_profiling / rpe_get_stage_ms)
 #define MARK(h, stage) do { if ((h)->profiling) hipEventRecord((h)->ev[stage], (h)->stream); } while (0)

@@ -161,6 +161,17 @@ class PoseEstimator:
             out.append({'ransac_mask': rm[p, :n].copy(), 'pose_mask': pm[p, :n].copy(), 'points3d': pts[p, :n].copy()})
         return out
 
+    def last_refined(self, max_iters=10):
+        """Refined poses of the pairs of the last estimate_batch / estimate_sequence call (not in the reference):
+        Levenberg-Marquardt on the Sampson error over findEssentialMat's inliers, started from the returned (R, t), on
+        the GPU.  Returns (R[B,3,3], t[B,3,1], inliers[B], status[B], info[B,4], rms[B,2]): the shape of estimate_batch
+        plus info = (_capi.REFINE_* code, iterations run, residuals used, accepted steps) and rms = (before, after) in
+        pixels.  Pairs that were skipped or rejected carry the unrefined pose.  Raises RpeError after a chunked host
+        batch, which keeps no per-match results."""
+        eng, B = self._last_engine, self._last_pairs
+        R, t, inl, info, rms = eng.refine_poses(B, max_iters)
+        return R, t, inl, eng.fetch_results(B)[4], info, rms
+
     def estimate_sequence(self, frames):
         """Relative poses of consecutive frames (frame i -> i+1): the pair loop of the reference's
         BatchProcessor.process_sequence (batch_processor.py:71-109) with features extracted once
@@ -244,6 +255,17 @@ class PoseEstimator:
             'pose_mask': pm[0, :n].copy(),
             'points3d': pts[0, :n].copy(),
         }
+
+    def estimate_refined(self, img1, img2, max_iters=10):
+        """estimate_with_debug's dict (the unrefined pose stays under 'R', 't', 'inliers'; VP refinement is never
+        applied) plus the non-linear refinement of that pose over findEssentialMat's inliers (not in the reference):
+        'R_refined', 't_refined', 'inliers_refined' (cheirality count), 'refine_code' (_capi.REFINE_*),
+        'refine_iters', 'rms_before', 'rms_after' (Sampson distance in pixels).  Raises what estimate raises."""
+        info = self.estimate_with_debug(img1, img2)
+        R, t, inl, rinfo, rms = self._last_engine.refine_poses(1, max_iters)
+        info.update(R_refined=R[0], t_refined=t[0], inliers_refined=int(inl[0]), refine_code=int(rinfo[0, 0]),
+                    refine_iters=int(rinfo[0, 1]), rms_before=float(rms[0, 0]), rms_after=float(rms[0, 1]))
+        return info
 
     def close(self):
         for e in self._engines.values():

@@ -192,6 +192,47 @@ int rpe_estimate_stream(rpe_handle *h, const uint8_t *h_frames, int F, const dou
                         double *R, double *t, int32_t *inliers, int32_t *n_matches, int32_t *status);
 int rpe_enqueue_stream_device(rpe_handle *h, const uint8_t *d_frames, int F, const double K[9]);
 
+/* ---------------------------------------------------------- frame store */
+/* Extraction separated from pairing (NOT in the reference, whose only shapes are the pair and the consecutive-frame
+ * sequence): per-frame features -- keypoint points, count, descriptors, the L2 matcher's norm words, RPE_OVF_* flags --
+ * stay resident in HBM slots across calls, and a pair list names two slots per pair.  Windowed matching (frame i
+ * against i+1 .. i+k), loop-closure candidates and online use (put the new frame, pair it with the ring of the last k)
+ * extract every frame once.  The store is created on demand and survives every other call on the handle (batch,
+ * stream, stage API, refinement); rpe_destroy frees it.  Bytes per slot:
+ * (nfeatures + 64) * (descriptor bytes + 8 + N) + 8, descriptor bytes = 32 (ORB) or 128 (SIFT), N = 8 for NORM_L2 handles
+ * in crossCheck mode (the only matcher that reads the norm words) and 0 otherwise, nfeatures = RPE_SIFT_UNCAPPED_CAPACITY
+ * for uncapped SIFT.
+ * rpe_frames_reserve: n_slots = 0 frees; growing or shrinking keeps the slots below the new size (it waits for the
+ * handle's stream) and ends the pair list's claim on rpe_fetch_overflow, which is refused until the next batch, stream or
+ * pair list.  RPE_ERR_HIP when the device cannot hold the new store: the old one is kept. */
+int rpe_frames_reserve(rpe_handle *h, int n_slots);
+int rpe_frames_capacity(const rpe_handle *h);
+/* extracts n frames (n <= 2*max_batch) and keeps them in slots[0..n) (host array, distinct, inside the store); a slot
+ * filled before is replaced.  The keypoint order of rpe_config.stl_runtime is a property of the extraction and so of
+ * the slot.  _device form: asynchronous on the handle's stream; the frames are read in place like
+ * rpe_enqueue_batch_device's and must stay valid until the next synchronising call.  rpe_frames_put stages host frames
+ * through the handle's own upload buffers.  slots[] may be reused as soon as the call returns.  Like a stage-API call,
+ * a put overwrites the extraction workspace: rpe_fetch_overflow / rpe_fetch_structure / rpe_refine_poses are refused
+ * until the next batch, stream or pair list.
+ * RPE_ERR_INVALID: no store, slot outside the store, a slot twice in one put.  RPE_ERR_CAPACITY: n > 2*max_batch. */
+int rpe_frames_put_device(rpe_handle *h, const uint8_t *d_frames, int n, const int32_t *slots);
+int rpe_frames_put(rpe_handle *h, const uint8_t *h_frames, int n, const int32_t *slots);
+/* keypoint count (-1 = slot never filled; 0 = a frame without keypoints) and RPE_OVF_* flags of n slots; either
+ * output may be NULL.  Synchronises the handle's stream. */
+int rpe_frames_info(rpe_handle *h, int n, const int32_t *slots, int32_t *counts, uint32_t *flags);
+/* hot path over the store: P pairs (P <= max_batch), pair p = (slot1[p], slot2[p]); any slots, repeats, reversed and
+ * self pairs allowed.  match -> findEssentialMat -> recoverPose exactly as a batch runs them: the result of pair (a, b)
+ * is bit for bit what rpe_estimate_batch_device returns for the frame put into slot a against the frame put into
+ * slot b.  Afterwards the pair list is "the last batch" of rpe_fetch_results(P), rpe_fetch_matched_points,
+ * rpe_fetch_structure, rpe_refine_poses, rpe_gather_poses and rpe_fetch_overflow (flags of slot1[p] | slot2[p]).
+ * A frame without keypoints gives its pairs RPE_PAIR_NO_DESCRIPTORS.  slot1 / slot2 may be reused as soon as the call
+ * returns.  rpe_get_stage_ms reports match / ransac / pose and zero for the extraction stages.
+ * RPE_ERR_INVALID: no store, slot outside the store, empty slot.  RPE_ERR_CAPACITY: P > max_batch.  Nothing is
+ * launched and the handle stays usable after either. */
+int rpe_enqueue_pairs(rpe_handle *h, const int32_t *slot1, const int32_t *slot2, int P, const double K[9]);
+int rpe_estimate_pairs(rpe_handle *h, const int32_t *slot1, const int32_t *slot2, int P, const double K[9],
+                       double *R, double *t, int32_t *inliers, int32_t *n_matches, int32_t *status);
+
 /* Image ingest, the step before the path (reference src/utils/image_loader.py:23-28:
  * cv2.imread -> BGR, cv2.cvtColor(BGR2GRAY)): interleaved 3-channel uint8 images -> gray with cv2's
  * fixed-point weights, gray = (B*3735 + G*19235 + R*9798 + 16384) >> 15, on the handle's stream.

@@ -41,6 +41,8 @@ EXPORTS = [
     "rpe_fetch_overflow", "rpe_calibrate_valu", "rpe_calibrate_valu_name", "rpe_calibrate_hbm",
     "rpe_comm_unique_id", "rpe_comm_create", "rpe_comm_prepare", "rpe_comm_connect", "rpe_comm_destroy", "rpe_comm_last_error", "rpe_gather_poses",
     "rpe_comm_allreduce_max", "rpe_comm_barrier",
+    "rpe_frames_reserve", "rpe_frames_capacity", "rpe_frames_put_device", "rpe_frames_put", "rpe_frames_info",
+    "rpe_enqueue_pairs", "rpe_estimate_pairs",
 ]
 
 
@@ -137,6 +139,13 @@ def load():
     lib.rpe_gather_poses.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp]; lib.rpe_gather_poses.restype = C.c_int
     lib.rpe_comm_allreduce_max.argtypes = [vp, C.POINTER(C.c_double)]; lib.rpe_comm_allreduce_max.restype = C.c_int
     lib.rpe_comm_barrier.argtypes = [vp]; lib.rpe_comm_barrier.restype = C.c_int
+    lib.rpe_frames_reserve.argtypes = [vp, C.c_int]; lib.rpe_frames_reserve.restype = C.c_int
+    lib.rpe_frames_capacity.argtypes = [vp]; lib.rpe_frames_capacity.restype = C.c_int
+    lib.rpe_frames_put_device.argtypes = [vp, vp, C.c_int, i32p]; lib.rpe_frames_put_device.restype = C.c_int
+    lib.rpe_frames_put.argtypes = [vp, vp, C.c_int, i32p]; lib.rpe_frames_put.restype = C.c_int
+    lib.rpe_frames_info.argtypes = [vp, C.c_int, i32p, i32p, vp]; lib.rpe_frames_info.restype = C.c_int
+    lib.rpe_enqueue_pairs.argtypes = [vp, i32p, i32p, C.c_int, vp]; lib.rpe_enqueue_pairs.restype = C.c_int
+    lib.rpe_estimate_pairs.argtypes = [vp, i32p, i32p, C.c_int, vp, vp, vp, i32p, i32p, i32p]; lib.rpe_estimate_pairs.restype = C.c_int
     _lib = lib
     return lib
 
@@ -332,6 +341,53 @@ class Engine:
         info = np.zeros((B, 4), np.int32); rms = np.zeros((B, 2))
         self._chk(self.lib.rpe_refine_poses(self.h, B, max_iters, _p(R), _p(t), _p(inl), _p(info), _p(rms)))
         return R, t, inl, info, rms
+
+    # ---- frame store (rpe_frames_* / rpe_enqueue_pairs; not in the reference)
+    def frames_reserve(self, n_slots):
+        """Create / resize / free (0) the store of per-frame features; slots below the new size are kept."""
+        self._chk(self.lib.rpe_frames_reserve(self.h, int(n_slots)))
+
+    def frames_capacity(self):
+        return int(self.lib.rpe_frames_capacity(self.h))
+
+    def frames_put(self, frames, slots):
+        """Extract frames [n, H, W] (host) once and keep their features in the store slots `slots` (n distinct ints)."""
+        frames = np.ascontiguousarray(frames, np.uint8)
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        n = frames.shape[0]
+        assert frames.shape == (n, self.height, self.width) and slots.size == n, (frames.shape, slots.shape)
+        self._chk(self.lib.rpe_frames_put(self.h, _p(frames), n, _p(slots)))
+
+    def frames_put_device(self, d_frames, n, slots):
+        """Same, frames resident in HBM; asynchronous (the frames must stay valid until the next synchronising call)."""
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        assert slots.size == n
+        self._chk(self.lib.rpe_frames_put_device(self.h, d_frames, int(n), _p(slots)))
+
+    def frames_info(self, slots):
+        """(keypoint counts, OVF_* flags) of the slots; count -1 = never filled."""
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        cnt = np.zeros(slots.size, np.int32); fl = np.zeros(slots.size, np.uint32)
+        self._chk(self.lib.rpe_frames_info(self.h, slots.size, _p(slots), _p(cnt), _p(fl)))
+        return cnt, fl
+
+    def enqueue_pairs(self, slot1, slot2, K):
+        s1 = np.ascontiguousarray(slot1, np.int32).reshape(-1); s2 = np.ascontiguousarray(slot2, np.int32).reshape(-1)
+        assert s1.size == s2.size
+        K = np.ascontiguousarray(K, np.float64)
+        self._chk(self.lib.rpe_enqueue_pairs(self.h, _p(s1), _p(s2), s1.size, _p(K)))
+
+    def estimate_pairs(self, slot1, slot2, K):
+        """Poses of the pairs (slot1[p], slot2[p]) of stored frames: the batch's match / RANSAC / pose kernels, no
+        extraction.  Returns R, t, inliers, n_matches, status like estimate_batch; the list is 'the last batch' of
+        fetch_structure / refine_poses / fetch_overflow / fetch_matched_points afterwards."""
+        s1 = np.ascontiguousarray(slot1, np.int32).reshape(-1); s2 = np.ascontiguousarray(slot2, np.int32).reshape(-1)
+        assert s1.size == s2.size
+        P = s1.size
+        K = np.ascontiguousarray(K, np.float64)
+        R, t, inl, nm, st = self._outs(P)
+        self._chk(self.lib.rpe_estimate_pairs(self.h, _p(s1), _p(s2), P, _p(K), _p(R), _p(t), _p(inl), _p(nm), _p(st)))
+        return R, t, inl, nm, st
 
     # ---- stage API
     def orb_detect_and_compute(self, imgs):

@@ -1039,10 +1039,11 @@ __device__ static int triangulate_one(const double *R, const double *t, double x
     return good;
 }
 
+template <bool TAB>
 __global__ __launch_bounds__(256) void recover_pose_kernel(const double *__restrict__ Eall, const float2 *__restrict__ pts1,
                                                             const float2 *__restrict__ pts2, const int *__restrict__ m_n,
                                                             const int *__restrict__ found, const int *__restrict__ kp_count,
-                                                            int img2_base, const double *__restrict__ K,
+                                                            int img2_base, const int2 *__restrict__ pair_tab, const double *__restrict__ K,
                                                             double *__restrict__ Rout, double *__restrict__ tout,
                                                             int *__restrict__ inliers, int *__restrict__ status, int max_matches)
 {
@@ -1050,7 +1051,9 @@ __global__ __launch_bounds__(256) void recover_pose_kernel(const double *__restr
     const int pair = blockIdx.x, tid = threadIdx.x;
     const int M = min(m_n[pair], max_matches);
     int stt = RPE_PAIR_OK;
-    if (kp_count && (kp_count[pair] == 0 || kp_count[img2_base + pair] == 0)) stt = RPE_PAIR_NO_DESCRIPTORS;
+    int img1, img2;
+    rpe_pair_slots<TAB>(pair_tab, img2_base, pair, img1, img2);
+    if (kp_count && (kp_count[img1] == 0 || kp_count[img2] == 0)) stt = RPE_PAIR_NO_DESCRIPTORS;
     else if (M < 5) stt = RPE_PAIR_INSUFFICIENT_MATCHES;
     else if (found && !found[pair]) stt = RPE_PAIR_NO_ESSENTIAL;
     else if (found && found[pair] > 1) stt = RPE_PAIR_AMBIGUOUS_ESSENTIAL;
@@ -1141,10 +1144,16 @@ void rpe_launch_structure(rpe_handle *h, int B)
 
 void rpe_launch_pose(rpe_handle *h, int B, bool fused)
 {
-    hipLaunchKernelGGL(recover_pose_kernel, dim3(B), dim3(256), 0, h->stream,
-                       h->d_E, h->d_pts1, h->d_pts2, h->d_m_n, fused ? h->d_found : (const int *)nullptr,
-                       fused ? h->d_kp_count : (const int *)nullptr, h->img2_base ? h->img2_base : B, h->d_K,
-                       h->d_R, h->d_t, h->d_inliers, h->d_status, h->cfg.max_matches);
+    const RpeFeatSrc f = rpe_feat_src(h, B);
+    if (fused && f.tab)
+        hipLaunchKernelGGL(recover_pose_kernel<true>, dim3(B), dim3(256), 0, h->stream,
+                           h->d_E, h->d_pts1, h->d_pts2, h->d_m_n, h->d_found, f.count, f.img2_base, f.tab, h->d_K,
+                           h->d_R, h->d_t, h->d_inliers, h->d_status, h->cfg.max_matches);
+    else
+        hipLaunchKernelGGL(recover_pose_kernel<false>, dim3(B), dim3(256), 0, h->stream,
+                           h->d_E, h->d_pts1, h->d_pts2, h->d_m_n, fused ? h->d_found : (const int *)nullptr,
+                           fused ? f.count : (const int *)nullptr, f.img2_base, (const int2 *)nullptr, h->d_K,
+                           h->d_R, h->d_t, h->d_inliers, h->d_status, h->cfg.max_matches);
 }
 
 // ------------------------------------------------------------ pose refinement

@@ -36,9 +36,9 @@ __device__ __forceinline__ int ham256(const uint4 &a0, const uint4 &a1, const ui
     return d;
 }
 
-template <bool RATIO>
+template <bool RATIO, bool TAB>
 __global__ __launch_bounds__(256) void match_hamming_kernel(const uint8_t *__restrict__ desc, const int *__restrict__ kp_count,
-                                                             const float2 *__restrict__ kp_pt, int img2_base, int kcap,
+                                                             const float2 *__restrict__ kp_pt, int img2_base, const int2 *__restrict__ pair_tab, int kcap,
                                                              int max_matches, double ratio,
                                                              int *__restrict__ m_q, int *__restrict__ m_t, int *__restrict__ m_d,
                                                              int *__restrict__ m_n, float2 *__restrict__ pts1, float2 *__restrict__ pts2)
@@ -49,7 +49,8 @@ __global__ __launch_bounds__(256) void match_hamming_kernel(const uint8_t *__res
     unsigned *s_row = s_best + kcap;                      // kcap entries: the query's own nearest train (second crossCheck pass)
     __shared__ int s_valid;
     const int tid = threadIdx.x, pair = blockIdx.x;
-    const int img1 = pair, img2 = img2_base + pair;
+    int img1, img2;
+    rpe_pair_slots<TAB>(pair_tab, img2_base, pair, img1, img2);
     const int n1 = min(kp_count[img1], kcap), n2 = min(kp_count[img2], kcap);
     for (int i = tid; i < n1; i += 256) { s_best[i] = 0xFFFFFFFFu; if (!RATIO) s_row[i] = 0xFFFFFFFEu; }      // ratio mode: no s_row (and no LDS for it)
     if (tid == 0) s_valid = 0;
@@ -179,9 +180,9 @@ __device__ __forceinline__ v4i_t expand16(unsigned b)
 // SPLIT = true: small batches (the drop-in's estimate() is a batch of ONE pair: a single workgroup walked 2 x 127 x 127 tiles
 // alone, 2.3 ms of a 2.9 ms call).  The rounds of 8 owner tiles are dealt over gridDim.y workgroups per pair, the election
 // words live in HBM (integer atomicMin: order independent), and match_hamming_select_kernel sorts and emits afterwards.
-template <bool SPLIT>
+template <bool SPLIT, bool TAB>
 __global__ __launch_bounds__(MM_NT) void match_hamming_mfma_kernel(const uint8_t *__restrict__ desc, const int *__restrict__ kp_count,
-                                                                    const float2 *__restrict__ kp_pt, int img2_base, int kcap,
+                                                                    const float2 *__restrict__ kp_pt, int img2_base, const int2 *__restrict__ pair_tab, int kcap,
                                                                     int max_matches, int region0,
                                                                     unsigned *__restrict__ g_best, unsigned *__restrict__ g_row,
                                                                     int *__restrict__ m_q, int *__restrict__ m_t, int *__restrict__ m_d,
@@ -196,7 +197,8 @@ __global__ __launch_bounds__(MM_NT) void match_hamming_mfma_kernel(const uint8_t
     unsigned *s_best = SPLIT ? g_best + (long long)pair * kcap : (unsigned *)(s_dyn + region0);          // kcap entries
     unsigned *s_row = SPLIT ? g_row + (long long)pair * kcap : s_best + kcap;     // kcap entries: the query's own nearest train (second crossCheck pass)
     __shared__ int s_valid;
-    const int img1 = pair, img2 = img2_base + pair;
+    int img1, img2;
+    rpe_pair_slots<TAB>(pair_tab, img2_base, pair, img1, img2);
     const int n1 = min(kp_count[img1], kcap), n2 = min(kp_count[img2], kcap);
     if (!SPLIT) for (int i = tid; i < n1; i += MM_NT) { s_best[i] = 0xFFFFFFFFu; s_row[i] = 0xFFFFFFFEu; }      // SPLIT: the host memsets them
     if (tid == 0) s_valid = 0;
@@ -336,16 +338,18 @@ __global__ __launch_bounds__(MM_NT) void match_hamming_mfma_kernel(const uint8_t
 
 
 // sort + top-max_matches + point gather of a SPLIT run (one workgroup per pair; the same steps as the fused epilogue)
+template <bool TAB>
 __global__ __launch_bounds__(MM_NT) void match_hamming_select_kernel(const unsigned *__restrict__ g_best, const unsigned *__restrict__ g_row,
                                                                       const int *__restrict__ kp_count, const float2 *__restrict__ kp_pt,
-                                                                      int img2_base, int kcap, int max_matches,
+                                                                      int img2_base, const int2 *__restrict__ pair_tab, int kcap, int max_matches,
                                                                       int *__restrict__ m_q, int *__restrict__ m_t, int *__restrict__ m_d,
                                                                       int *__restrict__ m_n, float2 *__restrict__ pts1, float2 *__restrict__ pts2)
 {
     extern __shared__ uint4 s_dyn[];
     __shared__ int s_valid;
     const int tid = threadIdx.x, pair = blockIdx.x;
-    const int img1 = pair, img2 = img2_base + pair;
+    int img1, img2;
+    rpe_pair_slots<TAB>(pair_tab, img2_base, pair, img1, img2);
     const int n1 = min(kp_count[img1], kcap);
     const unsigned *s_best = g_best + (long long)pair * kcap, *s_row = g_row + (long long)pair * kcap;
     if (tid == 0) s_valid = 0;
@@ -390,17 +394,26 @@ __global__ __launch_bounds__(MM_NT) void match_hamming_select_kernel(const unsig
     if (tid == 0) m_n[pair] = nm;
 }
 
+// Launches the pair-table instance of a kernel when the feature source carries a table (a pair list), the rule instance
+// otherwise (batch, stream, stage API): the two instances share one signature
+template <typename Kernel, typename... Args>
+static void launch_tab(bool tab, Kernel with_table, Kernel with_rule, dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args... args)
+{
+    hipLaunchKernelGGL(tab ? with_table : with_rule, grid, block, lds, stream, args...);
+}
+
 void rpe_launch_match(rpe_handle *h, int B)
 {
     const int kcap = h->lay.kcap;
+    const RpeFeatSrc f = rpe_feat_src(h, B);                  // the workspace (batch / stream rule) or the frame store (pair table)
     size_t lds = (size_t)QTILE * 32 + (size_t)kcap * 8;       // staging / sort keys + election words + own-nearest words
     if (h->cfg.match_mode == RPE_MATCH_RATIO)                 // the ratio mode has no own-nearest words: 4 bytes per keypoint (<= 64 KB at 8064)
-        hipLaunchKernelGGL((match_hamming_kernel<true>), dim3(B), dim3(256), (size_t)QTILE * 32 + (size_t)kcap * 4, h->stream,
-                           h->d_desc, h->d_kp_count, h->d_kp_pt, h->img2_base ? h->img2_base : B, kcap, h->cfg.max_matches, h->cfg.match_ratio,
+        launch_tab(f.tab, match_hamming_kernel<true, true>, match_hamming_kernel<true, false>, dim3(B), dim3(256), (size_t)QTILE * 32 + (size_t)kcap * 4, h->stream,
+                           f.desc, f.count, f.pt, f.img2_base, f.tab, kcap, h->cfg.max_matches, h->cfg.match_ratio,
                            h->d_m_q, h->d_m_t, h->d_m_d, h->d_m_n, h->d_pts1, h->d_pts2);
     else if (getenv("RPE_MATCH_VALU") && lds <= 65536)    // diagnostic: the vector-ALU crossCheck kernel (A/B runs, parity tests)
-        hipLaunchKernelGGL((match_hamming_kernel<false>), dim3(B), dim3(256), lds, h->stream,
-                           h->d_desc, h->d_kp_count, h->d_kp_pt, h->img2_base ? h->img2_base : B, kcap, h->cfg.max_matches, 0.0,
+        launch_tab(f.tab, match_hamming_kernel<false, true>, match_hamming_kernel<false, false>, dim3(B), dim3(256), lds, h->stream,
+                           f.desc, f.count, f.pt, f.img2_base, f.tab, kcap, h->cfg.max_matches, 0.0,
                            h->d_m_q, h->d_m_t, h->d_m_d, h->d_m_n, h->d_pts1, h->d_pts2);
     else {
         // first LDS region: max(staging 16 KB + 256 B of packed words + 2 B per scanned descriptor, 4 B x sort size)
@@ -415,16 +428,16 @@ void rpe_launch_match(rpe_handle *h, int B)
         if (split > 1 || !lds_fits) {
             hipMemsetAsync(h->d_hm_best, 0xFF, sizeof(unsigned) * (size_t)B * kcap, h->stream);
             hipMemsetAsync(h->d_hm_row, 0xFE, sizeof(unsigned) * (size_t)B * kcap, h->stream);
-            hipLaunchKernelGGL((match_hamming_mfma_kernel<true>), dim3(B, split), dim3(MM_NT), r0 * 16, h->stream,
-                               h->d_desc, h->d_kp_count, h->d_kp_pt, h->img2_base ? h->img2_base : B, kcap, h->cfg.max_matches, (int)r0,
+            launch_tab(f.tab, match_hamming_mfma_kernel<true, true>, match_hamming_mfma_kernel<true, false>, dim3(B, split), dim3(MM_NT), r0 * 16, h->stream,
+                               f.desc, f.count, f.pt, f.img2_base, f.tab, kcap, h->cfg.max_matches, (int)r0,
                                h->d_hm_best, h->d_hm_row, h->d_m_q, h->d_m_t, h->d_m_d, h->d_m_n, h->d_pts1, h->d_pts2);
-            hipLaunchKernelGGL(match_hamming_select_kernel, dim3(B), dim3(MM_NT), (size_t)sortP * 4, h->stream,
-                               (const unsigned *)h->d_hm_best, (const unsigned *)h->d_hm_row, h->d_kp_count, h->d_kp_pt,
-                               h->img2_base ? h->img2_base : B, kcap, h->cfg.max_matches,
+            launch_tab(f.tab, match_hamming_select_kernel<true>, match_hamming_select_kernel<false>, dim3(B), dim3(MM_NT), (size_t)sortP * 4, h->stream,
+                               (const unsigned *)h->d_hm_best, (const unsigned *)h->d_hm_row, f.count, f.pt,
+                               f.img2_base, f.tab, kcap, h->cfg.max_matches,
                                h->d_m_q, h->d_m_t, h->d_m_d, h->d_m_n, h->d_pts1, h->d_pts2);
         } else
-            hipLaunchKernelGGL((match_hamming_mfma_kernel<false>), dim3(B), dim3(MM_NT), r0 * 16 + (size_t)kcap * 8, h->stream,
-                               h->d_desc, h->d_kp_count, h->d_kp_pt, h->img2_base ? h->img2_base : B, kcap, h->cfg.max_matches, (int)r0,
+            launch_tab(f.tab, match_hamming_mfma_kernel<false, true>, match_hamming_mfma_kernel<false, false>, dim3(B), dim3(MM_NT), r0 * 16 + (size_t)kcap * 8, h->stream,
+                               f.desc, f.count, f.pt, f.img2_base, f.tab, kcap, h->cfg.max_matches, (int)r0,
                                (unsigned *)nullptr, (unsigned *)nullptr, h->d_m_q, h->d_m_t, h->d_m_d, h->d_m_n, h->d_pts1, h->d_pts2);
     }
 }
@@ -468,15 +481,17 @@ __device__ __forceinline__ unsigned dot_u8(const uint4 *q, const uint4 (&t)[NQ])
 
 // Vector-ALU form.  Workgroup = (256 owned descriptors, pair); the scanned descriptors stream through LDS.
 // MODE 0: owned = trains (NNq), MODE 2: owned = queries (NNt), MODE 1: Lowe ratio (extension; owned = queries).
-template <int NQ, int MODE>
+template <int NQ, int MODE, bool TAB>
 __global__ __launch_bounds__(256) void match_l2_nearest_kernel(const uint8_t *__restrict__ desc, const int *__restrict__ kp_count,
-                                                                int img2_base, int kcap, double ratio, unsigned long long *__restrict__ best)
+                                                                int img2_base, const int2 *__restrict__ pair_tab, int kcap, double ratio,
+                                                                unsigned long long *__restrict__ best)
 {
     constexpr int DIM = NQ * 16;
     __shared__ uint4 s_q[L2_QTILE * NQ];                                        // 32 KB (SIFT) / 8 KB (ORB)
     __shared__ unsigned s_qn[L2_QTILE];                                         // |q|^2 of the tile
     const int tid = threadIdx.x, pair = blockIdx.y, tc = blockIdx.x * 256;
-    const int img1 = pair, img2 = img2_base + pair;
+    int img1, img2;
+    rpe_pair_slots<TAB>(pair_tab, img2_base, pair, img1, img2);
     const int n1 = min(kp_count[img1], kcap), n2 = min(kp_count[img2], kcap);
     constexpr bool RATIO = MODE == 1, QOWN = MODE != 0;
     const int n_own = QOWN ? n1 : n2, n_scan = QOWN ? n2 : n1;
@@ -568,9 +583,9 @@ __global__ __launch_bounds__(256) void match_l2_norms_kernel(const uint8_t *__re
 // row has the lower index.  That test runs on the tile minimum; the exact (f32 distance, index) comparison of the
 // 16 rows runs only in a wave where some lane passes it.
 #define L2M_PF 3
-template <int KS>
+template <int KS, bool TAB>
 __global__ __launch_bounds__(256) void match_l2_mfma_kernel(const uint8_t *__restrict__ desc, const int2 *__restrict__ norms,
-                                                             const int *__restrict__ kp_count, int img2_base, int kcap,
+                                                             const int *__restrict__ kp_count, int img2_base, const int2 *__restrict__ pair_tab, int kcap,
                                                              unsigned long long *__restrict__ nn_t, unsigned long long *__restrict__ nn_q)
 {
     constexpr int DIM = KS * 32;
@@ -578,7 +593,8 @@ __global__ __launch_bounds__(256) void match_l2_mfma_kernel(const uint8_t *__res
     __shared__ __attribute__((aligned(16))) int s_qn[2][32];
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, h = lane >> 5, col = lane & 31;
     const int pair = blockIdx.z >> 1, pass = blockIdx.z & 1;
-    const int img1 = pair, img2 = img2_base + pair;
+    int img1, img2;
+    rpe_pair_slots<TAB>(pair_tab, img2_base, pair, img1, img2);
     const int n1 = min(kp_count[img1], kcap), n2 = min(kp_count[img2], kcap);
     // pass 0: the queries own the columns and find their nearest train (NNt); pass 1: the trains find their nearest query
     const int img_own = pass ? img2 : img1, img_scan = pass ? img1 : img2;
@@ -680,16 +696,18 @@ __global__ __launch_bounds__(256) void match_l2_mfma_kernel(const uint8_t *__res
 // Kernel 2: workgroup = pair: stable sort of the (distance, queryIdx) keys of the surviving matches, first max_matches,
 // point gather.  nn_t[i] = query i's nearest train; nn_q (crossCheck only, nullptr for the ratio mode) = train j's
 // nearest query: the match survives iff nn_q[nn_t[i]] names i
+template <bool TAB>
 __global__ __launch_bounds__(256) void match_l2_select_kernel(const unsigned long long *__restrict__ nn_t, const unsigned long long *__restrict__ nn_q,
                                                                const int *__restrict__ kp_count,
-                                                               const float2 *__restrict__ kp_pt, int img2_base, int kcap, int max_matches,
+                                                               const float2 *__restrict__ kp_pt, int img2_base, const int2 *__restrict__ pair_tab, int kcap, int max_matches,
                                                                int *__restrict__ m_q, int *__restrict__ m_t, float *__restrict__ m_d,
                                                                int *__restrict__ m_n, float2 *__restrict__ pts1, float2 *__restrict__ pts2)
 {
     extern __shared__ unsigned long long s_key[];          // sortP <= 16384 keys (128 KB)
     __shared__ int s_valid;
     const int tid = threadIdx.x, pair = blockIdx.x;
-    const int img1 = pair, img2 = img2_base + pair;
+    int img1, img2;
+    rpe_pair_slots<TAB>(pair_tab, img2_base, pair, img1, img2);
     const int n1 = min(kp_count[img1], kcap);
     const unsigned long long *bp = nn_t + (long long)pair * kcap;
     if (tid == 0) s_valid = 0;
@@ -732,10 +750,21 @@ __global__ __launch_bounds__(256) void match_l2_select_kernel(const unsigned lon
     if (tid == 0) m_n[pair] = nm;
 }
 
+// { |u|^2, |u|^2 + 2 sum(u) } of the descriptors of workspace images [0, n_img): once per batch / stream, and once per
+// rpe_frames_put* (the frame store keeps the words next to the descriptors; a pair list never recomputes them)
+void rpe_launch_l2_norms(rpe_handle *h, int n_img)
+{
+    const int kcap = h->lay.kcap;
+    const dim3 gn((kcap + 255) / 256, n_img);
+    if (h->desc_bytes == 128) hipLaunchKernelGGL(match_l2_norms_kernel<8>, gn, dim3(256), 0, h->stream, h->d_desc, h->d_kp_count, kcap, (int2 *)h->d_m_norm);
+    else                      hipLaunchKernelGGL(match_l2_norms_kernel<2>, gn, dim3(256), 0, h->stream, h->d_desc, h->d_kp_count, kcap, (int2 *)h->d_m_norm);
+}
+
 void rpe_launch_match_l2(rpe_handle *h, int B)
 {
     const int kcap = h->lay.kcap;
-    const int img2_base = h->img2_base ? h->img2_base : B;
+    const RpeFeatSrc f = rpe_feat_src(h, B);                  // the workspace (batch / stream rule) or the frame store (pair table)
+    const int img2_base = f.img2_base;
     // d_m_best2 = NNt (per query; the ratio mode's only list), d_m_best = NNq (per train)
     hipMemsetAsync(h->d_m_best2, 0xFF, sizeof(unsigned long long) * (size_t)B * kcap, h->stream);
     const bool rt = h->cfg.match_mode == RPE_MATCH_RATIO;
@@ -743,30 +772,29 @@ void rpe_launch_match_l2(rpe_handle *h, int B)
     const bool sift = h->desc_bytes == 128;
     if (rt || getenv("RPE_MATCH_VALU")) {
         const dim3 grid((kcap + 255) / 256, B);
-#define L2_LAUNCH(NQ, MODE, DST) hipLaunchKernelGGL((match_l2_nearest_kernel<NQ, MODE>), grid, dim3(256), 0, h->stream, \
-                                                    h->d_desc, h->d_kp_count, img2_base, kcap, h->cfg.match_ratio, DST)
+#define L2_LAUNCH(NQ, MODE, DST) launch_tab(f.tab, match_l2_nearest_kernel<NQ, MODE, true>, match_l2_nearest_kernel<NQ, MODE, false>, grid, dim3(256), 0, h->stream, \
+                                                    f.desc, f.count, img2_base, f.tab, kcap, h->cfg.match_ratio, DST)
         if (sift) { if (rt) L2_LAUNCH(8, 1, h->d_m_best2); else { L2_LAUNCH(8, 0, h->d_m_best); L2_LAUNCH(8, 2, h->d_m_best2); } }
         else      { if (rt) L2_LAUNCH(2, 1, h->d_m_best2); else { L2_LAUNCH(2, 0, h->d_m_best); L2_LAUNCH(2, 2, h->d_m_best2); } }
 #undef L2_LAUNCH
     } else {
-        const int n_img = img2_base + B;                       // images [0, B) and [img2_base, img2_base + B) (a stream: B + 1 frames)
-        const dim3 gn((kcap + 255) / 256, n_img);
-        if (sift) hipLaunchKernelGGL(match_l2_norms_kernel<8>, gn, dim3(256), 0, h->stream, h->d_desc, h->d_kp_count, kcap, (int2 *)h->d_m_norm);
-        else      hipLaunchKernelGGL(match_l2_norms_kernel<2>, gn, dim3(256), 0, h->stream, h->d_desc, h->d_kp_count, kcap, (int2 *)h->d_m_norm);
+        // images [0, B) and [img2_base, img2_base + B) (a stream: B + 1 frames); the frame store holds its slots' words already
+        if (!f.tab) rpe_launch_l2_norms(h, img2_base + B);
         // scanned tiles dealt over `split` workgroups until ~1024 workgroups are in flight (a single pair included)
         const int chunks = (kcap + 127) / 128;
         int split = (1024 + chunks * 2 * B - 1) / (chunks * 2 * B);
         split = split < 1 ? 1 : split > 8 ? 8 : split;
         const dim3 grid(chunks, split, 2 * B);
-        if (sift) hipLaunchKernelGGL(match_l2_mfma_kernel<4>, grid, dim3(256), 0, h->stream, h->d_desc, (const int2 *)h->d_m_norm, h->d_kp_count, img2_base, kcap, h->d_m_best2, h->d_m_best);
-        else      hipLaunchKernelGGL(match_l2_mfma_kernel<1>, grid, dim3(256), 0, h->stream, h->d_desc, (const int2 *)h->d_m_norm, h->d_kp_count, img2_base, kcap, h->d_m_best2, h->d_m_best);
+        if (sift) launch_tab(f.tab, match_l2_mfma_kernel<4, true>, match_l2_mfma_kernel<4, false>, grid, dim3(256), 0, h->stream, f.desc, f.norm, f.count, img2_base, f.tab, kcap, h->d_m_best2, h->d_m_best);
+        else      launch_tab(f.tab, match_l2_mfma_kernel<1, true>, match_l2_mfma_kernel<1, false>, grid, dim3(256), 0, h->stream, f.desc, f.norm, f.count, img2_base, f.tab, kcap, h->d_m_best2, h->d_m_best);
     }
     int sortP = 64;
     while (sortP < kcap) sortP <<= 1;
     if (sizeof(unsigned long long) * (size_t)sortP > 65536)   // more than 8128 keypoints per image: up to 128 KB of the CU's 160 KB
-        hipFuncSetAttribute((const void *)match_l2_select_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(unsigned long long) * (size_t)sortP));
-    hipLaunchKernelGGL(match_l2_select_kernel, dim3(B), dim3(256), sizeof(unsigned long long) * (size_t)sortP, h->stream,
+        hipFuncSetAttribute(f.tab ? (const void *)match_l2_select_kernel<true> : (const void *)match_l2_select_kernel<false>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(unsigned long long) * (size_t)sortP));
+    launch_tab(f.tab, match_l2_select_kernel<true>, match_l2_select_kernel<false>, dim3(B), dim3(256), sizeof(unsigned long long) * (size_t)sortP, h->stream,
                        (const unsigned long long *)h->d_m_best2, rt ? (const unsigned long long *)nullptr : (const unsigned long long *)h->d_m_best,
-                       h->d_kp_count, h->d_kp_pt, img2_base, kcap, h->cfg.max_matches,
+                       f.count, f.pt, img2_base, f.tab, kcap, h->cfg.max_matches,
                        h->d_m_q, h->d_m_t, (float *)h->d_m_d, h->d_m_n, h->d_pts1, h->d_pts2);
 }

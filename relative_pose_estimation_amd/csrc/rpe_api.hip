@@ -7,6 +7,7 @@
 #include <string.h>
 #include <stdio.h>
 #include <stdlib.h>
+#include <algorithm>
 
 void rpe_orb_upload_disc(const signed char *disc, int n);
 
@@ -388,6 +389,13 @@ extern "C" int rpe_create(const rpe_config *cfg, rpe_handle **out)
     return RPE_OK;
 }
 
+static void frames_free(rpe_handle::FrameStore &fs)
+{
+    void *ptrs[] = {fs.d_desc, fs.d_kp_pt, fs.d_norm, fs.d_count, fs.d_ovf};
+    for (void *p : ptrs) if (p) hipFree(p);
+    fs = rpe_handle::FrameStore();
+}
+
 extern "C" void rpe_destroy(rpe_handle *h)
 {
     if (!h) return;
@@ -402,6 +410,10 @@ extern "C" void rpe_destroy(rpe_handle *h)
                     h->d_nmodels, h->d_mask, h->d_pose_mask, h->d_points, h->d_ref_R, h->d_ref_t, h->d_ref_rms, h->d_ref_R0, h->d_ref_t0, h->d_ref_inl, h->d_ref_info, h->d_E, h->d_K, h->d_m_best, h->d_m_best2, h->d_m_norm, h->d_hm_best, h->d_hm_row, h->d_ovf, h->d_corner, h->d_corner_count, h->d_kp_lvl_count};
     for (void *p : ptrs) if (p) hipFree(p);
     if (h->h_resblk) hipHostFree(h->h_resblk);
+    frames_free(h->fs);
+    if (h->d_pairtab) hipFree(h->d_pairtab);
+    if (h->h_pairtab) hipHostFree(h->h_pairtab);
+    for (int i = 0; i < RPE_TAB_RING; ++i) if (h->ev_tab[i]) hipEventDestroy(h->ev_tab[i]);
     for (void *p : h->user_allocs) hipFree(p);
     for (int i = 0; i <= RPE_STAGE_COUNT; ++i) if (h->ev[i]) hipEventDestroy(h->ev[i]);
     for (int c = 0; c < 8; ++c) if (h->ev_up[c]) hipEventDestroy(h->ev_up[c]);
@@ -550,8 +562,9 @@ static int run_pairs(rpe_handle *h, const uint8_t *d_a, const uint8_t *d_b, int 
     } guard{h};
     h->img2_base = img2_base;
     h->last_pairs = pairs; h->last_img2_base = img2_base;
-    h->last_chunked = false;
+    h->last_chunked = false; h->last_from_store = false;
     h->structure_valid = false;
+    h->ev_first = 0;
     int rc;
     if (h->cfg.feature_method == RPE_FEATURE_SIFT) {
         if ((rc = rpe_sift_run(h, d_a, d_b, na, nb)) != RPE_OK) return rc;             // records PYRAMID .. DESCRIBE
@@ -587,7 +600,7 @@ extern "C" int rpe_enqueue_batch_device(rpe_handle *h, const uint8_t *d_imgs1, c
         return run_pairs(h, d_imgs1, d_imgs2, B, B, B, B);
     for (auto &g : h->graphs)
         if (g.a == d_imgs1 && g.b == d_imgs2 && g.B == B) {
-            h->last_pairs = B; h->last_img2_base = B; h->last_chunked = false; h->structure_valid = true;
+            h->last_pairs = B; h->last_img2_base = B; h->last_chunked = false; h->last_from_store = false; h->structure_valid = true;
             h->lay.in_na = B; h->level0_slots = 2 * B;
             const bool direct = h->lay.lv[0].pitch == h->cfg.width && (((uintptr_t)d_imgs1 | (uintptr_t)d_imgs2) & 15) == 0;
             h->lay.in_a = direct ? d_imgs1 : nullptr; h->lay.in_b = direct ? d_imgs2 : nullptr;
@@ -736,6 +749,18 @@ extern "C" int rpe_fetch_overflow(rpe_handle *h, int n_pairs, uint32_t *flags)
         return RPE_OK;
     }
     if (n_pairs > h->last_pairs) { h->err = "rpe_fetch_overflow: more pairs than the last batch had"; return RPE_ERR_INVALID; }
+    if (h->last_from_store) {
+        // a pair list: the flags live with the frames (a put since then cleared last_pairs, a resize of the store last_tab)
+        if (h->last_tab.size() < (size_t)2 * n_pairs) { h->err = "rpe_fetch_overflow: the frame store was resized since the pair list"; return RPE_ERR_INVALID; }
+        int lo = h->last_tab[0], hi = lo;
+        for (int i = 0; i < 2 * n_pairs; ++i) { lo = std::min(lo, h->last_tab[i]); hi = std::max(hi, h->last_tab[i]); }
+        if (lo < 0 || hi >= h->fs.cap) { h->err = "rpe_fetch_overflow: the pair list names slots outside the store"; return RPE_ERR_INVALID; }
+        std::vector<unsigned> ov((size_t)(hi - lo + 1));       // the slots the list names, not the whole store
+        HIPCHK(h, hipMemcpyAsync(ov.data(), h->fs.d_ovf + lo, sizeof(unsigned) * ov.size(), hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipStreamSynchronize(h->stream));
+        for (int p = 0; p < n_pairs; ++p) flags[p] = ov[(size_t)(h->last_tab[2 * p] - lo)] | ov[(size_t)(h->last_tab[2 * p + 1] - lo)];
+        return RPE_OK;
+    }
     const int nimg = h->last_img2_base + n_pairs;
     std::vector<unsigned> ov((size_t)nimg);
     HIPCHK(h, hipMemcpyAsync(ov.data(), h->d_ovf, sizeof(unsigned) * (size_t)nimg, hipMemcpyDeviceToHost, h->stream));
@@ -896,6 +921,241 @@ extern "C" int rpe_refine_poses(rpe_handle *h, int B, int max_iters, double *R, 
     int rc = refine_alloc(h);
     if (rc) return rc;
     return refine_run(h, B, max_iters, true, R, t, inliers, info, rms);
+}
+
+// ---------------------------------------------------------------- frame store
+// rpe_frames_* / rpe_enqueue_pairs (NOT in the reference): extraction separated from pairing.  A put extracts n frames in
+// the workspace slots [0, n) exactly as a stream does and one scatter kernel moves what the matchers and the status test
+// read -- count, flags, kp_pt, descriptors, and the L2 matcher's norm words -- to the frames' store slots.  A pair list
+// then launches the batch's own matcher / RANSAC / pose kernels with a (slot1, slot2) table in place of the
+// (pair, img2_base + pair) rule.
+
+// Workgroup (x, i): image i of the workspace -> store slot slots[i]; only the image's `count` rows move, 16 bytes per lane
+// (the descriptor rows are 32 or 128 bytes; kp_pt and the norm words are 8-byte records: pairs of them when kcap is even,
+// which keeps every slot 16-byte aligned, one by one otherwise).
+__global__ __launch_bounds__(256) void frames_scatter_kernel(const uint8_t *__restrict__ desc, const float2 *__restrict__ kp_pt,
+                                                              const int2 *__restrict__ norm, const int *__restrict__ kp_count,
+                                                              const unsigned *__restrict__ ovf, const int *__restrict__ slots,
+                                                              int kcap, int desc_bytes, uint8_t *__restrict__ s_desc,
+                                                              float2 *__restrict__ s_pt, int2 *__restrict__ s_norm,
+                                                              int *__restrict__ s_count, unsigned *__restrict__ s_ovf)
+{
+    const int img = blockIdx.y, slot = slots[img];
+    const int cnt = kp_count[img], n = min(cnt, kcap);
+    const int t0 = blockIdx.x * 256 + threadIdx.x, step = gridDim.x * 256;
+    if (t0 == 0) { s_count[slot] = cnt; s_ovf[slot] = ovf[img]; }
+    const long long src = (long long)img * kcap, dst = (long long)slot * kcap;
+    const uint4 *d_in = (const uint4 *)(desc + src * desc_bytes);
+    uint4 *d_out = (uint4 *)(s_desc + dst * desc_bytes);
+    const int nd = n * (desc_bytes >> 4);
+    for (int i = t0; i < nd; i += step) d_out[i] = d_in[i];
+    if ((kcap & 1) == 0) {
+        const int n2 = n >> 1;
+        const uint4 *p_in = (const uint4 *)(kp_pt + src); uint4 *p_out = (uint4 *)(s_pt + dst);
+        for (int i = t0; i < n2; i += step) p_out[i] = p_in[i];
+        if ((n & 1) && t0 == 0) s_pt[dst + n - 1] = kp_pt[src + n - 1];
+        if (norm) {
+            const uint4 *n_in = (const uint4 *)(norm + src); uint4 *n_out = (uint4 *)(s_norm + dst);
+            for (int i = t0; i < n2; i += step) n_out[i] = n_in[i];
+            if ((n & 1) && t0 == 0) s_norm[dst + n - 1] = norm[src + n - 1];
+        }
+    } else {
+        for (int i = t0; i < n; i += step) s_pt[dst + i] = kp_pt[src + i];
+        if (norm) for (int i = t0; i < n; i += step) s_norm[dst + i] = norm[src + i];
+    }
+}
+
+// the norm words are read by match_l2_mfma_kernel only: the crossCheck matcher of NORM_L2 handles (the Lowe-ratio matcher
+// runs on the vector ALU and computes its own)
+static bool frames_keep_norms(const rpe_handle *h) { return h->cfg.norm_type == RPE_NORM_L2 && h->cfg.match_mode != RPE_MATCH_RATIO; }
+
+extern "C" int rpe_frames_capacity(const rpe_handle *h) { return h ? h->fs.cap : 0; }
+
+extern "C" int rpe_frames_reserve(rpe_handle *h, int n_slots)
+{
+    if (!h) return RPE_ERR_INVALID;
+    if (n_slots < 0 || n_slots > (1 << 24)) { h->err = "rpe_frames_reserve: n_slots must be 0 ... 16777216"; return RPE_ERR_INVALID; }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (n_slots == h->fs.cap) return RPE_OK;
+    HIPCHK(h, hipStreamSynchronize(h->stream));            // nothing in flight reads the store that is about to go
+    h->last_tab.clear();                                   // slot numbers of the last pair list: rpe_fetch_overflow refuses from here on
+    if (n_slots == 0) { frames_free(h->fs); return RPE_OK; }
+    const size_t kcap = (size_t)h->lay.kcap, db = (size_t)h->desc_bytes, N = (size_t)n_slots;
+    const bool l2 = frames_keep_norms(h);
+    rpe_handle::FrameStore nf;
+    bool ok = hipMalloc((void **)&nf.d_desc, N * kcap * db) == hipSuccess && hipMalloc((void **)&nf.d_kp_pt, N * kcap * sizeof(float2)) == hipSuccess &&
+              (!l2 || hipMalloc((void **)&nf.d_norm, N * kcap * sizeof(int2)) == hipSuccess) &&
+              hipMalloc((void **)&nf.d_count, N * sizeof(int)) == hipSuccess && hipMalloc((void **)&nf.d_ovf, N * sizeof(unsigned)) == hipSuccess;
+    const size_t keep = (size_t)(h->fs.cap < n_slots ? h->fs.cap : n_slots);
+    ok = ok && hipMemsetAsync(nf.d_count, 0, N * sizeof(int), h->stream) == hipSuccess && hipMemsetAsync(nf.d_ovf, 0, N * sizeof(unsigned), h->stream) == hipSuccess;
+    if (ok && keep) {
+        ok = hipMemcpyAsync(nf.d_desc, h->fs.d_desc, keep * kcap * db, hipMemcpyDeviceToDevice, h->stream) == hipSuccess &&
+             hipMemcpyAsync(nf.d_kp_pt, h->fs.d_kp_pt, keep * kcap * sizeof(float2), hipMemcpyDeviceToDevice, h->stream) == hipSuccess &&
+             (!l2 || hipMemcpyAsync(nf.d_norm, h->fs.d_norm, keep * kcap * sizeof(int2), hipMemcpyDeviceToDevice, h->stream) == hipSuccess) &&
+             hipMemcpyAsync(nf.d_count, h->fs.d_count, keep * sizeof(int), hipMemcpyDeviceToDevice, h->stream) == hipSuccess &&
+             hipMemcpyAsync(nf.d_ovf, h->fs.d_ovf, keep * sizeof(unsigned), hipMemcpyDeviceToDevice, h->stream) == hipSuccess;
+    }
+    ok = ok && hipStreamSynchronize(h->stream) == hipSuccess;
+    if (!ok) {
+        const hipError_t e = hipGetLastError();
+        char b[256];
+        snprintf(b, sizeof(b), "rpe_frames_reserve: could not build a store of %d slots (%s); the old store of %d slots is kept", n_slots, hipGetErrorString(e), h->fs.cap);
+        frames_free(nf);
+        h->err = b;
+        return RPE_ERR_HIP;
+    }
+    nf.cap = n_slots;
+    nf.filled.assign(N, 0);
+    for (size_t i = 0; i < keep; ++i) nf.filled[i] = h->fs.filled[i];
+    rpe_handle::FrameStore old = h->fs;
+    h->fs = nf;
+    frames_free(old);
+    return RPE_OK;
+}
+
+// The caller's slot arrays go through a ring of pinned buffers (the caller may reuse its arrays as soon as the call
+// returns, and the host may run RPE_TAB_RING calls ahead of the stream) and from there to d_pairtab on the handle's stream
+static int upload_table(rpe_handle *h, const int32_t *a, const int32_t *b, int n)
+{
+    const size_t per = (size_t)2 * h->cfg.max_batch;                 // ints: 2*max_batch put slots or max_batch (slot1, slot2) entries
+    if (!h->h_pairtab) {
+        HIPCHK(h, hipHostMalloc((void **)&h->h_pairtab, RPE_TAB_RING * per * sizeof(int)));
+        HIPCHK(h, hipMalloc((void **)&h->d_pairtab, per * sizeof(int)));
+        for (int i = 0; i < RPE_TAB_RING; ++i) HIPCHK(h, hipEventCreateWithFlags(&h->ev_tab[i], hipEventDisableTiming));
+    }
+    const int r = h->tab_next;
+    h->tab_next = (r + 1) % RPE_TAB_RING;
+    HIPCHK(h, hipEventSynchronize(h->ev_tab[r]));                     // the upload that last used this piece has run
+    int *dst = h->h_pairtab + (size_t)r * per;
+    if (b) for (int i = 0; i < n; ++i) { dst[2 * i] = a[i]; dst[2 * i + 1] = b[i]; }
+    else memcpy(dst, a, sizeof(int) * (size_t)n);
+    HIPCHK(h, hipMemcpyAsync(h->d_pairtab, dst, sizeof(int) * (size_t)(b ? 2 * n : n), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipEventRecord(h->ev_tab[r], h->stream));
+    return RPE_OK;
+}
+
+static int frames_check_put(rpe_handle *h, const void *frames, int n, const int32_t *slots)
+{
+    if (!h || !frames || !slots || n < 1) { if (h) h->err = "rpe_frames_put: null argument or n < 1"; return RPE_ERR_INVALID; }
+    if (n > h->n_img_cap) { h->err = "rpe_frames_put: more than 2*max_batch frames in one call"; return RPE_ERR_CAPACITY; }
+    if (h->fs.cap == 0) { h->err = "rpe_frames_put: no frame store (rpe_frames_reserve)"; return RPE_ERR_INVALID; }
+    std::vector<int32_t> s(slots, slots + n);
+    std::sort(s.begin(), s.end());
+    if (s.front() < 0 || s.back() >= h->fs.cap) { h->err = "rpe_frames_put: slot outside the store"; return RPE_ERR_INVALID; }
+    for (int i = 1; i < n; ++i) if (s[i] == s[i - 1]) { h->err = "rpe_frames_put: a slot appears twice in one put"; return RPE_ERR_INVALID; }
+    return RPE_OK;
+}
+
+// extraction of na + nb images (workspace slots [0, na + nb), as a stream / the stage API place them) + scatter
+static int frames_put_run(rpe_handle *h, const uint8_t *d_a, const uint8_t *d_b, int na, int nb, const int32_t *slots)
+{
+    const int n = na + nb;
+    int rc = upload_table(h, slots, nullptr, n);
+    if (rc) return rc;
+    // the workspace's per-image arrays are overwritten: what described "the last batch" through them is gone
+    h->structure_valid = false; h->last_pairs = 0; h->last_from_store = false; h->last_chunked = false;
+    h->ev_valid = false;
+    if (h->cfg.feature_method == RPE_FEATURE_SIFT) rc = rpe_sift_run(h, d_a, d_b, na, nb);
+    else rc = run_orb(h, d_a, d_b, na, nb);
+    if (rc) return rc;
+    const bool l2 = frames_keep_norms(h);
+    if (l2) rpe_launch_l2_norms(h, n);
+    const int rows = h->lay.kcap * (h->desc_bytes >> 4);               // 16-byte pieces of a full image's descriptors
+    const int gx = rows >= 65536 ? 32 : rows >= 8192 ? 8 : 2;
+    hipLaunchKernelGGL(frames_scatter_kernel, dim3(gx, n), dim3(256), 0, h->stream,
+                       (const uint8_t *)h->d_desc, (const float2 *)h->d_kp_pt, l2 ? (const int2 *)h->d_m_norm : (const int2 *)nullptr,
+                       (const int *)h->d_kp_count, (const unsigned *)h->d_ovf, (const int *)h->d_pairtab, h->lay.kcap, h->desc_bytes,
+                       h->fs.d_desc, h->fs.d_kp_pt, h->fs.d_norm, h->fs.d_count, h->fs.d_ovf);
+    HIPCHK(h, hipGetLastError());
+    for (int i = 0; i < n; ++i) h->fs.filled[(size_t)slots[i]] = 1;
+    return RPE_OK;
+}
+
+extern "C" int rpe_frames_put_device(rpe_handle *h, const uint8_t *d_frames, int n, const int32_t *slots)
+{
+    int rc = frames_check_put(h, d_frames, n, slots);
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    return frames_put_run(h, d_frames, d_frames, n, 0, slots);
+}
+
+extern "C" int rpe_frames_put(rpe_handle *h, const uint8_t *h_frames, int n, const int32_t *slots)
+{
+    int rc = frames_check_put(h, h_frames, n, slots);
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const size_t img = (size_t)h->cfg.width * h->cfg.height;
+    const int na = n < h->cfg.max_batch ? n : h->cfg.max_batch, nb = n - na;
+    HIPCHK(h, hipMemcpyAsync(h->d_stage1, h_frames, img * na, hipMemcpyHostToDevice, h->stream));
+    if (nb) HIPCHK(h, hipMemcpyAsync(h->d_stage2, h_frames + img * na, img * nb, hipMemcpyHostToDevice, h->stream));
+    return frames_put_run(h, h->d_stage1, h->d_stage2, na, nb, slots);
+}
+
+extern "C" int rpe_frames_info(rpe_handle *h, int n, const int32_t *slots, int32_t *counts, uint32_t *flags)
+{
+    if (!h || !slots || n < 1) { if (h) h->err = "rpe_frames_info: null argument or n < 1"; return RPE_ERR_INVALID; }
+    if (h->fs.cap == 0) { h->err = "rpe_frames_info: no frame store (rpe_frames_reserve)"; return RPE_ERR_INVALID; }
+    for (int i = 0; i < n; ++i) if (slots[i] < 0 || slots[i] >= h->fs.cap) { h->err = "rpe_frames_info: slot outside the store"; return RPE_ERR_INVALID; }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    int lo = slots[0], hi = slots[0];
+    for (int i = 1; i < n; ++i) { lo = std::min(lo, (int)slots[i]); hi = std::max(hi, (int)slots[i]); }
+    const size_t span = (size_t)(hi - lo + 1);                 // the range the call names, not the whole store
+    std::vector<int> cnt(span);
+    std::vector<unsigned> ov(span);
+    HIPCHK(h, hipMemcpyAsync(cnt.data(), h->fs.d_count + lo, sizeof(int) * span, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(ov.data(), h->fs.d_ovf + lo, sizeof(unsigned) * span, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int i = 0; i < n; ++i) {
+        const size_t s = (size_t)slots[i];
+        const bool f = h->fs.filled[s] != 0;
+        if (counts) counts[i] = f ? cnt[s - lo] : -1;
+        if (flags) flags[i] = f ? ov[s - lo] : 0u;
+    }
+    return RPE_OK;
+}
+
+extern "C" int rpe_enqueue_pairs(rpe_handle *h, const int32_t *slot1, const int32_t *slot2, int P, const double K[9])
+{
+    if (!h || !slot1 || !slot2 || !K || P < 1) { if (h) h->err = "rpe_enqueue_pairs: null argument or P < 1"; return RPE_ERR_INVALID; }
+    if (P > h->cfg.max_batch) { h->err = "rpe_enqueue_pairs: pair list exceeds max_batch"; return RPE_ERR_CAPACITY; }
+    if (h->fs.cap == 0) { h->err = "rpe_enqueue_pairs: no frame store (rpe_frames_reserve)"; return RPE_ERR_INVALID; }
+    for (int p = 0; p < P; ++p) {
+        if (slot1[p] < 0 || slot1[p] >= h->fs.cap || slot2[p] < 0 || slot2[p] >= h->fs.cap) { h->err = "rpe_enqueue_pairs: slot outside the store"; return RPE_ERR_INVALID; }
+        if (!h->fs.filled[(size_t)slot1[p]] || !h->fs.filled[(size_t)slot2[p]]) { h->err = "rpe_enqueue_pairs: a pair names an empty slot"; return RPE_ERR_INVALID; }
+    }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    int rc = set_K(h, K);
+    if (rc) return rc;
+    if ((rc = upload_table(h, slot1, slot2, P)) != RPE_OK) return rc;
+    struct Guard {                          // the launchers read h->pair_tab; never leave it behind for a batch
+        rpe_handle *h; ~Guard() { h->pair_tab = nullptr; }
+    } guard{h};
+    h->pair_tab = (const int2 *)h->d_pairtab;
+    h->last_pairs = P; h->last_img2_base = 0;
+    h->last_chunked = false; h->last_from_store = true;
+    h->last_tab.resize((size_t)2 * P);
+    for (int p = 0; p < P; ++p) { h->last_tab[2 * p] = slot1[p]; h->last_tab[2 * p + 1] = slot2[p]; }
+    h->structure_valid = false;
+    h->ev_first = RPE_STAGE_MATCH;
+    MARK(h, RPE_STAGE_MATCH);
+    if (h->cfg.norm_type == RPE_NORM_L2) rpe_launch_match_l2(h, P);
+    else rpe_launch_match(h, P);
+    MARK(h, RPE_STAGE_RANSAC);
+    rpe_launch_ransac(h, P, false);
+    MARK(h, RPE_STAGE_POSE);
+    rpe_launch_pose(h, P, true);
+    if (h->profiling) { hipEventRecord(h->ev[RPE_STAGE_COUNT], h->stream); h->ev_valid = true; }
+    HIPCHK(h, hipGetLastError());
+    h->structure_valid = true;
+    return RPE_OK;
+}
+
+extern "C" int rpe_estimate_pairs(rpe_handle *h, const int32_t *slot1, const int32_t *slot2, int P, const double K[9],
+                                  double *R, double *t, int32_t *inliers, int32_t *n_matches, int32_t *status)
+{
+    int rc = rpe_enqueue_pairs(h, slot1, slot2, P, K);
+    if (rc) return rc;
+    return rpe_fetch_results(h, P, R, t, inliers, n_matches, status);
 }
 
 // ---------------------------------------------------------------- stage API
@@ -1104,7 +1364,10 @@ extern "C" int rpe_get_stage_ms(rpe_handle *h, float *ms)
     if (!h || !ms) return RPE_ERR_INVALID;
     if (!h->ev_valid) { h->err = "no profiled batch recorded"; return RPE_ERR_INVALID; }
     HIPCHK(h, hipEventSynchronize(h->ev[RPE_STAGE_COUNT]));
-    for (int i = 0; i < RPE_STAGE_COUNT; ++i) HIPCHK(h, hipEventElapsedTime(&ms[i], h->ev[i], h->ev[i + 1]));
+    for (int i = 0; i < RPE_STAGE_COUNT; ++i) {
+        if (i < h->ev_first) { ms[i] = 0.f; continue; }      // a pair list runs no extraction stage
+        HIPCHK(h, hipEventElapsedTime(&ms[i], h->ev[i], h->ev[i + 1]));
+    }
     return RPE_OK;
 }
 

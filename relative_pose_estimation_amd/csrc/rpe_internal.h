@@ -15,6 +15,7 @@
 #define RPE_MAX_MODELS 10
 #define RPE_GRAPH_MAX_PAIRS 16    // batches up to this many pairs are replayed as a captured hipGraph
 #define RPE_MATCH_SPLIT_PAIRS 64   // batches up to this many pairs split a pair's Hamming matching over several workgroups
+#define RPE_TAB_RING 4            // pinned pieces the slot tables of rpe_frames_put* / rpe_enqueue_pairs rotate through
 #define RPE_RESULT_BYTES 108     // per pair: R 72 + t 24 + inliers 4 + status 4 + n_matches 4
 // FAST tile = 64 x FAST_TH output pixels, FAST_TH * 4 threads.  Unlike the resize kernel (latency bound: smaller tiles
 // won), FAST is bound by instruction issue and 32-row tiles with two waves only add halo work: 4.43 -> 4.79 ms.
@@ -62,6 +63,19 @@ __device__ __forceinline__ const uint8_t *rpe_level_base(const uint8_t *pyr, con
     if (l == 0 && lay.in_a)
         return img < lay.in_na ? lay.in_a + (long long)img * lay.in_img : lay.in_b + (long long)(img - lay.in_na) * lay.in_img;
     return pyr + (long long)img * lay.stride + lay.lv[l].off;
+}
+
+// Image slots of pair `pair`.  TAB = false, batch and stream: the rule (pair, img2_base + pair), and the kernel is the one
+// those paths always ran.  TAB = true, rpe_enqueue_pairs: entry `pair` of the table, slot numbers of the frame store;
+// `pair` comes from the workgroup index and `tab` is a kernel argument, so the lookup is uniform: one 8-byte scalar load
+// per workgroup, no vector register, no per-lane load.  The switch is a template parameter and not a test of the
+// pointer: the uniform load in front of the count loads cost the fused Hamming matcher 1 % (0.506 -> 0.512 ms per 1024
+// pairs, four workgroups per CU one after the other) when the batch path carried it.
+template <bool TAB>
+__device__ __forceinline__ void rpe_pair_slots(const int2 *__restrict__ tab, int img2_base, int pair, int &img1, int &img2)
+{
+    if (TAB) { const int2 s = tab[pair]; img1 = s.x; img2 = s.y; }
+    else { img1 = pair; img2 = img2_base + pair; }
 }
 
 // Inclusive prefix operations over the 64 lanes with DPP row shifts / row broadcasts: 6 v_<op>_dpp instead of 6 rounds of
@@ -203,13 +217,42 @@ struct rpe_handle {
     uint8_t *d_resall = nullptr; unsigned *d_ovfall = nullptr;   // whole-batch result block / flag words of a chunked host batch (created on first use)
     uint8_t *d_resblk = nullptr, *h_resblk = nullptr;   // d_R, d_t, d_inliers, d_status, d_m_n live in d_resblk; pinned host mirror
     double *d_K = nullptr;
+    // Frame store (rpe_frames_*): per-frame features resident across calls, [slot][kcap] like the workspace arrays they
+    // are scattered from, so the pair kernels index them with the same arithmetic.  One allocation per array;
+    // rpe_frames_reserve builds the new set, copies the kept slots and frees the old one.
+    struct FrameStore {
+        int cap = 0;
+        uint8_t *d_desc = nullptr;        // [slot][kcap][desc_bytes]
+        float2 *d_kp_pt = nullptr;        // [slot][kcap]
+        int2 *d_norm = nullptr;           // [slot][kcap] NORM_L2 crossCheck handles only: the MFMA matcher's norm words, computed at put time
+        int *d_count = nullptr;           // [slot] keypoints (0 for a slot never filled)
+        unsigned *d_ovf = nullptr;        // [slot] RPE_OVF_* flags of the extraction that filled the slot
+        std::vector<uint8_t> filled;      // [slot] host side: the slot holds a frame (argument checks never read the device)
+    } fs;
+    int *h_pairtab = nullptr;             // pinned, RPE_TAB_RING pieces of 2*max_batch ints: slot list of a put / (slot1, slot2) table of a pair list
+    int *d_pairtab = nullptr;             // device copy, uploaded on the handle's stream
+    hipEvent_t ev_tab[RPE_TAB_RING] = {}; // piece r of h_pairtab has been uploaded (the call that takes it next may overwrite it)
+    int tab_next = 0;
+    const int2 *pair_tab = nullptr;       // set by rpe_enqueue_pairs around its launches: the matchers and the status test read the store
+    bool last_from_store = false;         // the last batch was a pair list: rpe_fetch_overflow reads last_tab and the store's flags
+    std::vector<int> last_tab;            // its (slot1, slot2) entries
     // profiling
     bool profiling = false;
     hipEvent_t ev[RPE_STAGE_COUNT + 1] = {};
     float stage_ms[RPE_STAGE_COUNT] = {};
     bool ev_valid = false;
+    int ev_first = 0;                     // first stage the last profiled call ran (a pair list starts at RPE_STAGE_MATCH)
     std::vector<void *> user_allocs;
 };
+
+// Where the matchers and the status test find the features of pair p: the extraction workspace under the batch / stream
+// rule, or the frame store under a pair table
+struct RpeFeatSrc { const uint8_t *desc; const int *count; const float2 *pt; const int2 *norm; const int2 *tab; int img2_base; };
+static inline RpeFeatSrc rpe_feat_src(const rpe_handle *h, int B)
+{
+    if (h->pair_tab) return {h->fs.d_desc, h->fs.d_count, h->fs.d_kp_pt, h->fs.d_norm, h->pair_tab, 0};
+    return {h->d_desc, h->d_kp_count, h->d_kp_pt, (const int2 *)h->d_m_norm, nullptr, h->img2_base ? h->img2_base : B};
+}
 
 // ---- kernel launchers (defined in the .hip files) --------------------------
 void rpe_launch_pyramid(rpe_handle *h, int n_img);
@@ -223,6 +266,7 @@ void rpe_launch_blur(rpe_handle *h, int n_img);
 void rpe_launch_describe(rpe_handle *h, int n_img);
 void rpe_launch_match(rpe_handle *h, int B);
 void rpe_launch_match_l2(rpe_handle *h, int B);
+void rpe_launch_l2_norms(rpe_handle *h, int n_img);
 int rpe_sift_create(rpe_handle *h);
 void rpe_sift_destroy(rpe_handle *h);
 int rpe_sift_run(rpe_handle *h, const uint8_t *d_a, const uint8_t *d_b, int na, int nb);

@@ -21,6 +21,96 @@ import numpy as np
 from . import _capi, vp_refinement
 
 
+def plan_pairs(n_frames, n_pairs, max_batch):
+    """Chunk plan of PoseEstimator.estimate_pairs, a pure function: (put_chunks, pair_chunks), lists of (start, stop).
+    Every frame is put exactly once, frame f into store slot f, in chunks of at most 2*max_batch frames (the library's
+    image workspace); the pair list then runs in list order in chunks of at most max_batch pairs."""
+    if n_frames < 1 or n_pairs < 0 or max_batch < 1:
+        raise ValueError(f"plan_pairs: need n_frames >= 1, n_pairs >= 0, max_batch >= 1, got {(n_frames, n_pairs, max_batch)}")
+    puts = [(a, min(a + 2 * max_batch, n_frames)) for a in range(0, n_frames, 2 * max_batch)]
+    runs = [(a, min(a + max_batch, n_pairs)) for a in range(0, n_pairs, max_batch)]
+    return puts, runs
+
+
+def _check_pairs(pairs, n_slots, what):
+    """[P, 2] integer array with every index inside [0, n_slots); ValueError otherwise, before any device call"""
+    a = np.asarray(pairs)
+    if a.ndim != 2 or a.shape[1] != 2 or a.shape[0] < 1:
+        raise ValueError(f"pairs: expected an integer array of shape [P, 2] with P >= 1, got shape {a.shape}")
+    if a.dtype.kind not in "iu":
+        raise ValueError(f"pairs: expected integers, got dtype {a.dtype}")
+    if (a < 0).any() or (a >= n_slots).any():
+        raise ValueError(f"pairs: {what} index outside [0, {n_slots})")
+    return np.ascontiguousarray(a, np.int32)
+
+
+class FrameStore:
+    """Per-frame features resident on the GPU for online use (PoseEstimator.frame_store; not in the reference): put a
+    frame into a numbered slot once, then estimate any list of (slot, slot) pairs without extracting again.  The slot
+    numbers are the caller's: a ring of the last k frames is `slot = frame_index % k`.  The store lives on the
+    estimator's engine for the frames' image size; a call that makes the estimator build a larger engine
+    (estimate_batch with more pairs than max_batch) ends it."""
+
+    def __init__(self, estimator, capacity):
+        if int(capacity) < 1:
+            raise ValueError("FrameStore: capacity must be >= 1")
+        self._est, self.capacity, self._eng = estimator, int(capacity), None
+
+    def _engine(self, shape):
+        if self._eng is None:
+            eng = self._est._engine(shape[0], shape[1], 1)
+            if getattr(eng, "_store_owner", None) is not None:
+                raise _capi.RpeError("the engine of this image size already serves a frame store: close it first")
+            eng.frames_reserve(self.capacity)
+            eng._store_owner = self
+            self._eng = eng
+        if self._eng.h is None or getattr(self._eng, "_store_owner", None) is not self:
+            raise _capi.RpeError("FrameStore: its engine is gone (closed, or replaced by a larger one)")
+        if (self._eng.height, self._eng.width) != tuple(shape):
+            raise ValueError(f"FrameStore: frames are {self._eng.height} x {self._eng.width}, got {tuple(shape)}")
+        return self._eng
+
+    def put(self, slot, image):
+        self.put_many([slot], self._est._gray(image)[None])
+
+    def put_many(self, slots, images):
+        slots = np.asarray(slots)
+        images = np.asarray(images)
+        if slots.ndim != 1 or slots.dtype.kind not in "iu" or images.ndim != 3 or images.dtype != np.uint8 or images.shape[0] != slots.size:
+            raise ValueError("put_many: expected n integer slots and n uint8 grayscale images [n, H, W]")
+        if slots.size == 0 or (slots < 0).any() or (slots >= self.capacity).any() or np.unique(slots).size != slots.size:
+            raise ValueError(f"put_many: slots must be distinct and inside [0, {self.capacity})")
+        eng = self._engine(images.shape[1:])
+        step = 2 * eng.max_batch
+        for a in range(0, slots.size, step):
+            eng.frames_put(images[a:a + step], slots[a:a + step])
+
+    def estimate(self, pairs):
+        """(R[P,3,3], t[P,3,1], inliers[P], n_matches[P], status[P]) of the slot pairs [P, 2]; a failing pair never
+        aborts the list.  last_structure / last_refined / last_overflow of the estimator describe the last chunk of
+        at most max_batch pairs."""
+        pairs = _check_pairs(pairs, self.capacity, "slot")
+        if self._eng is None:
+            raise _capi.RpeError("FrameStore: nothing has been put yet")
+        eng = self._engine((self._eng.height, self._eng.width))
+        return self._est._run_pair_list(eng, pairs)
+
+    def info(self, slots):
+        """(keypoint counts, OVF_* flags) of the slots; count -1 = never filled"""
+        slots = np.asarray(slots)
+        if slots.ndim != 1 or slots.size == 0 or slots.dtype.kind not in "iu" or (slots < 0).any() or (slots >= self.capacity).any():
+            raise ValueError(f"info: slots must be integers inside [0, {self.capacity})")
+        if self._eng is None:
+            return np.full(slots.size, -1, np.int32), np.zeros(slots.size, np.uint32)
+        return self._engine((self._eng.height, self._eng.width)).frames_info(slots)
+
+    def close(self):
+        eng, self._eng = self._eng, None
+        if eng is not None and eng.h is not None and getattr(eng, "_store_owner", None) is self:
+            eng.frames_reserve(0)
+            eng._store_owner = None
+
+
 class PoseEstimator:
     def __init__(self,
                  camera_matrix,
@@ -140,6 +230,50 @@ class PoseEstimator:
         self._last_n_matches = nm
         self._last_engine, self._last_pairs = eng, B
         return R, t, inl, st
+
+    def _run_pair_list(self, eng, pairs):
+        """pairs [P, 2] int32 of store slots, in chunks of at most max_batch"""
+        P = pairs.shape[0]
+        R = np.zeros((P, 3, 3)); t = np.zeros((P, 3, 1))
+        inl = np.zeros(P, np.int32); nm = np.zeros(P, np.int32); st = np.zeros(P, np.int32)
+        for a in range(0, P, eng.max_batch):
+            b = min(a + eng.max_batch, P)
+            R[a:b], t[a:b], inl[a:b], nm[a:b], st[a:b] = eng.estimate_pairs(pairs[a:b, 0], pairs[a:b, 1], self.K)
+            self._last_n_matches, self._last_engine, self._last_pairs = nm[a:b].copy(), eng, b - a
+        return R, t, inl, nm, st
+
+    def estimate_pairs(self, frames, pairs):
+        """Relative poses over an arbitrary pair list (not in the reference): frames [F, H, W] uint8 gray (or
+        [F, H, W, 3] BGR, converted with cv2's weights on the GPU), pairs [P, 2] integer frame indices -- any frames,
+        repeats, reversed and self pairs.  Every frame is extracted once, whatever the number of pairs that name it
+        (a window of k successors per frame costs F extractions, not 2 k F); pair (a, b) returns the bits estimate_batch
+        returns for (frames[a], frames[b]).  Returns (R[P,3,3], t[P,3,1], inliers[P], n_matches[P], status[P]); a failing
+        pair never aborts the list.  The frames are put in chunks of at most 2*max_batch and the list runs in chunks of
+        at most max_batch (plan_pairs); last_structure(), last_refined() and last_overflow() describe the LAST chunk of
+        pairs, as they do for estimate_batch.  Needs F store slots of GPU memory, which stay with the engine and are reused by the next call
+        (INTEGRATION.md section 7)."""
+        frames = np.asarray(frames)
+        if frames.dtype != np.uint8 or frames.ndim not in (3, 4) or (frames.ndim == 4 and frames.shape[-1] != 3) or frames.shape[0] < 1:
+            raise ValueError(f"frames: expected uint8 [F, H, W] or [F, H, W, 3], got {frames.dtype} {frames.shape}")
+        F, H, W = frames.shape[:3]
+        pairs = _check_pairs(pairs, F, "frame")
+        eng = self._engine(H, W, 1)
+        if getattr(eng, "_store_owner", None) is not None:
+            raise _capi.RpeError("the engine of this image size serves a FrameStore: use its estimate(), or close it first")
+        puts, _ = plan_pairs(F, pairs.shape[0], eng.max_batch)
+        if eng.frames_capacity() < F:         # a store left by an earlier call is reused when it is large enough
+            eng.frames_reserve(0)
+            eng.frames_reserve(F)
+        for a, b in puts:
+            chunk = frames[a:b]
+            gray = eng.bgr_to_gray(chunk) if chunk.ndim == 4 else chunk
+            eng.frames_put(gray, np.arange(a, b, dtype=np.int32))
+        return self._run_pair_list(eng, pairs)
+
+    def frame_store(self, capacity):
+        """A FrameStore of `capacity` slots on this estimator's engine (created for the size of the first frame put)."""
+        self._check_runnable()
+        return FrameStore(self, capacity)
 
     def last_overflow(self):
         """OVF_* capacity flags (see _capi) of the pairs of the last estimate_batch / estimate_sequence call: nonzero

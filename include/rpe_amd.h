@@ -233,6 +233,70 @@ int rpe_enqueue_pairs(rpe_handle *h, const int32_t *slot1, const int32_t *slot2,
 int rpe_estimate_pairs(rpe_handle *h, const int32_t *slot1, const int32_t *slot2, int P, const double K[9],
                        double *R, double *t, int32_t *inliers, int32_t *n_matches, int32_t *status);
 
+/* ---------------------------------------------------------- camera models */
+/* Per-frame camera: pinhole intrinsics plus cv2's Brown-Conrady / rational lens (NOT in the reference, which has one K
+ * and pinhole points).  The geometry stages of the *_cameras calls below normalise every matched point p (f32 pixel,
+ * converted to f64 first) with the camera of ITS frame: xd = (p.x - cx) / fx, yd = (p.y - cy) / fy, then -- unless all
+ * eight coefficients are zero -- cv2.undistortPoints' fixed-point iteration started at (xd, yd), exactly
+ * RPE_UNDISTORT_ITERS times, in f64 and in this operation order:
+ *     r2  = x*x + y*y
+ *     icd = (1 + r2*(k4 + r2*(k5 + r2*k6))) / (1 + r2*(k1 + r2*(k2 + r2*k3)))
+ *     dx  = 2*p1*x*y + p2*(r2 + 2*x*x);   dy = p1*(r2 + 2*y*y) + 2*p2*x*y
+ *     x   = (xd - dx) * icd;              y  = (yd - dy) * icd
+ * A camera whose dist is all zero skips the iteration: its normalised point is bit for bit the single-K path's.  The
+ * count is fixed (cv2's default criterion; results stay bit-deterministic): after five iterations the residual at the
+ * corner of a VGA image is 1e-4 px for (k1, k2, p1, p2, k3) = (-0.12, 0.03, 0.0008, -0.0005, 0) and 0.035 px for
+ * (-0.28, 0.09, 0.001, -0.0008, -0.01).  Where a focal length is a scale -- the RANSAC threshold
+ * (ransac_threshold / f) and the pixel scale of the refinement -- a pair uses the mean of its two cameras,
+ * f = (((fx1 + fy1) / 2) + ((fx2 + fy2) / 2)) / 2, which for equal cameras is the single-K value exactly.
+ * All images of a handle have one size; cameras differ in parameters only.  Triangulated points stay in the camera-1
+ * frame at |t| = 1.  Every call validates its cameras before anything is launched: a non-finite field, fx <= 0 or
+ * fy <= 0 is RPE_ERR_INVALID and leaves the handle usable. */
+#define RPE_UNDISTORT_ITERS 5
+typedef struct rpe_camera {      /* 96 bytes */
+    double fx, fy, cx, cy;       /* K[0], K[4], K[2], K[5]; skew is ignored, as everywhere in this library */
+    double dist[8];              /* cv2 order: k1 k2 p1 p2 k3 k4 k5 k6; all zero = pinhole */
+} rpe_camera;
+
+/* cameras of n frame-store slots (host arrays; slots inside the store, filled or not).  A slot keeps its camera across
+ * calls, across a later put of the same slot and across rpe_frames_reserve (slots below the new size); a slot never
+ * given one has no camera.  Ends the claim of a camera pair list on rpe_fetch_structure / rpe_refine_poses. */
+int rpe_frames_set_cameras(rpe_handle *h, int n, const int32_t *slots, const rpe_camera *cams);
+/* rpe_enqueue_pairs / rpe_estimate_pairs with every pair on the cameras of its two slots, resolved on the device.
+ * RPE_ERR_INVALID, nothing launched, handle usable, when a named slot has no camera.  (rpe_enqueue_pairs itself ignores
+ * slot cameras.)  Afterwards the list is "the last batch" exactly as after rpe_enqueue_pairs; rpe_fetch_matched_points
+ * returns the raw, distorted pixels of the matches. */
+int rpe_enqueue_pairs_cameras(rpe_handle *h, const int32_t *slot1, const int32_t *slot2, int P);
+int rpe_estimate_pairs_cameras(rpe_handle *h, const int32_t *slot1, const int32_t *slot2, int P,
+                               double *R, double *t, int32_t *inliers, int32_t *n_matches, int32_t *status);
+/* the batch forms with cam1[B] (cameras of imgs1) and cam2[B] (of imgs2) in place of K; plain launches for every B (no
+ * graph replay).  Afterwards the batch is "the last batch" of rpe_fetch_results, rpe_fetch_matched_points (raw,
+ * distorted pixels), rpe_fetch_structure, rpe_refine_poses, rpe_gather_poses and rpe_fetch_overflow.
+ * rpe_estimate_batch_cameras (host images) does not chunk: a batch large enough for rpe_estimate_batch's chunked upload
+ * (B >= 512 and >= 64 MiB per image set) is refused with RPE_ERR_INVALID; upload it and call the _device form. */
+int rpe_enqueue_batch_cameras_device(rpe_handle *h, const uint8_t *d_imgs1, const uint8_t *d_imgs2, int B,
+                                     const rpe_camera *cam1, const rpe_camera *cam2);
+int rpe_estimate_batch_cameras_device(rpe_handle *h, const uint8_t *d_imgs1, const uint8_t *d_imgs2, int B,
+                                      const rpe_camera *cam1, const rpe_camera *cam2, double *R, double *t,
+                                      int32_t *inliers, int32_t *n_matches, int32_t *status);
+int rpe_estimate_batch_cameras(rpe_handle *h, const uint8_t *h_imgs1, const uint8_t *h_imgs2, int B,
+                               const rpe_camera *cam1, const rpe_camera *cam2, double *R, double *t,
+                               int32_t *inliers, int32_t *n_matches, int32_t *status);
+/* stage forms for callers with their own matches.  rpe_undistort_points: n f32 pixels (x, y) of one camera ->
+ * out_xy[2n] f64 normalised, undistorted coordinates (host arrays), the values the geometry stages work on.  The other
+ * three are rpe_find_essential / rpe_recover_pose / rpe_refine_pose_points with cam1[B], cam2[B] for K. */
+int rpe_undistort_points(rpe_handle *h, const float *h_pts, int n, const rpe_camera *cam, double *h_out_xy);
+int rpe_find_essential_cameras(rpe_handle *h, const float *h_pts1, const float *h_pts2, const int32_t *m, int B,
+                               const rpe_camera *cam1, const rpe_camera *cam2, double *E, uint8_t *mask,
+                               int32_t *found, int32_t *info);
+int rpe_recover_pose_cameras(rpe_handle *h, const double *h_E, const float *h_pts1, const float *h_pts2,
+                             const int32_t *m, int B, const rpe_camera *cam1, const rpe_camera *cam2,
+                             double *R, double *t, int32_t *inliers);
+int rpe_refine_pose_points_cameras(rpe_handle *h, const double *h_R0, const double *h_t0, const float *h_pts1,
+                                   const float *h_pts2, const uint8_t *h_mask, const int32_t *m, int B,
+                                   const rpe_camera *cam1, const rpe_camera *cam2, int max_iters, double *R, double *t,
+                                   int32_t *inliers, int32_t *info, double *rms);
+
 /* Image ingest, the step before the path (reference src/utils/image_loader.py:23-28:
  * cv2.imread -> BGR, cv2.cvtColor(BGR2GRAY)): interleaved 3-channel uint8 images -> gray with cv2's
  * fixed-point weights, gray = (B*3735 + G*19235 + R*9798 + 16384) >> 15, on the handle's stream.

@@ -27,6 +27,7 @@ CALIB_KINDS = 16
 STAGE_COUNT = 12
 ORDER_BGR, ORDER_RGB = 0, 1
 REFINE_OK, REFINE_SKIPPED, REFINE_REJECTED = 0, 1, 2   # info[:, 0] of refine_poses (include/rpe_amd.h RPE_REFINE_*)
+UNDISTORT_ITERS = 5               # RPE_UNDISTORT_ITERS: fixed-point rounds of the camera path's undistortion
 
 EXPORTS = [
     "rpe_default_config", "rpe_create", "rpe_destroy", "rpe_last_error", "rpe_device_count",
@@ -43,6 +44,9 @@ EXPORTS = [
     "rpe_comm_allreduce_max", "rpe_comm_barrier",
     "rpe_frames_reserve", "rpe_frames_capacity", "rpe_frames_put_device", "rpe_frames_put", "rpe_frames_info",
     "rpe_enqueue_pairs", "rpe_estimate_pairs",
+    "rpe_frames_set_cameras", "rpe_enqueue_pairs_cameras", "rpe_estimate_pairs_cameras",
+    "rpe_enqueue_batch_cameras_device", "rpe_estimate_batch_cameras_device", "rpe_estimate_batch_cameras",
+    "rpe_undistort_points", "rpe_find_essential_cameras", "rpe_recover_pose_cameras", "rpe_refine_pose_points_cameras",
 ]
 
 
@@ -60,11 +64,62 @@ KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("angle", "<f4"), ("response", 
 SIFT_KP_DTYPE = np.dtype([("x", "<f4"), ("y", "<f4"), ("size", "<f4"), ("angle", "<f4"), ("response", "<f4"),
                           ("octave", "<i4")])
 
+# struct rpe_camera (include/rpe_amd.h): 96 bytes
+CAMERA_DTYPE = np.dtype([("fx", "<f8"), ("fy", "<f8"), ("cx", "<f8"), ("cy", "<f8"), ("dist", "<f8", (8,))])
+
 _lib = None
 
 
 class RpeError(RuntimeError):
     pass
+
+
+class Camera:
+    """Camera model of one frame (struct rpe_camera): pinhole intrinsics from K (fx, fy, cx, cy; skew is ignored, as
+    everywhere in the library) and cv2's distortion coefficients in cv2's order (k1, k2, p1, p2[, k3[, k4, k5, k6]]):
+    `dist` holds 4, 5 or 8 values, None = pinhole.  Validated here, before any device call: finite fields, fx > 0,
+    fy > 0."""
+
+    def __init__(self, K, dist=None):
+        K = np.asarray(K, np.float64)
+        if K.shape != (3, 3):
+            raise ValueError(f"Camera: K must be 3 x 3, got shape {K.shape}")
+        d = np.zeros(0) if dist is None else np.asarray(dist, np.float64).reshape(-1)
+        if d.size not in (0, 4, 5, 8):
+            raise ValueError(f"Camera: dist must hold 4, 5 or 8 coefficients (cv2 order), got {d.size}")
+        self.fx, self.fy, self.cx, self.cy = float(K[0, 0]), float(K[1, 1]), float(K[0, 2]), float(K[1, 2])
+        self.dist = np.zeros(8)
+        self.dist[:d.size] = d
+        if not (np.isfinite([self.fx, self.fy, self.cx, self.cy]).all() and np.isfinite(self.dist).all()):
+            raise ValueError("Camera: non-finite field")
+        if not (self.fx > 0 and self.fy > 0):
+            raise ValueError("Camera: fx and fy must be > 0")
+
+    @property
+    def K(self):
+        return np.array([[self.fx, 0., self.cx], [0., self.fy, self.cy], [0., 0., 1.]])
+
+    def record(self):
+        r = np.zeros(1, CAMERA_DTYPE)
+        r["fx"], r["fy"], r["cx"], r["cy"], r["dist"] = self.fx, self.fy, self.cx, self.cy, self.dist
+        return r
+
+
+def camera_records(cameras, n):
+    """n rpe_camera records from one Camera (repeated) or a sequence of n; an array of CAMERA_DTYPE passes through
+    unchecked (the library validates it)"""
+    if isinstance(cameras, np.ndarray) and cameras.dtype == CAMERA_DTYPE:
+        rec = np.ascontiguousarray(cameras).reshape(-1)
+    elif isinstance(cameras, Camera):
+        rec = np.repeat(cameras.record(), n)
+    else:
+        cameras = list(cameras)
+        if not all(isinstance(c, Camera) for c in cameras):
+            raise ValueError("cameras: expected Camera objects")
+        rec = np.concatenate([c.record() for c in cameras]) if cameras else np.zeros(0, CAMERA_DTYPE)
+    if rec.size != n:
+        raise ValueError(f"cameras: expected {n}, got {rec.size}")
+    return np.ascontiguousarray(rec)
 
 
 def load():
@@ -146,6 +201,21 @@ def load():
     lib.rpe_frames_info.argtypes = [vp, C.c_int, i32p, i32p, vp]; lib.rpe_frames_info.restype = C.c_int
     lib.rpe_enqueue_pairs.argtypes = [vp, i32p, i32p, C.c_int, vp]; lib.rpe_enqueue_pairs.restype = C.c_int
     lib.rpe_estimate_pairs.argtypes = [vp, i32p, i32p, C.c_int, vp, vp, vp, i32p, i32p, i32p]; lib.rpe_estimate_pairs.restype = C.c_int
+    lib.rpe_frames_set_cameras.argtypes = [vp, C.c_int, i32p, vp]; lib.rpe_frames_set_cameras.restype = C.c_int
+    lib.rpe_enqueue_pairs_cameras.argtypes = [vp, i32p, i32p, C.c_int]; lib.rpe_enqueue_pairs_cameras.restype = C.c_int
+    lib.rpe_estimate_pairs_cameras.argtypes = [vp, i32p, i32p, C.c_int, vp, vp, i32p, i32p, i32p]; lib.rpe_estimate_pairs_cameras.restype = C.c_int
+    lib.rpe_enqueue_batch_cameras_device.argtypes = [vp, vp, vp, C.c_int, vp, vp]; lib.rpe_enqueue_batch_cameras_device.restype = C.c_int
+    lib.rpe_estimate_batch_cameras_device.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp, vp, i32p, i32p, i32p]
+    lib.rpe_estimate_batch_cameras_device.restype = C.c_int
+    lib.rpe_estimate_batch_cameras.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp, vp, i32p, i32p, i32p]
+    lib.rpe_estimate_batch_cameras.restype = C.c_int
+    lib.rpe_undistort_points.argtypes = [vp, vp, C.c_int, vp, vp]; lib.rpe_undistort_points.restype = C.c_int
+    lib.rpe_find_essential_cameras.argtypes = [vp, vp, vp, i32p, C.c_int, vp, vp, vp, vp, i32p, i32p]
+    lib.rpe_find_essential_cameras.restype = C.c_int
+    lib.rpe_recover_pose_cameras.argtypes = [vp, vp, vp, vp, i32p, C.c_int, vp, vp, vp, vp, i32p]
+    lib.rpe_recover_pose_cameras.restype = C.c_int
+    lib.rpe_refine_pose_points_cameras.argtypes = [vp, vp, vp, vp, vp, vp, i32p, C.c_int, vp, vp, C.c_int, vp, vp, i32p, i32p, vp]
+    lib.rpe_refine_pose_points_cameras.restype = C.c_int
     _lib = lib
     return lib
 
@@ -388,6 +458,87 @@ class Engine:
         R, t, inl, nm, st = self._outs(P)
         self._chk(self.lib.rpe_estimate_pairs(self.h, _p(s1), _p(s2), P, _p(K), _p(R), _p(t), _p(inl), _p(nm), _p(st)))
         return R, t, inl, nm, st
+
+    # ---- camera models (rpe_*_cameras; not in the reference): one Camera, or one per frame
+    def frames_set_cameras(self, slots, cameras):
+        """Cameras of the store slots `slots`; a slot keeps its camera until it is given another."""
+        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        rec = camera_records(cameras, slots.size)
+        self._chk(self.lib.rpe_frames_set_cameras(self.h, slots.size, _p(slots), _p(rec)))
+
+    def enqueue_pairs_cameras(self, slot1, slot2):
+        s1 = np.ascontiguousarray(slot1, np.int32).reshape(-1); s2 = np.ascontiguousarray(slot2, np.int32).reshape(-1)
+        assert s1.size == s2.size
+        self._chk(self.lib.rpe_enqueue_pairs_cameras(self.h, _p(s1), _p(s2), s1.size))
+
+    def estimate_pairs_cameras(self, slot1, slot2):
+        """estimate_pairs with every pair on the cameras of its two slots (frames_set_cameras)."""
+        s1 = np.ascontiguousarray(slot1, np.int32).reshape(-1); s2 = np.ascontiguousarray(slot2, np.int32).reshape(-1)
+        assert s1.size == s2.size
+        P = s1.size
+        R, t, inl, nm, st = self._outs(P)
+        self._chk(self.lib.rpe_estimate_pairs_cameras(self.h, _p(s1), _p(s2), P, _p(R), _p(t), _p(inl), _p(nm), _p(st)))
+        return R, t, inl, nm, st
+
+    def enqueue_batch_cameras_device(self, d_imgs1, d_imgs2, B, cameras1, cameras2):
+        c1 = camera_records(cameras1, B); c2 = camera_records(cameras2, B)
+        self._chk(self.lib.rpe_enqueue_batch_cameras_device(self.h, d_imgs1, d_imgs2, B, _p(c1), _p(c2)))
+
+    def estimate_batch_cameras_device(self, d_imgs1, d_imgs2, B, cameras1, cameras2):
+        c1 = camera_records(cameras1, B); c2 = camera_records(cameras2, B)
+        R, t, inl, nm, st = self._outs(B)
+        self._chk(self.lib.rpe_estimate_batch_cameras_device(self.h, d_imgs1, d_imgs2, B, _p(c1), _p(c2), _p(R), _p(t), _p(inl), _p(nm), _p(st)))
+        return R, t, inl, nm, st
+
+    def estimate_batch_cameras(self, imgs1, imgs2, cameras1, cameras2):
+        """estimate_batch with a camera per image (cameras1[p] for imgs1[p], cameras2[p] for imgs2[p])."""
+        imgs1 = np.ascontiguousarray(imgs1, np.uint8); imgs2 = np.ascontiguousarray(imgs2, np.uint8)
+        B = imgs1.shape[0]
+        assert imgs1.shape == imgs2.shape == (B, self.height, self.width), (imgs1.shape, imgs2.shape)
+        c1 = camera_records(cameras1, B); c2 = camera_records(cameras2, B)
+        R, t, inl, nm, st = self._outs(B)
+        self._chk(self.lib.rpe_estimate_batch_cameras(self.h, _p(imgs1), _p(imgs2), B, _p(c1), _p(c2), _p(R), _p(t), _p(inl), _p(nm), _p(st)))
+        return R, t, inl, nm, st
+
+    def undistort_points(self, pts, camera):
+        """(n, 2) f32 pixels -> (n, 2) f64 normalised, undistorted coordinates: what the geometry stages of the camera
+        path work on."""
+        pts = np.ascontiguousarray(pts, np.float32).reshape(-1, 2)
+        rec = camera_records(camera, 1)
+        out = np.zeros((pts.shape[0], 2))
+        self._chk(self.lib.rpe_undistort_points(self.h, _p(pts), pts.shape[0], _p(rec), _p(out)))
+        return out
+
+    def find_essential_cameras(self, pts1, pts2, cameras1, cameras2):
+        p1, p2, m = self._pack_points(pts1, pts2)
+        B = len(m)
+        c1 = camera_records(cameras1, B); c2 = camera_records(cameras2, B)
+        E = np.zeros((B, 3, 3)); mask = np.zeros((B, self.max_matches), np.uint8)
+        found = np.zeros(B, np.int32); info = np.zeros((B, 4), np.int32)
+        self._chk(self.lib.rpe_find_essential_cameras(self.h, _p(p1), _p(p2), _p(m), B, _p(c1), _p(c2), _p(E), _p(mask), _p(found), _p(info)))
+        return E, mask, found, info
+
+    def recover_pose_cameras(self, E, pts1, pts2, cameras1, cameras2):
+        p1, p2, m = self._pack_points(pts1, pts2)
+        B = len(m); E = np.ascontiguousarray(E, np.float64)
+        c1 = camera_records(cameras1, B); c2 = camera_records(cameras2, B)
+        R = np.zeros((B, 3, 3)); t = np.zeros((B, 3, 1)); inl = np.zeros(B, np.int32)
+        self._chk(self.lib.rpe_recover_pose_cameras(self.h, _p(E), _p(p1), _p(p2), _p(m), B, _p(c1), _p(c2), _p(R), _p(t), _p(inl)))
+        return R, t, inl
+
+    def refine_pose_points_cameras(self, R0, t0, pts1, pts2, masks, cameras1, cameras2, max_iters=10):
+        p1, p2, m = self._pack_points(pts1, pts2)
+        B = len(m)
+        c1 = camera_records(cameras1, B); c2 = camera_records(cameras2, B)
+        R0 = np.ascontiguousarray(np.asarray(R0, np.float64).reshape(B, 9)); t0 = np.ascontiguousarray(np.asarray(t0, np.float64).reshape(B, 3))
+        mk = np.zeros((B, self.max_matches), np.uint8)
+        for i in range(B):
+            mk[i, :m[i]] = np.asarray(masks[i]).astype(bool)[:m[i]]
+        R = np.zeros((B, 3, 3)); t = np.zeros((B, 3, 1)); inl = np.zeros(B, np.int32)
+        info = np.zeros((B, 4), np.int32); rms = np.zeros((B, 2))
+        self._chk(self.lib.rpe_refine_pose_points_cameras(self.h, _p(R0), _p(t0), _p(p1), _p(p2), _p(mk), _p(m), B, _p(c1), _p(c2),
+                                                          max_iters, _p(R), _p(t), _p(inl), _p(info), _p(rms)))
+        return R, t, inl, info, rms
 
     # ---- stage API
     def orb_detect_and_compute(self, imgs):

@@ -338,20 +338,37 @@ __device__ static int five_point_poly(const double *x1, const double *x2, double
 }
 
 // ---------------------------------------------------------------- prepare
+// CAM (rpe_internal.h, RpeCamSrc): false = the shared K; true = the pair's two cameras, each point normalised and
+// undistorted with the camera of its own frame.  One thread per match; the cameras are workgroup-uniform scalar loads
+// and the lens test is a uniform branch, the five iterations run in registers.
+template <bool CAM>
 __global__ __launch_bounds__(256) void ransac_prepare_kernel(const float2 *__restrict__ pts1, const float2 *__restrict__ pts2,
                                                               const int *__restrict__ m_n, const double *__restrict__ K,
+                                                              const RpeCamSrc cam,
                                                               double2 *__restrict__ n1, double2 *__restrict__ n2,
                                                               RpeRansacState *__restrict__ st, int *__restrict__ found,
                                                               int max_matches, int max_iters)
 {
     const int pair = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
     const int M = min(m_n[pair], max_matches);
-    const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
-    if (i < M) {
-        long long o = (long long)pair * max_matches + i;
-        float2 a = pts1[o], b = pts2[o];
-        n1[o] = make_double2(((double)a.x - cx) / fx, ((double)a.y - cy) / fy);
-        n2[o] = make_double2(((double)b.x - cx) / fx, ((double)b.y - cy) / fy);
+    if (CAM) {
+        const rpe_camera *c1, *c2;
+        rpe_pair_cameras(cam, pair, c1, c2);
+        const bool lens1 = rpe_camera_has_lens(c1), lens2 = rpe_camera_has_lens(c2);
+        if (i < M) {
+            long long o = (long long)pair * max_matches + i;
+            float2 a = pts1[o], b = pts2[o];
+            n1[o] = rpe_camera_normalise(c1, lens1, a);
+            n2[o] = rpe_camera_normalise(c2, lens2, b);
+        }
+    } else {
+        const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
+        if (i < M) {
+            long long o = (long long)pair * max_matches + i;
+            float2 a = pts1[o], b = pts2[o];
+            n1[o] = make_double2(((double)a.x - cx) / fx, ((double)a.y - cy) / fy);
+            n2[o] = make_double2(((double)b.x - cx) / fx, ((double)b.y - cy) / fy);
+        }
     }
     if (i == 0) {
         RpeRansacState s;
@@ -679,10 +696,11 @@ __device__ __forceinline__ int update_niters(const double *nit_denom, const int 
 // workgroup = 4x the workgroups of the 64-iteration grouping, each a quarter as long.  The K-normalised matches sit in LDS; each of
 // the 4 waves scores a different model (lanes stride over the matches, Sampson error f64 -> f32
 // compare, wave-shuffle popcount), so there is no cross-wave reduction.  Counts go to HBM.
+template <bool CAM>
 __global__ __launch_bounds__(256) void ransac_score_kernel(const double2 *__restrict__ n1, const double2 *__restrict__ n2,
                                                             const RpeRansacState *__restrict__ st, const double *__restrict__ models,
                                                             const int *__restrict__ nmodels, const double *__restrict__ K,
-                                                            double threshold, int *__restrict__ counts, int max_matches, int use_lds)
+                                                            const RpeCamSrc cam, double threshold, int *__restrict__ counts, int max_matches, int use_lds)
 {
     extern __shared__ double2 s_pts[];              // [2][max_matches] when the points fit LDS (use_lds)
     __shared__ int s_nm[SCORE_GROUP], s_first[SCORE_GROUP + 1];
@@ -703,8 +721,7 @@ __global__ __launch_bounds__(256) void ransac_score_kernel(const double2 *__rest
     __syncthreads();
     if (tid == 0) { int acc = 0; for (int k = 0; k < SCORE_GROUP; ++k) { s_first[k] = acc; acc += s_nm[k]; } s_first[SCORE_GROUP] = acc; }
     __syncthreads();
-    const double fx = K[0], fy = K[4];
-    const double thr = threshold / ((fx + fy) / 2);
+    const double thr = threshold / rpe_pair_focal<CAM>(K, cam, pair);
     const float thr2 = (float)(thr * thr);
     const SampsonBound sbound = sampson_bound(thr2);
     const int total = s_first[SCORE_GROUP];
@@ -850,15 +867,15 @@ __global__ __launch_bounds__(256) void ransac_update_kernel(RpeRansacState *__re
 
 // ------------------------------------------------------------------- mask
 // status (may be null): pairs of a batch whose status is not RPE_PAIR_OK get an all-zero mask
+template <bool CAM>
 __global__ __launch_bounds__(256) void ransac_mask_kernel(const double2 *__restrict__ n1, const double2 *__restrict__ n2,
                                                            const RpeRansacState *__restrict__ st, const double *__restrict__ K,
-                                                           double threshold, const int *__restrict__ status,
+                                                           const RpeCamSrc cam, double threshold, const int *__restrict__ status,
                                                            uint8_t *__restrict__ mask, int max_matches)
 {
     const int pair = blockIdx.x, tid = threadIdx.x;
     const RpeRansacState s = st[pair];
-    const double fx = K[0], fy = K[4];
-    const double thr = threshold / ((fx + fy) / 2);
+    const double thr = threshold / rpe_pair_focal<CAM>(K, cam, pair);
     const float thr2 = (float)(thr * thr);
     const bool ok = !status || status[pair] == RPE_PAIR_OK;
     for (int i = tid; i < max_matches; i += 256) {
@@ -874,12 +891,28 @@ __global__ __launch_bounds__(256) void ransac_mask_kernel(const double2 *__restr
     }
 }
 
+static void launch_mask(rpe_handle *h, int B, const int *status)
+{
+    const int mm = h->cfg.max_matches;
+    if (h->cam.cams)
+        hipLaunchKernelGGL(ransac_mask_kernel<true>, dim3(B), dim3(256), 0, h->stream,
+                           h->d_n1, h->d_n2, h->d_rstate, h->d_K, h->cam, h->cfg.ransac_threshold, status, h->d_mask, mm);
+    else
+        hipLaunchKernelGGL(ransac_mask_kernel<false>, dim3(B), dim3(256), 0, h->stream,
+                           h->d_n1, h->d_n2, h->d_rstate, h->d_K, h->cam, h->cfg.ransac_threshold, status, h->d_mask, mm);
+}
+
 void rpe_launch_ransac(rpe_handle *h, int B, bool want_mask)
 {
     const int mm = h->cfg.max_matches, it = h->cfg.ransac_max_iters;
     double2 *n1 = h->d_n1, *n2 = h->d_n2;
-    hipLaunchKernelGGL(ransac_prepare_kernel, dim3((mm + 255) / 256, B), dim3(256), 0, h->stream,
-                       h->d_pts1, h->d_pts2, h->d_m_n, h->d_K, n1, n2, h->d_rstate, h->d_found, mm, it);
+    const bool cam = h->cam.cams != nullptr;          // camera path: the <true> instances; the single-K paths launch <false> only
+    if (cam)
+        hipLaunchKernelGGL(ransac_prepare_kernel<true>, dim3((mm + 255) / 256, B), dim3(256), 0, h->stream,
+                           h->d_pts1, h->d_pts2, h->d_m_n, h->d_K, h->cam, n1, n2, h->d_rstate, h->d_found, mm, it);
+    else
+        hipLaunchKernelGGL(ransac_prepare_kernel<false>, dim3((mm + 255) / 256, B), dim3(256), 0, h->stream,
+                           h->d_pts1, h->d_pts2, h->d_m_n, h->d_K, h->cam, n1, n2, h->d_rstate, h->d_found, mm, it);
     // chunk schedule 32, 96, 384, 512, 512, ... (cumulative 32, 128, 512, 1024).  A launch group costs
     //   max(latency floor, work): the floor is one wave's dependent chain through poly -> roots -> score -> update
     //   (~170-200 us whatever the number of pairs still running), the work is ~12.6 ns per (pair, iteration) that is
@@ -909,9 +942,14 @@ void rpe_launch_ransac(rpe_handle *h, int B, bool want_mask)
                            n1, n2, h->d_rstate, h->d_subsets, h->d_hyp, h->d_nmodels, mm, it);
         hipLaunchKernelGGL(ransac_roots_kernel, dim3((unsigned)((long long)B * chunk * RG / 256)), dim3(256), 0, h->stream,
                            (const RpeRansacState *)h->d_rstate, (const double *)h->d_hyp, h->d_models, h->d_nmodels, B, chunk);
-        hipLaunchKernelGGL(ransac_score_kernel, dim3(B, chunk / SCORE_GROUP), dim3(256), lds, h->stream,
-                           n1, n2, (const RpeRansacState *)h->d_rstate, (const double *)h->d_models, (const int *)h->d_nmodels,
-                           (const double *)h->d_K, h->cfg.ransac_threshold, h->d_counts, mm, use_lds);
+        if (cam)
+            hipLaunchKernelGGL(ransac_score_kernel<true>, dim3(B, chunk / SCORE_GROUP), dim3(256), lds, h->stream,
+                               n1, n2, (const RpeRansacState *)h->d_rstate, (const double *)h->d_models, (const int *)h->d_nmodels,
+                               (const double *)h->d_K, h->cam, h->cfg.ransac_threshold, h->d_counts, mm, use_lds);
+        else
+            hipLaunchKernelGGL(ransac_score_kernel<false>, dim3(B, chunk / SCORE_GROUP), dim3(256), lds, h->stream,
+                               n1, n2, (const RpeRansacState *)h->d_rstate, (const double *)h->d_models, (const int *)h->d_nmodels,
+                               (const double *)h->d_K, h->cam, h->cfg.ransac_threshold, h->d_counts, mm, use_lds);
         hipLaunchKernelGGL(ransac_update_kernel, dim3((B + 3) / 4), dim3(256), 0, h->stream,
                            h->d_rstate, (const double *)h->d_models, (const int *)h->d_nmodels, (const int *)h->d_counts,
                            (const double *)h->d_nit_denom, (const int *)h->d_nit_round, h->nit_num, h->d_E, h->d_found, chunk, B);
@@ -920,9 +958,7 @@ void rpe_launch_ransac(rpe_handle *h, int B, bool want_mask)
         if (!env_sched.empty()) chunk = env_sched[std::min((size_t)nlaunch, env_sched.size() - 1)];
         else chunk = kSchedule[std::min(nlaunch, 3)];
     }
-    if (want_mask)
-        hipLaunchKernelGGL(ransac_mask_kernel, dim3(B), dim3(256), 0, h->stream,
-                           n1, n2, h->d_rstate, h->d_K, h->cfg.ransac_threshold, (const int *)nullptr, h->d_mask, mm);
+    if (want_mask) launch_mask(h, B, (const int *)nullptr);
 }
 
 // ------------------------------------------------------------ recoverPose
@@ -1039,9 +1075,12 @@ __device__ static int triangulate_one(const double *R, const double *t, double x
     return good;
 }
 
-template <bool TAB>
+// CAM = true: the matches are read as d_n1 / d_n2, the normalised (and undistorted) coordinates the RANSAC of the same
+// call worked on, instead of being normalised again with K
+template <bool TAB, bool CAM>
 __global__ __launch_bounds__(256) void recover_pose_kernel(const double *__restrict__ Eall, const float2 *__restrict__ pts1,
-                                                            const float2 *__restrict__ pts2, const int *__restrict__ m_n,
+                                                            const float2 *__restrict__ pts2, const double2 *__restrict__ n1,
+                                                            const double2 *__restrict__ n2, const int *__restrict__ m_n,
                                                             const int *__restrict__ found, const int *__restrict__ kp_count,
                                                             int img2_base, const int2 *__restrict__ pair_tab, const double *__restrict__ K,
                                                             double *__restrict__ Rout, double *__restrict__ tout,
@@ -1070,12 +1109,19 @@ __global__ __launch_bounds__(256) void recover_pose_kernel(const double *__restr
     for (int e = 0; e < 9; ++e) E[e] = Eall[pair * 9 + e];
     decompose_essential(E, R1, R2, tt);
     tn[0] = -tt[0]; tn[1] = -tt[1]; tn[2] = -tt[2];
-    const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
+    double fx = 1., fy = 1., cx = 0., cy = 0.;
+    if (!CAM) { fx = K[0]; fy = K[4]; cx = K[2]; cy = K[5]; }
     int g1 = 0, g2 = 0, g3 = 0, g4 = 0;
     for (int i = tid; i < M; i += 256) {
-        float2 a = pts1[(long long)pair * max_matches + i], b = pts2[(long long)pair * max_matches + i];
-        double x1 = ((double)a.x - cx) / fx, y1 = ((double)a.y - cy) / fy;
-        double x2 = ((double)b.x - cx) / fx, y2 = ((double)b.y - cy) / fy;
+        double x1, y1, x2, y2;
+        if (CAM) {
+            const double2 a = n1[(long long)pair * max_matches + i], b = n2[(long long)pair * max_matches + i];
+            x1 = a.x; y1 = a.y; x2 = b.x; y2 = b.y;
+        } else {
+            float2 a = pts1[(long long)pair * max_matches + i], b = pts2[(long long)pair * max_matches + i];
+            x1 = ((double)a.x - cx) / fx; y1 = ((double)a.y - cy) / fy;
+            x2 = ((double)b.x - cx) / fx; y2 = ((double)b.y - cy) / fy;
+        }
         double P[3];
         g1 += triangulate_one(R1, tt, x1, y1, x2, y2, P);
         g2 += triangulate_one(R2, tt, x1, y1, x2, y2, P);
@@ -1102,7 +1148,9 @@ __global__ __launch_bounds__(256) void recover_pose_kernel(const double *__restr
 // Per-match results of the pose recover_pose_kernel returned (recoverPose's mask and triangulatedPoints, distanceThresh
 // 50): one block per pair, one candidate per match.  Entries past the pair's match count and every entry of a pair whose
 // status is not OK are zero.
+template <bool CAM>
 __global__ __launch_bounds__(256) void pose_structure_kernel(const float2 *__restrict__ pts1, const float2 *__restrict__ pts2,
+                                                              const double2 *__restrict__ n1, const double2 *__restrict__ n2,
                                                               const int *__restrict__ m_n, const int *__restrict__ status,
                                                               const double *__restrict__ K, const double *__restrict__ Rall,
                                                               const double *__restrict__ tall, uint8_t *__restrict__ pose_mask,
@@ -1115,15 +1163,22 @@ __global__ __launch_bounds__(256) void pose_structure_kernel(const float2 *__res
     for (int e = 0; e < 9; ++e) R[e] = Rall[pair * 9 + e];
 #pragma unroll
     for (int e = 0; e < 3; ++e) t[e] = tall[pair * 3 + e];
-    const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
+    double fx = 1., fy = 1., cx = 0., cy = 0.;
+    if (!CAM) { fx = K[0]; fy = K[4]; cx = K[2]; cy = K[5]; }
     for (int i = tid; i < max_matches; i += 256) {
         const long long o = (long long)pair * max_matches + i;
         double P[3] = {0., 0., 0.};
         int g = 0;
         if (i < M) {
-            float2 a = pts1[o], b = pts2[o];
-            double x1 = ((double)a.x - cx) / fx, y1 = ((double)a.y - cy) / fy;
-            double x2 = ((double)b.x - cx) / fx, y2 = ((double)b.y - cy) / fy;
+            double x1, y1, x2, y2;
+            if (CAM) {
+                const double2 a = n1[o], b = n2[o];
+                x1 = a.x; y1 = a.y; x2 = b.x; y2 = b.y;
+            } else {
+                float2 a = pts1[o], b = pts2[o];
+                x1 = ((double)a.x - cx) / fx; y1 = ((double)a.y - cy) / fy;
+                x2 = ((double)b.x - cx) / fx; y2 = ((double)b.y - cy) / fy;
+            }
             g = triangulate_one(R, t, x1, y1, x2, y2, P);
         }
         pose_mask[o] = (uint8_t)g;
@@ -1136,24 +1191,34 @@ __global__ __launch_bounds__(256) void pose_structure_kernel(const float2 *__res
 void rpe_launch_structure(rpe_handle *h, int B)
 {
     const int mm = h->cfg.max_matches;
-    hipLaunchKernelGGL(ransac_mask_kernel, dim3(B), dim3(256), 0, h->stream,
-                       h->d_n1, h->d_n2, h->d_rstate, h->d_K, h->cfg.ransac_threshold, (const int *)h->d_status, h->d_mask, mm);
-    hipLaunchKernelGGL(pose_structure_kernel, dim3(B), dim3(256), 0, h->stream,
-                       h->d_pts1, h->d_pts2, h->d_m_n, h->d_status, h->d_K, h->d_R, h->d_t, h->d_pose_mask, h->d_points, mm);
+    launch_mask(h, B, (const int *)h->d_status);
+    if (h->cam.cams)
+        hipLaunchKernelGGL(pose_structure_kernel<true>, dim3(B), dim3(256), 0, h->stream,
+                           h->d_pts1, h->d_pts2, h->d_n1, h->d_n2, h->d_m_n, h->d_status, h->d_K, h->d_R, h->d_t, h->d_pose_mask, h->d_points, mm);
+    else
+        hipLaunchKernelGGL(pose_structure_kernel<false>, dim3(B), dim3(256), 0, h->stream,
+                           h->d_pts1, h->d_pts2, h->d_n1, h->d_n2, h->d_m_n, h->d_status, h->d_K, h->d_R, h->d_t, h->d_pose_mask, h->d_points, mm);
 }
 
 void rpe_launch_pose(rpe_handle *h, int B, bool fused)
 {
     const RpeFeatSrc f = rpe_feat_src(h, B);
-    if (fused && f.tab)
-        hipLaunchKernelGGL(recover_pose_kernel<true>, dim3(B), dim3(256), 0, h->stream,
-                           h->d_E, h->d_pts1, h->d_pts2, h->d_m_n, h->d_found, f.count, f.img2_base, f.tab, h->d_K,
-                           h->d_R, h->d_t, h->d_inliers, h->d_status, h->cfg.max_matches);
-    else
-        hipLaunchKernelGGL(recover_pose_kernel<false>, dim3(B), dim3(256), 0, h->stream,
-                           h->d_E, h->d_pts1, h->d_pts2, h->d_m_n, fused ? h->d_found : (const int *)nullptr,
-                           fused ? f.count : (const int *)nullptr, f.img2_base, (const int2 *)nullptr, h->d_K,
-                           h->d_R, h->d_t, h->d_inliers, h->d_status, h->cfg.max_matches);
+    const int *found = fused ? h->d_found : (const int *)nullptr, *count = fused ? f.count : (const int *)nullptr;
+    // the camera instances read d_n1 / d_n2: ransac_prepare_kernel<true> (fused) or rpe_launch_camera_normalise (stage
+    // form) of the same call has filled them
+#define RPE_LAUNCH_POSE(TAB, CAM, FOUND, COUNT, TABP)                                                                    \
+    hipLaunchKernelGGL((recover_pose_kernel<TAB, CAM>), dim3(B), dim3(256), 0, h->stream,                                \
+                       h->d_E, h->d_pts1, h->d_pts2, h->d_n1, h->d_n2, h->d_m_n, FOUND, COUNT, f.img2_base, TABP, h->d_K, \
+                       h->d_R, h->d_t, h->d_inliers, h->d_status, h->cfg.max_matches)
+    const bool cam = h->cam.cams != nullptr;
+    if (fused && f.tab) {
+        if (cam) RPE_LAUNCH_POSE(true, true, h->d_found, f.count, f.tab);
+        else RPE_LAUNCH_POSE(true, false, h->d_found, f.count, f.tab);
+    } else {
+        if (cam) RPE_LAUNCH_POSE(false, true, found, count, (const int2 *)nullptr);
+        else RPE_LAUNCH_POSE(false, false, found, count, (const int2 *)nullptr);
+    }
+#undef RPE_LAUNCH_POSE
 }
 
 // ------------------------------------------------------------ pose refinement
@@ -1330,11 +1395,11 @@ __device__ __forceinline__ bool refine_solve(const double *H, const double *g, d
 }
 
 // status / inl_in may be null (stage form): every pair is then refined and the input pose's cheirality inliers are counted here
-template <bool LDS>
+template <bool LDS, bool CAM>
 __global__ __launch_bounds__(256) void pose_refine_kernel(const double2 *__restrict__ n1, const double2 *__restrict__ n2,
                                                            const uint8_t *__restrict__ mask, const int *__restrict__ m_n,
                                                            const int *__restrict__ status, const int *__restrict__ inl_in,
-                                                           const double *__restrict__ K, const double *__restrict__ Rin,
+                                                           const double *__restrict__ K, const RpeCamSrc cam, const double *__restrict__ Rin,
                                                            const double *__restrict__ tin, double *__restrict__ Rout,
                                                            double *__restrict__ tout, int *__restrict__ inl_out,
                                                            int *__restrict__ info, double *__restrict__ rms,
@@ -1375,7 +1440,7 @@ __global__ __launch_bounds__(256) void pose_refine_kernel(const double2 *__restr
     for (int e = 0; e < 9; ++e) R[e] = Rin[pair * 9 + e];
 #pragma unroll
     for (int e = 0; e < 3; ++e) t[e] = tin[pair * 3 + e];
-    const double scale = (K[0] + K[4]) / 2;
+    const double scale = rpe_pair_focal<CAM>(K, cam, pair);
     auto fetch = [&](int j, double2 &a, double2 &b) {
         if (LDS) { a = l1[j]; b = l2[j]; }
         else { const int i = s_idx[j]; a = gp1[i]; b = gp2[i]; }
@@ -1492,19 +1557,56 @@ __global__ __launch_bounds__(256) void pose_refine_kernel(const double2 *__restr
 }
 
 // normalised points of a stage call (the batch path leaves them in d_n1 / d_n2): same expression as ransac_prepare_kernel
+template <bool CAM>
 __global__ __launch_bounds__(256) void refine_normalise_kernel(const float2 *__restrict__ pts1, const float2 *__restrict__ pts2,
                                                                 const int *__restrict__ m_n, const double *__restrict__ K,
+                                                                const RpeCamSrc cam,
                                                                 double2 *__restrict__ n1, double2 *__restrict__ n2, int max_matches)
 {
     const int pair = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
     const int M = min(m_n[pair], max_matches);
-    const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
-    if (i < M) {
-        long long o = (long long)pair * max_matches + i;
-        float2 a = pts1[o], b = pts2[o];
-        n1[o] = make_double2(((double)a.x - cx) / fx, ((double)a.y - cy) / fy);
-        n2[o] = make_double2(((double)b.x - cx) / fx, ((double)b.y - cy) / fy);
+    if (CAM) {
+        const rpe_camera *c1, *c2;
+        rpe_pair_cameras(cam, pair, c1, c2);
+        const bool lens1 = rpe_camera_has_lens(c1), lens2 = rpe_camera_has_lens(c2);
+        if (i < M) {
+            long long o = (long long)pair * max_matches + i;
+            float2 a = pts1[o], b = pts2[o];
+            n1[o] = rpe_camera_normalise(c1, lens1, a);
+            n2[o] = rpe_camera_normalise(c2, lens2, b);
+        }
+    } else {
+        const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
+        if (i < M) {
+            long long o = (long long)pair * max_matches + i;
+            float2 a = pts1[o], b = pts2[o];
+            n1[o] = make_double2(((double)a.x - cx) / fx, ((double)a.y - cy) / fy);
+            n2[o] = make_double2(((double)b.x - cx) / fx, ((double)b.y - cy) / fy);
+        }
     }
+}
+
+// stage forms of the camera path (rpe_recover_pose_cameras, rpe_refine_pose_points_cameras): d_n1 / d_n2 of the uploaded points
+void rpe_launch_camera_normalise(rpe_handle *h, int B)
+{
+    const int mm = h->cfg.max_matches;
+    hipLaunchKernelGGL(refine_normalise_kernel<true>, dim3((mm + 255) / 256, B), dim3(256), 0, h->stream,
+                       h->d_pts1, h->d_pts2, h->d_m_n, h->d_K, h->cam, h->d_n1, h->d_n2, mm);
+}
+
+// rpe_undistort_points: n pixels of one camera -> normalised, undistorted coordinates; one thread per point, the camera a
+// uniform scalar load, one 16-byte store per point
+__global__ __launch_bounds__(256) void undistort_points_kernel(const float2 *__restrict__ pts, int n, const rpe_camera *__restrict__ cam,
+                                                                double2 *__restrict__ out)
+{
+    const bool lens = rpe_camera_has_lens(cam);
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < n; i += gridDim.x * 256) out[i] = rpe_camera_normalise(cam, lens, pts[i]);
+}
+
+void rpe_launch_undistort(rpe_handle *h, const float2 *d_pts, int n, const rpe_camera *d_cam, double2 *d_out)
+{
+    const int blocks = std::min((n + 255) / 256, 2048);
+    hipLaunchKernelGGL(undistort_points_kernel, dim3(blocks), dim3(256), 0, h->stream, d_pts, n, d_cam, d_out);
 }
 
 // after a batch / stream (from_batch): inliers = ransac_mask_kernel's mask of the winning model, start = d_R / d_t.
@@ -1512,20 +1614,24 @@ __global__ __launch_bounds__(256) void refine_normalise_kernel(const float2 *__r
 void rpe_launch_refine(rpe_handle *h, int B, int max_iters, bool from_batch)
 {
     const int mm = h->cfg.max_matches;
-    if (from_batch)
-        hipLaunchKernelGGL(ransac_mask_kernel, dim3(B), dim3(256), 0, h->stream,
-                           h->d_n1, h->d_n2, h->d_rstate, h->d_K, h->cfg.ransac_threshold, (const int *)h->d_status, h->d_mask, mm);
+    const bool cam = h->cam.cams != nullptr;
+    if (from_batch) launch_mask(h, B, (const int *)h->d_status);
+    else if (cam) rpe_launch_camera_normalise(h, B);
     else
-        hipLaunchKernelGGL(refine_normalise_kernel, dim3((mm + 255) / 256, B), dim3(256), 0, h->stream,
-                           h->d_pts1, h->d_pts2, h->d_m_n, h->d_K, h->d_n1, h->d_n2, mm);
+        hipLaunchKernelGGL(refine_normalise_kernel<false>, dim3((mm + 255) / 256, B), dim3(256), 0, h->stream,
+                           h->d_pts1, h->d_pts2, h->d_m_n, h->d_K, h->cam, h->d_n1, h->d_n2, mm);
     const double *Rin = from_batch ? h->d_R : h->d_ref_R0, *tin = from_batch ? h->d_t : h->d_ref_t0;
     const int *status = from_batch ? h->d_status : nullptr, *inl = from_batch ? h->d_inliers : nullptr;
-    if (mm <= REFINE_LDS_MATCHES)
-        hipLaunchKernelGGL(pose_refine_kernel<true>, dim3(B), dim3(256), sizeof(double2) * 2 * (size_t)mm, h->stream,
-                           h->d_n1, h->d_n2, h->d_mask, h->d_m_n, status, inl, h->d_K, Rin, tin,
-                           h->d_ref_R, h->d_ref_t, h->d_ref_inl, h->d_ref_info, h->d_ref_rms, mm, max_iters);
-    else
-        hipLaunchKernelGGL(pose_refine_kernel<false>, dim3(B), dim3(256), sizeof(unsigned short) * (size_t)mm, h->stream,
-                           h->d_n1, h->d_n2, h->d_mask, h->d_m_n, status, inl, h->d_K, Rin, tin,
-                           h->d_ref_R, h->d_ref_t, h->d_ref_inl, h->d_ref_info, h->d_ref_rms, mm, max_iters);
+#define RPE_LAUNCH_REFINE(LDS, CAM, BYTES)                                                                              \
+    hipLaunchKernelGGL((pose_refine_kernel<LDS, CAM>), dim3(B), dim3(256), BYTES, h->stream,                             \
+                       h->d_n1, h->d_n2, h->d_mask, h->d_m_n, status, inl, h->d_K, h->cam, Rin, tin,                      \
+                       h->d_ref_R, h->d_ref_t, h->d_ref_inl, h->d_ref_info, h->d_ref_rms, mm, max_iters)
+    if (mm <= REFINE_LDS_MATCHES) {
+        if (cam) RPE_LAUNCH_REFINE(true, true, sizeof(double2) * 2 * (size_t)mm);
+        else RPE_LAUNCH_REFINE(true, false, sizeof(double2) * 2 * (size_t)mm);
+    } else {
+        if (cam) RPE_LAUNCH_REFINE(false, true, sizeof(unsigned short) * (size_t)mm);
+        else RPE_LAUNCH_REFINE(false, false, sizeof(unsigned short) * (size_t)mm);
+    }
+#undef RPE_LAUNCH_REFINE
 }

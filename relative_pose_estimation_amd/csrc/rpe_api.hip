@@ -391,7 +391,7 @@ extern "C" int rpe_create(const rpe_config *cfg, rpe_handle **out)
 
 static void frames_free(rpe_handle::FrameStore &fs)
 {
-    void *ptrs[] = {fs.d_desc, fs.d_kp_pt, fs.d_norm, fs.d_count, fs.d_ovf};
+    void *ptrs[] = {fs.d_desc, fs.d_kp_pt, fs.d_norm, fs.d_count, fs.d_ovf, fs.d_cam};
     for (void *p : ptrs) if (p) hipFree(p);
     fs = rpe_handle::FrameStore();
 }
@@ -412,6 +412,7 @@ extern "C" void rpe_destroy(rpe_handle *h)
     if (h->h_resblk) hipHostFree(h->h_resblk);
     frames_free(h->fs);
     if (h->d_pairtab) hipFree(h->d_pairtab);
+    if (h->d_batch_cams) hipFree(h->d_batch_cams);
     if (h->h_pairtab) hipHostFree(h->h_pairtab);
     for (int i = 0; i < RPE_TAB_RING; ++i) if (h->ev_tab[i]) hipEventDestroy(h->ev_tab[i]);
     for (void *p : h->user_allocs) hipFree(p);
@@ -546,6 +547,7 @@ static int run_orb(rpe_handle *h, const uint8_t *d_a, const uint8_t *d_b, int na
 
 static int set_K(rpe_handle *h, const double K[9])
 {
+    h->cam = RpeCamSrc{nullptr, nullptr, 0};      // every single-K entry point comes through here: the launchers take the shared-K instances
     if (h->K_valid && memcmp(h->K_last, K, sizeof(double) * 9) == 0) return RPE_OK;      // same camera as the last batch: already resident
     memcpy(h->K_last, K, sizeof(double) * 9);
     h->K_valid = false;
@@ -979,21 +981,28 @@ extern "C" int rpe_frames_reserve(rpe_handle *h, int n_slots)
     if (n_slots == h->fs.cap) return RPE_OK;
     HIPCHK(h, hipStreamSynchronize(h->stream));            // nothing in flight reads the store that is about to go
     h->last_tab.clear();                                   // slot numbers of the last pair list: rpe_fetch_overflow refuses from here on
+    if (h->cam.tab) {                                      // a camera pair list reads the store's camera records: its per-match results end here
+        h->cam = RpeCamSrc{nullptr, nullptr, 0};
+        h->structure_valid = false;
+    }
     if (n_slots == 0) { frames_free(h->fs); return RPE_OK; }
     const size_t kcap = (size_t)h->lay.kcap, db = (size_t)h->desc_bytes, N = (size_t)n_slots;
     const bool l2 = frames_keep_norms(h);
     rpe_handle::FrameStore nf;
     bool ok = hipMalloc((void **)&nf.d_desc, N * kcap * db) == hipSuccess && hipMalloc((void **)&nf.d_kp_pt, N * kcap * sizeof(float2)) == hipSuccess &&
               (!l2 || hipMalloc((void **)&nf.d_norm, N * kcap * sizeof(int2)) == hipSuccess) &&
-              hipMalloc((void **)&nf.d_count, N * sizeof(int)) == hipSuccess && hipMalloc((void **)&nf.d_ovf, N * sizeof(unsigned)) == hipSuccess;
+              hipMalloc((void **)&nf.d_count, N * sizeof(int)) == hipSuccess && hipMalloc((void **)&nf.d_ovf, N * sizeof(unsigned)) == hipSuccess &&
+              hipMalloc((void **)&nf.d_cam, N * sizeof(rpe_camera)) == hipSuccess;
     const size_t keep = (size_t)(h->fs.cap < n_slots ? h->fs.cap : n_slots);
-    ok = ok && hipMemsetAsync(nf.d_count, 0, N * sizeof(int), h->stream) == hipSuccess && hipMemsetAsync(nf.d_ovf, 0, N * sizeof(unsigned), h->stream) == hipSuccess;
+    ok = ok && hipMemsetAsync(nf.d_count, 0, N * sizeof(int), h->stream) == hipSuccess && hipMemsetAsync(nf.d_ovf, 0, N * sizeof(unsigned), h->stream) == hipSuccess &&
+         hipMemsetAsync(nf.d_cam, 0, N * sizeof(rpe_camera), h->stream) == hipSuccess;
     if (ok && keep) {
         ok = hipMemcpyAsync(nf.d_desc, h->fs.d_desc, keep * kcap * db, hipMemcpyDeviceToDevice, h->stream) == hipSuccess &&
              hipMemcpyAsync(nf.d_kp_pt, h->fs.d_kp_pt, keep * kcap * sizeof(float2), hipMemcpyDeviceToDevice, h->stream) == hipSuccess &&
              (!l2 || hipMemcpyAsync(nf.d_norm, h->fs.d_norm, keep * kcap * sizeof(int2), hipMemcpyDeviceToDevice, h->stream) == hipSuccess) &&
              hipMemcpyAsync(nf.d_count, h->fs.d_count, keep * sizeof(int), hipMemcpyDeviceToDevice, h->stream) == hipSuccess &&
-             hipMemcpyAsync(nf.d_ovf, h->fs.d_ovf, keep * sizeof(unsigned), hipMemcpyDeviceToDevice, h->stream) == hipSuccess;
+             hipMemcpyAsync(nf.d_ovf, h->fs.d_ovf, keep * sizeof(unsigned), hipMemcpyDeviceToDevice, h->stream) == hipSuccess &&
+             hipMemcpyAsync(nf.d_cam, h->fs.d_cam, keep * sizeof(rpe_camera), hipMemcpyDeviceToDevice, h->stream) == hipSuccess;
     }
     ok = ok && hipStreamSynchronize(h->stream) == hipSuccess;
     if (!ok) {
@@ -1006,7 +1015,9 @@ extern "C" int rpe_frames_reserve(rpe_handle *h, int n_slots)
     }
     nf.cap = n_slots;
     nf.filled.assign(N, 0);
-    for (size_t i = 0; i < keep; ++i) nf.filled[i] = h->fs.filled[i];
+    nf.has_cam.assign(N, 0);
+    nf.h_cam.assign(N, rpe_camera{});
+    for (size_t i = 0; i < keep; ++i) { nf.filled[i] = h->fs.filled[i]; nf.has_cam[i] = h->fs.has_cam[i]; nf.h_cam[i] = h->fs.h_cam[i]; }
     rpe_handle::FrameStore old = h->fs;
     h->fs = nf;
     frames_free(old);
@@ -1114,19 +1125,22 @@ extern "C" int rpe_frames_info(rpe_handle *h, int n, const int32_t *slots, int32
     return RPE_OK;
 }
 
-extern "C" int rpe_enqueue_pairs(rpe_handle *h, const int32_t *slot1, const int32_t *slot2, int P, const double K[9])
+// K == nullptr: the camera form, every pair on the cameras of its two slots
+static int enqueue_pairs_run(rpe_handle *h, const int32_t *slot1, const int32_t *slot2, int P, const double *K, const char *who)
 {
-    if (!h || !slot1 || !slot2 || !K || P < 1) { if (h) h->err = "rpe_enqueue_pairs: null argument or P < 1"; return RPE_ERR_INVALID; }
-    if (P > h->cfg.max_batch) { h->err = "rpe_enqueue_pairs: pair list exceeds max_batch"; return RPE_ERR_CAPACITY; }
-    if (h->fs.cap == 0) { h->err = "rpe_enqueue_pairs: no frame store (rpe_frames_reserve)"; return RPE_ERR_INVALID; }
+    const std::string w(who);
+    if (P > h->cfg.max_batch) { h->err = w + ": pair list exceeds max_batch"; return RPE_ERR_CAPACITY; }
+    if (h->fs.cap == 0) { h->err = w + ": no frame store (rpe_frames_reserve)"; return RPE_ERR_INVALID; }
     for (int p = 0; p < P; ++p) {
-        if (slot1[p] < 0 || slot1[p] >= h->fs.cap || slot2[p] < 0 || slot2[p] >= h->fs.cap) { h->err = "rpe_enqueue_pairs: slot outside the store"; return RPE_ERR_INVALID; }
-        if (!h->fs.filled[(size_t)slot1[p]] || !h->fs.filled[(size_t)slot2[p]]) { h->err = "rpe_enqueue_pairs: a pair names an empty slot"; return RPE_ERR_INVALID; }
+        if (slot1[p] < 0 || slot1[p] >= h->fs.cap || slot2[p] < 0 || slot2[p] >= h->fs.cap) { h->err = w + ": slot outside the store"; return RPE_ERR_INVALID; }
+        if (!h->fs.filled[(size_t)slot1[p]] || !h->fs.filled[(size_t)slot2[p]]) { h->err = w + ": a pair names an empty slot"; return RPE_ERR_INVALID; }
+        if (!K && (!h->fs.has_cam[(size_t)slot1[p]] || !h->fs.has_cam[(size_t)slot2[p]])) { h->err = w + ": a pair names a slot without a camera (rpe_frames_set_cameras)"; return RPE_ERR_INVALID; }
     }
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    int rc = set_K(h, K);
-    if (rc) return rc;
+    int rc = RPE_OK;
+    if (K && (rc = set_K(h, K)) != RPE_OK) return rc;
     if ((rc = upload_table(h, slot1, slot2, P)) != RPE_OK) return rc;
+    if (!K) h->cam = RpeCamSrc{h->fs.d_cam, (const int2 *)h->d_pairtab, 0};
     struct Guard {                          // the launchers read h->pair_tab; never leave it behind for a batch
         rpe_handle *h; ~Guard() { h->pair_tab = nullptr; }
     } guard{h};
@@ -1148,6 +1162,12 @@ extern "C" int rpe_enqueue_pairs(rpe_handle *h, const int32_t *slot1, const int3
     HIPCHK(h, hipGetLastError());
     h->structure_valid = true;
     return RPE_OK;
+}
+
+extern "C" int rpe_enqueue_pairs(rpe_handle *h, const int32_t *slot1, const int32_t *slot2, int P, const double K[9])
+{
+    if (!h || !slot1 || !slot2 || !K || P < 1) { if (h) h->err = "rpe_enqueue_pairs: null argument or P < 1"; return RPE_ERR_INVALID; }
+    return enqueue_pairs_run(h, slot1, slot2, P, K, "rpe_enqueue_pairs");
 }
 
 extern "C" int rpe_estimate_pairs(rpe_handle *h, const int32_t *slot1, const int32_t *slot2, int P, const double K[9],
@@ -1342,6 +1362,203 @@ extern "C" int rpe_refine_pose_points(rpe_handle *h, const double *h_R0, const d
     int rc = upload_points(h, h_pts1, h_pts2, m, B);
     if (rc) return rc;
     if ((rc = set_K(h, K)) != RPE_OK) return rc;
+    if ((rc = refine_alloc(h)) != RPE_OK) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->d_mask, h_mask, (size_t)h->cfg.max_matches * B, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_ref_R0, h_R0, sizeof(double) * 9 * B, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_ref_t0, h_t0, sizeof(double) * 3 * B, hipMemcpyHostToDevice, h->stream));
+    return refine_run(h, B, max_iters, false, R, t, inliers, info, rms);
+}
+
+// ---------------------------------------------------------------- camera models
+// rpe_*_cameras (NOT in the reference): a camera per frame instead of one K per call.  The entry points validate, place
+// the camera records where the kernels find them -- 2 B records per batch / stage call in d_batch_cams, one record per
+// frame-store slot in fs.d_cam -- and set h->cam, which makes the launchers of geom_kernels.hip take the camera instances.
+static int check_cameras(rpe_handle *h, const rpe_camera *c, int n, const char *who)
+{
+    for (int i = 0; i < n; ++i) {
+        const double *f = &c[i].fx;                     // fx fy cx cy dist[8]: twelve doubles
+        bool fin = true;
+        for (int k = 0; k < 12; ++k) fin = fin && std::isfinite(f[k]);
+        if (!fin) { h->err = std::string(who) + ": a camera has a non-finite field"; return RPE_ERR_INVALID; }
+        if (!(c[i].fx > 0.) || !(c[i].fy > 0.)) { h->err = std::string(who) + ": a camera has fx <= 0 or fy <= 0"; return RPE_ERR_INVALID; }
+    }
+    return RPE_OK;
+}
+
+// cam1[0, B) then cam2[0, B): the image-slot order of a batch (pair p = records p and B + p)
+static int upload_batch_cameras(rpe_handle *h, const rpe_camera *cam1, const rpe_camera *cam2, int B)
+{
+    const size_t cap = (size_t)2 * h->cfg.max_batch;
+    if (!h->d_batch_cams) {
+        HIPCHK(h, hipMalloc((void **)&h->d_batch_cams, cap * sizeof(rpe_camera)));
+        h->h_batch_cams.resize(cap);
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));      // nothing in flight reads the records or their staging
+    memcpy(h->h_batch_cams.data(), cam1, sizeof(rpe_camera) * (size_t)B);
+    memcpy(h->h_batch_cams.data() + B, cam2, sizeof(rpe_camera) * (size_t)B);
+    HIPCHK(h, hipMemcpyAsync(h->d_batch_cams, h->h_batch_cams.data(), sizeof(rpe_camera) * 2 * (size_t)B, hipMemcpyHostToDevice, h->stream));
+    h->cam = RpeCamSrc{h->d_batch_cams, nullptr, B};
+    return RPE_OK;
+}
+
+extern "C" int rpe_frames_set_cameras(rpe_handle *h, int n, const int32_t *slots, const rpe_camera *cams)
+{
+    if (!h || !slots || !cams || n < 1) { if (h) h->err = "rpe_frames_set_cameras: null argument or n < 1"; return RPE_ERR_INVALID; }
+    if (h->fs.cap == 0) { h->err = "rpe_frames_set_cameras: no frame store (rpe_frames_reserve)"; return RPE_ERR_INVALID; }
+    for (int i = 0; i < n; ++i) if (slots[i] < 0 || slots[i] >= h->fs.cap) { h->err = "rpe_frames_set_cameras: slot outside the store"; return RPE_ERR_INVALID; }
+    int rc = check_cameras(h, cams, n, "rpe_frames_set_cameras");
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipStreamSynchronize(h->stream));      // a pair list in flight may read the records about to change
+    if (h->cam.tab) { h->cam = RpeCamSrc{nullptr, nullptr, 0}; h->structure_valid = false; }
+    for (int i = 0; i < n; ++i) {
+        const size_t s = (size_t)slots[i];
+        h->fs.h_cam[s] = cams[i];
+        h->fs.has_cam[s] = 1;
+        HIPCHK(h, hipMemcpyAsync(h->fs.d_cam + s, &h->fs.h_cam[s], sizeof(rpe_camera), hipMemcpyHostToDevice, h->stream));
+    }
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return RPE_OK;
+}
+
+extern "C" int rpe_enqueue_pairs_cameras(rpe_handle *h, const int32_t *slot1, const int32_t *slot2, int P)
+{
+    if (!h || !slot1 || !slot2 || P < 1) { if (h) h->err = "rpe_enqueue_pairs_cameras: null argument or P < 1"; return RPE_ERR_INVALID; }
+    return enqueue_pairs_run(h, slot1, slot2, P, nullptr, "rpe_enqueue_pairs_cameras");
+}
+
+extern "C" int rpe_estimate_pairs_cameras(rpe_handle *h, const int32_t *slot1, const int32_t *slot2, int P,
+                                          double *R, double *t, int32_t *inliers, int32_t *n_matches, int32_t *status)
+{
+    int rc = rpe_enqueue_pairs_cameras(h, slot1, slot2, P);
+    if (rc) return rc;
+    return rpe_fetch_results(h, P, R, t, inliers, n_matches, status);
+}
+
+extern "C" int rpe_enqueue_batch_cameras_device(rpe_handle *h, const uint8_t *d_imgs1, const uint8_t *d_imgs2, int B,
+                                                const rpe_camera *cam1, const rpe_camera *cam2)
+{
+    if (!h || !d_imgs1 || !d_imgs2 || !cam1 || !cam2 || B < 1) { if (h) h->err = "rpe_enqueue_batch_cameras_device: null argument or B < 1"; return RPE_ERR_INVALID; }
+    if (B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return RPE_ERR_CAPACITY; }
+    int rc = check_cameras(h, cam1, B, "rpe_enqueue_batch_cameras_device");
+    if (!rc) rc = check_cameras(h, cam2, B, "rpe_enqueue_batch_cameras_device");
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if ((rc = upload_batch_cameras(h, cam1, cam2, B)) != RPE_OK) return rc;
+    return run_pairs(h, d_imgs1, d_imgs2, B, B, B, B);          // plain launches whatever B: the captured graphs hold the shared-K instances
+}
+
+extern "C" int rpe_estimate_batch_cameras_device(rpe_handle *h, const uint8_t *d_imgs1, const uint8_t *d_imgs2, int B,
+                                                 const rpe_camera *cam1, const rpe_camera *cam2, double *R, double *t,
+                                                 int32_t *inliers, int32_t *n_matches, int32_t *status)
+{
+    int rc = rpe_enqueue_batch_cameras_device(h, d_imgs1, d_imgs2, B, cam1, cam2);
+    if (rc) return rc;
+    return rpe_fetch_results(h, B, R, t, inliers, n_matches, status);
+}
+
+extern "C" int rpe_estimate_batch_cameras(rpe_handle *h, const uint8_t *h_imgs1, const uint8_t *h_imgs2, int B,
+                                          const rpe_camera *cam1, const rpe_camera *cam2, double *R, double *t,
+                                          int32_t *inliers, int32_t *n_matches, int32_t *status)
+{
+    if (!h || !h_imgs1 || !h_imgs2 || !cam1 || !cam2 || B < 1) { if (h) h->err = "rpe_estimate_batch_cameras: null argument or B < 1"; return RPE_ERR_INVALID; }
+    if (B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return RPE_ERR_CAPACITY; }
+    const size_t img = (size_t)h->cfg.width * h->cfg.height;
+    if (B >= 512 && img * (size_t)B >= ((size_t)64 << 20)) {
+        h->err = "rpe_estimate_batch_cameras: host batches this large (B >= 512 and >= 64 MiB per image set) are not chunked by the camera form: upload the images and call rpe_estimate_batch_cameras_device";
+        return RPE_ERR_INVALID;
+    }
+    int rc = check_cameras(h, cam1, B, "rpe_estimate_batch_cameras");
+    if (!rc) rc = check_cameras(h, cam2, B, "rpe_estimate_batch_cameras");
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipMemcpyAsync(h->d_stage1, h_imgs1, img * B, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_stage2, h_imgs2, img * B, hipMemcpyHostToDevice, h->stream));
+    return rpe_estimate_batch_cameras_device(h, h->d_stage1, h->d_stage2, B, cam1, cam2, R, t, inliers, n_matches, status);
+}
+
+extern "C" int rpe_undistort_points(rpe_handle *h, const float *h_pts, int n, const rpe_camera *cam, double *h_out_xy)
+{
+    if (!h || !h_pts || !cam || !h_out_xy || n < 1) { if (h) h->err = "rpe_undistort_points: null argument or n < 1"; return RPE_ERR_INVALID; }
+    int rc = check_cameras(h, cam, 1, "rpe_undistort_points");
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    void *d_in = nullptr, *d_out = nullptr, *d_cam = nullptr;
+    const size_t nb_in = sizeof(float2) * (size_t)n, nb_out = sizeof(double2) * (size_t)n;
+    bool ok = hipMalloc(&d_in, nb_in) == hipSuccess && hipMalloc(&d_out, nb_out) == hipSuccess && hipMalloc(&d_cam, sizeof(rpe_camera)) == hipSuccess;
+    ok = ok && hipMemcpyAsync(d_in, h_pts, nb_in, hipMemcpyHostToDevice, h->stream) == hipSuccess &&
+         hipMemcpyAsync(d_cam, cam, sizeof(rpe_camera), hipMemcpyHostToDevice, h->stream) == hipSuccess;
+    if (ok) {
+        rpe_launch_undistort(h, (const float2 *)d_in, n, (const rpe_camera *)d_cam, (double2 *)d_out);
+        ok = hipGetLastError() == hipSuccess && hipMemcpyAsync(h_out_xy, d_out, nb_out, hipMemcpyDeviceToHost, h->stream) == hipSuccess;
+    }
+    ok = (hipStreamSynchronize(h->stream) == hipSuccess) && ok;
+    if (d_in) hipFree(d_in);
+    if (d_out) hipFree(d_out);
+    if (d_cam) hipFree(d_cam);
+    if (!ok) { (void)hipGetLastError(); h->err = "rpe_undistort_points: HIP failure"; return RPE_ERR_HIP; }
+    return RPE_OK;
+}
+
+// common head of the three stage forms: arguments, points, cameras
+static int stage_cameras_begin(rpe_handle *h, const float *p1, const float *p2, const int32_t *m, int B,
+                               const rpe_camera *cam1, const rpe_camera *cam2, const char *who)
+{
+    if (B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return RPE_ERR_CAPACITY; }
+    int rc = check_cameras(h, cam1, B, who);
+    if (!rc) rc = check_cameras(h, cam2, B, who);
+    if (rc) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    h->structure_valid = false;                 // overwrites buffers rpe_fetch_structure reads
+    if ((rc = upload_batch_cameras(h, cam1, cam2, B)) != RPE_OK) return rc;
+    return upload_points(h, p1, p2, m, B);
+}
+
+extern "C" int rpe_find_essential_cameras(rpe_handle *h, const float *h_pts1, const float *h_pts2, const int32_t *m, int B,
+                                          const rpe_camera *cam1, const rpe_camera *cam2, double *E, uint8_t *mask,
+                                          int32_t *found, int32_t *info)
+{
+    if (!h || !h_pts1 || !h_pts2 || !m || !cam1 || !cam2 || B < 1) return RPE_ERR_INVALID;
+    int rc = stage_cameras_begin(h, h_pts1, h_pts2, m, B, cam1, cam2, "rpe_find_essential_cameras");
+    if (rc) return rc;
+    HIPCHK(h, hipMemsetAsync(h->d_E, 0, sizeof(double) * 9 * B, h->stream));
+    rpe_launch_ransac(h, B, true);
+    HIPCHK(h, hipGetLastError());
+    std::vector<RpeRansacState> st(B);
+    HIPCHK(h, hipMemcpyAsync(st.data(), h->d_rstate, sizeof(RpeRansacState) * B, hipMemcpyDeviceToHost, h->stream));
+    if (mask) HIPCHK(h, hipMemcpyAsync(mask, h->d_mask, (size_t)h->cfg.max_matches * B, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int i = 0; i < B; ++i) {
+        if (E) memcpy(E + 9 * i, st[i].E, sizeof(double) * 9);
+        if (found) found[i] = st[i].found;
+        if (info) { info[4 * i] = st[i].best_count; info[4 * i + 1] = st[i].best_iter; info[4 * i + 2] = st[i].best_model; info[4 * i + 3] = st[i].iters_run; }
+    }
+    return RPE_OK;
+}
+
+extern "C" int rpe_recover_pose_cameras(rpe_handle *h, const double *h_E, const float *h_pts1, const float *h_pts2,
+                                        const int32_t *m, int B, const rpe_camera *cam1, const rpe_camera *cam2,
+                                        double *R, double *t, int32_t *inliers)
+{
+    if (!h || !h_E || !h_pts1 || !h_pts2 || !m || !cam1 || !cam2 || B < 1) return RPE_ERR_INVALID;
+    int rc = stage_cameras_begin(h, h_pts1, h_pts2, m, B, cam1, cam2, "rpe_recover_pose_cameras");
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->d_E, h_E, sizeof(double) * 9 * B, hipMemcpyHostToDevice, h->stream));
+    rpe_launch_camera_normalise(h, B);          // recover_pose_kernel's camera instances read d_n1 / d_n2
+    rpe_launch_pose(h, B, false);
+    HIPCHK(h, hipGetLastError());
+    return rpe_fetch_results(h, B, R, t, inliers, nullptr, nullptr);
+}
+
+extern "C" int rpe_refine_pose_points_cameras(rpe_handle *h, const double *h_R0, const double *h_t0, const float *h_pts1,
+                                              const float *h_pts2, const uint8_t *h_mask, const int32_t *m, int B,
+                                              const rpe_camera *cam1, const rpe_camera *cam2, int max_iters, double *R, double *t,
+                                              int32_t *inliers, int32_t *info, double *rms)
+{
+    if (!h || !h_R0 || !h_t0 || !h_pts1 || !h_pts2 || !h_mask || !m || !cam1 || !cam2 || B < 1) return RPE_ERR_INVALID;
+    if (max_iters < 1 || max_iters > 100) { h->err = "rpe_refine_pose_points_cameras: max_iters must be 1 ... 100"; return RPE_ERR_INVALID; }
+    int rc = stage_cameras_begin(h, h_pts1, h_pts2, m, B, cam1, cam2, "rpe_refine_pose_points_cameras");
+    if (rc) return rc;
     if ((rc = refine_alloc(h)) != RPE_OK) return rc;
     HIPCHK(h, hipMemcpyAsync(h->d_mask, h_mask, (size_t)h->cfg.max_matches * B, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->d_ref_R0, h_R0, sizeof(double) * 9 * B, hipMemcpyHostToDevice, h->stream));

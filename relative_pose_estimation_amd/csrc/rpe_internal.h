@@ -78,6 +78,65 @@ __device__ __forceinline__ void rpe_pair_slots(const int2 *__restrict__ tab, int
     else { img1 = pair; img2 = img2_base + pair; }
 }
 
+// Camera source of the geometry kernels (rpe_*_cameras calls).  Every kernel that uses intrinsics carries a template
+// switch CAM next to this argument, the pattern of rpe_pair_slots: CAM = false reads the shared d_K and is the instance
+// every single-K path launches (the argument is then never read); CAM = true takes the two cameras of pair `pair` from
+// `cams`: records (pair, img2_base + pair) of a batch's 2 B uploaded cameras, or, with `tab`, the frame store's per-slot
+// records named by entry `pair` of the pair list's device table.  `pair` comes from the workgroup index and the rest
+// from kernel arguments, so the 96-byte records are read with scalar loads, once per workgroup.
+struct RpeCamSrc { const rpe_camera *cams; const int2 *tab; int img2_base; };
+
+__device__ __forceinline__ void rpe_pair_cameras(const RpeCamSrc &src, int pair, const rpe_camera *&c1, const rpe_camera *&c2)
+{
+    int i1 = pair, i2 = src.img2_base + pair;
+    if (src.tab) { const int2 s = src.tab[pair]; i1 = s.x; i2 = s.y; }
+    c1 = src.cams + i1; c2 = src.cams + i2;
+}
+
+// The focal length used as a scale (RANSAC threshold, pixel scale of the refinement): (fx + fy) / 2 of K, or the mean
+// of that over the pair's two cameras -- (a + a) / 2 == a, so equal cameras give the single-K bits
+template <bool CAM>
+__device__ __forceinline__ double rpe_pair_focal(const double *__restrict__ K, const RpeCamSrc &src, int pair)
+{
+    if (CAM) {
+        const rpe_camera *c1, *c2;
+        rpe_pair_cameras(src, pair, c1, c2);
+        return (((c1->fx + c1->fy) / 2) + ((c2->fx + c2->fy) / 2)) / 2;
+    } else {
+        const double fx = K[0], fy = K[4];
+        return (fx + fy) / 2;
+    }
+}
+
+__device__ __forceinline__ bool rpe_camera_has_lens(const rpe_camera *c)
+{
+    bool lens = false;
+#pragma unroll
+    for (int k = 0; k < 8; ++k) lens = lens || c->dist[k] != 0.;
+    return lens;
+}
+
+// Normalised, undistorted coordinates of pixel p (include/rpe_amd.h, "camera models"): the single-K expression, then
+// RPE_UNDISTORT_ITERS rounds of cv2.undistortPoints' fixed-point iteration when the camera has a lens.  Operation order
+// of tests/camera_model.py; the build has no contraction, so the two agree bit for bit.
+__device__ __forceinline__ double2 rpe_camera_normalise(const rpe_camera *c, bool lens, float2 p)
+{
+    const double xd = ((double)p.x - c->cx) / c->fx, yd = ((double)p.y - c->cy) / c->fy;
+    double x = xd, y = yd;
+    if (lens) {
+        const double k1 = c->dist[0], k2 = c->dist[1], p1 = c->dist[2], p2 = c->dist[3];
+        const double k3 = c->dist[4], k4 = c->dist[5], k5 = c->dist[6], k6 = c->dist[7];
+#pragma unroll
+        for (int it = 0; it < RPE_UNDISTORT_ITERS; ++it) {
+            const double r2 = x * x + y * y;
+            const double icd = (1 + r2 * (k4 + r2 * (k5 + r2 * k6))) / (1 + r2 * (k1 + r2 * (k2 + r2 * k3)));
+            const double dx = 2 * p1 * x * y + p2 * (r2 + 2 * x * x), dy = p1 * (r2 + 2 * y * y) + 2 * p2 * x * y;
+            x = (xd - dx) * icd; y = (yd - dy) * icd;
+        }
+    }
+    return make_double2(x, y);
+}
+
 // Inclusive prefix operations over the 64 lanes with DPP row shifts / row broadcasts: 6 v_<op>_dpp instead of 6 rounds of
 // ds_bpermute + select + op (~30 vector + LDS instructions).  Shifted-out lanes read the `old` operand, the identity.
 // The wave total is the value of lane 63 (__builtin_amdgcn_readlane(x, 63)).
@@ -228,6 +287,9 @@ struct rpe_handle {
         int *d_count = nullptr;           // [slot] keypoints (0 for a slot never filled)
         unsigned *d_ovf = nullptr;        // [slot] RPE_OVF_* flags of the extraction that filled the slot
         std::vector<uint8_t> filled;      // [slot] host side: the slot holds a frame (argument checks never read the device)
+        rpe_camera *d_cam = nullptr;      // [slot] camera of the slot's frame (rpe_frames_set_cameras)
+        std::vector<rpe_camera> h_cam;    // [slot] host mirror: source of the uploads, kept across rpe_frames_reserve
+        std::vector<uint8_t> has_cam;     // [slot] host side: the slot has been given a camera
     } fs;
     int *h_pairtab = nullptr;             // pinned, RPE_TAB_RING pieces of 2*max_batch ints: slot list of a put / (slot1, slot2) table of a pair list
     int *d_pairtab = nullptr;             // device copy, uploaded on the handle's stream
@@ -236,6 +298,11 @@ struct rpe_handle {
     const int2 *pair_tab = nullptr;       // set by rpe_enqueue_pairs around its launches: the matchers and the status test read the store
     bool last_from_store = false;         // the last batch was a pair list: rpe_fetch_overflow reads last_tab and the store's flags
     std::vector<int> last_tab;            // its (slot1, slot2) entries
+    // Camera path (rpe_*_cameras): set by those calls and left standing, so that rpe_fetch_structure / rpe_refine_poses
+    // launch the camera instances for "the last batch"; every single-K entry point clears it (set_K)
+    RpeCamSrc cam{nullptr, nullptr, 0};
+    rpe_camera *d_batch_cams = nullptr;   // [2*max_batch] cameras of a camera batch / stage call: cam1[0, B) then cam2[0, B) (created on first use)
+    std::vector<rpe_camera> h_batch_cams; // their host staging
     // profiling
     bool profiling = false;
     hipEvent_t ev[RPE_STAGE_COUNT + 1] = {};
@@ -277,6 +344,8 @@ void rpe_launch_ransac(rpe_handle *h, int B, bool want_mask);
 void rpe_launch_pose(rpe_handle *h, int B, bool set_status);
 void rpe_launch_structure(rpe_handle *h, int B);
 void rpe_launch_refine(rpe_handle *h, int B, int max_iters, bool from_batch);
+void rpe_launch_camera_normalise(rpe_handle *h, int B);
+void rpe_launch_undistort(rpe_handle *h, const float2 *d_pts, int n, const rpe_camera *d_cam, double2 *d_out);
 
 // per-stage hipEvents on the handle's stream (rpe_set_profiling / rpe_get_stage_ms)
 #define MARK(h, stage) do { if ((h)->profiling) hipEventRecord((h)->ev[stage], (h)->stream); } while (0)

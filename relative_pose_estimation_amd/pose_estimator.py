@@ -5,7 +5,8 @@ defaults (:19-32), estimate(img1, img2, R_prev=None) -> (R, t) (:487-569),
 estimate_with_debug(...) -> dict with the reference's keys (:571-688, dict
 :624-633), same exception types and messages (:96, :129, :508-509, :514-515,
 :529-530).  Added: estimate_batch() for many pairs per call; estimate_with_structure() / last_structure() for the
-per-match inlier masks and triangulated points.
+per-match inlier masks and triangulated points; `dist_coeffs` / Camera for lens distortion and per-frame cameras
+(the camera path: matched points are undistorted on the GPU before the geometry stages).
 
 Scope: the feature -> match -> essential -> pose path on the GPU: ORB or SIFT features, Hamming or L2 matcher
 (every combination cv2 can run: ORB + Hamming, ORB + L2, SIFT + L2; SIFT + Hamming constructs, as in the reference,
@@ -55,6 +56,7 @@ class FrameStore:
         if int(capacity) < 1:
             raise ValueError("FrameStore: capacity must be >= 1")
         self._est, self.capacity, self._eng = estimator, int(capacity), None
+        self._has_cam = np.zeros(self.capacity, bool)      # slots that were given a camera
 
     def _engine(self, shape):
         if self._eng is None:
@@ -70,12 +72,19 @@ class FrameStore:
             raise ValueError(f"FrameStore: frames are {self._eng.height} x {self._eng.width}, got {tuple(shape)}")
         return self._eng
 
-    def put(self, slot, image):
-        self.put_many([slot], self._est._gray(image)[None])
+    def put(self, slot, image, camera=None):
+        self.put_many([slot], self._est._gray(image)[None], None if camera is None else [camera])
 
-    def put_many(self, slots, images):
+    def put_many(self, slots, images, cameras=None):
+        """cameras: None (the slots keep whatever camera they have; with none they run on the estimator's K), one Camera
+        for all the frames, or one per frame.  An estimator built with dist_coeffs gives its camera to every frame put
+        without one."""
         slots = np.asarray(slots)
         images = np.asarray(images)
+        if cameras is None and self._est._camera is not None:
+            cameras = self._est._camera
+        if cameras is not None:
+            cameras = _capi.camera_records(cameras, slots.size)         # ValueError before any device call
         if slots.ndim != 1 or slots.dtype.kind not in "iu" or images.ndim != 3 or images.dtype != np.uint8 or images.shape[0] != slots.size:
             raise ValueError("put_many: expected n integer slots and n uint8 grayscale images [n, H, W]")
         if slots.size == 0 or (slots < 0).any() or (slots >= self.capacity).any() or np.unique(slots).size != slots.size:
@@ -84,16 +93,23 @@ class FrameStore:
         step = 2 * eng.max_batch
         for a in range(0, slots.size, step):
             eng.frames_put(images[a:a + step], slots[a:a + step])
+        if cameras is not None:
+            eng.frames_set_cameras(slots, cameras)
+            self._has_cam[slots] = True
 
     def estimate(self, pairs):
         """(R[P,3,3], t[P,3,1], inliers[P], n_matches[P], status[P]) of the slot pairs [P, 2]; a failing pair never
         aborts the list.  last_structure / last_refined / last_overflow of the estimator describe the last chunk of
-        at most max_batch pairs."""
+        at most max_batch pairs.  The slots' own cameras are used when every slot the list names has one, the
+        estimator's K when none has; a list that mixes the two is a ValueError."""
         pairs = _check_pairs(pairs, self.capacity, "slot")
+        named = self._has_cam[np.unique(pairs)]
+        if named.any() and not named.all():
+            raise ValueError("FrameStore.estimate: the pair list mixes slots with a camera and slots without one")
         if self._eng is None:
             raise _capi.RpeError("FrameStore: nothing has been put yet")
         eng = self._engine((self._eng.height, self._eng.width))
-        return self._est._run_pair_list(eng, pairs)
+        return self._est._run_pair_list(eng, pairs, cameras=bool(named.all()))
 
     def info(self, slots):
         """(keypoint counts, OVF_* flags) of the slots; count -1 = never filled"""
@@ -129,8 +145,15 @@ class PoseEstimator:
                  device=0,
                  max_batch=1,
                  ratio=None,
-                 keypoint_order="libstdc++"):
+                 keypoint_order="libstdc++",
+                 *,
+                 dist_coeffs=None):
         self.K = np.asarray(camera_matrix, dtype=np.float64)
+        # dist_coeffs (cv2 order, 4 / 5 / 8 values; NOT in the reference): every estimate runs the camera path with
+        # Camera(K, dist_coeffs) for every frame.  None = the single-K calls, untouched.
+        self._camera = None if dist_coeffs is None else _capi.Camera(self.K, dist_coeffs)
+        if self._camera is not None and use_vp_refinement:
+            raise ValueError("use_vp_refinement works on image lines, which a lens bends: it cannot be combined with dist_coeffs")
         self.feature_method = feature_method
         self.norm_type = norm_type
         self.max_matches = max_matches
@@ -221,24 +244,40 @@ class PoseEstimator:
             raise ValueError("expected a 2-D uint8 grayscale image")
         return img
 
-    def estimate_batch(self, imgs1, imgs2):
-        """(R[B,3,3], t[B,3,1], inliers[B], status[B]); a failing pair never aborts the batch."""
+    def _run_batch(self, eng, imgs1, imgs2, cameras1=None, cameras2=None):
+        """one engine batch: the single-K call, or the camera call when cameras are given or the estimator has dist_coeffs"""
+        if cameras1 is None and cameras2 is None and self._camera is None:
+            return eng.estimate_batch(imgs1, imgs2, self.K)
+        default = self._camera if self._camera is not None else _capi.Camera(self.K)
+        return eng.estimate_batch_cameras(imgs1, imgs2, default if cameras1 is None else cameras1,
+                                          default if cameras2 is None else cameras2)
+
+    def estimate_batch(self, imgs1, imgs2, cameras1=None, cameras2=None):
+        """(R[B,3,3], t[B,3,1], inliers[B], status[B]); a failing pair never aborts the batch.  cameras1 / cameras2: a
+        Camera per image (or one for all) of imgs1 / imgs2; a side left None uses the estimator's own camera."""
         imgs1 = np.ascontiguousarray(imgs1, np.uint8); imgs2 = np.ascontiguousarray(imgs2, np.uint8)
         B, H, W = imgs1.shape
+        if cameras1 is not None:
+            cameras1 = _capi.camera_records(cameras1, B)                 # ValueError before any device call
+        if cameras2 is not None:
+            cameras2 = _capi.camera_records(cameras2, B)
         eng = self._engine(H, W, B)
-        R, t, inl, nm, st = eng.estimate_batch(imgs1, imgs2, self.K)
+        R, t, inl, nm, st = self._run_batch(eng, imgs1, imgs2, cameras1, cameras2)
         self._last_n_matches = nm
         self._last_engine, self._last_pairs = eng, B
         return R, t, inl, st
 
-    def _run_pair_list(self, eng, pairs):
-        """pairs [P, 2] int32 of store slots, in chunks of at most max_batch"""
+    def _run_pair_list(self, eng, pairs, cameras=False):
+        """pairs [P, 2] int32 of store slots, in chunks of at most max_batch; cameras: on the slots' cameras"""
         P = pairs.shape[0]
         R = np.zeros((P, 3, 3)); t = np.zeros((P, 3, 1))
         inl = np.zeros(P, np.int32); nm = np.zeros(P, np.int32); st = np.zeros(P, np.int32)
         for a in range(0, P, eng.max_batch):
             b = min(a + eng.max_batch, P)
-            R[a:b], t[a:b], inl[a:b], nm[a:b], st[a:b] = eng.estimate_pairs(pairs[a:b, 0], pairs[a:b, 1], self.K)
+            if cameras:
+                R[a:b], t[a:b], inl[a:b], nm[a:b], st[a:b] = eng.estimate_pairs_cameras(pairs[a:b, 0], pairs[a:b, 1])
+            else:
+                R[a:b], t[a:b], inl[a:b], nm[a:b], st[a:b] = eng.estimate_pairs(pairs[a:b, 0], pairs[a:b, 1], self.K)
             self._last_n_matches, self._last_engine, self._last_pairs = nm[a:b].copy(), eng, b - a
         return R, t, inl, nm, st
 
@@ -268,7 +307,9 @@ class PoseEstimator:
             chunk = frames[a:b]
             gray = eng.bgr_to_gray(chunk) if chunk.ndim == 4 else chunk
             eng.frames_put(gray, np.arange(a, b, dtype=np.int32))
-        return self._run_pair_list(eng, pairs)
+        if self._camera is not None:
+            eng.frames_set_cameras(np.arange(F, dtype=np.int32), self._camera)
+        return self._run_pair_list(eng, pairs, cameras=self._camera is not None)
 
     def frame_store(self, capacity):
         """A FrameStore of `capacity` slots on this estimator's engine (created for the size of the first frame put)."""
@@ -313,7 +354,11 @@ class PoseEstimator:
         frames = np.ascontiguousarray(frames, np.uint8)
         F, H, W = frames.shape
         eng = self._engine(H, W, F - 1)
-        R, t, inl, nm, st = eng.estimate_stream(frames, self.K)
+        if self._camera is not None:
+            # the camera path has no stream form: the same pairs as a batch (frame i, frame i + 1), same results
+            R, t, inl, nm, st = eng.estimate_batch_cameras(frames[:-1], frames[1:], self._camera, self._camera)
+        else:
+            R, t, inl, nm, st = eng.estimate_stream(frames, self.K)
         self._last_n_matches = nm
         self._last_engine, self._last_pairs = eng, F - 1
         return R, t, inl, st
@@ -328,7 +373,7 @@ class PoseEstimator:
     def estimate(self, img1, img2, R_prev=None):
         img1 = self._gray(img1); img2 = self._gray(img2)
         eng = self._engine(img1.shape[0], img1.shape[1], 1)
-        R, t, inl, nm, st = eng.estimate_batch(img1[None], img2[None], self.K)
+        R, t, inl, nm, st = self._run_batch(eng, img1[None], img2[None])
         self._last_n_matches, self._last_engine, self._last_pairs = nm, eng, 1
         self._raise_for(int(st[0]), int(nm[0]))
         R_rel = R[0]
@@ -339,7 +384,7 @@ class PoseEstimator:
     def estimate_with_debug(self, img1, img2, R_prev=None):
         img1 = self._gray(img1); img2 = self._gray(img2)
         eng = self._engine(img1.shape[0], img1.shape[1], 1)
-        R, t, inl, nm, st = eng.estimate_batch(img1[None], img2[None], self.K)
+        R, t, inl, nm, st = self._run_batch(eng, img1[None], img2[None])
         self._last_n_matches, self._last_engine, self._last_pairs = nm, eng, 1
         self._raise_for(int(st[0]), int(nm[0]))
         p1, p2 = eng.fetch_matched_points(1)
@@ -372,7 +417,7 @@ class PoseEstimator:
         describe."""
         img1 = self._gray(img1); img2 = self._gray(img2)
         eng = self._engine(img1.shape[0], img1.shape[1], 1)
-        R, t, inl, nm, st = eng.estimate_batch(img1[None], img2[None], self.K)
+        R, t, inl, nm, st = self._run_batch(eng, img1[None], img2[None])
         self._last_n_matches, self._last_engine, self._last_pairs = nm, eng, 1
         self._raise_for(int(st[0]), int(nm[0]))
         p1, p2 = eng.fetch_matched_points(1)

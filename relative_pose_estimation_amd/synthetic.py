@@ -40,11 +40,44 @@ def _rot(yaw, pitch, roll):
     return Ry @ Rx @ Rz
 
 
-def _render(K, R, t, W, H, seed, focal):
-    """Ray-cast the scene from the camera X_c = R X_w + t."""
+LENS_ITERS = 50            # fixed-point rounds of the exact lens inverse in _render (converged far below one ulp of a pixel)
+
+
+def _dist8(dist):
+    """cv2's coefficient order k1 k2 p1 p2 [k3 [k4 k5 k6]] padded to 8"""
+    d = np.asarray(dist, np.float64).reshape(-1)
+    if d.size not in (4, 5, 8):
+        raise ValueError(f"dist: expected 4, 5 or 8 coefficients (cv2 order), got {d.size}")
+    out = np.zeros(8)
+    out[:d.size] = d
+    return out
+
+
+def _undistort(xd, yd, dist, iters=LENS_ITERS):
+    """cv2.undistortPoints' fixed-point iteration (Brown-Conrady / rational model), started at (xd, yd)"""
+    k1, k2, p1, p2, k3, k4, k5, k6 = _dist8(dist)
+    x, y = xd, yd
+    for _ in range(iters):
+        r2 = x * x + y * y
+        icd = (1 + r2 * (k4 + r2 * (k5 + r2 * k6))) / (1 + r2 * (k1 + r2 * (k2 + r2 * k3)))
+        dx = 2 * p1 * x * y + p2 * (r2 + 2 * x * x)
+        dy = p1 * (r2 + 2 * y * y) + 2 * p2 * x * y
+        x = (xd - dx) * icd
+        y = (yd - dy) * icd
+    return x, y
+
+
+def _render(K, R, t, W, H, seed, focal, dist=None):
+    """Ray-cast the scene from the camera X_c = R X_w + t.  With `dist` the pixel grid is the DISTORTED image: the ray of
+    pixel (u, v) is the lens inverse of ((u - cx) / fx, (v - cy) / fy), so the image is what the lens would record, as
+    sharp as the pinhole one (no resampling)."""
     u, v = np.meshgrid(np.arange(W, dtype=np.float64), np.arange(H, dtype=np.float64))
-    Kinv = np.linalg.inv(K)
-    d_c = np.stack([u, v, np.ones_like(u)], -1) @ Kinv.T          # rays in camera frame
+    if dist is None:
+        Kinv = np.linalg.inv(K)
+        d_c = np.stack([u, v, np.ones_like(u)], -1) @ Kinv.T          # rays in camera frame
+    else:
+        x, y = _undistort((u - K[0, 2]) / K[0, 0], (v - K[1, 2]) / K[1, 1], dist)
+        d_c = np.stack([x, y, np.ones_like(u)], -1)
     d_w = d_c @ R                                                  # R^T applied to row vectors
     o = -R.T @ t
     hitX = np.zeros((H, W)); hitY = np.zeros((H, W)); plane = np.full((H, W), -1, np.int32)
@@ -73,8 +106,9 @@ def _finish(val, rng):
     return np.clip(np.rint(img), 0, 255).astype(np.uint8)
 
 
-def make_pair(seed, K, W=640, H=480, max_angle_deg=5.0, baseline=0.4):
-    """Returns img1, img2 (uint8 HxW), R_gt (3x3), t_gt (3x1 unit)."""
+def make_pair(seed, K, W=640, H=480, max_angle_deg=5.0, baseline=0.4, dist=None):
+    """Returns img1, img2 (uint8 HxW), R_gt (3x3), t_gt (3x1 unit).  dist: cv2 distortion coefficients of the lens both
+    views are recorded through (None: pinhole)."""
     rng = np.random.default_rng(int(seed))
     yaw, pitch, roll = rng.uniform(-max_angle_deg, max_angle_deg, 3)
     R = _rot(yaw, pitch, roll)
@@ -82,20 +116,20 @@ def make_pair(seed, K, W=640, H=480, max_angle_deg=5.0, baseline=0.4):
     t = tdir * baseline
     K = np.asarray(K, np.float64)
     focal = 0.5 * (K[0, 0] + K[1, 1])
-    v1 = _render(K, np.eye(3), np.zeros(3), W, H, int(seed), focal)
-    v2 = _render(K, R, t, W, H, int(seed), focal)
+    v1 = _render(K, np.eye(3), np.zeros(3), W, H, int(seed), focal, dist)
+    v2 = _render(K, R, t, W, H, int(seed), focal, dist)
     return _finish(v1, rng), _finish(v2, rng), R, tdir.reshape(3, 1)
 
 
 def _job(args):
-    seed, K, W, H = args
-    return make_pair(seed, K, W, H)
+    seed, K, W, H, dist = args
+    return make_pair(seed, K, W, H, dist=dist)
 
 
-def make_batch(n, K, W=640, H=480, cfg=2, first=0, workers=1):
-    """n seeded pairs (seed = 1_000_003*cfg + index): imgs1, imgs2 [n,H,W], R [n,3,3], t [n,3,1]."""
+def make_batch(n, K, W=640, H=480, cfg=2, first=0, workers=1, dist=None):
+    """n seeded pairs (seed = 1_000_003*cfg + index): imgs1, imgs2 [n,H,W], R [n,3,3], t [n,3,1]; dist as in make_pair."""
     seeds = [1_000_003 * cfg + first + i for i in range(n)]
-    jobs = [(s, np.asarray(K, np.float64), W, H) for s in seeds]
+    jobs = [(s, np.asarray(K, np.float64), W, H, dist) for s in seeds]
     if workers > 1:
         import multiprocessing as mp
         with mp.get_context("fork").Pool(workers) as pool:
@@ -108,19 +142,19 @@ def make_batch(n, K, W=640, H=480, cfg=2, first=0, workers=1):
 
 
 def _stream_job(args):
-    K, R, t, W, H, seed, focal, nseed = args
+    K, R, t, W, H, seed, focal, nseed, dist = args
     rng = np.random.default_rng(int(nseed))
-    return _finish(_render(K, R, t, W, H, int(seed), focal), rng)
+    return _finish(_render(K, R, t, W, H, int(seed), focal, dist), rng)
 
 
-def make_stream(n_frames, K, W=640, H=480, seed=5_000_011, max_angle_deg=2.0, step=0.12, workers=1, frame_range=None):
+def make_stream(n_frames, K, W=640, H=480, seed=5_000_011, max_angle_deg=2.0, step=0.12, workers=1, frame_range=None, dist=None):
     """One camera moving through ONE scene (KITTI-like consecutive-frame stream, BASELINE config 5
     stand-in): frames [n,H,W], and the ground-truth relative pose of every consecutive pair
     (X_{i+1} = R_rel X_i + t_rel, |t_rel| = 1).  The camera random-walks with small rotations and
     a bounded position so that the scene stays in view.
     frame_range=(lo, hi): render only frames [lo, hi) of the n_frames-long sequence (the trajectory is always
     computed whole, so every shard of a sharded stream sees the same sequence); poses returned are those of the
-    pairs inside the range."""
+    pairs inside the range.  dist as in make_pair."""
     rng = np.random.default_rng(int(seed))
     K = np.asarray(K, np.float64)
     focal = 0.5 * (K[0, 0] + K[1, 1])
@@ -134,7 +168,7 @@ def make_stream(n_frames, K, W=640, H=480, seed=5_000_011, max_angle_deg=2.0, st
         tr = d * step
         Rs.append(Rr @ Rs[-1]); ts.append(Rr @ ts[-1] + tr)
     lo, hi = (0, n_frames) if frame_range is None else (int(frame_range[0]), int(frame_range[1]))
-    jobs = [(K, Rs[i], ts[i], W, H, seed, focal, seed * 31 + i) for i in range(lo, hi)]
+    jobs = [(K, Rs[i], ts[i], W, H, seed, focal, seed * 31 + i, dist) for i in range(lo, hi)]
     if workers > 1:
         import multiprocessing as mp
         with mp.get_context("fork").Pool(workers) as pool:

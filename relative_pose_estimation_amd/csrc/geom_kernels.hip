@@ -891,28 +891,26 @@ __global__ __launch_bounds__(256) void ransac_mask_kernel(const double2 *__restr
     }
 }
 
-static void launch_mask(rpe_handle *h, int B, const int *status)
+// Launches the camera instance of a kernel when the run carries a camera source, the shared-K instance otherwise (the
+// single-K paths launch CAM = false only): the two instances share one signature
+template <typename Kernel, typename... Args>
+static void launch_cam(const RpeRun &r, Kernel with_cameras, Kernel with_K, dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args... args)
 {
-    const int mm = h->cfg.max_matches;
-    if (h->cam.cams)
-        hipLaunchKernelGGL(ransac_mask_kernel<true>, dim3(B), dim3(256), 0, h->stream,
-                           h->d_n1, h->d_n2, h->d_rstate, h->d_K, h->cam, h->cfg.ransac_threshold, status, h->d_mask, mm);
-    else
-        hipLaunchKernelGGL(ransac_mask_kernel<false>, dim3(B), dim3(256), 0, h->stream,
-                           h->d_n1, h->d_n2, h->d_rstate, h->d_K, h->cam, h->cfg.ransac_threshold, status, h->d_mask, mm);
+    hipLaunchKernelGGL(r.cam.cams ? with_cameras : with_K, grid, block, lds, stream, args...);
 }
 
-void rpe_launch_ransac(rpe_handle *h, int B, bool want_mask)
+static void launch_mask(rpe_handle *h, const RpeRun &r, const int *status)
 {
-    const int mm = h->cfg.max_matches, it = h->cfg.ransac_max_iters;
+    launch_cam(r, ransac_mask_kernel<true>, ransac_mask_kernel<false>, dim3(r.pairs), dim3(256), 0, h->stream,
+               h->d_n1, h->d_n2, h->d_rstate, h->d_K, r.cam, h->cfg.ransac_threshold, status, h->d_mask, h->cfg.max_matches);
+}
+
+void rpe_launch_ransac(rpe_handle *h, const RpeRun &r, bool want_mask)
+{
+    const int mm = h->cfg.max_matches, it = h->cfg.ransac_max_iters, B = r.pairs;
     double2 *n1 = h->d_n1, *n2 = h->d_n2;
-    const bool cam = h->cam.cams != nullptr;          // camera path: the <true> instances; the single-K paths launch <false> only
-    if (cam)
-        hipLaunchKernelGGL(ransac_prepare_kernel<true>, dim3((mm + 255) / 256, B), dim3(256), 0, h->stream,
-                           h->d_pts1, h->d_pts2, h->d_m_n, h->d_K, h->cam, n1, n2, h->d_rstate, h->d_found, mm, it);
-    else
-        hipLaunchKernelGGL(ransac_prepare_kernel<false>, dim3((mm + 255) / 256, B), dim3(256), 0, h->stream,
-                           h->d_pts1, h->d_pts2, h->d_m_n, h->d_K, h->cam, n1, n2, h->d_rstate, h->d_found, mm, it);
+    launch_cam(r, ransac_prepare_kernel<true>, ransac_prepare_kernel<false>, dim3((mm + 255) / 256, B), dim3(256), 0, h->stream,
+               h->d_pts1, h->d_pts2, h->d_m_n, h->d_K, r.cam, n1, n2, h->d_rstate, h->d_found, mm, it);
     // chunk schedule 32, 96, 384, 512, 512, ... (cumulative 32, 128, 512, 1024).  A launch group costs
     //   max(latency floor, work): the floor is one wave's dependent chain through poly -> roots -> score -> update
     //   (~170-200 us whatever the number of pairs still running), the work is ~12.6 ns per (pair, iteration) that is
@@ -942,14 +940,9 @@ void rpe_launch_ransac(rpe_handle *h, int B, bool want_mask)
                            n1, n2, h->d_rstate, h->d_subsets, h->d_hyp, h->d_nmodels, mm, it);
         hipLaunchKernelGGL(ransac_roots_kernel, dim3((unsigned)((long long)B * chunk * RG / 256)), dim3(256), 0, h->stream,
                            (const RpeRansacState *)h->d_rstate, (const double *)h->d_hyp, h->d_models, h->d_nmodels, B, chunk);
-        if (cam)
-            hipLaunchKernelGGL(ransac_score_kernel<true>, dim3(B, chunk / SCORE_GROUP), dim3(256), lds, h->stream,
-                               n1, n2, (const RpeRansacState *)h->d_rstate, (const double *)h->d_models, (const int *)h->d_nmodels,
-                               (const double *)h->d_K, h->cam, h->cfg.ransac_threshold, h->d_counts, mm, use_lds);
-        else
-            hipLaunchKernelGGL(ransac_score_kernel<false>, dim3(B, chunk / SCORE_GROUP), dim3(256), lds, h->stream,
-                               n1, n2, (const RpeRansacState *)h->d_rstate, (const double *)h->d_models, (const int *)h->d_nmodels,
-                               (const double *)h->d_K, h->cam, h->cfg.ransac_threshold, h->d_counts, mm, use_lds);
+        launch_cam(r, ransac_score_kernel<true>, ransac_score_kernel<false>, dim3(B, chunk / SCORE_GROUP), dim3(256), lds, h->stream,
+                   n1, n2, (const RpeRansacState *)h->d_rstate, (const double *)h->d_models, (const int *)h->d_nmodels,
+                   (const double *)h->d_K, r.cam, h->cfg.ransac_threshold, h->d_counts, mm, use_lds);
         hipLaunchKernelGGL(ransac_update_kernel, dim3((B + 3) / 4), dim3(256), 0, h->stream,
                            h->d_rstate, (const double *)h->d_models, (const int *)h->d_nmodels, (const int *)h->d_counts,
                            (const double *)h->d_nit_denom, (const int *)h->d_nit_round, h->nit_num, h->d_E, h->d_found, chunk, B);
@@ -958,7 +951,7 @@ void rpe_launch_ransac(rpe_handle *h, int B, bool want_mask)
         if (!env_sched.empty()) chunk = env_sched[std::min((size_t)nlaunch, env_sched.size() - 1)];
         else chunk = kSchedule[std::min(nlaunch, 3)];
     }
-    if (want_mask) launch_mask(h, B, (const int *)nullptr);
+    if (want_mask) launch_mask(h, r, (const int *)nullptr);
 }
 
 // ------------------------------------------------------------ recoverPose
@@ -1188,37 +1181,26 @@ __global__ __launch_bounds__(256) void pose_structure_kernel(const float2 *__res
 
 // Only rpe_fetch_structure launches these, after a batch: d_n1 / d_n2 / d_rstate still hold the batch's normalised points
 // and RANSAC state, d_R / d_t / d_status its results.
-void rpe_launch_structure(rpe_handle *h, int B)
+void rpe_launch_structure(rpe_handle *h, const RpeRun &r)
 {
-    const int mm = h->cfg.max_matches;
-    launch_mask(h, B, (const int *)h->d_status);
-    if (h->cam.cams)
-        hipLaunchKernelGGL(pose_structure_kernel<true>, dim3(B), dim3(256), 0, h->stream,
-                           h->d_pts1, h->d_pts2, h->d_n1, h->d_n2, h->d_m_n, h->d_status, h->d_K, h->d_R, h->d_t, h->d_pose_mask, h->d_points, mm);
-    else
-        hipLaunchKernelGGL(pose_structure_kernel<false>, dim3(B), dim3(256), 0, h->stream,
-                           h->d_pts1, h->d_pts2, h->d_n1, h->d_n2, h->d_m_n, h->d_status, h->d_K, h->d_R, h->d_t, h->d_pose_mask, h->d_points, mm);
+    launch_mask(h, r, (const int *)h->d_status);
+    launch_cam(r, pose_structure_kernel<true>, pose_structure_kernel<false>, dim3(r.pairs), dim3(256), 0, h->stream,
+               h->d_pts1, h->d_pts2, h->d_n1, h->d_n2, h->d_m_n, h->d_status, h->d_K, h->d_R, h->d_t, h->d_pose_mask, h->d_points, h->cfg.max_matches);
 }
 
-void rpe_launch_pose(rpe_handle *h, int B, bool fused)
+// fused (a batch, a stream, a pair list): the status test reads ransac's d_found and the keypoint counts of the pair's two
+// images, through the pair table when the run has one.  Stage form: neither, and the rule instances.
+void rpe_launch_pose(rpe_handle *h, const RpeRun &r, bool fused)
 {
-    const RpeFeatSrc f = rpe_feat_src(h, B);
-    const int *found = fused ? h->d_found : (const int *)nullptr, *count = fused ? f.count : (const int *)nullptr;
+    const RpeFeatSrc &f = r.feat;
+    const bool tab = fused && f.tab;
     // the camera instances read d_n1 / d_n2: ransac_prepare_kernel<true> (fused) or rpe_launch_camera_normalise (stage
     // form) of the same call has filled them
-#define RPE_LAUNCH_POSE(TAB, CAM, FOUND, COUNT, TABP)                                                                    \
-    hipLaunchKernelGGL((recover_pose_kernel<TAB, CAM>), dim3(B), dim3(256), 0, h->stream,                                \
-                       h->d_E, h->d_pts1, h->d_pts2, h->d_n1, h->d_n2, h->d_m_n, FOUND, COUNT, f.img2_base, TABP, h->d_K, \
-                       h->d_R, h->d_t, h->d_inliers, h->d_status, h->cfg.max_matches)
-    const bool cam = h->cam.cams != nullptr;
-    if (fused && f.tab) {
-        if (cam) RPE_LAUNCH_POSE(true, true, h->d_found, f.count, f.tab);
-        else RPE_LAUNCH_POSE(true, false, h->d_found, f.count, f.tab);
-    } else {
-        if (cam) RPE_LAUNCH_POSE(false, true, found, count, (const int2 *)nullptr);
-        else RPE_LAUNCH_POSE(false, false, found, count, (const int2 *)nullptr);
-    }
-#undef RPE_LAUNCH_POSE
+    launch_cam(r, tab ? recover_pose_kernel<true, true> : recover_pose_kernel<false, true>,
+               tab ? recover_pose_kernel<true, false> : recover_pose_kernel<false, false>, dim3(r.pairs), dim3(256), 0, h->stream,
+               h->d_E, h->d_pts1, h->d_pts2, h->d_n1, h->d_n2, h->d_m_n, fused ? (const int *)h->d_found : (const int *)nullptr,
+               fused ? f.count : (const int *)nullptr, f.img2_base, tab ? f.tab : (const int2 *)nullptr, h->d_K,
+               h->d_R, h->d_t, h->d_inliers, h->d_status, h->cfg.max_matches);
 }
 
 // ------------------------------------------------------------ pose refinement
@@ -1587,11 +1569,11 @@ __global__ __launch_bounds__(256) void refine_normalise_kernel(const float2 *__r
 }
 
 // stage forms of the camera path (rpe_recover_pose_cameras, rpe_refine_pose_points_cameras): d_n1 / d_n2 of the uploaded points
-void rpe_launch_camera_normalise(rpe_handle *h, int B)
+void rpe_launch_camera_normalise(rpe_handle *h, const RpeRun &r)
 {
     const int mm = h->cfg.max_matches;
-    hipLaunchKernelGGL(refine_normalise_kernel<true>, dim3((mm + 255) / 256, B), dim3(256), 0, h->stream,
-                       h->d_pts1, h->d_pts2, h->d_m_n, h->d_K, h->cam, h->d_n1, h->d_n2, mm);
+    hipLaunchKernelGGL(refine_normalise_kernel<true>, dim3((mm + 255) / 256, r.pairs), dim3(256), 0, h->stream,
+                       h->d_pts1, h->d_pts2, h->d_m_n, h->d_K, r.cam, h->d_n1, h->d_n2, mm);
 }
 
 // rpe_undistort_points: n pixels of one camera -> normalised, undistorted coordinates; one thread per point, the camera a
@@ -1611,27 +1593,21 @@ void rpe_launch_undistort(rpe_handle *h, const float2 *d_pts, int n, const rpe_c
 
 // after a batch / stream (from_batch): inliers = ransac_mask_kernel's mask of the winning model, start = d_R / d_t.
 // stage form: d_mask, d_ref_R0 / d_ref_t0 and d_pts* were uploaded by the caller.
-void rpe_launch_refine(rpe_handle *h, int B, int max_iters, bool from_batch)
+void rpe_launch_refine(rpe_handle *h, const RpeRun &r, int max_iters, bool from_batch)
 {
-    const int mm = h->cfg.max_matches;
-    const bool cam = h->cam.cams != nullptr;
-    if (from_batch) launch_mask(h, B, (const int *)h->d_status);
-    else if (cam) rpe_launch_camera_normalise(h, B);
+    const int mm = h->cfg.max_matches, B = r.pairs;
+    if (from_batch) launch_mask(h, r, (const int *)h->d_status);
+    else if (r.cam.cams) rpe_launch_camera_normalise(h, r);
     else
         hipLaunchKernelGGL(refine_normalise_kernel<false>, dim3((mm + 255) / 256, B), dim3(256), 0, h->stream,
-                           h->d_pts1, h->d_pts2, h->d_m_n, h->d_K, h->cam, h->d_n1, h->d_n2, mm);
+                           h->d_pts1, h->d_pts2, h->d_m_n, h->d_K, r.cam, h->d_n1, h->d_n2, mm);
     const double *Rin = from_batch ? h->d_R : h->d_ref_R0, *tin = from_batch ? h->d_t : h->d_ref_t0;
     const int *status = from_batch ? h->d_status : nullptr, *inl = from_batch ? h->d_inliers : nullptr;
-#define RPE_LAUNCH_REFINE(LDS, CAM, BYTES)                                                                              \
-    hipLaunchKernelGGL((pose_refine_kernel<LDS, CAM>), dim3(B), dim3(256), BYTES, h->stream,                             \
-                       h->d_n1, h->d_n2, h->d_mask, h->d_m_n, status, inl, h->d_K, h->cam, Rin, tin,                      \
-                       h->d_ref_R, h->d_ref_t, h->d_ref_inl, h->d_ref_info, h->d_ref_rms, mm, max_iters)
-    if (mm <= REFINE_LDS_MATCHES) {
-        if (cam) RPE_LAUNCH_REFINE(true, true, sizeof(double2) * 2 * (size_t)mm);
-        else RPE_LAUNCH_REFINE(true, false, sizeof(double2) * 2 * (size_t)mm);
-    } else {
-        if (cam) RPE_LAUNCH_REFINE(false, true, sizeof(unsigned short) * (size_t)mm);
-        else RPE_LAUNCH_REFINE(false, false, sizeof(unsigned short) * (size_t)mm);
-    }
-#undef RPE_LAUNCH_REFINE
+    // the inliers staged in LDS, or, above the cut, as 16-bit indices
+    const bool lds = mm <= REFINE_LDS_MATCHES;
+    launch_cam(r, lds ? pose_refine_kernel<true, true> : pose_refine_kernel<false, true>,
+               lds ? pose_refine_kernel<true, false> : pose_refine_kernel<false, false>, dim3(B), dim3(256),
+               lds ? sizeof(double2) * 2 * (size_t)mm : sizeof(unsigned short) * (size_t)mm, h->stream,
+               h->d_n1, h->d_n2, h->d_mask, h->d_m_n, status, inl, h->d_K, r.cam, Rin, tin,
+               h->d_ref_R, h->d_ref_t, h->d_ref_inl, h->d_ref_info, h->d_ref_rms, mm, max_iters);
 }

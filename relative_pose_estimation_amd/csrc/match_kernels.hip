@@ -402,10 +402,10 @@ static void launch_tab(bool tab, Kernel with_table, Kernel with_rule, dim3 grid,
     hipLaunchKernelGGL(tab ? with_table : with_rule, grid, block, lds, stream, args...);
 }
 
-void rpe_launch_match(rpe_handle *h, int B)
+void rpe_launch_match(rpe_handle *h, const RpeRun &r)
 {
-    const int kcap = h->lay.kcap;
-    const RpeFeatSrc f = rpe_feat_src(h, B);                  // the workspace (batch / stream rule) or the frame store (pair table)
+    const int kcap = h->lay.kcap, B = r.pairs;
+    const RpeFeatSrc &f = r.feat;                             // the workspace (batch / stream rule) or the frame store (pair table)
     size_t lds = (size_t)QTILE * 32 + (size_t)kcap * 8;       // staging / sort keys + election words + own-nearest words
     if (h->cfg.match_mode == RPE_MATCH_RATIO)                 // the ratio mode has no own-nearest words: 4 bytes per keypoint (<= 64 KB at 8064)
         launch_tab(f.tab, match_hamming_kernel<true, true>, match_hamming_kernel<true, false>, dim3(B), dim3(256), (size_t)QTILE * 32 + (size_t)kcap * 4, h->stream,
@@ -760,10 +760,10 @@ void rpe_launch_l2_norms(rpe_handle *h, int n_img)
     else                      hipLaunchKernelGGL(match_l2_norms_kernel<2>, gn, dim3(256), 0, h->stream, h->d_desc, h->d_kp_count, kcap, (int2 *)h->d_m_norm);
 }
 
-void rpe_launch_match_l2(rpe_handle *h, int B)
+void rpe_launch_match_l2(rpe_handle *h, const RpeRun &r)
 {
-    const int kcap = h->lay.kcap;
-    const RpeFeatSrc f = rpe_feat_src(h, B);                  // the workspace (batch / stream rule) or the frame store (pair table)
+    const int kcap = h->lay.kcap, B = r.pairs;
+    const RpeFeatSrc &f = r.feat;                             // the workspace (batch / stream rule) or the frame store (pair table)
     const int img2_base = f.img2_base;
     // d_m_best2 = NNt (per query; the ratio mode's only list), d_m_best = NNq (per train)
     hipMemsetAsync(h->d_m_best2, 0xFF, sizeof(unsigned long long) * (size_t)B * kcap, h->stream);

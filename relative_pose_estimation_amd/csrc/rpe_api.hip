@@ -130,13 +130,17 @@ static inline uint32_t rng_next(uint64_t &st)
     return (uint32_t)st;
 }
 
+// Every device buffer of the handle (the frame store keeps its own set, caller buffers are in user_allocs) comes from
+// here: rpe_destroy frees what this recorded.  DM_ONCE: a buffer created on first use.
 template <typename T>
 static int dmalloc(rpe_handle *h, T **p, size_t n)
 {
     HIPCHK(h, hipMalloc((void **)p, n * sizeof(T)));
+    h->dev_allocs.push_back(*p);
     return RPE_OK;
 }
 #define DM(h, p, n) do { int r_ = dmalloc(h, &(p), (size_t)(n)); if (r_) return r_; } while (0)
+#define DM_ONCE(h, p, n) do { if (!(p)) DM(h, p, n); } while (0)
 
 static int build_tables(rpe_handle *h)
 {
@@ -286,6 +290,26 @@ static int build_tables(rpe_handle *h)
     return RPE_OK;
 }
 
+// The result block of max_batch pairs: section k (R, t, inliers, status, n_matches) starts at off[k] and holds
+// kRpeResultElem[k] bytes per pair
+struct ResultBlock {
+    size_t off[RPE_RESULT_SECTIONS], bytes = 0;
+    explicit ResultBlock(const rpe_handle *h)
+    {
+        for (int k = 0; k < RPE_RESULT_SECTIONS; ++k) { off[k] = bytes; bytes += (size_t)h->cfg.max_batch * kRpeResultElem[k]; }
+    }
+};
+static_assert(9 * sizeof(double) + 3 * sizeof(double) + 3 * sizeof(int) == RPE_RESULT_BYTES, "result sections");
+
+// the first B pairs of the pinned mirror of a result block, section by section, into the caller's arrays (null: not wanted)
+static void unpack_results(const rpe_handle *h, int B, double *R, double *t, int32_t *inliers, int32_t *n_matches, int32_t *status)
+{
+    const ResultBlock rb(h);
+    void *dst[RPE_RESULT_SECTIONS] = {R, t, inliers, status, n_matches};
+    for (int k = 0; k < RPE_RESULT_SECTIONS; ++k)
+        if (dst[k]) memcpy(dst[k], h->h_resblk + rb.off[k], (size_t)B * kRpeResultElem[k]);
+}
+
 static int alloc_workspace(rpe_handle *h)
 {
     const RpeDeviceLayout &L = h->lay;
@@ -314,8 +338,9 @@ static int alloc_workspace(rpe_handle *h)
     // results of a batch in ONE block [R 9B f64 | t 3B f64 | inliers B | status B | n_matches B]: rpe_fetch_results is one
     // device-to-host copy into pinned memory (five copies into pageable memory left the GPU idle for ~100 us per step)
     DM(h, h->d_resblk, (size_t)B * RPE_RESULT_BYTES);
-    h->d_R = (double *)h->d_resblk; h->d_t = h->d_R + (size_t)B * 9;
-    h->d_inliers = (int *)(h->d_t + (size_t)B * 3); h->d_status = h->d_inliers + B; h->d_m_n = h->d_status + B;
+    const ResultBlock rb(h);
+    h->d_R = (double *)(h->d_resblk + rb.off[0]); h->d_t = (double *)(h->d_resblk + rb.off[1]);
+    h->d_inliers = (int *)(h->d_resblk + rb.off[2]); h->d_status = (int *)(h->d_resblk + rb.off[3]); h->d_m_n = (int *)(h->d_resblk + rb.off[4]);
     HIPCHK(h, hipHostMalloc((void **)&h->h_resblk, (size_t)B * RPE_RESULT_BYTES));
     DM(h, h->d_pts1, B * mm); DM(h, h->d_pts2, B * mm);
     if (h->cfg.norm_type == RPE_NORM_L2) { DM(h, h->d_m_best, B * L.kcap); DM(h, h->d_m_best2, B * L.kcap); DM(h, h->d_m_norm, 2 * NI * L.kcap); }
@@ -403,16 +428,9 @@ extern "C" void rpe_destroy(rpe_handle *h)
     if (h->stream) hipStreamSynchronize(h->stream);
     rpe_sift_destroy(h);
     for (auto &g : h->graphs) { hipGraphExecDestroy(g.exec); hipGraphDestroy(g.graph); }
-    void *ptrs[] = {h->d_tiles_full, h->d_tiles_fast, h->d_coef, h->d_pyr_tiles, h->d_pyr, h->d_bufA, h->d_tile_list, h->d_tile_cnt, h->d_stage1, h->d_stage2,
-                    h->d_hist, h->d_cand_xy, h->d_cand_resp, h->d_cand_count, h->d_kp_xy, h->d_kp_resp, h->d_kp_angle,
-                    h->d_kp_pt, h->d_kp_cs, h->d_kp_count, h->d_desc, h->d_m_q, h->d_m_t, h->d_m_d, h->d_resblk, h->d_pts1, h->d_pts2,
-                    h->d_subsets, h->d_nit_denom, h->d_nit_round, h->d_rstate, h->d_n1, h->d_n2, h->d_found, h->d_models, h->d_hyp, h->d_counts,
-                    h->d_nmodels, h->d_mask, h->d_pose_mask, h->d_points, h->d_ref_R, h->d_ref_t, h->d_ref_rms, h->d_ref_R0, h->d_ref_t0, h->d_ref_inl, h->d_ref_info, h->d_E, h->d_K, h->d_m_best, h->d_m_best2, h->d_m_norm, h->d_hm_best, h->d_hm_row, h->d_ovf, h->d_corner, h->d_corner_count, h->d_kp_lvl_count};
-    for (void *p : ptrs) if (p) hipFree(p);
+    for (void *p : h->dev_allocs) hipFree(p);
     if (h->h_resblk) hipHostFree(h->h_resblk);
     frames_free(h->fs);
-    if (h->d_pairtab) hipFree(h->d_pairtab);
-    if (h->d_batch_cams) hipFree(h->d_batch_cams);
     if (h->h_pairtab) hipHostFree(h->h_pairtab);
     for (int i = 0; i < RPE_TAB_RING; ++i) if (h->ev_tab[i]) hipEventDestroy(h->ev_tab[i]);
     for (void *p : h->user_allocs) hipFree(p);
@@ -515,19 +533,25 @@ static int load_level0_fast(rpe_handle *h, const uint8_t *d_a, const uint8_t *d_
     return RPE_OK;
 }
 
+// Level 0 is the input itself: when its pitch equals the image width and the batches are 16-B aligned the kernels read
+// it in place (rpe_level_base) -- the device-to-device copy into the pyramid buffer was 1.26 GB of HBM traffic and
+// 0.22 ms per 1024 VGA pairs.  Other widths / unaligned batches take the copy.  Records the source of the na + nb images
+// in the layout the kernels receive (a replayed graph holds it already; rpe_orb_debug_fetch reads it) and says which.
+static bool set_level0_source(rpe_handle *h, const uint8_t *d_a, const uint8_t *d_b, int na, int nb)
+{
+    const bool direct = h->lay.lv[0].pitch == h->cfg.width && (((uintptr_t)d_a | (uintptr_t)(nb ? d_b : d_a)) & 15) == 0;
+    h->lay.in_a = direct ? d_a : nullptr; h->lay.in_b = direct ? d_b : nullptr;
+    h->lay.in_na = na; h->lay.in_img = h->cfg.width * h->cfg.height;
+    h->level0_slots = na + nb;
+    return direct;
+}
+
 static int run_orb(rpe_handle *h, const uint8_t *d_a, const uint8_t *d_b, int na, int nb)
 {
     const int n = na + nb;
     MARK(h, RPE_STAGE_PYRAMID);
     HIPCHK(h, hipMemsetAsync(h->d_ovf, 0, sizeof(unsigned) * (size_t)n, h->stream));
-    // Level 0 is the input itself: when its pitch equals the image width and the batches are 16-B aligned the kernels read
-    // it in place (rpe_level_base) -- the device-to-device copy into the pyramid buffer was 1.26 GB of HBM traffic and
-    // 0.22 ms per 1024 VGA pairs.  Other widths / unaligned batches take the copy.
-    const bool direct = h->lay.lv[0].pitch == h->cfg.width && (((uintptr_t)d_a | (uintptr_t)(nb ? d_b : d_a)) & 15) == 0;
-    h->lay.in_a = direct ? d_a : nullptr; h->lay.in_b = direct ? d_b : nullptr;
-    h->lay.in_na = na; h->lay.in_img = h->cfg.width * h->cfg.height;
-    h->level0_slots = n;
-    if (!direct) {
+    if (!set_level0_source(h, d_a, d_b, na, nb)) {
         int rc = load_level0_fast(h, d_a, d_b, na, nb);
         if (rc) return rc;
     }
@@ -545,9 +569,9 @@ static int run_orb(rpe_handle *h, const uint8_t *d_a, const uint8_t *d_b, int na
     return RPE_OK;
 }
 
+// keeps d_K current (re-uploaded only when the camera matrix changes)
 static int set_K(rpe_handle *h, const double K[9])
 {
-    h->cam = RpeCamSrc{nullptr, nullptr, 0};      // every single-K entry point comes through here: the launchers take the shared-K instances
     if (h->K_valid && memcmp(h->K_last, K, sizeof(double) * 9) == 0) return RPE_OK;      // same camera as the last batch: already resident
     memcpy(h->K_last, K, sizeof(double) * 9);
     h->K_valid = false;
@@ -556,34 +580,72 @@ static int set_K(rpe_handle *h, const double K[9])
     return RPE_OK;
 }
 
-// feature extraction + matching + geometry of `pairs` pairs whose images sit in slots (p, img2_base + p)
-static int run_pairs(rpe_handle *h, const uint8_t *d_a, const uint8_t *d_b, int na, int nb, int pairs, int img2_base)
+// ---- the last run (RpeLastRun).  An entry point that runs pairs calls last_run_begin with the run it is about to launch
+// (a replayed graph included); one that overwrites workspace buffers without running pairs calls last_run_end.
+static RpeLastRun &last_run_begin(rpe_handle *h, RpeLastRun::Kind kind, const RpeRun &run)
 {
-    struct Guard {                          // the launchers read h->img2_base; never leave a stream's value behind
-        rpe_handle *h; ~Guard() { h->img2_base = 0; }
-    } guard{h};
-    h->img2_base = img2_base;
-    h->last_pairs = pairs; h->last_img2_base = img2_base;
-    h->last_chunked = false; h->last_from_store = false;
-    h->structure_valid = false;
-    h->ev_first = 0;
-    int rc;
-    if (h->cfg.feature_method == RPE_FEATURE_SIFT) {
-        if ((rc = rpe_sift_run(h, d_a, d_b, na, nb)) != RPE_OK) return rc;             // records PYRAMID .. DESCRIBE
-        MARK(h, RPE_STAGE_MATCH);
-    } else {
-        if ((rc = run_orb(h, d_a, d_b, na, nb)) != RPE_OK) return rc;
-    }
-    if (h->cfg.norm_type == RPE_NORM_L2) rpe_launch_match_l2(h, pairs);
-    else rpe_launch_match(h, pairs);
+    RpeLastRun &l = h->last;
+    l.kind = kind; l.pairs = run.pairs; l.run = run;
+    l.tab.clear(); l.ovf.clear();
+    l.per_match = kind != RpeLastRun::CHUNKED;      // a chunked batch leaves its last chunk's only
+    h->ev_first = kind == RpeLastRun::LIST ? RPE_STAGE_MATCH : 0;
+    return l;
+}
+
+// The last run's claim on the per-match buffers ends (a stage call overwrites them, a failed launch sequence never filled
+// them); images_too: on the per-image arrays and the device pair table as well (rpe_frames_put*), nothing is left to fetch
+static void last_run_end(rpe_handle *h, bool images_too = false)
+{
+    h->last.per_match = false;
+    if (images_too) { h->last.kind = RpeLastRun::NONE; h->last.pairs = 0; }
+}
+
+// Precondition of the calls behind the last run.  `chunked`: the refusal of a chunked host batch (nullptr: the call serves
+// one); per_match: the call reads the per-match buffers; n: pairs asked for
+static int last_run_check(rpe_handle *h, const char *who, int n, const char *chunked, bool per_match)
+{
+    const RpeLastRun &l = h->last;
+    if (chunked && l.kind == RpeLastRun::CHUNKED) { h->err = chunked; return RPE_ERR_INVALID; }
+    if (per_match && !l.per_match) { h->err = std::string(who) + ": no batch or stream since the last stage-API call (it overwrote the per-match buffers)"; return RPE_ERR_INVALID; }
+    if (n > l.pairs) { h->err = std::string(who) + ": more pairs than the last batch had"; return RPE_ERR_INVALID; }
+    return RPE_OK;
+}
+
+// the first B pairs of the last run: what rpe_fetch_structure / rpe_refine_poses launch on
+static RpeRun last_run_first(const rpe_handle *h, int B)
+{
+    RpeRun r = h->last.run;
+    r.pairs = B;
+    return r;
+}
+
+// match -> RANSAC -> pose of run r: the tail of the image paths and the whole of a pair list
+static int run_tail(rpe_handle *h, const RpeRun &r)
+{
+    if (h->cfg.norm_type == RPE_NORM_L2) rpe_launch_match_l2(h, r);
+    else rpe_launch_match(h, r);
     MARK(h, RPE_STAGE_RANSAC);
-    rpe_launch_ransac(h, pairs, false);
+    rpe_launch_ransac(h, r, false);
     MARK(h, RPE_STAGE_POSE);
-    rpe_launch_pose(h, pairs, true);
+    rpe_launch_pose(h, r, true);
     if (h->profiling) { hipEventRecord(h->ev[RPE_STAGE_COUNT], h->stream); h->ev_valid = true; }
     HIPCHK(h, hipGetLastError());
-    h->structure_valid = true;
     return RPE_OK;
+}
+
+// feature extraction of na + nb images into the workspace slots [0, na + nb), then the tail of run r over them
+static int run_images(rpe_handle *h, const uint8_t *d_a, const uint8_t *d_b, int na, int nb, const RpeRun &r)
+{
+    last_run_begin(h, RpeLastRun::RULE, r);
+    int rc;
+    if (h->cfg.feature_method == RPE_FEATURE_SIFT) {
+        rc = rpe_sift_run(h, d_a, d_b, na, nb);             // records PYRAMID .. DESCRIBE
+        MARK(h, RPE_STAGE_MATCH);
+    } else
+        rc = run_orb(h, d_a, d_b, na, nb);
+    if (rc == RPE_OK) rc = run_tail(h, r);
+    if (rc != RPE_OK) last_run_end(h);
+    return rc;
 }
 
 extern "C" int rpe_enqueue_batch_device(rpe_handle *h, const uint8_t *d_imgs1, const uint8_t *d_imgs2, int B, const double K[9])
@@ -599,27 +661,25 @@ extern "C" int rpe_enqueue_batch_device(rpe_handle *h, const uint8_t *d_imgs1, c
     // stage events are host-side records), not for SIFT (its launch sequence reads back counts), RPE_NO_GRAPH=1 turns it off.
     static const bool no_graph = getenv("RPE_NO_GRAPH") != nullptr;
     if (B > RPE_GRAPH_MAX_PAIRS || h->profiling || h->cfg.feature_method != RPE_FEATURE_ORB || no_graph)
-        return run_pairs(h, d_imgs1, d_imgs2, B, B, B, B);
+        return run_images(h, d_imgs1, d_imgs2, B, B, rpe_run_batch(h, B));
     for (auto &g : h->graphs)
         if (g.a == d_imgs1 && g.b == d_imgs2 && g.B == B) {
-            h->last_pairs = B; h->last_img2_base = B; h->last_chunked = false; h->last_from_store = false; h->structure_valid = true;
-            h->lay.in_na = B; h->level0_slots = 2 * B;
-            const bool direct = h->lay.lv[0].pitch == h->cfg.width && (((uintptr_t)d_imgs1 | (uintptr_t)d_imgs2) & 15) == 0;
-            h->lay.in_a = direct ? d_imgs1 : nullptr; h->lay.in_b = direct ? d_imgs2 : nullptr;
+            last_run_begin(h, RpeLastRun::RULE, rpe_run_batch(h, B));
+            set_level0_source(h, d_imgs1, d_imgs2, B, B);
             HIPCHK(h, hipGraphLaunch(g.exec, h->stream));
             return RPE_OK;
         }
     rpe_handle::GraphEntry e{d_imgs1, d_imgs2, B, nullptr, nullptr};
     if (hipStreamBeginCapture(h->stream, hipStreamCaptureModeThreadLocal) != hipSuccess) {
         (void)hipGetLastError();
-        return run_pairs(h, d_imgs1, d_imgs2, B, B, B, B);
+        return run_images(h, d_imgs1, d_imgs2, B, B, rpe_run_batch(h, B));
     }
-    rc = run_pairs(h, d_imgs1, d_imgs2, B, B, B, B);
+    rc = run_images(h, d_imgs1, d_imgs2, B, B, rpe_run_batch(h, B));
     const hipError_t ce = hipStreamEndCapture(h->stream, &e.graph);
     if (rc != RPE_OK || ce != hipSuccess || !e.graph || hipGraphInstantiate(&e.exec, e.graph, nullptr, nullptr, 0) != hipSuccess) {
         (void)hipGetLastError();
         if (e.graph) hipGraphDestroy(e.graph);
-        return rc != RPE_OK ? rc : run_pairs(h, d_imgs1, d_imgs2, B, B, B, B);       // capture unavailable: plain launches
+        return rc != RPE_OK ? rc : run_images(h, d_imgs1, d_imgs2, B, B, rpe_run_batch(h, B));       // capture unavailable: plain launches
     }
     if (h->graphs.size() >= 4) {                                                    // a handful of (buffers, B) combinations at most
         hipGraphExecDestroy(h->graphs.front().exec); hipGraphDestroy(h->graphs.front().graph);
@@ -640,7 +700,7 @@ extern "C" int rpe_enqueue_stream_device(rpe_handle *h, const uint8_t *d_frames,
     HIPCHK(h, hipSetDevice(h->cfg.device));
     int rc = set_K(h, K);
     if (rc) return rc;
-    return run_pairs(h, d_frames, d_frames, F, 0, F - 1, 1);
+    return run_images(h, d_frames, d_frames, F, 0, rpe_run_stream(h, F - 1));
 }
 
 extern "C" int rpe_estimate_stream(rpe_handle *h, const uint8_t *h_frames, int F, const double K[9],
@@ -722,52 +782,47 @@ extern "C" int rpe_bgr_to_gray(rpe_handle *h, const uint8_t *h_bgr, size_t n_pix
 extern "C" int rpe_fetch_results(rpe_handle *h, int B, double *R, double *t, int32_t *inliers, int32_t *n_matches, int32_t *status)
 {
     if (!h || B < 1 || B > h->cfg.max_batch) return RPE_ERR_INVALID;
-    const size_t MB = (size_t)h->cfg.max_batch;
+    const ResultBlock rb(h);
     // the used part of every section when the batch is small, the whole block in one piece otherwise
-    if ((size_t)B * 4 < MB) {
-        const uint8_t *d = h->d_resblk; uint8_t *o = h->h_resblk;
-        const size_t off[5] = {0, MB * 72, MB * 96, MB * 100, MB * 104}, len[5] = {(size_t)B * 72, (size_t)B * 24, (size_t)B * 4, (size_t)B * 4, (size_t)B * 4};
-        for (int k = 0; k < 5; ++k) HIPCHK(h, hipMemcpyAsync(o + off[k], d + off[k], len[k], hipMemcpyDeviceToHost, h->stream));
+    if ((size_t)B * 4 < (size_t)h->cfg.max_batch) {
+        for (int k = 0; k < RPE_RESULT_SECTIONS; ++k)
+            HIPCHK(h, hipMemcpyAsync(h->h_resblk + rb.off[k], h->d_resblk + rb.off[k], (size_t)B * kRpeResultElem[k], hipMemcpyDeviceToHost, h->stream));
     } else {
-        HIPCHK(h, hipMemcpyAsync(h->h_resblk, h->d_resblk, MB * RPE_RESULT_BYTES, hipMemcpyDeviceToHost, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->h_resblk, h->d_resblk, rb.bytes, hipMemcpyDeviceToHost, h->stream));
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    const uint8_t *o = h->h_resblk;
-    if (R) memcpy(R, o, (size_t)B * 72);
-    if (t) memcpy(t, o + MB * 72, (size_t)B * 24);
-    if (inliers) memcpy(inliers, o + MB * 96, (size_t)B * 4);
-    if (status) memcpy(status, o + MB * 100, (size_t)B * 4);
-    if (n_matches) memcpy(n_matches, o + MB * 104, (size_t)B * 4);
+    unpack_results(h, B, R, t, inliers, n_matches, status);
     return RPE_OK;
 }
 
 extern "C" int rpe_fetch_overflow(rpe_handle *h, int n_pairs, uint32_t *flags)
 {
     if (!h || !flags || n_pairs < 1 || n_pairs > h->cfg.max_batch) return RPE_ERR_INVALID;
-    if (h->last_chunked) {
+    int rc = last_run_check(h, "rpe_fetch_overflow", n_pairs, nullptr, false);
+    if (rc) return rc;
+    const RpeLastRun &l = h->last;
+    if (l.kind == RpeLastRun::CHUNKED) {
         // a chunked host batch reuses the per-image flag words chunk after chunk: they were collected per pair as the chunks finished
-        if ((size_t)n_pairs > h->ovf_pairs.size()) { h->err = "rpe_fetch_overflow: more pairs than the last batch had"; return RPE_ERR_INVALID; }
-        memcpy(flags, h->ovf_pairs.data(), sizeof(uint32_t) * (size_t)n_pairs);
+        memcpy(flags, l.ovf.data(), sizeof(uint32_t) * (size_t)n_pairs);
         return RPE_OK;
     }
-    if (n_pairs > h->last_pairs) { h->err = "rpe_fetch_overflow: more pairs than the last batch had"; return RPE_ERR_INVALID; }
-    if (h->last_from_store) {
-        // a pair list: the flags live with the frames (a put since then cleared last_pairs, a resize of the store last_tab)
-        if (h->last_tab.size() < (size_t)2 * n_pairs) { h->err = "rpe_fetch_overflow: the frame store was resized since the pair list"; return RPE_ERR_INVALID; }
-        int lo = h->last_tab[0], hi = lo;
-        for (int i = 0; i < 2 * n_pairs; ++i) { lo = std::min(lo, h->last_tab[i]); hi = std::max(hi, h->last_tab[i]); }
+    if (l.kind == RpeLastRun::LIST) {
+        // a pair list: the flags live with the frames (a put since then ended the run, a resize of the store emptied its table)
+        if (l.tab.size() < (size_t)2 * n_pairs) { h->err = "rpe_fetch_overflow: the frame store was resized since the pair list"; return RPE_ERR_INVALID; }
+        int lo = l.tab[0], hi = lo;
+        for (int i = 0; i < 2 * n_pairs; ++i) { lo = std::min(lo, l.tab[i]); hi = std::max(hi, l.tab[i]); }
         if (lo < 0 || hi >= h->fs.cap) { h->err = "rpe_fetch_overflow: the pair list names slots outside the store"; return RPE_ERR_INVALID; }
         std::vector<unsigned> ov((size_t)(hi - lo + 1));       // the slots the list names, not the whole store
         HIPCHK(h, hipMemcpyAsync(ov.data(), h->fs.d_ovf + lo, sizeof(unsigned) * ov.size(), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
-        for (int p = 0; p < n_pairs; ++p) flags[p] = ov[(size_t)(h->last_tab[2 * p] - lo)] | ov[(size_t)(h->last_tab[2 * p + 1] - lo)];
+        for (int p = 0; p < n_pairs; ++p) flags[p] = ov[(size_t)(l.tab[2 * p] - lo)] | ov[(size_t)(l.tab[2 * p + 1] - lo)];
         return RPE_OK;
     }
-    const int nimg = h->last_img2_base + n_pairs;
+    const int img2_base = l.run.feat.img2_base, nimg = img2_base + n_pairs;
     std::vector<unsigned> ov((size_t)nimg);
     HIPCHK(h, hipMemcpyAsync(ov.data(), h->d_ovf, sizeof(unsigned) * (size_t)nimg, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (int p = 0; p < n_pairs; ++p) flags[p] = ov[p] | ov[h->last_img2_base + p];
+    for (int p = 0; p < n_pairs; ++p) flags[p] = ov[p] | ov[img2_base + p];
     return RPE_OK;
 }
 
@@ -777,6 +832,23 @@ extern "C" int rpe_estimate_batch_device(rpe_handle *h, const uint8_t *d_imgs1, 
     int rc = rpe_enqueue_batch_device(h, d_imgs1, d_imgs2, B, K);
     if (rc) return rc;
     return rpe_fetch_results(h, B, R, t, inliers, n_matches, status);
+}
+
+// Large host batches run in chunks (rpe_estimate_batch)
+static bool batch_is_chunked(const rpe_handle *h, int B)
+{
+    return B >= 512 && (size_t)h->cfg.width * h->cfg.height * (size_t)B >= ((size_t)64 << 20);
+}
+
+// n host images into the staging buffers, the first max_batch into d_stage1 and the rest into d_stage2: the (d_a, d_b, na, nb)
+// an extraction over workspace slots [0, n) takes
+static int stage_images(rpe_handle *h, const uint8_t *h_imgs, int n, int &na, int &nb)
+{
+    const size_t img = (size_t)h->cfg.width * h->cfg.height;
+    na = n < h->cfg.max_batch ? n : h->cfg.max_batch; nb = n - na;
+    HIPCHK(h, hipMemcpyAsync(h->d_stage1, h_imgs, img * na, hipMemcpyHostToDevice, h->stream));
+    if (nb) HIPCHK(h, hipMemcpyAsync(h->d_stage2, h_imgs + img * na, img * nb, hipMemcpyHostToDevice, h->stream));
+    return RPE_OK;
 }
 
 extern "C" int rpe_estimate_batch(rpe_handle *h, const uint8_t *h_imgs1, const uint8_t *h_imgs2, int B, const double K[9],
@@ -789,7 +861,7 @@ extern "C" int rpe_estimate_batch(rpe_handle *h, const uint8_t *h_imgs1, const u
     // Large host batches run in chunks: all uploads are queued on a copy stream, chunk c's kernels wait for its
     // 'resident' event only, so the PCIe transfer of the later chunks hides behind the kernels of the earlier ones
     // (1024 VGA pairs: 629 MB = 12 ms of copy in front of 16 ms of kernels when done in one piece).
-    const int nchunks = (B >= 512 && img * (size_t)B >= ((size_t)64 << 20)) ? 4 : 1;    // 2/3/4/6/8 chunks measured: 23.1/22.4/22.1/24.1/26.7 ms
+    const int nchunks = batch_is_chunked(h, B) ? 4 : 1;    // 2/3/4/6/8 chunks measured: 23.1/22.4/22.1/24.1/26.7 ms
     if (nchunks == 1) {
         HIPCHK(h, hipMemcpyAsync(h->d_stage1, h_imgs1, img * B, hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipMemcpyAsync(h->d_stage2, h_imgs2, img * B, hipMemcpyHostToDevice, h->stream));
@@ -814,14 +886,10 @@ extern "C" int rpe_estimate_batch(rpe_handle *h, const uint8_t *h_imgs1, const u
     // they run, and the host waits ONCE, at the end (a fetch per chunk cost four stream drains per batch).  Copies from
     // pageable host memory still block the calling thread while they are staged -- after the kernels of the chunk before
     // have been queued; page-locked batches (rpe_host_alloc / rpe_host_register) do not block at all.
-    if (!h->d_resall) {
-        const size_t MBb = (size_t)h->cfg.max_batch;
-        HIPCHK(h, hipMalloc((void **)&h->d_resall, MBb * RPE_RESULT_BYTES));
-        HIPCHK(h, hipMalloc((void **)&h->d_ovfall, MBb * 2 * sizeof(unsigned)));
-        h->user_allocs.push_back(h->d_resall); h->user_allocs.push_back(h->d_ovfall);
-    }
     const size_t MB = (size_t)h->cfg.max_batch;
-    const size_t soff[5] = {0, MB * 72, MB * 96, MB * 100, MB * 104}, esz[5] = {72, 24, 4, 4, 4};
+    const ResultBlock rb(h);
+    DM_ONCE(h, h->d_resall, rb.bytes);
+    DM_ONCE(h, h->d_ovfall, MB * 2);
     int rc = upload(0);
     if (rc) return rc;
     for (int c = 0; c < nchunks; ++c) {
@@ -829,34 +897,29 @@ extern "C" int rpe_estimate_batch(rpe_handle *h, const uint8_t *h_imgs1, const u
         if (n <= 0) break;
         HIPCHK(h, hipStreamWaitEvent(h->stream, h->ev_up[c], 0));
         if ((rc = rpe_enqueue_batch_device(h, h->d_stage1 + (size_t)off * img, h->d_stage2 + (size_t)off * img, n, K)) != RPE_OK) return rc;
-        for (int k = 0; k < 5; ++k)
-            HIPCHK(h, hipMemcpyAsync(h->d_resall + soff[k] + (size_t)off * esz[k], h->d_resblk + soff[k], (size_t)n * esz[k], hipMemcpyDeviceToDevice, h->stream));
-        // the chunk's capacity flags (image slots p and img2_base + p of this launch), before the next chunk overwrites them
+        for (int k = 0; k < RPE_RESULT_SECTIONS; ++k)
+            HIPCHK(h, hipMemcpyAsync(h->d_resall + rb.off[k] + (size_t)off * kRpeResultElem[k], h->d_resblk + rb.off[k], (size_t)n * kRpeResultElem[k], hipMemcpyDeviceToDevice, h->stream));
+        // the chunk's capacity flags (image slots p and n + p of this launch), before the next chunk overwrites them
         HIPCHK(h, hipMemcpyAsync(h->d_ovfall + off, h->d_ovf, sizeof(unsigned) * (size_t)n, hipMemcpyDeviceToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->d_ovfall + MB + off, h->d_ovf + h->last_img2_base, sizeof(unsigned) * (size_t)n, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->d_ovfall + MB + off, h->d_ovf + n, sizeof(unsigned) * (size_t)n, hipMemcpyDeviceToDevice, h->stream));
         if (c + 1 < nchunks && (rc = upload(c + 1)) != RPE_OK) return rc;
     }
     std::vector<unsigned> ov(2 * MB);
-    HIPCHK(h, hipMemcpyAsync(h->h_resblk, h->d_resall, MB * RPE_RESULT_BYTES, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->h_resblk, h->d_resall, rb.bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipMemcpyAsync(ov.data(), h->d_ovfall, sizeof(unsigned) * 2 * MB, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
-    const uint8_t *o = h->h_resblk;
-    if (R) memcpy(R, o, (size_t)B * 72);
-    if (t) memcpy(t, o + MB * 72, (size_t)B * 24);
-    if (inliers) memcpy(inliers, o + MB * 96, (size_t)B * 4);
-    if (status) memcpy(status, o + MB * 100, (size_t)B * 4);
-    if (n_matches) memcpy(n_matches, o + MB * 104, (size_t)B * 4);
-    h->ovf_pairs.assign((size_t)B, 0u);
-    for (int p2 = 0; p2 < B; ++p2) h->ovf_pairs[(size_t)p2] = ov[(size_t)p2] | ov[MB + (size_t)p2];
-    h->last_chunked = true;
-    h->structure_valid = false;
+    unpack_results(h, B, R, t, inliers, n_matches, status);
+    RpeLastRun &l = last_run_begin(h, RpeLastRun::CHUNKED, rpe_run_batch(h, B));
+    l.ovf.resize((size_t)B);
+    for (int p2 = 0; p2 < B; ++p2) l.ovf[(size_t)p2] = ov[(size_t)p2] | ov[MB + (size_t)p2];
     return RPE_OK;
 }
 
 extern "C" int rpe_fetch_matched_points(rpe_handle *h, int B, float *pts1, float *pts2)
 {
     if (!h || B < 1 || B > h->cfg.max_batch) return RPE_ERR_INVALID;
-    if (h->last_chunked) { h->err = "the last host batch ran in chunks: matched points are kept for device-resident batches (rpe_estimate_batch_device) only"; return RPE_ERR_INVALID; }
+    int rc = last_run_check(h, "rpe_fetch_matched_points", 0, "the last host batch ran in chunks: matched points are kept for device-resident batches (rpe_estimate_batch_device) only", false);
+    if (rc) return rc;
     const size_t n = sizeof(float2) * (size_t)B * h->cfg.max_matches;
     if (pts1) HIPCHK(h, hipMemcpyAsync(pts1, h->d_pts1, n, hipMemcpyDeviceToHost, h->stream));
     if (pts2) HIPCHK(h, hipMemcpyAsync(pts2, h->d_pts2, n, hipMemcpyDeviceToHost, h->stream));
@@ -867,14 +930,13 @@ extern "C" int rpe_fetch_matched_points(rpe_handle *h, int B, float *pts1, float
 extern "C" int rpe_fetch_structure(rpe_handle *h, int B, uint8_t *ransac_mask, uint8_t *pose_mask, double *points)
 {
     if (!h || B < 1 || B > h->cfg.max_batch) return RPE_ERR_INVALID;
-    if (h->last_chunked) { h->err = "rpe_fetch_structure: the last host batch ran in chunks: per-match results are kept for unchunked and device-resident batches only"; return RPE_ERR_INVALID; }
-    if (!h->structure_valid) { h->err = "rpe_fetch_structure: no batch or stream since the last stage-API call (it overwrote the per-match buffers)"; return RPE_ERR_INVALID; }
-    if (B > h->last_pairs) { h->err = "rpe_fetch_structure: more pairs than the last batch had"; return RPE_ERR_INVALID; }
+    int rc = last_run_check(h, "rpe_fetch_structure", B, "rpe_fetch_structure: the last host batch ran in chunks: per-match results are kept for unchunked and device-resident batches only", true);
+    if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const size_t cap = (size_t)h->cfg.max_batch * h->cfg.max_matches, n = (size_t)B * h->cfg.max_matches;
-    if (!h->d_pose_mask) HIPCHK(h, hipMalloc((void **)&h->d_pose_mask, cap));
-    if (!h->d_points) HIPCHK(h, hipMalloc((void **)&h->d_points, cap * 3 * sizeof(double)));
-    rpe_launch_structure(h, B);
+    DM_ONCE(h, h->d_pose_mask, cap);
+    DM_ONCE(h, h->d_points, cap * 3);
+    rpe_launch_structure(h, last_run_first(h, B));
     HIPCHK(h, hipGetLastError());
     if (ransac_mask) HIPCHK(h, hipMemcpyAsync(ransac_mask, h->d_mask, n, hipMemcpyDeviceToHost, h->stream));
     if (pose_mask) HIPCHK(h, hipMemcpyAsync(pose_mask, h->d_pose_mask, n, hipMemcpyDeviceToHost, h->stream));
@@ -887,20 +949,17 @@ extern "C" int rpe_fetch_structure(rpe_handle *h, int B, uint8_t *ransac_mask, u
 static int refine_alloc(rpe_handle *h)
 {
     const size_t MB = (size_t)h->cfg.max_batch;
-    if (!h->d_ref_R) HIPCHK(h, hipMalloc((void **)&h->d_ref_R, MB * 9 * sizeof(double)));
-    if (!h->d_ref_t) HIPCHK(h, hipMalloc((void **)&h->d_ref_t, MB * 3 * sizeof(double)));
-    if (!h->d_ref_rms) HIPCHK(h, hipMalloc((void **)&h->d_ref_rms, MB * 2 * sizeof(double)));
-    if (!h->d_ref_R0) HIPCHK(h, hipMalloc((void **)&h->d_ref_R0, MB * 9 * sizeof(double)));
-    if (!h->d_ref_t0) HIPCHK(h, hipMalloc((void **)&h->d_ref_t0, MB * 3 * sizeof(double)));
-    if (!h->d_ref_inl) HIPCHK(h, hipMalloc((void **)&h->d_ref_inl, MB * sizeof(int)));
-    if (!h->d_ref_info) HIPCHK(h, hipMalloc((void **)&h->d_ref_info, MB * 4 * sizeof(int)));
+    DM_ONCE(h, h->d_ref_R, MB * 9); DM_ONCE(h, h->d_ref_t, MB * 3); DM_ONCE(h, h->d_ref_rms, MB * 2);
+    DM_ONCE(h, h->d_ref_R0, MB * 9); DM_ONCE(h, h->d_ref_t0, MB * 3);
+    DM_ONCE(h, h->d_ref_inl, MB); DM_ONCE(h, h->d_ref_info, MB * 4);
     return RPE_OK;
 }
 
-static int refine_run(rpe_handle *h, int B, int max_iters, bool from_batch, double *R, double *t, int32_t *inliers,
+static int refine_run(rpe_handle *h, const RpeRun &r, int max_iters, bool from_batch, double *R, double *t, int32_t *inliers,
                       int32_t *info, double *rms)
 {
-    rpe_launch_refine(h, B, max_iters, from_batch);
+    const int B = r.pairs;
+    rpe_launch_refine(h, r, max_iters, from_batch);
     HIPCHK(h, hipGetLastError());
     if (R) HIPCHK(h, hipMemcpyAsync(R, h->d_ref_R, sizeof(double) * 9 * B, hipMemcpyDeviceToHost, h->stream));
     if (t) HIPCHK(h, hipMemcpyAsync(t, h->d_ref_t, sizeof(double) * 3 * B, hipMemcpyDeviceToHost, h->stream));
@@ -916,13 +975,11 @@ extern "C" int rpe_refine_poses(rpe_handle *h, int B, int max_iters, double *R, 
 {
     if (!h || B < 1 || B > h->cfg.max_batch) return RPE_ERR_INVALID;
     if (max_iters < 1 || max_iters > 100) { h->err = "rpe_refine_poses: max_iters must be 1 ... 100"; return RPE_ERR_INVALID; }
-    if (h->last_chunked) { h->err = "rpe_refine_poses: the last host batch ran in chunks: per-match results are kept for unchunked and device-resident batches only"; return RPE_ERR_INVALID; }
-    if (!h->structure_valid) { h->err = "rpe_refine_poses: no batch or stream since the last stage-API call (it overwrote the per-match buffers)"; return RPE_ERR_INVALID; }
-    if (B > h->last_pairs) { h->err = "rpe_refine_poses: more pairs than the last batch had"; return RPE_ERR_INVALID; }
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    int rc = refine_alloc(h);
+    int rc = last_run_check(h, "rpe_refine_poses", B, "rpe_refine_poses: the last host batch ran in chunks: per-match results are kept for unchunked and device-resident batches only", true);
     if (rc) return rc;
-    return refine_run(h, B, max_iters, true, R, t, inliers, info, rms);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if ((rc = refine_alloc(h)) != RPE_OK) return rc;
+    return refine_run(h, last_run_first(h, B), max_iters, true, R, t, inliers, info, rms);
 }
 
 // ---------------------------------------------------------------- frame store
@@ -980,11 +1037,8 @@ extern "C" int rpe_frames_reserve(rpe_handle *h, int n_slots)
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (n_slots == h->fs.cap) return RPE_OK;
     HIPCHK(h, hipStreamSynchronize(h->stream));            // nothing in flight reads the store that is about to go
-    h->last_tab.clear();                                   // slot numbers of the last pair list: rpe_fetch_overflow refuses from here on
-    if (h->cam.tab) {                                      // a camera pair list reads the store's camera records: its per-match results end here
-        h->cam = RpeCamSrc{nullptr, nullptr, 0};
-        h->structure_valid = false;
-    }
+    h->last.tab.clear();                                   // slot numbers of the last pair list: rpe_fetch_overflow refuses from here on
+    if (h->last.run.cam.tab) last_run_end(h);              // a camera pair list reads the store's camera records: its per-match results end here
     if (n_slots == 0) { frames_free(h->fs); return RPE_OK; }
     const size_t kcap = (size_t)h->lay.kcap, db = (size_t)h->desc_bytes, N = (size_t)n_slots;
     const bool l2 = frames_keep_norms(h);
@@ -1031,7 +1085,7 @@ static int upload_table(rpe_handle *h, const int32_t *a, const int32_t *b, int n
     const size_t per = (size_t)2 * h->cfg.max_batch;                 // ints: 2*max_batch put slots or max_batch (slot1, slot2) entries
     if (!h->h_pairtab) {
         HIPCHK(h, hipHostMalloc((void **)&h->h_pairtab, RPE_TAB_RING * per * sizeof(int)));
-        HIPCHK(h, hipMalloc((void **)&h->d_pairtab, per * sizeof(int)));
+        DM(h, h->d_pairtab, per);
         for (int i = 0; i < RPE_TAB_RING; ++i) HIPCHK(h, hipEventCreateWithFlags(&h->ev_tab[i], hipEventDisableTiming));
     }
     const int r = h->tab_next;
@@ -1063,8 +1117,7 @@ static int frames_put_run(rpe_handle *h, const uint8_t *d_a, const uint8_t *d_b,
     const int n = na + nb;
     int rc = upload_table(h, slots, nullptr, n);
     if (rc) return rc;
-    // the workspace's per-image arrays are overwritten: what described "the last batch" through them is gone
-    h->structure_valid = false; h->last_pairs = 0; h->last_from_store = false; h->last_chunked = false;
+    last_run_end(h, true);      // the workspace's per-image arrays are overwritten: what described "the last batch" through them is gone
     h->ev_valid = false;
     if (h->cfg.feature_method == RPE_FEATURE_SIFT) rc = rpe_sift_run(h, d_a, d_b, na, nb);
     else rc = run_orb(h, d_a, d_b, na, nb);
@@ -1095,10 +1148,8 @@ extern "C" int rpe_frames_put(rpe_handle *h, const uint8_t *h_frames, int n, con
     int rc = frames_check_put(h, h_frames, n, slots);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    const size_t img = (size_t)h->cfg.width * h->cfg.height;
-    const int na = n < h->cfg.max_batch ? n : h->cfg.max_batch, nb = n - na;
-    HIPCHK(h, hipMemcpyAsync(h->d_stage1, h_frames, img * na, hipMemcpyHostToDevice, h->stream));
-    if (nb) HIPCHK(h, hipMemcpyAsync(h->d_stage2, h_frames + img * na, img * nb, hipMemcpyHostToDevice, h->stream));
+    int na, nb;
+    if ((rc = stage_images(h, h_frames, n, na, nb)) != RPE_OK) return rc;
     return frames_put_run(h, h->d_stage1, h->d_stage2, na, nb, slots);
 }
 
@@ -1128,40 +1179,26 @@ extern "C" int rpe_frames_info(rpe_handle *h, int n, const int32_t *slots, int32
 // K == nullptr: the camera form, every pair on the cameras of its two slots
 static int enqueue_pairs_run(rpe_handle *h, const int32_t *slot1, const int32_t *slot2, int P, const double *K, const char *who)
 {
-    const std::string w(who);
-    if (P > h->cfg.max_batch) { h->err = w + ": pair list exceeds max_batch"; return RPE_ERR_CAPACITY; }
-    if (h->fs.cap == 0) { h->err = w + ": no frame store (rpe_frames_reserve)"; return RPE_ERR_INVALID; }
-    for (int p = 0; p < P; ++p) {
-        if (slot1[p] < 0 || slot1[p] >= h->fs.cap || slot2[p] < 0 || slot2[p] >= h->fs.cap) { h->err = w + ": slot outside the store"; return RPE_ERR_INVALID; }
-        if (!h->fs.filled[(size_t)slot1[p]] || !h->fs.filled[(size_t)slot2[p]]) { h->err = w + ": a pair names an empty slot"; return RPE_ERR_INVALID; }
-        if (!K && (!h->fs.has_cam[(size_t)slot1[p]] || !h->fs.has_cam[(size_t)slot2[p]])) { h->err = w + ": a pair names a slot without a camera (rpe_frames_set_cameras)"; return RPE_ERR_INVALID; }
+    const char *bad = nullptr;
+    int rc = RPE_ERR_INVALID;
+    if (P > h->cfg.max_batch) { bad = ": pair list exceeds max_batch"; rc = RPE_ERR_CAPACITY; }
+    else if (h->fs.cap == 0) bad = ": no frame store (rpe_frames_reserve)";
+    for (int p = 0; p < P && !bad; ++p) {
+        if (slot1[p] < 0 || slot1[p] >= h->fs.cap || slot2[p] < 0 || slot2[p] >= h->fs.cap) bad = ": slot outside the store";
+        else if (!h->fs.filled[(size_t)slot1[p]] || !h->fs.filled[(size_t)slot2[p]]) bad = ": a pair names an empty slot";
+        else if (!K && (!h->fs.has_cam[(size_t)slot1[p]] || !h->fs.has_cam[(size_t)slot2[p]])) bad = ": a pair names a slot without a camera (rpe_frames_set_cameras)";
     }
+    if (bad) { h->err = std::string(who) + bad; return rc; }
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    int rc = RPE_OK;
     if (K && (rc = set_K(h, K)) != RPE_OK) return rc;
     if ((rc = upload_table(h, slot1, slot2, P)) != RPE_OK) return rc;
-    if (!K) h->cam = RpeCamSrc{h->fs.d_cam, (const int2 *)h->d_pairtab, 0};
-    struct Guard {                          // the launchers read h->pair_tab; never leave it behind for a batch
-        rpe_handle *h; ~Guard() { h->pair_tab = nullptr; }
-    } guard{h};
-    h->pair_tab = (const int2 *)h->d_pairtab;
-    h->last_pairs = P; h->last_img2_base = 0;
-    h->last_chunked = false; h->last_from_store = true;
-    h->last_tab.resize((size_t)2 * P);
-    for (int p = 0; p < P; ++p) { h->last_tab[2 * p] = slot1[p]; h->last_tab[2 * p + 1] = slot2[p]; }
-    h->structure_valid = false;
-    h->ev_first = RPE_STAGE_MATCH;
+    const RpeRun r = rpe_run_list(h, P, K ? RpeCamSrc{nullptr, nullptr, 0} : RpeCamSrc{h->fs.d_cam, (const int2 *)h->d_pairtab, 0});
+    RpeLastRun &l = last_run_begin(h, RpeLastRun::LIST, r);
+    l.tab.resize((size_t)2 * P);
+    for (int p = 0; p < P; ++p) { l.tab[2 * p] = slot1[p]; l.tab[2 * p + 1] = slot2[p]; }
     MARK(h, RPE_STAGE_MATCH);
-    if (h->cfg.norm_type == RPE_NORM_L2) rpe_launch_match_l2(h, P);
-    else rpe_launch_match(h, P);
-    MARK(h, RPE_STAGE_RANSAC);
-    rpe_launch_ransac(h, P, false);
-    MARK(h, RPE_STAGE_POSE);
-    rpe_launch_pose(h, P, true);
-    if (h->profiling) { hipEventRecord(h->ev[RPE_STAGE_COUNT], h->stream); h->ev_valid = true; }
-    HIPCHK(h, hipGetLastError());
-    h->structure_valid = true;
-    return RPE_OK;
+    if ((rc = run_tail(h, r)) != RPE_OK) last_run_end(h);
+    return rc;
 }
 
 extern "C" int rpe_enqueue_pairs(rpe_handle *h, const int32_t *slot1, const int32_t *slot2, int P, const double K[9])
@@ -1186,12 +1223,10 @@ extern "C" int rpe_orb_detect_and_compute(rpe_handle *h, const uint8_t *h_imgs, 
     if (h->cfg.feature_method != RPE_FEATURE_ORB) { h->err = "handle was not created for ORB"; return RPE_ERR_INVALID; }
     if (n_images > h->n_img_cap) { h->err = "n_images exceeds 2*max_batch"; return RPE_ERR_CAPACITY; }
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    h->structure_valid = false;                 // overwrites buffers rpe_fetch_structure reads
-    const size_t img = (size_t)h->cfg.width * h->cfg.height;
-    const int na = n_images < h->cfg.max_batch ? n_images : h->cfg.max_batch, nb = n_images - na;
-    HIPCHK(h, hipMemcpyAsync(h->d_stage1, h_imgs, img * na, hipMemcpyHostToDevice, h->stream));
-    if (nb) HIPCHK(h, hipMemcpyAsync(h->d_stage2, h_imgs + img * na, img * nb, hipMemcpyHostToDevice, h->stream));
-    int rc = run_orb(h, h->d_stage1, h->d_stage2, na, nb);
+    last_run_end(h);                            // overwrites buffers rpe_fetch_structure reads
+    int na, nb;
+    int rc = stage_images(h, h_imgs, n_images, na, nb);
+    if (rc == RPE_OK) rc = run_orb(h, h->d_stage1, h->d_stage2, na, nb);
     if (rc) return rc;
     const int kcap = h->lay.kcap;
     std::vector<unsigned> xy((size_t)n_images * kcap);
@@ -1274,22 +1309,16 @@ extern "C" int rpe_orb_debug_fetch(rpe_handle *h, int index, int which, uint8_t 
     return RPE_OK;
 }
 
-extern "C" int rpe_match_hamming(rpe_handle *h, const uint8_t *h_desc1, const int32_t *n1, const uint8_t *h_desc2,
-                                 const int32_t *n2, int B, int32_t *qidx, int32_t *tidx, int32_t *dist, int32_t *n_matches)
+// tail of rpe_match_hamming / rpe_match_l2 (descriptors of pair p uploaded to workspace slots p and B + p): counts,
+// the handle's matcher of that norm, the match lists (dist: int32 Hamming distances or f32 L2 distances, 4 bytes either)
+static int stage_match_run(rpe_handle *h, bool l2, const int32_t *n1, const int32_t *n2, int B, int32_t *qidx, int32_t *tidx,
+                           void *dist, int32_t *n_matches)
 {
-    if (!h || !h_desc1 || !h_desc2 || !n1 || !n2 || B < 1) return RPE_ERR_INVALID;
-    if (B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return RPE_ERR_CAPACITY; }
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    h->structure_valid = false;                 // overwrites buffers rpe_fetch_structure reads
-    const size_t per = (size_t)h->lay.kcap * 32, mm = h->cfg.max_matches;
-    for (int i = 0; i < B; ++i) if (n1[i] < 0 || n2[i] < 0 || n1[i] > h->lay.kcap || n2[i] > h->lay.kcap) {
-        h->err = "descriptor count exceeds keypoint capacity"; return RPE_ERR_INVALID;
-    }
-    HIPCHK(h, hipMemcpyAsync(h->d_desc, h_desc1, per * B, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_desc + per * B, h_desc2, per * B, hipMemcpyHostToDevice, h->stream));
+    const size_t mm = h->cfg.max_matches;
     HIPCHK(h, hipMemcpyAsync(h->d_kp_count, n1, sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->d_kp_count + B, n2, sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
-    rpe_launch_match(h, B);
+    if (l2) rpe_launch_match_l2(h, rpe_run_batch(h, B));
+    else rpe_launch_match(h, rpe_run_batch(h, B));
     HIPCHK(h, hipGetLastError());
     if (qidx) HIPCHK(h, hipMemcpyAsync(qidx, h->d_m_q, sizeof(int) * mm * B, hipMemcpyDeviceToHost, h->stream));
     if (tidx) HIPCHK(h, hipMemcpyAsync(tidx, h->d_m_t, sizeof(int) * mm * B, hipMemcpyDeviceToHost, h->stream));
@@ -1297,6 +1326,22 @@ extern "C" int rpe_match_hamming(rpe_handle *h, const uint8_t *h_desc1, const in
     if (n_matches) HIPCHK(h, hipMemcpyAsync(n_matches, h->d_m_n, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return RPE_OK;
+}
+
+extern "C" int rpe_match_hamming(rpe_handle *h, const uint8_t *h_desc1, const int32_t *n1, const uint8_t *h_desc2,
+                                 const int32_t *n2, int B, int32_t *qidx, int32_t *tidx, int32_t *dist, int32_t *n_matches)
+{
+    if (!h || !h_desc1 || !h_desc2 || !n1 || !n2 || B < 1) return RPE_ERR_INVALID;
+    if (B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return RPE_ERR_CAPACITY; }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    last_run_end(h);                            // overwrites buffers rpe_fetch_structure reads
+    const size_t per = (size_t)h->lay.kcap * 32;
+    for (int i = 0; i < B; ++i) if (n1[i] < 0 || n2[i] < 0 || n1[i] > h->lay.kcap || n2[i] > h->lay.kcap) {
+        h->err = "descriptor count exceeds keypoint capacity"; return RPE_ERR_INVALID;
+    }
+    HIPCHK(h, hipMemcpyAsync(h->d_desc, h_desc1, per * B, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_desc + per * B, h_desc2, per * B, hipMemcpyHostToDevice, h->stream));
+    return stage_match_run(h, false, n1, n2, B, qidx, tidx, dist, n_matches);
 }
 
 static int upload_points(rpe_handle *h, const float *p1, const float *p2, const int32_t *m, int B)
@@ -1309,70 +1354,11 @@ static int upload_points(rpe_handle *h, const float *p1, const float *p2, const 
     return RPE_OK;
 }
 
-extern "C" int rpe_find_essential(rpe_handle *h, const float *h_pts1, const float *h_pts2, const int32_t *m, int B,
-                                  const double K[9], double *E, uint8_t *mask, int32_t *found, int32_t *info)
-{
-    if (!h || !h_pts1 || !h_pts2 || !m || !K || B < 1) return RPE_ERR_INVALID;
-    if (B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return RPE_ERR_CAPACITY; }
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    h->structure_valid = false;                 // overwrites buffers rpe_fetch_structure reads
-    int rc = upload_points(h, h_pts1, h_pts2, m, B);
-    if (rc) return rc;
-    if ((rc = set_K(h, K)) != RPE_OK) return rc;
-    HIPCHK(h, hipMemsetAsync(h->d_E, 0, sizeof(double) * 9 * B, h->stream));
-    rpe_launch_ransac(h, B, true);
-    HIPCHK(h, hipGetLastError());
-    std::vector<RpeRansacState> st(B);
-    HIPCHK(h, hipMemcpyAsync(st.data(), h->d_rstate, sizeof(RpeRansacState) * B, hipMemcpyDeviceToHost, h->stream));
-    if (mask) HIPCHK(h, hipMemcpyAsync(mask, h->d_mask, (size_t)h->cfg.max_matches * B, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    for (int i = 0; i < B; ++i) {
-        if (E) memcpy(E + 9 * i, st[i].E, sizeof(double) * 9);
-        if (found) found[i] = st[i].found;
-        if (info) { info[4 * i] = st[i].best_count; info[4 * i + 1] = st[i].best_iter; info[4 * i + 2] = st[i].best_model; info[4 * i + 3] = st[i].iters_run; }
-    }
-    return RPE_OK;
-}
-
-extern "C" int rpe_recover_pose(rpe_handle *h, const double *h_E, const float *h_pts1, const float *h_pts2, const int32_t *m,
-                                int B, const double K[9], double *R, double *t, int32_t *inliers)
-{
-    if (!h || !h_E || !h_pts1 || !h_pts2 || !m || !K || B < 1) return RPE_ERR_INVALID;
-    if (B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return RPE_ERR_CAPACITY; }
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    h->structure_valid = false;                 // overwrites buffers rpe_fetch_structure reads
-    int rc = upload_points(h, h_pts1, h_pts2, m, B);
-    if (rc) return rc;
-    if ((rc = set_K(h, K)) != RPE_OK) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_E, h_E, sizeof(double) * 9 * B, hipMemcpyHostToDevice, h->stream));
-    rpe_launch_pose(h, B, false);
-    HIPCHK(h, hipGetLastError());
-    return rpe_fetch_results(h, B, R, t, inliers, nullptr, nullptr);
-}
-
-extern "C" int rpe_refine_pose_points(rpe_handle *h, const double *h_R0, const double *h_t0, const float *h_pts1,
-                                      const float *h_pts2, const uint8_t *h_mask, const int32_t *m, int B, const double K[9],
-                                      int max_iters, double *R, double *t, int32_t *inliers, int32_t *info, double *rms)
-{
-    if (!h || !h_R0 || !h_t0 || !h_pts1 || !h_pts2 || !h_mask || !m || !K || B < 1) return RPE_ERR_INVALID;
-    if (B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return RPE_ERR_CAPACITY; }
-    if (max_iters < 1 || max_iters > 100) { h->err = "rpe_refine_pose_points: max_iters must be 1 ... 100"; return RPE_ERR_INVALID; }
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    h->structure_valid = false;                 // overwrites buffers rpe_fetch_structure reads
-    int rc = upload_points(h, h_pts1, h_pts2, m, B);
-    if (rc) return rc;
-    if ((rc = set_K(h, K)) != RPE_OK) return rc;
-    if ((rc = refine_alloc(h)) != RPE_OK) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_mask, h_mask, (size_t)h->cfg.max_matches * B, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_ref_R0, h_R0, sizeof(double) * 9 * B, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_ref_t0, h_t0, sizeof(double) * 3 * B, hipMemcpyHostToDevice, h->stream));
-    return refine_run(h, B, max_iters, false, R, t, inliers, info, rms);
-}
-
 // ---------------------------------------------------------------- camera models
 // rpe_*_cameras (NOT in the reference): a camera per frame instead of one K per call.  The entry points validate, place
 // the camera records where the kernels find them -- 2 B records per batch / stage call in d_batch_cams, one record per
-// frame-store slot in fs.d_cam -- and set h->cam, which makes the launchers of geom_kernels.hip take the camera instances.
+// frame-store slot in fs.d_cam -- and name them in the camera source of the run they launch, which makes the launchers of
+// geom_kernels.hip take the camera instances.
 static int check_cameras(rpe_handle *h, const rpe_camera *c, int n, const char *who)
 {
     for (int i = 0; i < n; ++i) {
@@ -1390,14 +1376,13 @@ static int upload_batch_cameras(rpe_handle *h, const rpe_camera *cam1, const rpe
 {
     const size_t cap = (size_t)2 * h->cfg.max_batch;
     if (!h->d_batch_cams) {
-        HIPCHK(h, hipMalloc((void **)&h->d_batch_cams, cap * sizeof(rpe_camera)));
+        DM(h, h->d_batch_cams, cap);
         h->h_batch_cams.resize(cap);
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));      // nothing in flight reads the records or their staging
     memcpy(h->h_batch_cams.data(), cam1, sizeof(rpe_camera) * (size_t)B);
     memcpy(h->h_batch_cams.data() + B, cam2, sizeof(rpe_camera) * (size_t)B);
     HIPCHK(h, hipMemcpyAsync(h->d_batch_cams, h->h_batch_cams.data(), sizeof(rpe_camera) * 2 * (size_t)B, hipMemcpyHostToDevice, h->stream));
-    h->cam = RpeCamSrc{h->d_batch_cams, nullptr, B};
     return RPE_OK;
 }
 
@@ -1410,7 +1395,7 @@ extern "C" int rpe_frames_set_cameras(rpe_handle *h, int n, const int32_t *slots
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipStreamSynchronize(h->stream));      // a pair list in flight may read the records about to change
-    if (h->cam.tab) { h->cam = RpeCamSrc{nullptr, nullptr, 0}; h->structure_valid = false; }
+    if (h->last.run.cam.tab) last_run_end(h);
     for (int i = 0; i < n; ++i) {
         const size_t s = (size_t)slots[i];
         h->fs.h_cam[s] = cams[i];
@@ -1445,7 +1430,8 @@ extern "C" int rpe_enqueue_batch_cameras_device(rpe_handle *h, const uint8_t *d_
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if ((rc = upload_batch_cameras(h, cam1, cam2, B)) != RPE_OK) return rc;
-    return run_pairs(h, d_imgs1, d_imgs2, B, B, B, B);          // plain launches whatever B: the captured graphs hold the shared-K instances
+    // plain launches whatever B: the captured graphs hold the shared-K instances
+    return run_images(h, d_imgs1, d_imgs2, B, B, rpe_run_batch(h, B, RpeCamSrc{h->d_batch_cams, nullptr, B}));
 }
 
 extern "C" int rpe_estimate_batch_cameras_device(rpe_handle *h, const uint8_t *d_imgs1, const uint8_t *d_imgs2, int B,
@@ -1464,7 +1450,7 @@ extern "C" int rpe_estimate_batch_cameras(rpe_handle *h, const uint8_t *h_imgs1,
     if (!h || !h_imgs1 || !h_imgs2 || !cam1 || !cam2 || B < 1) { if (h) h->err = "rpe_estimate_batch_cameras: null argument or B < 1"; return RPE_ERR_INVALID; }
     if (B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return RPE_ERR_CAPACITY; }
     const size_t img = (size_t)h->cfg.width * h->cfg.height;
-    if (B >= 512 && img * (size_t)B >= ((size_t)64 << 20)) {
+    if (batch_is_chunked(h, B)) {
         h->err = "rpe_estimate_batch_cameras: host batches this large (B >= 512 and >= 64 MiB per image set) are not chunked by the camera form: upload the images and call rpe_estimate_batch_cameras_device";
         return RPE_ERR_INVALID;
     }
@@ -1500,29 +1486,35 @@ extern "C" int rpe_undistort_points(rpe_handle *h, const float *h_pts, int n, co
     return RPE_OK;
 }
 
-// common head of the three stage forms: arguments, points, cameras
-static int stage_cameras_begin(rpe_handle *h, const float *p1, const float *p2, const int32_t *m, int B,
-                               const rpe_camera *cam1, const rpe_camera *cam2, const char *who)
+// ---------------------------------------------------------------- stage API: geometry
+// findEssentialMat, recoverPose and the refinement over uploaded points, each on one K (rpe_*) or on a camera per side and
+// pair (rpe_*_cameras, K == nullptr here).  Head of the three: capacity, cameras, points and intrinsics resident; `run`
+// is the stage run over the B uploaded pairs.
+static int stage_begin(rpe_handle *h, const char *who, const float *p1, const float *p2, const int32_t *m, int B,
+                       const double *K, const rpe_camera *cam1, const rpe_camera *cam2, RpeRun &run)
 {
     if (B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return RPE_ERR_CAPACITY; }
-    int rc = check_cameras(h, cam1, B, who);
-    if (!rc) rc = check_cameras(h, cam2, B, who);
+    int rc = RPE_OK;
+    if (!K && (rc = check_cameras(h, cam1, B, who)) == RPE_OK) rc = check_cameras(h, cam2, B, who);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    h->structure_valid = false;                 // overwrites buffers rpe_fetch_structure reads
-    if ((rc = upload_batch_cameras(h, cam1, cam2, B)) != RPE_OK) return rc;
-    return upload_points(h, p1, p2, m, B);
+    last_run_end(h);                            // overwrites buffers rpe_fetch_structure reads
+    if (!K && (rc = upload_batch_cameras(h, cam1, cam2, B)) != RPE_OK) return rc;
+    if ((rc = upload_points(h, p1, p2, m, B)) != RPE_OK) return rc;
+    if (K && (rc = set_K(h, K)) != RPE_OK) return rc;
+    run = rpe_run_batch(h, B, K ? RpeCamSrc{nullptr, nullptr, 0} : RpeCamSrc{h->d_batch_cams, nullptr, B});
+    return RPE_OK;
 }
 
-extern "C" int rpe_find_essential_cameras(rpe_handle *h, const float *h_pts1, const float *h_pts2, const int32_t *m, int B,
-                                          const rpe_camera *cam1, const rpe_camera *cam2, double *E, uint8_t *mask,
-                                          int32_t *found, int32_t *info)
+static int stage_find_essential(rpe_handle *h, const char *who, const float *h_pts1, const float *h_pts2, const int32_t *m, int B,
+                                const double *K, const rpe_camera *cam1, const rpe_camera *cam2, double *E, uint8_t *mask,
+                                int32_t *found, int32_t *info)
 {
-    if (!h || !h_pts1 || !h_pts2 || !m || !cam1 || !cam2 || B < 1) return RPE_ERR_INVALID;
-    int rc = stage_cameras_begin(h, h_pts1, h_pts2, m, B, cam1, cam2, "rpe_find_essential_cameras");
+    RpeRun run;
+    int rc = stage_begin(h, who, h_pts1, h_pts2, m, B, K, cam1, cam2, run);
     if (rc) return rc;
     HIPCHK(h, hipMemsetAsync(h->d_E, 0, sizeof(double) * 9 * B, h->stream));
-    rpe_launch_ransac(h, B, true);
+    rpe_launch_ransac(h, run, true);
     HIPCHK(h, hipGetLastError());
     std::vector<RpeRansacState> st(B);
     HIPCHK(h, hipMemcpyAsync(st.data(), h->d_rstate, sizeof(RpeRansacState) * B, hipMemcpyDeviceToHost, h->stream));
@@ -1536,18 +1528,73 @@ extern "C" int rpe_find_essential_cameras(rpe_handle *h, const float *h_pts1, co
     return RPE_OK;
 }
 
+static int stage_recover_pose(rpe_handle *h, const char *who, const double *h_E, const float *h_pts1, const float *h_pts2,
+                              const int32_t *m, int B, const double *K, const rpe_camera *cam1, const rpe_camera *cam2,
+                              double *R, double *t, int32_t *inliers)
+{
+    RpeRun run;
+    int rc = stage_begin(h, who, h_pts1, h_pts2, m, B, K, cam1, cam2, run);
+    if (rc) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->d_E, h_E, sizeof(double) * 9 * B, hipMemcpyHostToDevice, h->stream));
+    if (run.cam.cams) rpe_launch_camera_normalise(h, run);      // recover_pose_kernel's camera instances read d_n1 / d_n2
+    rpe_launch_pose(h, run, false);
+    HIPCHK(h, hipGetLastError());
+    return rpe_fetch_results(h, B, R, t, inliers, nullptr, nullptr);
+}
+
+static int stage_refine(rpe_handle *h, const char *who, const double *h_R0, const double *h_t0, const float *h_pts1,
+                        const float *h_pts2, const uint8_t *h_mask, const int32_t *m, int B, const double *K,
+                        const rpe_camera *cam1, const rpe_camera *cam2, int max_iters, double *R, double *t, int32_t *inliers,
+                        int32_t *info, double *rms)
+{
+    RpeRun run;
+    int rc = stage_begin(h, who, h_pts1, h_pts2, m, B, K, cam1, cam2, run);
+    if (rc) return rc;
+    if ((rc = refine_alloc(h)) != RPE_OK) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->d_mask, h_mask, (size_t)h->cfg.max_matches * B, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_ref_R0, h_R0, sizeof(double) * 9 * B, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_ref_t0, h_t0, sizeof(double) * 3 * B, hipMemcpyHostToDevice, h->stream));
+    return refine_run(h, run, max_iters, false, R, t, inliers, info, rms);
+}
+
+extern "C" int rpe_find_essential(rpe_handle *h, const float *h_pts1, const float *h_pts2, const int32_t *m, int B,
+                                  const double K[9], double *E, uint8_t *mask, int32_t *found, int32_t *info)
+{
+    if (!h || !h_pts1 || !h_pts2 || !m || !K || B < 1) return RPE_ERR_INVALID;
+    return stage_find_essential(h, "rpe_find_essential", h_pts1, h_pts2, m, B, K, nullptr, nullptr, E, mask, found, info);
+}
+
+extern "C" int rpe_find_essential_cameras(rpe_handle *h, const float *h_pts1, const float *h_pts2, const int32_t *m, int B,
+                                          const rpe_camera *cam1, const rpe_camera *cam2, double *E, uint8_t *mask,
+                                          int32_t *found, int32_t *info)
+{
+    if (!h || !h_pts1 || !h_pts2 || !m || !cam1 || !cam2 || B < 1) return RPE_ERR_INVALID;
+    return stage_find_essential(h, "rpe_find_essential_cameras", h_pts1, h_pts2, m, B, nullptr, cam1, cam2, E, mask, found, info);
+}
+
+extern "C" int rpe_recover_pose(rpe_handle *h, const double *h_E, const float *h_pts1, const float *h_pts2, const int32_t *m,
+                                int B, const double K[9], double *R, double *t, int32_t *inliers)
+{
+    if (!h || !h_E || !h_pts1 || !h_pts2 || !m || !K || B < 1) return RPE_ERR_INVALID;
+    return stage_recover_pose(h, "rpe_recover_pose", h_E, h_pts1, h_pts2, m, B, K, nullptr, nullptr, R, t, inliers);
+}
+
 extern "C" int rpe_recover_pose_cameras(rpe_handle *h, const double *h_E, const float *h_pts1, const float *h_pts2,
                                         const int32_t *m, int B, const rpe_camera *cam1, const rpe_camera *cam2,
                                         double *R, double *t, int32_t *inliers)
 {
     if (!h || !h_E || !h_pts1 || !h_pts2 || !m || !cam1 || !cam2 || B < 1) return RPE_ERR_INVALID;
-    int rc = stage_cameras_begin(h, h_pts1, h_pts2, m, B, cam1, cam2, "rpe_recover_pose_cameras");
-    if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_E, h_E, sizeof(double) * 9 * B, hipMemcpyHostToDevice, h->stream));
-    rpe_launch_camera_normalise(h, B);          // recover_pose_kernel's camera instances read d_n1 / d_n2
-    rpe_launch_pose(h, B, false);
-    HIPCHK(h, hipGetLastError());
-    return rpe_fetch_results(h, B, R, t, inliers, nullptr, nullptr);
+    return stage_recover_pose(h, "rpe_recover_pose_cameras", h_E, h_pts1, h_pts2, m, B, nullptr, cam1, cam2, R, t, inliers);
+}
+
+extern "C" int rpe_refine_pose_points(rpe_handle *h, const double *h_R0, const double *h_t0, const float *h_pts1,
+                                      const float *h_pts2, const uint8_t *h_mask, const int32_t *m, int B, const double K[9],
+                                      int max_iters, double *R, double *t, int32_t *inliers, int32_t *info, double *rms)
+{
+    if (!h || !h_R0 || !h_t0 || !h_pts1 || !h_pts2 || !h_mask || !m || !K || B < 1) return RPE_ERR_INVALID;
+    if (B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return RPE_ERR_CAPACITY; }      // in front of max_iters, as ever
+    if (max_iters < 1 || max_iters > 100) { h->err = "rpe_refine_pose_points: max_iters must be 1 ... 100"; return RPE_ERR_INVALID; }
+    return stage_refine(h, "rpe_refine_pose_points", h_R0, h_t0, h_pts1, h_pts2, h_mask, m, B, K, nullptr, nullptr, max_iters, R, t, inliers, info, rms);
 }
 
 extern "C" int rpe_refine_pose_points_cameras(rpe_handle *h, const double *h_R0, const double *h_t0, const float *h_pts1,
@@ -1557,13 +1604,7 @@ extern "C" int rpe_refine_pose_points_cameras(rpe_handle *h, const double *h_R0,
 {
     if (!h || !h_R0 || !h_t0 || !h_pts1 || !h_pts2 || !h_mask || !m || !cam1 || !cam2 || B < 1) return RPE_ERR_INVALID;
     if (max_iters < 1 || max_iters > 100) { h->err = "rpe_refine_pose_points_cameras: max_iters must be 1 ... 100"; return RPE_ERR_INVALID; }
-    int rc = stage_cameras_begin(h, h_pts1, h_pts2, m, B, cam1, cam2, "rpe_refine_pose_points_cameras");
-    if (rc) return rc;
-    if ((rc = refine_alloc(h)) != RPE_OK) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_mask, h_mask, (size_t)h->cfg.max_matches * B, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_ref_R0, h_R0, sizeof(double) * 9 * B, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_ref_t0, h_t0, sizeof(double) * 3 * B, hipMemcpyHostToDevice, h->stream));
-    return refine_run(h, B, max_iters, false, R, t, inliers, info, rms);
+    return stage_refine(h, "rpe_refine_pose_points_cameras", h_R0, h_t0, h_pts1, h_pts2, h_mask, m, B, nullptr, cam1, cam2, max_iters, R, t, inliers, info, rms);
 }
 
 // ---------------------------------------------------------------- profiling
@@ -1738,12 +1779,10 @@ extern "C" int rpe_sift_detect_and_compute(rpe_handle *h, const uint8_t *h_imgs,
     if (h->cfg.feature_method != RPE_FEATURE_SIFT) { h->err = "handle was not created for SIFT"; return RPE_ERR_INVALID; }
     if (n_images > h->n_img_cap) { h->err = "n_images exceeds 2*max_batch"; return RPE_ERR_CAPACITY; }
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    h->structure_valid = false;                 // overwrites buffers rpe_fetch_structure reads
-    const size_t img = (size_t)h->cfg.width * h->cfg.height;
-    const int na = n_images < h->cfg.max_batch ? n_images : h->cfg.max_batch, nb = n_images - na;
-    HIPCHK(h, hipMemcpyAsync(h->d_stage1, h_imgs, img * na, hipMemcpyHostToDevice, h->stream));
-    if (nb) HIPCHK(h, hipMemcpyAsync(h->d_stage2, h_imgs + img * na, img * nb, hipMemcpyHostToDevice, h->stream));
-    int rc = rpe_sift_run(h, h->d_stage1, h->d_stage2, na, nb);
+    last_run_end(h);                            // overwrites buffers rpe_fetch_structure reads
+    int na, nb;
+    int rc = stage_images(h, h_imgs, n_images, na, nb);
+    if (rc == RPE_OK) rc = rpe_sift_run(h, h->d_stage1, h->d_stage2, na, nb);
     if (rc) return rc;
     const int kcap = h->lay.kcap;
     std::vector<float> fin((size_t)n_images * kcap * 6);
@@ -1782,9 +1821,9 @@ extern "C" int rpe_match_l2(rpe_handle *h, const float *h_desc1, const int32_t *
     if (h->cfg.norm_type != RPE_NORM_L2) { h->err = "handle was not created for NORM_L2"; return RPE_ERR_INVALID; }
     if (B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return RPE_ERR_CAPACITY; }
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    h->structure_valid = false;                 // overwrites buffers rpe_fetch_structure reads
+    last_run_end(h);                            // overwrites buffers rpe_fetch_structure reads
     const size_t dim = (size_t)h->desc_bytes;               // 128 (SIFT) or 32 (ORB descriptors under NORM_L2)
-    const size_t per = (size_t)h->lay.kcap * dim, mm = h->cfg.max_matches;
+    const size_t per = (size_t)h->lay.kcap * dim;
     std::vector<uint8_t> u(2 * per * B, 0);
     for (int s = 0; s < 2; ++s) {
         const float *src = s ? h_desc2 : h_desc1; const int32_t *cn = s ? n2 : n1;
@@ -1798,14 +1837,5 @@ extern "C" int rpe_match_l2(rpe_handle *h, const float *h_desc1, const int32_t *
         }
     }
     HIPCHK(h, hipMemcpyAsync(h->d_desc, u.data(), u.size(), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_kp_count, n1, sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_kp_count + B, n2, sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
-    rpe_launch_match_l2(h, B);
-    HIPCHK(h, hipGetLastError());
-    if (qidx) HIPCHK(h, hipMemcpyAsync(qidx, h->d_m_q, sizeof(int) * mm * B, hipMemcpyDeviceToHost, h->stream));
-    if (tidx) HIPCHK(h, hipMemcpyAsync(tidx, h->d_m_t, sizeof(int) * mm * B, hipMemcpyDeviceToHost, h->stream));
-    if (dist) HIPCHK(h, hipMemcpyAsync(dist, h->d_m_d, sizeof(float) * mm * B, hipMemcpyDeviceToHost, h->stream));
-    if (n_matches) HIPCHK(h, hipMemcpyAsync(n_matches, h->d_m_n, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return RPE_OK;
+    return stage_match_run(h, true, n1, n2, B, qidx, tidx, dist, n_matches);
 }

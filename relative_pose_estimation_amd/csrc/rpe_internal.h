@@ -16,7 +16,10 @@
 #define RPE_GRAPH_MAX_PAIRS 16    // batches up to this many pairs are replayed as a captured hipGraph
 #define RPE_MATCH_SPLIT_PAIRS 64   // batches up to this many pairs split a pair's Hamming matching over several workgroups
 #define RPE_TAB_RING 4            // pinned pieces the slot tables of rpe_frames_put* / rpe_enqueue_pairs rotate through
-#define RPE_RESULT_BYTES 108     // per pair: R 72 + t 24 + inliers 4 + status 4 + n_matches 4
+// one pair's results, section by section of the result block (d_resblk): R, t, inliers, status, n_matches
+#define RPE_RESULT_SECTIONS 5
+static const size_t kRpeResultElem[RPE_RESULT_SECTIONS] = {9 * sizeof(double), 3 * sizeof(double), sizeof(int), sizeof(int), sizeof(int)};
+#define RPE_RESULT_BYTES 108     // their sum
 // FAST tile = 64 x FAST_TH output pixels, FAST_TH * 4 threads.  Unlike the resize kernel (latency bound: smaller tiles
 // won), FAST is bound by instruction issue and 32-row tiles with two waves only add halo work: 4.43 -> 4.79 ms.
 #ifndef FAST_TH
@@ -196,21 +199,45 @@ struct RpeRansacState {
 
 struct RpeSiftState;
 
+// Where the matchers and the status test find the features of pair p: the extraction workspace under the rule
+// (p, img2_base + p), or the frame store under a pair table
+struct RpeFeatSrc { const uint8_t *desc; const int *count; const float2 *pt; const int2 *norm; const int2 *tab; int img2_base; };
+
+// What one launch sequence operates on.  The entry points build it (rpe_run_batch / rpe_run_stream / rpe_run_list below)
+// and hand it to the launchers of match_kernels.hip and geom_kernels.hip, which read nothing of it from the handle.
+struct RpeRun {
+    int pairs;
+    RpeFeatSrc feat;
+    RpeCamSrc cam;        // cam.cams == nullptr: the shared d_K and the kernels' CAM = false instances
+};
+
+// The last run, for the calls that come behind it: rpe_fetch_overflow, rpe_fetch_matched_points, rpe_fetch_structure and
+// rpe_refine_poses (the last two launch again, on exactly `run`).  Written by last_run_begin / last_run_end (rpe_api.hip)
+// and by nothing else.
+struct RpeLastRun {
+    enum Kind { NONE, RULE, LIST, CHUNKED };   // nothing / a batch or stream under the rule / a pair list / a host batch run in chunks
+    Kind kind = NONE;
+    int pairs = 0;                    // CHUNKED: of the whole batch
+    RpeRun run{};
+    std::vector<int> tab;             // LIST: its (slot1, slot2) entries; emptied when the store is resized
+    std::vector<uint32_t> ovf;        // CHUNKED: capacity flags per pair (OR of the pair's two images), collected across the chunks
+    bool per_match = false;           // d_pts*, d_n*, d_rstate, d_mask, d_R / d_t still hold the run's per-match data
+};
+
 struct rpe_handle {
     rpe_config cfg;
     RpeSiftState *sift = nullptr;             // SIFT workspace (feature_method == RPE_FEATURE_SIFT)
-    int img2_base = 0;                        // 0: pair p = slots (p, B+p); 1: stream, pair p = slots (p, p+1)
     int desc_bytes = 32;                      // 32 (rBRIEF) or 128 (SIFT, stored as u8)
     std::string err;
     hipStream_t stream = nullptr;
     hipStream_t copy_stream = nullptr;          // uploads of a chunked host batch (rpe_estimate_batch), created on first use
     hipEvent_t ev_up[8] = {};                   // 'chunk c is resident' events
-    bool last_chunked = false;                  // the last host batch ran in chunks: per-pair debug arrays hold its last chunk only
     // hipGraphs of the whole launch sequence of small batches (rpe_enqueue_batch_device): the drop-in's estimate() is a batch
     // of ONE pair, ~50 launches of a few microseconds each; replaying them as one graph removes the per-launch host cost
     struct GraphEntry { const uint8_t *a, *b; int B; hipGraph_t graph; hipGraphExec_t exec; };
     std::vector<GraphEntry> graphs;
-    std::vector<uint32_t> ovf_pairs;            // capacity flags of a chunked host batch, per pair (OR of the pair's two images), kept across its chunks
+    RpeLastRun last;
+    std::vector<void *> dev_allocs;             // every device buffer of the handle but the frame store's: workspace, tables, created-on-first-use; rpe_destroy frees them
     RpeDeviceLayout lay{};
     int n_img_cap = 0;              // 2*max_batch
     // tile tables
@@ -239,7 +266,6 @@ struct rpe_handle {
     float2 *d_kp_cs = nullptr;        // [img][kcap] (cos, sin) of the keypoint angle
     int *d_kp_count = nullptr;        // [img]
     unsigned *d_ovf = nullptr;        // [img] RPE_OVF_* capacity flags of the last extraction
-    int last_pairs = 0, last_img2_base = 0;   // image slots of the last batch's pairs: (p, last_img2_base + p)
     int level0_slots = 0;             // image slots of the last ORB run (debug fetch of an in-place level 0)
     uint8_t *d_desc = nullptr;        // [img][kcap][32]
     // matching
@@ -268,7 +294,6 @@ struct rpe_handle {
     // per pair; start pose of the stage form
     double *d_ref_R = nullptr, *d_ref_t = nullptr, *d_ref_rms = nullptr, *d_ref_R0 = nullptr, *d_ref_t0 = nullptr;
     int *d_ref_inl = nullptr, *d_ref_info = nullptr;
-    bool structure_valid = false;         // d_pts*, d_n*, d_rstate, d_R / d_t still describe the last batch / stream (run_pairs)
     // results
     double *d_R = nullptr, *d_t = nullptr, *d_E = nullptr;
     int *d_inliers = nullptr, *d_status = nullptr;
@@ -295,30 +320,29 @@ struct rpe_handle {
     int *d_pairtab = nullptr;             // device copy, uploaded on the handle's stream
     hipEvent_t ev_tab[RPE_TAB_RING] = {}; // piece r of h_pairtab has been uploaded (the call that takes it next may overwrite it)
     int tab_next = 0;
-    const int2 *pair_tab = nullptr;       // set by rpe_enqueue_pairs around its launches: the matchers and the status test read the store
-    bool last_from_store = false;         // the last batch was a pair list: rpe_fetch_overflow reads last_tab and the store's flags
-    std::vector<int> last_tab;            // its (slot1, slot2) entries
-    // Camera path (rpe_*_cameras): set by those calls and left standing, so that rpe_fetch_structure / rpe_refine_poses
-    // launch the camera instances for "the last batch"; every single-K entry point clears it (set_K)
-    RpeCamSrc cam{nullptr, nullptr, 0};
     rpe_camera *d_batch_cams = nullptr;   // [2*max_batch] cameras of a camera batch / stage call: cam1[0, B) then cam2[0, B) (created on first use)
     std::vector<rpe_camera> h_batch_cams; // their host staging
     // profiling
     bool profiling = false;
     hipEvent_t ev[RPE_STAGE_COUNT + 1] = {};
-    float stage_ms[RPE_STAGE_COUNT] = {};
     bool ev_valid = false;
     int ev_first = 0;                     // first stage the last profiled call ran (a pair list starts at RPE_STAGE_MATCH)
-    std::vector<void *> user_allocs;
+    std::vector<void *> user_allocs;            // rpe_device_malloc: the caller's buffers
 };
 
-// Where the matchers and the status test find the features of pair p: the extraction workspace under the batch / stream
-// rule, or the frame store under a pair table
-struct RpeFeatSrc { const uint8_t *desc; const int *count; const float2 *pt; const int2 *norm; const int2 *tab; int img2_base; };
-static inline RpeFeatSrc rpe_feat_src(const rpe_handle *h, int B)
+// The runs.  `cam` defaults to the shared K; a camera source must address its records as the run addresses its images.
+static inline RpeRun rpe_run_rule(const rpe_handle *h, int pairs, int img2_base, RpeCamSrc cam)
 {
-    if (h->pair_tab) return {h->fs.d_desc, h->fs.d_count, h->fs.d_kp_pt, h->fs.d_norm, h->pair_tab, 0};
-    return {h->d_desc, h->d_kp_count, h->d_kp_pt, (const int2 *)h->d_m_norm, nullptr, h->img2_base ? h->img2_base : B};
+    return {pairs, {h->d_desc, h->d_kp_count, h->d_kp_pt, (const int2 *)h->d_m_norm, nullptr, img2_base}, cam};
+}
+// B pairs on the workspace slots (p, B + p): a batch, and a stage call over B uploaded pairs
+static inline RpeRun rpe_run_batch(const rpe_handle *h, int B, RpeCamSrc cam = {nullptr, nullptr, 0}) { return rpe_run_rule(h, B, B, cam); }
+// pairs + 1 consecutive frames: pair p on the workspace slots (p, p + 1)
+static inline RpeRun rpe_run_stream(const rpe_handle *h, int pairs, RpeCamSrc cam = {nullptr, nullptr, 0}) { return rpe_run_rule(h, pairs, 1, cam); }
+// P entries of the device pair table over the frame store
+static inline RpeRun rpe_run_list(const rpe_handle *h, int P, RpeCamSrc cam = {nullptr, nullptr, 0})
+{
+    return {P, {h->fs.d_desc, h->fs.d_count, h->fs.d_kp_pt, h->fs.d_norm, (const int2 *)h->d_pairtab, 0}, cam};
 }
 
 // ---- kernel launchers (defined in the .hip files) --------------------------
@@ -331,8 +355,8 @@ void rpe_launch_keypoints(rpe_handle *h, int n_img);
 void rpe_launch_angle(rpe_handle *h, int n_img);
 void rpe_launch_blur(rpe_handle *h, int n_img);
 void rpe_launch_describe(rpe_handle *h, int n_img);
-void rpe_launch_match(rpe_handle *h, int B);
-void rpe_launch_match_l2(rpe_handle *h, int B);
+void rpe_launch_match(rpe_handle *h, const RpeRun &r);
+void rpe_launch_match_l2(rpe_handle *h, const RpeRun &r);
 void rpe_launch_l2_norms(rpe_handle *h, int n_img);
 int rpe_sift_create(rpe_handle *h);
 void rpe_sift_destroy(rpe_handle *h);
@@ -340,11 +364,11 @@ int rpe_sift_run(rpe_handle *h, const uint8_t *d_a, const uint8_t *d_b, int na, 
 int rpe_sift_fetch(rpe_handle *h, int n_images, float *fin_host, int *counts);
 int rpe_sift_fetch_gauss(rpe_handle *h, int index, float *out);
 long long rpe_sift_gauss_floats(rpe_handle *h);
-void rpe_launch_ransac(rpe_handle *h, int B, bool want_mask);
-void rpe_launch_pose(rpe_handle *h, int B, bool set_status);
-void rpe_launch_structure(rpe_handle *h, int B);
-void rpe_launch_refine(rpe_handle *h, int B, int max_iters, bool from_batch);
-void rpe_launch_camera_normalise(rpe_handle *h, int B);
+void rpe_launch_ransac(rpe_handle *h, const RpeRun &r, bool want_mask);
+void rpe_launch_pose(rpe_handle *h, const RpeRun &r, bool set_status);
+void rpe_launch_structure(rpe_handle *h, const RpeRun &r);
+void rpe_launch_refine(rpe_handle *h, const RpeRun &r, int max_iters, bool from_batch);
+void rpe_launch_camera_normalise(rpe_handle *h, const RpeRun &r);
 void rpe_launch_undistort(rpe_handle *h, const float2 *d_pts, int n, const rpe_camera *d_cam, double2 *d_out);
 
 // per-stage hipEvents on the handle's stream (rpe_set_profiling / rpe_get_stage_ms)

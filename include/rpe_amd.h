@@ -349,6 +349,48 @@ enum {
 int rpe_refine_poses(rpe_handle *h, int B, int max_iters, double *R, double *t, int32_t *inliers,
                      int32_t *info, double *rms);
 
+/* ------------------------------------------------------------ scale links */
+/* keypoint indices of the matches of the last batch / stream / pair list: qidx into image 1's keypoints, tidx into
+ * image 2's, [B * max_matches], -1 past n_matches[p].  Validity rules of rpe_fetch_matched_points.  Either output may be
+ * NULL.  (A pair list's keypoints are those of its two slots; rpe_fetch_matched_points returns their coordinates.) */
+int rpe_fetch_match_indices(rpe_handle *h, int B, int32_t *qidx, int32_t *tidx);
+
+/* Relative scale of two pairs of the last run that share a frame (NOT in the reference, which never relates two of its
+ * estimates): every pose comes back with |t| = 1, so the poses of pairs (i, i+1) and (i+1, i+2) of a stream, or of the
+ * pairs of a window, cannot be composed.  A keypoint of the shared frame that both pairs matched and triangulated lies
+ * at distance d_a from the frame's camera centre on pair a's scale and d_b on pair b's; d_a / d_b is the baseline of
+ * pair b in units of the baseline of pair a.
+ * L links over the last run.  Link l joins pairs pair_a[l] != pair_b[l] of that run at a frame they share:
+ * side[l] bit 0 = the shared frame is image 2 of pair_a (else image 1), bit 1 = the same for pair_b.
+ * stats[3 l .. 3 l + 2] = lower quartile, median, upper quartile of d_a / d_b over the shared keypoints
+ *   = baseline of pair_b in units of the baseline of pair_a;
+ * n_shared[l]; code[l] = RPE_LINK_*.  Any output may be NULL.
+ *  - usable match: match i of a pair is usable when the pair's status is RPE_PAIR_OK, i < n_matches, and both
+ *    ransac_mask[i] and pose_mask[i] (rpe_fetch_structure) are set.  Its key is its keypoint index on the shared frame:
+ *    qidx when that frame is the pair's image 1, tidx when it is image 2.
+ *  - duplicate keys (RPE_MATCH_RATIO lets several matches of a pair name one train keypoint): the usable match with the
+ *    lowest match index wins, in both pairs.
+ *  - shared set: the keys that have a usable match in both pairs.
+ *  - distance: X = the match's triangulated point (camera-1 frame of its pair, |t| = 1).  (x, y, z) = X when the shared
+ *    frame is the pair's image 1, R X + t when it is image 2, each row summed as ((r0*X + r1*Y) + r2*Z) + t;
+ *    d = sqrt((x*x + y*y) + z*z); the ratio is d_a / d_b.  f64, no contraction.
+ *  - order statistics: r[0 .. n) = the ratios sorted ascending; the outputs are r[(n-1)/4], r[(n-1)/2], r[(3*(n-1))/4]
+ *    (integer division): elements of the set, never an average.
+ *  - codes: RPE_LINK_PAIR_FAILED when either pair's status is not OK (n_shared = 0, stats zero); RPE_LINK_TOO_FEW when
+ *    n_shared < min_shared (n_shared reported, stats zero); otherwise RPE_LINK_OK.
+ * Validity rules of rpe_fetch_structure (refused after a chunked host batch, a stage call, a put, ...); the structure
+ * kernels are launched when the per-match buffers do not hold their results yet.  Changes none of the run's results:
+ * rpe_fetch_results / rpe_fetch_structure / rpe_refine_poses / rpe_gather_poses return the same bits afterwards.
+ * Bit-deterministic.  Works unchanged after the *_cameras runs: the triangulated points are in normalised coordinates.
+ * Argument checks are host-side; nothing is launched and the handle stays usable after a refusal.  RPE_ERR_INVALID: an
+ * index outside the last run, pair_a[l] == pair_b[l], side outside 0 .. 3, min_shared < 1, L < 0, a frame that is not
+ * shared -- pair list: slot (side bit ? slot2 : slot1) of the two pairs must be equal (refused once the store was
+ * resized); stream: pair_a + (side & 1) == pair_b + (side >> 1) -- and any link over a batch, whose pairs share no
+ * frame.  RPE_ERR_CAPACITY: L > 4 * max_batch. */
+enum { RPE_LINK_OK = 0, RPE_LINK_PAIR_FAILED = 1, RPE_LINK_TOO_FEW = 2 };
+int rpe_scale_links(rpe_handle *h, int L, const int32_t *pair_a, const int32_t *pair_b, const int32_t *side,
+                    int min_shared, double *stats, int32_t *n_shared, int32_t *code);
+
 /* ---------------------------------------------------------- stage entry */
 /* replaces extractor.detectAndCompute(image, None) (pose_estimator.py:108)
  * for n_images images (n_images <= 2*max_batch).  kps[n_images*cap],

@@ -27,6 +27,7 @@ CALIB_KINDS = 16
 STAGE_COUNT = 12
 ORDER_BGR, ORDER_RGB = 0, 1
 REFINE_OK, REFINE_SKIPPED, REFINE_REJECTED = 0, 1, 2   # info[:, 0] of refine_poses (include/rpe_amd.h RPE_REFINE_*)
+LINK_OK, LINK_PAIR_FAILED, LINK_TOO_FEW = 0, 1, 2      # code[] of scale_links (include/rpe_amd.h RPE_LINK_*)
 UNDISTORT_ITERS = 5               # RPE_UNDISTORT_ITERS: fixed-point rounds of the camera path's undistortion
 
 EXPORTS = [
@@ -47,6 +48,7 @@ EXPORTS = [
     "rpe_frames_set_cameras", "rpe_enqueue_pairs_cameras", "rpe_estimate_pairs_cameras",
     "rpe_enqueue_batch_cameras_device", "rpe_estimate_batch_cameras_device", "rpe_estimate_batch_cameras",
     "rpe_undistort_points", "rpe_find_essential_cameras", "rpe_recover_pose_cameras", "rpe_refine_pose_points_cameras",
+    "rpe_fetch_match_indices", "rpe_scale_links",
 ]
 
 
@@ -216,6 +218,8 @@ def load():
     lib.rpe_recover_pose_cameras.restype = C.c_int
     lib.rpe_refine_pose_points_cameras.argtypes = [vp, vp, vp, vp, vp, vp, i32p, C.c_int, vp, vp, C.c_int, vp, vp, i32p, i32p, vp]
     lib.rpe_refine_pose_points_cameras.restype = C.c_int
+    lib.rpe_fetch_match_indices.argtypes = [vp, C.c_int, i32p, i32p]; lib.rpe_fetch_match_indices.restype = C.c_int
+    lib.rpe_scale_links.argtypes = [vp, C.c_int, i32p, i32p, i32p, C.c_int, vp, i32p, i32p]; lib.rpe_scale_links.restype = C.c_int
     _lib = lib
     return lib
 
@@ -411,6 +415,29 @@ class Engine:
         info = np.zeros((B, 4), np.int32); rms = np.zeros((B, 2))
         self._chk(self.lib.rpe_refine_poses(self.h, B, max_iters, _p(R), _p(t), _p(inl), _p(info), _p(rms)))
         return R, t, inl, info, rms
+
+    # ---- scale links (rpe_fetch_match_indices / rpe_scale_links; not in the reference)
+    def fetch_match_indices(self, B):
+        """Keypoint indices of the matches of the last batch / stream / pair list: (qidx i32[B, mm] into image 1's
+        keypoints, tidx i32[B, mm] into image 2's), -1 past each pair's match count."""
+        q = np.zeros((B, self.max_matches), np.int32); t = np.zeros_like(q)
+        self._chk(self.lib.rpe_fetch_match_indices(self.h, B, _p(q), _p(t)))
+        return q, t
+
+    def scale_links(self, pair_a, pair_b, side, min_shared=8):
+        """Relative scale of pairs of the last stream / pair list that share a frame (rpe_scale_links).  Link l joins
+        pairs pair_a[l] and pair_b[l]; side[l] bit 0 / bit 1 = the shared frame is image 2 (else image 1) of pair_a /
+        pair_b.  Returns (stats f64[L, 3], n_shared i32[L], code i32[L]): stats = lower quartile, median, upper quartile
+        of d_a / d_b over the shared keypoints = baseline of pair_b in units of the baseline of pair_a; code = LINK_*
+        (stats are zero unless LINK_OK).  The run's own results are not modified."""
+        a = np.ascontiguousarray(pair_a, np.int32).reshape(-1); b = np.ascontiguousarray(pair_b, np.int32).reshape(-1)
+        s = np.ascontiguousarray(side, np.int32).reshape(-1)
+        if not (a.size == b.size == s.size):
+            raise ValueError(f"scale_links: pair_a, pair_b and side must have one length, got {(a.size, b.size, s.size)}")
+        L = a.size
+        stats = np.zeros((L, 3)); n = np.zeros(L, np.int32); code = np.zeros(L, np.int32)
+        self._chk(self.lib.rpe_scale_links(self.h, L, _p(a), _p(b), _p(s), int(min_shared), _p(stats), _p(n), _p(code)))
+        return stats, n, code
 
     # ---- frame store (rpe_frames_* / rpe_enqueue_pairs; not in the reference)
     def frames_reserve(self, n_slots):

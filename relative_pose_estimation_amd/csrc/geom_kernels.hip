@@ -1611,3 +1611,131 @@ void rpe_launch_refine(rpe_handle *h, const RpeRun &r, int max_iters, bool from_
                h->d_n1, h->d_n2, h->d_mask, h->d_m_n, status, inl, h->d_K, r.cam, Rin, tin,
                h->d_ref_R, h->d_ref_t, h->d_ref_inl, h->d_ref_info, h->d_ref_rms, mm, max_iters);
 }
+
+// ------------------------------------------------------------ scale links
+// rpe_scale_links (NOT in the reference; include/rpe_amd.h states the rules): the baseline of pair b in units of the
+// baseline of pair a, from the keypoints of the frame the two pairs share that both triangulated.  One 256-thread
+// workgroup per link, f64 throughout, everything between the per-match buffers and the three results stays in LDS.
+//   table   one word per keypoint of the shared frame: high half = lowest usable match index of pair a, low half = of
+//           pair b, 0xFFFF = none (max_matches <= 8064).  Pass 1: a's usable matches atomicMin (index << 16 | 0xFFFF):
+//           every low half is still 0xFFFF, so the minimum orders the high halves.  Pass 2: b's usable matches whose key
+//           has an a entry atomicMin (that high half << 16 | index): equal high halves, the minimum orders the low ones.
+//   ratios  pass 3: b's matches that won their key compute d_a / d_b and append it to an LDS array (integer atomicAdd on
+//           the fill count: the order inside the array varies run to run, the set does not)
+//   ranks   bitonic sort of the array, padded with +inf to a power of two; the three results are elements of the sorted
+//           array, so they are bit-deterministic whatever order pass 3 left (ties are equal values)
+// Dynamic LDS (all of the kernel's LDS, base 16-byte aligned): [sort_cap f64 ratios][kcap u32 table][fill count],
+// sort_cap = next power of two >= max_matches.  Defaults (500 matches, 4064 keypoints): 4 + 15.9 KB; uncapped SIFT
+// (8064 matches, 16384 keypoints): 64 + 64 KB, above the 64 KB a kernel gets without the function attribute.
+// The link, the two pairs' status, match counts, R and t come from blockIdx-indexed reads: uniform, scalar loads.
+#define LINK_NONE 0xFFFFu
+
+__device__ __forceinline__ double link_distance(const double *__restrict__ P, const double (&R)[9], const double (&t)[3], bool image2)
+{
+    double x = P[0], y = P[1], z = P[2];
+    if (image2) {
+        const double X = x, Y = y, Z = z;
+        x = ((R[0] * X + R[1] * Y) + R[2] * Z) + t[0];
+        y = ((R[3] * X + R[4] * Y) + R[5] * Z) + t[1];
+        z = ((R[6] * X + R[7] * Y) + R[8] * Z) + t[2];
+    }
+    return sqrt((x * x + y * y) + z * z);
+}
+
+__global__ __launch_bounds__(256) void scale_links_kernel(const RpeLink *__restrict__ links, const int *__restrict__ m_q,
+                                                           const int *__restrict__ m_t, const int *__restrict__ m_n,
+                                                           const int *__restrict__ status, const uint8_t *__restrict__ ransac_mask,
+                                                           const uint8_t *__restrict__ pose_mask, const double *__restrict__ points,
+                                                           const double *__restrict__ Rall, const double *__restrict__ tall,
+                                                           int max_matches, int kcap, int sort_cap, int min_shared,
+                                                           double *__restrict__ stats, int *__restrict__ n_shared, int *__restrict__ code)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_link[];
+    double *s_ratio = (double *)s_link;
+    unsigned *s_tab = (unsigned *)(s_link + sizeof(double) * (size_t)sort_cap);
+    int *s_fill = (int *)(s_tab + kcap);
+    const int link = blockIdx.x, tid = threadIdx.x;
+    const RpeLink lk = links[link];
+    if (status[lk.a] != RPE_PAIR_OK || status[lk.b] != RPE_PAIR_OK) {
+        if (tid < 3) stats[link * 3 + tid] = 0.;
+        if (tid == 0) { n_shared[link] = 0; code[link] = RPE_LINK_PAIR_FAILED; }
+        return;
+    }
+    const bool a2 = (lk.side & 1) != 0, b2 = (lk.side & 2) != 0;
+    const int na = min(m_n[lk.a], max_matches), nb = min(m_n[lk.b], max_matches);
+    const long long oa = (long long)lk.a * max_matches, ob = (long long)lk.b * max_matches;
+    const int *key_a = (a2 ? m_t : m_q) + oa, *key_b = (b2 ? m_t : m_q) + ob;
+    for (int k = tid; k < kcap; k += 256) s_tab[k] = 0xFFFFFFFFu;
+    if (tid == 0) *s_fill = 0;
+    __syncthreads();
+    for (int i = tid; i < na; i += 256) {
+        if (!(ransac_mask[oa + i] && pose_mask[oa + i])) continue;
+        const int key = key_a[i];
+        if ((unsigned)key < (unsigned)kcap) atomicMin(&s_tab[key], ((unsigned)i << 16) | LINK_NONE);
+    }
+    __syncthreads();
+    for (int i = tid; i < nb; i += 256) {
+        if (!(ransac_mask[ob + i] && pose_mask[ob + i])) continue;
+        const int key = key_b[i];
+        if ((unsigned)key >= (unsigned)kcap) continue;
+        const unsigned e = s_tab[key];                      // the high half is final since the barrier
+        if ((e >> 16) != LINK_NONE) atomicMin(&s_tab[key], (e & 0xFFFF0000u) | (unsigned)i);
+    }
+    __syncthreads();
+    double Ra[9], ta[3], Rb[9], tb[3];
+#pragma unroll
+    for (int e = 0; e < 9; ++e) { Ra[e] = Rall[lk.a * 9 + e]; Rb[e] = Rall[lk.b * 9 + e]; }
+#pragma unroll
+    for (int e = 0; e < 3; ++e) { ta[e] = tall[lk.a * 3 + e]; tb[e] = tall[lk.b * 3 + e]; }
+    for (int i = tid; i < nb; i += 256) {
+        if (!(ransac_mask[ob + i] && pose_mask[ob + i])) continue;
+        const int key = key_b[i];
+        if ((unsigned)key >= (unsigned)kcap) continue;
+        const unsigned e = s_tab[key];
+        if ((e >> 16) == LINK_NONE || (e & 0xFFFFu) != (unsigned)i) continue;
+        const double da = link_distance(points + (oa + (e >> 16)) * 3, Ra, ta, a2);
+        const double db = link_distance(points + (ob + i) * 3, Rb, tb, b2);
+        s_ratio[atomicAdd(s_fill, 1)] = da / db;             // at most one winner per match of b: fill <= nb <= sort_cap
+    }
+    __syncthreads();
+    const int n = *s_fill;
+    int N = 1;
+    while (N < n) N <<= 1;
+    for (int i = n + tid; i < N; i += 256) s_ratio[i] = __builtin_inf();
+    __syncthreads();
+    for (int k = 2; k <= N; k <<= 1)
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int i = tid; i < N; i += 256) {
+                const int p = i ^ j;
+                if (p > i) {
+                    const double u = s_ratio[i], v = s_ratio[p];
+                    if ((u > v) == ((i & k) == 0)) { s_ratio[i] = v; s_ratio[p] = u; }
+                }
+            }
+            __syncthreads();
+        }
+    const bool ok = n >= min_shared;
+    if (tid < 3) stats[link * 3 + tid] = ok ? s_ratio[((n - 1) * (tid + 1)) / 4] : 0.;
+    if (tid == 0) { n_shared[link] = n; code[link] = ok ? RPE_LINK_OK : RPE_LINK_TOO_FEW; }
+}
+
+// the last run's d_status / d_m_n / d_R / d_t, its match indices and the structure buffers -> d_link_stats / _n / _code of
+// the L links in d_links.  Raises the kernel's dynamic-LDS limit on first use (never inside a graph capture: only
+// rpe_scale_links comes here)
+int rpe_launch_scale_links(rpe_handle *h, int L, int min_shared)
+{
+    const int mm = h->cfg.max_matches, kcap = h->lay.kcap;
+    int sort_cap = 8;
+    while (sort_cap < mm) sort_cap <<= 1;
+    const size_t lds = sizeof(double) * (size_t)sort_cap + sizeof(unsigned) * (size_t)kcap + 16;
+    if (lds > 65536 && !h->link_lds_set) {
+        if (hipFuncSetAttribute((const void *)scale_links_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return RPE_ERR_HIP;
+        h->link_lds_set = true;
+    }
+    hipLaunchKernelGGL(scale_links_kernel, dim3(L), dim3(256), lds, h->stream, (const RpeLink *)h->d_links,
+                       (const int *)h->d_m_q, (const int *)h->d_m_t, (const int *)h->d_m_n, (const int *)h->d_status,
+                       (const uint8_t *)h->d_mask, (const uint8_t *)h->d_pose_mask, (const double *)h->d_points,
+                       (const double *)h->d_R, (const double *)h->d_t, mm, kcap, sort_cap, min_shared,
+                       h->d_link_stats, h->d_link_n, h->d_link_code);
+    return RPE_OK;
+}

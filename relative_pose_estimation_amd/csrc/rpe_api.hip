@@ -588,6 +588,7 @@ static RpeLastRun &last_run_begin(rpe_handle *h, RpeLastRun::Kind kind, const Rp
     l.kind = kind; l.pairs = run.pairs; l.run = run;
     l.tab.clear(); l.ovf.clear();
     l.per_match = kind != RpeLastRun::CHUNKED;      // a chunked batch leaves its last chunk's only
+    l.structure = 0;
     h->ev_first = kind == RpeLastRun::LIST ? RPE_STAGE_MATCH : 0;
     return l;
 }
@@ -597,6 +598,7 @@ static RpeLastRun &last_run_begin(rpe_handle *h, RpeLastRun::Kind kind, const Rp
 static void last_run_end(rpe_handle *h, bool images_too = false)
 {
     h->last.per_match = false;
+    h->last.structure = 0;
     if (images_too) { h->last.kind = RpeLastRun::NONE; h->last.pairs = 0; }
 }
 
@@ -938,10 +940,78 @@ extern "C" int rpe_fetch_structure(rpe_handle *h, int B, uint8_t *ransac_mask, u
     DM_ONCE(h, h->d_points, cap * 3);
     rpe_launch_structure(h, last_run_first(h, B));
     HIPCHK(h, hipGetLastError());
+    h->last.structure = std::max(h->last.structure, B);
     if (ransac_mask) HIPCHK(h, hipMemcpyAsync(ransac_mask, h->d_mask, n, hipMemcpyDeviceToHost, h->stream));
     if (pose_mask) HIPCHK(h, hipMemcpyAsync(pose_mask, h->d_pose_mask, n, hipMemcpyDeviceToHost, h->stream));
     if (points) HIPCHK(h, hipMemcpyAsync(points, h->d_points, n * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
+    return RPE_OK;
+}
+
+extern "C" int rpe_fetch_match_indices(rpe_handle *h, int B, int32_t *qidx, int32_t *tidx)
+{
+    if (!h || B < 1 || B > h->cfg.max_batch) return RPE_ERR_INVALID;
+    int rc = last_run_check(h, "rpe_fetch_match_indices", 0, "the last host batch ran in chunks: match indices are kept for device-resident batches (rpe_estimate_batch_device) only", false);
+    if (rc) return rc;
+    const size_t mm = (size_t)h->cfg.max_matches, n = sizeof(int) * (size_t)B * mm;
+    std::vector<int> cnt((size_t)B);
+    HIPCHK(h, hipMemcpyAsync(cnt.data(), h->d_m_n, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, h->stream));
+    if (qidx) HIPCHK(h, hipMemcpyAsync(qidx, h->d_m_q, n, hipMemcpyDeviceToHost, h->stream));
+    if (tidx) HIPCHK(h, hipMemcpyAsync(tidx, h->d_m_t, n, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    for (int p = 0; p < B; ++p)
+        for (size_t i = (size_t)std::min(std::max(cnt[(size_t)p], 0), (int)mm); i < mm; ++i) {
+            if (qidx) qidx[(size_t)p * mm + i] = -1;
+            if (tidx) tidx[(size_t)p * mm + i] = -1;
+        }
+    return RPE_OK;
+}
+
+// rpe_scale_links: every check on the host first (the kept pair table of a list, the rule of a stream), then the structure
+// kernels when the per-match buffers do not hold their results for the whole run, the link table, one kernel, one fetch
+extern "C" int rpe_scale_links(rpe_handle *h, int L, const int32_t *pair_a, const int32_t *pair_b, const int32_t *side,
+                               int min_shared, double *stats, int32_t *n_shared, int32_t *code)
+{
+    if (!h) return RPE_ERR_INVALID;
+    if (L < 0 || min_shared < 1 || (L > 0 && (!pair_a || !pair_b || !side))) { h->err = "rpe_scale_links: L < 0, min_shared < 1 or a null link array"; return RPE_ERR_INVALID; }
+    int rc = last_run_check(h, "rpe_scale_links", 0, "rpe_scale_links: the last host batch ran in chunks: per-match results are kept for unchunked and device-resident batches only", true);
+    if (rc) return rc;
+    RpeLastRun &l = h->last;
+    const bool list = l.kind == RpeLastRun::LIST;
+    if (!list && l.run.feat.img2_base != 1) { h->err = "rpe_scale_links: the pairs of a batch share no frame (links join the pairs of a stream or of a pair list)"; return RPE_ERR_INVALID; }
+    if (list && l.tab.size() < (size_t)2 * l.pairs) { h->err = "rpe_scale_links: the frame store was resized since the pair list"; return RPE_ERR_INVALID; }
+    if (L > 4 * h->cfg.max_batch) { h->err = "rpe_scale_links: more than 4*max_batch links in one call"; return RPE_ERR_CAPACITY; }
+    std::vector<RpeLink> tbl((size_t)L);
+    for (int i = 0; i < L; ++i) {
+        const int a = pair_a[i], b = pair_b[i], s = side[i];
+        const char *bad = nullptr;
+        if (a < 0 || a >= l.pairs || b < 0 || b >= l.pairs) bad = "rpe_scale_links: pair index outside the last run";
+        else if (a == b) bad = "rpe_scale_links: a link joins two different pairs";
+        else if (s < 0 || s > 3) bad = "rpe_scale_links: side must be 0 ... 3";
+        else if (list ? l.tab[(size_t)2 * a + (s & 1)] != l.tab[(size_t)2 * b + (s >> 1)] : a + (s & 1) != b + (s >> 1))
+            bad = "rpe_scale_links: the two pairs do not share the frame the link names";
+        if (bad) { h->err = bad; return RPE_ERR_INVALID; }
+        tbl[(size_t)i] = {a, b, s, 0};
+    }
+    if (L == 0) return RPE_OK;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const size_t cap = (size_t)h->cfg.max_batch * h->cfg.max_matches, lcap = (size_t)4 * h->cfg.max_batch;
+    DM_ONCE(h, h->d_pose_mask, cap);
+    DM_ONCE(h, h->d_points, cap * 3);
+    DM_ONCE(h, h->d_links, lcap); DM_ONCE(h, h->d_link_stats, lcap * 3);
+    DM_ONCE(h, h->d_link_n, lcap); DM_ONCE(h, h->d_link_code, lcap);
+    if (l.structure < l.pairs) {
+        rpe_launch_structure(h, l.run);
+        HIPCHK(h, hipGetLastError());
+        l.structure = l.pairs;
+    }
+    HIPCHK(h, hipMemcpyAsync(h->d_links, tbl.data(), sizeof(RpeLink) * (size_t)L, hipMemcpyHostToDevice, h->stream));
+    if ((rc = rpe_launch_scale_links(h, L, min_shared)) != RPE_OK) { h->err = "rpe_scale_links: could not size the kernel's LDS"; return rc; }
+    HIPCHK(h, hipGetLastError());
+    if (stats) HIPCHK(h, hipMemcpyAsync(stats, h->d_link_stats, sizeof(double) * 3 * (size_t)L, hipMemcpyDeviceToHost, h->stream));
+    if (n_shared) HIPCHK(h, hipMemcpyAsync(n_shared, h->d_link_n, sizeof(int) * (size_t)L, hipMemcpyDeviceToHost, h->stream));
+    if (code) HIPCHK(h, hipMemcpyAsync(code, h->d_link_code, sizeof(int) * (size_t)L, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));       // also: the link table has left tbl
     return RPE_OK;
 }
 

@@ -222,7 +222,11 @@ struct RpeLastRun {
     std::vector<int> tab;             // LIST: its (slot1, slot2) entries; emptied when the store is resized
     std::vector<uint32_t> ovf;        // CHUNKED: capacity flags per pair (OR of the pair's two images), collected across the chunks
     bool per_match = false;           // d_pts*, d_n*, d_rstate, d_mask, d_R / d_t still hold the run's per-match data
+    int structure = 0;                // pairs [0, structure) of the run have d_mask (status form), d_pose_mask and d_points filled
 };
+
+// One rpe_scale_links link on the device: pairs a and b of the last run, side bit 0 / 1 = the shared frame is image 2 of a / of b
+struct RpeLink { int a, b, side, pad; };
 
 struct rpe_handle {
     rpe_config cfg;
@@ -294,6 +298,11 @@ struct rpe_handle {
     // per pair; start pose of the stage form
     double *d_ref_R = nullptr, *d_ref_t = nullptr, *d_ref_rms = nullptr, *d_ref_R0 = nullptr, *d_ref_t0 = nullptr;
     int *d_ref_inl = nullptr, *d_ref_info = nullptr;
+    // rpe_scale_links only (created on first use): link table and outputs, 4*max_batch links
+    RpeLink *d_links = nullptr;
+    double *d_link_stats = nullptr;       // [link][3] lower quartile, median, upper quartile
+    int *d_link_n = nullptr, *d_link_code = nullptr;
+    bool link_lds_set = false;            // the kernel's dynamic-LDS limit has been raised for this handle's layout
     // results
     double *d_R = nullptr, *d_t = nullptr, *d_E = nullptr;
     int *d_inliers = nullptr, *d_status = nullptr;
@@ -368,6 +377,7 @@ void rpe_launch_ransac(rpe_handle *h, const RpeRun &r, bool want_mask);
 void rpe_launch_pose(rpe_handle *h, const RpeRun &r, bool set_status);
 void rpe_launch_structure(rpe_handle *h, const RpeRun &r);
 void rpe_launch_refine(rpe_handle *h, const RpeRun &r, int max_iters, bool from_batch);
+int rpe_launch_scale_links(rpe_handle *h, int L, int min_shared);
 void rpe_launch_camera_normalise(rpe_handle *h, const RpeRun &r);
 void rpe_launch_undistort(rpe_handle *h, const float2 *d_pts, int n, const rpe_camera *d_cam, double2 *d_out);
 

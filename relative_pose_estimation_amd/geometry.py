@@ -66,3 +66,43 @@ def bgr_to_gray(rgb):
     (image_loader.py:23-28 path): (B*3735 + G*19235 + R*9798 + 16384) >> 15."""
     a = np.asarray(rgb).astype(np.int64)
     return ((a[..., 2] * 3735 + a[..., 1] * 19235 + a[..., 0] * 9798 + 16384) >> 15).astype(np.uint8)
+
+
+# ---- trajectories from relative poses and scale links (not in the reference) -------------
+def chain_trajectory(R_rel, t_rel, status, ratio, code):
+    """Absolute poses of F = P + 1 frames from the P relative poses of consecutive pairs and the P - 1 scale links
+    between them (PoseEstimator.estimate_trajectory; pure host code).  Convention X_{i+1} = R_rel[i] X_i + t_rel[i],
+    |t_rel[i]| = 1; link i joins pair i and pair i + 1 and ratio[i] is its median (_capi.Engine.scale_links: baseline of
+    pair i + 1 in units of the baseline of pair i), code[i] its LINK_* code; status[i] is the pair's PAIR_* code.
+
+    baseline[0] = 1, baseline[i + 1] = baseline[i] * ratio[i]; R_{i+1} = R_rel[i] R_i and
+    T_{i+1} = R_rel[i] T_i + baseline[i] t_rel[i], frame 0 at the origin.  Returns (R_abs[F, 3, 3], T_abs[F, 3],
+    centers[F, 3] = -R^T T, baseline[P], segment[P]).
+
+    ONLY INSIDE A SEGMENT DO DISTANCES SHARE A SCALE.  segment[i] numbers the runs of pairs whose links are all LINK_OK:
+    a new segment starts at a failed pair (status != 0), at the pair after a failed pair, and at a pair whose link to its
+    predecessor is not LINK_OK.  Across such a boundary the chain continues with ratio 1, so the arrays stay usable, but
+    the baselines on the two sides are unrelated; a failed pair contributes the identity rotation and a zero step."""
+    R_rel = np.asarray(R_rel, np.float64).reshape(-1, 3, 3)
+    P = R_rel.shape[0]
+    t_rel = np.asarray(t_rel, np.float64).reshape(P, 3)
+    status = np.asarray(status).reshape(P)
+    ratio = np.asarray(ratio, np.float64).reshape(-1)
+    code = np.asarray(code).reshape(-1)
+    if P < 1 or ratio.size != P - 1 or code.size != P - 1:
+        raise ValueError(f"chain_trajectory: P >= 1 pairs need P - 1 links, got {P} pairs, {ratio.size} ratios, {code.size} codes")
+    ok = status == 0
+    baseline = np.ones(P)
+    segment = np.zeros(P, np.int32)
+    for i in range(1, P):
+        joined = bool(ok[i] and ok[i - 1] and code[i - 1] == 0)          # 0 = LINK_OK
+        baseline[i] = baseline[i - 1] * (ratio[i - 1] if joined else 1.0)
+        segment[i] = segment[i - 1] + (0 if joined else 1)
+    R_abs = np.zeros((P + 1, 3, 3)); T_abs = np.zeros((P + 1, 3))
+    R_abs[0] = np.eye(3)
+    for i in range(P):
+        Ri, ti = (R_rel[i], t_rel[i]) if ok[i] else (np.eye(3), np.zeros(3))
+        R_abs[i + 1] = Ri @ R_abs[i]
+        T_abs[i + 1] = Ri @ T_abs[i] + baseline[i] * ti
+    centers = -np.einsum("fji,fj->fi", R_abs, T_abs)
+    return R_abs, T_abs, centers, baseline, segment

@@ -19,7 +19,7 @@ library's LSD restatement (host code, as in the reference).
 """
 import numpy as np
 
-from . import _capi, vp_refinement
+from . import _capi, geometry, vp_refinement
 
 
 def plan_pairs(n_frames, n_pairs, max_batch):
@@ -346,6 +346,35 @@ class PoseEstimator:
         eng, B = self._last_engine, self._last_pairs
         R, t, inl, info, rms = eng.refine_poses(B, max_iters)
         return R, t, inl, eng.fetch_results(B)[4], info, rms
+
+    def last_scale_links(self, links, min_shared=8):
+        """Relative scale of pairs of the last estimate_sequence / estimate_pairs / FrameStore.estimate call that share
+        a frame (not in the reference; _capi.Engine.scale_links).  links: integer array [L, 3] of (pair_a, pair_b, side)
+        over the pairs of that call (of its LAST chunk when the call ran in several), side bit 0 / bit 1 = the shared
+        frame is image 2 (else image 1) of pair_a / pair_b: consecutive pairs (i, i + 1) of a sequence are (i, i + 1, 1).
+        Returns (stats[L, 3], n_shared[L], code[L]): lower quartile, median and upper quartile of the baseline of pair_b
+        in units of the baseline of pair_a, the number of shared keypoints, and the _capi.LINK_* code.  Raises RpeError
+        after estimate_batch (its pairs share no frame) and when a link names a frame the two pairs do not share."""
+        a = np.asarray(links)
+        if a.ndim != 2 or a.shape[1] != 3 or a.dtype.kind not in "iu":
+            raise ValueError(f"links: expected an integer array of shape [L, 3] (pair_a, pair_b, side), got {a.dtype} {a.shape}")
+        return self._last_engine.scale_links(a[:, 0], a[:, 1], a[:, 2], min_shared)
+
+    def estimate_trajectory(self, frames, min_shared=8):
+        """estimate_sequence plus what relates its poses (not in the reference): the scale link of every two consecutive
+        pairs and the chained trajectory (geometry.chain_trajectory).  Returns a dict: 'R', 't', 'inliers', 'status' of
+        the F - 1 pairs; 'ratio_stats' [F-2, 3], 'n_shared' [F-2], 'link_code' [F-2] of the links; 'R_abs' [F, 3, 3],
+        'T_abs' [F, 3], 'centers' [F, 3], 'baseline' [F-1], 'segment' [F-1].  Distances share a scale only inside a
+        segment; the unit is the baseline of the segment's first pair."""
+        if self._camera is not None:
+            raise ValueError("estimate_trajectory: the camera path has no stream form; use estimate_pairs and last_scale_links")
+        R, t, inl, st = self.estimate_sequence(frames)
+        P = len(st)
+        i = np.arange(P - 1, dtype=np.int32)
+        stats, n_shared, code = self._last_engine.scale_links(i, i + 1, np.ones(P - 1, np.int32), min_shared)
+        R_abs, T_abs, centers, baseline, segment = geometry.chain_trajectory(R, t, st, stats[:, 1], code)
+        return {'R': R, 't': t, 'inliers': inl, 'status': st, 'ratio_stats': stats, 'n_shared': n_shared, 'link_code': code,
+                'R_abs': R_abs, 'T_abs': T_abs, 'centers': centers, 'baseline': baseline, 'segment': segment}
 
     def estimate_sequence(self, frames):
         """Relative poses of consecutive frames (frame i -> i+1): the pair loop of the reference's

@@ -147,17 +147,11 @@ def _stream_job(args):
     return _finish(_render(K, R, t, W, H, int(seed), focal, dist), rng)
 
 
-def make_stream(n_frames, K, W=640, H=480, seed=5_000_011, max_angle_deg=2.0, step=0.12, workers=1, frame_range=None, dist=None):
-    """One camera moving through ONE scene (KITTI-like consecutive-frame stream, BASELINE config 5
-    stand-in): frames [n,H,W], and the ground-truth relative pose of every consecutive pair
-    (X_{i+1} = R_rel X_i + t_rel, |t_rel| = 1).  The camera random-walks with small rotations and
-    a bounded position so that the scene stays in view.
-    frame_range=(lo, hi): render only frames [lo, hi) of the n_frames-long sequence (the trajectory is always
-    computed whole, so every shard of a sharded stream sees the same sequence); poses returned are those of the
-    pairs inside the range.  dist as in make_pair."""
+def stream_poses(n_frames, seed=5_000_011, max_angle_deg=2.0, step=0.12):
+    """Absolute poses of make_stream's random walk for the same arguments: (Rs [n, 3, 3], ts [n, 3]) with
+    X_i = Rs[i] X_scene + ts[i]; frame 0 is the scene frame.  The camera centre of frame i is -Rs[i].T @ ts[i] and
+    every consecutive pair is `step` apart, so the sequence has ground-truth baselines."""
     rng = np.random.default_rng(int(seed))
-    K = np.asarray(K, np.float64)
-    focal = 0.5 * (K[0, 0] + K[1, 1])
     Rs, ts = [np.eye(3)], [np.zeros(3)]
     for i in range(1, n_frames):
         Rr = _rot(*rng.uniform(-max_angle_deg, max_angle_deg, 3))
@@ -167,6 +161,20 @@ def make_stream(n_frames, K, W=640, H=480, seed=5_000_011, max_angle_deg=2.0, st
             d = -Rs[-1] @ (c_prev / np.linalg.norm(c_prev))
         tr = d * step
         Rs.append(Rr @ Rs[-1]); ts.append(Rr @ ts[-1] + tr)
+    return np.stack(Rs), np.stack(ts)
+
+
+def make_stream(n_frames, K, W=640, H=480, seed=5_000_011, max_angle_deg=2.0, step=0.12, workers=1, frame_range=None, dist=None):
+    """One camera moving through ONE scene (KITTI-like consecutive-frame stream, BASELINE config 5
+    stand-in): frames [n,H,W], and the ground-truth relative pose of every consecutive pair
+    (X_{i+1} = R_rel X_i + t_rel, |t_rel| = 1).  The camera random-walks with small rotations and
+    a bounded position so that the scene stays in view.
+    frame_range=(lo, hi): render only frames [lo, hi) of the n_frames-long sequence (the trajectory is always
+    computed whole, so every shard of a sharded stream sees the same sequence); poses returned are those of the
+    pairs inside the range.  dist as in make_pair."""
+    K = np.asarray(K, np.float64)
+    focal = 0.5 * (K[0, 0] + K[1, 1])
+    Rs, ts = stream_poses(n_frames, seed=seed, max_angle_deg=max_angle_deg, step=step)
     lo, hi = (0, n_frames) if frame_range is None else (int(frame_range[0]), int(frame_range[1]))
     jobs = [(K, Rs[i], ts[i], W, H, seed, focal, seed * 31 + i, dist) for i in range(lo, hi)]
     if workers > 1:

@@ -130,16 +130,7 @@ static inline uint32_t rng_next(uint64_t &st)
     return (uint32_t)st;
 }
 
-// Every device buffer of the handle (the frame store keeps its own set, caller buffers are in user_allocs) comes from
-// here: rpe_destroy frees what this recorded.  DM_ONCE: a buffer created on first use.
-template <typename T>
-static int dmalloc(rpe_handle *h, T **p, size_t n)
-{
-    HIPCHK(h, hipMalloc((void **)p, n * sizeof(T)));
-    h->dev_allocs.push_back(*p);
-    return RPE_OK;
-}
-#define DM(h, p, n) do { int r_ = dmalloc(h, &(p), (size_t)(n)); if (r_) return r_; } while (0)
+// a buffer created on first use
 #define DM_ONCE(h, p, n) do { if (!(p)) DM(h, p, n); } while (0)
 
 static int build_tables(rpe_handle *h)

@@ -339,6 +339,18 @@ struct rpe_handle {
     std::vector<void *> user_allocs;            // rpe_device_malloc: the caller's buffers
 };
 
+// Every device buffer of the handle (the frame store keeps its own set, caller buffers are in user_allocs) comes from
+// here: rpe_destroy frees what this recorded, and nothing else frees it.
+template <typename T>
+static int dmalloc(rpe_handle *h, T **p, size_t n)
+{
+    const hipError_t e = hipMalloc((void **)p, n * sizeof(T));
+    if (e != hipSuccess) { *p = nullptr; h->err = std::string("hipMalloc failed: ") + hipGetErrorString(e); return RPE_ERR_HIP; }
+    h->dev_allocs.push_back(*p);
+    return RPE_OK;
+}
+#define DM(h, p, n) do { int r_ = dmalloc(h, &(p), (size_t)(n)); if (r_) return r_; } while (0)
+
 // The runs.  `cam` defaults to the shared K; a camera source must address its records as the run addresses its images.
 static inline RpeRun rpe_run_rule(const rpe_handle *h, int pairs, int img2_base, RpeCamSrc cam)
 {

@@ -5,11 +5,13 @@
 // sift.simd.hpp as restated in oracle/sift_oracle.c; every f32 operation keeps the oracle's
 // order (contraction off, deterministic exp/sincos, fixed partial-sum trees), so results
 // compare bit for bit.  Kernel groups (all images of the batch per launch):
-//   upsample  : u8 -> f32, 2x INTER_LINEAR in exact integer arithmetic (weights 1/4, 3/4), 4 x 2 outputs per lane
 //   blur      : fused separable Gaussian per 64 x 32 tile (window + row-pass plane in LDS, packed-f32 taps read as
-//               operand pairs by two-offset LDS reads, 16-byte stores), reflect-101; an unfused row/column pair
-//               remains as the fallback for other tap counts
-//   halve     : INTER_NEAREST octave decimation
+//               operand pairs by two-offset LDS reads, 16-byte stores), reflect-101; one instantiation per radius of
+//               the pyramid (5 5 6 8 10 13: the parameters are fixed, rpe_sift_create checks them)
+//   (upsample): never stored: the first blur forms the 2x INTER_LINEAR u8 -> f32 image (exact integer arithmetic,
+//               weights 1/4, 3/4) while it loads its window
+//   (halve)   : no pass of its own: the blur that makes level 3 of an octave also writes it at even x, even y
+//               (INTER_NEAREST) as level 0 of the next octave
 //   (DoG)     : never stored: layer l = G[l+1] - G[l] is formed where it is consumed (extrema scan, adjust)
 //   extrema   : tiled 26-neighbour test (rolling LDS layers with halo columns, 3x3x3 max/min from LDS reads) -> 1-bit hit
 //               mask + one counter per (octave, layer, row) band; parallel band scan; wave-per-row emit = raster-ordered seeds
@@ -40,20 +42,20 @@
 #define S_WAVE_SYNC() do { __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront"); __builtin_amdgcn_wave_barrier(); __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront"); } while (0)
 #define S_NOL 3
 #define S_NG 6
-#define S_ND 5
 #define S_BORDER 5
 #define S_BINS 36
 
 __constant__ float c_skern[6][32];     // [0] initial blur, [1..5] incremental octave blurs
 __constant__ int c_sks[6];
+static const int kSiftRadius[S_NG] = {5, 5, 6, 8, 10, 13};   // ks >> 1 of the six kernels: fixed by sigma 1.6, 3 layers, input blur 0.5
 
 struct SiftXTile { int o, x0, y0; };     // SX_TW x SX_TH tile of the extrema scan
 
 struct SiftDev {                        // passed by value to kernels
     int noct;
     int w[12], h[12];
-    long long goff[12], doff[12];       // float offsets inside the per-image gaussian / DoG buffers
-    long long gstride, dstride, tstride; // floats per image
+    long long goff[12];                 // float offsets of the octaves inside the per-image gaussian buffer
+    long long gstride;                  // floats per image
     int seed_cap, raw_cap, kcap, nfeatures, nbands;
     // extrema scan: a band = one row of one (octave, layer 1..3): index band0[o] + (l-1)*(h-10) + (r-5), i.e. the
     // oracle's enumeration order (octave, layer, row); hits live in a 1-bit-per-pixel mask [3][h][wpr] of 64-bit words
@@ -61,103 +63,30 @@ struct SiftDev {                        // passed by value to kernels
     long long bmoff[12], bmstride;
 };
 
-struct RpeSiftState {
+struct RpeSiftState {                   // the device buffers are in the handle's allocation record (DM): rpe_destroy frees them
     SiftDev dv;
-    float *d_gauss = nullptr, *d_dog = nullptr, *d_tmp = nullptr;
+    float *d_gauss = nullptr;
     SiftXTile *d_xtiles = nullptr; int n_xtiles = 0;
     unsigned long long *d_xmask = nullptr;                 // [img][bmstride]
     int *d_band_cnt = nullptr, *d_band_off = nullptr;     // [img][nbands]
     unsigned *d_seeds = nullptr; int *d_nseeds = nullptr; // [img][seed_cap], [img]
     float *d_raw = nullptr;                                // [img][raw_cap][6]: x y size angle response octave(bits)
-    int *d_nraw = nullptr, *d_overflow = nullptr, *d_ncand = nullptr;
+    int *d_nraw = nullptr, *d_ncand = nullptr;
     float *d_surv = nullptr; int *d_nsurv = nullptr;        // [img][seed_cap][SURV_W] refined seeds, [img]
     unsigned *d_sel = nullptr; int *d_nsel = nullptr;       // [img][seed_cap] survivors that get an orientation (sift_select_kernel), [img][4] = {count, cut, redo, -}
     int sel_k_override = 0;
     unsigned long long *d_k0 = nullptr, *d_k1 = nullptr; unsigned *d_sidx = nullptr; // sort keys [img][raw_pad]
     int raw_pad = 0;
-    int group = 0, group_octaves = 1;                     // image-major schedule (rpe_sift_run): images per group, octaves inside it
-    bool fused_all = false;                                // every blur radius has a fused instantiation
     bool march = false;                                    // levels 1-3 / 4-5 of the large octaves by sift_march_kernel
-    int xtile_oct_end[12] = {0};                           // tiles of octaves 0 .. o end here in d_xtiles
-    int ks[6] = {0, 0, 0, 0, 0, 0};                      // tap counts of c_skern
     float *d_fin = nullptr;                                // [img][kcap][6] un-halved keypoints in sorted order
 };
 
 // ------------------------------------------------------------------ image ops
-// 2x INTER_LINEAR of the u8 image into f32 (oracle: sift_oracle.c upsample; cv2.resize semantics: source position
-// (x + 0.5) / 2 - 0.5, clamped at the borders).  The interpolation weights are 0.25 / 0.75 and the pixels are integers
-// below 256, so every product and sum of a*(1-f) + b*f is exact in f32 and any evaluation order gives the oracle's bits:
-// the kernel works in integers, out = (wy0 (wx0 s00 + wx1 s01) + wy1 (wx0 s10 + wx1 s11)) / 16 with weights 1 and 3.
-// A lane produces the 4 x 2 outputs x = 4t .. 4t+3, y = 2r+1, 2r+2 from source rows r, r+1 and columns 2t-1 .. 2t+2
-// (clamping the indices reproduces the border rule: a clamped pair has two equal values, and (1 v + 3 v) / 4 = v).
-__global__ __launch_bounds__(256) void sift_upsample_kernel(const uint8_t *__restrict__ img, int W, int H, size_t img_stride,
-                                                             float *__restrict__ dst, long long dstride)
-{
-    const int bw = 2 * W, bh = 2 * H;
-    const int t = blockIdx.x * 256 + threadIdx.x, r = (int)blockIdx.y - 1;       // r = -1 .. H-1
-    if (4 * t >= bw) return;
-    const uint8_t *s = img + (size_t)blockIdx.z * img_stride;
-    const uint8_t *ra = s + (size_t)max(r, 0) * W, *rb = s + (size_t)min(r + 1, H - 1) * W;
-    const int c0 = max(2 * t - 1, 0), c1 = min(2 * t, W - 1), c2 = min(2 * t + 1, W - 1), c3 = min(2 * t + 2, W - 1);
-    const unsigned a0 = ra[c0], a1 = ra[c1], a2 = ra[c2], a3 = ra[c3];
-    const unsigned b0 = rb[c0], b1 = rb[c1], b2 = rb[c2], b3 = rb[c3];
-    // horizontal: x = 4t: (c0, c1) weights (1, 3); 4t+1: (c1, c2) (3, 1); 4t+2: (c1, c2) (1, 3); 4t+3: (c2, c3) (3, 1)
-    const unsigned ha[4] = {a0 + 3 * a1, 3 * a1 + a2, a1 + 3 * a2, 3 * a2 + a3};
-    const unsigned hb[4] = {b0 + 3 * b1, 3 * b1 + b2, b1 + 3 * b2, 3 * b2 + b3};
-    typedef float f4_t __attribute__((ext_vector_type(4)));
-    f4_t o1, o2;                                                                   // rows 2r+1 (weights 3, 1) and 2r+2 (1, 3)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        o1[j] = (float)(3 * ha[j] + hb[j]) * 0.0625f;
-        o2[j] = (float)(ha[j] + 3 * hb[j]) * 0.0625f;
-    }
-    float *d = dst + (long long)blockIdx.z * dstride + 4 * t;
-    const int y1 = 2 * r + 1, y2 = 2 * r + 2;
-    if (4 * t + 3 < bw) {
-        if (y1 >= 0) *(f4_t *)(d + (size_t)y1 * bw) = o1;
-        if (y2 < bh) *(f4_t *)(d + (size_t)y2 * bw) = o2;
-    } else {
-        for (int j = 0; j < 4 && 4 * t + j < bw; ++j) {
-            if (y1 >= 0) d[(size_t)y1 * bw + j] = o1[j];
-            if (y2 < bh) d[(size_t)y2 * bw + j] = o2[j];
-        }
-    }
-}
-
 __device__ __forceinline__ int s_refl(int p, int n)
 {
     if (n == 1) return 0;
     while (p < 0 || p >= n) { if (p < 0) p = -p; if (p >= n) p = 2 * n - 2 - p; }
     return p;
-}
-
-// row pass: one workgroup = 256 consecutive pixels of one row, taps staged in an LDS segment
-__global__ __launch_bounds__(256) void sift_blur_row_kernel(const float *__restrict__ src, long long sstride, float *__restrict__ dst,
-                                                             long long dstride, int w, int h, int kid)
-{
-    __shared__ float seg[256 + 32];
-    const int ks = c_sks[kid], r = ks >> 1;
-    const int x0 = blockIdx.x * 256, y = blockIdx.y;
-    const float *s = src + (long long)blockIdx.z * sstride + (size_t)y * w;
-    for (int i = threadIdx.x; i < 256 + 2 * r; i += 256) seg[i] = s[s_refl(x0 + i - r, w)];
-    __syncthreads();
-    const int x = x0 + threadIdx.x;
-    if (x >= w) return;
-    float acc = c_skern[kid][0] * seg[threadIdx.x];                      // cv2's RowVec_32f order: first product, then fused taps
-    for (int i = 1; i < ks; ++i) acc = __builtin_fmaf(c_skern[kid][i], seg[threadIdx.x + i], acc);
-    dst[(long long)blockIdx.z * dstride + (size_t)y * w + x] = acc;
-}
-
-__global__ __launch_bounds__(256) void sift_blur_col_kernel(const float *__restrict__ src, long long sstride, float *__restrict__ dst,
-                                                             long long dstride, int w, int h, int kid)
-{
-    const int ks = c_sks[kid], r = ks >> 1;
-    const int x = blockIdx.x * 256 + threadIdx.x, y = blockIdx.y;
-    if (x >= w) return;
-    const float *s = src + (long long)blockIdx.z * sstride;
-    float acc = c_skern[kid][r] * s[(size_t)y * w + x];                  // cv2's SymmColumnVec_32f order: centre, then fused symmetric pairs
-    for (int j = 1; j <= r; ++j) acc = __builtin_fmaf(c_skern[kid][r + j], s[(size_t)s_refl(y + j, h) * w + x] + s[(size_t)s_refl(y - j, h) * w + x], acc);
-    dst[(long long)blockIdx.z * dstride + (size_t)y * w + x] = acc;
 }
 
 // Fused separable Gaussian: one workgroup = 64 x TH output pixels of one pyramid level.
@@ -198,7 +127,11 @@ __device__ __forceinline__ void lds_pairs(f32x2 *P, unsigned addr, std::integer_
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     (asm_pin(P[Ms]), ...);
 }
-// 2x upsampled pixel (x, y) of a u8 image, as sift_upsample_kernel makes it (exact integer form, clamped source indices)
+// Pixel (x, y) of the 2x INTER_LINEAR upsampled u8 image as f32 (oracle: sift_oracle.c upsample; cv2.resize semantics: source
+// position (x + 0.5) / 2 - 0.5, clamped at the borders).  The interpolation weights are 0.25 / 0.75 and the pixels are
+// integers below 256, so every product and sum of a*(1-f) + b*f is exact in f32 and any evaluation order gives the oracle's
+// bits: the code works in integers, out = (wy0 (wx0 s00 + wx1 s01) + wy1 (wx0 s10 + wx1 s11)) / 16 with weights 1 and 3.
+// Clamping the source indices reproduces the border rule: a clamped pair has two equal values, and (1 v + 3 v) / 4 = v.
 __device__ __forceinline__ float sift_up_at(const uint8_t *__restrict__ s8, int W, int H, int x, int y)
 {
     const int t = (x - 1) >> 1, r = (y - 1) >> 1;                       // x odd: columns (t, t+1) weights (3, 1); even: (1, 3)
@@ -539,9 +472,6 @@ __device__ __forceinline__ void march_colfilter(float *lds, int kid, int tid, in
         }
     }
     const int y0 = -G::P + 8 * s - G::L(J);                       // first of the 8 rows produced in this step
-#ifdef MARCH_DIAG_NOSTORE
-    if (acc[0].x == 12345.678f)
-#endif
     if (tid >= HJ && tid < HJ + MARCH_SW && y0 + 7 >= 0 && y0 < h) {
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
@@ -627,35 +557,6 @@ __global__ __launch_bounds__(64 * (MarchGeo<NL, R0, R1, R2>::WBASE(NL))) void si
         iter(t, sB);
         iter(t + 1, sA);                                         // (an iteration past the end finds nothing to do)
     }
-}
-
-// INTER_NEAREST octave decimation: dst(x, y) = src(2x, 2y).  A lane writes 4 neighbouring outputs with one 16-byte store
-// from two 16-byte loads (one dword per lane each way left this copy issue-bound in its many small launches).
-__global__ __launch_bounds__(256) void sift_halve_kernel(const float *__restrict__ src, float *__restrict__ dst, long long stride,
-                                                          int sw, int w, int h)
-{
-    const int x = 4 * (blockIdx.x * 256 + threadIdx.x), y = blockIdx.y;
-    if (x >= w) return;
-    const long long b = (long long)blockIdx.z * stride;
-    const float *sp = src + b + (size_t)(2 * y) * sw + 2 * x;
-    float *dp = dst + b + (size_t)y * w + x;
-    typedef float f4_t __attribute__((ext_vector_type(4), aligned(4)));
-    if (x + 3 < w) {
-        const f4_t a0 = *(const f4_t *)sp, a1 = *(const f4_t *)(sp + 4);
-        f4_t o; o[0] = a0[0]; o[1] = a0[2]; o[2] = a1[0]; o[3] = a1[2];
-        *(f4_t *)dp = o;
-    } else {
-        for (int j = 0; x + j < w; ++j) dp[j] = sp[2 * j];
-    }
-}
-
-// d = a - b (DoG of one level pair; only the unfused fallback path uses it)
-__global__ __launch_bounds__(256) void sift_sub_kernel(const float *__restrict__ a, long long astride, const float *__restrict__ b,
-                                                        long long bstride, float *__restrict__ d, long long dstride, long long n)
-{
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    d[(long long)blockIdx.z * dstride + i] = a[(long long)blockIdx.z * astride + i] - b[(long long)blockIdx.z * bstride + i];
 }
 
 // ------------------------------------------------------------------ extrema
@@ -1604,13 +1505,12 @@ int rpe_sift_create(rpe_handle *h)
     const int bw = 2 * W, bh = 2 * H, mn = bw < bh ? bw : bh;
     dv.noct = s_round_d(log((double)mn) / log(2.) - 2) + 1;
     if (dv.noct > 12) dv.noct = 12;
-    long long go = 0, dof = 0;
+    long long go = 0;
     for (int o = 0; o < dv.noct; ++o) {
         dv.w[o] = o ? dv.w[o - 1] / 2 : bw; dv.h[o] = o ? dv.h[o - 1] / 2 : bh;
         dv.goff[o] = go; go += (long long)S_NG * dv.w[o] * dv.h[o];
-        dv.doff[o] = dof; dof += (long long)S_ND * dv.w[o] * dv.h[o];
     }
-    dv.gstride = go; dv.dstride = dof; dv.tstride = (long long)bw * bh;
+    dv.gstride = go;
     dv.nfeatures = h->cfg.nfeatures;
     dv.kcap = h->lay.kcap;
     // seeds: 1/16 of the base-image pixels (>= 16384); the oracle uses the same bound
@@ -1626,9 +1526,12 @@ int rpe_sift_create(rpe_handle *h)
         ks[i] = sift_gauss_kernel(sqrt(st * st - sp * sp), kern[i]);
         if (ks[i] > 31) { h->err = "SIFT kernel too wide"; return RPE_ERR_INVALID; }
     }
+    // sigma, the layer count and the assumed input blur are constants, so the radii are too: the blur kernels are
+    // instantiated for exactly these (sift_blur, sift_march_kernel) and there is no path for any other
+    for (int i = 0; i < S_NG; ++i)
+        if ((ks[i] >> 1) != kSiftRadius[i]) { h->err = "SIFT blur radii are not 5 5 6 8 10 13"; return RPE_ERR_INVALID; }
     SCHK(hipMemcpyToSymbol(HIP_SYMBOL(c_skern), kern, sizeof(kern)));
     SCHK(hipMemcpyToSymbol(HIP_SYMBOL(c_sks), ks, sizeof(ks)));
-    for (int i = 0; i < 6; ++i) S->ks[i] = ks[i];
     // extrema scan: bands (one per row of every (octave, inner layer)) in the oracle's enumeration order, the hit
     // mask layout and the tile list of the tiled first pass
     std::vector<SiftXTile> xt;
@@ -1637,14 +1540,12 @@ int rpe_sift_create(rpe_handle *h)
         for (int o = 0; o < 12; ++o) { dv.band0[o] = 0; dv.wpr[o] = 0; dv.bmoff[o] = 0; }
         for (int o = 0; o < dv.noct; ++o) {
             dv.band0[o] = nb; dv.wpr[o] = (dv.w[o] + 63) / 64; dv.bmoff[o] = bo;
-            S->xtile_oct_end[o] = (int)xt.size();
             if (dv.w[o] <= 2 * S_BORDER || dv.h[o] <= 2 * S_BORDER) continue;
             nb += S_NOL * (dv.h[o] - 2 * S_BORDER);
             bo += (long long)S_NOL * dv.h[o] * dv.wpr[o];
             for (int y = 0; y < dv.h[o] - S_BORDER; y += SX_TH)
                 for (int x = 0; x < dv.w[o] - S_BORDER; x += SX_TW)
                     if (y + SX_TH > S_BORDER && x + SX_TW > S_BORDER) xt.push_back({o, x, y});
-            S->xtile_oct_end[o] = (int)xt.size();
         }
         dv.nbands = nb > 0 ? nb : 1; dv.bmstride = bo > 0 ? bo : 1;
     }
@@ -1654,95 +1555,62 @@ int rpe_sift_create(rpe_handle *h)
     S->raw_pad = 16384;
     { const int need = dv.nfeatures > 0 ? 2 * dv.nfeatures + 1024 + 2048 : 2 * dv.kcap; while (S->raw_pad < need) S->raw_pad <<= 1; }
     S->n_xtiles = (int)xt.size();
-    SCHK(hipMalloc(&S->d_xtiles, sizeof(SiftXTile) * (xt.size() ? xt.size() : 1)));
+    DM(h, S->d_xtiles, xt.size() ? xt.size() : 1);
     if (!xt.empty()) SCHK(hipMemcpy(S->d_xtiles, xt.data(), sizeof(SiftXTile) * xt.size(), hipMemcpyHostToDevice));
-    SCHK(hipMalloc(&S->d_xmask, sizeof(unsigned long long) * NI * dv.bmstride));
-    SCHK(hipMalloc(&S->d_gauss, sizeof(float) * NI * dv.gstride));
-    {   // scratch of the unfused fallbacks (upsampled image + row-pass image, 66 MB per HD image): only when a tap count has
-        // no fused instantiation, which the reference's SIFT parameters (sigma 1.6, 3 layers: radii 5 5 6 8 10 13) never produce
-        bool need_tmp = (ks[0] >> 1) != 5;
-        for (int i = 0; i < S_NG; ++i) { const int r = ks[i] >> 1; if (r != 5 && r != 6 && r != 8 && r != 10 && r != 13) need_tmp = true; }
-        if (need_tmp) SCHK(hipMalloc(&S->d_tmp, sizeof(float) * NI * dv.tstride * 2));
-        S->fused_all = !need_tmp;
-        S->march = getenv("RPE_SIFT_MARCH") && (ks[1] >> 1) == 5 && (ks[2] >> 1) == 6 && (ks[3] >> 1) == 8 && (ks[4] >> 1) == 10 && (ks[5] >> 1) == 13;
-        if (const char *e = getenv("RPE_SIFT_GROUP")) S->group = atoi(e);
-        if (const char *e = getenv("RPE_SIFT_GROUP_OCTAVES")) S->group_octaves = atoi(e) > 0 ? atoi(e) : 1;
-    }
-    SCHK(hipMalloc(&S->d_band_cnt, sizeof(int) * NI * dv.nbands));
-    SCHK(hipMalloc(&S->d_band_off, sizeof(int) * NI * dv.nbands));
-    SCHK(hipMalloc(&S->d_seeds, sizeof(unsigned) * NI * dv.seed_cap));
-    SCHK(hipMalloc(&S->d_nseeds, sizeof(int) * NI));
-    SCHK(hipMalloc(&S->d_raw, sizeof(float) * NI * dv.raw_cap * 6));
-    SCHK(hipMalloc(&S->d_nraw, sizeof(int) * NI));
-    SCHK(hipMalloc(&S->d_surv, sizeof(float) * NI * dv.seed_cap * SURV_W));
-    SCHK(hipMalloc(&S->d_nsurv, sizeof(int) * NI));
-    SCHK(hipMalloc(&S->d_sel, sizeof(unsigned) * NI * dv.seed_cap));
-    SCHK(hipMalloc(&S->d_nsel, sizeof(int) * NI * 4));
+    DM(h, S->d_xmask, NI * dv.bmstride);
+    DM(h, S->d_gauss, NI * dv.gstride);
+    DM(h, S->d_band_cnt, NI * dv.nbands);
+    DM(h, S->d_band_off, NI * dv.nbands);
+    DM(h, S->d_seeds, NI * dv.seed_cap);
+    DM(h, S->d_nseeds, NI);
+    DM(h, S->d_raw, NI * dv.raw_cap * 6);
+    DM(h, S->d_nraw, NI);
+    DM(h, S->d_surv, NI * dv.seed_cap * SURV_W);
+    DM(h, S->d_nsurv, NI);
+    DM(h, S->d_sel, NI * dv.seed_cap);
+    DM(h, S->d_nsel, NI * 4);
+    S->march = getenv("RPE_SIFT_MARCH") != nullptr;
     if (const char *e = getenv("RPE_SIFT_SEL_K")) S->sel_k_override = atoi(e);      // tests: a small value forces the second round
-    SCHK(hipMalloc(&S->d_overflow, sizeof(int) * NI));
-    SCHK(hipMalloc(&S->d_ncand, sizeof(int) * NI));
-    SCHK(hipMalloc(&S->d_k0, sizeof(unsigned long long) * NI * S->raw_pad));
-    SCHK(hipMalloc(&S->d_k1, sizeof(unsigned long long) * NI * S->raw_pad));
-    SCHK(hipMalloc(&S->d_sidx, sizeof(unsigned) * NI * S->raw_pad));
-    SCHK(hipMalloc(&S->d_fin, sizeof(float) * NI * dv.kcap * 6));
+    DM(h, S->d_ncand, NI);
+    DM(h, S->d_k0, NI * S->raw_pad);
+    DM(h, S->d_k1, NI * S->raw_pad);
+    DM(h, S->d_sidx, NI * S->raw_pad);
+    DM(h, S->d_fin, NI * dv.kcap * 6);
     return RPE_OK;
 }
 
 void rpe_sift_destroy(rpe_handle *h)
 {
-    RpeSiftState *S = h->sift;
-    if (!S) return;
-    void *p[] = {S->d_gauss, S->d_dog, S->d_tmp, S->d_xtiles, S->d_xmask, S->d_band_cnt, S->d_band_off, S->d_seeds, S->d_nseeds, S->d_raw,
-                 S->d_nraw, S->d_overflow, S->d_ncand, S->d_k0, S->d_k1, S->d_sidx, S->d_fin, S->d_surv, S->d_nsurv, S->d_sel, S->d_nsel};
-    for (void *q : p) if (q) hipFree(q);
-    delete S;
+    delete h->sift;      // its device buffers belong to h->dev_allocs
     h->sift = nullptr;
 }
 
+// One fused blur of n_img images: dst = gauss(kid) * src on 64 x 32 tiles (32 rows measured best at every radius).  UPS: the
+// source is the 2x upsampled u8 input (u8a / u8b, na images in the first).  dec (optional, same per-image stride as dst) =
+// dst at even x, even y, w2 x h2.
 template <int R, bool UPS = false>
-static void sift_blur_launch(rpe_handle *h, const float *src, long long sstride, float *dst, long long dstride, float *dog,
-                             long long dogstride, int w, int hh, int kid, int n_img, const uint8_t *u8a = nullptr,
-                             const uint8_t *u8b = nullptr, int na = 0, float *dec = nullptr, int w2 = 0, int h2 = 0)
+static void sift_blur_launch(rpe_handle *h, const float *src, long long sstride, float *dst, long long dstride, int w, int hh, int kid,
+                             int n_img, const uint8_t *u8a = nullptr, const uint8_t *u8b = nullptr, int na = 0, float *dec = nullptr,
+                             int w2 = 0, int h2 = 0)
 {
-    // tile height: 32 rows everywhere measured best while the kernel was issue-limited; RPE_SIFT_TH64=<min radius> (diagnostic)
-    // gives the radii from that one on 64-row tiles (less halo per output row, half the workgroups per CU)
-    static const int th64_from = getenv("RPE_SIFT_TH64") ? atoi(getenv("RPE_SIFT_TH64")) : 1000;
+    constexpr int TH = 32;
     const int tcols = (w + 63) / 64;
-    if (R >= th64_from) {
-        constexpr int TH = 64;
-        const int ntiles = tcols * ((hh + TH - 1) / TH);
-        hipLaunchKernelGGL((sift_blur_fused_kernel<R, TH, UPS>), dim3((ntiles + 7) / 8 * 8, n_img), dim3(256), 0, h->stream, src, sstride, dst, dstride,
-                           w, hh, kid, tcols, ntiles, u8a, u8b, na, w / 2, hh / 2, dec, w2, h2);
-    } else {
-        constexpr int TH = 32;
-        const int ntiles = tcols * ((hh + TH - 1) / TH);
-        hipLaunchKernelGGL((sift_blur_fused_kernel<R, TH, UPS>), dim3((ntiles + 7) / 8 * 8, n_img), dim3(256), 0, h->stream, src, sstride, dst, dstride,
-                           w, hh, kid, tcols, ntiles, u8a, u8b, na, w / 2, hh / 2, dec, w2, h2);
-    }
-    if (dog)      // DoG planes are not stored by the product path (layers are formed where they are consumed); kept for callers that ask
-        hipLaunchKernelGGL(sift_sub_kernel, dim3((unsigned)(((long long)w * hh + 255) / 256), 1, n_img), dim3(256), 0, h->stream,
-                           (const float *)dst, dstride, src, sstride, dog, dogstride, (long long)w * hh);
+    const int ntiles = tcols * ((hh + TH - 1) / TH);
+    hipLaunchKernelGGL((sift_blur_fused_kernel<R, TH, UPS>), dim3((ntiles + 7) / 8 * 8, n_img), dim3(256), 0, h->stream, src, sstride, dst, dstride,
+                       w, hh, kid, tcols, ntiles, u8a, u8b, na, w / 2, hh / 2, dec, w2, h2);
 }
 
-// G[dst] = gauss(kid) * G[src]; dog (optional) = G[dst] - G[src]; dec (optional, same per-image stride as dst) = dst at even
-// x, even y.  Returns true when dec was written (fused instantiations only; the caller runs sift_halve_kernel otherwise).
-static bool sift_blur(rpe_handle *h, const float *src, long long sstride, float *dst, long long dstride, float *dog, long long dogstride,
-                      int w, int hh, int kid, int n_img, float *dec = nullptr, int w2 = 0, int h2 = 0)
+// level kid (1 .. 5) of an octave from level kid - 1: G[dst] = gauss(kid) * G[src]; dec as above
+static void sift_blur(rpe_handle *h, const float *src, long long sstride, float *dst, long long dstride, int w, int hh, int kid, int n_img,
+                      float *dec, int w2, int h2)
 {
-    switch (h->sift->ks[kid] >> 1) {
-    case 5:  sift_blur_launch<5>(h, src, sstride, dst, dstride, dog, dogstride, w, hh, kid, n_img, nullptr, nullptr, 0, dec, w2, h2); return dec != nullptr;
-    case 6:  sift_blur_launch<6>(h, src, sstride, dst, dstride, dog, dogstride, w, hh, kid, n_img, nullptr, nullptr, 0, dec, w2, h2); return dec != nullptr;
-    case 8:  sift_blur_launch<8>(h, src, sstride, dst, dstride, dog, dogstride, w, hh, kid, n_img, nullptr, nullptr, 0, dec, w2, h2); return dec != nullptr;
-    case 10: sift_blur_launch<10>(h, src, sstride, dst, dstride, dog, dogstride, w, hh, kid, n_img, nullptr, nullptr, 0, dec, w2, h2); return dec != nullptr;
-    case 13: sift_blur_launch<13>(h, src, sstride, dst, dstride, dog, dogstride, w, hh, kid, n_img, nullptr, nullptr, 0, dec, w2, h2); return dec != nullptr;
-    default: {      // any other width: unfused two-pass path
-        float *tmp = h->sift->d_tmp + (long long)h->n_img_cap * h->sift->dv.tstride;
-        hipLaunchKernelGGL(sift_blur_row_kernel, dim3((w + 255) / 256, hh, n_img), dim3(256), 0, h->stream, src, sstride, tmp, h->sift->dv.tstride, w, hh, kid);
-        hipLaunchKernelGGL(sift_blur_col_kernel, dim3((w + 255) / 256, hh, n_img), dim3(256), 0, h->stream, (const float *)tmp, h->sift->dv.tstride, dst, dstride, w, hh, kid);
-        if (dog) hipLaunchKernelGGL(sift_sub_kernel, dim3((unsigned)(((long long)w * hh + 255) / 256), 1, n_img), dim3(256), 0, h->stream,
-                                    (const float *)dst, dstride, src, sstride, dog, dogstride, (long long)w * hh);
-    } }
-    return false;
+    switch (kid) {      // radius kSiftRadius[kid]
+    case 1: sift_blur_launch<5>(h, src, sstride, dst, dstride, w, hh, kid, n_img, nullptr, nullptr, 0, dec, w2, h2); break;
+    case 2: sift_blur_launch<6>(h, src, sstride, dst, dstride, w, hh, kid, n_img, nullptr, nullptr, 0, dec, w2, h2); break;
+    case 3: sift_blur_launch<8>(h, src, sstride, dst, dstride, w, hh, kid, n_img, nullptr, nullptr, 0, dec, w2, h2); break;
+    case 4: sift_blur_launch<10>(h, src, sstride, dst, dstride, w, hh, kid, n_img, nullptr, nullptr, 0, dec, w2, h2); break;
+    case 5: sift_blur_launch<13>(h, src, sstride, dst, dstride, w, hh, kid, n_img, nullptr, nullptr, 0, dec, w2, h2); break;
+    }
 }
 
 // d_imgs: n_img tightly packed u8 images already resident (d_a followed by d_b as in the ORB path)
@@ -1751,89 +1619,40 @@ int rpe_sift_run(rpe_handle *h, const uint8_t *d_a, const uint8_t *d_b, int na, 
     RpeSiftState *S = h->sift;
     const SiftDev &dv = S->dv;
     const int W = h->cfg.width, H = h->cfg.height, bw = 2 * W, bh = 2 * H;
-    const size_t img = (size_t)W * H;
     // stage events (rpe_get_stage_ms slots reused for SIFT): PYRAMID = upsample + Gaussian pyramid + DoG, FAST = extrema
     // scan, SELECT = adjustLocalExtrema, HARRIS = orientation histograms, KEYPOINTS = prefilter + sort + retainBest,
     // DESCRIBE = descriptors; NMS / ANGLE / BLUR are empty
     MARK(h, RPE_STAGE_PYRAMID);
     const int n = na + nb;
-    // Pyramid of images [i0, i0 + g), octaves [o0, o1).  Octave 0 starts with the upsample + initial blur in one kernel (the
-    // upsampled image is formed in the blur's window loader; the separate upsample kernel only feeds the unfused fallback
-    // for an unexpected tap count); level 0 of octave o + 1 (= level S_NOL of octave o, halved) is written by the blur that
-    // makes that level.
-    auto pyramid = [&](int i0, int g, int o0, int o1) {
-        float *G = S->d_gauss + (long long)i0 * dv.gstride;
-        bool have_l0 = true;
-        if (o0 == 0) {
-            if ((S->ks[0] >> 1) == 5) {
-                const int na_g = na - i0 < 0 ? 0 : na - i0 > g ? g : na - i0;
-                sift_blur_launch<5, true>(h, nullptr, 0, G + dv.goff[0], dv.gstride, nullptr, 0, bw, bh, 0, g,
-                                          d_a + (size_t)i0 * img, d_b + (size_t)(i0 > na ? i0 - na : 0) * img, na_g);
-            } else {
-                for (int part = 0; part < 2; ++part) {
-                    const uint8_t *src = part ? d_b : d_a; const int cnt = part ? nb : na, first = part ? na : 0;
-                    if (!cnt) continue;
-                    hipLaunchKernelGGL(sift_upsample_kernel, dim3((bw / 4 + 256) / 256, H + 1, cnt), dim3(256), 0, h->stream, src, W, H, img,
-                                       S->d_tmp + (long long)first * dv.tstride, dv.tstride);
-                }
-                sift_blur(h, S->d_tmp, dv.tstride, S->d_gauss + dv.goff[0], dv.gstride, nullptr, 0, bw, bh, 0, n);
-            }
-        }
-        for (int o = o0; o < o1; ++o) {
-            const int w = dv.w[o], hh = dv.h[o];
-            const long long pn = (long long)w * hh;
-            if (!have_l0)
-                hipLaunchKernelGGL(sift_halve_kernel, dim3((w + 1023) / 1024, hh, g), dim3(256), 0, h->stream,
-                                   (const float *)(G + dv.goff[o - 1] + (long long)S_NOL * dv.w[o - 1] * dv.h[o - 1]),
-                                   G + dv.goff[o], dv.gstride, dv.w[o - 1], w, hh);
-            have_l0 = false;
-            if (S->march && w >= 256 && hh >= 64) {
-                // levels 1-3 in one march over level 0 (+ level 0 of the next octave), levels 4-5 in one march over level 3
-                const bool last = o + 1 >= dv.noct;
-                float *dec = !last ? G + dv.goff[o + 1] : nullptr;
-                const dim3 grid((w + MARCH_SW - 1) / MARCH_SW, g);
-                hipLaunchKernelGGL((sift_march_kernel<3, 5, 6, 8>), grid, dim3(MarchGeo<3, 5, 6, 8>::NT), 0, h->stream, (const float *)(G + dv.goff[o]), dv.gstride,
-                                   G + dv.goff[o] + pn, dv.gstride, pn, w, hh, 1, dec, 2, last ? 0 : dv.w[o + 1], last ? 0 : dv.h[o + 1]);
-                hipLaunchKernelGGL((sift_march_kernel<2, 10, 13, 0>), grid, dim3(MarchGeo<2, 10, 13, 0>::NT), 0, h->stream, (const float *)(G + dv.goff[o] + 3 * pn), dv.gstride,
-                                   G + dv.goff[o] + 4 * pn, dv.gstride, pn, w, hh, 4, (float *)nullptr, -1, 0, 0);
-                have_l0 = !last;
-                continue;
-            }
-            for (int i = 1; i < S_NG; ++i) {
-                const bool last = o + 1 >= dv.noct;
-                float *dec = i == S_NOL && !last ? G + dv.goff[o + 1] : nullptr;
-                const bool wrote = sift_blur(h, G + dv.goff[o] + (i - 1) * pn, dv.gstride, G + dv.goff[o] + i * pn, dv.gstride,
-                                             nullptr, 0, w, hh, i, g, dec, last ? 0 : dv.w[o + 1], last ? 0 : dv.h[o + 1]);
-                if (i == S_NOL) have_l0 = wrote;
-            }
-        }
-    };
-    // extrema scan of tiles [t0, t0 + nt) of images [i0, i0 + g)
-    auto extrema = [&](int i0, int g, int t0, int nt) {
-        if (nt > 0)
-            hipLaunchKernelGGL(sift_extrema_mask_kernel, dim3((nt + 7) / 8 * 8, g), dim3(256), 0, h->stream,
-                               (const float *)(S->d_gauss + (long long)i0 * dv.gstride), dv, (const SiftXTile *)(S->d_xtiles + t0),
-                               S->d_xmask + (long long)i0 * dv.bmstride, S->d_band_cnt + (long long)i0 * dv.nbands, nt);
-    };
     hipMemsetAsync(S->d_band_cnt, 0, sizeof(int) * (size_t)n * dv.nbands, h->stream);
-    if (S->group > 0 && S->fused_all && dv.noct > 1) {
-        // image-major schedule for the large octaves: the six levels of octave 0 of a few images (199 MB each at 1920x1080) are
-        // written, read by the next blur and scanned for extrema while they are still in the 256 MB memory-side cache
-        const int om = S->group_octaves < dv.noct ? S->group_octaves : dv.noct;
-        for (int i0 = 0; i0 < n; i0 += S->group) {
-            const int g = n - i0 < S->group ? n - i0 : S->group;
-            pyramid(i0, g, 0, om);
-            extrema(i0, g, 0, S->xtile_oct_end[om - 1]);
+    // Pyramid.  Octave 0 starts with the upsample + initial blur in one kernel (the upsampled image is formed in the blur's
+    // window loader); level 0 of octave o + 1 (= level S_NOL of octave o, halved) is written by the kernel that makes that level.
+    float *G = S->d_gauss;
+    sift_blur_launch<5, true>(h, nullptr, 0, G + dv.goff[0], dv.gstride, bw, bh, 0, n, d_a, d_b, na);
+    for (int o = 0; o < dv.noct; ++o) {
+        const int w = dv.w[o], hh = dv.h[o];
+        const long long pn = (long long)w * hh;
+        const bool last = o + 1 >= dv.noct;
+        float *dec = !last ? G + dv.goff[o + 1] : nullptr;
+        const int w2 = last ? 0 : dv.w[o + 1], h2 = last ? 0 : dv.h[o + 1];
+        if (S->march && w >= 256 && hh >= 64) {
+            // levels 1-3 in one march over level 0 (+ level 0 of the next octave), levels 4-5 in one march over level 3
+            const dim3 grid((w + MARCH_SW - 1) / MARCH_SW, n);
+            hipLaunchKernelGGL((sift_march_kernel<3, 5, 6, 8>), grid, dim3(MarchGeo<3, 5, 6, 8>::NT), 0, h->stream, (const float *)(G + dv.goff[o]), dv.gstride,
+                               G + dv.goff[o] + pn, dv.gstride, pn, w, hh, 1, dec, 2, w2, h2);
+            hipLaunchKernelGGL((sift_march_kernel<2, 10, 13, 0>), grid, dim3(MarchGeo<2, 10, 13, 0>::NT), 0, h->stream, (const float *)(G + dv.goff[o] + 3 * pn), dv.gstride,
+                               G + dv.goff[o] + 4 * pn, dv.gstride, pn, w, hh, 4, (float *)nullptr, -1, 0, 0);
+            continue;
         }
-        if (om < dv.noct) pyramid(0, n, om, dv.noct);
-        MARK(h, RPE_STAGE_FAST);
-        extrema(0, n, S->xtile_oct_end[om - 1], S->n_xtiles - S->xtile_oct_end[om - 1]);
-    } else {
-        pyramid(0, n, 0, dv.noct);
-        // 3. seeds (count, scan, emit)
-        MARK(h, RPE_STAGE_FAST);
-        extrema(0, n, 0, S->n_xtiles);
+        for (int i = 1; i < S_NG; ++i)
+            sift_blur(h, G + dv.goff[o] + (i - 1) * pn, dv.gstride, G + dv.goff[o] + i * pn, dv.gstride, w, hh, i, n,
+                      i == S_NOL ? dec : nullptr, w2, h2);
     }
+    // 3. seeds (count, scan, emit)
+    MARK(h, RPE_STAGE_FAST);
+    if (S->n_xtiles > 0)
+        hipLaunchKernelGGL(sift_extrema_mask_kernel, dim3((S->n_xtiles + 7) / 8 * 8, n), dim3(256), 0, h->stream, (const float *)S->d_gauss, dv,
+                           (const SiftXTile *)S->d_xtiles, S->d_xmask, S->d_band_cnt, S->n_xtiles);
     hipMemsetAsync(h->d_ovf, 0, sizeof(unsigned) * n, h->stream);
     hipLaunchKernelGGL(sift_band_scan_kernel, dim3(n), dim3(256), 0, h->stream, (const int *)S->d_band_cnt, S->d_band_off, S->d_nseeds, h->d_ovf, dv);
     hipLaunchKernelGGL(sift_extrema_emit_kernel, dim3((dv.nbands + 3) / 4, n), dim3(256), 0, h->stream, (const unsigned long long *)S->d_xmask, dv,

@@ -3,42 +3,37 @@
 // Replaces cv2.ORB_create(nfeatures, 1.1, 12, fastThreshold=15, HARRIS_SCORE)
 // .detectAndCompute(image, None)  (reference src/core/pose_estimator.py:85-91,:108).
 // Kernels (all images of the batch per launch; the stage names are the hipEvent slots of rpe_get_stage_ms):
-//   pyramid  : pyr_resize x11: INTER_LINEAR_EXACT chain, 8.8 fixed point, 128x64 tiles, source window in LDS
-//   fast     : fast_nms: FAST-9/16 score + 3x3 NMS + 31-px border filter, fused, per-tile keypoint lists;
+//   pyramid  : pyr_resize x11: INTER_LINEAR_EXACT chain, 8.8 fixed point, 256x16 tiles of one wave, source window in LDS
+//   fast     : fast_nms: FAST-9/16 score + 3x3 NMS + 31-px border filter, fused, 64x64 tiles, per-tile keypoint lists;
 //              tiles cover the border-filtered region only ("nms" slot is empty)
 //   select   : raster_corners (a level's tile lists -> one list in FAST's raster emission order) + retain_fast:
 //              retainBest(2*quota) on the FAST score, replayed as the C++ runtime's nth_element + partition (cv2's ORDER)
 //   harris   : 7x7 Harris response per candidate (f32, op order = oracle)
 //   keypoints: retain_harris: retainBest(quota) on the Harris response, same replay; compact_keypoints: level-major lists
-//   angle    : orient_describe: one wave per keypoint: patch in LDS -> intensity-centroid angle (fastAtan2) ->
-//              Gaussian 7x7 on the patch (cv2's sepFilter2D f32 route, fused multiply-adds) -> 256-bit steered BRIEF ("blur" / "describe" slots are empty; the
-//              whole-level blur kernel below only serves rpe_orb_debug_fetch)
+//   angle    : orient_describe: one keypoint per one-wave workgroup: patch in LDS -> intensity-centroid angle (fastAtan2) ->
+//              Gaussian 7x7 on the patch (cv2's sepFilter2D f32 route, fused multiply-adds) -> 256-bit steered BRIEF
+//              ("blur" / "describe" slots are empty; the whole-level blur kernel at the end only serves rpe_orb_debug_fetch)
+// There is one configuration: the tile shapes are constants (rpe_internal.h for those the host tables share, here for the
+// rest) and the static_asserts beside them hold the relations the kernels rely on.
 // Everything is integer or mirrored-order f32, so results equal the CPU oracle bit for bit -- and, on the reference's own
 // image pairs, cv2's (tests/test_reference_rows_cpu.py, tests/test_gpu_round3.py).
 #include "rpe_internal.h"
 #include "rpe_devmath.h"
 #include "retain_best_emul.h"
 
-#define TW 64
-#define TH 64
-
 __device__ float4 c_pattern_f[256];         // rBRIEF pattern (brief_pattern.inc) as f32 (x0, y0, x1, y1), uploaded at handle creation
-__constant__ signed char c_disc[768 * 2];   // (u,v) offsets of the radius-15 disc
-__constant__ int c_ndisc;
-__constant__ signed char c_circ[16 * 2] = {0,3, 1,3, 2,2, 3,1, 3,0, 3,-1, 2,-2, 1,-3, 0,-3, -1,-3, -2,-2, -3,-1, -3,0, -3,1, -2,2, -1,3};
 
-// the same disc as packed-u8 dot-product weights: item (row v = -15..15, dword j = 0..7) covers u = -16 + 4j .. +3;
-// .x = 1 per in-disc byte, .y = (u + 16) per in-disc byte (0 elsewhere)
+// the radius-15 intensity-centroid disc as packed-u8 dot-product weights: item (row v = -15..15, dword j = 0..7) covers
+// u = -16 + 4j .. +3; .x = 1 per in-disc byte, .y = (u + 16) per in-disc byte (0 elsewhere)
 __constant__ uint2 c_discw[31 * 8];
 
 // taps of the descriptor blur: GaussianBlur(7x7, sigma 2) as cv2's sepFilter2D f32 route holds them -- (float)(exp(-x^2 / 8) / sum),
 // getGaussianKernel's normalised f64 kernel cast to f32 (computed on the host at handle creation, like the oracle does)
 __constant__ float c_gauss[7];
 
-void rpe_orb_upload_disc(const signed char *disc, int n)
+// the kernels' constant tables: disc weights (from the n (u, v) offsets of the disc), rBRIEF pattern, blur taps
+void rpe_orb_upload_constants(const signed char *disc, int n)
 {
-    hipMemcpyToSymbol(HIP_SYMBOL(c_disc), disc, (size_t)n * 2);
-    hipMemcpyToSymbol(HIP_SYMBOL(c_ndisc), &n, sizeof(int));
     uint2 wt[31 * 8];
     for (int i = 0; i < 31 * 8; ++i) wt[i] = make_uint2(0u, 0u);
     for (int i = 0; i < n; ++i) {
@@ -90,23 +85,31 @@ __device__ __forceinline__ bool xcd_image_block(int nb, int n_img, int &img, int
 static inline unsigned xcd_image_grid(int nb, int n_img) { return (unsigned)(8 * ((n_img + 7) / 8) * nb); }
 
 // ---------------------------------------------------------------- pyramid
-// Workgroup = PYR_TW x PYR_TH destination tile of level l.  The source footprint in level l-1
-// (<= PYR_ROWS rows x 152 bytes, bounds derived arithmetically so the loads do not depend on
-// the coefficient tables; checked on the host) is staged in LDS with aligned 16-byte loads, all of
-// them in flight before the first LDS store -- 6.9 KB per workgroup at PYR_TH = 32.
-// One lane = 4 destination columns x 8 consecutive destination rows.  The bilinear chain is separable in exact
+// Workgroup = one wave = 256 x 16 destination tile of level l (PYR_TW x PYR_TH).  The source footprint in level l-1
+// (PYR_ROWS = 23 rows x PYR_DW = 84 dwords, bounds derived arithmetically so the loads do not depend on the coefficient
+// tables; checked on the host at create time) is staged in LDS with aligned 16-byte loads, all of them in flight before
+// the first LDS store -- 7744 B per workgroup, so the LDS of a CU (160 KB) holds 21 windows.
+// One lane = 4 destination columns x the tile's 16 rows, as two groups of 8.  The bilinear chain is separable in exact
 // integer arithmetic: h(src row, dst col) = a0 p[o] + a1 p[o+1] (16 bits), out = (b0 h(top) + b1 h(bottom) + 2^15) >> 16.
 // Reading p[o+1] and the row below unclamped is exact: the coefficient tables give weight 0 wherever OpenCV clamps
 // (last source column / row).  The row loop is described where it stands.
-// PYR_TW / PYR_TH (tile size), PYR_DW / PYR_ROWS (window size) and PYR_THREADS live in rpe_internal.h: the host builds the
-// tile table from them
-#define PYR_NCG (PYR_TW / 4)                    // column groups of 4 pixels per tile row
-#define PYR_NRG (PYR_THREADS / PYR_NCG)         // row groups of 8 rows side by side in a workgroup
-#define PYR_RGPL ((PYR_TH / 8) / PYR_NRG)       // row groups per lane: ty8, ty8 + PYR_NRG, ...
+// Why this tile.  The kernel lives on how many tile windows a CU keeps in flight (r02 diagnostic builds: loads + LDS alone
+// 1.12 ms, rows + stores alone 1.26 ms, together 1.92 ms -- the phases of a workgroup overlap only through OTHER
+// workgroups, and FAST run beside it on a second stream gained nothing: wave slots are the contended resource).  So a lane
+// takes two row groups (half the waves per window, the column constants serve 16 rows) and a tile is one wave: 64-row
+// tiles of two waves measured 1.89 ms, 128 x 32 of one wave 1.68.  And the longer the contiguous rows the better the
+// mixed read / write stream runs: 64-wide 1.82, 128-wide 1.67, 256 x 16 1.64 ms (partial tiles at the right edge idle
+// lanes, which a memory-bound kernel does not feel).
+constexpr int PYR_THREADS = 64;
+constexpr int PYR_LDS_DW = PYR_ROWS * PYR_DW + 4;          // +4: the unclamped p[o+1] of the last row's last column
+static_assert(PYR_THREADS == PYR_TW / 4 * PYR_TH / 16, "a lane takes 4 columns x 16 rows of the tile");
+static_assert(PYR_THREADS == 64 && PYR_TH == 16, "one wave per tile, whose lanes each take the tile's two groups of 8 rows");
+static_assert(PYR_DW % 4 == 0, "window rows are whole 16-byte chunks");
+static_assert(PYR_LDS_DW * 4 == 7744, "LDS per tile window");
 __global__ __launch_bounds__(PYR_THREADS) void pyr_resize_kernel(uint8_t *pyr, RpeDeviceLayout lay, const int *__restrict__ coef,
                                                                   const RpePyrTile *__restrict__ ptiles, int ntiles, int l)
 {
-    __shared__ __attribute__((aligned(16))) unsigned s_src[PYR_ROWS * PYR_DW + 4];   // +4: the unclamped p[o+1] of the last row's last column
+    __shared__ __attribute__((aligned(16))) unsigned s_src[PYR_LDS_DW];
     const RpeLevel &S = lay.lv[l - 1];
     const RpeLevel &D = lay.lv[l];
     const int tid = threadIdx.x;
@@ -121,22 +124,18 @@ __global__ __launch_bounds__(PYR_THREADS) void pyr_resize_kernel(uint8_t *pyr, R
     const uint8_t *src = rpe_level_base(pyr, lay, blockIdx.y, l - 1);
     // packed (offset | weight << 16) per destination column / row; the device table pads the x run to a multiple of 128
     // and the y run to a multiple of 64 entries (last entry replicated) and aligns both to 16 B, so a lane fetches its
-    // 4 columns with one 16-B load and 8 rows with two, without clamps
+    // 4 columns with one 16-B load and its 16 rows with four, without clamps
     const int *cxp = coef + D.dcoef_off, *cyp = cxp + ((D.w + 127) & ~127);
-    // The kernel lives on how many tile windows a CU keeps in flight (r02 diagnostic builds: loads + LDS alone 1.12 ms, rows +
-    // stores alone 1.26 ms, together 1.92 ms -- the phases of a workgroup overlap only through OTHER workgroups, and FAST
-    // run beside it on a second stream gained nothing: wave slots are the contended resource).  A lane therefore takes 4
-    // columns x TWO row groups of 8 rows (half the waves per window, the column constants serve 16 rows), and the tile is
-    // only PYR_TH = 32 rows high: one wave per tile, 23 independent windows per CU.
-    const int tx = tid % PYR_NCG, ty8 = tid / PYR_NCG;     // row groups ty8, ty8 + PYR_NRG, ...
+    // lane = column group of 4 pixels x row-group pair (the tile has one pair: yl == y0)
+    const int tx = tid % (PYR_TW / 4), yl = y0 + 16 * (tid / (PYR_TW / 4));
     const int x4 = x0 + 4 * tx;
     // coefficient loads go out first, in the shadow of the window loads
     const int4 cv = *(const int4 *)(cxp + x4);
-    int4 rq[2 * PYR_RGPL];
+    int4 rq[PYR_TH / 4];
 #pragma unroll
-    for (int k = 0; k < 2 * PYR_RGPL; ++k) rq[k] = *(const int4 *)(cyp + y0 + (ty8 + PYR_NRG * (k >> 1)) * 8 + 4 * (k & 1));
+    for (int k = 0; k < PYR_TH / 4; ++k) rq[k] = *(const int4 *)(cyp + yl + 4 * k);
     {   // all window loads (16 B per lane) in flight before the first LDS store (one HBM round trip per tile):
-        // chunk i = tid + 128 q of the 74 x 11 chunks of the window, row i / 11, 16-B column i % 11
+        // chunk i = tid + 64 q of the 23 x 21 chunks of the window (q < 8), row i / 21, 16-B column i % 21
         constexpr int NQ = PYR_DW / 4, NCHUNK = PYR_ROWS * NQ, NLD = (NCHUNK + PYR_THREADS - 1) / PYR_THREADS;
         uint4 stage[NLD];
 #pragma unroll
@@ -173,10 +172,10 @@ __global__ __launch_bounds__(PYR_THREADS) void pyr_resize_kernel(uint8_t *pyr, R
     // weight << 16).  Materialised here: rematerialised inside the row loop, every row's first use of a table register sits
     // behind an s_waitcnt vmcnt(0) -- which on gfx9 also waits for the previous row's global STORE (rows serialised on HBM
     // write latency)
-    unsigned rc[8 * PYR_RGPL];
+    unsigned rc[PYR_TH];
     {
 #pragma unroll
-        for (int k = 0; k < 2 * PYR_RGPL; ++k) {
+        for (int k = 0; k < PYR_TH / 4; ++k) {
             const int rv4[4] = {rq[k].x, rq[k].y, rq[k].z, rq[k].w};
 #pragma unroll
             for (int e = 0; e < 4; ++e) {
@@ -200,8 +199,8 @@ __global__ __launch_bounds__(PYR_THREADS) void pyr_resize_kernel(uint8_t *pyr, R
     const unsigned sh = (unsigned)bcol & 3u;
     const unsigned colmask = x4 + 3 < D.w ? 0xFFFFFFFFu : (x4 >= D.w ? 0u : (0xFFFFFFFFu >> (8 * (x4 + 4 - D.w))));   // bytes past D.w stay 0
 #pragma unroll
-    for (int half = 0; half < PYR_RGPL; ++half) {
-        const int yb = y0 + (ty8 + PYR_NRG * half) * 8;
+    for (int half = 0; half < 2; ++half) {
+        const int yb = yl + 8 * half;
         uint8_t *dstp = base + D.off + __umul24((unsigned)yb, (unsigned)D.pitch) + x4;
         const int nrows = min(8, D.h - yb);
 #pragma unroll
@@ -253,7 +252,6 @@ void rpe_launch_pyramid(rpe_handle *h, int n_img)
 //           tile; the corners (score > thr) are compacted to the front of the wave's slice.
 //  phase 3: strict 3x3 maximum on the LDS score tile over the corners only, 31-px border
 //           filter (KeyPointsFilter::runByImageBorder), per-tile keypoint list to HBM.
-__device__ __forceinline__ int imin3(int a, int b, int c) { return min(a, min(b, c)); }
 __device__ __forceinline__ int imax3(int a, int b, int c) { return max(a, max(b, c)); }
 // one v_max3_u32 / v_min3_u32 per window of 3: left to itself the compiler shares two-input partial results between
 // neighbouring windows (max(r[k+1], r[k+2]) ...) and spends ~48 instructions on a side's windows of 3 and 9 and the
@@ -265,12 +263,17 @@ typedef short short2_t __attribute__((ext_vector_type(2)));
 static constexpr int CIRC_DX[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1};
 static constexpr int CIRC_DY[16] = {3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1, 0, 1, 2, 3};
 
-#define FS_ROWS (FAST_TH + 2)        // score rows (y0-1 .. y0+FAST_TH)
-#define FAST_PROWS (FAST_TH + 8)     // pixel rows (y0-4 .. y0+FAST_TH+3)
-#define FAST_THREADS (FAST_TH * 4)
-#define FAST_NRP (FAST_THREADS / 18)  // rows of the 18-dword tile row that one pass of the lanes covers (14 or 7)
-#define FAST_LANES (FAST_NRP * 18)
-#define FAST_NCAND (FS_ROWS * 72)    // candidate list capacity: one entry per score-area pixel at most
+constexpr int FS_ROWS = FAST_TH + 2;         // score rows (y0-1 .. y0+FAST_TH)
+constexpr int FAST_PROWS = FAST_TH + 8;      // pixel rows (y0-4 .. y0+FAST_TH+3)
+constexpr int FAST_THREADS = 256;
+constexpr int FAST_NRP = 14;                 // rows of the 18-dword tile row that one pass of the lanes covers
+constexpr int FAST_LANES = FAST_NRP * 18;    // the 252 lanes that load pixels and run phase 1
+constexpr int FAST_NCAND = FS_ROWS * 72;     // candidate list capacity: one entry per score-area pixel at most
+static_assert(FAST_LANES <= FAST_THREADS, "a pass of FAST_NRP tile rows fits the workgroup");
+static_assert(6 * FAST_NRP >= FAST_PROWS && 5 * FAST_NRP >= FS_ROWS, "6 load passes cover the pixel rows, 5 phase-1 passes the score rows");
+static_assert(RPE_FAST_TILE_CAP == (64 / 2) * (FAST_TH / 2), "strict 3x3 maxima of a tile");
+static_assert(RPE_FAST_TILE_CAP <= FAST_PROWS * 18, "the tile's keypoint list lives in the dead pixel tile");
+static_assert((FAST_PROWS * 18 + FS_ROWS * 18) * 4 + FAST_NCAND * 2 + 8 == 19448, "LDS per workgroup");
 // Output: one compact list per tile of the keypoints that survive NMS and the border filter, packed
 // score << 24 | y << 12 | x (level coordinates).  A strict 3x3
 // maximum cannot have an 8-neighbour that is one too, so a 64x64 tile holds at most 32*32 = 1024 of them:
@@ -281,10 +284,9 @@ __global__ __launch_bounds__(FAST_THREADS) void fast_nms_kernel(const uint8_t *_
                                                         int *__restrict__ tile_cnt, RpeDeviceLayout lay,
                                                         const RpeTile *__restrict__ tiles, int ntiles)
 {
-    // 19.5 KB of LDS per workgroup = 8 workgroups (32 waves) per CU: the pixel tile is dead after phase 2, so the keypoint
-    // list of phase 3 lives in its place (4096 <= 5184 bytes); at 24.5 KB only 6 workgroups fit
-    constexpr int S_IN_DW = FAST_PROWS * 18 > RPE_FAST_TILE_CAP + 256 ? FAST_PROWS * 18 : RPE_FAST_TILE_CAP + 256;
-    __shared__ __attribute__((aligned(16))) unsigned s_in[S_IN_DW];                // pixels  y0-4 .. y0+FAST_TH+3, x0-4 .. x0+67 (sized for the phase-3 aliases too)
+    // 19448 B of LDS per workgroup = 8 workgroups (32 waves) per CU: the pixel tile is dead after phase 2, so the keypoint
+    // list of phase 3 lives in its place (4096 <= 5184 bytes); with a list of its own (24.5 KB) only 6 workgroups fitted
+    __shared__ __attribute__((aligned(16))) unsigned s_in[FAST_PROWS * 18];        // pixels  y0-4 .. y0+FAST_TH+3, x0-4 .. x0+67
     __shared__ __attribute__((aligned(16))) unsigned s_sc[FS_ROWS * 18];   // scores  y0-1 .. y0+64, x0-4 .. x0+67
     unsigned *s_out = s_in;                                               // phase 3: the tile's keypoint list [1024]
     __shared__ unsigned short s_cand[FAST_NCAND];
@@ -535,8 +537,6 @@ void rpe_launch_fast(rpe_handle *h, int n_img)
                        h->d_pyr, h->d_tile_list, h->d_tile_cnt, h->lay, h->d_tiles_fast, h->n_tiles_fast);
 }
 
-void rpe_launch_nms(rpe_handle *h, int n_img) { (void)h; (void)n_img; }   // fused into fast_nms_kernel
-
 // ------------------------------------------------- block-wide exclusive scan
 __device__ __forceinline__ int block_excl_scan(int v, int *s_wave /*[5]*/, int &total)
 {
@@ -729,7 +729,7 @@ __global__ __launch_bounds__(64) void retain_fast_kernel(const unsigned *__restr
 
 #define RPE_RETAIN_TIER 2048         // list length served by the small-LDS launch of the two retain kernels
 
-void rpe_launch_select(rpe_handle *h, int n_img)
+void rpe_launch_raster_retain(rpe_handle *h, int n_img)
 {
     // LDS: row starts + fill counters + staged entries (capacity: largest ccap + one full row of keypoints) + tile prefix
     int rows_cap = 0, ccap_max = 0, nt_max = 0, wmax = 0, nlev_big = 0;
@@ -920,42 +920,41 @@ void rpe_launch_keypoints(rpe_handle *h, int n_img)
 
 // ------------------------------------------------- orientation + descriptor
 // Fused per-keypoint kernel (replaces the separate ICAngles, whole-pyramid GaussianBlur
-// and rBRIEF launches of the first version): one wave per keypoint, KP_PER_WG (= 1) keypoints per
-// workgroup.  The 45 x 48-byte raw patch around the keypoint is staged in LDS once and
+// and rBRIEF launches of the first version): one keypoint per workgroup of one wave, kcap
+// workgroups per image.  The 45 x 48-byte raw patch around the keypoint is staged in LDS once and
 // feeds (1) the intensity-centroid moments over the radius-15 disc -> fastAtan2 angle,
-// (2) the horizontal pass of the fixed-point 7x7 Gaussian on the rows the descriptor can
+// (2) the horizontal pass of the f32 7x7 Gaussian on the rows the descriptor can
 // touch, (3) the vertical pass evaluated only at the 512 steered sampling points.
-// Integer results are identical to blurring the whole level (the patch never reaches
-// the image border: keypoints are >= 31 px inside, the footprint is 22 px).
-// keypoints (waves) per workgroup.  The phases of a keypoint (patch fetch 0.88 ms, moments + MFMA blur 0.36 ms, steered
-// sampling 0.65 ms when run alone -- diagnostic builds) overlap only through OTHER waves, and barriers that tie four
-// keypoints together cost more than the shared angle / sincos evaluation saves: 4 per workgroup 2.25 ms, 2: 2.25, 1: 2.17.
-#ifndef KP_PER_WG
-#define KP_PER_WG 1
-#endif
+// Results are identical to blurring the whole level (the patch never reaches
+// the image border: keypoints are >= 31 px inside, the footprint is 22 px).  10016 B of LDS per workgroup.
+// Why one keypoint per workgroup.  The phases of a keypoint (patch fetch 0.88 ms, moments + blur 0.36 ms, steered
+// sampling 0.65 ms when run alone -- diagnostic builds) overlap only through OTHER waves, and the barriers that tied the
+// keypoints of a larger workgroup together cost more than sharing the angle / sincos evaluation between them saved:
+// 4 per workgroup 2.25 ms, 2: 2.25, 1: 2.17.  The wave evaluates its own angle on uniform values, no exchange.
 #define KP_R 22
 #define KP_ROWS 45
 #define KP_RAW_DW 12                 // 48 bytes per raw row
 #define KP_HCOLS 40                  // horizontally blurred columns: x = x0 - 19 + j (the descriptor reaches |dx| <= 18: columns 1..37)
 #define KP_HSTRIDE 49                // f32 per column of the blurred buffer (45 rows + padding; odd, so neighbouring columns start in different banks)
-__global__ __launch_bounds__(64 * KP_PER_WG) void orient_describe_kernel(const uint8_t *__restrict__ pyr, const unsigned *__restrict__ kp_xy,
+static_assert((KP_ROWS * KP_RAW_DW + 4 + KP_HCOLS * KP_HSTRIDE) * 4 == 10016, "LDS per keypoint");
+__global__ __launch_bounds__(64) void orient_describe_kernel(const uint8_t *__restrict__ pyr, const unsigned *__restrict__ kp_xy,
                                                                const float2 *__restrict__ kp_pt, const int *__restrict__ kp_count,
                                                                float *__restrict__ kp_angle, uint8_t *__restrict__ desc,
                                                                RpeDeviceLayout lay, int nb, int n_img)
 {
-    __shared__ __attribute__((aligned(16))) unsigned s_raw[KP_PER_WG][KP_ROWS * KP_RAW_DW + 4];   // 16-B aligned rows of 48 B (+ one row pass over-read)
+    __shared__ __attribute__((aligned(16))) unsigned s_raw[1][KP_ROWS * KP_RAW_DW + 4];   // 16-B aligned rows of 48 B (+ one row pass over-read)
     // horizontally blurred patch, COLUMN-major f32 [column][row]: the 7 vertical taps of a steered sample are contiguous
-    __shared__ float s_hb[KP_PER_WG][KP_HCOLS * KP_HSTRIDE];
-#if KP_PER_WG > 1
-    __shared__ int s_m[KP_PER_WG][2];              // (m01, m10) of the workgroup's keypoints
-    __shared__ float s_ab[KP_PER_WG][2];           // (cos, sin) of their angles
-#endif
+    __shared__ float s_hb[1][KP_HCOLS * KP_HSTRIDE];
+    // The indexing is written per wave of the workgroup (wave wv takes keypoint blk + wv and its own LDS arrays).  The
+    // workgroup is one wave, so wv == 0 and `active` below is true for every workgroup that gets past the return; the
+    // compiler learns that only late, and spelling it out changes the schedule and register allocation of the whole
+    // kernel (40 VGPRs for 45).  That is a kernel change to measure on its own, so the form stays.
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     int img, blk;
     if (!xcd_image_block(nb, n_img, img, blk)) return;
-    const int k = blk * KP_PER_WG + wv;
+    const int k = blk + wv;
     const int nkp = kp_count[img];
-    if (blk * KP_PER_WG >= nkp) return;                               // workgroup-uniform: the grid is sized for the keypoint capacity
+    if (blk >= nkp) return;                                           // the grid is sized for the keypoint capacity
     const bool active = k < nkp;
     const long long g = (long long)img * lay.kcap + (active ? k : 0);
     const unsigned p = kp_xy[g];
@@ -979,11 +978,10 @@ __global__ __launch_bounds__(64 * KP_PER_WG) void orient_describe_kernel(const u
         }
     }
     __syncthreads();
-    int km01 = 0, km10 = 0;
+    int m10 = 0, m01 = 0;
     if (active) {
         // ---- orb.cpp ICAngles: integer moments over the disc, reduced with wave shuffles
         // integer sums, so any summation order gives the oracle's moments: 4 disc pixels per packed-u8 dot product
-        int m10 = 0, m01 = 0;
         {
             const unsigned *rw = raw + (KP_R - 15) * KP_RAW_DW;                  // patch row of v = -15
             const int bo = off0 + KP_R - 16;                                        // byte column of u = -16 (>= 6)
@@ -1007,13 +1005,6 @@ __global__ __launch_bounds__(64 * KP_PER_WG) void orient_describe_kernel(const u
         // rounds of __shfl_xor were 36 vector + 12 LDS (ds_bpermute) instructions
         m10 = wave_sum(m10);
         m01 = wave_sum(m01);
-        // fastAtan2 and the deterministic sincos are ~100 vector instructions on wave-uniform values: the four keypoints
-        // of the workgroup get them from four LANES of wave 0 after the barrier below instead of from four waves
-#if KP_PER_WG > 1
-        if (lane == 0) { s_m[wv][0] = m01; s_m[wv][1] = m10; }
-#else
-        km01 = m01; km10 = m10;
-#endif
         // ---- horizontal pass of the descriptor blur.  cv2 blurs every pyramid level with GaussianBlur(7x7, sigma 2) before
         // computeOrbDescriptors; on a pyramid SUB-matrix that call takes sepFilter2D's f32 route (filter.simd.hpp
         // RowFilter<uchar, float>, SymmColumnFilter<Cast<float, uchar>>), whose AVX2-dispatched build fuses s += f * x: the
@@ -1065,31 +1056,17 @@ __global__ __launch_bounds__(64 * KP_PER_WG) void orient_describe_kernel(const u
         }
     }
     __syncthreads();
-#if KP_PER_WG > 1
-    if (wv == 0 && lane < KP_PER_WG && blk * KP_PER_WG + lane < nkp) {
-        const float angle = fast_atan2_deg((float)s_m[lane][0], (float)s_m[lane][1]);
-        kp_angle[(long long)img * lay.kcap + blk * KP_PER_WG + lane] = angle;
-        const float ang = angle * (float)(3.141592653589793238462643383279502884 / 180.0);
-        double sn, cs;
-        det_sincos((double)ang, sn, cs);
-        s_ab[lane][0] = (float)cs; s_ab[lane][1] = (float)sn;
-    }
-    __syncthreads();
     if (!active) return;
-    const float a = s_ab[wv][0], b = s_ab[wv][1];
-#else
-    // one keypoint per workgroup: the wave evaluates its own angle (uniform values), no exchange and no barrier
-    if (!active) return;
+    // the angle, on wave-uniform values
     float a, b;
     {
-        const float angle = fast_atan2_deg((float)km01, (float)km10);
+        const float angle = fast_atan2_deg((float)m01, (float)m10);
         if (lane == 0) kp_angle[g] = angle;
         const float ang = angle * (float)(3.141592653589793238462643383279502884 / 180.0);
         double sn, cs;
         det_sincos((double)ang, sn, cs);
         a = (float)cs; b = (float)sn;
     }
-#endif
     // ---- orb.cpp computeOrbDescriptors: lane = 4 consecutive bit tests, vertical pass at the samples
     const float2 pt = kp_pt[g];
     const float sc = 1.f / L.scale;
@@ -1126,10 +1103,10 @@ __global__ __launch_bounds__(64 * KP_PER_WG) void orient_describe_kernel(const u
     if ((lane & 7) == 0) *(unsigned *)(desc + g * 32 + (lane >> 3) * 4) = v;
 }
 
-void rpe_launch_angle(rpe_handle *h, int n_img)
+void rpe_launch_orient_describe(rpe_handle *h, int n_img)
 {
-    const int nb = (h->lay.kcap + KP_PER_WG - 1) / KP_PER_WG;
-    hipLaunchKernelGGL(orient_describe_kernel, dim3(xcd_image_grid(nb, n_img)), dim3(64 * KP_PER_WG), 0, h->stream,
+    const int nb = h->lay.kcap;                                       // workgroups per image
+    hipLaunchKernelGGL(orient_describe_kernel, dim3(xcd_image_grid(nb, n_img)), dim3(64), 0, h->stream,
                        h->d_pyr, h->d_kp_xy, h->d_kp_pt, h->d_kp_count, h->d_kp_angle, h->d_desc, h->lay, nb, n_img);
 }
 
@@ -1144,6 +1121,7 @@ __global__ __launch_bounds__(256) void blur_kernel(const uint8_t *__restrict__ p
 {
     // 64x64 tile; input 70 rows x 72 bytes (x0-4 .. x0+67) loaded as aligned dwords; rows
     // are reflected at load time, the <=3 reflected columns per side are patched in LDS.
+    constexpr int TH = 64;
     __shared__ unsigned s_in[(TH + 6) * 18];
     __shared__ float4 s_h[(TH + 6) * 16];          // horizontal pass: 4 x f32 per entry
     const int tid = threadIdx.x;
@@ -1215,11 +1193,8 @@ __global__ __launch_bounds__(256) void blur_kernel(const uint8_t *__restrict__ p
 }
 
 // whole-level blur of ONE image of the last run into the one-image debug buffer (rpe_orb_debug_fetch which = 3)
-void rpe_launch_blur(rpe_handle *h, int img)
+void rpe_launch_debug_blur(rpe_handle *h, int img)
 {
     hipLaunchKernelGGL(blur_kernel, dim3(h->n_tiles_full, 1), dim3(256), 0, h->stream,
                        h->d_pyr, h->d_bufA, h->lay, h->d_tiles_full, img);
 }
-
-// --------------------------------------------------------------- describe
-void rpe_launch_describe(rpe_handle *h, int n_img) { (void)h; (void)n_img; }   // fused into orient_describe_kernel

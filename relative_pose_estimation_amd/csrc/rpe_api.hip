@@ -9,7 +9,7 @@
 #include <stdlib.h>
 #include <algorithm>
 
-void rpe_orb_upload_disc(const signed char *disc, int n);
+void rpe_orb_upload_constants(const signed char *disc, int n);
 
 static std::string g_create_err;
 
@@ -231,8 +231,7 @@ static int build_tables(rpe_handle *h)
             int d = umax[abs(vv)];
             for (int u = -d; u <= d; ++u) { disc.push_back((signed char)u); disc.push_back((signed char)vv); }
         }
-        if (disc.size() / 2 > 768) { h->err = "disc table overflow"; return RPE_ERR_INVALID; }
-        rpe_orb_upload_disc(disc.data(), (int)(disc.size() / 2));
+        rpe_orb_upload_constants(disc.data(), (int)(disc.size() / 2));
     }
     // RANSAC subset stream per M (ptsetreg.cpp getSubset; RNG seeded (uint64)-1 per run)
     const int mm = h->cfg.max_matches, iters = h->cfg.ransac_max_iters;
@@ -314,12 +313,11 @@ static int alloc_workspace(rpe_handle *h)
     HIPCHK(h, hipMemset(h->d_tile_cnt, 0, NIo * ntf * sizeof(int)));
     const size_t img = (size_t)h->cfg.width * h->cfg.height;
     DM(h, h->d_stage1, (B + 1) * img); DM(h, h->d_stage2, B * img);   // +1: a stream of max_batch pairs has max_batch + 1 frames
-    DM(h, h->d_hist, NI * RPE_NLEVELS * 256);
     DM(h, h->d_cand_xy, NI * L.cand_total); DM(h, h->d_cand_resp, NI * L.cand_total);
     DM(h, h->d_cand_count, NI * RPE_NLEVELS);
     DM(h, h->d_corner, NIo * L.corner_total); DM(h, h->d_corner_count, NI * RPE_NLEVELS); DM(h, h->d_kp_lvl_count, NI * RPE_NLEVELS);
     DM(h, h->d_kp_xy, NI * L.kcap); DM(h, h->d_kp_resp, NI * L.kcap); DM(h, h->d_kp_angle, NI * L.kcap);
-    DM(h, h->d_kp_pt, NI * L.kcap); DM(h, h->d_kp_cs, NI * L.kcap); DM(h, h->d_kp_count, NI);
+    DM(h, h->d_kp_pt, NI * L.kcap); DM(h, h->d_kp_count, NI);
     DM(h, h->d_ovf, NI);
     HIPCHK(h, hipMemset(h->d_ovf, 0, NI * sizeof(unsigned)));
     DM(h, h->d_desc, NI * L.kcap * h->desc_bytes);
@@ -498,29 +496,24 @@ extern "C" int rpe_synchronize(rpe_handle *h)
 
 // ------------------------------------------------------------- orchestration
 
-// copies level 0 of every image into the pyramid buffer (device to device)
+// copies level 0 of every image into the pyramid buffer (device to device): when the level's pitch equals the image
+// width, one strided copy per batch (an image is one "row" of it); otherwise one 2-D copy per image
 static int load_level0(rpe_handle *h, const uint8_t *d_a, const uint8_t *d_b, int na, int nb)
 {
     const int W = h->cfg.width, H = h->cfg.height;
     const RpeLevel &v = h->lay.lv[0];
+    const size_t img = (size_t)W * H;
+    if (v.pitch == W) {
+        if (na) HIPCHK(h, hipMemcpy2DAsync(h->d_pyr + v.off, h->lay.stride, d_a, img, img, na, hipMemcpyDeviceToDevice, h->stream));
+        if (nb) HIPCHK(h, hipMemcpy2DAsync(h->d_pyr + (size_t)na * h->lay.stride + v.off, h->lay.stride, d_b, img, img, nb,
+                                           hipMemcpyDeviceToDevice, h->stream));
+        return RPE_OK;
+    }
     for (int i = 0; i < na + nb; ++i) {
-        const uint8_t *src = i < na ? d_a + (size_t)i * W * H : d_b + (size_t)(i - na) * W * H;
+        const uint8_t *src = i < na ? d_a + (size_t)i * img : d_b + (size_t)(i - na) * img;
         uint8_t *dst = h->d_pyr + (size_t)i * h->lay.stride + v.off;
         HIPCHK(h, hipMemcpy2DAsync(dst, v.pitch, src, W, W, H, hipMemcpyDeviceToDevice, h->stream));
     }
-    return RPE_OK;
-}
-
-// strided batch copy kernel-free variant: when pitch == W one 2-D copy moves all images
-static int load_level0_fast(rpe_handle *h, const uint8_t *d_a, const uint8_t *d_b, int na, int nb)
-{
-    const int W = h->cfg.width, H = h->cfg.height;
-    const RpeLevel &v = h->lay.lv[0];
-    if (v.pitch != W) return load_level0(h, d_a, d_b, na, nb);
-    const size_t img = (size_t)W * H;
-    if (na) HIPCHK(h, hipMemcpy2DAsync(h->d_pyr + v.off, h->lay.stride, d_a, img, img, na, hipMemcpyDeviceToDevice, h->stream));
-    if (nb) HIPCHK(h, hipMemcpy2DAsync(h->d_pyr + (size_t)na * h->lay.stride + v.off, h->lay.stride, d_b, img, img, nb,
-                                       hipMemcpyDeviceToDevice, h->stream));
     return RPE_OK;
 }
 
@@ -543,18 +536,18 @@ static int run_orb(rpe_handle *h, const uint8_t *d_a, const uint8_t *d_b, int na
     MARK(h, RPE_STAGE_PYRAMID);
     HIPCHK(h, hipMemsetAsync(h->d_ovf, 0, sizeof(unsigned) * (size_t)n, h->stream));
     if (!set_level0_source(h, d_a, d_b, na, nb)) {
-        int rc = load_level0_fast(h, d_a, d_b, na, nb);
+        int rc = load_level0(h, d_a, d_b, na, nb);
         if (rc) return rc;
     }
     rpe_launch_pyramid(h, n);
     MARK(h, RPE_STAGE_FAST);      rpe_launch_fast(h, n);
-    MARK(h, RPE_STAGE_NMS);       rpe_launch_nms(h, n);
-    MARK(h, RPE_STAGE_SELECT);    rpe_launch_select(h, n);
+    MARK(h, RPE_STAGE_NMS);       // fused into fast_nms_kernel
+    MARK(h, RPE_STAGE_SELECT);    rpe_launch_raster_retain(h, n);
     MARK(h, RPE_STAGE_HARRIS);    rpe_launch_harris(h, n);
     MARK(h, RPE_STAGE_KEYPOINTS); rpe_launch_keypoints(h, n);
-    MARK(h, RPE_STAGE_ANGLE);     rpe_launch_angle(h, n);
-    MARK(h, RPE_STAGE_BLUR);      // fused into the per-keypoint kernel (the whole-level blur runs on demand in rpe_orb_debug_fetch)
-    MARK(h, RPE_STAGE_DESCRIBE);  rpe_launch_describe(h, n);
+    MARK(h, RPE_STAGE_ANGLE);     rpe_launch_orient_describe(h, n);
+    MARK(h, RPE_STAGE_BLUR);      // both fused into orient_describe_kernel (the whole-level blur runs on demand in rpe_orb_debug_fetch)
+    MARK(h, RPE_STAGE_DESCRIBE);
     MARK(h, RPE_STAGE_MATCH);
     HIPCHK(h, hipGetLastError());
     return RPE_OK;
@@ -1358,7 +1351,7 @@ extern "C" int rpe_orb_debug_fetch(rpe_handle *h, int index, int which, uint8_t 
             const uint8_t *in = index < h->lay.in_na ? h->lay.in_a + (size_t)index * img : h->lay.in_b + (size_t)(index - h->lay.in_na) * img;
             HIPCHK(h, hipMemcpyAsync(h->d_pyr + (size_t)index * h->lay.stride + h->lay.lv[0].off, in, img, hipMemcpyDeviceToDevice, h->stream));
         }
-        if (which == 3) { rpe_launch_blur(h, index); HIPCHK(h, hipGetLastError()); src = h->d_bufA; }
+        if (which == 3) { rpe_launch_debug_blur(h, index); HIPCHK(h, hipGetLastError()); src = h->d_bufA; }
         HIPCHK(h, hipMemcpyAsync(tmp.data(), src, tmp.size(), hipMemcpyDeviceToHost, h->stream));
         HIPCHK(h, hipStreamSynchronize(h->stream));
     }
@@ -1773,6 +1766,7 @@ extern "C" int rpe_calibrate_valu(rpe_handle *h, int kind, int waves_per_simd, d
     HIPCHK(h, hipSetDevice(h->cfg.device));
     hipDeviceProp_t prop;
     HIPCHK(h, hipGetDeviceProperties(&prop, h->cfg.device));
+    DM_ONCE(h, h->d_calib_sink, 1);
     const int ncu = prop.multiProcessorCount;
     // one 256-thread block = 4 waves = one wave per SIMD of a CU; waves_per_simd blocks per CU
     const int blocks = ncu * waves_per_simd, iters = 20000;
@@ -1782,7 +1776,7 @@ extern "C" int rpe_calibrate_valu(rpe_handle *h, int kind, int waves_per_simd, d
     for (int rep = 0; rep < 4; ++rep) {                    // first repetition warms up
         HIPCHK(h, hipEventRecord(e0, h->stream));
         switch (kind) {
-#define CALIB_CASE(K) case K: hipLaunchKernelGGL((valu_calib_kernel<K>), dim3(blocks), dim3(256), 0, h->stream, (unsigned *)h->d_hist, iters); break;
+#define CALIB_CASE(K) case K: hipLaunchKernelGGL((valu_calib_kernel<K>), dim3(blocks), dim3(256), 0, h->stream, h->d_calib_sink, iters); break;
             CALIB_CASE(0) CALIB_CASE(1) CALIB_CASE(2) CALIB_CASE(3) CALIB_CASE(4) CALIB_CASE(5) CALIB_CASE(6) CALIB_CASE(7)
             CALIB_CASE(8) CALIB_CASE(9) CALIB_CASE(10) CALIB_CASE(11) CALIB_CASE(12) CALIB_CASE(13) CALIB_CASE(14) CALIB_CASE(15)
 #undef CALIB_CASE
@@ -1814,12 +1808,13 @@ extern "C" int rpe_calibrate_hbm(rpe_handle *h, double *bytes_per_s)
     const size_t NIo = h->cfg.feature_method == RPE_FEATURE_SIFT ? 1 : (size_t)h->n_img_cap;
     const size_t bytes = NIo * (size_t)h->lay.stride;
     if (bytes < ((size_t)256 << 20)) { h->err = "rpe_calibrate_hbm: the handle's pyramid buffer is smaller than the 256 MiB Infinity Cache"; return RPE_ERR_INVALID; }
+    DM_ONCE(h, h->d_calib_sink, 1);
     hipEvent_t e0, e1;
     HIPCHK(h, hipEventCreate(&e0)); HIPCHK(h, hipEventCreate(&e1));
     float best = 1e30f;
     for (int rep = 0; rep < 4; ++rep) {
         HIPCHK(h, hipEventRecord(e0, h->stream));
-        hipLaunchKernelGGL(calib_read16_kernel, dim3(8192), dim3(256), 0, h->stream, (const uint4 *)h->d_pyr, bytes / 16, (unsigned *)h->d_hist);
+        hipLaunchKernelGGL(calib_read16_kernel, dim3(8192), dim3(256), 0, h->stream, (const uint4 *)h->d_pyr, bytes / 16, h->d_calib_sink);
         HIPCHK(h, hipEventRecord(e1, h->stream));
         HIPCHK(h, hipEventSynchronize(e1));
         float ms = 0.f;

@@ -20,12 +20,16 @@
 #define RPE_RESULT_SECTIONS 5
 static const size_t kRpeResultElem[RPE_RESULT_SECTIONS] = {9 * sizeof(double), 3 * sizeof(double), sizeof(int), sizeof(int), sizeof(int)};
 #define RPE_RESULT_BYTES 108     // their sum
-// FAST tile = 64 x FAST_TH output pixels, FAST_TH * 4 threads.  Unlike the resize kernel (latency bound: smaller tiles
-// won), FAST is bound by instruction issue and 32-row tiles with two waves only add halo work: 4.43 -> 4.79 ms.
-#ifndef FAST_TH
-#define FAST_TH 64
-#endif
-#define RPE_FAST_TILE_CAP (FAST_TH * 16) // entries of one FAST tile list = the most strict 3x3 maxima a 64 x FAST_TH tile can hold
+// ---- the one ORB configuration: what the host tables (rpe_api.hip) and the kernels (orb_kernels.hip) share ----
+// FAST tile = 64 x FAST_TH output pixels, 4 waves.  FAST is bound by instruction issue, not by latency like the resize
+// kernel, and 32-row tiles with two waves only added halo work when they were tried: 4.43 -> 4.79 ms.
+constexpr int FAST_TH = 64;
+constexpr int RPE_FAST_TILE_CAP = 1024;   // entries of one FAST tile list: the most strict 3x3 maxima a 64 x 64 tile can hold (32 x 32)
+// Resize tile = PYR_TW x PYR_TH destination pixels, one wave; its source window in the level below is PYR_ROWS rows of
+// PYR_DW dwords (336 B = 21 16-byte loads, origin aligned down to 16 B).  build_tables checks every tile of a handle
+// against the window at create time.  Why this shape: see pyr_resize_kernel.
+constexpr int PYR_TW = 256, PYR_TH = 16;
+constexpr int PYR_DW = 84, PYR_ROWS = 23;
 
 // ---- HBM layout of one image's pyramid-shaped buffers ---------------------
 // Level l is stored with row pitch align16(w_l) at byte offset off[l] (256-B
@@ -163,24 +167,8 @@ RPE_WAVE_SCAN(wave_inclusive_min, RPE_OP_MIN, 0x7FFFFFFF)
 __device__ __forceinline__ int wave_sum(int v) { return __builtin_amdgcn_readlane(wave_inclusive_sum(v), 63); }
 
 struct RpeTile { short level, tx, ty, pad; };
-// PYR_TW x PYR_TH destination tile of the resize kernel: destination origin and origin of its source window in the level below
+// destination tile of the resize kernel: its origin and the origin of its source window in the level below
 struct RpePyrTile { short x0, y0, a0, sy0; };
-// destination tile 256 x 16, ONE wave per tile: a lane computes 4 columns x 2 groups of 8 rows.  Small one-wave tiles put
-// many independent windows (7.7 KB each) on a CU -- the phases of a tile overlap only through other workgroups: 64-row
-// tiles of two waves 1.89 ms, 128 x 32 of one wave 1.68 -- and the longer the contiguous rows the better the mixed read /
-// write stream runs: 64-wide 1.82, 128-wide 1.67, 256 x 16 1.64 ms (partial tiles at the right edge idle lanes, which a
-// memory-bound kernel does not feel)
-#ifndef PYR_TH
-#define PYR_TH 16
-#endif
-#ifndef PYR_TW
-#define PYR_TW 256                   // destination tile width
-#endif
-#define PYR_DW (PYR_TW == 256 ? 84 : PYR_TW == 128 ? 44 : 24)   // window row in dwords: 336 B = 21 x 16-B loads (origin aligned down to 16 B); 176 B / 96 B for 128- / 64-wide tiles
-#ifndef PYR_THREADS
-#define PYR_THREADS (PYR_TW / 4 * PYR_TH / 16)   // PYR_TW / 4 column groups x PYR_TH / 16 row-group pairs
-#endif
-#define PYR_ROWS (PYR_TH == 64 ? 74 : PYR_TH == 16 ? 23 : 39)   // source rows staged per tile (checked against the tables at create time)
 
 // per-pair RANSAC state in HBM
 struct RpeRansacState {
@@ -245,19 +233,16 @@ struct rpe_handle {
     RpeDeviceLayout lay{};
     int n_img_cap = 0;              // 2*max_batch
     // tile tables
-    RpeTile *d_tiles_full = nullptr;  int n_tiles_full = 0;   // 64x16 tiles covering every level
     RpeTile *d_tiles_fast = nullptr;  int n_tiles_fast = 0;   // tiles covering [28,w-28)x[28,h-28)
     int *d_coef = nullptr;            // resize coefficient tables
     RpePyrTile *d_pyr_tiles = nullptr;  // resize tiles of levels 1..11, level l at pyr_tile_off[l], raster order
     int pyr_tile_off[RPE_NLEVELS] = {}, pyr_tile_cnt[RPE_NLEVELS] = {};
     // image-shaped buffers
     uint8_t *d_pyr = nullptr;
-    uint8_t *d_bufA = nullptr;        // ONE image's blurred pyramid (rpe_orb_debug_fetch only)
     unsigned *d_tile_list = nullptr;  // [img][n_tiles_fast][RPE_FAST_TILE_CAP] score << 24 | y << 12 | x
     int *d_tile_cnt = nullptr;        // [img][n_tiles_fast]
     uint8_t *d_stage1 = nullptr, *d_stage2 = nullptr; // staging for host-image API
     // detection
-    unsigned *d_hist = nullptr;       // [img][level][256]
     unsigned *d_corner = nullptr;     // [img][corner_total] raster-ordered FAST corners of a level: score << 24 | y << 12 | x
     int *d_corner_count = nullptr;    // [img][level]
     int *d_kp_lvl_count = nullptr;    // [img][level] keypoints kept per level (head of the level's candidate run)
@@ -267,11 +252,13 @@ struct rpe_handle {
     unsigned *d_kp_xy = nullptr;      // [img][kcap]  x | y<<12 | level<<24
     float *d_kp_resp = nullptr, *d_kp_angle = nullptr;
     float2 *d_kp_pt = nullptr;
-    float2 *d_kp_cs = nullptr;        // [img][kcap] (cos, sin) of the keypoint angle
     int *d_kp_count = nullptr;        // [img]
     unsigned *d_ovf = nullptr;        // [img] RPE_OVF_* capacity flags of the last extraction
     int level0_slots = 0;             // image slots of the last ORB run (debug fetch of an in-place level 0)
     uint8_t *d_desc = nullptr;        // [img][kcap][32]
+    // debug fetch only: rpe_orb_debug_fetch(which = 3) blurs whole levels of ONE image with blur_kernel
+    RpeTile *d_tiles_full = nullptr;  int n_tiles_full = 0;   // 64 x 64 tiles covering every level
+    uint8_t *d_bufA = nullptr;        // that image's blurred pyramid
     // matching
     int *d_m_q = nullptr, *d_m_t = nullptr, *d_m_d = nullptr, *d_m_n = nullptr;
     unsigned long long *d_m_best = nullptr;   // L2 matcher: [pair][kcap] per train: packed (f32 dist bits << 18 | queryIdx) of its nearest query
@@ -332,6 +319,7 @@ struct rpe_handle {
     rpe_camera *d_batch_cams = nullptr;   // [2*max_batch] cameras of a camera batch / stage call: cam1[0, B) then cam2[0, B) (created on first use)
     std::vector<rpe_camera> h_batch_cams; // their host staging
     // profiling
+    unsigned *d_calib_sink = nullptr;     // one word the rpe_calibrate_* kernels name as their output and never write (created on first use)
     bool profiling = false;
     hipEvent_t ev[RPE_STAGE_COUNT + 1] = {};
     bool ev_valid = false;
@@ -369,13 +357,11 @@ static inline RpeRun rpe_run_list(const rpe_handle *h, int P, RpeCamSrc cam = {n
 // ---- kernel launchers (defined in the .hip files) --------------------------
 void rpe_launch_pyramid(rpe_handle *h, int n_img);
 void rpe_launch_fast(rpe_handle *h, int n_img);
-void rpe_launch_nms(rpe_handle *h, int n_img);
-void rpe_launch_select(rpe_handle *h, int n_img);
+void rpe_launch_raster_retain(rpe_handle *h, int n_img);
 void rpe_launch_harris(rpe_handle *h, int n_img);
 void rpe_launch_keypoints(rpe_handle *h, int n_img);
-void rpe_launch_angle(rpe_handle *h, int n_img);
-void rpe_launch_blur(rpe_handle *h, int n_img);
-void rpe_launch_describe(rpe_handle *h, int n_img);
+void rpe_launch_orient_describe(rpe_handle *h, int n_img);
+void rpe_launch_debug_blur(rpe_handle *h, int img);
 void rpe_launch_match(rpe_handle *h, const RpeRun &r);
 void rpe_launch_match_l2(rpe_handle *h, const RpeRun &r);
 void rpe_launch_l2_norms(rpe_handle *h, int n_img);

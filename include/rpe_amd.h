@@ -391,6 +391,42 @@ enum { RPE_LINK_OK = 0, RPE_LINK_PAIR_FAILED = 1, RPE_LINK_TOO_FEW = 2 };
 int rpe_scale_links(rpe_handle *h, int L, const int32_t *pair_a, const int32_t *pair_b, const int32_t *side,
                     int min_shared, double *stats, int32_t *n_shared, int32_t *code);
 
+/* ------------------------------------------------------- guided matching */
+/* Matches of the last batch / stream / pair list again, under the epipolar gate of a pose (guided matching; NOT in the
+ * reference, whose only match rule is the brute-force crossCheck): the mutual nearest neighbour among the keypoint
+ * pairs that are consistent with (R, t).  Hamming handles only (ORB + RPE_NORM_HAMMING, either match_mode: the guided
+ * rule is always the mutual one).
+ * The rule, for a pair with pose (R, t), images 1 and 2, keypoints i < n1, j < n2 (n = min(count, capacity)); all
+ * arithmetic f64, no contraction:
+ *  1. x1_i = (x, y) = the f32 keypoint pixel of i normalised with the camera of image 1 as the geometry stages do it
+ *     (((double)p.x - cx) / fx, ((double)p.y - cy) / fy, then the undistortion of "camera models"); x2_j for image 2.
+ *  2. E = [t]x R: E[r][c] = t[(r+1)%3] * R[(r+2)%3][c] - t[(r+2)%3] * R[(r+1)%3][c].
+ *  3. per query i: l_k = (E[k][0]*x + E[k][1]*y) + E[k][2], k = 0, 1, 2; s1_i = l_0*l_0 + l_1*l_1.
+ *     per train j: m_k = (E[0][k]*x + E[1][k]*y) + E[2][k], k = 0, 1; s2_j = m_0*m_0 + m_1*m_1.
+ *  4. gate (Sampson, findEssentialMat's inlier test): v = (l_0*x2 + l_1*y2) + l_2; (i, j) is admissible iff
+ *     v*v <= thr2 * (s1_i + s2_j) and hamming(i, j) <= max_distance, thr = gate_px / f, thr2 = thr*thr, f = the focal
+ *     scale RANSAC uses ((fx + fy) / 2, or the mean of that over the pair's two cameras).  A comparison with a NaN is
+ *     false.
+ *  5. NNt(i) = the admissible j with the least (hamming, j), NNq(j) = the admissible i with the least (hamming, i);
+ *     (i, NNt(i)) is a match iff NNq(NNt(i)) == i.  Output: the matches sorted ascending by (hamming, i), the first
+ *     max_matches of them.
+ * With no effective gate (gate_px = 1e9, max_distance = 256) this is the crossCheck result bit for bit, and a
+ * crossCheck match that is admissible is always a guided match before truncation.
+ * R[B*9], t[B*3] (host): the poses to gate with -- refined poses, a prior from a trajectory -- and every pair is
+ * matched whatever its status.  R == t == NULL: the run's own poses; a pair whose status is not RPE_PAIR_OK then gets
+ * n_matches = 0.  The cameras are the run's own (its K, or the cameras of a *_cameras run).
+ * Outputs (host, any may be NULL), sized like the run's: qidx / tidx / dist [B*max_matches], pts1 / pts2
+ * [B*max_matches*2] (the keypoints the indices name), n_matches[B]; -1 (indices, dist) and zero (points) past
+ * n_matches[p].  The results live in buffers of their own: rpe_fetch_results, rpe_fetch_matched_points,
+ * rpe_fetch_match_indices, rpe_fetch_structure, rpe_refine_poses, rpe_scale_links and rpe_gather_poses return the same
+ * bits afterwards.  Bit-deterministic.
+ * Validity rules of rpe_fetch_structure: refused after a chunked host batch, a stage call, a put, once the store was
+ * resized under a pair list, and for B > pairs of the last run.  RPE_ERR_INVALID as well: an L2 handle, gate_px not
+ * finite or <= 0, max_distance outside 0 .. 256, a non-finite entry of R or t, exactly one of R, t NULL.  All checks
+ * are host-side; nothing is launched and the handle stays usable after a refusal. */
+int rpe_guided_matches(rpe_handle *h, int B, const double *R, const double *t, double gate_px, int max_distance,
+                       int32_t *qidx, int32_t *tidx, int32_t *dist, float *pts1, float *pts2, int32_t *n_matches);
+
 /* ---------------------------------------------------------- stage entry */
 /* replaces extractor.detectAndCompute(image, None) (pose_estimator.py:108)
  * for n_images images (n_images <= 2*max_batch).  kps[n_images*cap],
@@ -411,6 +447,15 @@ int64_t rpe_orb_pyramid_pixels(const rpe_handle *h);
 int rpe_match_hamming(rpe_handle *h, const uint8_t *h_desc1, const int32_t *n1,
                       const uint8_t *h_desc2, const int32_t *n2, int B,
                       int32_t *qidx, int32_t *tidx, int32_t *dist, int32_t *n_matches);
+
+/* stage form of rpe_guided_matches, the sibling of rpe_match_hamming: the caller's own features.  desc1 / desc2:
+ * B*cap*32 bytes, pts1 / pts2: B*cap*2 f32 keypoint pixels, n1 / n2: B counts; one K; R[B*9], t[B*3] required.
+ * Outputs sized B*max_matches, -1 past n_matches[p].  Goes through the workspace like every stage call (the last run's
+ * per-match results end here).  Same argument checks as rpe_guided_matches. */
+int rpe_match_hamming_guided(rpe_handle *h, const uint8_t *h_desc1, const float *h_pts1, const int32_t *n1,
+                             const uint8_t *h_desc2, const float *h_pts2, const int32_t *n2, int B,
+                             const double K[9], const double *R, const double *t, double gate_px, int max_distance,
+                             int32_t *qidx, int32_t *tidx, int32_t *dist, int32_t *n_matches);
 
 /* replaces cv2.SIFT_create().detectAndCompute(image, None) (pose_estimator.py:93-94, :108); the
  * handle must have been created with feature_method = RPE_FEATURE_SIFT, norm_type = RPE_NORM_L2.

@@ -49,6 +49,7 @@ EXPORTS = [
     "rpe_enqueue_batch_cameras_device", "rpe_estimate_batch_cameras_device", "rpe_estimate_batch_cameras",
     "rpe_undistort_points", "rpe_find_essential_cameras", "rpe_recover_pose_cameras", "rpe_refine_pose_points_cameras",
     "rpe_fetch_match_indices", "rpe_scale_links",
+    "rpe_guided_matches", "rpe_match_hamming_guided",
 ]
 
 
@@ -220,6 +221,10 @@ def load():
     lib.rpe_refine_pose_points_cameras.restype = C.c_int
     lib.rpe_fetch_match_indices.argtypes = [vp, C.c_int, i32p, i32p]; lib.rpe_fetch_match_indices.restype = C.c_int
     lib.rpe_scale_links.argtypes = [vp, C.c_int, i32p, i32p, i32p, C.c_int, vp, i32p, i32p]; lib.rpe_scale_links.restype = C.c_int
+    lib.rpe_guided_matches.argtypes = [vp, C.c_int, vp, vp, C.c_double, C.c_int, i32p, i32p, i32p, vp, vp, i32p]
+    lib.rpe_guided_matches.restype = C.c_int
+    lib.rpe_match_hamming_guided.argtypes = [vp, vp, vp, i32p, vp, vp, i32p, C.c_int, vp, vp, vp, C.c_double, C.c_int, i32p, i32p, i32p, i32p]
+    lib.rpe_match_hamming_guided.restype = C.c_int
     _lib = lib
     return lib
 
@@ -438,6 +443,52 @@ class Engine:
         stats = np.zeros((L, 3)); n = np.zeros(L, np.int32); code = np.zeros(L, np.int32)
         self._chk(self.lib.rpe_scale_links(self.h, L, _p(a), _p(b), _p(s), int(min_shared), _p(stats), _p(n), _p(code)))
         return stats, n, code
+
+    # ---- guided matching (rpe_guided_matches / rpe_match_hamming_guided; not in the reference)
+    def _poses(self, B, R, t):
+        if (R is None) != (t is None):
+            raise ValueError("guided matching: R and t must both be given or both be None")
+        if R is None:
+            return None, None
+        return (np.ascontiguousarray(np.asarray(R, np.float64).reshape(B, 9)),
+                np.ascontiguousarray(np.asarray(t, np.float64).reshape(B, 3)))
+
+    def guided_matches(self, B, R=None, t=None, gate_px=None, max_distance=256):
+        """Matches of the last batch / stream / pair list again under the epipolar gate of a pose (rpe_guided_matches):
+        the mutual nearest neighbour among the keypoint pairs within gate_px (Sampson, pixels; None = the handle's
+        ransac_threshold) of the pose and max_distance in Hamming distance.  R, t None: the run's own poses (pairs whose
+        status is not OK get no matches); otherwise R[B,3,3], t[B,3] to gate with, every pair matched.  Returns
+        (qidx, tidx, dist i32[B, mm], pts1, pts2 f32[B, mm, 2], n_matches i32[B]); -1 / zero past each pair's count.  The
+        run's own results are not modified."""
+        Rc, tc = self._poses(B, R, t)
+        mm = self.max_matches
+        q = np.zeros((B, mm), np.int32); ti = np.zeros_like(q); d = np.zeros_like(q); nm = np.zeros(B, np.int32)
+        p1 = np.zeros((B, mm, 2), np.float32); p2 = np.zeros_like(p1)
+        gate = float(self.cfg.ransac_threshold if gate_px is None else gate_px)
+        self._chk(self.lib.rpe_guided_matches(self.h, B, None if Rc is None else _p(Rc), None if tc is None else _p(tc), gate,
+                                              int(max_distance), _p(q), _p(ti), _p(d), _p(p1), _p(p2), _p(nm)))
+        return q, ti, d, p1, p2, nm
+
+    def match_hamming_guided(self, desc1, pts1, n1, desc2, pts2, n2, K, R, t, gate_px=None, max_distance=256):
+        """Stage form of guided_matches, the sibling of match_hamming: per pair the caller's descriptors (n, 32) u8 and
+        keypoint pixels (n, 2) f32 of both images, one K, the poses R[B,3,3], t[B,3].  Returns (qidx, tidx, dist,
+        n_matches)."""
+        B = len(n1)
+        d1 = np.zeros((B, self.kcap, 32), np.uint8); d2 = np.zeros_like(d1)
+        p1 = np.zeros((B, self.kcap, 2), np.float32); p2 = np.zeros_like(p1)
+        for i in range(B):
+            d1[i, :n1[i]] = desc1[i][:n1[i]]; d2[i, :n2[i]] = desc2[i][:n2[i]]
+            p1[i, :n1[i]] = pts1[i][:n1[i]]; p2[i, :n2[i]] = pts2[i][:n2[i]]
+        n1 = np.ascontiguousarray(n1, np.int32); n2 = np.ascontiguousarray(n2, np.int32)
+        K = np.ascontiguousarray(K, np.float64)
+        Rc, tc = self._poses(B, R, t)
+        mm = self.max_matches
+        q = np.zeros((B, mm), np.int32); ti = np.zeros_like(q); d = np.zeros_like(q); nm = np.zeros(B, np.int32)
+        gate = float(self.cfg.ransac_threshold if gate_px is None else gate_px)
+        self._chk(self.lib.rpe_match_hamming_guided(self.h, _p(d1), _p(p1), _p(n1), _p(d2), _p(p2), _p(n2), B, _p(K),
+                                                    None if Rc is None else _p(Rc), None if tc is None else _p(tc), gate,
+                                                    int(max_distance), _p(q), _p(ti), _p(d), _p(nm)))
+        return q, ti, d, nm
 
     # ---- frame store (rpe_frames_* / rpe_enqueue_pairs; not in the reference)
     def frames_reserve(self, n_slots):

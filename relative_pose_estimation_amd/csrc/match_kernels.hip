@@ -442,6 +442,286 @@ void rpe_launch_match(rpe_handle *h, const RpeRun &r)
     }
 }
 
+// ---------------------------------------------------------------- guided matching (rpe_guided_matches; NOT in the reference)
+// The crossCheck election again, but only among keypoint pairs (i, j) that pass the Sampson test of a given pose (the rule is
+// spelled out in include/rpe_amd.h).  A kernel family of its own next to match_hamming_mfma_kernel, whose instances stay the
+// code they are (the 1 % lesson at rpe_pair_slots).
+//
+// Everything of the gate that depends on one keypoint only is computed once per pair by guided_records_kernel, O(N), and
+// kept in HBM as one 32-byte record per keypoint:
+//   query i (image 1): (l_0, l_1, l_2, s1) -- its epipolar line E x1 in image 2 and l_0^2 + l_1^2
+//   train j (image 2): (x2, y2, s2, 0)     -- its normalised point and the squared norm of the first two rows of E^T x2
+// The cameras, the focal scale and the pose enter there and nowhere else: the tile kernel has no CAM switch.  thr2 of the
+// pair goes to g_thr2; NaN marks a pair that is not to be matched (status not OK under the run's own poses).
+template <bool TAB, bool CAM>
+__global__ __launch_bounds__(256) void guided_records_kernel(const int *__restrict__ kp_count, const float2 *__restrict__ kp_pt, int img2_base,
+                                                              const int2 *__restrict__ pair_tab, int kcap, const double *__restrict__ K,
+                                                              const RpeCamSrc cam, const double *__restrict__ R, const double *__restrict__ t,
+                                                              const int *__restrict__ status, double gate_px,
+                                                              double4 *__restrict__ rec, double *__restrict__ g_thr2)
+{
+    const int pair = blockIdx.z, side = blockIdx.y, k = blockIdx.x * 256 + threadIdx.x;
+    int img1, img2;
+    rpe_pair_slots<TAB>(pair_tab, img2_base, pair, img1, img2);
+    const int img = side ? img2 : img1;
+    if (side == 0 && k == 0) {
+        const double thr = gate_px / rpe_pair_focal<CAM>(K, cam, pair);
+        g_thr2[pair] = (status && status[pair] != RPE_PAIR_OK) ? __builtin_nan("") : thr * thr;
+    }
+    if (k >= min(kp_count[img], kcap)) return;
+    // E = [t]x R, row by row
+    const double *Rp = R + 9 * pair, *tp = t + 3 * pair;
+    double E[3][3];
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) E[r][c] = tp[(r + 1) % 3] * Rp[((r + 2) % 3) * 3 + c] - tp[(r + 2) % 3] * Rp[((r + 1) % 3) * 3 + c];
+    const float2 p = kp_pt[(long long)img * kcap + k];
+    double x, y;
+    if (CAM) {
+        const rpe_camera *c1, *c2;
+        rpe_pair_cameras(cam, pair, c1, c2);
+        const rpe_camera *c = side ? c2 : c1;
+        const double2 q = rpe_camera_normalise(c, rpe_camera_has_lens(c), p);
+        x = q.x; y = q.y;
+    } else {
+        const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
+        x = ((double)p.x - cx) / fx; y = ((double)p.y - cy) / fy;
+    }
+    double4 o;
+    if (side == 0) {
+        const double l0 = (E[0][0] * x + E[0][1] * y) + E[0][2], l1 = (E[1][0] * x + E[1][1] * y) + E[1][2], l2 = (E[2][0] * x + E[2][1] * y) + E[2][2];
+        o = make_double4(l0, l1, l2, l0 * l0 + l1 * l1);
+    } else {
+        const double m0 = (E[0][0] * x + E[1][0] * y) + E[2][0], m1 = (E[0][1] * x + E[1][1] * y) + E[2][1];
+        o = make_double4(x, y, m0 * m0 + m1 * m1, 0.);
+    }
+    rec[((long long)pair * 2 + side) * kcap + k] = o;
+}
+
+// The tile loop of match_hamming_mfma_kernel (same MFMA tile, key packing, two passes, SPLIT form) with the gate in the
+// epilogue.  The records of the 32 scanned rows of a tile travel with the tile: fetched MM_PF tiles ahead by wave 1 (64
+// 16-byte pieces), staged in LDS beside s_qpk; the owner lane keeps its own record in registers.  An accumulator entry is
+// gated only when its key would lower the column's running minimum -- min over the admissible keys either way, and the
+// f64 arithmetic (7 operations) runs for the few entries per column that are records so far.  Rows past the end and lanes
+// without an owner carry NaN records: never admissible, so a column without an admissible entry keeps 0xFFFFFFFF and
+// elects nobody.  max_distance is applied to the elected key: the nearest admissible neighbour is beyond it exactly when
+// every admissible one is.
+template <bool SPLIT, bool TAB>
+__global__ __launch_bounds__(MM_NT) void match_guided_mfma_kernel(const uint8_t *__restrict__ desc, const int *__restrict__ kp_count,
+                                                                   const float2 *__restrict__ kp_pt, int img2_base, const int2 *__restrict__ pair_tab, int kcap,
+                                                                   int max_matches, int max_distance, int region0,
+                                                                   const double4 *__restrict__ g_rec, const double *__restrict__ g_thr2,
+                                                                   unsigned *__restrict__ g_best, unsigned *__restrict__ g_row,
+                                                                   int *__restrict__ m_q, int *__restrict__ m_t, int *__restrict__ m_d,
+                                                                   int *__restrict__ m_n, float2 *__restrict__ pts1, float2 *__restrict__ pts2)
+{
+    extern __shared__ uint4 s_dyn[];
+    // [0, region0 x 16 B): the crossCheck kernel's staging (16 KB of expanded tiles, 256 B of packed words), 2 KB of scanned
+    // records, the popcounts; reused as the sort-key array afterwards.  Then kcap election words and kcap own-nearest words.
+    v4i_t *s_a = (v4i_t *)s_dyn;                               // [2][8][64]
+    unsigned *s_qpk = (unsigned *)(s_dyn + 2 * 8 * 64);        // [2][32]
+    double2 *s_rec = (double2 *)(s_dyn + 2 * 8 * 64 + 16);     // [2][32][2]
+    unsigned short *s_qpop = (unsigned short *)(s_dyn + 2 * 8 * 64 + 16 + 128);
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, pair = blockIdx.x;
+    unsigned *s_best = SPLIT ? g_best + (long long)pair * kcap : (unsigned *)(s_dyn + region0);
+    unsigned *s_row = SPLIT ? g_row + (long long)pair * kcap : s_best + kcap;
+    __shared__ int s_valid;
+    int img1, img2;
+    rpe_pair_slots<TAB>(pair_tab, img2_base, pair, img1, img2);
+    const double thr2 = g_thr2[pair];
+    const bool run = thr2 == thr2;                             // NaN: the pair is not matched
+    const int n1 = run ? min(kp_count[img1], kcap) : 0, n2 = run ? min(kp_count[img2], kcap) : 0;
+    if (!SPLIT) for (int i = tid; i < n1; i += MM_NT) { s_best[i] = 0xFFFFFFFFu; s_row[i] = 0xFFFFFFFEu; }      // SPLIT: the host memsets them
+    if (tid == 0) s_valid = 0;
+    const int h = lane >> 5, col = lane & 31;
+    const int xs = tid >> 6, xl = tid & 63, xrow = xl & 31, xh = xl >> 5;
+    const bool rec_loader = wv == 1;                           // piece (row lane >> 1, half lane & 1) of a tile's 32 records
+    const double qnan = __builtin_nan("");
+#pragma unroll 1
+    for (int pass = 0; pass < 2; ++pass) {
+    const int n_own = pass ? n1 : n2, n_scan = pass ? n2 : n1;
+    const unsigned *q32 = (const unsigned *)(desc + (long long)(pass ? img2 : img1) * kcap * 32);      // scanned: 8 dwords per descriptor
+    const uint4 *d2 = (const uint4 *)(desc + (long long)(pass ? img1 : img2) * kcap * 32);             // owners
+    const double2 *rec_scan = (const double2 *)(g_rec + ((long long)pair * 2 + (pass ? 1 : 0)) * kcap);
+    const double4 *rec_own = g_rec + ((long long)pair * 2 + (pass ? 0 : 1)) * kcap;
+    __syncthreads();                                           // the previous pass is done with s_qpop
+    for (int i = tid; i < n_scan; i += MM_NT) {
+        const uint4 a = ((const uint4 *)q32)[2 * i], b = ((const uint4 *)q32)[2 * i + 1];
+        s_qpop[i] = (unsigned short)(512u + __popc(a.x) + __popc(a.y) + __popc(a.z) + __popc(a.w) + __popc(b.x) + __popc(b.y) + __popc(b.z) + __popc(b.w));
+    }
+    const int ntq = (n_scan + 31) >> 5, ntt = (n_own + 31) >> 5;
+    for (int tt0 = SPLIT ? 8 * (int)blockIdx.y : 0; tt0 < ntt && n_scan > 0; tt0 += SPLIT ? 8 * (int)gridDim.y : 8) {
+        const int tt = tt0 + wv;                               // wave-uniform
+        const int j = tt * 32 + col;
+        const bool valid_t = tt < ntt && j < n_own;
+        v4i_t bop[8];
+        int tpop = 0;
+        {
+            uint4 t0 = make_uint4(0, 0, 0, 0), t1 = t0;
+            if (valid_t) { t0 = d2[2 * j]; t1 = d2[2 * j + 1]; }
+            const unsigned tw[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
+#pragma unroll
+            for (int sK = 0; sK < 8; ++sK) { bop[sK] = expand16((tw[sK] >> (16 * h)) & 0xFFFFu); tpop += __popc(tw[sK]); }
+        }
+        // the owner's record: pass 0 a train (x2, y2, s2, 0), pass 1 a query (l_0, l_1, l_2, s1)
+        const double4 own = valid_t ? rec_own[j] : make_double4(qnan, qnan, qnan, qnan);
+        unsigned best_key = 0xFFFFFFFFu;
+        unsigned ring[MM_PF];
+        double2 ring_rec[MM_PF];
+        auto fetch = [&](int qt) -> unsigned {
+            const int q = qt * 32 + xrow;
+            return (qt < ntq && q < n_scan) ? q32[(long long)q * 8 + xs] : 0u;
+        };
+        auto fetch_rec = [&](int qt) -> double2 {
+            const int q = qt * 32 + (lane >> 1);
+            return (rec_loader && qt < ntq && q < n_scan) ? rec_scan[(long long)q * 2 + (lane & 1)] : make_double2(qnan, qnan);
+        };
+        auto stage = [&](int qt, int buf, unsigned raw, const double2 &rr) {
+            s_a[(buf * 8 + xs) * 64 + xl] = expand16((raw >> (16 * xh)) & 0xFFFFu);
+            if (tid < 32) {
+                const int qq = qt * 32 + tid;
+                const unsigned pk = qq < n_scan ? (unsigned)s_qpop[qq] : 0x7000u;
+                s_qpk[buf * 32 + tid] = (pk << 16) | (unsigned)qq;
+            }
+            if (rec_loader) s_rec[buf * 64 + lane] = rr;
+        };
+        __syncthreads();                                       // the previous round has finished reading both buffers (and s_qpop is complete)
+#pragma unroll
+        for (int u = 0; u < MM_PF; ++u) { ring[u] = fetch(u); ring_rec[u] = fetch_rec(u); }
+        stage(0, 0, ring[0], ring_rec[0]);
+        ring[0] = fetch(MM_PF); ring_rec[0] = fetch_rec(MM_PF);
+        __syncthreads();
+        for (int qt0 = 0; qt0 < ntq; qt0 += MM_PF) {
+#pragma unroll
+            for (int u = 0; u < MM_PF; ++u) {
+                const int qt = qt0 + u;
+                if (qt < ntq) {                                // workgroup-uniform
+                    const int buf = qt & 1;
+                    if (tt < ntt) {
+                        v16i_t acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+                        for (int sK = 0; sK < 8; ++sK)
+                            acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(s_a[(buf * 8 + sK) * 64 + lane], bop[sK], acc, 0, 0, 0);
+                        // C layout (dtype independent): column = lane & 31, row of register r = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) {
+                            const int row = buf * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
+                            const unsigned key = (unsigned)__mul24(acc[r], -131072) + s_qpk[row];
+                            if (key < best_key) {
+                                const double2 ra = s_rec[2 * row], rb = s_rec[2 * row + 1];
+                                // v from the query's line in both passes; s1 + s2 in that order
+                                double v, ss;
+                                if (pass == 0) { v = (ra.x * own.x + ra.y * own.y) + rb.x; ss = rb.y + own.z; }
+                                else           { v = (own.x * ra.x + own.y * ra.y) + own.z; ss = own.w + rb.x; }
+                                if (v * v <= thr2 * ss) best_key = key;
+                            }
+                        }
+                    }
+                    if (qt + 1 < ntq) {
+                        stage(qt + 1, buf ^ 1, ring[(u + 1) % MM_PF], ring_rec[(u + 1) % MM_PF]);
+                        ring[(u + 1) % MM_PF] = fetch(qt + 1 + MM_PF); ring_rec[(u + 1) % MM_PF] = fetch_rec(qt + 1 + MM_PF);
+                    }
+                    __syncthreads();
+                }
+            }
+        }
+        best_key = min(best_key, (unsigned)__shfl_xor((int)best_key, 32));
+        if (valid_t && h == 0 && best_key != 0xFFFFFFFFu) {
+            const unsigned d = (best_key >> 16) - 512u + (unsigned)tpop, i = best_key & 0xFFFFu;
+            if ((int)d <= max_distance) {
+                if (pass == 0) atomicMin(&s_best[i], (d << 18) | (unsigned)j);      // train j elects query i
+                else s_row[j] = (d << 18) | i;                                      // query j's own nearest admissible train i
+            }
+        }
+    }
+    }
+    __syncthreads();
+    if (SPLIT) return;                                         // match_hamming_select_kernel sorts and emits
+    // (dist, queryIdx) keys; unmatched queries sort to the end -- same epilogue as the crossCheck kernel
+    int sortP = 64;
+    while (sortP < n1) sortP <<= 1;
+    unsigned *s_key = (unsigned *)s_dyn;
+    int myvalid = 0;
+    for (int i = tid; i < sortP; i += MM_NT) {
+        unsigned key = 0xFFFFFFFFu;
+        if (i < n1) {
+            unsigned b = s_best[i];
+            if (b != 0xFFFFFFFFu && b == s_row[i]) { key = ((b >> 18) << 16) | (unsigned)i; ++myvalid; }
+        }
+        s_key[i] = key;
+    }
+    if (myvalid) atomicAdd(&s_valid, myvalid);
+    __syncthreads();
+    for (int k = 2; k <= sortP; k <<= 1) {
+        for (int jj = k >> 1; jj > 0; jj >>= 1) {
+            for (int t = tid; t < (sortP >> 1); t += MM_NT) {
+                int i = 2 * jj * (t / jj) + (t % jj);
+                int ixj = i + jj;
+                bool asc = (i & k) == 0;
+                unsigned a = s_key[i], b = s_key[ixj];
+                if ((a > b) == asc) { s_key[i] = b; s_key[ixj] = a; }
+            }
+            __syncthreads();
+        }
+    }
+    const int nm = min(s_valid, max_matches);
+    for (int r = tid; r < nm; r += MM_NT) {
+        unsigned key = s_key[r];
+        int i = key & 0xFFFF, d = key >> 16;
+        int j = s_best[i] & 0x3FFFF;
+        long long o = (long long)pair * max_matches + r;
+        m_q[o] = i; m_t[o] = j; m_d[o] = d;
+        pts1[o] = kp_pt[(long long)img1 * kcap + i];
+        pts2[o] = kp_pt[(long long)img2 * kcap + j];
+    }
+    if (tid == 0) m_n[pair] = nm;
+}
+
+// Guided matches of run r under the poses d_R / d_t (d_status: the run's own poses, pairs that are not OK are skipped; nullptr:
+// every pair) into the d_gm_* buffers.  The election words of the HBM form are the crossCheck matcher's d_hm_*, scratch of one
+// launch sequence there as here.
+void rpe_launch_guided(rpe_handle *h, const RpeRun &r, const double *d_R, const double *d_t, const int *d_status, double gate_px, int max_distance)
+{
+    const int kcap = h->lay.kcap, B = r.pairs, mm = h->cfg.max_matches;
+    const RpeFeatSrc &f = r.feat;
+    // -1 / zero past n_matches
+    hipMemsetAsync(h->d_gm_q, 0xFF, sizeof(int) * (size_t)B * mm, h->stream);
+    hipMemsetAsync(h->d_gm_t, 0xFF, sizeof(int) * (size_t)B * mm, h->stream);
+    hipMemsetAsync(h->d_gm_d, 0xFF, sizeof(int) * (size_t)B * mm, h->stream);
+    hipMemsetAsync(h->d_gm_pts1, 0, sizeof(float2) * (size_t)B * mm, h->stream);
+    hipMemsetAsync(h->d_gm_pts2, 0, sizeof(float2) * (size_t)B * mm, h->stream);
+    const bool cam = r.cam.cams != nullptr;
+    auto records = f.tab ? (cam ? guided_records_kernel<true, true> : guided_records_kernel<true, false>)
+                         : (cam ? guided_records_kernel<false, true> : guided_records_kernel<false, false>);
+    hipLaunchKernelGGL(records, dim3((kcap + 255) / 256, 2, B), dim3(256), 0, h->stream,
+                       f.count, f.pt, f.img2_base, f.tab, kcap, (const double *)h->d_K, r.cam, d_R, d_t, d_status, gate_px,
+                       h->d_gm_rec, h->d_gm_thr2);
+    // LDS regions and the choice of the HBM form: as rpe_launch_match, with 2 KB of records in the first region
+    int sortP = 64;
+    while (sortP < kcap) sortP <<= 1;
+    const size_t r0 = (std::max((size_t)(2 * 8 * 64 + 16 + 128) * 16 + (size_t)kcap * 2, (size_t)sortP * 4) + 15) / 16;
+    const int rounds = ((kcap + 31) / 32 + 7) / 8;
+    const bool lds_fits = r0 * 16 + (size_t)kcap * 8 <= 65536;
+    const int split = B <= RPE_MATCH_SPLIT_PAIRS ? std::min(rounds, std::max(1, 256 / B)) : 1;
+    if (split > 1 || !lds_fits) {
+        hipMemsetAsync(h->d_hm_best, 0xFF, sizeof(unsigned) * (size_t)B * kcap, h->stream);
+        hipMemsetAsync(h->d_hm_row, 0xFE, sizeof(unsigned) * (size_t)B * kcap, h->stream);
+        launch_tab(f.tab, match_guided_mfma_kernel<true, true>, match_guided_mfma_kernel<true, false>, dim3(B, split), dim3(MM_NT), r0 * 16, h->stream,
+                           f.desc, f.count, f.pt, f.img2_base, f.tab, kcap, mm, max_distance, (int)r0,
+                           (const double4 *)h->d_gm_rec, (const double *)h->d_gm_thr2,
+                           h->d_hm_best, h->d_hm_row, h->d_gm_q, h->d_gm_t, h->d_gm_d, h->d_gm_n, h->d_gm_pts1, h->d_gm_pts2);
+        launch_tab(f.tab, match_hamming_select_kernel<true>, match_hamming_select_kernel<false>, dim3(B), dim3(MM_NT), (size_t)sortP * 4, h->stream,
+                           (const unsigned *)h->d_hm_best, (const unsigned *)h->d_hm_row, f.count, f.pt,
+                           f.img2_base, f.tab, kcap, mm,
+                           h->d_gm_q, h->d_gm_t, h->d_gm_d, h->d_gm_n, h->d_gm_pts1, h->d_gm_pts2);
+    } else
+        launch_tab(f.tab, match_guided_mfma_kernel<false, true>, match_guided_mfma_kernel<false, false>, dim3(B), dim3(MM_NT), r0 * 16 + (size_t)kcap * 8, h->stream,
+                           f.desc, f.count, f.pt, f.img2_base, f.tab, kcap, mm, max_distance, (int)r0,
+                           (const double4 *)h->d_gm_rec, (const double *)h->d_gm_thr2,
+                           (unsigned *)nullptr, (unsigned *)nullptr, h->d_gm_q, h->d_gm_t, h->d_gm_d, h->d_gm_n, h->d_gm_pts1, h->d_gm_pts2);
+}
+
 // ===================================================================== L2 (SIFT)
 // cv2.BFMatcher(NORM_L2, crossCheck=True) on SIFT descriptors (pose_estimator.py:94,:127-131).
 // SIFT descriptors are integer-valued 0..255 (saturate_cast<uchar> in calcSIFTDescriptor), so

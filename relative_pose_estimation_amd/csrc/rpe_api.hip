@@ -1036,6 +1036,99 @@ extern "C" int rpe_refine_poses(rpe_handle *h, int B, int max_iters, double *R, 
     return refine_run(h, last_run_first(h, B), max_iters, true, R, t, inliers, info, rms);
 }
 
+// ---------------------------------------------------------------- guided matching
+// rpe_guided_matches / rpe_match_hamming_guided (NOT in the reference): the mutual-nearest-neighbour match again, among the
+// keypoint pairs that pass the Sampson gate of a pose.  Results go to the d_gm_* buffers; nothing of the run is written.
+static int guided_check(rpe_handle *h, const char *who, int B, const double *R, const double *t, double gate_px, int max_distance)
+{
+    const std::string w(who);
+    if (h->cfg.norm_type != RPE_NORM_HAMMING) { h->err = w + ": Hamming handles only (ORB with RPE_NORM_HAMMING)"; return RPE_ERR_INVALID; }
+    if (!std::isfinite(gate_px) || !(gate_px > 0.)) { h->err = w + ": gate_px must be finite and > 0"; return RPE_ERR_INVALID; }
+    if (max_distance < 0 || max_distance > 256) { h->err = w + ": max_distance must be 0 ... 256"; return RPE_ERR_INVALID; }
+    if ((R == nullptr) != (t == nullptr)) { h->err = w + ": R and t must both be given or both be NULL"; return RPE_ERR_INVALID; }
+    if (R) {
+        bool fin = true;
+        for (int i = 0; i < 9 * B; ++i) fin = fin && std::isfinite(R[i]);
+        for (int i = 0; i < 3 * B; ++i) fin = fin && std::isfinite(t[i]);
+        if (!fin) { h->err = w + ": a pose has a non-finite entry"; return RPE_ERR_INVALID; }
+    }
+    return RPE_OK;
+}
+
+static int guided_alloc(rpe_handle *h)
+{
+    const size_t MB = (size_t)h->cfg.max_batch, cap = MB * h->cfg.max_matches;
+    DM_ONCE(h, h->d_gm_q, cap); DM_ONCE(h, h->d_gm_t, cap); DM_ONCE(h, h->d_gm_d, cap); DM_ONCE(h, h->d_gm_n, MB);
+    DM_ONCE(h, h->d_gm_pts1, cap); DM_ONCE(h, h->d_gm_pts2, cap);
+    DM_ONCE(h, h->d_gm_R, MB * 9); DM_ONCE(h, h->d_gm_tr, MB * 3); DM_ONCE(h, h->d_gm_thr2, MB);
+    DM_ONCE(h, h->d_gm_rec, MB * 2 * h->lay.kcap);
+    return RPE_OK;
+}
+
+// poses up (R == nullptr: the run's own, and its status words), launch, fetch
+static int guided_run(rpe_handle *h, const RpeRun &r, const double *R, const double *t, double gate_px, int max_distance,
+                      int32_t *qidx, int32_t *tidx, int32_t *dist, float *pts1, float *pts2, int32_t *n_matches)
+{
+    const size_t B = (size_t)r.pairs, n = B * h->cfg.max_matches;
+    if (R) {
+        HIPCHK(h, hipMemcpyAsync(h->d_gm_R, R, sizeof(double) * 9 * B, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->d_gm_tr, t, sizeof(double) * 3 * B, hipMemcpyHostToDevice, h->stream));
+    }
+    rpe_launch_guided(h, r, R ? h->d_gm_R : h->d_R, R ? h->d_gm_tr : h->d_t, R ? (const int *)nullptr : (const int *)h->d_status, gate_px, max_distance);
+    HIPCHK(h, hipGetLastError());
+    if (qidx) HIPCHK(h, hipMemcpyAsync(qidx, h->d_gm_q, sizeof(int) * n, hipMemcpyDeviceToHost, h->stream));
+    if (tidx) HIPCHK(h, hipMemcpyAsync(tidx, h->d_gm_t, sizeof(int) * n, hipMemcpyDeviceToHost, h->stream));
+    if (dist) HIPCHK(h, hipMemcpyAsync(dist, h->d_gm_d, sizeof(int) * n, hipMemcpyDeviceToHost, h->stream));
+    if (pts1) HIPCHK(h, hipMemcpyAsync(pts1, h->d_gm_pts1, sizeof(float2) * n, hipMemcpyDeviceToHost, h->stream));
+    if (pts2) HIPCHK(h, hipMemcpyAsync(pts2, h->d_gm_pts2, sizeof(float2) * n, hipMemcpyDeviceToHost, h->stream));
+    if (n_matches) HIPCHK(h, hipMemcpyAsync(n_matches, h->d_gm_n, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));       // also: the poses have left the caller's arrays
+    return RPE_OK;
+}
+
+extern "C" int rpe_guided_matches(rpe_handle *h, int B, const double *R, const double *t, double gate_px, int max_distance,
+                                  int32_t *qidx, int32_t *tidx, int32_t *dist, float *pts1, float *pts2, int32_t *n_matches)
+{
+    if (!h || B < 1 || B > h->cfg.max_batch) return RPE_ERR_INVALID;
+    int rc = guided_check(h, "rpe_guided_matches", B, R, t, gate_px, max_distance);
+    if (rc) return rc;
+    // the features of the run must still be where it read them (a stage call or a put overwrote the workspace's) and, under
+    // the run's own poses, d_R / d_t / d_status its results
+    rc = last_run_check(h, "rpe_guided_matches", B, "rpe_guided_matches: the last host batch ran in chunks: features are kept for unchunked and device-resident batches only", true);
+    if (rc) return rc;
+    if (h->last.kind == RpeLastRun::LIST && h->last.tab.size() < (size_t)2 * B) { h->err = "rpe_guided_matches: the frame store was resized since the pair list"; return RPE_ERR_INVALID; }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if ((rc = guided_alloc(h)) != RPE_OK) return rc;
+    return guided_run(h, last_run_first(h, B), R, t, gate_px, max_distance, qidx, tidx, dist, pts1, pts2, n_matches);
+}
+
+extern "C" int rpe_match_hamming_guided(rpe_handle *h, const uint8_t *h_desc1, const float *h_pts1, const int32_t *n1,
+                                        const uint8_t *h_desc2, const float *h_pts2, const int32_t *n2, int B,
+                                        const double K[9], const double *R, const double *t, double gate_px, int max_distance,
+                                        int32_t *qidx, int32_t *tidx, int32_t *dist, int32_t *n_matches)
+{
+    if (!h || !h_desc1 || !h_pts1 || !n1 || !h_desc2 || !h_pts2 || !n2 || !K || !R || !t || B < 1) return RPE_ERR_INVALID;
+    if (B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return RPE_ERR_CAPACITY; }
+    int rc = guided_check(h, "rpe_match_hamming_guided", B, R, t, gate_px, max_distance);
+    if (rc) return rc;
+    const size_t kcap = (size_t)h->lay.kcap;
+    for (int i = 0; i < B; ++i) if (n1[i] < 0 || n2[i] < 0 || n1[i] > (int)kcap || n2[i] > (int)kcap) {
+        h->err = "descriptor count exceeds keypoint capacity"; return RPE_ERR_INVALID;
+    }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if ((rc = guided_alloc(h)) != RPE_OK) return rc;
+    last_run_end(h);                            // overwrites the workspace's features
+    if ((rc = set_K(h, K)) != RPE_OK) return rc;
+    // pair p on the workspace slots (p, B + p), like every stage call
+    HIPCHK(h, hipMemcpyAsync(h->d_desc, h_desc1, kcap * 32 * B, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_desc + kcap * 32 * B, h_desc2, kcap * 32 * B, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_kp_pt, h_pts1, sizeof(float2) * kcap * B, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_kp_pt + kcap * B, h_pts2, sizeof(float2) * kcap * B, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_kp_count, n1, sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_kp_count + B, n2, sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
+    return guided_run(h, rpe_run_batch(h, B), R, t, gate_px, max_distance, qidx, tidx, dist, nullptr, nullptr, n_matches);
+}
+
 // ---------------------------------------------------------------- frame store
 // rpe_frames_* / rpe_enqueue_pairs (NOT in the reference): extraction separated from pairing.  A put extracts n frames in
 // the workspace slots [0, n) exactly as a stream does and one scatter kernel moves what the matchers and the status test

@@ -290,6 +290,13 @@ struct rpe_handle {
     double *d_link_stats = nullptr;       // [link][3] lower quartile, median, upper quartile
     int *d_link_n = nullptr, *d_link_code = nullptr;
     bool link_lds_set = false;            // the kernel's dynamic-LDS limit has been raised for this handle's layout
+    // rpe_guided_matches / rpe_match_hamming_guided only (created on first use): match lists of their own, shaped like the
+    // run's d_m_* / d_pts*; the poses gated with when the caller supplies them; per pair and image one 32-byte record per
+    // keypoint [pair][2][kcap] and the squared threshold (see guided_records_kernel)
+    int *d_gm_q = nullptr, *d_gm_t = nullptr, *d_gm_d = nullptr, *d_gm_n = nullptr;
+    float2 *d_gm_pts1 = nullptr, *d_gm_pts2 = nullptr;
+    double *d_gm_R = nullptr, *d_gm_tr = nullptr, *d_gm_thr2 = nullptr;
+    double4 *d_gm_rec = nullptr;
     // results
     double *d_R = nullptr, *d_t = nullptr, *d_E = nullptr;
     int *d_inliers = nullptr, *d_status = nullptr;
@@ -365,6 +372,7 @@ void rpe_launch_debug_blur(rpe_handle *h, int img);
 void rpe_launch_match(rpe_handle *h, const RpeRun &r);
 void rpe_launch_match_l2(rpe_handle *h, const RpeRun &r);
 void rpe_launch_l2_norms(rpe_handle *h, int n_img);
+void rpe_launch_guided(rpe_handle *h, const RpeRun &r, const double *d_R, const double *d_t, const int *d_status, double gate_px, int max_distance);
 int rpe_sift_create(rpe_handle *h);
 void rpe_sift_destroy(rpe_handle *h);
 int rpe_sift_run(rpe_handle *h, const uint8_t *d_a, const uint8_t *d_b, int na, int nb);

@@ -475,6 +475,39 @@ class PoseEstimator:
                     refine_iters=int(rinfo[0, 1]), rms_before=float(rms[0, 0]), rms_after=float(rms[0, 1]))
         return info
 
+    def last_guided(self, R=None, t=None, gate_px=None, max_distance=256):
+        """Guided matches of the pairs of the last estimate / estimate_batch / estimate_sequence / estimate_pairs call
+        (of its last chunk when it ran in several; not in the reference; _capi.Engine.guided_matches): the mutual
+        nearest neighbours among the keypoint pairs within gate_px (Sampson distance in pixels, None = the
+        estimator's RANSAC threshold) of a pose.  R, t None: the call's own poses, pairs that failed get no matches;
+        R[B,3,3], t[B,3(,1)]: poses to gate with (refined poses, a prior from a trajectory), every pair matched.
+        Returns one dict per pair, arrays trimmed to the pair's guided count: 'qidx', 'tidx' (keypoint indices in image
+        1 / 2), 'dist' (Hamming), 'pts1', 'pts2' (n, 2) pixels.  ORB with NORM_HAMMING only (RpeError otherwise)."""
+        eng, B = self._last_engine, self._last_pairs
+        q, ti, d, p1, p2, nm = eng.guided_matches(B, R, t, gate_px, max_distance)
+        return [{'qidx': q[p, :nm[p]].copy(), 'tidx': ti[p, :nm[p]].copy(), 'dist': d[p, :nm[p]].copy(),
+                 'pts1': p1[p, :nm[p]].copy(), 'pts2': p2[p, :nm[p]].copy()} for p in range(B)]
+
+    def estimate_guided(self, img1, img2, gate_px=None, max_distance=256, refine_iters=10):
+        """estimate, then the guided matches at that pose (last_guided), then the non-linear refinement of the pose over
+        all of them (rpe_refine_pose_points with a mask of ones; not in the reference).  Returns a dict: 'R', 't' the
+        refined pose (the five-point pose when the refinement was skipped or rejected), 'R_initial', 't_initial',
+        'num_guided', 'pts1', 'pts2' (the guided matches), 'inliers' (cheirality count of the returned pose),
+        'refine_code' (_capi.REFINE_*), 'refine_iters', 'rms_before', 'rms_after'.  Raises what estimate raises."""
+        R0, t0 = self.estimate(img1, img2)
+        eng = self._last_engine
+        g = self.last_guided(gate_px=gate_px, max_distance=max_distance)[0]
+        n = len(g['qidx'])
+        ones = [np.ones(n, bool)]
+        if self._camera is not None:
+            R, t, inl, rinfo, rms = eng.refine_pose_points_cameras([R0], [t0], [g['pts1']], [g['pts2']], ones, self._camera,
+                                                                   self._camera, refine_iters)
+        else:
+            R, t, inl, rinfo, rms = eng.refine_pose_points([R0], [t0], [g['pts1']], [g['pts2']], ones, self.K, refine_iters)
+        return {'R': R[0], 't': t[0], 'R_initial': R0, 't_initial': t0, 'num_guided': n, 'pts1': g['pts1'], 'pts2': g['pts2'],
+                'inliers': int(inl[0]), 'refine_code': int(rinfo[0, 0]), 'refine_iters': int(rinfo[0, 1]),
+                'rms_before': float(rms[0, 0]), 'rms_after': float(rms[0, 1])}
+
     def close(self):
         for e in self._engines.values():
             e.close()

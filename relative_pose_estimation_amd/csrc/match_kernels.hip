@@ -12,7 +12,8 @@
 // (strict '<', ascending query => lowest index on ties) and every query keeps its best elector through a packed
 // (dist<<18 | trainIdx) LDS atomicMin (lowest train on ties); then every query finds its OWN nearest train (same
 // key, lowest train on ties) and the match survives only if that train elected the query -- the two keys are
-// equal exactly then.  (Rounds 1-2 ran the first pass only, the rule of older OpenCV: a superset.  The reference's
+// equal exactly then.  (The vector-ALU kernel below scans twice; the matrix-core kernel takes both elections from one
+// pass over the product tiles.)  (Rounds 1-2 ran the first pass only, the rule of older OpenCV: a superset.  The reference's
 // result rows single out the two-pass rule: tests/test_reference_rows_cpu.py.)
 // The stable sort by distance is a bitonic sort of (dist<<16 | queryIdx) keys in LDS.
 //
@@ -158,8 +159,14 @@ __global__ __launch_bounds__(256) void match_hamming_kernel(const uint8_t *__res
 // What is left for the vector ALU per tile is the O(N) bit -> byte expansion and a 2-instruction epilogue per
 // accumulator: key = ((|q| + 512) << 16 | queryIdx) - (q.t << 17) (one v_mad_i32_i24), running v_min_u32 per train
 // column -- the minimum of (distance, queryIdx) keys IS batchDistance's "strict <, ascending query" election.  The second
-// crossCheck pass (the query's own nearest train) is the same loop with the two descriptor sets swapped.
-// Workgroup = one pair, 8 waves; wave w owns train tile 8 p + w of pass p (its 32 descriptors expanded once into
+// crossCheck side (the query's own nearest train) reads the SAME accumulators: q.t is symmetric, so the tile that elects
+// along its columns elects along its rows too.  Row key = ((|t| + 512) << 16 | trainIdx) - (q.t << 17), one v_add on the
+// product already formed for the column key; its minimum over a row's 32 columns is a transpose reduction across the lanes
+// (row_min32: 39 vector instructions per tile), joined over the 8 waves and the rounds by one atomicMin per row into s_row.
+// (Until round 5 a second pass ran the same loop with the descriptor sets swapped: 16 MFMAs and 128 vector instructions
+// per tile pair where this form has 8 and 106; 0.52 -> 0.37 ms per 1024 pairs)  s_row holds the raw key; it
+// is converted to the election words' (dist << 18 | trainIdx) once per query, before the two are compared.
+// Workgroup = one pair, 8 waves; wave w owns train tile 8 p + w of round p (its 32 descriptors expanded once into
 // 32 VGPRs: the B operand of all 8 K-steps), the query tiles stream through LDS, expanded by all 512 threads
 // (16 bits -> 16 bytes: nibble * 0x00204081 & 0x01010101), double buffered: one barrier per query tile.
 typedef int v4i_t __attribute__((ext_vector_type(4)));
@@ -175,6 +182,39 @@ __device__ __forceinline__ v4i_t expand16(unsigned b)
     r.z = (int)(__umul24((b >> 8) & 15u, 0x00204081u) & 0x01010101u);
     r.w = (int)(__umul24((b >> 12) & 15u, 0x00204081u) & 0x01010101u);
     return r;
+}
+
+// Row election of one accumulator tile.  k[r] is this lane's key of row (r & 3) + 8 (r >> 2) + 4 (lane >> 5) at column
+// lane & 31; the result is the minimum over the 32 columns of row r = (lane & 31) >> 1 (both lanes of a pair hold it).
+// A transpose reduction: at each step a lane pair trades half of its live registers and keeps the minima of the other
+// half -- the lane whose column bit is set keeps the upper half -- so 16 registers become 8, 4, 2, 1 and the last step
+// joins the two lanes of a pair.  Column bit 4 goes through v_permlane16_swap (one swap leaves both operands' partners in
+// place: min of the pair), bits 3..0 through DPP row_ror:8, row_half_mirror, quad_perm [2,3,0,1] and [1,0,3,2]; every
+// partner differs in the step's bit and agrees in the bits of the steps before it, and the five masks 16, 8, 7, 2, 1
+// span the 32 columns.  8 + 8 + 3 (4 + 2 + 1) + 2 = 39 vector instructions, against 80 for five full rounds.
+#define MM_DPP_ROR8 0x128
+#define MM_DPP_HALF_MIRROR 0x141
+#define MM_DPP_XOR2 0x4E
+#define MM_DPP_XOR1 0xB1
+template <int CTRL>
+__device__ __forceinline__ unsigned min_dpp(unsigned x)
+{
+    return min(x, (unsigned)__builtin_amdgcn_mov_dpp((int)x, CTRL, 0xF, 0xF, true));
+}
+
+__device__ __forceinline__ unsigned row_min32(unsigned (&k)[16], bool c3, bool c2, bool c1)
+{
+#pragma unroll
+    for (int r = 0; r < 8; ++r) {
+        const auto sw = __builtin_amdgcn_permlane16_swap(k[r], k[r + 8], false, false);
+        k[r] = min((unsigned)sw[0], (unsigned)sw[1]);          // register r + 8 (column bit 4)
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) { const unsigned a = min_dpp<MM_DPP_ROR8>(k[r]), b = min_dpp<MM_DPP_ROR8>(k[r + 4]); k[r] = c3 ? b : a; }
+#pragma unroll
+    for (int r = 0; r < 2; ++r) { const unsigned a = min_dpp<MM_DPP_HALF_MIRROR>(k[r]), b = min_dpp<MM_DPP_HALF_MIRROR>(k[r + 2]); k[r] = c2 ? b : a; }
+    const unsigned a = min_dpp<MM_DPP_XOR2>(k[0]), b = min_dpp<MM_DPP_XOR2>(k[1]);
+    return min_dpp<MM_DPP_XOR1>(c1 ? b : a);
 }
 
 // SPLIT = true: small batches (the drop-in's estimate() is a batch of ONE pair: a single workgroup walked 2 x 127 x 127 tiles
@@ -195,32 +235,32 @@ __global__ __launch_bounds__(MM_NT) void match_hamming_mfma_kernel(const uint8_t
     unsigned *s_qpk = (unsigned *)(s_dyn + 2 * 8 * 64);        // [2][32]
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, pair = blockIdx.x;
     unsigned *s_best = SPLIT ? g_best + (long long)pair * kcap : (unsigned *)(s_dyn + region0);          // kcap entries
-    unsigned *s_row = SPLIT ? g_row + (long long)pair * kcap : s_best + kcap;     // kcap entries: the query's own nearest train (second crossCheck pass)
+    unsigned *s_row = SPLIT ? g_row + (long long)pair * kcap : s_best + kcap;     // kcap entries: the query's own nearest train, as the raw row key
     __shared__ int s_valid;
     int img1, img2;
     rpe_pair_slots<TAB>(pair_tab, img2_base, pair, img1, img2);
     const int n1 = min(kp_count[img1], kcap), n2 = min(kp_count[img2], kcap);
     if (!SPLIT) for (int i = tid; i < n1; i += MM_NT) { s_best[i] = 0xFFFFFFFFu; s_row[i] = 0xFFFFFFFEu; }      // SPLIT: the host memsets them
     if (tid == 0) s_valid = 0;
-    // |x| + 512 of every scanned descriptor, once per pass (the passes over the scanned tiles all need them); kept in the free
-    // part of the first 32 KB (kcap <= 8064 entries)
+    // |q| + 512 of every query, once (the rounds over the query tiles all need them, and so does the row key's conversion);
+    // kept in the free part of the first 32 KB (kcap <= 8064 entries)
     unsigned short *s_qpop = (unsigned short *)(s_dyn + 2 * 8 * 64 + 16);
     const int h = lane >> 5, col = lane & 31;
     // this thread's share of a scanned tile's expansion: item = tid: K-step s = tid >> 6, lane slot l = tid & 63
     // (row = l & 31, half = l >> 5): the 16 bits [32 s + 16 half, +16) of scanned descriptor (tile * 32 + row)
     const int xs = tid >> 6, xl = tid & 63, xrow = xl & 31, xh = xl >> 5;
-    // pass 0: the TRAINS own the MFMA columns and elect their nearest query (scanned through LDS);
-    // pass 1: the QUERIES own the columns and find their own nearest train -- the same loop with the roles swapped
-#pragma unroll 1
-    for (int pass = 0; pass < 2; ++pass) {
-    const int n_own = pass ? n1 : n2, n_scan = pass ? n2 : n1;
-    const unsigned *q32 = (const unsigned *)(desc + (long long)(pass ? img2 : img1) * kcap * 32);      // scanned: 8 dwords per descriptor
-    const uint4 *d2 = (const uint4 *)(desc + (long long)(pass ? img1 : img2) * kcap * 32);             // owners
-    __syncthreads();                                           // the previous pass is done with s_qpop
+    // the TRAINS own the MFMA columns and elect their nearest query (the queries are scanned through LDS): a minimum down
+    // each column, carried in best_key over the query tiles.  The same accumulators elect every query's own nearest train: a
+    // minimum along each row (row_min32), joined over the 8 waves and the rounds by an atomicMin on s_row.
+    const int n_own = n2, n_scan = n1;
+    const unsigned *q32 = (const unsigned *)(desc + (long long)img1 * kcap * 32);      // scanned: 8 dwords per descriptor
+    const uint4 *d2 = (const uint4 *)(desc + (long long)img2 * kcap * 32);             // owners
     for (int i = tid; i < n_scan; i += MM_NT) {
         const uint4 a = ((const uint4 *)q32)[2 * i], b = ((const uint4 *)q32)[2 * i + 1];
         s_qpop[i] = (unsigned short)(512u + __popc(a.x) + __popc(a.y) + __popc(a.z) + __popc(a.w) + __popc(b.x) + __popc(b.y) + __popc(b.z) + __popc(b.w));
     }
+    const bool c3 = (lane & 8) != 0, c2 = (lane & 4) != 0, c1 = (lane & 2) != 0;
+    const int rrow = ((col >> 1) & 3) + 8 * (col >> 3) + 4 * h;      // the row whose minimum row_min32 leaves in this lane
     const int ntq = (n_scan + 31) >> 5, ntt = (n_own + 31) >> 5;
     for (int tt0 = SPLIT ? 8 * (int)blockIdx.y : 0; tt0 < ntt && n_scan > 0; tt0 += SPLIT ? 8 * (int)gridDim.y : 8) {
         const int tt = tt0 + wv;                               // wave-uniform
@@ -237,6 +277,9 @@ __global__ __launch_bounds__(MM_NT) void match_hamming_mfma_kernel(const uint8_t
             for (int sK = 0; sK < 8; ++sK) { bop[sK] = expand16((tw[sK] >> (16 * h)) & 0xFFFFu); tpop += __popc(tw[sK]); }
         }
         unsigned best_key = 0xFFFFFFFFu;
+        // row key of this lane's column: (|t| + 512 - 2 q.t) << 16 | trainIdx; its minimum over the trains is the query's nearest
+        // train, lowest index on ties (|q| is the same along a row).  Columns past the end: a key no real distance can beat.
+        const unsigned tpk = ((valid_t ? (unsigned)tpop + 512u : 0x7000u) << 16) | (unsigned)j;
         // The raw scanned words are fetched MM_PF tiles ahead into a register ring: with a one-tile lookahead every step of
         // the loop waited for an L2 round trip (diagnostic build: the loop without its MFMAs took 0.17 of the kernel's
         // 0.35 ms -- 128 steps of 1.3 us).  The loop is unrolled by MM_PF so that the ring is indexed statically.
@@ -271,11 +314,17 @@ __global__ __launch_bounds__(MM_NT) void match_hamming_mfma_kernel(const uint8_t
                         for (int sK = 0; sK < 8; ++sK)
                             acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(s_a[(buf * 8 + sK) * 64 + lane], bop[sK], acc, 0, 0, 0);
                         // C layout (dtype independent): column = lane & 31, row of register r = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+                        unsigned rk[16];
 #pragma unroll
                         for (int r = 0; r < 16; ++r) {
                             const unsigned qpk = s_qpk[buf * 32 + (r & 3) + 8 * (r >> 2) + 4 * h];
-                            best_key = min(best_key, (unsigned)__mul24(acc[r], -131072) + qpk);     // (|x| + 512 - 2 x.own) << 16 | scannedIdx
+                            const unsigned prod = (unsigned)__mul24(acc[r], -131072);
+                            best_key = min(best_key, prod + qpk);                                   // (|q| + 512 - 2 q.t) << 16 | queryIdx
+                            rk[r] = prod + tpk;
                         }
+                        const unsigned rmin = row_min32(rk, c3, c2, c1);
+                        const int q = qt * 32 + rrow;
+                        if (!(col & 1) && q < n_scan) atomicMin(&s_row[q], rmin);                  // rows past the end write nothing
                     }
                     if (qt + 1 < ntq) {
                         // tile qt + 1 sits in ring slot (u + 1) % MM_PF (tile 0 of this round was staged in the prologue)
@@ -289,13 +338,18 @@ __global__ __launch_bounds__(MM_NT) void match_hamming_mfma_kernel(const uint8_t
         best_key = min(best_key, (unsigned)__shfl_xor((int)best_key, 32));
         if (valid_t && h == 0) {
             const unsigned d = (best_key >> 16) - 512u + (unsigned)tpop, i = best_key & 0xFFFFu;
-            if (pass == 0) atomicMin(&s_best[i], (d << 18) | (unsigned)j);      // train j elects query i
-            else s_row[j] = (d << 18) | i;                                      // query j's own nearest train i
+            atomicMin(&s_best[i], (d << 18) | (unsigned)j);                     // train j elects query i
         }
-    }
     }
     __syncthreads();
     if (SPLIT) return;
+    // the row keys in the election words' format, (dist << 18) | trainIdx: dist = (key >> 16) - 512 + |q|.  The initial value
+    // (no train at all) keeps a train index that no election word holds.
+    for (int i = tid; i < n1; i += MM_NT) {
+        const unsigned k = s_row[i];
+        s_row[i] = (((k >> 16) - 1024u + (unsigned)s_qpop[i]) << 18) | (k & 0xFFFFu);
+    }
+    __syncthreads();
     // (dist, queryIdx) keys; unmatched queries sort to the end -- same epilogue as the VALU kernel
     int sortP = 64;
     while (sortP < n1) sortP <<= 1;
@@ -337,9 +391,12 @@ __global__ __launch_bounds__(MM_NT) void match_hamming_mfma_kernel(const uint8_t
 }
 
 
-// sort + top-max_matches + point gather of a SPLIT run (one workgroup per pair; the same steps as the fused epilogue)
+// sort + top-max_matches + point gather of a SPLIT run (one workgroup per pair; the same steps as the fused epilogue).
+// raw_desc != nullptr: g_row holds match_hamming_mfma_kernel's raw row keys, converted here with |q| counted from the
+// descriptors; nullptr: it holds (dist << 18) | trainIdx words already (the guided matcher).
 template <bool TAB>
 __global__ __launch_bounds__(MM_NT) void match_hamming_select_kernel(const unsigned *__restrict__ g_best, const unsigned *__restrict__ g_row,
+                                                                      const uint8_t *__restrict__ raw_desc,
                                                                       const int *__restrict__ kp_count, const float2 *__restrict__ kp_pt,
                                                                       int img2_base, const int2 *__restrict__ pair_tab, int kcap, int max_matches,
                                                                       int *__restrict__ m_q, int *__restrict__ m_t, int *__restrict__ m_d,
@@ -362,8 +419,14 @@ __global__ __launch_bounds__(MM_NT) void match_hamming_select_kernel(const unsig
     for (int i = tid; i < sortP; i += MM_NT) {
         unsigned key = 0xFFFFFFFFu;
         if (i < n1) {
-            unsigned b = s_best[i];
-            if (b != 0xFFFFFFFFu && b == s_row[i]) { key = ((b >> 18) << 16) | (unsigned)i; ++myvalid; }
+            unsigned b = s_best[i], row = s_row[i];
+            if (raw_desc) {
+                const uint4 *q = (const uint4 *)(raw_desc + ((long long)img1 * kcap + i) * 32);
+                const uint4 a = q[0], c = q[1];
+                const unsigned pop = __popc(a.x) + __popc(a.y) + __popc(a.z) + __popc(a.w) + __popc(c.x) + __popc(c.y) + __popc(c.z) + __popc(c.w);
+                row = (((row >> 16) - 512u + pop) << 18) | (row & 0xFFFFu);
+            }
+            if (b != 0xFFFFFFFFu && b == row) { key = ((b >> 18) << 16) | (unsigned)i; ++myvalid; }
         }
         s_key[i] = key;
     }
@@ -427,12 +490,12 @@ void rpe_launch_match(rpe_handle *h, const RpeRun &r)
         const int split = B <= RPE_MATCH_SPLIT_PAIRS ? std::min(rounds, std::max(1, 256 / B)) : 1;
         if (split > 1 || !lds_fits) {
             hipMemsetAsync(h->d_hm_best, 0xFF, sizeof(unsigned) * (size_t)B * kcap, h->stream);
-            hipMemsetAsync(h->d_hm_row, 0xFE, sizeof(unsigned) * (size_t)B * kcap, h->stream);
+            hipMemsetAsync(h->d_hm_row, 0xFE, sizeof(unsigned) * (size_t)B * kcap, h->stream);     // above every row key; its train index is no one's
             launch_tab(f.tab, match_hamming_mfma_kernel<true, true>, match_hamming_mfma_kernel<true, false>, dim3(B, split), dim3(MM_NT), r0 * 16, h->stream,
                                f.desc, f.count, f.pt, f.img2_base, f.tab, kcap, h->cfg.max_matches, (int)r0,
                                h->d_hm_best, h->d_hm_row, h->d_m_q, h->d_m_t, h->d_m_d, h->d_m_n, h->d_pts1, h->d_pts2);
             launch_tab(f.tab, match_hamming_select_kernel<true>, match_hamming_select_kernel<false>, dim3(B), dim3(MM_NT), (size_t)sortP * 4, h->stream,
-                               (const unsigned *)h->d_hm_best, (const unsigned *)h->d_hm_row, f.count, f.pt,
+                               (const unsigned *)h->d_hm_best, (const unsigned *)h->d_hm_row, f.desc, f.count, f.pt,
                                f.img2_base, f.tab, kcap, h->cfg.max_matches,
                                h->d_m_q, h->d_m_t, h->d_m_d, h->d_m_n, h->d_pts1, h->d_pts2);
         } else
@@ -499,7 +562,8 @@ __global__ __launch_bounds__(256) void guided_records_kernel(const int *__restri
     rec[((long long)pair * 2 + side) * kcap + k] = o;
 }
 
-// The tile loop of match_hamming_mfma_kernel (same MFMA tile, key packing, two passes, SPLIT form) with the gate in the
+// The tile loop of match_hamming_mfma_kernel (same MFMA tile, key packing and SPLIT form; still one pass per crossCheck
+// side, the second with the descriptor sets swapped, writing (dist << 18 | index) row words) with the gate in the
 // epilogue.  The records of the 32 scanned rows of a tile travel with the tile: fetched MM_PF tiles ahead by wave 1 (64
 // 16-byte pieces), staged in LDS beside s_qpk; the owner lane keeps its own record in registers.  An accumulator entry is
 // gated only when its key would lower the column's running minimum -- min over the admissible keys either way, and the
@@ -712,7 +776,7 @@ void rpe_launch_guided(rpe_handle *h, const RpeRun &r, const double *d_R, const 
                            (const double4 *)h->d_gm_rec, (const double *)h->d_gm_thr2,
                            h->d_hm_best, h->d_hm_row, h->d_gm_q, h->d_gm_t, h->d_gm_d, h->d_gm_n, h->d_gm_pts1, h->d_gm_pts2);
         launch_tab(f.tab, match_hamming_select_kernel<true>, match_hamming_select_kernel<false>, dim3(B), dim3(MM_NT), (size_t)sortP * 4, h->stream,
-                           (const unsigned *)h->d_hm_best, (const unsigned *)h->d_hm_row, f.count, f.pt,
+                           (const unsigned *)h->d_hm_best, (const unsigned *)h->d_hm_row, (const uint8_t *)nullptr, f.count, f.pt,
                            f.img2_base, f.tab, kcap, mm,
                            h->d_gm_q, h->d_gm_t, h->d_gm_d, h->d_gm_n, h->d_gm_pts1, h->d_gm_pts2);
     } else

@@ -24,8 +24,9 @@
 __device__ float4 c_pattern_f[256];         // rBRIEF pattern (brief_pattern.inc) as f32 (x0, y0, x1, y1), uploaded at handle creation
 
 // the radius-15 intensity-centroid disc as packed-u8 dot-product weights: item (row v = -15..15, dword j = 0..7) covers
-// u = -16 + 4j .. +3; .x = 1 per in-disc byte, .y = (u + 16) per in-disc byte (0 elsewhere)
-__constant__ uint2 c_discw[31 * 8];
+// u = -16 + 4j .. +3; .x = 1 per in-disc byte, .y = (u + 16) per in-disc byte (0 elsewhere).  A 32nd row of zeros lets
+// orient_describe_kernel run its four rounds of 64 items without a bound on the last one.
+__constant__ uint2 c_discw[32 * 8];
 
 // taps of the descriptor blur: GaussianBlur(7x7, sigma 2) as cv2's sepFilter2D f32 route holds them -- (float)(exp(-x^2 / 8) / sum),
 // getGaussianKernel's normalised f64 kernel cast to f32 (computed on the host at handle creation, like the oracle does)
@@ -34,8 +35,8 @@ __constant__ float c_gauss[7];
 // the kernels' constant tables: disc weights (from the n (u, v) offsets of the disc), rBRIEF pattern, blur taps
 void rpe_orb_upload_constants(const signed char *disc, int n)
 {
-    uint2 wt[31 * 8];
-    for (int i = 0; i < 31 * 8; ++i) wt[i] = make_uint2(0u, 0u);
+    uint2 wt[32 * 8];
+    for (int i = 0; i < 32 * 8; ++i) wt[i] = make_uint2(0u, 0u);
     for (int i = 0; i < n; ++i) {
         const int u = disc[2 * i], v = disc[2 * i + 1];
         const int j = (u + 16) >> 2, b = (u + 16) & 3;
@@ -942,36 +943,49 @@ __global__ __launch_bounds__(64) void orient_describe_kernel(const uint8_t *__re
                                                                float *__restrict__ kp_angle, uint8_t *__restrict__ desc,
                                                                RpeDeviceLayout lay, int nb, int n_img)
 {
-    __shared__ __attribute__((aligned(16))) unsigned s_raw[1][KP_ROWS * KP_RAW_DW + 4];   // 16-B aligned rows of 48 B (+ one row pass over-read)
+    __shared__ __attribute__((aligned(16))) unsigned raw[KP_ROWS * KP_RAW_DW + 4];   // 16-B aligned rows of 48 B (+ one row pass over-read)
     // horizontally blurred patch, COLUMN-major f32 [column][row]: the 7 vertical taps of a steered sample are contiguous
-    __shared__ float s_hb[1][KP_HCOLS * KP_HSTRIDE];
-    // The indexing is written per wave of the workgroup (wave wv takes keypoint blk + wv and its own LDS arrays).  The
-    // workgroup is one wave, so wv == 0 and `active` below is true for every workgroup that gets past the return; the
-    // compiler learns that only late, and spelling it out changes the schedule and register allocation of the whole
-    // kernel (40 VGPRs for 45).  That is a kernel change to measure on its own, so the form stays.
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    __shared__ float hb[KP_HCOLS * KP_HSTRIDE];
+    // The workgroup is one wave and the keypoint depends on the workgroup index alone, so everything about the keypoint is
+    // wave-uniform.  The record is read through readfirstlane so that the compiler keeps it, the level's layout fields and
+    // the patch's base address in scalar registers: the patch loads take a scalar base and one 32-bit offset per lane.
+    // (The kernel used to index keypoint and LDS arrays by threadIdx.x >> 6, which hid the uniformity: the level's
+    // fields came through vector loads and every address was 64-bit vector arithmetic.)  Measured on its own, together with
+    // the row-paired blur pass below: 14 % fewer vector instructions executed and the same kernel time (2.91 -> 2.89 ms) --
+    // with 4 waves per SIMD the kernel waits on its memory round trips, which is why the loads below leave early
+    // (round 6 in DESIGN section 4).
+    const int lane = threadIdx.x;
     int img, blk;
     if (!xcd_image_block(nb, n_img, img, blk)) return;
-    const int k = blk + wv;
+    // the count and the record leave together (the record of a slot past the count is inside the array and is not used)
+    const long long g = (long long)img * lay.kcap + blk;
     const int nkp = kp_count[img];
+    const unsigned p = (unsigned)__builtin_amdgcn_readfirstlane((int)kp_xy[g]);
     if (blk >= nkp) return;                                           // the grid is sized for the keypoint capacity
-    const bool active = k < nkp;
-    const long long g = (long long)img * lay.kcap + (active ? k : 0);
-    const unsigned p = kp_xy[g];
     const int x0 = p & 0xFFF, y0 = (p >> 12) & 0xFFF, l = p >> 24;
     const RpeLevel &L = lay.lv[l];
     const int pitch = L.pitch;
     const int xal = (x0 - KP_R) & ~3, off0 = (x0 - KP_R) - xal;     // off0 in 0..3
-    unsigned *raw = s_raw[wv];
-    float *hb = s_hb[wv];
-    if (active) {
+    // The kernel runs 4 waves per SIMD (LDS) and its phases are dependent chains, so it pays for every memory round trip it
+    // does not overlap: the loads of the two constant tables go out right behind the patch loads instead of where their
+    // values are used (24 VGPRs held meanwhile; the kernel has 128 to spend).
+    uint2 wt[4];
+    float4 pf[4];
+    {
         const uint8_t *src = rpe_level_base(pyr, lay, img, l) + (long long)(y0 - KP_R) * pitch + xal;
-        // lane -> fixed dword column (lane % 12) and rows lane / 12 + 5 q (60 lanes x 9 loads = 45 x 12 dwords)
+        // lane -> fixed dword column (lane % 12) and rows lane / 12 + 5 q (60 lanes x 9 loads = 45 x 12 dwords), all loads in
+        // flight before the first LDS store.  Byte offsets inside the patch (< 45 pitch) are 32-bit.
         const int lc = lane % KP_RAW_DW, lr = lane / KP_RAW_DW;
         unsigned stage[9];
-        const uint8_t *col = src + 4 * lc;
+        if (lane < 60) {
+            const unsigned vo = 4u * (unsigned)lc + (unsigned)lr * (unsigned)pitch, p5 = 5u * (unsigned)pitch;
 #pragma unroll
-        for (int q = 0; q < 9; ++q) stage[q] = *(const unsigned *)(col + (long long)min(lr + 5 * q, KP_ROWS - 1) * pitch);
+            for (int q = 0; q < 9; ++q) stage[q] = *(const unsigned *)(src + (vo + (unsigned)q * p5));
+        }
+#pragma unroll
+        for (int q = 0; q < 4; ++q) wt[q] = c_discw[lane + 64 * q];
+#pragma unroll
+        for (int bit = 0; bit < 4; ++bit) pf[bit] = c_pattern_f[lane * 4 + bit];
         if (lane < 60) {
 #pragma unroll
             for (int q = 0; q < 9; ++q) raw[(lr + 5 * q) * KP_RAW_DW + lc] = stage[q];
@@ -979,27 +993,26 @@ __global__ __launch_bounds__(64) void orient_describe_kernel(const uint8_t *__re
     }
     __syncthreads();
     int m10 = 0, m01 = 0;
-    if (active) {
+    {
         // ---- orb.cpp ICAngles: integer moments over the disc, reduced with wave shuffles
-        // integer sums, so any summation order gives the oracle's moments: 4 disc pixels per packed-u8 dot product
+        // integer sums, so any summation order gives the oracle's moments: 4 disc pixels per packed-u8 dot product.
+        // Item = (v + 15) * 8 + j = lane + 64 q: a lane keeps its dword j = lane % 8 and takes rows v0 + 8 q, v0 = lane / 8 - 15,
+        // so the four items share one address and differ by constant offsets (the table's 32nd row is zero: row v = 16
+        // of the patch is read and weighs nothing).  The dot products chain their sums: c[q] = s1_0 + .. + s1_q, and
+        // sum_q (v0 + 8 q) s1_q = (v0 + 24) c[3] - 8 (c[0] + c[1] + c[2]).
         {
-            const unsigned *rw = raw + (KP_R - 15) * KP_RAW_DW;                  // patch row of v = -15
             const int bo = off0 + KP_R - 16;                                        // byte column of u = -16 (>= 6)
             const int sh = bo & 3;
+            const unsigned *pw = raw + ((KP_R - 15) + (lane >> 3)) * KP_RAW_DW + ((bo >> 2) + (lane & 7));
+            unsigned c[4], su = 0u;
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
-                const int it = lane + 64 * q;                                       // item = (v + 15) * 8 + j
-                if (it < 31 * 8) {
-                    const int vr = it >> 3, j = it & 7;
-                    const uint2 wt = c_discw[it];
-                    const unsigned *pw = rw + vr * KP_RAW_DW + ((bo >> 2) + j);
-                    const unsigned px = __builtin_amdgcn_alignbyte(pw[1], pw[0], sh);
-                    const int s1 = (int)__builtin_amdgcn_udot4(px, wt.x, 0u, false);
-                    const int su = (int)__builtin_amdgcn_udot4(px, wt.y, 0u, false);
-                    m10 += su - 16 * s1;
-                    m01 += (vr - 15) * s1;
-                }
+                const unsigned px = __builtin_amdgcn_alignbyte(pw[8 * q * KP_RAW_DW + 1], pw[8 * q * KP_RAW_DW], sh);
+                c[q] = __builtin_amdgcn_udot4(px, wt[q].x, q ? c[q - 1] : 0u, false);
+                su = __builtin_amdgcn_udot4(px, wt[q].y, su, false);
             }
+            m10 = (int)su - 16 * (int)c[3];
+            m01 = __mul24((lane >> 3) + 9, (int)c[3]) - 8 * (int)(c[0] + c[1] + c[2]);
         }
         // wave sums by DPP row shifts / broadcasts (total in lane 63, read back as a scalar): 12 + 2 instructions; six
         // rounds of __shfl_xor were 36 vector + 12 LDS (ds_bpermute) instructions
@@ -1010,53 +1023,55 @@ __global__ __launch_bounds__(64) void orient_describe_kernel(const uint8_t *__re
         // RowFilter<uchar, float>, SymmColumnFilter<Cast<float, uchar>>), whose AVX2-dispatched build fuses s += f * x: the
         // reference's own result rows single this out against every fixed-point variant (tests/test_reference_rows_cpu.py).
         // Row pass: s = g0 p[x-3]; s = fma(g_k, p[x-3+k], s), k = 1..6, in that order.  hbuf column j <-> x = x0 - 19 + j.
-        // Item = (patch row, group of 8 columns): 45 x 5 items, 20 raw bytes each, shared by the item's 8 outputs.
+        // Item = (two patch rows r, r + 1, group of 8 columns), 2 x 20 raw bytes shared by the item's 2 x 8 outputs.  Round 0:
+        // rows (0,1) .. (22,23), 12 pairs x 5 groups on 60 lanes; round 1: rows (23,24) .. (43,44), 11 pairs on 55 lanes, so
+        // a lane's second item sits a constant 23 rows below its first and nothing is clamped (row 23 is computed twice, to
+        // the same value).
         {
             const float g0 = c_gauss[0], g1 = c_gauss[1], g2 = c_gauss[2], g3 = c_gauss[3];
+            const int rp = lane / 5, cg = lane - 5 * rp;
 #pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int it = lane + 64 * q;
-                if (it < KP_ROWS * 5) {
-                    const int row = it / 5, cg = it - 5 * row;
+            for (int q = 0; q < 2; ++q) {
+                if (lane < (q == 0 ? 60 : 55)) {
+                    const int row = 2 * rp + (KP_ROWS / 2 + 1) * q;
                     const unsigned *pw = raw + row * KP_RAW_DW + 2 * cg;
-                    const unsigned d0 = pw[0], d1 = pw[1], d2 = pw[2], d3 = pw[3], d4 = pw[4];
-                    const unsigned q0 = __builtin_amdgcn_alignbyte(d1, d0, off0), q1 = __builtin_amdgcn_alignbyte(d2, d1, off0),
-                                   q2 = __builtin_amdgcn_alignbyte(d3, d2, off0), q3 = __builtin_amdgcn_alignbyte(d4, d3, off0);
-                    // two outputs per v_pk_mul_f32 / v_pk_fma_f32 (each half an IEEE fma of its own: same bits as the scalar
-                    // form).  A packed operand is an aligned register pair, so the converted pixels are kept twice: pairs
-                    // starting at even bytes (fe) and at odd bytes (fo); output pair (o, o + 1), tap k reads pair o + k.
-                    typedef float v2f_t __attribute__((ext_vector_type(2)));
-                    const unsigned qq[4] = {q0, q1, q2, q3};
-                    v2f_t fe[8], fo[7];
+                    unsigned qq[2][4];
 #pragma unroll
-                    for (int e = 0; e < 8; ++e) {
-                        const unsigned w = qq[e >> 1] >> (16 * (e & 1));
-                        fe[e] = (v2f_t){(float)(w & 255u), (float)((w >> 8) & 255u)};
+                    for (int h = 0; h < 2; ++h) {
+                        const unsigned *ph = pw + h * KP_RAW_DW;
+                        const unsigned d0 = ph[0], d1 = ph[1], d2 = ph[2], d3 = ph[3], d4 = ph[4];
+                        qq[h][0] = __builtin_amdgcn_alignbyte(d1, d0, off0); qq[h][1] = __builtin_amdgcn_alignbyte(d2, d1, off0);
+                        qq[h][2] = __builtin_amdgcn_alignbyte(d3, d2, off0); qq[h][3] = __builtin_amdgcn_alignbyte(d4, d3, off0);
                     }
+                    // two outputs per v_pk_mul_f32 / v_pk_fma_f32 (each half an IEEE fma of its own: same bits as the scalar
+                    // form).  A packed operand is an aligned register pair; pairing the two ROWS of a column, F[j] = (byte j
+                    // of row r, byte j of row r + 1), lets each v_cvt_f32_ubyteN write its half in place and tap k of
+                    // output column o read F[o + k] as it stands.  (Pairing two columns of one row needed every converted
+                    // pixel twice, at even and at odd pair alignment, and register moves to build the second set.)
+                    typedef float v2f_t __attribute__((ext_vector_type(2)));
+                    v2f_t F[14];
 #pragma unroll
-                    for (int e = 0; e < 7; ++e) fo[e] = (v2f_t){fe[e].y, fe[e + 1].x};
+                    for (int j = 0; j < 14; ++j)
+                        F[j] = (v2f_t){(float)((qq[0][j >> 2] >> (8 * (j & 3))) & 255u), (float)((qq[1][j >> 2] >> (8 * (j & 3))) & 255u)};
                     float *dst = hb + (8 * cg) * KP_HSTRIDE + row;
                     const v2f_t G0 = {g0, g0}, G1 = {g1, g1}, G2 = {g2, g2}, G3 = {g3, g3};
 #pragma unroll
-                    for (int o = 0; o < 8; o += 2) {
-                        // pair j = o + k: even j -> fe[j / 2], odd j -> fo[(j - 1) / 2]
-                        auto P = [&](int j) -> v2f_t { return (j & 1) ? fo[(j - 1) >> 1] : fe[j >> 1]; };
-                        v2f_t sacc = G0 * P(o);
-                        sacc = __builtin_elementwise_fma(G1, P(o + 1), sacc);
-                        sacc = __builtin_elementwise_fma(G2, P(o + 2), sacc);
-                        sacc = __builtin_elementwise_fma(G3, P(o + 3), sacc);
-                        sacc = __builtin_elementwise_fma(G2, P(o + 4), sacc);      // the kernel is symmetric: g4 = g2, g5 = g1, g6 = g0 (same f32 values)
-                        sacc = __builtin_elementwise_fma(G1, P(o + 5), sacc);
-                        sacc = __builtin_elementwise_fma(G0, P(o + 6), sacc);
-                        dst[o * KP_HSTRIDE] = sacc.x;
-                        dst[(o + 1) * KP_HSTRIDE] = sacc.y;
+                    for (int o = 0; o < 8; ++o) {
+                        v2f_t sacc = G0 * F[o];
+                        sacc = __builtin_elementwise_fma(G1, F[o + 1], sacc);
+                        sacc = __builtin_elementwise_fma(G2, F[o + 2], sacc);
+                        sacc = __builtin_elementwise_fma(G3, F[o + 3], sacc);
+                        sacc = __builtin_elementwise_fma(G2, F[o + 4], sacc);      // the kernel is symmetric: g4 = g2, g5 = g1, g6 = g0 (same f32 values)
+                        sacc = __builtin_elementwise_fma(G1, F[o + 5], sacc);
+                        sacc = __builtin_elementwise_fma(G0, F[o + 6], sacc);
+                        dst[o * KP_HSTRIDE] = sacc.x;                               // adjacent dwords: one ds_write2_b32
+                        dst[o * KP_HSTRIDE + 1] = sacc.y;
                     }
                 }
             }
         }
     }
     __syncthreads();
-    if (!active) return;
     // the angle, on wave-uniform values
     float a, b;
     {
@@ -1069,27 +1084,36 @@ __global__ __launch_bounds__(64) void orient_describe_kernel(const uint8_t *__re
     }
     // ---- orb.cpp computeOrbDescriptors: lane = 4 consecutive bit tests, vertical pass at the samples
     const float2 pt = kp_pt[g];
-    const float sc = 1.f / L.scale;
+    const float sc = L.inv_scale;                                 // 1.f / L.scale, divided once on the host
     const int cx = __float2int_rn(pt.x * sc), cy = __float2int_rn(pt.y * sc);
     const int dxo = cx - x0 + 19, dyo = cy - y0 + KP_R - 3;       // (cx,cy) == (x0,y0) in practice
+    // the sample (0, 0), wave-uniform, in a scalar register.  The empty asm hides its value: left to itself the compiler moves the
+    // constant part (19 columns + 19 rows = 3800 B) into the offset fields of the LDS reads, where it does not fit (ds_read2_b32
+    // reaches 1020 B), and adds it back three times per sample
+    int o00 = __builtin_amdgcn_readfirstlane(dxo * KP_HSTRIDE + dyo);
+    asm volatile("" : "+s"(o00));
+    const float *hb0 = hb + o00;
     const float g3 = c_gauss[3], g4 = c_gauss[4], g5 = c_gauss[5], g6 = c_gauss[6];
     unsigned nib = 0;
 #pragma unroll
     for (int bit = 0; bit < 4; ++bit) {
-        const float4 pf = c_pattern_f[lane * 4 + bit];
-        const float p0 = pf.x, p1 = pf.y, p2 = pf.z, p3 = pf.w;
+        const float p0 = pf[bit].x, p1 = pf[bit].y, p2 = pf[bit].z, p3 = pf[bit].w;
         float fx0 = p0 * a - p1 * b, fy0 = p0 * b + p1 * a;
         float fx1 = p2 * a - p3 * b, fy1 = p2 * b + p3 * a;
         float t01[2];
-        const int ixs[2] = {__float2int_rn(fx0), __float2int_rn(fx1)}, iys[2] = {__float2int_rn(fy0), __float2int_rn(fy1)};
+        // cvRound of both coordinates, then the sample's offset ix * KP_HSTRIDE + iy in f32: whole numbers below 2^24, so
+        // the fused multiply-add is exact and one conversion gives the integer the two conversions and a multiply gave
+        const float rxs[2] = {__builtin_rintf(fx0), __builtin_rintf(fx1)}, rys[2] = {__builtin_rintf(fy0), __builtin_rintf(fy1)};
 #pragma unroll
         for (int e = 0; e < 2; ++e) {
             // vertical pass at the sample only: the 7 taps = rows iy + dyo .. + 6 of column ix + dxo, contiguous f32;
             // s = g3 c; s = fma(g_{3+k}, t[3+k] + t[3-k], s), k = 1..3 (SymmColumnFilter), then cvRound (saturate_cast<uchar>)
-            const float *t = hb + (ixs[e] + dxo) * KP_HSTRIDE + (iys[e] + dyo);
+            const float *t = hb0 + (int)__builtin_fmaf(rxs[e], (float)KP_HSTRIDE, rys[e]);
+            typedef float v2f_t __attribute__((ext_vector_type(2)));
+            const v2f_t s45 = (v2f_t){t[4], t[5]} + (v2f_t){t[2], t[1]};     // two of the three tap sums in one v_pk_add_f32
             float sacc = g3 * t[3];
-            sacc = __builtin_fmaf(g4, t[4] + t[2], sacc);
-            sacc = __builtin_fmaf(g5, t[5] + t[1], sacc);
+            sacc = __builtin_fmaf(g4, s45.x, sacc);
+            sacc = __builtin_fmaf(g5, s45.y, sacc);
             sacc = __builtin_fmaf(g6, t[6] + t[0], sacc);
             t01[e] = __builtin_rintf(sacc);                           // 0 <= value <= 255 (convex combination of bytes): no saturation to apply
         }

@@ -43,6 +43,7 @@ struct RpeLevel {
     int kcap2;        // capacity of the candidate list after retainBest(2 quota) (FAST-score ties extend it): 4 quota + 256
     int cand_off;     // offset of this level inside per-image candidate arrays
     float scale;      // (float)pow(1.1f, l)
+    float inv_scale;  // 1.f / scale (orb.cpp's inv_scale: the level size and the keypoint's level coordinates come from it)
     long long off;    // byte offset inside the per-image pyramid buffer
     int coef_off;     // offset of xo/xa (w entries) then yo/ya (h entries) in the HOST coefficient table
     int dcoef_off;    // device table: [align128(w) packed x][align64(h) packed y], 16-B aligned, last entry replicated

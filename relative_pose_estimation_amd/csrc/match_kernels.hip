@@ -21,8 +21,16 @@
 // crossCheck, pose_estimator.py:131): cv2's knnMatch(k=2) + Lowe's ratio test.  Roles swap: a lane owns a QUERY
 // descriptor, the TRAIN descriptors stream through LDS; the lane keeps its best (distance, lowest train index) and
 // second-best distance and emits the match iff  best < ratio * second  (compared in f64, as Python compares
-// m.distance < ratio * n.distance); queries with fewer than two candidates emit nothing.  Sort / truncation /
-// point gather are shared.
+// m.distance < ratio * n.distance); queries with fewer than two candidates emit nothing.
+//
+// What the file shares.  Every matcher -- the vector-ALU kernel, the fused matrix-core and guided kernels, the Hamming and
+// the L2 select kernels -- ends in ONE tail, select_sort_emit<NT, Key>: keys from the election words, their count, the
+// bitonic sort, the first max_matches ranks with the point gather (MatchOut), m_n.  A caller states only which query
+// survives (the ratio flag, best == row, the raw row key's conversion, nn_q[nn_t[i]] == i) and where its train index is.
+// The two matrix-core Hamming kernels (crossCheck, guided) share popc256, fill_qpop and load_owner but keep their own tile
+// loops (the lesson at rpe_pair_slots), and ONE launch plan, rpe_hamming_plan: the LDS regions, the split over workgroups
+// and whether the election words live in LDS (fused kernel) or in HBM (tile kernel + match_hamming_select_kernel) are decided
+// there, for both launchers (launch_hamming_plan) and for the allocation of the HBM words (rpe_api.hip).
 #include "rpe_internal.h"
 #include <stdlib.h>
 #include <algorithm>
@@ -37,6 +45,79 @@ __device__ __forceinline__ int ham256(const uint4 &a0, const uint4 &a1, const ui
     return d;
 }
 
+__device__ __forceinline__ unsigned popc256(const uint4 &a, const uint4 &b)
+{
+    return __popc(a.x) + __popc(a.y) + __popc(a.z) + __popc(a.w) + __popc(b.x) + __popc(b.y) + __popc(b.z) + __popc(b.w);
+}
+
+// ---------------------------------------------------------------- the tail of every matcher
+// Where the matches of one pair go: its max_matches output rows and the keypoints of its two images
+template <typename Dist>
+struct MatchOut {
+    int *q, *t;
+    Dist *d;
+    float2 *p1, *p2;
+    const float2 *kp1, *kp2;
+    __device__ MatchOut(int pair, int max_matches, int img1, int img2, int kcap, const float2 *kp_pt,
+                        int *m_q, int *m_t, Dist *m_d, float2 *pts1, float2 *pts2)
+    {
+        const long long o = (long long)pair * max_matches;
+        q = m_q + o; t = m_t + o; d = m_d + o; p1 = pts1 + o; p2 = pts2 + o;
+        kp1 = kp_pt + (long long)img1 * kcap; kp2 = kp_pt + (long long)img2 * kcap;
+    }
+    __device__ void put(int r, int i, int j, Dist dist) const
+    {
+        q[r] = i; t[r] = j; d[r] = dist;
+        p1[r] = kp1[i]; p2[r] = kp2[j];
+    }
+};
+
+// One workgroup of NT threads: the sort key of every query i < n1 from key_of(i) -- (distance << 16 | i), or all ones for
+// "no match", which sorts to the end -- a bitonic sort of the next power of two (>= 64) of keys in s_key (ascending: the
+// stable sort by distance, the query index breaks ties), then emit(r, i, key) for the first min(valid, max_matches) ranks
+// and their number to *n_out.  It opens with a barrier: what the workgroup wrote before the call is visible to key_of, and
+// s_key may alias LDS that was read until then -- but nothing that key_of itself reads.
+template <int NT, typename Key, typename KeyOf, typename Emit>
+__device__ __forceinline__ void select_sort_emit(Key *s_key, int n1, int max_matches, int *n_out, KeyOf key_of, Emit emit)
+{
+    __shared__ int s_valid;
+    constexpr Key NONE = ~(Key)0;
+    const int tid = threadIdx.x;
+    if (tid == 0) s_valid = 0;
+    __syncthreads();
+    int sortP = 64;
+    while (sortP < n1) sortP <<= 1;
+    int myvalid = 0;
+    for (int i = tid; i < sortP; i += NT) {
+        Key key = NONE;
+        if (i < n1) { key = key_of(i); if (key != NONE) ++myvalid; }
+        s_key[i] = key;
+    }
+    if (myvalid) atomicAdd(&s_valid, myvalid);
+    __syncthreads();
+    for (int k = 2; k <= sortP; k <<= 1) {
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            for (int t = tid; t < (sortP >> 1); t += NT) {
+                int i = 2 * j * (t / j) + (t % j);
+                int ixj = i + j;
+                bool asc = (i & k) == 0;
+                Key a = s_key[i], b = s_key[ixj];
+                if ((a > b) == asc) { s_key[i] = b; s_key[ixj] = a; }
+            }
+            __syncthreads();
+        }
+    }
+    const int nm = min(s_valid, max_matches);
+    for (int r = tid; r < nm; r += NT) {
+        const Key key = s_key[r];
+        emit(r, (int)(key & 0xFFFF), key);
+    }
+    if (tid == 0) *n_out = nm;
+}
+
+// The Hamming matchers' sort key of query i from its election word b = (dist << 18 | trainIdx)
+__device__ __forceinline__ unsigned ham_sort_key(unsigned b, int i) { return ((b >> 18) << 16) | (unsigned)i; }
+
 template <bool RATIO, bool TAB>
 __global__ __launch_bounds__(256) void match_hamming_kernel(const uint8_t *__restrict__ desc, const int *__restrict__ kp_count,
                                                              const float2 *__restrict__ kp_pt, int img2_base, const int2 *__restrict__ pair_tab, int kcap,
@@ -48,13 +129,11 @@ __global__ __launch_bounds__(256) void match_hamming_kernel(const uint8_t *__res
     uint4 *s_q = s_dyn;                                   // QTILE*2 uint4 = 32 KB (later: sort keys)
     unsigned *s_best = (unsigned *)(s_dyn + QTILE * 2);   // kcap entries
     unsigned *s_row = s_best + kcap;                      // kcap entries: the query's own nearest train (second crossCheck pass)
-    __shared__ int s_valid;
     const int tid = threadIdx.x, pair = blockIdx.x;
     int img1, img2;
     rpe_pair_slots<TAB>(pair_tab, img2_base, pair, img1, img2);
     const int n1 = min(kp_count[img1], kcap), n2 = min(kp_count[img2], kcap);
     for (int i = tid; i < n1; i += 256) { s_best[i] = 0xFFFFFFFFu; if (!RATIO) s_row[i] = 0xFFFFFFFEu; }      // ratio mode: no s_row (and no LDS for it)
-    if (tid == 0) s_valid = 0;
     const uint4 *d1 = (const uint4 *)(desc + (long long)img1 * kcap * 32);
     const uint4 *d2 = (const uint4 *)(desc + (long long)img2 * kcap * 32);
     // owner descriptors (one per lane, in registers) x scanned descriptors (through LDS):
@@ -109,45 +188,11 @@ __global__ __launch_bounds__(256) void match_hamming_kernel(const uint8_t *__res
         }
     }
     }
-    __syncthreads();
-    // (dist, queryIdx) keys; unmatched queries sort to the end
-    int sortP = 64;
-    while (sortP < n1) sortP <<= 1;
-    unsigned *s_key = (unsigned *)s_q;
-    int myvalid = 0;
-    for (int i = tid; i < sortP; i += 256) {
-        unsigned key = 0xFFFFFFFFu;
-        if (i < n1) {
-            unsigned b = s_best[i];
-            if (b != 0xFFFFFFFFu && (RATIO || b == s_row[i])) { key = ((b >> 18) << 16) | (unsigned)i; ++myvalid; }
-        }
-        s_key[i] = key;
-    }
-    if (myvalid) atomicAdd(&s_valid, myvalid);
-    __syncthreads();
-    for (int k = 2; k <= sortP; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = tid; t < (sortP >> 1); t += 256) {
-                int i = 2 * j * (t / j) + (t % j);
-                int ixj = i + j;
-                bool asc = (i & k) == 0;
-                unsigned a = s_key[i], b = s_key[ixj];
-                if ((a > b) == asc) { s_key[i] = b; s_key[ixj] = a; }
-            }
-            __syncthreads();
-        }
-    }
-    const int nm = min(s_valid, max_matches);
-    for (int r = tid; r < nm; r += 256) {
-        unsigned key = s_key[r];
-        int i = key & 0xFFFF, d = key >> 16;
-        int j = s_best[i] & 0x3FFFF;
-        long long o = (long long)pair * max_matches + r;
-        m_q[o] = i; m_t[o] = j; m_d[o] = d;
-        pts1[o] = kp_pt[(long long)img1 * kcap + i];
-        pts2[o] = kp_pt[(long long)img2 * kcap + j];
-    }
-    if (tid == 0) m_n[pair] = nm;
+    // the staging tile becomes the key array; ratio mode: s_best holds a word only where the test passed
+    const MatchOut<int> out(pair, max_matches, img1, img2, kcap, kp_pt, m_q, m_t, m_d, pts1, pts2);
+    select_sort_emit<256>((unsigned *)s_q, n1, max_matches, m_n + pair,
+        [&](int i) { const unsigned b = s_best[i]; return b != 0xFFFFFFFFu && (RATIO || b == s_row[i]) ? ham_sort_key(b, i) : 0xFFFFFFFFu; },
+        [&](int r, int i, unsigned key) { out.put(r, i, s_best[i] & 0x3FFFF, (int)(key >> 16)); });
 }
 
 // ---------------------------------------------------------------- crossCheck on the matrix cores
@@ -173,6 +218,7 @@ typedef int v4i_t __attribute__((ext_vector_type(4)));
 typedef int v16i_t __attribute__((ext_vector_type(16)));
 #define MM_NT 512
 #define MM_PF 4                      // query tiles fetched ahead of the one being multiplied
+#define MM_STAGE (2 * 8 * 64 + 16)   // uint4 at the head of LDS: two expanded scanned tiles [2][8][64] + their packed words [2][32]
 
 __device__ __forceinline__ v4i_t expand16(unsigned b)
 {
@@ -182,6 +228,24 @@ __device__ __forceinline__ v4i_t expand16(unsigned b)
     r.z = (int)(__umul24((b >> 8) & 15u, 0x00204081u) & 0x01010101u);
     r.w = (int)(__umul24((b >> 12) & 15u, 0x00204081u) & 0x01010101u);
     return r;
+}
+
+// |q| + 512 of the n scanned descriptors d, for the packed (|q| + 512, index) words of the staged tiles
+__device__ __forceinline__ void fill_qpop(unsigned short *s_qpop, const uint4 *d, int n)
+{
+    for (int i = threadIdx.x; i < n; i += MM_NT) s_qpop[i] = (unsigned short)(512u + popc256(d[2 * i], d[2 * i + 1]));
+}
+
+// B operand of the 8 K-steps: the lane's own descriptor j (zeros without one), bits [32 s + 16 h, +16) of step s; returns |t|
+__device__ __forceinline__ int load_owner(v4i_t (&bop)[8], const uint4 *d, int j, bool valid, int h)
+{
+    uint4 t0 = make_uint4(0, 0, 0, 0), t1 = t0;
+    if (valid) { t0 = d[2 * j]; t1 = d[2 * j + 1]; }
+    const unsigned tw[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
+    int tpop = 0;
+#pragma unroll
+    for (int sK = 0; sK < 8; ++sK) { bop[sK] = expand16((tw[sK] >> (16 * h)) & 0xFFFFu); tpop += __popc(tw[sK]); }
+    return tpop;
 }
 
 // Row election of one accumulator tile.  k[r] is this lane's key of row (r & 3) + 8 (r >> 2) + 4 (lane >> 5) at column
@@ -236,15 +300,13 @@ __global__ __launch_bounds__(MM_NT) void match_hamming_mfma_kernel(const uint8_t
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, pair = blockIdx.x;
     unsigned *s_best = SPLIT ? g_best + (long long)pair * kcap : (unsigned *)(s_dyn + region0);          // kcap entries
     unsigned *s_row = SPLIT ? g_row + (long long)pair * kcap : s_best + kcap;     // kcap entries: the query's own nearest train, as the raw row key
-    __shared__ int s_valid;
     int img1, img2;
     rpe_pair_slots<TAB>(pair_tab, img2_base, pair, img1, img2);
     const int n1 = min(kp_count[img1], kcap), n2 = min(kp_count[img2], kcap);
     if (!SPLIT) for (int i = tid; i < n1; i += MM_NT) { s_best[i] = 0xFFFFFFFFu; s_row[i] = 0xFFFFFFFEu; }      // SPLIT: the host memsets them
-    if (tid == 0) s_valid = 0;
     // |q| + 512 of every query, once (the rounds over the query tiles all need them, and so does the row key's conversion);
     // kept in the free part of the first 32 KB (kcap <= 8064 entries)
-    unsigned short *s_qpop = (unsigned short *)(s_dyn + 2 * 8 * 64 + 16);
+    unsigned short *s_qpop = (unsigned short *)(s_dyn + MM_STAGE);
     const int h = lane >> 5, col = lane & 31;
     // this thread's share of a scanned tile's expansion: item = tid: K-step s = tid >> 6, lane slot l = tid & 63
     // (row = l & 31, half = l >> 5): the 16 bits [32 s + 16 half, +16) of scanned descriptor (tile * 32 + row)
@@ -255,10 +317,7 @@ __global__ __launch_bounds__(MM_NT) void match_hamming_mfma_kernel(const uint8_t
     const int n_own = n2, n_scan = n1;
     const unsigned *q32 = (const unsigned *)(desc + (long long)img1 * kcap * 32);      // scanned: 8 dwords per descriptor
     const uint4 *d2 = (const uint4 *)(desc + (long long)img2 * kcap * 32);             // owners
-    for (int i = tid; i < n_scan; i += MM_NT) {
-        const uint4 a = ((const uint4 *)q32)[2 * i], b = ((const uint4 *)q32)[2 * i + 1];
-        s_qpop[i] = (unsigned short)(512u + __popc(a.x) + __popc(a.y) + __popc(a.z) + __popc(a.w) + __popc(b.x) + __popc(b.y) + __popc(b.z) + __popc(b.w));
-    }
+    fill_qpop(s_qpop, (const uint4 *)q32, n_scan);
     const bool c3 = (lane & 8) != 0, c2 = (lane & 4) != 0, c1 = (lane & 2) != 0;
     const int rrow = ((col >> 1) & 3) + 8 * (col >> 3) + 4 * h;      // the row whose minimum row_min32 leaves in this lane
     const int ntq = (n_scan + 31) >> 5, ntt = (n_own + 31) >> 5;
@@ -266,16 +325,8 @@ __global__ __launch_bounds__(MM_NT) void match_hamming_mfma_kernel(const uint8_t
         const int tt = tt0 + wv;                               // wave-uniform
         const int j = tt * 32 + col;
         const bool valid_t = tt < ntt && j < n_own;
-        // B operand of the 8 K-steps: this lane's own descriptor, bits [32 s + 16 h, +16) of step s
         v4i_t bop[8];
-        int tpop = 0;
-        {
-            uint4 t0 = make_uint4(0, 0, 0, 0), t1 = t0;
-            if (valid_t) { t0 = d2[2 * j]; t1 = d2[2 * j + 1]; }
-            const unsigned tw[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
-#pragma unroll
-            for (int sK = 0; sK < 8; ++sK) { bop[sK] = expand16((tw[sK] >> (16 * h)) & 0xFFFFu); tpop += __popc(tw[sK]); }
-        }
+        const int tpop = load_owner(bop, d2, j, valid_t, h);
         unsigned best_key = 0xFFFFFFFFu;
         // row key of this lane's column: (|t| + 512 - 2 q.t) << 16 | trainIdx; its minimum over the trains is the query's nearest
         // train, lowest index on ties (|q| is the same along a row).  Columns past the end: a key no real distance can beat.
@@ -349,45 +400,11 @@ __global__ __launch_bounds__(MM_NT) void match_hamming_mfma_kernel(const uint8_t
         const unsigned k = s_row[i];
         s_row[i] = (((k >> 16) - 1024u + (unsigned)s_qpop[i]) << 18) | (k & 0xFFFFu);
     }
-    __syncthreads();
-    // (dist, queryIdx) keys; unmatched queries sort to the end -- same epilogue as the VALU kernel
-    int sortP = 64;
-    while (sortP < n1) sortP <<= 1;
-    unsigned *s_key = (unsigned *)s_dyn;
-    int myvalid = 0;
-    for (int i = tid; i < sortP; i += MM_NT) {
-        unsigned key = 0xFFFFFFFFu;
-        if (i < n1) {
-            unsigned b = s_best[i];
-            if (b != 0xFFFFFFFFu && b == s_row[i]) { key = ((b >> 18) << 16) | (unsigned)i; ++myvalid; }
-        }
-        s_key[i] = key;
-    }
-    if (myvalid) atomicAdd(&s_valid, myvalid);
-    __syncthreads();
-    for (int k = 2; k <= sortP; k <<= 1) {
-        for (int jj = k >> 1; jj > 0; jj >>= 1) {
-            for (int t = tid; t < (sortP >> 1); t += MM_NT) {
-                int i = 2 * jj * (t / jj) + (t % jj);
-                int ixj = i + jj;
-                bool asc = (i & k) == 0;
-                unsigned a = s_key[i], b = s_key[ixj];
-                if ((a > b) == asc) { s_key[i] = b; s_key[ixj] = a; }
-            }
-            __syncthreads();
-        }
-    }
-    const int nm = min(s_valid, max_matches);
-    for (int r = tid; r < nm; r += MM_NT) {
-        unsigned key = s_key[r];
-        int i = key & 0xFFFF, d = key >> 16;
-        int j = s_best[i] & 0x3FFFF;
-        long long o = (long long)pair * max_matches + r;
-        m_q[o] = i; m_t[o] = j; m_d[o] = d;
-        pts1[o] = kp_pt[(long long)img1 * kcap + i];
-        pts2[o] = kp_pt[(long long)img2 * kcap + j];
-    }
-    if (tid == 0) m_n[pair] = nm;
+    // the key array takes the place of the staging region (and of s_qpop: converted above, not in key_of)
+    const MatchOut<int> out(pair, max_matches, img1, img2, kcap, kp_pt, m_q, m_t, m_d, pts1, pts2);
+    select_sort_emit<MM_NT>((unsigned *)s_dyn, n1, max_matches, m_n + pair,
+        [&](int i) { const unsigned b = s_best[i]; return b != 0xFFFFFFFFu && b == s_row[i] ? ham_sort_key(b, i) : 0xFFFFFFFFu; },
+        [&](int r, int i, unsigned key) { out.put(r, i, s_best[i] & 0x3FFFF, (int)(key >> 16)); });
 }
 
 
@@ -403,58 +420,23 @@ __global__ __launch_bounds__(MM_NT) void match_hamming_select_kernel(const unsig
                                                                       int *__restrict__ m_n, float2 *__restrict__ pts1, float2 *__restrict__ pts2)
 {
     extern __shared__ uint4 s_dyn[];
-    __shared__ int s_valid;
-    const int tid = threadIdx.x, pair = blockIdx.x;
+    const int pair = blockIdx.x;
     int img1, img2;
     rpe_pair_slots<TAB>(pair_tab, img2_base, pair, img1, img2);
     const int n1 = min(kp_count[img1], kcap);
     const unsigned *s_best = g_best + (long long)pair * kcap, *s_row = g_row + (long long)pair * kcap;
-    if (tid == 0) s_valid = 0;
-    __syncthreads();
-    // (dist, queryIdx) keys; unmatched queries sort to the end -- same epilogue as the VALU kernel
-    int sortP = 64;
-    while (sortP < n1) sortP <<= 1;
-    unsigned *s_key = (unsigned *)s_dyn;
-    int myvalid = 0;
-    for (int i = tid; i < sortP; i += MM_NT) {
-        unsigned key = 0xFFFFFFFFu;
-        if (i < n1) {
-            unsigned b = s_best[i], row = s_row[i];
+    const MatchOut<int> out(pair, max_matches, img1, img2, kcap, kp_pt, m_q, m_t, m_d, pts1, pts2);
+    select_sort_emit<MM_NT>((unsigned *)s_dyn, n1, max_matches, m_n + pair,
+        [&](int i) {
+            const unsigned b = s_best[i];
+            unsigned row = s_row[i];
             if (raw_desc) {
                 const uint4 *q = (const uint4 *)(raw_desc + ((long long)img1 * kcap + i) * 32);
-                const uint4 a = q[0], c = q[1];
-                const unsigned pop = __popc(a.x) + __popc(a.y) + __popc(a.z) + __popc(a.w) + __popc(c.x) + __popc(c.y) + __popc(c.z) + __popc(c.w);
-                row = (((row >> 16) - 512u + pop) << 18) | (row & 0xFFFFu);
+                row = (((row >> 16) - 512u + popc256(q[0], q[1])) << 18) | (row & 0xFFFFu);
             }
-            if (b != 0xFFFFFFFFu && b == row) { key = ((b >> 18) << 16) | (unsigned)i; ++myvalid; }
-        }
-        s_key[i] = key;
-    }
-    if (myvalid) atomicAdd(&s_valid, myvalid);
-    __syncthreads();
-    for (int k = 2; k <= sortP; k <<= 1) {
-        for (int jj = k >> 1; jj > 0; jj >>= 1) {
-            for (int t = tid; t < (sortP >> 1); t += MM_NT) {
-                int i = 2 * jj * (t / jj) + (t % jj);
-                int ixj = i + jj;
-                bool asc = (i & k) == 0;
-                unsigned a = s_key[i], b = s_key[ixj];
-                if ((a > b) == asc) { s_key[i] = b; s_key[ixj] = a; }
-            }
-            __syncthreads();
-        }
-    }
-    const int nm = min(s_valid, max_matches);
-    for (int r = tid; r < nm; r += MM_NT) {
-        unsigned key = s_key[r];
-        int i = key & 0xFFFF, d = key >> 16;
-        int j = s_best[i] & 0x3FFFF;
-        long long o = (long long)pair * max_matches + r;
-        m_q[o] = i; m_t[o] = j; m_d[o] = d;
-        pts1[o] = kp_pt[(long long)img1 * kcap + i];
-        pts2[o] = kp_pt[(long long)img2 * kcap + j];
-    }
-    if (tid == 0) m_n[pair] = nm;
+            return b != 0xFFFFFFFFu && b == row ? ham_sort_key(b, i) : 0xFFFFFFFFu;
+        },
+        [&](int r, int i, unsigned key) { out.put(r, i, s_best[i] & 0x3FFFF, (int)(key >> 16)); });
 }
 
 // Launches the pair-table instance of a kernel when the feature source carries a table (a pair list), the rule instance
@@ -465,10 +447,62 @@ static void launch_tab(bool tab, Kernel with_table, Kernel with_rule, dim3 grid,
     hipLaunchKernelGGL(tab ? with_table : with_rule, grid, block, lds, stream, args...);
 }
 
+// The launch plan of the matrix-core Hamming matchers for B pairs of capacity kcap; extra_uint4: what the matcher keeps in the
+// first LDS region besides the crossCheck staging (the guided matcher's records).  The ONE statement of the rule: both
+// launchers follow it and alloc_workspace sizes the HBM election words from it.
+//   region0: max(staging + 2 B per scanned descriptor (|q| + 512), 4 B x sort size) -- the key array reuses it;
+//   fused:   region0 + 8 B of election / own-nearest words per keypoint, while that fits 64 KB of LDS per workgroup
+//            (kcap <= 4096);
+//   hbm:     the words live in HBM and match_hamming_select_kernel sorts and emits -- batches of up to RPE_MATCH_SPLIT_PAIRS
+//            pairs whose rounds of 8 owner tiles are dealt over `split` > 1 workgroups (256 in flight at most), and every
+//            batch once the fused form does not fit.
+RpeHammingPlan rpe_hamming_plan(int kcap, int B, int extra_uint4)
+{
+    RpeHammingPlan p;
+    p.sortP = 64;
+    while (p.sortP < kcap) p.sortP <<= 1;
+    p.region0 = (int)((std::max((size_t)(MM_STAGE + extra_uint4) * 16 + (size_t)kcap * 2, (size_t)p.sortP * 4) + 15) / 16);
+    const int rounds = ((kcap + 31) / 32 + 7) / 8;
+    p.split = B <= RPE_MATCH_SPLIT_PAIRS ? std::min(rounds, std::max(1, 256 / B)) : 1;
+    const size_t fused = (size_t)p.region0 * 16 + (size_t)kcap * 8;
+    p.hbm = p.split > 1 || fused > 65536;
+    p.lds_tile = p.hbm ? (size_t)p.region0 * 16 : fused;
+    p.lds_select = (size_t)p.sortP * 4;
+    return p;
+}
+
+// Where a matcher's launch sequence leaves its matches
+struct MatchBufs { int *q, *t, *d, *n; float2 *p1, *p2; };
+
+// The launches of a plan: the fused tile kernel, or the two memsets of the HBM words, the SPLIT tile kernel and the select
+// kernel.  k_* : the tile kernel's instances <SPLIT, TAB>; mid: its arguments between max_matches and the HBM words;
+// raw_desc: see match_hamming_select_kernel.
+template <typename Kernel, typename... Mid>
+static void launch_hamming_plan(rpe_handle *h, const RpeRun &r, const RpeHammingPlan &p, Kernel k_hbm_tab, Kernel k_hbm, Kernel k_fused_tab, Kernel k_fused,
+                                const uint8_t *raw_desc, const MatchBufs &o, Mid... mid)
+{
+    const int kcap = h->lay.kcap, B = r.pairs, mm = h->cfg.max_matches;
+    const RpeFeatSrc &f = r.feat;                             // the workspace (batch / stream rule) or the frame store (pair table)
+    if (!p.hbm) {
+        launch_tab(f.tab, k_fused_tab, k_fused, dim3(B), dim3(MM_NT), p.lds_tile, h->stream,
+                           f.desc, f.count, f.pt, f.img2_base, f.tab, kcap, mm, mid...,
+                           (unsigned *)nullptr, (unsigned *)nullptr, o.q, o.t, o.d, o.n, o.p1, o.p2);
+        return;
+    }
+    hipMemsetAsync(h->d_hm_best, 0xFF, sizeof(unsigned) * (size_t)B * kcap, h->stream);
+    hipMemsetAsync(h->d_hm_row, 0xFE, sizeof(unsigned) * (size_t)B * kcap, h->stream);     // above every row key; its train index is no one's
+    launch_tab(f.tab, k_hbm_tab, k_hbm, dim3(B, p.split), dim3(MM_NT), p.lds_tile, h->stream,
+                       f.desc, f.count, f.pt, f.img2_base, f.tab, kcap, mm, mid...,
+                       h->d_hm_best, h->d_hm_row, o.q, o.t, o.d, o.n, o.p1, o.p2);
+    launch_tab(f.tab, match_hamming_select_kernel<true>, match_hamming_select_kernel<false>, dim3(B), dim3(MM_NT), p.lds_select, h->stream,
+                       (const unsigned *)h->d_hm_best, (const unsigned *)h->d_hm_row, raw_desc, f.count, f.pt,
+                       f.img2_base, f.tab, kcap, mm, o.q, o.t, o.d, o.n, o.p1, o.p2);
+}
+
 void rpe_launch_match(rpe_handle *h, const RpeRun &r)
 {
     const int kcap = h->lay.kcap, B = r.pairs;
-    const RpeFeatSrc &f = r.feat;                             // the workspace (batch / stream rule) or the frame store (pair table)
+    const RpeFeatSrc &f = r.feat;
     size_t lds = (size_t)QTILE * 32 + (size_t)kcap * 8;       // staging / sort keys + election words + own-nearest words
     if (h->cfg.match_mode == RPE_MATCH_RATIO)                 // the ratio mode has no own-nearest words: 4 bytes per keypoint (<= 64 KB at 8064)
         launch_tab(f.tab, match_hamming_kernel<true, true>, match_hamming_kernel<true, false>, dim3(B), dim3(256), (size_t)QTILE * 32 + (size_t)kcap * 4, h->stream,
@@ -479,29 +513,10 @@ void rpe_launch_match(rpe_handle *h, const RpeRun &r)
                            f.desc, f.count, f.pt, f.img2_base, f.tab, kcap, h->cfg.max_matches, 0.0,
                            h->d_m_q, h->d_m_t, h->d_m_d, h->d_m_n, h->d_pts1, h->d_pts2);
     else {
-        // first LDS region: max(staging 16 KB + 256 B of packed words + 2 B per scanned descriptor, 4 B x sort size)
-        int sortP = 64;
-        while (sortP < kcap) sortP <<= 1;
-        const size_t r0 = (std::max((size_t)(2 * 8 * 64 + 16) * 16 + (size_t)kcap * 2, (size_t)sortP * 4) + 15) / 16;
-        const int rounds = ((kcap + 31) / 32 + 7) / 8;
-        // the fused kernel keeps 8 bytes of election words per keypoint in LDS: beyond 64 KB per workgroup (nfeatures > ~4900) the
-        // HBM-resident form serves every batch size (rpe_create sizes d_hm_* for the whole batch then)
-        const bool lds_fits = r0 * 16 + (size_t)kcap * 8 <= 65536;
-        const int split = B <= RPE_MATCH_SPLIT_PAIRS ? std::min(rounds, std::max(1, 256 / B)) : 1;
-        if (split > 1 || !lds_fits) {
-            hipMemsetAsync(h->d_hm_best, 0xFF, sizeof(unsigned) * (size_t)B * kcap, h->stream);
-            hipMemsetAsync(h->d_hm_row, 0xFE, sizeof(unsigned) * (size_t)B * kcap, h->stream);     // above every row key; its train index is no one's
-            launch_tab(f.tab, match_hamming_mfma_kernel<true, true>, match_hamming_mfma_kernel<true, false>, dim3(B, split), dim3(MM_NT), r0 * 16, h->stream,
-                               f.desc, f.count, f.pt, f.img2_base, f.tab, kcap, h->cfg.max_matches, (int)r0,
-                               h->d_hm_best, h->d_hm_row, h->d_m_q, h->d_m_t, h->d_m_d, h->d_m_n, h->d_pts1, h->d_pts2);
-            launch_tab(f.tab, match_hamming_select_kernel<true>, match_hamming_select_kernel<false>, dim3(B), dim3(MM_NT), (size_t)sortP * 4, h->stream,
-                               (const unsigned *)h->d_hm_best, (const unsigned *)h->d_hm_row, f.desc, f.count, f.pt,
-                               f.img2_base, f.tab, kcap, h->cfg.max_matches,
-                               h->d_m_q, h->d_m_t, h->d_m_d, h->d_m_n, h->d_pts1, h->d_pts2);
-        } else
-            launch_tab(f.tab, match_hamming_mfma_kernel<false, true>, match_hamming_mfma_kernel<false, false>, dim3(B), dim3(MM_NT), r0 * 16 + (size_t)kcap * 8, h->stream,
-                               f.desc, f.count, f.pt, f.img2_base, f.tab, kcap, h->cfg.max_matches, (int)r0,
-                               (unsigned *)nullptr, (unsigned *)nullptr, h->d_m_q, h->d_m_t, h->d_m_d, h->d_m_n, h->d_pts1, h->d_pts2);
+        const RpeHammingPlan p = rpe_hamming_plan(kcap, B, 0);
+        launch_hamming_plan(h, r, p, match_hamming_mfma_kernel<true, true>, match_hamming_mfma_kernel<true, false>,
+                            match_hamming_mfma_kernel<false, true>, match_hamming_mfma_kernel<false, false>, f.desc,
+                            MatchBufs{h->d_m_q, h->d_m_t, h->d_m_d, h->d_m_n, h->d_pts1, h->d_pts2}, p.region0);
     }
 }
 
@@ -585,19 +600,17 @@ __global__ __launch_bounds__(MM_NT) void match_guided_mfma_kernel(const uint8_t 
     // records, the popcounts; reused as the sort-key array afterwards.  Then kcap election words and kcap own-nearest words.
     v4i_t *s_a = (v4i_t *)s_dyn;                               // [2][8][64]
     unsigned *s_qpk = (unsigned *)(s_dyn + 2 * 8 * 64);        // [2][32]
-    double2 *s_rec = (double2 *)(s_dyn + 2 * 8 * 64 + 16);     // [2][32][2]
-    unsigned short *s_qpop = (unsigned short *)(s_dyn + 2 * 8 * 64 + 16 + 128);
+    double2 *s_rec = (double2 *)(s_dyn + MM_STAGE);            // [2][32][2]: RPE_GUIDED_LDS_UINT4
+    unsigned short *s_qpop = (unsigned short *)(s_dyn + MM_STAGE + RPE_GUIDED_LDS_UINT4);
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, pair = blockIdx.x;
     unsigned *s_best = SPLIT ? g_best + (long long)pair * kcap : (unsigned *)(s_dyn + region0);
     unsigned *s_row = SPLIT ? g_row + (long long)pair * kcap : s_best + kcap;
-    __shared__ int s_valid;
     int img1, img2;
     rpe_pair_slots<TAB>(pair_tab, img2_base, pair, img1, img2);
     const double thr2 = g_thr2[pair];
     const bool run = thr2 == thr2;                             // NaN: the pair is not matched
     const int n1 = run ? min(kp_count[img1], kcap) : 0, n2 = run ? min(kp_count[img2], kcap) : 0;
     if (!SPLIT) for (int i = tid; i < n1; i += MM_NT) { s_best[i] = 0xFFFFFFFFu; s_row[i] = 0xFFFFFFFEu; }      // SPLIT: the host memsets them
-    if (tid == 0) s_valid = 0;
     const int h = lane >> 5, col = lane & 31;
     const int xs = tid >> 6, xl = tid & 63, xrow = xl & 31, xh = xl >> 5;
     const bool rec_loader = wv == 1;                           // piece (row lane >> 1, half lane & 1) of a tile's 32 records
@@ -610,24 +623,14 @@ __global__ __launch_bounds__(MM_NT) void match_guided_mfma_kernel(const uint8_t 
     const double2 *rec_scan = (const double2 *)(g_rec + ((long long)pair * 2 + (pass ? 1 : 0)) * kcap);
     const double4 *rec_own = g_rec + ((long long)pair * 2 + (pass ? 0 : 1)) * kcap;
     __syncthreads();                                           // the previous pass is done with s_qpop
-    for (int i = tid; i < n_scan; i += MM_NT) {
-        const uint4 a = ((const uint4 *)q32)[2 * i], b = ((const uint4 *)q32)[2 * i + 1];
-        s_qpop[i] = (unsigned short)(512u + __popc(a.x) + __popc(a.y) + __popc(a.z) + __popc(a.w) + __popc(b.x) + __popc(b.y) + __popc(b.z) + __popc(b.w));
-    }
+    fill_qpop(s_qpop, (const uint4 *)q32, n_scan);
     const int ntq = (n_scan + 31) >> 5, ntt = (n_own + 31) >> 5;
     for (int tt0 = SPLIT ? 8 * (int)blockIdx.y : 0; tt0 < ntt && n_scan > 0; tt0 += SPLIT ? 8 * (int)gridDim.y : 8) {
         const int tt = tt0 + wv;                               // wave-uniform
         const int j = tt * 32 + col;
         const bool valid_t = tt < ntt && j < n_own;
         v4i_t bop[8];
-        int tpop = 0;
-        {
-            uint4 t0 = make_uint4(0, 0, 0, 0), t1 = t0;
-            if (valid_t) { t0 = d2[2 * j]; t1 = d2[2 * j + 1]; }
-            const unsigned tw[8] = {t0.x, t0.y, t0.z, t0.w, t1.x, t1.y, t1.z, t1.w};
-#pragma unroll
-            for (int sK = 0; sK < 8; ++sK) { bop[sK] = expand16((tw[sK] >> (16 * h)) & 0xFFFFu); tpop += __popc(tw[sK]); }
-        }
+        const int tpop = load_owner(bop, d2, j, valid_t, h);
         // the owner's record: pass 0 a train (x2, y2, s2, 0), pass 1 a query (l_0, l_1, l_2, s1)
         const double4 own = valid_t ? rec_own[j] : make_double4(qnan, qnan, qnan, qnan);
         unsigned best_key = 0xFFFFFFFFu;
@@ -700,46 +703,11 @@ __global__ __launch_bounds__(MM_NT) void match_guided_mfma_kernel(const uint8_t 
         }
     }
     }
-    __syncthreads();
     if (SPLIT) return;                                         // match_hamming_select_kernel sorts and emits
-    // (dist, queryIdx) keys; unmatched queries sort to the end -- same epilogue as the crossCheck kernel
-    int sortP = 64;
-    while (sortP < n1) sortP <<= 1;
-    unsigned *s_key = (unsigned *)s_dyn;
-    int myvalid = 0;
-    for (int i = tid; i < sortP; i += MM_NT) {
-        unsigned key = 0xFFFFFFFFu;
-        if (i < n1) {
-            unsigned b = s_best[i];
-            if (b != 0xFFFFFFFFu && b == s_row[i]) { key = ((b >> 18) << 16) | (unsigned)i; ++myvalid; }
-        }
-        s_key[i] = key;
-    }
-    if (myvalid) atomicAdd(&s_valid, myvalid);
-    __syncthreads();
-    for (int k = 2; k <= sortP; k <<= 1) {
-        for (int jj = k >> 1; jj > 0; jj >>= 1) {
-            for (int t = tid; t < (sortP >> 1); t += MM_NT) {
-                int i = 2 * jj * (t / jj) + (t % jj);
-                int ixj = i + jj;
-                bool asc = (i & k) == 0;
-                unsigned a = s_key[i], b = s_key[ixj];
-                if ((a > b) == asc) { s_key[i] = b; s_key[ixj] = a; }
-            }
-            __syncthreads();
-        }
-    }
-    const int nm = min(s_valid, max_matches);
-    for (int r = tid; r < nm; r += MM_NT) {
-        unsigned key = s_key[r];
-        int i = key & 0xFFFF, d = key >> 16;
-        int j = s_best[i] & 0x3FFFF;
-        long long o = (long long)pair * max_matches + r;
-        m_q[o] = i; m_t[o] = j; m_d[o] = d;
-        pts1[o] = kp_pt[(long long)img1 * kcap + i];
-        pts2[o] = kp_pt[(long long)img2 * kcap + j];
-    }
-    if (tid == 0) m_n[pair] = nm;
+    const MatchOut<int> out(pair, max_matches, img1, img2, kcap, kp_pt, m_q, m_t, m_d, pts1, pts2);
+    select_sort_emit<MM_NT>((unsigned *)s_dyn, n1, max_matches, m_n + pair,
+        [&](int i) { const unsigned b = s_best[i]; return b != 0xFFFFFFFFu && b == s_row[i] ? ham_sort_key(b, i) : 0xFFFFFFFFu; },
+        [&](int r, int i, unsigned key) { out.put(r, i, s_best[i] & 0x3FFFF, (int)(key >> 16)); });
 }
 
 // Guided matches of run r under the poses d_R / d_t (d_status: the run's own poses, pairs that are not OK are skipped; nullptr:
@@ -761,29 +729,12 @@ void rpe_launch_guided(rpe_handle *h, const RpeRun &r, const double *d_R, const 
     hipLaunchKernelGGL(records, dim3((kcap + 255) / 256, 2, B), dim3(256), 0, h->stream,
                        f.count, f.pt, f.img2_base, f.tab, kcap, (const double *)h->d_K, r.cam, d_R, d_t, d_status, gate_px,
                        h->d_gm_rec, h->d_gm_thr2);
-    // LDS regions and the choice of the HBM form: as rpe_launch_match, with 2 KB of records in the first region
-    int sortP = 64;
-    while (sortP < kcap) sortP <<= 1;
-    const size_t r0 = (std::max((size_t)(2 * 8 * 64 + 16 + 128) * 16 + (size_t)kcap * 2, (size_t)sortP * 4) + 15) / 16;
-    const int rounds = ((kcap + 31) / 32 + 7) / 8;
-    const bool lds_fits = r0 * 16 + (size_t)kcap * 8 <= 65536;
-    const int split = B <= RPE_MATCH_SPLIT_PAIRS ? std::min(rounds, std::max(1, 256 / B)) : 1;
-    if (split > 1 || !lds_fits) {
-        hipMemsetAsync(h->d_hm_best, 0xFF, sizeof(unsigned) * (size_t)B * kcap, h->stream);
-        hipMemsetAsync(h->d_hm_row, 0xFE, sizeof(unsigned) * (size_t)B * kcap, h->stream);
-        launch_tab(f.tab, match_guided_mfma_kernel<true, true>, match_guided_mfma_kernel<true, false>, dim3(B, split), dim3(MM_NT), r0 * 16, h->stream,
-                           f.desc, f.count, f.pt, f.img2_base, f.tab, kcap, mm, max_distance, (int)r0,
-                           (const double4 *)h->d_gm_rec, (const double *)h->d_gm_thr2,
-                           h->d_hm_best, h->d_hm_row, h->d_gm_q, h->d_gm_t, h->d_gm_d, h->d_gm_n, h->d_gm_pts1, h->d_gm_pts2);
-        launch_tab(f.tab, match_hamming_select_kernel<true>, match_hamming_select_kernel<false>, dim3(B), dim3(MM_NT), (size_t)sortP * 4, h->stream,
-                           (const unsigned *)h->d_hm_best, (const unsigned *)h->d_hm_row, (const uint8_t *)nullptr, f.count, f.pt,
-                           f.img2_base, f.tab, kcap, mm,
-                           h->d_gm_q, h->d_gm_t, h->d_gm_d, h->d_gm_n, h->d_gm_pts1, h->d_gm_pts2);
-    } else
-        launch_tab(f.tab, match_guided_mfma_kernel<false, true>, match_guided_mfma_kernel<false, false>, dim3(B), dim3(MM_NT), r0 * 16 + (size_t)kcap * 8, h->stream,
-                           f.desc, f.count, f.pt, f.img2_base, f.tab, kcap, mm, max_distance, (int)r0,
-                           (const double4 *)h->d_gm_rec, (const double *)h->d_gm_thr2,
-                           (unsigned *)nullptr, (unsigned *)nullptr, h->d_gm_q, h->d_gm_t, h->d_gm_d, h->d_gm_n, h->d_gm_pts1, h->d_gm_pts2);
+    // the crossCheck matcher's plan with 2 KB of scanned records in the first LDS region; the row words are final: no raw_desc
+    const RpeHammingPlan p = rpe_hamming_plan(kcap, B, RPE_GUIDED_LDS_UINT4);
+    launch_hamming_plan(h, r, p, match_guided_mfma_kernel<true, true>, match_guided_mfma_kernel<true, false>,
+                        match_guided_mfma_kernel<false, true>, match_guided_mfma_kernel<false, false>, (const uint8_t *)nullptr,
+                        MatchBufs{h->d_gm_q, h->d_gm_t, h->d_gm_d, h->d_gm_n, h->d_gm_pts1, h->d_gm_pts2},
+                        max_distance, p.region0, (const double4 *)h->d_gm_rec, (const double *)h->d_gm_thr2);
 }
 
 // ===================================================================== L2 (SIFT)
@@ -1048,50 +999,19 @@ __global__ __launch_bounds__(256) void match_l2_select_kernel(const unsigned lon
                                                                int *__restrict__ m_n, float2 *__restrict__ pts1, float2 *__restrict__ pts2)
 {
     extern __shared__ unsigned long long s_key[];          // sortP <= 16384 keys (128 KB)
-    __shared__ int s_valid;
-    const int tid = threadIdx.x, pair = blockIdx.x;
+    const int pair = blockIdx.x;
     int img1, img2;
     rpe_pair_slots<TAB>(pair_tab, img2_base, pair, img1, img2);
     const int n1 = min(kp_count[img1], kcap);
     const unsigned long long *bp = nn_t + (long long)pair * kcap;
-    if (tid == 0) s_valid = 0;
-    __syncthreads();
-    int sortP = 64;
-    while (sortP < n1) sortP <<= 1;
-    int myvalid = 0;
-    for (int i = tid; i < sortP; i += 256) {
-        unsigned long long key = ~0ull;
-        if (i < n1) {
-            unsigned long long b = bp[i];
-            if (b != ~0ull && (!nn_q || (int)(nn_q[(long long)pair * kcap + (int)(b & 0x3FFFF)] & 0x3FFFF) == i)) { key = ((b >> 18) << 16) | (unsigned long long)i; ++myvalid; }
-        }
-        s_key[i] = key;
-    }
-    if (myvalid) atomicAdd(&s_valid, myvalid);
-    __syncthreads();
-    for (int k = 2; k <= sortP; k <<= 1) {
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t2 = tid; t2 < (sortP >> 1); t2 += 256) {
-                int i = 2 * j * (t2 / j) + (t2 % j);
-                int ixj = i + j;
-                bool asc = (i & k) == 0;
-                unsigned long long a = s_key[i], b = s_key[ixj];
-                if ((a > b) == asc) { s_key[i] = b; s_key[ixj] = a; }
-            }
-            __syncthreads();
-        }
-    }
-    const int nm = min(s_valid, max_matches);
-    for (int r = tid; r < nm; r += 256) {
-        unsigned long long key = s_key[r];
-        int i = (int)(key & 0xFFFF);
-        int j = (int)(bp[i] & 0x3FFFF);
-        long long o = (long long)pair * max_matches + r;
-        m_q[o] = i; m_t[o] = j; m_d[o] = __uint_as_float((unsigned)(key >> 16));
-        pts1[o] = kp_pt[(long long)img1 * kcap + i];
-        pts2[o] = kp_pt[(long long)img2 * kcap + j];
-    }
-    if (tid == 0) m_n[pair] = nm;
+    const unsigned long long *nq = nn_q ? nn_q + (long long)pair * kcap : nullptr;
+    const MatchOut<float> out(pair, max_matches, img1, img2, kcap, kp_pt, m_q, m_t, m_d, pts1, pts2);
+    select_sort_emit<256>(s_key, n1, max_matches, m_n + pair,
+        [&](int i) {
+            const unsigned long long b = bp[i];
+            return b != ~0ull && (!nq || (int)(nq[b & 0x3FFFF] & 0x3FFFF) == i) ? ((b >> 18) << 16) | (unsigned long long)i : ~0ull;
+        },
+        [&](int r, int i, unsigned long long key) { out.put(r, i, (int)(bp[i] & 0x3FFFF), __uint_as_float((unsigned)(key >> 16))); });
 }
 
 // { |u|^2, |u|^2 + 2 sum(u) } of the descriptors of workspace images [0, n_img): once per batch / stream, and once per

@@ -334,9 +334,12 @@ static int alloc_workspace(rpe_handle *h)
     DM(h, h->d_pts1, B * mm); DM(h, h->d_pts2, B * mm);
     if (h->cfg.norm_type == RPE_NORM_L2) { DM(h, h->d_m_best, B * L.kcap); DM(h, h->d_m_best2, B * L.kcap); DM(h, h->d_m_norm, 2 * NI * L.kcap); }
     else {
-        // small batches (and, when the fused matcher's LDS would not fit, all batches) keep the election words in HBM
-        const bool big = (size_t)L.kcap * 8 + 32768 > 65536;
-        const size_t bs = big || B < RPE_MATCH_SPLIT_PAIRS ? B : RPE_MATCH_SPLIT_PAIRS;
+        // the election words in HBM: for the batches that split (at most RPE_MATCH_SPLIT_PAIRS pairs), and for max_batch pairs
+        // when the plan of either matcher keeps them there at that size too (beyond the split limit that is a matter of kcap
+        // alone: every larger batch of this engine plans the same)
+        size_t bs = std::min<size_t>(B, RPE_MATCH_SPLIT_PAIRS);
+        for (int extra : {0, RPE_GUIDED_LDS_UINT4})
+            if (rpe_hamming_plan(L.kcap, (int)B, extra).hbm) bs = B;
         DM(h, h->d_hm_best, bs * L.kcap); DM(h, h->d_hm_row, bs * L.kcap);
     }
     DM(h, h->d_n1, B * mm); DM(h, h->d_n2, B * mm);

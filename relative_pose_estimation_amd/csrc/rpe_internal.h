@@ -15,6 +15,7 @@
 #define RPE_MAX_MODELS 10
 #define RPE_GRAPH_MAX_PAIRS 16    // batches up to this many pairs are replayed as a captured hipGraph
 #define RPE_MATCH_SPLIT_PAIRS 64   // batches up to this many pairs split a pair's Hamming matching over several workgroups
+#define RPE_GUIDED_LDS_UINT4 128    // the guided matcher's part of the first LDS region: 2 x 32 scanned records of 32 bytes
 #define RPE_TAB_RING 4            // pinned pieces the slot tables of rpe_frames_put* / rpe_enqueue_pairs rotate through
 // one pair's results, section by section of the result block (d_resblk): R, t, inliers, status, n_matches
 #define RPE_RESULT_SECTIONS 5
@@ -370,6 +371,16 @@ void rpe_launch_harris(rpe_handle *h, int n_img);
 void rpe_launch_keypoints(rpe_handle *h, int n_img);
 void rpe_launch_orient_describe(rpe_handle *h, int n_img);
 void rpe_launch_debug_blur(rpe_handle *h, int img);
+// How the matrix-core Hamming matchers (crossCheck: extra_uint4 = 0, guided: RPE_GUIDED_LDS_UINT4) run B pairs of capacity
+// kcap; the rule is rpe_hamming_plan's alone (match_kernels.hip)
+struct RpeHammingPlan {
+    int region0;                   // the tile kernel's first LDS region, in 16-byte units
+    int sortP;                     // sort size: the power of two >= max(kcap, 64)
+    int split;                     // workgroups per pair (gridDim.y of the tile kernel)
+    bool hbm;                      // election words in d_hm_*: tile kernel + select kernel; false: the fused tile kernel alone
+    size_t lds_tile, lds_select;   // dynamic LDS of the tile kernel (as launched) and of the select kernel
+};
+RpeHammingPlan rpe_hamming_plan(int kcap, int B, int extra_uint4);
 void rpe_launch_match(rpe_handle *h, const RpeRun &r);
 void rpe_launch_match_l2(rpe_handle *h, const RpeRun &r);
 void rpe_launch_l2_norms(rpe_handle *h, int n_img);

@@ -212,6 +212,26 @@ def test_hamming_split_twenty_workgroups(ham5000):
     _check(ham5000, "ham_5000", [mc.cases("ham_5000")[0]])
 
 
+def test_hamming_first_capacity_beyond_lds(capi):
+    """kcap = 4097 is the first capacity whose fused form does not fit LDS (the sort size doubles to 8192 keys), in an engine
+    of 65 pairs: the launcher's memsets of B x kcap election words and the engine's allocation of them must follow one rule.
+    65 pairs: beyond the split limit, the HBM form with one workgroup per pair; then 64 pairs: gridDim = (64, 4).  The pairs
+    cycle the small cases of ham_5000 (at most 64 rows: one owner tile or two, so the workgroups y >= 1 have no round);
+    each case with both sides >= 2 has a model match."""
+    e = _engine(capi, "ham_5000", 4033, 65)
+    try:
+        assert e.kcap == 4097 and hamming_form(4096, 65)[0] == "fused"
+        small = mc.cases("ham_5000")[1:]
+        assert all(max(len(c.desc1), len(c.desc2)) <= 64 for c in small)
+        assert all(len(mc.expected("ham_5000", c)[0]) >= 1 for c in small if min(len(c.desc1), len(c.desc2)) >= 2)
+        assert hamming_form(4097, 65) == ("split", 1, 17)
+        _check(e, "ham_5000", [small[i % len(small)] for i in range(65)])
+        assert hamming_form(4097, 64) == ("split", 4, 17)
+        _check(e, "ham_5000", [small[i % len(small)] for i in range(64)])
+    finally:
+        e.close()
+
+
 # ================================================================= Hamming, vector ALU
 # The two RPE_MATCH_VALU tests cannot observe which kernel ran: they rely on the launchers reading the variable with getenv
 # at every launch, as they do today.  Were that read ever cached in a static, they would pass on the matrix-core path.

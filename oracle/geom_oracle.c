@@ -175,11 +175,22 @@ static double root_bound(const double *p, int k)
     return R;
 }
 
+/* Test instrumentation: which paths of the root chain the solves since the last read took -- solves, solves of degree
+ * below 10, levels entered with more than 8 intervals (two rounds of the HIP kernel's 8 lanes), solves returning more
+ * than 8 roots (a second back-substitution round).  Not thread-safe: single-threaded tests only. */
+static int64_t g_poly_counters[4];
+void orc_debug_poly_counters(int64_t out[4])
+{
+    for (int i = 0; i < 4; ++i) { out[i] = g_poly_counters[i]; g_poly_counters[i] = 0; }
+}
+
 static int poly_real_roots(const double *c, int n, double *roots)
 {
     double d[11][11];      /* d[k] = coefficients of the degree-k member of the derivative chain */
     double rts[2][11];
     int nr_prev = 0, cur = 0;
+    ++g_poly_counters[0];
+    if (n < 10) ++g_poly_counters[1];
     for (int i = 0; i <= n; ++i) d[n][i] = c[i];
     for (int k = n; k >= 2; --k)
         for (int i = 0; i < k; ++i) d[k - 1][i] = d[k][i + 1] * (double)(i + 1);
@@ -191,6 +202,7 @@ static int poly_real_roots(const double *c, int n, double *roots)
         double *out = rts[cur ^ 1];
         int nout = 0;
         double R = root_bound(p, k);
+        if (nr_prev + 1 > 8) ++g_poly_counters[2];
         for (int iv = 0; iv <= nr_prev; ++iv) {
             double a = (iv == 0) ? -R : crit[iv - 1];
             double b = (iv == nr_prev) ? R : crit[iv];
@@ -204,6 +216,7 @@ static int poly_real_roots(const double *c, int n, double *roots)
         nr_prev = nout; cur ^= 1;
     }
     for (int i = 0; i < nr_prev; ++i) roots[i] = rts[cur][i];
+    if (nr_prev > 8) ++g_poly_counters[3];
     return nr_prev;
 }
 

@@ -235,6 +235,14 @@ def set_ransac_seed(seed=0xFFFFFFFFFFFFFFFF):
     lib().orc_debug_set_ransac_seed(C.c_uint64(seed))
 
 
+def poly_counters():
+    """Root-chain paths taken by the five-point solves since the last call (then cleared): solves, solves of degree below
+    10, levels entered with more than 8 intervals, solves returning more than 8 roots.  Single-threaded callers only."""
+    out = np.zeros(4, np.int64)
+    lib().orc_debug_poly_counters(_p(out))
+    return [int(v) for v in out]
+
+
 def set_variant(key, val):
     lib().orc_debug_set_variant(int(key), int(val))
 

@@ -9,9 +9,9 @@
 //   ransac_prepare : normalise points with K (f64), reset per-pair state
 //   ransac_poly    : one lane = one minimal sample: null space, 10x20 elimination in lane-interleaved
 //                    LDS, determinant polynomial of degree 10 (f64)
-//   ransac_roots   : 16 lanes per sample: lane = bracketing interval of the derivative chain, safeguarded
+//   ransac_roots   : 8 lanes per sample (RG): lane = bracketing interval of the derivative chain, safeguarded
 //                    Newton, ballot/shuffle compaction; back-substitution lane = root -> up to 10 models
-//   ransac_score   : workgroup per (pair, 64 iterations), wave per model: Sampson error (f64 -> f32
+//   ransac_score   : workgroup per (pair, 8 iterations) (SCORE_GROUP), wave per model: Sampson error (f64 -> f32
 //                    compare) over the matches in LDS, shuffle-reduced inlier counts
 //   ransac_update  : wave per pair: the sequential "strictly more inliers wins / niters shrinks / stop at
 //                    niters" rule as prefix-max and prefix-min scans (bit-identical termination)
@@ -40,119 +40,13 @@ __device__ static void ql_acc(double *c, const double *a, const double *b, doubl
     for (int i = 0; i < 10; ++i) for (int j = 0; j < 4; ++j) c[QL2C[i][j]] += s * (a[i] * b[j]);
 }
 
-// Fixed Estrin scheme for degree <= 10 (dependency depth 7 instead of Horner's 20; the
-// root finder is latency bound).  Identical arithmetic to oracle/geom_oracle.c.
-__device__ static double horner(const double *c, int n, double x)
-{
-    double cc[11];
-    for (int i = 0; i < 11; ++i) cc[i] = i <= n ? c[i] : 0.;
-    const double x2 = x * x, x4 = x2 * x2, x8 = x4 * x4;
-    const double a0 = cc[0] + cc[1] * x, a1 = cc[2] + cc[3] * x, a2 = cc[4] + cc[5] * x;
-    const double a3 = cc[6] + cc[7] * x, a4 = cc[8] + cc[9] * x, a5 = cc[10];
-    const double b0 = a0 + a1 * x2, b1 = a2 + a3 * x2, b2 = a4 + a5 * x2;
-    return (b0 + b1 * x4) + b2 * x8;
-}
-
-// Safeguarded Newton on a bracket with a sign change (same code path as the oracle).
-__device__ static double refine_root(const double *p, const double *dp, int k, double a, double b, int sa)
-{
-    double xl = sa ? b : a, xh = sa ? a : b;
-    double rts = 0.5 * (a + b);
-    double dxold = fabs(b - a), dx = dxold;
-    double f = horner(p, k, rts), df = horner(dp, k - 1, rts);
-    for (int it = 0; it < 100; ++it) {
-        int bis = ((((rts - xh) * df - f) * ((rts - xl) * df - f)) > 0.0) || (fabs(2.0 * f) > fabs(dxold * df));
-        double nr;
-        dxold = dx;
-        if (bis) { dx = 0.5 * (xh - xl); nr = xl + dx; }
-        else { dx = f / df; nr = rts - dx; }
-        if (nr == rts || fabs(nr - rts) <= 2.3e-13 * fabs(nr)) { rts = nr; break; }
-        rts = nr;
-        f = horner(p, k, rts); df = horner(dp, k - 1, rts);
-        if (f > 0.0) xh = rts; else xl = rts;
-    }
-    return rts;
-}
-
-// Root bound from binary exponents only (same integers on CPU and GPU): Fujiwara's |z| <= 2 max_i |a_{k-i}/a_k|^(1/i)
-// with |a| < 2^(ilogb(a)+1): R = 2^(1 + max_i ceil((e_{k-i} - e_k + 1)/i)).  Cauchy's bound put the outer brackets
-// orders of magnitude beyond the roots and the safeguarded Newton bisected its way back (oracle: root_bound()).
-__device__ static double root_bound(const double *p, int k)
-{
-    const int ek = ilogb(p[k]);
-    int emax = -100000;
-    for (int i = 0; i < k; ++i) {
-        if (p[i] == 0.) continue;
-        const int d = ilogb(p[i]) - ek + 1, m = k - i;
-        const int q = d >= 0 ? (d + m - 1) / m : -((-d) / m);
-        if (q > emax) emax = q;
-    }
-    double R = emax == -100000 ? 1. : ldexp(1., emax + 1);
-    if (!(R < 1e12)) R = 1e12;
-    return R;
-}
-template <int K>
-__device__ __forceinline__ double root_bound_s(const double (&p)[11])
-{
-    const int ek = ilogb(p[K]);
-    int emax = -100000;
-#pragma unroll
-    for (int i = 0; i < K; ++i) {
-        if (p[i] != 0.) {
-            const int d = ilogb(p[i]) - ek + 1;
-            const int m = K - i;
-            const int q = d >= 0 ? (d + m - 1) / m : -((-d) / m);
-            if (q > emax) emax = q;
-        }
-    }
-    double R = emax == -100000 ? 1. : ldexp(1., emax + 1);
-    if (!(R < 1e12)) R = 1e12;
-    return R;
-}
-
-// generic path (leading coefficient trimmed to degree < 10: rare): one lane walks the whole chain serially with dynamic
-// indexing.  Its arrays live in workspace the CALLER
-// provides (LDS in ransac_roots_kernel): as private arrays they are a scratch segment, and a kernel with one is
-// dispatched with fewer resident waves.  Level k's polynomial is c differentiated n - k times, rebuilt from c on every
-// level by the same multiplications in the same order as the oracle's derivative table (identical values), so the
-// workspace is two rows instead of the 11 x 11 table.
-#define GEN_WS_DOUBLES (4 * 11)          // p[11], dp[11], rts[2][11]
-__device__ static int poly_real_roots_generic(const double *c, int n, double *roots, double *ws)
-{
-    double *p = ws, *dp = ws + 11, *rts = ws + 22;          // rts[which * 11 + i]
-    int nr_prev = 0, cur = 0;
-    for (int k = 1; k <= n; ++k) {
-        for (int i = 0; i <= n; ++i) p[i] = c[i];
-        for (int kk = n; kk > k; --kk)
-            for (int i = 0; i < kk; ++i) p[i] = p[i + 1] * (double)(i + 1);
-        if (k == 1) { rts[0] = -p[0] / p[1]; nr_prev = 1; cur = 0; continue; }
-        for (int i = 0; i < k; ++i) dp[i] = p[i + 1] * (double)(i + 1);
-        const double *crit = rts + cur * 11;
-        double *out = rts + (cur ^ 1) * 11;
-        int nout = 0;
-        double R = root_bound(p, k);
-        for (int iv = 0; iv <= nr_prev; ++iv) {
-            double a = (iv == 0) ? -R : crit[iv - 1];
-            double b = (iv == nr_prev) ? R : crit[iv];
-            if (a < -R) a = -R;
-            if (b > R) b = R;
-            if (!(a < b)) continue;
-            int sa = horner(p, k, a) > 0., sb = horner(p, k, b) > 0.;
-            if (sa == sb) continue;
-            out[nout++] = refine_root(p, dp, k, a, b, sa);
-        }
-        nr_prev = nout; cur ^= 1;
-    }
-    for (int i = 0; i < nr_prev; ++i) roots[i] = rts[cur * 11 + i];
-    return nr_prev;
-}
-
-// ---- degree-10 fast path: the polynomial of each chain level lives in registers
-// (static indexing); arithmetic identical to the generic path.
-// static-degree Estrin: terms whose coefficients are structurally zero (index > K) are
-// omitted; they would only add exact zeros, so the value equals horner(c, K, x) bit for bit.
-template <int K>
-__device__ __forceinline__ double horner_s(const double (&c)[11], double x)
+// Fixed Estrin scheme for degree <= 10 (dependency depth 7 instead of Horner's 20; the root finder is latency bound), the
+// arithmetic of horner() in oracle/geom_oracle.c.  c is anything indexable: a register array (static indices: K is the
+// level's degree) or an LDS row.  The oracle evaluates the full degree-10 scheme on coefficients zero-padded above the
+// degree; here the terms whose coefficients are structurally zero (index > K) are omitted: they would only add exact
+// zeros, so estrin<K> on a degree-K polynomial equals estrin<10> on its zero-padded row bit for bit.
+template <int K, typename C>
+__device__ __forceinline__ double estrin(const C &c, double x)
 {
     const double x2 = x * x, x4 = x2 * x2, x8 = x4 * x4;
     auto A = [&](int i) -> double {           // a_i = c[2i] + c[2i+1] x
@@ -168,13 +62,15 @@ __device__ __forceinline__ double horner_s(const double (&c)[11], double x)
     return r;
 }
 
-template <int K>
-__device__ __forceinline__ double refine_root_s(const double (&p)[11], const double (&dp)[11], double a, double b, int sa)
+// Safeguarded Newton on a bracket with a sign change (same code path as the oracle); p and dp evaluate the polynomial
+// and its derivative.
+template <typename P, typename DP>
+__device__ __forceinline__ double refine_root(P p, DP dp, double a, double b, int sa)
 {
     double xl = sa ? b : a, xh = sa ? a : b;
     double rts = 0.5 * (a + b);
     double dxold = fabs(b - a), dx = dxold;
-    double f = horner_s<K>(p, rts), df = horner_s<K - 1>(dp, rts);
+    double f = p(rts), df = dp(rts);
     for (int it = 0; it < 100; ++it) {
         int bis = ((((rts - xh) * df - f) * ((rts - xl) * df - f)) > 0.0) || (fabs(2.0 * f) > fabs(dxold * df));
         double nr;
@@ -183,10 +79,102 @@ __device__ __forceinline__ double refine_root_s(const double (&p)[11], const dou
         else { dx = f / df; nr = rts - dx; }
         if (nr == rts || fabs(nr - rts) <= 2.3e-13 * fabs(nr)) { rts = nr; break; }
         rts = nr;
-        f = horner_s<K>(p, rts); df = horner_s<K - 1>(dp, rts);
+        f = p(rts); df = dp(rts);
         if (f > 0.0) xh = rts; else xl = rts;
     }
     return rts;
+}
+
+// Root bound from binary exponents only (same integers on CPU and GPU): Fujiwara's |z| <= 2 max_i |a_{k-i}/a_k|^(1/i)
+// with |a| < 2^(ilogb(a)+1): R = 2^(1 + max_i ceil((e_{k-i} - e_k + 1)/i)).  Cauchy's bound put the outer brackets
+// orders of magnitude beyond the roots and the safeguarded Newton bisected its way back (oracle: root_bound()).
+// K: the degree where it is a compile-time constant (the register path: the loop unrolls, p keeps static indices and
+// the divisions by m are by constants), 0 where it is k at run time (the generic path).  The constant has to be a
+// template argument: as a function argument it arrived, after inlining, too late for the unsigned form of the
+// divisions: 121 more instructions over levels 2..10 and 0.5 % on the ransac stage.
+template <int K, typename C>
+__device__ __forceinline__ double root_bound(const C &p, int k_run = 0)
+{
+    const int k = K ? K : k_run;
+    const int ek = ilogb(p[k]);
+    int emax = -100000;
+#pragma unroll
+    for (int i = 0; i < k; ++i) {
+        if (p[i] != 0.) {
+            const int d = ilogb(p[i]) - ek + 1, m = k - i;
+            const int q = d >= 0 ? (d + m - 1) / m : -((-d) / m);
+            if (q > emax) emax = q;
+        }
+    }
+    double R = emax == -100000 ? 1. : ldexp(1., emax + 1);
+    if (!(R < 1e12)) R = 1e12;
+    return R;
+}
+
+// One interval of a level (the oracle's loop body in poly_real_roots): clamp the bracket to the root bound, test the
+// signs, refine.  p has degree K, dp = p'; both may be rows zero-padded to degree 10 (K = 10 then evaluates any level).
+template <int K, typename C>
+__device__ __forceinline__ bool bracket_root(const C &p, const C &dp, double a, double b, double R, bool active, double &root)
+{
+    if (a < -R) a = -R;
+    if (b > R) b = R;
+    if (!(active && a < b)) return false;
+    const int sa = estrin<K>(p, a) > 0., sb = estrin<K>(p, b) > 0.;
+    if (sa == sb) return false;
+    root = refine_root([&](double x) { return estrin<K>(p, x); }, [&](double x) { return estrin<K - 1>(dp, x); }, a, b, sa);
+    return true;
+}
+
+// generic path (leading coefficient trimmed to degree < 10: rare): one lane walks the whole chain serially with dynamic
+// indexing.  Its arrays live in workspace the CALLER provides (LDS in ransac_roots_kernel): as private arrays they would
+// be a scratch segment of their own.  The kernel has one all the same: its metadata shows 114 spilled VGPRs of the
+// degree-10 levels and 460 B of scratch (open).  Inlined: as a call this function added its
+// own frame to that segment.
+// Level k's polynomial is c differentiated n - k times, rebuilt from c on every level by the same multiplications in the
+// same order as the oracle's derivative table (identical values), so the workspace is two rows instead of the 11 x 11
+// table.  Both rows are kept zero above their degree: they are the oracle's zero-padded coefficients, evaluated by
+// estrin<10> / estrin<9>.
+#define GEN_WS_DOUBLES (4 * 11)          // p[11], dp[11], rts[2][11]
+__device__ __forceinline__ int poly_real_roots_generic(const double *c, int n, double *roots, double *ws)
+{
+    double *p = ws, *dp = ws + 11, *rts = ws + 22;          // rts[which * 11 + i]
+    int nr_prev = 0, cur = 0;
+    for (int k = 1; k <= n; ++k) {
+        for (int i = 0; i <= n; ++i) p[i] = c[i];
+        for (int kk = n; kk > k; --kk)
+            for (int i = 0; i < kk; ++i) p[i] = p[i + 1] * (double)(i + 1);
+        if (k == 1) { rts[0] = -p[0] / p[1]; nr_prev = 1; cur = 0; continue; }
+        for (int i = 0; i < k; ++i) dp[i] = p[i + 1] * (double)(i + 1);
+        for (int i = k; i <= 10; ++i) { dp[i] = 0.; if (i > k) p[i] = 0.; }
+        const double *crit = rts + cur * 11;
+        double *out = rts + (cur ^ 1) * 11;
+        int nout = 0;
+        const double R = root_bound<0>(p, k);
+        for (int iv = 0; iv <= nr_prev; ++iv) {
+            double root;
+            if (bracket_root<10>(p, dp, (iv == 0) ? -R : crit[iv - 1], (iv == nr_prev) ? R : crit[iv], R, true, root)) out[nout++] = root;
+        }
+        nr_prev = nout; cur ^= 1;
+    }
+    for (int i = 0; i < nr_prev; ++i) roots[i] = rts[cur * 11 + i];
+    return nr_prev;
+}
+
+// ---- degree-10 fast path: the polynomial of each chain level lives in registers (static indexing); arithmetic
+// identical to the generic path.  Level K's polynomial p = c10 differentiated 10 - K times and dp = p', by the
+// multiplications of the oracle's derivative table in its order; returns the root bound of p.
+template <int K>
+__device__ __forceinline__ double level_poly(const double (&c10)[11], double (&p)[11], double (&dp)[11])
+{
+#pragma unroll
+    for (int i = 0; i <= 10; ++i) p[i] = c10[i];
+#pragma unroll
+    for (int kk = 10; kk > K; --kk)
+#pragma unroll
+        for (int i = 0; i < kk; ++i) p[i] = p[i + 1] * (double)(i + 1);
+#pragma unroll
+    for (int i = 0; i < K; ++i) dp[i] = p[i + 1] * (double)(i + 1);
+    return root_bound<K>(p);
 }
 
 // Nister five-point solver (five-point.cpp EMEstimatorCallback::runKernel restated;
@@ -339,8 +327,34 @@ __device__ static int five_point_poly(const double *x1, const double *x2, double
 
 // ---------------------------------------------------------------- prepare
 // CAM (rpe_internal.h, RpeCamSrc): false = the shared K; true = the pair's two cameras, each point normalised and
-// undistorted with the camera of its own frame.  One thread per match; the cameras are workgroup-uniform scalar loads
-// and the lens test is a uniform branch, the five iterations run in registers.
+// undistorted with the camera of its own frame.  One thread per match (RpePairNormalise: the cameras are
+// workgroup-uniform scalar loads and the lens test is a uniform branch, the five iterations run in registers).
+// Returns the pair's match count.
+template <bool CAM>
+__device__ __forceinline__ int normalise_match(const float2 *__restrict__ pts1, const float2 *__restrict__ pts2,
+                                               const int *__restrict__ m_n, const double *__restrict__ K, const RpeCamSrc &cam,
+                                               double2 *__restrict__ n1, double2 *__restrict__ n2, int max_matches)
+{
+    const int pair = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
+    const int M = min(m_n[pair], max_matches);
+    const RpePairNormalise<CAM> normalise(K, cam, pair);
+    if (i < M) {
+        const long long o = (long long)pair * max_matches + i;
+        normalise(pts1[o], pts2[o], n1[o], n2[o]);
+    }
+    return M;
+}
+
+// d_n1 / d_n2 of the uploaded points of a stage call that runs no RANSAC (recoverPose, the refinement)
+template <bool CAM>
+__global__ __launch_bounds__(256) void normalise_kernel(const float2 *__restrict__ pts1, const float2 *__restrict__ pts2,
+                                                         const int *__restrict__ m_n, const double *__restrict__ K,
+                                                         const RpeCamSrc cam,
+                                                         double2 *__restrict__ n1, double2 *__restrict__ n2, int max_matches)
+{
+    normalise_match<CAM>(pts1, pts2, m_n, K, cam, n1, n2, max_matches);
+}
+
 template <bool CAM>
 __global__ __launch_bounds__(256) void ransac_prepare_kernel(const float2 *__restrict__ pts1, const float2 *__restrict__ pts2,
                                                               const int *__restrict__ m_n, const double *__restrict__ K,
@@ -350,26 +364,7 @@ __global__ __launch_bounds__(256) void ransac_prepare_kernel(const float2 *__res
                                                               int max_matches, int max_iters)
 {
     const int pair = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
-    const int M = min(m_n[pair], max_matches);
-    if (CAM) {
-        const rpe_camera *c1, *c2;
-        rpe_pair_cameras(cam, pair, c1, c2);
-        const bool lens1 = rpe_camera_has_lens(c1), lens2 = rpe_camera_has_lens(c2);
-        if (i < M) {
-            long long o = (long long)pair * max_matches + i;
-            float2 a = pts1[o], b = pts2[o];
-            n1[o] = rpe_camera_normalise(c1, lens1, a);
-            n2[o] = rpe_camera_normalise(c2, lens2, b);
-        }
-    } else {
-        const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
-        if (i < M) {
-            long long o = (long long)pair * max_matches + i;
-            float2 a = pts1[o], b = pts2[o];
-            n1[o] = make_double2(((double)a.x - cx) / fx, ((double)a.y - cy) / fy);
-            n2[o] = make_double2(((double)b.x - cx) / fx, ((double)b.y - cy) / fy);
-        }
-    }
+    const int M = normalise_match<CAM>(pts1, pts2, m_n, K, cam, n1, n2, max_matches);
     if (i == 0) {
         RpeRansacState s;
         s.best_count = 0; s.best_iter = -1; s.best_model = -1;
@@ -436,26 +431,10 @@ template <int K>
 __device__ __forceinline__ int roots_level_grp(const double (&c)[11], double &crit, int nr_prev, int j, int gbase)
 {
     double p[11], dp[11];
-#pragma unroll
-    for (int i = 0; i <= 10; ++i) p[i] = c[i];
-#pragma unroll
-    for (int kk = 10; kk > K; --kk)
-#pragma unroll
-        for (int i = 0; i < kk; ++i) p[i] = p[i + 1] * (double)(i + 1);
-#pragma unroll
-    for (int i = 0; i < K; ++i) dp[i] = p[i + 1] * (double)(i + 1);
-    const double R = root_bound_s<K>(p);
+    const double R = level_poly<K>(c, p, dp);
     const double below = __shfl_up(crit, 1);
-    double a = (j == 0) ? -R : below;
-    double b = (j == nr_prev) ? R : crit;
-    if (a < -R) a = -R;
-    if (b > R) b = R;
-    bool has = false;
     double root = 0.;
-    if (j <= nr_prev && a < b) {
-        const int sa = horner_s<K>(p, a) > 0., sb = horner_s<K>(p, b) > 0.;
-        if (sa != sb) { root = refine_root_s<K>(p, dp, a, b, sa); has = true; }
-    }
+    const bool has = bracket_root<K>(p, dp, (j == 0) ? -R : below, (j == nr_prev) ? R : crit, R, j <= nr_prev, root);
     const unsigned m = (unsigned)(__ballot(has) >> gbase) & ((1u << RG) - 1u);
     crit = __shfl(root, gbase + nth_set_bit(m, j));
     return __popc(m);
@@ -467,15 +446,7 @@ template <int K>
 __device__ __forceinline__ int roots_level_grp2(const double (&c)[11], double &crit0, double &crit1, int nr_prev, int j, int gbase)
 {
     double p[11], dp[11];
-#pragma unroll
-    for (int i = 0; i <= 10; ++i) p[i] = c[i];
-#pragma unroll
-    for (int kk = 10; kk > K; --kk)
-#pragma unroll
-        for (int i = 0; i < kk; ++i) p[i] = p[i + 1] * (double)(i + 1);
-#pragma unroll
-    for (int i = 0; i < K; ++i) dp[i] = p[i + 1] * (double)(i + 1);
-    const double R = root_bound_s<K>(p);
+    const double R = level_poly<K>(c, p, dp);
     // crit[iv - 1] and crit[iv] of this lane's interval in each round (nr_prev >= RG here)
     const double below0 = __shfl_up(crit0, 1);                    // crit[j - 1]
     const double c7 = __shfl(crit0, gbase + RG - 1), c8 = __shfl(crit1, gbase);
@@ -484,16 +455,10 @@ __device__ __forceinline__ int roots_level_grp2(const double (&c)[11], double &c
 #pragma unroll 1
     for (int rnd = 0; rnd < 2; ++rnd) {
         const int iv = rnd * RG + j;
-        double a = rnd == 0 ? (j == 0 ? -R : below0) : (j == 0 ? c7 : c8);
-        double b = (iv == nr_prev) ? R : (rnd == 0 ? crit0 : crit1);
-        if (a < -R) a = -R;
-        if (b > R) b = R;
-        bool h = false;
+        const double a = rnd == 0 ? (j == 0 ? -R : below0) : (j == 0 ? c7 : c8);
+        const double b = (iv == nr_prev) ? R : (rnd == 0 ? crit0 : crit1);
         double r = 0.;
-        if (iv <= nr_prev && a < b) {
-            const int sa = horner_s<K>(p, a) > 0., sb = horner_s<K>(p, b) > 0.;
-            if (sa != sb) { r = refine_root_s<K>(p, dp, a, b, sa); h = true; }
-        }
+        const bool h = bracket_root<K>(p, dp, a, b, R, iv <= nr_prev, r);
         if (rnd == 0) { root[0] = r; has[0] = h; } else { root[1] = r; has[1] = h; }
     }
     const unsigned mA = (unsigned)(__ballot(has[0]) >> gbase) & ((1u << RG) - 1u);
@@ -532,14 +497,9 @@ __global__ __launch_bounds__(256, 4) void ransac_roots_kernel(const RpeRansacSta
     const bool generic = (n != 10);
     if (!generic) {
         {
-            double p[11];
-#pragma unroll
-            for (int i = 0; i <= 10; ++i) p[i] = c10[i];
-#pragma unroll
-            for (int kk = 10; kk > 1; --kk)
-#pragma unroll
-                for (int i = 0; i < kk; ++i) p[i] = p[i + 1] * (double)(i + 1);
-            z = -p[0] / p[1];
+            double p[11], dp[11];
+            level_poly<1>(c10, p, dp);
+            z = -p[0] / p[1];          // level 1 in closed form, as the oracle has it
         }
         nroots = 1;
         // a level has nroots + 1 intervals; levels 2..8 cannot exceed the 8 lanes (nroots <= K - 1 <= 7 below level K <= 8),
@@ -570,7 +530,7 @@ __global__ __launch_bounds__(256, 4) void ransac_roots_kernel(const RpeRansacSta
         nroots = __shfl(nr, gbase);
     }
     // back-substitution: lane j <- root #j (five_point_roots' loop body), models compacted in root order; more than RG
-    // roots (generic path only) take a second round
+    // roots (9 or 10: either path can return them) take a second round
     int nmod = 0;
     for (int r0 = 0; r0 < nroots; r0 += RG) {                          // group-uniform trip count (1, rarely 2)
         const int ri = r0 + j;
@@ -633,7 +593,27 @@ __global__ __launch_bounds__(256, 4) void ransac_roots_kernel(const RpeRansacSta
 }
 
 // ------------------------------------------------------- Sampson inlier test
-// EMEstimatorCallback::computeError + findInliers: (float)err <= (float)(thr*thr)
+// EMEstimatorCallback::computeError + findInliers: (float)err <= (float)(thr*thr), err = num / den in the oracle's
+// operation order (count_inliers)
+__device__ __forceinline__ void sampson_terms(const double *E, double x1, double y1, double x2, double y2, double &num, double &den)
+{
+    double Ex0 = (E[0] * x1 + E[1] * y1) + E[2];
+    double Ex1 = (E[3] * x1 + E[4] * y1) + E[5];
+    double Ex2 = (E[6] * x1 + E[7] * y1) + E[8];
+    double Et0 = (E[0] * x2 + E[3] * y2) + E[6];
+    double Et1 = (E[1] * x2 + E[4] * y2) + E[7];
+    double x2tEx1 = (x2 * Ex0 + y2 * Ex1) + Ex2;
+    double a = Ex0 * Ex0, b = Ex1 * Ex1, c = Et0 * Et0, d = Et1 * Et1;
+    num = x2tEx1 * x2tEx1; den = ((a + b) + c) + d;
+}
+
+__device__ __forceinline__ int sampson_inlier(const double *E, double x1, double y1, double x2, double y2, float thr2)
+{
+    double num, den;
+    sampson_terms(E, x1, y1, x2, y2, num, den);
+    return (float)(num / den) <= thr2;
+}
+
 // The same predicate without the f64 division (a ~30-instruction IEEE sequence in the innermost RANSAC loop).
 // (float)(num / den) <= thr2  <=>  fl64(num / den) <= B, B = the largest double that still rounds (to nearest even) to a
 // float <= thr2.  num <= 0.999.. * fl(B * den) proves the left side, num >= 1.000.. * fl(B * den) disproves it (margins
@@ -651,33 +631,14 @@ __device__ __forceinline__ SampsonBound sampson_bound(float thr2)
 }
 __device__ __forceinline__ int sampson_inlier_fast(const double *E, double x1, double y1, double x2, double y2, float thr2, SampsonBound sb)
 {
-    double Ex0 = (E[0] * x1 + E[1] * y1) + E[2];
-    double Ex1 = (E[3] * x1 + E[4] * y1) + E[5];
-    double Ex2 = (E[6] * x1 + E[7] * y1) + E[8];
-    double Et0 = (E[0] * x2 + E[3] * y2) + E[6];
-    double Et1 = (E[1] * x2 + E[4] * y2) + E[7];
-    double x2tEx1 = (x2 * Ex0 + y2 * Ex1) + Ex2;
-    double a = Ex0 * Ex0, b = Ex1 * Ex1, c = Et0 * Et0, d = Et1 * Et1;
-    const double num = x2tEx1 * x2tEx1, den = ((a + b) + c) + d;
+    double num, den;
+    sampson_terms(E, x1, y1, x2, y2, num, den);
     const double p = sb.B * den;
     if (den > 0. && p < 1e300) {
         if (num <= p * (1. - 0x1p-40)) return 1;
         if (num >= p * (1. + 0x1p-40)) return 0;
     }
     return (float)(num / den) <= thr2;
-}
-
-__device__ __forceinline__ int sampson_inlier(const double *E, double x1, double y1, double x2, double y2, float thr2)
-{
-    double Ex0 = (E[0] * x1 + E[1] * y1) + E[2];
-    double Ex1 = (E[3] * x1 + E[4] * y1) + E[5];
-    double Ex2 = (E[6] * x1 + E[7] * y1) + E[8];
-    double Et0 = (E[0] * x2 + E[3] * y2) + E[6];
-    double Et1 = (E[1] * x2 + E[4] * y2) + E[7];
-    double x2tEx1 = (x2 * Ex0 + y2 * Ex1) + Ex2;
-    double a = Ex0 * Ex0, b = Ex1 * Ex1, c = Et0 * Et0, d = Et1 * Et1;
-    float err = (float)(x2tEx1 * x2tEx1 / (((a + b) + c) + d));
-    return err <= thr2;
 }
 
 // RANSACUpdateNumIters with log() terms tabulated on the host per (M, goodCount)
@@ -692,10 +653,10 @@ __device__ __forceinline__ int update_niters(const double *nit_denom, const int 
 
 // ------------------------------------------------------------------ score
 // One workgroup per (pair, group of SCORE_GROUP iterations): a wave scores its models one after the other, so the group
-// size sets the kernel's latency (the later RANSAC rounds run few pairs and are pure latency): 16 iterations per
-// workgroup = 4x the workgroups of the 64-iteration grouping, each a quarter as long.  The K-normalised matches sit in LDS; each of
-// the 4 waves scores a different model (lanes stride over the matches, Sampson error f64 -> f32
-// compare, wave-shuffle popcount), so there is no cross-wave reduction.  Counts go to HBM.
+// size sets the kernel's latency (the later RANSAC rounds run few pairs and are pure latency): SCORE_GROUP = 8
+// iterations per workgroup = 8x the workgroups of a 64-iteration grouping, each an eighth as long.  The normalised
+// matches sit in LDS; each of the 4 waves scores a different model (lanes stride over the matches, Sampson error
+// f64 -> f32 compare, wave-shuffle popcount), so there is no cross-wave reduction.  Counts go to HBM.
 template <bool CAM>
 __global__ __launch_bounds__(256) void ransac_score_kernel(const double2 *__restrict__ n1, const double2 *__restrict__ n2,
                                                             const RpeRansacState *__restrict__ st, const double *__restrict__ models,
@@ -765,11 +726,6 @@ __global__ __launch_bounds__(256) void ransac_score_kernel(const double2 *__rest
 // (who is a record breaker), per-lane replay of its <= 10 models against that prefix, exclusive prefix
 // min of the resulting niters, first lane whose iteration index reaches its niters = the break.
 // Bit-identical to the serial loop (it was 0.25-1.1 ms of single-lane latency per step).
-__device__ __forceinline__ int niters_cap(const double *nit_denom, const int *nit_round, double num, int M, int good, int niters)
-{
-    return update_niters(nit_denom, nit_round, num, M, good, niters);
-}
-
 __global__ __launch_bounds__(256) void ransac_update_kernel(RpeRansacState *__restrict__ st, const double *__restrict__ models,
                                                             const int *__restrict__ nmodels, const int *__restrict__ counts,
                                                             const double *__restrict__ nit_denom, const int *__restrict__ nit_round,
@@ -818,7 +774,7 @@ __global__ __launch_bounds__(256) void ransac_update_kernel(RpeRansacState *__re
             for (int m = 0; m < RPE_MAX_MODELS; ++m) {
                 if (m < nm && c[m] > max(run, 4)) {
                     run = c[m]; wm = m;
-                    lmin = min(lmin, niters_cap(nit_denom, nit_round, nit_num, M, c[m], 0x7FFFFFFF));
+                    lmin = min(lmin, update_niters(nit_denom, nit_round, nit_num, M, c[m], 0x7FFFFFFF));
                 }
             }
             // exclusive prefix min of niters
@@ -903,6 +859,14 @@ static void launch_mask(rpe_handle *h, const RpeRun &r, const int *status)
 {
     launch_cam(r, ransac_mask_kernel<true>, ransac_mask_kernel<false>, dim3(r.pairs), dim3(256), 0, h->stream,
                h->d_n1, h->d_n2, h->d_rstate, h->d_K, r.cam, h->cfg.ransac_threshold, status, h->d_mask, h->cfg.max_matches);
+}
+
+// stage forms that run no RANSAC (recoverPose, the refinement over uploaded points): d_n1 / d_n2 of the uploaded points
+void rpe_launch_normalise(rpe_handle *h, const RpeRun &r)
+{
+    const int mm = h->cfg.max_matches;
+    launch_cam(r, normalise_kernel<true>, normalise_kernel<false>, dim3((mm + 255) / 256, r.pairs), dim3(256), 0, h->stream,
+               h->d_pts1, h->d_pts2, h->d_m_n, h->d_K, r.cam, h->d_n1, h->d_n2, mm);
 }
 
 void rpe_launch_ransac(rpe_handle *h, const RpeRun &r, bool want_mask)
@@ -1068,8 +1032,19 @@ __device__ static int triangulate_one(const double *R, const double *t, double x
     return good;
 }
 
-// CAM = true: the matches are read as d_n1 / d_n2, the normalised (and undistorted) coordinates the RANSAC of the same
-// call worked on, instead of being normalised again with K
+// The normalised coordinates of match o for recover_pose_kernel and pose_structure_kernel.  CAM = true: read from
+// d_n1 / d_n2, the normalised and undistorted coordinates the RANSAC of the same call worked on (or normalise_kernel's,
+// stage form); CAM = false: normalised again with K, the same expression and so the same bits as d_n1 / d_n2 (reading
+// those here too did not pass the timing check of DESIGN section 4, round 8).
+template <bool CAM>
+__device__ __forceinline__ void pose_match(const RpePairNormalise<false> &with_K, const float2 *__restrict__ pts1,
+                                           const float2 *__restrict__ pts2, const double2 *__restrict__ n1,
+                                           const double2 *__restrict__ n2, long long o, double2 &a, double2 &b)
+{
+    if (CAM) { a = n1[o]; b = n2[o]; }
+    else with_K(pts1[o], pts2[o], a, b);
+}
+
 template <bool TAB, bool CAM>
 __global__ __launch_bounds__(256) void recover_pose_kernel(const double *__restrict__ Eall, const float2 *__restrict__ pts1,
                                                             const float2 *__restrict__ pts2, const double2 *__restrict__ n1,
@@ -1102,24 +1077,16 @@ __global__ __launch_bounds__(256) void recover_pose_kernel(const double *__restr
     for (int e = 0; e < 9; ++e) E[e] = Eall[pair * 9 + e];
     decompose_essential(E, R1, R2, tt);
     tn[0] = -tt[0]; tn[1] = -tt[1]; tn[2] = -tt[2];
-    double fx = 1., fy = 1., cx = 0., cy = 0.;
-    if (!CAM) { fx = K[0]; fy = K[4]; cx = K[2]; cy = K[5]; }
+    const RpePairNormalise<false> with_K(K, RpeCamSrc{}, pair);
     int g1 = 0, g2 = 0, g3 = 0, g4 = 0;
     for (int i = tid; i < M; i += 256) {
-        double x1, y1, x2, y2;
-        if (CAM) {
-            const double2 a = n1[(long long)pair * max_matches + i], b = n2[(long long)pair * max_matches + i];
-            x1 = a.x; y1 = a.y; x2 = b.x; y2 = b.y;
-        } else {
-            float2 a = pts1[(long long)pair * max_matches + i], b = pts2[(long long)pair * max_matches + i];
-            x1 = ((double)a.x - cx) / fx; y1 = ((double)a.y - cy) / fy;
-            x2 = ((double)b.x - cx) / fx; y2 = ((double)b.y - cy) / fy;
-        }
+        double2 a, b;
+        pose_match<CAM>(with_K, pts1, pts2, n1, n2, (long long)pair * max_matches + i, a, b);
         double P[3];
-        g1 += triangulate_one(R1, tt, x1, y1, x2, y2, P);
-        g2 += triangulate_one(R2, tt, x1, y1, x2, y2, P);
-        g3 += triangulate_one(R1, tn, x1, y1, x2, y2, P);
-        g4 += triangulate_one(R2, tn, x1, y1, x2, y2, P);
+        g1 += triangulate_one(R1, tt, a.x, a.y, b.x, b.y, P);
+        g2 += triangulate_one(R2, tt, a.x, a.y, b.x, b.y, P);
+        g3 += triangulate_one(R1, tn, a.x, a.y, b.x, b.y, P);
+        g4 += triangulate_one(R2, tn, a.x, a.y, b.x, b.y, P);
     }
     g1 = wave_sum(g1); g2 = wave_sum(g2); g3 = wave_sum(g3); g4 = wave_sum(g4);
     if ((tid & 63) == 0) { atomicAdd(&s_g[0], g1); atomicAdd(&s_g[1], g2); atomicAdd(&s_g[2], g3); atomicAdd(&s_g[3], g4); }
@@ -1156,23 +1123,15 @@ __global__ __launch_bounds__(256) void pose_structure_kernel(const float2 *__res
     for (int e = 0; e < 9; ++e) R[e] = Rall[pair * 9 + e];
 #pragma unroll
     for (int e = 0; e < 3; ++e) t[e] = tall[pair * 3 + e];
-    double fx = 1., fy = 1., cx = 0., cy = 0.;
-    if (!CAM) { fx = K[0]; fy = K[4]; cx = K[2]; cy = K[5]; }
+    const RpePairNormalise<false> with_K(K, RpeCamSrc{}, pair);
     for (int i = tid; i < max_matches; i += 256) {
         const long long o = (long long)pair * max_matches + i;
         double P[3] = {0., 0., 0.};
         int g = 0;
         if (i < M) {
-            double x1, y1, x2, y2;
-            if (CAM) {
-                const double2 a = n1[o], b = n2[o];
-                x1 = a.x; y1 = a.y; x2 = b.x; y2 = b.y;
-            } else {
-                float2 a = pts1[o], b = pts2[o];
-                x1 = ((double)a.x - cx) / fx; y1 = ((double)a.y - cy) / fy;
-                x2 = ((double)b.x - cx) / fx; y2 = ((double)b.y - cy) / fy;
-            }
-            g = triangulate_one(R, t, x1, y1, x2, y2, P);
+            double2 a, b;
+            pose_match<CAM>(with_K, pts1, pts2, n1, n2, o, a, b);
+            g = triangulate_one(R, t, a.x, a.y, b.x, b.y, P);
         }
         pose_mask[o] = (uint8_t)g;
         points[o * 3] = P[0]; points[o * 3 + 1] = P[1]; points[o * 3 + 2] = P[2];
@@ -1194,8 +1153,8 @@ void rpe_launch_pose(rpe_handle *h, const RpeRun &r, bool fused)
 {
     const RpeFeatSrc &f = r.feat;
     const bool tab = fused && f.tab;
-    // the camera instances read d_n1 / d_n2: ransac_prepare_kernel<true> (fused) or rpe_launch_camera_normalise (stage
-    // form) of the same call has filled them
+    // the camera instances read d_n1 / d_n2: ransac_prepare_kernel<true> (fused) or rpe_launch_normalise (stage form) of
+    // the same call has filled them
     launch_cam(r, tab ? recover_pose_kernel<true, true> : recover_pose_kernel<false, true>,
                tab ? recover_pose_kernel<true, false> : recover_pose_kernel<false, false>, dim3(r.pairs), dim3(256), 0, h->stream,
                h->d_E, h->d_pts1, h->d_pts2, h->d_n1, h->d_n2, h->d_m_n, fused ? (const int *)h->d_found : (const int *)nullptr,
@@ -1538,44 +1497,6 @@ __global__ __launch_bounds__(256) void pose_refine_kernel(const double2 *__restr
     }
 }
 
-// normalised points of a stage call (the batch path leaves them in d_n1 / d_n2): same expression as ransac_prepare_kernel
-template <bool CAM>
-__global__ __launch_bounds__(256) void refine_normalise_kernel(const float2 *__restrict__ pts1, const float2 *__restrict__ pts2,
-                                                                const int *__restrict__ m_n, const double *__restrict__ K,
-                                                                const RpeCamSrc cam,
-                                                                double2 *__restrict__ n1, double2 *__restrict__ n2, int max_matches)
-{
-    const int pair = blockIdx.y, i = blockIdx.x * 256 + threadIdx.x;
-    const int M = min(m_n[pair], max_matches);
-    if (CAM) {
-        const rpe_camera *c1, *c2;
-        rpe_pair_cameras(cam, pair, c1, c2);
-        const bool lens1 = rpe_camera_has_lens(c1), lens2 = rpe_camera_has_lens(c2);
-        if (i < M) {
-            long long o = (long long)pair * max_matches + i;
-            float2 a = pts1[o], b = pts2[o];
-            n1[o] = rpe_camera_normalise(c1, lens1, a);
-            n2[o] = rpe_camera_normalise(c2, lens2, b);
-        }
-    } else {
-        const double fx = K[0], fy = K[4], cx = K[2], cy = K[5];
-        if (i < M) {
-            long long o = (long long)pair * max_matches + i;
-            float2 a = pts1[o], b = pts2[o];
-            n1[o] = make_double2(((double)a.x - cx) / fx, ((double)a.y - cy) / fy);
-            n2[o] = make_double2(((double)b.x - cx) / fx, ((double)b.y - cy) / fy);
-        }
-    }
-}
-
-// stage forms of the camera path (rpe_recover_pose_cameras, rpe_refine_pose_points_cameras): d_n1 / d_n2 of the uploaded points
-void rpe_launch_camera_normalise(rpe_handle *h, const RpeRun &r)
-{
-    const int mm = h->cfg.max_matches;
-    hipLaunchKernelGGL(refine_normalise_kernel<true>, dim3((mm + 255) / 256, r.pairs), dim3(256), 0, h->stream,
-                       h->d_pts1, h->d_pts2, h->d_m_n, h->d_K, r.cam, h->d_n1, h->d_n2, mm);
-}
-
 // rpe_undistort_points: n pixels of one camera -> normalised, undistorted coordinates; one thread per point, the camera a
 // uniform scalar load, one 16-byte store per point
 __global__ __launch_bounds__(256) void undistort_points_kernel(const float2 *__restrict__ pts, int n, const rpe_camera *__restrict__ cam,
@@ -1597,10 +1518,7 @@ void rpe_launch_refine(rpe_handle *h, const RpeRun &r, int max_iters, bool from_
 {
     const int mm = h->cfg.max_matches, B = r.pairs;
     if (from_batch) launch_mask(h, r, (const int *)h->d_status);
-    else if (r.cam.cams) rpe_launch_camera_normalise(h, r);
-    else
-        hipLaunchKernelGGL(refine_normalise_kernel<false>, dim3((mm + 255) / 256, B), dim3(256), 0, h->stream,
-                           h->d_pts1, h->d_pts2, h->d_m_n, h->d_K, r.cam, h->d_n1, h->d_n2, mm);
+    else rpe_launch_normalise(h, r);
     const double *Rin = from_batch ? h->d_R : h->d_ref_R0, *tin = from_batch ? h->d_t : h->d_ref_t0;
     const int *status = from_batch ? h->d_status : nullptr, *inl = from_batch ? h->d_inliers : nullptr;
     // the inliers staged in LDS, or, above the cut, as 16-bit indices

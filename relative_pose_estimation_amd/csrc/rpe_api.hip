@@ -1686,7 +1686,7 @@ static int stage_recover_pose(rpe_handle *h, const char *who, const double *h_E,
     int rc = stage_begin(h, who, h_pts1, h_pts2, m, B, K, cam1, cam2, run);
     if (rc) return rc;
     HIPCHK(h, hipMemcpyAsync(h->d_E, h_E, sizeof(double) * 9 * B, hipMemcpyHostToDevice, h->stream));
-    if (run.cam.cams) rpe_launch_camera_normalise(h, run);      // recover_pose_kernel's camera instances read d_n1 / d_n2
+    if (run.cam.cams) rpe_launch_normalise(h, run);             // recover_pose_kernel's camera instances read d_n1 / d_n2
     rpe_launch_pose(h, run, false);
     HIPCHK(h, hipGetLastError());
     return rpe_fetch_results(h, B, R, t, inliers, nullptr, nullptr);

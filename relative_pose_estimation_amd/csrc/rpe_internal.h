@@ -146,6 +146,36 @@ __device__ __forceinline__ double2 rpe_camera_normalise(const rpe_camera *c, boo
     return make_double2(x, y);
 }
 
+// The normalisation of pair `pair`'s matches, the one every geometry kernel's d_n1 / d_n2 come from.  Built once per
+// thread in front of the per-match part: the four scalars of K, or the pair's two cameras and their lens tests
+// (workgroup-uniform scalar loads, a uniform branch).  Applied per match: the two pixel points of a match -> the
+// normalised (CAM: and undistorted, each with the camera of its own frame) coordinates.
+template <bool CAM>
+struct RpePairNormalise {
+    const rpe_camera *c1, *c2;
+    bool lens1, lens2;
+    double fx, fy, cx, cy;
+    __device__ __forceinline__ RpePairNormalise(const double *__restrict__ K, const RpeCamSrc &src, int pair)
+    {
+        if (CAM) {
+            rpe_pair_cameras(src, pair, c1, c2);
+            lens1 = rpe_camera_has_lens(c1); lens2 = rpe_camera_has_lens(c2);
+        } else {
+            fx = K[0]; fy = K[4]; cx = K[2]; cy = K[5];
+        }
+    }
+    __device__ __forceinline__ void operator()(float2 a, float2 b, double2 &na, double2 &nb) const
+    {
+        if (CAM) {
+            na = rpe_camera_normalise(c1, lens1, a);
+            nb = rpe_camera_normalise(c2, lens2, b);
+        } else {
+            na = make_double2(((double)a.x - cx) / fx, ((double)a.y - cy) / fy);
+            nb = make_double2(((double)b.x - cx) / fx, ((double)b.y - cy) / fy);
+        }
+    }
+};
+
 // Inclusive prefix operations over the 64 lanes with DPP row shifts / row broadcasts: 6 v_<op>_dpp instead of 6 rounds of
 // ds_bpermute + select + op (~30 vector + LDS instructions).  Shifted-out lanes read the `old` operand, the identity.
 // The wave total is the value of lane 63 (__builtin_amdgcn_readlane(x, 63)).
@@ -396,7 +426,7 @@ void rpe_launch_pose(rpe_handle *h, const RpeRun &r, bool set_status);
 void rpe_launch_structure(rpe_handle *h, const RpeRun &r);
 void rpe_launch_refine(rpe_handle *h, const RpeRun &r, int max_iters, bool from_batch);
 int rpe_launch_scale_links(rpe_handle *h, int L, int min_shared);
-void rpe_launch_camera_normalise(rpe_handle *h, const RpeRun &r);
+void rpe_launch_normalise(rpe_handle *h, const RpeRun &r);
 void rpe_launch_undistort(rpe_handle *h, const float2 *d_pts, int n, const rpe_camera *d_cam, double2 *d_out);
 
 // per-stage hipEvents on the handle's stream (rpe_set_profiling / rpe_get_stage_ms)

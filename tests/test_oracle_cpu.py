@@ -250,3 +250,18 @@ def test_sift_oracle_properties(oracle):
     E, m, info = oracle.find_essential(p1, p2, K)
     n, Re, te = oracle.recover_pose(E, p1, p2, K)
     assert geometry.rotation_error(Re, R) < 1.5
+
+
+@pytest.mark.parametrize("family", ["A", "B", "C"])
+def test_geom_cases_reach_the_rare_root_paths(oracle, K_vga, family):
+    """The families of tests/geom_cases.py take the root-chain paths they are meant for.  poly_counters() over a whole
+    family (solves, degree below 10, two-round levels, more than 8 roots), numpy 2.2.6's default_rng streams:
+    A [256, 9, 14, 0], B [710, 12, 36, 6], C [8581, 0, 141, 0]; the floors are about half of that."""
+    from tests import geom_cases
+    oracle.poly_counters()
+    for p1, p2 in geom_cases.FAMILIES[family]():
+        oracle.find_essential(p1, p2, K_vga)
+    got = oracle.poly_counters()
+    assert got[0] > 0
+    for count, floor in zip(got[1:], geom_cases.FLOORS[family]):
+        assert count == 0 if floor is None else count >= floor, (family, got)

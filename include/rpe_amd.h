@@ -427,6 +427,68 @@ int rpe_scale_links(rpe_handle *h, int L, const int32_t *pair_a, const int32_t *
 int rpe_guided_matches(rpe_handle *h, int B, const double *R, const double *t, double gate_px, int max_distance,
                        int32_t *qidx, int32_t *tidx, int32_t *dist, float *pts1, float *pts2, int32_t *n_matches);
 
+/* ------------------------------------------- homography / rotation-only */
+/* A second geometric model over the matches of a pair (NOT in the reference, whose only model is the essential matrix):
+ * a homography by RANSAC over the run's own subset stream, and a rotation fitted to the homography's inliers.  Under a
+ * pure rotation, or a baseline far below the scene depth, findEssentialMat -> recoverPose is degenerate and reports
+ * RPE_PAIR_OK all the same; there the homography explains most matches and the fitted rotation explains as many, while
+ * on a general scene both explain few.  counts[] puts the three inlier counts side by side; what ratio of them names a
+ * pair "rotation-only" or "planar" is the caller's policy (geometry.classify_pair).
+ * The rule, for one pair.  All arithmetic f64, no contraction; a comparison with a NaN is false.
+ *  Inputs: matches i < M with the normalised points a_i = (x, y) of image 1 and b_i of image 2 exactly as the geometry
+ *   stages use them (normalised with K or, after a *_cameras run, normalised and undistorted with the camera of each
+ *   frame).  thr = threshold_px / f, f = the focal scale RANSAC uses ((fx + fy) / 2, or the mean of that over the pair's
+ *   two cameras); thr2 = thr * thr (a double; no float cast).
+ *  Helpers: p = (x, y, 1); cross(a, b) = (a1*b2 - a2*b1, a2*b0 - a0*b2, a0*b1 - a1*b0); dot(a, b) = (a0*b0 + a1*b1) + a2*b2;
+ *   adj(A) = the matrix with rows cross(c1, c2), cross(c2, c0), cross(c0, c1), c0 c1 c2 the columns of A.
+ *  Sample: iteration it < iters takes the first four of the five indices of findEssentialMat's subset stream for M
+ *   (ptsetreg.cpp getSubset, RNG seeded (uint64)-1; the stream depends on M alone): points p0 .. p3 of image 1 and
+ *   q0 .. q3 of image 2.
+ *  Four-point model, closed form, no pivoting:
+ *   lambda = (dot(cross(p1, p2), p3), dot(cross(p2, p0), p3), dot(cross(p0, p1), p3)); A = the matrix with columns
+ *   lambda_k * p_k (A[r][k] = lambda_k * p_k[r]); mu and B the same from q; J = adj(A);
+ *   H[r][c] = (B[r][0]*J[0][c] + B[r][1]*J[1][c]) + B[r][2]*J[2][c]; n = sqrt(the sum of the nine squares H[r][c]*H[r][c],
+ *   row-major, added left to right); every entry is divided by n.  The model is invalid when a lambda_k or a mu_k
+ *   equals 0 or an entry after the division is not finite.  Gauge: H is negated when
+ *   (H[2][0]*x + H[2][1]*y) + H[2][2] < 0 at p0.  G = adj(H) (not divided by the determinant), negated by the same test
+ *   at q0.
+ *  Transfer test T(F, p -> q): u = (F[0][0]*x + F[0][1]*y) + F[0][2], v and w likewise from rows 1 and 2 at p = (x, y);
+ *   dx = u - qx*w, dy = v - qy*w; true iff w > 0 and (dx*dx + dy*dy) <= thr2 * (w*w).  No division.
+ *   Match i is an inlier of H iff T(H, a_i -> b_i) and T(G, b_i -> a_i).
+ *  Election: all `iters` samples are evaluated (no early stop: the counts do not depend on how the work is launched); the
+ *   winner is the valid model with the most inliers, ties to the lowest iteration; mask = the winner's inlier set.
+ *  Rotation fit over the winner's inliers: bearings a^ = (x, y, 1) / sqrt((x*x + y*y) + 1), b^ likewise;
+ *   C[r][c] = sum of b^_r * a^_c, added in this fixed order: lane l of 256 adds its inliers i = l, l + 256, ... in
+ *   ascending order starting from 0; inside each group of 64 lanes the partial sums are combined by the butterfly
+ *   v += v(lane ^ 32), ^ 16, ^ 8, ^ 4, ^ 2, ^ 1; the four group totals are added as ((g0 + g1) + g2) + g3.
+ *   C = U S V^T by the library's one-sided Jacobi SVD (recoverPose's), singular values sorted descending, u2 = u0 x u1;
+ *   R_rot[r][c] = (u0[r]*v0[c] + u1[r]*v1[c]) + (d*u2[r])*v2[c], d = -1 when the determinant of the matrix with rows
+ *   v0 v1 v2 is negative and 1 otherwise (= U diag(1, 1, det(U V^T)) V^T).  n_rot = the number of matches i < M with
+ *   T(R_rot, a_i -> b_i) and T(R_rot^T, b_i -> a_i), no gauge step, evaluated with exactly the bits of R_rot that are
+ *   returned.  A non-finite R_rot is returned as zeros with n_rot = 0.
+ *  Codes (info[4 p]): RPE_HOMOGRAPHY_OK; RPE_HOMOGRAPHY_SKIPPED: M < 6 (the subset stream starts at 6) or, batch form, a
+ *   pair whose status is not RPE_PAIR_OK; RPE_HOMOGRAPHY_NONE: no valid model.  H, R_rot, mask, n_H, n_rot and the rest
+ *   of info are zero for the last two.
+ * Outputs (host, any may be NULL): H[B*9] in normalised coordinates (pixels: K2 H K1^-1), unit Frobenius norm, in the gauge
+ * above; R_rot[B*9]; mask[B*max_matches], zero past M; counts[B*3] = {n_H, n_rot, n_E}, n_E = findEssentialMat's inlier
+ * count of the run (the sum of rpe_fetch_structure's ransac_mask; -1 in the stage form, which runs no essential RANSAC);
+ * info[B*4] = {RPE_HOMOGRAPHY_* code, winning iteration, number of valid models, 0}.
+ * rpe_pair_homographies: over the first B pairs of the last batch / stream / pair list / *_cameras run.  Validity rules of
+ * rpe_fetch_structure: refused after a chunked host batch, a stage call, a put, once the store was resized under a pair
+ * list, and for B > pairs of the last run.  The results live in buffers of their own: rpe_fetch_results,
+ * rpe_fetch_structure, rpe_refine_poses, rpe_scale_links, rpe_guided_matches and rpe_gather_poses return the same bits
+ * afterwards.  rpe_find_homography: stage form over the caller's matches (pts as in rpe_find_essential), one K; goes
+ * through the workspace like every stage call.
+ * RPE_ERR_INVALID: iters outside 1 .. rpe_config.ransac_max_iters, threshold_px not finite or <= 0.  All checks are
+ * host-side; nothing is launched and the handle stays usable after a refusal.  Bit-deterministic (no floating-point
+ * atomics). */
+enum { RPE_HOMOGRAPHY_OK = 0, RPE_HOMOGRAPHY_SKIPPED = 1, RPE_HOMOGRAPHY_NONE = 2 };
+int rpe_pair_homographies(rpe_handle *h, int B, int iters, double threshold_px,
+                          double *H, double *R_rot, uint8_t *mask, int32_t *counts, int32_t *info);
+int rpe_find_homography(rpe_handle *h, const float *h_pts1, const float *h_pts2, const int32_t *m, int B,
+                        const double K[9], int iters, double threshold_px,
+                        double *H, double *R_rot, uint8_t *mask, int32_t *counts, int32_t *info);
+
 /* ---------------------------------------------------------- stage entry */
 /* replaces extractor.detectAndCompute(image, None) (pose_estimator.py:108)
  * for n_images images (n_images <= 2*max_batch).  kps[n_images*cap],

@@ -28,6 +28,7 @@ STAGE_COUNT = 12
 ORDER_BGR, ORDER_RGB = 0, 1
 REFINE_OK, REFINE_SKIPPED, REFINE_REJECTED = 0, 1, 2   # info[:, 0] of refine_poses (include/rpe_amd.h RPE_REFINE_*)
 LINK_OK, LINK_PAIR_FAILED, LINK_TOO_FEW = 0, 1, 2      # code[] of scale_links (include/rpe_amd.h RPE_LINK_*)
+HOMOGRAPHY_OK, HOMOGRAPHY_SKIPPED, HOMOGRAPHY_NONE = 0, 1, 2   # info[:, 0] of pair_homographies (include/rpe_amd.h RPE_HOMOGRAPHY_*)
 UNDISTORT_ITERS = 5               # RPE_UNDISTORT_ITERS: fixed-point rounds of the camera path's undistortion
 
 EXPORTS = [
@@ -50,6 +51,7 @@ EXPORTS = [
     "rpe_undistort_points", "rpe_find_essential_cameras", "rpe_recover_pose_cameras", "rpe_refine_pose_points_cameras",
     "rpe_fetch_match_indices", "rpe_scale_links",
     "rpe_guided_matches", "rpe_match_hamming_guided",
+    "rpe_pair_homographies", "rpe_find_homography",
 ]
 
 
@@ -225,6 +227,10 @@ def load():
     lib.rpe_guided_matches.restype = C.c_int
     lib.rpe_match_hamming_guided.argtypes = [vp, vp, vp, i32p, vp, vp, i32p, C.c_int, vp, vp, vp, C.c_double, C.c_int, i32p, i32p, i32p, i32p]
     lib.rpe_match_hamming_guided.restype = C.c_int
+    lib.rpe_pair_homographies.argtypes = [vp, C.c_int, C.c_int, C.c_double, vp, vp, vp, i32p, i32p]
+    lib.rpe_pair_homographies.restype = C.c_int
+    lib.rpe_find_homography.argtypes = [vp, vp, vp, i32p, C.c_int, vp, C.c_int, C.c_double, vp, vp, vp, i32p, i32p]
+    lib.rpe_find_homography.restype = C.c_int
     _lib = lib
     return lib
 
@@ -489,6 +495,34 @@ class Engine:
                                                     None if Rc is None else _p(Rc), None if tc is None else _p(tc), gate,
                                                     int(max_distance), _p(q), _p(ti), _p(d), _p(nm)))
         return q, ti, d, nm
+
+    # ---- homography / rotation-only (rpe_pair_homographies / rpe_find_homography; not in the reference)
+    def _homography_outs(self, B):
+        return (np.zeros((B, 3, 3)), np.zeros((B, 3, 3)), np.zeros((B, self.max_matches), np.uint8),
+                np.zeros((B, 3), np.int32), np.zeros((B, 4), np.int32))
+
+    def pair_homographies(self, B, iters=256, threshold_px=None):
+        """A homography by RANSAC over the matches of each of the first B pairs of the last batch / stream / pair list
+        (rpe_pair_homographies), the rotation fitted to its inliers, and the inlier counts of the three models.
+        `iters` samples, all evaluated; threshold_px = the transfer gate in pixels (None = the handle's
+        ransac_threshold).  Returns (H f64[B, 3, 3] in normalised coordinates, unit norm; R_rot f64[B, 3, 3];
+        mask bool[B, mm], H's inliers; counts i32[B, 3] = (n_H, n_rot, n_E); info i32[B, 4] = (HOMOGRAPHY_* code, winning
+        iteration, valid models, 0)).  The run's own results are not modified."""
+        H, R, mask, counts, info = self._homography_outs(B)
+        thr = float(self.cfg.ransac_threshold if threshold_px is None else threshold_px)
+        self._chk(self.lib.rpe_pair_homographies(self.h, B, int(iters), thr, _p(H), _p(R), _p(mask), _p(counts), _p(info)))
+        return H, R, mask.astype(bool), counts, info
+
+    def find_homography(self, pts1, pts2, K, iters=256, threshold_px=None):
+        """Stage form of pair_homographies, the sibling of find_essential: per pair the caller's matched pixels (n, 2)
+        f32 of both images, one K.  Same outputs; counts[:, 2] (n_E) is -1: no essential RANSAC runs."""
+        p1, p2, m = self._pack_points(pts1, pts2)
+        B = len(m); K = np.ascontiguousarray(K, np.float64)
+        H, R, mask, counts, info = self._homography_outs(B)
+        thr = float(self.cfg.ransac_threshold if threshold_px is None else threshold_px)
+        self._chk(self.lib.rpe_find_homography(self.h, _p(p1), _p(p2), _p(m), B, _p(K), int(iters), thr,
+                                               _p(H), _p(R), _p(mask), _p(counts), _p(info)))
+        return H, R, mask.astype(bool), counts, info
 
     # ---- frame store (rpe_frames_* / rpe_enqueue_pairs; not in the reference)
     def frames_reserve(self, n_slots):

@@ -1657,3 +1657,297 @@ int rpe_launch_scale_links(rpe_handle *h, int L, int min_shared)
                        h->d_link_stats, h->d_link_n, h->d_link_code);
     return RPE_OK;
 }
+
+// ------------------------------------------------------------ homography / rotation-only
+// rpe_pair_homographies / rpe_find_homography (NOT in the reference; include/rpe_amd.h states the rule): a homography by
+// RANSAC over the first four indices of findEssentialMat's subset stream, the rotation fitted to its inliers, and the
+// inlier count of that rotation.  One 256-thread workgroup per pair, f64 throughout, no contraction.
+//   rounds   HG_ROUND = 256 samples at a time: thread j solves sample j in registers (closed form, static indexing, no
+//            scratch) and parks H and G = adj(H), 18 doubles, in LDS; the four waves then score the round's valid models
+//            round-robin (wave w: models w, w + 4, ...), lanes striding the matches, wave_sum for the count.  A wave meets
+//            its models in ascending iteration order and replaces its best on a strictly larger count only, so its best
+//            is its lowest iteration of that count; the cross-wave election compares (count, iteration).
+//   points   the pair's normalised points in LDS behind the models, as ransac_score_kernel holds them
+//            (max_matches <= HG_LDS_MATCHES: 32 B per match); read from d_n1 / d_n2 directly above the cut
+//   winner   solved again by every thread from its sample (the same code on the same operands: the same bits), then the
+//            mask, the bearing sums C (block_sum_f64: lane partials in strided order, xor butterfly, waves in wave
+//            order), recoverPose's 3x3 Jacobi on every lane (identical operands), and n_rot
+// Dynamic LDS (base 16-byte aligned): [HG_ROUND][18] f64 models = 36 KB, then [2][max_matches] double2 points: 52 KB at
+// the default 500 matches, 100 KB at the cut -- above the 64 KB a kernel gets without the function attribute.
+#define HG_ROUND 256
+#define HG_MODEL_DOUBLES 18
+#define HG_LDS_MATCHES 2048
+
+__device__ __forceinline__ double hg_dot(const double (&a)[3], const double (&b)[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
+__device__ __forceinline__ void hg_cross(const double (&a)[3], const double (&b)[3], double (&c)[3])
+{
+    c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
+}
+
+// adj(A), A row-major: rows cross(c1, c2), cross(c2, c0), cross(c0, c1) of A's columns
+__device__ __forceinline__ void hg_adj(const double (&A)[9], double (&J)[9])
+{
+    const double c0[3] = {A[0], A[3], A[6]}, c1[3] = {A[1], A[4], A[7]}, c2[3] = {A[2], A[5], A[8]};
+    double r0[3], r1[3], r2[3];
+    hg_cross(c1, c2, r0); hg_cross(c2, c0, r1); hg_cross(c0, c1, r2);
+    J[0] = r0[0]; J[1] = r0[1]; J[2] = r0[2]; J[3] = r1[0]; J[4] = r1[1]; J[5] = r1[2]; J[6] = r2[0]; J[7] = r2[1]; J[8] = r2[2];
+}
+
+// lambda of four points and the matrix with columns lambda_k * p_k; false when a lambda_k is 0
+__device__ __forceinline__ bool hg_basis(const double2 (&s)[4], double (&A)[9])
+{
+    const double p0[3] = {s[0].x, s[0].y, 1.}, p1[3] = {s[1].x, s[1].y, 1.}, p2[3] = {s[2].x, s[2].y, 1.}, p3[3] = {s[3].x, s[3].y, 1.};
+    double c[3];
+    hg_cross(p1, p2, c); const double l0 = hg_dot(c, p3);
+    hg_cross(p2, p0, c); const double l1 = hg_dot(c, p3);
+    hg_cross(p0, p1, c); const double l2 = hg_dot(c, p3);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) { A[r * 3] = l0 * p0[r]; A[r * 3 + 1] = l1 * p1[r]; A[r * 3 + 2] = l2 * p2[r]; }
+    return l0 != 0. && l1 != 0. && l2 != 0.;
+}
+
+__device__ __forceinline__ bool hg_finite(double v) { return fabs(v) <= DBL_MAX; }
+
+// the four-point model of the header: H (unit norm, gauged at p0), G = adj(H) (gauged at q0); returns its validity
+__device__ __forceinline__ bool hg_four_point(const double2 (&p)[4], const double2 (&q)[4], double (&H)[9], double (&G)[9])
+{
+    double A[9], Bm[9], J[9];
+    const bool okp = hg_basis(p, A), okq = hg_basis(q, Bm);
+    bool ok = okp && okq;
+    hg_adj(A, J);
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) H[r * 3 + c] = (Bm[r * 3] * J[c] + Bm[r * 3 + 1] * J[3 + c]) + Bm[r * 3 + 2] * J[6 + c];
+    double ss = H[0] * H[0];
+#pragma unroll
+    for (int e = 1; e < 9; ++e) ss = ss + H[e] * H[e];
+    const double n = sqrt(ss);
+#pragma unroll
+    for (int e = 0; e < 9; ++e) { H[e] = H[e] / n; ok = ok && hg_finite(H[e]); }
+    if ((H[6] * p[0].x + H[7] * p[0].y) + H[8] < 0.) {
+#pragma unroll
+        for (int e = 0; e < 9; ++e) H[e] = -H[e];
+    }
+    hg_adj(H, G);
+    if ((G[6] * q[0].x + G[7] * q[0].y) + G[8] < 0.) {
+#pragma unroll
+        for (int e = 0; e < 9; ++e) G[e] = -G[e];
+    }
+    return ok;
+}
+
+// T(F, p -> q) of the header
+__device__ __forceinline__ bool hg_transfer(const double (&F)[9], double x, double y, double qx, double qy, double thr2)
+{
+    const double u = (F[0] * x + F[1] * y) + F[2], v = (F[3] * x + F[4] * y) + F[5], w = (F[6] * x + F[7] * y) + F[8];
+    const double dx = u - qx * w, dy = v - qy * w;
+    return w > 0. && (dx * dx + dy * dy) <= thr2 * (w * w);
+}
+
+__device__ __forceinline__ void hg_sample(const unsigned short *__restrict__ sub, int it, const double2 *sp1, const double2 *sp2,
+                                          double2 (&p)[4], double2 (&q)[4])
+{
+    const unsigned short *s5 = sub + (long long)it * 5;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { const int v = s5[k]; p[k] = sp1[v]; q[k] = sp2[v]; }
+}
+
+__device__ __forceinline__ void hg_swap3(double (&a)[3], double (&b)[3])
+{
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { const double t = a[k]; a[k] = b[k]; b[k] = t; }
+}
+
+// R_rot of the header from C = sum b^ a^T; false when an entry is not finite
+__device__ __forceinline__ bool hg_rotation_fit(const double (&C)[9], double (&R)[9])
+{
+    double A[9], V[9];
+#pragma unroll
+    for (int e = 0; e < 9; ++e) A[e] = C[e];
+    jacobi_cols<3, 3>(A, V);                         // A = C V = U S, column by column
+    double u0[3] = {A[0], A[3], A[6]}, u1[3] = {A[1], A[4], A[7]}, u2[3] = {A[2], A[5], A[8]};
+    double v0[3] = {V[0], V[3], V[6]}, v1[3] = {V[1], V[4], V[7]}, v2[3] = {V[2], V[5], V[8]};
+    double s0 = sqrt((u0[0] * u0[0] + u0[1] * u0[1]) + u0[2] * u0[2]);
+    double s1 = sqrt((u1[0] * u1[0] + u1[1] * u1[1]) + u1[2] * u1[2]);
+    double s2 = sqrt((u2[0] * u2[0] + u2[1] * u2[1]) + u2[2] * u2[2]);
+    // descending: compare-and-swap (0, 1), (1, 2), (0, 1)
+    if (s0 < s1) { const double t = s0; s0 = s1; s1 = t; hg_swap3(u0, u1); hg_swap3(v0, v1); }
+    if (s1 < s2) { const double t = s1; s1 = s2; s2 = t; hg_swap3(u1, u2); hg_swap3(v1, v2); }
+    if (s0 < s1) { const double t = s0; s0 = s1; s1 = t; hg_swap3(u0, u1); hg_swap3(v0, v1); }
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { u0[k] = u0[k] / s0; u1[k] = u1[k] / s1; }
+    hg_cross(u0, u1, u2);
+    const double Vt[9] = {v0[0], v0[1], v0[2], v1[0], v1[1], v1[2], v2[0], v2[1], v2[2]};
+    const double d = det3(Vt) < 0. ? -1. : 1.;
+    bool fin = true;
+#pragma unroll
+    for (int r = 0; r < 3; ++r)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            R[r * 3 + c] = (u0[r] * v0[c] + u1[r] * v1[c]) + (d * u2[r]) * v2[c];
+            fin = fin && hg_finite(R[r * 3 + c]);
+        }
+    return fin;
+}
+
+// status (batch form; null in the stage form): a pair whose status is not RPE_PAIR_OK is skipped.  rstate (batch form; null
+// in the stage form): the run's RANSAC state, whose best_count is n_E.
+template <bool CAM>
+__global__ __launch_bounds__(256) void homography_kernel(const double2 *__restrict__ n1, const double2 *__restrict__ n2,
+                                                          const int *__restrict__ m_n, const int *__restrict__ status,
+                                                          const RpeRansacState *__restrict__ rstate,
+                                                          const unsigned short *__restrict__ subsets, const double *__restrict__ K,
+                                                          const RpeCamSrc cam, double threshold_px, int iters, int max_iters,
+                                                          int max_matches, int use_lds, double *__restrict__ Hout,
+                                                          double *__restrict__ Rout, uint8_t *__restrict__ mask,
+                                                          int *__restrict__ counts, int *__restrict__ info)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_hg[];
+    double *s_model = (double *)s_hg;                                                        // [HG_ROUND][18]
+    double2 *s_pts = (double2 *)(s_hg + sizeof(double) * HG_ROUND * HG_MODEL_DOUBLES);       // [2][max_matches] when use_lds
+    __shared__ int s_ok[HG_ROUND], s_best[8], s_cnt[4], s_nvalid;
+    __shared__ double s_red[4 * 9];
+    const int pair = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int M = min(m_n[pair], max_matches);
+    const bool pair_ok = !status || status[pair] == RPE_PAIR_OK;
+    const int nE = rstate ? (pair_ok ? rstate[pair].best_count : 0) : -1;
+    const long long o = (long long)pair * max_matches;
+    int code = (!pair_ok || M < 6) ? RPE_HOMOGRAPHY_SKIPPED : RPE_HOMOGRAPHY_OK;
+    int win_cnt = -1, win_it = -1, nvalid_all = 0;
+    const double2 *sp1 = n1 + o, *sp2 = n2 + o;
+    double thr2 = 0.;
+    if (code == RPE_HOMOGRAPHY_OK) {                         // workgroup-uniform
+        if (use_lds) {
+            double2 *l1 = s_pts, *l2 = s_pts + max_matches;
+            for (int i = tid; i < M; i += 256) { l1[i] = sp1[i]; l2[i] = sp2[i]; }
+            sp1 = l1; sp2 = l2;
+        }
+        if (tid == 0) s_nvalid = 0;
+        const double thr = threshold_px / rpe_pair_focal<CAM>(K, cam, pair);
+        thr2 = thr * thr;
+        const unsigned short *sub = subsets + (long long)M * max_iters * 5;
+        int best_cnt = -1, best_it = -1, nvalid = 0;
+        for (int base = 0; base < iters; base += HG_ROUND) {
+            const int nr = min(HG_ROUND, iters - base);
+            __syncthreads();                                 // the points are staged; the previous round's models have been scored
+            int ok = 0;
+            if (tid < nr) {
+                double2 p[4], q[4];
+                double H[9], G[9];
+                hg_sample(sub, base + tid, sp1, sp2, p, q);
+                ok = hg_four_point(p, q, H, G);
+                double *d = s_model + tid * HG_MODEL_DOUBLES;
+#pragma unroll
+                for (int e = 0; e < 9; ++e) { d[e] = H[e]; d[9 + e] = G[e]; }
+            }
+            s_ok[tid] = ok;
+            nvalid += ok;
+            __syncthreads();
+            for (int j = wv; j < nr; j += 4) {
+                if (!s_ok[j]) continue;                      // wave-uniform
+                double H[9], G[9];
+                const double *d = s_model + j * HG_MODEL_DOUBLES;
+#pragma unroll
+                for (int e = 0; e < 9; ++e) { H[e] = d[e]; G[e] = d[9 + e]; }
+                int cnt = 0;
+                for (int i = lane; i < M; i += 64) {
+                    const double2 a = sp1[i], b = sp2[i];
+                    cnt += (hg_transfer(H, a.x, a.y, b.x, b.y, thr2) && hg_transfer(G, b.x, b.y, a.x, a.y, thr2)) ? 1 : 0;
+                }
+                cnt = wave_sum(cnt);
+                if (cnt > best_cnt) { best_cnt = cnt; best_it = base + j; }
+            }
+        }
+        nvalid = wave_sum(nvalid);
+        if (lane == 0) { s_best[wv * 2] = best_cnt; s_best[wv * 2 + 1] = best_it; atomicAdd(&s_nvalid, nvalid); }
+        __syncthreads();
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const int c = s_best[w * 2], it = s_best[w * 2 + 1];
+            if (it >= 0 && (c > win_cnt || (c == win_cnt && it < win_it))) { win_cnt = c; win_it = it; }
+        }
+        nvalid_all = s_nvalid;
+        if (win_it < 0) code = RPE_HOMOGRAPHY_NONE;
+    }
+    if (code != RPE_HOMOGRAPHY_OK) {
+        for (int i = tid; i < max_matches; i += 256) mask[o + i] = 0;
+        if (tid < 9) { Hout[pair * 9 + tid] = 0.; Rout[pair * 9 + tid] = 0.; }
+        if (tid == 0) {
+            counts[pair * 3] = 0; counts[pair * 3 + 1] = 0; counts[pair * 3 + 2] = nE;
+            info[pair * 4] = code; info[pair * 4 + 1] = 0; info[pair * 4 + 2] = 0; info[pair * 4 + 3] = 0;
+        }
+        return;
+    }
+    // the winner again, on every thread
+    double H[9], G[9];
+    {
+        double2 p[4], q[4];
+        hg_sample(subsets + (long long)M * max_iters * 5, win_it, sp1, sp2, p, q);
+        hg_four_point(p, q, H, G);
+    }
+    double C[9];
+#pragma unroll
+    for (int e = 0; e < 9; ++e) C[e] = 0.;
+    for (int i = tid; i < max_matches; i += 256) {
+        uint8_t v = 0;
+        if (i < M) {
+            const double2 a = sp1[i], b = sp2[i];
+            if (hg_transfer(H, a.x, a.y, b.x, b.y, thr2) && hg_transfer(G, b.x, b.y, a.x, a.y, thr2)) {
+                v = 1;
+                const double na = sqrt((a.x * a.x + a.y * a.y) + 1), nb = sqrt((b.x * b.x + b.y * b.y) + 1);
+                const double ah[3] = {a.x / na, a.y / na, 1 / na}, bh[3] = {b.x / nb, b.y / nb, 1 / nb};
+#pragma unroll
+                for (int r = 0; r < 3; ++r)
+#pragma unroll
+                    for (int c = 0; c < 3; ++c) C[r * 3 + c] += bh[r] * ah[c];
+            }
+        }
+        mask[o + i] = v;
+    }
+    block_sum_f64<9>(C, s_red, tid);
+    double R[9];
+    const bool fin = hg_rotation_fit(C, R);
+    int nrot = 0;
+    if (fin) {                                               // workgroup-uniform: every lane holds the same C
+        const double Rt[9] = {R[0], R[3], R[6], R[1], R[4], R[7], R[2], R[5], R[8]};
+        for (int i = tid; i < M; i += 256) {
+            const double2 a = sp1[i], b = sp2[i];
+            nrot += (hg_transfer(R, a.x, a.y, b.x, b.y, thr2) && hg_transfer(Rt, b.x, b.y, a.x, a.y, thr2)) ? 1 : 0;
+        }
+    }
+    nrot = wave_sum(nrot);
+    if (lane == 0) s_cnt[wv] = nrot;
+    __syncthreads();
+    if (tid == 0) {
+        nrot = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+#pragma unroll
+        for (int e = 0; e < 9; ++e) { Hout[pair * 9 + e] = H[e]; Rout[pair * 9 + e] = fin ? R[e] : 0.; }
+        counts[pair * 3] = win_cnt; counts[pair * 3 + 1] = nrot; counts[pair * 3 + 2] = nE;
+        info[pair * 4] = RPE_HOMOGRAPHY_OK; info[pair * 4 + 1] = win_it; info[pair * 4 + 2] = nvalid_all; info[pair * 4 + 3] = 0;
+    }
+}
+
+// d_n1 / d_n2 (the run's, or rpe_launch_normalise's in the stage form) -> d_hg_*.  from_batch: the run's d_status and
+// d_rstate gate the pairs and supply n_E.  Raises the kernel's dynamic-LDS limit on first use (never inside a graph
+// capture: only rpe_pair_homographies / rpe_find_homography come here).
+int rpe_launch_homography(rpe_handle *h, const RpeRun &r, int iters, double threshold_px, bool from_batch)
+{
+    const int mm = h->cfg.max_matches;
+    const int use_lds = mm <= HG_LDS_MATCHES;
+    const size_t lds = sizeof(double) * HG_ROUND * HG_MODEL_DOUBLES + (use_lds ? sizeof(double2) * 2 * (size_t)mm : 0);
+    if (lds > 65536 && !h->hg_lds_set) {
+        // the limit belongs to the kernel, not to the handle: raise it to the most any handle asks for (the cut)
+        const int lds_max = (int)(sizeof(double) * HG_ROUND * HG_MODEL_DOUBLES + sizeof(double2) * 2 * HG_LDS_MATCHES);
+        if (hipFuncSetAttribute((const void *)homography_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max) != hipSuccess ||
+            hipFuncSetAttribute((const void *)homography_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max) != hipSuccess) return RPE_ERR_HIP;
+        h->hg_lds_set = true;
+    }
+    launch_cam(r, homography_kernel<true>, homography_kernel<false>, dim3(r.pairs), dim3(256), lds, h->stream,
+               (const double2 *)h->d_n1, (const double2 *)h->d_n2, (const int *)h->d_m_n,
+               from_batch ? (const int *)h->d_status : (const int *)nullptr,
+               from_batch ? (const RpeRansacState *)h->d_rstate : (const RpeRansacState *)nullptr,
+               (const unsigned short *)h->d_subsets, (const double *)h->d_K, r.cam, threshold_px, iters, h->cfg.ransac_max_iters,
+               mm, use_lds, h->d_hg_H, h->d_hg_R, h->d_hg_mask, h->d_hg_counts, h->d_hg_info);
+    return RPE_OK;
+}

@@ -1132,6 +1132,58 @@ extern "C" int rpe_match_hamming_guided(rpe_handle *h, const uint8_t *h_desc1, c
     return guided_run(h, rpe_run_batch(h, B), R, t, gate_px, max_distance, qidx, tidx, dist, nullptr, nullptr, n_matches);
 }
 
+// ---------------------------------------------------------------- homography / rotation-only
+// rpe_pair_homographies / rpe_find_homography (NOT in the reference): a homography by RANSAC over the matches of a pair,
+// the rotation fitted to its inliers and the three inlier counts.  Results go to the d_hg_* buffers; nothing of the run
+// is written.
+static int homography_check(rpe_handle *h, const char *who, int iters, double threshold_px)
+{
+    const std::string w(who);
+    if (iters < 1 || iters > h->cfg.ransac_max_iters) { h->err = w + ": iters must be 1 ... ransac_max_iters"; return RPE_ERR_INVALID; }
+    if (!std::isfinite(threshold_px) || !(threshold_px > 0.)) { h->err = w + ": threshold_px must be finite and > 0"; return RPE_ERR_INVALID; }
+    return RPE_OK;
+}
+
+static int homography_alloc(rpe_handle *h)
+{
+    const size_t MB = (size_t)h->cfg.max_batch;
+    DM_ONCE(h, h->d_hg_H, MB * 9); DM_ONCE(h, h->d_hg_R, MB * 9);
+    DM_ONCE(h, h->d_hg_counts, MB * 3); DM_ONCE(h, h->d_hg_info, MB * 4);
+    DM_ONCE(h, h->d_hg_mask, MB * h->cfg.max_matches);
+    return RPE_OK;
+}
+
+static int homography_run(rpe_handle *h, const RpeRun &r, int iters, double threshold_px, bool from_batch, double *H, double *R_rot,
+                          uint8_t *mask, int32_t *counts, int32_t *info)
+{
+    const size_t B = (size_t)r.pairs;
+    int rc = rpe_launch_homography(h, r, iters, threshold_px, from_batch);
+    if (rc != RPE_OK) { h->err = "homography: could not size the kernel's LDS"; return rc; }
+    HIPCHK(h, hipGetLastError());
+    if (H) HIPCHK(h, hipMemcpyAsync(H, h->d_hg_H, sizeof(double) * 9 * B, hipMemcpyDeviceToHost, h->stream));
+    if (R_rot) HIPCHK(h, hipMemcpyAsync(R_rot, h->d_hg_R, sizeof(double) * 9 * B, hipMemcpyDeviceToHost, h->stream));
+    if (mask) HIPCHK(h, hipMemcpyAsync(mask, h->d_hg_mask, B * h->cfg.max_matches, hipMemcpyDeviceToHost, h->stream));
+    if (counts) HIPCHK(h, hipMemcpyAsync(counts, h->d_hg_counts, sizeof(int) * 3 * B, hipMemcpyDeviceToHost, h->stream));
+    if (info) HIPCHK(h, hipMemcpyAsync(info, h->d_hg_info, sizeof(int) * 4 * B, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return RPE_OK;
+}
+
+extern "C" int rpe_pair_homographies(rpe_handle *h, int B, int iters, double threshold_px, double *H, double *R_rot,
+                                     uint8_t *mask, int32_t *counts, int32_t *info)
+{
+    if (!h || B < 1 || B > h->cfg.max_batch) return RPE_ERR_INVALID;
+    int rc = homography_check(h, "rpe_pair_homographies", iters, threshold_px);
+    if (rc) return rc;
+    // d_n1 / d_n2, d_rstate and d_status must still hold the run's (a stage call or a put overwrote them)
+    rc = last_run_check(h, "rpe_pair_homographies", B, "rpe_pair_homographies: the last host batch ran in chunks: per-match results are kept for unchunked and device-resident batches only", true);
+    if (rc) return rc;
+    if (h->last.kind == RpeLastRun::LIST && h->last.tab.size() < (size_t)2 * B) { h->err = "rpe_pair_homographies: the frame store was resized since the pair list"; return RPE_ERR_INVALID; }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if ((rc = homography_alloc(h)) != RPE_OK) return rc;
+    return homography_run(h, last_run_first(h, B), iters, threshold_px, true, H, R_rot, mask, counts, info);
+}
+
 // ---------------------------------------------------------------- frame store
 // rpe_frames_* / rpe_enqueue_pairs (NOT in the reference): extraction separated from pairing.  A put extracts n frames in
 // the workspace slots [0, n) exactly as a stream does and one scatter kernel moves what the matchers and the status test
@@ -1720,6 +1772,22 @@ extern "C" int rpe_find_essential_cameras(rpe_handle *h, const float *h_pts1, co
 {
     if (!h || !h_pts1 || !h_pts2 || !m || !cam1 || !cam2 || B < 1) return RPE_ERR_INVALID;
     return stage_find_essential(h, "rpe_find_essential_cameras", h_pts1, h_pts2, m, B, nullptr, cam1, cam2, E, mask, found, info);
+}
+
+extern "C" int rpe_find_homography(rpe_handle *h, const float *h_pts1, const float *h_pts2, const int32_t *m, int B,
+                                   const double K[9], int iters, double threshold_px, double *H, double *R_rot, uint8_t *mask,
+                                   int32_t *counts, int32_t *info)
+{
+    if (!h || !h_pts1 || !h_pts2 || !m || !K || B < 1) return RPE_ERR_INVALID;
+    if (B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return RPE_ERR_CAPACITY; }
+    int rc = homography_check(h, "rpe_find_homography", iters, threshold_px);
+    if (rc) return rc;
+    for (int i = 0; i < B; ++i) if (m[i] < 0 || m[i] > h->cfg.max_matches) { h->err = "match count exceeds max_matches"; return RPE_ERR_INVALID; }
+    RpeRun run;
+    if ((rc = stage_begin(h, "rpe_find_homography", h_pts1, h_pts2, m, B, K, nullptr, nullptr, run)) != RPE_OK) return rc;
+    if ((rc = homography_alloc(h)) != RPE_OK) return rc;
+    rpe_launch_normalise(h, run);
+    return homography_run(h, run, iters, threshold_px, false, H, R_rot, mask, counts, info);
 }
 
 extern "C" int rpe_recover_pose(rpe_handle *h, const double *h_E, const float *h_pts1, const float *h_pts2, const int32_t *m,

@@ -329,6 +329,12 @@ struct rpe_handle {
     float2 *d_gm_pts1 = nullptr, *d_gm_pts2 = nullptr;
     double *d_gm_R = nullptr, *d_gm_tr = nullptr, *d_gm_thr2 = nullptr;
     double4 *d_gm_rec = nullptr;
+    // rpe_pair_homographies / rpe_find_homography only (created on first use): H, R_rot, {n_H, n_rot, n_E} and info[4] per
+    // pair, the winner's inlier mask [pair][max_matches]
+    double *d_hg_H = nullptr, *d_hg_R = nullptr;
+    int *d_hg_counts = nullptr, *d_hg_info = nullptr;
+    uint8_t *d_hg_mask = nullptr;
+    bool hg_lds_set = false;              // the kernel's dynamic-LDS limit has been raised for this handle's layout
     // results
     double *d_R = nullptr, *d_t = nullptr, *d_E = nullptr;
     int *d_inliers = nullptr, *d_status = nullptr;
@@ -427,6 +433,7 @@ void rpe_launch_structure(rpe_handle *h, const RpeRun &r);
 void rpe_launch_refine(rpe_handle *h, const RpeRun &r, int max_iters, bool from_batch);
 int rpe_launch_scale_links(rpe_handle *h, int L, int min_shared);
 void rpe_launch_normalise(rpe_handle *h, const RpeRun &r);
+int rpe_launch_homography(rpe_handle *h, const RpeRun &r, int iters, double threshold_px, bool from_batch);
 void rpe_launch_undistort(rpe_handle *h, const float2 *d_pts, int n, const rpe_camera *d_cam, double2 *d_out);
 
 // per-stage hipEvents on the handle's stream (rpe_set_profiling / rpe_get_stage_ms)

@@ -106,3 +106,27 @@ def chain_trajectory(R_rel, t_rel, status, ratio, code):
         T_abs[i + 1] = Ri @ T_abs[i] + baseline[i] * ti
     centers = -np.einsum("fji,fj->fi", R_abs, T_abs)
     return R_abs, T_abs, centers, baseline, segment
+
+
+# ---- which model a pair obeys (not in the reference) -------------
+def classify_pair(n_matches, n_E, n_H, n_rot, rotation_ratio=0.7, planar_ratio=0.8):
+    """Names the geometric model a pair obeys from the inlier counts of PoseEstimator.last_homographies /
+    _capi.Engine.pair_homographies: n_E of findEssentialMat, n_H of the homography, n_rot of the rotation fitted to the
+    homography's inliers, out of n_matches matches.
+      "rotation"  n_rot >= rotation_ratio * max(n_H, 1): a rotation alone explains what the homography explains -- no
+                  usable baseline; the five-point (R, t) of such a pair is not to be trusted, R_rot is the rotation
+      "planar"    otherwise, n_H >= planar_ratio * max(n_E, 1): one plane carries the matches
+      "general"   otherwise
+    THE RATIOS ARE CALLER POLICY, not properties of the library: the defaults separate the rendered pairs of
+    DESIGN.md section 8 with a wide margin, and a scene, a matcher or a gate of your own may want others.  n_matches
+    takes no part in the rule; it is an argument so that a caller's policy can use it."""
+    if n_rot >= rotation_ratio * max(n_H, 1):
+        return "rotation"
+    if n_H >= planar_ratio * max(n_E, 1):
+        return "planar"
+    return "general"
+
+
+def pixel_homography(H, K1, K2):
+    """K2 H K1^-1: a homography of normalised coordinates (pair_homographies' H) as one of pixels, image 1 -> image 2"""
+    return np.asarray(K2, np.float64) @ np.asarray(H, np.float64) @ np.linalg.inv(np.asarray(K1, np.float64))

@@ -6,7 +6,8 @@ estimate_with_debug(...) -> dict with the reference's keys (:571-688, dict
 :624-633), same exception types and messages (:96, :129, :508-509, :514-515,
 :529-530).  Added: estimate_batch() for many pairs per call; estimate_with_structure() / last_structure() for the
 per-match inlier masks and triangulated points; `dist_coeffs` / Camera for lens distortion and per-frame cameras
-(the camera path: matched points are undistorted on the GPU before the geometry stages).
+(the camera path: matched points are undistorted on the GPU before the geometry stages); last_homographies() /
+estimate_with_geometry() for the homography, the rotation-only fit and which model a pair obeys.
 
 Scope: the feature -> match -> essential -> pose path on the GPU: ORB or SIFT features, Hamming or L2 matcher
 (every combination cv2 can run: ORB + Hamming, ORB + L2, SIFT + L2; SIFT + Hamming constructs, as in the reference,
@@ -507,6 +508,34 @@ class PoseEstimator:
         return {'R': R[0], 't': t[0], 'R_initial': R0, 't_initial': t0, 'num_guided': n, 'pts1': g['pts1'], 'pts2': g['pts2'],
                 'inliers': int(inl[0]), 'refine_code': int(rinfo[0, 0]), 'refine_iters': int(rinfo[0, 1]),
                 'rms_before': float(rms[0, 0]), 'rms_after': float(rms[0, 1])}
+
+    def last_homographies(self, iters=256, threshold_px=None):
+        """The second geometric model of the pairs of the last estimate / estimate_batch / estimate_sequence /
+        estimate_pairs call (of its last chunk when it ran in several; not in the reference;
+        _capi.Engine.pair_homographies): a homography by RANSAC (`iters` samples, transfer gate threshold_px pixels, None =
+        the RANSAC threshold), the rotation fitted to its inliers, and the inlier counts.  Returns a dict of arrays over
+        the B pairs: 'H' [B, 3, 3] (normalised coordinates; geometry.pixel_homography gives pixels), 'R_rot' [B, 3, 3],
+        'mask' [B, max_matches] bool, 'n_H', 'n_rot', 'n_E' [B], 'n_matches' [B], 'code' [B] (_capi.HOMOGRAPHY_*),
+        'iteration' [B], 'n_valid' [B].  geometry.classify_pair turns the counts into a name."""
+        eng, B = self._last_engine, self._last_pairs
+        H, R, mask, counts, info = eng.pair_homographies(B, iters, threshold_px)
+        return {'H': H, 'R_rot': R, 'mask': mask, 'n_H': counts[:, 0].copy(), 'n_rot': counts[:, 1].copy(),
+                'n_E': counts[:, 2].copy(), 'n_matches': np.asarray(self._last_n_matches, np.int32)[:B].copy(),
+                'code': info[:, 0].copy(), 'iteration': info[:, 1].copy(), 'n_valid': info[:, 2].copy()}
+
+    def estimate_with_geometry(self, img1, img2, iters=256, threshold_px=None, rotation_ratio=0.7, planar_ratio=0.8):
+        """estimate, then last_homographies and geometry.classify_pair (not in the reference).  Returns
+        (R, t, inliers, geom): the five-point pose and its cheirality count exactly as estimate_with_debug reports them,
+        and geom = {'H', 'R_rot', 'n_H', 'n_rot', 'n_E', 'n_matches', 'mask' (n_matches,) bool, 'code', 'kind'}, kind =
+        "rotation" / "planar" / "general" under the two ratios (caller policy: geometry.classify_pair).  A "rotation"
+        pair has no usable baseline: t is noise there and R_rot is the rotation to use.  Raises what estimate raises."""
+        d = self.estimate_with_debug(img1, img2)
+        g = self.last_homographies(iters, threshold_px)
+        n = int(g['n_matches'][0])
+        geom = {'H': g['H'][0], 'R_rot': g['R_rot'][0], 'n_H': int(g['n_H'][0]), 'n_rot': int(g['n_rot'][0]),
+                'n_E': int(g['n_E'][0]), 'n_matches': n, 'mask': g['mask'][0, :n].copy(), 'code': int(g['code'][0])}
+        geom['kind'] = geometry.classify_pair(n, geom['n_E'], geom['n_H'], geom['n_rot'], rotation_ratio, planar_ratio)
+        return d['R'], d['t'], d['inliers'], geom
 
     def close(self):
         for e in self._engines.values():

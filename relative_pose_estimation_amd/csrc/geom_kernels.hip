@@ -20,6 +20,7 @@
 //                    DLT triangulation + cheirality vote, wave-reduced counts
 // All f64 arithmetic uses the oracle's operation order (compiled with -ffp-contract=off).
 #include "rpe_internal.h"
+#include "pose_triangulate.h"
 #include <float.h>
 #include <stdlib.h>
 #include <algorithm>
@@ -919,48 +920,7 @@ void rpe_launch_ransac(rpe_handle *h, const RpeRun &r, bool want_mask)
 }
 
 // ------------------------------------------------------------ recoverPose
-// one-sided Jacobi (Hestenes) on the columns of A (M x N row-major); V accumulates rotations.
-template <int MM, int NN>
-__device__ __forceinline__ void jacobi_cols(double *A, double *V)
-{
-    const double eps = DBL_EPSILON * 10;
-#pragma unroll
-    for (int i = 0; i < NN; ++i)
-#pragma unroll
-        for (int j = 0; j < NN; ++j) V[i * NN + j] = (i == j) ? 1. : 0.;
-    for (int sweep = 0; sweep < 30; ++sweep) {
-        int changed = 0;
-#pragma unroll
-        for (int p = 0; p < NN - 1; ++p)
-#pragma unroll
-            for (int q = p + 1; q < NN; ++q) {
-                double al = 0., be = 0., ga = 0.;
-#pragma unroll
-                for (int k = 0; k < MM; ++k) {
-                    double ap = A[k * NN + p], aq = A[k * NN + q];
-                    al += ap * ap; be += aq * aq; ga += ap * aq;
-                }
-                if (!(fabs(ga) <= eps * sqrt(al * be))) {
-                    changed = 1;
-                    double zeta = (be - al) / (2. * ga);
-                    double t = (zeta >= 0. ? 1. : -1.) / (fabs(zeta) + sqrt(1. + zeta * zeta));
-                    double c = 1. / sqrt(1. + t * t), s = c * t;
-#pragma unroll
-                    for (int k = 0; k < MM; ++k) {
-                        double ap = A[k * NN + p], aq = A[k * NN + q];
-                        A[k * NN + p] = c * ap - s * aq; A[k * NN + q] = s * ap + c * aq;
-                    }
-#pragma unroll
-                    for (int k = 0; k < NN; ++k) {
-                        double vp = V[k * NN + p], vq = V[k * NN + q];
-                        V[k * NN + p] = c * vp - s * vq; V[k * NN + q] = s * vp + c * vq;
-                    }
-                }
-            }
-        if (!changed) break;
-    }
-}
-
+// jacobi_cols, triangulate_one and triangulate_pm: pose_triangulate.h (shared with the host test of the -t mirror)
 __device__ __forceinline__ double det3(const double *m)
 {
     return m[0] * (m[4] * m[8] - m[5] * m[7]) - m[1] * (m[3] * m[8] - m[5] * m[6]) + m[2] * (m[3] * m[7] - m[4] * m[6]);
@@ -999,37 +959,6 @@ __device__ static void decompose_essential(const double *E, double *R1, double *
         R2[r * 3 + c] = (UWt[r * 3] * Vt[c] + UWt[r * 3 + 1] * Vt[3 + c]) + UWt[r * 3 + 2] * Vt[6 + c];
     }
     t[0] = U[2]; t[1] = U[5]; t[2] = U[8];
-}
-
-// triangulate.cpp DLT with P0 = [I|0], P = [R|t]; cheirality test of recoverPose (dist 50).  P receives the point
-// (X/W, Y/W, Z/W) in the camera-1 frame, whatever the test says.  recover_pose_kernel and pose_structure_kernel both call
-// this one helper, so the structure's mask sums to the inlier count exactly.
-__device__ static int triangulate_one(const double *R, const double *t, double x1, double y1, double x2, double y2, double *P)
-{
-    double A[16], V[16];
-    A[0] = -1.; A[1] = 0.;  A[2] = x1; A[3] = 0.;
-    A[4] = 0.;  A[5] = -1.; A[6] = y1; A[7] = 0.;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        A[8 + k]  = x2 * R[6 + k] - R[k];
-        A[12 + k] = y2 * R[6 + k] - R[3 + k];
-    }
-    A[11] = x2 * t[2] - t[0];
-    A[15] = y2 * t[2] - t[1];
-    jacobi_cols<4, 4>(A, V);
-    double X = 0., Y = 0., Z = 0., W = 0., best = 0.;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        double nn = ((A[j] * A[j] + A[4 + j] * A[4 + j]) + A[8 + j] * A[8 + j]) + A[12 + j] * A[12 + j];
-        if (j == 0 || nn < best) { best = nn; X = V[j]; Y = V[4 + j]; Z = V[8 + j]; W = V[12 + j]; }
-    }
-    int good = (Z * W) > 0.;
-    X /= W; Y /= W; Z /= W;
-    P[0] = X; P[1] = Y; P[2] = Z;
-    good = good && (Z < 50.);
-    double z2 = ((R[6] * X + R[7] * Y) + R[8] * Z) + t[2];
-    good = good && (z2 > 0.) && (z2 < 50.);
-    return good;
 }
 
 // The normalised coordinates of match o for recover_pose_kernel and pose_structure_kernel.  CAM = true: read from
@@ -1079,14 +1008,16 @@ __global__ __launch_bounds__(256) void recover_pose_kernel(const double *__restr
     tn[0] = -tt[0]; tn[1] = -tt[1]; tn[2] = -tt[2];
     const RpePairNormalise<false> with_K(K, RpeCamSrc{}, pair);
     int g1 = 0, g2 = 0, g3 = 0, g4 = 0;
+    // one SVD per rotation: the verdict of (R, -t) is the mirror of (R, t)'s (pose_triangulate.h)
     for (int i = tid; i < M; i += 256) {
         double2 a, b;
         pose_match<CAM>(with_K, pts1, pts2, n1, n2, (long long)pair * max_matches + i, a, b);
         double P[3];
-        g1 += triangulate_one(R1, tt, a.x, a.y, b.x, b.y, P);
-        g2 += triangulate_one(R2, tt, a.x, a.y, b.x, b.y, P);
-        g3 += triangulate_one(R1, tn, a.x, a.y, b.x, b.y, P);
-        g4 += triangulate_one(R2, tn, a.x, a.y, b.x, b.y, P);
+        int gp, gm;
+        triangulate_pm(R1, tt, a.x, a.y, b.x, b.y, gp, gm, P);
+        g1 += gp; g3 += gm;
+        triangulate_pm(R2, tt, a.x, a.y, b.x, b.y, gp, gm, P);
+        g2 += gp; g4 += gm;
     }
     g1 = wave_sum(g1); g2 = wave_sum(g2); g3 = wave_sum(g3); g4 = wave_sum(g4);
     if ((tid & 63) == 0) { atomicAdd(&s_g[0], g1); atomicAdd(&s_g[1], g2); atomicAdd(&s_g[2], g3); atomicAdd(&s_g[3], g4); }

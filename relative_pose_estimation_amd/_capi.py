@@ -31,28 +31,44 @@ LINK_OK, LINK_PAIR_FAILED, LINK_TOO_FEW = 0, 1, 2      # code[] of scale_links (
 HOMOGRAPHY_OK, HOMOGRAPHY_SKIPPED, HOMOGRAPHY_NONE = 0, 1, 2   # info[:, 0] of pair_homographies (include/rpe_amd.h RPE_HOMOGRAPHY_*)
 UNDISTORT_ITERS = 5               # RPE_UNDISTORT_ITERS: fixed-point rounds of the camera path's undistortion
 
-EXPORTS = [
-    "rpe_default_config", "rpe_create", "rpe_destroy", "rpe_last_error", "rpe_device_count",
-    "rpe_keypoint_capacity", "rpe_device_malloc", "rpe_device_free", "rpe_memcpy_h2d", "rpe_memcpy_d2h",
-    "rpe_synchronize", "rpe_host_alloc", "rpe_host_free", "rpe_host_register", "rpe_host_unregister", "rpe_estimate_batch", "rpe_estimate_batch_device", "rpe_enqueue_batch_device",
-    "rpe_fetch_results", "rpe_fetch_matched_points", "rpe_fetch_structure", "rpe_refine_poses", "rpe_refine_pose_points", "rpe_orb_detect_and_compute", "rpe_orb_debug_fetch",
-    "rpe_orb_pyramid_pixels", "rpe_match_hamming", "rpe_find_essential", "rpe_recover_pose",
-    "rpe_set_profiling", "rpe_get_stage_ms", "rpe_stage_name",
-    "rpe_sift_detect_and_compute", "rpe_sift_debug_gauss", "rpe_match_l2",
-    "rpe_estimate_stream", "rpe_enqueue_stream_device",
-    "rpe_bgr_to_gray_device", "rpe_bgr_to_gray", "rpe_lsd_detect",
-    "rpe_fetch_overflow", "rpe_calibrate_valu", "rpe_calibrate_valu_name", "rpe_calibrate_hbm",
-    "rpe_comm_unique_id", "rpe_comm_create", "rpe_comm_prepare", "rpe_comm_connect", "rpe_comm_destroy", "rpe_comm_last_error", "rpe_gather_poses",
-    "rpe_comm_allreduce_max", "rpe_comm_barrier",
-    "rpe_frames_reserve", "rpe_frames_capacity", "rpe_frames_put_device", "rpe_frames_put", "rpe_frames_info",
-    "rpe_enqueue_pairs", "rpe_estimate_pairs",
-    "rpe_frames_set_cameras", "rpe_enqueue_pairs_cameras", "rpe_estimate_pairs_cameras",
-    "rpe_enqueue_batch_cameras_device", "rpe_estimate_batch_cameras_device", "rpe_estimate_batch_cameras",
-    "rpe_undistort_points", "rpe_find_essential_cameras", "rpe_recover_pose_cameras", "rpe_refine_pose_points_cameras",
-    "rpe_fetch_match_indices", "rpe_scale_links",
-    "rpe_guided_matches", "rpe_match_hamming_guided",
-    "rpe_pair_homographies", "rpe_find_homography",
-]
+# The binding, one entry per function of include/rpe_amd.h: "<return>:<one letter per parameter>".  Parameters: p pointer or
+# array, i int / int32_t, d double, z size_t.  Returns: i int, l int64_t, s const char *, v void.  ctypes checks nothing
+# against the header (a wrong arity or an int where the header has a double goes through silently), so
+# tests/test_capi_cpu.py compares this table with the header's declarations.
+_SIGNATURES = {
+    "rpe_default_config": "v:p", "rpe_create": "i:pp", "rpe_destroy": "v:p", "rpe_last_error": "s:p", "rpe_device_count": "i:",
+    "rpe_keypoint_capacity": "i:p", "rpe_device_malloc": "i:pzp", "rpe_device_free": "i:pp", "rpe_memcpy_h2d": "i:pppz",
+    "rpe_memcpy_d2h": "i:pppz", "rpe_synchronize": "i:p", "rpe_host_alloc": "i:pzp", "rpe_host_free": "i:pp",
+    "rpe_host_register": "i:ppz", "rpe_host_unregister": "i:pp",
+    "rpe_estimate_batch": "i:pppipppppp", "rpe_estimate_batch_device": "i:pppipppppp", "rpe_enqueue_batch_device": "i:pppip",
+    "rpe_fetch_results": "i:pippppp", "rpe_fetch_overflow": "i:pip", "rpe_estimate_stream": "i:ppipppppp",
+    "rpe_enqueue_stream_device": "i:ppip",
+    "rpe_frames_reserve": "i:pi", "rpe_frames_capacity": "i:p", "rpe_frames_put_device": "i:ppip", "rpe_frames_put": "i:ppip",
+    "rpe_frames_info": "i:pippp", "rpe_enqueue_pairs": "i:pppip", "rpe_estimate_pairs": "i:pppipppppp",
+    "rpe_frames_set_cameras": "i:pipp", "rpe_enqueue_pairs_cameras": "i:pppi", "rpe_estimate_pairs_cameras": "i:pppippppp",
+    "rpe_enqueue_batch_cameras_device": "i:pppipp", "rpe_estimate_batch_cameras_device": "i:pppippppppp",
+    "rpe_estimate_batch_cameras": "i:pppippppppp", "rpe_undistort_points": "i:ppipp",
+    "rpe_find_essential_cameras": "i:ppppipppppp", "rpe_recover_pose_cameras": "i:pppppippppp",
+    "rpe_refine_pose_points_cameras": "i:pppppppippippppp",
+    "rpe_bgr_to_gray_device": "i:ppzip", "rpe_bgr_to_gray": "i:ppzip", "rpe_lsd_detect": "i:piipip",
+    "rpe_fetch_matched_points": "i:pipp", "rpe_fetch_structure": "i:pippp", "rpe_refine_poses": "i:piippppp",
+    "rpe_fetch_match_indices": "i:pipp", "rpe_scale_links": "i:pipppippp", "rpe_guided_matches": "i:pippdipppppp",
+    "rpe_pair_homographies": "i:piidppppp", "rpe_find_homography": "i:ppppipidppppp",
+    "rpe_orb_detect_and_compute": "i:ppippp", "rpe_orb_debug_fetch": "i:piip", "rpe_orb_pyramid_pixels": "l:p",
+    "rpe_match_hamming": "i:pppppipppp", "rpe_match_hamming_guided": "i:pppppppipppdipppp",
+    "rpe_sift_detect_and_compute": "i:ppippp", "rpe_sift_debug_gauss": "l:pip", "rpe_match_l2": "i:pppppipppp",
+    "rpe_find_essential": "i:ppppippppp", "rpe_recover_pose": "i:pppppipppp", "rpe_refine_pose_points": "i:pppppppipippppp",
+    "rpe_set_profiling": "i:pi", "rpe_get_stage_ms": "i:pp", "rpe_stage_name": "s:i",
+    "rpe_comm_unique_id": "i:p", "rpe_comm_create": "i:piipp", "rpe_comm_prepare": "i:piip", "rpe_comm_connect": "i:pp",
+    "rpe_comm_destroy": "i:p", "rpe_comm_last_error": "s:", "rpe_gather_poses": "i:ppiiip", "rpe_comm_allreduce_max": "i:pp",
+    "rpe_comm_barrier": "i:p",
+    "rpe_calibrate_valu": "i:piip", "rpe_calibrate_valu_name": "s:i", "rpe_calibrate_hbm": "i:pp",
+}
+_ARG = {"p": C.c_void_p, "i": C.c_int, "d": C.c_double, "z": C.c_size_t}
+_RET = {"i": C.c_int, "l": C.c_int64, "s": C.c_char_p, "v": None}
+# name -> (restype, argtypes): what load() sets on the library, readable without it
+SIGNATURES = {name: (_RET[sig[0]], [_ARG[c] for c in sig[2:]]) for name, sig in _SIGNATURES.items()}
+EXPORTS = list(SIGNATURES)
 
 
 class Config(C.Structure):
@@ -136,107 +152,35 @@ def load():
         raise RpeError(f"{LIB_PATH} not found: build it with __graft_entry__.build() "
                        "(make -C relative_pose_estimation_amd/csrc); there is no CPU fallback")
     lib = C.CDLL(LIB_PATH)
-    vp, i32p = C.c_void_p, C.c_void_p
-    lib.rpe_default_config.argtypes = [C.POINTER(Config)]; lib.rpe_default_config.restype = None
-    lib.rpe_create.argtypes = [C.POINTER(Config), C.POINTER(vp)]; lib.rpe_create.restype = C.c_int
-    lib.rpe_destroy.argtypes = [vp]; lib.rpe_destroy.restype = None
-    lib.rpe_last_error.argtypes = [vp]; lib.rpe_last_error.restype = C.c_char_p
-    lib.rpe_device_count.argtypes = []; lib.rpe_device_count.restype = C.c_int
-    lib.rpe_keypoint_capacity.argtypes = [vp]; lib.rpe_keypoint_capacity.restype = C.c_int
-    lib.rpe_device_malloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]; lib.rpe_device_malloc.restype = C.c_int
-    lib.rpe_host_alloc.argtypes = [vp, C.c_size_t, C.POINTER(vp)]; lib.rpe_host_alloc.restype = C.c_int
-    lib.rpe_host_free.argtypes = [vp, vp]; lib.rpe_host_free.restype = C.c_int
-    lib.rpe_host_register.argtypes = [vp, vp, C.c_size_t]; lib.rpe_host_register.restype = C.c_int
-    lib.rpe_host_unregister.argtypes = [vp, vp]; lib.rpe_host_unregister.restype = C.c_int
-    lib.rpe_device_free.argtypes = [vp, vp]; lib.rpe_device_free.restype = C.c_int
-    lib.rpe_memcpy_h2d.argtypes = [vp, vp, vp, C.c_size_t]; lib.rpe_memcpy_h2d.restype = C.c_int
-    lib.rpe_memcpy_d2h.argtypes = [vp, vp, vp, C.c_size_t]; lib.rpe_memcpy_d2h.restype = C.c_int
-    lib.rpe_synchronize.argtypes = [vp]; lib.rpe_synchronize.restype = C.c_int
-    lib.rpe_estimate_batch.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp, i32p, i32p, i32p]
-    lib.rpe_estimate_batch.restype = C.c_int
-    lib.rpe_estimate_batch_device.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp, i32p, i32p, i32p]
-    lib.rpe_estimate_batch_device.restype = C.c_int
-    lib.rpe_enqueue_batch_device.argtypes = [vp, vp, vp, C.c_int, vp]; lib.rpe_enqueue_batch_device.restype = C.c_int
-    lib.rpe_fetch_results.argtypes = [vp, C.c_int, vp, vp, i32p, i32p, i32p]; lib.rpe_fetch_results.restype = C.c_int
-    lib.rpe_fetch_matched_points.argtypes = [vp, C.c_int, vp, vp]; lib.rpe_fetch_matched_points.restype = C.c_int
-    lib.rpe_fetch_structure.argtypes = [vp, C.c_int, vp, vp, vp]; lib.rpe_fetch_structure.restype = C.c_int
-    lib.rpe_refine_poses.argtypes = [vp, C.c_int, C.c_int, vp, vp, i32p, i32p, vp]; lib.rpe_refine_poses.restype = C.c_int
-    lib.rpe_refine_pose_points.argtypes = [vp, vp, vp, vp, vp, vp, i32p, C.c_int, vp, C.c_int, vp, vp, i32p, i32p, vp]
-    lib.rpe_refine_pose_points.restype = C.c_int
-    lib.rpe_orb_detect_and_compute.argtypes = [vp, vp, C.c_int, vp, vp, i32p]
-    lib.rpe_orb_detect_and_compute.restype = C.c_int
-    lib.rpe_orb_debug_fetch.argtypes = [vp, C.c_int, C.c_int, vp]; lib.rpe_orb_debug_fetch.restype = C.c_int
-    lib.rpe_orb_pyramid_pixels.argtypes = [vp]; lib.rpe_orb_pyramid_pixels.restype = C.c_int64
-    lib.rpe_match_hamming.argtypes = [vp, vp, i32p, vp, i32p, C.c_int, i32p, i32p, i32p, i32p]
-    lib.rpe_match_hamming.restype = C.c_int
-    lib.rpe_find_essential.argtypes = [vp, vp, vp, i32p, C.c_int, vp, vp, vp, i32p, i32p]
-    lib.rpe_find_essential.restype = C.c_int
-    lib.rpe_recover_pose.argtypes = [vp, vp, vp, vp, i32p, C.c_int, vp, vp, vp, i32p]
-    lib.rpe_recover_pose.restype = C.c_int
-    lib.rpe_set_profiling.argtypes = [vp, C.c_int]; lib.rpe_set_profiling.restype = C.c_int
-    lib.rpe_get_stage_ms.argtypes = [vp, vp]; lib.rpe_get_stage_ms.restype = C.c_int
-    lib.rpe_stage_name.argtypes = [C.c_int]; lib.rpe_stage_name.restype = C.c_char_p
-    lib.rpe_sift_detect_and_compute.argtypes = [vp, vp, C.c_int, vp, vp, i32p]
-    lib.rpe_sift_detect_and_compute.restype = C.c_int
-    lib.rpe_sift_debug_gauss.argtypes = [vp, C.c_int, vp]; lib.rpe_sift_debug_gauss.restype = C.c_int64
-    lib.rpe_match_l2.argtypes = [vp, vp, i32p, vp, i32p, C.c_int, i32p, i32p, vp, i32p]
-    lib.rpe_match_l2.restype = C.c_int
-    lib.rpe_estimate_stream.argtypes = [vp, vp, C.c_int, vp, vp, vp, i32p, i32p, i32p]; lib.rpe_estimate_stream.restype = C.c_int
-    lib.rpe_enqueue_stream_device.argtypes = [vp, vp, C.c_int, vp]; lib.rpe_enqueue_stream_device.restype = C.c_int
-    lib.rpe_bgr_to_gray_device.argtypes = [vp, vp, C.c_size_t, C.c_int, vp]; lib.rpe_bgr_to_gray_device.restype = C.c_int
-    lib.rpe_bgr_to_gray.argtypes = [vp, vp, C.c_size_t, C.c_int, vp]; lib.rpe_bgr_to_gray.restype = C.c_int
-    lib.rpe_lsd_detect.argtypes = [vp, C.c_int, C.c_int, vp, C.c_int, i32p]; lib.rpe_lsd_detect.restype = C.c_int
-    lib.rpe_fetch_overflow.argtypes = [vp, C.c_int, vp]; lib.rpe_fetch_overflow.restype = C.c_int
-    lib.rpe_calibrate_valu.argtypes = [vp, C.c_int, C.c_int, C.POINTER(C.c_double)]; lib.rpe_calibrate_valu.restype = C.c_int
-    lib.rpe_calibrate_valu_name.argtypes = [C.c_int]; lib.rpe_calibrate_valu_name.restype = C.c_char_p
-    lib.rpe_calibrate_hbm.argtypes = [vp, C.POINTER(C.c_double)]; lib.rpe_calibrate_hbm.restype = C.c_int
-    lib.rpe_comm_unique_id.argtypes = [vp]; lib.rpe_comm_unique_id.restype = C.c_int
-    lib.rpe_comm_create.argtypes = [vp, C.c_int, C.c_int, vp, C.POINTER(vp)]; lib.rpe_comm_create.restype = C.c_int
-    lib.rpe_comm_prepare.argtypes = [vp, C.c_int, C.c_int, C.POINTER(vp)]; lib.rpe_comm_prepare.restype = C.c_int
-    lib.rpe_comm_connect.argtypes = [vp, vp]; lib.rpe_comm_connect.restype = C.c_int
-    lib.rpe_comm_destroy.argtypes = [vp]; lib.rpe_comm_destroy.restype = C.c_int
-    lib.rpe_comm_last_error.argtypes = []; lib.rpe_comm_last_error.restype = C.c_char_p
-    lib.rpe_gather_poses.argtypes = [vp, vp, C.c_int, C.c_int, C.c_int, vp]; lib.rpe_gather_poses.restype = C.c_int
-    lib.rpe_comm_allreduce_max.argtypes = [vp, C.POINTER(C.c_double)]; lib.rpe_comm_allreduce_max.restype = C.c_int
-    lib.rpe_comm_barrier.argtypes = [vp]; lib.rpe_comm_barrier.restype = C.c_int
-    lib.rpe_frames_reserve.argtypes = [vp, C.c_int]; lib.rpe_frames_reserve.restype = C.c_int
-    lib.rpe_frames_capacity.argtypes = [vp]; lib.rpe_frames_capacity.restype = C.c_int
-    lib.rpe_frames_put_device.argtypes = [vp, vp, C.c_int, i32p]; lib.rpe_frames_put_device.restype = C.c_int
-    lib.rpe_frames_put.argtypes = [vp, vp, C.c_int, i32p]; lib.rpe_frames_put.restype = C.c_int
-    lib.rpe_frames_info.argtypes = [vp, C.c_int, i32p, i32p, vp]; lib.rpe_frames_info.restype = C.c_int
-    lib.rpe_enqueue_pairs.argtypes = [vp, i32p, i32p, C.c_int, vp]; lib.rpe_enqueue_pairs.restype = C.c_int
-    lib.rpe_estimate_pairs.argtypes = [vp, i32p, i32p, C.c_int, vp, vp, vp, i32p, i32p, i32p]; lib.rpe_estimate_pairs.restype = C.c_int
-    lib.rpe_frames_set_cameras.argtypes = [vp, C.c_int, i32p, vp]; lib.rpe_frames_set_cameras.restype = C.c_int
-    lib.rpe_enqueue_pairs_cameras.argtypes = [vp, i32p, i32p, C.c_int]; lib.rpe_enqueue_pairs_cameras.restype = C.c_int
-    lib.rpe_estimate_pairs_cameras.argtypes = [vp, i32p, i32p, C.c_int, vp, vp, i32p, i32p, i32p]; lib.rpe_estimate_pairs_cameras.restype = C.c_int
-    lib.rpe_enqueue_batch_cameras_device.argtypes = [vp, vp, vp, C.c_int, vp, vp]; lib.rpe_enqueue_batch_cameras_device.restype = C.c_int
-    lib.rpe_estimate_batch_cameras_device.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp, vp, i32p, i32p, i32p]
-    lib.rpe_estimate_batch_cameras_device.restype = C.c_int
-    lib.rpe_estimate_batch_cameras.argtypes = [vp, vp, vp, C.c_int, vp, vp, vp, vp, i32p, i32p, i32p]
-    lib.rpe_estimate_batch_cameras.restype = C.c_int
-    lib.rpe_undistort_points.argtypes = [vp, vp, C.c_int, vp, vp]; lib.rpe_undistort_points.restype = C.c_int
-    lib.rpe_find_essential_cameras.argtypes = [vp, vp, vp, i32p, C.c_int, vp, vp, vp, vp, i32p, i32p]
-    lib.rpe_find_essential_cameras.restype = C.c_int
-    lib.rpe_recover_pose_cameras.argtypes = [vp, vp, vp, vp, i32p, C.c_int, vp, vp, vp, vp, i32p]
-    lib.rpe_recover_pose_cameras.restype = C.c_int
-    lib.rpe_refine_pose_points_cameras.argtypes = [vp, vp, vp, vp, vp, vp, i32p, C.c_int, vp, vp, C.c_int, vp, vp, i32p, i32p, vp]
-    lib.rpe_refine_pose_points_cameras.restype = C.c_int
-    lib.rpe_fetch_match_indices.argtypes = [vp, C.c_int, i32p, i32p]; lib.rpe_fetch_match_indices.restype = C.c_int
-    lib.rpe_scale_links.argtypes = [vp, C.c_int, i32p, i32p, i32p, C.c_int, vp, i32p, i32p]; lib.rpe_scale_links.restype = C.c_int
-    lib.rpe_guided_matches.argtypes = [vp, C.c_int, vp, vp, C.c_double, C.c_int, i32p, i32p, i32p, vp, vp, i32p]
-    lib.rpe_guided_matches.restype = C.c_int
-    lib.rpe_match_hamming_guided.argtypes = [vp, vp, vp, i32p, vp, vp, i32p, C.c_int, vp, vp, vp, C.c_double, C.c_int, i32p, i32p, i32p, i32p]
-    lib.rpe_match_hamming_guided.restype = C.c_int
-    lib.rpe_pair_homographies.argtypes = [vp, C.c_int, C.c_int, C.c_double, vp, vp, vp, i32p, i32p]
-    lib.rpe_pair_homographies.restype = C.c_int
-    lib.rpe_find_homography.argtypes = [vp, vp, vp, i32p, C.c_int, vp, C.c_int, C.c_double, vp, vp, vp, i32p, i32p]
-    lib.rpe_find_homography.restype = C.c_int
+    for name, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = lib
     return lib
 
 
 def _p(a):
     return a.ctypes.data_as(C.c_void_p)
+
+
+def _opt(a):
+    return None if a is None else _p(a)
+
+
+def _f64(a):
+    """a camera matrix (or any f64 array) as the library reads it"""
+    return np.ascontiguousarray(a, np.float64)
+
+
+def _i32(a):
+    """slot numbers, counts, pair indices: a flat int32 array"""
+    return np.ascontiguousarray(a, np.int32).reshape(-1)
+
+
+def _slot_pairs(slot1, slot2):
+    s1, s2 = _i32(slot1), _i32(slot2)
+    assert s1.size == s2.size
+    return s1, s2
 
 
 def lsd_detect(gray, capacity=8192):
@@ -358,42 +302,44 @@ class Engine:
         return (np.zeros((B, 3, 3)), np.zeros((B, 3, 1)), np.zeros(B, np.int32), np.zeros(B, np.int32),
                 np.zeros(B, np.int32))
 
-    def estimate_batch(self, imgs1, imgs2, K):
+    def _image_pair(self, imgs1, imgs2):
         imgs1 = np.ascontiguousarray(imgs1, np.uint8); imgs2 = np.ascontiguousarray(imgs2, np.uint8)
         B = imgs1.shape[0]
         assert imgs1.shape == imgs2.shape == (B, self.height, self.width), (imgs1.shape, imgs2.shape)
-        K = np.ascontiguousarray(K, np.float64)
-        R, t, inl, nm, st = self._outs(B)
-        self._chk(self.lib.rpe_estimate_batch(self.h, _p(imgs1), _p(imgs2), B, _p(K), _p(R), _p(t), _p(inl), _p(nm), _p(st)))
-        return R, t, inl, nm, st
+        return imgs1, imgs2, B
+
+    def _estimate(self, fn, n, *args):
+        """fn(handle, *args, R, t, inliers, n_matches, status) over n pairs: the five results"""
+        outs = self._outs(n)
+        self._chk(fn(self.h, *args, *map(_p, outs)))
+        return outs
+
+    def estimate_batch(self, imgs1, imgs2, K):
+        imgs1, imgs2, B = self._image_pair(imgs1, imgs2)
+        K = _f64(K)
+        return self._estimate(self.lib.rpe_estimate_batch, B, _p(imgs1), _p(imgs2), B, _p(K))
 
     def estimate_stream(self, frames, K):
         frames = np.ascontiguousarray(frames, np.uint8)
         F = frames.shape[0]
         assert frames.shape == (F, self.height, self.width)
-        K = np.ascontiguousarray(K, np.float64)
-        R, t, inl, nm, st = self._outs(F - 1)
-        self._chk(self.lib.rpe_estimate_stream(self.h, _p(frames), F, _p(K), _p(R), _p(t), _p(inl), _p(nm), _p(st)))
-        return R, t, inl, nm, st
+        K = _f64(K)
+        return self._estimate(self.lib.rpe_estimate_stream, F - 1, _p(frames), F, _p(K))
 
     def enqueue_stream_device(self, d_frames, F, K):
-        K = np.ascontiguousarray(K, np.float64)
+        K = _f64(K)
         self._chk(self.lib.rpe_enqueue_stream_device(self.h, d_frames, F, _p(K)))
 
     def estimate_batch_device(self, d_imgs1, d_imgs2, B, K):
-        K = np.ascontiguousarray(K, np.float64)
-        R, t, inl, nm, st = self._outs(B)
-        self._chk(self.lib.rpe_estimate_batch_device(self.h, d_imgs1, d_imgs2, B, _p(K), _p(R), _p(t), _p(inl), _p(nm), _p(st)))
-        return R, t, inl, nm, st
+        K = _f64(K)
+        return self._estimate(self.lib.rpe_estimate_batch_device, B, d_imgs1, d_imgs2, B, _p(K))
 
     def enqueue_batch_device(self, d_imgs1, d_imgs2, B, K):
-        K = np.ascontiguousarray(K, np.float64)
+        K = _f64(K)
         self._chk(self.lib.rpe_enqueue_batch_device(self.h, d_imgs1, d_imgs2, B, _p(K)))
 
     def fetch_results(self, B):
-        R, t, inl, nm, st = self._outs(B)
-        self._chk(self.lib.rpe_fetch_results(self.h, B, _p(R), _p(t), _p(inl), _p(nm), _p(st)))
-        return R, t, inl, nm, st
+        return self._estimate(self.lib.rpe_fetch_results, B, B)
 
     def fetch_overflow(self, n_pairs):
         """OVF_* capacity flags of the last batch / stream, one word per pair."""
@@ -417,15 +363,17 @@ class Engine:
         self._chk(self.lib.rpe_fetch_structure(self.h, B, _p(rm), _p(pm), _p(pts)))
         return rm.astype(bool), pm.astype(bool), pts
 
+    def _refine_outs(self, B):
+        return np.zeros((B, 3, 3)), np.zeros((B, 3, 1)), np.zeros(B, np.int32), np.zeros((B, 4), np.int32), np.zeros((B, 2))
+
     def refine_poses(self, B, max_iters=10):
         """Non-linear refinement of the poses of the last batch / stream (rpe_refine_poses; not in the reference):
         Levenberg-Marquardt on the Sampson error over findEssentialMat's inliers, started from the batch's (R, t).
         Returns (R[B,3,3], t[B,3,1], inliers[B], info[B,4], rms[B,2]): info = (REFINE_* code, iterations run, residuals
         used, accepted steps), rms = (before, after) in pixels.  The batch's own results are not modified."""
-        R = np.zeros((B, 3, 3)); t = np.zeros((B, 3, 1)); inl = np.zeros(B, np.int32)
-        info = np.zeros((B, 4), np.int32); rms = np.zeros((B, 2))
-        self._chk(self.lib.rpe_refine_poses(self.h, B, max_iters, _p(R), _p(t), _p(inl), _p(info), _p(rms)))
-        return R, t, inl, info, rms
+        outs = self._refine_outs(B)
+        self._chk(self.lib.rpe_refine_poses(self.h, B, max_iters, *map(_p, outs)))
+        return outs
 
     # ---- scale links (rpe_fetch_match_indices / rpe_scale_links; not in the reference)
     def fetch_match_indices(self, B):
@@ -441,8 +389,7 @@ class Engine:
         pair_b.  Returns (stats f64[L, 3], n_shared i32[L], code i32[L]): stats = lower quartile, median, upper quartile
         of d_a / d_b over the shared keypoints = baseline of pair_b in units of the baseline of pair_a; code = LINK_*
         (stats are zero unless LINK_OK).  The run's own results are not modified."""
-        a = np.ascontiguousarray(pair_a, np.int32).reshape(-1); b = np.ascontiguousarray(pair_b, np.int32).reshape(-1)
-        s = np.ascontiguousarray(side, np.int32).reshape(-1)
+        a, b, s = _i32(pair_a), _i32(pair_b), _i32(side)
         if not (a.size == b.size == s.size):
             raise ValueError(f"scale_links: pair_a, pair_b and side must have one length, got {(a.size, b.size, s.size)}")
         L = a.size
@@ -459,6 +406,18 @@ class Engine:
         return (np.ascontiguousarray(np.asarray(R, np.float64).reshape(B, 9)),
                 np.ascontiguousarray(np.asarray(t, np.float64).reshape(B, 3)))
 
+    def _match_outs(self, B, dist_dtype=np.int32):
+        """qidx, tidx, dist [B, mm] and n_matches [B]"""
+        mm = self.max_matches
+        return np.zeros((B, mm), np.int32), np.zeros((B, mm), np.int32), np.zeros((B, mm), dist_dtype), np.zeros(B, np.int32)
+
+    def _pack_features(self, rows, n, tail, dtype):
+        """per pair the first n[i] rows of rows[i], packed to [B, kcap, *tail]"""
+        out = np.zeros((len(n), self.kcap) + tail, dtype)
+        for i in range(len(n)):
+            out[i, :n[i]] = rows[i][:n[i]]
+        return out
+
     def guided_matches(self, B, R=None, t=None, gate_px=None, max_distance=256):
         """Matches of the last batch / stream / pair list again under the epipolar gate of a pose (rpe_guided_matches):
         the mutual nearest neighbour among the keypoint pairs within gate_px (Sampson, pixels; None = the handle's
@@ -467,12 +426,11 @@ class Engine:
         (qidx, tidx, dist i32[B, mm], pts1, pts2 f32[B, mm, 2], n_matches i32[B]); -1 / zero past each pair's count.  The
         run's own results are not modified."""
         Rc, tc = self._poses(B, R, t)
-        mm = self.max_matches
-        q = np.zeros((B, mm), np.int32); ti = np.zeros_like(q); d = np.zeros_like(q); nm = np.zeros(B, np.int32)
-        p1 = np.zeros((B, mm, 2), np.float32); p2 = np.zeros_like(p1)
+        q, ti, d, nm = self._match_outs(B)
+        p1 = np.zeros((B, self.max_matches, 2), np.float32); p2 = np.zeros_like(p1)
         gate = float(self.cfg.ransac_threshold if gate_px is None else gate_px)
-        self._chk(self.lib.rpe_guided_matches(self.h, B, None if Rc is None else _p(Rc), None if tc is None else _p(tc), gate,
-                                              int(max_distance), _p(q), _p(ti), _p(d), _p(p1), _p(p2), _p(nm)))
+        self._chk(self.lib.rpe_guided_matches(self.h, B, _opt(Rc), _opt(tc), gate, int(max_distance),
+                                              _p(q), _p(ti), _p(d), _p(p1), _p(p2), _p(nm)))
         return q, ti, d, p1, p2, nm
 
     def match_hamming_guided(self, desc1, pts1, n1, desc2, pts2, n2, K, R, t, gate_px=None, max_distance=256):
@@ -480,20 +438,14 @@ class Engine:
         keypoint pixels (n, 2) f32 of both images, one K, the poses R[B,3,3], t[B,3].  Returns (qidx, tidx, dist,
         n_matches)."""
         B = len(n1)
-        d1 = np.zeros((B, self.kcap, 32), np.uint8); d2 = np.zeros_like(d1)
-        p1 = np.zeros((B, self.kcap, 2), np.float32); p2 = np.zeros_like(p1)
-        for i in range(B):
-            d1[i, :n1[i]] = desc1[i][:n1[i]]; d2[i, :n2[i]] = desc2[i][:n2[i]]
-            p1[i, :n1[i]] = pts1[i][:n1[i]]; p2[i, :n2[i]] = pts2[i][:n2[i]]
-        n1 = np.ascontiguousarray(n1, np.int32); n2 = np.ascontiguousarray(n2, np.int32)
-        K = np.ascontiguousarray(K, np.float64)
+        d1 = self._pack_features(desc1, n1, (32,), np.uint8); d2 = self._pack_features(desc2, n2, (32,), np.uint8)
+        p1 = self._pack_features(pts1, n1, (2,), np.float32); p2 = self._pack_features(pts2, n2, (2,), np.float32)
+        n1, n2, K = _i32(n1), _i32(n2), _f64(K)
         Rc, tc = self._poses(B, R, t)
-        mm = self.max_matches
-        q = np.zeros((B, mm), np.int32); ti = np.zeros_like(q); d = np.zeros_like(q); nm = np.zeros(B, np.int32)
+        q, ti, d, nm = self._match_outs(B)
         gate = float(self.cfg.ransac_threshold if gate_px is None else gate_px)
         self._chk(self.lib.rpe_match_hamming_guided(self.h, _p(d1), _p(p1), _p(n1), _p(d2), _p(p2), _p(n2), B, _p(K),
-                                                    None if Rc is None else _p(Rc), None if tc is None else _p(tc), gate,
-                                                    int(max_distance), _p(q), _p(ti), _p(d), _p(nm)))
+                                                    _opt(Rc), _opt(tc), gate, int(max_distance), _p(q), _p(ti), _p(d), _p(nm)))
         return q, ti, d, nm
 
     # ---- homography / rotation-only (rpe_pair_homographies / rpe_find_homography; not in the reference)
@@ -517,7 +469,7 @@ class Engine:
         """Stage form of pair_homographies, the sibling of find_essential: per pair the caller's matched pixels (n, 2)
         f32 of both images, one K.  Same outputs; counts[:, 2] (n_E) is -1: no essential RANSAC runs."""
         p1, p2, m = self._pack_points(pts1, pts2)
-        B = len(m); K = np.ascontiguousarray(K, np.float64)
+        B = len(m); K = _f64(K)
         H, R, mask, counts, info = self._homography_outs(B)
         thr = float(self.cfg.ransac_threshold if threshold_px is None else threshold_px)
         self._chk(self.lib.rpe_find_homography(self.h, _p(p1), _p(p2), _p(m), B, _p(K), int(iters), thr,
@@ -535,62 +487,52 @@ class Engine:
     def frames_put(self, frames, slots):
         """Extract frames [n, H, W] (host) once and keep their features in the store slots `slots` (n distinct ints)."""
         frames = np.ascontiguousarray(frames, np.uint8)
-        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        slots = _i32(slots)
         n = frames.shape[0]
         assert frames.shape == (n, self.height, self.width) and slots.size == n, (frames.shape, slots.shape)
         self._chk(self.lib.rpe_frames_put(self.h, _p(frames), n, _p(slots)))
 
     def frames_put_device(self, d_frames, n, slots):
         """Same, frames resident in HBM; asynchronous (the frames must stay valid until the next synchronising call)."""
-        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        slots = _i32(slots)
         assert slots.size == n
         self._chk(self.lib.rpe_frames_put_device(self.h, d_frames, int(n), _p(slots)))
 
     def frames_info(self, slots):
         """(keypoint counts, OVF_* flags) of the slots; count -1 = never filled."""
-        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        slots = _i32(slots)
         cnt = np.zeros(slots.size, np.int32); fl = np.zeros(slots.size, np.uint32)
         self._chk(self.lib.rpe_frames_info(self.h, slots.size, _p(slots), _p(cnt), _p(fl)))
         return cnt, fl
 
     def enqueue_pairs(self, slot1, slot2, K):
-        s1 = np.ascontiguousarray(slot1, np.int32).reshape(-1); s2 = np.ascontiguousarray(slot2, np.int32).reshape(-1)
-        assert s1.size == s2.size
-        K = np.ascontiguousarray(K, np.float64)
+        s1, s2 = _slot_pairs(slot1, slot2)
+        K = _f64(K)
         self._chk(self.lib.rpe_enqueue_pairs(self.h, _p(s1), _p(s2), s1.size, _p(K)))
 
     def estimate_pairs(self, slot1, slot2, K):
         """Poses of the pairs (slot1[p], slot2[p]) of stored frames: the batch's match / RANSAC / pose kernels, no
         extraction.  Returns R, t, inliers, n_matches, status like estimate_batch; the list is 'the last batch' of
         fetch_structure / refine_poses / fetch_overflow / fetch_matched_points afterwards."""
-        s1 = np.ascontiguousarray(slot1, np.int32).reshape(-1); s2 = np.ascontiguousarray(slot2, np.int32).reshape(-1)
-        assert s1.size == s2.size
-        P = s1.size
-        K = np.ascontiguousarray(K, np.float64)
-        R, t, inl, nm, st = self._outs(P)
-        self._chk(self.lib.rpe_estimate_pairs(self.h, _p(s1), _p(s2), P, _p(K), _p(R), _p(t), _p(inl), _p(nm), _p(st)))
-        return R, t, inl, nm, st
+        s1, s2 = _slot_pairs(slot1, slot2)
+        K = _f64(K)
+        return self._estimate(self.lib.rpe_estimate_pairs, s1.size, _p(s1), _p(s2), s1.size, _p(K))
 
     # ---- camera models (rpe_*_cameras; not in the reference): one Camera, or one per frame
     def frames_set_cameras(self, slots, cameras):
         """Cameras of the store slots `slots`; a slot keeps its camera until it is given another."""
-        slots = np.ascontiguousarray(slots, np.int32).reshape(-1)
+        slots = _i32(slots)
         rec = camera_records(cameras, slots.size)
         self._chk(self.lib.rpe_frames_set_cameras(self.h, slots.size, _p(slots), _p(rec)))
 
     def enqueue_pairs_cameras(self, slot1, slot2):
-        s1 = np.ascontiguousarray(slot1, np.int32).reshape(-1); s2 = np.ascontiguousarray(slot2, np.int32).reshape(-1)
-        assert s1.size == s2.size
+        s1, s2 = _slot_pairs(slot1, slot2)
         self._chk(self.lib.rpe_enqueue_pairs_cameras(self.h, _p(s1), _p(s2), s1.size))
 
     def estimate_pairs_cameras(self, slot1, slot2):
         """estimate_pairs with every pair on the cameras of its two slots (frames_set_cameras)."""
-        s1 = np.ascontiguousarray(slot1, np.int32).reshape(-1); s2 = np.ascontiguousarray(slot2, np.int32).reshape(-1)
-        assert s1.size == s2.size
-        P = s1.size
-        R, t, inl, nm, st = self._outs(P)
-        self._chk(self.lib.rpe_estimate_pairs_cameras(self.h, _p(s1), _p(s2), P, _p(R), _p(t), _p(inl), _p(nm), _p(st)))
-        return R, t, inl, nm, st
+        s1, s2 = _slot_pairs(slot1, slot2)
+        return self._estimate(self.lib.rpe_estimate_pairs_cameras, s1.size, _p(s1), _p(s2), s1.size)
 
     def enqueue_batch_cameras_device(self, d_imgs1, d_imgs2, B, cameras1, cameras2):
         c1 = camera_records(cameras1, B); c2 = camera_records(cameras2, B)
@@ -598,19 +540,13 @@ class Engine:
 
     def estimate_batch_cameras_device(self, d_imgs1, d_imgs2, B, cameras1, cameras2):
         c1 = camera_records(cameras1, B); c2 = camera_records(cameras2, B)
-        R, t, inl, nm, st = self._outs(B)
-        self._chk(self.lib.rpe_estimate_batch_cameras_device(self.h, d_imgs1, d_imgs2, B, _p(c1), _p(c2), _p(R), _p(t), _p(inl), _p(nm), _p(st)))
-        return R, t, inl, nm, st
+        return self._estimate(self.lib.rpe_estimate_batch_cameras_device, B, d_imgs1, d_imgs2, B, _p(c1), _p(c2))
 
     def estimate_batch_cameras(self, imgs1, imgs2, cameras1, cameras2):
         """estimate_batch with a camera per image (cameras1[p] for imgs1[p], cameras2[p] for imgs2[p])."""
-        imgs1 = np.ascontiguousarray(imgs1, np.uint8); imgs2 = np.ascontiguousarray(imgs2, np.uint8)
-        B = imgs1.shape[0]
-        assert imgs1.shape == imgs2.shape == (B, self.height, self.width), (imgs1.shape, imgs2.shape)
+        imgs1, imgs2, B = self._image_pair(imgs1, imgs2)
         c1 = camera_records(cameras1, B); c2 = camera_records(cameras2, B)
-        R, t, inl, nm, st = self._outs(B)
-        self._chk(self.lib.rpe_estimate_batch_cameras(self.h, _p(imgs1), _p(imgs2), B, _p(c1), _p(c2), _p(R), _p(t), _p(inl), _p(nm), _p(st)))
-        return R, t, inl, nm, st
+        return self._estimate(self.lib.rpe_estimate_batch_cameras, B, _p(imgs1), _p(imgs2), B, _p(c1), _p(c2))
 
     def undistort_points(self, pts, camera):
         """(n, 2) f32 pixels -> (n, 2) f64 normalised, undistorted coordinates: what the geometry stages of the camera
@@ -622,35 +558,13 @@ class Engine:
         return out
 
     def find_essential_cameras(self, pts1, pts2, cameras1, cameras2):
-        p1, p2, m = self._pack_points(pts1, pts2)
-        B = len(m)
-        c1 = camera_records(cameras1, B); c2 = camera_records(cameras2, B)
-        E = np.zeros((B, 3, 3)); mask = np.zeros((B, self.max_matches), np.uint8)
-        found = np.zeros(B, np.int32); info = np.zeros((B, 4), np.int32)
-        self._chk(self.lib.rpe_find_essential_cameras(self.h, _p(p1), _p(p2), _p(m), B, _p(c1), _p(c2), _p(E), _p(mask), _p(found), _p(info)))
-        return E, mask, found, info
+        return self._find_essential(self.lib.rpe_find_essential_cameras, pts1, pts2, cameras1, cameras2)
 
     def recover_pose_cameras(self, E, pts1, pts2, cameras1, cameras2):
-        p1, p2, m = self._pack_points(pts1, pts2)
-        B = len(m); E = np.ascontiguousarray(E, np.float64)
-        c1 = camera_records(cameras1, B); c2 = camera_records(cameras2, B)
-        R = np.zeros((B, 3, 3)); t = np.zeros((B, 3, 1)); inl = np.zeros(B, np.int32)
-        self._chk(self.lib.rpe_recover_pose_cameras(self.h, _p(E), _p(p1), _p(p2), _p(m), B, _p(c1), _p(c2), _p(R), _p(t), _p(inl)))
-        return R, t, inl
+        return self._recover_pose(self.lib.rpe_recover_pose_cameras, E, pts1, pts2, cameras1, cameras2)
 
     def refine_pose_points_cameras(self, R0, t0, pts1, pts2, masks, cameras1, cameras2, max_iters=10):
-        p1, p2, m = self._pack_points(pts1, pts2)
-        B = len(m)
-        c1 = camera_records(cameras1, B); c2 = camera_records(cameras2, B)
-        R0 = np.ascontiguousarray(np.asarray(R0, np.float64).reshape(B, 9)); t0 = np.ascontiguousarray(np.asarray(t0, np.float64).reshape(B, 3))
-        mk = np.zeros((B, self.max_matches), np.uint8)
-        for i in range(B):
-            mk[i, :m[i]] = np.asarray(masks[i]).astype(bool)[:m[i]]
-        R = np.zeros((B, 3, 3)); t = np.zeros((B, 3, 1)); inl = np.zeros(B, np.int32)
-        info = np.zeros((B, 4), np.int32); rms = np.zeros((B, 2))
-        self._chk(self.lib.rpe_refine_pose_points_cameras(self.h, _p(R0), _p(t0), _p(p1), _p(p2), _p(mk), _p(m), B, _p(c1), _p(c2),
-                                                          max_iters, _p(R), _p(t), _p(inl), _p(info), _p(rms)))
-        return R, t, inl, info, rms
+        return self._refine_pose_points(self.lib.rpe_refine_pose_points_cameras, R0, t0, pts1, pts2, masks, max_iters, cameras1, cameras2)
 
     # ---- stage API
     def orb_detect_and_compute(self, imgs):
@@ -680,29 +594,20 @@ class Engine:
         self.lib.rpe_sift_debug_gauss(self.h, index, _p(out))
         return out
 
-    def match_l2(self, desc1, n1, desc2, n2):
+    def _match(self, fn, desc1, n1, desc2, n2, dim, dtype):
+        """the stage matchers: descriptors [n, dim] of `dtype` per pair and image; distances come back in that norm's type"""
         B = len(n1)
-        d1 = np.zeros((B, self.kcap, self.desc_dim), np.float32); d2 = np.zeros_like(d1)
-        for i in range(B):
-            d1[i, :n1[i]] = desc1[i][:n1[i]]; d2[i, :n2[i]] = desc2[i][:n2[i]]
-        n1 = np.ascontiguousarray(n1, np.int32); n2 = np.ascontiguousarray(n2, np.int32)
-        mm = self.max_matches
-        q = np.zeros((B, mm), np.int32); t = np.zeros((B, mm), np.int32); d = np.zeros((B, mm), np.float32)
-        nm = np.zeros(B, np.int32)
-        self._chk(self.lib.rpe_match_l2(self.h, _p(d1), _p(n1), _p(d2), _p(n2), B, _p(q), _p(t), _p(d), _p(nm)))
+        d1 = self._pack_features(desc1, n1, (dim,), dtype); d2 = self._pack_features(desc2, n2, (dim,), dtype)
+        n1, n2 = _i32(n1), _i32(n2)
+        q, t, d, nm = self._match_outs(B, np.float32 if dtype == np.float32 else np.int32)
+        self._chk(fn(self.h, _p(d1), _p(n1), _p(d2), _p(n2), B, _p(q), _p(t), _p(d), _p(nm)))
         return q, t, d, nm
 
+    def match_l2(self, desc1, n1, desc2, n2):
+        return self._match(self.lib.rpe_match_l2, desc1, n1, desc2, n2, self.desc_dim, np.float32)
+
     def match_hamming(self, desc1, n1, desc2, n2):
-        B = len(n1)
-        d1 = np.zeros((B, self.kcap, 32), np.uint8); d2 = np.zeros_like(d1)
-        for i in range(B):
-            d1[i, :n1[i]] = desc1[i][:n1[i]]; d2[i, :n2[i]] = desc2[i][:n2[i]]
-        n1 = np.ascontiguousarray(n1, np.int32); n2 = np.ascontiguousarray(n2, np.int32)
-        mm = self.max_matches
-        q = np.zeros((B, mm), np.int32); t = np.zeros((B, mm), np.int32); d = np.zeros((B, mm), np.int32)
-        nm = np.zeros(B, np.int32)
-        self._chk(self.lib.rpe_match_hamming(self.h, _p(d1), _p(n1), _p(d2), _p(n2), B, _p(q), _p(t), _p(d), _p(nm)))
-        return q, t, d, nm
+        return self._match(self.lib.rpe_match_hamming, desc1, n1, desc2, n2, 32, np.uint8)
 
     def _pack_points(self, pts1, pts2):
         B = len(pts1)
@@ -712,35 +617,50 @@ class Engine:
             m[i] = len(pts1[i]); p1[i, :m[i]] = pts1[i]; p2[i, :m[i]] = pts2[i]
         return p1, p2, m
 
-    def find_essential(self, pts1, pts2, K):
+    # The geometry stages take one K (rpe_*) or the cameras of the two sides (rpe_*_cameras): `cam` is (K,) or
+    # (cameras1, cameras2), and the arrays it becomes sit where the C signatures have K / cam1, cam2
+    def _camera_args(self, B, *cam):
+        return (_f64(cam[0]),) if len(cam) == 1 else (camera_records(cam[0], B), camera_records(cam[1], B))
+
+    def _find_essential(self, fn, pts1, pts2, *cam):
         p1, p2, m = self._pack_points(pts1, pts2)
-        B = len(m); K = np.ascontiguousarray(K, np.float64)
+        B = len(m)
+        cam = self._camera_args(B, *cam)
         E = np.zeros((B, 3, 3)); mask = np.zeros((B, self.max_matches), np.uint8)
         found = np.zeros(B, np.int32); info = np.zeros((B, 4), np.int32)
-        self._chk(self.lib.rpe_find_essential(self.h, _p(p1), _p(p2), _p(m), B, _p(K), _p(E), _p(mask), _p(found), _p(info)))
+        self._chk(fn(self.h, _p(p1), _p(p2), _p(m), B, *map(_p, cam), _p(E), _p(mask), _p(found), _p(info)))
         return E, mask, found, info
 
-    def recover_pose(self, E, pts1, pts2, K):
+    def _recover_pose(self, fn, E, pts1, pts2, *cam):
         p1, p2, m = self._pack_points(pts1, pts2)
-        B = len(m); K = np.ascontiguousarray(K, np.float64); E = np.ascontiguousarray(E, np.float64)
-        R = np.zeros((B, 3, 3)); t = np.zeros((B, 3, 1)); inl = np.zeros(B, np.int32)
-        self._chk(self.lib.rpe_recover_pose(self.h, _p(E), _p(p1), _p(p2), _p(m), B, _p(K), _p(R), _p(t), _p(inl)))
+        B = len(m); E = _f64(E)
+        cam = self._camera_args(B, *cam)
+        R, t, inl = self._outs(B)[:3]
+        self._chk(fn(self.h, _p(E), _p(p1), _p(p2), _p(m), B, *map(_p, cam), _p(R), _p(t), _p(inl)))
         return R, t, inl
 
-    def refine_pose_points(self, R0, t0, pts1, pts2, masks, K, max_iters=10):
-        """Stage form of refine_poses: per pair the start (R0, t0), the matched points and a mask (one entry per match)
-        selecting the residuals.  Same outputs as refine_poses."""
+    def _refine_pose_points(self, fn, R0, t0, pts1, pts2, masks, max_iters, *cam):
         p1, p2, m = self._pack_points(pts1, pts2)
-        B = len(m); K = np.ascontiguousarray(K, np.float64)
+        B = len(m)
+        cam = self._camera_args(B, *cam)
         R0 = np.ascontiguousarray(np.asarray(R0, np.float64).reshape(B, 9)); t0 = np.ascontiguousarray(np.asarray(t0, np.float64).reshape(B, 3))
         mk = np.zeros((B, self.max_matches), np.uint8)
         for i in range(B):
             mk[i, :m[i]] = np.asarray(masks[i]).astype(bool)[:m[i]]
-        R = np.zeros((B, 3, 3)); t = np.zeros((B, 3, 1)); inl = np.zeros(B, np.int32)
-        info = np.zeros((B, 4), np.int32); rms = np.zeros((B, 2))
-        self._chk(self.lib.rpe_refine_pose_points(self.h, _p(R0), _p(t0), _p(p1), _p(p2), _p(mk), _p(m), B, _p(K), max_iters,
-                                                  _p(R), _p(t), _p(inl), _p(info), _p(rms)))
-        return R, t, inl, info, rms
+        outs = self._refine_outs(B)
+        self._chk(fn(self.h, _p(R0), _p(t0), _p(p1), _p(p2), _p(mk), _p(m), B, *map(_p, cam), max_iters, *map(_p, outs)))
+        return outs
+
+    def find_essential(self, pts1, pts2, K):
+        return self._find_essential(self.lib.rpe_find_essential, pts1, pts2, K)
+
+    def recover_pose(self, E, pts1, pts2, K):
+        return self._recover_pose(self.lib.rpe_recover_pose, E, pts1, pts2, K)
+
+    def refine_pose_points(self, R0, t0, pts1, pts2, masks, K, max_iters=10):
+        """Stage form of refine_poses: per pair the start (R0, t0), the matched points and a mask (one entry per match)
+        selecting the residuals.  Same outputs as refine_poses."""
+        return self._refine_pose_points(self.lib.rpe_refine_pose_points, R0, t0, pts1, pts2, masks, max_iters, K)
 
     # ---- roofline calibration
     def calibrate_valu(self, kind, waves_per_simd):

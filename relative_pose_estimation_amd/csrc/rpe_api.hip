@@ -11,18 +11,39 @@
 
 void rpe_orb_upload_constants(const signed char *disc, int n);
 
-static std::string g_create_err;
+std::string g_create_err;       // what rpe_last_error(NULL) returns: the failure of the last rpe_create
 
-#define HIPCHK(h, call)                                                                         \
-    do {                                                                                        \
-        hipError_t e_ = (call);                                                                 \
-        if (e_ != hipSuccess) {                                                                 \
-            char b_[512];                                                                       \
-            snprintf(b_, sizeof(b_), "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
-            if (h) (h)->err = b_; else g_create_err = b_;                                       \
-            return RPE_ERR_HIP;                                                                 \
-        }                                                                                       \
-    } while (0)
+// ---- argument heads: the checks several entry points share, each with its one message
+static int check_batch(rpe_handle *h, int B)
+{
+    if (B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return RPE_ERR_CAPACITY; }
+    return RPE_OK;
+}
+static int check_stream(rpe_handle *h, int F)
+{
+    if (F > h->n_img_cap || F - 1 > h->cfg.max_batch) { h->err = "stream longer than the handle capacity (frames <= 2*max_batch, pairs <= max_batch)"; return RPE_ERR_CAPACITY; }
+    return RPE_OK;
+}
+static int check_desc_counts(rpe_handle *h, const int32_t *n, int B)
+{
+    for (int i = 0; i < B; ++i) if (n[i] < 0 || n[i] > h->lay.kcap) { h->err = "descriptor count exceeds keypoint capacity"; return RPE_ERR_INVALID; }
+    return RPE_OK;
+}
+static int check_match_counts(rpe_handle *h, const int32_t *m, int B)
+{
+    for (int i = 0; i < B; ++i) if (m[i] < 0 || m[i] > h->cfg.max_matches) { h->err = "match count exceeds max_matches"; return RPE_ERR_INVALID; }
+    return RPE_OK;
+}
+
+// ---- the fetch: a device-to-host copy on the handle's stream for every piece the caller wants (dst != NULL), one wait
+struct Fetch { void *dst; const void *src; size_t bytes; };
+static int fetch(rpe_handle *h, std::initializer_list<Fetch> pieces)
+{
+    for (const Fetch &f : pieces)
+        if (f.dst) HIPCHK(h, hipMemcpyAsync(f.dst, f.src, f.bytes, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
+    return RPE_OK;
+}
 
 static int cv_round(double v) { return (int)lrint(v); }
 static long long align_up(long long v, long long a) { return (v + a - 1) / a * a; }
@@ -129,9 +150,6 @@ static inline uint32_t rng_next(uint64_t &st)
     st = (uint64_t)(uint32_t)st * 4164903690ULL + (uint32_t)(st >> 32);
     return (uint32_t)st;
 }
-
-// a buffer created on first use
-#define DM_ONCE(h, p, n) do { if (!(p)) DM(h, p, n); } while (0)
 
 static int build_tables(rpe_handle *h)
 {
@@ -436,7 +454,7 @@ extern "C" void rpe_destroy(rpe_handle *h)
 // ------------------------------------------------------------ device buffers
 extern "C" int rpe_device_malloc(rpe_handle *h, size_t bytes, void **d_ptr)
 {
-    if (!h || !d_ptr) return RPE_ERR_INVALID;
+    if (!h || !d_ptr) return rpe_invalid(h, "rpe_device_malloc");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipMalloc(d_ptr, bytes));
     h->user_allocs.push_back(*d_ptr);
@@ -444,7 +462,7 @@ extern "C" int rpe_device_malloc(rpe_handle *h, size_t bytes, void **d_ptr)
 }
 extern "C" int rpe_device_free(rpe_handle *h, void *d_ptr)
 {
-    if (!h) return RPE_ERR_INVALID;
+    if (!h) return rpe_invalid(h, "rpe_device_free");
     for (size_t i = 0; i < h->user_allocs.size(); ++i)
         if (h->user_allocs[i] == d_ptr) { h->user_allocs.erase(h->user_allocs.begin() + i); HIPCHK(h, hipFree(d_ptr)); return RPE_OK; }
     h->err = "rpe_device_free: unknown pointer";
@@ -452,47 +470,47 @@ extern "C" int rpe_device_free(rpe_handle *h, void *d_ptr)
 }
 extern "C" int rpe_host_alloc(rpe_handle *h, size_t bytes, void **h_ptr)
 {
-    if (!h || !h_ptr) return RPE_ERR_INVALID;
+    if (!h || !h_ptr) return rpe_invalid(h, "rpe_host_alloc");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipHostMalloc(h_ptr, bytes, hipHostMallocDefault));
     return RPE_OK;
 }
 extern "C" int rpe_host_free(rpe_handle *h, void *h_ptr)
 {
-    if (!h) return RPE_ERR_INVALID;
+    if (!h) return rpe_invalid(h, "rpe_host_free");
     HIPCHK(h, hipHostFree(h_ptr));
     return RPE_OK;
 }
 extern "C" int rpe_host_register(rpe_handle *h, void *h_ptr, size_t bytes)
 {
-    if (!h || !h_ptr) return RPE_ERR_INVALID;
+    if (!h || !h_ptr) return rpe_invalid(h, "rpe_host_register");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipHostRegister(h_ptr, bytes, hipHostRegisterDefault));
     return RPE_OK;
 }
 extern "C" int rpe_host_unregister(rpe_handle *h, void *h_ptr)
 {
-    if (!h || !h_ptr) return RPE_ERR_INVALID;
+    if (!h || !h_ptr) return rpe_invalid(h, "rpe_host_unregister");
     HIPCHK(h, hipHostUnregister(h_ptr));
     return RPE_OK;
 }
 extern "C" int rpe_memcpy_h2d(rpe_handle *h, void *d, const void *s, size_t n)
 {
-    if (!h) return RPE_ERR_INVALID;
+    if (!h) return rpe_invalid(h, "rpe_memcpy_h2d");
     HIPCHK(h, hipMemcpyAsync(d, s, n, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return RPE_OK;
 }
 extern "C" int rpe_memcpy_d2h(rpe_handle *h, void *d, const void *s, size_t n)
 {
-    if (!h) return RPE_ERR_INVALID;
+    if (!h) return rpe_invalid(h, "rpe_memcpy_d2h");
     HIPCHK(h, hipMemcpyAsync(d, s, n, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return RPE_OK;
 }
 extern "C" int rpe_synchronize(rpe_handle *h)
 {
-    if (!h) return RPE_ERR_INVALID;
+    if (!h) return rpe_invalid(h, "rpe_synchronize");
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return RPE_OK;
 }
@@ -567,17 +585,22 @@ static int set_K(rpe_handle *h, const double K[9])
     return RPE_OK;
 }
 
-// ---- the last run (RpeLastRun).  An entry point that runs pairs calls last_run_begin with the run it is about to launch
-// (a replayed graph included); one that overwrites workspace buffers without running pairs calls last_run_end.
-static RpeLastRun &last_run_begin(rpe_handle *h, RpeLastRun::Kind kind, const RpeRun &run)
+// ---- the last run (RpeLastRun).  Every write to h->last is in the four functions below; every test of it in last_run_gate.
+// An entry point that runs pairs calls last_run_begin with the run it is about to launch (a replayed graph included); one
+// that overwrites workspace buffers without running pairs calls last_run_end.  A pair list hands over its slot arrays
+// (kept as `tab`); a chunked host batch runs first and hands over the flag words it collected, image 1 of pair p at
+// flags[p] and image 2 at flags[max_batch + p] (kept per pair as `ovf`).
+static void last_run_begin(rpe_handle *h, RpeLastRun::Kind kind, const RpeRun &run, const int32_t *slot1 = nullptr,
+                           const int32_t *slot2 = nullptr, const unsigned *flags = nullptr)
 {
     RpeLastRun &l = h->last;
     l.kind = kind; l.pairs = run.pairs; l.run = run;
     l.tab.clear(); l.ovf.clear();
+    for (int p = 0; kind == RpeLastRun::LIST && p < run.pairs; ++p) { l.tab.push_back(slot1[p]); l.tab.push_back(slot2[p]); }
+    for (int p = 0; kind == RpeLastRun::CHUNKED && p < run.pairs; ++p) l.ovf.push_back(flags[p] | flags[h->cfg.max_batch + p]);
     l.per_match = kind != RpeLastRun::CHUNKED;      // a chunked batch leaves its last chunk's only
     l.structure = 0;
     h->ev_first = kind == RpeLastRun::LIST ? RPE_STAGE_MATCH : 0;
-    return l;
 }
 
 // The last run's claim on the per-match buffers ends (a stage call overwrites them, a failed launch sequence never filled
@@ -589,23 +612,61 @@ static void last_run_end(rpe_handle *h, bool images_too = false)
     if (images_too) { h->last.kind = RpeLastRun::NONE; h->last.pairs = 0; }
 }
 
-// Precondition of the calls behind the last run.  `chunked`: the refusal of a chunked host batch (nullptr: the call serves
-// one); per_match: the call reads the per-match buffers; n: pairs asked for
-static int last_run_check(rpe_handle *h, const char *who, int n, const char *chunked, bool per_match)
+// The frame store changed under a pair list.  resized (rpe_frames_reserve): the list's slot numbers mean nothing any more,
+// its table goes; either way (rpe_frames_set_cameras too) a camera list read the store's camera records: its per-match
+// results end here
+static void last_run_store_changed(rpe_handle *h, bool resized)
 {
-    const RpeLastRun &l = h->last;
-    if (chunked && l.kind == RpeLastRun::CHUNKED) { h->err = chunked; return RPE_ERR_INVALID; }
-    if (per_match && !l.per_match) { h->err = std::string(who) + ": no batch or stream since the last stage-API call (it overwrote the per-match buffers)"; return RPE_ERR_INVALID; }
-    if (n > l.pairs) { h->err = std::string(who) + ": more pairs than the last batch had"; return RPE_ERR_INVALID; }
-    return RPE_OK;
+    if (resized) h->last.tab.clear();
+    if (h->last.run.cam.tab) last_run_end(h);
 }
 
-// the first B pairs of the last run: what rpe_fetch_structure / rpe_refine_poses launch on
+// the first B pairs of the last run: what the calls behind it launch on
 static RpeRun last_run_first(const rpe_handle *h, int B)
 {
     RpeRun r = h->last.run;
     r.pairs = B;
     return r;
+}
+
+// Makes d_mask (status form), d_pose_mask and d_points current for the first B pairs of the last run: the two buffers on
+// first use, the structure kernels (again: always; otherwise only when the run is not covered that far), the record
+static int last_run_structure(rpe_handle *h, int B, bool always)
+{
+    const size_t cap = (size_t)h->cfg.max_batch * h->cfg.max_matches;
+    DM_ONCE(h, h->d_pose_mask, cap);
+    DM_ONCE(h, h->d_points, cap * 3);
+    if (!always && h->last.structure >= B) return RPE_OK;
+    rpe_launch_structure(h, last_run_first(h, B));
+    HIPCHK(h, hipGetLastError());
+    h->last.structure = std::max(h->last.structure, B);
+    return RPE_OK;
+}
+
+// The gate of the calls behind the last run: the only code that refuses one for the state of h->last.  n: pairs asked for.
+//
+// | call                                                  | NEED_UNCHUNKED        | NEED_PER_MATCH | NEED_COUNT (n <= pairs)    | NEED_TABLE (a list keeps 2*n entries) |
+// |-------------------------------------------------------|-----------------------|----------------|----------------------------|---------------------------------------|
+// | rpe_fetch_overflow                                    | no (served from ovf)  | no             | yes                        | yes, n = n_pairs                      |
+// | rpe_fetch_matched_points, rpe_fetch_match_indices     | yes                   | no             | no                         | no                                    |
+// | rpe_fetch_structure, rpe_refine_poses                 | yes                   | yes            | yes                        | no                                    |
+// | rpe_scale_links                                       | yes                   | yes            | no (checks its links' own) | yes, n = the run's pairs              |
+// | rpe_guided_matches, rpe_pair_homographies             | yes                   | yes            | yes                        | yes, n = B                            |
+//
+// Tested in this order, so a state gives one message whatever the call.  Two tests stay with their only caller:
+// rpe_scale_links' "the pairs of a batch share no frame" and rpe_fetch_overflow's slot range.
+enum : unsigned { NEED_UNCHUNKED = 1, NEED_PER_MATCH = 2, NEED_COUNT = 4, NEED_TABLE = 8 };
+static int last_run_gate(rpe_handle *h, const char *who, int n, unsigned needs)
+{
+    const RpeLastRun &l = h->last;
+    const char *why = nullptr;
+    if ((needs & NEED_UNCHUNKED) && l.kind == RpeLastRun::CHUNKED)
+        why = ": the last host batch ran in chunks: what a run leaves per match is kept for unchunked and device-resident batches (rpe_estimate_batch_device) only";
+    else if ((needs & NEED_PER_MATCH) && !l.per_match) why = ": no batch or stream since the last stage-API call (it overwrote the per-match buffers)";
+    else if ((needs & NEED_COUNT) && n > l.pairs) why = ": more pairs than the last batch had";
+    else if ((needs & NEED_TABLE) && l.kind == RpeLastRun::LIST && l.tab.size() < (size_t)2 * n) why = ": the frame store was resized since the pair list";
+    if (why) { h->err = std::string(who) + why; return RPE_ERR_INVALID; }
+    return RPE_OK;
 }
 
 // match -> RANSAC -> pose of run r: the tail of the image paths and the whole of a pair list
@@ -639,8 +700,8 @@ static int run_images(rpe_handle *h, const uint8_t *d_a, const uint8_t *d_b, int
 
 extern "C" int rpe_enqueue_batch_device(rpe_handle *h, const uint8_t *d_imgs1, const uint8_t *d_imgs2, int B, const double K[9])
 {
-    if (!h || !d_imgs1 || !d_imgs2 || !K || B < 1) return RPE_ERR_INVALID;
-    if (B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return RPE_ERR_CAPACITY; }
+    if (!h || !d_imgs1 || !d_imgs2 || !K || B < 1) return rpe_invalid(h, "rpe_enqueue_batch_device");
+    if (int rc = check_batch(h, B)) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     int rc = set_K(h, K);
     if (rc) return rc;
@@ -684,8 +745,8 @@ extern "C" int rpe_enqueue_batch_device(rpe_handle *h, const uint8_t *d_imgs1, c
 // frame twice, batch_processor.py:79,92); pair p reads image slots p and p+1.
 extern "C" int rpe_enqueue_stream_device(rpe_handle *h, const uint8_t *d_frames, int F, const double K[9])
 {
-    if (!h || !d_frames || !K || F < 2) return RPE_ERR_INVALID;
-    if (F > h->n_img_cap || F - 1 > h->cfg.max_batch) { h->err = "stream longer than the handle capacity (frames <= 2*max_batch, pairs <= max_batch)"; return RPE_ERR_CAPACITY; }
+    if (!h || !d_frames || !K || F < 2) return rpe_invalid(h, "rpe_enqueue_stream_device");
+    if (int rc = check_stream(h, F)) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     int rc = set_K(h, K);
     if (rc) return rc;
@@ -695,8 +756,8 @@ extern "C" int rpe_enqueue_stream_device(rpe_handle *h, const uint8_t *d_frames,
 extern "C" int rpe_estimate_stream(rpe_handle *h, const uint8_t *h_frames, int F, const double K[9],
                                    double *R, double *t, int32_t *inliers, int32_t *n_matches, int32_t *status)
 {
-    if (!h || !h_frames || F < 2) return RPE_ERR_INVALID;
-    if (F > h->n_img_cap || F - 1 > h->cfg.max_batch) { h->err = "stream longer than the handle capacity (frames <= 2*max_batch, pairs <= max_batch)"; return RPE_ERR_CAPACITY; }
+    if (!h || !h_frames || F < 2) return rpe_invalid(h, "rpe_estimate_stream");
+    if (int rc = check_stream(h, F)) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const size_t img = (size_t)h->cfg.width * h->cfg.height;
     // d_stage1 holds max_batch + 1 frames: every legal stream fits the persistent staging buffer
@@ -738,7 +799,7 @@ __global__ __launch_bounds__(256) void bgr_to_gray_kernel(const uint8_t *__restr
 
 extern "C" int rpe_bgr_to_gray_device(rpe_handle *h, const uint8_t *d_bgr, size_t n_pixels, int order, uint8_t *d_gray)
 {
-    if (!h || !d_bgr || !d_gray || (order != RPE_ORDER_BGR && order != RPE_ORDER_RGB)) return RPE_ERR_INVALID;
+    if (!h || !d_bgr || !d_gray || (order != RPE_ORDER_BGR && order != RPE_ORDER_RGB)) return rpe_invalid(h, "rpe_bgr_to_gray_device");
     if (((uintptr_t)d_bgr | (uintptr_t)d_gray) & 15) { h->err = "rpe_bgr_to_gray_device: buffers must be 16-byte aligned"; return RPE_ERR_INVALID; }
     if (n_pixels == 0) return RPE_OK;
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -752,25 +813,25 @@ extern "C" int rpe_bgr_to_gray_device(rpe_handle *h, const uint8_t *d_bgr, size_
 
 extern "C" int rpe_bgr_to_gray(rpe_handle *h, const uint8_t *h_bgr, size_t n_pixels, int order, uint8_t *h_gray)
 {
-    if (!h || !h_bgr || !h_gray) return RPE_ERR_INVALID;
+    if (!h || !h_bgr || !h_gray) return rpe_invalid(h, "rpe_bgr_to_gray");
     if (n_pixels == 0) return RPE_OK;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     void *d_in = nullptr, *d_out = nullptr;
     HIPCHK(h, hipMalloc(&d_in, n_pixels * 3));
     if (hipMalloc(&d_out, n_pixels) != hipSuccess) { hipFree(d_in); h->err = "hipMalloc failed"; return RPE_ERR_HIP; }
-    int rc = RPE_OK;
-    if (hipMemcpyAsync(d_in, h_bgr, n_pixels * 3, hipMemcpyHostToDevice, h->stream) != hipSuccess) rc = RPE_ERR_HIP;
-    if (!rc) rc = rpe_bgr_to_gray_device(h, (const uint8_t *)d_in, n_pixels, order, (uint8_t *)d_out);
-    if (!rc && hipMemcpyAsync(h_gray, d_out, n_pixels, hipMemcpyDeviceToHost, h->stream) != hipSuccess) rc = RPE_ERR_HIP;
-    if (hipStreamSynchronize(h->stream) != hipSuccess && !rc) rc = RPE_ERR_HIP;
+    int rc = RPE_OK;                                         // of the conversion, which leaves its own text
+    bool copied = hipMemcpyAsync(d_in, h_bgr, n_pixels * 3, hipMemcpyHostToDevice, h->stream) == hipSuccess;
+    if (copied) rc = rpe_bgr_to_gray_device(h, (const uint8_t *)d_in, n_pixels, order, (uint8_t *)d_out);
+    if (copied && !rc) copied = hipMemcpyAsync(h_gray, d_out, n_pixels, hipMemcpyDeviceToHost, h->stream) == hipSuccess;
+    copied = (hipStreamSynchronize(h->stream) == hipSuccess) && copied;
     hipFree(d_in); hipFree(d_out);
-    if (rc == RPE_ERR_HIP && h->err.empty()) h->err = "rpe_bgr_to_gray: HIP failure";
+    if (!rc && !copied) { h->err = "rpe_bgr_to_gray: HIP failure"; rc = RPE_ERR_HIP; }
     return rc;
 }
 
 extern "C" int rpe_fetch_results(rpe_handle *h, int B, double *R, double *t, int32_t *inliers, int32_t *n_matches, int32_t *status)
 {
-    if (!h || B < 1 || B > h->cfg.max_batch) return RPE_ERR_INVALID;
+    if (!h || B < 1 || B > h->cfg.max_batch) return rpe_invalid(h, "rpe_fetch_results");
     const ResultBlock rb(h);
     // the used part of every section when the batch is small, the whole block in one piece otherwise
     if ((size_t)B * 4 < (size_t)h->cfg.max_batch) {
@@ -786,8 +847,8 @@ extern "C" int rpe_fetch_results(rpe_handle *h, int B, double *R, double *t, int
 
 extern "C" int rpe_fetch_overflow(rpe_handle *h, int n_pairs, uint32_t *flags)
 {
-    if (!h || !flags || n_pairs < 1 || n_pairs > h->cfg.max_batch) return RPE_ERR_INVALID;
-    int rc = last_run_check(h, "rpe_fetch_overflow", n_pairs, nullptr, false);
+    if (!h || !flags || n_pairs < 1 || n_pairs > h->cfg.max_batch) return rpe_invalid(h, "rpe_fetch_overflow");
+    int rc = last_run_gate(h, "rpe_fetch_overflow", n_pairs, NEED_COUNT | NEED_TABLE);
     if (rc) return rc;
     const RpeLastRun &l = h->last;
     if (l.kind == RpeLastRun::CHUNKED) {
@@ -797,20 +858,17 @@ extern "C" int rpe_fetch_overflow(rpe_handle *h, int n_pairs, uint32_t *flags)
     }
     if (l.kind == RpeLastRun::LIST) {
         // a pair list: the flags live with the frames (a put since then ended the run, a resize of the store emptied its table)
-        if (l.tab.size() < (size_t)2 * n_pairs) { h->err = "rpe_fetch_overflow: the frame store was resized since the pair list"; return RPE_ERR_INVALID; }
         int lo = l.tab[0], hi = lo;
         for (int i = 0; i < 2 * n_pairs; ++i) { lo = std::min(lo, l.tab[i]); hi = std::max(hi, l.tab[i]); }
         if (lo < 0 || hi >= h->fs.cap) { h->err = "rpe_fetch_overflow: the pair list names slots outside the store"; return RPE_ERR_INVALID; }
         std::vector<unsigned> ov((size_t)(hi - lo + 1));       // the slots the list names, not the whole store
-        HIPCHK(h, hipMemcpyAsync(ov.data(), h->fs.d_ovf + lo, sizeof(unsigned) * ov.size(), hipMemcpyDeviceToHost, h->stream));
-        HIPCHK(h, hipStreamSynchronize(h->stream));
+        if ((rc = fetch(h, {{ov.data(), h->fs.d_ovf + lo, sizeof(unsigned) * ov.size()}})) != RPE_OK) return rc;
         for (int p = 0; p < n_pairs; ++p) flags[p] = ov[(size_t)(l.tab[2 * p] - lo)] | ov[(size_t)(l.tab[2 * p + 1] - lo)];
         return RPE_OK;
     }
     const int img2_base = l.run.feat.img2_base, nimg = img2_base + n_pairs;
     std::vector<unsigned> ov((size_t)nimg);
-    HIPCHK(h, hipMemcpyAsync(ov.data(), h->d_ovf, sizeof(unsigned) * (size_t)nimg, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if ((rc = fetch(h, {{ov.data(), h->d_ovf, sizeof(unsigned) * (size_t)nimg}})) != RPE_OK) return rc;
     for (int p = 0; p < n_pairs; ++p) flags[p] = ov[p] | ov[img2_base + p];
     return RPE_OK;
 }
@@ -843,8 +901,8 @@ static int stage_images(rpe_handle *h, const uint8_t *h_imgs, int n, int &na, in
 extern "C" int rpe_estimate_batch(rpe_handle *h, const uint8_t *h_imgs1, const uint8_t *h_imgs2, int B, const double K[9],
                                   double *R, double *t, int32_t *inliers, int32_t *n_matches, int32_t *status)
 {
-    if (!h || !h_imgs1 || !h_imgs2 || B < 1) return RPE_ERR_INVALID;
-    if (B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return RPE_ERR_CAPACITY; }
+    if (!h || !h_imgs1 || !h_imgs2 || B < 1) return rpe_invalid(h, "rpe_estimate_batch");
+    if (int rc = check_batch(h, B)) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const size_t img = (size_t)h->cfg.width * h->cfg.height;
     // Large host batches run in chunks: all uploads are queued on a copy stream, chunk c's kernels wait for its
@@ -898,54 +956,38 @@ extern "C" int rpe_estimate_batch(rpe_handle *h, const uint8_t *h_imgs1, const u
     HIPCHK(h, hipMemcpyAsync(ov.data(), h->d_ovfall, sizeof(unsigned) * 2 * MB, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     unpack_results(h, B, R, t, inliers, n_matches, status);
-    RpeLastRun &l = last_run_begin(h, RpeLastRun::CHUNKED, rpe_run_batch(h, B));
-    l.ovf.resize((size_t)B);
-    for (int p2 = 0; p2 < B; ++p2) l.ovf[(size_t)p2] = ov[(size_t)p2] | ov[MB + (size_t)p2];
+    last_run_begin(h, RpeLastRun::CHUNKED, rpe_run_batch(h, B), nullptr, nullptr, ov.data());
     return RPE_OK;
 }
 
 extern "C" int rpe_fetch_matched_points(rpe_handle *h, int B, float *pts1, float *pts2)
 {
-    if (!h || B < 1 || B > h->cfg.max_batch) return RPE_ERR_INVALID;
-    int rc = last_run_check(h, "rpe_fetch_matched_points", 0, "the last host batch ran in chunks: matched points are kept for device-resident batches (rpe_estimate_batch_device) only", false);
+    if (!h || B < 1 || B > h->cfg.max_batch) return rpe_invalid(h, "rpe_fetch_matched_points");
+    int rc = last_run_gate(h, "rpe_fetch_matched_points", B, NEED_UNCHUNKED);
     if (rc) return rc;
     const size_t n = sizeof(float2) * (size_t)B * h->cfg.max_matches;
-    if (pts1) HIPCHK(h, hipMemcpyAsync(pts1, h->d_pts1, n, hipMemcpyDeviceToHost, h->stream));
-    if (pts2) HIPCHK(h, hipMemcpyAsync(pts2, h->d_pts2, n, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return RPE_OK;
+    return fetch(h, {{pts1, h->d_pts1, n}, {pts2, h->d_pts2, n}});
 }
 
 extern "C" int rpe_fetch_structure(rpe_handle *h, int B, uint8_t *ransac_mask, uint8_t *pose_mask, double *points)
 {
-    if (!h || B < 1 || B > h->cfg.max_batch) return RPE_ERR_INVALID;
-    int rc = last_run_check(h, "rpe_fetch_structure", B, "rpe_fetch_structure: the last host batch ran in chunks: per-match results are kept for unchunked and device-resident batches only", true);
+    if (!h || B < 1 || B > h->cfg.max_batch) return rpe_invalid(h, "rpe_fetch_structure");
+    int rc = last_run_gate(h, "rpe_fetch_structure", B, NEED_UNCHUNKED | NEED_PER_MATCH | NEED_COUNT);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    const size_t cap = (size_t)h->cfg.max_batch * h->cfg.max_matches, n = (size_t)B * h->cfg.max_matches;
-    DM_ONCE(h, h->d_pose_mask, cap);
-    DM_ONCE(h, h->d_points, cap * 3);
-    rpe_launch_structure(h, last_run_first(h, B));
-    HIPCHK(h, hipGetLastError());
-    h->last.structure = std::max(h->last.structure, B);
-    if (ransac_mask) HIPCHK(h, hipMemcpyAsync(ransac_mask, h->d_mask, n, hipMemcpyDeviceToHost, h->stream));
-    if (pose_mask) HIPCHK(h, hipMemcpyAsync(pose_mask, h->d_pose_mask, n, hipMemcpyDeviceToHost, h->stream));
-    if (points) HIPCHK(h, hipMemcpyAsync(points, h->d_points, n * 3 * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return RPE_OK;
+    if ((rc = last_run_structure(h, B, true)) != RPE_OK) return rc;
+    const size_t n = (size_t)B * h->cfg.max_matches;
+    return fetch(h, {{ransac_mask, h->d_mask, n}, {pose_mask, h->d_pose_mask, n}, {points, h->d_points, n * 3 * sizeof(double)}});
 }
 
 extern "C" int rpe_fetch_match_indices(rpe_handle *h, int B, int32_t *qidx, int32_t *tidx)
 {
-    if (!h || B < 1 || B > h->cfg.max_batch) return RPE_ERR_INVALID;
-    int rc = last_run_check(h, "rpe_fetch_match_indices", 0, "the last host batch ran in chunks: match indices are kept for device-resident batches (rpe_estimate_batch_device) only", false);
+    if (!h || B < 1 || B > h->cfg.max_batch) return rpe_invalid(h, "rpe_fetch_match_indices");
+    int rc = last_run_gate(h, "rpe_fetch_match_indices", B, NEED_UNCHUNKED);
     if (rc) return rc;
     const size_t mm = (size_t)h->cfg.max_matches, n = sizeof(int) * (size_t)B * mm;
     std::vector<int> cnt((size_t)B);
-    HIPCHK(h, hipMemcpyAsync(cnt.data(), h->d_m_n, sizeof(int) * (size_t)B, hipMemcpyDeviceToHost, h->stream));
-    if (qidx) HIPCHK(h, hipMemcpyAsync(qidx, h->d_m_q, n, hipMemcpyDeviceToHost, h->stream));
-    if (tidx) HIPCHK(h, hipMemcpyAsync(tidx, h->d_m_t, n, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if ((rc = fetch(h, {{cnt.data(), h->d_m_n, sizeof(int) * (size_t)B}, {qidx, h->d_m_q, n}, {tidx, h->d_m_t, n}})) != RPE_OK) return rc;
     for (int p = 0; p < B; ++p)
         for (size_t i = (size_t)std::min(std::max(cnt[(size_t)p], 0), (int)mm); i < mm; ++i) {
             if (qidx) qidx[(size_t)p * mm + i] = -1;
@@ -959,14 +1001,13 @@ extern "C" int rpe_fetch_match_indices(rpe_handle *h, int B, int32_t *qidx, int3
 extern "C" int rpe_scale_links(rpe_handle *h, int L, const int32_t *pair_a, const int32_t *pair_b, const int32_t *side,
                                int min_shared, double *stats, int32_t *n_shared, int32_t *code)
 {
-    if (!h) return RPE_ERR_INVALID;
+    if (!h) return rpe_invalid(h, "rpe_scale_links");
     if (L < 0 || min_shared < 1 || (L > 0 && (!pair_a || !pair_b || !side))) { h->err = "rpe_scale_links: L < 0, min_shared < 1 or a null link array"; return RPE_ERR_INVALID; }
-    int rc = last_run_check(h, "rpe_scale_links", 0, "rpe_scale_links: the last host batch ran in chunks: per-match results are kept for unchunked and device-resident batches only", true);
+    int rc = last_run_gate(h, "rpe_scale_links", h->last.pairs, NEED_UNCHUNKED | NEED_PER_MATCH | NEED_TABLE);
     if (rc) return rc;
-    RpeLastRun &l = h->last;
+    const RpeLastRun &l = h->last;
     const bool list = l.kind == RpeLastRun::LIST;
     if (!list && l.run.feat.img2_base != 1) { h->err = "rpe_scale_links: the pairs of a batch share no frame (links join the pairs of a stream or of a pair list)"; return RPE_ERR_INVALID; }
-    if (list && l.tab.size() < (size_t)2 * l.pairs) { h->err = "rpe_scale_links: the frame store was resized since the pair list"; return RPE_ERR_INVALID; }
     if (L > 4 * h->cfg.max_batch) { h->err = "rpe_scale_links: more than 4*max_batch links in one call"; return RPE_ERR_CAPACITY; }
     std::vector<RpeLink> tbl((size_t)L);
     for (int i = 0; i < L; ++i) {
@@ -982,24 +1023,16 @@ extern "C" int rpe_scale_links(rpe_handle *h, int L, const int32_t *pair_a, cons
     }
     if (L == 0) return RPE_OK;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    const size_t cap = (size_t)h->cfg.max_batch * h->cfg.max_matches, lcap = (size_t)4 * h->cfg.max_batch;
-    DM_ONCE(h, h->d_pose_mask, cap);
-    DM_ONCE(h, h->d_points, cap * 3);
+    const size_t lcap = (size_t)4 * h->cfg.max_batch;
     DM_ONCE(h, h->d_links, lcap); DM_ONCE(h, h->d_link_stats, lcap * 3);
     DM_ONCE(h, h->d_link_n, lcap); DM_ONCE(h, h->d_link_code, lcap);
-    if (l.structure < l.pairs) {
-        rpe_launch_structure(h, l.run);
-        HIPCHK(h, hipGetLastError());
-        l.structure = l.pairs;
-    }
+    if ((rc = last_run_structure(h, l.pairs, false)) != RPE_OK) return rc;
     HIPCHK(h, hipMemcpyAsync(h->d_links, tbl.data(), sizeof(RpeLink) * (size_t)L, hipMemcpyHostToDevice, h->stream));
     if ((rc = rpe_launch_scale_links(h, L, min_shared)) != RPE_OK) { h->err = "rpe_scale_links: could not size the kernel's LDS"; return rc; }
     HIPCHK(h, hipGetLastError());
-    if (stats) HIPCHK(h, hipMemcpyAsync(stats, h->d_link_stats, sizeof(double) * 3 * (size_t)L, hipMemcpyDeviceToHost, h->stream));
-    if (n_shared) HIPCHK(h, hipMemcpyAsync(n_shared, h->d_link_n, sizeof(int) * (size_t)L, hipMemcpyDeviceToHost, h->stream));
-    if (code) HIPCHK(h, hipMemcpyAsync(code, h->d_link_code, sizeof(int) * (size_t)L, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));       // also: the link table has left tbl
-    return RPE_OK;
+    // the wait also covers the upload: the link table has left tbl
+    return fetch(h, {{stats, h->d_link_stats, sizeof(double) * 3 * (size_t)L}, {n_shared, h->d_link_n, sizeof(int) * (size_t)L},
+                     {code, h->d_link_code, sizeof(int) * (size_t)L}});
 }
 
 // refined poses: device buffers on first use, launch, fetch
@@ -1018,21 +1051,16 @@ static int refine_run(rpe_handle *h, const RpeRun &r, int max_iters, bool from_b
     const int B = r.pairs;
     rpe_launch_refine(h, r, max_iters, from_batch);
     HIPCHK(h, hipGetLastError());
-    if (R) HIPCHK(h, hipMemcpyAsync(R, h->d_ref_R, sizeof(double) * 9 * B, hipMemcpyDeviceToHost, h->stream));
-    if (t) HIPCHK(h, hipMemcpyAsync(t, h->d_ref_t, sizeof(double) * 3 * B, hipMemcpyDeviceToHost, h->stream));
-    if (inliers) HIPCHK(h, hipMemcpyAsync(inliers, h->d_ref_inl, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
-    if (info) HIPCHK(h, hipMemcpyAsync(info, h->d_ref_info, sizeof(int) * 4 * B, hipMemcpyDeviceToHost, h->stream));
-    if (rms) HIPCHK(h, hipMemcpyAsync(rms, h->d_ref_rms, sizeof(double) * 2 * B, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return RPE_OK;
+    return fetch(h, {{R, h->d_ref_R, sizeof(double) * 9 * B}, {t, h->d_ref_t, sizeof(double) * 3 * B}, {inliers, h->d_ref_inl, sizeof(int) * B},
+                     {info, h->d_ref_info, sizeof(int) * 4 * B}, {rms, h->d_ref_rms, sizeof(double) * 2 * B}});
 }
 
 extern "C" int rpe_refine_poses(rpe_handle *h, int B, int max_iters, double *R, double *t, int32_t *inliers,
                                 int32_t *info, double *rms)
 {
-    if (!h || B < 1 || B > h->cfg.max_batch) return RPE_ERR_INVALID;
+    if (!h || B < 1 || B > h->cfg.max_batch) return rpe_invalid(h, "rpe_refine_poses");
     if (max_iters < 1 || max_iters > 100) { h->err = "rpe_refine_poses: max_iters must be 1 ... 100"; return RPE_ERR_INVALID; }
-    int rc = last_run_check(h, "rpe_refine_poses", B, "rpe_refine_poses: the last host batch ran in chunks: per-match results are kept for unchunked and device-resident batches only", true);
+    int rc = last_run_gate(h, "rpe_refine_poses", B, NEED_UNCHUNKED | NEED_PER_MATCH | NEED_COUNT);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if ((rc = refine_alloc(h)) != RPE_OK) return rc;
@@ -1079,27 +1107,21 @@ static int guided_run(rpe_handle *h, const RpeRun &r, const double *R, const dou
     }
     rpe_launch_guided(h, r, R ? h->d_gm_R : h->d_R, R ? h->d_gm_tr : h->d_t, R ? (const int *)nullptr : (const int *)h->d_status, gate_px, max_distance);
     HIPCHK(h, hipGetLastError());
-    if (qidx) HIPCHK(h, hipMemcpyAsync(qidx, h->d_gm_q, sizeof(int) * n, hipMemcpyDeviceToHost, h->stream));
-    if (tidx) HIPCHK(h, hipMemcpyAsync(tidx, h->d_gm_t, sizeof(int) * n, hipMemcpyDeviceToHost, h->stream));
-    if (dist) HIPCHK(h, hipMemcpyAsync(dist, h->d_gm_d, sizeof(int) * n, hipMemcpyDeviceToHost, h->stream));
-    if (pts1) HIPCHK(h, hipMemcpyAsync(pts1, h->d_gm_pts1, sizeof(float2) * n, hipMemcpyDeviceToHost, h->stream));
-    if (pts2) HIPCHK(h, hipMemcpyAsync(pts2, h->d_gm_pts2, sizeof(float2) * n, hipMemcpyDeviceToHost, h->stream));
-    if (n_matches) HIPCHK(h, hipMemcpyAsync(n_matches, h->d_gm_n, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));       // also: the poses have left the caller's arrays
-    return RPE_OK;
+    // the wait also covers the upload: the poses have left the caller's arrays
+    return fetch(h, {{qidx, h->d_gm_q, sizeof(int) * n}, {tidx, h->d_gm_t, sizeof(int) * n}, {dist, h->d_gm_d, sizeof(int) * n},
+                     {pts1, h->d_gm_pts1, sizeof(float2) * n}, {pts2, h->d_gm_pts2, sizeof(float2) * n}, {n_matches, h->d_gm_n, sizeof(int) * B}});
 }
 
 extern "C" int rpe_guided_matches(rpe_handle *h, int B, const double *R, const double *t, double gate_px, int max_distance,
                                   int32_t *qidx, int32_t *tidx, int32_t *dist, float *pts1, float *pts2, int32_t *n_matches)
 {
-    if (!h || B < 1 || B > h->cfg.max_batch) return RPE_ERR_INVALID;
+    if (!h || B < 1 || B > h->cfg.max_batch) return rpe_invalid(h, "rpe_guided_matches");
     int rc = guided_check(h, "rpe_guided_matches", B, R, t, gate_px, max_distance);
     if (rc) return rc;
     // the features of the run must still be where it read them (a stage call or a put overwrote the workspace's) and, under
     // the run's own poses, d_R / d_t / d_status its results
-    rc = last_run_check(h, "rpe_guided_matches", B, "rpe_guided_matches: the last host batch ran in chunks: features are kept for unchunked and device-resident batches only", true);
+    rc = last_run_gate(h, "rpe_guided_matches", B, NEED_UNCHUNKED | NEED_PER_MATCH | NEED_COUNT | NEED_TABLE);
     if (rc) return rc;
-    if (h->last.kind == RpeLastRun::LIST && h->last.tab.size() < (size_t)2 * B) { h->err = "rpe_guided_matches: the frame store was resized since the pair list"; return RPE_ERR_INVALID; }
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if ((rc = guided_alloc(h)) != RPE_OK) return rc;
     return guided_run(h, last_run_first(h, B), R, t, gate_px, max_distance, qidx, tidx, dist, pts1, pts2, n_matches);
@@ -1110,14 +1132,12 @@ extern "C" int rpe_match_hamming_guided(rpe_handle *h, const uint8_t *h_desc1, c
                                         const double K[9], const double *R, const double *t, double gate_px, int max_distance,
                                         int32_t *qidx, int32_t *tidx, int32_t *dist, int32_t *n_matches)
 {
-    if (!h || !h_desc1 || !h_pts1 || !n1 || !h_desc2 || !h_pts2 || !n2 || !K || !R || !t || B < 1) return RPE_ERR_INVALID;
-    if (B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return RPE_ERR_CAPACITY; }
+    if (!h || !h_desc1 || !h_pts1 || !n1 || !h_desc2 || !h_pts2 || !n2 || !K || !R || !t || B < 1) return rpe_invalid(h, "rpe_match_hamming_guided");
+    if (int rc = check_batch(h, B)) return rc;
     int rc = guided_check(h, "rpe_match_hamming_guided", B, R, t, gate_px, max_distance);
     if (rc) return rc;
     const size_t kcap = (size_t)h->lay.kcap;
-    for (int i = 0; i < B; ++i) if (n1[i] < 0 || n2[i] < 0 || n1[i] > (int)kcap || n2[i] > (int)kcap) {
-        h->err = "descriptor count exceeds keypoint capacity"; return RPE_ERR_INVALID;
-    }
+    if ((rc = check_desc_counts(h, n1, B)) != RPE_OK || (rc = check_desc_counts(h, n2, B)) != RPE_OK) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if ((rc = guided_alloc(h)) != RPE_OK) return rc;
     last_run_end(h);                            // overwrites the workspace's features
@@ -1160,25 +1180,19 @@ static int homography_run(rpe_handle *h, const RpeRun &r, int iters, double thre
     int rc = rpe_launch_homography(h, r, iters, threshold_px, from_batch);
     if (rc != RPE_OK) { h->err = "homography: could not size the kernel's LDS"; return rc; }
     HIPCHK(h, hipGetLastError());
-    if (H) HIPCHK(h, hipMemcpyAsync(H, h->d_hg_H, sizeof(double) * 9 * B, hipMemcpyDeviceToHost, h->stream));
-    if (R_rot) HIPCHK(h, hipMemcpyAsync(R_rot, h->d_hg_R, sizeof(double) * 9 * B, hipMemcpyDeviceToHost, h->stream));
-    if (mask) HIPCHK(h, hipMemcpyAsync(mask, h->d_hg_mask, B * h->cfg.max_matches, hipMemcpyDeviceToHost, h->stream));
-    if (counts) HIPCHK(h, hipMemcpyAsync(counts, h->d_hg_counts, sizeof(int) * 3 * B, hipMemcpyDeviceToHost, h->stream));
-    if (info) HIPCHK(h, hipMemcpyAsync(info, h->d_hg_info, sizeof(int) * 4 * B, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return RPE_OK;
+    return fetch(h, {{H, h->d_hg_H, sizeof(double) * 9 * B}, {R_rot, h->d_hg_R, sizeof(double) * 9 * B}, {mask, h->d_hg_mask, B * h->cfg.max_matches},
+                     {counts, h->d_hg_counts, sizeof(int) * 3 * B}, {info, h->d_hg_info, sizeof(int) * 4 * B}});
 }
 
 extern "C" int rpe_pair_homographies(rpe_handle *h, int B, int iters, double threshold_px, double *H, double *R_rot,
                                      uint8_t *mask, int32_t *counts, int32_t *info)
 {
-    if (!h || B < 1 || B > h->cfg.max_batch) return RPE_ERR_INVALID;
+    if (!h || B < 1 || B > h->cfg.max_batch) return rpe_invalid(h, "rpe_pair_homographies");
     int rc = homography_check(h, "rpe_pair_homographies", iters, threshold_px);
     if (rc) return rc;
     // d_n1 / d_n2, d_rstate and d_status must still hold the run's (a stage call or a put overwrote them)
-    rc = last_run_check(h, "rpe_pair_homographies", B, "rpe_pair_homographies: the last host batch ran in chunks: per-match results are kept for unchunked and device-resident batches only", true);
+    rc = last_run_gate(h, "rpe_pair_homographies", B, NEED_UNCHUNKED | NEED_PER_MATCH | NEED_COUNT | NEED_TABLE);
     if (rc) return rc;
-    if (h->last.kind == RpeLastRun::LIST && h->last.tab.size() < (size_t)2 * B) { h->err = "rpe_pair_homographies: the frame store was resized since the pair list"; return RPE_ERR_INVALID; }
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if ((rc = homography_alloc(h)) != RPE_OK) return rc;
     return homography_run(h, last_run_first(h, B), iters, threshold_px, true, H, R_rot, mask, counts, info);
@@ -1234,13 +1248,12 @@ extern "C" int rpe_frames_capacity(const rpe_handle *h) { return h ? h->fs.cap :
 
 extern "C" int rpe_frames_reserve(rpe_handle *h, int n_slots)
 {
-    if (!h) return RPE_ERR_INVALID;
+    if (!h) return rpe_invalid(h, "rpe_frames_reserve");
     if (n_slots < 0 || n_slots > (1 << 24)) { h->err = "rpe_frames_reserve: n_slots must be 0 ... 16777216"; return RPE_ERR_INVALID; }
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (n_slots == h->fs.cap) return RPE_OK;
     HIPCHK(h, hipStreamSynchronize(h->stream));            // nothing in flight reads the store that is about to go
-    h->last.tab.clear();                                   // slot numbers of the last pair list: rpe_fetch_overflow refuses from here on
-    if (h->last.run.cam.tab) last_run_end(h);              // a camera pair list reads the store's camera records: its per-match results end here
+    last_run_store_changed(h, true);
     if (n_slots == 0) { frames_free(h->fs); return RPE_OK; }
     const size_t kcap = (size_t)h->lay.kcap, db = (size_t)h->desc_bytes, N = (size_t)n_slots;
     const bool l2 = frames_keep_norms(h);
@@ -1366,9 +1379,7 @@ extern "C" int rpe_frames_info(rpe_handle *h, int n, const int32_t *slots, int32
     const size_t span = (size_t)(hi - lo + 1);                 // the range the call names, not the whole store
     std::vector<int> cnt(span);
     std::vector<unsigned> ov(span);
-    HIPCHK(h, hipMemcpyAsync(cnt.data(), h->fs.d_count + lo, sizeof(int) * span, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(ov.data(), h->fs.d_ovf + lo, sizeof(unsigned) * span, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if (int rc = fetch(h, {{cnt.data(), h->fs.d_count + lo, sizeof(int) * span}, {ov.data(), h->fs.d_ovf + lo, sizeof(unsigned) * span}})) return rc;
     for (int i = 0; i < n; ++i) {
         const size_t s = (size_t)slots[i];
         const bool f = h->fs.filled[s] != 0;
@@ -1395,9 +1406,7 @@ static int enqueue_pairs_run(rpe_handle *h, const int32_t *slot1, const int32_t 
     if (K && (rc = set_K(h, K)) != RPE_OK) return rc;
     if ((rc = upload_table(h, slot1, slot2, P)) != RPE_OK) return rc;
     const RpeRun r = rpe_run_list(h, P, K ? RpeCamSrc{nullptr, nullptr, 0} : RpeCamSrc{h->fs.d_cam, (const int2 *)h->d_pairtab, 0});
-    RpeLastRun &l = last_run_begin(h, RpeLastRun::LIST, r);
-    l.tab.resize((size_t)2 * P);
-    for (int p = 0; p < P; ++p) { l.tab[2 * p] = slot1[p]; l.tab[2 * p + 1] = slot2[p]; }
+    last_run_begin(h, RpeLastRun::LIST, r, slot1, slot2);
     MARK(h, RPE_STAGE_MATCH);
     if ((rc = run_tail(h, r)) != RPE_OK) last_run_end(h);
     return rc;
@@ -1421,7 +1430,7 @@ extern "C" int rpe_estimate_pairs(rpe_handle *h, const int32_t *slot1, const int
 extern "C" int rpe_orb_detect_and_compute(rpe_handle *h, const uint8_t *h_imgs, int n_images,
                                           rpe_keypoint *kps, uint8_t *desc, int32_t *counts)
 {
-    if (!h || !h_imgs || n_images < 1) return RPE_ERR_INVALID;
+    if (!h || !h_imgs || n_images < 1) return rpe_invalid(h, "rpe_orb_detect_and_compute");
     if (h->cfg.feature_method != RPE_FEATURE_ORB) { h->err = "handle was not created for ORB"; return RPE_ERR_INVALID; }
     if (n_images > h->n_img_cap) { h->err = "n_images exceeds 2*max_batch"; return RPE_ERR_CAPACITY; }
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -1435,13 +1444,9 @@ extern "C" int rpe_orb_detect_and_compute(rpe_handle *h, const uint8_t *h_imgs, 
     std::vector<float> resp((size_t)n_images * kcap), ang((size_t)n_images * kcap);
     std::vector<float2> pt((size_t)n_images * kcap);
     std::vector<int> cnt(n_images);
-    HIPCHK(h, hipMemcpyAsync(xy.data(), h->d_kp_xy, xy.size() * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(resp.data(), h->d_kp_resp, resp.size() * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(ang.data(), h->d_kp_angle, ang.size() * 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(pt.data(), h->d_kp_pt, pt.size() * 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipMemcpyAsync(cnt.data(), h->d_kp_count, cnt.size() * 4, hipMemcpyDeviceToHost, h->stream));
-    if (desc) HIPCHK(h, hipMemcpyAsync(desc, h->d_desc, (size_t)n_images * kcap * 32, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    rc = fetch(h, {{xy.data(), h->d_kp_xy, xy.size() * 4}, {resp.data(), h->d_kp_resp, resp.size() * 4}, {ang.data(), h->d_kp_angle, ang.size() * 4},
+                   {pt.data(), h->d_kp_pt, pt.size() * 8}, {cnt.data(), h->d_kp_count, cnt.size() * 4}, {desc, h->d_desc, (size_t)n_images * kcap * 32}});
+    if (rc) return rc;
     for (int i = 0; i < n_images; ++i) {
         if (counts) counts[i] = cnt[i];
         if (!kps) continue;
@@ -1465,7 +1470,7 @@ extern "C" int64_t rpe_orb_pyramid_pixels(const rpe_handle *h)
 
 extern "C" int rpe_orb_debug_fetch(rpe_handle *h, int index, int which, uint8_t *h_out)
 {
-    if (!h || !h_out || index < 0 || index >= h->n_img_cap) return RPE_ERR_INVALID;
+    if (!h || !h_out || index < 0 || index >= h->n_img_cap) return rpe_invalid(h, "rpe_orb_debug_fetch");
     if (h->cfg.feature_method != RPE_FEATURE_ORB) { h->err = "rpe_orb_debug_fetch: handle was not created for ORB"; return RPE_ERR_INVALID; }
     if (which != 0 && which != 2 && which != 3) { h->err = "rpe_orb_debug_fetch: which must be 0 (pyramid), 2 (NMS map) or 3 (blurred pyramid)"; return RPE_ERR_INVALID; }
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -1522,25 +1527,20 @@ static int stage_match_run(rpe_handle *h, bool l2, const int32_t *n1, const int3
     if (l2) rpe_launch_match_l2(h, rpe_run_batch(h, B));
     else rpe_launch_match(h, rpe_run_batch(h, B));
     HIPCHK(h, hipGetLastError());
-    if (qidx) HIPCHK(h, hipMemcpyAsync(qidx, h->d_m_q, sizeof(int) * mm * B, hipMemcpyDeviceToHost, h->stream));
-    if (tidx) HIPCHK(h, hipMemcpyAsync(tidx, h->d_m_t, sizeof(int) * mm * B, hipMemcpyDeviceToHost, h->stream));
-    if (dist) HIPCHK(h, hipMemcpyAsync(dist, h->d_m_d, sizeof(int) * mm * B, hipMemcpyDeviceToHost, h->stream));
-    if (n_matches) HIPCHK(h, hipMemcpyAsync(n_matches, h->d_m_n, sizeof(int) * B, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
-    return RPE_OK;
+    return fetch(h, {{qidx, h->d_m_q, sizeof(int) * mm * B}, {tidx, h->d_m_t, sizeof(int) * mm * B}, {dist, h->d_m_d, sizeof(int) * mm * B},
+                     {n_matches, h->d_m_n, sizeof(int) * B}});
 }
 
 extern "C" int rpe_match_hamming(rpe_handle *h, const uint8_t *h_desc1, const int32_t *n1, const uint8_t *h_desc2,
                                  const int32_t *n2, int B, int32_t *qidx, int32_t *tidx, int32_t *dist, int32_t *n_matches)
 {
-    if (!h || !h_desc1 || !h_desc2 || !n1 || !n2 || B < 1) return RPE_ERR_INVALID;
-    if (B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return RPE_ERR_CAPACITY; }
+    if (!h || !h_desc1 || !h_desc2 || !n1 || !n2 || B < 1) return rpe_invalid(h, "rpe_match_hamming");
+    if (int rc = check_batch(h, B)) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     last_run_end(h);                            // overwrites buffers rpe_fetch_structure reads
     const size_t per = (size_t)h->lay.kcap * 32;
-    for (int i = 0; i < B; ++i) if (n1[i] < 0 || n2[i] < 0 || n1[i] > h->lay.kcap || n2[i] > h->lay.kcap) {
-        h->err = "descriptor count exceeds keypoint capacity"; return RPE_ERR_INVALID;
-    }
+    if (int rc = check_desc_counts(h, n1, B)) return rc;
+    if (int rc = check_desc_counts(h, n2, B)) return rc;
     HIPCHK(h, hipMemcpyAsync(h->d_desc, h_desc1, per * B, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->d_desc + per * B, h_desc2, per * B, hipMemcpyHostToDevice, h->stream));
     return stage_match_run(h, false, n1, n2, B, qidx, tidx, dist, n_matches);
@@ -1549,7 +1549,7 @@ extern "C" int rpe_match_hamming(rpe_handle *h, const uint8_t *h_desc1, const in
 static int upload_points(rpe_handle *h, const float *p1, const float *p2, const int32_t *m, int B)
 {
     const size_t mm = h->cfg.max_matches;
-    for (int i = 0; i < B; ++i) if (m[i] < 0 || m[i] > (int)mm) { h->err = "match count exceeds max_matches"; return RPE_ERR_INVALID; }
+    if (int rc = check_match_counts(h, m, B)) return rc;
     HIPCHK(h, hipMemcpyAsync(h->d_pts1, p1, sizeof(float2) * mm * B, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->d_pts2, p2, sizeof(float2) * mm * B, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->d_m_n, m, sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
@@ -1597,7 +1597,7 @@ extern "C" int rpe_frames_set_cameras(rpe_handle *h, int n, const int32_t *slots
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipStreamSynchronize(h->stream));      // a pair list in flight may read the records about to change
-    if (h->last.run.cam.tab) last_run_end(h);
+    last_run_store_changed(h, false);
     for (int i = 0; i < n; ++i) {
         const size_t s = (size_t)slots[i];
         h->fs.h_cam[s] = cams[i];
@@ -1626,7 +1626,7 @@ extern "C" int rpe_enqueue_batch_cameras_device(rpe_handle *h, const uint8_t *d_
                                                 const rpe_camera *cam1, const rpe_camera *cam2)
 {
     if (!h || !d_imgs1 || !d_imgs2 || !cam1 || !cam2 || B < 1) { if (h) h->err = "rpe_enqueue_batch_cameras_device: null argument or B < 1"; return RPE_ERR_INVALID; }
-    if (B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return RPE_ERR_CAPACITY; }
+    if (int rc = check_batch(h, B)) return rc;
     int rc = check_cameras(h, cam1, B, "rpe_enqueue_batch_cameras_device");
     if (!rc) rc = check_cameras(h, cam2, B, "rpe_enqueue_batch_cameras_device");
     if (rc) return rc;
@@ -1650,7 +1650,7 @@ extern "C" int rpe_estimate_batch_cameras(rpe_handle *h, const uint8_t *h_imgs1,
                                           int32_t *inliers, int32_t *n_matches, int32_t *status)
 {
     if (!h || !h_imgs1 || !h_imgs2 || !cam1 || !cam2 || B < 1) { if (h) h->err = "rpe_estimate_batch_cameras: null argument or B < 1"; return RPE_ERR_INVALID; }
-    if (B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return RPE_ERR_CAPACITY; }
+    if (int rc = check_batch(h, B)) return rc;
     const size_t img = (size_t)h->cfg.width * h->cfg.height;
     if (batch_is_chunked(h, B)) {
         h->err = "rpe_estimate_batch_cameras: host batches this large (B >= 512 and >= 64 MiB per image set) are not chunked by the camera form: upload the images and call rpe_estimate_batch_cameras_device";
@@ -1695,7 +1695,7 @@ extern "C" int rpe_undistort_points(rpe_handle *h, const float *h_pts, int n, co
 static int stage_begin(rpe_handle *h, const char *who, const float *p1, const float *p2, const int32_t *m, int B,
                        const double *K, const rpe_camera *cam1, const rpe_camera *cam2, RpeRun &run)
 {
-    if (B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return RPE_ERR_CAPACITY; }
+    if (int rc = check_batch(h, B)) return rc;
     int rc = RPE_OK;
     if (!K && (rc = check_cameras(h, cam1, B, who)) == RPE_OK) rc = check_cameras(h, cam2, B, who);
     if (rc) return rc;
@@ -1719,9 +1719,7 @@ static int stage_find_essential(rpe_handle *h, const char *who, const float *h_p
     rpe_launch_ransac(h, run, true);
     HIPCHK(h, hipGetLastError());
     std::vector<RpeRansacState> st(B);
-    HIPCHK(h, hipMemcpyAsync(st.data(), h->d_rstate, sizeof(RpeRansacState) * B, hipMemcpyDeviceToHost, h->stream));
-    if (mask) HIPCHK(h, hipMemcpyAsync(mask, h->d_mask, (size_t)h->cfg.max_matches * B, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(h, hipStreamSynchronize(h->stream));
+    if ((rc = fetch(h, {{st.data(), h->d_rstate, sizeof(RpeRansacState) * B}, {mask, h->d_mask, (size_t)h->cfg.max_matches * B}})) != RPE_OK) return rc;
     for (int i = 0; i < B; ++i) {
         if (E) memcpy(E + 9 * i, st[i].E, sizeof(double) * 9);
         if (found) found[i] = st[i].found;
@@ -1762,7 +1760,7 @@ static int stage_refine(rpe_handle *h, const char *who, const double *h_R0, cons
 extern "C" int rpe_find_essential(rpe_handle *h, const float *h_pts1, const float *h_pts2, const int32_t *m, int B,
                                   const double K[9], double *E, uint8_t *mask, int32_t *found, int32_t *info)
 {
-    if (!h || !h_pts1 || !h_pts2 || !m || !K || B < 1) return RPE_ERR_INVALID;
+    if (!h || !h_pts1 || !h_pts2 || !m || !K || B < 1) return rpe_invalid(h, "rpe_find_essential");
     return stage_find_essential(h, "rpe_find_essential", h_pts1, h_pts2, m, B, K, nullptr, nullptr, E, mask, found, info);
 }
 
@@ -1770,7 +1768,7 @@ extern "C" int rpe_find_essential_cameras(rpe_handle *h, const float *h_pts1, co
                                           const rpe_camera *cam1, const rpe_camera *cam2, double *E, uint8_t *mask,
                                           int32_t *found, int32_t *info)
 {
-    if (!h || !h_pts1 || !h_pts2 || !m || !cam1 || !cam2 || B < 1) return RPE_ERR_INVALID;
+    if (!h || !h_pts1 || !h_pts2 || !m || !cam1 || !cam2 || B < 1) return rpe_invalid(h, "rpe_find_essential_cameras");
     return stage_find_essential(h, "rpe_find_essential_cameras", h_pts1, h_pts2, m, B, nullptr, cam1, cam2, E, mask, found, info);
 }
 
@@ -1778,11 +1776,11 @@ extern "C" int rpe_find_homography(rpe_handle *h, const float *h_pts1, const flo
                                    const double K[9], int iters, double threshold_px, double *H, double *R_rot, uint8_t *mask,
                                    int32_t *counts, int32_t *info)
 {
-    if (!h || !h_pts1 || !h_pts2 || !m || !K || B < 1) return RPE_ERR_INVALID;
-    if (B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return RPE_ERR_CAPACITY; }
+    if (!h || !h_pts1 || !h_pts2 || !m || !K || B < 1) return rpe_invalid(h, "rpe_find_homography");
+    if (int rc = check_batch(h, B)) return rc;
     int rc = homography_check(h, "rpe_find_homography", iters, threshold_px);
     if (rc) return rc;
-    for (int i = 0; i < B; ++i) if (m[i] < 0 || m[i] > h->cfg.max_matches) { h->err = "match count exceeds max_matches"; return RPE_ERR_INVALID; }
+    if ((rc = check_match_counts(h, m, B)) != RPE_OK) return rc;
     RpeRun run;
     if ((rc = stage_begin(h, "rpe_find_homography", h_pts1, h_pts2, m, B, K, nullptr, nullptr, run)) != RPE_OK) return rc;
     if ((rc = homography_alloc(h)) != RPE_OK) return rc;
@@ -1793,7 +1791,7 @@ extern "C" int rpe_find_homography(rpe_handle *h, const float *h_pts1, const flo
 extern "C" int rpe_recover_pose(rpe_handle *h, const double *h_E, const float *h_pts1, const float *h_pts2, const int32_t *m,
                                 int B, const double K[9], double *R, double *t, int32_t *inliers)
 {
-    if (!h || !h_E || !h_pts1 || !h_pts2 || !m || !K || B < 1) return RPE_ERR_INVALID;
+    if (!h || !h_E || !h_pts1 || !h_pts2 || !m || !K || B < 1) return rpe_invalid(h, "rpe_recover_pose");
     return stage_recover_pose(h, "rpe_recover_pose", h_E, h_pts1, h_pts2, m, B, K, nullptr, nullptr, R, t, inliers);
 }
 
@@ -1801,7 +1799,7 @@ extern "C" int rpe_recover_pose_cameras(rpe_handle *h, const double *h_E, const 
                                         const int32_t *m, int B, const rpe_camera *cam1, const rpe_camera *cam2,
                                         double *R, double *t, int32_t *inliers)
 {
-    if (!h || !h_E || !h_pts1 || !h_pts2 || !m || !cam1 || !cam2 || B < 1) return RPE_ERR_INVALID;
+    if (!h || !h_E || !h_pts1 || !h_pts2 || !m || !cam1 || !cam2 || B < 1) return rpe_invalid(h, "rpe_recover_pose_cameras");
     return stage_recover_pose(h, "rpe_recover_pose_cameras", h_E, h_pts1, h_pts2, m, B, nullptr, cam1, cam2, R, t, inliers);
 }
 
@@ -1809,8 +1807,8 @@ extern "C" int rpe_refine_pose_points(rpe_handle *h, const double *h_R0, const d
                                       const float *h_pts2, const uint8_t *h_mask, const int32_t *m, int B, const double K[9],
                                       int max_iters, double *R, double *t, int32_t *inliers, int32_t *info, double *rms)
 {
-    if (!h || !h_R0 || !h_t0 || !h_pts1 || !h_pts2 || !h_mask || !m || !K || B < 1) return RPE_ERR_INVALID;
-    if (B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return RPE_ERR_CAPACITY; }      // in front of max_iters, as ever
+    if (!h || !h_R0 || !h_t0 || !h_pts1 || !h_pts2 || !h_mask || !m || !K || B < 1) return rpe_invalid(h, "rpe_refine_pose_points");
+    if (int rc = check_batch(h, B)) return rc;      // in front of max_iters, as ever
     if (max_iters < 1 || max_iters > 100) { h->err = "rpe_refine_pose_points: max_iters must be 1 ... 100"; return RPE_ERR_INVALID; }
     return stage_refine(h, "rpe_refine_pose_points", h_R0, h_t0, h_pts1, h_pts2, h_mask, m, B, K, nullptr, nullptr, max_iters, R, t, inliers, info, rms);
 }
@@ -1820,7 +1818,7 @@ extern "C" int rpe_refine_pose_points_cameras(rpe_handle *h, const double *h_R0,
                                               const rpe_camera *cam1, const rpe_camera *cam2, int max_iters, double *R, double *t,
                                               int32_t *inliers, int32_t *info, double *rms)
 {
-    if (!h || !h_R0 || !h_t0 || !h_pts1 || !h_pts2 || !h_mask || !m || !cam1 || !cam2 || B < 1) return RPE_ERR_INVALID;
+    if (!h || !h_R0 || !h_t0 || !h_pts1 || !h_pts2 || !h_mask || !m || !cam1 || !cam2 || B < 1) return rpe_invalid(h, "rpe_refine_pose_points_cameras");
     if (max_iters < 1 || max_iters > 100) { h->err = "rpe_refine_pose_points_cameras: max_iters must be 1 ... 100"; return RPE_ERR_INVALID; }
     return stage_refine(h, "rpe_refine_pose_points_cameras", h_R0, h_t0, h_pts1, h_pts2, h_mask, m, B, nullptr, cam1, cam2, max_iters, R, t, inliers, info, rms);
 }
@@ -1831,13 +1829,13 @@ static const char *kStageNames[RPE_STAGE_COUNT] = {"pyramid", "fast", "nms", "se
 extern "C" const char *rpe_stage_name(int s) { return (s >= 0 && s < RPE_STAGE_COUNT) ? kStageNames[s] : "?"; }
 extern "C" int rpe_set_profiling(rpe_handle *h, int enable)
 {
-    if (!h) return RPE_ERR_INVALID;
+    if (!h) return rpe_invalid(h, "rpe_set_profiling");
     h->profiling = enable != 0; h->ev_valid = false;
     return RPE_OK;
 }
 extern "C" int rpe_get_stage_ms(rpe_handle *h, float *ms)
 {
-    if (!h || !ms) return RPE_ERR_INVALID;
+    if (!h || !ms) return rpe_invalid(h, "rpe_get_stage_ms");
     if (!h->ev_valid) { h->err = "no profiled batch recorded"; return RPE_ERR_INVALID; }
     HIPCHK(h, hipEventSynchronize(h->ev[RPE_STAGE_COUNT]));
     for (int i = 0; i < RPE_STAGE_COUNT; ++i) {
@@ -1847,155 +1845,11 @@ extern "C" int rpe_get_stage_ms(rpe_handle *h, float *ms)
     return RPE_OK;
 }
 
-// ------------------------------------------------------------ roofline calibration
-// The hot path is bound by vector-instruction ISSUE, not by HBM, so bench.py prices the
-// dominant kernel and the matcher against a MEASURED issue rate: each kernel below runs a long stream of one
-// instruction kind (inline asm: the count is exact, nothing is folded away) over independent register chains,
-// at 1, 2, 4 or 8 resident waves per SIMD on every CU.  MI355X_MICROARCH.md: a wave64 VALU instruction takes
-// 2 cycles on the 32-wide SIMD when >= 2 waves feed it, 4 cycles for one wave alone; f64 and transcendental
-// instructions take longer.  Kinds: the instructions the ORB / matcher / RANSAC inner loops are made of.
-#define CALIB_UNROLL 16
-template <int KIND>
-__global__ __launch_bounds__(256) void valu_calib_kernel(unsigned *sink, int iters)
-{
-    unsigned a[8];
-    double d[8];
-    float f[8];
-    typedef float f2_t __attribute__((ext_vector_type(2)));
-    f2_t f2[8];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        a[u] = threadIdx.x * 2654435761u + u * 40503u + blockIdx.x; d[u] = 1.0 + 1e-9 * (double)(a[u] & 1023u);
-        f[u] = 1.0f + 1e-6f * (float)(a[u] & 1023u); f2[u].x = f[u]; f2[u].y = f[u] * 0.5f;
-    }
-    const float fk = 1.0000001f;
-    const f2_t fk2 = {1.0000001f, 0.9999999f};
-    const unsigned k0 = 0x9E3779B9u ^ threadIdx.x, k1 = 0x01010101u;
-    const double dk = 1.0000000001;
-    for (int it = 0; it < iters; ++it) {
-#pragma unroll
-        for (int r = 0; r < CALIB_UNROLL / 8; ++r) {
-#pragma unroll
-            for (int u = 0; u < 8; ++u) {
-                if (KIND == 0)       // the Hamming inner loop: v_xor_b32 + v_bcnt_u32_b32 (2 instructions)
-                    asm volatile("v_xor_b32 %0, %0, %1\n\tv_bcnt_u32_b32 %0, %0, %2" : "+v"(a[u]) : "v"(k0), "v"(k1));
-                else if (KIND == 1)  // FAST pair test: packed 16-bit min / max (2 instructions)
-                    asm volatile("v_pk_min_i16 %0, %0, %1\n\tv_pk_max_i16 %0, %0, %2" : "+v"(a[u]) : "v"(k0), "v"(k1));
-                else if (KIND == 2)  // byte gather: v_perm_b32 (1 instruction)
-                    asm volatile("v_perm_b32 %0, %0, %1, %2" : "+v"(a[u]) : "v"(k0), "v"(k1));
-                else if (KIND == 3)  // packed-u8 dot product: v_dot4_u32_u8 (1 instruction)
-                    asm volatile("v_dot4_u32_u8 %0, %1, %2, %0" : "+v"(a[u]) : "v"(k0), "v"(k1));
-                else if (KIND == 4)  // FAST ring score: v_min3_i32 + v_max3_i32 (2 instructions)
-                    asm volatile("v_min3_i32 %0, %0, %1, %2\n\tv_max3_i32 %0, %0, %1, %2" : "+v"(a[u]) : "v"(k0), "v"(k1));
-                else if (KIND == 5)  // resize / blur taps: v_mad_u32_u24 (1 instruction)
-                    asm volatile("v_mad_u32_u24 %0, %0, %1, %2" : "+v"(a[u]) : "v"(k1), "v"(k0));
-                else if (KIND == 6)  // RANSAC / pose: v_mul_f64 + v_add_f64 (2 instructions; the library compiles without contraction)
-                    asm volatile("v_mul_f64 %0, %0, %1\n\tv_add_f64 %0, %0, %1" : "+v"(d[u]) : "v"(dk));
-                else if (KIND == 7)  // v_fma_f64 (1 instruction), for reference
-                    asm volatile("v_fma_f64 %0, %0, %1, %1" : "+v"(d[u]) : "v"(dk));
-                else if (KIND == 8)  // v_fma_f32 (1 instruction): the guide's 2-cycle instruction
-                    asm volatile("v_fma_f32 %0, %0, %1, %1" : "+v"(f[u]) : "v"(fk));
-                else if (KIND == 9)  // v_pk_fma_f32 (1 instruction, 2 FMAs per lane): the 157 TFLOP/s f32 vector peak
-                    asm volatile("v_pk_fma_f32 %0, %0, %1, %1" : "+v"(f2[u]) : "v"(fk2));
-                else if (KIND == 10) // pyramid / descriptor taps: v_dot2_u32_u16
-                    asm volatile("v_dot2_u32_u16 %0, %1, %2, %0" : "+v"(a[u]) : "v"(k0), "v"(k1));
-                else if (KIND == 11) // byte phase: v_alignbyte_b32
-                    asm volatile("v_alignbyte_b32 %0, %0, %1, %2" : "+v"(a[u]) : "v"(k0), "v"(k1));
-                else if (KIND == 12) // 32-bit multiply: v_mul_lo_u32
-                    asm volatile("v_mul_lo_u32 %0, %0, %1" : "+v"(a[u]) : "v"(k0));
-                else if (KIND == 13) // 64-bit multiply-add (what 32-bit index arithmetic often compiles to): v_mad_u64_u32
-                    asm volatile("v_mad_u64_u32 %0, vcc, %1, %2, %0" : "+v"(d[u]) : "v"(k0), "v"(k1) : "vcc");
-                else if (KIND == 14) // SDWA operand select: v_mul_u32_u24_sdwa
-                    asm volatile("v_mul_u32_u24_sdwa %0, %0, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1" : "+v"(a[u]) : "v"(k0));
-                else                 // packed 16-bit multiply-add: v_pk_mad_u16
-                    asm volatile("v_pk_mad_u16 %0, %0, %1, %2" : "+v"(a[u]) : "v"(k0), "v"(k1));
-            }
-        }
-    }
-    unsigned acc = 0;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) acc ^= a[u] ^ (unsigned)__double_as_longlong(d[u]) ^ __float_as_uint(f[u]) ^ __float_as_uint(f2[u].x) ^ __float_as_uint(f2[u].y);
-    if (acc == 0x12345679u) *sink = acc;
-}
-
-static const int kCalibInstPerSlot[16] = {2, 2, 1, 1, 2, 1, 2, 1, 1, 1, 1, 1, 1, 1, 1, 1};
-static const char *kCalibNames[16] = {"v_xor_b32+v_bcnt_u32_b32", "v_pk_min_i16+v_pk_max_i16", "v_perm_b32", "v_dot4_u32_u8",
-                                      "v_min3_i32+v_max3_i32", "v_mad_u32_u24", "v_mul_f64+v_add_f64", "v_fma_f64", "v_fma_f32", "v_pk_fma_f32",
-                                      "v_dot2_u32_u16", "v_alignbyte_b32", "v_mul_lo_u32", "v_mad_u64_u32", "v_mul_u32_u24_sdwa", "v_pk_mad_u16"};
-extern "C" const char *rpe_calibrate_valu_name(int kind) { return (kind >= 0 && kind < 16) ? kCalibNames[kind] : "?"; }
-
-extern "C" int rpe_calibrate_valu(rpe_handle *h, int kind, int waves_per_simd, double *wave_insts_per_s)
-{
-    if (!h || !wave_insts_per_s || kind < 0 || kind > 15 || waves_per_simd < 1 || waves_per_simd > 8) return RPE_ERR_INVALID;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    hipDeviceProp_t prop;
-    HIPCHK(h, hipGetDeviceProperties(&prop, h->cfg.device));
-    DM_ONCE(h, h->d_calib_sink, 1);
-    const int ncu = prop.multiProcessorCount;
-    // one 256-thread block = 4 waves = one wave per SIMD of a CU; waves_per_simd blocks per CU
-    const int blocks = ncu * waves_per_simd, iters = 20000;
-    hipEvent_t e0, e1;
-    HIPCHK(h, hipEventCreate(&e0)); HIPCHK(h, hipEventCreate(&e1));
-    float best = 1e30f;
-    for (int rep = 0; rep < 4; ++rep) {                    // first repetition warms up
-        HIPCHK(h, hipEventRecord(e0, h->stream));
-        switch (kind) {
-#define CALIB_CASE(K) case K: hipLaunchKernelGGL((valu_calib_kernel<K>), dim3(blocks), dim3(256), 0, h->stream, h->d_calib_sink, iters); break;
-            CALIB_CASE(0) CALIB_CASE(1) CALIB_CASE(2) CALIB_CASE(3) CALIB_CASE(4) CALIB_CASE(5) CALIB_CASE(6) CALIB_CASE(7)
-            CALIB_CASE(8) CALIB_CASE(9) CALIB_CASE(10) CALIB_CASE(11) CALIB_CASE(12) CALIB_CASE(13) CALIB_CASE(14) CALIB_CASE(15)
-#undef CALIB_CASE
-        }
-        HIPCHK(h, hipEventRecord(e1, h->stream));
-        HIPCHK(h, hipEventSynchronize(e1));
-        float ms = 0.f;
-        HIPCHK(h, hipEventElapsedTime(&ms, e0, e1));
-        if (rep > 0 && ms < best) best = ms;
-    }
-    hipEventDestroy(e0); hipEventDestroy(e1);
-    const double insts = (double)blocks * 4.0 * (double)iters * CALIB_UNROLL * kCalibInstPerSlot[kind];
-    *wave_insts_per_s = insts / ((double)best * 1e-3);
-    return RPE_OK;
-}
-
-// HBM streaming rate of this device: 16-B-per-lane read of the handle's pyramid buffer (>= 256 MiB so the
-// Infinity Cache cannot serve it) -- the "achievable" figure next to the 8 TB/s spec peak in the bench line.
-__global__ __launch_bounds__(256) void calib_read16_kernel(const uint4 *__restrict__ p, size_t n, unsigned *sink)
-{
-    unsigned acc = 0;
-    for (size_t i = (size_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (size_t)gridDim.x * 256) { uint4 v = p[i]; acc ^= v.x ^ v.y ^ v.z ^ v.w; }
-    if (acc == 0x12345679u) *sink = acc;
-}
-extern "C" int rpe_calibrate_hbm(rpe_handle *h, double *bytes_per_s)
-{
-    if (!h || !bytes_per_s) return RPE_ERR_INVALID;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    const size_t NIo = h->cfg.feature_method == RPE_FEATURE_SIFT ? 1 : (size_t)h->n_img_cap;
-    const size_t bytes = NIo * (size_t)h->lay.stride;
-    if (bytes < ((size_t)256 << 20)) { h->err = "rpe_calibrate_hbm: the handle's pyramid buffer is smaller than the 256 MiB Infinity Cache"; return RPE_ERR_INVALID; }
-    DM_ONCE(h, h->d_calib_sink, 1);
-    hipEvent_t e0, e1;
-    HIPCHK(h, hipEventCreate(&e0)); HIPCHK(h, hipEventCreate(&e1));
-    float best = 1e30f;
-    for (int rep = 0; rep < 4; ++rep) {
-        HIPCHK(h, hipEventRecord(e0, h->stream));
-        hipLaunchKernelGGL(calib_read16_kernel, dim3(8192), dim3(256), 0, h->stream, (const uint4 *)h->d_pyr, bytes / 16, h->d_calib_sink);
-        HIPCHK(h, hipEventRecord(e1, h->stream));
-        HIPCHK(h, hipEventSynchronize(e1));
-        float ms = 0.f;
-        HIPCHK(h, hipEventElapsedTime(&ms, e0, e1));
-        if (rep > 0 && ms < best) best = ms;
-    }
-    hipEventDestroy(e0); hipEventDestroy(e1);
-    *bytes_per_s = (double)bytes / ((double)best * 1e-3);
-    return RPE_OK;
-}
-
-
 // ------------------------------------------------------------------ SIFT stage API
 extern "C" int rpe_sift_detect_and_compute(rpe_handle *h, const uint8_t *h_imgs, int n_images,
                                            rpe_sift_keypoint *kps, float *desc, int32_t *counts)
 {
-    if (!h || !h_imgs || n_images < 1) return RPE_ERR_INVALID;
+    if (!h || !h_imgs || n_images < 1) return rpe_invalid(h, "rpe_sift_detect_and_compute");
     if (h->cfg.feature_method != RPE_FEATURE_SIFT) { h->err = "handle was not created for SIFT"; return RPE_ERR_INVALID; }
     if (n_images > h->n_img_cap) { h->err = "n_images exceeds 2*max_batch"; return RPE_ERR_CAPACITY; }
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -2037,9 +1891,9 @@ extern "C" int64_t rpe_sift_debug_gauss(rpe_handle *h, int index, float *out)
 extern "C" int rpe_match_l2(rpe_handle *h, const float *h_desc1, const int32_t *n1, const float *h_desc2, const int32_t *n2, int B,
                             int32_t *qidx, int32_t *tidx, float *dist, int32_t *n_matches)
 {
-    if (!h || !h_desc1 || !h_desc2 || !n1 || !n2 || B < 1) return RPE_ERR_INVALID;
+    if (!h || !h_desc1 || !h_desc2 || !n1 || !n2 || B < 1) return rpe_invalid(h, "rpe_match_l2");
     if (h->cfg.norm_type != RPE_NORM_L2) { h->err = "handle was not created for NORM_L2"; return RPE_ERR_INVALID; }
-    if (B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return RPE_ERR_CAPACITY; }
+    if (int rc = check_batch(h, B)) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     last_run_end(h);                            // overwrites buffers rpe_fetch_structure reads
     const size_t dim = (size_t)h->desc_bytes;               // 128 (SIFT) or 32 (ORB descriptors under NORM_L2)
@@ -2048,7 +1902,7 @@ extern "C" int rpe_match_l2(rpe_handle *h, const float *h_desc1, const int32_t *
     for (int s = 0; s < 2; ++s) {
         const float *src = s ? h_desc2 : h_desc1; const int32_t *cn = s ? n2 : n1;
         for (int i = 0; i < B; ++i) {
-            if (cn[i] < 0 || cn[i] > h->lay.kcap) { h->err = "descriptor count exceeds keypoint capacity"; return RPE_ERR_INVALID; }
+            if (int rc = check_desc_counts(h, cn + i, 1)) return rc;
             for (size_t e = 0; e < (size_t)cn[i] * dim; ++e) {
                 float v = src[(size_t)i * per + e];
                 if (!(v >= 0.f && v <= 255.f) || v != (float)(int)v) { h->err = "NORM_L2 path expects byte-valued descriptors (SIFT's integer-valued 0..255 floats, or ORB bytes)"; return RPE_ERR_INVALID; }

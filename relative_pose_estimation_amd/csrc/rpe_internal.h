@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdio.h>
 #include <string>
 #include <vector>
 #include "../../include/rpe_amd.h"
@@ -231,9 +232,9 @@ struct RpeRun {
     RpeCamSrc cam;        // cam.cams == nullptr: the shared d_K and the kernels' CAM = false instances
 };
 
-// The last run, for the calls that come behind it: rpe_fetch_overflow, rpe_fetch_matched_points, rpe_fetch_structure and
-// rpe_refine_poses (the last two launch again, on exactly `run`).  Written by last_run_begin / last_run_end (rpe_api.hip)
-// and by nothing else.
+// The last run, for the calls that come behind it (the table at last_run_gate, rpe_api.hip, names them and what each needs;
+// those that launch again do so on exactly `run`).  Written by last_run_begin, last_run_end, last_run_store_changed and
+// last_run_structure (rpe_api.hip) and by nothing else; read through last_run_gate.
 struct RpeLastRun {
     enum Kind { NONE, RULE, LIST, CHUNKED };   // nothing / a batch or stream under the rule / a pair list / a host batch run in chunks
     Kind kind = NONE;
@@ -383,6 +384,28 @@ static int dmalloc(rpe_handle *h, T **p, size_t n)
     return RPE_OK;
 }
 #define DM(h, p, n) do { int r_ = dmalloc(h, &(p), (size_t)(n)); if (r_) return r_; } while (0)
+// a buffer created on first use
+#define DM_ONCE(h, p, n) do { if (!(p)) DM(h, p, n); } while (0)
+
+// A failed HIP call ends the entry point: the text goes to the handle, or (rpe_create, no handle yet) to the create-time string
+extern std::string g_create_err;
+#define HIPCHK(h, call)                                                                         \
+    do {                                                                                        \
+        hipError_t e_ = (call);                                                                 \
+        if (e_ != hipSuccess) {                                                                 \
+            char b_[512];                                                                       \
+            snprintf(b_, sizeof(b_), "%s failed: %s (%s:%d)", #call, hipGetErrorString(e_), __FILE__, __LINE__); \
+            if (h) (h)->err = b_; else g_create_err = b_;                                       \
+            return RPE_ERR_HIP;                                                                 \
+        }                                                                                       \
+    } while (0)
+
+// The refusal of an argument head: every failed call leaves a text of its own for rpe_last_error (h == NULL: nowhere to)
+static inline int rpe_invalid(rpe_handle *h, const char *who, const char *what = "a null argument or a count out of range")
+{
+    if (h) h->err = std::string(who) + ": " + what;
+    return RPE_ERR_INVALID;
+}
 
 // The runs.  `cam` defaults to the shared K; a camera source must address its records as the run addresses its images.
 static inline RpeRun rpe_run_rule(const rpe_handle *h, int pairs, int img2_base, RpeCamSrc cam)

@@ -10,10 +10,20 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
-def _header_symbols():
+def _header_declarations():
+    """name -> (return type, [parameter declarations]) of every function include/rpe_amd.h declares"""
     src = open(os.path.join(ROOT, "include", "rpe_amd.h")).read()
     src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    return sorted(set(re.findall(r"\b(rpe_[a-z0-9_]+)\s*\(", src)))
+    src = re.sub(r"//[^\n]*|^[ \t]*#[^\n]*", "", src, flags=re.M)
+    decls = {}
+    for ret, name, params in re.findall(r"([A-Za-z_][\w\s\*]*?)\b(rpe_[a-z0-9_]+)\s*\(([^()]*)\)\s*;", src):
+        params = [p.strip() for p in params.split(",")]
+        decls[name] = (" ".join(ret.split()), [] if params in ([""], ["void"]) else params)
+    return decls
+
+
+def _header_symbols():
+    return sorted(_header_declarations())
 
 
 def test_library_exports_every_declared_symbol():
@@ -24,6 +34,47 @@ def test_library_exports_every_declared_symbol():
     for s in syms:
         assert hasattr(lib, s), f"{s} declared in include/rpe_amd.h but not exported"
     assert sorted(_capi.EXPORTS) == syms
+
+
+def _ctypes_class(decl, is_return=False):
+    """the ctypes class a C declaration binds to: a pointer type for pointers and arrays, else the scalar's own"""
+    import ctypes as C
+    if "*" in decl or "[" in decl:
+        return C.c_char_p if is_return else "pointer"
+    words = [w for w in decl.split() if w != "const"]
+    ctype = " ".join(words if is_return else words[:-1])          # a parameter's last word is its name
+    return {"int": C.c_int, "int32_t": C.c_int, "double": C.c_double, "size_t": C.c_size_t, "int64_t": C.c_int64, "void": None}[ctype]
+
+
+def _binding_mismatches(signatures):
+    import ctypes as C
+    decls = _header_declarations()
+    bad = sorted(set(decls) ^ set(signatures))
+    for name in sorted(set(decls) & set(signatures)):
+        ret, params = decls[name]
+        restype, argtypes = signatures[name]
+        bound = ["pointer" if t is C.c_void_p or issubclass(t, (C._Pointer, C.Array)) else t for t in argtypes]
+        if restype is not _ctypes_class(ret, True) or bound != [_ctypes_class(p) for p in params]:
+            bad.append(name)
+    return len(decls), bad
+
+
+def test_binding_table_matches_the_header():
+    """ctypes takes any argtypes: a wrong arity, or a c_int where the header has a double, only shows as wrong numbers.
+    Every function the header declares is bound with as many parameters, of the class the declaration has (pointer or
+    array -> a pointer type, int / int32_t -> c_int, double -> c_double, size_t -> c_size_t, int64_t -> c_int64), and
+    with its return type.  Reads the table only; the library is not loaded."""
+    import ctypes as C
+    from relative_pose_estimation_amd import _capi
+    n, bad = _binding_mismatches(_capi.SIGNATURES)
+    assert n >= 76 and bad == [], bad
+    # the comparison itself: a wrong class, a wrong arity and a wrong return type are each found
+    for name, wrong in (("rpe_guided_matches", lambda r, a: (r, a[:4] + [C.c_int] + a[5:])),      # gate_px is a double
+                        ("rpe_fetch_results", lambda r, a: (r, a[:-1])),
+                        ("rpe_orb_pyramid_pixels", lambda r, a: (C.c_int, a))):
+        sig = dict(_capi.SIGNATURES)
+        sig[name] = wrong(*sig[name])
+        assert _binding_mismatches(sig)[1] == [name]
 
 
 def test_no_cpu_fallback():

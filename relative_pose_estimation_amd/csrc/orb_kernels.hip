@@ -538,21 +538,6 @@ void rpe_launch_fast(rpe_handle *h, int n_img)
                        h->d_pyr, h->d_tile_list, h->d_tile_cnt, h->lay, h->d_tiles_fast, h->n_tiles_fast);
 }
 
-// ------------------------------------------------- block-wide exclusive scan
-__device__ __forceinline__ int block_excl_scan(int v, int *s_wave /*[5]*/, int &total)
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int inc = wave_inclusive_sum(v);
-    if (lane == 63) s_wave[wv] = inc;
-    __syncthreads();
-    int base = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { int s = s_wave[k]; if (k < wv) base += s; }
-    total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-    __syncthreads();
-    return base + inc - v;
-}
-
 // ----------------------------------------------------------------- select
 // cv2's keypoint ORDER (orb.cpp computeKeyPoints): FAST emits a level's corners in raster order, then
 // KeyPointsFilter::retainBest(2 * quota) on the FAST score reorders them through std::nth_element + std::partition;

@@ -45,7 +45,6 @@ static int fetch(rpe_handle *h, std::initializer_list<Fetch> pieces)
     return RPE_OK;
 }
 
-static int cv_round(double v) { return (int)lrint(v); }
 static long long align_up(long long v, long long a) { return (v + a - 1) / a * a; }
 
 extern "C" void rpe_default_config(rpe_config *c)

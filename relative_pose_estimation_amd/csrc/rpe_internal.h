@@ -2,6 +2,7 @@
 // Host handle, HBM workspace layout and kernel-launcher prototypes.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <math.h>
 #include <stdint.h>
 #include <stdio.h>
 #include <string>
@@ -180,6 +181,9 @@ struct RpePairNormalise {
 // Inclusive prefix operations over the 64 lanes with DPP row shifts / row broadcasts: 6 v_<op>_dpp instead of 6 rounds of
 // ds_bpermute + select + op (~30 vector + LDS instructions).  Shifted-out lanes read the `old` operand, the identity.
 // The wave total is the value of lane 63 (__builtin_amdgcn_readlane(x, 63)).
+// A lane that is switched off also reads as the identity and is not written: every call site runs with all 64 lanes of
+// the wave active (the early returns in front of the SIFT ones -- band / keypoint index, empty band, redo gate -- depend
+// on the wave's index only), and a new one must too.
 #define RPE_WAVE_SCAN(NAME, OP, IDENT)                                                                            \
     __device__ __forceinline__ int NAME(int v)                                                                    \
     {                                                                                                             \
@@ -198,6 +202,21 @@ RPE_WAVE_SCAN(wave_inclusive_sum, RPE_OP_ADD, 0)
 RPE_WAVE_SCAN(wave_inclusive_max, RPE_OP_MAX, (int)0x80000000)
 RPE_WAVE_SCAN(wave_inclusive_min, RPE_OP_MIN, 0x7FFFFFFF)
 __device__ __forceinline__ int wave_sum(int v) { return __builtin_amdgcn_readlane(wave_inclusive_sum(v), 63); }
+// exclusive scan over a 256-thread workgroup (all of it takes part: two barriers inside); total = the sum of all 256.
+// s_wave: one LDS word per wave
+__device__ __forceinline__ int block_excl_scan(int v, int *s_wave /*[4]*/, int &total)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int inc = wave_inclusive_sum(v);
+    if (lane == 63) s_wave[wv] = inc;
+    __syncthreads();
+    int base = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) { int s = s_wave[k]; if (k < wv) base += s; }
+    total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
+    __syncthreads();
+    return base + inc - v;
+}
 
 struct RpeTile { short level, tx, ty, pad; };
 // destination tile of the resize kernel: its origin and the origin of its source window in the level below
@@ -399,6 +418,9 @@ extern std::string g_create_err;
             return RPE_ERR_HIP;                                                                 \
         }                                                                                       \
     } while (0)
+
+// cv2's cvRound of a double: to nearest, ties to even
+static inline int cv_round(double v) { return (int)lrint(v); }
 
 // The refusal of an argument head: every failed call leaves a text of its own for rpe_last_error (h == NULL: nowhere to)
 static inline int rpe_invalid(rpe_handle *h, const char *who, const char *what = "a null argument or a count out of range")

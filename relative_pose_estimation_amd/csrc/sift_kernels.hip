@@ -14,18 +14,22 @@
 //               (INTER_NEAREST) as level 0 of the next octave
 //   (DoG)     : never stored: layer l = G[l+1] - G[l] is formed where it is consumed (extrema scan, adjust)
 //   extrema   : tiled 26-neighbour test (rolling LDS layers with halo columns, 3x3x3 max/min from LDS reads) -> 1-bit hit
-//               mask + one counter per (octave, layer, row) band; parallel band scan; wave-per-row emit = raster-ordered seeds
+//               mask + one counter per (octave, layer, row) band; parallel band scan (block_excl_scan of rpe_internal.h);
+//               wave-per-row emit (wave_inclusive_sum) = raster-ordered seeds (SiftSeed)
 //   adjust    : one lane per seed: adjustLocalExtrema (contrast / edge tests); survivors appended by integer atomics
 //   select    : under a cap only the nfeatures * 5/4 + 256 strongest survivors (radix select on |contrast|) get an orientation;
-//               exact because retainBest's threshold lies inside them (a second round covers the case that it does not)
+//               exact because retainBest's threshold lies inside them (a second round covers the case that it does not:
+//               SiftRound per image, sift_round_skips in the five kernels of a round)
 //   orient    : one wave per selected survivor: 36-bin orientation histogram in 8 interleaved partials per bin (per-slot order
 //               kept in registers by DPP row shifts), Gaussian weights from a per-keypoint table, peaks -> raw keypoints
-//   sort      : response prefilter, bitonic sort of the raw keypoints by KeyPoint_LessThan (one workgroup / image)
+//   sort      : response prefilter (radix select), bitonic sort of the raw keypoints by KeyPoint_LessThan (one workgroup / image)
 //   finalize  : duplicate removal, retainBest(nfeatures) by radix select, ordered compaction
+//               (the three radix selects are sift_kth_largest_key: one body, the caller says which entries take part and their key)
 //   describe  : one wave per keypoint: the sample positions kept in a row of the square are an interval (one lane per row finds
 //               it), dense batches of 64 samples, 4x4x8 trilinear histogram in 8 interleaved partials, lane = (slot, corner)
 //   march     : (RPE_SIFT_MARCH=1) levels 1-3 / 4-5 of the large octaves in one pass over the source level each, rings of
 //               row-filtered rows in LDS; bit-identical to the tile kernels
+// Records between the kernels: SiftSeed (one word), the survivor (SV_*, SURV_W floats) and the keypoint (KP_*, KP_W floats).
 // Kernels whose lanes append through a returning atomic on a per-image counter (adjust, orient) put the image index on
 // the fastest grid axis, so that workgroups in flight together hit different counters.
 #include "rpe_internal.h"
@@ -63,6 +67,20 @@ struct SiftDev {                        // passed by value to kernels
     long long bmoff[12], bmstride;
 };
 
+// ---- records of the stages behind the pyramid
+// a hit of the extrema scan, and where a survivor's refinement ended: octave, layer, row, column in one word
+struct SiftSeed {
+    int o, l, r, c;
+    __device__ __forceinline__ unsigned pack() const { return ((unsigned)o << 28) | ((unsigned)l << 26) | ((unsigned)r << 13) | (unsigned)c; }
+    static __device__ __forceinline__ SiftSeed unpack(unsigned sd) { return {(int)(sd >> 28), (int)((sd >> 26) & 3), (int)((sd >> 13) & 0x1FFF), (int)(sd & 0x1FFF)}; }
+};
+enum { SV_SEED, SV_XI, SV_XR, SV_XC, SV_CONTR, SURV_W = 8 };          // floats of a survivor: SiftSeed (bits), offsets, contrast; 8 per record
+enum { KP_X, KP_Y, KP_SIZE, KP_ANGLE, KP_RESP, KP_OCT, KP_W };         // floats of a raw / final keypoint (KP_OCT: cv2's packed octave, bits)
+// per image, the state of the two rounds of select .. finalize: round 0 orients the n_sel strongest survivors (cut: weaker
+// ones were left out) and finalize sets redo where they did not fill the cap; round 1 runs for those images alone
+struct SiftRound { int n_sel, cut, redo, pad; };
+__device__ __forceinline__ bool sift_round_skips(const SiftRound *round, int img, int redo) { return redo && !round[img].redo; }
+
 struct RpeSiftState {                   // the device buffers are in the handle's allocation record (DM): rpe_destroy frees them
     SiftDev dv;
     float *d_gauss = nullptr;
@@ -70,15 +88,15 @@ struct RpeSiftState {                   // the device buffers are in the handle'
     unsigned long long *d_xmask = nullptr;                 // [img][bmstride]
     int *d_band_cnt = nullptr, *d_band_off = nullptr;     // [img][nbands]
     unsigned *d_seeds = nullptr; int *d_nseeds = nullptr; // [img][seed_cap], [img]
-    float *d_raw = nullptr;                                // [img][raw_cap][6]: x y size angle response octave(bits)
+    float *d_raw = nullptr;                                // [img][raw_cap][KP_W]
     int *d_nraw = nullptr, *d_ncand = nullptr;
     float *d_surv = nullptr; int *d_nsurv = nullptr;        // [img][seed_cap][SURV_W] refined seeds, [img]
-    unsigned *d_sel = nullptr; int *d_nsel = nullptr;       // [img][seed_cap] survivors that get an orientation (sift_select_kernel), [img][4] = {count, cut, redo, -}
+    unsigned *d_sel = nullptr; SiftRound *d_round = nullptr; // [img][seed_cap] survivors that get an orientation (sift_select_kernel), [img] SiftRound
     int sel_k_override = 0;
     unsigned long long *d_k0 = nullptr, *d_k1 = nullptr; unsigned *d_sidx = nullptr; // sort keys [img][raw_pad]
     int raw_pad = 0;
     bool march = false;                                    // levels 1-3 / 4-5 of the large octaves by sift_march_kernel
-    float *d_fin = nullptr;                                // [img][kcap][6] un-halved keypoints in sorted order
+    float *d_fin = nullptr;                                // [img][kcap][KP_W] un-halved keypoints in sorted order
 };
 
 // ------------------------------------------------------------------ image ops
@@ -361,9 +379,7 @@ __global__ __launch_bounds__(256) void sift_blur_fused_kernel(const float *__res
 // yields every level's own reflect-101 extension exactly -- no special rows.  The row filter accumulates left to right and
 // is not symmetric: at the image's left / right edge a level's out-of-image columns are written as copies of its mirror
 // columns (the column-filter lane of such a column reads the ring at the mirrored column).
-#ifndef MARCH_SW
 #define MARCH_SW 128
-#endif
 #define MARCH_NT (MARCH_SW >= 128 ? 256 : 128)     // threads per workgroup: one lane per column of the widest level
 // (lds[addr + 4 TS i], lds[addr + 4 TS (i + 4)]) for every i of the sequence: each half is its own ds_read_b32 at a static
 // offset, so it lands in its half of the register pair (left to the compiler the two uses of a value share one load and
@@ -560,22 +576,6 @@ __global__ __launch_bounds__(64 * (MarchGeo<NL, R0, R1, R2>::WBASE(NL))) void si
 }
 
 // ------------------------------------------------------------------ extrema
-__device__ __forceinline__ int s_block_excl_scan(int v, int *s_wave, int &total)
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) { int n = __shfl_up(inc, o); if (lane >= o) inc += n; }
-    if (lane == 63) s_wave[wv] = inc;
-    __syncthreads();
-    int base = 0;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) { int s = s_wave[k]; if (k < wv) base += s; }
-    total = s_wave[0] + s_wave[1] + s_wave[2] + s_wave[3];
-    __syncthreads();
-    return base + inc - v;
-}
-
 // Pass 1 (tiled, any order): 26-neighbour test of the three inner DoG layers of a 128x16 tile (rows of 520 bytes
 // per level: 16.9 -> 16.2 ms against 64x32 tiles with 264-byte rows; 256x8 reads 18 % more halo and gains nothing).  The
 // five layers roll through three LDS planes (each DoG value leaves HBM once per tile).  "No
@@ -693,14 +693,14 @@ __global__ __launch_bounds__(256) void sift_extrema_mask_kernel(const float *__r
 __global__ __launch_bounds__(256) void sift_band_scan_kernel(const int *__restrict__ band_cnt, int *__restrict__ band_off, int *__restrict__ nseeds,
                                                               unsigned *__restrict__ overflow, SiftDev dv)
 {
-    __shared__ int s_wave[5];
+    __shared__ int s_wave[4];
     const int img = blockIdx.x, tid = threadIdx.x;
     const int per = (dv.nbands + 255) / 256, b0 = tid * per, b1 = min(b0 + per, dv.nbands);
     const int *bc = band_cnt + (long long)img * dv.nbands;
     int sum = 0;
     for (int b = b0; b < b1; ++b) sum += bc[b];
     int total;
-    int acc = s_block_excl_scan(sum, s_wave, total);
+    int acc = block_excl_scan(sum, s_wave, total);
     int *bo = band_off + (long long)img * dv.nbands;
     for (int b = b0; b < b1; ++b) { bo[b] = acc; acc += bc[b]; }
     if (tid == 0) {
@@ -729,17 +729,15 @@ __global__ __launch_bounds__(256) void sift_extrema_emit_kernel(const unsigned l
         const int wi = w0 + lane;
         unsigned long long m = wi < wpr ? words[wi] : 0ull;
         const int cnt = __popcll(m);
-        int inc = cnt;
-#pragma unroll
-        for (int s = 1; s < 64; s <<= 1) { int v = __shfl_up(inc, s); if (lane >= s) inc += v; }
+        const int inc = wave_inclusive_sum(cnt);
         int idx = base + inc - cnt;
         while (m) {
             const int b = __ffsll((long long)m) - 1;
             m &= m - 1;
-            if (idx < dv.seed_cap) out[idx] = ((unsigned)o << 28) | ((unsigned)l << 26) | ((unsigned)r << 13) | (unsigned)(wi * 64 + b);
+            if (idx < dv.seed_cap) out[idx] = SiftSeed{o, l, r, wi * 64 + b}.pack();
             ++idx;
         }
-        base += __shfl(inc, 63);
+        base += __builtin_amdgcn_readlane(inc, 63);
     }
 }
 
@@ -825,7 +823,6 @@ __device__ static bool sift_adjust(const DogCtx &c, int &layer, int &r, int &x, 
 // per-seed computation (one LANE per seed; most seeds die here on the contrast / edge tests), the
 // orientation histogram is a per-survivor reduction (one WAVE per survivor).  Survivors and raw
 // keypoints are appended through integer atomics; their order is irrelevant (sorted afterwards).
-#define SURV_W 8        // floats per survivor record: packed(o,l,r,c), xi, xr, xc, contr
 __global__ __launch_bounds__(256) void sift_adjust_kernel(const float *__restrict__ gauss, SiftDev dv,
                                                            const unsigned *__restrict__ seeds, const int *__restrict__ nseeds,
                                                            float *__restrict__ surv, int *__restrict__ nsurv)
@@ -833,17 +830,15 @@ __global__ __launch_bounds__(256) void sift_adjust_kernel(const float *__restric
     // image = fastest grid dimension (see sift_orient_kernel: the survivors' atomicAdd(&nsurv[img]) spread over the images)
     const int sidx = blockIdx.y * 256 + threadIdx.x, img = blockIdx.x;
     if (sidx >= nseeds[img]) return;
-    const unsigned sd = seeds[(long long)img * dv.seed_cap + sidx];
-    const int o = sd >> 28;
-    int l = (sd >> 26) & 3, r = (sd >> 13) & 0x1FFF, c = sd & 0x1FFF;
-    const int w = dv.w[o], h = dv.h[o];
-    DogCtx dc = {gauss + (long long)img * dv.gstride + dv.goff[o], (long long)w * h, w, h};
+    SiftSeed sd = SiftSeed::unpack(seeds[(long long)img * dv.seed_cap + sidx]);
+    const int w = dv.w[sd.o], h = dv.h[sd.o];
+    DogCtx dc = {gauss + (long long)img * dv.gstride + dv.goff[sd.o], (long long)w * h, w, h};
     float xi = 0, xr = 0, xc = 0, contr = 0;
-    if (!sift_adjust(dc, l, r, c, xi, xr, xc, contr)) return;
+    if (!sift_adjust(dc, sd.l, sd.r, sd.c, xi, xr, xc, contr)) return;
     const int slot = atomicAdd(&nsurv[img], 1);               // <= nseeds <= seed_cap
     float *q = surv + ((long long)img * dv.seed_cap + slot) * SURV_W;
-    q[0] = __int_as_float((int)(((unsigned)o << 28) | ((unsigned)l << 26) | ((unsigned)r << 13) | (unsigned)c));
-    q[1] = xi; q[2] = xr; q[3] = xc; q[4] = contr;
+    q[SV_SEED] = __int_as_float((int)sd.pack());
+    q[SV_XI] = xi; q[SV_XR] = xr; q[SV_XC] = xc; q[SV_CONTR] = contr;
 }
 
 // retainBest(nfeatures) keeps the strongest responses, and a keypoint's response (|contrast|) is known before its orientation
@@ -852,79 +847,106 @@ __global__ __launch_bounds__(256) void sift_adjust_kernel(const float *__restric
 // keypoints (every survivor yields one or more, except a histogram whose maximum is a plateau): then the nfeatures-th best
 // response, the threshold of retainBest, lies inside the selected set and nothing below it could have been kept.  Otherwise
 // sift_finalize_kernel raises RPE_OVF_SIFT_PREFILTER.  sel_k = 0 (no cap): every survivor is selected.
-__device__ __forceinline__ unsigned s_float_key(float f);
-__global__ __launch_bounds__(256) void sift_select_kernel(const float *__restrict__ surv, const int *__restrict__ nsurv, SiftDev dv, int sel_k,
-                                                           unsigned *__restrict__ sel, int *__restrict__ nsel, int *__restrict__ nraw, int redo)
+// order-preserving map of a float to an unsigned key (-0 = +0)
+__device__ __forceinline__ unsigned s_float_key(float f)
 {
-    __shared__ unsigned s_hist[256];
-    __shared__ unsigned s_prefix;
-    __shared__ int s_kk, s_cnt;
+    unsigned u = __float_as_uint(f);
+    if (u == 0x80000000u) u = 0;
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+
+// Key of the k-th largest of the entries i < n that take part (entry(i, key) says whether i does and gives its key), for a
+// 256-thread workgroup and 1 <= k <= their number: four passes from the top byte down, each a 256-bin histogram of the keys
+// that share the prefix found so far; lane 0 walks the bins from 255 down to the one that holds the k-th.  Keeping every
+// key >= the result keeps the k largest and all that tie with the k-th.
+struct SiftRadix { unsigned hist[256]; unsigned prefix; int kk; };
+template <class Entry>
+__device__ __forceinline__ unsigned sift_kth_largest_key(SiftRadix &s, int n, int k, Entry entry)
+{
+    const int tid = threadIdx.x;
+    unsigned prefix = 0, mask = 0;
+    if (tid == 0) s.kk = k;
+    for (int pass = 3; pass >= 0; --pass) {
+        const int shift = 8 * pass;
+        s.hist[tid] = 0;
+        __syncthreads();
+        for (int i = tid; i < n; i += 256) {
+            unsigned key;
+            if (entry(i, key) && (key & mask) == prefix) atomicAdd(&s.hist[(key >> shift) & 255], 1u);
+        }
+        __syncthreads();
+        if (tid == 0) {
+            int kk = s.kk, acc = 0, bin = 0;
+            for (int b = 255; b >= 0; --b) { int c = (int)s.hist[b]; if (acc + c >= kk) { bin = b; break; } acc += c; }
+            s.kk = kk - acc;
+            s.prefix = prefix | ((unsigned)bin << shift);
+        }
+        __syncthreads();
+        prefix = s.prefix;
+        mask |= 255u << shift;
+    }
+    return prefix;
+}
+
+__global__ __launch_bounds__(256) void sift_select_kernel(const float *__restrict__ surv, const int *__restrict__ nsurv, SiftDev dv, int sel_k,
+                                                           unsigned *__restrict__ sel, SiftRound *__restrict__ round, int *__restrict__ nraw, int redo)
+{
+    __shared__ SiftRadix s_radix;
+    __shared__ int s_cnt;
     const int img = blockIdx.x, tid = threadIdx.x;
     // second round (redo): only the images whose selected survivors did not fill the cap, this time with every survivor
-    if (redo) { if (!nsel[4 * img + 2]) return; sel_k = 0; }
+    if (sift_round_skips(round, img, redo)) return;
+    if (redo) sel_k = 0;
     const int n = min(nsurv[img], dv.seed_cap);
     const float *sv = surv + (long long)img * dv.seed_cap * SURV_W;
     unsigned *out = sel + (long long)img * dv.seed_cap;
+    auto key_of = [&](int i) { return s_float_key(fabsf(sv[(long long)i * SURV_W + SV_CONTR])); };
     unsigned thr_key = 0;
-    if (sel_k > 0 && n > sel_k) {
-        unsigned prefix = 0, mask = 0;
-        if (tid == 0) s_kk = sel_k;
-        for (int pass = 3; pass >= 0; --pass) {
-            const int shift = 8 * pass;
-            s_hist[tid] = 0;
-            __syncthreads();
-            for (int i = tid; i < n; i += 256) {
-                const unsigned key = s_float_key(fabsf(sv[(long long)i * SURV_W + 4]));
-                if ((key & mask) == prefix) atomicAdd(&s_hist[(key >> shift) & 255], 1u);
-            }
-            __syncthreads();
-            if (tid == 0) {
-                int kk = s_kk, acc = 0, bin = 0;
-                for (int b = 255; b >= 0; --b) { int c = (int)s_hist[b]; if (acc + c >= kk) { bin = b; break; } acc += c; }
-                s_kk = kk - acc;
-                s_prefix = prefix | ((unsigned)bin << shift);
-            }
-            __syncthreads();
-            prefix = s_prefix;
-            mask |= 255u << shift;
-        }
-        thr_key = prefix;
-    }
+    if (sel_k > 0 && n > sel_k) thr_key = sift_kth_largest_key(s_radix, n, sel_k, [&](int i, unsigned &key) { key = key_of(i); return true; });
     if (tid == 0) s_cnt = 0;
     __syncthreads();
     for (int i = tid; i < n; i += 256)
-        if (s_float_key(fabsf(sv[(long long)i * SURV_W + 4])) >= thr_key) out[atomicAdd(&s_cnt, 1)] = (unsigned)i;   // order is irrelevant: the keypoints are sorted later
+        if (key_of(i) >= thr_key) out[atomicAdd(&s_cnt, 1)] = (unsigned)i;   // order is irrelevant: the keypoints are sorted later
     __syncthreads();
     if (tid == 0) {
-        nsel[4 * img] = s_cnt; nsel[4 * img + 1] = s_cnt < n ? 1 : 0;
-        if (!redo) nsel[4 * img + 2] = 0; else nraw[img] = 0;
+        round[img].n_sel = s_cnt; round[img].cut = s_cnt < n ? 1 : 0;
+        if (!redo) round[img].redo = 0; else nraw[img] = 0;
     }
+}
+
+// the sum of the 8 interleaved partials of a histogram bin (orient, describe), in the oracle's association
+__device__ __forceinline__ float sum8(const float *p) { return ((p[0] + p[4]) + (p[2] + p[6])) + ((p[1] + p[5]) + (p[3] + p[7])); }
+// cv2 keeps 360 - angle, and 0 where that lies within FLT_EPSILON of 360
+__device__ __forceinline__ float s_angle_flip(float a)
+{
+    float r = 360.f - a;
+    if (fabsf(r - 360.f) < FLT_EPSILON) r = 0.f;
+    return r;
 }
 
 // One wave per workgroup: survivors differ in window size (6 to 14+ batches of 64 samples), and a 4-wave workgroup
 // holds its wave slots and LDS until its slowest wave is done.
-#define SIFT_ORI_WPW 1
 #define S_ORI_RMAX1 20      // radius + 1 <= 18: radius = round(4.5 * 1.6 * 2^((l + xi) / 3)), l <= 3, |xi| < 0.5 -> <= 17
-__global__ __launch_bounds__(64 * SIFT_ORI_WPW) void sift_orient_kernel(const float *__restrict__ gauss, SiftDev dv,
-                                                           const float *__restrict__ surv, const unsigned *__restrict__ sel, const int *__restrict__ nsel,
+__global__ __launch_bounds__(64) void sift_orient_kernel(const float *__restrict__ gauss, SiftDev dv,
+                                                           const float *__restrict__ surv, const unsigned *__restrict__ sel, const SiftRound *__restrict__ round,
                                                            float *__restrict__ raw, int *__restrict__ nraw, unsigned *__restrict__ overflow, int redo)
 {
-    __shared__ float s_part[SIFT_ORI_WPW][S_BINS][8];
-    __shared__ float s_hist[SIFT_ORI_WPW][S_BINS + 4];
-    __shared__ float s_wtab[SIFT_ORI_WPW][S_ORI_RMAX1 * S_ORI_RMAX1];
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    __shared__ float part[S_BINS][8];
+    __shared__ float s_hist[S_BINS + 4];
+    __shared__ float wtab[S_ORI_RMAX1 * S_ORI_RMAX1];
+    const int lane = threadIdx.x;
     // image = fastest grid dimension: workgroups in flight together then belong to different images and their
     // atomicAdd(&nraw[img]) go to different addresses (with one image at a time 14 k returning atomics per image queued
     // on a single L2 line: 12 of this kernel's 20 ms)
-    const int img = blockIdx.x, ns = nsel[4 * img];
-    if (redo && !nsel[4 * img + 2]) return;
+    const int img = blockIdx.x, ns = round[img].n_sel;
+    if (sift_round_skips(round, img, redo)) return;
     // waves stride over the list of selected survivors (a grid sized for seed_cap would be millions of empty workgroups)
-    for (int si = blockIdx.y * SIFT_ORI_WPW + wv; si < ns; si += gridDim.y * SIFT_ORI_WPW) {
+    for (int si = blockIdx.y; si < ns; si += gridDim.y) {
     const int sidx = (int)sel[(long long)img * dv.seed_cap + si];
     const float *sq = surv + ((long long)img * dv.seed_cap + sidx) * SURV_W;
-    const unsigned sd = (unsigned)__float_as_int(sq[0]);
-    const int o = sd >> 28, l = (sd >> 26) & 3, r = (sd >> 13) & 0x1FFF, c = sd & 0x1FFF;
-    const float xi = sq[1], xr = sq[2], xc = sq[3], contr = sq[4];
+    const SiftSeed sd = SiftSeed::unpack((unsigned)__float_as_int(sq[SV_SEED]));
+    const int o = sd.o, l = sd.l, r = sd.r, c = sd.c;
+    const float xi = sq[SV_XI], xr = sq[SV_XR], xc = sq[SV_XC], contr = sq[SV_CONTR];
     const int w = dv.w[o], h = dv.h[o];
     const long long n = (long long)w * h;
     const float kx = ((float)c + xc) * (float)(1 << o), ky = ((float)r + xr) * (float)(1 << o);
@@ -940,14 +962,12 @@ __global__ __launch_bounds__(64 * SIFT_ORI_WPW) void sift_orient_kernel(const fl
     // LDS accessed as LDS (ds_* instructions, in order within the wave); S_WAVE_SYNC orders the lanes' accesses for the
     // compiler.  (Through a volatile generic pointer every access became a flat_* instruction with system-scope cache
     // bits and a full wait: 16 serialized round trips per 64 samples.)
-    float (*part)[8] = s_part[wv];
     for (int i = lane; i < S_BINS * 8; i += 64) (&part[0][0])[i] = 0.f;
     S_WAVE_SYNC();
     // Gaussian weights: exp((i*i + j*j) * expf_scale) is the same number for the up to 8 samples (+-i, +-j), (+-j, +-i),
     // and det_expf (22 dependent f64 operations) was 60 % of this kernel: evaluate it once per pair a <= b into an LDS
     // table.  Rows a and radius - a of the triangle together have radius + 2 entries, so the triangle is walked as a
     // ceil((radius+1)/2) x (radius+2) rectangle: 2 rounds of 64 lanes at radius 14 instead of 14 batches of samples.
-    float *wtab = s_wtab[wv];
     const int r1 = radius + 1;
     if (r1 <= S_ORI_RMAX1) {
         const int wdt = radius + 2, nent = ((r1 + 1) >> 1) * wdt;
@@ -1023,14 +1043,8 @@ __global__ __launch_bounds__(64 * SIFT_ORI_WPW) void sift_orient_kernel(const fl
             }
         }
     }
-    float *th = s_hist[wv] + 2;
-    if (lane < S_BINS) {
-        float p0 = part[lane][0], p1 = part[lane][1], p2 = part[lane][2], p3 = part[lane][3];
-        float p4 = part[lane][4], p5 = part[lane][5], p6 = part[lane][6], p7 = part[lane][7];
-        p0 = p0 + p4; p1 = p1 + p5; p2 = p2 + p6; p3 = p3 + p7;
-        p0 = p0 + p2; p1 = p1 + p3;
-        th[lane] = p0 + p1;
-    }
+    float *th = s_hist + 2;
+    if (lane < S_BINS) th[lane] = sum8(part[lane]);
     S_WAVE_SYNC();
     if (lane == 0) { th[-1] = th[S_BINS - 1]; th[-2] = th[S_BINS - 2]; th[S_BINS] = th[0]; th[S_BINS + 1] = th[1]; }
     S_WAVE_SYNC();
@@ -1045,12 +1059,11 @@ __global__ __launch_bounds__(64 * SIFT_ORI_WPW) void sift_orient_kernel(const fl
     if (lane < S_BINS && hv > hl && hv > hr && hv >= mag_thr) {
         float bin = (float)lane + 0.5f * (hl - hr) / (hl - 2 * hv + hr);
         bin = bin < 0 ? S_BINS + bin : bin >= S_BINS ? bin - S_BINS : bin;
-        float angle = 360.f - (360.f / S_BINS) * bin;
-        if (fabsf(angle - 360.f) < FLT_EPSILON) angle = 0.f;
+        const float angle = s_angle_flip((360.f / S_BINS) * bin);
         const int slot = atomicAdd(&nraw[img], 1);
         if (slot < dv.raw_cap) {
-            float *q = raw + ((long long)img * dv.raw_cap + slot) * 6;
-            q[0] = kx; q[1] = ky; q[2] = ksize; q[3] = angle; q[4] = kresp; q[5] = __int_as_float(koct);
+            float *q = raw + ((long long)img * dv.raw_cap + slot) * KP_W;
+            q[KP_X] = kx; q[KP_Y] = ky; q[KP_SIZE] = ksize; q[KP_ANGLE] = angle; q[KP_RESP] = kresp; q[KP_OCT] = __int_as_float(koct);
         } else atomicOr(&overflow[img], (unsigned)RPE_OVF_SIFT_RAW);
     }
     S_WAVE_SYNC();
@@ -1060,13 +1073,6 @@ __global__ __launch_bounds__(64 * SIFT_ORI_WPW) void sift_orient_kernel(const fl
 // ------------------------------------------------------------------ sort
 // KeyPoint_LessThan as a 128-bit key: (x, y) ascending, size descending, angle ascending.
 // Exact duplicates (same seed end point) get identical keys and become neighbours.
-__device__ __forceinline__ unsigned s_float_key(float f)
-{
-    unsigned u = __float_as_uint(f);
-    if (u == 0x80000000u) u = 0;
-    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
-}
-
 // Response prefilter: retainBest(nfeatures) only ever keeps the strongest keypoints, so only the
 // K = 2*nfeatures + 1024 strongest raw entries (ties included) go through the sort.  Equivalent
 // to OpenCV's dedup -> retainBest as long as the top K hold >= nfeatures unique keypoints
@@ -1074,52 +1080,29 @@ __device__ __forceinline__ unsigned s_float_key(float f)
 __global__ __launch_bounds__(256) void sift_prefilter_kernel(const float *__restrict__ raw, const int *__restrict__ nraw, SiftDev dv, int pad,
                                                               unsigned long long *__restrict__ k0, unsigned long long *__restrict__ k1,
                                                               unsigned *__restrict__ sidx, int *__restrict__ ncand, unsigned *__restrict__ overflow,
-                                                              const int *__restrict__ nsel, int redo)
+                                                              const SiftRound *__restrict__ round, int redo)
 {
-    __shared__ unsigned s_hist[256];
-    __shared__ unsigned s_prefix;
-    __shared__ int s_kk, s_cnt;
+    __shared__ SiftRadix s_radix;
+    __shared__ int s_cnt;
     const int img = blockIdx.x, tid = threadIdx.x;
-    if (redo && !nsel[4 * img + 2]) return;
+    if (sift_round_skips(round, img, redo)) return;
     const int n = min(nraw[img], dv.raw_cap);
-    const float *rw = raw + (long long)img * dv.raw_cap * 6;
+    const float *rw = raw + (long long)img * dv.raw_cap * KP_W;
     const int K = 2 * dv.nfeatures + 1024;
+    auto key_of = [&](int i) { return s_float_key(rw[(long long)i * KP_W + KP_RESP]); };
     unsigned thr_key = 0;
-    if (dv.nfeatures > 0 && n > K) {
-        unsigned prefix = 0, mask = 0;
-        if (tid == 0) s_kk = K;
-        for (int pass = 3; pass >= 0; --pass) {
-            const int shift = 8 * pass;
-            s_hist[tid] = 0;
-            __syncthreads();
-            for (int i = tid; i < n; i += 256) {
-                unsigned key = s_float_key(rw[(long long)i * 6 + 4]);
-                if ((key & mask) == prefix) atomicAdd(&s_hist[(key >> shift) & 255], 1u);
-            }
-            __syncthreads();
-            if (tid == 0) {
-                int kk = s_kk, acc = 0, bin = 0;
-                for (int b = 255; b >= 0; --b) { int c = (int)s_hist[b]; if (acc + c >= kk) { bin = b; break; } acc += c; }
-                s_kk = kk - acc;
-                s_prefix = prefix | ((unsigned)bin << shift);
-            }
-            __syncthreads();
-            prefix = s_prefix;
-            mask |= 255u << shift;
-        }
-        thr_key = prefix;
-    }
+    if (dv.nfeatures > 0 && n > K) thr_key = sift_kth_largest_key(s_radix, n, K, [&](int i, unsigned &key) { key = key_of(i); return true; });
     if (tid == 0) s_cnt = 0;
     __syncthreads();
     unsigned long long *a0 = k0 + (long long)img * pad, *a1 = k1 + (long long)img * pad;
     unsigned *ix = sidx + (long long)img * pad;
     for (int i = tid; i < n; i += 256) {
-        const float *q = rw + (long long)i * 6;
-        if (s_float_key(q[4]) >= thr_key) {
+        if (key_of(i) >= thr_key) {
+            const float *q = rw + (long long)i * KP_W;
             const int slot = atomicAdd(&s_cnt, 1);               // order is irrelevant: the list is sorted next
             if (slot < pad) {
-                a0[slot] = ((unsigned long long)__float_as_uint(q[0]) << 32) | __float_as_uint(q[1]);   // x, y > 0: bit order = value order
-                a1[slot] = ((unsigned long long)(~__float_as_uint(q[2])) << 32) | __float_as_uint(q[3]);
+                a0[slot] = ((unsigned long long)__float_as_uint(q[KP_X]) << 32) | __float_as_uint(q[KP_Y]);   // x, y > 0: bit order = value order
+                a1[slot] = ((unsigned long long)(~__float_as_uint(q[KP_SIZE])) << 32) | __float_as_uint(q[KP_ANGLE]);
                 ix[slot] = (unsigned)i;
             }
         }
@@ -1133,14 +1116,22 @@ __global__ __launch_bounds__(256) void sift_prefilter_kernel(const float *__rest
 // stages with partner distance >= SORT_C go through global memory (6 of the 105 stages at 16 384 entries: through global memory
 // every stage was a dependent L2 round trip -- 0.74 ms per 256-image launch, 1.0 ms of the single uncapped pair's call).
 #define SORT_C 2048
+// one compare-exchange of a bitonic stage: entries i < j of the triple list, the larger one to j if asc, to i if not
+__device__ __forceinline__ void sift_sort_cmpxchg(unsigned long long *k0, unsigned long long *k1, unsigned *ix, int i, int j, bool asc)
+{
+    const unsigned long long x0 = k0[i], x1 = k1[i], y0 = k0[j], y1 = k1[j];
+    const unsigned xi = ix[i], yi = ix[j];
+    const bool gt = x0 > y0 || (x0 == y0 && (x1 > y1 || (x1 == y1 && xi > yi)));
+    if (gt == asc) { k0[i] = y0; k1[i] = y1; ix[i] = yi; k0[j] = x0; k1[j] = x1; ix[j] = xi; }
+}
 __global__ __launch_bounds__(1024) void sift_sort_kernel(const int *__restrict__ ncand, int pad,
                                                           unsigned long long *__restrict__ k0, unsigned long long *__restrict__ k1,
-                                                          unsigned *__restrict__ sidx, const int *__restrict__ nsel, int redo)
+                                                          unsigned *__restrict__ sidx, const SiftRound *__restrict__ round, int redo)
 {
     __shared__ unsigned long long s0[SORT_C], s1[SORT_C];
     __shared__ unsigned si[SORT_C];
     const int img = blockIdx.x, tid = threadIdx.x;
-    if (redo && !nsel[4 * img + 2]) return;
+    if (sift_round_skips(round, img, redo)) return;
     const int n = ncand[img];
     int P = 64;
     while (P < n) P <<= 1;
@@ -1157,12 +1148,8 @@ __global__ __launch_bounds__(1024) void sift_sort_kernel(const int *__restrict__
             for (int k = k_lo; k <= k_hi; k <<= 1)
                 for (int j = min(k >> 1, C >> 1); j > 0; j >>= 1) {
                     for (int t = tid; t < (C >> 1); t += 1024) {
-                        const int i = 2 * j * (t / j) + (t % j), ixj = i + j;
-                        const bool asc = ((base + i) & k) == 0;
-                        const unsigned long long x0 = s0[i], x1 = s1[i], y0 = s0[ixj], y1 = s1[ixj];
-                        const unsigned xi = si[i], yi = si[ixj];
-                        const bool gt = x0 > y0 || (x0 == y0 && (x1 > y1 || (x1 == y1 && xi > yi)));
-                        if (gt == asc) { s0[i] = y0; s1[i] = y1; si[i] = yi; s0[ixj] = x0; s1[ixj] = x1; si[ixj] = xi; }
+                        const int i = 2 * j * (t / j) + (t % j);
+                        sift_sort_cmpxchg(s0, s1, si, i, i + j, ((base + i) & k) == 0);
                     }
                     __syncthreads();
                 }
@@ -1174,12 +1161,8 @@ __global__ __launch_bounds__(1024) void sift_sort_kernel(const int *__restrict__
     for (int k = 2 * C; k <= P; k <<= 1) {
         for (int j = k >> 1; j >= C; j >>= 1) {
             for (int t = tid; t < (P >> 1); t += 1024) {
-                const int i = 2 * j * (t / j) + (t % j), ixj = i + j;
-                const bool asc = (i & k) == 0;
-                const unsigned long long x0 = a0[i], x1 = a1[i], y0 = a0[ixj], y1 = a1[ixj];
-                const unsigned xi = ix[i], yi = ix[ixj];
-                const bool gt = x0 > y0 || (x0 == y0 && (x1 > y1 || (x1 == y1 && xi > yi)));
-                if (gt == asc) { a0[i] = y0; a1[i] = y1; ix[i] = yi; a0[ixj] = x0; a1[ixj] = x1; ix[ixj] = xi; }
+                const int i = 2 * j * (t / j) + (t % j);
+                sift_sort_cmpxchg(a0, a1, ix, i, i + j, (i & k) == 0);
             }
             __syncthreads();
         }
@@ -1190,20 +1173,20 @@ __global__ __launch_bounds__(1024) void sift_sort_kernel(const int *__restrict__
 // ---------------------------------------------------------------- finalize
 __global__ __launch_bounds__(256) void sift_finalize_kernel(const float *__restrict__ raw, const int *__restrict__ ncand, SiftDev dv, int pad,
                                                              const unsigned long long *__restrict__ k0, const unsigned long long *__restrict__ k1,
-                                                             const unsigned *__restrict__ sidx, int *__restrict__ nsel, int redo, float *__restrict__ fin,
+                                                             const unsigned *__restrict__ sidx, SiftRound *__restrict__ round, int redo, float *__restrict__ fin,
                                                              float2 *__restrict__ kp_pt, int *__restrict__ kp_count, unsigned *__restrict__ overflow)
 {
-    __shared__ unsigned s_hist[256];
-    __shared__ int s_wave[5];
-    __shared__ unsigned s_prefix;
-    __shared__ int s_kk, s_nuniq;
+    __shared__ SiftRadix s_radix;
+    __shared__ int s_wave[4];
+    __shared__ int s_nuniq;
     const int img = blockIdx.x, tid = threadIdx.x;
-    if (redo && !nsel[4 * img + 2]) return;
+    if (sift_round_skips(round, img, redo)) return;
     const int n = ncand[img];
     const unsigned long long *a0 = k0 + (long long)img * pad, *a1 = k1 + (long long)img * pad;
     const unsigned *ix = sidx + (long long)img * pad;
-    const float *rw = raw + (long long)img * dv.raw_cap * 6;
+    const float *rw = raw + (long long)img * dv.raw_cap * KP_W;
     auto uniq = [&](int i) { return i == 0 || a0[i] != a0[i - 1] || a1[i] != a1[i - 1]; };
+    auto key_of = [&](int i) { return s_float_key(rw[(long long)ix[i] * KP_W + KP_RESP]); };
     // count unique keypoints (removeDuplicatedSorted)
     if (tid == 0) s_nuniq = 0;
     __syncthreads();
@@ -1212,53 +1195,30 @@ __global__ __launch_bounds__(256) void sift_finalize_kernel(const float *__restr
     atomicAdd(&s_nuniq, cnt);
     __syncthreads();
     const int nuniq = s_nuniq;
-    const bool cut = nsel[4 * img + 1] != 0;             // sift_select_kernel left weaker survivors without an orientation
+    const bool cut = round[img].cut != 0;                // sift_select_kernel left weaker survivors without an orientation
     if (cut && nuniq < dv.nfeatures) {
         // the selected survivors did not fill the cap: keypoints of the ones left out belong to the result.  Nothing is
         // written; the second round orients every survivor of this image and comes back here with cut = 0
-        if (tid == 0) nsel[4 * img + 2] = 1;
+        if (tid == 0) round[img].redo = 1;
         return;
     }
     unsigned thr_key = 0;
-    if (dv.nfeatures > 0 && nuniq > dv.nfeatures) {       // retainBest: response >= the nfeatures-th best
-        unsigned prefix = 0, mask = 0;
-        if (tid == 0) s_kk = dv.nfeatures;
-        for (int pass = 3; pass >= 0; --pass) {
-            const int shift = 8 * pass;
-            s_hist[tid] = 0;
-            __syncthreads();
-            for (int i = tid; i < n; i += 256)
-                if (uniq(i)) {
-                    unsigned key = s_float_key(rw[(long long)ix[i] * 6 + 4]);
-                    if ((key & mask) == prefix) atomicAdd(&s_hist[(key >> shift) & 255], 1u);
-                }
-            __syncthreads();
-            if (tid == 0) {
-                int kk = s_kk, acc = 0, bin = 0;
-                for (int b = 255; b >= 0; --b) { int c = (int)s_hist[b]; if (acc + c >= kk) { bin = b; break; } acc += c; }
-                s_kk = kk - acc;
-                s_prefix = prefix | ((unsigned)bin << shift);
-            }
-            __syncthreads();
-            prefix = s_prefix;
-            mask |= 255u << shift;
-        }
-        thr_key = prefix;
-    }
+    if (dv.nfeatures > 0 && nuniq > dv.nfeatures)         // retainBest: response >= the nfeatures-th best
+        thr_key = sift_kth_largest_key(s_radix, n, dv.nfeatures, [&](int i, unsigned &key) { if (!uniq(i)) return false; key = key_of(i); return true; });
     int offset = 0;
     for (int c0 = 0; c0 < n; c0 += 256) {
         const int i = c0 + tid;
         bool keep = false;
-        if (i < n && uniq(i)) keep = s_float_key(rw[(long long)ix[i] * 6 + 4]) >= thr_key;
+        if (i < n && uniq(i)) keep = key_of(i) >= thr_key;
         int total;
-        const int ex = s_block_excl_scan(keep ? 1 : 0, s_wave, total);
+        const int ex = block_excl_scan(keep ? 1 : 0, s_wave, total);
         if (keep) {
             const int o = offset + ex;
             if (o < dv.kcap) {
-                const float *q = rw + (long long)ix[i] * 6;
-                float *f = fin + ((long long)img * dv.kcap + o) * 6;
-                f[0] = q[0]; f[1] = q[1]; f[2] = q[2]; f[3] = q[3]; f[4] = q[4]; f[5] = q[5];
-                kp_pt[(long long)img * dv.kcap + o] = make_float2(q[0] * 0.5f, q[1] * 0.5f);   // firstOctave = -1
+                const float *q = rw + (long long)ix[i] * KP_W;
+                float *f = fin + ((long long)img * dv.kcap + o) * KP_W;
+                for (int e = 0; e < KP_W; ++e) f[e] = q[e];
+                kp_pt[(long long)img * dv.kcap + o] = make_float2(q[KP_X] * 0.5f, q[KP_Y] * 0.5f);   // firstOctave = -1
             }
         }
         offset += total;
@@ -1275,29 +1235,26 @@ __global__ __launch_bounds__(256) void sift_finalize_kernel(const float *__restr
 // ---------------------------------------------------------------- descriptor
 // One keypoint per 64-lane workgroup: the 15 KB of accumulators per keypoint decide the occupancy (four keypoints per
 // workgroup were 61 KB: 2 workgroups = 8 waves per CU; one per workgroup gives 10).
-#define SIFT_DESC_KPW 1
 #define S_DESC_ROWS 128       // rows of the sample square: 2 radius + 1 <= 77 (radius = round(3 scl sqrt2 2.5), scl <= 1.6 * 2^(3.5/3))
-__global__ __launch_bounds__(64 * SIFT_DESC_KPW) void sift_describe_kernel(const float *__restrict__ gauss, SiftDev dv, const float *__restrict__ fin,
+__global__ __launch_bounds__(64) void sift_describe_kernel(const float *__restrict__ gauss, SiftDev dv, const float *__restrict__ fin,
                                                              const int *__restrict__ kp_count, uint8_t *__restrict__ desc)
 {
     // accumulators of the 4 x 4 inner cells only: the border cells of calcSIFTDescriptor's 6 x 6 x 10 histogram are never read
     // (each (bin, slot) accumulator is independent, so leaving them out changes nothing that is), and 5 KB instead of 11.5 KB
     // per keypoint decide how many workgroups a CU holds
-    __shared__ float s_part[SIFT_DESC_KPW][160][8];
-    __shared__ float s_hist[SIFT_DESC_KPW][160];
-    __shared__ float s_stage[SIFT_DESC_KPW][64 * 9];
-    __shared__ int s_ja[SIFT_DESC_KPW][S_DESC_ROWS], s_pre[SIFT_DESC_KPW][S_DESC_ROWS + 1];   // per raster row: first valid column, samples before the row
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const int kidx = blockIdx.x * SIFT_DESC_KPW + wv, img = blockIdx.y;
+    __shared__ float part[160][8];
+    __shared__ float hist[160];
+    __shared__ float stg[64 * 9];
+    __shared__ int rja[S_DESC_ROWS], rpre[S_DESC_ROWS + 1];   // per raster row: first valid column, samples before the row
+    const int lane = threadIdx.x;
+    const int kidx = blockIdx.x, img = blockIdx.y;
     if (kidx >= kp_count[img]) return;
-    const float *f = fin + ((long long)img * dv.kcap + kidx) * 6;
-    const int koct = __float_as_int(f[5]);
+    const float *f = fin + ((long long)img * dv.kcap + kidx) * KP_W;
+    const int koct = __float_as_int(f[KP_OCT]);
     const int o = koct & 255, l = (koct >> 8) & 255;
     const float scale = 1.f / (float)(1 << o);
-    const float size = f[2] * scale;
-    float angle = 360.f - f[3];
-    if (fabsf(angle - 360.f) < FLT_EPSILON) angle = 0.f;
-    const float ptx = f[0] * scale, pty = f[1] * scale, ori = angle, scl = size * 0.5f;
+    const float size = f[KP_SIZE] * scale;
+    const float ptx = f[KP_X] * scale, pty = f[KP_Y] * scale, ori = s_angle_flip(f[KP_ANGLE]), scl = size * 0.5f;
     const int w = dv.w[o], h = dv.h[o];
     const float *img_l = gauss + (long long)img * dv.gstride + dv.goff[o] + (long long)l * w * h;
     const int d = 4, n = 8;
@@ -1310,8 +1267,6 @@ __global__ __launch_bounds__(64 * SIFT_DESC_KPW) void sift_describe_kernel(const
     const int rmax = (int)sqrt(((double)w) * w + ((double)h) * h);
     if (radius > rmax) radius = rmax;
     cos_t /= hist_width; sin_t /= hist_width;
-    float (*part)[8] = s_part[wv];
-    float *stg = s_stage[wv];
     for (int i = lane; i < 160 * 8; i += 64) (&part[0][0])[i] = 0.f;
     S_WAVE_SYNC();
     const int side = 2 * radius + 1;
@@ -1322,7 +1277,6 @@ __global__ __launch_bounds__(64 * SIFT_DESC_KPW) void sift_describe_kernel(const
     // a wave scan numbers the samples, and the expensive part below runs on dense batches of 64 samples whose (i, j) come from
     // the row table.  Sample number k counts the samples that pass, as cv2's arrays do.
     constexpr int DU = 4;                                   // dense batches whose gradient loads fly together
-    int *rja = s_ja[wv], *rpre = s_pre[wv];
     auto okpos = [&](int i, int j) -> bool {
         const float crot = j * cos_t - i * sin_t, rrot = j * sin_t + i * cos_t;
         const float rbn = rrot + d / 2 - 0.5f, cbn = crot + d / 2 - 0.5f;
@@ -1355,11 +1309,9 @@ __global__ __launch_bounds__(64 * SIFT_DESC_KPW) void sift_describe_kernel(const
                 ja = jl; cnt = jh - jl + 1;
             }
         }
-        int incl = cnt;                                      // inclusive scan over the 64 rows of this pass
-#pragma unroll
-        for (int of = 1; of < 64; of <<= 1) { const int t = __shfl_up(incl, of); if (lane >= of) incl += t; }
+        const int incl = wave_inclusive_sum(cnt);            // over the 64 rows of this pass
         if (row < side) { rja[row] = ja; rpre[row] = ntotal + incl - cnt; }
-        ntotal += __shfl(incl, 63);
+        ntotal += __builtin_amdgcn_readlane(incl, 63);
     }
     if (lane == 0) rpre[side] = ntotal;
     S_WAVE_SYNC();
@@ -1447,13 +1399,7 @@ __global__ __launch_bounds__(64 * SIFT_DESC_KPW) void sift_describe_kernel(const
         }
     }
     S_WAVE_SYNC();
-    float *hist = s_hist[wv];
-    for (int b = lane; b < 160; b += 64) {
-        float p0 = part[b][0], p1 = part[b][1], p2 = part[b][2], p3 = part[b][3], p4 = part[b][4], p5 = part[b][5], p6 = part[b][6], p7 = part[b][7];
-        p0 = p0 + p4; p1 = p1 + p5; p2 = p2 + p6; p3 = p3 + p7;
-        p0 = p0 + p2; p1 = p1 + p3;
-        hist[b] = p0 + p1;
-    }
+    for (int b = lane; b < 160; b += 64) hist[b] = sum8(part[b]);
     S_WAVE_SYNC();
     // circular orientation bins, then element e = (i*d + j)*n + k ; lane holds e = lane and lane + 64
     float dv0, dv1;
@@ -1483,18 +1429,14 @@ __global__ __launch_bounds__(64 * SIFT_DESC_KPW) void sift_describe_kernel(const
 }
 
 // ================================================================== host side
-static int s_round_d(double v) { return (int)lrint(v); }
-
 static int sift_gauss_kernel(double sigma, float *k)
 {
-    int ks = s_round_d(sigma * 8 + 1) | 1;
+    int ks = cv_round(sigma * 8 + 1) | 1;
     double sum = 0, t[64];
     for (int i = 0; i < ks; ++i) { double x = i - (ks - 1) * 0.5; t[i] = exp(-0.5 * x * x / (sigma * sigma)); sum += t[i]; }
     for (int i = 0; i < ks; ++i) k[i] = (float)(t[i] / sum);
     return ks;
 }
-
-#define SCHK(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { h->err = std::string(#call) + ": " + hipGetErrorString(e_); return RPE_ERR_HIP; } } while (0)
 
 int rpe_sift_create(rpe_handle *h)
 {
@@ -1503,7 +1445,7 @@ int rpe_sift_create(rpe_handle *h)
     SiftDev &dv = S->dv;
     const int W = h->cfg.width, H = h->cfg.height;
     const int bw = 2 * W, bh = 2 * H, mn = bw < bh ? bw : bh;
-    dv.noct = s_round_d(log((double)mn) / log(2.) - 2) + 1;
+    dv.noct = cv_round(log((double)mn) / log(2.) - 2) + 1;
     if (dv.noct > 12) dv.noct = 12;
     long long go = 0;
     for (int o = 0; o < dv.noct; ++o) {
@@ -1530,8 +1472,8 @@ int rpe_sift_create(rpe_handle *h)
     // instantiated for exactly these (sift_blur, sift_march_kernel) and there is no path for any other
     for (int i = 0; i < S_NG; ++i)
         if ((ks[i] >> 1) != kSiftRadius[i]) { h->err = "SIFT blur radii are not 5 5 6 8 10 13"; return RPE_ERR_INVALID; }
-    SCHK(hipMemcpyToSymbol(HIP_SYMBOL(c_skern), kern, sizeof(kern)));
-    SCHK(hipMemcpyToSymbol(HIP_SYMBOL(c_sks), ks, sizeof(ks)));
+    HIPCHK(h, hipMemcpyToSymbol(HIP_SYMBOL(c_skern), kern, sizeof(kern)));
+    HIPCHK(h, hipMemcpyToSymbol(HIP_SYMBOL(c_sks), ks, sizeof(ks)));
     // extrema scan: bands (one per row of every (octave, inner layer)) in the oracle's enumeration order, the hit
     // mask layout and the tile list of the tiled first pass
     std::vector<SiftXTile> xt;
@@ -1556,26 +1498,26 @@ int rpe_sift_create(rpe_handle *h)
     { const int need = dv.nfeatures > 0 ? 2 * dv.nfeatures + 1024 + 2048 : 2 * dv.kcap; while (S->raw_pad < need) S->raw_pad <<= 1; }
     S->n_xtiles = (int)xt.size();
     DM(h, S->d_xtiles, xt.size() ? xt.size() : 1);
-    if (!xt.empty()) SCHK(hipMemcpy(S->d_xtiles, xt.data(), sizeof(SiftXTile) * xt.size(), hipMemcpyHostToDevice));
+    if (!xt.empty()) HIPCHK(h, hipMemcpy(S->d_xtiles, xt.data(), sizeof(SiftXTile) * xt.size(), hipMemcpyHostToDevice));
     DM(h, S->d_xmask, NI * dv.bmstride);
     DM(h, S->d_gauss, NI * dv.gstride);
     DM(h, S->d_band_cnt, NI * dv.nbands);
     DM(h, S->d_band_off, NI * dv.nbands);
     DM(h, S->d_seeds, NI * dv.seed_cap);
     DM(h, S->d_nseeds, NI);
-    DM(h, S->d_raw, NI * dv.raw_cap * 6);
+    DM(h, S->d_raw, NI * dv.raw_cap * KP_W);
     DM(h, S->d_nraw, NI);
     DM(h, S->d_surv, NI * dv.seed_cap * SURV_W);
     DM(h, S->d_nsurv, NI);
     DM(h, S->d_sel, NI * dv.seed_cap);
-    DM(h, S->d_nsel, NI * 4);
+    DM(h, S->d_round, NI);
     S->march = getenv("RPE_SIFT_MARCH") != nullptr;
     if (const char *e = getenv("RPE_SIFT_SEL_K")) S->sel_k_override = atoi(e);      // tests: a small value forces the second round
     DM(h, S->d_ncand, NI);
     DM(h, S->d_k0, NI * S->raw_pad);
     DM(h, S->d_k1, NI * S->raw_pad);
     DM(h, S->d_sidx, NI * S->raw_pad);
-    DM(h, S->d_fin, NI * dv.kcap * 6);
+    DM(h, S->d_fin, NI * dv.kcap * KP_W);
     return RPE_OK;
 }
 
@@ -1669,23 +1611,23 @@ int rpe_sift_run(rpe_handle *h, const uint8_t *d_a, const uint8_t *d_b, int na, 
     const int sel_k = dv.nfeatures > 0 ? (S->sel_k_override > 0 ? S->sel_k_override : dv.nfeatures + dv.nfeatures / 4 + 256) : 0;
     for (int redo = 0; redo < (sel_k > 0 ? 2 : 1); ++redo) {
         hipLaunchKernelGGL(sift_select_kernel, dim3(n), dim3(256), 0, h->stream, (const float *)S->d_surv, (const int *)S->d_nsurv, dv,
-                           sel_k, S->d_sel, S->d_nsel, S->d_nraw, redo);
-        hipLaunchKernelGGL(sift_orient_kernel, dim3(n, (redo ? 64 : 8192) / SIFT_ORI_WPW), dim3(64 * SIFT_ORI_WPW), 0, h->stream, (const float *)S->d_gauss, dv,
-                           (const float *)S->d_surv, (const unsigned *)S->d_sel, (const int *)S->d_nsel, S->d_raw, S->d_nraw, h->d_ovf, redo);
+                           sel_k, S->d_sel, S->d_round, S->d_nraw, redo);
+        hipLaunchKernelGGL(sift_orient_kernel, dim3(n, redo ? 64 : 8192), dim3(64), 0, h->stream, (const float *)S->d_gauss, dv,
+                           (const float *)S->d_surv, (const unsigned *)S->d_sel, (const SiftRound *)S->d_round, S->d_raw, S->d_nraw, h->d_ovf, redo);
         if (!redo) MARK(h, RPE_STAGE_KEYPOINTS);
         hipLaunchKernelGGL(sift_prefilter_kernel, dim3(n), dim3(256), 0, h->stream, (const float *)S->d_raw, (const int *)S->d_nraw, dv, S->raw_pad,
-                           S->d_k0, S->d_k1, S->d_sidx, S->d_ncand, h->d_ovf, (const int *)S->d_nsel, redo);
+                           S->d_k0, S->d_k1, S->d_sidx, S->d_ncand, h->d_ovf, (const SiftRound *)S->d_round, redo);
         hipLaunchKernelGGL(sift_sort_kernel, dim3(n), dim3(1024), 0, h->stream, (const int *)S->d_ncand, S->raw_pad, S->d_k0, S->d_k1, S->d_sidx,
-                           (const int *)S->d_nsel, redo);
+                           (const SiftRound *)S->d_round, redo);
         hipLaunchKernelGGL(sift_finalize_kernel, dim3(n), dim3(256), 0, h->stream, (const float *)S->d_raw, (const int *)S->d_ncand, dv, S->raw_pad,
-                           (const unsigned long long *)S->d_k0, (const unsigned long long *)S->d_k1, (const unsigned *)S->d_sidx, S->d_nsel, redo,
+                           (const unsigned long long *)S->d_k0, (const unsigned long long *)S->d_k1, (const unsigned *)S->d_sidx, S->d_round, redo,
                            S->d_fin, h->d_kp_pt, h->d_kp_count, h->d_ovf);
     }
     // 6. descriptors
     MARK(h, RPE_STAGE_ANGLE); MARK(h, RPE_STAGE_BLUR); MARK(h, RPE_STAGE_DESCRIBE);
-    hipLaunchKernelGGL(sift_describe_kernel, dim3((dv.kcap + SIFT_DESC_KPW - 1) / SIFT_DESC_KPW, n), dim3(64 * SIFT_DESC_KPW), 0, h->stream, (const float *)S->d_gauss, dv,
+    hipLaunchKernelGGL(sift_describe_kernel, dim3(dv.kcap, n), dim3(64), 0, h->stream, (const float *)S->d_gauss, dv,
                        (const float *)S->d_fin, (const int *)h->d_kp_count, h->d_desc);
-    SCHK(hipGetLastError());
+    HIPCHK(h, hipGetLastError());
     return RPE_OK;
 }
 
@@ -1693,17 +1635,17 @@ int rpe_sift_run(rpe_handle *h, const uint8_t *d_a, const uint8_t *d_b, int na, 
 int rpe_sift_fetch(rpe_handle *h, int n_images, float *fin_host, int *counts)
 {
     RpeSiftState *S = h->sift;
-    SCHK(hipMemcpyAsync(fin_host, S->d_fin, sizeof(float) * 6 * (size_t)n_images * S->dv.kcap, hipMemcpyDeviceToHost, h->stream));
-    SCHK(hipMemcpyAsync(counts, h->d_kp_count, sizeof(int) * n_images, hipMemcpyDeviceToHost, h->stream));
-    SCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpyAsync(fin_host, S->d_fin, sizeof(float) * KP_W * (size_t)n_images * S->dv.kcap, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipMemcpyAsync(counts, h->d_kp_count, sizeof(int) * n_images, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return RPE_OK;
 }
 
 int rpe_sift_fetch_gauss(rpe_handle *h, int index, float *out)
 {
     RpeSiftState *S = h->sift;
-    SCHK(hipMemcpyAsync(out, S->d_gauss + (long long)index * S->dv.gstride, sizeof(float) * S->dv.gstride, hipMemcpyDeviceToHost, h->stream));
-    SCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(h, hipMemcpyAsync(out, S->d_gauss + (long long)index * S->dv.gstride, sizeof(float) * S->dv.gstride, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(h, hipStreamSynchronize(h->stream));
     return RPE_OK;
 }
 long long rpe_sift_gauss_floats(rpe_handle *h) { return h->sift ? h->sift->dv.gstride : 0; }

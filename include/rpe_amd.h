@@ -502,6 +502,14 @@ int rpe_orb_detect_and_compute(rpe_handle *h, const uint8_t *h_imgs, int n_image
  * fused kernel; which = 1 is rejected.)  ORB handles only. */
 int rpe_orb_debug_fetch(rpe_handle *h, int index, int which, uint8_t *h_out);
 int64_t rpe_orb_pyramid_pixels(const rpe_handle *h);
+/* KeyPointsFilter::retainBest as retain_fast / retain_harris replay it, on n_lists caller-supplied lists in one launch
+ * (one workgroup per list, the kernels' own device routine).  kind 0: u32 FAST entries, compared on bits 24..31 (the
+ * score); kind 1: u64 Harris entries, compared on the f32 in bits 32..63.  elems[n_lists*cap]: list i at elems + i*cap
+ * holds len[i] elements and is reordered in place exactly as retainBest(n_points[i]) of the stl_runtime (RPE_STL_*)
+ * leaves it; out_len[i] receives its new size.  RPE_ERR_INVALID, nothing launched: a list longer than cap, cap beyond
+ * 8192 elements or 64 KB of LDS (elements + 2 bytes each).  ORB handles only. */
+int rpe_orb_debug_retain(rpe_handle *h, int kind, int stl_runtime, void *elems, const int32_t *len, const int32_t *n_points,
+                         int n_lists, int cap, int32_t *out_len);
 
 /* replaces matcher.match + sorted + truncate (pose_estimator.py:144-151) for B
  * descriptor-set pairs.  desc1/desc2: B*cap*32 bytes (cap = keypoint

@@ -55,6 +55,7 @@ _SIGNATURES = {
     "rpe_fetch_match_indices": "i:pipp", "rpe_scale_links": "i:pipppippp", "rpe_guided_matches": "i:pippdipppppp",
     "rpe_pair_homographies": "i:piidppppp", "rpe_find_homography": "i:ppppipidppppp",
     "rpe_orb_detect_and_compute": "i:ppippp", "rpe_orb_debug_fetch": "i:piip", "rpe_orb_pyramid_pixels": "l:p",
+    "rpe_orb_debug_retain": "i:piipppiip",
     "rpe_match_hamming": "i:pppppipppp", "rpe_match_hamming_guided": "i:pppppppipppdipppp",
     "rpe_sift_detect_and_compute": "i:ppippp", "rpe_sift_debug_gauss": "l:pip", "rpe_match_l2": "i:pppppipppp",
     "rpe_find_essential": "i:ppppippppp", "rpe_recover_pose": "i:pppppipppp", "rpe_refine_pose_points": "i:pppppppipippppp",
@@ -579,6 +580,19 @@ class Engine:
         out = np.zeros(self.lib.rpe_orb_pyramid_pixels(self.h), np.uint8)
         self._chk(self.lib.rpe_orb_debug_fetch(self.h, index, which, _p(out)))
         return out
+
+    def orb_debug_retain(self, kind, stl, lists, n_points, cap=None):
+        """retainBest(n_points[i]) on every list (kind 0: uint32 FAST entries, 1: uint64 Harris entries) in one launch of
+        the selection kernels' routine; returns the lists as left behind (whole, by their old lengths) and the new sizes"""
+        dt = np.uint64 if kind else np.uint32
+        n = len(lists)
+        cap = max(1, max(len(a) for a in lists)) if cap is None else cap
+        ln = _i32([len(a) for a in lists]); npts = _i32(n_points); out_len = np.zeros(n, np.int32)
+        buf = np.zeros((n, max(cap, int(ln.max()))), dt)
+        for i, a in enumerate(lists):
+            buf[i, :len(a)] = a
+        self._chk(self.lib.rpe_orb_debug_retain(self.h, kind, stl, _p(buf), _p(ln), _p(npts), n, cap, _p(out_len)))
+        return [buf[i, :ln[i]].copy() for i in range(n)], out_len
 
     def sift_detect_and_compute(self, imgs):
         imgs = np.ascontiguousarray(imgs, np.uint8)

@@ -546,9 +546,9 @@ void rpe_launch_fast(rpe_handle *h, int n_img)
 // selection is replayed move for move:
 //   raster_corners  one workgroup per (level, image): the level's FAST tile lists -> ONE list in raster order
 //                   (counting sort over rows in LDS, rank by x inside a row), the first ccap entries
-//   retain_fast     one wave per (level, image), one lane working: retainBest(2 * quota) on the FAST score -> candidates
+//   retain_fast     one workgroup per (level, image): retainBest(2 * quota) on the FAST score -> candidates
 //   harris          (below)
-//   retain_harris   one wave per (level, image): retainBest(quota) on the Harris response, in place
+//   retain_harris   one workgroup per (level, image): retainBest(quota) on the Harris response, in place
 //   compact         one workgroup per image: level-major concatenation into the keypoint arrays
 // Raster order, pass by pass:
 //   pass 1  per-row count of the entries (LDS atomics)                          -> exclusive scan = row starts
@@ -660,22 +660,37 @@ __global__ __launch_bounds__(256) void raster_corners_kernel(const unsigned *__r
     }
 }
 
-// retainBest(2 * quota) on the FAST score.  One wave per (level, image); the list sits in LDS and the wave replays the
-// runtime library's nth_element + partition on it (retain_best_emul.h): libstdc++'s partition passes have a closed form
-// that the 64 lanes evaluate with ballots and popcounts (one lane alone spent 2.5 ms per 2048 images chasing dependent
-// LDS round trips); the few-element steps and MSVC's fat-pivot partition run on one lane.  Two launches share the work by
-// list length (lo < n0 <= cap) so that the common short lists do not reserve the LDS of the longest possible one.
+// retainBest(2 * quota) on the FAST score.  One workgroup of RPE_RETAIN_FAST_WAVES waves per (level, image); the list sits in
+// LDS and the workgroup replays the runtime library's nth_element + partition on it (retain_best_emul.h): libstdc++'s
+// partition passes have a closed form that the lanes evaluate with ballots and popcounts, every wave on its own slice of
+// the range (one lane alone spent 2.5 ms per 2048 images chasing dependent LDS round trips, one wave per list filled 10
+// of a CU's 32 wave slots); the few-element steps and MSVC's fat-pivot partition run on one lane.  Two launches share the
+// work by list length (lo < n0 <= cap) so that the common short lists do not reserve the LDS of the longest possible one.
+#define RPE_RETAIN_FAST_WAVES 2     // measured 1 / 2 / 4: the long lists of retain_fast gain from a second wave,
+#define RPE_RETAIN_HARRIS_WAVES 1   // the <= 2 quota + ties candidates of retain_harris lose to the barriers of any more
+
+// retainBest(n_points) on one list in LDS, by the whole workgroup (uniform arguments and result): the routine of
+// retain_fast_kernel, retain_harris_kernel and the stage entry rpe_orb_debug_retain.  s_pos: [n + 2] u16, s_ctl: 3 ints per wave.
+template <int NW, class E, class GT, class GE>
+__device__ __forceinline__ int retain_list(E *s_a, int n, int n_points, int stl, GT gt, GE ge, unsigned short *s_pos, int *s_ctl)
+{
+    if (stl == rb::RT_LIBSTDCXX)                             // the partition passes as ballot / popcount sweeps of all waves
+        return rb::block_retain_best_gnu<NW>(s_a, n, n_points, gt, ge, s_pos, s_ctl);
+    if (threadIdx.x == 0) s_ctl[0] = rb::retain_best(s_a, n, n_points, stl, gt, ge);   // MSVC's fat-pivot partition: one lane, move for move
+    __syncthreads();
+    return s_ctl[0];
+}
+
 struct FastScoreGT { __device__ __forceinline__ bool operator()(unsigned a, unsigned b) const { return (a >> 24) > (b >> 24); } };
 struct FastScoreGE { __device__ __forceinline__ bool operator()(unsigned a, unsigned b) const { return (a >> 24) >= (b >> 24); } };
 
-__global__ __launch_bounds__(64) void retain_fast_kernel(const unsigned *__restrict__ corner, const int *__restrict__ corner_count,
+__global__ __launch_bounds__(64 * RPE_RETAIN_FAST_WAVES) void retain_fast_kernel(const unsigned *__restrict__ corner, const int *__restrict__ corner_count,
                                                           unsigned *__restrict__ cand_xy, int *__restrict__ cand_count,
                                                           unsigned *__restrict__ ovf, RpeDeviceLayout lay, int lo, int cap, int n_img)
 {
-    extern __shared__ unsigned s_a[];                          // [cap] elements, then [cap + 2] u16 stopper positions (wave_pair_swap)
-    __shared__ unsigned long long s_mask[2 * 128];           // stopper masks of <= 8192 elements
-    __shared__ int s_n1;
-    const int lane = threadIdx.x, l = blockIdx.x;
+    extern __shared__ unsigned s_a[];                          // [cap] elements, then [cap + 2] u16 stopper positions (block_pair_swap)
+    __shared__ int s_ctl[3 * RPE_RETAIN_FAST_WAVES];
+    const int tid = threadIdx.x, l = blockIdx.x;
     const RpeLevel &L = lay.lv[l];
     // the long-list launch runs a small grid whose workgroups walk over the images: on ordinary images it has nothing to do,
     // and 10 000 empty workgroups that each reserve 26 KB of LDS took 64 us
@@ -691,22 +706,16 @@ __global__ __launch_bounds__(64) void retain_fast_kernel(const unsigned *__restr
     unsigned *out = cand_xy + (long long)img * lay.cand_total + L.cand_off;
     int n1 = n0;
     if (active) {
-        for (int i = lane; i < n0; i += 64) s_a[i] = in[i];
+        for (int i = tid; i < n0; i += 64 * RPE_RETAIN_FAST_WAVES) s_a[i] = in[i];
         __syncthreads();
-        if (lay.stl == rb::RT_LIBSTDCXX)                     // the partition passes as ballot / popcount sweeps of the whole wave
-            n1 = rb::wave_retain_best_gnu(s_a, n0, n_points, FastScoreGT(), FastScoreGE(), s_mask, (unsigned short *)(s_a + cap), &s_n1);
-        else {                                               // MSVC's fat-pivot partition: one lane, move for move
-            if (lane == 0) s_n1 = rb::retain_best(s_a, n0, n_points, lay.stl, FastScoreGT(), FastScoreGE());
-            __syncthreads();
-            n1 = s_n1;
-        }
+        n1 = retain_list<RPE_RETAIN_FAST_WAVES>(s_a, n0, n_points, lay.stl, FastScoreGT(), FastScoreGE(), (unsigned short *)(s_a + cap), s_ctl);
     }
     const int nw = min(n1, L.kcap2);
-    for (int i = lane; i < nw; i += 64) {
+    for (int i = tid; i < nw; i += 64 * RPE_RETAIN_FAST_WAVES) {
         const unsigned e = active ? s_a[i] : in[i];
         out[i] = (((e >> 12) & 0xFFFu) << 16) | (e & 0xFFFu);
     }
-    if (lane == 0) {
+    if (tid == 0) {
         cand_count[img * RPE_NLEVELS + l] = nw;
         if (n1 > L.kcap2) atomicOr(&ovf[img], (unsigned)RPE_OVF_ORB_CANDIDATES);
     }
@@ -732,11 +741,11 @@ void rpe_launch_raster_retain(rpe_handle *h, int n_img)
                        (const unsigned *)h->d_tile_list, (const int *)h->d_tile_cnt,
                        h->d_corner, h->d_corner_count, h->d_ovf, h->lay, h->n_tiles_fast, rows_cap, key_cap);
     auto lds_of = [](int cap) { return sizeof(unsigned) * (size_t)cap + sizeof(unsigned short) * ((size_t)cap + 4); };
-    hipLaunchKernelGGL(retain_fast_kernel, dim3(RPE_NLEVELS, n_img), dim3(64), lds_of(std::min(ccap_max, RPE_RETAIN_TIER)), h->stream,
+    hipLaunchKernelGGL(retain_fast_kernel, dim3(RPE_NLEVELS, n_img), dim3(64 * RPE_RETAIN_FAST_WAVES), lds_of(std::min(ccap_max, RPE_RETAIN_TIER)), h->stream,
                        (const unsigned *)h->d_corner, (const int *)h->d_corner_count, h->d_cand_xy, h->d_cand_count, h->d_ovf, h->lay,
                        0, std::min(ccap_max, RPE_RETAIN_TIER), n_img);
     if (nlev_big > 0)
-        hipLaunchKernelGGL(retain_fast_kernel, dim3(nlev_big, std::min(n_img, 512)), dim3(64), lds_of(ccap_max), h->stream,
+        hipLaunchKernelGGL(retain_fast_kernel, dim3(nlev_big, std::min(n_img, 512)), dim3(64 * RPE_RETAIN_FAST_WAVES), lds_of(ccap_max), h->stream,
                            (const unsigned *)h->d_corner, (const int *)h->d_corner_count, h->d_cand_xy, h->d_cand_count, h->d_ovf, h->lay,
                            RPE_RETAIN_TIER, ccap_max, n_img);
 }
@@ -816,40 +825,63 @@ void rpe_launch_harris(rpe_handle *h, int n_img)
 
 // -------------------------------------------------------------- keypoints
 // KeyPointsFilter::retainBest(quota) on the Harris response, per level, replayed on the candidates in the order the
-// first retainBest left them (see "select" above): element = (f32 response bits << 32 | y << 16 | x), one lane, in LDS;
+// first retainBest left them (see "select" above): element = (f32 response bits << 32 | y << 16 | x), in LDS;
 // the survivors go back to the head of the level's candidate run, in order.  compact_keypoints then concatenates the
 // levels into the level-major keypoint arrays the descriptor kernel and the matcher read.
 struct HarrisGT { __device__ __forceinline__ bool operator()(unsigned long long a, unsigned long long b) const { return __uint_as_float((unsigned)(a >> 32)) > __uint_as_float((unsigned)(b >> 32)); } };
 struct HarrisGE { __device__ __forceinline__ bool operator()(unsigned long long a, unsigned long long b) const { return __uint_as_float((unsigned)(a >> 32)) >= __uint_as_float((unsigned)(b >> 32)); } };
 
-__global__ __launch_bounds__(64) void retain_harris_kernel(unsigned *__restrict__ cand_xy, float *__restrict__ cand_resp,
+__global__ __launch_bounds__(64 * RPE_RETAIN_HARRIS_WAVES) void retain_harris_kernel(unsigned *__restrict__ cand_xy, float *__restrict__ cand_resp,
                                                             const int *__restrict__ cand_count, int *__restrict__ kp_lvl_count,
                                                             RpeDeviceLayout lay, int lo, int cap)
 {
     extern __shared__ unsigned long long s_e[];               // [cap] elements, then [cap + 2] u16 stopper positions
-    __shared__ unsigned long long s_mask[2 * 128];
-    __shared__ int s_n2;
-    const int lane = threadIdx.x, l = blockIdx.x, img = blockIdx.y;
+    __shared__ int s_ctl[3 * RPE_RETAIN_HARRIS_WAVES];
+    const int tid = threadIdx.x, l = blockIdx.x, img = blockIdx.y;
     const RpeLevel &L = lay.lv[l];
     const int n1 = cand_count[img * RPE_NLEVELS + l];
     const int q = L.quota;
     const bool active = n1 > q;
     if (active ? !(n1 > lo && n1 <= cap) : lo != 0) return;
-    if (!active) { if (lane == 0) kp_lvl_count[img * RPE_NLEVELS + l] = n1; return; }
+    if (!active) { if (tid == 0) kp_lvl_count[img * RPE_NLEVELS + l] = n1; return; }
     unsigned *xy = cand_xy + (long long)img * lay.cand_total + L.cand_off;
     float *resp = cand_resp + (long long)img * lay.cand_total + L.cand_off;
-    for (int i = lane; i < n1; i += 64) s_e[i] = ((unsigned long long)__float_as_uint(resp[i]) << 32) | xy[i];
+    for (int i = tid; i < n1; i += 64 * RPE_RETAIN_HARRIS_WAVES) s_e[i] = ((unsigned long long)__float_as_uint(resp[i]) << 32) | xy[i];
     __syncthreads();
-    int n2;
-    if (lay.stl == rb::RT_LIBSTDCXX)
-        n2 = rb::wave_retain_best_gnu(s_e, n1, q, HarrisGT(), HarrisGE(), s_mask, (unsigned short *)(s_e + cap), &s_n2);
-    else {
-        if (lane == 0) s_n2 = rb::retain_best(s_e, n1, q, lay.stl, HarrisGT(), HarrisGE());
-        __syncthreads();
-        n2 = s_n2;
-    }
-    for (int i = lane; i < n2; i += 64) { const unsigned long long e = s_e[i]; xy[i] = (unsigned)e; resp[i] = __uint_as_float((unsigned)(e >> 32)); }
-    if (lane == 0) kp_lvl_count[img * RPE_NLEVELS + l] = n2;
+    const int n2 = retain_list<RPE_RETAIN_HARRIS_WAVES>(s_e, n1, q, lay.stl, HarrisGT(), HarrisGE(), (unsigned short *)(s_e + cap), s_ctl);
+    for (int i = tid; i < n2; i += 64 * RPE_RETAIN_HARRIS_WAVES) { const unsigned long long e = s_e[i]; xy[i] = (unsigned)e; resp[i] = __uint_as_float((unsigned)(e >> 32)); }
+    if (tid == 0) kp_lvl_count[img * RPE_NLEVELS + l] = n2;
+}
+
+// stage entry rpe_orb_debug_retain: retainBest(n_points[i]) on list i of a batch (elements at elems + i * cap, len[i] of
+// them), one workgroup per list, through retain_list with the waves of the kind's kernel; every list goes back as it was left, with its new size.
+template <int NW, class E, class GT, class GE>
+__global__ __launch_bounds__(64 * NW) void retain_debug_kernel(E *__restrict__ elems, const int *__restrict__ len,
+                                                                          const int *__restrict__ n_points, int *__restrict__ out_len, int cap, int stl)
+{
+    extern __shared__ unsigned long long s_dbg[];             // [cap] elements, then [cap + 2] u16 stopper positions
+    __shared__ int s_ctl[3 * NW];
+    E *s_l = (E *)s_dbg;
+    E *list = elems + (long long)blockIdx.x * cap;
+    const int tid = threadIdx.x, n = len[blockIdx.x];
+    for (int i = tid; i < n; i += 64 * NW) s_l[i] = list[i];
+    __syncthreads();
+    const int n1 = retain_list<NW>(s_l, n, n_points[blockIdx.x], stl, GT(), GE(), (unsigned short *)(s_l + cap), s_ctl);
+    for (int i = tid; i < n; i += 64 * NW) list[i] = s_l[i];
+    if (tid == 0) out_len[blockIdx.x] = n1;
+}
+
+size_t rpe_debug_retain_lds(int kind, int cap) { return (kind ? sizeof(unsigned long long) : sizeof(unsigned)) * (size_t)cap + sizeof(unsigned short) * ((size_t)cap + 4); }
+
+void rpe_launch_debug_retain(rpe_handle *h, int kind, int stl, void *d_elems, const int *d_len, const int *d_n_points, int *d_out_len, int n_lists, int cap)
+{
+    const size_t lds = rpe_debug_retain_lds(kind, cap);
+    if (kind == 0)
+        hipLaunchKernelGGL((retain_debug_kernel<RPE_RETAIN_FAST_WAVES, unsigned, FastScoreGT, FastScoreGE>), dim3(n_lists), dim3(64 * RPE_RETAIN_FAST_WAVES), lds, h->stream,
+                           (unsigned *)d_elems, d_len, d_n_points, d_out_len, cap, stl);
+    else
+        hipLaunchKernelGGL((retain_debug_kernel<RPE_RETAIN_HARRIS_WAVES, unsigned long long, HarrisGT, HarrisGE>), dim3(n_lists), dim3(64 * RPE_RETAIN_HARRIS_WAVES), lds, h->stream,
+                           (unsigned long long *)d_elems, d_len, d_n_points, d_out_len, cap, stl);
 }
 
 __global__ __launch_bounds__(256) void compact_keypoints_kernel(const unsigned *__restrict__ cand_xy, const float *__restrict__ cand_resp,
@@ -894,10 +926,10 @@ void rpe_launch_keypoints(rpe_handle *h, int n_img)
     }
     const int tier = std::min(kcap2_max, RPE_RETAIN_TIER / 2);
     auto lds_of = [](int cap) { return sizeof(unsigned long long) * (size_t)cap + sizeof(unsigned short) * ((size_t)cap + 4); };
-    hipLaunchKernelGGL(retain_harris_kernel, dim3(RPE_NLEVELS, n_img), dim3(64), lds_of(tier), h->stream,
+    hipLaunchKernelGGL(retain_harris_kernel, dim3(RPE_NLEVELS, n_img), dim3(64 * RPE_RETAIN_HARRIS_WAVES), lds_of(tier), h->stream,
                        h->d_cand_xy, h->d_cand_resp, (const int *)h->d_cand_count, h->d_kp_lvl_count, h->lay, 0, tier);
     if (nlev_big > 0)
-        hipLaunchKernelGGL(retain_harris_kernel, dim3(nlev_big, n_img), dim3(64), lds_of(kcap2_max), h->stream,
+        hipLaunchKernelGGL(retain_harris_kernel, dim3(nlev_big, n_img), dim3(64 * RPE_RETAIN_HARRIS_WAVES), lds_of(kcap2_max), h->stream,
                            h->d_cand_xy, h->d_cand_resp, (const int *)h->d_cand_count, h->d_kp_lvl_count, h->lay, RPE_RETAIN_TIER / 2, kcap2_max);
     hipLaunchKernelGGL(compact_keypoints_kernel, dim3(n_img), dim3(256), 0, h->stream,
                        (const unsigned *)h->d_cand_xy, (const float *)h->d_cand_resp, (const int *)h->d_kp_lvl_count,

@@ -262,7 +262,7 @@ template <class E, class GT, class GE> RB_FN int retain_best(E *a, int n, int n_
     return partition_pred(a, n_points, n, [&](const E &x) { return ge(x, amb); });
 }
 
-// ================================================================================================ wave-parallel form
+// ================================================================================================ closed form of the passes
 // The two linear passes of the libstdc++ procedure -- __unguarded_partition and std::partition -- are Hoare-style
 // two-pointer scans, and their net effect has a closed form: let A_1 < A_2 < ... be the positions (ascending) where the
 // LEFT scan stops, B_1 > B_2 > ... the positions (descending) where the RIGHT scan stops; the k-th swap exchanges A_k and
@@ -271,10 +271,10 @@ template <class E, class GT, class GE> RB_FN int retain_best(E *a, int n, int n_
 // equal to the pivot stops both scans.)  With K = #{k : A_k < B_k}: the pass = those K swaps, and __unguarded_partition
 // returns min(A_{K+1}, B_K) (the left scan rests on the next stopper of the untouched middle or on the element the last swap
 // put at B_K), std::partition returns first + #{pred true}.  K follows from ranks alone: the left stopper at i with rank
-// r is swapped iff at least r right stoppers lie beyond i.  That is a few ballot / popcount sweeps for a wave instead of a
-// chain of dependent LDS round trips for one lane.
+// r is swapped iff at least r right stoppers lie beyond i.  That is a few ballot / popcount sweeps for the waves of a workgroup
+// instead of a chain of dependent LDS round trips for one lane.
 //
-// pair_swap_model: the same arithmetic as the device routine below, lane by lane, on the host -- the unit test compares it
+// pair_swap_model: the closed form with the range as one slice, lane by lane, on the host -- the unit test compares it
 // with the sequential scans above (tests/test_retain_best_cpu.py), the GPU parity tests compare the device routine with the
 // oracle.  LS(e): the left scan stops at e;  RS(e): the right scan stops at e.
 template <class E, class LS, class RS> RB_FN int pair_swap_model(E *a, int lo, int hi, LS ls, RS rs, int *cut /* A_{K+1}, or hi */)
@@ -303,30 +303,153 @@ template <class E, class LS, class RS> RB_FN int pair_swap_model(E *a, int lo, i
     return K;
 }
 
-#ifdef __HIPCC__
-// One wave (all 64 lanes, uniform arguments); a[] in LDS; s_mask: 2 x ceil(m / 64) u64 of LDS; s_pos: 2 x (m / 2 + 1) u16 of LDS.
+// ================================================================================================ workgroup form
+// The same closed form with the range cut into NW contiguous slices of 64-element chunks, one slice per wave of a
+// workgroup of NW waves: a wave ballots its own chunks, the waves exchange only their slice totals (left stoppers, right
+// stoppers) through LDS, and every rank is the slice's offset (the totals of the slices before it) plus the prefix count
+// inside the slice.  The ranks, K, the K swaps and the cut are those of pair_swap_model whatever NW is; NW = 1 is the
+// former one-wave routine.
+//
+// block_pair_swap_model: the arithmetic of block_pair_swap slice by slice, chunk by chunk, lane by lane on the host
+// (tests/test_retain_block_cpu.py compares it with the sequential scans).  *n_rs receives the number of right stoppers.
+RB_FN int popc64(unsigned long long v) { int c = 0; for (; v; v &= v - 1) ++c; return c; }
+
 template <class E, class LS, class RS>
-__device__ __forceinline__ int wave_pair_swap(E *a, int lo, int hi, LS ls, RS rs, unsigned long long *s_mask, unsigned short *s_pos, int &cut)
+RB_FN int block_pair_swap_model(E *a, int lo, int hi, LS ls, RS rs, int nwaves, int *cut, int *n_rs = nullptr)
 {
-    const int lane = threadIdx.x & 63, m = hi - lo, nc = (m + 63) >> 6, capK = m / 2 + 1;
-    unsigned long long *mL = s_mask, *mR = s_mask + nc;
+    const int m = hi - lo, nc = (m + 63) >> 6, capK = m / 2 + 1, cpw = (nc + nwaves - 1) / nwaves;
+    int *tot = new int[3 * nwaves];                                 // the LDS slots: L, R and K of every slice
+    int *posA = new int[capK + 1], *posB = new int[capK + 1];
+    // the ballots of chunk c, from the ORIGINAL contents (no swap happens before every rank is known)
+    auto ballots = [&](int c, unsigned long long &bl, unsigned long long &br) {
+        bl = br = 0ull;
+        for (int lane = 0; lane < 64; ++lane) {
+            const int x = lo + 64 * c + lane;
+            if (x < hi) { if (ls(a[x])) bl |= 1ull << lane; if (rs(a[x])) br |= 1ull << lane; }
+        }
+    };
+    for (int w = 0; w < nwaves; ++w) {                             // sweep 1: slice totals
+        const int c0 = w * cpw < nc ? w * cpw : nc, c1 = c0 + cpw < nc ? c0 + cpw : nc;
+        int sumL = 0, sumR = 0;
+        for (int c = c0; c < c1; ++c) { unsigned long long bl, br; ballots(c, bl, br); sumL += popc64(bl); sumR += popc64(br); }
+        tot[w] = sumL; tot[nwaves + w] = sumR;
+    }
+    int totalL = 0, totalR = 0;
+    for (int v = 0; v < nwaves; ++v) { totalL += tot[v]; totalR += tot[nwaves + v]; }
+    for (int w = 0; w < nwaves; ++w) {                             // sweep 2: offsets, ranks, the slice's share of K
+        const int c0 = w * cpw < nc ? w * cpw : nc, c1 = c0 + cpw < nc ? c0 + cpw : nc;
+        int cumL = 0, cumR = 0, K = 0;
+        for (int v = 0; v < w; ++v) { cumL += tot[v]; cumR += tot[nwaves + v]; }
+        for (int c = c0; c < c1; ++c) {
+            unsigned long long bl, br;
+            ballots(c, bl, br);
+            for (int lane = 0; lane < 64; ++lane) {
+                const int x = lo + 64 * c + lane;
+                const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
+                const bool l = (bl >> lane) & 1ull, r = (br >> lane) & 1ull;
+                const int rl = cumL + popc64(bl & below) + 1;
+                const int r_le = cumR + popc64(br & below) + (r ? 1 : 0);
+                if (r) { const int rr = totalR - r_le + 1; if (rr <= capK) posB[rr - 1] = x; }
+                if (l) { if (rl <= capK) posA[rl - 1] = x; if (totalR - r_le >= rl) ++K; }
+            }
+            cumL += popc64(bl); cumR += popc64(br);
+        }
+        tot[2 * nwaves + w] = K;
+    }
+    int K = 0;
+    for (int v = 0; v < nwaves; ++v) K += tot[2 * nwaves + v];
+    *cut = K < totalL && K < capK ? posA[K] : hi;
+    if (K >= 1 && posB[K - 1] < *cut) *cut = posB[K - 1];
+    for (int k = 0; k < K; ++k) swp(a, posA[k], posB[k]);
+    if (n_rs) *n_rs = totalR;
+    delete[] tot; delete[] posA; delete[] posB;
+    return K;
+}
+
+// KeyPointsFilter::retainBest on libstdc++ with its two linear passes -- __unguarded_partition and std::partition --
+// handed to `pass` (a pair-swap routine: the workgroup's on the device, its model on the host) and its few-element steps
+// (median of three, the <= 3-element insertion sort, the never-taken heap fallback) to `one`, which runs them on one lane.
+// Returns the new size.  pass(a, lo, hi, ls, rs, cut, n_rs);  one(f).
+template <class E, class GT, class GE, class PASS, class ONE>
+RB_FN int retain_best_gnu_by_passes(E *a, int n, int n_points, GT gt, GE ge, PASS pass, ONE one, int depth_limit_override = -1)
+{
+    if (!(n_points >= 0 && n > n_points)) return n;
+    if (n_points == 0) return 0;
+    const int nth = n_points - 1;
+    int first = 0, last = n, depth = 0;
+    for (int m = n; m > 1; m >>= 1) ++depth;
+    depth *= 2;
+    if (depth_limit_override >= 0) depth = depth_limit_override;
+    while (last - first > 3) {
+        if (depth == 0) {
+            one([&]() { gnu_heap_select(a, first, nth + 1, last, gt); swp(a, first, nth); });
+            first = last;                                      // done (the library returns here)
+            break;
+        }
+        --depth;
+        const int mid = first + (last - first) / 2;
+        one([&]() { gnu_move_median_to_first(a, first, first + 1, mid, last - 1, gt); });
+        const E pv = a[first];
+        int cut, n_rs;
+        pass(a, first + 1, last, [&](const E &e) { return !gt(e, pv); }, [&](const E &e) { return !gt(pv, e); }, cut, n_rs);
+        if (cut <= nth) first = cut; else last = cut;
+    }
+    one([&]() { gnu_insertion_sort(a, first, last, gt); });
+    const E amb = a[nth];
+    int cut2, cnt;
+    // std::partition(a + n_points, a + n, e >= amb): the left scan stops at !pred, the right scan at pred; the right
+    // stoppers are the elements it keeps
+    pass(a, n_points, n, [&](const E &e) { return !ge(e, amb); }, [&](const E &e) { return ge(e, amb); }, cut2, cnt);
+    return n_points + cnt;
+}
+
+struct ModelPass {
+    int nwaves;
+    template <class E, class LS, class RS> int operator()(E *a, int lo, int hi, LS ls, RS rs, int &cut, int &n_rs) const
+    { return block_pair_swap_model(a, lo, hi, ls, rs, nwaves, &cut, &n_rs); }
+};
+struct ModelOne { template <class F> void operator()(F f) const { f(); } };
+
+// the workgroup procedure on the host: block_retain_best_gnu with the model in place of the device pass
+template <class E, class GT, class GE>
+RB_FN int block_retain_best_gnu_model(E *a, int n, int n_points, GT gt, GE ge, int nwaves, int depth_limit_override = -1)
+{
+    return retain_best_gnu_by_passes(a, n, n_points, gt, ge, ModelPass{nwaves}, ModelOne(), depth_limit_override);
+}
+
+#ifdef __HIPCC__
+// One workgroup of NW waves (all 64 NW lanes, uniform arguments); a[] in LDS; s_pos: 2 x (m / 2 + 1) u16 of LDS;
+// s_tot: 3 NW ints of LDS.  Both sweeps read the stoppers off a[], which no lane writes before the barrier that follows them.
+template <int NW, class E, class LS, class RS>
+__device__ __forceinline__ int block_pair_swap(E *a, int lo, int hi, LS ls, RS rs, unsigned short *s_pos, int *s_tot, int &cut, int &n_rs)
+{
+    const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const int m = hi - lo, nc = (m + 63) >> 6, capK = m / 2 + 1, cpw = (nc + NW - 1) / NW;
+    const int c0 = min(w * cpw, nc), c1 = min(c0 + cpw, nc);                      // this wave's slice of chunks
     unsigned short *posA = s_pos, *posB = s_pos + capK;
-    int totalR = 0, totalL = 0;
-    for (int c = 0; c < nc; ++c) {
+    int sumL = 0, sumR = 0;
+    for (int c = c0; c < c1; ++c) {
+        const int x = lo + 64 * c + lane;
+        bool l = false, r = false;
+        if (x < hi) { const E e = a[x]; l = ls(e); r = rs(e); }
+        sumL += __popcll(__ballot(l)); sumR += __popcll(__ballot(r));
+    }
+    if (lane == 0) { s_tot[w] = sumL; s_tot[NW + w] = sumR; }
+    __syncthreads();
+    int cumL = 0, cumR = 0, totalL = 0, totalR = 0;
+#pragma unroll
+    for (int v = 0; v < NW; ++v) {
+        const int tl = s_tot[v], tr = s_tot[NW + v];
+        if (v < w) { cumL += tl; cumR += tr; }
+        totalL += tl; totalR += tr;
+    }
+    const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;        // lanes < lane
+    int K = 0;
+    for (int c = c0; c < c1; ++c) {
         const int x = lo + 64 * c + lane;
         bool l = false, r = false;
         if (x < hi) { const E e = a[x]; l = ls(e); r = rs(e); }
         const unsigned long long bl = __ballot(l), br = __ballot(r);
-        if (lane == 0) { mL[c] = bl; mR[c] = br; }
-        totalL += __popcll(bl); totalR += __popcll(br);
-    }
-    __syncthreads();
-    const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;        // lanes < lane
-    int K = 0, cumL = 0, cumR = 0;
-    for (int c = 0; c < nc; ++c) {
-        const unsigned long long bl = mL[c], br = mR[c];
-        const int x = lo + 64 * c + lane;
-        const bool l = (bl >> lane) & 1ull, r = (br >> lane) & 1ull;
         const int rl = cumL + __popcll(bl & below) + 1;                            // rank of this left stopper
         const int r_le = cumR + __popcll(br & below) + (r ? 1 : 0);                // right stoppers at positions <= x
         if (r) { const int rr = totalR - r_le + 1; if (rr <= capK) posB[rr - 1] = (unsigned short)x; }
@@ -335,51 +458,32 @@ __device__ __forceinline__ int wave_pair_swap(E *a, int lo, int hi, LS ls, RS rs
         K += __popcll(__ballot(sw));
         cumL += __popcll(bl); cumR += __popcll(br);
     }
+    if (lane == 0) s_tot[2 * NW + w] = K;
     __syncthreads();
+    K = 0;
+#pragma unroll
+    for (int v = 0; v < NW; ++v) K += s_tot[2 * NW + v];
     cut = (K < totalL && K < capK) ? (int)posA[K] : hi;
     if (K >= 1) cut = min(cut, (int)posB[K - 1]);              // see pair_swap_model
-    for (int k = lane; k < K; k += 64) { const int i = posA[k], j = posB[k]; const E t = a[i]; a[i] = a[j]; a[j] = t; }
+    for (int k = threadIdx.x; k < K; k += 64 * NW) { const int i = posA[k], j = posB[k]; const E t = a[i]; a[i] = a[j]; a[j] = t; }
     __syncthreads();
+    n_rs = totalR;
     return K;
 }
 
-// KeyPointsFilter::retainBest on libstdc++, one wave: the partition passes through wave_pair_swap, the few-element steps
-// (median of three, the <= 3-element insertion sort, the never-taken heap fallback) by lane 0.  Returns the new size (uniform).
-template <class E, class GT, class GE>
-__device__ __forceinline__ int wave_retain_best_gnu(E *a, int n, int n_points, GT gt, GE ge, unsigned long long *s_mask, unsigned short *s_pos, int *s_ctl)
+template <int NW> struct BlockPass {
+    unsigned short *s_pos; int *s_tot;
+    template <class E, class LS, class RS> __device__ __forceinline__ int operator()(E *a, int lo, int hi, LS ls, RS rs, int &cut, int &n_rs) const
+    { return block_pair_swap<NW>(a, lo, hi, ls, rs, s_pos, s_tot, cut, n_rs); }
+};
+struct BlockOne { template <class F> __device__ __forceinline__ void operator()(F f) const { if (threadIdx.x == 0) f(); __syncthreads(); } };
+
+// KeyPointsFilter::retainBest on libstdc++, one workgroup of NW waves: the partition passes through block_pair_swap, the
+// few-element steps by lane 0 of wave 0 with a barrier behind each.  Returns the new size (uniform).
+template <int NW, class E, class GT, class GE>
+__device__ __forceinline__ int block_retain_best_gnu(E *a, int n, int n_points, GT gt, GE ge, unsigned short *s_pos, int *s_tot)
 {
-    if (!(n_points >= 0 && n > n_points)) return n;
-    if (n_points == 0) return 0;
-    const int lane = threadIdx.x & 63, nth = n_points - 1;
-    int first = 0, last = n, depth = 0;
-    for (int m = n; m > 1; m >>= 1) ++depth;
-    depth *= 2;
-    while (last - first > 3) {
-        if (depth == 0) {
-            if (lane == 0) { gnu_heap_select(a, first, nth + 1, last, gt); swp(a, first, nth); }
-            __syncthreads();
-            first = last;                                      // done (the library returns here)
-            break;
-        }
-        --depth;
-        const int mid = first + (last - first) / 2;
-        if (lane == 0) gnu_move_median_to_first(a, first, first + 1, mid, last - 1, gt);
-        __syncthreads();
-        const E pv = a[first];
-        int cut;
-        wave_pair_swap(a, first + 1, last, [&](const E &e) { return !gt(e, pv); }, [&](const E &e) { return !gt(pv, e); }, s_mask, s_pos, cut);
-        if (cut <= nth) first = cut; else last = cut;
-    }
-    if (lane == 0 && last > first) gnu_insertion_sort(a, first, last, gt);
-    __syncthreads();
-    const E amb = a[nth];
-    int cut2, cnt = 0;
-    // std::partition(a + n_points, a + n, e >= amb): the left scan stops at !pred, the right scan at pred
-    for (int x = n_points + lane; x < n; x += 64) cnt += ge(a[x], amb) ? 1 : 0;
-    cnt = wave_sum(cnt);
-    wave_pair_swap(a, n_points, n, [&](const E &e) { return !ge(e, amb); }, [&](const E &e) { return ge(e, amb); }, s_mask, s_pos, cut2);
-    (void)s_ctl;
-    return n_points + cnt;
+    return retain_best_gnu_by_passes(a, n, n_points, gt, ge, BlockPass<NW>{s_pos, s_tot}, BlockOne());
 }
 #endif
 

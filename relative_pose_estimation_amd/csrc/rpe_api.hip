@@ -1515,6 +1515,37 @@ extern "C" int rpe_orb_debug_fetch(rpe_handle *h, int index, int which, uint8_t 
     return RPE_OK;
 }
 
+extern "C" int rpe_orb_debug_retain(rpe_handle *h, int kind, int stl_runtime, void *elems, const int32_t *len, const int32_t *n_points,
+                                    int n_lists, int cap, int32_t *out_len)
+{
+    if (!h || !elems || !len || !n_points || !out_len || n_lists < 1 || cap < 1) return rpe_invalid(h, "rpe_orb_debug_retain");
+    if (h->cfg.feature_method != RPE_FEATURE_ORB) return rpe_invalid(h, "rpe_orb_debug_retain", "handle was not created for ORB");
+    if (kind != 0 && kind != 1) return rpe_invalid(h, "rpe_orb_debug_retain", "kind must be 0 (u32 FAST entries) or 1 (u64 Harris entries)");
+    if (stl_runtime != RPE_STL_LIBSTDCXX && stl_runtime != RPE_STL_MSVC) return rpe_invalid(h, "rpe_orb_debug_retain", "unknown stl_runtime");
+    // positions travel as u16 and the list, with its stopper positions, must fit the default dynamic LDS of a workgroup
+    if (cap > 8192 || rpe_debug_retain_lds(kind, cap) > 65536) return rpe_invalid(h, "rpe_orb_debug_retain", "cap too large for one workgroup's LDS");
+    for (int i = 0; i < n_lists; ++i)
+        if (len[i] < 0 || len[i] > cap) return rpe_invalid(h, "rpe_orb_debug_retain", "a list is longer than the capacity the launch is sized for");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    const size_t esz = kind ? 8 : 4, bytes = esz * (size_t)n_lists * cap, ibytes = sizeof(int) * (size_t)n_lists;
+    void *d_elems = nullptr; int *d_int = nullptr;                   // len | n_points | out_len
+    HIPCHK(h, hipMalloc(&d_elems, bytes));
+    hipError_t e = hipMalloc((void **)&d_int, 3 * ibytes);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_elems, elems, bytes, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_int, len, ibytes, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(d_int + n_lists, n_points, ibytes, hipMemcpyHostToDevice, h->stream);
+    if (e == hipSuccess) {
+        rpe_launch_debug_retain(h, kind, stl_runtime, d_elems, d_int, d_int + n_lists, d_int + 2 * (size_t)n_lists, n_lists, cap);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(elems, d_elems, bytes, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipMemcpyAsync(out_len, d_int + 2 * (size_t)n_lists, ibytes, hipMemcpyDeviceToHost, h->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
+    hipFree(d_elems); hipFree(d_int);
+    HIPCHK(h, e);
+    return RPE_OK;
+}
+
 // tail of rpe_match_hamming / rpe_match_l2 (descriptors of pair p uploaded to workspace slots p and B + p): counts,
 // the handle's matcher of that norm, the match lists (dist: int32 Hamming distances or f32 L2 distances, 4 bytes either)
 static int stage_match_run(rpe_handle *h, bool l2, const int32_t *n1, const int32_t *n2, int B, int32_t *qidx, int32_t *tidx,

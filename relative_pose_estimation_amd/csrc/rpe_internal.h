@@ -452,6 +452,8 @@ void rpe_launch_harris(rpe_handle *h, int n_img);
 void rpe_launch_keypoints(rpe_handle *h, int n_img);
 void rpe_launch_orient_describe(rpe_handle *h, int n_img);
 void rpe_launch_debug_blur(rpe_handle *h, int img);
+size_t rpe_debug_retain_lds(int kind, int cap);
+void rpe_launch_debug_retain(rpe_handle *h, int kind, int stl, void *d_elems, const int *d_len, const int *d_n_points, int *d_out_len, int n_lists, int cap);
 // How the matrix-core Hamming matchers (crossCheck: extra_uint4 = 0, guided: RPE_GUIDED_LDS_UINT4) run B pairs of capacity
 // kcap; the rule is rpe_hamming_plan's alone (match_kernels.hip)
 struct RpeHammingPlan {

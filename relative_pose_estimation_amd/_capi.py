@@ -23,7 +23,7 @@ OVF_ORB_CANDIDATES, OVF_ORB_KEYPOINTS = 1 << 0, 1 << 1
 OVF_SIFT_SEEDS, OVF_SIFT_RAW, OVF_SIFT_PREFILTER, OVF_SIFT_CAP, OVF_SIFT_KEYPOINTS = 1 << 4, 1 << 5, 1 << 6, 1 << 7, 1 << 8
 SIFT_UNCAPPED_CAPACITY = 16320   # RPE_SIFT_UNCAPPED_CAPACITY: keypoints per image kept by SIFT with nfeatures = 0
 MAX_MATCHES_LIMIT = 8064          # rpe_config.max_matches upper bound
-CALIB_KINDS = 16
+CALIB_KINDS = 18
 STAGE_COUNT = 12
 ORDER_BGR, ORDER_RGB = 0, 1
 REFINE_OK, REFINE_SKIPPED, REFINE_REJECTED = 0, 1, 2   # info[:, 0] of refine_poses (include/rpe_amd.h RPE_REFINE_*)

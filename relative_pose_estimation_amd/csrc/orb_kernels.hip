@@ -245,7 +245,10 @@ void rpe_launch_pyramid(rpe_handle *h, int n_img)
 //  phase 1: every dword group (4 px) of the 66x72 score area: OpenCV's pair test on the
 //           4 compass + 4 diagonal ring pixels, darker and brighter side apart:
 //           a 9-arc contains one pixel of every opposite pair, so a darker (brighter) arc needs
-//           every pair to hold a pixel below v - thr (above v + thr).  Survivors are appended
+//           every pair to hold a pixel below v - thr (above v + thr).  The four pixels stay four
+//           bytes of one register: each comparison is the carry of a byte sum against a saturated
+//           threshold (v_lerp_u8, bit 7 of every byte), the pair logic runs on whole dwords.
+//           Exact for every (r, v, thr): tests/test_fast_bytes_cpu.py.  Survivors are appended
 //           to an LDS list with one wave-aggregated LDS atomic per wave: candidates with a darker
 //           arc possible from the front, brighter-only ones from the back.
 //  phase 2: the list in one contiguous slice per wave: the score of the possible side(s) only,
@@ -259,7 +262,7 @@ __device__ __forceinline__ int imax3(int a, int b, int c) { return max(a, max(b,
 // reduction instead of 16 + 16 + 8
 __device__ __forceinline__ int vmax3u(int a, int b, int c) { int d; asm("v_max3_u32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c)); return d; }
 __device__ __forceinline__ int vmin3u(int a, int b, int c) { int d; asm("v_min3_u32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c)); return d; }
-typedef short short2_t __attribute__((ext_vector_type(2)));
+typedef unsigned short ushort2_t __attribute__((ext_vector_type(2)));
 // Bresenham circle of radius 3 (fast.cpp), compile-time offsets
 static constexpr int CIRC_DX[16] = {0, 1, 2, 3, 3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1};
 static constexpr int CIRC_DY[16] = {3, 3, 2, 1, 0, -1, -2, -3, -3, -3, -2, -1, 0, 1, 2, 3};
@@ -332,12 +335,12 @@ __global__ __launch_bounds__(FAST_THREADS) void fast_nms_kernel(const uint8_t *_
         for (int i = tid; i < FS_ROWS * 18 / 4; i += FAST_THREADS) z1[i] = z;
     }
     __syncthreads();
-    // ---- phase 1 (packed 16-bit SWAR: even / odd pixels of the dword group in one VGPR each)
+    // ---- phase 1 (byte SWAR: the four pixels of the dword group in one VGPR, two v_lerp_u8 per ring pixel)
     // lane -> fixed dword column c (18 per row) and rows r0, r0+14, ... : the x-validity mask is
     // computed once per tile and the candidate bits of the 5 rows are appended in one go
-    const unsigned T0 = (unsigned)thr * 0x00010001u;
+    const unsigned T0 = (unsigned)thr * 0x01000100u;                      // thr in the high byte of both 16-bit lanes
     const int c = tid % 18, r0 = tid / 18;
-    unsigned dark_bits = 0, brt_bits = 0;
+    unsigned dark_bits = 0, brt_bits = 0, ndark_bits = 0xFFFFFFFFu;
     if (tid < FAST_LANES) {
         const int cl = max(c - 1, 0), cr = min(c + 1, 17);
         const int pxb = x0 - 4 + 4 * c;
@@ -346,9 +349,10 @@ __global__ __launch_bounds__(FAST_THREADS) void fast_nms_kernel(const uint8_t *_
         if (pxb < xlo) vmask &= 0xFu << min(xlo - pxb, 4);
         if (pxb + 3 > xhi) vmask &= 0xFu >> min(pxb + 3 - xhi, 4);
         vmask &= 0xFu;
-        // candidate flags of the 5 rows share one dword per side: pixel px of row it -> bit 8 px + it (the four sign bytes of
-        // a row are gathered by one v_perm and dropped into place by a shift and a v_and_or: 3 instructions per row and side
-        // instead of 14 for the compact 4-bit form; the x-validity mask is applied once, spread to bytes)
+        // candidate flags of the 5 rows share one dword per side: pixel px of row it -> bit 8 px + it (a row's flags are
+        // bit 7 of its four bytes and drop into place by a shift and a v_bfi / v_and_or: 2 instructions per row and side
+        // instead of 14 for the compact 4-bit form; the x-validity mask is applied once, spread to bytes).  The darker side
+        // is kept inverted ("no darker arc") until the five rows are done
         const unsigned vmask5 = ((vmask * 0x00204081u) & 0x01010101u) * 0x1Fu;
         const unsigned *pC = s_in + (r0 + 3) * 18 + c, *pL = s_in + (r0 + 3) * 18 + cl, *pR = s_in + (r0 + 3) * 18 + cr;
 #pragma unroll
@@ -363,41 +367,52 @@ __global__ __launch_bounds__(FAST_THREADS) void fast_nms_kernel(const uint8_t *_
             const unsigned upl = pL[ro - 36], upc = pC[ro - 36], upr = pR[ro - 36];
             const unsigned dnl = pL[ro + 36], dnc = pC[ro + 36], dnr = pR[ro + 36];
             const unsigned bot = pC[ro + 54], top = pC[ro - 54];
-            unsigned zd[2], zb[2];
+            // thresholds of the row, per byte, from n = ~v: Yd = min(n + thr, 255), Yb = max(n - thr, 0).  The even bytes
+            // (n << 8) and the odd ones (n itself) sit in the HIGH bytes of 16-bit lanes; thr << 8 has an empty low byte, so
+            // whatever is in the low bytes neither carries nor borrows, and the clamps (0xFFFF / 0) are 255 / 0 in the high byte
+            const unsigned n = ~cdw;
+            const ushort2_t ne = __builtin_bit_cast(ushort2_t, n << 8), no = __builtin_bit_cast(ushort2_t, n);
+            const ushort2_t T8 = __builtin_bit_cast(ushort2_t, T0);
+            const unsigned Yd = __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, __builtin_elementwise_add_sat(no, T8)),
+                                                      __builtin_bit_cast(unsigned, __builtin_elementwise_add_sat(ne, T8)), 0x07030501u);
+            const unsigned Yb = __builtin_amdgcn_perm(__builtin_bit_cast(unsigned, __builtin_elementwise_sub_sat(no, T8)),
+                                                      __builtin_bit_cast(unsigned, __builtin_elementwise_sub_sat(ne, T8)), 0x07030501u);
+            // ring values of the four pixels, one byte each: v_alignbyte_b32 shifts the dword pair {hi:lo} right by sh bytes
+            unsigned r[8];
+            r[0] = bot;                                         // ( 0, 3)
+            r[1] = top;                                         // ( 0,-3)
+            r[2] = __builtin_amdgcn_alignbyte(rdw, cdw, 3);     // ( 3, 0)
+            r[3] = __builtin_amdgcn_alignbyte(cdw, ldw, 1);     // (-3, 0)
+            r[4] = __builtin_amdgcn_alignbyte(dnr, dnc, 2);     // ( 2, 2)
+            r[5] = __builtin_amdgcn_alignbyte(upc, upl, 2);     // (-2,-2)
+            r[6] = __builtin_amdgcn_alignbyte(upr, upc, 2);     // ( 2,-2)
+            r[7] = __builtin_amdgcn_alignbyte(dnc, dnl, 2);     // (-2, 2)
+            // v_lerp_u8: per byte (a + b + (c & 1)) >> 1 with a 9-bit sum, so bit 7 is the carry of a + b + (c & 1):
+            //   nd: r + Yd + 1 >= 256  <=>  r >= v - thr  (not darker; always when thr >= v: Yd = 255)
+            //   br: r + Yb     >= 256  <=>  r >  v + thr  (brighter;   never  when v + thr >= 255: Yb = 0)
+            unsigned nd[8], br[8];
 #pragma unroll
-            for (int par = 0; par < 2; ++par) {
-                // v_perm_b32 picks bytes (sh+par, sh+par+2) of {hi:lo} into the low bytes of two 16-bit lanes
-#define PK2(hi, lo, sh) __builtin_bit_cast(short2_t, __builtin_amdgcn_perm((hi), (lo), 0x0c000c00u | (unsigned)((sh) + par) | ((unsigned)((sh) + par + 2) << 16)))
-                const short2_t ce = PK2(0u, cdw, 0);
-                // ring values r (not differences): with d = ce - r,
-                //   min_pairs max(d_a,d_b) = ce - max_pairs min(r_a,r_b),  max_pairs min(d_a,d_b) = ce - min_pairs max(r_a,r_b)
-                short2_t r[8];
-                r[0] = PK2(0u, bot, 0);          // ( 0, 3)
-                r[1] = PK2(0u, top, 0);          // ( 0,-3)
-                r[2] = PK2(rdw, cdw, 3);         // ( 3, 0)
-                r[3] = PK2(cdw, ldw, 1);         // (-3, 0)
-                r[4] = PK2(dnr, dnc, 2);         // ( 2, 2)
-                r[5] = PK2(upc, upl, 2);         // (-2,-2)
-                r[6] = PK2(upr, upc, 2);         // ( 2,-2)
-                r[7] = PK2(dnc, dnl, 2);         // (-2, 2)
-#undef PK2
-                // opposite pairs: (0,1) (2,3) (4,5) (6,7)
-                const short2_t lo = __builtin_elementwise_max(__builtin_elementwise_max(__builtin_elementwise_min(r[0], r[1]), __builtin_elementwise_min(r[2], r[3])),
-                                                              __builtin_elementwise_max(__builtin_elementwise_min(r[4], r[5]), __builtin_elementwise_min(r[6], r[7])));
-                const short2_t hi = __builtin_elementwise_min(__builtin_elementwise_min(__builtin_elementwise_max(r[0], r[1]), __builtin_elementwise_max(r[2], r[3])),
-                                                              __builtin_elementwise_min(__builtin_elementwise_max(r[4], r[5]), __builtin_elementwise_max(r[6], r[7])));
-                // darker arc possible:   ce - lo > thr  <=>  (lo - ce) + thr < 0
-                // brighter arc possible: hi - ce > thr  <=>  (ce - hi) + thr < 0
-                // bit 15 / 31: the side's flag of the even / odd pixel pair
-                zd[par] = __builtin_bit_cast(unsigned, (lo - ce) + __builtin_bit_cast(short2_t, T0));
-                zb[par] = __builtin_bit_cast(unsigned, (ce - hi) + __builtin_bit_cast(short2_t, T0));
+            for (int k = 0; k < 8; ++k) {
+                nd[k] = __builtin_amdgcn_lerp(r[k], Yd, 0xFFFFFFFFu);
+                br[k] = __builtin_amdgcn_lerp(r[k], Yb, 0u);
             }
-            const unsigned xd = __builtin_amdgcn_perm(zd[1], zd[0], 0x07030501u);    // bytes (px0, px1, px2, px3), flag = bit 7
-            const unsigned xb = __builtin_amdgcn_perm(zb[1], zb[0], 0x07030501u);
-            dark_bits |= (xd >> (7 - it)) & (0x01010101u << it);
-            brt_bits |= (xb >> (7 - it)) & (0x01010101u << it);
+            // opposite pairs (0,1) (2,3) (4,5) (6,7), whole dwords, the flags in bit 7 of each byte:
+            //   no darker arc:         some pair with both pixels not darker
+            //   brighter arc possible: every pair holds a brighter pixel
+            // one three-input instruction per further pair (v_and_or_b32 and its dual, v_bitop3_b32 with the truth table
+            // of (a | b) & c): left to itself the compiler balances the chains into five instructions a side instead of four
+            unsigned xnd = nd[0] & nd[1], xb = br[0] | br[1];
+#pragma unroll
+            for (int k = 2; k < 8; k += 2) {
+                xnd = __builtin_amdgcn_bitop3_b32(nd[k], nd[k + 1], xnd, 0xEA);     // (a & b) | c
+                xb = __builtin_amdgcn_bitop3_b32(br[k], br[k + 1], xb, 0xA8);       // (a | b) & c
+            }
+            // drop bit 7 of the four bytes into bits 8 px + it (v_bfi_b32); rows that are skipped keep "no darker arc"
+            const unsigned rowm = 0x01010101u << it;
+            ndark_bits = (ndark_bits & ~rowm) | ((xnd >> (7 - it)) & rowm);
+            brt_bits |= (xb >> (7 - it)) & rowm;
         }
-        dark_bits &= vmask5;
+        dark_bits = ~ndark_bits & vmask5;
         brt_bits &= vmask5;
     }
     {   // one append per tile: wave prefix sum of the per-lane counts (front | back << 16), one LDS atomic per wave.

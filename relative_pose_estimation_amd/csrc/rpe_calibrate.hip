@@ -34,7 +34,7 @@ __global__ __launch_bounds__(256) void valu_calib_kernel(unsigned *sink, int ite
             for (int u = 0; u < 8; ++u) {
                 if (KIND == 0)       // the Hamming inner loop: v_xor_b32 + v_bcnt_u32_b32 (2 instructions)
                     asm volatile("v_xor_b32 %0, %0, %1\n\tv_bcnt_u32_b32 %0, %0, %2" : "+v"(a[u]) : "v"(k0), "v"(k1));
-                else if (KIND == 1)  // FAST pair test: packed 16-bit min / max (2 instructions)
+                else if (KIND == 1)  // packed 16-bit min / max (2 instructions): the FAST pair test before it went to bytes (kind 16)
                     asm volatile("v_pk_min_i16 %0, %0, %1\n\tv_pk_max_i16 %0, %0, %2" : "+v"(a[u]) : "v"(k0), "v"(k1));
                 else if (KIND == 2)  // byte gather: v_perm_b32 (1 instruction)
                     asm volatile("v_perm_b32 %0, %0, %1, %2" : "+v"(a[u]) : "v"(k0), "v"(k1));
@@ -62,8 +62,12 @@ __global__ __launch_bounds__(256) void valu_calib_kernel(unsigned *sink, int ite
                     asm volatile("v_mad_u64_u32 %0, vcc, %1, %2, %0" : "+v"(d[u]) : "v"(k0), "v"(k1) : "vcc");
                 else if (KIND == 14) // SDWA operand select: v_mul_u32_u24_sdwa
                     asm volatile("v_mul_u32_u24_sdwa %0, %0, %1 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_1" : "+v"(a[u]) : "v"(k0));
-                else                 // packed 16-bit multiply-add: v_pk_mad_u16
+                else if (KIND == 15) // packed 16-bit multiply-add: v_pk_mad_u16
                     asm volatile("v_pk_mad_u16 %0, %0, %1, %2" : "+v"(a[u]) : "v"(k0), "v"(k1));
+                else if (KIND == 16) // FAST pair test on four pixels per register: v_lerp_u8 (1 instruction, 4 byte compares)
+                    asm volatile("v_lerp_u8 %0, %0, %1, %2" : "+v"(a[u]) : "v"(k0), "v"(k1));
+                else                 // its pair logic: v_bitop3_b32, (a | b) & c
+                    asm volatile("v_bitop3_b32 %0, %0, %1, %2 bitop3:0xa8" : "+v"(a[u]) : "v"(k0), "v"(k1));
             }
         }
     }
@@ -73,15 +77,16 @@ __global__ __launch_bounds__(256) void valu_calib_kernel(unsigned *sink, int ite
     if (acc == 0x12345679u) *sink = acc;
 }
 
-static const int kCalibInstPerSlot[16] = {2, 2, 1, 1, 2, 1, 2, 1, 1, 1, 1, 1, 1, 1, 1, 1};
-static const char *kCalibNames[16] = {"v_xor_b32+v_bcnt_u32_b32", "v_pk_min_i16+v_pk_max_i16", "v_perm_b32", "v_dot4_u32_u8",
+static const int kCalibInstPerSlot[18] = {2, 2, 1, 1, 2, 1, 2, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1, 1};
+static const char *kCalibNames[18] = {"v_xor_b32+v_bcnt_u32_b32", "v_pk_min_i16+v_pk_max_i16", "v_perm_b32", "v_dot4_u32_u8",
                                       "v_min3_i32+v_max3_i32", "v_mad_u32_u24", "v_mul_f64+v_add_f64", "v_fma_f64", "v_fma_f32", "v_pk_fma_f32",
-                                      "v_dot2_u32_u16", "v_alignbyte_b32", "v_mul_lo_u32", "v_mad_u64_u32", "v_mul_u32_u24_sdwa", "v_pk_mad_u16"};
-extern "C" const char *rpe_calibrate_valu_name(int kind) { return (kind >= 0 && kind < 16) ? kCalibNames[kind] : "?"; }
+                                      "v_dot2_u32_u16", "v_alignbyte_b32", "v_mul_lo_u32", "v_mad_u64_u32", "v_mul_u32_u24_sdwa", "v_pk_mad_u16",
+                                      "v_lerp_u8", "v_bitop3_b32"};
+extern "C" const char *rpe_calibrate_valu_name(int kind) { return (kind >= 0 && kind < 18) ? kCalibNames[kind] : "?"; }
 
 extern "C" int rpe_calibrate_valu(rpe_handle *h, int kind, int waves_per_simd, double *wave_insts_per_s)
 {
-    if (!h || !wave_insts_per_s || kind < 0 || kind > 15 || waves_per_simd < 1 || waves_per_simd > 8) return rpe_invalid(h, "rpe_calibrate_valu");
+    if (!h || !wave_insts_per_s || kind < 0 || kind > 17 || waves_per_simd < 1 || waves_per_simd > 8) return rpe_invalid(h, "rpe_calibrate_valu");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     hipDeviceProp_t prop;
     HIPCHK(h, hipGetDeviceProperties(&prop, h->cfg.device));
@@ -97,7 +102,7 @@ extern "C" int rpe_calibrate_valu(rpe_handle *h, int kind, int waves_per_simd, d
         switch (kind) {
 #define CALIB_CASE(K) case K: hipLaunchKernelGGL((valu_calib_kernel<K>), dim3(blocks), dim3(256), 0, h->stream, h->d_calib_sink, iters); break;
             CALIB_CASE(0) CALIB_CASE(1) CALIB_CASE(2) CALIB_CASE(3) CALIB_CASE(4) CALIB_CASE(5) CALIB_CASE(6) CALIB_CASE(7)
-            CALIB_CASE(8) CALIB_CASE(9) CALIB_CASE(10) CALIB_CASE(11) CALIB_CASE(12) CALIB_CASE(13) CALIB_CASE(14) CALIB_CASE(15)
+            CALIB_CASE(8) CALIB_CASE(9) CALIB_CASE(10) CALIB_CASE(11) CALIB_CASE(12) CALIB_CASE(13) CALIB_CASE(14) CALIB_CASE(15) CALIB_CASE(16) CALIB_CASE(17)
 #undef CALIB_CASE
         }
         HIPCHK(h, hipEventRecord(e1, h->stream));

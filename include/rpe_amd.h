@@ -200,8 +200,8 @@ int rpe_enqueue_stream_device(rpe_handle *h, const uint8_t *d_frames, int F, con
  * extract every frame once.  The store is created on demand and survives every other call on the handle (batch,
  * stream, stage API, refinement); rpe_destroy frees it.  Bytes per slot:
  * (nfeatures + 64) * (descriptor bytes + 8 + N) + 8, descriptor bytes = 32 (ORB) or 128 (SIFT), N = 8 for NORM_L2 handles
- * in crossCheck mode (the only matcher that reads the norm words) and 0 otherwise, nfeatures = RPE_SIFT_UNCAPPED_CAPACITY
- * for uncapped SIFT.
+ * of either match mode (the crossCheck matcher and rpe_guided_matches_l2 read the norm words) and 0 for Hamming handles,
+ * nfeatures = RPE_SIFT_UNCAPPED_CAPACITY for uncapped SIFT.
  * rpe_frames_reserve: n_slots = 0 frees; growing or shrinking keeps the slots below the new size (it waits for the
  * handle's stream) and ends the pair list's claim on rpe_fetch_overflow, which is refused until the next batch, stream or
  * pair list.  RPE_ERR_HIP when the device cannot hold the new store: the old one is kept. */
@@ -394,8 +394,9 @@ int rpe_scale_links(rpe_handle *h, int L, const int32_t *pair_a, const int32_t *
 /* ------------------------------------------------------- guided matching */
 /* Matches of the last batch / stream / pair list again, under the epipolar gate of a pose (guided matching; NOT in the
  * reference, whose only match rule is the brute-force crossCheck): the mutual nearest neighbour among the keypoint
- * pairs that are consistent with (R, t).  Hamming handles only (ORB + RPE_NORM_HAMMING, either match_mode: the guided
- * rule is always the mutual one).
+ * pairs that are consistent with (R, t).  rpe_guided_matches / rpe_match_hamming_guided serve Hamming handles only (ORB +
+ * RPE_NORM_HAMMING); L2 handles have rpe_guided_matches_l2 / rpe_match_l2_guided below, whose distance is an f32 and whose
+ * bound is a double.  Either match_mode of a handle is served: the guided rule is always the mutual one.
  * The rule, for a pair with pose (R, t), images 1 and 2, keypoints i < n1, j < n2 (n = min(count, capacity)); all
  * arithmetic f64, no contraction:
  *  1. x1_i = (x, y) = the f32 keypoint pixel of i normalised with the camera of image 1 as the geometry stages do it
@@ -426,6 +427,27 @@ int rpe_scale_links(rpe_handle *h, int L, const int32_t *pair_a, const int32_t *
  * are host-side; nothing is launched and the handle stays usable after a refusal. */
 int rpe_guided_matches(rpe_handle *h, int B, const double *R, const double *t, double gate_px, int max_distance,
                        int32_t *qidx, int32_t *tidx, int32_t *dist, float *pts1, float *pts2, int32_t *n_matches);
+
+/* The same for RPE_NORM_L2 handles (SIFT, or ORB bytes under L2; either match_mode).  Steps 1 - 4 of the rule above hold
+ * unchanged as far as the gate goes (the normalisation, E, l_k, s1, s2, v, thr2; a comparison with a NaN is false); the
+ * rest reads:
+ *  4'. dist(i, j) is the matcher's own distance: the f32 sqrtf((float)S), S the exact integer sum of squared byte
+ *      differences of the two descriptors (128 bytes for SIFT handles, 32 for ORB handles created with RPE_NORM_L2).
+ *      (i, j) is admissible iff it passes the gate and (double)dist(i, j) <= max_distance.
+ *  5'. NNt(i) = the admissible j with the least (dist, j), compared as f32 and then by index; NNq(j) = the admissible i with
+ *      the least (dist, i); (i, NNt(i)) is a match iff NNq(NNt(i)) == i.  Output: the matches sorted ascending by
+ *      (dist, i), the first max_matches of them.
+ * With no effective gate (gate_px = 1e9, max_distance = +inf) this is the crossCheck result of rpe_match_l2 bit for bit,
+ * and a crossCheck match that is admissible is always a guided match before truncation.
+ * R, t, the run's own poses for R == t == NULL, the cameras and the output shapes are those of rpe_guided_matches; dist is
+ * f32.  Past n_matches[p]: -1 (indices), zero (points), and dist holds all-ones bits (0xFFFFFFFF, a NaN: compare the bits
+ * or slice by n_matches).  The results live in the same buffers of their own, and every fetch of the run returns the same
+ * bits afterwards.  Bit-deterministic.
+ * Validity rules of rpe_guided_matches.  RPE_ERR_INVALID as well: a handle that is not RPE_NORM_L2, gate_px not finite or
+ * <= 0, max_distance NaN or < 0 (+inf is allowed and means no bound), a non-finite entry of R or t, exactly one of R, t
+ * NULL.  All checks are host-side; nothing is launched and the handle stays usable after a refusal. */
+int rpe_guided_matches_l2(rpe_handle *h, int B, const double *R, const double *t, double gate_px, double max_distance,
+                          int32_t *qidx, int32_t *tidx, float *dist, float *pts1, float *pts2, int32_t *n_matches);
 
 /* ------------------------------------------- homography / rotation-only */
 /* A second geometric model over the matches of a pair (NOT in the reference, whose only model is the essential matrix):
@@ -476,7 +498,7 @@ int rpe_guided_matches(rpe_handle *h, int B, const double *R, const double *t, d
  * rpe_pair_homographies: over the first B pairs of the last batch / stream / pair list / *_cameras run.  Validity rules of
  * rpe_fetch_structure: refused after a chunked host batch, a stage call, a put, once the store was resized under a pair
  * list, and for B > pairs of the last run.  The results live in buffers of their own: rpe_fetch_results,
- * rpe_fetch_structure, rpe_refine_poses, rpe_scale_links, rpe_guided_matches and rpe_gather_poses return the same bits
+ * rpe_fetch_structure, rpe_refine_poses, rpe_scale_links, rpe_guided_matches(_l2) and rpe_gather_poses return the same bits
  * afterwards.  rpe_find_homography: stage form over the caller's matches (pts as in rpe_find_essential), one K; goes
  * through the workspace like every stage call.
  * RPE_ERR_INVALID: iters outside 1 .. rpe_config.ransac_max_iters, threshold_px not finite or <= 0.  All checks are
@@ -542,6 +564,16 @@ int64_t rpe_sift_debug_gauss(rpe_handle *h, int index, float *out);
  * integer-valued f32), ORB handles created with NORM_L2 B*cap*32 each.  dist: f32 L2 distances. */
 int rpe_match_l2(rpe_handle *h, const float *h_desc1, const int32_t *n1, const float *h_desc2,
                  const int32_t *n2, int B, int32_t *qidx, int32_t *tidx, float *dist, int32_t *n_matches);
+
+/* stage form of rpe_guided_matches_l2, the sibling of rpe_match_l2: the caller's own features.  desc1 / desc2: byte-valued
+ * f32 as in rpe_match_l2 (the same conversion and refusal), pts1 / pts2: B*cap*2 f32 keypoint pixels, n1 / n2: B counts;
+ * one K; R[B*9], t[B*3] required.  Outputs sized B*max_matches; past n_matches[p] -1 (indices) and all-ones bits (dist).
+ * Goes through the workspace like every stage call (the last run's per-match results end here).  Same argument checks
+ * as rpe_guided_matches_l2. */
+int rpe_match_l2_guided(rpe_handle *h, const float *h_desc1, const float *h_pts1, const int32_t *n1,
+                        const float *h_desc2, const float *h_pts2, const int32_t *n2, int B,
+                        const double K[9], const double *R, const double *t, double gate_px, double max_distance,
+                        int32_t *qidx, int32_t *tidx, float *dist, int32_t *n_matches);
 
 /* replaces cv2.findEssentialMat(pts1, pts2, K, RANSAC, prob, threshold)
  * (pose_estimator.py:522-527).  pts: B*max_matches*2 f32, m[B] counts.

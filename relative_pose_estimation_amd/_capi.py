@@ -53,11 +53,13 @@ _SIGNATURES = {
     "rpe_bgr_to_gray_device": "i:ppzip", "rpe_bgr_to_gray": "i:ppzip", "rpe_lsd_detect": "i:piipip",
     "rpe_fetch_matched_points": "i:pipp", "rpe_fetch_structure": "i:pippp", "rpe_refine_poses": "i:piippppp",
     "rpe_fetch_match_indices": "i:pipp", "rpe_scale_links": "i:pipppippp", "rpe_guided_matches": "i:pippdipppppp",
+    "rpe_guided_matches_l2": "i:pippddpppppp",
     "rpe_pair_homographies": "i:piidppppp", "rpe_find_homography": "i:ppppipidppppp",
     "rpe_orb_detect_and_compute": "i:ppippp", "rpe_orb_debug_fetch": "i:piip", "rpe_orb_pyramid_pixels": "l:p",
     "rpe_orb_debug_retain": "i:piipppiip",
     "rpe_match_hamming": "i:pppppipppp", "rpe_match_hamming_guided": "i:pppppppipppdipppp",
     "rpe_sift_detect_and_compute": "i:ppippp", "rpe_sift_debug_gauss": "l:pip", "rpe_match_l2": "i:pppppipppp",
+    "rpe_match_l2_guided": "i:pppppppipppddpppp",
     "rpe_find_essential": "i:ppppippppp", "rpe_recover_pose": "i:pppppipppp", "rpe_refine_pose_points": "i:pppppppipippppp",
     "rpe_set_profiling": "i:pi", "rpe_get_stage_ms": "i:pp", "rpe_stage_name": "s:i",
     "rpe_comm_unique_id": "i:p", "rpe_comm_create": "i:piipp", "rpe_comm_prepare": "i:piip", "rpe_comm_connect": "i:pp",
@@ -447,6 +449,37 @@ class Engine:
         gate = float(self.cfg.ransac_threshold if gate_px is None else gate_px)
         self._chk(self.lib.rpe_match_hamming_guided(self.h, _p(d1), _p(p1), _p(n1), _p(d2), _p(p2), _p(n2), B, _p(K),
                                                     _opt(Rc), _opt(tc), gate, int(max_distance), _p(q), _p(ti), _p(d), _p(nm)))
+        return q, ti, d, nm
+
+    # the same for NORM_L2 handles (rpe_guided_matches_l2 / rpe_match_l2_guided): f32 distances, a float bound
+    def guided_matches_l2(self, B, R=None, t=None, gate_px=None, max_distance=None):
+        """guided_matches for an L2 handle (SIFT, or ORB bytes under NORM_L2; rpe_guided_matches_l2): dist is the
+        matcher's f32 distance, max_distance a float bound on it (None: no bound).  Returns (qidx, tidx i32[B, mm],
+        dist f32[B, mm], pts1, pts2 f32[B, mm, 2], n_matches i32[B]); past each pair's count -1 / zero and, in dist,
+        all-ones bits (a NaN)."""
+        Rc, tc = self._poses(B, R, t)
+        q, ti, d, nm = self._match_outs(B, np.float32)
+        p1 = np.zeros((B, self.max_matches, 2), np.float32); p2 = np.zeros_like(p1)
+        gate = float(self.cfg.ransac_threshold if gate_px is None else gate_px)
+        bound = float("inf") if max_distance is None else float(max_distance)
+        self._chk(self.lib.rpe_guided_matches_l2(self.h, B, _opt(Rc), _opt(tc), gate, bound,
+                                                 _p(q), _p(ti), _p(d), _p(p1), _p(p2), _p(nm)))
+        return q, ti, d, p1, p2, nm
+
+    def match_l2_guided(self, desc1, pts1, n1, desc2, pts2, n2, K, R, t, gate_px=None, max_distance=None):
+        """Stage form of guided_matches_l2, the sibling of match_l2: per pair the caller's byte-valued descriptors
+        (n, desc_dim) and keypoint pixels (n, 2) f32 of both images, one K, the poses R[B,3,3], t[B,3].  Returns
+        (qidx, tidx, dist f32, n_matches)."""
+        B = len(n1)
+        d1 = self._pack_features(desc1, n1, (self.desc_dim,), np.float32); d2 = self._pack_features(desc2, n2, (self.desc_dim,), np.float32)
+        p1 = self._pack_features(pts1, n1, (2,), np.float32); p2 = self._pack_features(pts2, n2, (2,), np.float32)
+        n1, n2, K = _i32(n1), _i32(n2), _f64(K)
+        Rc, tc = self._poses(B, R, t)
+        q, ti, d, nm = self._match_outs(B, np.float32)
+        gate = float(self.cfg.ransac_threshold if gate_px is None else gate_px)
+        bound = float("inf") if max_distance is None else float(max_distance)
+        self._chk(self.lib.rpe_match_l2_guided(self.h, _p(d1), _p(p1), _p(n1), _p(d2), _p(p2), _p(n2), B, _p(K),
+                                               _opt(Rc), _opt(tc), gate, bound, _p(q), _p(ti), _p(d), _p(nm)))
         return q, ti, d, nm
 
     # ---- homography / rotation-only (rpe_pair_homographies / rpe_find_homography; not in the reference)

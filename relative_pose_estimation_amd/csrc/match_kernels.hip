@@ -710,14 +710,12 @@ __global__ __launch_bounds__(MM_NT) void match_guided_mfma_kernel(const uint8_t 
         [&](int r, int i, unsigned key) { out.put(r, i, s_best[i] & 0x3FFFF, (int)(key >> 16)); });
 }
 
-// Guided matches of run r under the poses d_R / d_t (d_status: the run's own poses, pairs that are not OK are skipped; nullptr:
-// every pair) into the d_gm_* buffers.  The election words of the HBM form are the crossCheck matcher's d_hm_*, scratch of one
-// launch sequence there as here.
-void rpe_launch_guided(rpe_handle *h, const RpeRun &r, const double *d_R, const double *d_t, const int *d_status, double gate_px, int max_distance)
+// What both norms' guided launchers open with: the d_gm_* lists cleared and the records of the run under the poses
+static void launch_guided_records(rpe_handle *h, const RpeRun &r, const double *d_R, const double *d_t, const int *d_status, double gate_px)
 {
     const int kcap = h->lay.kcap, B = r.pairs, mm = h->cfg.max_matches;
     const RpeFeatSrc &f = r.feat;
-    // -1 / zero past n_matches
+    // -1 / zero past n_matches (an L2 distance of all-ones bits)
     hipMemsetAsync(h->d_gm_q, 0xFF, sizeof(int) * (size_t)B * mm, h->stream);
     hipMemsetAsync(h->d_gm_t, 0xFF, sizeof(int) * (size_t)B * mm, h->stream);
     hipMemsetAsync(h->d_gm_d, 0xFF, sizeof(int) * (size_t)B * mm, h->stream);
@@ -729,6 +727,15 @@ void rpe_launch_guided(rpe_handle *h, const RpeRun &r, const double *d_R, const 
     hipLaunchKernelGGL(records, dim3((kcap + 255) / 256, 2, B), dim3(256), 0, h->stream,
                        f.count, f.pt, f.img2_base, f.tab, kcap, (const double *)h->d_K, r.cam, d_R, d_t, d_status, gate_px,
                        h->d_gm_rec, h->d_gm_thr2);
+}
+
+// Guided matches of run r under the poses d_R / d_t (d_status: the run's own poses, pairs that are not OK are skipped; nullptr:
+// every pair) into the d_gm_* buffers.  The election words of the HBM form are the crossCheck matcher's d_hm_*, scratch of one
+// launch sequence there as here.
+void rpe_launch_guided(rpe_handle *h, const RpeRun &r, const double *d_R, const double *d_t, const int *d_status, double gate_px, int max_distance)
+{
+    const int kcap = h->lay.kcap, B = r.pairs;
+    launch_guided_records(h, r, d_R, d_t, d_status, gate_px);
     // the crossCheck matcher's plan with 2 KB of scanned records in the first LDS region; the row words are final: no raw_desc
     const RpeHammingPlan p = rpe_hamming_plan(kcap, B, RPE_GUIDED_LDS_UINT4);
     launch_hamming_plan(h, r, p, match_guided_mfma_kernel<true, true>, match_guided_mfma_kernel<true, false>,
@@ -988,6 +995,150 @@ __global__ __launch_bounds__(256) void match_l2_mfma_kernel(const uint8_t *__res
     }
 }
 
+// The tile loop of match_l2_mfma_kernel (same grid, B operand, A tiles, ring and e = (acc << 1) + qn epilogue) with the gate of
+// guided matching (include/rpe_amd.h, rpe_guided_matches_l2) in the exact branch: a kernel family of its own, as
+// match_guided_mfma_kernel is beside the Hamming tile kernel.  The records are guided_records_kernel's.  The owner lane
+// keeps its 32-byte record in registers; the 32 records of a scanned tile travel with the tile: 64 16-byte pieces fetched
+// L2M_PF tiles ahead by wave 3, staged in 2 KB of LDS beside s_qn and read only by an entry that reaches the gate.  An
+// entry reaches it when it passes e <= best_e + 2 and beats (best_g, best_idx) in the f32 (distance, index) order; best_e,
+// best_g and best_idx move on admissible entries only, so the + 2 allowance is relative to the best admissible entry so
+// far and the result is the minimum over the admissible entries whatever the order of the tiles.  Rows past the end carry
+// NaN records and an e above every allowance; a lane without an owner starts from a best_e below every e and never enters
+// the branch.  A pair whose thr2 is NaN is not matched.  max_distance is applied to the column's elected key: the
+// nearest admissible neighbour is beyond it exactly when every admissible one is.
+template <int KS, bool TAB>
+__global__ __launch_bounds__(256) void match_l2_guided_mfma_kernel(const uint8_t *__restrict__ desc, const int2 *__restrict__ norms,
+                                                                    const int *__restrict__ kp_count, int img2_base, const int2 *__restrict__ pair_tab, int kcap,
+                                                                    const double4 *__restrict__ g_rec, const double *__restrict__ g_thr2, double max_distance,
+                                                                    unsigned long long *__restrict__ nn_t, unsigned long long *__restrict__ nn_q)
+{
+    constexpr int DIM = KS * 32;
+    __shared__ v4i_t s_a[2][KS][64];
+    __shared__ __attribute__((aligned(16))) int s_qn[2][32];
+    __shared__ double2 s_rec[2][64];                          // [buf][2 row + half]
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6, h = lane >> 5, col = lane & 31;
+    const int pair = blockIdx.z >> 1, pass = blockIdx.z & 1;
+    int img1, img2;
+    rpe_pair_slots<TAB>(pair_tab, img2_base, pair, img1, img2);
+    const double thr2 = g_thr2[pair];
+    if (thr2 != thr2) return;                                  // NaN: the pair is not matched
+    const int n1 = min(kp_count[img1], kcap), n2 = min(kp_count[img2], kcap);
+    // pass 0: the queries own the columns and find their nearest admissible train (NNt); pass 1: the trains find their query
+    const int img_own = pass ? img2 : img1, img_scan = pass ? img1 : img2;
+    const int n_own = pass ? n2 : n1, n_scan = pass ? n1 : n2;
+    if (blockIdx.x * 128 >= n_own || n_scan <= 0) return;
+    const int ntq = (n_scan + 31) >> 5;
+    const int per = (ntq + (int)gridDim.y - 1) / (int)gridDim.y;
+    const int qt_lo = (int)blockIdx.y * per, qt_hi = min(ntq, qt_lo + per);
+    if (qt_lo >= qt_hi) return;
+    const uint4 *d_own = (const uint4 *)(desc + (long long)img_own * kcap * DIM);
+    const uint4 *d_scan = (const uint4 *)(desc + (long long)img_scan * kcap * DIM);
+    const int2 *nrm_scan = norms + (long long)img_scan * kcap;
+    // records: side 0 the queries' (l_0, l_1, l_2, s1), side 1 the trains' (x2, y2, s2, 0)
+    const double4 *rec_own = g_rec + ((long long)pair * 2 + pass) * kcap;
+    const double2 *rec_scan = (const double2 *)(g_rec + ((long long)pair * 2 + (pass ^ 1)) * kcap);
+    const int j = (blockIdx.x * 4 + wv) * 32 + col;
+    const bool valid_own = j < n_own;
+    v4i_t bop[KS];
+#pragma unroll
+    for (int sK = 0; sK < KS; ++sK) {
+        uint4 t = make_uint4(0x7F7F7F7Fu, 0x7F7F7F7Fu, 0x7F7F7F7Fu, 0x7F7F7F7Fu);
+        if (valid_own) t = d_own[(long long)j * (DIM / 16) + 2 * sK + h];
+        bop[sK].x = (int)(t.x ^ 0x7F7F7F7Fu); bop[sK].y = (int)(t.y ^ 0x7F7F7F7Fu); bop[sK].z = (int)(t.z ^ 0x7F7F7F7Fu); bop[sK].w = (int)(t.w ^ 0x7F7F7F7Fu);
+    }
+    const int tn = valid_own ? norms[(long long)img_own * kcap + j].x : 0;
+    const double qnan = __builtin_nan("");
+    const double4 own = valid_own ? rec_own[j] : make_double4(qnan, qnan, qnan, qnan);
+    const int xs = tid >> 6, xrow = lane & 31, xh = lane >> 5;
+    const bool loader = xs < KS;
+    const bool rec_loader = wv == 3;                           // piece (row lane >> 1, half lane & 1) of a tile's 32 records
+    auto fetch = [&](int qt) -> uint4 {
+        const int q = qt * 32 + xrow;
+        return (loader && qt < qt_hi && q < n_scan) ? d_scan[(long long)q * (DIM / 16) + 2 * xs + xh] : make_uint4(0x80808080u, 0x80808080u, 0x80808080u, 0x80808080u);
+    };
+    auto fetch_n = [&](int qt) -> int {
+        const int q = qt * 32 + tid;
+        return (tid < 32 && qt < qt_hi && q < n_scan) ? nrm_scan[q].y : 0x3FFFFFFF;     // rows past the end never win
+    };
+    auto fetch_rec = [&](int qt) -> double2 {
+        const int q = qt * 32 + (lane >> 1);
+        return (rec_loader && qt < qt_hi && q < n_scan) ? rec_scan[(long long)q * 2 + (lane & 1)] : make_double2(qnan, qnan);
+    };
+    auto stage = [&](int buf, const uint4 &raw, int qn, const double2 &rr) {
+        if (loader) {
+            v4i_t v; v.x = (int)(raw.x ^ 0x80808080u); v.y = (int)(raw.y ^ 0x80808080u); v.z = (int)(raw.z ^ 0x80808080u); v.w = (int)(raw.w ^ 0x80808080u);
+            s_a[buf][xs][lane] = v;
+        }
+        if (tid < 32) s_qn[buf][tid] = qn;
+        if (rec_loader) s_rec[buf][lane] = rr;
+    };
+    uint4 ring[L2M_PF]; int ring_n[L2M_PF]; double2 ring_rec[L2M_PF];
+#pragma unroll
+    for (int u = 0; u < L2M_PF; ++u) { ring[u] = fetch(qt_lo + u); ring_n[u] = fetch_n(qt_lo + u); ring_rec[u] = fetch_rec(qt_lo + u); }
+    stage(0, ring[0], ring_n[0], ring_rec[0]);
+    ring[0] = fetch(qt_lo + L2M_PF); ring_n[0] = fetch_n(qt_lo + L2M_PF); ring_rec[0] = fetch_rec(qt_lo + L2M_PF);
+    __syncthreads();
+    int best_e = valid_own ? 0x3FFFFFF0 : -0x40000000, best_idx = 0x7FFFFFFF;
+    float best_g = __builtin_inff();
+    for (int qt0 = qt_lo; qt0 < qt_hi; qt0 += L2M_PF) {
+#pragma unroll
+        for (int u = 0; u < L2M_PF; ++u) {
+            const int qt = qt0 + u;
+            if (qt < qt_hi) {                                  // workgroup-uniform
+                const int buf = (qt - qt_lo) & 1;
+                v16i_t acc = {0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};
+#pragma unroll
+                for (int sK = 0; sK < KS; ++sK)
+                    acc = __builtin_amdgcn_mfma_i32_32x32x32_i8(s_a[buf][sK][lane], bop[sK], acc, 0, 0, 0);
+                // C layout: column = lane & 31, row of register r = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
+                int e[16];
+#pragma unroll
+                for (int g4 = 0; g4 < 4; ++g4) {
+                    const v4i_t qn4 = *(const v4i_t *)&s_qn[buf][8 * g4 + 4 * h];
+                    e[4 * g4 + 0] = (acc[4 * g4 + 0] << 1) + qn4.x; e[4 * g4 + 1] = (acc[4 * g4 + 1] << 1) + qn4.y;
+                    e[4 * g4 + 2] = (acc[4 * g4 + 2] << 1) + qn4.z; e[4 * g4 + 3] = (acc[4 * g4 + 3] << 1) + qn4.w;
+                }
+                int tmin = e[0];
+#pragma unroll
+                for (int r = 1; r < 16; ++r) tmin = min(tmin, e[r]);
+                if (__any(tmin <= best_e + 2)) {
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        if (e[r] <= best_e + 2) {
+                            const float g = sqrtf((float)(e[r] + tn));
+                            const int row = (r & 3) + 8 * (r >> 2) + 4 * h, idx = qt * 32 + row;
+                            if (g < best_g || (g == best_g && idx < best_idx)) {
+                                const double2 ra = s_rec[buf][2 * row], rb = s_rec[buf][2 * row + 1];
+                                // v from the query's line in both passes; s1 + s2 in that order
+                                double v, ss;
+                                if (pass == 0) { v = (own.x * ra.x + own.y * ra.y) + own.z; ss = own.w + rb.x; }
+                                else           { v = (ra.x * own.x + ra.y * own.y) + rb.x; ss = rb.y + own.z; }
+                                if (v * v <= thr2 * ss) { best_g = g; best_idx = idx; best_e = e[r]; }
+                            }
+                        }
+                    }
+                }
+                if (qt + 1 < qt_hi) {
+                    stage(buf ^ 1, ring[(u + 1) % L2M_PF], ring_n[(u + 1) % L2M_PF], ring_rec[(u + 1) % L2M_PF]);
+                    ring[(u + 1) % L2M_PF] = fetch(qt + 1 + L2M_PF); ring_n[(u + 1) % L2M_PF] = fetch_n(qt + 1 + L2M_PF);
+                    ring_rec[(u + 1) % L2M_PF] = fetch_rec(qt + 1 + L2M_PF);
+                }
+                __syncthreads();
+            }
+        }
+    }
+    // the two half-waves hold the same columns (different rows)
+    {
+        const float og = __shfl_xor(best_g, 32); const int oi = __shfl_xor(best_idx, 32);
+        if (og < best_g || (og == best_g && oi < best_idx)) { best_g = og; best_idx = oi; }
+    }
+    // a column without an admissible entry within max_distance publishes nothing
+    if (valid_own && h == 0 && best_idx != 0x7FFFFFFF && (double)best_g <= max_distance) {
+        unsigned long long *out = (pass ? nn_q : nn_t) + (long long)pair * kcap + j;
+        atomicMin(out, ((unsigned long long)__float_as_uint(best_g) << 18) | (unsigned long long)best_idx);
+    }
+}
+
 // Kernel 2: workgroup = pair: stable sort of the (distance, queryIdx) keys of the surviving matches, first max_matches,
 // point gather.  nn_t[i] = query i's nearest train; nn_q (crossCheck only, nullptr for the ratio mode) = train j's
 // nearest query: the match survives iff nn_q[nn_t[i]] names i
@@ -1012,6 +1163,31 @@ __global__ __launch_bounds__(256) void match_l2_select_kernel(const unsigned lon
             return b != ~0ull && (!nq || (int)(nq[b & 0x3FFFF] & 0x3FFFF) == i) ? ((b >> 18) << 16) | (unsigned long long)i : ~0ull;
         },
         [&](int r, int i, unsigned long long key) { out.put(r, i, (int)(bp[i] & 0x3FFFF), __uint_as_float((unsigned)(key >> 16))); });
+}
+
+// The launch of match_l2_select_kernel over the words in d_m_best2 (and nn_q, see there) into the lists o (o.d holds f32)
+static void launch_l2_select(rpe_handle *h, const RpeRun &r, const unsigned long long *nn_q, const MatchBufs &o)
+{
+    const int kcap = h->lay.kcap;
+    const RpeFeatSrc &f = r.feat;
+    int sortP = 64;
+    while (sortP < kcap) sortP <<= 1;
+    if (sizeof(unsigned long long) * (size_t)sortP > 65536)   // more than 8128 keypoints per image: up to 128 KB of the CU's 160 KB
+        hipFuncSetAttribute(f.tab ? (const void *)match_l2_select_kernel<true> : (const void *)match_l2_select_kernel<false>,
+                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(unsigned long long) * (size_t)sortP));
+    launch_tab(f.tab, match_l2_select_kernel<true>, match_l2_select_kernel<false>, dim3(r.pairs), dim3(256), sizeof(unsigned long long) * (size_t)sortP, h->stream,
+                       (const unsigned long long *)h->d_m_best2, nn_q, f.count, f.pt, f.img2_base, f.tab, kcap, h->cfg.max_matches,
+                       o.q, o.t, (float *)o.d, o.n, o.p1, o.p2);
+}
+
+// The split of the matrix-core L2 tile kernels for B pairs: owner chunks of 128, the scanned tiles dealt over gridDim.y
+// workgroups until ~1024 workgroups are in flight (a single pair included), blockIdx.z = 2 pair + pass
+static dim3 l2_mfma_grid(int kcap, int B)
+{
+    const int chunks = (kcap + 127) / 128;
+    int split = (1024 + chunks * 2 * B - 1) / (chunks * 2 * B);
+    split = split < 1 ? 1 : split > 8 ? 8 : split;
+    return dim3(chunks, split, 2 * B);
 }
 
 // { |u|^2, |u|^2 + 2 sum(u) } of the descriptors of workspace images [0, n_img): once per batch / stream, and once per
@@ -1044,21 +1220,33 @@ void rpe_launch_match_l2(rpe_handle *h, const RpeRun &r)
     } else {
         // images [0, B) and [img2_base, img2_base + B) (a stream: B + 1 frames); the frame store holds its slots' words already
         if (!f.tab) rpe_launch_l2_norms(h, img2_base + B);
-        // scanned tiles dealt over `split` workgroups until ~1024 workgroups are in flight (a single pair included)
-        const int chunks = (kcap + 127) / 128;
-        int split = (1024 + chunks * 2 * B - 1) / (chunks * 2 * B);
-        split = split < 1 ? 1 : split > 8 ? 8 : split;
-        const dim3 grid(chunks, split, 2 * B);
+        const dim3 grid = l2_mfma_grid(kcap, B);
         if (sift) launch_tab(f.tab, match_l2_mfma_kernel<4, true>, match_l2_mfma_kernel<4, false>, grid, dim3(256), 0, h->stream, f.desc, f.norm, f.count, img2_base, f.tab, kcap, h->d_m_best2, h->d_m_best);
         else      launch_tab(f.tab, match_l2_mfma_kernel<1, true>, match_l2_mfma_kernel<1, false>, grid, dim3(256), 0, h->stream, f.desc, f.norm, f.count, img2_base, f.tab, kcap, h->d_m_best2, h->d_m_best);
     }
-    int sortP = 64;
-    while (sortP < kcap) sortP <<= 1;
-    if (sizeof(unsigned long long) * (size_t)sortP > 65536)   // more than 8128 keypoints per image: up to 128 KB of the CU's 160 KB
-        hipFuncSetAttribute(f.tab ? (const void *)match_l2_select_kernel<true> : (const void *)match_l2_select_kernel<false>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(unsigned long long) * (size_t)sortP));
-    launch_tab(f.tab, match_l2_select_kernel<true>, match_l2_select_kernel<false>, dim3(B), dim3(256), sizeof(unsigned long long) * (size_t)sortP, h->stream,
-                       (const unsigned long long *)h->d_m_best2, rt ? (const unsigned long long *)nullptr : (const unsigned long long *)h->d_m_best,
-                       f.count, f.pt, img2_base, f.tab, kcap, h->cfg.max_matches,
-                       h->d_m_q, h->d_m_t, (float *)h->d_m_d, h->d_m_n, h->d_pts1, h->d_pts2);
+    launch_l2_select(h, r, rt ? (const unsigned long long *)nullptr : (const unsigned long long *)h->d_m_best,
+                     MatchBufs{h->d_m_q, h->d_m_t, h->d_m_d, h->d_m_n, h->d_pts1, h->d_pts2});
+}
+
+// Guided matches of run r for an L2 handle, into the d_gm_* buffers (d_gm_d read as f32); poses and d_status as in
+// rpe_launch_guided.  Served for both match modes: the guided rule is the mutual one, and the matrix-core form needs the norm
+// words, which a ratio-mode or RPE_MATCH_VALU run of the workspace never wrote (the kernel is idempotent and O(N); the frame
+// store of every NORM_L2 handle, ratio mode included, holds its slots' words from the put).  d_m_best2 / d_m_best are scratch of one matcher launch sequence -- nothing reads
+// them after rpe_launch_match_l2's select -- and serve as the guided NNt / NNq words here.
+void rpe_launch_guided_l2(rpe_handle *h, const RpeRun &r, const double *d_R, const double *d_t, const int *d_status, double gate_px, double max_distance)
+{
+    const int kcap = h->lay.kcap, B = r.pairs;
+    const RpeFeatSrc &f = r.feat;
+    launch_guided_records(h, r, d_R, d_t, d_status, gate_px);
+    if (!f.tab) rpe_launch_l2_norms(h, f.img2_base + B);
+    hipMemsetAsync(h->d_m_best2, 0xFF, sizeof(unsigned long long) * (size_t)B * kcap, h->stream);
+    hipMemsetAsync(h->d_m_best, 0xFF, sizeof(unsigned long long) * (size_t)B * kcap, h->stream);
+    const dim3 grid = l2_mfma_grid(kcap, B);
+    if (h->desc_bytes == 128)
+        launch_tab(f.tab, match_l2_guided_mfma_kernel<4, true>, match_l2_guided_mfma_kernel<4, false>, grid, dim3(256), 0, h->stream,
+                   f.desc, f.norm, f.count, f.img2_base, f.tab, kcap, (const double4 *)h->d_gm_rec, (const double *)h->d_gm_thr2, max_distance, h->d_m_best2, h->d_m_best);
+    else
+        launch_tab(f.tab, match_l2_guided_mfma_kernel<1, true>, match_l2_guided_mfma_kernel<1, false>, grid, dim3(256), 0, h->stream,
+                   f.desc, f.norm, f.count, f.img2_base, f.tab, kcap, (const double4 *)h->d_gm_rec, (const double *)h->d_gm_thr2, max_distance, h->d_m_best2, h->d_m_best);
+    launch_l2_select(h, r, (const unsigned long long *)h->d_m_best, MatchBufs{h->d_gm_q, h->d_gm_t, h->d_gm_d, h->d_gm_n, h->d_gm_pts1, h->d_gm_pts2});
 }

@@ -29,6 +29,26 @@ static int check_desc_counts(rpe_handle *h, const int32_t *n, int B)
     for (int i = 0; i < B; ++i) if (n[i] < 0 || n[i] > h->lay.kcap) { h->err = "descriptor count exceeds keypoint capacity"; return RPE_ERR_INVALID; }
     return RPE_OK;
 }
+// The byte-valued f32 descriptors of the L2 stage calls as the workspace holds them: u8 rows, the B sets of side 1 and then
+// those of side 2, each of keypoint capacity; the counts are checked on the way
+static int l2_desc_bytes(rpe_handle *h, const float *h_desc1, const int32_t *n1, const float *h_desc2, const int32_t *n2, int B, std::vector<uint8_t> &u)
+{
+    const size_t dim = (size_t)h->desc_bytes;               // 128 (SIFT) or 32 (ORB descriptors under NORM_L2)
+    const size_t per = (size_t)h->lay.kcap * dim;
+    u.assign(2 * per * B, 0);
+    for (int s = 0; s < 2; ++s) {
+        const float *src = s ? h_desc2 : h_desc1; const int32_t *cn = s ? n2 : n1;
+        for (int i = 0; i < B; ++i) {
+            if (int rc = check_desc_counts(h, cn + i, 1)) return rc;
+            for (size_t e = 0; e < (size_t)cn[i] * dim; ++e) {
+                float v = src[(size_t)i * per + e];
+                if (!(v >= 0.f && v <= 255.f) || v != (float)(int)v) { h->err = "NORM_L2 path expects byte-valued descriptors (SIFT's integer-valued 0..255 floats, or ORB bytes)"; return RPE_ERR_INVALID; }
+                u[(size_t)s * per * B + (size_t)i * per + e] = (uint8_t)v;
+            }
+        }
+    }
+    return RPE_OK;
+}
 static int check_match_counts(rpe_handle *h, const int32_t *m, int B)
 {
     for (int i = 0; i < B; ++i) if (m[i] < 0 || m[i] > h->cfg.max_matches) { h->err = "match count exceeds max_matches"; return RPE_ERR_INVALID; }
@@ -338,6 +358,7 @@ static int alloc_workspace(rpe_handle *h)
     DM(h, h->d_ovf, NI);
     HIPCHK(h, hipMemset(h->d_ovf, 0, NI * sizeof(unsigned)));
     DM(h, h->d_desc, NI * L.kcap * h->desc_bytes);
+    HIPCHK(h, hipMemset(h->d_desc, 0, NI * L.kcap * h->desc_bytes));      // rpe_orb_detect_and_compute / rpe_sift_detect_and_compute copy whole rows of keypoint capacity out: rows no extraction ever wrote read as zero, not as what the allocator kept
     HIPCHK(h, hipMemset(h->d_kp_pt, 0, NI * L.kcap * sizeof(float2)));
     HIPCHK(h, hipMemset(h->d_kp_count, 0, NI * sizeof(int)));
     DM(h, h->d_m_q, B * mm); DM(h, h->d_m_t, B * mm); DM(h, h->d_m_d, B * mm);
@@ -650,7 +671,7 @@ static int last_run_structure(rpe_handle *h, int B, bool always)
 // | rpe_fetch_matched_points, rpe_fetch_match_indices     | yes                   | no             | no                         | no                                    |
 // | rpe_fetch_structure, rpe_refine_poses                 | yes                   | yes            | yes                        | no                                    |
 // | rpe_scale_links                                       | yes                   | yes            | no (checks its links' own) | yes, n = the run's pairs              |
-// | rpe_guided_matches, rpe_pair_homographies             | yes                   | yes            | yes                        | yes, n = B                            |
+// | rpe_guided_matches(_l2), rpe_pair_homographies        | yes                   | yes            | yes                        | yes, n = B                            |
 //
 // Tested in this order, so a state gives one message whatever the call.  Two tests stay with their only caller:
 // rpe_scale_links' "the pairs of a batch share no frame" and rpe_fetch_overflow's slot range.
@@ -1067,14 +1088,23 @@ extern "C" int rpe_refine_poses(rpe_handle *h, int B, int max_iters, double *R, 
 }
 
 // ---------------------------------------------------------------- guided matching
-// rpe_guided_matches / rpe_match_hamming_guided (NOT in the reference): the mutual-nearest-neighbour match again, among the
-// keypoint pairs that pass the Sampson gate of a pose.  Results go to the d_gm_* buffers; nothing of the run is written.
-static int guided_check(rpe_handle *h, const char *who, int B, const double *R, const double *t, double gate_px, int max_distance)
+// rpe_guided_matches / rpe_match_hamming_guided and their L2 forms rpe_guided_matches_l2 / rpe_match_l2_guided (NOT in the
+// reference): the mutual-nearest-neighbour match again, among the keypoint pairs that pass the Sampson gate of a pose.
+// Results go to the d_gm_* buffers (d_gm_d: int32 Hamming or f32 L2 distances); nothing of the run's results is written.
+// norm: the norm the entry point serves; max_distance: an integer 0 ... 256 for Hamming, >= 0 or +inf for L2.
+static int guided_check(rpe_handle *h, const char *who, int norm, int B, const double *R, const double *t, double gate_px, double max_distance)
 {
     const std::string w(who);
-    if (h->cfg.norm_type != RPE_NORM_HAMMING) { h->err = w + ": Hamming handles only (ORB with RPE_NORM_HAMMING)"; return RPE_ERR_INVALID; }
+    const bool l2 = norm == RPE_NORM_L2;
+    if (h->cfg.norm_type != norm) {
+        h->err = w + (l2 ? ": L2 handles only (RPE_NORM_L2: SIFT, or ORB bytes under L2)" : ": Hamming handles only (ORB with RPE_NORM_HAMMING)");
+        return RPE_ERR_INVALID;
+    }
     if (!std::isfinite(gate_px) || !(gate_px > 0.)) { h->err = w + ": gate_px must be finite and > 0"; return RPE_ERR_INVALID; }
-    if (max_distance < 0 || max_distance > 256) { h->err = w + ": max_distance must be 0 ... 256"; return RPE_ERR_INVALID; }
+    if (l2 ? !(max_distance >= 0.) : (max_distance < 0 || max_distance > 256)) {
+        h->err = w + (l2 ? ": max_distance must be >= 0 (+inf: no bound)" : ": max_distance must be 0 ... 256");
+        return RPE_ERR_INVALID;
+    }
     if ((R == nullptr) != (t == nullptr)) { h->err = w + ": R and t must both be given or both be NULL"; return RPE_ERR_INVALID; }
     if (R) {
         bool fin = true;
@@ -1096,34 +1126,64 @@ static int guided_alloc(rpe_handle *h)
 }
 
 // poses up (R == nullptr: the run's own, and its status words), launch, fetch
-static int guided_run(rpe_handle *h, const RpeRun &r, const double *R, const double *t, double gate_px, int max_distance,
-                      int32_t *qidx, int32_t *tidx, int32_t *dist, float *pts1, float *pts2, int32_t *n_matches)
+static int guided_run(rpe_handle *h, const RpeRun &r, const double *R, const double *t, double gate_px, double max_distance,
+                      int32_t *qidx, int32_t *tidx, void *dist, float *pts1, float *pts2, int32_t *n_matches)
 {
     const size_t B = (size_t)r.pairs, n = B * h->cfg.max_matches;
     if (R) {
         HIPCHK(h, hipMemcpyAsync(h->d_gm_R, R, sizeof(double) * 9 * B, hipMemcpyHostToDevice, h->stream));
         HIPCHK(h, hipMemcpyAsync(h->d_gm_tr, t, sizeof(double) * 3 * B, hipMemcpyHostToDevice, h->stream));
     }
-    rpe_launch_guided(h, r, R ? h->d_gm_R : h->d_R, R ? h->d_gm_tr : h->d_t, R ? (const int *)nullptr : (const int *)h->d_status, gate_px, max_distance);
+    const double *d_R = R ? h->d_gm_R : h->d_R, *d_t = R ? h->d_gm_tr : h->d_t;
+    const int *d_status = R ? (const int *)nullptr : (const int *)h->d_status;
+    if (h->cfg.norm_type == RPE_NORM_L2) rpe_launch_guided_l2(h, r, d_R, d_t, d_status, gate_px, max_distance);
+    else rpe_launch_guided(h, r, d_R, d_t, d_status, gate_px, (int)max_distance);
     HIPCHK(h, hipGetLastError());
     // the wait also covers the upload: the poses have left the caller's arrays
     return fetch(h, {{qidx, h->d_gm_q, sizeof(int) * n}, {tidx, h->d_gm_t, sizeof(int) * n}, {dist, h->d_gm_d, sizeof(int) * n},
                      {pts1, h->d_gm_pts1, sizeof(float2) * n}, {pts2, h->d_gm_pts2, sizeof(float2) * n}, {n_matches, h->d_gm_n, sizeof(int) * B}});
 }
 
-extern "C" int rpe_guided_matches(rpe_handle *h, int B, const double *R, const double *t, double gate_px, int max_distance,
-                                  int32_t *qidx, int32_t *tidx, int32_t *dist, float *pts1, float *pts2, int32_t *n_matches)
+// the run form of either norm: over the first B pairs of the last run
+static int guided_last_run(rpe_handle *h, const char *who, int norm, int B, const double *R, const double *t, double gate_px, double max_distance,
+                           int32_t *qidx, int32_t *tidx, void *dist, float *pts1, float *pts2, int32_t *n_matches)
 {
-    if (!h || B < 1 || B > h->cfg.max_batch) return rpe_invalid(h, "rpe_guided_matches");
-    int rc = guided_check(h, "rpe_guided_matches", B, R, t, gate_px, max_distance);
+    int rc = guided_check(h, who, norm, B, R, t, gate_px, max_distance);
     if (rc) return rc;
     // the features of the run must still be where it read them (a stage call or a put overwrote the workspace's) and, under
     // the run's own poses, d_R / d_t / d_status its results
-    rc = last_run_gate(h, "rpe_guided_matches", B, NEED_UNCHUNKED | NEED_PER_MATCH | NEED_COUNT | NEED_TABLE);
+    rc = last_run_gate(h, who, B, NEED_UNCHUNKED | NEED_PER_MATCH | NEED_COUNT | NEED_TABLE);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if ((rc = guided_alloc(h)) != RPE_OK) return rc;
     return guided_run(h, last_run_first(h, B), R, t, gate_px, max_distance, qidx, tidx, dist, pts1, pts2, n_matches);
+}
+
+extern "C" int rpe_guided_matches(rpe_handle *h, int B, const double *R, const double *t, double gate_px, int max_distance,
+                                  int32_t *qidx, int32_t *tidx, int32_t *dist, float *pts1, float *pts2, int32_t *n_matches)
+{
+    if (!h || B < 1 || B > h->cfg.max_batch) return rpe_invalid(h, "rpe_guided_matches");
+    return guided_last_run(h, "rpe_guided_matches", RPE_NORM_HAMMING, B, R, t, gate_px, max_distance, qidx, tidx, dist, pts1, pts2, n_matches);
+}
+
+extern "C" int rpe_guided_matches_l2(rpe_handle *h, int B, const double *R, const double *t, double gate_px, double max_distance,
+                                     int32_t *qidx, int32_t *tidx, float *dist, float *pts1, float *pts2, int32_t *n_matches)
+{
+    if (!h || B < 1 || B > h->cfg.max_batch) return rpe_invalid(h, "rpe_guided_matches_l2");
+    return guided_last_run(h, "rpe_guided_matches_l2", RPE_NORM_L2, B, R, t, gate_px, max_distance, qidx, tidx, dist, pts1, pts2, n_matches);
+}
+
+// tail of the stage forms (descriptors of pair p uploaded to workspace slots p and B + p): points, counts, match, fetch
+static int guided_stage_run(rpe_handle *h, const float *h_pts1, const int32_t *n1, const float *h_pts2, const int32_t *n2, int B,
+                            const double *R, const double *t, double gate_px, double max_distance,
+                            int32_t *qidx, int32_t *tidx, void *dist, int32_t *n_matches)
+{
+    const size_t kcap = (size_t)h->lay.kcap;
+    HIPCHK(h, hipMemcpyAsync(h->d_kp_pt, h_pts1, sizeof(float2) * kcap * B, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_kp_pt + kcap * B, h_pts2, sizeof(float2) * kcap * B, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_kp_count, n1, sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_kp_count + B, n2, sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
+    return guided_run(h, rpe_run_batch(h, B), R, t, gate_px, max_distance, qidx, tidx, dist, nullptr, nullptr, n_matches);
 }
 
 extern "C" int rpe_match_hamming_guided(rpe_handle *h, const uint8_t *h_desc1, const float *h_pts1, const int32_t *n1,
@@ -1133,7 +1193,7 @@ extern "C" int rpe_match_hamming_guided(rpe_handle *h, const uint8_t *h_desc1, c
 {
     if (!h || !h_desc1 || !h_pts1 || !n1 || !h_desc2 || !h_pts2 || !n2 || !K || !R || !t || B < 1) return rpe_invalid(h, "rpe_match_hamming_guided");
     if (int rc = check_batch(h, B)) return rc;
-    int rc = guided_check(h, "rpe_match_hamming_guided", B, R, t, gate_px, max_distance);
+    int rc = guided_check(h, "rpe_match_hamming_guided", RPE_NORM_HAMMING, B, R, t, gate_px, max_distance);
     if (rc) return rc;
     const size_t kcap = (size_t)h->lay.kcap;
     if ((rc = check_desc_counts(h, n1, B)) != RPE_OK || (rc = check_desc_counts(h, n2, B)) != RPE_OK) return rc;
@@ -1144,11 +1204,26 @@ extern "C" int rpe_match_hamming_guided(rpe_handle *h, const uint8_t *h_desc1, c
     // pair p on the workspace slots (p, B + p), like every stage call
     HIPCHK(h, hipMemcpyAsync(h->d_desc, h_desc1, kcap * 32 * B, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->d_desc + kcap * 32 * B, h_desc2, kcap * 32 * B, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_kp_pt, h_pts1, sizeof(float2) * kcap * B, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_kp_pt + kcap * B, h_pts2, sizeof(float2) * kcap * B, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_kp_count, n1, sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_kp_count + B, n2, sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
-    return guided_run(h, rpe_run_batch(h, B), R, t, gate_px, max_distance, qidx, tidx, dist, nullptr, nullptr, n_matches);
+    return guided_stage_run(h, h_pts1, n1, h_pts2, n2, B, R, t, gate_px, max_distance, qidx, tidx, dist, n_matches);
+}
+
+extern "C" int rpe_match_l2_guided(rpe_handle *h, const float *h_desc1, const float *h_pts1, const int32_t *n1,
+                                   const float *h_desc2, const float *h_pts2, const int32_t *n2, int B,
+                                   const double K[9], const double *R, const double *t, double gate_px, double max_distance,
+                                   int32_t *qidx, int32_t *tidx, float *dist, int32_t *n_matches)
+{
+    if (!h || !h_desc1 || !h_pts1 || !n1 || !h_desc2 || !h_pts2 || !n2 || !K || !R || !t || B < 1) return rpe_invalid(h, "rpe_match_l2_guided");
+    if (int rc = check_batch(h, B)) return rc;
+    int rc = guided_check(h, "rpe_match_l2_guided", RPE_NORM_L2, B, R, t, gate_px, max_distance);
+    if (rc) return rc;
+    std::vector<uint8_t> u;
+    if ((rc = l2_desc_bytes(h, h_desc1, n1, h_desc2, n2, B, u)) != RPE_OK) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if ((rc = guided_alloc(h)) != RPE_OK) return rc;
+    last_run_end(h);                            // overwrites the workspace's features
+    if ((rc = set_K(h, K)) != RPE_OK) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->d_desc, u.data(), u.size(), hipMemcpyHostToDevice, h->stream));
+    return guided_stage_run(h, h_pts1, n1, h_pts2, n2, B, R, t, gate_px, max_distance, qidx, tidx, dist, n_matches);   // waits: u is read by then
 }
 
 // ---------------------------------------------------------------- homography / rotation-only
@@ -1239,9 +1314,10 @@ __global__ __launch_bounds__(256) void frames_scatter_kernel(const uint8_t *__re
     }
 }
 
-// the norm words are read by match_l2_mfma_kernel only: the crossCheck matcher of NORM_L2 handles (the Lowe-ratio matcher
-// runs on the vector ALU and computes its own)
-static bool frames_keep_norms(const rpe_handle *h) { return h->cfg.norm_type == RPE_NORM_L2 && h->cfg.match_mode != RPE_MATCH_RATIO; }
+// the norm words are read by the matrix-core L2 kernels: the crossCheck matcher, and the guided matcher of either match
+// mode (the Lowe-ratio matcher itself runs on the vector ALU and computes its own).  Every NORM_L2 handle keeps them, so
+// a pair list of any L2 handle can be matched again under a pose
+static bool frames_keep_norms(const rpe_handle *h) { return h->cfg.norm_type == RPE_NORM_L2; }
 
 extern "C" int rpe_frames_capacity(const rpe_handle *h) { return h ? h->fs.cap : 0; }
 
@@ -1926,20 +2002,8 @@ extern "C" int rpe_match_l2(rpe_handle *h, const float *h_desc1, const int32_t *
     if (int rc = check_batch(h, B)) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     last_run_end(h);                            // overwrites buffers rpe_fetch_structure reads
-    const size_t dim = (size_t)h->desc_bytes;               // 128 (SIFT) or 32 (ORB descriptors under NORM_L2)
-    const size_t per = (size_t)h->lay.kcap * dim;
-    std::vector<uint8_t> u(2 * per * B, 0);
-    for (int s = 0; s < 2; ++s) {
-        const float *src = s ? h_desc2 : h_desc1; const int32_t *cn = s ? n2 : n1;
-        for (int i = 0; i < B; ++i) {
-            if (int rc = check_desc_counts(h, cn + i, 1)) return rc;
-            for (size_t e = 0; e < (size_t)cn[i] * dim; ++e) {
-                float v = src[(size_t)i * per + e];
-                if (!(v >= 0.f && v <= 255.f) || v != (float)(int)v) { h->err = "NORM_L2 path expects byte-valued descriptors (SIFT's integer-valued 0..255 floats, or ORB bytes)"; return RPE_ERR_INVALID; }
-                u[(size_t)s * per * B + (size_t)i * per + e] = (uint8_t)v;
-            }
-        }
-    }
+    std::vector<uint8_t> u;
+    if (int rc = l2_desc_bytes(h, h_desc1, n1, h_desc2, n2, B, u)) return rc;
     HIPCHK(h, hipMemcpyAsync(h->d_desc, u.data(), u.size(), hipMemcpyHostToDevice, h->stream));
     return stage_match_run(h, true, n1, n2, B, qidx, tidx, dist, n_matches);
 }

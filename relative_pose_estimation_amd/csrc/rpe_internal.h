@@ -317,6 +317,7 @@ struct rpe_handle {
     int *d_m_norm = nullptr;                  // L2 matcher: [img][kcap][2] { |u|^2, |u|^2 + 2 sum(u) }, u = byte - 128, of every descriptor
     unsigned *d_hm_best = nullptr, *d_hm_row = nullptr;   // Hamming matcher, small batches (<= RPE_MATCH_SPLIT_PAIRS pairs): election / own-nearest words in HBM
     unsigned long long *d_m_best2 = nullptr;  // L2 matcher: [pair][kcap] per query: the same key of its nearest train (the ratio mode's only list)
+                                              // both lists are scratch of one launch sequence: the guided L2 matcher (rpe_launch_guided_l2) elects into them too
     float2 *d_pts1 = nullptr, *d_pts2 = nullptr;   // [pair][max_matches]
     // RANSAC
     unsigned short *d_subsets = nullptr;  // [M 0..max_matches][iters][5]
@@ -342,8 +343,9 @@ struct rpe_handle {
     double *d_link_stats = nullptr;       // [link][3] lower quartile, median, upper quartile
     int *d_link_n = nullptr, *d_link_code = nullptr;
     bool link_lds_set = false;            // the kernel's dynamic-LDS limit has been raised for this handle's layout
-    // rpe_guided_matches / rpe_match_hamming_guided only (created on first use): match lists of their own, shaped like the
-    // run's d_m_* / d_pts*; the poses gated with when the caller supplies them; per pair and image one 32-byte record per
+    // the guided matchers of either norm only (rpe_guided_matches[_l2], rpe_match_hamming_guided, rpe_match_l2_guided;
+    // created on first use): match lists of their own, shaped like the run's d_m_* / d_pts* (d_gm_d: int32 Hamming
+    // distances, or f32 L2 distances in the same four bytes); the poses gated with when the caller supplies them; per pair and image one 32-byte record per
     // keypoint [pair][2][kcap] and the squared threshold (see guided_records_kernel)
     int *d_gm_q = nullptr, *d_gm_t = nullptr, *d_gm_d = nullptr, *d_gm_n = nullptr;
     float2 *d_gm_pts1 = nullptr, *d_gm_pts2 = nullptr;
@@ -369,7 +371,7 @@ struct rpe_handle {
         int cap = 0;
         uint8_t *d_desc = nullptr;        // [slot][kcap][desc_bytes]
         float2 *d_kp_pt = nullptr;        // [slot][kcap]
-        int2 *d_norm = nullptr;           // [slot][kcap] NORM_L2 crossCheck handles only: the MFMA matcher's norm words, computed at put time
+        int2 *d_norm = nullptr;           // [slot][kcap] NORM_L2 handles only (either match mode): the MFMA matchers' norm words, computed at put time
         int *d_count = nullptr;           // [slot] keypoints (0 for a slot never filled)
         unsigned *d_ovf = nullptr;        // [slot] RPE_OVF_* flags of the extraction that filled the slot
         std::vector<uint8_t> filled;      // [slot] host side: the slot holds a frame (argument checks never read the device)
@@ -468,6 +470,7 @@ void rpe_launch_match(rpe_handle *h, const RpeRun &r);
 void rpe_launch_match_l2(rpe_handle *h, const RpeRun &r);
 void rpe_launch_l2_norms(rpe_handle *h, int n_img);
 void rpe_launch_guided(rpe_handle *h, const RpeRun &r, const double *d_R, const double *d_t, const int *d_status, double gate_px, int max_distance);
+void rpe_launch_guided_l2(rpe_handle *h, const RpeRun &r, const double *d_R, const double *d_t, const int *d_status, double gate_px, double max_distance);
 int rpe_sift_create(rpe_handle *h);
 void rpe_sift_destroy(rpe_handle *h);
 int rpe_sift_run(rpe_handle *h, const uint8_t *d_a, const uint8_t *d_b, int na, int nb);

@@ -476,20 +476,25 @@ class PoseEstimator:
                     refine_iters=int(rinfo[0, 1]), rms_before=float(rms[0, 0]), rms_after=float(rms[0, 1]))
         return info
 
-    def last_guided(self, R=None, t=None, gate_px=None, max_distance=256):
+    def last_guided(self, R=None, t=None, gate_px=None, max_distance=None):
         """Guided matches of the pairs of the last estimate / estimate_batch / estimate_sequence / estimate_pairs call
-        (of its last chunk when it ran in several; not in the reference; _capi.Engine.guided_matches): the mutual
-        nearest neighbours among the keypoint pairs within gate_px (Sampson distance in pixels, None = the
-        estimator's RANSAC threshold) of a pose.  R, t None: the call's own poses, pairs that failed get no matches;
+        (of its last chunk when it ran in several; not in the reference; _capi.Engine.guided_matches, or
+        guided_matches_l2 for an estimator with NORM_L2): the mutual nearest neighbours among the keypoint pairs within
+        gate_px (Sampson distance in pixels, None = the estimator's RANSAC threshold) of a pose and within max_distance
+        of each other (None = no bound: 256 for Hamming, +inf for L2).  R, t None: the call's own poses, pairs that failed get no matches;
         R[B,3,3], t[B,3(,1)]: poses to gate with (refined poses, a prior from a trajectory), every pair matched.
         Returns one dict per pair, arrays trimmed to the pair's guided count: 'qidx', 'tidx' (keypoint indices in image
-        1 / 2), 'dist' (Hamming), 'pts1', 'pts2' (n, 2) pixels.  ORB with NORM_HAMMING only (RpeError otherwise)."""
+        1 / 2), 'dist' (int32 Hamming distances, or the matcher's f32 distances under NORM_L2), 'pts1', 'pts2' (n, 2)
+        pixels."""
         eng, B = self._last_engine, self._last_pairs
-        q, ti, d, p1, p2, nm = eng.guided_matches(B, R, t, gate_px, max_distance)
+        if self._norm == _capi.NORM_L2:
+            q, ti, d, p1, p2, nm = eng.guided_matches_l2(B, R, t, gate_px, max_distance)
+        else:
+            q, ti, d, p1, p2, nm = eng.guided_matches(B, R, t, gate_px, 256 if max_distance is None else max_distance)
         return [{'qidx': q[p, :nm[p]].copy(), 'tidx': ti[p, :nm[p]].copy(), 'dist': d[p, :nm[p]].copy(),
                  'pts1': p1[p, :nm[p]].copy(), 'pts2': p2[p, :nm[p]].copy()} for p in range(B)]
 
-    def estimate_guided(self, img1, img2, gate_px=None, max_distance=256, refine_iters=10):
+    def estimate_guided(self, img1, img2, gate_px=None, max_distance=None, refine_iters=10):
         """estimate, then the guided matches at that pose (last_guided), then the non-linear refinement of the pose over
         all of them (rpe_refine_pose_points with a mask of ones; not in the reference).  Returns a dict: 'R', 't' the
         refined pose (the five-point pose when the refinement was skipped or rejected), 'R_initial', 't_initial',

@@ -44,7 +44,7 @@ def _timed(fn, warmup, reps):
 
 
 def slot_bytes(kcap, desc_bytes, l2):
-    """bytes of one store slot: descriptors + kp_pt (+ the norm words of the L2 crossCheck matcher) per keypoint row, count and flags"""
+    """bytes of one store slot: descriptors + kp_pt (+ the norm words of NORM_L2 handles) per keypoint row, count and flags"""
     return kcap * (desc_bytes + 8 + (8 if l2 else 0)) + 8
 
 

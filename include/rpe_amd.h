@@ -511,6 +511,86 @@ int rpe_find_homography(rpe_handle *h, const float *h_pts1, const float *h_pts2,
                         const double K[9], int iters, double threshold_px,
                         double *H, double *R_rot, uint8_t *mask, int32_t *counts, int32_t *info);
 
+/* ------------------------------------------------------------ link poses */
+/* Absolute pose of a frame against the structure of a linked pair (NOT in the reference, which has no 2D-3D path): for a
+ * link (pair a, pair b, shared frame S) pair a's triangulated points are the map, pair b's matches the observations in
+ * b's other frame C, and the pose of C is solved by P3P RANSAC.  The result is pair b's relative pose on pair a's scale
+ * (|t| is the baseline of pair b in units of the baseline of pair a); it uses pair b's matches only -- neither b's
+ * essential matrix nor any parallax in b: a rotation-only pair b gets its rotation and |t| ~ 0.
+ * Links: exactly those of rpe_scale_links -- the same side bits, validity rules and refusals (one argument head serves
+ * both calls); the structure kernels are launched when the per-match buffers do not hold their results yet.
+ * The rule, for one link.  All arithmetic f64, + - * / sqrt only, no contraction; a comparison with a NaN is false;
+ * dot(a, b) = (a0*b0 + a1*b1) + a2*b2; cross(a, b) = (a1*b2 - a2*b1, a2*b0 - a0*b2, a0*b1 - a1*b0); |a| = sqrt(dot(a, a));
+ * finite(v) = fabs(v) <= DBL_MAX.
+ *  Map side (pair a): pair a's status must be RPE_PAIR_OK, else RPE_LINKPOSE_PAIR_FAILED.  A usable match is as in
+ *   rpe_scale_links (i < n_matches, ransac_mask and pose_mask set); its key is its keypoint index on S; the lowest match
+ *   index wins a duplicate key.  Its 3D point is the triangulated point (X, Y, Z) taken into S's camera frame by the
+ *   expression of "scale links": itself when S is a's image 1, ((r0*X + r1*Y) + r2*Z) + t per row when S is a's image 2.
+ *  Observation side (pair b): every match i < n_matches takes part whatever b's masks say; the lowest match index wins
+ *   a duplicate key.  Pair b need not be RPE_PAIR_OK: every status leaves n_matches, the match indices and the matched
+ *   points defined (the matcher writes them before any status is decided: RPE_PAIR_NO_DESCRIPTORS has n_matches = 0,
+ *   RPE_PAIR_INSUFFICIENT_MATCHES fewer than 5 -- both end as RPE_LINKPOSE_TOO_FEW -- and RPE_PAIR_NO_ESSENTIAL /
+ *   RPE_PAIR_AMBIGUOUS_ESSENTIAL keep their full match list and are solved like an OK pair), so no status of pair b is
+ *   RPE_LINKPOSE_PAIR_FAILED.  The observation q = (qx, qy) is b's point on C (image 2 of b when S is its image 1, else
+ *   image 1) in the normalised coordinates the geometry stages use (K, or undistorted with C's camera after a *_cameras
+ *   run): the same expression, the same bits.  thr = threshold_px / f, f = pair b's RANSAC focal scale as
+ *   rpe_pair_homographies takes it; thr2 = thr * thr (a double).
+ *  Correspondences: the keys with an entry on both sides, numbered c = 0 .. n-1 in ascending order of pair b's match
+ *   index.  n < max(min_shared, 6): RPE_LINKPOSE_TOO_FEW, n reported, the rest zero.
+ *  Sample: iteration it < iters takes the first three of the five indices of findEssentialMat's subset stream for M = n:
+ *   points P1 P2 P3 (3D) and q1 q2 q3.
+ *  Minimal solver:
+ *   bearings j_k = (x/m, y/m, 1/m), m = sqrt((x*x + y*y) + 1) at q_k;
+ *   a2 = dot(P2-P3, P2-P3), b2 = dot(P1-P3, P1-P3), c2 = dot(P1-P2, P1-P2); ca = dot(j2, j3), cb = dot(j1, j3),
+ *   cg = dot(j1, j2).  With the depths s2 = u s1, s3 = v s1 (ascending coefficients, index = power of v):
+ *   Q = (1, q1, 1), q1 = -(2*cb);  m = a2 - c2;  N = (b2 + m, m*q1, m - b2);  D = (d0, d1), d0 = (2*b2)*cg,
+ *   d1 = -((2*b2)*ca);  u = N(v) / D(v), and v is a root of b2 N^2 - 2 b2 cg N D + (b2 - c2 Q) D^2, formed as
+ *   NN = (n0*n0, 2*(n0*n1), 2*(n0*n2) + n1*n1, 2*(n1*n2), n2*n2);  ND = (n0*d0, n0*d1 + n1*d0, n1*d1 + n2*d0, n2*d1);
+ *   DD = (d0*d0, 2*(d0*d1), d1*d1);  W = (b2 - c2, -(c2*q1), -c2);
+ *   WD = (w0*dd0, w0*dd1 + w1*dd0, (w0*dd2 + w1*dd1) + w2*dd0, w1*dd2 + w2*dd1, w2*dd2);
+ *   c_i = (b2*nn_i - d0*nd_i) + wd_i for i = 0 .. 3, c_4 = b2*nn_4 + wd_4.
+ *   Degree = the highest i with c_i != 0 (none or 0: no root); the real roots come from the library's derivative-chain
+ *   finder (Fujiwara bound from the binary exponents, sign-change brackets between the roots of the derivative,
+ *   safeguarded Newton, Estrin evaluation: findEssentialMat's), ascending, root index r = 0, 1, ...
+ *   A root v is a candidate iff v > 0, Dv = d0 + d1*v != 0, u = Nv / Dv > 0 with Nv = (n0 + n1*v) + n2*(v*v),
+ *   Qv = (1 + q1*v) + v*v > 0, and every entry of the R and t below is finite.
+ *   Depths s1 = sqrt(b2 / Qv), s2 = u*s1, s3 = v*s1; Y_k = s_k * j_k.  Frames: e1 = (P2-P1) / |P2-P1|,
+ *   e3 = cross(e1, P3-P1) / |cross(e1, P3-P1)|, e2 = cross(e3, e1); f1 f2 f3 the same from Y1 Y2 Y3;
+ *   R[r][c] = (f1[r]*e1[c] + f2[r]*e2[c]) + f3[r]*e3[c]; t[r] = Y1[r] - ((R[r][0]*P1[0] + R[r][1]*P1[1]) + R[r][2]*P1[2]).
+ *   Collinear or repeated points give non-finite entries and so no candidate.
+ *  Score: y = R X + t, each row ((R[r][0]*X + R[r][1]*Y) + R[r][2]*Z) + t[r]; dx = y0 - qx*y2, dy = y1 - qy*y2;
+ *   correspondence c is an inlier iff y2 > 0 and (dx*dx + dy*dy) <= thr2 * (y2*y2).  No division.
+ *  Election: all `iters` samples are evaluated; the winner is the candidate with the most inliers, ties to the lowest
+ *   iteration, then to the lowest root index.  No candidate at all: RPE_LINKPOSE_NONE.
+ *  Polish (refine_iters > 0): Levenberg-Marquardt on the reprojection residuals in pixels, two per correspondence,
+ *   (f*(y0/y2 - qx), f*(y1/y2 - qy)), over the winner's inlier set, which stays fixed; six parameters (w, d):
+ *   R <- exp([w]x) R, t <- t + d; the conventions of rpe_refine_poses (initial damping 1e-3, the step solves
+ *   (J'J + lambda diag J'J) step = -J'r by Cholesky and a matrix that is not positive definite counts as a rejection, a
+ *   step is accepted only when it strictly lowers the cost, damping / 10 after an accepted step and * 10 after a
+ *   rejected one, the same stop tolerances on the cost decrease and the step length, at most refine_iters iterations;
+ *   the sums over the inliers in the fixed order of "homography": lane partials, butterfly, wave totals).  The polished pose is
+ *   returned only if a step was accepted, it is finite and its inlier count over all n correspondences is not below the
+ *   winner's; otherwise the minimal pose is returned.  refine_iters = 0 returns the minimal pose.
+ *  Outputs (host, any may be NULL): R[L*9], t[L*3] in pair b's own convention (image 1 -> image 2 of pair b) on pair a's
+ *   scale: the solved pose (S -> C) when S is b's image 1; when S is b's image 2 its inverse, R_out[r][c] = R[c][r],
+ *   t_out[r] = -((R[0][r]*t[0] + R[1][r]*t[1]) + R[2][r]*t[2]).  mask[L*max_matches], indexed by pair b's match index:
+ *   the inliers of the returned pose (scored in the solved form), zero elsewhere.  counts[L*2] = {n, inliers of the
+ *   returned pose}.  info[L*4] = {RPE_LINKPOSE_* code, winning iteration, winning root index, polish: the iterations run
+ *   when the polished pose is returned, 0 when there was no polish or no accepted step, -1 when the polished pose was
+ *   rejected}.  rms[L*2] = root mean square over the winner's m inliers of the residual length in pixels,
+ *   sqrt(sum(rx*rx + ry*ry) / m), of the minimal pose and of the returned pose.  For every code but RPE_LINKPOSE_OK
+ *   everything except the code and n is zero.
+ * The results live in buffers of their own: rpe_fetch_results, rpe_fetch_structure, rpe_refine_poses, rpe_scale_links,
+ * rpe_pair_homographies, rpe_guided_matches(_l2) and rpe_gather_poses return the same bits afterwards.  Bit-deterministic
+ * (no atomics decide an order, no floating-point atomics).
+ * RPE_ERR_INVALID / RPE_ERR_CAPACITY: every refusal of rpe_scale_links, and iters outside 1 .. rpe_config.ransac_max_iters,
+ * threshold_px not finite or <= 0, refine_iters outside 0 .. 100.  All checks are host-side; nothing is launched and the
+ * handle stays usable after a refusal. */
+enum { RPE_LINKPOSE_OK = 0, RPE_LINKPOSE_PAIR_FAILED = 1, RPE_LINKPOSE_TOO_FEW = 2, RPE_LINKPOSE_NONE = 3 };
+int rpe_link_poses(rpe_handle *h, int L, const int32_t *pair_a, const int32_t *pair_b, const int32_t *side,
+                   int iters, double threshold_px, int min_shared, int refine_iters,
+                   double *R, double *t, uint8_t *mask, int32_t *counts, int32_t *info, double *rms);
+
 /* ---------------------------------------------------------- stage entry */
 /* replaces extractor.detectAndCompute(image, None) (pose_estimator.py:108)
  * for n_images images (n_images <= 2*max_batch).  kps[n_images*cap],

@@ -29,6 +29,7 @@ ORDER_BGR, ORDER_RGB = 0, 1
 REFINE_OK, REFINE_SKIPPED, REFINE_REJECTED = 0, 1, 2   # info[:, 0] of refine_poses (include/rpe_amd.h RPE_REFINE_*)
 LINK_OK, LINK_PAIR_FAILED, LINK_TOO_FEW = 0, 1, 2      # code[] of scale_links (include/rpe_amd.h RPE_LINK_*)
 HOMOGRAPHY_OK, HOMOGRAPHY_SKIPPED, HOMOGRAPHY_NONE = 0, 1, 2   # info[:, 0] of pair_homographies (include/rpe_amd.h RPE_HOMOGRAPHY_*)
+LINKPOSE_OK, LINKPOSE_PAIR_FAILED, LINKPOSE_TOO_FEW, LINKPOSE_NONE = 0, 1, 2, 3   # info[:, 0] of link_poses (RPE_LINKPOSE_*)
 UNDISTORT_ITERS = 5               # RPE_UNDISTORT_ITERS: fixed-point rounds of the camera path's undistortion
 
 # The binding, one entry per function of include/rpe_amd.h: "<return>:<one letter per parameter>".  Parameters: p pointer or
@@ -52,7 +53,8 @@ _SIGNATURES = {
     "rpe_refine_pose_points_cameras": "i:pppppppippippppp",
     "rpe_bgr_to_gray_device": "i:ppzip", "rpe_bgr_to_gray": "i:ppzip", "rpe_lsd_detect": "i:piipip",
     "rpe_fetch_matched_points": "i:pipp", "rpe_fetch_structure": "i:pippp", "rpe_refine_poses": "i:piippppp",
-    "rpe_fetch_match_indices": "i:pipp", "rpe_scale_links": "i:pipppippp", "rpe_guided_matches": "i:pippdipppppp",
+    "rpe_fetch_match_indices": "i:pipp", "rpe_scale_links": "i:pipppippp", "rpe_link_poses": "i:pipppidiipppppp",
+    "rpe_guided_matches": "i:pippdipppppp",
     "rpe_guided_matches_l2": "i:pippddpppppp",
     "rpe_pair_homographies": "i:piidppppp", "rpe_find_homography": "i:ppppipidppppp",
     "rpe_orb_detect_and_compute": "i:ppippp", "rpe_orb_debug_fetch": "i:piip", "rpe_orb_pyramid_pixels": "l:p",
@@ -399,6 +401,27 @@ class Engine:
         stats = np.zeros((L, 3)); n = np.zeros(L, np.int32); code = np.zeros(L, np.int32)
         self._chk(self.lib.rpe_scale_links(self.h, L, _p(a), _p(b), _p(s), int(min_shared), _p(stats), _p(n), _p(code)))
         return stats, n, code
+
+    def link_poses(self, pair_a, pair_b, side, iters=256, threshold_px=None, min_shared=8, refine_iters=10):
+        """Pose of pair_b's other frame against the points pair_a triangulated, per link of the last stream / pair list
+        (rpe_link_poses): P3P RANSAC over the keypoints of the shared frame, `iters` samples, all evaluated;
+        threshold_px = the reprojection gate in pixels (None = the handle's ransac_threshold); refine_iters
+        Levenberg-Marquardt iterations over the winner's inliers (0: the minimal pose).  Links as in scale_links.
+        Returns (R f64[L, 3, 3], t f64[L, 3]: pair_b's relative pose, image 1 -> image 2, on pair_a's scale -- |t| is the
+        baseline ratio; mask bool[L, mm] by pair_b's match index; counts i32[L, 2] = (shared keypoints, inliers);
+        info i32[L, 4] = (LINKPOSE_* code, winning iteration, winning root, polish iterations / 0 none / -1 rejected);
+        rms f64[L, 2] = reprojection rms in pixels of the minimal and of the returned pose).  Everything but the code and
+        the shared count is zero unless LINKPOSE_OK.  The run's own results are not modified."""
+        a, b, s = _i32(pair_a), _i32(pair_b), _i32(side)
+        if not (a.size == b.size == s.size):
+            raise ValueError(f"link_poses: pair_a, pair_b and side must have one length, got {(a.size, b.size, s.size)}")
+        L = a.size
+        R = np.zeros((L, 3, 3)); t = np.zeros((L, 3)); mask = np.zeros((L, self.max_matches), np.uint8)
+        counts = np.zeros((L, 2), np.int32); info = np.zeros((L, 4), np.int32); rms = np.zeros((L, 2))
+        thr = float(self.cfg.ransac_threshold if threshold_px is None else threshold_px)
+        self._chk(self.lib.rpe_link_poses(self.h, L, _p(a), _p(b), _p(s), int(iters), thr, int(min_shared), int(refine_iters),
+                                          _p(R), _p(t), _p(mask), _p(counts), _p(info), _p(rms)))
+        return R, t, mask.astype(bool), counts, info, rms
 
     # ---- guided matching (rpe_guided_matches / rpe_match_hamming_guided; not in the reference)
     def _poses(self, B, R, t):

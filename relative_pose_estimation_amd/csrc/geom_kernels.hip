@@ -1138,6 +1138,24 @@ __device__ __forceinline__ void block_sum_f64(double (&v)[N], double *s_red, int
     for (int k = 0; k < N; ++k) v[k] = ((s_red[k] + s_red[N + k]) + s_red[2 * N + k]) + s_red[3 * N + k];
 }
 
+// Ordered compaction, one step of 256 candidates in thread order: the slot of this thread's element when f is set (n + the
+// number of flagged threads below it), and n advanced by the step's total.  All 256 threads call it (two barriers, both
+// in front of the caller's store to the slot: a barrier follows the last step before anyone reads the list);
+// ballot / popcount only, so the order never depends on timing.  s_wc: one LDS word per wave.
+__device__ __forceinline__ int ordered_slot(bool f, int *s_wc /*[4]*/, int &n)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const unsigned long long bal = __ballot(f);
+    if (lane == 0) s_wc[wv] = __popcll(bal);
+    __syncthreads();
+    int off = n, tot = 0;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) { const int c = s_wc[w]; if (w < wv) off += c; tot += c; }
+    n += tot;
+    __syncthreads();
+    return off + __popcll(bal & ((1ull << lane) - 1ull));
+}
+
 __device__ __forceinline__ void cross3(const double *a, const double *b, double *c)
 {
     c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
@@ -1220,20 +1238,22 @@ __device__ __forceinline__ void refine_rotate(const double *w, const double *R, 
         for (int j = 0; j < 3; ++j) Rn[i * 3 + j] = (X[i * 3] * R[j] + X[i * 3 + 1] * R[3 + j]) + X[i * 3 + 2] * R[6 + j];
 }
 
-// (H + lambda diag H) d = -g, H given as its upper triangle (row-major, 15 entries); false when not positive definite
+// (H + lambda diag H) d = -g for N parameters, H given as its upper triangle (row-major, N (N + 1) / 2 entries); false when
+// not positive definite
+template <int N>
 __device__ __forceinline__ bool refine_solve(const double *H, const double *g, double lambda, double *d)
 {
-    double L[5][5];
+    double L[N][N];
     int q = 0;
 #pragma unroll
-    for (int i = 0; i < 5; ++i)
+    for (int i = 0; i < N; ++i)
 #pragma unroll
-        for (int j = i; j < 5; ++j, ++q) { L[i][j] = H[q]; L[j][i] = H[q]; }
+        for (int j = i; j < N; ++j, ++q) { L[i][j] = H[q]; L[j][i] = H[q]; }
 #pragma unroll
-    for (int i = 0; i < 5; ++i) L[i][i] = L[i][i] + lambda * L[i][i];
+    for (int i = 0; i < N; ++i) L[i][i] = L[i][i] + lambda * L[i][i];
     bool ok = true;
 #pragma unroll
-    for (int j = 0; j < 5; ++j) {
+    for (int j = 0; j < N; ++j) {
         double s = L[j][j];
 #pragma unroll
         for (int k = 0; k < j; ++k) s -= L[j][k] * L[j][k];
@@ -1241,26 +1261,26 @@ __device__ __forceinline__ bool refine_solve(const double *H, const double *g, d
         const double dj = sqrt(s);
         L[j][j] = dj;
 #pragma unroll
-        for (int i = j + 1; i < 5; ++i) {
+        for (int i = j + 1; i < N; ++i) {
             double v = L[i][j];
 #pragma unroll
             for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
             L[i][j] = v / dj;
         }
     }
-    double y[5];
+    double y[N];
 #pragma unroll
-    for (int i = 0; i < 5; ++i) {
+    for (int i = 0; i < N; ++i) {
         double v = -g[i];
 #pragma unroll
         for (int k = 0; k < i; ++k) v -= L[i][k] * y[k];
         y[i] = v / L[i][i];
     }
 #pragma unroll
-    for (int i = 4; i >= 0; --i) {
+    for (int i = N - 1; i >= 0; --i) {
         double v = y[i];
 #pragma unroll
-        for (int k = i + 1; k < 5; ++k) v -= L[k][i] * d[k];
+        for (int k = i + 1; k < N; ++k) v -= L[k][i] * d[k];
         d[i] = v / L[i][i];
     }
     return ok;
@@ -1280,7 +1300,7 @@ __global__ __launch_bounds__(256) void pose_refine_kernel(const double2 *__restr
     extern __shared__ double2 s_dyn[];            // LDS: [2][max_matches] compacted inlier points; else u16 [max_matches] inlier indices
     __shared__ double s_red[4 * REFINE_NSUM];
     __shared__ int s_wc[4], s_g[2];
-    const int pair = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int pair = blockIdx.x, tid = threadIdx.x, lane = tid & 63;
     const int M = min(m_n[pair], max_matches);
     const bool st_ok = !status || status[pair] == RPE_PAIR_OK;
     const double2 *gp1 = n1 + (long long)pair * max_matches, *gp2 = n2 + (long long)pair * max_matches;
@@ -1293,20 +1313,13 @@ __global__ __launch_bounds__(256) void pose_refine_kernel(const double2 *__restr
     for (int i0 = 0; i0 < (st_ok ? M : 0); i0 += 256) {
         const int i = i0 + tid;
         const bool f = i < M && mk[i] != 0;
-        const unsigned long long bal = __ballot(f);
-        if (lane == 0) s_wc[wv] = __popcll(bal);
-        __syncthreads();
-        int off = n, tot = 0;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) { const int c = s_wc[w]; if (w < wv) off += c; tot += c; }
+        const int pos = ordered_slot(f, s_wc, n);
         if (f) {
-            const int pos = off + __popcll(bal & ((1ull << lane) - 1ull));
             if (LDS) { l1[pos] = gp1[i]; l2[pos] = gp2[i]; }
             else s_idx[pos] = (unsigned short)i;
         }
-        n += tot;
-        __syncthreads();
     }
+    __syncthreads();                                   // the list is complete
     double R[9], t[3];
 #pragma unroll
     for (int e = 0; e < 9; ++e) R[e] = Rin[pair * 9 + e];
@@ -1358,7 +1371,7 @@ __global__ __launch_bounds__(256) void pose_refine_kernel(const double2 *__restr
             if (need_lin) { double dummy; linearise(dummy); need_lin = false; }
             ++iters;
             double d[5];
-            if (!refine_solve(H, g, lambda, d)) { lambda = lambda * 10.; continue; }
+            if (!refine_solve<5>(H, g, lambda, d)) { lambda = lambda * 10.; continue; }
             double Rn[9], tn[3];
             refine_rotate(d, R, Rn);
 #pragma unroll
@@ -1880,5 +1893,531 @@ int rpe_launch_homography(rpe_handle *h, const RpeRun &r, int iters, double thre
                from_batch ? (const RpeRansacState *)h->d_rstate : (const RpeRansacState *)nullptr,
                (const unsigned short *)h->d_subsets, (const double *)h->d_K, r.cam, threshold_px, iters, h->cfg.ransac_max_iters,
                mm, use_lds, h->d_hg_H, h->d_hg_R, h->d_hg_mask, h->d_hg_counts, h->d_hg_info);
+    return RPE_OK;
+}
+
+// ------------------------------------------------------------ link poses
+// rpe_link_poses (NOT in the reference; include/rpe_amd.h states the rule): the pose of pair b's other frame C against the
+// points pair a triangulated, by P3P RANSAC over the keypoints of the shared frame S, on pair a's scale.  One 256-thread
+// workgroup per link, f64 throughout, no contraction.
+//   join     scale_links_kernel's packed table (high half: lowest usable match of a, low half: lowest match of b; here
+//            every match of b takes part).  The winners of b are then compacted in match order by ordered_slot (ballot /
+//            popcount): correspondence c = the c-th winner, so no atomic decides an order.
+//   list     per correspondence X (3 f64, in S's frame), q (2 f64) and b's match index (u16).  X and q live in LDS up to
+//            LP_LDS_MATCHES matches (40 B each: 20 KB at the default 500) and in d_lp_corr above it; both forms are
+//            walked through the same pointers in the same order.  The indices are always in LDS.
+//   rounds   homography_kernel's: LP_ROUND = 256 samples at a time, thread j solves sample j in registers (quartic, the
+//            derivative chain with static indices, up to four poses) and parks its candidates at slot 4 j + root; the
+//            slots of the valid ones are listed densely in (iteration, root) order (block_excl_scan of the per-thread
+//            counts).  The four waves score the dense list round-robin, lanes striding the correspondences, wave_sum
+//            for the count; a wave meets its candidates in ascending (iteration, root) order and replaces its best on a
+//            strictly larger count only; the cross-wave election compares (count, 4 * iteration + root).
+//   winner   solved again by every thread (the same code on the same operands: the same bits), its inlier flags, then the
+//            polish: pose_refine_kernel's loop with six parameters on the reprojection residuals (block_sum_f64 sums,
+//            refine_solve<6>, refine_rotate), and the fallback test over all correspondences.
+// Dynamic LDS (all of the kernel's LDS, base 16-byte aligned):
+//   [A] max(kcap u32 table, LP_ROUND * 4 poses of 12 f64 = 96 KB): the table is dead once the list is built, the poses
+//       once the election is over (the winner's inlier flags then live there)
+//   [s_red 4 * 28 f64][X, q: 40 B * max_matches when in LDS][dense list 1024 u16][match indices max_matches u16][32 ints]
+// 120 KB at the defaults (one workgroup per CU), 141 KB at the cut, 115 KB for uncapped SIFT (8064 matches in d_lp_corr).
+#define LP_ROUND 256
+#define LP_POSE_DOUBLES 12
+#define LP_LDS_MATCHES 1024
+#define LP_NSUM 28                   // 21 J'J + 6 J'r + 1 r'r
+
+struct LpQuartic { double j[9], b2, q1, n0, n1, n2, d0, d1, c[5]; };
+
+// bearings, side lengths, cosines and the quartic in v of the header
+__device__ __forceinline__ void lp_quartic(const double (&P)[9], const double (&q)[6], LpQuartic &g)
+{
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const double x = q[2 * k], y = q[2 * k + 1], m = sqrt((x * x + y * y) + 1.);
+        g.j[3 * k] = x / m; g.j[3 * k + 1] = y / m; g.j[3 * k + 2] = 1. / m;
+    }
+    const double d23[3] = {P[3] - P[6], P[4] - P[7], P[5] - P[8]}, d13[3] = {P[0] - P[6], P[1] - P[7], P[2] - P[8]};
+    const double d12[3] = {P[0] - P[3], P[1] - P[4], P[2] - P[5]};
+    const double j1[3] = {g.j[0], g.j[1], g.j[2]}, j2[3] = {g.j[3], g.j[4], g.j[5]}, j3[3] = {g.j[6], g.j[7], g.j[8]};
+    const double a2 = hg_dot(d23, d23), b2 = hg_dot(d13, d13), c2 = hg_dot(d12, d12);
+    const double ca = hg_dot(j2, j3), cb = hg_dot(j1, j3), cg = hg_dot(j1, j2);
+    const double q1 = -(2. * cb), m = a2 - c2;
+    const double n0 = b2 + m, n1 = m * q1, n2 = m - b2;
+    const double d0 = (2. * b2) * cg, d1 = -((2. * b2) * ca);
+    const double nn[5] = {n0 * n0, 2. * (n0 * n1), 2. * (n0 * n2) + n1 * n1, 2. * (n1 * n2), n2 * n2};
+    const double nd[4] = {n0 * d0, n0 * d1 + n1 * d0, n1 * d1 + n2 * d0, n2 * d1};
+    const double dd[3] = {d0 * d0, 2. * (d0 * d1), d1 * d1};
+    const double w0 = b2 - c2, w1 = -(c2 * q1), w2 = -c2;
+    const double wd[5] = {w0 * dd[0], w0 * dd[1] + w1 * dd[0], (w0 * dd[2] + w1 * dd[1]) + w2 * dd[0], w1 * dd[2] + w2 * dd[1], w2 * dd[2]};
+#pragma unroll
+    for (int i = 0; i < 4; ++i) g.c[i] = (b2 * nn[i] - d0 * nd[i]) + wd[i];
+    g.c[4] = b2 * nn[4] + wd[4];
+    g.b2 = b2; g.q1 = q1; g.n0 = n0; g.n1 = n1; g.n2 = n2; g.d0 = d0; g.d1 = d1;
+}
+
+// One level of the derivative chain in registers: the roots of p (degree K, p' = dp) between the nr_prev roots of dp in
+// crit, ascending into out.  Every index is static: the interval loop unrolls, a root lands in its slot by compares.
+template <int K>
+__device__ __forceinline__ int lp_level(const double (&p)[5], const double (&dp)[5], const double (&crit)[4], int nr_prev, double (&out)[4])
+{
+    const double R = root_bound<K>(p);
+    int nout = 0;
+#pragma unroll
+    for (int iv = 0; iv < K; ++iv) {                     // dp has at most K - 1 roots: at most K intervals
+        const double a = iv == 0 ? -R : crit[iv - 1], b = iv == nr_prev ? R : crit[iv];
+        double root;
+        if (bracket_root<K>(p, dp, a, b, R, iv <= nr_prev, root)) {
+#pragma unroll
+            for (int s = 0; s < 4; ++s) if (s == nout) out[s] = root;
+            ++nout;
+        }
+    }
+    return nout;
+}
+
+// real roots, ascending, of c[0] + ... + c[N] x^N (c[N] != 0): poly_real_roots_generic's chain for a degree known at
+// compile time
+template <int N>
+__device__ __forceinline__ int lp_chain(const double (&c)[5], double (&roots)[4])
+{
+    double lv[5][5];
+#pragma unroll
+    for (int k = 0; k < 5; ++k)
+#pragma unroll
+        for (int i = 0; i < 5; ++i) lv[k][i] = (k == N && i <= N) ? c[i] : 0.;
+#pragma unroll
+    for (int k = N; k >= 2; --k)
+#pragma unroll
+        for (int i = 0; i < k; ++i) lv[k - 1][i] = lv[k][i + 1] * (double)(i + 1);
+    double crit[4] = {-lv[1][0] / lv[1][1], 0., 0., 0.};
+    int nr = 1;
+    if (N >= 2) {
+        double out[4] = {0., 0., 0., 0.};
+        nr = lp_level<2>(lv[2], lv[1], crit, nr, out);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) crit[s] = out[s];
+    }
+    if (N >= 3) {
+        double out[4] = {0., 0., 0., 0.};
+        nr = lp_level<3>(lv[3], lv[2], crit, nr, out);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) crit[s] = out[s];
+    }
+    if (N >= 4) {
+        double out[4] = {0., 0., 0., 0.};
+        nr = lp_level<4>(lv[4], lv[3], crit, nr, out);
+#pragma unroll
+        for (int s = 0; s < 4; ++s) crit[s] = out[s];
+    }
+#pragma unroll
+    for (int s = 0; s < 4; ++s) roots[s] = crit[s];
+    return nr;
+}
+
+// the quartic's real roots: its degree is the highest non-zero coefficient
+__device__ __forceinline__ int lp_roots(const double (&c)[5], double (&roots)[4])
+{
+    if (c[4] != 0.) return lp_chain<4>(c, roots);
+    if (c[3] != 0.) return lp_chain<3>(c, roots);
+    if (c[2] != 0.) return lp_chain<2>(c, roots);
+    if (c[1] != 0.) return lp_chain<1>(c, roots);
+    return 0;
+}
+
+// e1 = (A2 - A1) / |.|, e3 = (e1 x (A3 - A1)) / |.|, e2 = e3 x e1 of three points A1 A2 A3 (rows of A); e = rows e1 e2 e3
+__device__ __forceinline__ void lp_frame(const double (&A)[9], double (&e)[9])
+{
+    const double d[3] = {A[3] - A[0], A[4] - A[1], A[5] - A[2]}, w[3] = {A[6] - A[0], A[7] - A[1], A[8] - A[2]};
+    const double nd = sqrt(hg_dot(d, d));
+    const double e1[3] = {d[0] / nd, d[1] / nd, d[2] / nd};
+    double c[3], e2[3];
+    hg_cross(e1, w, c);
+    const double nc = sqrt(hg_dot(c, c));
+    const double e3[3] = {c[0] / nc, c[1] / nc, c[2] / nc};
+    hg_cross(e3, e1, e2);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { e[k] = e1[k]; e[3 + k] = e2[k]; e[6 + k] = e3[k]; }
+}
+
+// the candidate of root v: Rt = R (9, row-major) then t (3); false when v is no candidate
+__device__ __forceinline__ bool lp_pose(const double (&P)[9], const LpQuartic &g, double v, double (&Rt)[LP_POSE_DOUBLES])
+{
+    const double Dv = g.d0 + g.d1 * v, Nv = (g.n0 + g.n1 * v) + g.n2 * (v * v), Qv = (1. + g.q1 * v) + v * v;
+    const double u = Nv / Dv;
+    bool ok = v > 0. && Dv != 0. && u > 0. && Qv > 0.;
+    const double s1 = sqrt(g.b2 / Qv), s2 = u * s1, s3 = v * s1;
+    double Y[9], e[9], f[9];
+#pragma unroll
+    for (int k = 0; k < 3; ++k) { Y[k] = s1 * g.j[k]; Y[3 + k] = s2 * g.j[3 + k]; Y[6 + k] = s3 * g.j[6 + k]; }
+    lp_frame(P, e); lp_frame(Y, f);
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) Rt[r * 3 + c] = (f[r] * e[c] + f[3 + r] * e[3 + c]) + f[6 + r] * e[6 + c];
+        Rt[9 + r] = Y[r] - ((Rt[r * 3] * P[0] + Rt[r * 3 + 1] * P[1]) + Rt[r * 3 + 2] * P[2]);
+    }
+#pragma unroll
+    for (int k = 0; k < LP_POSE_DOUBLES; ++k) ok = ok && hg_finite(Rt[k]);
+    return ok;
+}
+
+// y = R X + t and the inlier test of the header
+__device__ __forceinline__ bool lp_inlier(const double (&Rt)[LP_POSE_DOUBLES], const double *X, const double *q, double thr2)
+{
+    const double y0 = ((Rt[0] * X[0] + Rt[1] * X[1]) + Rt[2] * X[2]) + Rt[9];
+    const double y1 = ((Rt[3] * X[0] + Rt[4] * X[1]) + Rt[5] * X[2]) + Rt[10];
+    const double y2 = ((Rt[6] * X[0] + Rt[7] * X[1]) + Rt[8] * X[2]) + Rt[11];
+    const double dx = y0 - q[0] * y2, dy = y1 - q[1] * y2;
+    return y2 > 0. && (dx * dx + dy * dy) <= thr2 * (y2 * y2);
+}
+
+// the three correspondences of iteration `it`
+__device__ __forceinline__ void lp_sample(const unsigned short *__restrict__ sub, int it, const double *cX, const double *cq,
+                                          double (&P)[9], double (&q)[6])
+{
+    const unsigned short *s5 = sub + (long long)it * 5;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        const int v = s5[k];
+        P[3 * k] = cX[3 * v]; P[3 * k + 1] = cX[3 * v + 1]; P[3 * k + 2] = cX[3 * v + 2];
+        q[2 * k] = cq[2 * v]; q[2 * k + 1] = cq[2 * v + 1];
+    }
+}
+
+// the two reprojection residuals of one correspondence in pixels; optionally their derivatives by (w0 w1 w2 | d0 d1 d2)
+template <bool JAC>
+__device__ __forceinline__ void lp_residual(const double *R, const double *t, double scale, const double *X, const double *q,
+                                            double &rx, double &ry, double *Jx, double *Jy)
+{
+    const double a0 = (R[0] * X[0] + R[1] * X[1]) + R[2] * X[2], a1 = (R[3] * X[0] + R[4] * X[1]) + R[5] * X[2];
+    const double a2 = (R[6] * X[0] + R[7] * X[1]) + R[8] * X[2];
+    const double y0 = a0 + t[0], y1 = a1 + t[1], y2 = a2 + t[2];
+    const double ux = y0 / y2, uy = y1 / y2;
+    rx = scale * (ux - q[0]); ry = scale * (uy - q[1]);
+    if (JAC) {                                            // d y / d w_k = e_k x (R X), d y / d d = I
+        const double s = scale / y2;
+        Jx[0] = -s * (ux * a1); Jx[1] = s * (a2 + ux * a0); Jx[2] = -s * a1; Jx[3] = s; Jx[4] = 0.; Jx[5] = -s * ux;
+        Jy[0] = -s * (a2 + uy * a1); Jy[1] = s * (uy * a0); Jy[2] = s * a0; Jy[3] = 0.; Jy[4] = s; Jy[5] = -s * uy;
+    }
+}
+
+template <bool CAM>
+__global__ __launch_bounds__(256) void link_pose_kernel(const RpeLink *__restrict__ links, const int *__restrict__ m_q,
+                                                         const int *__restrict__ m_t, const int *__restrict__ m_n,
+                                                         const int *__restrict__ status, const uint8_t *__restrict__ ransac_mask,
+                                                         const uint8_t *__restrict__ pose_mask, const double *__restrict__ points,
+                                                         const double *__restrict__ Rall, const double *__restrict__ tall,
+                                                         const double2 *__restrict__ n1, const double2 *__restrict__ n2,
+                                                         const unsigned short *__restrict__ subsets, const double *__restrict__ K,
+                                                         const RpeCamSrc cam, double threshold_px, int iters, int max_iters,
+                                                         int max_matches, int kcap, int min_shared, int refine_iters,
+                                                         double *__restrict__ corr, double *__restrict__ Rout,
+                                                         double *__restrict__ tout, uint8_t *__restrict__ mask,
+                                                         int *__restrict__ counts, int *__restrict__ info, double *__restrict__ rms)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_lp[];
+    const bool use_lds = corr == nullptr;
+    const size_t bytesT = sizeof(unsigned) * (size_t)kcap, bytesM = sizeof(double) * LP_ROUND * 4 * LP_POSE_DOUBLES;
+    const size_t bytesA = bytesT > bytesM ? bytesT : bytesM;
+    unsigned *s_tab = (unsigned *)s_lp;                                      // [kcap], until the list is built
+    double *s_model = (double *)s_lp;                                        // [LP_ROUND * 4][12], during the rounds
+    uint8_t *s_in = (uint8_t *)s_lp;                                         // [n] the winner's inlier flags, after the election
+    double *s_red = (double *)(s_lp + ((bytesA + 15) & ~(size_t)15));        // [4 * LP_NSUM]
+    double *s_corr = s_red + 4 * LP_NSUM;                                    // [5 * max_matches] when use_lds
+    unsigned short *s_list = (unsigned short *)(s_corr + (use_lds ? 5 * (size_t)max_matches : 0));   // [LP_ROUND * 4]
+    unsigned short *s_idx = s_list + LP_ROUND * 4;                           // [max_matches rounded up to 8]
+    int *s_int = (int *)(s_idx + ((max_matches + 7) & ~7));                  // [4] wave counts, [8] bests, [4] counts
+    int *s_wc = s_int, *s_best = s_int + 4, *s_cnt = s_int + 12;
+    const int link = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const RpeLink lk = links[link];
+    const long long om = (long long)link * max_matches;
+    int code = status[lk.a] == RPE_PAIR_OK ? RPE_LINKPOSE_OK : RPE_LINKPOSE_PAIR_FAILED;
+    int n = 0;
+    double *cX = use_lds ? s_corr : corr + (long long)link * 5 * max_matches, *cq = cX + 3 * (size_t)max_matches;
+    const bool a2 = (lk.side & 1) != 0, b2 = (lk.side & 2) != 0;
+    if (code == RPE_LINKPOSE_OK) {                                           // workgroup-uniform
+        // ---- join and ordered list
+        const int na = min(m_n[lk.a], max_matches), nb = min(m_n[lk.b], max_matches);
+        const long long oa = (long long)lk.a * max_matches, ob = (long long)lk.b * max_matches;
+        const int *key_a = (a2 ? m_t : m_q) + oa, *key_b = (b2 ? m_t : m_q) + ob;
+        const double2 *obs = (b2 ? n1 : n2) + ob;                            // b's point on C, its frame that is not shared
+        for (int k = tid; k < kcap; k += 256) s_tab[k] = 0xFFFFFFFFu;
+        __syncthreads();
+        for (int i = tid; i < na; i += 256) {
+            if (!(ransac_mask[oa + i] && pose_mask[oa + i])) continue;
+            const int key = key_a[i];
+            if ((unsigned)key < (unsigned)kcap) atomicMin(&s_tab[key], ((unsigned)i << 16) | LINK_NONE);
+        }
+        __syncthreads();
+        for (int i = tid; i < nb; i += 256) {
+            const int key = key_b[i];
+            if ((unsigned)key >= (unsigned)kcap) continue;
+            const unsigned e = s_tab[key];                                   // the high half is final since the barrier
+            if ((e >> 16) != LINK_NONE) atomicMin(&s_tab[key], (e & 0xFFFF0000u) | (unsigned)i);
+        }
+        __syncthreads();
+        double Ra[9], ta[3];
+#pragma unroll
+        for (int e = 0; e < 9; ++e) Ra[e] = Rall[lk.a * 9 + e];
+#pragma unroll
+        for (int e = 0; e < 3; ++e) ta[e] = tall[lk.a * 3 + e];
+        for (int i0 = 0; i0 < nb; i0 += 256) {
+            const int i = i0 + tid;
+            unsigned e = 0xFFFFFFFFu;
+            if (i < nb) { const int key = key_b[i]; if ((unsigned)key < (unsigned)kcap) e = s_tab[key]; }
+            const bool f = i < nb && (e >> 16) != LINK_NONE && (e & 0xFFFFu) == (unsigned)i;
+            const int pos = ordered_slot(f, s_wc, n);
+            if (f) {
+                const double *Pm = points + (oa + (e >> 16)) * 3;
+                double x = Pm[0], y = Pm[1], z = Pm[2];
+                if (a2) {                                                    // link_distance's expression and order
+                    const double X = x, Y = y, Z = z;
+                    x = ((Ra[0] * X + Ra[1] * Y) + Ra[2] * Z) + ta[0];
+                    y = ((Ra[3] * X + Ra[4] * Y) + Ra[5] * Z) + ta[1];
+                    z = ((Ra[6] * X + Ra[7] * Y) + Ra[8] * Z) + ta[2];
+                }
+                const double2 o = obs[i];
+                // the table and an LDS list share no bytes: s_corr lies behind region A
+                cX[3 * pos] = x; cX[3 * pos + 1] = y; cX[3 * pos + 2] = z;
+                cq[2 * pos] = o.x; cq[2 * pos + 1] = o.y;
+                s_idx[pos] = (unsigned short)i;
+            }
+        }
+        __syncthreads();                                                     // the list is complete, the table is dead
+        if (n < max(min_shared, 6)) code = RPE_LINKPOSE_TOO_FEW;
+    }
+    int win_cnt = -1, win_key = -1;
+    double thr2 = 0., scale = 0.;
+    const unsigned short *sub = subsets + (long long)n * max_iters * 5;
+    if (code == RPE_LINKPOSE_OK) {
+        scale = rpe_pair_focal<CAM>(K, cam, lk.b);
+        const double thr = threshold_px / scale;
+        thr2 = thr * thr;
+        int best_cnt = -1, best_key = -1;
+        for (int base = 0; base < iters; base += LP_ROUND) {
+            const int nr = min(LP_ROUND, iters - base);
+            __syncthreads();                                                 // the previous round's candidates have been scored
+            unsigned vm = 0;
+            if (tid < nr) {
+                double P[9], q[6], roots[4];
+                LpQuartic g;
+                lp_sample(sub, base + tid, cX, cq, P, q);
+                lp_quartic(P, q, g);
+                const int nroots = lp_roots(g.c, roots);
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    double Rt[LP_POSE_DOUBLES];
+                    if (r < nroots && lp_pose(P, g, roots[r], Rt)) {
+                        double *d = s_model + (tid * 4 + r) * LP_POSE_DOUBLES;
+#pragma unroll
+                        for (int e = 0; e < LP_POSE_DOUBLES; ++e) d[e] = Rt[e];
+                        vm |= 1u << r;
+                    }
+                }
+            }
+            int total;
+            int off = block_excl_scan(__popc(vm), s_wc, total);
+#pragma unroll
+            for (int r = 0; r < 4; ++r) if (vm & (1u << r)) s_list[off++] = (unsigned short)(tid * 4 + r);
+            __syncthreads();
+            for (int j = wv; j < total; j += 4) {                            // wave-uniform
+                const int id = s_list[j];
+                double Rt[LP_POSE_DOUBLES];
+                const double *d = s_model + id * LP_POSE_DOUBLES;
+#pragma unroll
+                for (int e = 0; e < LP_POSE_DOUBLES; ++e) Rt[e] = d[e];
+                int cnt = 0;
+                for (int c = lane; c < n; c += 64) cnt += lp_inlier(Rt, cX + 3 * c, cq + 2 * c, thr2) ? 1 : 0;
+                cnt = wave_sum(cnt);
+                if (cnt > best_cnt) { best_cnt = cnt; best_key = (base + (id >> 2)) * 4 + (id & 3); }
+            }
+        }
+        if (lane == 0) { s_best[wv * 2] = best_cnt; s_best[wv * 2 + 1] = best_key; }
+        __syncthreads();
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const int c = s_best[w * 2], key = s_best[w * 2 + 1];
+            if (key >= 0 && (c > win_cnt || (c == win_cnt && key < win_key))) { win_cnt = c; win_key = key; }
+        }
+        if (win_key < 0) code = RPE_LINKPOSE_NONE;
+    }
+    if (code != RPE_LINKPOSE_OK) {
+        for (int i = tid; i < max_matches; i += 256) mask[om + i] = 0;
+        if (tid < 9) Rout[link * 9 + tid] = 0.;
+        if (tid < 3) tout[link * 3 + tid] = 0.;
+        if (tid < 2) rms[link * 2 + tid] = 0.;
+        if (tid == 0) {
+            counts[link * 2] = n; counts[link * 2 + 1] = 0;
+            info[link * 4] = code; info[link * 4 + 1] = 0; info[link * 4 + 2] = 0; info[link * 4 + 3] = 0;
+        }
+        return;
+    }
+    // ---- the winner again, on every thread
+    const int win_it = win_key >> 2, win_root = win_key & 3;
+    double Rt[LP_POSE_DOUBLES];
+    {
+        double P[9], q[6], roots[4];
+        LpQuartic g;
+        lp_sample(sub, win_it, cX, cq, P, q);
+        lp_quartic(P, q, g);
+        lp_roots(g.c, roots);
+        double v = roots[0];
+#pragma unroll
+        for (int r = 1; r < 4; ++r) if (r == win_root) v = roots[r];
+        lp_pose(P, g, v, Rt);
+    }
+    // its inlier flags (the candidates are dead: every wave passed the barrier in front of the election)
+    for (int c = tid; c < n; c += 256) s_in[c] = lp_inlier(Rt, cX + 3 * c, cq + 2 * c, thr2) ? 1 : 0;
+    __syncthreads();
+    double R[9], t[3];
+#pragma unroll
+    for (int e = 0; e < 9; ++e) R[e] = Rt[e];
+#pragma unroll
+    for (int e = 0; e < 3; ++e) t[e] = Rt[9 + e];
+    // ---- polish over the winner's inliers
+    double H[21], g[6];
+    auto linearise = [&](double &rtr) {
+        double s[LP_NSUM];
+#pragma unroll
+        for (int k = 0; k < LP_NSUM; ++k) s[k] = 0.;
+        for (int c = tid; c < n; c += 256) {
+            if (!s_in[c]) continue;
+            double rx, ry, Jx[6], Jy[6];
+            lp_residual<true>(R, t, scale, cX + 3 * c, cq + 2 * c, rx, ry, Jx, Jy);
+            int q = 0;
+#pragma unroll
+            for (int u = 0; u < 6; ++u)
+#pragma unroll
+                for (int v = u; v < 6; ++v, ++q) s[q] += Jx[u] * Jx[v] + Jy[u] * Jy[v];
+#pragma unroll
+            for (int u = 0; u < 6; ++u) s[21 + u] += Jx[u] * rx + Jy[u] * ry;
+            s[27] += rx * rx + ry * ry;
+        }
+        block_sum_f64<LP_NSUM>(s, s_red, tid);
+#pragma unroll
+        for (int k = 0; k < 21; ++k) H[k] = s[k];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) g[k] = s[21 + k];
+        rtr = s[27];
+    };
+    double cost0, cost, lambda = REFINE_LAMBDA0;
+    linearise(cost0);
+    cost = cost0;
+    int lm_iters = 0, acc = 0;
+    if (isfinite(cost0)) {
+        bool need_lin = false;
+        for (int it = 0; it < refine_iters; ++it) {
+            if (need_lin) { double dummy; linearise(dummy); need_lin = false; }
+            ++lm_iters;
+            double d[6];
+            if (!refine_solve<6>(H, g, lambda, d)) { lambda = lambda * 10.; continue; }
+            double Rn[9], tn[3];
+            refine_rotate(d, R, Rn);
+#pragma unroll
+            for (int e = 0; e < 3; ++e) tn[e] = t[e] + d[3 + e];
+            double c1[1] = {0.};
+            for (int c = tid; c < n; c += 256) {
+                if (!s_in[c]) continue;
+                double rx, ry;
+                lp_residual<false>(Rn, tn, scale, cX + 3 * c, cq + 2 * c, rx, ry, nullptr, nullptr);
+                c1[0] += rx * rx + ry * ry;
+            }
+            block_sum_f64<1>(c1, s_red, tid);
+            if (isfinite(c1[0]) && c1[0] < cost) {
+                const double dec = cost - c1[0], prev = cost;
+                const double dn = sqrt(((((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) + d[3] * d[3]) + d[4] * d[4]) + d[5] * d[5]);
+#pragma unroll
+                for (int e = 0; e < 9; ++e) R[e] = Rn[e];
+#pragma unroll
+                for (int e = 0; e < 3; ++e) t[e] = tn[e];
+                cost = c1[0]; lambda = lambda / 10.; ++acc; need_lin = true;
+                if (dec <= REFINE_REL_TOL * prev || dn <= REFINE_STEP_TOL) break;
+            } else {
+                lambda = lambda * 10.;
+            }
+        }
+    }
+    // ---- fallback: the polished pose must be finite and keep the winner's count over all correspondences
+    const int m = win_cnt;                                                  // the winner's inliers: the residual set
+    int polish = 0;
+    if (acc > 0) {
+        double Rp[LP_POSE_DOUBLES];
+        bool fin = true;
+#pragma unroll
+        for (int e = 0; e < 9; ++e) { Rp[e] = R[e]; fin = fin && hg_finite(R[e]); }
+#pragma unroll
+        for (int e = 0; e < 3; ++e) { Rp[9 + e] = t[e]; fin = fin && hg_finite(t[e]); }
+        int cnt = 0;
+        for (int c = tid; c < n; c += 256) cnt += lp_inlier(Rp, cX + 3 * c, cq + 2 * c, thr2) ? 1 : 0;
+        cnt = wave_sum(cnt);
+        if (lane == 0) s_cnt[wv] = cnt;
+        __syncthreads();
+        cnt = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+        if (fin && cnt >= win_cnt) {
+            polish = lm_iters;
+            win_cnt = cnt;
+#pragma unroll
+            for (int e = 0; e < LP_POSE_DOUBLES; ++e) Rt[e] = Rp[e];
+        } else
+            polish = -1;
+    }
+    // ---- outputs: the mask by pair b's match index, the pose in pair b's convention
+    for (int i = tid; i < max_matches; i += 256) mask[om + i] = 0;
+    __syncthreads();                                                         // zeros first: another thread sets the inliers
+    for (int c = tid; c < n; c += 256)
+        if (lp_inlier(Rt, cX + 3 * c, cq + 2 * c, thr2)) mask[om + s_idx[c]] = 1;
+    if (tid == 0) {
+        double Ro[9], to[3];
+#pragma unroll
+        for (int r = 0; r < 3; ++r) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) Ro[r * 3 + c] = b2 ? Rt[c * 3 + r] : Rt[r * 3 + c];
+            to[r] = b2 ? -((Rt[r] * Rt[9] + Rt[3 + r] * Rt[10]) + Rt[6 + r] * Rt[11]) : Rt[9 + r];
+        }
+#pragma unroll
+        for (int e = 0; e < 9; ++e) Rout[link * 9 + e] = Ro[e];
+#pragma unroll
+        for (int e = 0; e < 3; ++e) tout[link * 3 + e] = to[e];
+        counts[link * 2] = n; counts[link * 2 + 1] = win_cnt;
+        info[link * 4] = RPE_LINKPOSE_OK; info[link * 4 + 1] = win_it; info[link * 4 + 2] = win_root; info[link * 4 + 3] = polish;
+        const double before = m > 0 ? sqrt(cost0 / m) : 0.;
+        rms[link * 2] = before;
+        rms[link * 2 + 1] = polish > 0 ? sqrt(cost / m) : before;
+    }
+}
+
+// dynamic LDS of link_pose_kernel for max_matches matches and kcap keypoints (the layout at the head of the kernel)
+static size_t link_pose_lds(int mm, int kcap)
+{
+    const size_t bytesA = std::max(sizeof(unsigned) * (size_t)kcap, sizeof(double) * LP_ROUND * 4 * LP_POSE_DOUBLES);
+    return ((bytesA + 15) & ~(size_t)15) + sizeof(double) * 4 * LP_NSUM + (mm <= LP_LDS_MATCHES ? sizeof(double) * 5 * (size_t)mm : 0) +
+           sizeof(unsigned short) * (LP_ROUND * 4 + (size_t)((mm + 7) & ~7)) + sizeof(int) * 32;
+}
+
+// the correspondence lists of this handle fit the kernel's LDS (else rpe_link_poses creates d_lp_corr)
+bool rpe_link_poses_in_lds(const rpe_handle *h) { return h->cfg.max_matches <= LP_LDS_MATCHES; }
+
+// the links in d_links over the last run r (its d_status / d_m_n / d_R / d_t, match indices, d_n1 / d_n2 and the structure
+// buffers) -> d_lp_*.  Raises the kernel's dynamic-LDS limit on first use (never inside a graph capture: only
+// rpe_link_poses comes here); above LP_LDS_MATCHES the lists go to d_lp_corr, which the caller has allocated.
+int rpe_launch_link_poses(rpe_handle *h, const RpeRun &r, int L, int iters, double threshold_px, int min_shared, int refine_iters)
+{
+    const int mm = h->cfg.max_matches, kcap = h->lay.kcap;
+    const size_t lds = link_pose_lds(mm, kcap);
+    // the limit belongs to the kernel, not to the handle: raise it to the most any handle asks for (the cut, or the largest
+    // max_matches; no table is larger than the candidates it shares region A with)
+    const int lds_max = (int)std::max(link_pose_lds(LP_LDS_MATCHES, 0), link_pose_lds(8064, 0));
+    if (lds > (size_t)lds_max) return RPE_ERR_HIP;
+    if (!h->lp_lds_set) {
+        if (hipFuncSetAttribute((const void *)link_pose_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max) != hipSuccess ||
+            hipFuncSetAttribute((const void *)link_pose_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max) != hipSuccess) return RPE_ERR_HIP;
+        h->lp_lds_set = true;
+    }
+    launch_cam(r, link_pose_kernel<true>, link_pose_kernel<false>, dim3(L), dim3(256), lds, h->stream, (const RpeLink *)h->d_links,
+               (const int *)h->d_m_q, (const int *)h->d_m_t, (const int *)h->d_m_n, (const int *)h->d_status,
+               (const uint8_t *)h->d_mask, (const uint8_t *)h->d_pose_mask, (const double *)h->d_points,
+               (const double *)h->d_R, (const double *)h->d_t, (const double2 *)h->d_n1, (const double2 *)h->d_n2,
+               (const unsigned short *)h->d_subsets, (const double *)h->d_K, r.cam, threshold_px, iters, h->cfg.ransac_max_iters,
+               mm, kcap, min_shared, refine_iters, mm <= LP_LDS_MATCHES ? (double *)nullptr : h->d_lp_corr,
+               h->d_lp_R, h->d_lp_t, h->d_lp_mask, h->d_lp_counts, h->d_lp_info, h->d_lp_rms);
     return RPE_OK;
 }

@@ -670,11 +670,11 @@ static int last_run_structure(rpe_handle *h, int B, bool always)
 // | rpe_fetch_overflow                                    | no (served from ovf)  | no             | yes                        | yes, n = n_pairs                      |
 // | rpe_fetch_matched_points, rpe_fetch_match_indices     | yes                   | no             | no                         | no                                    |
 // | rpe_fetch_structure, rpe_refine_poses                 | yes                   | yes            | yes                        | no                                    |
-// | rpe_scale_links                                       | yes                   | yes            | no (checks its links' own) | yes, n = the run's pairs              |
+// | rpe_scale_links, rpe_link_poses                       | yes                   | yes            | no (checks its links' own) | yes, n = the run's pairs              |
 // | rpe_guided_matches(_l2), rpe_pair_homographies        | yes                   | yes            | yes                        | yes, n = B                            |
 //
 // Tested in this order, so a state gives one message whatever the call.  Two tests stay with their only caller:
-// rpe_scale_links' "the pairs of a batch share no frame" and rpe_fetch_overflow's slot range.
+// the link calls' "the pairs of a batch share no frame" and rpe_fetch_overflow's slot range.
 enum : unsigned { NEED_UNCHUNKED = 1, NEED_PER_MATCH = 2, NEED_COUNT = 4, NEED_TABLE = 8 };
 static int last_run_gate(rpe_handle *h, const char *who, int n, unsigned needs)
 {
@@ -1016,43 +1016,85 @@ extern "C" int rpe_fetch_match_indices(rpe_handle *h, int B, int32_t *qidx, int3
     return RPE_OK;
 }
 
-// rpe_scale_links: every check on the host first (the kept pair table of a list, the rule of a stream), then the structure
-// kernels when the per-match buffers do not hold their results for the whole run, the link table, one kernel, one fetch
-extern "C" int rpe_scale_links(rpe_handle *h, int L, const int32_t *pair_a, const int32_t *pair_b, const int32_t *side,
-                               int min_shared, double *stats, int32_t *n_shared, int32_t *code)
+// iters and threshold_px of the calls that run a RANSAC of their own behind the last run (homography, link poses)
+static int homography_check(rpe_handle *h, const char *who, int iters, double threshold_px)
 {
-    if (!h) return rpe_invalid(h, "rpe_scale_links");
-    if (L < 0 || min_shared < 1 || (L > 0 && (!pair_a || !pair_b || !side))) { h->err = "rpe_scale_links: L < 0, min_shared < 1 or a null link array"; return RPE_ERR_INVALID; }
-    int rc = last_run_gate(h, "rpe_scale_links", h->last.pairs, NEED_UNCHUNKED | NEED_PER_MATCH | NEED_TABLE);
+    const std::string w(who);
+    if (iters < 1 || iters > h->cfg.ransac_max_iters) { h->err = w + ": iters must be 1 ... ransac_max_iters"; return RPE_ERR_INVALID; }
+    if (!std::isfinite(threshold_px) || !(threshold_px > 0.)) { h->err = w + ": threshold_px must be finite and > 0"; return RPE_ERR_INVALID; }
+    return RPE_OK;
+}
+
+// The argument head of the calls over links (rpe_scale_links, rpe_link_poses): every check on the host first (the kept
+// pair table of a list, the rule of a stream), then the structure kernels when the per-match buffers do not hold their
+// results for the whole run, and the link table on its way to d_links.  L == 0 passes the checks and does nothing more.
+static int links_begin(rpe_handle *h, const char *who, int L, const int32_t *pair_a, const int32_t *pair_b, const int32_t *side, int min_shared)
+{
+    const std::string w(who);
+    if (L < 0 || min_shared < 1 || (L > 0 && (!pair_a || !pair_b || !side))) { h->err = w + ": L < 0, min_shared < 1 or a null link array"; return RPE_ERR_INVALID; }
+    int rc = last_run_gate(h, who, h->last.pairs, NEED_UNCHUNKED | NEED_PER_MATCH | NEED_TABLE);
     if (rc) return rc;
     const RpeLastRun &l = h->last;
     const bool list = l.kind == RpeLastRun::LIST;
-    if (!list && l.run.feat.img2_base != 1) { h->err = "rpe_scale_links: the pairs of a batch share no frame (links join the pairs of a stream or of a pair list)"; return RPE_ERR_INVALID; }
-    if (L > 4 * h->cfg.max_batch) { h->err = "rpe_scale_links: more than 4*max_batch links in one call"; return RPE_ERR_CAPACITY; }
-    std::vector<RpeLink> tbl((size_t)L);
+    if (!list && l.run.feat.img2_base != 1) { h->err = w + ": the pairs of a batch share no frame (links join the pairs of a stream or of a pair list)"; return RPE_ERR_INVALID; }
+    if (L > 4 * h->cfg.max_batch) { h->err = w + ": more than 4*max_batch links in one call"; return RPE_ERR_CAPACITY; }
+    std::vector<RpeLink> &tbl = h->link_tab;                // outlives the call: the upload below is asynchronous
+    tbl.assign((size_t)L, RpeLink{0, 0, 0, 0});
     for (int i = 0; i < L; ++i) {
         const int a = pair_a[i], b = pair_b[i], s = side[i];
         const char *bad = nullptr;
-        if (a < 0 || a >= l.pairs || b < 0 || b >= l.pairs) bad = "rpe_scale_links: pair index outside the last run";
-        else if (a == b) bad = "rpe_scale_links: a link joins two different pairs";
-        else if (s < 0 || s > 3) bad = "rpe_scale_links: side must be 0 ... 3";
+        if (a < 0 || a >= l.pairs || b < 0 || b >= l.pairs) bad = ": pair index outside the last run";
+        else if (a == b) bad = ": a link joins two different pairs";
+        else if (s < 0 || s > 3) bad = ": side must be 0 ... 3";
         else if (list ? l.tab[(size_t)2 * a + (s & 1)] != l.tab[(size_t)2 * b + (s >> 1)] : a + (s & 1) != b + (s >> 1))
-            bad = "rpe_scale_links: the two pairs do not share the frame the link names";
-        if (bad) { h->err = bad; return RPE_ERR_INVALID; }
+            bad = ": the two pairs do not share the frame the link names";
+        if (bad) { h->err = w + bad; return RPE_ERR_INVALID; }
         tbl[(size_t)i] = {a, b, s, 0};
     }
     if (L == 0) return RPE_OK;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    const size_t lcap = (size_t)4 * h->cfg.max_batch;
-    DM_ONCE(h, h->d_links, lcap); DM_ONCE(h, h->d_link_stats, lcap * 3);
-    DM_ONCE(h, h->d_link_n, lcap); DM_ONCE(h, h->d_link_code, lcap);
+    DM_ONCE(h, h->d_links, (size_t)4 * h->cfg.max_batch);
     if ((rc = last_run_structure(h, l.pairs, false)) != RPE_OK) return rc;
     HIPCHK(h, hipMemcpyAsync(h->d_links, tbl.data(), sizeof(RpeLink) * (size_t)L, hipMemcpyHostToDevice, h->stream));
+    return RPE_OK;
+}
+
+extern "C" int rpe_scale_links(rpe_handle *h, int L, const int32_t *pair_a, const int32_t *pair_b, const int32_t *side,
+                               int min_shared, double *stats, int32_t *n_shared, int32_t *code)
+{
+    if (!h) return rpe_invalid(h, "rpe_scale_links");
+    int rc = links_begin(h, "rpe_scale_links", L, pair_a, pair_b, side, min_shared);
+    if (rc != RPE_OK || L == 0) return rc;
+    const size_t lcap = (size_t)4 * h->cfg.max_batch;
+    DM_ONCE(h, h->d_link_stats, lcap * 3);
+    DM_ONCE(h, h->d_link_n, lcap); DM_ONCE(h, h->d_link_code, lcap);
     if ((rc = rpe_launch_scale_links(h, L, min_shared)) != RPE_OK) { h->err = "rpe_scale_links: could not size the kernel's LDS"; return rc; }
     HIPCHK(h, hipGetLastError());
-    // the wait also covers the upload: the link table has left tbl
     return fetch(h, {{stats, h->d_link_stats, sizeof(double) * 3 * (size_t)L}, {n_shared, h->d_link_n, sizeof(int) * (size_t)L},
                      {code, h->d_link_code, sizeof(int) * (size_t)L}});
+}
+
+// rpe_link_poses: the links' argument head, its own three checks (all before anything is launched), the buffers on first
+// use, one kernel, one fetch.  Nothing of the run is written.
+extern "C" int rpe_link_poses(rpe_handle *h, int L, const int32_t *pair_a, const int32_t *pair_b, const int32_t *side,
+                              int iters, double threshold_px, int min_shared, int refine_iters,
+                              double *R, double *t, uint8_t *mask, int32_t *counts, int32_t *info, double *rms)
+{
+    if (!h) return rpe_invalid(h, "rpe_link_poses");
+    int rc = homography_check(h, "rpe_link_poses", iters, threshold_px);
+    if (rc) return rc;
+    if (refine_iters < 0 || refine_iters > 100) return rpe_invalid(h, "rpe_link_poses", "refine_iters must be 0 ... 100");
+    rc = links_begin(h, "rpe_link_poses", L, pair_a, pair_b, side, min_shared);
+    if (rc != RPE_OK || L == 0) return rc;
+    const size_t lcap = (size_t)4 * h->cfg.max_batch, mm = (size_t)h->cfg.max_matches;
+    DM_ONCE(h, h->d_lp_R, lcap * 9); DM_ONCE(h, h->d_lp_t, lcap * 3); DM_ONCE(h, h->d_lp_rms, lcap * 2);
+    DM_ONCE(h, h->d_lp_counts, lcap * 2); DM_ONCE(h, h->d_lp_info, lcap * 4); DM_ONCE(h, h->d_lp_mask, lcap * mm);
+    if (!rpe_link_poses_in_lds(h)) DM_ONCE(h, h->d_lp_corr, lcap * 5 * mm);
+    if ((rc = rpe_launch_link_poses(h, h->last.run, L, iters, threshold_px, min_shared, refine_iters)) != RPE_OK) { h->err = "rpe_link_poses: could not size the kernel's LDS"; return rc; }
+    HIPCHK(h, hipGetLastError());
+    const size_t n = (size_t)L;
+    return fetch(h, {{R, h->d_lp_R, sizeof(double) * 9 * n}, {t, h->d_lp_t, sizeof(double) * 3 * n}, {mask, h->d_lp_mask, n * mm},
+                     {counts, h->d_lp_counts, sizeof(int) * 2 * n}, {info, h->d_lp_info, sizeof(int) * 4 * n}, {rms, h->d_lp_rms, sizeof(double) * 2 * n}});
 }
 
 // refined poses: device buffers on first use, launch, fetch
@@ -1230,14 +1272,6 @@ extern "C" int rpe_match_l2_guided(rpe_handle *h, const float *h_desc1, const fl
 // rpe_pair_homographies / rpe_find_homography (NOT in the reference): a homography by RANSAC over the matches of a pair,
 // the rotation fitted to its inliers and the three inlier counts.  Results go to the d_hg_* buffers; nothing of the run
 // is written.
-static int homography_check(rpe_handle *h, const char *who, int iters, double threshold_px)
-{
-    const std::string w(who);
-    if (iters < 1 || iters > h->cfg.ransac_max_iters) { h->err = w + ": iters must be 1 ... ransac_max_iters"; return RPE_ERR_INVALID; }
-    if (!std::isfinite(threshold_px) || !(threshold_px > 0.)) { h->err = w + ": threshold_px must be finite and > 0"; return RPE_ERR_INVALID; }
-    return RPE_OK;
-}
-
 static int homography_alloc(rpe_handle *h)
 {
     const size_t MB = (size_t)h->cfg.max_batch;

@@ -340,6 +340,7 @@ struct rpe_handle {
     int *d_ref_inl = nullptr, *d_ref_info = nullptr;
     // rpe_scale_links only (created on first use): link table and outputs, 4*max_batch links
     RpeLink *d_links = nullptr;
+    std::vector<RpeLink> link_tab;        // host side of d_links: the table of the last link call, source of its upload
     double *d_link_stats = nullptr;       // [link][3] lower quartile, median, upper quartile
     int *d_link_n = nullptr, *d_link_code = nullptr;
     bool link_lds_set = false;            // the kernel's dynamic-LDS limit has been raised for this handle's layout
@@ -357,6 +358,13 @@ struct rpe_handle {
     int *d_hg_counts = nullptr, *d_hg_info = nullptr;
     uint8_t *d_hg_mask = nullptr;
     bool hg_lds_set = false;              // the kernel's dynamic-LDS limit has been raised for this handle's layout
+    // rpe_link_poses only (created on first use): per link the pose, {n, inliers}, info[4], rms[2] and the inlier mask
+    // [link][max_matches], 4*max_batch links (the link table is rpe_scale_links' d_links); d_lp_corr [link][5 * max_matches]
+    // holds the correspondence lists of handles above the kernel's LDS cut only
+    double *d_lp_R = nullptr, *d_lp_t = nullptr, *d_lp_rms = nullptr, *d_lp_corr = nullptr;
+    int *d_lp_counts = nullptr, *d_lp_info = nullptr;
+    uint8_t *d_lp_mask = nullptr;
+    bool lp_lds_set = false;              // the kernel's dynamic-LDS limit has been raised
     // results
     double *d_R = nullptr, *d_t = nullptr, *d_E = nullptr;
     int *d_inliers = nullptr, *d_status = nullptr;
@@ -482,6 +490,8 @@ void rpe_launch_pose(rpe_handle *h, const RpeRun &r, bool set_status);
 void rpe_launch_structure(rpe_handle *h, const RpeRun &r);
 void rpe_launch_refine(rpe_handle *h, const RpeRun &r, int max_iters, bool from_batch);
 int rpe_launch_scale_links(rpe_handle *h, int L, int min_shared);
+int rpe_launch_link_poses(rpe_handle *h, const RpeRun &r, int L, int iters, double threshold_px, int min_shared, int refine_iters);
+bool rpe_link_poses_in_lds(const rpe_handle *h);
 void rpe_launch_normalise(rpe_handle *h, const RpeRun &r);
 int rpe_launch_homography(rpe_handle *h, const RpeRun &r, int iters, double threshold_px, bool from_batch);
 void rpe_launch_undistort(rpe_handle *h, const float2 *d_pts, int n, const rpe_camera *d_cam, double2 *d_out);

@@ -108,6 +108,28 @@ def chain_trajectory(R_rel, t_rel, status, ratio, code):
     return R_abs, T_abs, centers, baseline, segment
 
 
+def registered_chain_inputs(R_rel, t_rel, status, ratio, code, R_link, t_link, link_pose_code):
+    """chain_trajectory's five inputs with pair i + 1 taken from link pose i (_capi.Engine.link_poses over the links
+    (i, i + 1, 1)) where link_pose_code[i] is 0 (LINKPOSE_OK): R_link[i], t_link[i] / |t_link[i]| (zero when the link pose
+    has no baseline), ratio |t_link[i]|, status 0, link code 0; the pair's own pose, status and scale link elsewhere.
+    Returns copies (R_rel[P, 3, 3], t_rel[P, 3], status[P], ratio[P - 1], code[P - 1])."""
+    R = np.array(R_rel, np.float64).reshape(-1, 3, 3)
+    P = R.shape[0]
+    t = np.array(t_rel, np.float64).reshape(P, 3)
+    status = np.array(status).reshape(P)
+    ratio = np.array(ratio, np.float64).reshape(-1)
+    code = np.array(code).reshape(-1)
+    R_link = np.asarray(R_link, np.float64).reshape(-1, 3, 3); t_link = np.asarray(t_link, np.float64).reshape(-1, 3)
+    for i in np.flatnonzero(np.asarray(link_pose_code).reshape(-1) == 0):
+        norm = float(np.sqrt(t_link[i] @ t_link[i]))
+        R[i + 1] = R_link[i]
+        t[i + 1] = t_link[i] / norm if norm > 0 else 0.0
+        status[i + 1] = 0
+        ratio[i] = norm
+        code[i] = 0
+    return R, t, status, ratio, code
+
+
 # ---- which model a pair obeys (not in the reference) -------------
 def classify_pair(n_matches, n_E, n_H, n_rot, rotation_ratio=0.7, planar_ratio=0.8):
     """Names the geometric model a pair obeys from the inlier counts of PoseEstimator.last_homographies /

@@ -361,12 +361,27 @@ class PoseEstimator:
             raise ValueError(f"links: expected an integer array of shape [L, 3] (pair_a, pair_b, side), got {a.dtype} {a.shape}")
         return self._last_engine.scale_links(a[:, 0], a[:, 1], a[:, 2], min_shared)
 
-    def estimate_trajectory(self, frames, min_shared=8):
+    def last_link_poses(self, links, iters=256, threshold_px=None, min_shared=8, refine_iters=10):
+        """Pose of pair_b's other frame against the points pair_a triangulated, for links over the last
+        estimate_sequence / estimate_pairs / FrameStore.estimate call (not in the reference;
+        _capi.Engine.link_poses): pair_b's relative pose on pair_a's scale, from pair_b's matches alone -- it needs
+        neither pair_b's essential matrix nor any parallax in pair_b.  links as in last_scale_links.  Returns
+        (R[L, 3, 3], t[L, 3], mask[L, mm], counts[L, 2], info[L, 4], rms[L, 2])."""
+        a = np.asarray(links)
+        if a.ndim != 2 or a.shape[1] != 3 or a.dtype.kind not in "iu":
+            raise ValueError(f"links: expected an integer array of shape [L, 3] (pair_a, pair_b, side), got {a.dtype} {a.shape}")
+        return self._last_engine.link_poses(a[:, 0], a[:, 1], a[:, 2], iters, threshold_px, min_shared, refine_iters)
+
+    def estimate_trajectory(self, frames, min_shared=8, register=False):
         """estimate_sequence plus what relates its poses (not in the reference): the scale link of every two consecutive
         pairs and the chained trajectory (geometry.chain_trajectory).  Returns a dict: 'R', 't', 'inliers', 'status' of
         the F - 1 pairs; 'ratio_stats' [F-2, 3], 'n_shared' [F-2], 'link_code' [F-2] of the links; 'R_abs' [F, 3, 3],
         'T_abs' [F, 3], 'centers' [F, 3], 'baseline' [F-1], 'segment' [F-1].  Distances share a scale only inside a
-        segment; the unit is the baseline of the segment's first pair."""
+        segment; the unit is the baseline of the segment's first pair.
+        register=True adds the link pose of every link (last_link_poses with its defaults and this min_shared): 'R_link'
+        [F-2, 3, 3], 't_link' [F-2, 3], 'link_pose_code' [F-2], 'link_pose_counts' [F-2, 2], and 'R_abs_reg' [F, 3, 3],
+        'centers_reg' [F, 3]: chain_trajectory again with pair i + 1 taken from link i where its code is LINKPOSE_OK
+        (R_link, t_link / |t_link|, ratio |t_link|, status 0) and from the pair's own pose and scale link elsewhere."""
         if self._camera is not None:
             raise ValueError("estimate_trajectory: the camera path has no stream form; use estimate_pairs and last_scale_links")
         R, t, inl, st = self.estimate_sequence(frames)
@@ -374,8 +389,15 @@ class PoseEstimator:
         i = np.arange(P - 1, dtype=np.int32)
         stats, n_shared, code = self._last_engine.scale_links(i, i + 1, np.ones(P - 1, np.int32), min_shared)
         R_abs, T_abs, centers, baseline, segment = geometry.chain_trajectory(R, t, st, stats[:, 1], code)
-        return {'R': R, 't': t, 'inliers': inl, 'status': st, 'ratio_stats': stats, 'n_shared': n_shared, 'link_code': code,
-                'R_abs': R_abs, 'T_abs': T_abs, 'centers': centers, 'baseline': baseline, 'segment': segment}
+        out = {'R': R, 't': t, 'inliers': inl, 'status': st, 'ratio_stats': stats, 'n_shared': n_shared, 'link_code': code,
+               'R_abs': R_abs, 'T_abs': T_abs, 'centers': centers, 'baseline': baseline, 'segment': segment}
+        if register:
+            Rl, tl, _, counts, info, _ = self._last_engine.link_poses(i, i + 1, np.ones(P - 1, np.int32), min_shared=min_shared)
+            Rr, tr, sr, ratio, cr = geometry.registered_chain_inputs(R, t, st, stats[:, 1], code, Rl, tl, info[:, 0])
+            reg = geometry.chain_trajectory(Rr, tr, sr, ratio, cr)
+            out.update({'R_link': Rl, 't_link': tl, 'link_pose_code': info[:, 0], 'link_pose_counts': counts,
+                        'R_abs_reg': reg[0], 'centers_reg': reg[2]})
+        return out
 
     def estimate_sequence(self, frames):
         """Relative poses of consecutive frames (frame i -> i+1): the pair loop of the reference's

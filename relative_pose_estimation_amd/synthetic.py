@@ -187,3 +187,17 @@ def make_stream(n_frames, K, W=640, H=480, seed=5_000_011, max_angle_deg=2.0, st
     t_rel = np.stack([(ts[i + 1] - Rs[i + 1] @ Rs[i].T @ ts[i]) for i in range(lo, hi - 1)])
     t_rel = t_rel / np.linalg.norm(t_rel, axis=1, keepdims=True)
     return np.stack(frames), R_rel, t_rel.reshape(-1, 3, 1)
+
+
+def make_views(Rs, ts, K, W=640, H=480, seed=5_000_011, dist=None):
+    """Views of ONE scene from arbitrary absolute poses: frame i is the scene seen from X_i = Rs[i] X_scene + ts[i]
+    (stream_poses' convention), rendered and noise-seeded per frame exactly as make_stream does (scene seed `seed`, noise
+    seed seed * 31 + i), so make_views(*stream_poses(n, seed=s, ...), K, seed=s) is make_stream's frames.  For sequences a
+    random walk cannot give: a frame rotated about the centre of another (no baseline), loops, arbitrary pair lists.
+    Returns frames u8[n, H, W].  dist as in make_pair."""
+    K = np.asarray(K, np.float64)
+    focal = 0.5 * (K[0, 0] + K[1, 1])
+    Rs = np.asarray(Rs, np.float64).reshape(-1, 3, 3); ts = np.asarray(ts, np.float64).reshape(-1, 3)
+    if Rs.shape[0] != ts.shape[0]:
+        raise ValueError(f"make_views: {Rs.shape[0]} rotations, {ts.shape[0]} translations")
+    return np.stack([_stream_job((K, Rs[i], ts[i], W, H, seed, focal, seed * 31 + i, dist)) for i in range(Rs.shape[0])])

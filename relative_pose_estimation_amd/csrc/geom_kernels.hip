@@ -1098,8 +1098,8 @@ void rpe_launch_pose(rpe_handle *h, const RpeRun &r, bool fused)
 // findEssentialMat's inliers, started from recoverPose's (R, t).  One 256-thread workgroup per pair, f64 throughout.
 //   parameters  R <- exp([w]x) R (Rodrigues), t <- normalise(t + a b1 + b b2), (b1, b2) = tangent basis of the sphere at t
 //   residual    signed Sampson distance of E = [t]x R in pixels (scale (fx + fy) / 2, as the RANSAC threshold)
-//   step        (J'J + lambda diag(J'J)) d = -J'r by 5x5 Cholesky (every lane, identical operands), trial cost in a
-//               second pass, accepted only on a strict decrease (lambda / 10), rejected otherwise (lambda * 10)
+//   step        refine_lm<5>: (J'J + lambda diag(J'J)) d = -J'r by 5x5 Cholesky (every lane, identical operands), trial
+//               cost in a second pass, accepted only on a strict decrease (lambda / 10), rejected otherwise (lambda * 10)
 //   sums        lane partials in strided order -> xor butterfly inside the wave -> the four waves added in wave order
 //               through LDS: no floating-point atomics, bit-deterministic
 //   points      the inliers are compacted in match order once: into LDS (max_matches <= REFINE_LDS_MATCHES: 32 B per
@@ -1286,6 +1286,46 @@ __device__ __forceinline__ bool refine_solve(const double *H, const double *g, d
     return ok;
 }
 
+// The Levenberg-Marquardt loop over N parameters, shared by pose_refine_kernel and link_pose_kernel; all 256 threads call
+// it with identical operands.  s holds the normal equations at (R, t): the upper triangle of J'J, then J'r, then r'r = cost.
+//   linearise()        s at the caller's (R, t), summed over the workgroup (block_sum_f64 over all of s)
+//   trial(d, Rn, tn)   the pose (Rn, tn) that step d leads to from (R, t), and this thread's part of its cost
+// A failed solve or a step that does not strictly lower the cost multiplies lambda by 10; an accepted step divides it by
+// 10, moves (R, t, cost) and stops the loop when it lowered the cost by no more than REFINE_REL_TOL of it or is no longer
+// than REFINE_STEP_TOL.  (R, t) is linearised again only when another iteration follows an accepted step.  iters counts
+// the iterations begun, acc the steps accepted.
+template <int N, class Linearise, class Trial>
+__device__ __forceinline__ void refine_lm(double (&R)[9], double (&t)[3], const double (&s)[N * (N + 1) / 2 + N + 1], double &cost,
+                                          int max_iters, double *s_red, Linearise linearise, Trial trial, int &iters, int &acc)
+{
+    double lambda = REFINE_LAMBDA0;
+    bool need_lin = false;
+    for (int it = 0; it < max_iters; ++it) {
+        if (need_lin) { linearise(); need_lin = false; }
+        ++iters;
+        double d[N];
+        if (!refine_solve<N>(s, s + N * (N + 1) / 2, lambda, d)) { lambda = lambda * 10.; continue; }
+        double Rn[9], tn[3];
+        double c1[1] = {trial(d, Rn, tn)};
+        block_sum_f64<1>(c1, s_red, threadIdx.x);
+        if (isfinite(c1[0]) && c1[0] < cost) {
+            const double dec = cost - c1[0], prev = cost;
+            double dn = d[0] * d[0];
+#pragma unroll
+            for (int k = 1; k < N; ++k) dn = dn + d[k] * d[k];
+            dn = sqrt(dn);
+#pragma unroll
+            for (int e = 0; e < 9; ++e) R[e] = Rn[e];
+#pragma unroll
+            for (int e = 0; e < 3; ++e) t[e] = tn[e];
+            cost = c1[0]; lambda = lambda / 10.; ++acc; need_lin = true;
+            if (dec <= REFINE_REL_TOL * prev || dn <= REFINE_STEP_TOL) break;
+        } else {
+            lambda = lambda * 10.;
+        }
+    }
+}
+
 // status / inl_in may be null (stage form): every pair is then refined and the input pose's cheirality inliers are counted here
 template <bool LDS, bool CAM>
 __global__ __launch_bounds__(256) void pose_refine_kernel(const double2 *__restrict__ n1, const double2 *__restrict__ n2,
@@ -1330,13 +1370,13 @@ __global__ __launch_bounds__(256) void pose_refine_kernel(const double2 *__restr
         if (LDS) { a = l1[j]; b = l2[j]; }
         else { const int i = s_idx[j]; a = gp1[i]; b = gp2[i]; }
     };
-    double H[15], g[5], b1[3], b2[3];
-    double cost = 0., cost0 = 0., lambda = REFINE_LAMBDA0;
+    double s[REFINE_NSUM], b1[3], b2[3];
+    double cost = 0., cost0 = 0.;
     int iters = 0, acc = 0;
     bool finite = true;
-    auto linearise = [&](double &rtr) {
+    // also leaves the tangent basis at t in (b1, b2) for the trial steps
+    auto linearise = [&]() {
         refine_basis(t, b1, b2);
-        double s[REFINE_NSUM];
 #pragma unroll
         for (int k = 0; k < REFINE_NSUM; ++k) s[k] = 0.;
         for (int j = tid; j < n; j += 256) {
@@ -1353,51 +1393,30 @@ __global__ __launch_bounds__(256) void pose_refine_kernel(const double2 *__restr
             s[20] += r * r;
         }
         block_sum_f64<REFINE_NSUM>(s, s_red, tid);
-#pragma unroll
-        for (int k = 0; k < 15; ++k) H[k] = s[k];
-#pragma unroll
-        for (int k = 0; k < 5; ++k) g[k] = s[15 + k];
-        rtr = s[20];
     };
     const bool skip = !st_ok || n < REFINE_MIN_RESIDUALS;
+    // R <- exp([w]x) R, t <- normalise(t + d3 b1 + d4 b2)
+    auto trial = [&](const double (&d)[5], double (&Rn)[9], double (&tn)[3]) {
+        refine_rotate(d, R, Rn);
+#pragma unroll
+        for (int e = 0; e < 3; ++e) tn[e] = (t[e] + d[3] * b1[e]) + d[4] * b2[e];
+        const double nt = sqrt((tn[0] * tn[0] + tn[1] * tn[1]) + tn[2] * tn[2]);
+        tn[0] /= nt; tn[1] /= nt; tn[2] /= nt;
+        double c = 0.;
+        for (int j = tid; j < n; j += 256) {
+            double2 a, b; fetch(j, a, b);
+            const double r = refine_residual<false>(Rn, tn, b1, b2, scale, a.x, a.y, b.x, b.y, nullptr);
+            c += r * r;
+        }
+        return c;
+    };
     if (n > 0) {
-        linearise(cost0);
-        cost = cost0;
+        linearise();
+        cost = cost0 = s[20];
         finite = isfinite(cost0);
     }
     if (!skip && finite) {
-        bool need_lin = false;
-        for (int it = 0; it < max_iters; ++it) {
-            if (need_lin) { double dummy; linearise(dummy); need_lin = false; }
-            ++iters;
-            double d[5];
-            if (!refine_solve<5>(H, g, lambda, d)) { lambda = lambda * 10.; continue; }
-            double Rn[9], tn[3];
-            refine_rotate(d, R, Rn);
-#pragma unroll
-            for (int e = 0; e < 3; ++e) tn[e] = (t[e] + d[3] * b1[e]) + d[4] * b2[e];
-            const double nt = sqrt((tn[0] * tn[0] + tn[1] * tn[1]) + tn[2] * tn[2]);
-            tn[0] /= nt; tn[1] /= nt; tn[2] /= nt;
-            double c1[1] = {0.};
-            for (int j = tid; j < n; j += 256) {
-                double2 a, b; fetch(j, a, b);
-                const double r = refine_residual<false>(Rn, tn, b1, b2, scale, a.x, a.y, b.x, b.y, nullptr);
-                c1[0] += r * r;
-            }
-            block_sum_f64<1>(c1, s_red, tid);
-            if (isfinite(c1[0]) && c1[0] < cost) {
-                const double dec = cost - c1[0], prev = cost;
-                const double dn = sqrt((((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) + d[3] * d[3]) + d[4] * d[4]);
-#pragma unroll
-                for (int e = 0; e < 9; ++e) R[e] = Rn[e];
-#pragma unroll
-                for (int e = 0; e < 3; ++e) t[e] = tn[e];
-                cost = c1[0]; lambda = lambda / 10.; ++acc; need_lin = true;
-                if (dec <= REFINE_REL_TOL * prev || dn <= REFINE_STEP_TOL) break;
-            } else {
-                lambda = lambda * 10.;
-            }
-        }
+        refine_lm<5>(R, t, s, cost, max_iters, s_red, linearise, trial, iters, acc);
 #pragma unroll
         for (int e = 0; e < 9; ++e) finite = finite && isfinite(R[e]);
 #pragma unroll
@@ -1478,10 +1497,11 @@ void rpe_launch_refine(rpe_handle *h, const RpeRun &r, int max_iters, bool from_
 // rpe_scale_links (NOT in the reference; include/rpe_amd.h states the rules): the baseline of pair b in units of the
 // baseline of pair a, from the keypoints of the frame the two pairs share that both triangulated.  One 256-thread
 // workgroup per link, f64 throughout, everything between the per-match buffers and the three results stays in LDS.
-//   table   one word per keypoint of the shared frame: high half = lowest usable match index of pair a, low half = of
-//           pair b, 0xFFFF = none (max_matches <= 8064).  Pass 1: a's usable matches atomicMin (index << 16 | 0xFFFF):
-//           every low half is still 0xFFFF, so the minimum orders the high halves.  Pass 2: b's usable matches whose key
-//           has an a entry atomicMin (that high half << 16 | index): equal high halves, the minimum orders the low ones.
+//   table   (link_join) one word per keypoint of the shared frame: high half = lowest usable match index of pair a, low
+//           half = of pair b, 0xFFFF = none (max_matches <= 8064).  Pass 1: a's usable matches atomicMin (index << 16 |
+//           0xFFFF): every low half is still 0xFFFF, so the minimum orders the high halves.  Pass 2: b's usable matches
+//           whose key has an a entry atomicMin (that high half << 16 | index): equal high halves, the minimum orders the
+//           low ones.
 //   ratios  pass 3: b's matches that won their key compute d_a / d_b and append it to an LDS array (integer atomicAdd on
 //           the fill count: the order inside the array varies run to run, the set does not)
 //   ranks   bitonic sort of the array, padded with +inf to a power of two; the three results are elements of the sorted
@@ -1492,16 +1512,53 @@ void rpe_launch_refine(rpe_handle *h, const RpeRun &r, int max_iters, bool from_
 // The link, the two pairs' status, match counts, R and t come from blockIdx-indexed reads: uniform, scalar loads.
 #define LINK_NONE 0xFFFFu
 
-__device__ __forceinline__ double link_distance(const double *__restrict__ P, const double (&R)[9], const double (&t)[3], bool image2)
+// the triangulated point P of a pair with pose (R, t) in the shared frame's coordinates: P itself when the shared frame is
+// the pair's image 1, R P + t when it is its image 2
+__device__ __forceinline__ void link_point(const double *__restrict__ P, const double (&R)[9], const double (&t)[3], bool image2,
+                                           double &x, double &y, double &z)
 {
-    double x = P[0], y = P[1], z = P[2];
+    x = P[0]; y = P[1]; z = P[2];
     if (image2) {
         const double X = x, Y = y, Z = z;
         x = ((R[0] * X + R[1] * Y) + R[2] * Z) + t[0];
         y = ((R[3] * X + R[4] * Y) + R[5] * Z) + t[1];
         z = ((R[6] * X + R[7] * Y) + R[8] * Z) + t[2];
     }
+}
+
+__device__ __forceinline__ double link_distance(const double *__restrict__ P, const double (&R)[9], const double (&t)[3], bool image2)
+{
+    double x, y, z;
+    link_point(P, R, t, image2, x, y, z);
     return sqrt((x * x + y * y) + z * z);
+}
+
+// The table of the header in s_tab[kcap], for pairs a and b of a link: key_a / key_b their matches' keypoint indices in the
+// shared frame, na / nb their match counts, oa / ob their offsets into the two masks.  A match of a is usable when both
+// masks hold it; FILTER_B asks the same of b's matches, else every match of b takes part.  All 256 threads call it (three
+// barriers, the last behind pass 2: the table is final on return).
+template <bool FILTER_B>
+__device__ __forceinline__ void link_join(unsigned *s_tab, int kcap, const int *__restrict__ key_a, int na, long long oa,
+                                          const int *__restrict__ key_b, int nb, long long ob,
+                                          const uint8_t *__restrict__ ransac_mask, const uint8_t *__restrict__ pose_mask)
+{
+    const int tid = threadIdx.x;
+    for (int k = tid; k < kcap; k += 256) s_tab[k] = 0xFFFFFFFFu;
+    __syncthreads();
+    for (int i = tid; i < na; i += 256) {
+        if (!(ransac_mask[oa + i] && pose_mask[oa + i])) continue;
+        const int key = key_a[i];
+        if ((unsigned)key < (unsigned)kcap) atomicMin(&s_tab[key], ((unsigned)i << 16) | LINK_NONE);
+    }
+    __syncthreads();
+    for (int i = tid; i < nb; i += 256) {
+        if (FILTER_B && !(ransac_mask[ob + i] && pose_mask[ob + i])) continue;
+        const int key = key_b[i];
+        if ((unsigned)key >= (unsigned)kcap) continue;
+        const unsigned e = s_tab[key];                      // the high half is final since the barrier
+        if ((e >> 16) != LINK_NONE) atomicMin(&s_tab[key], (e & 0xFFFF0000u) | (unsigned)i);
+    }
+    __syncthreads();
 }
 
 __global__ __launch_bounds__(256) void scale_links_kernel(const RpeLink *__restrict__ links, const int *__restrict__ m_q,
@@ -1527,23 +1584,8 @@ __global__ __launch_bounds__(256) void scale_links_kernel(const RpeLink *__restr
     const int na = min(m_n[lk.a], max_matches), nb = min(m_n[lk.b], max_matches);
     const long long oa = (long long)lk.a * max_matches, ob = (long long)lk.b * max_matches;
     const int *key_a = (a2 ? m_t : m_q) + oa, *key_b = (b2 ? m_t : m_q) + ob;
-    for (int k = tid; k < kcap; k += 256) s_tab[k] = 0xFFFFFFFFu;
     if (tid == 0) *s_fill = 0;
-    __syncthreads();
-    for (int i = tid; i < na; i += 256) {
-        if (!(ransac_mask[oa + i] && pose_mask[oa + i])) continue;
-        const int key = key_a[i];
-        if ((unsigned)key < (unsigned)kcap) atomicMin(&s_tab[key], ((unsigned)i << 16) | LINK_NONE);
-    }
-    __syncthreads();
-    for (int i = tid; i < nb; i += 256) {
-        if (!(ransac_mask[ob + i] && pose_mask[ob + i])) continue;
-        const int key = key_b[i];
-        if ((unsigned)key >= (unsigned)kcap) continue;
-        const unsigned e = s_tab[key];                      // the high half is final since the barrier
-        if ((e >> 16) != LINK_NONE) atomicMin(&s_tab[key], (e & 0xFFFF0000u) | (unsigned)i);
-    }
-    __syncthreads();
+    link_join<true>(s_tab, kcap, key_a, na, oa, key_b, nb, ob, ransac_mask, pose_mask);
     double Ra[9], ta[3], Rb[9], tb[3];
 #pragma unroll
     for (int e = 0; e < 9; ++e) { Ra[e] = Rall[lk.a * 9 + e]; Rb[e] = Rall[lk.b * 9 + e]; }
@@ -1581,19 +1623,41 @@ __global__ __launch_bounds__(256) void scale_links_kernel(const RpeLink *__restr
     if (tid == 0) { n_shared[link] = n; code[link] = ok ? RPE_LINK_OK : RPE_LINK_TOO_FEW; }
 }
 
+// A launch with more than 64 KB of dynamic LDS needs the kernels' limit raised first, once per device: the launchers of
+// scale links, homographies and link poses call this when their handle asks for that much.  The limit belongs to the
+// kernel, not to the handle, so lds_max is the most any legal handle asks of these kernels; the handle records the
+// kernels it has raised.  Never inside a graph capture: rpe_scale_links, rpe_pair_homographies / rpe_find_homography and
+// rpe_link_poses alone come here.
+static int raise_lds_limit(rpe_handle *h, std::initializer_list<const void *> kernels, size_t lds_max)
+{
+    for (const void *k : kernels) {
+        if (std::find(h->lds_raised.begin(), h->lds_raised.end(), k) != h->lds_raised.end()) continue;
+        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max) != hipSuccess) return RPE_ERR_HIP;
+        h->lds_raised.push_back(k);
+    }
+    return RPE_OK;
+}
+
+// sort_cap and the dynamic LDS of scale_links_kernel for max_matches matches and kcap keypoints (the layout at the head of
+// the section)
+static int scale_links_sort_cap(int mm)
+{
+    int sort_cap = 8;
+    while (sort_cap < mm) sort_cap <<= 1;
+    return sort_cap;
+}
+static size_t scale_links_lds(int mm, int kcap) { return sizeof(double) * (size_t)scale_links_sort_cap(mm) + sizeof(unsigned) * (size_t)kcap + 16; }
+
 // the last run's d_status / d_m_n / d_R / d_t, its match indices and the structure buffers -> d_link_stats / _n / _code of
-// the L links in d_links.  Raises the kernel's dynamic-LDS limit on first use (never inside a graph capture: only
-// rpe_scale_links comes here)
+// the L links in d_links
 int rpe_launch_scale_links(rpe_handle *h, int L, int min_shared)
 {
     const int mm = h->cfg.max_matches, kcap = h->lay.kcap;
-    int sort_cap = 8;
-    while (sort_cap < mm) sort_cap <<= 1;
-    const size_t lds = sizeof(double) * (size_t)sort_cap + sizeof(unsigned) * (size_t)kcap + 16;
-    if (lds > 65536 && !h->link_lds_set) {
-        if (hipFuncSetAttribute((const void *)scale_links_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) return RPE_ERR_HIP;
-        h->link_lds_set = true;
-    }
+    const int sort_cap = scale_links_sort_cap(mm);
+    const size_t lds = scale_links_lds(mm, kcap);
+    // the most: 8064 matches of uncapped SIFT's keypoints
+    if (lds > 65536 && raise_lds_limit(h, {(const void *)scale_links_kernel}, scale_links_lds(8064, RPE_SIFT_UNCAPPED_CAPACITY + 64)) != RPE_OK)
+        return RPE_ERR_HIP;
     hipLaunchKernelGGL(scale_links_kernel, dim3(L), dim3(256), lds, h->stream, (const RpeLink *)h->d_links,
                        (const int *)h->d_m_q, (const int *)h->d_m_t, (const int *)h->d_m_n, (const int *)h->d_status,
                        (const uint8_t *)h->d_mask, (const uint8_t *)h->d_pose_mask, (const double *)h->d_points,
@@ -1610,7 +1674,7 @@ int rpe_launch_scale_links(rpe_handle *h, int L, int min_shared)
 //            scratch) and parks H and G = adj(H), 18 doubles, in LDS; the four waves then score the round's valid models
 //            round-robin (wave w: models w, w + 4, ...), lanes striding the matches, wave_sum for the count.  A wave meets
 //            its models in ascending iteration order and replaces its best on a strictly larger count only, so its best
-//            is its lowest iteration of that count; the cross-wave election compares (count, iteration).
+//            is its lowest iteration of that count; the cross-wave election (elect_best) compares (count, iteration).
 //   points   the pair's normalised points in LDS behind the models, as ransac_score_kernel holds them
 //            (max_matches <= HG_LDS_MATCHES: 32 B per match); read from d_n1 / d_n2 directly above the cut
 //   winner   solved again by every thread from its sample (the same code on the same operands: the same bits), then the
@@ -1804,13 +1868,8 @@ __global__ __launch_bounds__(256) void homography_kernel(const double2 *__restri
             }
         }
         nvalid = wave_sum(nvalid);
-        if (lane == 0) { s_best[wv * 2] = best_cnt; s_best[wv * 2 + 1] = best_it; atomicAdd(&s_nvalid, nvalid); }
-        __syncthreads();
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const int c = s_best[w * 2], it = s_best[w * 2 + 1];
-            if (it >= 0 && (c > win_cnt || (c == win_cnt && it < win_it))) { win_cnt = c; win_it = it; }
-        }
+        if (lane == 0) atomicAdd(&s_nvalid, nvalid);
+        elect_best(best_cnt, best_it, s_best, win_cnt, win_it);
         nvalid_all = s_nvalid;
         if (win_it < 0) code = RPE_HOMOGRAPHY_NONE;
     }
@@ -1860,11 +1919,8 @@ __global__ __launch_bounds__(256) void homography_kernel(const double2 *__restri
             nrot += (hg_transfer(R, a.x, a.y, b.x, b.y, thr2) && hg_transfer(Rt, b.x, b.y, a.x, a.y, thr2)) ? 1 : 0;
         }
     }
-    nrot = wave_sum(nrot);
-    if (lane == 0) s_cnt[wv] = nrot;
-    __syncthreads();
+    nrot = block_count(nrot, s_cnt);
     if (tid == 0) {
-        nrot = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
 #pragma unroll
         for (int e = 0; e < 9; ++e) { Hout[pair * 9 + e] = H[e]; Rout[pair * 9 + e] = fin ? R[e] : 0.; }
         counts[pair * 3] = win_cnt; counts[pair * 3 + 1] = nrot; counts[pair * 3 + 2] = nE;
@@ -1873,20 +1929,16 @@ __global__ __launch_bounds__(256) void homography_kernel(const double2 *__restri
 }
 
 // d_n1 / d_n2 (the run's, or rpe_launch_normalise's in the stage form) -> d_hg_*.  from_batch: the run's d_status and
-// d_rstate gate the pairs and supply n_E.  Raises the kernel's dynamic-LDS limit on first use (never inside a graph
-// capture: only rpe_pair_homographies / rpe_find_homography come here).
+// d_rstate gate the pairs and supply n_E.
 int rpe_launch_homography(rpe_handle *h, const RpeRun &r, int iters, double threshold_px, bool from_batch)
 {
     const int mm = h->cfg.max_matches;
     const int use_lds = mm <= HG_LDS_MATCHES;
     const size_t lds = sizeof(double) * HG_ROUND * HG_MODEL_DOUBLES + (use_lds ? sizeof(double2) * 2 * (size_t)mm : 0);
-    if (lds > 65536 && !h->hg_lds_set) {
-        // the limit belongs to the kernel, not to the handle: raise it to the most any handle asks for (the cut)
-        const int lds_max = (int)(sizeof(double) * HG_ROUND * HG_MODEL_DOUBLES + sizeof(double2) * 2 * HG_LDS_MATCHES);
-        if (hipFuncSetAttribute((const void *)homography_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max) != hipSuccess ||
-            hipFuncSetAttribute((const void *)homography_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max) != hipSuccess) return RPE_ERR_HIP;
-        h->hg_lds_set = true;
-    }
+    // the most: the points of the cut
+    const size_t lds_max = sizeof(double) * HG_ROUND * HG_MODEL_DOUBLES + sizeof(double2) * 2 * HG_LDS_MATCHES;
+    if (lds > 65536 && raise_lds_limit(h, {(const void *)homography_kernel<true>, (const void *)homography_kernel<false>}, lds_max) != RPE_OK)
+        return RPE_ERR_HIP;
     launch_cam(r, homography_kernel<true>, homography_kernel<false>, dim3(r.pairs), dim3(256), lds, h->stream,
                (const double2 *)h->d_n1, (const double2 *)h->d_n2, (const int *)h->d_m_n,
                from_batch ? (const int *)h->d_status : (const int *)nullptr,
@@ -1900,21 +1952,21 @@ int rpe_launch_homography(rpe_handle *h, const RpeRun &r, int iters, double thre
 // rpe_link_poses (NOT in the reference; include/rpe_amd.h states the rule): the pose of pair b's other frame C against the
 // points pair a triangulated, by P3P RANSAC over the keypoints of the shared frame S, on pair a's scale.  One 256-thread
 // workgroup per link, f64 throughout, no contraction.
-//   join     scale_links_kernel's packed table (high half: lowest usable match of a, low half: lowest match of b; here
-//            every match of b takes part).  The winners of b are then compacted in match order by ordered_slot (ballot /
-//            popcount): correspondence c = the c-th winner, so no atomic decides an order.
-//   list     per correspondence X (3 f64, in S's frame), q (2 f64) and b's match index (u16).  X and q live in LDS up to
-//            LP_LDS_MATCHES matches (40 B each: 20 KB at the default 500) and in d_lp_corr above it; both forms are
-//            walked through the same pointers in the same order.  The indices are always in LDS.
-//   rounds   homography_kernel's: LP_ROUND = 256 samples at a time, thread j solves sample j in registers (quartic, the
+//   join     link_join's packed table (high half: lowest usable match of a, low half: lowest match of b; here every match
+//            of b takes part).  The winners of b are then compacted in match order by ordered_slot (ballot / popcount):
+//            correspondence c = the c-th winner, so no atomic decides an order.
+//   list     per correspondence X (3 f64, link_point: in S's frame), q (2 f64) and b's match index (u16).  X and q live in
+//            LDS up to LP_LDS_MATCHES matches (40 B each: 20 KB at the default 500) and in d_lp_corr above it; both forms
+//            are walked through the same pointers in the same order.  The indices are always in LDS.
+//   rounds   as the homography's: LP_ROUND = 256 samples at a time, thread j solves sample j in registers (quartic, the
 //            derivative chain with static indices, up to four poses) and parks its candidates at slot 4 j + root; the
 //            slots of the valid ones are listed densely in (iteration, root) order (block_excl_scan of the per-thread
 //            counts).  The four waves score the dense list round-robin, lanes striding the correspondences, wave_sum
 //            for the count; a wave meets its candidates in ascending (iteration, root) order and replaces its best on a
-//            strictly larger count only; the cross-wave election compares (count, 4 * iteration + root).
+//            strictly larger count only; the cross-wave election (elect_best) compares (count, 4 * iteration + root).
 //   winner   solved again by every thread (the same code on the same operands: the same bits), its inlier flags, then the
-//            polish: pose_refine_kernel's loop with six parameters on the reprojection residuals (block_sum_f64 sums,
-//            refine_solve<6>, refine_rotate), and the fallback test over all correspondences.
+//            polish: refine_lm<6> on the reprojection residuals (block_sum_f64 sums, refine_rotate), and the fallback
+//            test over all correspondences.
 // Dynamic LDS (all of the kernel's LDS, base 16-byte aligned):
 //   [A] max(kcap u32 table, LP_ROUND * 4 poses of 12 f64 = 96 KB): the table is dead once the list is built, the poses
 //       once the election is over (the winner's inlier flags then live there)
@@ -2140,21 +2192,7 @@ __global__ __launch_bounds__(256) void link_pose_kernel(const RpeLink *__restric
         const long long oa = (long long)lk.a * max_matches, ob = (long long)lk.b * max_matches;
         const int *key_a = (a2 ? m_t : m_q) + oa, *key_b = (b2 ? m_t : m_q) + ob;
         const double2 *obs = (b2 ? n1 : n2) + ob;                            // b's point on C, its frame that is not shared
-        for (int k = tid; k < kcap; k += 256) s_tab[k] = 0xFFFFFFFFu;
-        __syncthreads();
-        for (int i = tid; i < na; i += 256) {
-            if (!(ransac_mask[oa + i] && pose_mask[oa + i])) continue;
-            const int key = key_a[i];
-            if ((unsigned)key < (unsigned)kcap) atomicMin(&s_tab[key], ((unsigned)i << 16) | LINK_NONE);
-        }
-        __syncthreads();
-        for (int i = tid; i < nb; i += 256) {
-            const int key = key_b[i];
-            if ((unsigned)key >= (unsigned)kcap) continue;
-            const unsigned e = s_tab[key];                                   // the high half is final since the barrier
-            if ((e >> 16) != LINK_NONE) atomicMin(&s_tab[key], (e & 0xFFFF0000u) | (unsigned)i);
-        }
-        __syncthreads();
+        link_join<false>(s_tab, kcap, key_a, na, oa, key_b, nb, ob, ransac_mask, pose_mask);
         double Ra[9], ta[3];
 #pragma unroll
         for (int e = 0; e < 9; ++e) Ra[e] = Rall[lk.a * 9 + e];
@@ -2167,14 +2205,8 @@ __global__ __launch_bounds__(256) void link_pose_kernel(const RpeLink *__restric
             const bool f = i < nb && (e >> 16) != LINK_NONE && (e & 0xFFFFu) == (unsigned)i;
             const int pos = ordered_slot(f, s_wc, n);
             if (f) {
-                const double *Pm = points + (oa + (e >> 16)) * 3;
-                double x = Pm[0], y = Pm[1], z = Pm[2];
-                if (a2) {                                                    // link_distance's expression and order
-                    const double X = x, Y = y, Z = z;
-                    x = ((Ra[0] * X + Ra[1] * Y) + Ra[2] * Z) + ta[0];
-                    y = ((Ra[3] * X + Ra[4] * Y) + Ra[5] * Z) + ta[1];
-                    z = ((Ra[6] * X + Ra[7] * Y) + Ra[8] * Z) + ta[2];
-                }
+                double x, y, z;
+                link_point(points + (oa + (e >> 16)) * 3, Ra, ta, a2, x, y, z);
                 const double2 o = obs[i];
                 // the table and an LDS list share no bytes: s_corr lies behind region A
                 cX[3 * pos] = x; cX[3 * pos + 1] = y; cX[3 * pos + 2] = z;
@@ -2231,13 +2263,7 @@ __global__ __launch_bounds__(256) void link_pose_kernel(const RpeLink *__restric
                 if (cnt > best_cnt) { best_cnt = cnt; best_key = (base + (id >> 2)) * 4 + (id & 3); }
             }
         }
-        if (lane == 0) { s_best[wv * 2] = best_cnt; s_best[wv * 2 + 1] = best_key; }
-        __syncthreads();
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            const int c = s_best[w * 2], key = s_best[w * 2 + 1];
-            if (key >= 0 && (c > win_cnt || (c == win_cnt && key < win_key))) { win_cnt = c; win_key = key; }
-        }
+        elect_best(best_cnt, best_key, s_best, win_cnt, win_key);
         if (win_key < 0) code = RPE_LINKPOSE_NONE;
     }
     if (code != RPE_LINKPOSE_OK) {
@@ -2265,7 +2291,7 @@ __global__ __launch_bounds__(256) void link_pose_kernel(const RpeLink *__restric
         for (int r = 1; r < 4; ++r) if (r == win_root) v = roots[r];
         lp_pose(P, g, v, Rt);
     }
-    // its inlier flags (the candidates are dead: every wave passed the barrier in front of the election)
+    // its inlier flags (the candidates are dead: every wave passed the barrier of the election)
     for (int c = tid; c < n; c += 256) s_in[c] = lp_inlier(Rt, cX + 3 * c, cq + 2 * c, thr2) ? 1 : 0;
     __syncthreads();
     double R[9], t[3];
@@ -2274,9 +2300,8 @@ __global__ __launch_bounds__(256) void link_pose_kernel(const RpeLink *__restric
 #pragma unroll
     for (int e = 0; e < 3; ++e) t[e] = Rt[9 + e];
     // ---- polish over the winner's inliers
-    double H[21], g[6];
-    auto linearise = [&](double &rtr) {
-        double s[LP_NSUM];
+    double s[LP_NSUM];
+    auto linearise = [&]() {
 #pragma unroll
         for (int k = 0; k < LP_NSUM; ++k) s[k] = 0.;
         for (int c = tid; c < n; c += 256) {
@@ -2293,49 +2318,26 @@ __global__ __launch_bounds__(256) void link_pose_kernel(const RpeLink *__restric
             s[27] += rx * rx + ry * ry;
         }
         block_sum_f64<LP_NSUM>(s, s_red, tid);
-#pragma unroll
-        for (int k = 0; k < 21; ++k) H[k] = s[k];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) g[k] = s[21 + k];
-        rtr = s[27];
     };
-    double cost0, cost, lambda = REFINE_LAMBDA0;
-    linearise(cost0);
-    cost = cost0;
-    int lm_iters = 0, acc = 0;
-    if (isfinite(cost0)) {
-        bool need_lin = false;
-        for (int it = 0; it < refine_iters; ++it) {
-            if (need_lin) { double dummy; linearise(dummy); need_lin = false; }
-            ++lm_iters;
-            double d[6];
-            if (!refine_solve<6>(H, g, lambda, d)) { lambda = lambda * 10.; continue; }
-            double Rn[9], tn[3];
-            refine_rotate(d, R, Rn);
+    // R <- exp([w]x) R, t <- t + (d3 d4 d5)
+    auto trial = [&](const double (&d)[6], double (&Rn)[9], double (&tn)[3]) {
+        refine_rotate(d, R, Rn);
 #pragma unroll
-            for (int e = 0; e < 3; ++e) tn[e] = t[e] + d[3 + e];
-            double c1[1] = {0.};
-            for (int c = tid; c < n; c += 256) {
-                if (!s_in[c]) continue;
-                double rx, ry;
-                lp_residual<false>(Rn, tn, scale, cX + 3 * c, cq + 2 * c, rx, ry, nullptr, nullptr);
-                c1[0] += rx * rx + ry * ry;
-            }
-            block_sum_f64<1>(c1, s_red, tid);
-            if (isfinite(c1[0]) && c1[0] < cost) {
-                const double dec = cost - c1[0], prev = cost;
-                const double dn = sqrt(((((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) + d[3] * d[3]) + d[4] * d[4]) + d[5] * d[5]);
-#pragma unroll
-                for (int e = 0; e < 9; ++e) R[e] = Rn[e];
-#pragma unroll
-                for (int e = 0; e < 3; ++e) t[e] = tn[e];
-                cost = c1[0]; lambda = lambda / 10.; ++acc; need_lin = true;
-                if (dec <= REFINE_REL_TOL * prev || dn <= REFINE_STEP_TOL) break;
-            } else {
-                lambda = lambda * 10.;
-            }
+        for (int e = 0; e < 3; ++e) tn[e] = t[e] + d[3 + e];
+        double cs = 0.;
+        for (int c = tid; c < n; c += 256) {
+            if (!s_in[c]) continue;
+            double rx, ry;
+            lp_residual<false>(Rn, tn, scale, cX + 3 * c, cq + 2 * c, rx, ry, nullptr, nullptr);
+            cs += rx * rx + ry * ry;
         }
-    }
+        return cs;
+    };
+    linearise();
+    const double cost0 = s[27];
+    double cost = cost0;
+    int lm_iters = 0, acc = 0;
+    if (isfinite(cost0)) refine_lm<6>(R, t, s, cost, refine_iters, s_red, linearise, trial, lm_iters, acc);
     // ---- fallback: the polished pose must be finite and keep the winner's count over all correspondences
     const int m = win_cnt;                                                  // the winner's inliers: the residual set
     int polish = 0;
@@ -2348,10 +2350,7 @@ __global__ __launch_bounds__(256) void link_pose_kernel(const RpeLink *__restric
         for (int e = 0; e < 3; ++e) { Rp[9 + e] = t[e]; fin = fin && hg_finite(t[e]); }
         int cnt = 0;
         for (int c = tid; c < n; c += 256) cnt += lp_inlier(Rp, cX + 3 * c, cq + 2 * c, thr2) ? 1 : 0;
-        cnt = wave_sum(cnt);
-        if (lane == 0) s_cnt[wv] = cnt;
-        __syncthreads();
-        cnt = (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+        cnt = block_count(cnt, s_cnt);
         if (fin && cnt >= win_cnt) {
             polish = lm_iters;
             win_cnt = cnt;
@@ -2397,21 +2396,16 @@ static size_t link_pose_lds(int mm, int kcap)
 bool rpe_link_poses_in_lds(const rpe_handle *h) { return h->cfg.max_matches <= LP_LDS_MATCHES; }
 
 // the links in d_links over the last run r (its d_status / d_m_n / d_R / d_t, match indices, d_n1 / d_n2 and the structure
-// buffers) -> d_lp_*.  Raises the kernel's dynamic-LDS limit on first use (never inside a graph capture: only
-// rpe_link_poses comes here); above LP_LDS_MATCHES the lists go to d_lp_corr, which the caller has allocated.
+// buffers) -> d_lp_*.  Above LP_LDS_MATCHES the lists go to d_lp_corr, which the caller has allocated.
 int rpe_launch_link_poses(rpe_handle *h, const RpeRun &r, int L, int iters, double threshold_px, int min_shared, int refine_iters)
 {
     const int mm = h->cfg.max_matches, kcap = h->lay.kcap;
     const size_t lds = link_pose_lds(mm, kcap);
-    // the limit belongs to the kernel, not to the handle: raise it to the most any handle asks for (the cut, or the largest
-    // max_matches; no table is larger than the candidates it shares region A with)
-    const int lds_max = (int)std::max(link_pose_lds(LP_LDS_MATCHES, 0), link_pose_lds(8064, 0));
-    if (lds > (size_t)lds_max) return RPE_ERR_HIP;
-    if (!h->lp_lds_set) {
-        if (hipFuncSetAttribute((const void *)link_pose_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max) != hipSuccess ||
-            hipFuncSetAttribute((const void *)link_pose_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_max) != hipSuccess) return RPE_ERR_HIP;
-        h->lp_lds_set = true;
-    }
+    // the most: the cut, or the largest max_matches; no table is larger than the candidates it shares region A with
+    const size_t lds_max = std::max(link_pose_lds(LP_LDS_MATCHES, 0), link_pose_lds(8064, 0));
+    if (lds > lds_max) return RPE_ERR_HIP;
+    if (lds > 65536 && raise_lds_limit(h, {(const void *)link_pose_kernel<true>, (const void *)link_pose_kernel<false>}, lds_max) != RPE_OK)
+        return RPE_ERR_HIP;
     launch_cam(r, link_pose_kernel<true>, link_pose_kernel<false>, dim3(L), dim3(256), lds, h->stream, (const RpeLink *)h->d_links,
                (const int *)h->d_m_q, (const int *)h->d_m_t, (const int *)h->d_m_n, (const int *)h->d_status,
                (const uint8_t *)h->d_mask, (const uint8_t *)h->d_pose_mask, (const double *)h->d_points,

@@ -217,6 +217,30 @@ __device__ __forceinline__ int block_excl_scan(int v, int *s_wave /*[4]*/, int &
     __syncthreads();
     return base + inc - v;
 }
+// Cross-wave election over a 256-thread workgroup (all of it takes part: one barrier inside).  Each wave brings its best
+// (count, key), key < 0 = none; every thread gets the winner: the largest count, the lowest key among equal counts, or
+// (-1, -1) when no wave has a candidate.  s_best: eight LDS words
+__device__ __forceinline__ void elect_best(int best_cnt, int best_key, int *s_best /*[8]*/, int &win_cnt, int &win_key)
+{
+    const int wv = threadIdx.x >> 6;
+    if ((threadIdx.x & 63) == 0) { s_best[wv * 2] = best_cnt; s_best[wv * 2 + 1] = best_key; }
+    __syncthreads();
+    win_cnt = -1; win_key = -1;
+#pragma unroll
+    for (int w = 0; w < 4; ++w) {
+        const int c = s_best[w * 2], key = s_best[w * 2 + 1];
+        if (key >= 0 && (c > win_cnt || (c == win_cnt && key < win_key))) { win_cnt = c; win_key = key; }
+    }
+}
+// the sum of cnt over a 256-thread workgroup, on every thread (all of it takes part: one barrier inside), the waves added
+// in wave order.  s_cnt: one LDS word per wave
+__device__ __forceinline__ int block_count(int cnt, int *s_cnt /*[4]*/)
+{
+    cnt = wave_sum(cnt);
+    if ((threadIdx.x & 63) == 0) s_cnt[threadIdx.x >> 6] = cnt;
+    __syncthreads();
+    return (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
+}
 
 struct RpeTile { short level, tx, ty, pad; };
 // destination tile of the resize kernel: its origin and the origin of its source window in the level below
@@ -343,7 +367,6 @@ struct rpe_handle {
     std::vector<RpeLink> link_tab;        // host side of d_links: the table of the last link call, source of its upload
     double *d_link_stats = nullptr;       // [link][3] lower quartile, median, upper quartile
     int *d_link_n = nullptr, *d_link_code = nullptr;
-    bool link_lds_set = false;            // the kernel's dynamic-LDS limit has been raised for this handle's layout
     // the guided matchers of either norm only (rpe_guided_matches[_l2], rpe_match_hamming_guided, rpe_match_l2_guided;
     // created on first use): match lists of their own, shaped like the run's d_m_* / d_pts* (d_gm_d: int32 Hamming
     // distances, or f32 L2 distances in the same four bytes); the poses gated with when the caller supplies them; per pair and image one 32-byte record per
@@ -357,14 +380,15 @@ struct rpe_handle {
     double *d_hg_H = nullptr, *d_hg_R = nullptr;
     int *d_hg_counts = nullptr, *d_hg_info = nullptr;
     uint8_t *d_hg_mask = nullptr;
-    bool hg_lds_set = false;              // the kernel's dynamic-LDS limit has been raised for this handle's layout
     // rpe_link_poses only (created on first use): per link the pose, {n, inliers}, info[4], rms[2] and the inlier mask
     // [link][max_matches], 4*max_batch links (the link table is rpe_scale_links' d_links); d_lp_corr [link][5 * max_matches]
     // holds the correspondence lists of handles above the kernel's LDS cut only
     double *d_lp_R = nullptr, *d_lp_t = nullptr, *d_lp_rms = nullptr, *d_lp_corr = nullptr;
     int *d_lp_counts = nullptr, *d_lp_info = nullptr;
     uint8_t *d_lp_mask = nullptr;
-    bool lp_lds_set = false;              // the kernel's dynamic-LDS limit has been raised
+    // the kernels of geom_kernels.hip whose dynamic-LDS limit a launch of this handle has raised (raise_lds_limit): the
+    // attribute is per device, so the record is per handle
+    std::vector<const void *> lds_raised;
     // results
     double *d_R = nullptr, *d_t = nullptr, *d_E = nullptr;
     int *d_inliers = nullptr, *d_status = nullptr;

@@ -87,25 +87,41 @@ static inline unsigned xcd_image_grid(int nb, int n_img) { return (unsigned)(8 *
 
 // ---------------------------------------------------------------- pyramid
 // Workgroup = one wave = 256 x 16 destination tile of level l (PYR_TW x PYR_TH).  The source footprint in level l-1
-// (PYR_ROWS = 23 rows x PYR_DW = 84 dwords, bounds derived arithmetically so the loads do not depend on the coefficient
-// tables; checked on the host at create time) is staged in LDS with aligned 16-byte loads, all of them in flight before
-// the first LDS store -- 7744 B per workgroup, so the LDS of a CU (160 KB) holds 21 windows.
-// One lane = 4 destination columns x the tile's 16 rows, as two groups of 8.  The bilinear chain is separable in exact
-// integer arithmetic: h(src row, dst col) = a0 p[o] + a1 p[o+1] (16 bits), out = (b0 h(top) + b1 h(bottom) + 2^15) >> 16.
+// (at most PYR_ROWS = 23 rows x PYR_DW = 84 dwords; origin and row count come from the host's tile record, which
+// build_tables checks against the window at create time) is staged in LDS with aligned 16-byte loads, all of them in
+// flight before the first LDS store -- 7744 B per workgroup, so the LDS of a CU (160 KB) holds 21 windows.
+// One lane = 4 destination columns x the tile's 16 rows, one run.  The bilinear chain is separable in exact integer
+// arithmetic: h(src row, dst col) = a0 p[o] + a1 p[o+1] (16 bits), out = (b0 h(top) + b1 h(bottom) + 2^15) >> 16.
 // Reading p[o+1] and the row below unclamped is exact: the coefficient tables give weight 0 wherever OpenCV clamps
-// (last source column / row).  The row loop is described where it stands.
+// (last source column / row).  A source row passes the horizontal filter once: the h of a row's bottom source row stay
+// in registers and are the next row's top h wherever the source row advances by one (15 rows of 16 at scale 1.1).
+// Everything that is the same in all 64 lanes -- the tile record, the 16 row-table entries, weights, row offsets, the
+// re-use mask, the destination row pointer -- lives in scalar registers.  The row loop is described where it stands.
+// Cost per tile (static count of the gfx950 code, path of a full tile whose 15 later rows re-use): about 435 vector
+// instructions and 34 LDS read instructions; the form before (both source rows filtered per output row, row constants
+// built per lane, a division per window load) took 866 and 48.  Measured: 841 -> 444 vector instructions per tile, 1.63 ->
+// 1.41 ms per step of 1024 VGA pairs.
 // Why this tile.  The kernel lives on how many tile windows a CU keeps in flight (r02 diagnostic builds: loads + LDS alone
 // 1.12 ms, rows + stores alone 1.26 ms, together 1.92 ms -- the phases of a workgroup overlap only through OTHER
-// workgroups, and FAST run beside it on a second stream gained nothing: wave slots are the contended resource).  So a lane
-// takes two row groups (half the waves per window, the column constants serve 16 rows) and a tile is one wave: 64-row
-// tiles of two waves measured 1.89 ms, 128 x 32 of one wave 1.68.  And the longer the contiguous rows the better the
-// mixed read / write stream runs: 64-wide 1.82, 128-wide 1.67, 256 x 16 1.64 ms (partial tiles at the right edge idle
-// lanes, which a memory-bound kernel does not feel).
+// workgroups, and FAST run beside it on a second stream gained nothing: wave slots are the contended resource), so
+// every instruction taken out of a tile's life shortens its stay in a wave slot.  A lane takes all 16 rows (half the
+// waves per window of an 8-row split, the column constants serve 16 rows) and a tile is one wave: 64-row tiles of two
+// waves measured 1.89 ms, 128 x 32 of one wave 1.68.  And the longer the contiguous rows the better the mixed read /
+// write stream runs: 64-wide 1.82, 128-wide 1.67, 256 x 16 1.64 ms (all three with the row body of that time; partial
+// tiles at the right edge idle lanes: 73 % of the lane-pixels of a VGA pyramid are pixels).
 constexpr int PYR_THREADS = 64;
 constexpr int PYR_LDS_DW = PYR_ROWS * PYR_DW + 4;          // +4: the unclamped p[o+1] of the last row's last column
-static_assert(PYR_THREADS == PYR_TW / 4 * PYR_TH / 16, "a lane takes 4 columns x 16 rows of the tile");
-static_assert(PYR_THREADS == 64 && PYR_TH == 16, "one wave per tile, whose lanes each take the tile's two groups of 8 rows");
+constexpr int PYR_NQ = PYR_DW / 4;                                 // 16-byte chunks of a window row
+constexpr int PYR_LROWS = PYR_THREADS / PYR_NQ;                    // window rows a round of loads covers: lane = (row tid / 21, chunk tid % 21)
+constexpr int PYR_LLANES = PYR_LROWS * PYR_NQ;                     // lanes that stage a chunk per round (63)
+constexpr int PYR_NLD = (PYR_ROWS + PYR_LROWS - 1) / PYR_LROWS;    // rounds
+constexpr int PYR_NLD_FULL = (PYR_TH + 1 + PYR_LROWS - 1) / PYR_LROWS;  // rounds every tile runs: a full tile reads PYR_TH + 1 rows or more
+constexpr int PYR_NCHUNK = PYR_ROWS * PYR_NQ;
+static_assert(PYR_THREADS == PYR_TW / 4 && PYR_THREADS == 64 && PYR_TH == 16, "one wave per tile; a lane takes 4 columns x the tile's 16 rows");
 static_assert(PYR_DW % 4 == 0, "window rows are whole 16-byte chunks");
+static_assert(PYR_LROWS == 3 && PYR_LLANES == 63 && PYR_NLD == 8, "63 lanes x 8 rounds of 3 rows cover the 23 x 21 chunks");
+static_assert(PYR_NCHUNK * 4 <= PYR_LDS_DW && (PYR_NLD - 1) * PYR_LLANES < PYR_NCHUNK, "only the last round is cut short by the window's end");
+static_assert((PYR_ROWS + 1) * PYR_DW * 4 < (1 << PYR_YW_SHIFT), "a window byte offset fits the row field of the y table");
 static_assert(PYR_LDS_DW * 4 == 7744, "LDS per tile window");
 __global__ __launch_bounds__(PYR_THREADS) void pyr_resize_kernel(uint8_t *pyr, RpeDeviceLayout lay, const int *__restrict__ coef,
                                                                   const RpePyrTile *__restrict__ ptiles, int ntiles, int l)
@@ -119,38 +135,48 @@ __global__ __launch_bounds__(PYR_THREADS) void pyr_resize_kernel(uint8_t *pyr, R
     // tile origin and source-window origin come from a host table: the two 64-bit divisions that derive the window from
     // the tile (floor(x0 * S.w / D.w), floor(y0 * S.h / D.h)) cost ~250 scalar instructions per wave when done here, and
     // the scalar unit issues at the same 1-per-4-cycles cadence per SIMD as the vector ALU
+    // (one 16-byte scalar load: everything in the record is the same in all 64 lanes)
     const RpePyrTile pt = ptiles[ti];
-    const int x0 = pt.x0, y0 = pt.y0, a0 = pt.a0, sy0 = pt.sy0;
-    uint8_t *base = pyr + (long long)blockIdx.y * lay.stride;
+    const int x0 = pt.x0, y0 = pt.y0, a0 = pt.a0, sy0 = pt.sy0, nsrc = pt.nsrc;
+    const unsigned reuse = pt.reuse;
     const uint8_t *src = rpe_level_base(pyr, lay, blockIdx.y, l - 1);
-    // packed (offset | weight << 16) per destination column / row; the device table pads the x run to a multiple of 128
-    // and the y run to a multiple of 64 entries (last entry replicated) and aligns both to 16 B, so a lane fetches its
-    // 4 columns with one 16-B load and its 16 rows with four, without clamps
-    const int *cxp = coef + D.dcoef_off, *cyp = cxp + ((D.w + 127) & ~127);
-    // lane = column group of 4 pixels x row-group pair (the tile has one pair: yl == y0)
-    const int tx = tid % (PYR_TW / 4), yl = y0 + 16 * (tid / (PYR_TW / 4));
-    const int x4 = x0 + 4 * tx;
+    // per destination column: offset | weight << 16; per destination row: window byte offset of the source row (row x 4
+    // PYR_DW) | weight << PYR_YW_SHIFT.  The device table pads the x run to a multiple of 128 and the y run to a multiple
+    // of 64 entries (last entry replicated) and aligns both to 16 B, so a lane fetches its 4 columns with one 16-B load
+    // and the wave its 16 rows with scalar loads (the address is uniform), without clamps
+    const int *cxp = coef + D.dcoef_off, *cyp = cxp + ((D.w + 127) & ~127) + y0;
+    // lane = column group of 4 pixels
+    const int x4 = x0 + 4 * tid;
     // coefficient loads go out first, in the shadow of the window loads
     const int4 cv = *(const int4 *)(cxp + x4);
-    int4 rq[PYR_TH / 4];
+    unsigned ys[PYR_TH];
 #pragma unroll
-    for (int k = 0; k < PYR_TH / 4; ++k) rq[k] = *(const int4 *)(cyp + yl + 4 * k);
-    {   // all window loads (16 B per lane) in flight before the first LDS store (one HBM round trip per tile):
-        // chunk i = tid + 64 q of the 23 x 21 chunks of the window (q < 8), row i / 21, 16-B column i % 21
-        constexpr int NQ = PYR_DW / 4, NCHUNK = PYR_ROWS * NQ, NLD = (NCHUNK + PYR_THREADS - 1) / PYR_THREADS;
-        uint4 stage[NLD];
+    for (int r = 0; r < PYR_TH; ++r) ys[r] = (unsigned)cyp[r];
+    {   // all window loads (16 B per lane) in flight before the first LDS store (one HBM round trip per tile).  Lane =
+        // (window row tid / 21, 16-B column tid % 21) + 3 rows per round q: one division per tile, and the LDS chunk of
+        // round q is tid + 63 q.  Only rows 0 .. nsrc - 1 of the window are read by the tile: rows past them load row
+        // nsrc - 1 again, and the rounds that lie past the rows every full tile needs (PYR_TH + 1 at any scale >= 1) are
+        // skipped when they lie past nsrc (a uniform branch; 21 rows and up: never at scale 1.1).  Lane 63 loads a valid
+        // chunk and stores nothing.
+        const int lr = tid / PYR_NQ, lc = tid - lr * PYR_NQ;
+        const unsigned colb = (unsigned)min(a0 + 16 * lc, S.pitch - 16) + __umul24((unsigned)sy0, (unsigned)S.pitch);   // pitch is a multiple of 16; clamped columns are never read
+        const unsigned off0 = colb + __umul24((unsigned)lr, (unsigned)S.pitch), offmax = colb + __umul24((unsigned)(nsrc - 1), (unsigned)S.pitch);
+        const unsigned pitch3 = PYR_LROWS * S.pitch;
+        uint4 stage[PYR_NLD];
 #pragma unroll
-        for (int q = 0; q < NLD; ++q) {
-            const int i = min(tid + PYR_THREADS * q, NCHUNK - 1);
-            const int r = i / NQ, c = i - r * NQ;
-            stage[q] = *(const uint4 *)(src + min(a0 + 16 * c, S.pitch - 16) + __umul24((unsigned)min(sy0 + r, S.h - 1), (unsigned)S.pitch));   // pitch is a multiple of 16; clamped columns are never read
-        }
+        for (int q = 0; q < PYR_NLD; ++q)
+            if (q < PYR_NLD_FULL || PYR_LROWS * q < nsrc) stage[q] = *(const uint4 *)(src + min(off0 + q * pitch3, offmax));
         // pin the loads above the guarded stores: left alone the compiler sinks every load into the block of its store
         // (load, s_waitcnt vmcnt(0), ds_write, next load ...: dependent HBM round trips instead of one)
 #pragma unroll
-        for (int q = 0; q < NLD; ++q) asm volatile("" : "+v"(stage[q].x), "+v"(stage[q].y), "+v"(stage[q].z), "+v"(stage[q].w));
+        for (int q = 0; q < PYR_NLD; ++q)
+            if (q < PYR_NLD_FULL || PYR_LROWS * q < nsrc) asm volatile("" : "+v"(stage[q].x), "+v"(stage[q].y), "+v"(stage[q].z), "+v"(stage[q].w));
+        if (tid < PYR_LLANES) {
 #pragma unroll
-        for (int q = 0; q < NLD; ++q) { const int i = tid + PYR_THREADS * q; if (i < NCHUNK) ((uint4 *)s_src)[i] = stage[q]; }
+            for (int q = 0; q < PYR_NLD; ++q)
+                if ((q < PYR_NLD_FULL || PYR_LROWS * q < nsrc) && (PYR_LLANES * (q + 1) <= PYR_NCHUNK || tid < PYR_NCHUNK - PYR_LLANES * q))
+                    ((uint4 *)s_src)[tid + PYR_LLANES * q] = stage[q];
+        }
     }
     // per-lane column constants: source offsets o_j (non-decreasing, o_3 - o_0 <= 4) -> byte selectors, packed weights
     typedef unsigned short v2u16_t __attribute__((ext_vector_type(2)));
@@ -169,63 +195,67 @@ __global__ __launch_bounds__(PYR_THREADS) void pyr_resize_kernel(uint8_t *pyr, R
             apk[j] = __builtin_bit_cast(v2u16_t, (256u - a1) | (a1 << 16));
         }
     }
-    // per-lane row constants, packed (LDS dword index of the top source row at the dword holding p[o_0]) | (bottom-row
-    // weight << 16).  Materialised here: rematerialised inside the row loop, every row's first use of a table register sits
-    // behind an s_waitcnt vmcnt(0) -- which on gfx9 also waits for the previous row's global STORE (rows serialised on HBM
-    // write latency)
-    unsigned rc[PYR_TH];
-    {
-#pragma unroll
-        for (int k = 0; k < PYR_TH / 4; ++k) {
-            const int rv4[4] = {rq[k].x, rq[k].y, rq[k].z, rq[k].w};
-#pragma unroll
-            for (int e = 0; e < 4; ++e) {
-                const int rr = 4 * k + e;
-                rc[rr] = (__umul24((unsigned)((rv4[e] & 0xFFFF) - sy0), PYR_DW) + (unsigned)(bcol >> 2)) | ((unsigned)rv4[e] & 0xFFFF0000u);
-                asm volatile("" : "+v"(rc[rr]));
-            }
-        }
-    }
+    // row constants: the table entries are scalars (waited for once, before the row loop, and never behind a vmcnt that
+    // would also wait for the previous row's global STORE), so a row's weights and the window offset of its source row
+    // come from scalar code; the lane's own term is one register: the LDS byte offset of the dword holding p[o_0] in
+    // window row 0, less the window's first row
+    const unsigned vbase = ((unsigned)bcol & ~3u) - (unsigned)sy0 * (PYR_DW * 4);
     __syncthreads();
     if (x4 >= D.pitch) return;
-    // One output row = the horizontal pass of its two source rows + the vertical blend, no branches:
-    //   source row: three aligned LDS dwords from the one holding p[o_0] (the 4 columns span <= 6 bytes), two v_alignbyte to
-    //   the lane's byte phase; the bottom row is the top row + one window row -- where OpenCV clamps it (last source row)
-    //   its weight is 0 and the window holds finite bytes, so the unclamped read is exact;
-    //   column j: v_perm_b32 -> (p[o_j], p[o_j + 1]) as two u16, v_dot2_u32_u16 with (256 - a1_j, a1_j) -> h (16 bits);
-    //   out_j = (b0 h_top + b1 h_bot + 2^15) >> 16 by two 24-bit mads; the four results are byte 2 of four 24-bit sums.
-    // ~38 vector instructions per row of 4 pixels, and no divergent control flow; the version with a cached bottom row and
-    // separate byte extraction / multiplies took 62.  (Byte-unaligned ds_read_b64 straight at p[o_0] saves the two
-    // v_alignbyte and was measured 70 % SLOWER: the LDS serialises misaligned 8-byte lanes.)
+    // One source row = three aligned LDS dwords from the one holding p[o_0] (the 4 columns span <= 6 bytes), two v_alignbyte
+    // to the lane's byte phase, then per column j a v_perm_b32 -> (p[o_j], p[o_j + 1]) as two u16 and a v_dot2_u32_u16 with
+    // (256 - a1_j, a1_j) -> h_j (16 bits): 10 vector instructions and 3 LDS reads.  (Byte-unaligned ds_read_b64 straight at
+    // p[o_0] saves the two v_alignbyte and was measured 70 % SLOWER: the LDS serialises misaligned 8-byte lanes.)
     const unsigned sh = (unsigned)bcol & 3u;
-    const unsigned colmask = x4 + 3 < D.w ? 0xFFFFFFFFu : (x4 >= D.w ? 0u : (0xFFFFFFFFu >> (8 * (x4 + 4 - D.w))));   // bytes past D.w stay 0
+    auto fetch = [&](unsigned lds_byte, unsigned (&t)[3]) {
+        const unsigned *p = (const unsigned *)((const uint8_t *)s_src + lds_byte);
+        t[0] = p[0]; t[1] = p[1]; t[2] = p[2];
+    };
+    auto hpass = [&](const unsigned (&t)[3], unsigned (&hh)[4]) {
+        const unsigned lo = __builtin_amdgcn_alignbyte(t[1], t[0], sh), hi = __builtin_amdgcn_alignbyte(t[2], t[1], sh);
 #pragma unroll
-    for (int half = 0; half < 2; ++half) {
-        const int yb = yl + 8 * half;
-        uint8_t *dstp = base + D.off + __umul24((unsigned)yb, (unsigned)D.pitch) + x4;
-        const int nrows = min(8, D.h - yb);
+        for (int j = 0; j < 4; ++j) hh[j] = __builtin_amdgcn_udot2(__builtin_bit_cast(v2u16_t, __builtin_amdgcn_perm(hi, lo, selp[j])), apk[j], 0u, false);
+    };
+    // the four results of a row are byte 2 of four 24-bit sums; bytes past D.w stay 0: their selector byte picks the constant 0
+    const unsigned colmask = x4 + 3 < D.w ? 0xFFFFFFFFu : (x4 >= D.w ? 0u : (0xFFFFFFFFu >> (8 * (x4 + 4 - D.w))));
+    const unsigned sel01 = (0x0c0c0602u & colmask) | (0x0c0c0c0cu & ~colmask), sel23 = (0x06020c0cu & colmask) | (0x0c0c0c0cu & ~colmask);
+    // One output row = the horizontal pass of its bottom source row + the vertical blend
+    //   out_j = (b0 h_top + b1 h_bot + 2^15) >> 16 by two 24-bit mads.
+    // The bottom row is the top row + one window row -- where OpenCV clamps it (last source row) its weight is 0 and whatever
+    // the window holds there is finite, so the unclamped read is exact.  The top row's h is the previous output row's bottom h
+    // wherever the source row advances by exactly one (bit r of the tile's reuse mask, a scalar: 15 rows of 16 at scale 1.1);
+    // the first row of a tile and rows after a step of 0 or 2 pass their top row too.  The 16 rows are one unrolled run and
+    // the two sets of four h alternate between top and bottom from row to row, so the two paths join without a copy.  Both
+    // branches of a row (reuse, rows past D.h in the last tile row) are scalar.
+    uint8_t *drow = pyr + (long long)blockIdx.y * lay.stride + D.off + __umul24((unsigned)y0, (unsigned)D.pitch) + x0;
+    const int nrows = min(PYR_TH, D.h - y0);
+    unsigned vo = 4u * (unsigned)tid, half = 32768u;
+    asm("" : "+v"(half));                    // the rounding term stays in one register (it is an operand of a three-operand mad)
+    auto rowtop = [&](int r) { return (ys[r] & ((1u << PYR_YW_SHIFT) - 1u)) + vbase; };
+    unsigned hs[2][4], nb[3];
+    fetch(rowtop(0) + PYR_DW * 4, nb);
 #pragma unroll
-        for (int r8 = 0; r8 < 8; ++r8) {
-            if (r8 < nrows) {
-                const unsigned rcv = rc[8 * half + r8];
-                const unsigned *rt = s_src + (rcv & 0xFFFFu), *rb = rt + PYR_DW;
-                const unsigned t0 = rt[0], t1 = rt[1], t2 = rt[2], u0 = rb[0], u1 = rb[1], u2 = rb[2];
-                uint2 vt, vb;
-                vt.x = __builtin_amdgcn_alignbyte(t1, t0, sh); vt.y = __builtin_amdgcn_alignbyte(t2, t1, sh);
-                vb.x = __builtin_amdgcn_alignbyte(u1, u0, sh); vb.y = __builtin_amdgcn_alignbyte(u2, u1, sh);
-                const unsigned b1u = rcv >> 16, b0u = 256u - b1u;
-                unsigned sm[4];
+    for (int r = 0; r < PYR_TH; ++r) {
+        if (r == 0 || !((reuse >> r) & 1u)) { unsigned tt[3]; fetch(rowtop(r), tt); hpass(tt, hs[r & 1]); }
+        // the next row's bottom source row is on its way from LDS while this row is computed
+        const unsigned cb[3] = {nb[0], nb[1], nb[2]};
+        if (r + 1 < PYR_TH) fetch(rowtop(r + 1) + PYR_DW * 4, nb);
+        hpass(cb, hs[(r + 1) & 1]);
+        const unsigned (&ht)[4] = hs[r & 1], (&hb)[4] = hs[(r + 1) & 1];
+        const unsigned b1u = ys[r] >> PYR_YW_SHIFT, b0u = 256u - b1u;
+        unsigned sm[4];
 #pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    const unsigned ht = __builtin_amdgcn_udot2(__builtin_bit_cast(v2u16_t, __builtin_amdgcn_perm(vt.y, vt.x, selp[j])), apk[j], 0u, false);
-                    const unsigned hb = __builtin_amdgcn_udot2(__builtin_bit_cast(v2u16_t, __builtin_amdgcn_perm(vb.y, vb.x, selp[j])), apk[j], 0u, false);
-                    sm[j] = __umul24(b1u, hb) + (__umul24(b0u, ht) + 32768u);
-                }
-                const unsigned out = __builtin_amdgcn_perm(sm[1], sm[0], 0x0c0c0602u) | __builtin_amdgcn_perm(sm[3], sm[2], 0x06020c0cu);
-                *(unsigned *)dstp = out & colmask;
-                dstp += D.pitch;
-            }
+        for (int j = 0; j < 4; ++j) {
+            unsigned t = __umul24(b0u, ht[j]) + half;
+            asm("" : "+v"(t));               // two v_mad_u32_u24 per column; left alone the sums are re-associated into mul, mul, add3
+            sm[j] = __umul24(b1u, hb[j]) + t;
         }
+        asm("" : "+v"(vo));                  // keeps the zero-extension in the row's block: the store takes (scalar row pointer, lane offset)
+        // rows past D.h (last tile row of a level) are computed like any other -- the y table repeats its last entry, so they
+        // read inside the window -- and only their store is skipped: a branch around the whole row would make every value
+        // carried from row to row a merge of two paths, paid for in copies by all rows
+        if (r < nrows) *(unsigned *)(drow + vo) = __builtin_amdgcn_perm(sm[1], sm[0], sel01) | __builtin_amdgcn_perm(sm[3], sm[2], sel23);
+        drow += D.pitch;
     }
 }
 

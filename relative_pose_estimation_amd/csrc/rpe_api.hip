@@ -200,39 +200,45 @@ static int build_tables(rpe_handle *h)
         lin_coeffs(S.w, D.w, xo, xa);
         lin_coeffs(S.h, D.h, yo, ya);
     }
-    // resize tiles (PYR_TW x PYR_TH destination pixels) with the origin of their source window, levels 1..11
+    // resize tiles (PYR_TW x PYR_TH destination pixels), levels 1..11: the origin of the source window (anchored at
+    // floor(scale * tile origin), x aligned down to 16 B), the source rows the tile reads and its row-reuse mask.  The
+    // kernel stages at most PYR_ROWS rows x (4 PYR_DW) bytes per tile and packs a source row's window byte offset into
+    // PYR_YW_SHIFT bits: verify the tables fit both for every tile.
     {
         std::vector<RpePyrTile> pt;
         for (int l = 1; l < RPE_NLEVELS; ++l) {
             const RpeLevel &S = L.lv[l - 1], &D = L.lv[l];
+            const int *xo = coef.data() + D.coef_off, *yo = xo + 2 * D.w;
+            if ((long long)S.h * PYR_DW * 4 >= (1ll << PYR_YW_SHIFT)) { h->err = "pyramid level too tall for the packed row table"; return RPE_ERR_INVALID; }
+            for (int x0 = 0; x0 < D.w; x0 += PYR_TW) {
+                int a0 = ((int)(((long long)x0 * S.w) / D.w)) & ~15, xl = x0 + PYR_TW - 1 < D.w ? x0 + PYR_TW - 1 : D.w - 1;
+                int hi = xo[xl] + 1 < S.w ? xo[xl] + 1 : S.w - 1;
+                if (xo[x0] < a0 || hi - a0 >= PYR_DW * 4) { h->err = "pyramid footprint bound violated (x)"; return RPE_ERR_INVALID; }
+            }
             h->pyr_tile_off[l] = (int)pt.size();
-            for (int y0 = 0; y0 < D.h; y0 += PYR_TH)
+            for (int y0 = 0; y0 < D.h; y0 += PYR_TH) {
+                const int s0 = (int)(((long long)y0 * S.h) / D.h), yl = y0 + PYR_TH - 1 < D.h ? y0 + PYR_TH - 1 : D.h - 1;
+                // the last source row a destination row reads with a non-zero weight: rows 0 .. hi - s0 of the window are
+                // loaded (all inside the level); the bottom row of a clamped top row (weight 0) is window row hi - s0 + 1,
+                // which is read but need not hold anything, so it too has to lie inside the window
+                const int hi = yo[yl] + 1 < S.h ? yo[yl] + 1 : S.h - 1;
+                if (yo[y0] < s0 || hi - s0 >= PYR_ROWS || yo[yl] + 1 - s0 >= PYR_ROWS) { h->err = "pyramid footprint bound violated (y)"; return RPE_ERR_INVALID; }
+                unsigned reuse = 0;
+                for (int r = 1; y0 + r <= yl; ++r) reuse |= (unsigned)(yo[y0 + r] == yo[y0 + r - 1] + 1) << r;
                 for (int x0 = 0; x0 < D.pitch; x0 += PYR_TW)
-                    pt.push_back({(short)x0, (short)y0, (short)(((int)(((long long)x0 * S.w) / D.w)) & ~15), (short)(((long long)y0 * S.h) / D.h)});
+                    pt.push_back({(short)x0, (short)y0, (short)(((int)(((long long)x0 * S.w) / D.w)) & ~15), (short)s0,
+                                  (unsigned short)(hi - s0 + 1), (unsigned short)reuse, 0});
+            }
             h->pyr_tile_cnt[l] = (int)pt.size() - h->pyr_tile_off[l];
         }
         DM(h, h->d_pyr_tiles, pt.size() ? pt.size() : 1);
         if (!pt.empty()) HIPCHK(h, hipMemcpy(h->d_pyr_tiles, pt.data(), pt.size() * sizeof(RpePyrTile), hipMemcpyHostToDevice));
     }
-    // the resize kernel stages a fixed PYR_ROWS-row x (4 PYR_DW)-byte source footprint per PYR_TW x PYR_TH tile (origin 16-B aligned),
-    // anchored at floor(scale * tile origin); verify the tables fit it for every tile
-    for (int l = 1; l < RPE_NLEVELS; ++l) {
-        const RpeLevel &S = L.lv[l - 1], &D = L.lv[l];
-        const int *xo = coef.data() + D.coef_off, *yo = xo + 2 * D.w;
-        for (int x0 = 0; x0 < D.w; x0 += PYR_TW) {
-            int a0 = ((int)(((long long)x0 * S.w) / D.w)) & ~15, xl = x0 + PYR_TW - 1 < D.w ? x0 + PYR_TW - 1 : D.w - 1;
-            int hi = xo[xl] + 1 < S.w ? xo[xl] + 1 : S.w - 1;
-            if (xo[x0] < a0 || hi - a0 >= PYR_DW * 4) { h->err = "pyramid footprint bound violated (x)"; return RPE_ERR_INVALID; }
-        }
-        for (int y0 = 0; y0 < D.h; y0 += PYR_TH) {
-            int s0 = (int)(((long long)y0 * S.h) / D.h), yl = y0 + PYR_TH - 1 < D.h ? y0 + PYR_TH - 1 : D.h - 1;
-            int hi = yo[yl] + 1 < S.h ? yo[yl] + 1 : S.h - 1;
-            if (yo[y0] < s0 || hi - s0 >= PYR_ROWS) { h->err = "pyramid footprint bound violated (y)"; return RPE_ERR_INVALID; }
-        }
-    }
-    // device form: (offset, weight) packed into one dword per destination column / row (offset < 65536, weight <= 256).
+    // device form: one dword per destination column / row.  x: offset | weight << 16 (offset < 65536, weight <= 256).
+    // y: source row x window row pitch in bytes | weight << PYR_YW_SHIFT -- the row part is the same in every lane of a
+    // tile, so the kernel reads its 16 entries with scalar loads and a lane adds one term to each (bound checked above).
     // Per level: [align128(w) packed x][align64(h) packed y], padded with the last entry, every run 16-B aligned: a lane
-    // of the resize kernel fetches its 4 columns with one 16-B load and its 8 rows with two, without clamps.
+    // of the resize kernel fetches its 4 columns with one 16-B load, a wave its 16 rows with one scalar load, without clamps.
     {
         int dtotal = 0;
         for (int l = 1; l < RPE_NLEVELS; ++l) {
@@ -247,7 +253,7 @@ static int build_tables(rpe_handle *h)
             const int xw = (D.w + 127) & ~127, yh = (D.h + 63) & ~63;
             int *px = packed.data() + D.dcoef_off, *py = px + xw;
             for (int x = 0; x < xw; ++x) { const int k = x < D.w ? x : D.w - 1; px[x] = xo[k] | (xa[k] << 16); }
-            for (int y = 0; y < yh; ++y) { const int k = y < D.h ? y : D.h - 1; py[y] = yo[k] | (ya[k] << 16); }
+            for (int y = 0; y < yh; ++y) { const int k = y < D.h ? y : D.h - 1; py[y] = (int)((unsigned)(yo[k] * (PYR_DW * 4)) | ((unsigned)ya[k] << PYR_YW_SHIFT)); }
         }
         DM(h, h->d_coef, packed.size());
         HIPCHK(h, hipMemcpy(h->d_coef, packed.data(), sizeof(int) * packed.size(), hipMemcpyHostToDevice));

@@ -49,7 +49,7 @@ struct RpeLevel {
     float inv_scale;  // 1.f / scale (orb.cpp's inv_scale: the level size and the keypoint's level coordinates come from it)
     long long off;    // byte offset inside the per-image pyramid buffer
     int coef_off;     // offset of xo/xa (w entries) then yo/ya (h entries) in the HOST coefficient table
-    int dcoef_off;    // device table: [align128(w) packed x][align64(h) packed y], 16-B aligned, last entry replicated
+    int dcoef_off;    // device table: [align128(w) packed x][align64(h) packed y], 16-B aligned, last entry replicated (build_tables)
     int tile0, ntile; // this level's run inside the FAST tile table (raster order inside the level)
 };
 
@@ -243,8 +243,14 @@ __device__ __forceinline__ int block_count(int cnt, int *s_cnt /*[4]*/)
 }
 
 struct RpeTile { short level, tx, ty, pad; };
-// destination tile of the resize kernel: its origin and the origin of its source window in the level below
-struct RpePyrTile { short x0, y0, a0, sy0; };
+// destination tile of the resize kernel: its origin, the origin of its source window in the level below, the number of
+// source rows its destination rows read (nsrc <= PYR_ROWS; window rows past it are neither loaded nor stored) and the rows
+// whose top source row is the row below the previous row's (bit r of reuse, 0 < r < PYR_TH: yo[y0 + r] == yo[y0 + r - 1] + 1).
+// One 16-byte scalar load per wave.
+struct alignas(16) RpePyrTile { short x0, y0, a0, sy0; unsigned short nsrc, reuse; int pad; };
+static_assert(sizeof(RpePyrTile) == 16 && PYR_TH <= 16, "one reuse bit per tile row");
+// device y table of the resize kernel: (byte offset of the source row in a window-pitch array) | (bottom-row weight << PYR_YW_SHIFT)
+constexpr int PYR_YW_SHIFT = 23;
 
 // per-pair RANSAC state in HBM
 struct RpeRansacState {

@@ -591,6 +591,82 @@ int rpe_link_poses(rpe_handle *h, int L, const int32_t *pair_a, const int32_t *p
                    int iters, double threshold_px, int min_shared, int refine_iters,
                    double *R, double *t, uint8_t *mask, int32_t *counts, int32_t *info, double *rms);
 
+/* ---------------------------------------------------------- link bundles */
+/* Bundle adjustment of the three views of a link (NOT in the reference): for a link (pair a, pair b, shared frame S) with
+ * A = pair a's other frame and C = pair b's other frame, the poses S -> A and S -> C and the points both pairs see are
+ * refined together on one reprojection cost.  S is the gauge (identity, never moved) and |t_A| = 1 the unit of scale.
+ * Links: exactly those of rpe_scale_links / rpe_link_poses (one argument head serves the three calls).
+ * The rule, for one link.  All arithmetic f64, + - * / sqrt only (sin for a rotation increment, as rpe_refine_poses), no
+ * contraction; a comparison with a NaN is false; finite(v) = fabs(v) <= DBL_MAX.
+ *  Codes, tested in this order: pair a not RPE_PAIR_OK: RPE_BUNDLE_PAIR_FAILED, counts {0, 0}.  All nine entries of the
+ *   link's R0 zero (what rpe_link_poses returns for every code but OK): RPE_BUNDLE_SKIPPED, counts {n2, 0}.
+ *   n3 < max(min_shared, 6): RPE_BUNDLE_TOO_FEW, counts {n2, n3}.  For these three everything else is zero.
+ *  Points: the usable matches of pair a as in rpe_scale_links (i < n_matches, ransac_mask and pose_mask set; key = keypoint
+ *   index on S; the lowest match index wins a duplicate key), numbered j = 0 .. n2-1 in ascending order of pair a's match
+ *   index.  Point j starts at pair a's triangulated point taken into S's frame by the link_point expression of "link
+ *   poses".  Its observations on S and on A are pair a's matched points in the normalised coordinates of the geometry
+ *   stages (camera path included).  It has an observation on C when its key has a match in pair b (every match
+ *   i < n_matches of b takes part whatever b's masks or status say, the lowest index wins) and that correspondence passes
+ *   the Score test of "link poses" (y2 > 0, dx*dx + dy*dy <= thr2 * (y2*y2), thr = threshold_px / f_c) under the INPUT
+ *   pose of C; n3 counts these points.  The sets are fixed for the whole optimisation.
+ *  Start: A from pair a's own (R, t), C from the caller's R0[L*9], t0[L*3] in pair b's own convention on pair a's scale
+ *   (what rpe_link_poses returns); each is taken to the solved form (S -> other frame) by the inverse expression of "link
+ *   poses" when S is that pair's image 2.
+ *  Parameters: 11 for the cameras, d = (wA[3], bA[2], wC[3], dC[3]), and 3 per point.  R_A <- exp([wA]x) R_A,
+ *   t_A <- normalise(t_A + bA0*b1 + bA1*b2) with (b1, b2) the tangent basis of rpe_refine_poses at t_A;
+ *   R_C <- exp([wC]x) R_C, t_C <- t_C + dC;  X_j <- X_j + dp_j.
+ *  Residuals, in pixels, rows in the order S x, S y, A x, A y, C x, C y: f*(y0/y2 - qx), f*(y1/y2 - qy) with y = X on S,
+ *   y = R_V X + t_V (each row ((r0*X + r1*Y) + r2*Z) + t) on A and C; f = f_a (pair a's RANSAC focal scale, as
+ *   rpe_pair_homographies takes it) on S and A, f_c (pair b's) on C.  A point without the C observation has zero C rows.
+ *   cost = sum over the points of ((e0*e0 + e1*e1) + (e2*e2 + e3*e3)) + (e4*e4 + e5*e5).
+ *  Derivatives of a row with y = R X + t, a = R X, u = y0/y2 (or y1/y2), s = f/y2: by w as in "link poses" polish, by t:
+ *   (s, 0, -s*ux) / (0, s, -s*uy) = Jt; by the tangent step: (Jt . b1, Jt . b2); by X: Jt R (column k:
+ *   (Jt0*R[0][k] + Jt1*R[1][k]) + Jt2*R[2][k]); on S, Jt itself.
+ *  LM: the conventions of rpe_refine_poses: lambda0 = 1e-3; a step that does not strictly lower the cost (or that cannot
+ *   be solved) multiplies lambda by 10, an accepted one divides it by 10; the same two stop tolerances (cost decrease
+ *   <= 1e-6 of the cost, |d| of the 11 camera parameters <= 1e-9); at most max_iters iterations.  The step solves
+ *   (J'J + lambda diag J'J) step = -J'r exactly by eliminating the points:
+ *    per point V = Jp'Jp (rows added in order) with V_ii <- V_ii + lambda*V_ii; its inverse by the adjugate divided by
+ *    det = (v00*c00 + v01*c01) + v02*c02; det > 0 and finite, else the step is rejected; g_p = Jp'e; W = Jc'Jp (11 x 3, the
+ *    A rows x A block, the C rows x C block); Y = W V^-1;
+ *    U = sum Jc'Jc (block diagonal: no residual sees both cameras), g_c = sum Jc'e;
+ *    H = (U + lambda diag U) - sum Y W', g = g_c - sum Y g_p;  H d = -g by the Cholesky of rpe_refine_poses (not positive
+ *    definite: rejected);  dp_j = -V^-1 (g_p + W' d), W' d added to g_p in ascending parameter order.
+ *   All sums over points run in the fixed order of "homography": lane l of 256 adds its points l, l + 256, ... in
+ *   ascending order, then the butterfly, then the four wave totals.  No atomics: bit-deterministic run to run.
+ *  Result: the bundled state is returned (RPE_BUNDLE_OK) only if a step was accepted, every pose entry and point
+ *   coordinate is finite and every point has positive depth in every view that observes it.  Otherwise
+ *   RPE_BUNDLE_REJECTED with the input poses and the input points.
+ *  Outputs (host, any may be NULL): R_a[L*9], t_a[L*3]: pair a's pose in pair a's own convention, |t_a| = 1;  R_b, t_b:
+ *   pair b's pose in its own convention on pair a's scale (the inverse expression of "link poses" where S is image 2);
+ *   points[L*max_matches*3] indexed by pair a's match index, in pair a's camera-1 frame (X itself when S is a's image 1,
+ *   R_A X + t_A when it is image 2), the layout of rpe_fetch_structure, zeros for a match that is not a point;
+ *   views[L*max_matches]: 0 not a point, 1 seen by S and A, 3 also by C;  counts[L*2] = {n2, n3};
+ *   info[L*4] = {RPE_BUNDLE_* code, iterations begun, accepted steps, 0};  rms[L*2] = sqrt(cost / (2*n2 + n3)), the root
+ *   mean square residual length in pixels over all observations, of the input state and of the returned state.
+ * The results live in buffers of their own, created on first use: every fetch of the run, rpe_refine_poses,
+ * rpe_scale_links, rpe_link_poses, rpe_pair_homographies and rpe_guided_matches(_l2) return the same bits afterwards.
+ * RPE_ERR_INVALID / RPE_ERR_CAPACITY: every refusal of rpe_scale_links; threshold_px not finite or <= 0; max_iters outside
+ * 1 .. 100; exactly one of R0 / t0 NULL, both NULL with L > 0, or a non-finite entry in either.  All checks are host-side;
+ * nothing is launched and the handle stays usable after a refusal.
+ *
+ * rpe_bundle_three_view is the stage form: B problems (B <= max_batch) of n[p] <= max_matches points each, arrays laid out
+ * [B][max_matches]: normalised observations obs_s / obs_a / obs_c (two doubles per point; obs_c is read where has_c is
+ * set), start points X0 (three doubles, S's frame), start poses in the solved form (Ra0, ta0 with |ta0| = 1: S -> A;
+ * Rc0, tc0: S -> C), one focal scale per view pair for the whole call.  No join and no gate: has_c is the caller's, and
+ * n3 < 6 is RPE_BUNDLE_TOO_FEW.  Outputs as above, in the solved form and S's frame, points indexed by point number.  It
+ * uses the bundle buffers only: the last run stays as it was. */
+enum { RPE_BUNDLE_OK = 0, RPE_BUNDLE_PAIR_FAILED = 1, RPE_BUNDLE_TOO_FEW = 2, RPE_BUNDLE_SKIPPED = 3, RPE_BUNDLE_REJECTED = 4 };
+int rpe_link_bundles(rpe_handle *h, int L, const int32_t *pair_a, const int32_t *pair_b, const int32_t *side,
+                     const double *R0, const double *t0, double threshold_px, int min_shared, int max_iters,
+                     double *R_a, double *t_a, double *R_b, double *t_b, double *points, uint8_t *views,
+                     int32_t *counts, int32_t *info, double *rms);
+int rpe_bundle_three_view(rpe_handle *h, int B, const int32_t *n, const double *obs_s, const double *obs_a,
+                          const double *obs_c, const uint8_t *has_c, const double *X0, const double *Ra0, const double *ta0,
+                          const double *Rc0, const double *tc0, double f_a, double f_c, int max_iters,
+                          double *R_a, double *t_a, double *R_c, double *t_c, double *points, uint8_t *views,
+                          int32_t *counts, int32_t *info, double *rms);
+
 /* ---------------------------------------------------------- stage entry */
 /* replaces extractor.detectAndCompute(image, None) (pose_estimator.py:108)
  * for n_images images (n_images <= 2*max_batch).  kps[n_images*cap],

@@ -30,6 +30,7 @@ REFINE_OK, REFINE_SKIPPED, REFINE_REJECTED = 0, 1, 2   # info[:, 0] of refine_po
 LINK_OK, LINK_PAIR_FAILED, LINK_TOO_FEW = 0, 1, 2      # code[] of scale_links (include/rpe_amd.h RPE_LINK_*)
 HOMOGRAPHY_OK, HOMOGRAPHY_SKIPPED, HOMOGRAPHY_NONE = 0, 1, 2   # info[:, 0] of pair_homographies (include/rpe_amd.h RPE_HOMOGRAPHY_*)
 LINKPOSE_OK, LINKPOSE_PAIR_FAILED, LINKPOSE_TOO_FEW, LINKPOSE_NONE = 0, 1, 2, 3   # info[:, 0] of link_poses (RPE_LINKPOSE_*)
+BUNDLE_OK, BUNDLE_PAIR_FAILED, BUNDLE_TOO_FEW, BUNDLE_SKIPPED, BUNDLE_REJECTED = 0, 1, 2, 3, 4   # info[:, 0] of link_bundles (RPE_BUNDLE_*)
 UNDISTORT_ITERS = 5               # RPE_UNDISTORT_ITERS: fixed-point rounds of the camera path's undistortion
 
 # The binding, one entry per function of include/rpe_amd.h: "<return>:<one letter per parameter>".  Parameters: p pointer or
@@ -54,6 +55,7 @@ _SIGNATURES = {
     "rpe_bgr_to_gray_device": "i:ppzip", "rpe_bgr_to_gray": "i:ppzip", "rpe_lsd_detect": "i:piipip",
     "rpe_fetch_matched_points": "i:pipp", "rpe_fetch_structure": "i:pippp", "rpe_refine_poses": "i:piippppp",
     "rpe_fetch_match_indices": "i:pipp", "rpe_scale_links": "i:pipppippp", "rpe_link_poses": "i:pipppidiipppppp",
+    "rpe_link_bundles": "i:pipppppdiippppppppp", "rpe_bundle_three_view": "i:pippppppppppddippppppppp",
     "rpe_guided_matches": "i:pippdipppppp",
     "rpe_guided_matches_l2": "i:pippddpppppp",
     "rpe_pair_homographies": "i:piidppppp", "rpe_find_homography": "i:ppppipidppppp",
@@ -422,6 +424,54 @@ class Engine:
         self._chk(self.lib.rpe_link_poses(self.h, L, _p(a), _p(b), _p(s), int(iters), thr, int(min_shared), int(refine_iters),
                                           _p(R), _p(t), _p(mask), _p(counts), _p(info), _p(rms)))
         return R, t, mask.astype(bool), counts, info, rms
+
+    # ---- link bundles (rpe_link_bundles / rpe_bundle_three_view; not in the reference)
+    def _bundle_outs(self, n):
+        mm = self.max_matches
+        return (np.zeros((n, 3, 3)), np.zeros((n, 3)), np.zeros((n, 3, 3)), np.zeros((n, 3)), np.zeros((n, mm, 3)),
+                np.zeros((n, mm), np.uint8), np.zeros((n, 2), np.int32), np.zeros((n, 4), np.int32), np.zeros((n, 2)))
+
+    def link_bundles(self, pair_a, pair_b, side, R0, t0, threshold_px=None, min_shared=8, max_iters=10):
+        """Bundle adjustment of the three views of every link of the last stream / pair list (rpe_link_bundles): the poses
+        of pair_a and pair_b and the points both see, refined together on the reprojection error, the shared frame fixed
+        and |t_a| = 1.  R0 f64[L, 3, 3], t0 f64[L, 3]: the start pose of pair_b on pair_a's scale, what link_poses
+        returns (an all-zero R0 skips the link: BUNDLE_SKIPPED); threshold_px gates pair_b's observations under that pose
+        (None = the handle's ransac_threshold).  Links as in scale_links.  Returns (R_a, t_a, R_b, t_b: the two pairs'
+        poses in their own conventions, t_b on pair_a's scale; points f64[L, mm, 3] by pair_a's match index in its camera-1
+        frame; views u8[L, mm]: 0 no point, 1 seen by pair_a's two frames, 3 by all three; counts i32[L, 2] = (points,
+        points seen by all three); info i32[L, 4] = (BUNDLE_* code, iterations, accepted steps, 0); rms f64[L, 2] =
+        reprojection rms in pixels before and after).  BUNDLE_REJECTED returns the input poses and points; the other codes
+        but OK return zeros.  The run's own results are not modified."""
+        a, b, s = _i32(pair_a), _i32(pair_b), _i32(side)
+        if not (a.size == b.size == s.size):
+            raise ValueError(f"link_bundles: pair_a, pair_b and side must have one length, got {(a.size, b.size, s.size)}")
+        L = a.size
+        R0 = None if R0 is None else np.ascontiguousarray(np.asarray(R0, np.float64).reshape(L, 9))
+        t0 = None if t0 is None else np.ascontiguousarray(np.asarray(t0, np.float64).reshape(L, 3))
+        outs = self._bundle_outs(L)
+        thr = float(self.cfg.ransac_threshold if threshold_px is None else threshold_px)
+        self._chk(self.lib.rpe_link_bundles(self.h, L, _p(a), _p(b), _p(s), _opt(R0), _opt(t0), thr, int(min_shared), int(max_iters),
+                                            *map(_p, outs)))
+        return outs
+
+    def bundle_three_view(self, obs_s, obs_a, obs_c, has_c, X0, Ra0, ta0, Rc0, tc0, f_a, f_c, max_iters=10):
+        """The bundle kernel on the caller's own tracks (rpe_bundle_three_view): B problems, problem p with obs_s[p], obs_a[p],
+        obs_c[p] f64[n_p, 2] (normalised observations on the gauge view S and on A and C), has_c[p] bool[n_p], X0[p]
+        f64[n_p, 3] (start points in S's frame) and start poses S -> A (|ta0| = 1) and S -> C; f_a, f_c scale the residuals
+        to pixels.  Returns link_bundles' tuple in the solved form: (R_a, t_a, R_c, t_c, points by point number in S's
+        frame, views, counts, info, rms).  Fewer than 6 points seen by C: BUNDLE_TOO_FEW."""
+        B, mm = len(X0), self.max_matches
+        n = np.array([len(x) for x in X0], np.int32)
+        if n.max(initial=0) > mm:
+            raise ValueError(f"bundle_three_view: more than max_matches = {mm} points in a problem")
+        pad = lambda arrs, w, dt: np.stack([np.concatenate([np.asarray(x, dt).reshape(-1, w), np.zeros((mm - len(x), w), dt)]) for x in arrs])
+        os_, oa, oc, x0 = pad(obs_s, 2, np.float64), pad(obs_a, 2, np.float64), pad(obs_c, 2, np.float64), pad(X0, 3, np.float64)
+        hc = pad(has_c, 1, np.uint8)
+        poses = [np.ascontiguousarray(np.asarray(v, np.float64).reshape(B, w)) for v, w in ((Ra0, 9), (ta0, 3), (Rc0, 9), (tc0, 3))]
+        outs = self._bundle_outs(B)
+        self._chk(self.lib.rpe_bundle_three_view(self.h, B, _p(n), _p(os_), _p(oa), _p(oc), _p(hc), _p(x0), *map(_p, poses),
+                                                 float(f_a), float(f_c), int(max_iters), *map(_p, outs)))
+        return outs
 
     # ---- guided matching (rpe_guided_matches / rpe_match_hamming_guided; not in the reference)
     def _poses(self, B, R, t):

@@ -1286,17 +1286,27 @@ __device__ __forceinline__ bool refine_solve(const double *H, const double *g, d
     return ok;
 }
 
-// The Levenberg-Marquardt loop over N parameters, shared by pose_refine_kernel and link_pose_kernel; all 256 threads call
-// it with identical operands.  s holds the normal equations at (R, t): the upper triangle of J'J, then J'r, then r'r = cost.
-//   linearise()        s at the caller's (R, t), summed over the workgroup (block_sum_f64 over all of s)
+// The Levenberg-Marquardt loop over N parameters, shared by pose_refine_kernel, link_pose_kernel and bundle_kernel; all 256
+// threads call it with identical operands.
+//   linearise()        the normal equations at the caller's state, summed over the workgroup (block_sum_f64)
+//   solve(lambda, d)   the damped step d from them; false when there is none (a matrix that is not positive definite).
+//                      RefineNormalSolve is the plain form: s holds the upper triangle of J'J, then J'r, then r'r
 //   trial(d, Rn, tn)   the pose (Rn, tn) that step d leads to from (R, t), and this thread's part of its cost
+//   commit()           an accepted step: whatever state the caller keeps outside (R, t) moves with it
 // A failed solve or a step that does not strictly lower the cost multiplies lambda by 10; an accepted step divides it by
 // 10, moves (R, t, cost) and stops the loop when it lowered the cost by no more than REFINE_REL_TOL of it or is no longer
-// than REFINE_STEP_TOL.  (R, t) is linearised again only when another iteration follows an accepted step.  iters counts
+// than REFINE_STEP_TOL.  The state is linearised again only when another iteration follows an accepted step.  iters counts
 // the iterations begun, acc the steps accepted.
-template <int N, class Linearise, class Trial>
-__device__ __forceinline__ void refine_lm(double (&R)[9], double (&t)[3], const double (&s)[N * (N + 1) / 2 + N + 1], double &cost,
-                                          int max_iters, double *s_red, Linearise linearise, Trial trial, int &iters, int &acc)
+template <int N>
+struct RefineNormalSolve {
+    const double *s;
+    __device__ __forceinline__ bool operator()(double lambda, double (&d)[N]) const { return refine_solve<N>(s, s + N * (N + 1) / 2, lambda, d); }
+};
+struct RefineNoCommit { __device__ __forceinline__ void operator()() const {} };
+
+template <int N, class Linearise, class Solve, class Trial, class Commit>
+__device__ __forceinline__ void refine_lm(double (&R)[9], double (&t)[3], double &cost, int max_iters, double *s_red,
+                                          Linearise linearise, Solve solve, Trial trial, Commit commit, int &iters, int &acc)
 {
     double lambda = REFINE_LAMBDA0;
     bool need_lin = false;
@@ -1304,7 +1314,7 @@ __device__ __forceinline__ void refine_lm(double (&R)[9], double (&t)[3], const 
         if (need_lin) { linearise(); need_lin = false; }
         ++iters;
         double d[N];
-        if (!refine_solve<N>(s, s + N * (N + 1) / 2, lambda, d)) { lambda = lambda * 10.; continue; }
+        if (!solve(lambda, d)) { lambda = lambda * 10.; continue; }
         double Rn[9], tn[3];
         double c1[1] = {trial(d, Rn, tn)};
         block_sum_f64<1>(c1, s_red, threadIdx.x);
@@ -1318,6 +1328,7 @@ __device__ __forceinline__ void refine_lm(double (&R)[9], double (&t)[3], const 
             for (int e = 0; e < 9; ++e) R[e] = Rn[e];
 #pragma unroll
             for (int e = 0; e < 3; ++e) t[e] = tn[e];
+            commit();
             cost = c1[0]; lambda = lambda / 10.; ++acc; need_lin = true;
             if (dec <= REFINE_REL_TOL * prev || dn <= REFINE_STEP_TOL) break;
         } else {
@@ -1416,7 +1427,7 @@ __global__ __launch_bounds__(256) void pose_refine_kernel(const double2 *__restr
         finite = isfinite(cost0);
     }
     if (!skip && finite) {
-        refine_lm<5>(R, t, s, cost, max_iters, s_red, linearise, trial, iters, acc);
+        refine_lm<5>(R, t, cost, max_iters, s_red, linearise, RefineNormalSolve<5>{s}, trial, RefineNoCommit{}, iters, acc);
 #pragma unroll
         for (int e = 0; e < 9; ++e) finite = finite && isfinite(R[e]);
 #pragma unroll
@@ -2337,7 +2348,7 @@ __global__ __launch_bounds__(256) void link_pose_kernel(const RpeLink *__restric
     const double cost0 = s[27];
     double cost = cost0;
     int lm_iters = 0, acc = 0;
-    if (isfinite(cost0)) refine_lm<6>(R, t, s, cost, refine_iters, s_red, linearise, trial, lm_iters, acc);
+    if (isfinite(cost0)) refine_lm<6>(R, t, cost, refine_iters, s_red, linearise, RefineNormalSolve<6>{s}, trial, RefineNoCommit{}, lm_iters, acc);
     // ---- fallback: the polished pose must be finite and keep the winner's count over all correspondences
     const int m = win_cnt;                                                  // the winner's inliers: the residual set
     int polish = 0;
@@ -2413,5 +2424,510 @@ int rpe_launch_link_poses(rpe_handle *h, const RpeRun &r, int L, int iters, doub
                (const unsigned short *)h->d_subsets, (const double *)h->d_K, r.cam, threshold_px, iters, h->cfg.ransac_max_iters,
                mm, kcap, min_shared, refine_iters, mm <= LP_LDS_MATCHES ? (double *)nullptr : h->d_lp_corr,
                h->d_lp_R, h->d_lp_t, h->d_lp_mask, h->d_lp_counts, h->d_lp_info, h->d_lp_rms);
+    return RPE_OK;
+}
+
+// ------------------------------------------------------------ link bundles
+// rpe_link_bundles / rpe_bundle_three_view (NOT in the reference; include/rpe_amd.h states the rule): bundle adjustment of
+// the three views of a link -- the poses of A and C relative to the shared frame S and the points both pairs see, on one
+// reprojection cost.  Two device steps, f64 throughout, no contraction:
+//   gather   (run form only) bundle_gather_kernel, one workgroup per link: link_join's table, then per match of pair a its
+//            view code (0 no point, 1 seen by S and A, 3 also by C: lp_inlier under the input pose of C), its three
+//            observations and its start point (link_point), all indexed by pair a's match index; the two start poses in
+//            the solved form (S -> A, S -> C) and the two focal scales.  The stage form uploads the same arrays.
+//   bundle   bundle_kernel, one workgroup per problem, whichever form filled the arrays: the points are compacted in index
+//            order (ordered_slot), their state (X and the trial X, 48 B per point) lives in LDS up to BA_LDS_MATCHES matches
+//            and in d_ba_state above it, walked through the same pointers in the same order; the observations are read
+//            where the gather left them.  refine_lm<11> with a solve policy of its own:
+//              linearise  U (block diagonal: 15 + 21), g_c (11) and the cost: 48 sums, parked in LDS between the trials
+//              solve      per point V = Jp'Jp + lambda diag, its adjugate inverse, W (11 x 3): 66 sums of W V^-1 W', 11 of
+//                         W V^-1 g_p and the count of singular V: 78 sums per damping trial; the reduced 11 x 11 system by
+//                         refine_solve<11> on every lane (identical operands)
+//              trial      the points' back-substitution d_p = -V^-1 (g_p + W' d_c) and the cost at the new state
+//            Every sum is block_sum_f64 over lane partials in strided order: bit-deterministic.
+// A point's Jacobians are formed three times per trial (solve, trial, and linearise after an accepted step): arithmetic is
+// small next to the barriers, and nothing per point but X is kept.
+#define BA_LDS_MATCHES 1024
+#define BA_NLIN 48                   // 15 U_AA + 21 U_CC + 11 g_c + 1 r'r
+#define BA_NRED 78                   // 66 W V^-1 W' + 11 W V^-1 g_p + 1 singular V
+
+// One point's rows of the Jacobian at the current state.  Rows: S x, S y, A x, A y, C x, C y; the C rows are zero without
+// that observation.
+struct BaPoint {
+    double e[6];                     // residuals in pixels
+    double JX[6][3];                 // by the point
+    double JA[2][5];                 // the A rows by (w0 w1 w2 | b1 b2)
+    double JC[2][6];                 // the C rows by (w0 w1 w2 | d0 d1 d2)
+};
+
+__device__ __forceinline__ void ba_point(const double (&RA)[9], const double (&tA)[3], const double (&b1)[3], const double (&b2)[3],
+                                         const double (&RC)[9], const double (&tC)[3], double fa, double fc, const double *X,
+                                         const double *q /*[6]*/, bool hc, BaPoint &p)
+{
+    {   // S: y = X
+        const double ux = X[0] / X[2], uy = X[1] / X[2], s = fa / X[2];
+        p.e[0] = fa * (ux - q[0]); p.e[1] = fa * (uy - q[1]);
+        p.JX[0][0] = s; p.JX[0][1] = 0.; p.JX[0][2] = -s * ux;
+        p.JX[1][0] = 0.; p.JX[1][1] = s; p.JX[1][2] = -s * uy;
+    }
+    double Jx[6], Jy[6];
+    lp_residual<true>(RA, tA, fa, X, q + 2, p.e[2], p.e[3], Jx, Jy);
+#pragma unroll
+    for (int k = 0; k < 3; ++k) {
+        p.JA[0][k] = Jx[k]; p.JA[1][k] = Jy[k];
+        p.JX[2][k] = (Jx[3] * RA[k] + Jx[4] * RA[3 + k]) + Jx[5] * RA[6 + k];
+        p.JX[3][k] = (Jy[3] * RA[k] + Jy[4] * RA[3 + k]) + Jy[5] * RA[6 + k];
+    }
+    p.JA[0][3] = (Jx[3] * b1[0] + Jx[4] * b1[1]) + Jx[5] * b1[2]; p.JA[0][4] = (Jx[3] * b2[0] + Jx[4] * b2[1]) + Jx[5] * b2[2];
+    p.JA[1][3] = (Jy[3] * b1[0] + Jy[4] * b1[1]) + Jy[5] * b1[2]; p.JA[1][4] = (Jy[3] * b2[0] + Jy[4] * b2[1]) + Jy[5] * b2[2];
+    if (hc) {
+        lp_residual<true>(RC, tC, fc, X, q + 4, p.e[4], p.e[5], Jx, Jy);
+#pragma unroll
+        for (int k = 0; k < 6; ++k) { p.JC[0][k] = Jx[k]; p.JC[1][k] = Jy[k]; }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) {
+            p.JX[4][k] = (Jx[3] * RC[k] + Jx[4] * RC[3 + k]) + Jx[5] * RC[6 + k];
+            p.JX[5][k] = (Jy[3] * RC[k] + Jy[4] * RC[3 + k]) + Jy[5] * RC[6 + k];
+        }
+    } else {
+        p.e[4] = 0.; p.e[5] = 0.;
+#pragma unroll
+        for (int k = 0; k < 6; ++k) { p.JC[0][k] = 0.; p.JC[1][k] = 0.; }
+#pragma unroll
+        for (int k = 0; k < 3; ++k) { p.JX[4][k] = 0.; p.JX[5][k] = 0.; }
+    }
+}
+
+// the squared residual length of one point over its views
+__device__ __forceinline__ double ba_cost(const double (&e)[6]) { return ((e[0] * e[0] + e[1] * e[1]) + (e[2] * e[2] + e[3] * e[3])) + (e[4] * e[4] + e[5] * e[5]); }
+
+// The point block of p under damping lambda: Vi = (Jp'Jp + lambda diag)^-1 by the adjugate (upper triangle 00 01 02 11 12
+// 22), g_p = Jp'r and W = Jc'Jp (rows 0..4: A, 5..10: C).  False when V is singular.
+__device__ __forceinline__ bool ba_block(const BaPoint &p, double lambda, double (&Vi)[6], double (&gp)[3], double (&W)[11][3])
+{
+    double v[6] = {0., 0., 0., 0., 0., 0.};
+#pragma unroll
+    for (int i = 0; i < 3; ++i) gp[i] = 0.;
+#pragma unroll
+    for (int r = 0; r < 6; ++r) {
+        v[0] += p.JX[r][0] * p.JX[r][0]; v[1] += p.JX[r][0] * p.JX[r][1]; v[2] += p.JX[r][0] * p.JX[r][2];
+        v[3] += p.JX[r][1] * p.JX[r][1]; v[4] += p.JX[r][1] * p.JX[r][2]; v[5] += p.JX[r][2] * p.JX[r][2];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) gp[i] += p.JX[r][i] * p.e[r];
+    }
+    v[0] = v[0] + lambda * v[0]; v[3] = v[3] + lambda * v[3]; v[5] = v[5] + lambda * v[5];
+    const double c00 = v[3] * v[5] - v[4] * v[4], c01 = v[2] * v[4] - v[1] * v[5], c02 = v[1] * v[4] - v[2] * v[3];
+    const double c11 = v[0] * v[5] - v[2] * v[2], c12 = v[1] * v[2] - v[0] * v[4], c22 = v[0] * v[3] - v[1] * v[1];
+    const double det = (v[0] * c00 + v[1] * c01) + v[2] * c02;
+    Vi[0] = c00 / det; Vi[1] = c01 / det; Vi[2] = c02 / det; Vi[3] = c11 / det; Vi[4] = c12 / det; Vi[5] = c22 / det;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+#pragma unroll
+        for (int k = 0; k < 5; ++k) W[k][i] = p.JA[0][k] * p.JX[2][i] + p.JA[1][k] * p.JX[3][i];
+#pragma unroll
+        for (int k = 0; k < 6; ++k) W[5 + k][i] = p.JC[0][k] * p.JX[4][i] + p.JC[1][k] * p.JX[5][i];
+    }
+    return det > 0. && hg_finite(det);
+}
+
+// row i of the symmetric 3 x 3 held as its upper triangle, times u
+__device__ __forceinline__ double ba_sym_row(const double (&S)[6], int i, const double (&u)[3])
+{
+    const double a = i == 0 ? S[0] : (i == 1 ? S[1] : S[2]), b = i == 0 ? S[1] : (i == 1 ? S[3] : S[4]);
+    const double c = i == 0 ? S[2] : (i == 1 ? S[4] : S[5]);
+    return (a * u[0] + b * u[1]) + c * u[2];
+}
+
+// R' and -R't: the inverse of x -> R x + t, by the expression of the link poses' output
+__device__ __forceinline__ void ba_invert(const double (&R)[9], const double (&t)[3], double (&Ri)[9], double (&ti)[3])
+{
+#pragma unroll
+    for (int r = 0; r < 3; ++r) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) Ri[r * 3 + c] = R[c * 3 + r];
+        ti[r] = -((R[r] * t[0] + R[3 + r] * t[1]) + R[6 + r] * t[2]);
+    }
+}
+
+template <bool CAM>
+__global__ __launch_bounds__(256) void bundle_gather_kernel(const RpeLink *__restrict__ links, const int *__restrict__ m_q,
+                                                             const int *__restrict__ m_t, const int *__restrict__ m_n,
+                                                             const int *__restrict__ status, const uint8_t *__restrict__ ransac_mask,
+                                                             const uint8_t *__restrict__ pose_mask, const double *__restrict__ points,
+                                                             const double *__restrict__ Rall, const double *__restrict__ tall,
+                                                             const double2 *__restrict__ n1, const double2 *__restrict__ n2,
+                                                             const double *__restrict__ K, const RpeCamSrc cam,
+                                                             const double *__restrict__ Rb_in, const double *__restrict__ tb_in,
+                                                             double threshold_px, int max_matches, int kcap,
+                                                             uint8_t *__restrict__ views, double *__restrict__ obs, double *__restrict__ X0,
+                                                             double *__restrict__ pose0, double *__restrict__ focal,
+                                                             int *__restrict__ pre, int *__restrict__ n_in)
+{
+    extern __shared__ unsigned s_ba_tab[];
+    const int link = blockIdx.x, tid = threadIdx.x;
+    const RpeLink lk = links[link];
+    const long long om = (long long)link * max_matches;
+    double Rb[9], tb[3];
+    bool zero = true;
+#pragma unroll
+    for (int e = 0; e < 9; ++e) { Rb[e] = Rb_in[link * 9 + e]; zero = zero && Rb[e] == 0.; }
+#pragma unroll
+    for (int e = 0; e < 3; ++e) tb[e] = tb_in[link * 3 + e];
+    const int code = status[lk.a] != RPE_PAIR_OK ? RPE_BUNDLE_PAIR_FAILED : (zero ? RPE_BUNDLE_SKIPPED : RPE_BUNDLE_OK);
+    if (code == RPE_BUNDLE_PAIR_FAILED) {                                    // workgroup-uniform
+        for (int i = tid; i < max_matches; i += 256) {
+            views[om + i] = 0;
+            X0[(om + i) * 3] = 0.; X0[(om + i) * 3 + 1] = 0.; X0[(om + i) * 3 + 2] = 0.;
+        }
+        if (tid < 24) pose0[link * 24 + tid] = 0.;
+        if (tid < 2) focal[link * 2 + tid] = 0.;
+        if (tid == 0) { pre[link] = code; n_in[link] = 0; }
+        return;
+    }
+    const bool a2 = (lk.side & 1) != 0, b2 = (lk.side & 2) != 0;
+    const int na = min(m_n[lk.a], max_matches), nb = min(m_n[lk.b], max_matches);
+    const long long oa = (long long)lk.a * max_matches, ob = (long long)lk.b * max_matches;
+    const int *key_a = (a2 ? m_t : m_q) + oa, *key_b = (b2 ? m_t : m_q) + ob;
+    link_join<false>(s_ba_tab, kcap, key_a, na, oa, key_b, nb, ob, ransac_mask, pose_mask);
+    double Ra[9], ta[3], RtC[LP_POSE_DOUBLES];
+#pragma unroll
+    for (int e = 0; e < 9; ++e) Ra[e] = Rall[lk.a * 9 + e];
+#pragma unroll
+    for (int e = 0; e < 3; ++e) ta[e] = tall[lk.a * 3 + e];
+    {   // the solved form of C: S -> C
+        double Ri[9], ti[3];
+        ba_invert(Rb, tb, Ri, ti);
+#pragma unroll
+        for (int e = 0; e < 9; ++e) RtC[e] = b2 ? Ri[e] : Rb[e];
+#pragma unroll
+        for (int e = 0; e < 3; ++e) RtC[9 + e] = b2 ? ti[e] : tb[e];
+    }
+    const double fa = rpe_pair_focal<CAM>(K, cam, lk.a), fc = rpe_pair_focal<CAM>(K, cam, lk.b);
+    const double thr = threshold_px / fc, thr2 = thr * thr;
+    const double2 *oS = (a2 ? n2 : n1) + oa, *oA = (a2 ? n1 : n2) + oa, *oC = (b2 ? n1 : n2) + ob;
+    for (int i = tid; i < max_matches; i += 256) {
+        int v = 0;
+        double X[3] = {0., 0., 0.};
+        if (i < na && ransac_mask[oa + i] && pose_mask[oa + i]) {
+            const int key = key_a[i];
+            const unsigned e = (unsigned)key < (unsigned)kcap ? s_ba_tab[key] : 0xFFFFFFFFu;
+            if ((e >> 16) == (unsigned)i) {
+                v = 1;
+                link_point(points + (oa + i) * 3, Ra, ta, a2, X[0], X[1], X[2]);
+                double *o = obs + (om + i) * 6;
+                const double2 s = oS[i], a = oA[i];
+                o[0] = s.x; o[1] = s.y; o[2] = a.x; o[3] = a.y;
+                if ((e & 0xFFFFu) != LINK_NONE) {
+                    const double2 c = oC[e & 0xFFFFu];
+                    const double q[2] = {c.x, c.y};
+                    o[4] = c.x; o[5] = c.y;
+                    if (lp_inlier(RtC, X, q, thr2)) v = 3;
+                }
+            }
+        }
+        views[om + i] = (uint8_t)v;
+        X0[(om + i) * 3] = X[0]; X0[(om + i) * 3 + 1] = X[1]; X0[(om + i) * 3 + 2] = X[2];
+    }
+    if (tid == 0) {
+        double Ri[9], ti[3];
+        ba_invert(Ra, ta, Ri, ti);
+        double *o = pose0 + link * 24;
+#pragma unroll
+        for (int e = 0; e < 9; ++e) { o[e] = a2 ? Ri[e] : Ra[e]; o[12 + e] = RtC[e]; }
+#pragma unroll
+        for (int e = 0; e < 3; ++e) { o[9 + e] = a2 ? ti[e] : ta[e]; o[21 + e] = RtC[9 + e]; }
+        focal[link * 2] = fa; focal[link * 2 + 1] = fc;
+        pre[link] = code; n_in[link] = na;
+    }
+}
+
+// links == nullptr: the stage form, results in the solved form and in S's frame.  Otherwise the results go back into the
+// two pairs' own conventions and pair a's camera-1 frame, and a rejected bundle returns the run's own poses and points
+// (src_points / Rall / tall of pair a) and the caller's pose of pair b (Rb_in / tb_in).
+__global__ __launch_bounds__(256) void bundle_kernel(const int *__restrict__ n_in, const int *__restrict__ pre, uint8_t *__restrict__ views,
+                                                      const double *__restrict__ obs, double *__restrict__ points,
+                                                      const double *__restrict__ pose0, const double *__restrict__ focal,
+                                                      int min_shared, int max_iters, int max_matches, double *__restrict__ state,
+                                                      const RpeLink *__restrict__ links, const double *__restrict__ src_points,
+                                                      const double *__restrict__ Rall, const double *__restrict__ tall,
+                                                      const double *__restrict__ Rb_in, const double *__restrict__ tb_in,
+                                                      double *__restrict__ Ra_out, double *__restrict__ ta_out, double *__restrict__ Rb_out,
+                                                      double *__restrict__ tb_out, int *__restrict__ counts, int *__restrict__ info,
+                                                      double *__restrict__ rms)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char s_ba[];
+    __shared__ double s_red[4 * BA_NRED], s_lin[BA_NLIN];
+    __shared__ int s_wc[4];
+    const int prob = blockIdx.x, tid = threadIdx.x;
+    const long long om = (long long)prob * max_matches;
+    double *sX = state ? state + om * 6 : (double *)s_ba, *sXn = sX + 3 * (size_t)max_matches;     // [n][3] each
+    unsigned short *s_idx = (unsigned short *)(s_ba + (state ? 0 : sizeof(double) * 6 * (size_t)max_matches));
+    const int M = min(max(n_in[prob], 0), max_matches);
+    uint8_t *vw = views + om;
+    double *pts = points + om * 3;
+    const double *ob = obs + om * 6;
+    // ---- the points in index order, their state, the counts
+    int n = 0, n3 = 0;
+    for (int i0 = 0; i0 < M; i0 += 256) {
+        const int i = i0 + tid;
+        const int v = i < M ? vw[i] : 0;
+        const int pos = ordered_slot(v != 0, s_wc, n);
+        (void)ordered_slot(v == 3, s_wc, n3);
+        if (v != 0) {
+            s_idx[pos] = (unsigned short)i;
+            sX[3 * pos] = pts[3 * i]; sX[3 * pos + 1] = pts[3 * i + 1]; sX[3 * pos + 2] = pts[3 * i + 2];
+        }
+    }
+    __syncthreads();                                                         // the list is complete
+    int code = pre[prob];
+    if (code == RPE_BUNDLE_OK && n3 < max(min_shared, 6)) code = RPE_BUNDLE_TOO_FEW;
+    if (code != RPE_BUNDLE_OK) {                                             // workgroup-uniform
+        for (int i = tid; i < max_matches; i += 256) { vw[i] = 0; pts[3 * i] = 0.; pts[3 * i + 1] = 0.; pts[3 * i + 2] = 0.; }
+        if (tid < 9) { Ra_out[prob * 9 + tid] = 0.; Rb_out[prob * 9 + tid] = 0.; }
+        if (tid < 3) { ta_out[prob * 3 + tid] = 0.; tb_out[prob * 3 + tid] = 0.; }
+        if (tid < 2) rms[prob * 2 + tid] = 0.;
+        if (tid == 0) {
+            counts[prob * 2] = n; counts[prob * 2 + 1] = n3;
+            info[prob * 4] = code; info[prob * 4 + 1] = 0; info[prob * 4 + 2] = 0; info[prob * 4 + 3] = 0;
+        }
+        return;
+    }
+    double RA[9], tA[3], RC[9], tC[3], RCn[9], tCn[3], b1[3], b2[3];
+#pragma unroll
+    for (int e = 0; e < 9; ++e) { RA[e] = pose0[prob * 24 + e]; RC[e] = pose0[prob * 24 + 12 + e]; }
+#pragma unroll
+    for (int e = 0; e < 3; ++e) { tA[e] = pose0[prob * 24 + 9 + e]; tC[e] = pose0[prob * 24 + 21 + e]; }
+    const double fa = focal[prob * 2], fc = focal[prob * 2 + 1];
+    double lam = 0.;                                                         // the damping solve() met last: trial() builds the same blocks
+    auto point = [&](int j, BaPoint &p) {
+        const int i = s_idx[j];
+        ba_point(RA, tA, b1, b2, RC, tC, fa, fc, sX + 3 * j, ob + 6 * i, vw[i] == 3, p);
+    };
+    // also leaves the tangent basis at tA in (b1, b2)
+    auto linearise = [&]() {
+        refine_basis(tA, b1, b2);
+        double s[BA_NLIN];
+#pragma unroll
+        for (int k = 0; k < BA_NLIN; ++k) s[k] = 0.;
+        for (int j = tid; j < n; j += 256) {
+            BaPoint p;
+            point(j, p);
+            int q = 0;
+#pragma unroll
+            for (int u = 0; u < 5; ++u)
+#pragma unroll
+                for (int v = u; v < 5; ++v, ++q) s[q] += p.JA[0][u] * p.JA[0][v] + p.JA[1][u] * p.JA[1][v];
+#pragma unroll
+            for (int u = 0; u < 6; ++u)
+#pragma unroll
+                for (int v = u; v < 6; ++v, ++q) s[q] += p.JC[0][u] * p.JC[0][v] + p.JC[1][u] * p.JC[1][v];
+#pragma unroll
+            for (int u = 0; u < 5; ++u) s[36 + u] += p.JA[0][u] * p.e[2] + p.JA[1][u] * p.e[3];
+#pragma unroll
+            for (int u = 0; u < 6; ++u) s[41 + u] += p.JC[0][u] * p.e[4] + p.JC[1][u] * p.e[5];
+            s[47] += ba_cost(p.e);
+        }
+        block_sum_f64<BA_NLIN>(s, s_red, tid);
+        __syncthreads();                                                     // readers of the previous s_lin are done
+        if (tid == 0) {
+#pragma unroll
+            for (int k = 0; k < BA_NLIN; ++k) s_lin[k] = s[k];
+        }
+        __syncthreads();
+    };
+    // the reduced camera system (U + lambda diag U) - sum W V^-1 W', right-hand side g_c - sum W V^-1 g_p
+    auto solve = [&](double lambda, double (&d)[11]) {
+        lam = lambda;
+        double r[BA_NRED];
+#pragma unroll
+        for (int k = 0; k < BA_NRED; ++k) r[k] = 0.;
+        for (int j = tid; j < n; j += 256) {
+            BaPoint p;
+            point(j, p);
+            double Vi[6], gp[3], W[11][3];
+            if (!ba_block(p, lambda, Vi, gp, W)) { r[77] += 1.; continue; }
+            int q = 0;
+#pragma unroll
+            for (int k = 0; k < 11; ++k) {
+                const double Y[3] = {ba_sym_row(Vi, 0, W[k]), ba_sym_row(Vi, 1, W[k]), ba_sym_row(Vi, 2, W[k])};
+#pragma unroll
+                for (int l = k; l < 11; ++l, ++q) r[q] += (Y[0] * W[l][0] + Y[1] * W[l][1]) + Y[2] * W[l][2];
+                r[66 + k] += (Y[0] * gp[0] + Y[1] * gp[1]) + Y[2] * gp[2];
+            }
+        }
+        block_sum_f64<BA_NRED>(r, s_red, tid);
+        if (r[77] != 0.) return false;
+        double g[11];
+        int q = 0;
+#pragma unroll
+        for (int k = 0; k < 11; ++k) {
+#pragma unroll
+            for (int l = k; l < 11; ++l, ++q) {
+                double u = 0.;                                               // no residual sees both cameras
+                if (k < 5 && l < 5) u = s_lin[k * 5 - k * (k - 1) / 2 + (l - k)];
+                if (k >= 5) u = s_lin[15 + (k - 5) * 6 - (k - 5) * (k - 6) / 2 + (l - k)];
+                if (l == k) u = u + lambda * u;
+                r[q] = u - r[q];
+            }
+            g[k] = s_lin[36 + k] - r[66 + k];
+        }
+        return refine_solve<11>(r, g, 0., d);
+    };
+    // RA <- exp([w]x) RA, tA <- normalise(tA + d3 b1 + d4 b2), RC <- exp([w']x) RC, tC <- tC + d', X <- X + d_p
+    auto trial = [&](const double (&d)[11], double (&RAn)[9], double (&tAn)[3]) {
+        refine_rotate(d, RA, RAn);
+#pragma unroll
+        for (int e = 0; e < 3; ++e) tAn[e] = (tA[e] + d[3] * b1[e]) + d[4] * b2[e];
+        const double nt = sqrt((tAn[0] * tAn[0] + tAn[1] * tAn[1]) + tAn[2] * tAn[2]);
+        tAn[0] /= nt; tAn[1] /= nt; tAn[2] /= nt;
+        refine_rotate(d + 5, RC, RCn);
+#pragma unroll
+        for (int e = 0; e < 3; ++e) tCn[e] = tC[e] + d[8 + e];
+        double c = 0.;
+        for (int j = tid; j < n; j += 256) {
+            BaPoint p;
+            point(j, p);
+            double Vi[6], gp[3], W[11][3];
+            ba_block(p, lam, Vi, gp, W);
+            double u[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) {
+                double a = gp[i];
+#pragma unroll
+                for (int k = 0; k < 11; ++k) a += W[k][i] * d[k];
+                u[i] = a;
+            }
+            double Xn[3];
+#pragma unroll
+            for (int i = 0; i < 3; ++i) { Xn[i] = sX[3 * j + i] - ba_sym_row(Vi, i, u); sXn[3 * j + i] = Xn[i]; }
+            const double *q = ob + 6 * s_idx[j];
+            double e[6];
+            e[0] = fa * (Xn[0] / Xn[2] - q[0]); e[1] = fa * (Xn[1] / Xn[2] - q[1]);
+            lp_residual<false>(RAn, tAn, fa, Xn, q + 2, e[2], e[3], nullptr, nullptr);
+            e[4] = 0.; e[5] = 0.;
+            if (vw[s_idx[j]] == 3) lp_residual<false>(RCn, tCn, fc, Xn, q + 4, e[4], e[5], nullptr, nullptr);
+            c += ba_cost(e);
+        }
+        return c;
+    };
+    // a thread owns the same points in every pass: no barrier between its trial and its commit
+    auto commit = [&]() {
+#pragma unroll
+        for (int e = 0; e < 9; ++e) RC[e] = RCn[e];
+#pragma unroll
+        for (int e = 0; e < 3; ++e) tC[e] = tCn[e];
+        for (int j = tid; j < n; j += 256) { sX[3 * j] = sXn[3 * j]; sX[3 * j + 1] = sXn[3 * j + 1]; sX[3 * j + 2] = sXn[3 * j + 2]; }
+    };
+    linearise();
+    const double cost0 = s_lin[47];
+    double cost = cost0;
+    int iters = 0, acc = 0;
+    if (isfinite(cost0)) refine_lm<11>(RA, tA, cost, max_iters, s_red, linearise, solve, trial, commit, iters, acc);
+    // ---- the bundled state is returned only if a step was accepted, it is finite and every point lies in front of its views
+    double bad[1] = {0.};
+    if (acc > 0) {
+#pragma unroll
+        for (int e = 0; e < 9; ++e) if (!hg_finite(RA[e]) || !hg_finite(RC[e])) bad[0] = 1.;
+#pragma unroll
+        for (int e = 0; e < 3; ++e) if (!hg_finite(tA[e]) || !hg_finite(tC[e])) bad[0] = 1.;
+        for (int j = tid; j < n; j += 256) {
+            const double *X = sX + 3 * j;
+            const double zA = ((RA[6] * X[0] + RA[7] * X[1]) + RA[8] * X[2]) + tA[2], zC = ((RC[6] * X[0] + RC[7] * X[1]) + RC[8] * X[2]) + tC[2];
+            bool ok = hg_finite(X[0]) && hg_finite(X[1]) && hg_finite(X[2]) && X[2] > 0. && zA > 0.;
+            if (vw[s_idx[j]] == 3) ok = ok && zC > 0.;
+            if (!ok) bad[0] += 1.;
+        }
+        block_sum_f64<1>(bad, s_red, tid);
+    }
+    const bool take = acc > 0 && bad[0] == 0.;
+    const int nobs = 2 * n + n3;
+    // ---- outputs
+    int sa = 0, sb = 0, pa = 0;
+    if (links) { const RpeLink lk = links[prob]; sa = lk.side & 1; sb = lk.side & 2; pa = lk.a; }
+    if (take) {
+        for (int j = tid; j < n; j += 256) {
+            const double *X = sX + 3 * j;
+            double *o = pts + 3 * s_idx[j];
+            if (sa) {                                                        // pair a's camera 1 is A
+#pragma unroll
+                for (int r = 0; r < 3; ++r) o[r] = ((RA[3 * r] * X[0] + RA[3 * r + 1] * X[1]) + RA[3 * r + 2] * X[2]) + tA[r];
+            } else { o[0] = X[0]; o[1] = X[1]; o[2] = X[2]; }
+        }
+    } else if (links) {
+        for (int j = tid; j < n; j += 256) {
+            const int i = s_idx[j];
+            const double *P = src_points + ((long long)pa * max_matches + i) * 3;
+            pts[3 * i] = P[0]; pts[3 * i + 1] = P[1]; pts[3 * i + 2] = P[2];
+        }
+    }
+    if (tid == 0) {
+        double Ro[9], to[3], Ri[9], ti[3];
+        if (take || !links) {
+            if (!take) {
+#pragma unroll
+                for (int e = 0; e < 9; ++e) { RA[e] = pose0[prob * 24 + e]; RC[e] = pose0[prob * 24 + 12 + e]; }
+#pragma unroll
+                for (int e = 0; e < 3; ++e) { tA[e] = pose0[prob * 24 + 9 + e]; tC[e] = pose0[prob * 24 + 21 + e]; }
+            }
+            ba_invert(RA, tA, Ri, ti);
+#pragma unroll
+            for (int e = 0; e < 9; ++e) Ro[e] = sa ? Ri[e] : RA[e];
+#pragma unroll
+            for (int e = 0; e < 3; ++e) to[e] = sa ? ti[e] : tA[e];
+#pragma unroll
+            for (int e = 0; e < 9; ++e) Ra_out[prob * 9 + e] = Ro[e];
+#pragma unroll
+            for (int e = 0; e < 3; ++e) ta_out[prob * 3 + e] = to[e];
+            ba_invert(RC, tC, Ri, ti);
+#pragma unroll
+            for (int e = 0; e < 9; ++e) Rb_out[prob * 9 + e] = sb ? Ri[e] : RC[e];
+#pragma unroll
+            for (int e = 0; e < 3; ++e) tb_out[prob * 3 + e] = sb ? ti[e] : tC[e];
+        } else {
+#pragma unroll
+            for (int e = 0; e < 9; ++e) { Ra_out[prob * 9 + e] = Rall[pa * 9 + e]; Rb_out[prob * 9 + e] = Rb_in[prob * 9 + e]; }
+#pragma unroll
+            for (int e = 0; e < 3; ++e) { ta_out[prob * 3 + e] = tall[pa * 3 + e]; tb_out[prob * 3 + e] = tb_in[prob * 3 + e]; }
+        }
+        counts[prob * 2] = n; counts[prob * 2 + 1] = n3;
+        info[prob * 4] = take ? RPE_BUNDLE_OK : RPE_BUNDLE_REJECTED; info[prob * 4 + 1] = iters; info[prob * 4 + 2] = acc; info[prob * 4 + 3] = 0;
+        const double before = sqrt(cost0 / nobs);
+        rms[prob * 2] = before;
+        rms[prob * 2 + 1] = take ? sqrt(cost / nobs) : before;
+    }
+}
+
+// dynamic LDS of bundle_kernel: the point state up to the cut, then the index list
+static size_t bundle_lds(int mm) { return (mm <= BA_LDS_MATCHES ? sizeof(double) * 6 * (size_t)mm : 0) + sizeof(unsigned short) * (size_t)((mm + 7) & ~7); }
+
+// the point state of this handle fits the kernel's LDS (else the callers create d_ba_state)
+bool rpe_bundles_in_lds(const rpe_handle *h) { return h->cfg.max_matches <= BA_LDS_MATCHES; }
+
+// n problems whose arrays are in d_ba_* (the stage form uploaded them, or the gather below wrote them) -> d_ba_* results
+void rpe_launch_bundle(rpe_handle *h, int n, int min_shared, int max_iters, bool links)
+{
+    const int mm = h->cfg.max_matches;
+    hipLaunchKernelGGL(bundle_kernel, dim3(n), dim3(256), bundle_lds(mm), h->stream, (const int *)h->d_ba_n, (const int *)h->d_ba_pre,
+                       h->d_ba_views, (const double *)h->d_ba_obs, h->d_ba_points, (const double *)h->d_ba_pose0, (const double *)h->d_ba_focal,
+                       min_shared, max_iters, mm, mm <= BA_LDS_MATCHES ? (double *)nullptr : h->d_ba_state,
+                       links ? (const RpeLink *)h->d_links : (const RpeLink *)nullptr, (const double *)h->d_points,
+                       (const double *)h->d_R, (const double *)h->d_t, (const double *)h->d_ba_Rin, (const double *)h->d_ba_tin,
+                       h->d_ba_Ra, h->d_ba_ta, h->d_ba_Rb, h->d_ba_tb, h->d_ba_counts, h->d_ba_info, h->d_ba_rms);
+}
+
+// the links in d_links over the last run r, the callers' poses of pair b in d_ba_Rin / d_ba_tin -> the problems' arrays
+int rpe_launch_bundle_gather(rpe_handle *h, const RpeRun &r, int L, double threshold_px)
+{
+    const int mm = h->cfg.max_matches, kcap = h->lay.kcap;
+    const size_t lds = sizeof(unsigned) * (size_t)kcap;
+    // the table is all of the kernel's LDS: the largest (uncapped SIFT, 16384 entries) is exactly the 64 KB a kernel gets
+    // without the function attribute
+    if (lds > 65536) return RPE_ERR_HIP;
+    launch_cam(r, bundle_gather_kernel<true>, bundle_gather_kernel<false>, dim3(L), dim3(256), lds, h->stream, (const RpeLink *)h->d_links,
+               (const int *)h->d_m_q, (const int *)h->d_m_t, (const int *)h->d_m_n, (const int *)h->d_status,
+               (const uint8_t *)h->d_mask, (const uint8_t *)h->d_pose_mask, (const double *)h->d_points,
+               (const double *)h->d_R, (const double *)h->d_t, (const double2 *)h->d_n1, (const double2 *)h->d_n2,
+               (const double *)h->d_K, r.cam, (const double *)h->d_ba_Rin, (const double *)h->d_ba_tin, threshold_px, mm, kcap,
+               h->d_ba_views, h->d_ba_obs, h->d_ba_points, h->d_ba_pose0, h->d_ba_focal, h->d_ba_pre, h->d_ba_n);
     return RPE_OK;
 }

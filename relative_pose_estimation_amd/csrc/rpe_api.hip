@@ -676,7 +676,7 @@ static int last_run_structure(rpe_handle *h, int B, bool always)
 // | rpe_fetch_overflow                                    | no (served from ovf)  | no             | yes                        | yes, n = n_pairs                      |
 // | rpe_fetch_matched_points, rpe_fetch_match_indices     | yes                   | no             | no                         | no                                    |
 // | rpe_fetch_structure, rpe_refine_poses                 | yes                   | yes            | yes                        | no                                    |
-// | rpe_scale_links, rpe_link_poses                       | yes                   | yes            | no (checks its links' own) | yes, n = the run's pairs              |
+// | rpe_scale_links, rpe_link_poses, rpe_link_bundles     | yes                   | yes            | no (checks its links' own) | yes, n = the run's pairs              |
 // | rpe_guided_matches(_l2), rpe_pair_homographies        | yes                   | yes            | yes                        | yes, n = B                            |
 //
 // Tested in this order, so a state gives one message whatever the call.  Two tests stay with their only caller:
@@ -1031,7 +1031,7 @@ static int homography_check(rpe_handle *h, const char *who, int iters, double th
     return RPE_OK;
 }
 
-// The argument head of the calls over links (rpe_scale_links, rpe_link_poses): every check on the host first (the kept
+// The argument head of the calls over links (rpe_scale_links, rpe_link_poses, rpe_link_bundles): every check on the host first (the kept
 // pair table of a list, the rule of a stream), then the structure kernels when the per-match buffers do not hold their
 // results for the whole run, and the link table on its way to d_links.  L == 0 passes the checks and does nothing more.
 static int links_begin(rpe_handle *h, const char *who, int L, const int32_t *pair_a, const int32_t *pair_b, const int32_t *side, int min_shared)
@@ -1101,6 +1101,106 @@ extern "C" int rpe_link_poses(rpe_handle *h, int L, const int32_t *pair_a, const
     const size_t n = (size_t)L;
     return fetch(h, {{R, h->d_lp_R, sizeof(double) * 9 * n}, {t, h->d_lp_t, sizeof(double) * 3 * n}, {mask, h->d_lp_mask, n * mm},
                      {counts, h->d_lp_counts, sizeof(int) * 2 * n}, {info, h->d_lp_info, sizeof(int) * 4 * n}, {rms, h->d_lp_rms, sizeof(double) * 2 * n}});
+}
+
+// link bundles: the buffers of both forms on first use
+static int bundle_alloc(rpe_handle *h)
+{
+    const size_t lcap = (size_t)4 * h->cfg.max_batch, mm = (size_t)h->cfg.max_matches;
+    DM_ONCE(h, h->d_ba_views, lcap * mm); DM_ONCE(h, h->d_ba_obs, lcap * mm * 6); DM_ONCE(h, h->d_ba_points, lcap * mm * 3);
+    DM_ONCE(h, h->d_ba_pose0, lcap * 24); DM_ONCE(h, h->d_ba_focal, lcap * 2); DM_ONCE(h, h->d_ba_n, lcap); DM_ONCE(h, h->d_ba_pre, lcap);
+    DM_ONCE(h, h->d_ba_Rin, lcap * 9); DM_ONCE(h, h->d_ba_tin, lcap * 3);
+    DM_ONCE(h, h->d_ba_Ra, lcap * 9); DM_ONCE(h, h->d_ba_ta, lcap * 3); DM_ONCE(h, h->d_ba_Rb, lcap * 9); DM_ONCE(h, h->d_ba_tb, lcap * 3);
+    DM_ONCE(h, h->d_ba_counts, lcap * 2); DM_ONCE(h, h->d_ba_info, lcap * 4); DM_ONCE(h, h->d_ba_rms, lcap * 2);
+    if (!rpe_bundles_in_lds(h)) DM_ONCE(h, h->d_ba_state, lcap * mm * 6);
+    return RPE_OK;
+}
+
+static int bundle_fetch(rpe_handle *h, size_t n, double *R_a, double *t_a, double *R_b, double *t_b, double *points, uint8_t *views,
+                        int32_t *counts, int32_t *info, double *rms)
+{
+    const size_t mm = (size_t)h->cfg.max_matches;
+    return fetch(h, {{R_a, h->d_ba_Ra, sizeof(double) * 9 * n}, {t_a, h->d_ba_ta, sizeof(double) * 3 * n}, {R_b, h->d_ba_Rb, sizeof(double) * 9 * n},
+                     {t_b, h->d_ba_tb, sizeof(double) * 3 * n}, {points, h->d_ba_points, sizeof(double) * 3 * n * mm}, {views, h->d_ba_views, n * mm},
+                     {counts, h->d_ba_counts, sizeof(int) * 2 * n}, {info, h->d_ba_info, sizeof(int) * 4 * n}, {rms, h->d_ba_rms, sizeof(double) * 2 * n}});
+}
+
+static bool all_finite(const double *v, size_t n)
+{
+    bool fin = true;
+    for (size_t i = 0; i < n; ++i) fin = fin && std::isfinite(v[i]);
+    return fin;
+}
+
+// rpe_link_bundles: its own checks and the links' argument head (all before anything is launched), the buffers on first
+// use, the poses of pair b up, two kernels, one fetch.  Nothing of the run is written.
+extern "C" int rpe_link_bundles(rpe_handle *h, int L, const int32_t *pair_a, const int32_t *pair_b, const int32_t *side,
+                                const double *R0, const double *t0, double threshold_px, int min_shared, int max_iters,
+                                double *R_a, double *t_a, double *R_b, double *t_b, double *points, uint8_t *views,
+                                int32_t *counts, int32_t *info, double *rms)
+{
+    if (!h) return rpe_invalid(h, "rpe_link_bundles");
+    if (!std::isfinite(threshold_px) || !(threshold_px > 0.)) return rpe_invalid(h, "rpe_link_bundles", "threshold_px must be finite and > 0");
+    if (max_iters < 1 || max_iters > 100) return rpe_invalid(h, "rpe_link_bundles", "max_iters must be 1 ... 100");
+    if ((R0 == nullptr) != (t0 == nullptr) || (L > 0 && !R0)) return rpe_invalid(h, "rpe_link_bundles", "R0 and t0 must both be given");
+    const size_t n = (size_t)std::max(L, 0);
+    if (R0 && (!all_finite(R0, 9 * n) || !all_finite(t0, 3 * n))) return rpe_invalid(h, "rpe_link_bundles", "a pose has a non-finite entry");
+    int rc = links_begin(h, "rpe_link_bundles", L, pair_a, pair_b, side, min_shared);
+    if (rc != RPE_OK || L == 0) return rc;
+    if ((rc = bundle_alloc(h)) != RPE_OK) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->d_ba_Rin, R0, sizeof(double) * 9 * n, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_ba_tin, t0, sizeof(double) * 3 * n, hipMemcpyHostToDevice, h->stream));
+    if ((rc = rpe_launch_bundle_gather(h, h->last.run, L, threshold_px)) != RPE_OK) { h->err = "rpe_link_bundles: could not size the kernel's LDS"; return rc; }
+    rpe_launch_bundle(h, L, min_shared, max_iters, true);
+    HIPCHK(h, hipGetLastError());
+    // the wait also covers the upload: the poses have left the caller's arrays
+    return bundle_fetch(h, n, R_a, t_a, R_b, t_b, points, views, counts, info, rms);
+}
+
+// rpe_bundle_three_view: the problems' arrays packed on the host as the gather kernel leaves them, one kernel, one fetch
+extern "C" int rpe_bundle_three_view(rpe_handle *h, int B, const int32_t *n, const double *obs_s, const double *obs_a,
+                                     const double *obs_c, const uint8_t *has_c, const double *X0, const double *Ra0, const double *ta0,
+                                     const double *Rc0, const double *tc0, double f_a, double f_c, int max_iters,
+                                     double *R_a, double *t_a, double *R_c, double *t_c, double *points, uint8_t *views,
+                                     int32_t *counts, int32_t *info, double *rms)
+{
+    if (!h || !n || !obs_s || !obs_a || !obs_c || !has_c || !X0 || !Ra0 || !ta0 || !Rc0 || !tc0 || B < 1) return rpe_invalid(h, "rpe_bundle_three_view");
+    if (int rc = check_batch(h, B)) return rc;
+    if (max_iters < 1 || max_iters > 100) return rpe_invalid(h, "rpe_bundle_three_view", "max_iters must be 1 ... 100");
+    if (!std::isfinite(f_a) || !(f_a > 0.) || !std::isfinite(f_c) || !(f_c > 0.)) return rpe_invalid(h, "rpe_bundle_three_view", "f_a and f_c must be finite and > 0");
+    int rc = check_match_counts(h, n, B);
+    if (rc) return rc;
+    const size_t nb = (size_t)B, mm = (size_t)h->cfg.max_matches;
+    if (!all_finite(Ra0, 9 * nb) || !all_finite(ta0, 3 * nb) || !all_finite(Rc0, 9 * nb) || !all_finite(tc0, 3 * nb))
+        return rpe_invalid(h, "rpe_bundle_three_view", "a pose has a non-finite entry");
+    std::vector<uint8_t> vw(nb * mm, 0);
+    std::vector<double> ob(nb * mm * 6, 0.), x0(nb * mm * 3, 0.), pose(nb * 24), foc(nb * 2);
+    std::vector<int> pre(nb, RPE_BUNDLE_OK);
+    for (size_t p = 0; p < nb; ++p) {
+        for (size_t i = 0; i < (size_t)n[p]; ++i) {
+            const size_t k = p * mm + i;
+            vw[k] = has_c[k] ? 3 : 1;
+            ob[k * 6] = obs_s[k * 2]; ob[k * 6 + 1] = obs_s[k * 2 + 1]; ob[k * 6 + 2] = obs_a[k * 2]; ob[k * 6 + 3] = obs_a[k * 2 + 1];
+            if (has_c[k]) { ob[k * 6 + 4] = obs_c[k * 2]; ob[k * 6 + 5] = obs_c[k * 2 + 1]; }
+            for (int e = 0; e < 3; ++e) x0[k * 3 + e] = X0[k * 3 + e];
+        }
+        for (int e = 0; e < 9; ++e) { pose[p * 24 + e] = Ra0[p * 9 + e]; pose[p * 24 + 12 + e] = Rc0[p * 9 + e]; }
+        for (int e = 0; e < 3; ++e) { pose[p * 24 + 9 + e] = ta0[p * 3 + e]; pose[p * 24 + 21 + e] = tc0[p * 3 + e]; }
+        foc[p * 2] = f_a; foc[p * 2 + 1] = f_c;
+    }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if ((rc = bundle_alloc(h)) != RPE_OK) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->d_ba_views, vw.data(), vw.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_ba_obs, ob.data(), sizeof(double) * ob.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_ba_points, x0.data(), sizeof(double) * x0.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_ba_pose0, pose.data(), sizeof(double) * pose.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_ba_focal, foc.data(), sizeof(double) * foc.size(), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_ba_pre, pre.data(), sizeof(int) * nb, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_ba_n, n, sizeof(int) * nb, hipMemcpyHostToDevice, h->stream));
+    rpe_launch_bundle(h, B, 1, max_iters, false);
+    HIPCHK(h, hipGetLastError());
+    // the wait also covers the uploads: the staging vectors live until it returns
+    return bundle_fetch(h, nb, R_a, t_a, R_c, t_c, points, views, counts, info, rms);
 }
 
 // refined poses: device buffers on first use, launch, fetch

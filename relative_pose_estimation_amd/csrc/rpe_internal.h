@@ -392,6 +392,17 @@ struct rpe_handle {
     double *d_lp_R = nullptr, *d_lp_t = nullptr, *d_lp_rms = nullptr, *d_lp_corr = nullptr;
     int *d_lp_counts = nullptr, *d_lp_info = nullptr;
     uint8_t *d_lp_mask = nullptr;
+    // rpe_link_bundles / rpe_bundle_three_view only (created on first use), 4*max_batch problems.  The problems' arrays,
+    // indexed by pair a's match index (stage form: point number): view code [prob][max_matches], observations
+    // [prob][max_matches][6] (S, A, C), points [prob][max_matches][3] (start points in, results out); per problem the scan
+    // length, the code decided before the bundle, the start poses in the solved form [24] and the focal scales [2]; the
+    // callers' poses of pair b; the results; d_ba_state [prob][6 * max_matches] holds the point state of handles above
+    // the kernel's LDS cut only
+    uint8_t *d_ba_views = nullptr;
+    double *d_ba_obs = nullptr, *d_ba_points = nullptr, *d_ba_pose0 = nullptr, *d_ba_focal = nullptr, *d_ba_state = nullptr;
+    double *d_ba_Rin = nullptr, *d_ba_tin = nullptr;
+    int *d_ba_n = nullptr, *d_ba_pre = nullptr, *d_ba_counts = nullptr, *d_ba_info = nullptr;
+    double *d_ba_Ra = nullptr, *d_ba_ta = nullptr, *d_ba_Rb = nullptr, *d_ba_tb = nullptr, *d_ba_rms = nullptr;
     // the kernels of geom_kernels.hip whose dynamic-LDS limit a launch of this handle has raised (raise_lds_limit): the
     // attribute is per device, so the record is per handle
     std::vector<const void *> lds_raised;
@@ -522,6 +533,9 @@ void rpe_launch_refine(rpe_handle *h, const RpeRun &r, int max_iters, bool from_
 int rpe_launch_scale_links(rpe_handle *h, int L, int min_shared);
 int rpe_launch_link_poses(rpe_handle *h, const RpeRun &r, int L, int iters, double threshold_px, int min_shared, int refine_iters);
 bool rpe_link_poses_in_lds(const rpe_handle *h);
+int rpe_launch_bundle_gather(rpe_handle *h, const RpeRun &r, int L, double threshold_px);
+void rpe_launch_bundle(rpe_handle *h, int n, int min_shared, int max_iters, bool links);
+bool rpe_bundles_in_lds(const rpe_handle *h);
 void rpe_launch_normalise(rpe_handle *h, const RpeRun &r);
 int rpe_launch_homography(rpe_handle *h, const RpeRun &r, int iters, double threshold_px, bool from_batch);
 void rpe_launch_undistort(rpe_handle *h, const float2 *d_pts, int n, const rpe_camera *d_cam, double2 *d_out);

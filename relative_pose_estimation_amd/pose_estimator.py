@@ -372,7 +372,21 @@ class PoseEstimator:
             raise ValueError(f"links: expected an integer array of shape [L, 3] (pair_a, pair_b, side), got {a.dtype} {a.shape}")
         return self._last_engine.link_poses(a[:, 0], a[:, 1], a[:, 2], iters, threshold_px, min_shared, refine_iters)
 
-    def estimate_trajectory(self, frames, min_shared=8, register=False):
+    def last_link_bundles(self, links, threshold_px=None, min_shared=8, max_iters=10):
+        """Bundle adjustment of the three views of every link over the last estimate_sequence / estimate_pairs /
+        FrameStore.estimate call (not in the reference; _capi.Engine.link_bundles): the link poses first
+        (last_link_poses with its defaults and this min_shared), then both pairs' poses and the points they share refined
+        together.  A link whose link pose is not LINKPOSE_OK comes back BUNDLE_SKIPPED.  links as in last_scale_links.
+        Returns (R_a[L, 3, 3], t_a[L, 3], R_b[L, 3, 3], t_b[L, 3], points[L, mm, 3], views[L, mm], counts[L, 2], info[L, 4],
+        rms[L, 2])."""
+        a = np.asarray(links)
+        if a.ndim != 2 or a.shape[1] != 3 or a.dtype.kind not in "iu":
+            raise ValueError(f"links: expected an integer array of shape [L, 3] (pair_a, pair_b, side), got {a.dtype} {a.shape}")
+        eng = self._last_engine
+        R0, t0 = eng.link_poses(a[:, 0], a[:, 1], a[:, 2], min_shared=min_shared)[:2]
+        return eng.link_bundles(a[:, 0], a[:, 1], a[:, 2], R0, t0, threshold_px, min_shared, max_iters)
+
+    def estimate_trajectory(self, frames, min_shared=8, register=False, bundle=False):
         """estimate_sequence plus what relates its poses (not in the reference): the scale link of every two consecutive
         pairs and the chained trajectory (geometry.chain_trajectory).  Returns a dict: 'R', 't', 'inliers', 'status' of
         the F - 1 pairs; 'ratio_stats' [F-2, 3], 'n_shared' [F-2], 'link_code' [F-2] of the links; 'R_abs' [F, 3, 3],
@@ -381,7 +395,12 @@ class PoseEstimator:
         register=True adds the link pose of every link (last_link_poses with its defaults and this min_shared): 'R_link'
         [F-2, 3, 3], 't_link' [F-2, 3], 'link_pose_code' [F-2], 'link_pose_counts' [F-2, 2], and 'R_abs_reg' [F, 3, 3],
         'centers_reg' [F, 3]: chain_trajectory again with pair i + 1 taken from link i where its code is LINKPOSE_OK
-        (R_link, t_link / |t_link|, ratio |t_link|, status 0) and from the pair's own pose and scale link elsewhere."""
+        (R_link, t_link / |t_link|, ratio |t_link|, status 0) and from the pair's own pose and scale link elsewhere.
+        bundle=True implies register and adds the link bundle of every link fed with those link poses
+        (_capi.Engine.link_bundles with its defaults and this min_shared): 'R_bundle' [F-2, 3, 3], 't_bundle' [F-2, 3]
+        (pair i + 1's pose on pair i's scale), 'bundle_code' [F-2], 'bundle_counts' [F-2, 2], and 'R_abs_ba' [F, 3, 3],
+        'centers_ba' [F, 3]: the registered chain with the bundle's pose where its code is BUNDLE_OK, the link pose
+        elsewhere."""
         if self._camera is not None:
             raise ValueError("estimate_trajectory: the camera path has no stream form; use estimate_pairs and last_scale_links")
         R, t, inl, st = self.estimate_sequence(frames)
@@ -391,12 +410,20 @@ class PoseEstimator:
         R_abs, T_abs, centers, baseline, segment = geometry.chain_trajectory(R, t, st, stats[:, 1], code)
         out = {'R': R, 't': t, 'inliers': inl, 'status': st, 'ratio_stats': stats, 'n_shared': n_shared, 'link_code': code,
                'R_abs': R_abs, 'T_abs': T_abs, 'centers': centers, 'baseline': baseline, 'segment': segment}
-        if register:
+        if register or bundle:
             Rl, tl, _, counts, info, _ = self._last_engine.link_poses(i, i + 1, np.ones(P - 1, np.int32), min_shared=min_shared)
             Rr, tr, sr, ratio, cr = geometry.registered_chain_inputs(R, t, st, stats[:, 1], code, Rl, tl, info[:, 0])
             reg = geometry.chain_trajectory(Rr, tr, sr, ratio, cr)
             out.update({'R_link': Rl, 't_link': tl, 'link_pose_code': info[:, 0], 'link_pose_counts': counts,
                         'R_abs_reg': reg[0], 'centers_reg': reg[2]})
+        if bundle:
+            one = np.ones(P - 1, np.int32)
+            ba = self._last_engine.link_bundles(i, i + 1, one, Rl, tl, min_shared=min_shared)
+            ok = ba[7][:, 0] == 0
+            Rb = np.where(ok[:, None, None], ba[2], Rl); tb = np.where(ok[:, None], ba[3], tl)
+            chain = geometry.chain_trajectory(*geometry.registered_chain_inputs(R, t, st, stats[:, 1], code, Rb, tb, info[:, 0]))
+            out.update({'R_bundle': ba[2], 't_bundle': ba[3], 'bundle_code': ba[7][:, 0], 'bundle_counts': ba[6],
+                        'R_abs_ba': chain[0], 'centers_ba': chain[2]})
         return out
 
     def estimate_sequence(self, frames):

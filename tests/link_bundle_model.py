@@ -1,0 +1,311 @@
+"""float64 model of rpe_link_bundles / rpe_bundle_three_view, written from the rule in include/rpe_amd.h ("link bundles"):
+the point set of a link from plain dicts (the usable matches of pair a, the lowest match of pair b on the same key, the
+Score test under the input pose of C), the Jacobians of the three views, the Levenberg-Marquardt loop of
+rpe_refine_poses and the Schur elimination of the 3 x 3 point blocks.  NumPy over the points, the sums over points through
+one function (np.sum, or np.sum of the flipped array with order="reversed"), so the model differs from the library by the
+order of its sums and of a few products -- what reduction_margin() measures on the model itself.  Independent of the
+kernel's table, compaction, LDS state and register layout.  Used by test_link_bundle_cpu.py and test_gpu_link_bundle.py."""
+import math
+
+import numpy as np
+
+from tests import link_pose_model as lp
+from tests import refine_model as rf
+from tests import scale_model as sc
+
+BUNDLE_OK, BUNDLE_PAIR_FAILED, BUNDLE_TOO_FEW, BUNDLE_SKIPPED, BUNDLE_REJECTED = 0, 1, 2, 3, 4
+LAMBDA0, REL_TOL, STEP_TOL = lp.LAMBDA0, lp.REL_TOL, lp.STEP_TOL
+NCAM = 11
+
+
+# ---------------------------------------------------------------- one point's rows
+def rows(P, X):
+    """the residuals and Jacobians of every point at poses P = (RA, tA, RC, tC) and points X: e (n, 6) in pixels (rows S x,
+    S y, A x, A y, C x, C y; the C rows zero without that observation), JX (n, 6, 3) by the point, JC (n, 6, 11) by the
+    camera parameters (wA[3], bA[2], wC[3], dC[3])"""
+    RA, tA, RC, tC = P["RA"], P["tA"], P["RC"], P["tC"]
+    q, hc, fa, fc = P["obs"], P["hc"], P["fa"], P["fc"]
+    n = len(X)
+    e = np.zeros((n, 6)); JX = np.zeros((n, 6, 3)); JC = np.zeros((n, 6, NCAM))
+    with np.errstate(all="ignore"):
+        u = X[:, :2] / X[:, 2:3]; s = fa / X[:, 2]
+        e[:, 0:2] = fa * (u - q[:, 0:2])
+        JX[:, 0, 0] = s; JX[:, 0, 2] = -s * u[:, 0]; JX[:, 1, 1] = s; JX[:, 1, 2] = -s * u[:, 1]
+        b1, b2 = rf.tangent_basis(tA)
+        r, J = lp.residuals(RA, tA, X, q[:, 2:4], fa, True)
+        e[:, 2:4] = r
+        JC[:, 2:4, 0:3] = J[:, :, 0:3]
+        JC[:, 2:4, 3] = (J[:, :, 3] * b1[0] + J[:, :, 4] * b1[1]) + J[:, :, 5] * b1[2]
+        JC[:, 2:4, 4] = (J[:, :, 3] * b2[0] + J[:, :, 4] * b2[1]) + J[:, :, 5] * b2[2]
+        for k in range(3):
+            JX[:, 2:4, k] = (J[:, :, 3] * RA[0, k] + J[:, :, 4] * RA[1, k]) + J[:, :, 5] * RA[2, k]
+        r, J = lp.residuals(RC, tC, X, q[:, 4:6], fc, True)
+        m = hc.astype(bool)
+        e[m, 4:6] = r[m]
+        JC[m, 4:6, 5:11] = J[m]
+        for k in range(3):
+            JX[m, 4:6, k] = ((J[:, :, 3] * RC[0, k] + J[:, :, 4] * RC[1, k]) + J[:, :, 5] * RC[2, k])[m]
+    return e, JX, JC
+
+
+def point_costs(e):
+    return ((e[:, 0] * e[:, 0] + e[:, 1] * e[:, 1]) + (e[:, 2] * e[:, 2] + e[:, 3] * e[:, 3])) + (e[:, 4] * e[:, 4] + e[:, 5] * e[:, 5])
+
+
+def residuals_only(P, poses, X):
+    Q = dict(P); Q.update(poses)
+    RA, tA, RC, tC = Q["RA"], Q["tA"], Q["RC"], Q["tC"]
+    q, hc = Q["obs"], Q["hc"].astype(bool)
+    e = np.zeros((len(X), 6))
+    with np.errstate(all="ignore"):
+        e[:, 0:2] = Q["fa"] * (X[:, :2] / X[:, 2:3] - q[:, 0:2])
+        e[:, 2:4] = lp.residuals(RA, tA, X, q[:, 2:4], Q["fa"])
+        e[hc, 4:6] = lp.residuals(RC, tC, X, q[:, 4:6], Q["fc"])[hc]
+    return e
+
+
+# ---------------------------------------------------------------- the Schur step
+def blocks(e, JX, JC, lam):
+    """per point Vi (n, 3, 3) = (Jp'Jp + lam diag)^-1 by the adjugate, ok (n,), g_p (n, 3), W (n, 11, 3)"""
+    V = np.zeros((len(e), 3, 3)); gp = np.zeros((len(e), 3))
+    for r in range(6):                                        # rows added in order
+        V += JX[:, r, :, None] * JX[:, r, None, :]
+        gp += JX[:, r, :] * e[:, r, None]
+    for i in range(3):
+        V[:, i, i] = V[:, i, i] + lam * V[:, i, i]
+    v00, v01, v02, v11, v12, v22 = V[:, 0, 0], V[:, 0, 1], V[:, 0, 2], V[:, 1, 1], V[:, 1, 2], V[:, 2, 2]
+    c00 = v11 * v22 - v12 * v12; c01 = v02 * v12 - v01 * v22; c02 = v01 * v12 - v02 * v11
+    c11 = v00 * v22 - v02 * v02; c12 = v01 * v02 - v00 * v12; c22 = v00 * v11 - v01 * v01
+    det = (v00 * c00 + v01 * c01) + v02 * c02
+    with np.errstate(all="ignore"):
+        Vi = np.stack([np.stack([c00, c01, c02], 1), np.stack([c01, c11, c12], 1), np.stack([c02, c12, c22], 1)], 1) / det[:, None, None]
+    ok = (det > 0.0) & (np.abs(det) <= lp.DBL_MAX)
+    W = JC[:, 2, :, None] * JX[:, 2, None, :] + JC[:, 3, :, None] * JX[:, 3, None, :]
+    W[:, 5:] = (JC[:, 4, :, None] * JX[:, 4, None, :] + JC[:, 5, :, None] * JX[:, 5, None, :])[:, 5:]
+    return Vi, ok, gp, W
+
+
+def normal_sums(e, JC, S):
+    """U (11, 11), g_c (11,), cost: the sums linearise() takes"""
+    U = np.zeros((NCAM, NCAM))
+    iu = np.triu_indices(NCAM)
+    U[iu] = S(JC[:, 2, iu[0]] * JC[:, 2, iu[1]] + JC[:, 3, iu[0]] * JC[:, 3, iu[1]]) + S(JC[:, 4, iu[0]] * JC[:, 4, iu[1]] + JC[:, 5, iu[0]] * JC[:, 5, iu[1]])
+    U[:5, 5:] = 0.0
+    U = np.triu(U) + np.triu(U, 1).T
+    gc = np.zeros(NCAM)
+    gc[:5] = S(JC[:, 2, :5] * e[:, 2, None] + JC[:, 3, :5] * e[:, 3, None])
+    gc[5:] = S(JC[:, 4, 5:] * e[:, 4, None] + JC[:, 5, 5:] * e[:, 5, None])
+    return U, gc, float(S(point_costs(e)))
+
+
+def schur_step(e, JX, JC, U, gc, lam, S):
+    """(d_c (11,), d_p (n, 3)) of (J'J + lam diag J'J) step = -J'r by eliminating the points, or None (a singular V, or a
+    reduced matrix that is not positive definite)"""
+    Vi, ok, gp, W = blocks(e, JX, JC, lam)
+    if not ok.all():
+        return None
+    Y = (W[:, :, 0, None] * Vi[:, None, 0, :] + W[:, :, 1, None] * Vi[:, None, 1, :]) + W[:, :, 2, None] * Vi[:, None, 2, :]   # W V^-1
+    SW = S((Y[:, :, None, 0] * W[:, None, :, 0] + Y[:, :, None, 1] * W[:, None, :, 1]) + Y[:, :, None, 2] * W[:, None, :, 2])
+    v = S((Y[:, :, 0] * gp[:, None, 0] + Y[:, :, 1] * gp[:, None, 1]) + Y[:, :, 2] * gp[:, None, 2])
+    H = U - SW
+    for k in range(NCAM):
+        H[k, k] = (U[k, k] + lam * U[k, k]) - SW[k, k]
+    H = np.triu(H) + np.triu(H, 1).T
+    d = lp.solve(H, gc - v, 0.0)
+    if d is None:
+        return None
+    u = gp.copy()
+    for k in range(NCAM):                                     # ascending parameter order
+        u += W[:, k, :] * d[k]
+    dp = -((Vi[:, :, 0] * u[:, None, 0] + Vi[:, :, 1] * u[:, None, 1]) + Vi[:, :, 2] * u[:, None, 2])
+    return d, dp
+
+
+def dense_step(e, JX, JC, lam):
+    """the same step from the dense (11 + 3n)-parameter system with numpy.linalg.solve, and its condition number"""
+    n = len(e)
+    J = np.zeros((6 * n, NCAM + 3 * n)); r = e.reshape(-1)
+    for j in range(n):
+        J[6 * j:6 * j + 6, :NCAM] = JC[j]
+        J[6 * j:6 * j + 6, NCAM + 3 * j:NCAM + 3 * j + 3] = JX[j]
+    H = J.T @ J
+    H[np.diag_indices_from(H)] *= 1.0 + lam
+    d = np.linalg.solve(H, -(J.T @ r))
+    return d[:NCAM], d[NCAM:].reshape(n, 3), float(np.linalg.cond(H))
+
+
+def apply_step(P, X, d, dp):
+    b1, b2 = rf.tangent_basis(P["tA"])
+    tA = (P["tA"] + d[3] * b1) + d[4] * b2
+    tA = tA / math.sqrt((tA[0] * tA[0] + tA[1] * tA[1]) + tA[2] * tA[2])
+    return dict(RA=lp.rotate(d[0:3], P["RA"]), tA=tA, RC=lp.rotate(d[5:8], P["RC"]), tC=P["tC"] + d[8:11]), X + dp
+
+
+# ---------------------------------------------------------------- the problem (stage form)
+def problem(obs, hc, X0, RA, tA, RC, tC, fa, fc):
+    f = lambda a, s: np.array(a, np.float64).reshape(s)
+    return dict(obs=f(obs, (-1, 6)), hc=np.asarray(hc).astype(bool).reshape(-1), X0=f(X0, (-1, 3)), RA=f(RA, (3, 3)), tA=f(tA, 3),
+                RC=f(RC, (3, 3)), tC=f(tC, 3), fa=float(fa), fc=float(fc))
+
+
+def bundle(P, max_iters=10, min_shared=1, order="forward"):
+    """one problem as rpe_bundle_three_view returns it (solved form, S's frame): dict code, RA, tA, RC, tC, X (n, 3), counts,
+    info, rms, decisions"""
+    S = lp.SUMS[order]
+    n, n3 = len(P["X0"]), int(P["hc"].sum())
+    res = dict(code=BUNDLE_OK, RA=np.zeros((3, 3)), tA=np.zeros(3), RC=np.zeros((3, 3)), tC=np.zeros(3), X=np.zeros((n, 3)),
+               counts=(n, n3), info=(BUNDLE_TOO_FEW, 0, 0, 0), rms=(0.0, 0.0), decisions=[], taken=False)
+    if n3 < max(min_shared, 6):
+        res["code"] = BUNDLE_TOO_FEW
+        return res
+    cur = dict(P); X = P["X0"].copy()
+    e, JX, JC = rows(cur, X)
+    U, gc, cost0 = normal_sums(e, JC, S)
+    cost = cost0
+    iters = acc = 0
+    dec = []
+    if np.isfinite(cost0):
+        lam = LAMBDA0
+        need_lin = False
+        for _ in range(max_iters):
+            if need_lin:
+                e, JX, JC = rows(cur, X)
+                U, gc, _ = normal_sums(e, JC, S)
+                need_lin = False
+            iters += 1
+            st = schur_step(e, JX, JC, U, gc, lam, S)
+            ok = st is not None
+            if ok:
+                d, dp = st
+                poses, Xn = apply_step(cur, X, d, dp)
+                c1 = float(S(point_costs(residuals_only(cur, poses, Xn))))
+                ok = bool(np.isfinite(c1) and c1 < cost)
+            dec.append(ok)
+            if not ok:
+                lam = lam * 10.0
+                continue
+            drop, prev = cost - c1, cost
+            cur.update(poses); X = Xn; cost = c1
+            lam = lam / 10.0
+            acc += 1
+            need_lin = True
+            dn = d[0] * d[0]
+            for k in range(1, NCAM):
+                dn = dn + d[k] * d[k]
+            if drop <= REL_TOL * prev or math.sqrt(dn) <= STEP_TOL:
+                break
+    take = acc > 0
+    if take:
+        fin = all(np.isfinite(cur[k]).all() for k in ("RA", "tA", "RC", "tC")) and np.isfinite(X).all()
+        zA = ((cur["RA"][2, 0] * X[:, 0] + cur["RA"][2, 1] * X[:, 1]) + cur["RA"][2, 2] * X[:, 2]) + cur["tA"][2]
+        zC = ((cur["RC"][2, 0] * X[:, 0] + cur["RC"][2, 1] * X[:, 1]) + cur["RC"][2, 2] * X[:, 2]) + cur["tC"][2]
+        take = bool(fin and (X[:, 2] > 0).all() and (zA > 0).all() and (zC[P["hc"]] > 0).all())
+    nobs = 2 * n + n3
+    before = float(np.sqrt(cost0 / nobs))
+    src = cur if take else P
+    res.update(code=BUNDLE_OK if take else BUNDLE_REJECTED, RA=src["RA"], tA=src["tA"], RC=src["RC"], tC=src["tC"],
+               X=X if take else P["X0"].copy(), info=(BUNDLE_OK if take else BUNDLE_REJECTED, iters, acc, 0),
+               rms=(before, float(np.sqrt(cost / nobs)) if take else before), decisions=dec, taken=take)
+    return res
+
+
+# ---------------------------------------------------------------- one link (run form)
+def _invert(R, t):
+    return R.T.copy(), np.array([-((R[0, k] * t[0] + R[1, k] * t[1]) + R[2, k] * t[2]) for k in range(3)])
+
+
+def link_problem(run, x1, x2, focal, link, R0, t0, threshold_px):
+    """(code, problem, idx): the point set of a link; idx = pair a's match index of every point.  code: BUNDLE_PAIR_FAILED
+    (no problem), BUNDLE_SKIPPED (zero R0: the points without any C observation) or BUNDLE_OK"""
+    a, b, side = (int(v) for v in link)
+    if run.status[a] != 0:
+        return BUNDLE_PAIR_FAILED, None, None
+    a2, b2 = bool(side & 1), bool(side & 2)
+    R0 = np.asarray(R0, np.float64).reshape(3, 3); t0 = np.asarray(t0, np.float64).reshape(3)
+    ka = sc.usable_keys(run, a, a2)
+    kidx = run.tidx[b] if b2 else run.qidx[b]
+    first = {}
+    for i in range(min(int(run.n_matches[b]), kidx.shape[0])):
+        first.setdefault(int(kidx[i]), i)
+    RC, tC = _invert(R0, t0) if b2 else (R0, t0)
+    RA, tA = _invert(run.R[a], run.t[a]) if a2 else (run.R[a], run.t[a])
+    oS, oA = (x2[a], x1[a]) if a2 else (x1[a], x2[a])
+    oC = x1[b] if b2 else x2[b]
+    thr = threshold_px / float(focal[b]); thr2 = thr * thr
+    idx = sorted(ka.values())
+    key_of = {i: k for k, i in ka.items()}
+    obs = np.zeros((len(idx), 6)); X0 = np.zeros((len(idx), 3)); hc = np.zeros(len(idx), bool)
+    for j, i in enumerate(idx):
+        X0[j] = lp.map_point(run, a, i, a2)
+        obs[j, 0:2] = oS[i]; obs[j, 2:4] = oA[i]
+        m = first.get(key_of[i])
+        if m is not None:
+            obs[j, 4:6] = oC[m]
+            hc[j] = bool(lp.inlier_mask(RC, tC, X0[j:j + 1], obs[j:j + 1, 4:6], thr2)[0])
+    code = BUNDLE_SKIPPED if not R0.any() else BUNDLE_OK
+    return code, problem(obs, hc, X0, RA, tA, RC, tC, focal[a], focal[b]), np.array(idx, np.int64)
+
+
+def link_bundle(run, x1, x2, focal, link, R0, t0, threshold_px=1.0, min_shared=8, max_iters=10, order="forward"):
+    """one link as rpe_link_bundles returns it: dict code, R_a, t_a, R_b, t_b, points (mm, 3), views u8[mm], counts, info, rms,
+    decisions"""
+    a, b, side = (int(v) for v in link)
+    mm = run.qidx.shape[1]
+    out = dict(code=BUNDLE_OK, R_a=np.zeros((3, 3)), t_a=np.zeros(3), R_b=np.zeros((3, 3)), t_b=np.zeros(3), points=np.zeros((mm, 3)),
+               views=np.zeros(mm, np.uint8), counts=(0, 0), info=(0, 0, 0, 0), rms=(0.0, 0.0), decisions=[])
+    code, P, idx = link_problem(run, x1, x2, focal, link, R0, t0, threshold_px)
+    if code == BUNDLE_PAIR_FAILED:
+        out.update(code=code, info=(code, 0, 0, 0))
+        return out
+    if code == BUNDLE_SKIPPED:
+        out.update(code=code, counts=(len(idx), 0), info=(code, 0, 0, 0))
+        return out
+    r = bundle(P, max_iters, min_shared, order)
+    out.update(code=r["code"], counts=r["counts"], info=r["info"], rms=r["rms"], decisions=r["decisions"])
+    if r["code"] == BUNDLE_TOO_FEW:
+        return out
+    a2, b2 = bool(side & 1), bool(side & 2)
+    out["views"][idx] = np.where(P["hc"], 3, 1)
+    if r["code"] == BUNDLE_OK:
+        RA, tA, RC, tC, X = r["RA"], r["tA"], r["RC"], r["tC"], r["X"]
+        out["R_a"], out["t_a"] = _invert(RA, tA) if a2 else (RA, tA)
+        out["R_b"], out["t_b"] = _invert(RC, tC) if b2 else (RC, tC)
+        if a2:
+            X = np.stack([((RA[k, 0] * X[:, 0] + RA[k, 1] * X[:, 1]) + RA[k, 2] * X[:, 2]) + tA[k] for k in range(3)], 1)
+        out["points"][idx] = X
+    else:
+        out.update(R_a=run.R[a].copy(), t_a=run.t[a].copy(), R_b=np.asarray(R0, np.float64).reshape(3, 3).copy(),
+                   t_b=np.asarray(t0, np.float64).reshape(3).copy())
+        out["points"][idx] = run.points[a, idx]
+    return out
+
+
+def reduction_margin(results_fwd, results_rev):
+    """the model against itself with the sums reversed, over lists of link_bundle() / bundle() results: (tied indices, largest
+    differences [rms_after px, rotation degrees (either pose), translation (either pose), point coordinate, rms_before px]).
+    A result is tied when the two runs disagree on a decision or on an integer output."""
+    ties, d = [], np.zeros(5)
+    for i, (f, r) in enumerate(zip(results_fwd, results_rev)):
+        if f["decisions"] != r["decisions"] or f["info"] != r["info"] or f["counts"] != r["counts"]:
+            ties.append(i)
+            continue
+        if f["code"] != BUNDLE_OK:
+            continue
+        ka, kb, kp = ("RA", "RC", "X") if "RA" in f else ("R_a", "R_b", "points")
+        ta, tb = ("tA", "tC") if "RA" in f else ("t_a", "t_b")
+        d = np.maximum(d, [abs(f["rms"][1] - r["rms"][1]), max(lp.rot_angle_deg(f[ka], r[ka]), lp.rot_angle_deg(f[kb], r[kb])),
+                           max(np.abs(f[ta] - r[ta]).max(), np.abs(f[tb] - r[tb]).max()), np.abs(f[kp] - r[kp]).max(),
+                           abs(f["rms"][0] - r["rms"][0])])
+    return ties, d
+
+
+# ---------------------------------------------------------------- accuracy bands
+# Twice the model's worst over the noisy hand runs of link_bundle_cases (every count of link_pose_cases.COUNTS from 6 up, all
+# four sides, NOISE_PX 0.3 on every view, OUTLIER_FRAC 0.25 on C), as test_link_bundle_cpu.py::test_accuracy_table prints
+# them; the measured values stand beside the constants.  See DESIGN section 8 for the whole table.
+BUNDLE_ROT_A_WORST_DEG = 0.4046      # measured 0.40459 (input state 0.5700: link_bundle_cases.POSE_NOISE_DEG)
+BUNDLE_ROT_B_WORST_DEG = 0.6518      # measured 0.65178 (link-pose-polished 1.0349)
+BUNDLE_SCALE_WORST = 0.0999          # measured 0.09990 (link-pose-polished 0.1396)
+BUNDLE_ROT_A_BAND_DEG = 2 * BUNDLE_ROT_A_WORST_DEG
+BUNDLE_ROT_B_BAND_DEG = 2 * BUNDLE_ROT_B_WORST_DEG
+BUNDLE_SCALE_BAND = 2 * BUNDLE_SCALE_WORST

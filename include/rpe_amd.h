@@ -667,6 +667,69 @@ int rpe_bundle_three_view(rpe_handle *h, int B, const int32_t *n, const double *
                           double *R_a, double *t_a, double *R_c, double *t_c, double *points, uint8_t *views,
                           int32_t *counts, int32_t *info, double *rms);
 
+/* ------------------------------------------------------ multi-view tracks */
+/* Feature tracks of a run (NOT in the reference, which never relates more than two frames): which keypoint of which frame
+ * is the same scene point, over all frames of the last stream or pair list, as the connected components of the match
+ * graph, with the standard consistency filter (a track holds at most one keypoint per frame).  Integers only.
+ * The rule.  KC = rpe_keypoint_capacity(h), P = the pairs of the run, mm = max_matches.
+ *  Frames: in a pair list a frame is its slot number and n_frames = rpe_frames_capacity(h); in a stream pair p joins
+ *   frames p and p + 1 and n_frames = P + 1.  A batch of two or more pairs is refused: its pairs share no frame.  A batch
+ *   of ONE pair cannot be told from a stream of two frames and is served as one: frame 0 is its image 1, frame 1 its
+ *   image 2 (rpe_scale_links draws the same line).
+ *  Node: (frame f, keypoint index k), 0 <= k < KC; its id is f * KC + k.
+ *  Edge: match i of pair p is an edge when (use_pair == NULL or use_pair[p] != 0) and i < n_matches[p] and edge_rule
+ *   admits it:
+ *    RPE_TRACK_EDGES_USABLE: the usable match of rpe_scale_links: status[p] == RPE_PAIR_OK and both ransac_mask[i] and
+ *     pose_mask[i] of rpe_fetch_structure set.
+ *    RPE_TRACK_EDGES_RANSAC: ransac_mask[i] of rpe_fetch_structure set.  That mask is findEssentialMat's inlier set of
+ *     the one essential matrix of a pair whose status is RPE_PAIR_OK and zero for every other status:
+ *     RPE_PAIR_NO_DESCRIPTORS and RPE_PAIR_INSUFFICIENT_MATCHES run no RANSAC, RPE_PAIR_NO_ESSENTIAL has no model and
+ *     RPE_PAIR_AMBIGUOUS_ESSENTIAL (exactly five matches, several models) has no single one.  So RPE_PAIR_OK is the only
+ *     status that leaves it valid.  The rule for rotation-only pairs, which are RPE_PAIR_OK and whose cheirality mask keeps
+ *     next to nothing.
+ *    RPE_TRACK_EDGES_ALL: every match i < n_matches[p], whatever the pair's status.
+ *   The edge joins node (frame of image 1, qidx[i]) and node (frame of image 2, tidx[i]); its id is p * mm + i.
+ *  Component: a connected component of the nodes that have at least one edge (a self pair (a, a) with qidx == tidx gives a
+ *   component of one node).  It conflicts when it holds two nodes of one frame: a wrong match anywhere on a cycle, two
+ *   matches of a RPE_MATCH_RATIO pair that name one train keypoint, a self pair with qidx != tidx.  A conflicting
+ *   component is dropped and counted, whatever its length.  A conflict-free component with fewer than min_len nodes
+ *   (min_len >= 2) is dropped and counted as short.  Every other component is a track.
+ *  Order: tracks by ascending smallest node id; a track's observations by ascending node id (frame first, then keypoint).
+ *  Outputs (host, any may be NULL; the caller sizes them by the bound track_start[P*mm + 1], obs_*[2*P*mm],
+ *   match_track[P*mm]; only the used prefix of track_start and obs_* is written, match_track is written whole):
+ *   counts[6] = {n_tracks, n_obs, n_edges, dropped_conflict, dropped_short, frames with at least one observation};
+ *   track_start[n_tracks + 1]: CSR offsets into the observation arrays;  obs_frame[n_obs], obs_kp[n_obs]: frame and
+ *   keypoint index of each observation;  obs_xy[2 * n_obs]: the keypoint's f32 pixel coordinates, the bits
+ *   rpe_fetch_matched_points returns for the edge with the lowest id among those that name the node (image 1's point when
+ *   that edge names the node on both sides);  match_track[P*mm]: the track index of the edge's component, -1 for a
+ *   non-edge, an edge of a dropped component and past n_matches -- it ties a track to rpe_fetch_structure's points and masks.
+ * The run's own results are untouched: every fetch of the run, rpe_refine_poses, rpe_scale_links, rpe_link_poses,
+ * rpe_link_bundles, rpe_pair_homographies and rpe_guided_matches(_l2) return the same bits afterwards.  Bit-deterministic:
+ * integer atomics only (min, add, compare-and-swap towards the smaller id), and no result depends on their order.
+ * rpe_build_tracks: over all pairs of the last stream / pair list (use_pair[P] switches pairs off); P is
+ * rpe_last_run_pairs(h), the count every output bound above is taken from.  Validity rules of
+ * rpe_scale_links (refused after a chunked host batch, a stage call, a put, once the store was resized under a pair list,
+ * and after a batch of two or more pairs); the structure kernels are launched when edge_rule reads masks that are not current.
+ * RPE_ERR_INVALID as well: edge_rule outside 0 .. 2, min_len < 2.
+ * rpe_tracks_from_matches: the stage form over the caller's own matches: P pairs (0 .. max_batch; RPE_ERR_CAPACITY above),
+ * pair p joins frames frame1[p] and frame2[p] of n_frames and has m[p] matches; qidx / tidx / edge at p * mm (edge == NULL:
+ * every match is an edge), pts1 / pts2 at (p * mm) * 2 (both NULL: obs_xy is zero).  It uses buffers of its own, created on
+ * first use: the last run stays fetchable.  RPE_ERR_INVALID: n_frames < 1 or n_frames * KC >= 2^31, a frame index outside
+ * 0 .. n_frames - 1, m[p] outside 0 .. mm, an index outside 0 .. KC - 1 among the first m[p], exactly one of pts1 / pts2
+ * NULL, min_len < 2.  P == 0 returns all-zero counts.
+ * All checks are host-side; nothing is launched and the handle stays usable after a refusal. */
+enum { RPE_TRACK_EDGES_USABLE = 0, RPE_TRACK_EDGES_RANSAC = 1, RPE_TRACK_EDGES_ALL = 2 };
+/* pairs of the last batch / stream / pair list of the handle (a chunked host batch: of the whole batch); 0 before any run,
+ * after rpe_frames_put* and for h == NULL.  What rpe_build_tracks sizes its outputs by. */
+int rpe_last_run_pairs(const rpe_handle *h);
+int rpe_build_tracks(rpe_handle *h, const uint8_t *use_pair, int edge_rule, int min_len,
+                     int32_t *counts, int32_t *track_start, int32_t *obs_frame, int32_t *obs_kp, float *obs_xy,
+                     int32_t *match_track);
+int rpe_tracks_from_matches(rpe_handle *h, int P, int n_frames, const int32_t *frame1, const int32_t *frame2, const int32_t *m,
+                            const int32_t *qidx, const int32_t *tidx, const uint8_t *edge, const float *pts1, const float *pts2,
+                            int min_len, int32_t *counts, int32_t *track_start, int32_t *obs_frame, int32_t *obs_kp,
+                            float *obs_xy, int32_t *match_track);
+
 /* ---------------------------------------------------------- stage entry */
 /* replaces extractor.detectAndCompute(image, None) (pose_estimator.py:108)
  * for n_images images (n_images <= 2*max_batch).  kps[n_images*cap],

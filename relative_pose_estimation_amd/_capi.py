@@ -31,6 +31,8 @@ LINK_OK, LINK_PAIR_FAILED, LINK_TOO_FEW = 0, 1, 2      # code[] of scale_links (
 HOMOGRAPHY_OK, HOMOGRAPHY_SKIPPED, HOMOGRAPHY_NONE = 0, 1, 2   # info[:, 0] of pair_homographies (include/rpe_amd.h RPE_HOMOGRAPHY_*)
 LINKPOSE_OK, LINKPOSE_PAIR_FAILED, LINKPOSE_TOO_FEW, LINKPOSE_NONE = 0, 1, 2, 3   # info[:, 0] of link_poses (RPE_LINKPOSE_*)
 BUNDLE_OK, BUNDLE_PAIR_FAILED, BUNDLE_TOO_FEW, BUNDLE_SKIPPED, BUNDLE_REJECTED = 0, 1, 2, 3, 4   # info[:, 0] of link_bundles (RPE_BUNDLE_*)
+TRACK_EDGES_USABLE, TRACK_EDGES_RANSAC, TRACK_EDGES_ALL = 0, 1, 2   # edge_rule of build_tracks (RPE_TRACK_EDGES_*)
+TRACK_COUNTS = ("n_tracks", "n_obs", "n_edges", "dropped_conflict", "dropped_short", "n_frames_seen")   # counts[6] of the track calls
 UNDISTORT_ITERS = 5               # RPE_UNDISTORT_ITERS: fixed-point rounds of the camera path's undistortion
 
 # The binding, one entry per function of include/rpe_amd.h: "<return>:<one letter per parameter>".  Parameters: p pointer or
@@ -56,6 +58,7 @@ _SIGNATURES = {
     "rpe_fetch_matched_points": "i:pipp", "rpe_fetch_structure": "i:pippp", "rpe_refine_poses": "i:piippppp",
     "rpe_fetch_match_indices": "i:pipp", "rpe_scale_links": "i:pipppippp", "rpe_link_poses": "i:pipppidiipppppp",
     "rpe_link_bundles": "i:pipppppdiippppppppp", "rpe_bundle_three_view": "i:pippppppppppddippppppppp",
+    "rpe_last_run_pairs": "i:p", "rpe_build_tracks": "i:ppiipppppp", "rpe_tracks_from_matches": "i:piippppppppipppppp",
     "rpe_guided_matches": "i:pippdipppppp",
     "rpe_guided_matches_l2": "i:pippddpppppp",
     "rpe_pair_homographies": "i:piidppppp", "rpe_find_homography": "i:ppppipidppppp",
@@ -472,6 +475,62 @@ class Engine:
         self._chk(self.lib.rpe_bundle_three_view(self.h, B, _p(n), _p(os_), _p(oa), _p(oc), _p(hc), _p(x0), *map(_p, poses),
                                                  float(f_a), float(f_c), int(max_iters), *map(_p, outs)))
         return outs
+
+    # ---- multi-view tracks (rpe_build_tracks / rpe_tracks_from_matches; not in the reference)
+    def _tracks(self, P, call):
+        """call(counts, track_start, obs_frame, obs_kp, obs_xy, match_track) -> rc, over arrays sized by the bound; the
+        dict of both track calls, trimmed to the counts"""
+        n = P * self.max_matches
+        counts = np.zeros(6, np.int32); ts = np.zeros(n + 1, np.int32)
+        of = np.zeros(2 * n, np.int32); ok = np.zeros(2 * n, np.int32); xy = np.zeros((2 * n, 2), np.float32)
+        mt = np.full((P, self.max_matches), -1, np.int32)
+        self._chk(call(_p(counts), _p(ts), _p(of), _p(ok), _p(xy), _p(mt)))
+        nt, no = int(counts[0]), int(counts[1])
+        out = {'track_start': ts[:nt + 1].copy(), 'obs_frame': of[:no].copy(), 'obs_kp': ok[:no].copy(), 'obs_xy': xy[:no].copy(),
+               'match_track': mt}
+        out.update({k: int(v) for k, v in zip(TRACK_COUNTS, counts)})
+        return out
+
+    def build_tracks(self, use_pair=None, edge_rule=TRACK_EDGES_USABLE, min_len=2):
+        """Feature tracks over all pairs of the last stream / pair list (rpe_build_tracks): the connected components of the
+        match graph with at most one keypoint per frame and at least min_len of them.  A frame is its position in the
+        stream or its store slot.  edge_rule: TRACK_EDGES_USABLE (RANSAC and cheirality inliers of OK pairs),
+        TRACK_EDGES_RANSAC (RANSAC inliers: the rule for rotation-only pairs) or TRACK_EDGES_ALL (every match); use_pair
+        bool[P] switches pairs off.  Returns a dict: 'track_start' i32[n_tracks + 1] (CSR), 'obs_frame' / 'obs_kp'
+        i32[n_obs], 'obs_xy' f32[n_obs, 2] (pixels), 'match_track' i32[P, mm] (the track of each match, -1 none) and the
+        counts 'n_tracks', 'n_obs', 'n_edges', 'dropped_conflict', 'dropped_short', 'n_frames_seen'.  Tracks are ordered by
+        their first observation, observations by (frame, keypoint).  The run's own results are not modified.  A batch is
+        refused (its pairs share no frame), except a batch of ONE pair, which is the stream of its two images (frames 0, 1)."""
+        P = int(self.lib.rpe_last_run_pairs(self.h))        # the library writes its outputs by this count: sized by it
+        up = None if use_pair is None else np.ascontiguousarray(np.asarray(use_pair).astype(bool), np.uint8).reshape(-1)
+        if up is not None and up.size != P:
+            raise ValueError(f"build_tracks: use_pair must have one entry per pair of the last run ({P}), got {up.size}")
+        return self._tracks(P, lambda *o: self.lib.rpe_build_tracks(self.h, _opt(up), int(edge_rule), int(min_len), *o))
+
+    def tracks_from_matches(self, frame1, frame2, qidx, tidx, n_frames, edge=None, pts1=None, pts2=None, min_len=2):
+        """The track kernels on the caller's own matches (rpe_tracks_from_matches): pair p joins frames frame1[p] and
+        frame2[p] of n_frames and has the matches (qidx[p][i], tidx[p][i]) -- ragged per-pair lists; edge[p] bool[n_p]
+        (None: every match is an edge); pts1[p] / pts2[p] f32[n_p, 2] the matched pixels (None: 'obs_xy' is zero).
+        Returns build_tracks' dict.  The last run stays fetchable."""
+        f1, f2 = _i32(frame1), _i32(frame2)
+        P, mm = f1.size, self.max_matches
+        if not (f2.size == len(qidx) == len(tidx) == P) or any(x is not None and len(x) != P for x in (edge, pts1, pts2)):
+            raise ValueError("tracks_from_matches: frame1, frame2 and the per-pair lists must have one length")
+        m = np.array([len(x) for x in qidx], np.int32)
+        if m.max(initial=0) > mm or any(len(t) != n for t, n in zip(tidx, m)):
+            raise ValueError(f"tracks_from_matches: qidx[p] and tidx[p] must have one length of at most max_matches = {mm}")
+
+        def pad(rows, w, dt):
+            a = np.zeros((P, mm) + ((w,) if w else ()), dt)
+            for p, r in enumerate(rows):
+                a[p, :m[p]] = np.asarray(r, dt).reshape((m[p], w) if w else (m[p],))
+            return a
+        q, t = pad(qidx, 0, np.int32), pad(tidx, 0, np.int32)
+        e = None if edge is None else pad(edge, 0, np.uint8)
+        p1 = None if pts1 is None else pad(pts1, 2, np.float32)
+        p2 = None if pts2 is None else pad(pts2, 2, np.float32)
+        return self._tracks(P, lambda *o: self.lib.rpe_tracks_from_matches(
+            self.h, P, int(n_frames), _p(f1), _p(f2), _p(m), _p(q), _p(t), _opt(e), _opt(p1), _opt(p2), int(min_len), *o))
 
     # ---- guided matching (rpe_guided_matches / rpe_match_hamming_guided; not in the reference)
     def _poses(self, B, R, t):

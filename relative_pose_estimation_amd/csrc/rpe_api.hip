@@ -678,9 +678,10 @@ static int last_run_structure(rpe_handle *h, int B, bool always)
 // | rpe_fetch_structure, rpe_refine_poses                 | yes                   | yes            | yes                        | no                                    |
 // | rpe_scale_links, rpe_link_poses, rpe_link_bundles     | yes                   | yes            | no (checks its links' own) | yes, n = the run's pairs              |
 // | rpe_guided_matches(_l2), rpe_pair_homographies        | yes                   | yes            | yes                        | yes, n = B                            |
+// | rpe_build_tracks                                      | yes                   | yes            | no (runs over all pairs)   | yes, n = the run's pairs              |
 //
-// Tested in this order, so a state gives one message whatever the call.  Two tests stay with their only caller:
-// the link calls' "the pairs of a batch share no frame" and rpe_fetch_overflow's slot range.
+// Tested in this order, so a state gives one message whatever the call.  Two tests stay with their callers:
+// the link calls' and rpe_build_tracks' "the pairs of a batch share no frame" and rpe_fetch_overflow's slot range.
 enum : unsigned { NEED_UNCHUNKED = 1, NEED_PER_MATCH = 2, NEED_COUNT = 4, NEED_TABLE = 8 };
 static int last_run_gate(rpe_handle *h, const char *who, int n, unsigned needs)
 {
@@ -1201,6 +1202,152 @@ extern "C" int rpe_bundle_three_view(rpe_handle *h, int B, const int32_t *n, con
     HIPCHK(h, hipGetLastError());
     // the wait also covers the uploads: the staging vectors live until it returns
     return bundle_fetch(h, nb, R_a, t_a, R_c, t_c, points, views, counts, info, rms);
+}
+
+// ---- multi-view tracks (rpe_build_tracks / rpe_tracks_from_matches)
+// A buffer that grows: the old one leaves the handle's record and is freed (every track call ends in a wait on the stream,
+// so nothing is in flight on it)
+template <typename T>
+static int tracks_regrow(rpe_handle *h, T **p, size_t n)
+{
+    if (*p) {
+        h->dev_allocs.erase(std::remove(h->dev_allocs.begin(), h->dev_allocs.end(), (void *)*p), h->dev_allocs.end());
+        HIPCHK(h, hipFree(*p));
+        *p = nullptr;
+    }
+    return dmalloc(h, p, n);
+}
+
+// the buffers of both forms: per match slot on first use, per node and per frame grown to n_frames
+static int tracks_alloc(rpe_handle *h, int n_frames)
+{
+    const size_t MB = (size_t)h->cfg.max_batch, cap = MB * h->cfg.max_matches;
+    DM_ONCE(h, h->d_tk_eflag, cap); DM_ONCE(h, h->d_tk_edge, cap); DM_ONCE(h, h->d_tk_use, MB);
+    DM_ONCE(h, h->d_tk_mtrack, cap); DM_ONCE(h, h->d_tk_q, cap); DM_ONCE(h, h->d_tk_t, cap); DM_ONCE(h, h->d_tk_m, MB);
+    DM_ONCE(h, h->d_tk_counts, 8); DM_ONCE(h, h->d_tk_tstart, cap + 1); DM_ONCE(h, h->d_tk_oframe, 2 * cap); DM_ONCE(h, h->d_tk_okp, 2 * cap);
+    DM_ONCE(h, h->d_tk_oxy, 2 * cap); DM_ONCE(h, h->d_tk_pts1, cap); DM_ONCE(h, h->d_tk_pts2, cap); DM_ONCE(h, h->d_tk_frames, MB);
+    const int N = n_frames * h->lay.kcap;
+    if (N > h->tk_nodes) {
+        h->tk_nodes = 0;
+        if (int rc = tracks_regrow(h, &h->d_tk_node, (size_t)RPE_TRACK_NODE_WORDS * N)) return rc;
+        if (int rc = tracks_regrow(h, &h->d_tk_partial, (size_t)rpe_track_scan_blocks(N))) return rc;
+        h->tk_nodes = N;
+    }
+    if (n_frames > h->tk_frames) {
+        h->tk_frames = 0;
+        if (int rc = tracks_regrow(h, &h->d_tk_seen, (size_t)n_frames)) return rc;
+        h->tk_frames = n_frames;
+    }
+    return RPE_OK;
+}
+
+// min_len, and the node ids and edge ids of n_frames frames must fit an int.  frames_what: the refusal in the caller's terms
+static int tracks_check(rpe_handle *h, const char *who, int n_frames, int min_len, const char *frames_what)
+{
+    if (min_len < 2) return rpe_invalid(h, who, "min_len must be >= 2");
+    if (n_frames < 1 || (long long)n_frames * h->lay.kcap >= (1LL << 31)) return rpe_invalid(h, who, frames_what);
+    if ((long long)h->cfg.max_batch * h->cfg.max_matches >= (1LL << 30)) return rpe_invalid(h, who, "max_batch * max_matches must be < 2^30");
+    return RPE_OK;
+}
+
+// the frame table up, the kernels, counts first and then the used prefixes
+static int tracks_run(rpe_handle *h, RpeTrackJob job, int32_t *counts, int32_t *track_start, int32_t *obs_frame, int32_t *obs_kp,
+                      float *obs_xy, int32_t *match_track)
+{
+    const size_t P = (size_t)job.P;
+    HIPCHK(h, hipMemcpyAsync(h->d_tk_frames, h->tk_frame_tab.data(), sizeof(int2) * P, hipMemcpyHostToDevice, h->stream));
+    job.frames = h->d_tk_frames;
+    rpe_launch_tracks(h, job);
+    HIPCHK(h, hipGetLastError());
+    int32_t c[6];
+    int rc = fetch(h, {{c, h->d_tk_counts, sizeof(c)}});
+    if (rc) return rc;
+    if (counts) memcpy(counts, c, sizeof(c));
+    const size_t nt = (size_t)c[0], no = (size_t)c[1];
+    return fetch(h, {{track_start, h->d_tk_tstart, sizeof(int) * (nt + 1)}, {obs_frame, h->d_tk_oframe, sizeof(int) * no},
+                     {obs_kp, h->d_tk_okp, sizeof(int) * no}, {obs_xy, h->d_tk_oxy, sizeof(float2) * no},
+                     {match_track, h->d_tk_mtrack, sizeof(int) * P * h->cfg.max_matches}});
+}
+
+extern "C" int rpe_last_run_pairs(const rpe_handle *h) { return h ? h->last.pairs : 0; }
+
+// rpe_build_tracks: every check on the host first, the buffers, the structure kernels when the rule reads masks that are
+// not current, the kernels, the fetch.  Nothing of the run is written.
+extern "C" int rpe_build_tracks(rpe_handle *h, const uint8_t *use_pair, int edge_rule, int min_len,
+                                int32_t *counts, int32_t *track_start, int32_t *obs_frame, int32_t *obs_kp, float *obs_xy,
+                                int32_t *match_track)
+{
+    if (!h) return rpe_invalid(h, "rpe_build_tracks");
+    if (edge_rule < RPE_TRACK_EDGES_USABLE || edge_rule > RPE_TRACK_EDGES_ALL) return rpe_invalid(h, "rpe_build_tracks", "edge_rule must be 0 ... 2");
+    int rc = last_run_gate(h, "rpe_build_tracks", h->last.pairs, NEED_UNCHUNKED | NEED_PER_MATCH | NEED_TABLE);
+    if (rc) return rc;
+    const RpeLastRun &l = h->last;
+    const bool list = l.kind == RpeLastRun::LIST;
+    // a batch of one pair has img2_base == 1 like a stream of two frames: it is served as that stream (the header says so)
+    if (!list && l.run.feat.img2_base != 1) return rpe_invalid(h, "rpe_build_tracks", "the pairs of a batch share no frame (links join the pairs of a stream or of a pair list)");
+    const int P = l.pairs, n_frames = list ? h->fs.cap : P + 1;
+    if ((rc = tracks_check(h, "rpe_build_tracks", n_frames, min_len,
+                           "the frames of the run (a pair list: the store's capacity) times the keypoint capacity must be < 2^31")) != RPE_OK) return rc;
+    h->tk_frame_tab.resize((size_t)2 * P);
+    for (int p = 0; p < P; ++p) {
+        h->tk_frame_tab[(size_t)2 * p] = list ? l.tab[(size_t)2 * p] : p;
+        h->tk_frame_tab[(size_t)2 * p + 1] = list ? l.tab[(size_t)2 * p + 1] : p + 1;
+    }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if ((rc = tracks_alloc(h, n_frames)) != RPE_OK) return rc;
+    if (edge_rule != RPE_TRACK_EDGES_ALL && (rc = last_run_structure(h, P, false)) != RPE_OK) return rc;
+    if (use_pair) HIPCHK(h, hipMemcpyAsync(h->d_tk_use, use_pair, (size_t)P, hipMemcpyHostToDevice, h->stream));
+    const RpeTrackJob job = {P, n_frames, edge_rule, min_len, nullptr, h->d_m_n, h->d_m_q, h->d_m_t, use_pair ? h->d_tk_use : nullptr, nullptr,
+                             h->d_status, h->d_mask, h->d_pose_mask, h->d_pts1, h->d_pts2};
+    // the first wait also covers the uploads: use_pair has left the caller's array
+    return tracks_run(h, job, counts, track_start, obs_frame, obs_kp, obs_xy, match_track);
+}
+
+// rpe_tracks_from_matches: the caller's lists into the track buffers, the same kernels under RPE_TRACK_EDGES_ALL.  Neither
+// the workspace nor the record of the last run is touched.
+extern "C" int rpe_tracks_from_matches(rpe_handle *h, int P, int n_frames, const int32_t *frame1, const int32_t *frame2, const int32_t *m,
+                                       const int32_t *qidx, const int32_t *tidx, const uint8_t *edge, const float *pts1, const float *pts2,
+                                       int min_len, int32_t *counts, int32_t *track_start, int32_t *obs_frame, int32_t *obs_kp,
+                                       float *obs_xy, int32_t *match_track)
+{
+    const char *who = "rpe_tracks_from_matches";
+    if (!h || P < 0 || (P > 0 && (!frame1 || !frame2 || !m || !qidx || !tidx))) return rpe_invalid(h, who);
+    if (int rc = check_batch(h, P)) return rc;
+    int rc = tracks_check(h, who, n_frames, min_len, "n_frames must be >= 1 and n_frames * keypoint capacity < 2^31");
+    if (rc) return rc;
+    if ((pts1 == nullptr) != (pts2 == nullptr)) return rpe_invalid(h, who, "pts1 and pts2 must both be given or both be NULL");
+    if ((rc = check_match_counts(h, m, P)) != RPE_OK) return rc;
+    const size_t mm = (size_t)h->cfg.max_matches;
+    const int KC = h->lay.kcap;
+    for (int p = 0; p < P; ++p) {
+        if (frame1[p] < 0 || frame1[p] >= n_frames || frame2[p] < 0 || frame2[p] >= n_frames) return rpe_invalid(h, who, "a frame index outside 0 ... n_frames - 1");
+        for (size_t i = 0; i < (size_t)m[p]; ++i) {
+            const int q = qidx[p * mm + i], t = tidx[p * mm + i];
+            if (q < 0 || q >= KC || t < 0 || t >= KC) return rpe_invalid(h, who, "a keypoint index outside 0 ... keypoint capacity - 1");
+        }
+    }
+    if (P == 0) {
+        if (counts) memset(counts, 0, sizeof(int32_t) * 6);
+        if (track_start) track_start[0] = 0;
+        return RPE_OK;
+    }
+    h->tk_frame_tab.resize((size_t)2 * P);
+    for (int p = 0; p < P; ++p) { h->tk_frame_tab[(size_t)2 * p] = frame1[p]; h->tk_frame_tab[(size_t)2 * p + 1] = frame2[p]; }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if ((rc = tracks_alloc(h, n_frames)) != RPE_OK) return rc;
+    const size_t n = (size_t)P * mm;
+    HIPCHK(h, hipMemcpyAsync(h->d_tk_m, m, sizeof(int) * (size_t)P, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_tk_q, qidx, sizeof(int) * n, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_tk_t, tidx, sizeof(int) * n, hipMemcpyHostToDevice, h->stream));
+    if (edge) HIPCHK(h, hipMemcpyAsync(h->d_tk_edge, edge, n, hipMemcpyHostToDevice, h->stream));
+    if (pts1) {
+        HIPCHK(h, hipMemcpyAsync(h->d_tk_pts1, pts1, sizeof(float2) * n, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(h, hipMemcpyAsync(h->d_tk_pts2, pts2, sizeof(float2) * n, hipMemcpyHostToDevice, h->stream));
+    }
+    const RpeTrackJob job = {P, n_frames, RPE_TRACK_EDGES_ALL, min_len, nullptr, h->d_tk_m, h->d_tk_q, h->d_tk_t, nullptr, edge ? h->d_tk_edge : nullptr,
+                             nullptr, nullptr, nullptr, pts1 ? h->d_tk_pts1 : nullptr, pts1 ? h->d_tk_pts2 : nullptr};
+    // the first wait also covers the uploads: the lists have left the caller's arrays
+    return tracks_run(h, job, counts, track_start, obs_frame, obs_kp, obs_xy, match_track);
 }
 
 // refined poses: device buffers on first use, launch, fetch

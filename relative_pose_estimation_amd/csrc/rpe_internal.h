@@ -5,6 +5,7 @@
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <algorithm>
 #include <string>
 #include <vector>
 #include "../../include/rpe_amd.h"
@@ -295,6 +296,22 @@ struct RpeLastRun {
     int structure = 0;                // pairs [0, structure) of the run have d_mask (status form), d_pose_mask and d_points filled
 };
 
+// One job of the track kernels (track_kernels.hip): P pairs over n_frames frames, pair p between frames[p].x and frames[p].y,
+// its matches at p * max_matches.  Run form: the run's own match lists, status and masks (rmask / pmask read only under the
+// rules that name them), use_pair or null, edge null.  Stage form: the uploaded lists, rule ALL, edge or null.  pts1 == null:
+// obs_xy is zero
+struct RpeTrackJob {
+    int P, n_frames, rule, min_len;
+    const int2 *frames;
+    const int *m_n, *q, *t;
+    const uint8_t *use_pair, *edge;
+    const int *status;
+    const uint8_t *rmask, *pmask;
+    const float2 *pts1, *pts2;
+};
+#define RPE_TRACK_NODE_WORDS 11   // int arrays of one word per node in d_tk_node
+static inline int rpe_track_scan_blocks(int N) { return (int)(((long long)N + 2047) / 2048); }   // workgroups of the track scans (2048 nodes each)
+
 // One rpe_scale_links link on the device: pairs a and b of the last run, side bit 0 / 1 = the shared frame is image 2 of a / of b
 struct RpeLink { int a, b, side, pad; };
 
@@ -403,6 +420,19 @@ struct rpe_handle {
     double *d_ba_Rin = nullptr, *d_ba_tin = nullptr;
     int *d_ba_n = nullptr, *d_ba_pre = nullptr, *d_ba_counts = nullptr, *d_ba_info = nullptr;
     double *d_ba_Ra = nullptr, *d_ba_ta = nullptr, *d_ba_Rb = nullptr, *d_ba_tb = nullptr, *d_ba_rms = nullptr;
+    // rpe_build_tracks / rpe_tracks_from_matches only (created on first use).  Per match slot [max_batch * max_matches]: the
+    // edge flag and match_track; the stage form's uploaded lists (d_tk_q / _t / _edge / _pts1 / _pts2) and per pair its match
+    // count; per pair of either form the frame pair and use_pair.  Outputs: counts[8], track_start [slots + 1], observations
+    // [2 * slots].  Per node: d_tk_node, RPE_TRACK_NODE_WORDS arrays of tk_nodes words, with d_tk_partial (one int2 per scan
+    // workgroup) grown when a larger n_frames * kcap arrives; d_tk_seen [tk_frames] likewise
+    uint8_t *d_tk_eflag = nullptr, *d_tk_edge = nullptr, *d_tk_use = nullptr;
+    int *d_tk_mtrack = nullptr, *d_tk_q = nullptr, *d_tk_t = nullptr, *d_tk_m = nullptr, *d_tk_counts = nullptr;
+    int *d_tk_tstart = nullptr, *d_tk_oframe = nullptr, *d_tk_okp = nullptr;
+    float2 *d_tk_oxy = nullptr, *d_tk_pts1 = nullptr, *d_tk_pts2 = nullptr;
+    int2 *d_tk_frames = nullptr, *d_tk_partial = nullptr;
+    int *d_tk_node = nullptr, *d_tk_seen = nullptr;
+    int tk_nodes = 0, tk_frames = 0;
+    std::vector<int> tk_frame_tab;        // host side of d_tk_frames: source of its upload
     // the kernels of geom_kernels.hip whose dynamic-LDS limit a launch of this handle has raised (raise_lds_limit): the
     // attribute is per device, so the record is per handle
     std::vector<const void *> lds_raised;
@@ -536,6 +566,7 @@ bool rpe_link_poses_in_lds(const rpe_handle *h);
 int rpe_launch_bundle_gather(rpe_handle *h, const RpeRun &r, int L, double threshold_px);
 void rpe_launch_bundle(rpe_handle *h, int n, int min_shared, int max_iters, bool links);
 bool rpe_bundles_in_lds(const rpe_handle *h);
+void rpe_launch_tracks(rpe_handle *h, const RpeTrackJob &job);
 void rpe_launch_normalise(rpe_handle *h, const RpeRun &r);
 int rpe_launch_homography(rpe_handle *h, const RpeRun &r, int iters, double threshold_px, bool from_batch);
 void rpe_launch_undistort(rpe_handle *h, const float2 *d_pts, int n, const rpe_camera *d_cam, double2 *d_out);

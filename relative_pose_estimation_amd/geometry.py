@@ -152,3 +152,28 @@ def classify_pair(n_matches, n_E, n_H, n_rot, rotation_ratio=0.7, planar_ratio=0
 def pixel_homography(H, K1, K2):
     """K2 H K1^-1: a homography of normalised coordinates (pair_homographies' H) as one of pixels, image 1 -> image 2"""
     return np.asarray(K2, np.float64) @ np.asarray(H, np.float64) @ np.linalg.inv(np.asarray(K1, np.float64))
+
+
+def track_lengths(tracks):
+    """Observations per track of a tracks dict (_capi.Engine.build_tracks / tracks_from_matches): i32[n_tracks]."""
+    return np.diff(np.asarray(tracks['track_start'], np.int64)).astype(np.int32)
+
+
+def tracks_of_frames(tracks, frames):
+    """The tracks seen by ALL of the given frames: (track i32[n], obs i32[n, len(frames)]), one row per track (ascending
+    track index) with the index into 'obs_frame' / 'obs_kp' / 'obs_xy' of its observation on frames[0], frames[1], ...
+    The gather an N-view solver (or _capi.Engine.bundle_three_view) needs.  A track has at most one observation per
+    frame, so the row is unique."""
+    frames = np.asarray(frames, np.int64).reshape(-1)
+    if np.unique(frames).size != frames.size:
+        raise ValueError("tracks_of_frames: the frames must be distinct")
+    start = np.asarray(tracks['track_start'], np.int64)
+    of = np.asarray(tracks['obs_frame'], np.int64)
+    n_tracks = start.size - 1
+    track_of_obs = np.repeat(np.arange(n_tracks), np.diff(start))
+    obs = np.full((n_tracks, frames.size), -1, np.int64)
+    for c, f in enumerate(frames):
+        hit = np.nonzero(of == f)[0]
+        obs[track_of_obs[hit], c] = hit
+    keep = (obs >= 0).all(axis=1) if frames.size else np.zeros(n_tracks, bool)
+    return np.nonzero(keep)[0].astype(np.int32), obs[keep].astype(np.int32)

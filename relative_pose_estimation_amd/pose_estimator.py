@@ -386,7 +386,16 @@ class PoseEstimator:
         R0, t0 = eng.link_poses(a[:, 0], a[:, 1], a[:, 2], min_shared=min_shared)[:2]
         return eng.link_bundles(a[:, 0], a[:, 1], a[:, 2], R0, t0, threshold_px, min_shared, max_iters)
 
-    def estimate_trajectory(self, frames, min_shared=8, register=False, bundle=False):
+    def last_tracks(self, edge_rule=_capi.TRACK_EDGES_USABLE, min_len=2, use_pair=None):
+        """Feature tracks over the pairs of the last estimate_sequence / estimate_pairs / FrameStore.estimate call (of its
+        LAST chunk when the call ran in several; not in the reference; _capi.Engine.build_tracks): which keypoint of which
+        frame is the same scene point, at most one keypoint per frame and at least min_len frames per track.  A frame is
+        its index in the sequence, or its store slot (estimate_pairs: its index in `frames`).  Returns the dict of
+        build_tracks.  Raises RpeError after an estimate_batch of two or more pairs (its pairs share no frame); a batch of
+        one pair -- estimate() -- is the stream of its two images: frame 0 is image 1, frame 1 is image 2."""
+        return self._last_engine.build_tracks(use_pair, edge_rule, min_len)
+
+    def estimate_trajectory(self, frames, min_shared=8, register=False, bundle=False, tracks=False):
         """estimate_sequence plus what relates its poses (not in the reference): the scale link of every two consecutive
         pairs and the chained trajectory (geometry.chain_trajectory).  Returns a dict: 'R', 't', 'inliers', 'status' of
         the F - 1 pairs; 'ratio_stats' [F-2, 3], 'n_shared' [F-2], 'link_code' [F-2] of the links; 'R_abs' [F, 3, 3],
@@ -400,7 +409,8 @@ class PoseEstimator:
         (_capi.Engine.link_bundles with its defaults and this min_shared): 'R_bundle' [F-2, 3, 3], 't_bundle' [F-2, 3]
         (pair i + 1's pose on pair i's scale), 'bundle_code' [F-2], 'bundle_counts' [F-2, 2], and 'R_abs_ba' [F, 3, 3],
         'centers_ba' [F, 3]: the registered chain with the bundle's pose where its code is BUNDLE_OK, the link pose
-        elsewhere."""
+        elsewhere.
+        tracks=True adds 'tracks': the feature tracks of the sequence (last_tracks with its defaults)."""
         if self._camera is not None:
             raise ValueError("estimate_trajectory: the camera path has no stream form; use estimate_pairs and last_scale_links")
         R, t, inl, st = self.estimate_sequence(frames)
@@ -424,6 +434,8 @@ class PoseEstimator:
             chain = geometry.chain_trajectory(*geometry.registered_chain_inputs(R, t, st, stats[:, 1], code, Rb, tb, info[:, 0]))
             out.update({'R_bundle': ba[2], 't_bundle': ba[3], 'bundle_code': ba[7][:, 0], 'bundle_counts': ba[6],
                         'R_abs_ba': chain[0], 'centers_ba': chain[2]})
+        if tracks:
+            out['tracks'] = self._last_engine.build_tracks()
         return out
 
     def estimate_sequence(self, frames):

@@ -21,6 +21,7 @@
 // All f64 arithmetic uses the oracle's operation order (compiled with -ffp-contract=off).
 #include "rpe_internal.h"
 #include "pose_triangulate.h"
+#include "geom_device.h"
 #include <float.h>
 #include <stdlib.h>
 #include <algorithm>
@@ -39,91 +40,6 @@ __device__ static void ll_acc(double *c, const double *a, const double *b)
 __device__ static void ql_acc(double *c, const double *a, const double *b, double s)
 {
     for (int i = 0; i < 10; ++i) for (int j = 0; j < 4; ++j) c[QL2C[i][j]] += s * (a[i] * b[j]);
-}
-
-// Fixed Estrin scheme for degree <= 10 (dependency depth 7 instead of Horner's 20; the root finder is latency bound), the
-// arithmetic of horner() in oracle/geom_oracle.c.  c is anything indexable: a register array (static indices: K is the
-// level's degree) or an LDS row.  The oracle evaluates the full degree-10 scheme on coefficients zero-padded above the
-// degree; here the terms whose coefficients are structurally zero (index > K) are omitted: they would only add exact
-// zeros, so estrin<K> on a degree-K polynomial equals estrin<10> on its zero-padded row bit for bit.
-template <int K, typename C>
-__device__ __forceinline__ double estrin(const C &c, double x)
-{
-    const double x2 = x * x, x4 = x2 * x2, x8 = x4 * x4;
-    auto A = [&](int i) -> double {           // a_i = c[2i] + c[2i+1] x
-        if (2 * i + 1 <= K) return c[2 * i] + c[2 * i + 1] * x;
-        return (2 * i <= K) ? c[2 * i] : 0.;
-    };
-    double b0, b1 = 0., b2 = 0.;
-    b0 = (2 <= K) ? A(0) + A(1) * x2 : A(0);
-    if (4 <= K) b1 = (6 <= K) ? A(2) + A(3) * x2 : A(2);
-    if (8 <= K) b2 = (10 <= K) ? A(4) + c[10] * x2 : A(4);
-    double r = (4 <= K) ? b0 + b1 * x4 : b0;
-    if (8 <= K) r = r + b2 * x8;
-    return r;
-}
-
-// Safeguarded Newton on a bracket with a sign change (same code path as the oracle); p and dp evaluate the polynomial
-// and its derivative.
-template <typename P, typename DP>
-__device__ __forceinline__ double refine_root(P p, DP dp, double a, double b, int sa)
-{
-    double xl = sa ? b : a, xh = sa ? a : b;
-    double rts = 0.5 * (a + b);
-    double dxold = fabs(b - a), dx = dxold;
-    double f = p(rts), df = dp(rts);
-    for (int it = 0; it < 100; ++it) {
-        int bis = ((((rts - xh) * df - f) * ((rts - xl) * df - f)) > 0.0) || (fabs(2.0 * f) > fabs(dxold * df));
-        double nr;
-        dxold = dx;
-        if (bis) { dx = 0.5 * (xh - xl); nr = xl + dx; }
-        else { dx = f / df; nr = rts - dx; }
-        if (nr == rts || fabs(nr - rts) <= 2.3e-13 * fabs(nr)) { rts = nr; break; }
-        rts = nr;
-        f = p(rts); df = dp(rts);
-        if (f > 0.0) xh = rts; else xl = rts;
-    }
-    return rts;
-}
-
-// Root bound from binary exponents only (same integers on CPU and GPU): Fujiwara's |z| <= 2 max_i |a_{k-i}/a_k|^(1/i)
-// with |a| < 2^(ilogb(a)+1): R = 2^(1 + max_i ceil((e_{k-i} - e_k + 1)/i)).  Cauchy's bound put the outer brackets
-// orders of magnitude beyond the roots and the safeguarded Newton bisected its way back (oracle: root_bound()).
-// K: the degree where it is a compile-time constant (the register path: the loop unrolls, p keeps static indices and
-// the divisions by m are by constants), 0 where it is k at run time (the generic path).  The constant has to be a
-// template argument: as a function argument it arrived, after inlining, too late for the unsigned form of the
-// divisions: 121 more instructions over levels 2..10 and 0.5 % on the ransac stage.
-template <int K, typename C>
-__device__ __forceinline__ double root_bound(const C &p, int k_run = 0)
-{
-    const int k = K ? K : k_run;
-    const int ek = ilogb(p[k]);
-    int emax = -100000;
-#pragma unroll
-    for (int i = 0; i < k; ++i) {
-        if (p[i] != 0.) {
-            const int d = ilogb(p[i]) - ek + 1, m = k - i;
-            const int q = d >= 0 ? (d + m - 1) / m : -((-d) / m);
-            if (q > emax) emax = q;
-        }
-    }
-    double R = emax == -100000 ? 1. : ldexp(1., emax + 1);
-    if (!(R < 1e12)) R = 1e12;
-    return R;
-}
-
-// One interval of a level (the oracle's loop body in poly_real_roots): clamp the bracket to the root bound, test the
-// signs, refine.  p has degree K, dp = p'; both may be rows zero-padded to degree 10 (K = 10 then evaluates any level).
-template <int K, typename C>
-__device__ __forceinline__ bool bracket_root(const C &p, const C &dp, double a, double b, double R, bool active, double &root)
-{
-    if (a < -R) a = -R;
-    if (b > R) b = R;
-    if (!(active && a < b)) return false;
-    const int sa = estrin<K>(p, a) > 0., sb = estrin<K>(p, b) > 0.;
-    if (sa == sb) return false;
-    root = refine_root([&](double x) { return estrin<K>(p, x); }, [&](double x) { return estrin<K - 1>(dp, x); }, a, b, sa);
-    return true;
 }
 
 // generic path (leading coefficient trimmed to degree < 10: rare): one lane walks the whole chain serially with dynamic
@@ -848,14 +764,6 @@ __global__ __launch_bounds__(256) void ransac_mask_kernel(const double2 *__restr
     }
 }
 
-// Launches the camera instance of a kernel when the run carries a camera source, the shared-K instance otherwise (the
-// single-K paths launch CAM = false only): the two instances share one signature
-template <typename Kernel, typename... Args>
-static void launch_cam(const RpeRun &r, Kernel with_cameras, Kernel with_K, dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args... args)
-{
-    hipLaunchKernelGGL(r.cam.cams ? with_cameras : with_K, grid, block, lds, stream, args...);
-}
-
 static void launch_mask(rpe_handle *h, const RpeRun &r, const int *status)
 {
     launch_cam(r, ransac_mask_kernel<true>, ransac_mask_kernel<false>, dim3(r.pairs), dim3(256), 0, h->stream,
@@ -1107,59 +1015,9 @@ void rpe_launch_pose(rpe_handle *h, const RpeRun &r, bool fused)
 //               (both forms walk the same list in the same order: same sums)
 //   fallback    the refined pose is returned only if it is finite and keeps at least the cheirality inliers of the
 //               input pose (triangulate_one over all matches, as recover_pose_kernel counts them)
-#define REFINE_LAMBDA0 1e-3          // initial damping
-#define REFINE_REL_TOL 1e-6          // stop when an accepted step lowers the cost by no more than this fraction
-#define REFINE_STEP_TOL 1e-9         // ... or its 5-vector is no longer than this
-#define REFINE_SMALL_ANGLE 1e-4      // Rodrigues: series for sin(th)/th and (1 - cos th)/th^2 below this angle
 #define REFINE_MIN_RESIDUALS 6       // 5 degrees of freedom
 #define REFINE_LDS_MATCHES 2048      // staging cut (max_matches)
 #define REFINE_NSUM 21               // 15 J'J + 5 J'r + 1 r'r
-
-__device__ __forceinline__ double wave_sum_f64(double v)
-{
-#pragma unroll
-    for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o);
-    return v;
-}
-
-// all 256 threads return the same N totals: ((wave 0 + wave 1) + wave 2) + wave 3
-template <int N>
-__device__ __forceinline__ void block_sum_f64(double (&v)[N], double *s_red, int tid)
-{
-#pragma unroll
-    for (int k = 0; k < N; ++k) v[k] = wave_sum_f64(v[k]);
-    __syncthreads();                                   // readers of the previous reduction are done
-    if ((tid & 63) == 0) {
-#pragma unroll
-        for (int k = 0; k < N; ++k) s_red[(tid >> 6) * N + k] = v[k];
-    }
-    __syncthreads();
-#pragma unroll
-    for (int k = 0; k < N; ++k) v[k] = ((s_red[k] + s_red[N + k]) + s_red[2 * N + k]) + s_red[3 * N + k];
-}
-
-// Ordered compaction, one step of 256 candidates in thread order: the slot of this thread's element when f is set (n + the
-// number of flagged threads below it), and n advanced by the step's total.  All 256 threads call it (two barriers, both
-// in front of the caller's store to the slot: a barrier follows the last step before anyone reads the list);
-// ballot / popcount only, so the order never depends on timing.  s_wc: one LDS word per wave.
-__device__ __forceinline__ int ordered_slot(bool f, int *s_wc /*[4]*/, int &n)
-{
-    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-    const unsigned long long bal = __ballot(f);
-    if (lane == 0) s_wc[wv] = __popcll(bal);
-    __syncthreads();
-    int off = n, tot = 0;
-#pragma unroll
-    for (int w = 0; w < 4; ++w) { const int c = s_wc[w]; if (w < wv) off += c; tot += c; }
-    n += tot;
-    __syncthreads();
-    return off + __popcll(bal & ((1ull << lane) - 1ull));
-}
-
-__device__ __forceinline__ void cross3(const double *a, const double *b, double *c)
-{
-    c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
-}
 
 // Sampson residual of one match in pixels; optionally its 5 derivatives (w0 w1 w2 | b1 b2)
 template <bool JAC>
@@ -1200,141 +1058,6 @@ __device__ __forceinline__ double refine_residual(const double *R, const double 
         }
     }
     return C * inv;
-}
-
-// tangent basis of the unit sphere at t: b1 = normalise(t x e_k), k = axis of smallest |t_k| (lowest on ties), b2 = t x b1
-__device__ __forceinline__ void refine_basis(const double *t, double *b1, double *b2)
-{
-    int k = 0;                                       // static indices only
-    double m = fabs(t[0]);
-    if (fabs(t[1]) < m) { k = 1; m = fabs(t[1]); }
-    if (fabs(t[2]) < m) k = 2;
-    const double e[3] = {k == 0 ? 1. : 0., k == 1 ? 1. : 0., k == 2 ? 1. : 0.};
-    cross3(t, e, b1);
-    const double n = sqrt((b1[0] * b1[0] + b1[1] * b1[1]) + b1[2] * b1[2]);
-    b1[0] /= n; b1[1] /= n; b1[2] /= n;
-    cross3(t, b1, b2);
-}
-
-// Rn = exp([w]x) R
-__device__ __forceinline__ void refine_rotate(const double *w, const double *R, double *Rn)
-{
-    const double th2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2], th = sqrt(th2);
-    double A, B;
-    if (th < REFINE_SMALL_ANGLE) { A = 1. - th2 / 6.; B = 0.5 - th2 / 24.; }
-    else { const double sh = sin(0.5 * th); A = sin(th) / th; B = 2. * (sh * sh) / th2; }
-    // exp = I + A [w]x + B [w]x^2,  [w]x^2 = w w' - th2 I
-    double X[9];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) X[i * 3 + j] = B * (w[i] * w[j]) + (i == j ? 1. - B * th2 : 0.);
-    X[1] -= A * w[2]; X[2] += A * w[1];
-    X[3] += A * w[2]; X[5] -= A * w[0];
-    X[6] -= A * w[1]; X[7] += A * w[0];
-#pragma unroll
-    for (int i = 0; i < 3; ++i)
-#pragma unroll
-        for (int j = 0; j < 3; ++j) Rn[i * 3 + j] = (X[i * 3] * R[j] + X[i * 3 + 1] * R[3 + j]) + X[i * 3 + 2] * R[6 + j];
-}
-
-// (H + lambda diag H) d = -g for N parameters, H given as its upper triangle (row-major, N (N + 1) / 2 entries); false when
-// not positive definite
-template <int N>
-__device__ __forceinline__ bool refine_solve(const double *H, const double *g, double lambda, double *d)
-{
-    double L[N][N];
-    int q = 0;
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-#pragma unroll
-        for (int j = i; j < N; ++j, ++q) { L[i][j] = H[q]; L[j][i] = H[q]; }
-#pragma unroll
-    for (int i = 0; i < N; ++i) L[i][i] = L[i][i] + lambda * L[i][i];
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-        double s = L[j][j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) s -= L[j][k] * L[j][k];
-        if (!(s > 0.) || !isfinite(s)) ok = false;
-        const double dj = sqrt(s);
-        L[j][j] = dj;
-#pragma unroll
-        for (int i = j + 1; i < N; ++i) {
-            double v = L[i][j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
-            L[i][j] = v / dj;
-        }
-    }
-    double y[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        double v = -g[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) v -= L[i][k] * y[k];
-        y[i] = v / L[i][i];
-    }
-#pragma unroll
-    for (int i = N - 1; i >= 0; --i) {
-        double v = y[i];
-#pragma unroll
-        for (int k = i + 1; k < N; ++k) v -= L[k][i] * d[k];
-        d[i] = v / L[i][i];
-    }
-    return ok;
-}
-
-// The Levenberg-Marquardt loop over N parameters, shared by pose_refine_kernel, link_pose_kernel and bundle_kernel; all 256
-// threads call it with identical operands.
-//   linearise()        the normal equations at the caller's state, summed over the workgroup (block_sum_f64)
-//   solve(lambda, d)   the damped step d from them; false when there is none (a matrix that is not positive definite).
-//                      RefineNormalSolve is the plain form: s holds the upper triangle of J'J, then J'r, then r'r
-//   trial(d, Rn, tn)   the pose (Rn, tn) that step d leads to from (R, t), and this thread's part of its cost
-//   commit()           an accepted step: whatever state the caller keeps outside (R, t) moves with it
-// A failed solve or a step that does not strictly lower the cost multiplies lambda by 10; an accepted step divides it by
-// 10, moves (R, t, cost) and stops the loop when it lowered the cost by no more than REFINE_REL_TOL of it or is no longer
-// than REFINE_STEP_TOL.  The state is linearised again only when another iteration follows an accepted step.  iters counts
-// the iterations begun, acc the steps accepted.
-template <int N>
-struct RefineNormalSolve {
-    const double *s;
-    __device__ __forceinline__ bool operator()(double lambda, double (&d)[N]) const { return refine_solve<N>(s, s + N * (N + 1) / 2, lambda, d); }
-};
-struct RefineNoCommit { __device__ __forceinline__ void operator()() const {} };
-
-template <int N, class Linearise, class Solve, class Trial, class Commit>
-__device__ __forceinline__ void refine_lm(double (&R)[9], double (&t)[3], double &cost, int max_iters, double *s_red,
-                                          Linearise linearise, Solve solve, Trial trial, Commit commit, int &iters, int &acc)
-{
-    double lambda = REFINE_LAMBDA0;
-    bool need_lin = false;
-    for (int it = 0; it < max_iters; ++it) {
-        if (need_lin) { linearise(); need_lin = false; }
-        ++iters;
-        double d[N];
-        if (!solve(lambda, d)) { lambda = lambda * 10.; continue; }
-        double Rn[9], tn[3];
-        double c1[1] = {trial(d, Rn, tn)};
-        block_sum_f64<1>(c1, s_red, threadIdx.x);
-        if (isfinite(c1[0]) && c1[0] < cost) {
-            const double dec = cost - c1[0], prev = cost;
-            double dn = d[0] * d[0];
-#pragma unroll
-            for (int k = 1; k < N; ++k) dn = dn + d[k] * d[k];
-            dn = sqrt(dn);
-#pragma unroll
-            for (int e = 0; e < 9; ++e) R[e] = Rn[e];
-#pragma unroll
-            for (int e = 0; e < 3; ++e) t[e] = tn[e];
-            commit();
-            cost = c1[0]; lambda = lambda / 10.; ++acc; need_lin = true;
-            if (dec <= REFINE_REL_TOL * prev || dn <= REFINE_STEP_TOL) break;
-        } else {
-            lambda = lambda * 10.;
-        }
-    }
 }
 
 // status / inl_in may be null (stage form): every pair is then refined and the input pose's cheirality inliers are counted here
@@ -1504,179 +1227,6 @@ void rpe_launch_refine(rpe_handle *h, const RpeRun &r, int max_iters, bool from_
                h->d_ref_R, h->d_ref_t, h->d_ref_inl, h->d_ref_info, h->d_ref_rms, mm, max_iters);
 }
 
-// ------------------------------------------------------------ scale links
-// rpe_scale_links (NOT in the reference; include/rpe_amd.h states the rules): the baseline of pair b in units of the
-// baseline of pair a, from the keypoints of the frame the two pairs share that both triangulated.  One 256-thread
-// workgroup per link, f64 throughout, everything between the per-match buffers and the three results stays in LDS.
-//   table   (link_join) one word per keypoint of the shared frame: high half = lowest usable match index of pair a, low
-//           half = of pair b, 0xFFFF = none (max_matches <= 8064).  Pass 1: a's usable matches atomicMin (index << 16 |
-//           0xFFFF): every low half is still 0xFFFF, so the minimum orders the high halves.  Pass 2: b's usable matches
-//           whose key has an a entry atomicMin (that high half << 16 | index): equal high halves, the minimum orders the
-//           low ones.
-//   ratios  pass 3: b's matches that won their key compute d_a / d_b and append it to an LDS array (integer atomicAdd on
-//           the fill count: the order inside the array varies run to run, the set does not)
-//   ranks   bitonic sort of the array, padded with +inf to a power of two; the three results are elements of the sorted
-//           array, so they are bit-deterministic whatever order pass 3 left (ties are equal values)
-// Dynamic LDS (all of the kernel's LDS, base 16-byte aligned): [sort_cap f64 ratios][kcap u32 table][fill count],
-// sort_cap = next power of two >= max_matches.  Defaults (500 matches, 4064 keypoints): 4 + 15.9 KB; uncapped SIFT
-// (8064 matches, 16384 keypoints): 64 + 64 KB, above the 64 KB a kernel gets without the function attribute.
-// The link, the two pairs' status, match counts, R and t come from blockIdx-indexed reads: uniform, scalar loads.
-#define LINK_NONE 0xFFFFu
-
-// the triangulated point P of a pair with pose (R, t) in the shared frame's coordinates: P itself when the shared frame is
-// the pair's image 1, R P + t when it is its image 2
-__device__ __forceinline__ void link_point(const double *__restrict__ P, const double (&R)[9], const double (&t)[3], bool image2,
-                                           double &x, double &y, double &z)
-{
-    x = P[0]; y = P[1]; z = P[2];
-    if (image2) {
-        const double X = x, Y = y, Z = z;
-        x = ((R[0] * X + R[1] * Y) + R[2] * Z) + t[0];
-        y = ((R[3] * X + R[4] * Y) + R[5] * Z) + t[1];
-        z = ((R[6] * X + R[7] * Y) + R[8] * Z) + t[2];
-    }
-}
-
-__device__ __forceinline__ double link_distance(const double *__restrict__ P, const double (&R)[9], const double (&t)[3], bool image2)
-{
-    double x, y, z;
-    link_point(P, R, t, image2, x, y, z);
-    return sqrt((x * x + y * y) + z * z);
-}
-
-// The table of the header in s_tab[kcap], for pairs a and b of a link: key_a / key_b their matches' keypoint indices in the
-// shared frame, na / nb their match counts, oa / ob their offsets into the two masks.  A match of a is usable when both
-// masks hold it; FILTER_B asks the same of b's matches, else every match of b takes part.  All 256 threads call it (three
-// barriers, the last behind pass 2: the table is final on return).
-template <bool FILTER_B>
-__device__ __forceinline__ void link_join(unsigned *s_tab, int kcap, const int *__restrict__ key_a, int na, long long oa,
-                                          const int *__restrict__ key_b, int nb, long long ob,
-                                          const uint8_t *__restrict__ ransac_mask, const uint8_t *__restrict__ pose_mask)
-{
-    const int tid = threadIdx.x;
-    for (int k = tid; k < kcap; k += 256) s_tab[k] = 0xFFFFFFFFu;
-    __syncthreads();
-    for (int i = tid; i < na; i += 256) {
-        if (!(ransac_mask[oa + i] && pose_mask[oa + i])) continue;
-        const int key = key_a[i];
-        if ((unsigned)key < (unsigned)kcap) atomicMin(&s_tab[key], ((unsigned)i << 16) | LINK_NONE);
-    }
-    __syncthreads();
-    for (int i = tid; i < nb; i += 256) {
-        if (FILTER_B && !(ransac_mask[ob + i] && pose_mask[ob + i])) continue;
-        const int key = key_b[i];
-        if ((unsigned)key >= (unsigned)kcap) continue;
-        const unsigned e = s_tab[key];                      // the high half is final since the barrier
-        if ((e >> 16) != LINK_NONE) atomicMin(&s_tab[key], (e & 0xFFFF0000u) | (unsigned)i);
-    }
-    __syncthreads();
-}
-
-__global__ __launch_bounds__(256) void scale_links_kernel(const RpeLink *__restrict__ links, const int *__restrict__ m_q,
-                                                           const int *__restrict__ m_t, const int *__restrict__ m_n,
-                                                           const int *__restrict__ status, const uint8_t *__restrict__ ransac_mask,
-                                                           const uint8_t *__restrict__ pose_mask, const double *__restrict__ points,
-                                                           const double *__restrict__ Rall, const double *__restrict__ tall,
-                                                           int max_matches, int kcap, int sort_cap, int min_shared,
-                                                           double *__restrict__ stats, int *__restrict__ n_shared, int *__restrict__ code)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char s_link[];
-    double *s_ratio = (double *)s_link;
-    unsigned *s_tab = (unsigned *)(s_link + sizeof(double) * (size_t)sort_cap);
-    int *s_fill = (int *)(s_tab + kcap);
-    const int link = blockIdx.x, tid = threadIdx.x;
-    const RpeLink lk = links[link];
-    if (status[lk.a] != RPE_PAIR_OK || status[lk.b] != RPE_PAIR_OK) {
-        if (tid < 3) stats[link * 3 + tid] = 0.;
-        if (tid == 0) { n_shared[link] = 0; code[link] = RPE_LINK_PAIR_FAILED; }
-        return;
-    }
-    const bool a2 = (lk.side & 1) != 0, b2 = (lk.side & 2) != 0;
-    const int na = min(m_n[lk.a], max_matches), nb = min(m_n[lk.b], max_matches);
-    const long long oa = (long long)lk.a * max_matches, ob = (long long)lk.b * max_matches;
-    const int *key_a = (a2 ? m_t : m_q) + oa, *key_b = (b2 ? m_t : m_q) + ob;
-    if (tid == 0) *s_fill = 0;
-    link_join<true>(s_tab, kcap, key_a, na, oa, key_b, nb, ob, ransac_mask, pose_mask);
-    double Ra[9], ta[3], Rb[9], tb[3];
-#pragma unroll
-    for (int e = 0; e < 9; ++e) { Ra[e] = Rall[lk.a * 9 + e]; Rb[e] = Rall[lk.b * 9 + e]; }
-#pragma unroll
-    for (int e = 0; e < 3; ++e) { ta[e] = tall[lk.a * 3 + e]; tb[e] = tall[lk.b * 3 + e]; }
-    for (int i = tid; i < nb; i += 256) {
-        if (!(ransac_mask[ob + i] && pose_mask[ob + i])) continue;
-        const int key = key_b[i];
-        if ((unsigned)key >= (unsigned)kcap) continue;
-        const unsigned e = s_tab[key];
-        if ((e >> 16) == LINK_NONE || (e & 0xFFFFu) != (unsigned)i) continue;
-        const double da = link_distance(points + (oa + (e >> 16)) * 3, Ra, ta, a2);
-        const double db = link_distance(points + (ob + i) * 3, Rb, tb, b2);
-        s_ratio[atomicAdd(s_fill, 1)] = da / db;             // at most one winner per match of b: fill <= nb <= sort_cap
-    }
-    __syncthreads();
-    const int n = *s_fill;
-    int N = 1;
-    while (N < n) N <<= 1;
-    for (int i = n + tid; i < N; i += 256) s_ratio[i] = __builtin_inf();
-    __syncthreads();
-    for (int k = 2; k <= N; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int i = tid; i < N; i += 256) {
-                const int p = i ^ j;
-                if (p > i) {
-                    const double u = s_ratio[i], v = s_ratio[p];
-                    if ((u > v) == ((i & k) == 0)) { s_ratio[i] = v; s_ratio[p] = u; }
-                }
-            }
-            __syncthreads();
-        }
-    const bool ok = n >= min_shared;
-    if (tid < 3) stats[link * 3 + tid] = ok ? s_ratio[((n - 1) * (tid + 1)) / 4] : 0.;
-    if (tid == 0) { n_shared[link] = n; code[link] = ok ? RPE_LINK_OK : RPE_LINK_TOO_FEW; }
-}
-
-// A launch with more than 64 KB of dynamic LDS needs the kernels' limit raised first, once per device: the launchers of
-// scale links, homographies and link poses call this when their handle asks for that much.  The limit belongs to the
-// kernel, not to the handle, so lds_max is the most any legal handle asks of these kernels; the handle records the
-// kernels it has raised.  Never inside a graph capture: rpe_scale_links, rpe_pair_homographies / rpe_find_homography and
-// rpe_link_poses alone come here.
-static int raise_lds_limit(rpe_handle *h, std::initializer_list<const void *> kernels, size_t lds_max)
-{
-    for (const void *k : kernels) {
-        if (std::find(h->lds_raised.begin(), h->lds_raised.end(), k) != h->lds_raised.end()) continue;
-        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max) != hipSuccess) return RPE_ERR_HIP;
-        h->lds_raised.push_back(k);
-    }
-    return RPE_OK;
-}
-
-// sort_cap and the dynamic LDS of scale_links_kernel for max_matches matches and kcap keypoints (the layout at the head of
-// the section)
-static int scale_links_sort_cap(int mm)
-{
-    int sort_cap = 8;
-    while (sort_cap < mm) sort_cap <<= 1;
-    return sort_cap;
-}
-static size_t scale_links_lds(int mm, int kcap) { return sizeof(double) * (size_t)scale_links_sort_cap(mm) + sizeof(unsigned) * (size_t)kcap + 16; }
-
-// the last run's d_status / d_m_n / d_R / d_t, its match indices and the structure buffers -> d_link_stats / _n / _code of
-// the L links in d_links
-int rpe_launch_scale_links(rpe_handle *h, int L, int min_shared)
-{
-    const int mm = h->cfg.max_matches, kcap = h->lay.kcap;
-    const int sort_cap = scale_links_sort_cap(mm);
-    const size_t lds = scale_links_lds(mm, kcap);
-    // the most: 8064 matches of uncapped SIFT's keypoints
-    if (lds > 65536 && raise_lds_limit(h, {(const void *)scale_links_kernel}, scale_links_lds(8064, RPE_SIFT_UNCAPPED_CAPACITY + 64)) != RPE_OK)
-        return RPE_ERR_HIP;
-    hipLaunchKernelGGL(scale_links_kernel, dim3(L), dim3(256), lds, h->stream, (const RpeLink *)h->d_links,
-                       (const int *)h->d_m_q, (const int *)h->d_m_t, (const int *)h->d_m_n, (const int *)h->d_status,
-                       (const uint8_t *)h->d_mask, (const uint8_t *)h->d_pose_mask, (const double *)h->d_points,
-                       (const double *)h->d_R, (const double *)h->d_t, mm, kcap, sort_cap, min_shared,
-                       h->d_link_stats, h->d_link_n, h->d_link_code);
-    return RPE_OK;
-}
-
 // ------------------------------------------------------------ homography / rotation-only
 // rpe_pair_homographies / rpe_find_homography (NOT in the reference; include/rpe_amd.h states the rule): a homography by
 // RANSAC over the first four indices of findEssentialMat's subset stream, the rotation fitted to its inliers, and the
@@ -1696,12 +1246,6 @@ int rpe_launch_scale_links(rpe_handle *h, int L, int min_shared)
 #define HG_ROUND 256
 #define HG_MODEL_DOUBLES 18
 #define HG_LDS_MATCHES 2048
-
-__device__ __forceinline__ double hg_dot(const double (&a)[3], const double (&b)[3]) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; }
-__device__ __forceinline__ void hg_cross(const double (&a)[3], const double (&b)[3], double (&c)[3])
-{
-    c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
-}
 
 // adj(A), A row-major: rows cross(c1, c2), cross(c2, c0), cross(c0, c1) of A's columns
 __device__ __forceinline__ void hg_adj(const double (&A)[9], double (&J)[9])
@@ -1724,8 +1268,6 @@ __device__ __forceinline__ bool hg_basis(const double2 (&s)[4], double (&A)[9])
     for (int r = 0; r < 3; ++r) { A[r * 3] = l0 * p0[r]; A[r * 3 + 1] = l1 * p1[r]; A[r * 3 + 2] = l2 * p2[r]; }
     return l0 != 0. && l1 != 0. && l2 != 0.;
 }
-
-__device__ __forceinline__ bool hg_finite(double v) { return fabs(v) <= DBL_MAX; }
 
 // the four-point model of the header: H (unit norm, gauged at p0), G = adj(H) (gauged at q0); returns its validity
 __device__ __forceinline__ bool hg_four_point(const double2 (&p)[4], const double2 (&q)[4], double (&H)[9], double (&G)[9])
@@ -1956,978 +1498,5 @@ int rpe_launch_homography(rpe_handle *h, const RpeRun &r, int iters, double thre
                from_batch ? (const RpeRansacState *)h->d_rstate : (const RpeRansacState *)nullptr,
                (const unsigned short *)h->d_subsets, (const double *)h->d_K, r.cam, threshold_px, iters, h->cfg.ransac_max_iters,
                mm, use_lds, h->d_hg_H, h->d_hg_R, h->d_hg_mask, h->d_hg_counts, h->d_hg_info);
-    return RPE_OK;
-}
-
-// ------------------------------------------------------------ link poses
-// rpe_link_poses (NOT in the reference; include/rpe_amd.h states the rule): the pose of pair b's other frame C against the
-// points pair a triangulated, by P3P RANSAC over the keypoints of the shared frame S, on pair a's scale.  One 256-thread
-// workgroup per link, f64 throughout, no contraction.
-//   join     link_join's packed table (high half: lowest usable match of a, low half: lowest match of b; here every match
-//            of b takes part).  The winners of b are then compacted in match order by ordered_slot (ballot / popcount):
-//            correspondence c = the c-th winner, so no atomic decides an order.
-//   list     per correspondence X (3 f64, link_point: in S's frame), q (2 f64) and b's match index (u16).  X and q live in
-//            LDS up to LP_LDS_MATCHES matches (40 B each: 20 KB at the default 500) and in d_lp_corr above it; both forms
-//            are walked through the same pointers in the same order.  The indices are always in LDS.
-//   rounds   as the homography's: LP_ROUND = 256 samples at a time, thread j solves sample j in registers (quartic, the
-//            derivative chain with static indices, up to four poses) and parks its candidates at slot 4 j + root; the
-//            slots of the valid ones are listed densely in (iteration, root) order (block_excl_scan of the per-thread
-//            counts).  The four waves score the dense list round-robin, lanes striding the correspondences, wave_sum
-//            for the count; a wave meets its candidates in ascending (iteration, root) order and replaces its best on a
-//            strictly larger count only; the cross-wave election (elect_best) compares (count, 4 * iteration + root).
-//   winner   solved again by every thread (the same code on the same operands: the same bits), its inlier flags, then the
-//            polish: refine_lm<6> on the reprojection residuals (block_sum_f64 sums, refine_rotate), and the fallback
-//            test over all correspondences.
-// Dynamic LDS (all of the kernel's LDS, base 16-byte aligned):
-//   [A] max(kcap u32 table, LP_ROUND * 4 poses of 12 f64 = 96 KB): the table is dead once the list is built, the poses
-//       once the election is over (the winner's inlier flags then live there)
-//   [s_red 4 * 28 f64][X, q: 40 B * max_matches when in LDS][dense list 1024 u16][match indices max_matches u16][32 ints]
-// 120 KB at the defaults (one workgroup per CU), 141 KB at the cut, 115 KB for uncapped SIFT (8064 matches in d_lp_corr).
-#define LP_ROUND 256
-#define LP_POSE_DOUBLES 12
-#define LP_LDS_MATCHES 1024
-#define LP_NSUM 28                   // 21 J'J + 6 J'r + 1 r'r
-
-struct LpQuartic { double j[9], b2, q1, n0, n1, n2, d0, d1, c[5]; };
-
-// bearings, side lengths, cosines and the quartic in v of the header
-__device__ __forceinline__ void lp_quartic(const double (&P)[9], const double (&q)[6], LpQuartic &g)
-{
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const double x = q[2 * k], y = q[2 * k + 1], m = sqrt((x * x + y * y) + 1.);
-        g.j[3 * k] = x / m; g.j[3 * k + 1] = y / m; g.j[3 * k + 2] = 1. / m;
-    }
-    const double d23[3] = {P[3] - P[6], P[4] - P[7], P[5] - P[8]}, d13[3] = {P[0] - P[6], P[1] - P[7], P[2] - P[8]};
-    const double d12[3] = {P[0] - P[3], P[1] - P[4], P[2] - P[5]};
-    const double j1[3] = {g.j[0], g.j[1], g.j[2]}, j2[3] = {g.j[3], g.j[4], g.j[5]}, j3[3] = {g.j[6], g.j[7], g.j[8]};
-    const double a2 = hg_dot(d23, d23), b2 = hg_dot(d13, d13), c2 = hg_dot(d12, d12);
-    const double ca = hg_dot(j2, j3), cb = hg_dot(j1, j3), cg = hg_dot(j1, j2);
-    const double q1 = -(2. * cb), m = a2 - c2;
-    const double n0 = b2 + m, n1 = m * q1, n2 = m - b2;
-    const double d0 = (2. * b2) * cg, d1 = -((2. * b2) * ca);
-    const double nn[5] = {n0 * n0, 2. * (n0 * n1), 2. * (n0 * n2) + n1 * n1, 2. * (n1 * n2), n2 * n2};
-    const double nd[4] = {n0 * d0, n0 * d1 + n1 * d0, n1 * d1 + n2 * d0, n2 * d1};
-    const double dd[3] = {d0 * d0, 2. * (d0 * d1), d1 * d1};
-    const double w0 = b2 - c2, w1 = -(c2 * q1), w2 = -c2;
-    const double wd[5] = {w0 * dd[0], w0 * dd[1] + w1 * dd[0], (w0 * dd[2] + w1 * dd[1]) + w2 * dd[0], w1 * dd[2] + w2 * dd[1], w2 * dd[2]};
-#pragma unroll
-    for (int i = 0; i < 4; ++i) g.c[i] = (b2 * nn[i] - d0 * nd[i]) + wd[i];
-    g.c[4] = b2 * nn[4] + wd[4];
-    g.b2 = b2; g.q1 = q1; g.n0 = n0; g.n1 = n1; g.n2 = n2; g.d0 = d0; g.d1 = d1;
-}
-
-// One level of the derivative chain in registers: the roots of p (degree K, p' = dp) between the nr_prev roots of dp in
-// crit, ascending into out.  Every index is static: the interval loop unrolls, a root lands in its slot by compares.
-template <int K>
-__device__ __forceinline__ int lp_level(const double (&p)[5], const double (&dp)[5], const double (&crit)[4], int nr_prev, double (&out)[4])
-{
-    const double R = root_bound<K>(p);
-    int nout = 0;
-#pragma unroll
-    for (int iv = 0; iv < K; ++iv) {                     // dp has at most K - 1 roots: at most K intervals
-        const double a = iv == 0 ? -R : crit[iv - 1], b = iv == nr_prev ? R : crit[iv];
-        double root;
-        if (bracket_root<K>(p, dp, a, b, R, iv <= nr_prev, root)) {
-#pragma unroll
-            for (int s = 0; s < 4; ++s) if (s == nout) out[s] = root;
-            ++nout;
-        }
-    }
-    return nout;
-}
-
-// real roots, ascending, of c[0] + ... + c[N] x^N (c[N] != 0): poly_real_roots_generic's chain for a degree known at
-// compile time
-template <int N>
-__device__ __forceinline__ int lp_chain(const double (&c)[5], double (&roots)[4])
-{
-    double lv[5][5];
-#pragma unroll
-    for (int k = 0; k < 5; ++k)
-#pragma unroll
-        for (int i = 0; i < 5; ++i) lv[k][i] = (k == N && i <= N) ? c[i] : 0.;
-#pragma unroll
-    for (int k = N; k >= 2; --k)
-#pragma unroll
-        for (int i = 0; i < k; ++i) lv[k - 1][i] = lv[k][i + 1] * (double)(i + 1);
-    double crit[4] = {-lv[1][0] / lv[1][1], 0., 0., 0.};
-    int nr = 1;
-    if (N >= 2) {
-        double out[4] = {0., 0., 0., 0.};
-        nr = lp_level<2>(lv[2], lv[1], crit, nr, out);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) crit[s] = out[s];
-    }
-    if (N >= 3) {
-        double out[4] = {0., 0., 0., 0.};
-        nr = lp_level<3>(lv[3], lv[2], crit, nr, out);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) crit[s] = out[s];
-    }
-    if (N >= 4) {
-        double out[4] = {0., 0., 0., 0.};
-        nr = lp_level<4>(lv[4], lv[3], crit, nr, out);
-#pragma unroll
-        for (int s = 0; s < 4; ++s) crit[s] = out[s];
-    }
-#pragma unroll
-    for (int s = 0; s < 4; ++s) roots[s] = crit[s];
-    return nr;
-}
-
-// the quartic's real roots: its degree is the highest non-zero coefficient
-__device__ __forceinline__ int lp_roots(const double (&c)[5], double (&roots)[4])
-{
-    if (c[4] != 0.) return lp_chain<4>(c, roots);
-    if (c[3] != 0.) return lp_chain<3>(c, roots);
-    if (c[2] != 0.) return lp_chain<2>(c, roots);
-    if (c[1] != 0.) return lp_chain<1>(c, roots);
-    return 0;
-}
-
-// e1 = (A2 - A1) / |.|, e3 = (e1 x (A3 - A1)) / |.|, e2 = e3 x e1 of three points A1 A2 A3 (rows of A); e = rows e1 e2 e3
-__device__ __forceinline__ void lp_frame(const double (&A)[9], double (&e)[9])
-{
-    const double d[3] = {A[3] - A[0], A[4] - A[1], A[5] - A[2]}, w[3] = {A[6] - A[0], A[7] - A[1], A[8] - A[2]};
-    const double nd = sqrt(hg_dot(d, d));
-    const double e1[3] = {d[0] / nd, d[1] / nd, d[2] / nd};
-    double c[3], e2[3];
-    hg_cross(e1, w, c);
-    const double nc = sqrt(hg_dot(c, c));
-    const double e3[3] = {c[0] / nc, c[1] / nc, c[2] / nc};
-    hg_cross(e3, e1, e2);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { e[k] = e1[k]; e[3 + k] = e2[k]; e[6 + k] = e3[k]; }
-}
-
-// the candidate of root v: Rt = R (9, row-major) then t (3); false when v is no candidate
-__device__ __forceinline__ bool lp_pose(const double (&P)[9], const LpQuartic &g, double v, double (&Rt)[LP_POSE_DOUBLES])
-{
-    const double Dv = g.d0 + g.d1 * v, Nv = (g.n0 + g.n1 * v) + g.n2 * (v * v), Qv = (1. + g.q1 * v) + v * v;
-    const double u = Nv / Dv;
-    bool ok = v > 0. && Dv != 0. && u > 0. && Qv > 0.;
-    const double s1 = sqrt(g.b2 / Qv), s2 = u * s1, s3 = v * s1;
-    double Y[9], e[9], f[9];
-#pragma unroll
-    for (int k = 0; k < 3; ++k) { Y[k] = s1 * g.j[k]; Y[3 + k] = s2 * g.j[3 + k]; Y[6 + k] = s3 * g.j[6 + k]; }
-    lp_frame(P, e); lp_frame(Y, f);
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) Rt[r * 3 + c] = (f[r] * e[c] + f[3 + r] * e[3 + c]) + f[6 + r] * e[6 + c];
-        Rt[9 + r] = Y[r] - ((Rt[r * 3] * P[0] + Rt[r * 3 + 1] * P[1]) + Rt[r * 3 + 2] * P[2]);
-    }
-#pragma unroll
-    for (int k = 0; k < LP_POSE_DOUBLES; ++k) ok = ok && hg_finite(Rt[k]);
-    return ok;
-}
-
-// y = R X + t and the inlier test of the header
-__device__ __forceinline__ bool lp_inlier(const double (&Rt)[LP_POSE_DOUBLES], const double *X, const double *q, double thr2)
-{
-    const double y0 = ((Rt[0] * X[0] + Rt[1] * X[1]) + Rt[2] * X[2]) + Rt[9];
-    const double y1 = ((Rt[3] * X[0] + Rt[4] * X[1]) + Rt[5] * X[2]) + Rt[10];
-    const double y2 = ((Rt[6] * X[0] + Rt[7] * X[1]) + Rt[8] * X[2]) + Rt[11];
-    const double dx = y0 - q[0] * y2, dy = y1 - q[1] * y2;
-    return y2 > 0. && (dx * dx + dy * dy) <= thr2 * (y2 * y2);
-}
-
-// the three correspondences of iteration `it`
-__device__ __forceinline__ void lp_sample(const unsigned short *__restrict__ sub, int it, const double *cX, const double *cq,
-                                          double (&P)[9], double (&q)[6])
-{
-    const unsigned short *s5 = sub + (long long)it * 5;
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        const int v = s5[k];
-        P[3 * k] = cX[3 * v]; P[3 * k + 1] = cX[3 * v + 1]; P[3 * k + 2] = cX[3 * v + 2];
-        q[2 * k] = cq[2 * v]; q[2 * k + 1] = cq[2 * v + 1];
-    }
-}
-
-// the two reprojection residuals of one correspondence in pixels; optionally their derivatives by (w0 w1 w2 | d0 d1 d2)
-template <bool JAC>
-__device__ __forceinline__ void lp_residual(const double *R, const double *t, double scale, const double *X, const double *q,
-                                            double &rx, double &ry, double *Jx, double *Jy)
-{
-    const double a0 = (R[0] * X[0] + R[1] * X[1]) + R[2] * X[2], a1 = (R[3] * X[0] + R[4] * X[1]) + R[5] * X[2];
-    const double a2 = (R[6] * X[0] + R[7] * X[1]) + R[8] * X[2];
-    const double y0 = a0 + t[0], y1 = a1 + t[1], y2 = a2 + t[2];
-    const double ux = y0 / y2, uy = y1 / y2;
-    rx = scale * (ux - q[0]); ry = scale * (uy - q[1]);
-    if (JAC) {                                            // d y / d w_k = e_k x (R X), d y / d d = I
-        const double s = scale / y2;
-        Jx[0] = -s * (ux * a1); Jx[1] = s * (a2 + ux * a0); Jx[2] = -s * a1; Jx[3] = s; Jx[4] = 0.; Jx[5] = -s * ux;
-        Jy[0] = -s * (a2 + uy * a1); Jy[1] = s * (uy * a0); Jy[2] = s * a0; Jy[3] = 0.; Jy[4] = s; Jy[5] = -s * uy;
-    }
-}
-
-template <bool CAM>
-__global__ __launch_bounds__(256) void link_pose_kernel(const RpeLink *__restrict__ links, const int *__restrict__ m_q,
-                                                         const int *__restrict__ m_t, const int *__restrict__ m_n,
-                                                         const int *__restrict__ status, const uint8_t *__restrict__ ransac_mask,
-                                                         const uint8_t *__restrict__ pose_mask, const double *__restrict__ points,
-                                                         const double *__restrict__ Rall, const double *__restrict__ tall,
-                                                         const double2 *__restrict__ n1, const double2 *__restrict__ n2,
-                                                         const unsigned short *__restrict__ subsets, const double *__restrict__ K,
-                                                         const RpeCamSrc cam, double threshold_px, int iters, int max_iters,
-                                                         int max_matches, int kcap, int min_shared, int refine_iters,
-                                                         double *__restrict__ corr, double *__restrict__ Rout,
-                                                         double *__restrict__ tout, uint8_t *__restrict__ mask,
-                                                         int *__restrict__ counts, int *__restrict__ info, double *__restrict__ rms)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char s_lp[];
-    const bool use_lds = corr == nullptr;
-    const size_t bytesT = sizeof(unsigned) * (size_t)kcap, bytesM = sizeof(double) * LP_ROUND * 4 * LP_POSE_DOUBLES;
-    const size_t bytesA = bytesT > bytesM ? bytesT : bytesM;
-    unsigned *s_tab = (unsigned *)s_lp;                                      // [kcap], until the list is built
-    double *s_model = (double *)s_lp;                                        // [LP_ROUND * 4][12], during the rounds
-    uint8_t *s_in = (uint8_t *)s_lp;                                         // [n] the winner's inlier flags, after the election
-    double *s_red = (double *)(s_lp + ((bytesA + 15) & ~(size_t)15));        // [4 * LP_NSUM]
-    double *s_corr = s_red + 4 * LP_NSUM;                                    // [5 * max_matches] when use_lds
-    unsigned short *s_list = (unsigned short *)(s_corr + (use_lds ? 5 * (size_t)max_matches : 0));   // [LP_ROUND * 4]
-    unsigned short *s_idx = s_list + LP_ROUND * 4;                           // [max_matches rounded up to 8]
-    int *s_int = (int *)(s_idx + ((max_matches + 7) & ~7));                  // [4] wave counts, [8] bests, [4] counts
-    int *s_wc = s_int, *s_best = s_int + 4, *s_cnt = s_int + 12;
-    const int link = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
-    const RpeLink lk = links[link];
-    const long long om = (long long)link * max_matches;
-    int code = status[lk.a] == RPE_PAIR_OK ? RPE_LINKPOSE_OK : RPE_LINKPOSE_PAIR_FAILED;
-    int n = 0;
-    double *cX = use_lds ? s_corr : corr + (long long)link * 5 * max_matches, *cq = cX + 3 * (size_t)max_matches;
-    const bool a2 = (lk.side & 1) != 0, b2 = (lk.side & 2) != 0;
-    if (code == RPE_LINKPOSE_OK) {                                           // workgroup-uniform
-        // ---- join and ordered list
-        const int na = min(m_n[lk.a], max_matches), nb = min(m_n[lk.b], max_matches);
-        const long long oa = (long long)lk.a * max_matches, ob = (long long)lk.b * max_matches;
-        const int *key_a = (a2 ? m_t : m_q) + oa, *key_b = (b2 ? m_t : m_q) + ob;
-        const double2 *obs = (b2 ? n1 : n2) + ob;                            // b's point on C, its frame that is not shared
-        link_join<false>(s_tab, kcap, key_a, na, oa, key_b, nb, ob, ransac_mask, pose_mask);
-        double Ra[9], ta[3];
-#pragma unroll
-        for (int e = 0; e < 9; ++e) Ra[e] = Rall[lk.a * 9 + e];
-#pragma unroll
-        for (int e = 0; e < 3; ++e) ta[e] = tall[lk.a * 3 + e];
-        for (int i0 = 0; i0 < nb; i0 += 256) {
-            const int i = i0 + tid;
-            unsigned e = 0xFFFFFFFFu;
-            if (i < nb) { const int key = key_b[i]; if ((unsigned)key < (unsigned)kcap) e = s_tab[key]; }
-            const bool f = i < nb && (e >> 16) != LINK_NONE && (e & 0xFFFFu) == (unsigned)i;
-            const int pos = ordered_slot(f, s_wc, n);
-            if (f) {
-                double x, y, z;
-                link_point(points + (oa + (e >> 16)) * 3, Ra, ta, a2, x, y, z);
-                const double2 o = obs[i];
-                // the table and an LDS list share no bytes: s_corr lies behind region A
-                cX[3 * pos] = x; cX[3 * pos + 1] = y; cX[3 * pos + 2] = z;
-                cq[2 * pos] = o.x; cq[2 * pos + 1] = o.y;
-                s_idx[pos] = (unsigned short)i;
-            }
-        }
-        __syncthreads();                                                     // the list is complete, the table is dead
-        if (n < max(min_shared, 6)) code = RPE_LINKPOSE_TOO_FEW;
-    }
-    int win_cnt = -1, win_key = -1;
-    double thr2 = 0., scale = 0.;
-    const unsigned short *sub = subsets + (long long)n * max_iters * 5;
-    if (code == RPE_LINKPOSE_OK) {
-        scale = rpe_pair_focal<CAM>(K, cam, lk.b);
-        const double thr = threshold_px / scale;
-        thr2 = thr * thr;
-        int best_cnt = -1, best_key = -1;
-        for (int base = 0; base < iters; base += LP_ROUND) {
-            const int nr = min(LP_ROUND, iters - base);
-            __syncthreads();                                                 // the previous round's candidates have been scored
-            unsigned vm = 0;
-            if (tid < nr) {
-                double P[9], q[6], roots[4];
-                LpQuartic g;
-                lp_sample(sub, base + tid, cX, cq, P, q);
-                lp_quartic(P, q, g);
-                const int nroots = lp_roots(g.c, roots);
-#pragma unroll
-                for (int r = 0; r < 4; ++r) {
-                    double Rt[LP_POSE_DOUBLES];
-                    if (r < nroots && lp_pose(P, g, roots[r], Rt)) {
-                        double *d = s_model + (tid * 4 + r) * LP_POSE_DOUBLES;
-#pragma unroll
-                        for (int e = 0; e < LP_POSE_DOUBLES; ++e) d[e] = Rt[e];
-                        vm |= 1u << r;
-                    }
-                }
-            }
-            int total;
-            int off = block_excl_scan(__popc(vm), s_wc, total);
-#pragma unroll
-            for (int r = 0; r < 4; ++r) if (vm & (1u << r)) s_list[off++] = (unsigned short)(tid * 4 + r);
-            __syncthreads();
-            for (int j = wv; j < total; j += 4) {                            // wave-uniform
-                const int id = s_list[j];
-                double Rt[LP_POSE_DOUBLES];
-                const double *d = s_model + id * LP_POSE_DOUBLES;
-#pragma unroll
-                for (int e = 0; e < LP_POSE_DOUBLES; ++e) Rt[e] = d[e];
-                int cnt = 0;
-                for (int c = lane; c < n; c += 64) cnt += lp_inlier(Rt, cX + 3 * c, cq + 2 * c, thr2) ? 1 : 0;
-                cnt = wave_sum(cnt);
-                if (cnt > best_cnt) { best_cnt = cnt; best_key = (base + (id >> 2)) * 4 + (id & 3); }
-            }
-        }
-        elect_best(best_cnt, best_key, s_best, win_cnt, win_key);
-        if (win_key < 0) code = RPE_LINKPOSE_NONE;
-    }
-    if (code != RPE_LINKPOSE_OK) {
-        for (int i = tid; i < max_matches; i += 256) mask[om + i] = 0;
-        if (tid < 9) Rout[link * 9 + tid] = 0.;
-        if (tid < 3) tout[link * 3 + tid] = 0.;
-        if (tid < 2) rms[link * 2 + tid] = 0.;
-        if (tid == 0) {
-            counts[link * 2] = n; counts[link * 2 + 1] = 0;
-            info[link * 4] = code; info[link * 4 + 1] = 0; info[link * 4 + 2] = 0; info[link * 4 + 3] = 0;
-        }
-        return;
-    }
-    // ---- the winner again, on every thread
-    const int win_it = win_key >> 2, win_root = win_key & 3;
-    double Rt[LP_POSE_DOUBLES];
-    {
-        double P[9], q[6], roots[4];
-        LpQuartic g;
-        lp_sample(sub, win_it, cX, cq, P, q);
-        lp_quartic(P, q, g);
-        lp_roots(g.c, roots);
-        double v = roots[0];
-#pragma unroll
-        for (int r = 1; r < 4; ++r) if (r == win_root) v = roots[r];
-        lp_pose(P, g, v, Rt);
-    }
-    // its inlier flags (the candidates are dead: every wave passed the barrier of the election)
-    for (int c = tid; c < n; c += 256) s_in[c] = lp_inlier(Rt, cX + 3 * c, cq + 2 * c, thr2) ? 1 : 0;
-    __syncthreads();
-    double R[9], t[3];
-#pragma unroll
-    for (int e = 0; e < 9; ++e) R[e] = Rt[e];
-#pragma unroll
-    for (int e = 0; e < 3; ++e) t[e] = Rt[9 + e];
-    // ---- polish over the winner's inliers
-    double s[LP_NSUM];
-    auto linearise = [&]() {
-#pragma unroll
-        for (int k = 0; k < LP_NSUM; ++k) s[k] = 0.;
-        for (int c = tid; c < n; c += 256) {
-            if (!s_in[c]) continue;
-            double rx, ry, Jx[6], Jy[6];
-            lp_residual<true>(R, t, scale, cX + 3 * c, cq + 2 * c, rx, ry, Jx, Jy);
-            int q = 0;
-#pragma unroll
-            for (int u = 0; u < 6; ++u)
-#pragma unroll
-                for (int v = u; v < 6; ++v, ++q) s[q] += Jx[u] * Jx[v] + Jy[u] * Jy[v];
-#pragma unroll
-            for (int u = 0; u < 6; ++u) s[21 + u] += Jx[u] * rx + Jy[u] * ry;
-            s[27] += rx * rx + ry * ry;
-        }
-        block_sum_f64<LP_NSUM>(s, s_red, tid);
-    };
-    // R <- exp([w]x) R, t <- t + (d3 d4 d5)
-    auto trial = [&](const double (&d)[6], double (&Rn)[9], double (&tn)[3]) {
-        refine_rotate(d, R, Rn);
-#pragma unroll
-        for (int e = 0; e < 3; ++e) tn[e] = t[e] + d[3 + e];
-        double cs = 0.;
-        for (int c = tid; c < n; c += 256) {
-            if (!s_in[c]) continue;
-            double rx, ry;
-            lp_residual<false>(Rn, tn, scale, cX + 3 * c, cq + 2 * c, rx, ry, nullptr, nullptr);
-            cs += rx * rx + ry * ry;
-        }
-        return cs;
-    };
-    linearise();
-    const double cost0 = s[27];
-    double cost = cost0;
-    int lm_iters = 0, acc = 0;
-    if (isfinite(cost0)) refine_lm<6>(R, t, cost, refine_iters, s_red, linearise, RefineNormalSolve<6>{s}, trial, RefineNoCommit{}, lm_iters, acc);
-    // ---- fallback: the polished pose must be finite and keep the winner's count over all correspondences
-    const int m = win_cnt;                                                  // the winner's inliers: the residual set
-    int polish = 0;
-    if (acc > 0) {
-        double Rp[LP_POSE_DOUBLES];
-        bool fin = true;
-#pragma unroll
-        for (int e = 0; e < 9; ++e) { Rp[e] = R[e]; fin = fin && hg_finite(R[e]); }
-#pragma unroll
-        for (int e = 0; e < 3; ++e) { Rp[9 + e] = t[e]; fin = fin && hg_finite(t[e]); }
-        int cnt = 0;
-        for (int c = tid; c < n; c += 256) cnt += lp_inlier(Rp, cX + 3 * c, cq + 2 * c, thr2) ? 1 : 0;
-        cnt = block_count(cnt, s_cnt);
-        if (fin && cnt >= win_cnt) {
-            polish = lm_iters;
-            win_cnt = cnt;
-#pragma unroll
-            for (int e = 0; e < LP_POSE_DOUBLES; ++e) Rt[e] = Rp[e];
-        } else
-            polish = -1;
-    }
-    // ---- outputs: the mask by pair b's match index, the pose in pair b's convention
-    for (int i = tid; i < max_matches; i += 256) mask[om + i] = 0;
-    __syncthreads();                                                         // zeros first: another thread sets the inliers
-    for (int c = tid; c < n; c += 256)
-        if (lp_inlier(Rt, cX + 3 * c, cq + 2 * c, thr2)) mask[om + s_idx[c]] = 1;
-    if (tid == 0) {
-        double Ro[9], to[3];
-#pragma unroll
-        for (int r = 0; r < 3; ++r) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) Ro[r * 3 + c] = b2 ? Rt[c * 3 + r] : Rt[r * 3 + c];
-            to[r] = b2 ? -((Rt[r] * Rt[9] + Rt[3 + r] * Rt[10]) + Rt[6 + r] * Rt[11]) : Rt[9 + r];
-        }
-#pragma unroll
-        for (int e = 0; e < 9; ++e) Rout[link * 9 + e] = Ro[e];
-#pragma unroll
-        for (int e = 0; e < 3; ++e) tout[link * 3 + e] = to[e];
-        counts[link * 2] = n; counts[link * 2 + 1] = win_cnt;
-        info[link * 4] = RPE_LINKPOSE_OK; info[link * 4 + 1] = win_it; info[link * 4 + 2] = win_root; info[link * 4 + 3] = polish;
-        const double before = m > 0 ? sqrt(cost0 / m) : 0.;
-        rms[link * 2] = before;
-        rms[link * 2 + 1] = polish > 0 ? sqrt(cost / m) : before;
-    }
-}
-
-// dynamic LDS of link_pose_kernel for max_matches matches and kcap keypoints (the layout at the head of the kernel)
-static size_t link_pose_lds(int mm, int kcap)
-{
-    const size_t bytesA = std::max(sizeof(unsigned) * (size_t)kcap, sizeof(double) * LP_ROUND * 4 * LP_POSE_DOUBLES);
-    return ((bytesA + 15) & ~(size_t)15) + sizeof(double) * 4 * LP_NSUM + (mm <= LP_LDS_MATCHES ? sizeof(double) * 5 * (size_t)mm : 0) +
-           sizeof(unsigned short) * (LP_ROUND * 4 + (size_t)((mm + 7) & ~7)) + sizeof(int) * 32;
-}
-
-// the correspondence lists of this handle fit the kernel's LDS (else rpe_link_poses creates d_lp_corr)
-bool rpe_link_poses_in_lds(const rpe_handle *h) { return h->cfg.max_matches <= LP_LDS_MATCHES; }
-
-// the links in d_links over the last run r (its d_status / d_m_n / d_R / d_t, match indices, d_n1 / d_n2 and the structure
-// buffers) -> d_lp_*.  Above LP_LDS_MATCHES the lists go to d_lp_corr, which the caller has allocated.
-int rpe_launch_link_poses(rpe_handle *h, const RpeRun &r, int L, int iters, double threshold_px, int min_shared, int refine_iters)
-{
-    const int mm = h->cfg.max_matches, kcap = h->lay.kcap;
-    const size_t lds = link_pose_lds(mm, kcap);
-    // the most: the cut, or the largest max_matches; no table is larger than the candidates it shares region A with
-    const size_t lds_max = std::max(link_pose_lds(LP_LDS_MATCHES, 0), link_pose_lds(8064, 0));
-    if (lds > lds_max) return RPE_ERR_HIP;
-    if (lds > 65536 && raise_lds_limit(h, {(const void *)link_pose_kernel<true>, (const void *)link_pose_kernel<false>}, lds_max) != RPE_OK)
-        return RPE_ERR_HIP;
-    launch_cam(r, link_pose_kernel<true>, link_pose_kernel<false>, dim3(L), dim3(256), lds, h->stream, (const RpeLink *)h->d_links,
-               (const int *)h->d_m_q, (const int *)h->d_m_t, (const int *)h->d_m_n, (const int *)h->d_status,
-               (const uint8_t *)h->d_mask, (const uint8_t *)h->d_pose_mask, (const double *)h->d_points,
-               (const double *)h->d_R, (const double *)h->d_t, (const double2 *)h->d_n1, (const double2 *)h->d_n2,
-               (const unsigned short *)h->d_subsets, (const double *)h->d_K, r.cam, threshold_px, iters, h->cfg.ransac_max_iters,
-               mm, kcap, min_shared, refine_iters, mm <= LP_LDS_MATCHES ? (double *)nullptr : h->d_lp_corr,
-               h->d_lp_R, h->d_lp_t, h->d_lp_mask, h->d_lp_counts, h->d_lp_info, h->d_lp_rms);
-    return RPE_OK;
-}
-
-// ------------------------------------------------------------ link bundles
-// rpe_link_bundles / rpe_bundle_three_view (NOT in the reference; include/rpe_amd.h states the rule): bundle adjustment of
-// the three views of a link -- the poses of A and C relative to the shared frame S and the points both pairs see, on one
-// reprojection cost.  Two device steps, f64 throughout, no contraction:
-//   gather   (run form only) bundle_gather_kernel, one workgroup per link: link_join's table, then per match of pair a its
-//            view code (0 no point, 1 seen by S and A, 3 also by C: lp_inlier under the input pose of C), its three
-//            observations and its start point (link_point), all indexed by pair a's match index; the two start poses in
-//            the solved form (S -> A, S -> C) and the two focal scales.  The stage form uploads the same arrays.
-//   bundle   bundle_kernel, one workgroup per problem, whichever form filled the arrays: the points are compacted in index
-//            order (ordered_slot), their state (X and the trial X, 48 B per point) lives in LDS up to BA_LDS_MATCHES matches
-//            and in d_ba_state above it, walked through the same pointers in the same order; the observations are read
-//            where the gather left them.  refine_lm<11> with a solve policy of its own:
-//              linearise  U (block diagonal: 15 + 21), g_c (11) and the cost: 48 sums, parked in LDS between the trials
-//              solve      per point V = Jp'Jp + lambda diag, its adjugate inverse, W (11 x 3): 66 sums of W V^-1 W', 11 of
-//                         W V^-1 g_p and the count of singular V: 78 sums per damping trial; the reduced 11 x 11 system by
-//                         refine_solve<11> on every lane (identical operands)
-//              trial      the points' back-substitution d_p = -V^-1 (g_p + W' d_c) and the cost at the new state
-//            Every sum is block_sum_f64 over lane partials in strided order: bit-deterministic.
-// A point's Jacobians are formed three times per trial (solve, trial, and linearise after an accepted step): arithmetic is
-// small next to the barriers, and nothing per point but X is kept.
-#define BA_LDS_MATCHES 1024
-#define BA_NLIN 48                   // 15 U_AA + 21 U_CC + 11 g_c + 1 r'r
-#define BA_NRED 78                   // 66 W V^-1 W' + 11 W V^-1 g_p + 1 singular V
-
-// One point's rows of the Jacobian at the current state.  Rows: S x, S y, A x, A y, C x, C y; the C rows are zero without
-// that observation.
-struct BaPoint {
-    double e[6];                     // residuals in pixels
-    double JX[6][3];                 // by the point
-    double JA[2][5];                 // the A rows by (w0 w1 w2 | b1 b2)
-    double JC[2][6];                 // the C rows by (w0 w1 w2 | d0 d1 d2)
-};
-
-__device__ __forceinline__ void ba_point(const double (&RA)[9], const double (&tA)[3], const double (&b1)[3], const double (&b2)[3],
-                                         const double (&RC)[9], const double (&tC)[3], double fa, double fc, const double *X,
-                                         const double *q /*[6]*/, bool hc, BaPoint &p)
-{
-    {   // S: y = X
-        const double ux = X[0] / X[2], uy = X[1] / X[2], s = fa / X[2];
-        p.e[0] = fa * (ux - q[0]); p.e[1] = fa * (uy - q[1]);
-        p.JX[0][0] = s; p.JX[0][1] = 0.; p.JX[0][2] = -s * ux;
-        p.JX[1][0] = 0.; p.JX[1][1] = s; p.JX[1][2] = -s * uy;
-    }
-    double Jx[6], Jy[6];
-    lp_residual<true>(RA, tA, fa, X, q + 2, p.e[2], p.e[3], Jx, Jy);
-#pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        p.JA[0][k] = Jx[k]; p.JA[1][k] = Jy[k];
-        p.JX[2][k] = (Jx[3] * RA[k] + Jx[4] * RA[3 + k]) + Jx[5] * RA[6 + k];
-        p.JX[3][k] = (Jy[3] * RA[k] + Jy[4] * RA[3 + k]) + Jy[5] * RA[6 + k];
-    }
-    p.JA[0][3] = (Jx[3] * b1[0] + Jx[4] * b1[1]) + Jx[5] * b1[2]; p.JA[0][4] = (Jx[3] * b2[0] + Jx[4] * b2[1]) + Jx[5] * b2[2];
-    p.JA[1][3] = (Jy[3] * b1[0] + Jy[4] * b1[1]) + Jy[5] * b1[2]; p.JA[1][4] = (Jy[3] * b2[0] + Jy[4] * b2[1]) + Jy[5] * b2[2];
-    if (hc) {
-        lp_residual<true>(RC, tC, fc, X, q + 4, p.e[4], p.e[5], Jx, Jy);
-#pragma unroll
-        for (int k = 0; k < 6; ++k) { p.JC[0][k] = Jx[k]; p.JC[1][k] = Jy[k]; }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            p.JX[4][k] = (Jx[3] * RC[k] + Jx[4] * RC[3 + k]) + Jx[5] * RC[6 + k];
-            p.JX[5][k] = (Jy[3] * RC[k] + Jy[4] * RC[3 + k]) + Jy[5] * RC[6 + k];
-        }
-    } else {
-        p.e[4] = 0.; p.e[5] = 0.;
-#pragma unroll
-        for (int k = 0; k < 6; ++k) { p.JC[0][k] = 0.; p.JC[1][k] = 0.; }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) { p.JX[4][k] = 0.; p.JX[5][k] = 0.; }
-    }
-}
-
-// the squared residual length of one point over its views
-__device__ __forceinline__ double ba_cost(const double (&e)[6]) { return ((e[0] * e[0] + e[1] * e[1]) + (e[2] * e[2] + e[3] * e[3])) + (e[4] * e[4] + e[5] * e[5]); }
-
-// The point block of p under damping lambda: Vi = (Jp'Jp + lambda diag)^-1 by the adjugate (upper triangle 00 01 02 11 12
-// 22), g_p = Jp'r and W = Jc'Jp (rows 0..4: A, 5..10: C).  False when V is singular.
-__device__ __forceinline__ bool ba_block(const BaPoint &p, double lambda, double (&Vi)[6], double (&gp)[3], double (&W)[11][3])
-{
-    double v[6] = {0., 0., 0., 0., 0., 0.};
-#pragma unroll
-    for (int i = 0; i < 3; ++i) gp[i] = 0.;
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {
-        v[0] += p.JX[r][0] * p.JX[r][0]; v[1] += p.JX[r][0] * p.JX[r][1]; v[2] += p.JX[r][0] * p.JX[r][2];
-        v[3] += p.JX[r][1] * p.JX[r][1]; v[4] += p.JX[r][1] * p.JX[r][2]; v[5] += p.JX[r][2] * p.JX[r][2];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) gp[i] += p.JX[r][i] * p.e[r];
-    }
-    v[0] = v[0] + lambda * v[0]; v[3] = v[3] + lambda * v[3]; v[5] = v[5] + lambda * v[5];
-    const double c00 = v[3] * v[5] - v[4] * v[4], c01 = v[2] * v[4] - v[1] * v[5], c02 = v[1] * v[4] - v[2] * v[3];
-    const double c11 = v[0] * v[5] - v[2] * v[2], c12 = v[1] * v[2] - v[0] * v[4], c22 = v[0] * v[3] - v[1] * v[1];
-    const double det = (v[0] * c00 + v[1] * c01) + v[2] * c02;
-    Vi[0] = c00 / det; Vi[1] = c01 / det; Vi[2] = c02 / det; Vi[3] = c11 / det; Vi[4] = c12 / det; Vi[5] = c22 / det;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-#pragma unroll
-        for (int k = 0; k < 5; ++k) W[k][i] = p.JA[0][k] * p.JX[2][i] + p.JA[1][k] * p.JX[3][i];
-#pragma unroll
-        for (int k = 0; k < 6; ++k) W[5 + k][i] = p.JC[0][k] * p.JX[4][i] + p.JC[1][k] * p.JX[5][i];
-    }
-    return det > 0. && hg_finite(det);
-}
-
-// row i of the symmetric 3 x 3 held as its upper triangle, times u
-__device__ __forceinline__ double ba_sym_row(const double (&S)[6], int i, const double (&u)[3])
-{
-    const double a = i == 0 ? S[0] : (i == 1 ? S[1] : S[2]), b = i == 0 ? S[1] : (i == 1 ? S[3] : S[4]);
-    const double c = i == 0 ? S[2] : (i == 1 ? S[4] : S[5]);
-    return (a * u[0] + b * u[1]) + c * u[2];
-}
-
-// R' and -R't: the inverse of x -> R x + t, by the expression of the link poses' output
-__device__ __forceinline__ void ba_invert(const double (&R)[9], const double (&t)[3], double (&Ri)[9], double (&ti)[3])
-{
-#pragma unroll
-    for (int r = 0; r < 3; ++r) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) Ri[r * 3 + c] = R[c * 3 + r];
-        ti[r] = -((R[r] * t[0] + R[3 + r] * t[1]) + R[6 + r] * t[2]);
-    }
-}
-
-template <bool CAM>
-__global__ __launch_bounds__(256) void bundle_gather_kernel(const RpeLink *__restrict__ links, const int *__restrict__ m_q,
-                                                             const int *__restrict__ m_t, const int *__restrict__ m_n,
-                                                             const int *__restrict__ status, const uint8_t *__restrict__ ransac_mask,
-                                                             const uint8_t *__restrict__ pose_mask, const double *__restrict__ points,
-                                                             const double *__restrict__ Rall, const double *__restrict__ tall,
-                                                             const double2 *__restrict__ n1, const double2 *__restrict__ n2,
-                                                             const double *__restrict__ K, const RpeCamSrc cam,
-                                                             const double *__restrict__ Rb_in, const double *__restrict__ tb_in,
-                                                             double threshold_px, int max_matches, int kcap,
-                                                             uint8_t *__restrict__ views, double *__restrict__ obs, double *__restrict__ X0,
-                                                             double *__restrict__ pose0, double *__restrict__ focal,
-                                                             int *__restrict__ pre, int *__restrict__ n_in)
-{
-    extern __shared__ unsigned s_ba_tab[];
-    const int link = blockIdx.x, tid = threadIdx.x;
-    const RpeLink lk = links[link];
-    const long long om = (long long)link * max_matches;
-    double Rb[9], tb[3];
-    bool zero = true;
-#pragma unroll
-    for (int e = 0; e < 9; ++e) { Rb[e] = Rb_in[link * 9 + e]; zero = zero && Rb[e] == 0.; }
-#pragma unroll
-    for (int e = 0; e < 3; ++e) tb[e] = tb_in[link * 3 + e];
-    const int code = status[lk.a] != RPE_PAIR_OK ? RPE_BUNDLE_PAIR_FAILED : (zero ? RPE_BUNDLE_SKIPPED : RPE_BUNDLE_OK);
-    if (code == RPE_BUNDLE_PAIR_FAILED) {                                    // workgroup-uniform
-        for (int i = tid; i < max_matches; i += 256) {
-            views[om + i] = 0;
-            X0[(om + i) * 3] = 0.; X0[(om + i) * 3 + 1] = 0.; X0[(om + i) * 3 + 2] = 0.;
-        }
-        if (tid < 24) pose0[link * 24 + tid] = 0.;
-        if (tid < 2) focal[link * 2 + tid] = 0.;
-        if (tid == 0) { pre[link] = code; n_in[link] = 0; }
-        return;
-    }
-    const bool a2 = (lk.side & 1) != 0, b2 = (lk.side & 2) != 0;
-    const int na = min(m_n[lk.a], max_matches), nb = min(m_n[lk.b], max_matches);
-    const long long oa = (long long)lk.a * max_matches, ob = (long long)lk.b * max_matches;
-    const int *key_a = (a2 ? m_t : m_q) + oa, *key_b = (b2 ? m_t : m_q) + ob;
-    link_join<false>(s_ba_tab, kcap, key_a, na, oa, key_b, nb, ob, ransac_mask, pose_mask);
-    double Ra[9], ta[3], RtC[LP_POSE_DOUBLES];
-#pragma unroll
-    for (int e = 0; e < 9; ++e) Ra[e] = Rall[lk.a * 9 + e];
-#pragma unroll
-    for (int e = 0; e < 3; ++e) ta[e] = tall[lk.a * 3 + e];
-    {   // the solved form of C: S -> C
-        double Ri[9], ti[3];
-        ba_invert(Rb, tb, Ri, ti);
-#pragma unroll
-        for (int e = 0; e < 9; ++e) RtC[e] = b2 ? Ri[e] : Rb[e];
-#pragma unroll
-        for (int e = 0; e < 3; ++e) RtC[9 + e] = b2 ? ti[e] : tb[e];
-    }
-    const double fa = rpe_pair_focal<CAM>(K, cam, lk.a), fc = rpe_pair_focal<CAM>(K, cam, lk.b);
-    const double thr = threshold_px / fc, thr2 = thr * thr;
-    const double2 *oS = (a2 ? n2 : n1) + oa, *oA = (a2 ? n1 : n2) + oa, *oC = (b2 ? n1 : n2) + ob;
-    for (int i = tid; i < max_matches; i += 256) {
-        int v = 0;
-        double X[3] = {0., 0., 0.};
-        if (i < na && ransac_mask[oa + i] && pose_mask[oa + i]) {
-            const int key = key_a[i];
-            const unsigned e = (unsigned)key < (unsigned)kcap ? s_ba_tab[key] : 0xFFFFFFFFu;
-            if ((e >> 16) == (unsigned)i) {
-                v = 1;
-                link_point(points + (oa + i) * 3, Ra, ta, a2, X[0], X[1], X[2]);
-                double *o = obs + (om + i) * 6;
-                const double2 s = oS[i], a = oA[i];
-                o[0] = s.x; o[1] = s.y; o[2] = a.x; o[3] = a.y;
-                if ((e & 0xFFFFu) != LINK_NONE) {
-                    const double2 c = oC[e & 0xFFFFu];
-                    const double q[2] = {c.x, c.y};
-                    o[4] = c.x; o[5] = c.y;
-                    if (lp_inlier(RtC, X, q, thr2)) v = 3;
-                }
-            }
-        }
-        views[om + i] = (uint8_t)v;
-        X0[(om + i) * 3] = X[0]; X0[(om + i) * 3 + 1] = X[1]; X0[(om + i) * 3 + 2] = X[2];
-    }
-    if (tid == 0) {
-        double Ri[9], ti[3];
-        ba_invert(Ra, ta, Ri, ti);
-        double *o = pose0 + link * 24;
-#pragma unroll
-        for (int e = 0; e < 9; ++e) { o[e] = a2 ? Ri[e] : Ra[e]; o[12 + e] = RtC[e]; }
-#pragma unroll
-        for (int e = 0; e < 3; ++e) { o[9 + e] = a2 ? ti[e] : ta[e]; o[21 + e] = RtC[9 + e]; }
-        focal[link * 2] = fa; focal[link * 2 + 1] = fc;
-        pre[link] = code; n_in[link] = na;
-    }
-}
-
-// links == nullptr: the stage form, results in the solved form and in S's frame.  Otherwise the results go back into the
-// two pairs' own conventions and pair a's camera-1 frame, and a rejected bundle returns the run's own poses and points
-// (src_points / Rall / tall of pair a) and the caller's pose of pair b (Rb_in / tb_in).
-__global__ __launch_bounds__(256) void bundle_kernel(const int *__restrict__ n_in, const int *__restrict__ pre, uint8_t *__restrict__ views,
-                                                      const double *__restrict__ obs, double *__restrict__ points,
-                                                      const double *__restrict__ pose0, const double *__restrict__ focal,
-                                                      int min_shared, int max_iters, int max_matches, double *__restrict__ state,
-                                                      const RpeLink *__restrict__ links, const double *__restrict__ src_points,
-                                                      const double *__restrict__ Rall, const double *__restrict__ tall,
-                                                      const double *__restrict__ Rb_in, const double *__restrict__ tb_in,
-                                                      double *__restrict__ Ra_out, double *__restrict__ ta_out, double *__restrict__ Rb_out,
-                                                      double *__restrict__ tb_out, int *__restrict__ counts, int *__restrict__ info,
-                                                      double *__restrict__ rms)
-{
-    extern __shared__ __attribute__((aligned(16))) unsigned char s_ba[];
-    __shared__ double s_red[4 * BA_NRED], s_lin[BA_NLIN];
-    __shared__ int s_wc[4];
-    const int prob = blockIdx.x, tid = threadIdx.x;
-    const long long om = (long long)prob * max_matches;
-    double *sX = state ? state + om * 6 : (double *)s_ba, *sXn = sX + 3 * (size_t)max_matches;     // [n][3] each
-    unsigned short *s_idx = (unsigned short *)(s_ba + (state ? 0 : sizeof(double) * 6 * (size_t)max_matches));
-    const int M = min(max(n_in[prob], 0), max_matches);
-    uint8_t *vw = views + om;
-    double *pts = points + om * 3;
-    const double *ob = obs + om * 6;
-    // ---- the points in index order, their state, the counts
-    int n = 0, n3 = 0;
-    for (int i0 = 0; i0 < M; i0 += 256) {
-        const int i = i0 + tid;
-        const int v = i < M ? vw[i] : 0;
-        const int pos = ordered_slot(v != 0, s_wc, n);
-        (void)ordered_slot(v == 3, s_wc, n3);
-        if (v != 0) {
-            s_idx[pos] = (unsigned short)i;
-            sX[3 * pos] = pts[3 * i]; sX[3 * pos + 1] = pts[3 * i + 1]; sX[3 * pos + 2] = pts[3 * i + 2];
-        }
-    }
-    __syncthreads();                                                         // the list is complete
-    int code = pre[prob];
-    if (code == RPE_BUNDLE_OK && n3 < max(min_shared, 6)) code = RPE_BUNDLE_TOO_FEW;
-    if (code != RPE_BUNDLE_OK) {                                             // workgroup-uniform
-        for (int i = tid; i < max_matches; i += 256) { vw[i] = 0; pts[3 * i] = 0.; pts[3 * i + 1] = 0.; pts[3 * i + 2] = 0.; }
-        if (tid < 9) { Ra_out[prob * 9 + tid] = 0.; Rb_out[prob * 9 + tid] = 0.; }
-        if (tid < 3) { ta_out[prob * 3 + tid] = 0.; tb_out[prob * 3 + tid] = 0.; }
-        if (tid < 2) rms[prob * 2 + tid] = 0.;
-        if (tid == 0) {
-            counts[prob * 2] = n; counts[prob * 2 + 1] = n3;
-            info[prob * 4] = code; info[prob * 4 + 1] = 0; info[prob * 4 + 2] = 0; info[prob * 4 + 3] = 0;
-        }
-        return;
-    }
-    double RA[9], tA[3], RC[9], tC[3], RCn[9], tCn[3], b1[3], b2[3];
-#pragma unroll
-    for (int e = 0; e < 9; ++e) { RA[e] = pose0[prob * 24 + e]; RC[e] = pose0[prob * 24 + 12 + e]; }
-#pragma unroll
-    for (int e = 0; e < 3; ++e) { tA[e] = pose0[prob * 24 + 9 + e]; tC[e] = pose0[prob * 24 + 21 + e]; }
-    const double fa = focal[prob * 2], fc = focal[prob * 2 + 1];
-    double lam = 0.;                                                         // the damping solve() met last: trial() builds the same blocks
-    auto point = [&](int j, BaPoint &p) {
-        const int i = s_idx[j];
-        ba_point(RA, tA, b1, b2, RC, tC, fa, fc, sX + 3 * j, ob + 6 * i, vw[i] == 3, p);
-    };
-    // also leaves the tangent basis at tA in (b1, b2)
-    auto linearise = [&]() {
-        refine_basis(tA, b1, b2);
-        double s[BA_NLIN];
-#pragma unroll
-        for (int k = 0; k < BA_NLIN; ++k) s[k] = 0.;
-        for (int j = tid; j < n; j += 256) {
-            BaPoint p;
-            point(j, p);
-            int q = 0;
-#pragma unroll
-            for (int u = 0; u < 5; ++u)
-#pragma unroll
-                for (int v = u; v < 5; ++v, ++q) s[q] += p.JA[0][u] * p.JA[0][v] + p.JA[1][u] * p.JA[1][v];
-#pragma unroll
-            for (int u = 0; u < 6; ++u)
-#pragma unroll
-                for (int v = u; v < 6; ++v, ++q) s[q] += p.JC[0][u] * p.JC[0][v] + p.JC[1][u] * p.JC[1][v];
-#pragma unroll
-            for (int u = 0; u < 5; ++u) s[36 + u] += p.JA[0][u] * p.e[2] + p.JA[1][u] * p.e[3];
-#pragma unroll
-            for (int u = 0; u < 6; ++u) s[41 + u] += p.JC[0][u] * p.e[4] + p.JC[1][u] * p.e[5];
-            s[47] += ba_cost(p.e);
-        }
-        block_sum_f64<BA_NLIN>(s, s_red, tid);
-        __syncthreads();                                                     // readers of the previous s_lin are done
-        if (tid == 0) {
-#pragma unroll
-            for (int k = 0; k < BA_NLIN; ++k) s_lin[k] = s[k];
-        }
-        __syncthreads();
-    };
-    // the reduced camera system (U + lambda diag U) - sum W V^-1 W', right-hand side g_c - sum W V^-1 g_p
-    auto solve = [&](double lambda, double (&d)[11]) {
-        lam = lambda;
-        double r[BA_NRED];
-#pragma unroll
-        for (int k = 0; k < BA_NRED; ++k) r[k] = 0.;
-        for (int j = tid; j < n; j += 256) {
-            BaPoint p;
-            point(j, p);
-            double Vi[6], gp[3], W[11][3];
-            if (!ba_block(p, lambda, Vi, gp, W)) { r[77] += 1.; continue; }
-            int q = 0;
-#pragma unroll
-            for (int k = 0; k < 11; ++k) {
-                const double Y[3] = {ba_sym_row(Vi, 0, W[k]), ba_sym_row(Vi, 1, W[k]), ba_sym_row(Vi, 2, W[k])};
-#pragma unroll
-                for (int l = k; l < 11; ++l, ++q) r[q] += (Y[0] * W[l][0] + Y[1] * W[l][1]) + Y[2] * W[l][2];
-                r[66 + k] += (Y[0] * gp[0] + Y[1] * gp[1]) + Y[2] * gp[2];
-            }
-        }
-        block_sum_f64<BA_NRED>(r, s_red, tid);
-        if (r[77] != 0.) return false;
-        double g[11];
-        int q = 0;
-#pragma unroll
-        for (int k = 0; k < 11; ++k) {
-#pragma unroll
-            for (int l = k; l < 11; ++l, ++q) {
-                double u = 0.;                                               // no residual sees both cameras
-                if (k < 5 && l < 5) u = s_lin[k * 5 - k * (k - 1) / 2 + (l - k)];
-                if (k >= 5) u = s_lin[15 + (k - 5) * 6 - (k - 5) * (k - 6) / 2 + (l - k)];
-                if (l == k) u = u + lambda * u;
-                r[q] = u - r[q];
-            }
-            g[k] = s_lin[36 + k] - r[66 + k];
-        }
-        return refine_solve<11>(r, g, 0., d);
-    };
-    // RA <- exp([w]x) RA, tA <- normalise(tA + d3 b1 + d4 b2), RC <- exp([w']x) RC, tC <- tC + d', X <- X + d_p
-    auto trial = [&](const double (&d)[11], double (&RAn)[9], double (&tAn)[3]) {
-        refine_rotate(d, RA, RAn);
-#pragma unroll
-        for (int e = 0; e < 3; ++e) tAn[e] = (tA[e] + d[3] * b1[e]) + d[4] * b2[e];
-        const double nt = sqrt((tAn[0] * tAn[0] + tAn[1] * tAn[1]) + tAn[2] * tAn[2]);
-        tAn[0] /= nt; tAn[1] /= nt; tAn[2] /= nt;
-        refine_rotate(d + 5, RC, RCn);
-#pragma unroll
-        for (int e = 0; e < 3; ++e) tCn[e] = tC[e] + d[8 + e];
-        double c = 0.;
-        for (int j = tid; j < n; j += 256) {
-            BaPoint p;
-            point(j, p);
-            double Vi[6], gp[3], W[11][3];
-            ba_block(p, lam, Vi, gp, W);
-            double u[3];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) {
-                double a = gp[i];
-#pragma unroll
-                for (int k = 0; k < 11; ++k) a += W[k][i] * d[k];
-                u[i] = a;
-            }
-            double Xn[3];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) { Xn[i] = sX[3 * j + i] - ba_sym_row(Vi, i, u); sXn[3 * j + i] = Xn[i]; }
-            const double *q = ob + 6 * s_idx[j];
-            double e[6];
-            e[0] = fa * (Xn[0] / Xn[2] - q[0]); e[1] = fa * (Xn[1] / Xn[2] - q[1]);
-            lp_residual<false>(RAn, tAn, fa, Xn, q + 2, e[2], e[3], nullptr, nullptr);
-            e[4] = 0.; e[5] = 0.;
-            if (vw[s_idx[j]] == 3) lp_residual<false>(RCn, tCn, fc, Xn, q + 4, e[4], e[5], nullptr, nullptr);
-            c += ba_cost(e);
-        }
-        return c;
-    };
-    // a thread owns the same points in every pass: no barrier between its trial and its commit
-    auto commit = [&]() {
-#pragma unroll
-        for (int e = 0; e < 9; ++e) RC[e] = RCn[e];
-#pragma unroll
-        for (int e = 0; e < 3; ++e) tC[e] = tCn[e];
-        for (int j = tid; j < n; j += 256) { sX[3 * j] = sXn[3 * j]; sX[3 * j + 1] = sXn[3 * j + 1]; sX[3 * j + 2] = sXn[3 * j + 2]; }
-    };
-    linearise();
-    const double cost0 = s_lin[47];
-    double cost = cost0;
-    int iters = 0, acc = 0;
-    if (isfinite(cost0)) refine_lm<11>(RA, tA, cost, max_iters, s_red, linearise, solve, trial, commit, iters, acc);
-    // ---- the bundled state is returned only if a step was accepted, it is finite and every point lies in front of its views
-    double bad[1] = {0.};
-    if (acc > 0) {
-#pragma unroll
-        for (int e = 0; e < 9; ++e) if (!hg_finite(RA[e]) || !hg_finite(RC[e])) bad[0] = 1.;
-#pragma unroll
-        for (int e = 0; e < 3; ++e) if (!hg_finite(tA[e]) || !hg_finite(tC[e])) bad[0] = 1.;
-        for (int j = tid; j < n; j += 256) {
-            const double *X = sX + 3 * j;
-            const double zA = ((RA[6] * X[0] + RA[7] * X[1]) + RA[8] * X[2]) + tA[2], zC = ((RC[6] * X[0] + RC[7] * X[1]) + RC[8] * X[2]) + tC[2];
-            bool ok = hg_finite(X[0]) && hg_finite(X[1]) && hg_finite(X[2]) && X[2] > 0. && zA > 0.;
-            if (vw[s_idx[j]] == 3) ok = ok && zC > 0.;
-            if (!ok) bad[0] += 1.;
-        }
-        block_sum_f64<1>(bad, s_red, tid);
-    }
-    const bool take = acc > 0 && bad[0] == 0.;
-    const int nobs = 2 * n + n3;
-    // ---- outputs
-    int sa = 0, sb = 0, pa = 0;
-    if (links) { const RpeLink lk = links[prob]; sa = lk.side & 1; sb = lk.side & 2; pa = lk.a; }
-    if (take) {
-        for (int j = tid; j < n; j += 256) {
-            const double *X = sX + 3 * j;
-            double *o = pts + 3 * s_idx[j];
-            if (sa) {                                                        // pair a's camera 1 is A
-#pragma unroll
-                for (int r = 0; r < 3; ++r) o[r] = ((RA[3 * r] * X[0] + RA[3 * r + 1] * X[1]) + RA[3 * r + 2] * X[2]) + tA[r];
-            } else { o[0] = X[0]; o[1] = X[1]; o[2] = X[2]; }
-        }
-    } else if (links) {
-        for (int j = tid; j < n; j += 256) {
-            const int i = s_idx[j];
-            const double *P = src_points + ((long long)pa * max_matches + i) * 3;
-            pts[3 * i] = P[0]; pts[3 * i + 1] = P[1]; pts[3 * i + 2] = P[2];
-        }
-    }
-    if (tid == 0) {
-        double Ro[9], to[3], Ri[9], ti[3];
-        if (take || !links) {
-            if (!take) {
-#pragma unroll
-                for (int e = 0; e < 9; ++e) { RA[e] = pose0[prob * 24 + e]; RC[e] = pose0[prob * 24 + 12 + e]; }
-#pragma unroll
-                for (int e = 0; e < 3; ++e) { tA[e] = pose0[prob * 24 + 9 + e]; tC[e] = pose0[prob * 24 + 21 + e]; }
-            }
-            ba_invert(RA, tA, Ri, ti);
-#pragma unroll
-            for (int e = 0; e < 9; ++e) Ro[e] = sa ? Ri[e] : RA[e];
-#pragma unroll
-            for (int e = 0; e < 3; ++e) to[e] = sa ? ti[e] : tA[e];
-#pragma unroll
-            for (int e = 0; e < 9; ++e) Ra_out[prob * 9 + e] = Ro[e];
-#pragma unroll
-            for (int e = 0; e < 3; ++e) ta_out[prob * 3 + e] = to[e];
-            ba_invert(RC, tC, Ri, ti);
-#pragma unroll
-            for (int e = 0; e < 9; ++e) Rb_out[prob * 9 + e] = sb ? Ri[e] : RC[e];
-#pragma unroll
-            for (int e = 0; e < 3; ++e) tb_out[prob * 3 + e] = sb ? ti[e] : tC[e];
-        } else {
-#pragma unroll
-            for (int e = 0; e < 9; ++e) { Ra_out[prob * 9 + e] = Rall[pa * 9 + e]; Rb_out[prob * 9 + e] = Rb_in[prob * 9 + e]; }
-#pragma unroll
-            for (int e = 0; e < 3; ++e) { ta_out[prob * 3 + e] = tall[pa * 3 + e]; tb_out[prob * 3 + e] = tb_in[prob * 3 + e]; }
-        }
-        counts[prob * 2] = n; counts[prob * 2 + 1] = n3;
-        info[prob * 4] = take ? RPE_BUNDLE_OK : RPE_BUNDLE_REJECTED; info[prob * 4 + 1] = iters; info[prob * 4 + 2] = acc; info[prob * 4 + 3] = 0;
-        const double before = sqrt(cost0 / nobs);
-        rms[prob * 2] = before;
-        rms[prob * 2 + 1] = take ? sqrt(cost / nobs) : before;
-    }
-}
-
-// dynamic LDS of bundle_kernel: the point state up to the cut, then the index list
-static size_t bundle_lds(int mm) { return (mm <= BA_LDS_MATCHES ? sizeof(double) * 6 * (size_t)mm : 0) + sizeof(unsigned short) * (size_t)((mm + 7) & ~7); }
-
-// the point state of this handle fits the kernel's LDS (else the callers create d_ba_state)
-bool rpe_bundles_in_lds(const rpe_handle *h) { return h->cfg.max_matches <= BA_LDS_MATCHES; }
-
-// n problems whose arrays are in d_ba_* (the stage form uploaded them, or the gather below wrote them) -> d_ba_* results
-void rpe_launch_bundle(rpe_handle *h, int n, int min_shared, int max_iters, bool links)
-{
-    const int mm = h->cfg.max_matches;
-    hipLaunchKernelGGL(bundle_kernel, dim3(n), dim3(256), bundle_lds(mm), h->stream, (const int *)h->d_ba_n, (const int *)h->d_ba_pre,
-                       h->d_ba_views, (const double *)h->d_ba_obs, h->d_ba_points, (const double *)h->d_ba_pose0, (const double *)h->d_ba_focal,
-                       min_shared, max_iters, mm, mm <= BA_LDS_MATCHES ? (double *)nullptr : h->d_ba_state,
-                       links ? (const RpeLink *)h->d_links : (const RpeLink *)nullptr, (const double *)h->d_points,
-                       (const double *)h->d_R, (const double *)h->d_t, (const double *)h->d_ba_Rin, (const double *)h->d_ba_tin,
-                       h->d_ba_Ra, h->d_ba_ta, h->d_ba_Rb, h->d_ba_tb, h->d_ba_counts, h->d_ba_info, h->d_ba_rms);
-}
-
-// the links in d_links over the last run r, the callers' poses of pair b in d_ba_Rin / d_ba_tin -> the problems' arrays
-int rpe_launch_bundle_gather(rpe_handle *h, const RpeRun &r, int L, double threshold_px)
-{
-    const int mm = h->cfg.max_matches, kcap = h->lay.kcap;
-    const size_t lds = sizeof(unsigned) * (size_t)kcap;
-    // the table is all of the kernel's LDS: the largest (uncapped SIFT, 16384 entries) is exactly the 64 KB a kernel gets
-    // without the function attribute
-    if (lds > 65536) return RPE_ERR_HIP;
-    launch_cam(r, bundle_gather_kernel<true>, bundle_gather_kernel<false>, dim3(L), dim3(256), lds, h->stream, (const RpeLink *)h->d_links,
-               (const int *)h->d_m_q, (const int *)h->d_m_t, (const int *)h->d_m_n, (const int *)h->d_status,
-               (const uint8_t *)h->d_mask, (const uint8_t *)h->d_pose_mask, (const double *)h->d_points,
-               (const double *)h->d_R, (const double *)h->d_t, (const double2 *)h->d_n1, (const double2 *)h->d_n2,
-               (const double *)h->d_K, r.cam, (const double *)h->d_ba_Rin, (const double *)h->d_ba_tin, threshold_px, mm, kcap,
-               h->d_ba_views, h->d_ba_obs, h->d_ba_points, h->d_ba_pose0, h->d_ba_focal, h->d_ba_pre, h->d_ba_n);
     return RPE_OK;
 }

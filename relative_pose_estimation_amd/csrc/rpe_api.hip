@@ -421,7 +421,7 @@ extern "C" int rpe_create(const rpe_config *cfg, rpe_handle **out)
         g_create_err = "SIFT: nfeatures must be 0 (no cap: cv2's SIFT_create()) or a cap <= 16320, and the image <= 4000 px"; return RPE_ERR_INVALID;
     }
     if (cfg->width < 96 || cfg->height < 96 || cfg->width > 4095 || cfg->height > 4095 || cfg->max_batch < 1 ||
-        (!is_sift && (cfg->nfeatures < 1 || cfg->nfeatures > 8000)) || cfg->max_matches < 5 || cfg->max_matches > 8064 ||
+        (!is_sift && (cfg->nfeatures < 1 || cfg->nfeatures > 8000)) || cfg->max_matches < 5 || cfg->max_matches > RPE_MAX_MATCHES_LIMIT ||
         cfg->ransac_max_iters < 1 || cfg->ransac_max_iters > 4096 || cfg->fast_threshold < 1 || cfg->fast_threshold > 254) {
         g_create_err = "configuration out of supported range"; return RPE_ERR_INVALID;
     }
@@ -1044,7 +1044,7 @@ static int links_begin(rpe_handle *h, const char *who, int L, const int32_t *pai
     const RpeLastRun &l = h->last;
     const bool list = l.kind == RpeLastRun::LIST;
     if (!list && l.run.feat.img2_base != 1) { h->err = w + ": the pairs of a batch share no frame (links join the pairs of a stream or of a pair list)"; return RPE_ERR_INVALID; }
-    if (L > 4 * h->cfg.max_batch) { h->err = w + ": more than 4*max_batch links in one call"; return RPE_ERR_CAPACITY; }
+    if (L > rpe_link_capacity(h)) { h->err = w + ": more than 4*max_batch links in one call"; return RPE_ERR_CAPACITY; }
     std::vector<RpeLink> &tbl = h->link_tab;                // outlives the call: the upload below is asynchronous
     tbl.assign((size_t)L, RpeLink{0, 0, 0, 0});
     for (int i = 0; i < L; ++i) {
@@ -1060,7 +1060,7 @@ static int links_begin(rpe_handle *h, const char *who, int L, const int32_t *pai
     }
     if (L == 0) return RPE_OK;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    DM_ONCE(h, h->d_links, (size_t)4 * h->cfg.max_batch);
+    DM_ONCE(h, h->d_links, (size_t)rpe_link_capacity(h));
     if ((rc = last_run_structure(h, l.pairs, false)) != RPE_OK) return rc;
     HIPCHK(h, hipMemcpyAsync(h->d_links, tbl.data(), sizeof(RpeLink) * (size_t)L, hipMemcpyHostToDevice, h->stream));
     return RPE_OK;
@@ -1072,10 +1072,10 @@ extern "C" int rpe_scale_links(rpe_handle *h, int L, const int32_t *pair_a, cons
     if (!h) return rpe_invalid(h, "rpe_scale_links");
     int rc = links_begin(h, "rpe_scale_links", L, pair_a, pair_b, side, min_shared);
     if (rc != RPE_OK || L == 0) return rc;
-    const size_t lcap = (size_t)4 * h->cfg.max_batch;
+    const size_t lcap = (size_t)rpe_link_capacity(h);
     DM_ONCE(h, h->d_link_stats, lcap * 3);
     DM_ONCE(h, h->d_link_n, lcap); DM_ONCE(h, h->d_link_code, lcap);
-    if ((rc = rpe_launch_scale_links(h, L, min_shared)) != RPE_OK) { h->err = "rpe_scale_links: could not size the kernel's LDS"; return rc; }
+    if ((rc = rpe_launch_scale_links(h, L, min_shared)) != RPE_OK) return rpe_lds_unsized(h, "rpe_scale_links", rc);
     HIPCHK(h, hipGetLastError());
     return fetch(h, {{stats, h->d_link_stats, sizeof(double) * 3 * (size_t)L}, {n_shared, h->d_link_n, sizeof(int) * (size_t)L},
                      {code, h->d_link_code, sizeof(int) * (size_t)L}});
@@ -1093,11 +1093,11 @@ extern "C" int rpe_link_poses(rpe_handle *h, int L, const int32_t *pair_a, const
     if (refine_iters < 0 || refine_iters > 100) return rpe_invalid(h, "rpe_link_poses", "refine_iters must be 0 ... 100");
     rc = links_begin(h, "rpe_link_poses", L, pair_a, pair_b, side, min_shared);
     if (rc != RPE_OK || L == 0) return rc;
-    const size_t lcap = (size_t)4 * h->cfg.max_batch, mm = (size_t)h->cfg.max_matches;
+    const size_t lcap = (size_t)rpe_link_capacity(h), mm = (size_t)h->cfg.max_matches;
     DM_ONCE(h, h->d_lp_R, lcap * 9); DM_ONCE(h, h->d_lp_t, lcap * 3); DM_ONCE(h, h->d_lp_rms, lcap * 2);
     DM_ONCE(h, h->d_lp_counts, lcap * 2); DM_ONCE(h, h->d_lp_info, lcap * 4); DM_ONCE(h, h->d_lp_mask, lcap * mm);
     if (!rpe_link_poses_in_lds(h)) DM_ONCE(h, h->d_lp_corr, lcap * 5 * mm);
-    if ((rc = rpe_launch_link_poses(h, h->last.run, L, iters, threshold_px, min_shared, refine_iters)) != RPE_OK) { h->err = "rpe_link_poses: could not size the kernel's LDS"; return rc; }
+    if ((rc = rpe_launch_link_poses(h, h->last.run, L, iters, threshold_px, min_shared, refine_iters)) != RPE_OK) return rpe_lds_unsized(h, "rpe_link_poses", rc);
     HIPCHK(h, hipGetLastError());
     const size_t n = (size_t)L;
     return fetch(h, {{R, h->d_lp_R, sizeof(double) * 9 * n}, {t, h->d_lp_t, sizeof(double) * 3 * n}, {mask, h->d_lp_mask, n * mm},
@@ -1107,7 +1107,7 @@ extern "C" int rpe_link_poses(rpe_handle *h, int L, const int32_t *pair_a, const
 // link bundles: the buffers of both forms on first use
 static int bundle_alloc(rpe_handle *h)
 {
-    const size_t lcap = (size_t)4 * h->cfg.max_batch, mm = (size_t)h->cfg.max_matches;
+    const size_t lcap = (size_t)rpe_link_capacity(h), mm = (size_t)h->cfg.max_matches;
     DM_ONCE(h, h->d_ba_views, lcap * mm); DM_ONCE(h, h->d_ba_obs, lcap * mm * 6); DM_ONCE(h, h->d_ba_points, lcap * mm * 3);
     DM_ONCE(h, h->d_ba_pose0, lcap * 24); DM_ONCE(h, h->d_ba_focal, lcap * 2); DM_ONCE(h, h->d_ba_n, lcap); DM_ONCE(h, h->d_ba_pre, lcap);
     DM_ONCE(h, h->d_ba_Rin, lcap * 9); DM_ONCE(h, h->d_ba_tin, lcap * 3);
@@ -1151,7 +1151,7 @@ extern "C" int rpe_link_bundles(rpe_handle *h, int L, const int32_t *pair_a, con
     if ((rc = bundle_alloc(h)) != RPE_OK) return rc;
     HIPCHK(h, hipMemcpyAsync(h->d_ba_Rin, R0, sizeof(double) * 9 * n, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->d_ba_tin, t0, sizeof(double) * 3 * n, hipMemcpyHostToDevice, h->stream));
-    if ((rc = rpe_launch_bundle_gather(h, h->last.run, L, threshold_px)) != RPE_OK) { h->err = "rpe_link_bundles: could not size the kernel's LDS"; return rc; }
+    if ((rc = rpe_launch_bundle_gather(h, h->last.run, L, threshold_px)) != RPE_OK) return rpe_lds_unsized(h, "rpe_link_bundles", rc);
     rpe_launch_bundle(h, L, min_shared, max_iters, true);
     HIPCHK(h, hipGetLastError());
     // the wait also covers the upload: the poses have left the caller's arrays
@@ -1538,8 +1538,7 @@ static int homography_run(rpe_handle *h, const RpeRun &r, int iters, double thre
                           uint8_t *mask, int32_t *counts, int32_t *info)
 {
     const size_t B = (size_t)r.pairs;
-    int rc = rpe_launch_homography(h, r, iters, threshold_px, from_batch);
-    if (rc != RPE_OK) { h->err = "homography: could not size the kernel's LDS"; return rc; }
+    if (int rc = rpe_launch_homography(h, r, iters, threshold_px, from_batch)) return rpe_lds_unsized(h, "homography", rc);
     HIPCHK(h, hipGetLastError());
     return fetch(h, {{H, h->d_hg_H, sizeof(double) * 9 * B}, {R_rot, h->d_hg_R, sizeof(double) * 9 * B}, {mask, h->d_hg_mask, B * h->cfg.max_matches},
                      {counts, h->d_hg_counts, sizeof(int) * 3 * B}, {info, h->d_hg_info, sizeof(int) * 4 * B}});
@@ -1953,7 +1952,7 @@ static int upload_points(rpe_handle *h, const float *p1, const float *p2, const 
 // rpe_*_cameras (NOT in the reference): a camera per frame instead of one K per call.  The entry points validate, place
 // the camera records where the kernels find them -- 2 B records per batch / stage call in d_batch_cams, one record per
 // frame-store slot in fs.d_cam -- and name them in the camera source of the run they launch, which makes the launchers of
-// geom_kernels.hip take the camera instances.
+// geom_kernels.hip and link_kernels.hip take the camera instances (launch_cam, geom_device.h).
 static int check_cameras(rpe_handle *h, const rpe_camera *c, int n, const char *who)
 {
     for (int i = 0; i < n; ++i) {

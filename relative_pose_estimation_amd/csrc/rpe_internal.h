@@ -20,6 +20,8 @@
 #define RPE_MATCH_SPLIT_PAIRS 64   // batches up to this many pairs split a pair's Hamming matching over several workgroups
 #define RPE_GUIDED_LDS_UINT4 128    // the guided matcher's part of the first LDS region: 2 x 32 scanned records of 32 bytes
 #define RPE_TAB_RING 4            // pinned pieces the slot tables of rpe_frames_put* / rpe_enqueue_pairs rotate through
+#define RPE_MAX_MATCHES_LIMIT 8064   // the largest cfg.max_matches rpe_create accepts: the most any kernel's LDS is sized for
+#define RPE_CU_LDS_BYTES (160 * 1024)   // LDS of one gfx950 CU: the most a workgroup can ask for
 // one pair's results, section by section of the result block (d_resblk): R, t, inliers, status, n_matches
 #define RPE_RESULT_SECTIONS 5
 static const size_t kRpeResultElem[RPE_RESULT_SECTIONS] = {9 * sizeof(double), 3 * sizeof(double), sizeof(int), sizeof(int), sizeof(int)};
@@ -275,7 +277,8 @@ struct RpeSiftState;
 struct RpeFeatSrc { const uint8_t *desc; const int *count; const float2 *pt; const int2 *norm; const int2 *tab; int img2_base; };
 
 // What one launch sequence operates on.  The entry points build it (rpe_run_batch / rpe_run_stream / rpe_run_list below)
-// and hand it to the launchers of match_kernels.hip and geom_kernels.hip, which read nothing of it from the handle.
+// and hand it to the launchers of match_kernels.hip, geom_kernels.hip and link_kernels.hip, which read nothing of it from
+// the handle.
 struct RpeRun {
     int pairs;
     RpeFeatSrc feat;
@@ -314,6 +317,18 @@ static inline int rpe_track_scan_blocks(int N) { return (int)(((long long)N + 20
 
 // One rpe_scale_links link on the device: pairs a and b of the last run, side bit 0 / 1 = the shared frame is image 2 of a / of b
 struct RpeLink { int a, b, side, pad; };
+// What the link kernels (link_kernels.hip) read of the last run, by value (rpe_link_src fills it from the handle): the link
+// table; the run's match lists, status, the two structure masks, points and poses; its normalised points; the capacities
+// of a pair's match arrays and of a frame's keypoints.  Everything is indexed from the workgroup's link, so the link, the
+// two pairs' status, counts and poses are uniform scalar loads.
+struct RpeLinkSrc {
+    const RpeLink *links;
+    const int *m_q, *m_t, *m_n, *status;
+    const uint8_t *ransac_mask, *pose_mask;
+    const double *points, *R, *t;
+    const double2 *n1, *n2;
+    int max_matches, kcap;
+};
 
 struct rpe_handle {
     rpe_config cfg;
@@ -433,8 +448,8 @@ struct rpe_handle {
     int *d_tk_node = nullptr, *d_tk_seen = nullptr;
     int tk_nodes = 0, tk_frames = 0;
     std::vector<int> tk_frame_tab;        // host side of d_tk_frames: source of its upload
-    // the kernels of geom_kernels.hip whose dynamic-LDS limit a launch of this handle has raised (raise_lds_limit): the
-    // attribute is per device, so the record is per handle
+    // the kernels of geom_kernels.hip and link_kernels.hip whose dynamic-LDS limit a launch of this handle has raised
+    // (raise_lds_limit, geom_device.h): the attribute is per device, so the record is per handle
     std::vector<const void *> lds_raised;
     // results
     double *d_R = nullptr, *d_t = nullptr, *d_E = nullptr;
@@ -510,6 +525,13 @@ static inline int rpe_invalid(rpe_handle *h, const char *who, const char *what =
     return RPE_ERR_INVALID;
 }
 
+// The refusal of a launcher that could not raise or fit its kernel's dynamic LDS (rc: what it returned)
+static inline int rpe_lds_unsized(rpe_handle *h, const char *who, int rc)
+{
+    h->err = std::string(who) + ": could not size the kernel's LDS";
+    return rc;
+}
+
 // The runs.  `cam` defaults to the shared K; a camera source must address its records as the run addresses its images.
 static inline RpeRun rpe_run_rule(const rpe_handle *h, int pairs, int img2_base, RpeCamSrc cam)
 {
@@ -523,6 +545,15 @@ static inline RpeRun rpe_run_stream(const rpe_handle *h, int pairs, RpeCamSrc ca
 static inline RpeRun rpe_run_list(const rpe_handle *h, int P, RpeCamSrc cam = {nullptr, nullptr, 0})
 {
     return {P, {h->fs.d_desc, h->fs.d_count, h->fs.d_kp_pt, h->fs.d_norm, (const int2 *)h->d_pairtab, 0}, cam};
+}
+
+// The links one call may carry, and the entries of d_links and of every per-link buffer
+static inline int rpe_link_capacity(const rpe_handle *h) { return 4 * h->cfg.max_batch; }
+// The link kernels' source: the table in d_links over the last run's buffers
+static inline RpeLinkSrc rpe_link_src(const rpe_handle *h)
+{
+    return {h->d_links, h->d_m_q, h->d_m_t, h->d_m_n, h->d_status, h->d_mask, h->d_pose_mask, h->d_points, h->d_R, h->d_t,
+            h->d_n1, h->d_n2, h->cfg.max_matches, h->lay.kcap};
 }
 
 // ---- kernel launchers (defined in the .hip files) --------------------------

@@ -23,7 +23,6 @@
 #include "pose_triangulate.h"
 #include "geom_device.h"
 #include <float.h>
-#include <stdlib.h>
 #include <algorithm>
 
 // ------------------------------------------------ polynomial bookkeeping
@@ -797,17 +796,8 @@ void rpe_launch_ransac(rpe_handle *h, const RpeRun &r, bool want_mask)
     const int use_lds = mm <= 2048;
     const size_t lds = use_lds ? sizeof(double2) * 2 * (size_t)mm : 0;
     static_assert(RPE_RANSAC_FIRST_CHUNK % POLY_LANES == 0 && RPE_RANSAC_FIRST_CHUNK % SCORE_GROUP == 0 && (RPE_RANSAC_FIRST_CHUNK * RG) % 256 == 0, "chunk granularity");
-    // experiment hook: RPE_RANSAC_SCHEDULE="32,96,384,512" replaces the chunk schedule (multiples of 32, <= 512; the last
-    // entry repeats)
-    static std::vector<int> env_sched = [] {
-        std::vector<int> v;
-        if (const char *e = getenv("RPE_RANSAC_SCHEDULE")) {
-            for (const char *q = e; *q;) { const int c = atoi(q); if (c >= 32 && c <= RPE_RANSAC_MAXCHUNK && c % 32 == 0) v.push_back(c); while (*q && *q != ',') ++q; if (*q) ++q; }
-        }
-        return v;
-    }();
-    static const int kSchedule[] = {RPE_RANSAC_FIRST_CHUNK, 96, 384, RPE_RANSAC_MAXCHUNK};
-    int done_iters = 0, chunk = env_sched.empty() ? kSchedule[0] : env_sched[0], nlaunch = 0;
+    static const int kSchedule[] = {RPE_RANSAC_FIRST_CHUNK, 96, 384, RPE_RANSAC_MAXCHUNK};      // the last entry repeats
+    int done_iters = 0, chunk = kSchedule[0], nlaunch = 0;
     while (done_iters < it) {
         hipLaunchKernelGGL(ransac_poly_kernel, dim3(B, chunk / POLY_LANES), dim3(POLY_LANES), 0, h->stream,
                            n1, n2, h->d_rstate, h->d_subsets, h->d_hyp, h->d_nmodels, mm, it);
@@ -821,8 +811,7 @@ void rpe_launch_ransac(rpe_handle *h, const RpeRun &r, bool want_mask)
                            (const double *)h->d_nit_denom, (const int *)h->d_nit_round, h->nit_num, h->d_E, h->d_found, chunk, B);
         done_iters += chunk;
         ++nlaunch;
-        if (!env_sched.empty()) chunk = env_sched[std::min((size_t)nlaunch, env_sched.size() - 1)];
-        else chunk = kSchedule[std::min(nlaunch, 3)];
+        chunk = kSchedule[std::min(nlaunch, 3)];
     }
     if (want_mask) launch_mask(h, r, (const int *)nullptr);
 }

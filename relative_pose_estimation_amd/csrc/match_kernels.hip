@@ -4,26 +4,26 @@
 // + sorted(key=distance) + [:max_matches]   (reference src/core/pose_estimator.py:131,:144-151)
 // and the point gather of :518-519 (fused epilogue).
 //
-// One workgroup (256 lanes) per image pair.  Each lane owns one train descriptor
-// (8 dwords in VGPRs); query descriptors are staged through LDS in 1024-row tiles
-// with coalesced 16-B loads and read back as wave-uniform (broadcast) ds_read_b128;
-// distance = 8 x (v_xor_b32 + v_bcnt_u32_b32).  Selection follows
-// core/batch_distance.cpp (crosscheck=true) of OpenCV >= 4.5.x, two passes: every train elects its nearest query
-// (strict '<', ascending query => lowest index on ties) and every query keeps its best elector through a packed
-// (dist<<18 | trainIdx) LDS atomicMin (lowest train on ties); then every query finds its OWN nearest train (same
+// Every configuration has one kernel path.  crossCheck (Hamming and L2) runs on the matrix cores, one workgroup per
+// image pair or per tile of one (match_hamming_mfma_kernel, match_l2_mfma_kernel, and the guided kernels next to them).
+// Selection follows core/batch_distance.cpp (crosscheck=true) of OpenCV >= 4.5.x, two elections: every train elects its
+// nearest query (strict '<', ascending query => lowest index on ties) and every query keeps its best elector as a packed
+// (dist<<18 | trainIdx) word under atomicMin (lowest train on ties); every query also finds its OWN nearest train (same
 // key, lowest train on ties) and the match survives only if that train elected the query -- the two keys are
-// equal exactly then.  (The vector-ALU kernel below scans twice; the matrix-core kernel takes both elections from one
-// pass over the product tiles.)  (Rounds 1-2 ran the first pass only, the rule of older OpenCV: a superset.  The reference's
-// result rows single out the two-pass rule: tests/test_reference_rows_cpu.py.)
+// equal exactly then.  The matrix-core kernels take both elections from one pass over the product tiles.  (Rounds 1-2
+// ran the first election only, the rule of older OpenCV: a superset.  The reference's result rows single out the
+// two-election rule: tests/test_reference_rows_cpu.py.)
 // The stable sort by distance is a bitonic sort of (dist<<16 | queryIdx) keys in LDS.
 //
-// RATIO = true is the opt-in extension named by the project brief and absent from the reference (which uses
-// crossCheck, pose_estimator.py:131): cv2's knnMatch(k=2) + Lowe's ratio test.  Roles swap: a lane owns a QUERY
-// descriptor, the TRAIN descriptors stream through LDS; the lane keeps its best (distance, lowest train index) and
-// second-best distance and emits the match iff  best < ratio * second  (compared in f64, as Python compares
-// m.distance < ratio * n.distance); queries with fewer than two candidates emit nothing.
+// The Lowe-ratio mode is the opt-in extension named by the project brief and absent from the reference (which uses
+// crossCheck, pose_estimator.py:131): cv2's knnMatch(k=2) + Lowe's ratio test.  It runs on the vector ALU, and these
+// are the only vector-ALU matchers (match_hamming_ratio_kernel: 8 x (v_xor_b32 + v_bcnt_u32_b32) per distance;
+// match_l2_ratio_kernel): a lane owns a QUERY descriptor, the TRAIN descriptors stream through LDS; the lane keeps its
+// best (distance, lowest train index) and second-best distance and emits the match iff  best < ratio * second
+// (compared in f64, as Python compares m.distance < ratio * n.distance); queries with fewer than two candidates emit
+// nothing.
 //
-// What the file shares.  Every matcher -- the vector-ALU kernel, the fused matrix-core and guided kernels, the Hamming and
+// What the file shares.  Every matcher -- the ratio kernels, the fused matrix-core and guided kernels, the Hamming and
 // the L2 select kernels -- ends in ONE tail, select_sort_emit<NT, Key>: keys from the election words, their count, the
 // bitonic sort, the first max_matches ranks with the point gather (MatchOut), m_n.  A caller states only which query
 // survives (the ratio flag, best == row, the raw row key's conversion, nn_q[nn_t[i]] == i) and where its train index is.
@@ -32,7 +32,6 @@
 // and whether the election words live in LDS (fused kernel) or in HBM (tile kernel + match_hamming_select_kernel) are decided
 // there, for both launchers (launch_hamming_plan) and for the allocation of the HBM words (rpe_api.hip).
 #include "rpe_internal.h"
-#include <stdlib.h>
 #include <algorithm>
 
 #define QTILE 1024
@@ -118,85 +117,54 @@ __device__ __forceinline__ void select_sort_emit(Key *s_key, int n1, int max_mat
 // The Hamming matchers' sort key of query i from its election word b = (dist << 18 | trainIdx)
 __device__ __forceinline__ unsigned ham_sort_key(unsigned b, int i) { return ((b >> 18) << 16) | (unsigned)i; }
 
-template <bool RATIO, bool TAB>
-__global__ __launch_bounds__(256) void match_hamming_kernel(const uint8_t *__restrict__ desc, const int *__restrict__ kp_count,
-                                                             const float2 *__restrict__ kp_pt, int img2_base, const int2 *__restrict__ pair_tab, int kcap,
-                                                             int max_matches, double ratio,
-                                                             int *__restrict__ m_q, int *__restrict__ m_t, int *__restrict__ m_d,
-                                                             int *__restrict__ m_n, float2 *__restrict__ pts1, float2 *__restrict__ pts2)
+// The Lowe-ratio Hamming matcher: one workgroup (256 lanes) per pair, a lane owns one QUERY descriptor (8 dwords in
+// registers), the train descriptors stream through LDS in QTILE-row tiles and are read back as wave-uniform ds_read_b128.
+template <bool TAB>
+__global__ __launch_bounds__(256) void match_hamming_ratio_kernel(const uint8_t *__restrict__ desc, const int *__restrict__ kp_count,
+                                                                   const float2 *__restrict__ kp_pt, int img2_base, const int2 *__restrict__ pair_tab, int kcap,
+                                                                   int max_matches, double ratio,
+                                                                   int *__restrict__ m_q, int *__restrict__ m_t, int *__restrict__ m_d,
+                                                                   int *__restrict__ m_n, float2 *__restrict__ pts1, float2 *__restrict__ pts2)
 {
     extern __shared__ uint4 s_dyn[];
-    uint4 *s_q = s_dyn;                                   // QTILE*2 uint4 = 32 KB (later: sort keys)
-    unsigned *s_best = (unsigned *)(s_dyn + QTILE * 2);   // kcap entries
-    unsigned *s_row = s_best + kcap;                      // kcap entries: the query's own nearest train (second crossCheck pass)
+    uint4 *s_t = s_dyn;                                   // QTILE*2 uint4 = 32 KB (later: sort keys)
+    unsigned *s_best = (unsigned *)(s_dyn + QTILE * 2);   // kcap entries: (dist << 18 | trainIdx) where the ratio test passed
     const int tid = threadIdx.x, pair = blockIdx.x;
     int img1, img2;
     rpe_pair_slots<TAB>(pair_tab, img2_base, pair, img1, img2);
     const int n1 = min(kp_count[img1], kcap), n2 = min(kp_count[img2], kcap);
-    for (int i = tid; i < n1; i += 256) { s_best[i] = 0xFFFFFFFFu; if (!RATIO) s_row[i] = 0xFFFFFFFEu; }      // ratio mode: no s_row (and no LDS for it)
+    for (int i = tid; i < n1; i += 256) s_best[i] = 0xFFFFFFFFu;
     const uint4 *d1 = (const uint4 *)(desc + (long long)img1 * kcap * 32);
     const uint4 *d2 = (const uint4 *)(desc + (long long)img2 * kcap * 32);
-    // owner descriptors (one per lane, in registers) x scanned descriptors (through LDS):
-    // crossCheck pass 0: owner = train j, scanned = queries; pass 1 and ratio: owner = query i, scanned = trains
-#pragma unroll 1
-    for (int pass = 0; pass < (RATIO ? 1 : 2); ++pass) {
-    const bool qown = RATIO || pass == 1;
-    const uint4 *d_own = qown ? d1 : d2, *d_scan = qown ? d2 : d1;
-    const int n_own = qown ? n1 : n2, n_scan = qown ? n2 : n1;
-    for (int tc = 0; tc < n_own; tc += 256) {
-        const int j = tc + tid;
-        const bool valid = j < n_own;
-        uint4 t0 = make_uint4(0, 0, 0, 0), t1 = t0;
-        if (valid) { t0 = d_own[2 * j]; t1 = d_own[2 * j + 1]; }
-        int bestd = 0x7FFFFFFF, besti = 0, second = 0x7FFFFFFF;
-        for (int qt = 0; qt < n_scan; qt += QTILE) {
-            const int nq = min(QTILE, n_scan - qt);
+    for (int qc = 0; qc < n1; qc += 256) {
+        const int i = qc + tid;
+        const bool valid = i < n1;
+        uint4 q0 = make_uint4(0, 0, 0, 0), q1 = q0;
+        if (valid) { q0 = d1[2 * i]; q1 = d1[2 * i + 1]; }
+        int bestd = 0x7FFFFFFF, bestj = 0, second = 0x7FFFFFFF;
+        for (int tt = 0; tt < n2; tt += QTILE) {
+            const int nt = min(QTILE, n2 - tt);
             __syncthreads();
-            for (int idx = tid; idx < nq * 2; idx += 256) s_q[idx] = d_scan[2 * qt + idx];
+            for (int idx = tid; idx < nt * 2; idx += 256) s_t[idx] = d2[2 * tt + idx];
             __syncthreads();
-            int i = 0;
-            if (!RATIO) {
-                for (; i + 4 <= nq; i += 4) {
-                    int da = ham256(s_q[2 * i], s_q[2 * i + 1], t0, t1);
-                    int db = ham256(s_q[2 * i + 2], s_q[2 * i + 3], t0, t1);
-                    int dc = ham256(s_q[2 * i + 4], s_q[2 * i + 5], t0, t1);
-                    int dd = ham256(s_q[2 * i + 6], s_q[2 * i + 7], t0, t1);
-                    if (da < bestd) { bestd = da; besti = qt + i; }
-                    if (db < bestd) { bestd = db; besti = qt + i + 1; }
-                    if (dc < bestd) { bestd = dc; besti = qt + i + 2; }
-                    if (dd < bestd) { bestd = dd; besti = qt + i + 3; }
-                }
-                for (; i < nq; ++i) {
-                    int da = ham256(s_q[2 * i], s_q[2 * i + 1], t0, t1);
-                    if (da < bestd) { bestd = da; besti = qt + i; }
-                }
-            } else {
-                for (; i < nq; ++i) {
-                    const int da = ham256(s_q[2 * i], s_q[2 * i + 1], t0, t1);
-                    if (da < bestd) { second = bestd; bestd = da; besti = qt + i; }
-                    else if (da < second) second = da;
-                }
+            for (int j = 0; j < nt; ++j) {
+                const int da = ham256(s_t[2 * j], s_t[2 * j + 1], q0, q1);
+                if (da < bestd) { second = bestd; bestd = da; bestj = tt + j; }
+                else if (da < second) second = da;
             }
         }
-        if (!RATIO) {
-            if (valid && n_scan > 0) {
-                if (pass == 0) atomicMin(&s_best[besti], ((unsigned)bestd << 18) | (unsigned)j);
-                else s_row[j] = ((unsigned)bestd << 18) | (unsigned)besti;   // owner j is the query, besti its nearest train
-            }
-        } else if (valid && n_scan >= 2 && (double)bestd < ratio * (double)second) {
-            s_best[j] = ((unsigned)bestd << 18) | (unsigned)besti;          // owner j is the query, besti the train
-        }
+        if (valid && n2 >= 2 && (double)bestd < ratio * (double)second) s_best[i] = ((unsigned)bestd << 18) | (unsigned)bestj;
     }
-    }
-    // the staging tile becomes the key array; ratio mode: s_best holds a word only where the test passed
+    // the staging tile becomes the key array
     const MatchOut<int> out(pair, max_matches, img1, img2, kcap, kp_pt, m_q, m_t, m_d, pts1, pts2);
-    select_sort_emit<256>((unsigned *)s_q, n1, max_matches, m_n + pair,
-        [&](int i) { const unsigned b = s_best[i]; return b != 0xFFFFFFFFu && (RATIO || b == s_row[i]) ? ham_sort_key(b, i) : 0xFFFFFFFFu; },
+    select_sort_emit<256>((unsigned *)s_t, n1, max_matches, m_n + pair,
+        [&](int i) { const unsigned b = s_best[i]; return b != 0xFFFFFFFFu ? ham_sort_key(b, i) : 0xFFFFFFFFu; },
         [&](int r, int i, unsigned key) { out.put(r, i, s_best[i] & 0x3FFFF, (int)(key >> 16)); });
 }
 
 // ---------------------------------------------------------------- crossCheck on the matrix cores
-// The measured bound of the VALU kernel above is vector-instruction issue: 19 instructions per 64 distances
+// The measured bound of a vector-ALU crossCheck kernel (the ratio kernel's loop without the second best, shipped until
+// the matrix-core kernel replaced it) is vector-instruction issue: 19 instructions per 64 distances
 // (8 v_xor + 8 v_bcnt + compare / select) at the 4-cycle integer issue cadence = 0.75 ms for 1024 pairs of
 // 1000 x 1000 descriptors, 91 % of the measured issue roof (profiles/r02_counters.json, r02_calibration.json).
 // Hamming distance is a dot product in disguise: d(q, t) = |q| + |t| - 2 q.t with the 256 bits as 0/1 bytes, so the
@@ -503,14 +471,9 @@ void rpe_launch_match(rpe_handle *h, const RpeRun &r)
 {
     const int kcap = h->lay.kcap, B = r.pairs;
     const RpeFeatSrc &f = r.feat;
-    size_t lds = (size_t)QTILE * 32 + (size_t)kcap * 8;       // staging / sort keys + election words + own-nearest words
-    if (h->cfg.match_mode == RPE_MATCH_RATIO)                 // the ratio mode has no own-nearest words: 4 bytes per keypoint (<= 64 KB at 8064)
-        launch_tab(f.tab, match_hamming_kernel<true, true>, match_hamming_kernel<true, false>, dim3(B), dim3(256), (size_t)QTILE * 32 + (size_t)kcap * 4, h->stream,
+    if (h->cfg.match_mode == RPE_MATCH_RATIO)                 // staging / sort keys + 4 bytes of election word per keypoint (<= 64 KB at 8064)
+        launch_tab(f.tab, match_hamming_ratio_kernel<true>, match_hamming_ratio_kernel<false>, dim3(B), dim3(256), (size_t)QTILE * 32 + (size_t)kcap * 4, h->stream,
                            f.desc, f.count, f.pt, f.img2_base, f.tab, kcap, h->cfg.max_matches, h->cfg.match_ratio,
-                           h->d_m_q, h->d_m_t, h->d_m_d, h->d_m_n, h->d_pts1, h->d_pts2);
-    else if (getenv("RPE_MATCH_VALU") && lds <= 65536)    // diagnostic: the vector-ALU crossCheck kernel (A/B runs, parity tests)
-        launch_tab(f.tab, match_hamming_kernel<false, true>, match_hamming_kernel<false, false>, dim3(B), dim3(256), lds, h->stream,
-                           f.desc, f.count, f.pt, f.img2_base, f.tab, kcap, h->cfg.max_matches, 0.0,
                            h->d_m_q, h->d_m_t, h->d_m_d, h->d_m_n, h->d_pts1, h->d_pts2);
     else {
         const RpeHammingPlan p = rpe_hamming_plan(kcap, B, 0);
@@ -759,8 +722,8 @@ void rpe_launch_guided(rpe_handle *h, const RpeRun &r, const double *d_R, const 
 //
 // The O(N^2) part runs on the matrix cores (match_l2_mfma_kernel): with a' = a - 128 (a XOR 0x80 per byte: u8 -> i8),
 // |a-b|^2 = |a'|^2 + |b'|^2 - 2 a'.b' and a'.b' is v_mfma_i32_32x32x32_i8 over K = 128 (4 MFMAs per 32 x 32 tile; exact
-// integers).  The vector-ALU kernel below it (32 x v_dot4_u32_u8 per distance) remains for the Lowe-ratio extension,
-// which also needs the second-best distance, and as the A/B diagnostic (RPE_MATCH_VALU).
+// integers).  The Lowe-ratio extension, which also needs the second-best distance, has a vector-ALU kernel of its own
+// (match_l2_ratio_kernel: 32 x v_dot4_u32_u8 per distance); it serves that mode and nothing else.
 #define L2_QTILE 256
 
 // NQ = descriptor bytes / 16: 8 for SIFT (128 B), 2 for ORB descriptors matched with NORM_L2 (32 B; cv2 builds this
@@ -781,75 +744,65 @@ __device__ __forceinline__ unsigned dot_u8(const uint4 *q, const uint4 (&t)[NQ])
     return acc;
 }
 
-// Vector-ALU form.  Workgroup = (256 owned descriptors, pair); the scanned descriptors stream through LDS.
-// MODE 0: owned = trains (NNq), MODE 2: owned = queries (NNt), MODE 1: Lowe ratio (extension; owned = queries).
-template <int NQ, int MODE, bool TAB>
-__global__ __launch_bounds__(256) void match_l2_nearest_kernel(const uint8_t *__restrict__ desc, const int *__restrict__ kp_count,
-                                                                int img2_base, const int2 *__restrict__ pair_tab, int kcap, double ratio,
-                                                                unsigned long long *__restrict__ best)
+// The Lowe-ratio L2 matcher, on the vector ALU.  Workgroup = (256 queries, pair), a lane owns one query descriptor; the
+// train descriptors stream through LDS.  best[] gets a word only where the ratio test passed.
+template <int NQ, bool TAB>
+__global__ __launch_bounds__(256) void match_l2_ratio_kernel(const uint8_t *__restrict__ desc, const int *__restrict__ kp_count,
+                                                              int img2_base, const int2 *__restrict__ pair_tab, int kcap, double ratio,
+                                                              unsigned long long *__restrict__ best)
 {
     constexpr int DIM = NQ * 16;
-    __shared__ uint4 s_q[L2_QTILE * NQ];                                        // 32 KB (SIFT) / 8 KB (ORB)
-    __shared__ unsigned s_qn[L2_QTILE];                                         // |q|^2 of the tile
-    const int tid = threadIdx.x, pair = blockIdx.y, tc = blockIdx.x * 256;
+    __shared__ uint4 s_t[L2_QTILE * NQ];                                        // 32 KB (SIFT) / 8 KB (ORB)
+    __shared__ unsigned s_tn[L2_QTILE];                                         // |t|^2 of the tile
+    const int tid = threadIdx.x, pair = blockIdx.y, qc = blockIdx.x * 256;
     int img1, img2;
     rpe_pair_slots<TAB>(pair_tab, img2_base, pair, img1, img2);
     const int n1 = min(kp_count[img1], kcap), n2 = min(kp_count[img2], kcap);
-    constexpr bool RATIO = MODE == 1, QOWN = MODE != 0;
-    const int n_own = QOWN ? n1 : n2, n_scan = QOWN ? n2 : n1;
-    if (tc >= n_own || n_scan <= 0) return;
+    if (qc >= n1 || n2 <= 0) return;
     const uint4 *d1 = (const uint4 *)(desc + (long long)img1 * kcap * DIM);
     const uint4 *d2 = (const uint4 *)(desc + (long long)img2 * kcap * DIM);
-    const uint4 *d_own = QOWN ? d1 : d2, *d_scan = QOWN ? d2 : d1;
-    const int j = tc + tid;
-    const bool valid = j < n_own;
-    uint4 t[NQ];
-    unsigned tn = 0;
+    const int i = qc + tid;
+    const bool valid = i < n1;
+    uint4 q[NQ];
+    unsigned qn = 0;
 #pragma unroll
     for (int k = 0; k < NQ; ++k) {
-        t[k] = valid ? d_own[NQ * j + k] : make_uint4(0, 0, 0, 0);
-        tn = __builtin_amdgcn_udot4(t[k].x, t[k].x, tn, false); tn = __builtin_amdgcn_udot4(t[k].y, t[k].y, tn, false);
-        tn = __builtin_amdgcn_udot4(t[k].z, t[k].z, tn, false); tn = __builtin_amdgcn_udot4(t[k].w, t[k].w, tn, false);
+        q[k] = valid ? d1[NQ * i + k] : make_uint4(0, 0, 0, 0);
+        qn = __builtin_amdgcn_udot4(q[k].x, q[k].x, qn, false); qn = __builtin_amdgcn_udot4(q[k].y, q[k].y, qn, false);
+        qn = __builtin_amdgcn_udot4(q[k].z, q[k].z, qn, false); qn = __builtin_amdgcn_udot4(q[k].w, q[k].w, qn, false);
     }
     float bestd = __builtin_inff(), second = __builtin_inff();
-    int besti = -1;
-    for (int qt = 0; qt < n_scan; qt += L2_QTILE) {
-        const int nq = min(L2_QTILE, n_scan - qt);
+    int bestj = -1;
+    for (int tt = 0; tt < n2; tt += L2_QTILE) {
+        const int nt = min(L2_QTILE, n2 - tt);
         __syncthreads();
         {
             uint4 stage[NQ];
 #pragma unroll
-            for (int q = 0; q < NQ; ++q) { const int idx = tid + 256 * q; stage[q] = idx < nq * NQ ? d_scan[NQ * qt + idx] : make_uint4(0, 0, 0, 0); }
+            for (int c = 0; c < NQ; ++c) { const int idx = tid + 256 * c; stage[c] = idx < nt * NQ ? d2[NQ * tt + idx] : make_uint4(0, 0, 0, 0); }
 #pragma unroll
-            for (int q = 0; q < NQ; ++q) s_q[tid + 256 * q] = stage[q];
+            for (int c = 0; c < NQ; ++c) s_t[tid + 256 * c] = stage[c];
         }
         __syncthreads();
-        if (tid < nq) {
-            unsigned qn = 0;
+        if (tid < nt) {
+            unsigned tn = 0;
             for (int k = 0; k < NQ; ++k) {
-                const uint4 a = s_q[NQ * tid + k];
-                qn = __builtin_amdgcn_udot4(a.x, a.x, qn, false); qn = __builtin_amdgcn_udot4(a.y, a.y, qn, false);
-                qn = __builtin_amdgcn_udot4(a.z, a.z, qn, false); qn = __builtin_amdgcn_udot4(a.w, a.w, qn, false);
+                const uint4 a = s_t[NQ * tid + k];
+                tn = __builtin_amdgcn_udot4(a.x, a.x, tn, false); tn = __builtin_amdgcn_udot4(a.y, a.y, tn, false);
+                tn = __builtin_amdgcn_udot4(a.z, a.z, tn, false); tn = __builtin_amdgcn_udot4(a.w, a.w, tn, false);
             }
-            s_qn[tid] = qn;
+            s_tn[tid] = tn;
         }
         __syncthreads();
-        for (int i = 0; i < nq; ++i) {
-            const unsigned ab = dot_u8<NQ>(s_q + NQ * i, t);
-            const float d = sqrtf((float)(s_qn[i] + tn - 2u * ab));
-            if (!RATIO) { if (d < bestd) { bestd = d; besti = qt + i; } }
-            else {
-                if (d < bestd) { second = bestd; bestd = d; besti = qt + i; }
-                else if (d < second) second = d;
-            }
+        for (int j = 0; j < nt; ++j) {
+            const unsigned ab = dot_u8<NQ>(s_t + NQ * j, q);
+            const float d = sqrtf((float)(s_tn[j] + qn - 2u * ab));
+            if (d < bestd) { second = bestd; bestd = d; bestj = tt + j; }
+            else if (d < second) second = d;
         }
     }
-    if (!RATIO) {
-        if (valid && besti >= 0)
-            best[(long long)pair * kcap + j] = ((unsigned long long)__float_as_uint(bestd) << 18) | (unsigned long long)besti;
-    } else if (valid && n_scan >= 2 && (double)bestd < ratio * (double)second) {
-        best[(long long)pair * kcap + j] = ((unsigned long long)__float_as_uint(bestd) << 18) | (unsigned long long)besti;
-    }
+    if (valid && n2 >= 2 && (double)bestd < ratio * (double)second)
+        best[(long long)pair * kcap + i] = ((unsigned long long)__float_as_uint(bestd) << 18) | (unsigned long long)bestj;
 }
 
 // Per descriptor a (u = a - 128 per byte): { |u|^2, |u|^2 + 2 sum(u) } -- the owner's and the scanned row's terms of the MFMA kernel
@@ -1210,13 +1163,10 @@ void rpe_launch_match_l2(rpe_handle *h, const RpeRun &r)
     const bool rt = h->cfg.match_mode == RPE_MATCH_RATIO;
     if (!rt) hipMemsetAsync(h->d_m_best, 0xFF, sizeof(unsigned long long) * (size_t)B * kcap, h->stream);
     const bool sift = h->desc_bytes == 128;
-    if (rt || getenv("RPE_MATCH_VALU")) {
+    if (rt) {
         const dim3 grid((kcap + 255) / 256, B);
-#define L2_LAUNCH(NQ, MODE, DST) launch_tab(f.tab, match_l2_nearest_kernel<NQ, MODE, true>, match_l2_nearest_kernel<NQ, MODE, false>, grid, dim3(256), 0, h->stream, \
-                                                    f.desc, f.count, img2_base, f.tab, kcap, h->cfg.match_ratio, DST)
-        if (sift) { if (rt) L2_LAUNCH(8, 1, h->d_m_best2); else { L2_LAUNCH(8, 0, h->d_m_best); L2_LAUNCH(8, 2, h->d_m_best2); } }
-        else      { if (rt) L2_LAUNCH(2, 1, h->d_m_best2); else { L2_LAUNCH(2, 0, h->d_m_best); L2_LAUNCH(2, 2, h->d_m_best2); } }
-#undef L2_LAUNCH
+        if (sift) launch_tab(f.tab, match_l2_ratio_kernel<8, true>, match_l2_ratio_kernel<8, false>, grid, dim3(256), 0, h->stream, f.desc, f.count, img2_base, f.tab, kcap, h->cfg.match_ratio, h->d_m_best2);
+        else      launch_tab(f.tab, match_l2_ratio_kernel<2, true>, match_l2_ratio_kernel<2, false>, grid, dim3(256), 0, h->stream, f.desc, f.count, img2_base, f.tab, kcap, h->cfg.match_ratio, h->d_m_best2);
     } else {
         // images [0, B) and [img2_base, img2_base + B) (a stream: B + 1 frames); the frame store holds its slots' words already
         if (!f.tab) rpe_launch_l2_norms(h, img2_base + B);
@@ -1230,7 +1180,7 @@ void rpe_launch_match_l2(rpe_handle *h, const RpeRun &r)
 
 // Guided matches of run r for an L2 handle, into the d_gm_* buffers (d_gm_d read as f32); poses and d_status as in
 // rpe_launch_guided.  Served for both match modes: the guided rule is the mutual one, and the matrix-core form needs the norm
-// words, which a ratio-mode or RPE_MATCH_VALU run of the workspace never wrote (the kernel is idempotent and O(N); the frame
+// words, which a ratio-mode run of the workspace never wrote (the kernel is idempotent and O(N); the frame
 // store of every NORM_L2 handle, ratio mode included, holds its slots' words from the put).  d_m_best2 / d_m_best are scratch of one matcher launch sequence -- nothing reads
 // them after rpe_launch_match_l2's select -- and serve as the guided NNt / NNq words here.
 void rpe_launch_guided_l2(rpe_handle *h, const RpeRun &r, const double *d_R, const double *d_t, const int *d_status, double gate_px, double max_distance)

@@ -735,7 +735,9 @@ extern "C" int rpe_enqueue_batch_device(rpe_handle *h, const uint8_t *d_imgs1, c
     // Small batches are launch-bound on the HOST (one pair: ~50 launches for 0.6 ms of GPU work): the sequence is captured
     // once per (input buffers, B) and replayed as a hipGraph.  Everything in it is stream-ordered kernels and memsets whose
     // arguments depend only on the handle, the two buffers and B; K travels outside (set_K above).  Not while profiling (the
-    // stage events are host-side records), not for SIFT (its launch sequence reads back counts), RPE_NO_GRAPH=1 turns it off.
+    // stage events are host-side records) and only for ORB (rpe_sift_run has no host sync either, but its sequence is not
+    // captured: the condition below is the ORB one), RPE_NO_GRAPH=1 turns it off.  No launcher in the sequence reads the
+    // environment, so a cached graph cannot freeze a switch.
     static const bool no_graph = getenv("RPE_NO_GRAPH") != nullptr;
     if (B > RPE_GRAPH_MAX_PAIRS || h->profiling || h->cfg.feature_method != RPE_FEATURE_ORB || no_graph)
         return run_images(h, d_imgs1, d_imgs2, B, B, rpe_run_batch(h, B));

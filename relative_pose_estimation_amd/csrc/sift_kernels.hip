@@ -27,8 +27,6 @@
 //               (the three radix selects are sift_kth_largest_key: one body, the caller says which entries take part and their key)
 //   describe  : one wave per keypoint: the sample positions kept in a row of the square are an interval (one lane per row finds
 //               it), dense batches of 64 samples, 4x4x8 trilinear histogram in 8 interleaved partials, lane = (slot, corner)
-//   march     : (RPE_SIFT_MARCH=1) levels 1-3 / 4-5 of the large octaves in one pass over the source level each, rings of
-//               row-filtered rows in LDS; bit-identical to the tile kernels
 // Records between the kernels: SiftSeed (one word), the survivor (SV_*, SURV_W floats) and the keypoint (KP_*, KP_W floats).
 // Kernels whose lanes append through a returning atomic on a per-image counter (adjust, orient) put the image index on
 // the fastest grid axis, so that workgroups in flight together hit different counters.
@@ -95,7 +93,6 @@ struct RpeSiftState {                   // the device buffers are in the handle'
     int sel_k_override = 0;
     unsigned long long *d_k0 = nullptr, *d_k1 = nullptr; unsigned *d_sidx = nullptr; // sort keys [img][raw_pad]
     int raw_pad = 0;
-    bool march = false;                                    // levels 1-3 / 4-5 of the large octaves by sift_march_kernel
     float *d_fin = nullptr;                                // [img][kcap][KP_W] un-halved keypoints in sorted order
 };
 
@@ -365,213 +362,6 @@ __global__ __launch_bounds__(256) void sift_blur_fused_kernel(const float *__res
                 }
             }
         }
-    }
-}
-
-// ------------------------------------------------------------------ marching pyramid
-// NL consecutive levels of one octave in ONE pass over the source level: a workgroup owns a strip of MARCH_SW columns and
-// marches down the image 8 rows per step.  Level j keeps a ring of its last 2 R_j + 8 row-filtered rows in LDS; its column
-// filter produces the 8 rows that lie R_j rows above the newest one, which are stored and are at once the source rows of
-// level j + 1's row filter.  The source level is read once (the tile kernels read every level back), every row filter runs
-// once per row (the 32-row tiles ran it on 32 + 2R rows), and there are no window loads.
-// Arithmetic and its order are those of sift_blur_fused_kernel, bit for bit.  Borders: the column filter adds its taps as
-// symmetric pairs, so running the march over a source extended by reflect-101 above and below (P = sum of the radii rows)
-// yields every level's own reflect-101 extension exactly -- no special rows.  The row filter accumulates left to right and
-// is not symmetric: at the image's left / right edge a level's out-of-image columns are written as copies of its mirror
-// columns (the column-filter lane of such a column reads the ring at the mirrored column).
-#define MARCH_SW 128
-#define MARCH_NT (MARCH_SW >= 128 ? 256 : 128)     // threads per workgroup: one lane per column of the widest level
-// (lds[addr + 4 TS i], lds[addr + 4 TS (i + 4)]) for every i of the sequence: each half is its own ds_read_b32 at a static
-// offset, so it lands in its half of the register pair (left to the compiler the two uses of a value share one load and
-// ~100 v_mov per step rebuild the packed operands)
-template <int TS, int I>
-__device__ __forceinline__ void lds_colpair(f32x2 &p, unsigned addr)
-{
-    float a, b;
-    asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(a) : "v"(addr), "n"(4 * TS * I) : "memory");
-    asm volatile("ds_read_b32 %0, %1 offset:%2" : "=v"(b) : "v"(addr), "n"(4 * TS * (I + 4)) : "memory");
-    p = f32x2{a, b};
-}
-template <int TS, int... Is>
-__device__ __forceinline__ void lds_colpairs(f32x2 *P, unsigned addr, std::integer_sequence<int, Is...>)
-{
-    (lds_colpair<TS, Is>(P[Is], addr), ...);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    (asm_pin(P[Is]), ...);
-}
-template <int NL, int R0, int R1, int R2>
-struct MarchGeo {
-    static constexpr int R(int j) { return j == 0 ? R0 : j == 1 ? R1 : R2; }
-    static constexpr int P = R0 + R1 + (NL > 2 ? R2 : 0);
-    static constexpr int H(int j) { int a = 0; for (int m = j + 1; m < NL; ++m) a += R(m); return a; }     // halo columns of level j on either side
-    static constexpr int L(int j) { int a = 0; for (int m = 0; m <= j; ++m) a += R(m); return a; }         // rows level j lags behind the source
-    static constexpr int W(int j) { return MARCH_SW + 2 * H(j); }
-    static constexpr int NG(int j) { return (W(j) + 7) / 8; }
-    static constexpr int SRCW(int j) { return 8 * NG(j) + 2 * R(j); }      // columns of level j's source rows that are read
-    static constexpr int SS(int j) { return SRCW(j) | 1; }
-    static constexpr int TS(int j) { return (8 * NG(j)) | 1; }
-    static constexpr int D(int j) { return 2 * R(j) + 8; }
-    static constexpr int OFF_SRC(int j) { int a = 0; for (int m = 0; m < j; ++m) a += 8 * SS(m) + D(m) * TS(m); return a; }
-    static constexpr int OFF_T(int j) { return OFF_SRC(j) + 8 * SS(j); }
-    static constexpr int TOTAL = OFF_SRC(NL);
-    // waves have roles: level j owns WV(j) waves (one lane per row-filter item / per column)
-    static constexpr int WV(int j) { return (NG(j) + 7) / 8; }
-    static constexpr int WBASE(int j) { int a = 0; for (int m = 0; m < j; ++m) a += WV(m); return a; }
-    static constexpr int NT = 64 * WBASE(NL);
-};
-
-template <class G, int J>
-__device__ __forceinline__ void march_rowfilter(float *lds, int kid, int tid)
-{
-    constexpr int R = G::R(J), KS = 2 * R + 1, NGJ = G::NG(J), SSJ = G::SS(J), TSJ = G::TS(J);
-    float k[KS];
-#pragma unroll
-    for (int i = 0; i < KS; ++i) k[i] = c_skern[kid][i];
-    const float *srcb = lds + G::OFF_SRC(J);
-    float *win = lds + G::OFF_T(J) + 2 * R * TSJ;              // the 8 new rows go behind the 2R rows carried over
-    {
-        const int it = tid;                                      // tid = lane index inside the level's waves
-        const int r = (it >> 2) & 7, g = 8 * (it >> 6) + (((it >> 3) & 4) | (it & 3));
-        if (g >= NGJ) return;
-        f32x2 P[4 + 2 * R];
-        lds_pairs<false>(P, lds_addr(srcb + r * SSJ + 8 * g), std::make_integer_sequence<int, 4 + 2 * R>());
-        float *o = win + r * TSJ + 8 * g;
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            f32x2 acc = f32x2{k[0], k[0]} * P[j];
-#pragma unroll
-            for (int i = 1; i < KS; ++i) { const f32x2 kk = {k[i], k[i]}; acc = __builtin_elementwise_fma(kk, P[j + i], acc); }
-            o[j] = acc.x;
-            o[j + 4] = acc.y;
-        }
-    }
-}
-
-template <class G, int J, int NL>
-__device__ __forceinline__ void march_colfilter(float *lds, int kid, int tid, int s, int x0, int w, int h, float *__restrict__ plane,
-                                                float *__restrict__ decp, int w2, int h2)
-{
-    constexpr int R = G::R(J), WJ = G::W(J), HJ = G::H(J), TSJ = G::TS(J);
-    const int c = x0 - HJ + tid;                                  // absolute column of this lane
-    if (tid >= WJ || c < 0 || c >= w) return;                     // out-of-image columns are written by the lane of their mirror column
-    float k[R + 1];
-#pragma unroll
-    for (int i = 0; i <= R; ++i) k[i] = c_skern[kid][R + i];
-    // the window of this column: rows 0 .. 2R-1 carried over from the previous step, rows 2R .. 2R+7 new; static addresses
-    float *win = lds + G::OFF_T(J) + tid;
-    f32x2 P[4 + 2 * R];
-    lds_colpairs<TSJ>(P, lds_addr(win), std::make_integer_sequence<int, 4 + 2 * R>());
-    // the last 2R rows move up for the next step (this lane is the only one that touches its column)
-#pragma unroll
-    for (int i = 0; i < 2 * R; ++i) win[i * TSJ] = i + 8 < 4 + 2 * R ? P[i + 8].x : P[i + 4].y;
-    f32x2 acc[4];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        acc[j] = f32x2{k[0], k[0]} * P[j + R];
-#pragma unroll
-        for (int t = 1; t <= R; ++t) { const f32x2 kk = {k[t], k[t]}; acc[j] = __builtin_elementwise_fma(kk, P[j + R + t] + P[j + R - t], acc[j]); }
-    }
-    if constexpr (J + 1 < NL) {                                   // source rows of the next level (this level's column range)
-        constexpr int SSN = G::SS(J + 1 < NL ? J + 1 : J);
-        float *nb = lds + G::OFF_SRC(J + 1 < NL ? J + 1 : J);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) { nb[j * SSN + tid] = acc[j].x; nb[(j + 4) * SSN + tid] = acc[j].y; }
-        // reflect-101 of this level at the image's left / right edge: the mirror columns inside the strip's range
-        const int ml = -c - (x0 - HJ), mr = 2 * (w - 1) - c - (x0 - HJ);
-        if (c > 0 && ml >= 0) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { nb[j * SSN + ml] = acc[j].x; nb[(j + 4) * SSN + ml] = acc[j].y; }
-        }
-        if (c < w - 1 && mr < WJ) {
-#pragma unroll
-            for (int j = 0; j < 4; ++j) { nb[j * SSN + mr] = acc[j].x; nb[(j + 4) * SSN + mr] = acc[j].y; }
-        }
-    }
-    const int y0 = -G::P + 8 * s - G::L(J);                       // first of the 8 rows produced in this step
-    if (tid >= HJ && tid < HJ + MARCH_SW && y0 + 7 >= 0 && y0 < h) {
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-#pragma unroll
-            for (int hh = 0; hh < 2; ++hh) {
-                const int y = y0 + j + 4 * hh;
-                const float v = hh ? acc[j].y : acc[j].x;
-                if (y >= 0 && y < h) {
-                    (plane + (size_t)y * w)[c] = v;
-                    if (decp && !(y & 1) && !(c & 1) && (y >> 1) < h2 && (c >> 1) < w2) decp[(size_t)(y >> 1) * w2 + (c >> 1)] = v;
-                }
-            }
-        }
-    }
-}
-
-template <int NL, int R0, int R1, int R2>
-__global__ __launch_bounds__(64 * (MarchGeo<NL, R0, R1, R2>::WBASE(NL))) void sift_march_kernel(
-    const float *__restrict__ src, long long sstride, float *__restrict__ dst, long long dstride,
-    long long pn, int w, int h, int kid0, float *__restrict__ dec, int dec_level, int w2, int h2)
-{
-    // All levels work in the same phase on different steps: in iteration t level j is at step t - j (its source rows were
-    // written one iteration earlier), so an iteration has two phases and two barriers whatever NL is -- every level's row
-    // filter, then every level's column filter -- and every wave has work in both.
-    typedef MarchGeo<NL, R0, R1, R2> G;
-    constexpr int NT = G::NT;
-    __shared__ __attribute__((aligned(16))) float lds[G::TOTAL];
-    const int tid = threadIdx.x, x0 = blockIdx.x * MARCH_SW;
-    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);      // the wave's role is a scalar
-    const float *s = src + (long long)blockIdx.y * sstride;
-    float *d = dst + (long long)blockIdx.y * dstride;
-    float *decp = dec ? dec + (long long)blockIdx.y * dstride : nullptr;
-    // this lane's share of the 8 x SRCW(0) source values of a step: fixed (row, column) slots, only the row base moves
-    constexpr int SW0 = G::SRCW(0), NLD = (8 * SW0 + NT - 1) / NT;
-    int lrow[NLD], lcol[NLD], loff[NLD];
-#pragma unroll
-    for (int q = 0; q < NLD; ++q) {
-        const int idx = min(tid + NT * q, 8 * SW0 - 1);
-        const int r = idx / SW0, cc = idx - r * SW0;
-        int c = x0 - G::P + cc;
-        c = c < 0 ? -c : c; c = c >= w ? 2 * w - 2 - c : c; c = min(max(c, 0), w - 1);
-        lrow[q] = r; lcol[q] = c; loff[q] = r * G::SS(0) + cc;
-    }
-    // Source rows are requested two steps ahead into two register sets.  A set is written to LDS right after the row phase
-    // (whose readers of the previous rows are past the barrier), i.e. BEFORE this iteration's level stores are issued: vmcnt
-    // counts in order, so waiting for a set drains every older request -- with the wait placed after the stores (one set, one
-    // step ahead) every iteration sat out the write acknowledgement of the stores it had just issued.
-    float sA[NLD], sB[NLD];
-    auto fetch = [&](float (&stage)[NLD], int step) {
-#pragma unroll
-        for (int q = 0; q < NLD; ++q) {
-            int y = -G::P + 8 * step + lrow[q];
-            y = y < 0 ? -y : y; y = y >= h ? 2 * h - 2 - y : y; y = min(max(y, 0), h - 1);
-            stage[q] = s[(size_t)y * w + lcol[q]];
-        }
-    };
-    auto put = [&](const float (&stage)[NLD]) {
-#pragma unroll
-        for (int q = 0; q < NLD; ++q) lds[G::OFF_SRC(0) + loff[q]] = stage[q];      // (the clamped duplicates of the last slot rewrite the same value)
-    };
-    const int nsteps = (h + 2 * G::P + 7) / 8;
-    // iteration t: level j is at step t - j (its source rows were written one iteration earlier)
-    auto iter = [&](int t, float (&cur)[NLD]) {
-        if (wv < G::WBASE(1)) { if (t < nsteps) march_rowfilter<G, 0>(lds, kid0, tid); }
-        else if (NL > 1 && wv < G::WBASE(NL > 1 ? 2 : 1)) { if (t >= 1 && t - 1 < nsteps) march_rowfilter<G, (NL > 1 ? 1 : 0)>(lds, kid0 + 1, tid - 64 * G::WBASE(1)); }
-        else if (NL > 2) { if (t >= 2 && t - 2 < nsteps) march_rowfilter<G, (NL > 2 ? 2 : 0)>(lds, kid0 + 2, tid - 64 * G::WBASE(NL > 2 ? 2 : 1)); }
-        __syncthreads();
-        if (t + 1 < nsteps) put(cur);                            // source rows of step t + 1 (requested two iterations ago)
-        if (wv < G::WBASE(1)) { if (t < nsteps) march_colfilter<G, 0, NL>(lds, kid0, tid, t, x0, w, h, d, dec_level == 0 ? decp : nullptr, w2, h2); }
-        else if (NL > 1 && wv < G::WBASE(NL > 1 ? 2 : 1)) { if (t >= 1 && t - 1 < nsteps) march_colfilter<G, (NL > 1 ? 1 : 0), NL>(lds, kid0 + 1, tid - 64 * G::WBASE(1), t - 1, x0, w, h, d + pn, dec_level == 1 ? decp : nullptr, w2, h2); }
-        else if (NL > 2) { if (t >= 2 && t - 2 < nsteps) march_colfilter<G, (NL > 2 ? 2 : 0), NL>(lds, kid0 + 2, tid - 64 * G::WBASE(NL > 2 ? 2 : 1), t - 2, x0, w, h, d + 2 * pn, dec_level == 2 ? decp : nullptr, w2, h2); }
-        // requested AFTER this iteration's stores and unconditionally (rows past the end are clamped): vmcnt counts in order, so the
-        // next wait (for the other set) can name exactly these NLD requests as the ones that may stay in flight
-        fetch(cur, t + 3);
-        __syncthreads();                                         // every window access of this iteration done; step t + 1's rows in place
-    };
-    fetch(sA, 0); fetch(sB, 1);
-    put(sA);
-    __syncthreads();
-    fetch(sA, 2);
-    const int T = nsteps + NL - 1;
-    for (int t = 0; t < T; t += 2) {
-        iter(t, sB);
-        iter(t + 1, sA);                                         // (an iteration past the end finds nothing to do)
     }
 }
 
@@ -1469,7 +1259,7 @@ int rpe_sift_create(rpe_handle *h)
         if (ks[i] > 31) { h->err = "SIFT kernel too wide"; return RPE_ERR_INVALID; }
     }
     // sigma, the layer count and the assumed input blur are constants, so the radii are too: the blur kernels are
-    // instantiated for exactly these (sift_blur, sift_march_kernel) and there is no path for any other
+    // instantiated for exactly these (sift_blur) and there is no path for any other
     for (int i = 0; i < S_NG; ++i)
         if ((ks[i] >> 1) != kSiftRadius[i]) { h->err = "SIFT blur radii are not 5 5 6 8 10 13"; return RPE_ERR_INVALID; }
     HIPCHK(h, hipMemcpyToSymbol(HIP_SYMBOL(c_skern), kern, sizeof(kern)));
@@ -1511,7 +1301,6 @@ int rpe_sift_create(rpe_handle *h)
     DM(h, S->d_nsurv, NI);
     DM(h, S->d_sel, NI * dv.seed_cap);
     DM(h, S->d_round, NI);
-    S->march = getenv("RPE_SIFT_MARCH") != nullptr;
     if (const char *e = getenv("RPE_SIFT_SEL_K")) S->sel_k_override = atoi(e);      // tests: a small value forces the second round
     DM(h, S->d_ncand, NI);
     DM(h, S->d_k0, NI * S->raw_pad);
@@ -1577,15 +1366,6 @@ int rpe_sift_run(rpe_handle *h, const uint8_t *d_a, const uint8_t *d_b, int na, 
         const bool last = o + 1 >= dv.noct;
         float *dec = !last ? G + dv.goff[o + 1] : nullptr;
         const int w2 = last ? 0 : dv.w[o + 1], h2 = last ? 0 : dv.h[o + 1];
-        if (S->march && w >= 256 && hh >= 64) {
-            // levels 1-3 in one march over level 0 (+ level 0 of the next octave), levels 4-5 in one march over level 3
-            const dim3 grid((w + MARCH_SW - 1) / MARCH_SW, n);
-            hipLaunchKernelGGL((sift_march_kernel<3, 5, 6, 8>), grid, dim3(MarchGeo<3, 5, 6, 8>::NT), 0, h->stream, (const float *)(G + dv.goff[o]), dv.gstride,
-                               G + dv.goff[o] + pn, dv.gstride, pn, w, hh, 1, dec, 2, w2, h2);
-            hipLaunchKernelGGL((sift_march_kernel<2, 10, 13, 0>), grid, dim3(MarchGeo<2, 10, 13, 0>::NT), 0, h->stream, (const float *)(G + dv.goff[o] + 3 * pn), dv.gstride,
-                               G + dv.goff[o] + 4 * pn, dv.gstride, pn, w, hh, 4, (float *)nullptr, -1, 0, 0);
-            continue;
-        }
         for (int i = 1; i < S_NG; ++i)
             sift_blur(h, G + dv.goff[o] + (i - 1) * pn, dv.gstride, G + dv.goff[o] + i * pn, dv.gstride, w, hh, i, n,
                       i == S_NOL ? dec : nullptr, w2, h2);

@@ -130,7 +130,6 @@ def _l2_lists(dim):
         # kcap 2048, one pair: 8 chunks of 8 tiles
         f"l2_{s}_1984_full": Spec("l2", dim, "cross", (), 100, _m((2048, 2048)) + [(300, 2048, "far")]),
         f"l2_{s}_448_ratio": Spec("l2", dim, "ratio", (0.8, 1.0), 40, _m(*_RATIO_L2) + [(255, 257, "far")]),
-        f"l2_{s}_448_valu": Spec("l2", dim, "cross", (), 40, _m((257, 255), (255, 257)) + [(257, 255, "far")]),
     }
 
 
@@ -144,9 +143,6 @@ SPECS = {
     # kcap 5064: the election words do not fit LDS
     "ham_5000": Spec("hamming", 32, "cross", (), 200, _m((5064, 5000)) + [(64, 64, "far")] + _m(*_SMALL[:8], (64, 50), (50, 64))),
     "ham_8000_ratio": Spec("hamming", 32, "ratio", (0.75, 1.0), 100, _m(*_RATIO_H) + [(257, 6, "far")]),
-    # kcap 1164: scanned 1023 .. 1027 against owners 255 .. 257, either way round
-    "ham_1100_valu": Spec("hamming", 32, "cross", (), 100,
-                          _m((1023, 255), (1024, 256), (1025, 257), (1027, 256), (255, 1023), (256, 1024), (257, 1025), (256, 1027)) + [(1027, 257, "far")]),
     **_l2_lists(128), **_l2_lists(32),
     # kcap 16384: the select kernel sorts 16384 keys
     "l2_sift_uncapped": Spec("l2", 128, "cross", (), 40, _m((8200, 70), (70, 8200)) + [(70, 300, "far")]),

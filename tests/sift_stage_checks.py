@@ -29,7 +29,7 @@ Tolerances and margins, with their derivations (u = 2^-24, the f32 unit roundoff
   the fastAtan2 / exp conventions only flip elements that sit at .5.
 
 Largest errors measured on the MI355X run of tests/test_gpu_sift_reference.py (the kernels equal the oracle bit for bit,
-so the CPU rows measure the same): pyramid 7.3e-5 (HD frame, also with RPE_SIFT_MARCH=1); pt 1.2e-4 octave pixels (HD,
+so the CPU rows measure the same): pyramid 7.3e-5 (HD frame); pt 1.2e-4 octave pixels (HD,
 the f32 rounding of c + xc), size 1.5e-7 and response 1.6e-7 relative, xi byte 0; angle 3.9e-5 degrees beyond the flip
 allowance; descriptor elements 1, at most 0.06 % not exact.  Set aside as close calls: at most 0.9 % of keypoint
 locations and 0.7 % of orientation locations.

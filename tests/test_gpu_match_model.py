@@ -52,8 +52,8 @@ def hamming_form(kcap, B):
     return ("split" if split > 1 or not lds_fits else "fused"), split, rounds
 
 
-def hamming_valu_lds(kcap, ratio):
-    return QTILE * 32 + kcap * (4 if ratio else 8)
+def hamming_ratio_lds(kcap):
+    return QTILE * 32 + kcap * 4
 
 
 def l2_form(kcap, B):
@@ -232,33 +232,17 @@ def test_hamming_first_capacity_beyond_lds(capi):
         e.close()
 
 
-# ================================================================= Hamming, vector ALU
-# The two RPE_MATCH_VALU tests cannot observe which kernel ran: they rely on the launchers reading the variable with getenv
-# at every launch, as they do today.  Were that read ever cached in a static, they would pass on the matrix-core path.
+# ================================================================= Hamming, Lowe ratio (vector ALU)
 @pytest.mark.parametrize("ratio", [0.75, 1.0])
 def test_hamming_ratio_valu(capi, ratio):
-    """match_hamming_kernel<true> (Lowe ratio) at the largest capacity, kcap = 8064: 32 KB of staging + 4 bytes per keypoint
+    """match_hamming_ratio_kernel (Lowe ratio) at the largest capacity, kcap = 8064: 32 KB of staging + 4 bytes per keypoint
     = 65 024 B of LDS.  n2 = 1023 / 1024 / 1025 / 2049 trains cross the QTILE = 1024 staging tile once and twice; n2 < 2
     gives nothing; n1 = 257 and 1500 queries take 2 and 6 owner chunks of 256.  ratio = 1.0: best == second is dropped."""
     e = _engine(capi, "ham_8000_ratio", 8000, 2, match_mode=capi.MATCH_RATIO, match_ratio=ratio)
     try:
-        assert e.kcap == 8064 and hamming_valu_lds(e.kcap, True) == 65024 <= 65536
+        assert e.kcap == 8064 and hamming_ratio_lds(e.kcap) == 65024 <= 65536
         _in_calls(e, "ham_8000_ratio", mc.cases("ham_8000_ratio"), 2, ratio)
     finally:
-        e.close()
-
-
-def test_hamming_crosscheck_valu(capi, monkeypatch):
-    """match_hamming_kernel<false> behind RPE_MATCH_VALU: 1023 / 1024 / 1025 / 1027 scanned rows end the 4-unrolled scan with
-    a remainder of 3, 0, 1 and 3 rows, the last two in a second QTILE; 255 / 256 / 257 owners around the 256-lane chunk.
-    Each pair is scanned both ways round (pass 0: the trains own, pass 1: the queries)."""
-    e = _engine(capi, "ham_1100_valu", 1100, 4)
-    try:
-        assert e.kcap == 1164 and hamming_valu_lds(e.kcap, False) <= 65536      # else the launcher takes the matrix cores
-        monkeypatch.setenv("RPE_MATCH_VALU", "1")
-        _in_calls(e, "ham_1100_valu", mc.cases("ham_1100_valu"), 4)
-    finally:
-        monkeypatch.delenv("RPE_MATCH_VALU", raising=False)
         e.close()
 
 
@@ -321,7 +305,7 @@ def test_l2_eight_chunks_of_eight_tiles(capi, sift):
 @pytest.mark.parametrize("ratio", [0.8, 1.0])
 @pytest.mark.parametrize("sift", WIDTHS)
 def test_l2_ratio(capi, sift, ratio):
-    """match_l2_nearest_kernel<8 | 2, 1> (Lowe ratio; the only L2 ratio matcher): n2 = 255 / 256 / 257 / 512 trains cross
+    """match_l2_ratio_kernel<8 | 2> (Lowe ratio; the only L2 ratio matcher): n2 = 255 / 256 / 257 / 512 trains cross
     the L2_QTILE = 256 staging tile (512 = kcap: two full tiles), n2 < 2 gives nothing, n1 = 255 / 257 queries are one
     owner chunk and one row more.  Near-extreme rows under ratio = 1.0: best < second must be decided on the float32
     roots, which collide where the integers differ."""
@@ -331,20 +315,6 @@ def test_l2_ratio(capi, sift, ratio):
         assert e.kcap == 512 == 2 * L2_QTILE
         _in_calls(e, name, mc.cases(name), 4, ratio)
     finally:
-        e.close()
-
-
-@pytest.mark.parametrize("sift", WIDTHS)
-def test_l2_valu_modes(capi, monkeypatch, sift):
-    """match_l2_nearest_kernel<8 | 2, 0> and <8 | 2, 2> behind RPE_MATCH_VALU (the trains', then the queries' nearest):
-    257 x 255 and 255 x 257 cross L2_QTILE = 256 as scanned rows in one mode and the 256-lane owner chunk in the other"""
-    name = _l2_name(sift, "448_valu")
-    e = _engine(capi, name, 448, 4, sift=sift)
-    try:
-        monkeypatch.setenv("RPE_MATCH_VALU", "1")
-        _in_calls(e, name, mc.cases(name), 4)
-    finally:
-        monkeypatch.delenv("RPE_MATCH_VALU", raising=False)
         e.close()
 
 

@@ -207,31 +207,6 @@ def test_other_configurations(capi, name, W, H, kw):
         e.close()
 
 
-@pytest.mark.parametrize("name,kw", [("orb_hamming_valu", dict(nfeatures=1000)), ("orb_l2_valu", dict(nfeatures=1000, norm_type=1)),
-                                     ("sift_l2_valu", dict(nfeatures=512, feature_method=1, norm_type=1))])
-def test_vector_alu_matchers_with_a_table(capi, monkeypatch, name, kw):
-    """RPE_MATCH_VALU selects the vector-ALU crossCheck matchers (match_hamming_kernel<false>, match_l2_nearest_kernel modes
-    0 and 2): their pair-table instances equal their batch instances too"""
-    from relative_pose_estimation_amd import synthetic, geometry
-    W, H = (320, 240) if kw.get("feature_method") else (640, 480)
-    K = geometry.default_camera_matrix(W, H)
-    fr = synthetic.make_stream(4, K, W, H)[0]
-    e = capi.Engine(W, H, max_batch=8, max_matches=500, **kw)
-    try:
-        e.frames_reserve(6)
-        e.frames_put(fr, [4, 0, 5, 2])
-        w = np.array([4, 0, 5, 2])[np.asarray(SHORT)]
-        plain = _pairs(e, w, K)
-        monkeypatch.setenv("RPE_MATCH_VALU", "1")
-        res = _pairs(e, w, K)
-        assert (res[3] > 0).all()
-        _same(res, _batch(e, fr, SHORT, K), name)
-        _same(res, plain, name + ": the vector-ALU and the matrix-core matcher agree")
-    finally:
-        monkeypatch.delenv("RPE_MATCH_VALU", raising=False)
-        e.close()
-
-
 def test_fused_matcher_with_a_table(capi, frames, ref, K_vga):
     """more than RPE_MATCH_SPLIT_PAIRS (64) pairs in one list: the fused Hamming matcher (election words in LDS, in-kernel
     sort and point gather) instead of the split form every shorter list takes -- scattered slots, an 80-pair engine"""

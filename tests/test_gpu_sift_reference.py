@@ -109,14 +109,3 @@ def test_cap_2048_hd(hd):
     assert len(ku) > 2048
     chk.check_post(ku, kc, 2048)
     print("cap 2048:", chk.check_orientations(pyr, kc, sample=600), chk.check_descriptors(pyr, kc, dc, sample=300))
-
-
-def test_marching_pyramid_hd(monkeypatch):
-    """RPE_SIFT_MARCH=1 (sift_march_kernel for the large octaves): the pyramid stage on the HD frame"""
-    img = _frames(1920, 1080, 5)[:1]
-    monkeypatch.setenv("RPE_SIFT_MARCH", "1")
-    e = _engine(1920, 1080, 0)
-    monkeypatch.delenv("RPE_SIFT_MARCH")
-    pyr, _, _ = _run(e, img)[0]
-    e.close()
-    print("march pyramid max |err|:", chk.check_pyramid(img[0], pyr))

@@ -730,6 +730,66 @@ int rpe_tracks_from_matches(rpe_handle *h, int P, int n_frames, const int32_t *f
                             int min_len, int32_t *counts, int32_t *track_start, int32_t *obs_frame, int32_t *obs_kp,
                             float *obs_xy, int32_t *match_track);
 
+/* ----------------------------------------------------------- track points */
+/* The sparse map of a run (NOT in the reference): one scene point per track, triangulated from ALL the views of the track
+ * under absolute poses, with a verdict on every observation.  A stage-form call over the caller's arrays: the tracks as
+ * rpe_build_tracks writes them (track_start[n_tracks + 1], obs_frame[n_obs], obs_xy[2 * n_obs] f32 pixels, n_obs =
+ * track_start[n_tracks]); world-to-camera poses x = R X + T per frame, R_abs[9 * n_frames] row-major, T_abs[3 * n_frames];
+ * frame_group[n_frames]: frames with the same value >= 0 share one scale (one segment of a chained trajectory), a negative
+ * value is a frame without a pose, NULL puts every frame in group 0; and exactly one of K[9] (one camera for all frames)
+ * and cams[n_frames] (one per frame, normalised and undistorted as in "camera models"; K is the camera {K[0], K[4], K[2],
+ * K[5], no lens}, so K and cams filled with that pinhole give the same bits).
+ * The rule, for one track with observations o = s .. e-1 (s = track_start[k], e = track_start[k + 1]).  All arithmetic
+ * f64, + - * / sqrt only, no contraction; a comparison with a NaN is false; every sum over observations starts from 0 and
+ * adds the observations in ascending o, left to right; a 3-vector dot product is (a0*b0 + a1*b1) + a2*b2.
+ *  Per observation, with (R, T) and the camera of its frame: (x, y) = the normalised, undistorted point; v = R'(x, y, 1):
+ *   v_k = (R[0][k]*x + R[1][k]*y) + R[2][k];  bearing d = v / sqrt(v.v);  centre c_k = -((R[0][k]*T0 + R[1][k]*T1) +
+ *   R[2][k]*T2);  f = (fx + fy) / 2.
+ *  1 Group and used set.  G = the group of the first observation whose frame has a group >= 0; U = the observations whose
+ *   frame has group G.  No such observation, or |U| < min_views: RPE_TRACKPT_TOO_FEW.
+ *  2 Midpoint start over a selection S (first S = U): M = I - d d', m_ij = (i == j ? 1 : 0) - d_i*d_j;  A = sum M (upper
+ *   triangle), b_i = sum ((m_i0*c0 + m_i1*c1) + m_i2*c2);  A X = b by the Cholesky of rpe_refine_poses at lambda = 0
+ *   (pivot s of column j: L_jj minus the squares of the row so far; s > 0 and finite, else not positive definite).  Not
+ *   positive definite: RPE_TRACKPT_DEGENERATE.  Depth of X in a view: z = y2, y = R X + T, each row ((r0*X0 + r1*X1) +
+ *   r2*X2) + t.  A view of S without z > 0: RPE_TRACKPT_BEHIND.
+ *  3 Levenberg-Marquardt on X over S.  Residual of a view, in pixels: u = y0/y2, w = y1/y2, e0 = f*(u - x), e1 = f*(w - y);
+ *   cost = sum (e0*e0 + e1*e1).  With q = f/y2, a = q*u, b = q*w the two Jacobian rows are J0_k = q*R[0][k] - a*R[2][k],
+ *   J1_k = q*R[1][k] - b*R[2][k];  H_ij = sum (J0_i*J0_j + J1_i*J1_j) (upper triangle), g_i = sum (J0_i*e0 + J1_i*e1).
+ *   The loop is rpe_refine_poses': lambda0 = 1e-3; at most max_iters iterations, each solving (H + lambda diag H) step = -g
+ *   (not positive definite: lambda * 10, next iteration) and trying X + step; a trial with a view of S without z > 0 has
+ *   infinite cost; a trial whose cost is finite and strictly lower is accepted (lambda / 10) and ends the loop when it
+ *   lowered the cost by no more than 1e-6 of it or sqrt((s0*s0 + s1*s1) + s2*s2) <= 1e-9; any other trial: lambda * 10.
+ *   max_iters = 0 leaves the midpoint.
+ *  4 Classify, over all of U at X: a view with z > 0 has err = sqrt(e0*e0 + e1*e1) and is an inlier when err <=
+ *   threshold_px; a view without z > 0 is an outlier with err = -1.  All of U inliers: step 5.  Else, after the first pass
+ *   and with at least min_views inliers: steps 2 and 3 once more with S = the inliers, then U is classified again at the
+ *   new X; there is exactly one such reselection.  Fewer than min_views inliers at the end: RPE_TRACKPT_OUTLIERS.
+ *  5 Parallax.  r = c - X per inlier view; min_cos = the smallest of 1 and, for every inlier view but the first,
+ *   (r1 . r) / (sqrt(r1 . r1) * sqrt(r . r)) with r1 that of the first inlier view.  min_cos > max_cos:
+ *   RPE_TRACKPT_LOW_PARALLAX (max_cos = 1 switches the gate off), else RPE_TRACKPT_OK.
+ *  Outputs (host, any may be NULL): points[3 * n_tracks], in the frame of the poses; info[4 * n_tracks] = {RPE_TRACKPT_*
+ *   code, |U|, inliers, LM iterations begun over both rounds}; rms[n_tracks] = sqrt((sum over the inliers of (e0*e0 +
+ *   e1*e1)) / inliers), pixels; min_cos[n_tracks]; obs_flag[n_obs]: 0 not used, 1 inlier, 2 outlier; obs_err[n_obs]: err,
+ *   0 where not used.  By code: OK and LOW_PARALLAX return everything.  OUTLIERS returns the last X, the flags, err and rms
+ *   (0 without an inlier) and min_cos = 0.  BEHIND (either round) returns the midpoint it was found at, flags 2 for all of
+ *   U, and zero err, rms, min_cos and inlier count.  TOO_FEW and DEGENERATE (either round) return zeros: point, flags,
+ *   err, rms, min_cos, inlier count.
+ * Bit-deterministic: one thread walks a track's observations in order, so there is no reduction tree and no atomic.  The
+ * call uses device buffers of its own, created on the first call and grown to the largest call; neither the workspace nor
+ * the record of the last run is touched: every fetch of the run and every call behind it returns the same bits afterwards.
+ * RPE_ERR_INVALID: n_tracks < 0; a NULL input that is read (n_tracks > 0: track_start, R_abs, T_abs; n_obs > 0: obs_frame,
+ * obs_xy); track_start[0] != 0 or track_start decreasing; n_frames < 1; a frame index outside 0 .. n_frames - 1; both or
+ * neither of K / cams; a camera with a non-finite field, fx <= 0 or fy <= 0; threshold_px not finite or <= 0; min_views < 2;
+ * max_cos outside (-1, 1]; max_iters outside 0 .. 100; a non-finite pose entry of a frame whose group is >= 0.  All checks
+ * are host-side; nothing is launched and the handle stays usable after a refusal.  n_tracks == 0 passes the scalar checks,
+ * succeeds and writes nothing. */
+enum { RPE_TRACKPT_OK = 0, RPE_TRACKPT_TOO_FEW = 1, RPE_TRACKPT_DEGENERATE = 2, RPE_TRACKPT_BEHIND = 3, RPE_TRACKPT_OUTLIERS = 4,
+       RPE_TRACKPT_LOW_PARALLAX = 5 };
+int rpe_triangulate_tracks(rpe_handle *h, int n_tracks, const int32_t *track_start, const int32_t *obs_frame, const float *obs_xy,
+                           int n_frames, const double *R_abs, const double *T_abs, const int32_t *frame_group, const double *K,
+                           const rpe_camera *cams, double threshold_px, int min_views, double max_cos, int max_iters,
+                           double *points, int32_t *info, double *rms, double *min_cos, uint8_t *obs_flag, double *obs_err);
+
 /* ---------------------------------------------------------- stage entry */
 /* replaces extractor.detectAndCompute(image, None) (pose_estimator.py:108)
  * for n_images images (n_images <= 2*max_batch).  kps[n_images*cap],

@@ -33,6 +33,9 @@ LINKPOSE_OK, LINKPOSE_PAIR_FAILED, LINKPOSE_TOO_FEW, LINKPOSE_NONE = 0, 1, 2, 3 
 BUNDLE_OK, BUNDLE_PAIR_FAILED, BUNDLE_TOO_FEW, BUNDLE_SKIPPED, BUNDLE_REJECTED = 0, 1, 2, 3, 4   # info[:, 0] of link_bundles (RPE_BUNDLE_*)
 TRACK_EDGES_USABLE, TRACK_EDGES_RANSAC, TRACK_EDGES_ALL = 0, 1, 2   # edge_rule of build_tracks (RPE_TRACK_EDGES_*)
 TRACK_COUNTS = ("n_tracks", "n_obs", "n_edges", "dropped_conflict", "dropped_short", "n_frames_seen")   # counts[6] of the track calls
+# info[:, 0] / 'code' of triangulate_tracks (RPE_TRACKPT_*)
+TRACKPT_OK, TRACKPT_TOO_FEW, TRACKPT_DEGENERATE, TRACKPT_BEHIND, TRACKPT_OUTLIERS, TRACKPT_LOW_PARALLAX = 0, 1, 2, 3, 4, 5
+TRACKPT_NAMES = ("OK", "TOO_FEW", "DEGENERATE", "BEHIND", "OUTLIERS", "LOW_PARALLAX")
 UNDISTORT_ITERS = 5               # RPE_UNDISTORT_ITERS: fixed-point rounds of the camera path's undistortion
 
 # The binding, one entry per function of include/rpe_amd.h: "<return>:<one letter per parameter>".  Parameters: p pointer or
@@ -59,6 +62,7 @@ _SIGNATURES = {
     "rpe_fetch_match_indices": "i:pipp", "rpe_scale_links": "i:pipppippp", "rpe_link_poses": "i:pipppidiipppppp",
     "rpe_link_bundles": "i:pipppppdiippppppppp", "rpe_bundle_three_view": "i:pippppppppppddippppppppp",
     "rpe_last_run_pairs": "i:p", "rpe_build_tracks": "i:ppiipppppp", "rpe_tracks_from_matches": "i:piippppppppipppppp",
+    "rpe_triangulate_tracks": "i:pipppipppppdidipppppp",
     "rpe_guided_matches": "i:pippdipppppp",
     "rpe_guided_matches_l2": "i:pippddpppppp",
     "rpe_pair_homographies": "i:piidppppp", "rpe_find_homography": "i:ppppipidppppp",
@@ -531,6 +535,41 @@ class Engine:
         p2 = None if pts2 is None else pad(pts2, 2, np.float32)
         return self._tracks(P, lambda *o: self.lib.rpe_tracks_from_matches(
             self.h, P, int(n_frames), _p(f1), _p(f2), _p(m), _p(q), _p(t), _opt(e), _opt(p1), _opt(p2), int(min_len), *o))
+
+    # ---- track points (rpe_triangulate_tracks; not in the reference)
+    def triangulate_tracks(self, tracks, R_abs, T_abs, K=None, cameras=None, frame_group=None, threshold_px=2.0, min_views=2,
+                           max_cos=1.0, max_iters=10):
+        """One scene point per track from all its views (rpe_triangulate_tracks).  tracks: the dict build_tracks returns
+        ('track_start', 'obs_frame' and 'obs_xy' are read); R_abs [F, 3, 3], T_abs [F, 3]: world-to-camera poses
+        x = R X + T per frame, as geometry.chain_trajectory returns them; exactly one of K (one camera) and cameras (one
+        Camera, or F of them); frame_group i32[F]: frames of one value >= 0 share a scale, negative = no pose, None = all
+        in one group (geometry.frame_groups gives a chain's).  A track uses the views of its first group, is solved by a
+        midpoint start and Levenberg-Marquardt, loses the views beyond threshold_px and is solved once more.  Returns a
+        dict: 'points' f64[n, 3] in the frame of the poses, 'code' (TRACKPT_*), 'n_used', 'n_inliers', 'iterations'
+        i32[n], 'rms' f64[n] (px, over the inliers), 'min_cos' f64[n] (smallest cosine between the rays of two inlier
+        views; above max_cos the code is TRACKPT_LOW_PARALLAX), 'obs_flag' u8[n_obs] (0 not used, 1 inlier, 2 outlier),
+        'obs_err' f64[n_obs] (px; -1 behind the camera).  The last run stays fetchable."""
+        ts, of = _i32(tracks['track_start']), _i32(tracks['obs_frame'])
+        xy = np.ascontiguousarray(tracks['obs_xy'], np.float32).reshape(-1, 2)
+        R = np.ascontiguousarray(np.asarray(R_abs, np.float64).reshape(-1, 9))
+        T = np.ascontiguousarray(np.asarray(T_abs, np.float64).reshape(-1, 3))
+        F, n = R.shape[0], ts.size - 1
+        if n < 0 or T.shape[0] != F or of.size != xy.shape[0] or (n >= 0 and ts.size and int(ts[-1]) != of.size):
+            raise ValueError("triangulate_tracks: track_start must end at the number of observations, and R_abs and T_abs hold one pose per frame")
+        if (K is None) == (cameras is None):
+            raise ValueError("triangulate_tracks: exactly one of K and cameras must be given")
+        g = None if frame_group is None else _i32(frame_group)
+        if g is not None and g.size != F:
+            raise ValueError(f"triangulate_tracks: frame_group must have one entry per frame ({F}), got {g.size}")
+        k = None if K is None else _f64(K).reshape(9)
+        cams = None if cameras is None else camera_records(cameras, F)
+        pts = np.zeros((n, 3)); info = np.zeros((n, 4), np.int32); rms = np.zeros(n); mc = np.zeros(n)
+        flag = np.zeros(of.size, np.uint8); err = np.zeros(of.size)
+        self._chk(self.lib.rpe_triangulate_tracks(self.h, n, _p(ts), _p(of), _p(xy), F, _p(R), _p(T), _opt(g), _opt(k), _opt(cams),
+                                                  float(threshold_px), int(min_views), float(max_cos), int(max_iters),
+                                                  _p(pts), _p(info), _p(rms), _p(mc), _p(flag), _p(err)))
+        return {'points': pts, 'code': info[:, 0].copy(), 'n_used': info[:, 1].copy(), 'n_inliers': info[:, 2].copy(),
+                'iterations': info[:, 3].copy(), 'rms': rms, 'min_cos': mc, 'obs_flag': flag, 'obs_err': err}
 
     # ---- guided matching (rpe_guided_matches / rpe_match_hamming_guided; not in the reference)
     def _poses(self, B, R, t):

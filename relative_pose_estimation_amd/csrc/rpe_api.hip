@@ -2082,6 +2082,102 @@ extern "C" int rpe_undistort_points(rpe_handle *h, const float *h_pts, int n, co
     return RPE_OK;
 }
 
+// ---------------------------------------------------------------- track points (rpe_triangulate_tracks)
+// the buffers of one call, each grown to the largest call seen (tracks_regrow: every call ends in a wait on the stream)
+static int track_points_alloc(rpe_handle *h, size_t n_tracks, size_t n_obs, size_t n_frames)
+{
+    int rc = RPE_OK;
+    if (n_tracks > h->tp_cap_tracks) {
+        h->tp_cap_tracks = 0;
+        if (!rc) rc = tracks_regrow(h, &h->d_tp_tstart, n_tracks + 1);
+        if (!rc) rc = tracks_regrow(h, &h->d_tp_points, 3 * n_tracks);
+        if (!rc) rc = tracks_regrow(h, &h->d_tp_info, 4 * n_tracks);
+        if (!rc) rc = tracks_regrow(h, &h->d_tp_rms, n_tracks);
+        if (!rc) rc = tracks_regrow(h, &h->d_tp_mincos, n_tracks);
+        if (rc) return rc;
+        h->tp_cap_tracks = n_tracks;
+    }
+    if (n_obs > h->tp_cap_obs) {
+        h->tp_cap_obs = 0;
+        if (!rc) rc = tracks_regrow(h, &h->d_tp_oframe, n_obs);
+        if (!rc) rc = tracks_regrow(h, &h->d_tp_oxy, n_obs);
+        if (!rc) rc = tracks_regrow(h, &h->d_tp_obs, 5 * n_obs);
+        if (!rc) rc = tracks_regrow(h, &h->d_tp_oflag, n_obs);
+        if (!rc) rc = tracks_regrow(h, &h->d_tp_oerr, n_obs);
+        if (rc) return rc;
+        h->tp_cap_obs = n_obs;
+    }
+    if (n_frames > h->tp_cap_frames) {
+        h->tp_cap_frames = 0;
+        if (!rc) rc = tracks_regrow(h, &h->d_tp_R, 9 * n_frames);
+        if (!rc) rc = tracks_regrow(h, &h->d_tp_T, 3 * n_frames);
+        if (!rc) rc = tracks_regrow(h, &h->d_tp_group, n_frames);
+        if (!rc) rc = tracks_regrow(h, &h->d_tp_cams, n_frames);
+        if (rc) return rc;
+        h->tp_cap_frames = n_frames;
+    }
+    return RPE_OK;
+}
+
+// Every check on the host first, the buffers, the uploads, the two kernels, the fetch.  Neither the workspace nor the record
+// of the last run is touched.
+extern "C" int rpe_triangulate_tracks(rpe_handle *h, int n_tracks, const int32_t *track_start, const int32_t *obs_frame, const float *obs_xy,
+                                      int n_frames, const double *R_abs, const double *T_abs, const int32_t *frame_group, const double *K,
+                                      const rpe_camera *cams, double threshold_px, int min_views, double max_cos, int max_iters,
+                                      double *points, int32_t *info, double *rms, double *min_cos, uint8_t *obs_flag, double *obs_err)
+{
+    const char *who = "rpe_triangulate_tracks";
+    if (!h) return rpe_invalid(h, who);
+    if (n_tracks < 0) return rpe_invalid(h, who, "n_tracks must be >= 0");
+    if (n_frames < 1) return rpe_invalid(h, who, "n_frames must be >= 1");
+    if ((K == nullptr) == (cams == nullptr)) return rpe_invalid(h, who, "exactly one of K and cams must be given");
+    if (!std::isfinite(threshold_px) || !(threshold_px > 0.)) return rpe_invalid(h, who, "threshold_px must be finite and > 0");
+    if (min_views < 2) return rpe_invalid(h, who, "min_views must be >= 2");
+    if (!(max_cos > -1. && max_cos <= 1.)) return rpe_invalid(h, who, "max_cos must lie in (-1, 1]");
+    if (max_iters < 0 || max_iters > 100) return rpe_invalid(h, who, "max_iters must be 0 ... 100");
+    if (K) h->tp_cam_k = rpe_camera{K[0], K[4], K[2], K[5], {0., 0., 0., 0., 0., 0., 0., 0.}};
+    if (int rc = K ? check_cameras(h, &h->tp_cam_k, 1, who) : check_cameras(h, cams, n_frames, who)) return rc;
+    if (track_start) {
+        if (track_start[0] != 0) return rpe_invalid(h, who, "track_start[0] must be 0");
+        for (int k = 0; k < n_tracks; ++k)
+            if (track_start[k + 1] < track_start[k]) return rpe_invalid(h, who, "track_start must not decrease");
+    }
+    if (n_tracks == 0) return RPE_OK;
+    if (!track_start || !R_abs || !T_abs) return rpe_invalid(h, who);
+    const size_t nt = (size_t)n_tracks, no = (size_t)track_start[n_tracks], nf = (size_t)n_frames;
+    if (no > 0 && (!obs_frame || !obs_xy)) return rpe_invalid(h, who);
+    for (size_t o = 0; o < no; ++o)
+        if (obs_frame[o] < 0 || obs_frame[o] >= n_frames) return rpe_invalid(h, who, "a frame index outside 0 ... n_frames - 1");
+    for (size_t f = 0; f < nf; ++f) {
+        if (frame_group && frame_group[f] < 0) continue;
+        bool fin = true;
+        for (int k = 0; k < 9; ++k) fin = fin && std::isfinite(R_abs[f * 9 + k]);
+        for (int k = 0; k < 3; ++k) fin = fin && std::isfinite(T_abs[f * 3 + k]);
+        if (!fin) return rpe_invalid(h, who, "a non-finite pose of a frame that has a group");
+    }
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (int rc = track_points_alloc(h, nt, std::max(no, (size_t)1), nf)) return rc;
+    const hipStream_t s = h->stream;
+    HIPCHK(h, hipMemcpyAsync(h->d_tp_tstart, track_start, sizeof(int) * (nt + 1), hipMemcpyHostToDevice, s));
+    if (no > 0) {
+        HIPCHK(h, hipMemcpyAsync(h->d_tp_oframe, obs_frame, sizeof(int) * no, hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipMemcpyAsync(h->d_tp_oxy, obs_xy, sizeof(float2) * no, hipMemcpyHostToDevice, s));
+    }
+    HIPCHK(h, hipMemcpyAsync(h->d_tp_R, R_abs, sizeof(double) * 9 * nf, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(h->d_tp_T, T_abs, sizeof(double) * 3 * nf, hipMemcpyHostToDevice, s));
+    if (frame_group) HIPCHK(h, hipMemcpyAsync(h->d_tp_group, frame_group, sizeof(int) * nf, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(h->d_tp_cams, K ? &h->tp_cam_k : cams, sizeof(rpe_camera) * (K ? 1 : nf), hipMemcpyHostToDevice, s));
+    const RpeTrackPointJob job = {n_tracks, (int)no, min_views, max_iters, K ? 0 : 1, threshold_px, max_cos,
+                                  h->d_tp_tstart, h->d_tp_oframe, frame_group ? h->d_tp_group : nullptr, h->d_tp_oxy,
+                                  h->d_tp_R, h->d_tp_T, h->d_tp_cams};
+    rpe_launch_track_points(h, job);
+    HIPCHK(h, hipGetLastError());
+    // the wait also covers the uploads: the inputs have left the caller's arrays
+    return fetch(h, {{points, h->d_tp_points, sizeof(double) * 3 * nt}, {info, h->d_tp_info, sizeof(int) * 4 * nt},
+                     {rms, h->d_tp_rms, sizeof(double) * nt}, {min_cos, h->d_tp_mincos, sizeof(double) * nt},
+                     {obs_flag, h->d_tp_oflag, no}, {obs_err, h->d_tp_oerr, sizeof(double) * no}});
+}
+
 // ---------------------------------------------------------------- stage API: geometry
 // findEssentialMat, recoverPose and the refinement over uploaded points, each on one K (rpe_*) or on a camera per side and
 // pair (rpe_*_cameras, K == nullptr here).  Head of the three: capacity, cameras, points and intrinsics resident; `run`

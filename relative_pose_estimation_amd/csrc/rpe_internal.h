@@ -245,6 +245,14 @@ __device__ __forceinline__ int block_count(int cnt, int *s_cnt /*[4]*/)
     return (s_cnt[0] + s_cnt[1]) + (s_cnt[2] + s_cnt[3]);
 }
 
+// this thread's index in a one-thread-per-item launch of 256-thread workgroups, -1 past n.  The product is 64-bit, so the
+// bound holds for every n an int can be
+__device__ __forceinline__ int tk_thread_index(int n)
+{
+    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+    return i < n ? (int)i : -1;
+}
+
 struct RpeTile { short level, tx, ty, pad; };
 // destination tile of the resize kernel: its origin, the origin of its source window in the level below, the number of
 // source rows its destination rows read (nsrc <= PYR_ROWS; window rows past it are neither loaded nor stored) and the rows
@@ -314,6 +322,17 @@ struct RpeTrackJob {
 };
 #define RPE_TRACK_NODE_WORDS 11   // int arrays of one word per node in d_tk_node
 static inline int rpe_track_scan_blocks(int N) { return (int)(((long long)N + 2047) / 2048); }   // workgroups of the track scans (2048 nodes each)
+
+// One job of the track-point kernels (track_point_kernels.hip): the uploaded tracks, poses, groups (null: all 0) and cameras
+// (cam_stride 1: one per frame; 0: the one record K became)
+struct RpeTrackPointJob {
+    int n_tracks, n_obs, min_views, max_iters, cam_stride;
+    double threshold_px, max_cos;
+    const int *track_start, *obs_frame, *group;
+    const float2 *obs_xy;
+    const double *R, *T;
+    const rpe_camera *cams;
+};
 
 // One rpe_scale_links link on the device: pairs a and b of the last run, side bit 0 / 1 = the shared frame is image 2 of a / of b
 struct RpeLink { int a, b, side, pad; };
@@ -448,6 +467,17 @@ struct rpe_handle {
     int *d_tk_node = nullptr, *d_tk_seen = nullptr;
     int tk_nodes = 0, tk_frames = 0;
     std::vector<int> tk_frame_tab;        // host side of d_tk_frames: source of its upload
+    // rpe_triangulate_tracks only (created on first use, each grown to the largest call: tp_cap_*).  Per track: the CSR
+    // offsets in, point, info[4], rms, min_cos out.  Per observation: frame and pixel in, the 80-byte record between the two
+    // kernels, flag and error out.  Per frame: R, T, group, camera (tp_cam_k: the host side of the one record K becomes)
+    int *d_tp_tstart = nullptr, *d_tp_oframe = nullptr, *d_tp_group = nullptr, *d_tp_info = nullptr;
+    float2 *d_tp_oxy = nullptr;
+    double2 *d_tp_obs = nullptr;          // [5 * n_obs]: one 80-byte record per observation
+    double *d_tp_R = nullptr, *d_tp_T = nullptr, *d_tp_points = nullptr, *d_tp_rms = nullptr, *d_tp_mincos = nullptr, *d_tp_oerr = nullptr;
+    uint8_t *d_tp_oflag = nullptr;
+    rpe_camera *d_tp_cams = nullptr;
+    rpe_camera tp_cam_k{};
+    size_t tp_cap_tracks = 0, tp_cap_obs = 0, tp_cap_frames = 0;
     // the kernels of geom_kernels.hip and link_kernels.hip whose dynamic-LDS limit a launch of this handle has raised
     // (raise_lds_limit, geom_device.h): the attribute is per device, so the record is per handle
     std::vector<const void *> lds_raised;
@@ -598,6 +628,7 @@ int rpe_launch_bundle_gather(rpe_handle *h, const RpeRun &r, int L, double thres
 void rpe_launch_bundle(rpe_handle *h, int n, int min_shared, int max_iters, bool links);
 bool rpe_bundles_in_lds(const rpe_handle *h);
 void rpe_launch_tracks(rpe_handle *h, const RpeTrackJob &job);
+void rpe_launch_track_points(rpe_handle *h, const RpeTrackPointJob &job);
 void rpe_launch_normalise(rpe_handle *h, const RpeRun &r);
 int rpe_launch_homography(rpe_handle *h, const RpeRun &r, int iters, double threshold_px, bool from_batch);
 void rpe_launch_undistort(rpe_handle *h, const float2 *d_pts, int n, const rpe_camera *d_cam, double2 *d_out);

@@ -38,14 +38,6 @@ struct TkArgs {
 constexpr int TK_NONE = 0x7FFFFFFF;      // first-edge word of a node without an edge
 constexpr int TK_SCAN_ITEMS = 2048;      // nodes per workgroup of the scans: 8 rounds of 256
 
-// this thread's index in a one-thread-per-item launch of 256-thread workgroups, -1 past n.  The product is 64-bit, so the
-// bound holds for every n an int can be
-__device__ __forceinline__ int tk_thread_index(int n)
-{
-    const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-    return i < n ? (int)i : -1;
-}
-
 __global__ __launch_bounds__(256) void tk_init_kernel(const TkArgs a)
 {
     const long long id = (long long)blockIdx.x * 256 + threadIdx.x;      // 64-bit: the bound holds for every N an int can be

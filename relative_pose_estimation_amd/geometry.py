@@ -108,6 +108,32 @@ def chain_trajectory(R_rel, t_rel, status, ratio, code):
     return R_abs, T_abs, centers, baseline, segment
 
 
+def frame_groups(status, segment):
+    """The scale group of each of the F = P + 1 frames of a chain (frame_group of _capi.Engine.triangulate_tracks), from
+    the status[P] the chain was built with and the segment[P] chain_trajectory returned; pure host code.
+    g[0] = segment[0]; g[i + 1] = segment[i] where pair i is OK (status 0): the pair placed frame i + 1, on its own
+    baseline.  Where pair i failed the chain only repeated frame i's pose, so frame i + 1 is related to nothing before
+    it: it is the origin of the segment pair i + 1 starts, g[i + 1] = segment[i + 1], or -1 (no pose) when pair i is the
+    last.
+
+    A frame between two OK pairs whose link failed lies in two segments: it ends the earlier one and is the origin of the
+    later one.  One integer cannot say both, and it goes with the EARLIER: there its position is a measured one (pair i's
+    baseline, which is what a triangulation needs to be on the scale of the other frames), while as an origin it fixes
+    nothing but the later segment's gauge.  A track's group is that of its first observation and observations are ordered
+    by frame, so a track crossing the boundary keeps this frame's view with the earlier views.  The price: the later
+    segment is seen from its second frame on, and a later segment of one pair has a single frame and gives no points."""
+    status = np.asarray(status).reshape(-1)
+    segment = np.asarray(segment, np.int32).reshape(-1)
+    P = status.size
+    if P < 1 or segment.size != P:
+        raise ValueError(f"frame_groups: status and segment must have one entry per pair, got {P} and {segment.size}")
+    g = np.empty(P + 1, np.int32)
+    g[0] = segment[0]
+    for i in range(P):
+        g[i + 1] = segment[i] if status[i] == 0 else (segment[i + 1] if i + 1 < P else -1)
+    return g
+
+
 def registered_chain_inputs(R_rel, t_rel, status, ratio, code, R_link, t_link, link_pose_code):
     """chain_trajectory's five inputs with pair i + 1 taken from link pose i (_capi.Engine.link_poses over the links
     (i, i + 1, 1)) where link_pose_code[i] is 0 (LINKPOSE_OK): R_link[i], t_link[i] / |t_link[i]| (zero when the link pose

@@ -395,7 +395,18 @@ class PoseEstimator:
         one pair -- estimate() -- is the stream of its two images: frame 0 is image 1, frame 1 is image 2."""
         return self._last_engine.build_tracks(use_pair, edge_rule, min_len)
 
-    def estimate_trajectory(self, frames, min_shared=8, register=False, bundle=False, tracks=False):
+    def last_track_points(self, R_abs, T_abs, frame_group=None, tracks=None, **gates):
+        """One scene point per track from all its views under the absolute poses R_abs [F, 3, 3], T_abs [F, 3]
+        (x = R X + T; not in the reference; _capi.Engine.triangulate_tracks, whose dict it returns).  tracks: a dict of
+        last_tracks / build_tracks, None = last_tracks() with its defaults; a frame of the tracks indexes the poses.
+        frame_group: see geometry.frame_groups.  The camera is the estimator's: its K, or its Camera (one for all frames)
+        when it was built with dist_coeffs.  gates: threshold_px, min_views, max_cos, max_iters of triangulate_tracks."""
+        if tracks is None:
+            tracks = self.last_tracks()
+        cam = {'cameras': self._camera} if self._camera is not None else {'K': self.K}
+        return self._last_engine.triangulate_tracks(tracks, R_abs, T_abs, frame_group=frame_group, **cam, **gates)
+
+    def estimate_trajectory(self, frames, min_shared=8, register=False, bundle=False, tracks=False, points=False):
         """estimate_sequence plus what relates its poses (not in the reference): the scale link of every two consecutive
         pairs and the chained trajectory (geometry.chain_trajectory).  Returns a dict: 'R', 't', 'inliers', 'status' of
         the F - 1 pairs; 'ratio_stats' [F-2, 3], 'n_shared' [F-2], 'link_code' [F-2] of the links; 'R_abs' [F, 3, 3],
@@ -410,7 +421,11 @@ class PoseEstimator:
         (pair i + 1's pose on pair i's scale), 'bundle_code' [F-2], 'bundle_counts' [F-2, 2], and 'R_abs_ba' [F, 3, 3],
         'centers_ba' [F, 3]: the registered chain with the bundle's pose where its code is BUNDLE_OK, the link pose
         elsewhere.
-        tracks=True adds 'tracks': the feature tracks of the sequence (last_tracks with its defaults)."""
+        tracks=True adds 'tracks': the feature tracks of the sequence (last_tracks with its defaults).
+        points=True implies tracks and adds 'points': the dict of last_track_points (its defaults) over those tracks under
+        the best chain built, plus 'chain', the key of that chain's rotations ('R_abs_ba' with bundle, else 'R_abs_reg'
+        with register, else 'R_abs'), and the 'T_abs' [F, 3] and 'frame_group' [F] (geometry.frame_groups of that chain)
+        it was run with.  Points of different groups are on unrelated scales."""
         if self._camera is not None:
             raise ValueError("estimate_trajectory: the camera path has no stream form; use estimate_pairs and last_scale_links")
         R, t, inl, st = self.estimate_sequence(frames)
@@ -420,22 +435,30 @@ class PoseEstimator:
         R_abs, T_abs, centers, baseline, segment = geometry.chain_trajectory(R, t, st, stats[:, 1], code)
         out = {'R': R, 't': t, 'inliers': inl, 'status': st, 'ratio_stats': stats, 'n_shared': n_shared, 'link_code': code,
                'R_abs': R_abs, 'T_abs': T_abs, 'centers': centers, 'baseline': baseline, 'segment': segment}
+        best = ('R_abs', T_abs, st, segment)      # the chain the points are triangulated under: key, T, status, segment
         if register or bundle:
             Rl, tl, _, counts, info, _ = self._last_engine.link_poses(i, i + 1, np.ones(P - 1, np.int32), min_shared=min_shared)
             Rr, tr, sr, ratio, cr = geometry.registered_chain_inputs(R, t, st, stats[:, 1], code, Rl, tl, info[:, 0])
             reg = geometry.chain_trajectory(Rr, tr, sr, ratio, cr)
             out.update({'R_link': Rl, 't_link': tl, 'link_pose_code': info[:, 0], 'link_pose_counts': counts,
                         'R_abs_reg': reg[0], 'centers_reg': reg[2]})
+            best = ('R_abs_reg', reg[1], sr, reg[4])
         if bundle:
             one = np.ones(P - 1, np.int32)
             ba = self._last_engine.link_bundles(i, i + 1, one, Rl, tl, min_shared=min_shared)
             ok = ba[7][:, 0] == 0
             Rb = np.where(ok[:, None, None], ba[2], Rl); tb = np.where(ok[:, None], ba[3], tl)
-            chain = geometry.chain_trajectory(*geometry.registered_chain_inputs(R, t, st, stats[:, 1], code, Rb, tb, info[:, 0]))
+            ba_in = geometry.registered_chain_inputs(R, t, st, stats[:, 1], code, Rb, tb, info[:, 0])
+            chain = geometry.chain_trajectory(*ba_in)
             out.update({'R_bundle': ba[2], 't_bundle': ba[3], 'bundle_code': ba[7][:, 0], 'bundle_counts': ba[6],
                         'R_abs_ba': chain[0], 'centers_ba': chain[2]})
-        if tracks:
+            best = ('R_abs_ba', chain[1], ba_in[2], chain[4])
+        if tracks or points:
             out['tracks'] = self._last_engine.build_tracks()
+        if points:
+            group = geometry.frame_groups(best[2], best[3])
+            out['points'] = self.last_track_points(out[best[0]], best[1], group, out['tracks'])
+            out['points'].update({'chain': best[0], 'T_abs': best[1], 'frame_group': group})
         return out
 
     def estimate_sequence(self, frames):

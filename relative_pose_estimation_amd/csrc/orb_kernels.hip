@@ -20,6 +20,7 @@
 #include "rpe_internal.h"
 #include "rpe_devmath.h"
 #include "retain_best_emul.h"
+#include "fast_entry.h"
 
 __device__ float4 c_pattern_f[256];         // rBRIEF pattern (brief_pattern.inc) as f32 (x0, y0, x1, y1), uploaded at handle creation
 
@@ -304,6 +305,8 @@ constexpr int FAST_NRP = 14;                 // rows of the 18-dword tile row th
 constexpr int FAST_LANES = FAST_NRP * 18;    // the 252 lanes that load pixels and run phase 1
 constexpr int FAST_NCAND = FS_ROWS * 72;     // candidate list capacity: one entry per score-area pixel at most
 static_assert(FAST_LANES <= FAST_THREADS, "a pass of FAST_NRP tile rows fits the workgroup");
+static_assert(FAST_ENTRY_NRP == FAST_NRP && FAST_ENTRY_LANES == FAST_LANES && FAST_ENTRY_PITCH == 72 && FAST_ENTRY_NPASS == 5,
+              "fast_entry.h describes this kernel's lane mapping");
 static_assert(6 * FAST_NRP >= FAST_PROWS && 5 * FAST_NRP >= FS_ROWS, "6 load passes cover the pixel rows, 5 phase-1 passes the score rows");
 static_assert(RPE_FAST_TILE_CAP == (64 / 2) * (FAST_TH / 2), "strict 3x3 maxima of a tile");
 static_assert(RPE_FAST_TILE_CAP <= FAST_PROWS * 18, "the tile's keypoint list lives in the dead pixel tile");
@@ -343,14 +346,16 @@ __global__ __launch_bounds__(FAST_THREADS) void fast_nms_kernel(const uint8_t *_
     const uint8_t *src = rpe_level_base(pyr, lay, blockIdx.y, t.level);
     if (tid == 0) { s_ncand = 0; s_nout = 0; }
     {   // all tile loads in flight before the first LDS store.  lane -> fixed dword column (tid % 18) and rows
-        // tid / 18 + 14 q: one column clamp and one division per tile instead of one per load
+        // tid / 18 + 14 q: one column clamp and one division per tile instead of one per load.  Only the upper clamps
+        // exist (last tile row and column): a FAST tile starts at x0 >= FAST_TILE_X0 = 28 and y0 >= RPE_EDGE = 31
+        // (build_tables checks its table against both), so x0 - 4 and y0 - 4 are never negative
         const int lc = tid % 18, lr = tid / 18;
-        const int lx = min(max(x0 - 4 + 4 * lc, 0), pitch - 4);
+        const int lx = min(x0 - 4 + 4 * lc, pitch - 4);
         unsigned stage[6];
 #pragma unroll
         for (int q = 0; q < 6; ++q) {
             const int r = min(lr + FAST_NRP * q, FAST_PROWS - 1);
-            const int y = min(max(y0 - 4 + r, 0), hgt - 1);
+            const int y = min(y0 - 4 + r, hgt - 1);
             stage[q] = *(const unsigned *)(src + (__umul24((unsigned)y, (unsigned)pitch) + (unsigned)lx));
         }
         // pin the loads above the guarded stores (the compiler sinks a load into the block of its store: dependent round trips)
@@ -384,6 +389,10 @@ __global__ __launch_bounds__(FAST_THREADS) void fast_nms_kernel(const uint8_t *_
         // instead of 14 for the compact 4-bit form; the x-validity mask is applied once, spread to bytes).  The darker side
         // is kept inverted ("no darker arc") until the five rows are done
         const unsigned vmask5 = ((vmask * 0x00204081u) & 0x01010101u) * 0x1Fu;
+        // The compiler pairs the 11 dwords of a row into four ds_read2_b32 + three ds_read_b32; a pass is 252 dwords and a
+        // ds_read2 offset ends at 255, so rows 1-4 pay four address additions each.  Eleven single ds_read_b32 (volatile LDS
+        // pointers; their 16-bit byte offset reaches every pass) took the additions out and were not faster: four more
+        // LDS instructions a row cost what the four additions did
         const unsigned *pC = s_in + (r0 + 3) * 18 + c, *pL = s_in + (r0 + 3) * 18 + cl, *pR = s_in + (r0 + 3) * 18 + cr;
 #pragma unroll
         for (int it = 0; it < 5; ++it) {
@@ -446,10 +455,14 @@ __global__ __launch_bounds__(FAST_THREADS) void fast_nms_kernel(const uint8_t *_
         brt_bits &= vmask5;
     }
     {   // one append per tile: wave prefix sum of the per-lane counts (front | back << 16), one LDS atomic per wave.
-        // List entry (ry << 7) | bx | side bits: 0x4000 darker arc possible, 0x8000 brighter arc possible.  Entries with
-        // the darker side go to the front (0.1 % of them have both bits), brighter-only ones to the back, so the lanes of a
-        // phase-2 round almost always share one side.  Both lists together hold at most one entry per score-area pixel.
-        const unsigned bo_bits = brt_bits & ~dark_bits;
+        // List entry in lane form (fast_entry.h): (tid << 5) | bit position | side bits, 0x4000 darker arc possible, 0x8000
+        // brighter arc possible -- the lane's part with the side bits is one register, so a trip is find-first-set, clear
+        // the bit, or, store, advance.  Entries with the darker side go to the front, brighter-only ones to the back, so
+        // the lanes of a phase-2 round almost always share one side.  The 0.1 % with both sides possible follow the
+        // darker-only ones at the front in a loop of their own, which most waves skip: taking the brighter flag out of
+        // brt_bits per bit cost every trip of the darker loop two instructions.  Both lists together hold at most one
+        // entry per score-area pixel.
+        const unsigned both_bits = brt_bits & dark_bits, do_bits = dark_bits & ~brt_bits, bo_bits = brt_bits & ~dark_bits;
         const int n = __popc(dark_bits) | (__popc(bo_bits) << 16);
         const int inc = wave_inclusive_sum(n);
         const int total = __shfl(inc, 63);
@@ -457,21 +470,23 @@ __global__ __launch_bounds__(FAST_THREADS) void fast_nms_kernel(const uint8_t *_
             int base = 0;
             if (lane == 63) base = atomicAdd(&s_ncand, total);
             const int pre = __shfl(base, 63) + inc - n;
-            // one loop per side: choosing the side per bit inside one loop cost 20 instructions per trip instead of ~10,
-            // more than the trips it saves
-            int posF = pre & 0xFFFF, posB = FAST_NCAND - 1 - (pre >> 16);
-            unsigned bits = dark_bits;
-            while (bits) {
-                const int bpos = __ffs((int)bits) - 1;
-                bits &= bits - 1;
-                s_cand[posF++] = (unsigned short)(((r0 + FAST_NRP * (bpos & 7)) << 7) | (4 * c + (bpos >> 3)) | 0x4000 | (((brt_bits >> bpos) & 1u) << 15));
-            }
-            bits = bo_bits;
-            while (bits) {
-                const int bpos = __ffs((int)bits) - 1;
-                bits &= bits - 1;
-                s_cand[posB--] = (unsigned short)(((r0 + FAST_NRP * (bpos & 7)) << 7) | (4 * c + (bpos >> 3)) | 0x8000);
-            }
+            // one loop per kind of entry: choosing the side per bit inside one loop cost 20 instructions per trip instead
+            // of ~10, more than the trips it saves
+            unsigned short *wF = s_cand + (pre & 0xFFFF), *wB = s_cand + (FAST_NCAND - 1 - (pre >> 16));
+            const unsigned ebase = fast_entry_lane_base((unsigned)tid);
+            auto append = [&](unsigned bits, unsigned sides, unsigned short *&w, int step) {
+                unsigned e = fast_entry_lane(ebase, 0u, sides);
+                asm("" : "+v"(e));           // one register for the loop: left alone the constant is or-ed in again on every trip
+                while (bits) {
+                    const unsigned bpos = (unsigned)__ffs((int)bits) - 1u;
+                    bits &= bits - 1;
+                    *w = (unsigned short)(e | bpos);
+                    w += step;
+                }
+            };
+            append(do_bits, FAST_ENTRY_DARK, wF, 1);
+            append(both_bits, FAST_ENTRY_SIDES, wF, 1);
+            append(bo_bits, FAST_ENTRY_BRIGHT, wB, -1);
         }
     }
     __syncthreads();
@@ -493,8 +508,9 @@ __global__ __launch_bounds__(FAST_THREADS) void fast_nms_kernel(const uint8_t *_
         int cc = 0;
         if (j < je) {
             cc = s_cand[j < nF ? j : j + gap];
-            const int bx = cc & 127, ry = (cc >> 7) & 127;
-            const uint8_t *p = sb + (ry + 3) * 72 + bx;
+            // lane form: the byte offset 72 ry + bx of the pixel comes straight from the entry's fields (fast_entry.h)
+            const unsigned off = fast_entry_offset((unsigned)cc);
+            const uint8_t *p = sb + 3 * 72 + off;
             const int v = p[0];
             int r[16];
 #pragma unroll
@@ -526,12 +542,13 @@ __global__ __launch_bounds__(FAST_THREADS) void fast_nms_kernel(const uint8_t *_
                 s = max(s, m - v);
             }
             if (s > thr) {
-                ((uint8_t *)s_sc)[ry * 72 + bx] = (uint8_t)(s - 1);
+                ((uint8_t *)s_sc)[off] = (uint8_t)(s - 1);
                 corner = true;
             }
         }
         const unsigned long long km = __ballot(corner);
-        if (corner) s_cand[cb + ncorner + __popcll(km & ((1ull << lane) - 1ull))] = (unsigned short)cc;
+        // a corner goes back in compact form (ry << 7) | bx | side bits, which is what phase 3 reads
+        if (corner) s_cand[cb + ncorner + __popcll(km & ((1ull << lane) - 1ull))] = (unsigned short)fast_entry_to_compact((unsigned)cc);
         ncorner += __popcll(km);
     }
     __syncthreads();
@@ -545,7 +562,7 @@ __global__ __launch_bounds__(FAST_THREADS) void fast_nms_kernel(const uint8_t *_
         unsigned ent = 0;
         if (i < ncorner) {
             const int cc = s_cand[cb + i];
-            const int bx = cc & 127, ry = (cc >> 7) & 127;
+            const int bx = (int)fast_entry_compact_bx((unsigned)cc), ry = (int)fast_entry_compact_ry((unsigned)cc);
             const int px = x0 - 4 + bx, py = y0 - 1 + ry;
             // branch-free: the eight neighbour reads go out together (as a short-circuit chain they were nine dependent LDS
             // round trips with an exec-mask save / restore each); reads of halo corners past the score tile land in

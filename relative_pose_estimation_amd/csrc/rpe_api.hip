@@ -183,9 +183,12 @@ static int build_tables(rpe_handle *h)
         if (v.w > 2 * RPE_EDGE && v.h > 2 * RPE_EDGE)
             // keypoints survive the border filter on [31, w-31) x [31, h-31) only; x origin dword aligned
             for (int y = RPE_EDGE; y < v.h - RPE_EDGE; y += FAST_TH)
-                for (int x = RPE_EDGE & ~3; x < v.w - RPE_EDGE; x += 64) fast.push_back({(short)l, (short)x, (short)y, 0});
+                for (int x = FAST_TILE_X0; x < v.w - RPE_EDGE; x += 64) fast.push_back({(short)l, (short)x, (short)y, 0});
         h->lay.lv[l].ntile = (int)fast.size() - h->lay.lv[l].tile0;
     }
+    // fast_nms_kernel loads pixels from (tx - 4, ty - 4) on and clamps only against the level's far edges
+    for (const RpeTile &t : fast)
+        if (t.tx < 4 || t.ty < 4) { h->err = "FAST tile origin below 4: the tile loads would start outside the level"; return RPE_ERR_INVALID; }
     h->n_tiles_full = (int)full.size(); h->n_tiles_fast = (int)fast.size();
     DM(h, h->d_tiles_full, full.size());
     DM(h, h->d_tiles_fast, fast.size() ? fast.size() : 1);

@@ -30,6 +30,11 @@ static const size_t kRpeResultElem[RPE_RESULT_SECTIONS] = {9 * sizeof(double), 3
 // FAST tile = 64 x FAST_TH output pixels, 4 waves.  FAST is bound by instruction issue, not by latency like the resize
 // kernel, and 32-row tiles with two waves only added halo work when they were tried: 4.43 -> 4.79 ms.
 constexpr int FAST_TH = 64;
+// The FAST tiles of a level start at (FAST_TILE_X0, RPE_EDGE): keypoints survive the border filter on [31, w - 31) x
+// [31, h - 31) only, and the x origin is dword aligned.  The kernel loads a 4-pixel halo to the left of and above a tile
+// without clamping at 0, which needs both origins >= 4.
+constexpr int FAST_TILE_X0 = RPE_EDGE & ~3;
+static_assert(FAST_TILE_X0 >= 4 && RPE_EDGE >= 4, "the FAST tile loads do not clamp x0 - 4 and y0 - 4 at 0");
 constexpr int RPE_FAST_TILE_CAP = 1024;   // entries of one FAST tile list: the most strict 3x3 maxima a 64 x 64 tile can hold (32 x 32)
 // Resize tile = PYR_TW x PYR_TH destination pixels, one wave; its source window in the level below is PYR_ROWS rows of
 // PYR_DW dwords (336 B = 21 16-byte loads, origin aligned down to 16 B).  build_tables checks every tile of a handle

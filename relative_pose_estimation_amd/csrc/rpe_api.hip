@@ -65,6 +65,41 @@ static int fetch(rpe_handle *h, std::initializer_list<Fetch> pieces)
     return RPE_OK;
 }
 
+// ---- the buffer set of a first-use feature, fitted to one call (the rule: rpe_internal.h)
+int rpe_bufset_fit(rpe_handle *h, RpeBufSet &s, std::initializer_list<RpeBufPiece> pieces)
+{
+    RpeBufLayout need;
+    for (const RpeBufPiece &pc : pieces) need.place(pc.bytes);
+    if (need.total() > s.bytes) {
+        uint8_t *old = s.block;
+        if (old) HIPCHK(h, hipStreamSynchronize(h->stream));
+        s = {};
+        for (const RpeBufPiece &pc : pieces) *pc.p = nullptr;
+        h->dev_allocs.erase(std::remove(h->dev_allocs.begin(), h->dev_allocs.end(), (void *)old), h->dev_allocs.end());
+        if (old) HIPCHK(h, hipFree(old));
+        if (int rc = dmalloc(h, &s.block, need.total())) return rc;
+        s.bytes = need.total();
+    }
+    RpeBufLayout at;
+    for (const RpeBufPiece &pc : pieces) {
+        const size_t off = at.place(pc.bytes);
+        *pc.p = off == RPE_BUF_NONE ? nullptr : s.block + off;
+    }
+    return RPE_OK;
+}
+
+// ---- argument heads of the calls behind a run: a parameter that must be finite and > 0, an array that must be finite
+static int check_positive(rpe_handle *h, const char *who, const char *name, double v)
+{
+    return std::isfinite(v) && v > 0. ? RPE_OK : rpe_invalid(h, who, (std::string(name) + " must be finite and > 0").c_str());
+}
+static bool all_finite(const double *v, size_t n)
+{
+    bool fin = true;
+    for (size_t i = 0; i < n; ++i) fin = fin && std::isfinite(v[i]);
+    return fin;
+}
+
 static long long align_up(long long v, long long a) { return (v + a - 1) / a * a; }
 
 extern "C" void rpe_default_config(rpe_config *c)
@@ -1031,10 +1066,8 @@ extern "C" int rpe_fetch_match_indices(rpe_handle *h, int B, int32_t *qidx, int3
 // iters and threshold_px of the calls that run a RANSAC of their own behind the last run (homography, link poses)
 static int homography_check(rpe_handle *h, const char *who, int iters, double threshold_px)
 {
-    const std::string w(who);
-    if (iters < 1 || iters > h->cfg.ransac_max_iters) { h->err = w + ": iters must be 1 ... ransac_max_iters"; return RPE_ERR_INVALID; }
-    if (!std::isfinite(threshold_px) || !(threshold_px > 0.)) { h->err = w + ": threshold_px must be finite and > 0"; return RPE_ERR_INVALID; }
-    return RPE_OK;
+    if (iters < 1 || iters > h->cfg.ransac_max_iters) return rpe_invalid(h, who, "iters must be 1 ... ransac_max_iters");
+    return check_positive(h, who, "threshold_px", threshold_px);
 }
 
 // The argument head of the calls over links (rpe_scale_links, rpe_link_poses, rpe_link_bundles): every check on the host first (the kept
@@ -1071,19 +1104,33 @@ static int links_begin(rpe_handle *h, const char *who, int L, const int32_t *pai
     return RPE_OK;
 }
 
+static int scale_links_alloc(rpe_handle *h)
+{
+    const size_t lcap = (size_t)rpe_link_capacity(h);
+    return rpe_bufset_fit(h, h->set_links, {buf_piece(h->d_link_stats, lcap * 3), buf_piece(h->d_link_n, lcap), buf_piece(h->d_link_code, lcap)});
+}
+
 extern "C" int rpe_scale_links(rpe_handle *h, int L, const int32_t *pair_a, const int32_t *pair_b, const int32_t *side,
                                int min_shared, double *stats, int32_t *n_shared, int32_t *code)
 {
     if (!h) return rpe_invalid(h, "rpe_scale_links");
     int rc = links_begin(h, "rpe_scale_links", L, pair_a, pair_b, side, min_shared);
     if (rc != RPE_OK || L == 0) return rc;
-    const size_t lcap = (size_t)rpe_link_capacity(h);
-    DM_ONCE(h, h->d_link_stats, lcap * 3);
-    DM_ONCE(h, h->d_link_n, lcap); DM_ONCE(h, h->d_link_code, lcap);
+    if ((rc = scale_links_alloc(h)) != RPE_OK) return rc;
     if ((rc = rpe_launch_scale_links(h, L, min_shared)) != RPE_OK) return rpe_lds_unsized(h, "rpe_scale_links", rc);
     HIPCHK(h, hipGetLastError());
     return fetch(h, {{stats, h->d_link_stats, sizeof(double) * 3 * (size_t)L}, {n_shared, h->d_link_n, sizeof(int) * (size_t)L},
                      {code, h->d_link_code, sizeof(int) * (size_t)L}});
+}
+
+// d_lp_corr: 0 bytes, so null, on handles whose kernel keeps the correspondence lists in LDS
+static int link_poses_alloc(rpe_handle *h)
+{
+    const size_t lcap = (size_t)rpe_link_capacity(h), mm = (size_t)h->cfg.max_matches;
+    return rpe_bufset_fit(h, h->set_link_poses,
+                          {buf_piece(h->d_lp_R, lcap * 9), buf_piece(h->d_lp_t, lcap * 3), buf_piece(h->d_lp_rms, lcap * 2),
+                           buf_piece(h->d_lp_counts, lcap * 2), buf_piece(h->d_lp_info, lcap * 4), buf_piece(h->d_lp_mask, lcap * mm),
+                           buf_piece(h->d_lp_corr, rpe_link_poses_in_lds(h) ? 0 : lcap * 5 * mm)});
 }
 
 // rpe_link_poses: the links' argument head, its own three checks (all before anything is launched), the buffers on first
@@ -1098,28 +1145,25 @@ extern "C" int rpe_link_poses(rpe_handle *h, int L, const int32_t *pair_a, const
     if (refine_iters < 0 || refine_iters > 100) return rpe_invalid(h, "rpe_link_poses", "refine_iters must be 0 ... 100");
     rc = links_begin(h, "rpe_link_poses", L, pair_a, pair_b, side, min_shared);
     if (rc != RPE_OK || L == 0) return rc;
-    const size_t lcap = (size_t)rpe_link_capacity(h), mm = (size_t)h->cfg.max_matches;
-    DM_ONCE(h, h->d_lp_R, lcap * 9); DM_ONCE(h, h->d_lp_t, lcap * 3); DM_ONCE(h, h->d_lp_rms, lcap * 2);
-    DM_ONCE(h, h->d_lp_counts, lcap * 2); DM_ONCE(h, h->d_lp_info, lcap * 4); DM_ONCE(h, h->d_lp_mask, lcap * mm);
-    if (!rpe_link_poses_in_lds(h)) DM_ONCE(h, h->d_lp_corr, lcap * 5 * mm);
+    if ((rc = link_poses_alloc(h)) != RPE_OK) return rc;
     if ((rc = rpe_launch_link_poses(h, h->last.run, L, iters, threshold_px, min_shared, refine_iters)) != RPE_OK) return rpe_lds_unsized(h, "rpe_link_poses", rc);
     HIPCHK(h, hipGetLastError());
-    const size_t n = (size_t)L;
+    const size_t n = (size_t)L, mm = (size_t)h->cfg.max_matches;
     return fetch(h, {{R, h->d_lp_R, sizeof(double) * 9 * n}, {t, h->d_lp_t, sizeof(double) * 3 * n}, {mask, h->d_lp_mask, n * mm},
                      {counts, h->d_lp_counts, sizeof(int) * 2 * n}, {info, h->d_lp_info, sizeof(int) * 4 * n}, {rms, h->d_lp_rms, sizeof(double) * 2 * n}});
 }
 
-// link bundles: the buffers of both forms on first use
+// link bundles: the buffers of both forms; d_ba_state: 0 bytes, so null, on handles whose kernel keeps the point state in LDS
 static int bundle_alloc(rpe_handle *h)
 {
     const size_t lcap = (size_t)rpe_link_capacity(h), mm = (size_t)h->cfg.max_matches;
-    DM_ONCE(h, h->d_ba_views, lcap * mm); DM_ONCE(h, h->d_ba_obs, lcap * mm * 6); DM_ONCE(h, h->d_ba_points, lcap * mm * 3);
-    DM_ONCE(h, h->d_ba_pose0, lcap * 24); DM_ONCE(h, h->d_ba_focal, lcap * 2); DM_ONCE(h, h->d_ba_n, lcap); DM_ONCE(h, h->d_ba_pre, lcap);
-    DM_ONCE(h, h->d_ba_Rin, lcap * 9); DM_ONCE(h, h->d_ba_tin, lcap * 3);
-    DM_ONCE(h, h->d_ba_Ra, lcap * 9); DM_ONCE(h, h->d_ba_ta, lcap * 3); DM_ONCE(h, h->d_ba_Rb, lcap * 9); DM_ONCE(h, h->d_ba_tb, lcap * 3);
-    DM_ONCE(h, h->d_ba_counts, lcap * 2); DM_ONCE(h, h->d_ba_info, lcap * 4); DM_ONCE(h, h->d_ba_rms, lcap * 2);
-    if (!rpe_bundles_in_lds(h)) DM_ONCE(h, h->d_ba_state, lcap * mm * 6);
-    return RPE_OK;
+    return rpe_bufset_fit(h, h->set_bundles,
+                          {buf_piece(h->d_ba_views, lcap * mm), buf_piece(h->d_ba_obs, lcap * mm * 6), buf_piece(h->d_ba_points, lcap * mm * 3),
+                           buf_piece(h->d_ba_pose0, lcap * 24), buf_piece(h->d_ba_focal, lcap * 2), buf_piece(h->d_ba_n, lcap), buf_piece(h->d_ba_pre, lcap),
+                           buf_piece(h->d_ba_Rin, lcap * 9), buf_piece(h->d_ba_tin, lcap * 3),
+                           buf_piece(h->d_ba_Ra, lcap * 9), buf_piece(h->d_ba_ta, lcap * 3), buf_piece(h->d_ba_Rb, lcap * 9), buf_piece(h->d_ba_tb, lcap * 3),
+                           buf_piece(h->d_ba_counts, lcap * 2), buf_piece(h->d_ba_info, lcap * 4), buf_piece(h->d_ba_rms, lcap * 2),
+                           buf_piece(h->d_ba_state, rpe_bundles_in_lds(h) ? 0 : lcap * mm * 6)});
 }
 
 static int bundle_fetch(rpe_handle *h, size_t n, double *R_a, double *t_a, double *R_b, double *t_b, double *points, uint8_t *views,
@@ -1131,13 +1175,6 @@ static int bundle_fetch(rpe_handle *h, size_t n, double *R_a, double *t_a, doubl
                      {counts, h->d_ba_counts, sizeof(int) * 2 * n}, {info, h->d_ba_info, sizeof(int) * 4 * n}, {rms, h->d_ba_rms, sizeof(double) * 2 * n}});
 }
 
-static bool all_finite(const double *v, size_t n)
-{
-    bool fin = true;
-    for (size_t i = 0; i < n; ++i) fin = fin && std::isfinite(v[i]);
-    return fin;
-}
-
 // rpe_link_bundles: its own checks and the links' argument head (all before anything is launched), the buffers on first
 // use, the poses of pair b up, two kernels, one fetch.  Nothing of the run is written.
 extern "C" int rpe_link_bundles(rpe_handle *h, int L, const int32_t *pair_a, const int32_t *pair_b, const int32_t *side,
@@ -1146,7 +1183,7 @@ extern "C" int rpe_link_bundles(rpe_handle *h, int L, const int32_t *pair_a, con
                                 int32_t *counts, int32_t *info, double *rms)
 {
     if (!h) return rpe_invalid(h, "rpe_link_bundles");
-    if (!std::isfinite(threshold_px) || !(threshold_px > 0.)) return rpe_invalid(h, "rpe_link_bundles", "threshold_px must be finite and > 0");
+    if (int rc = check_positive(h, "rpe_link_bundles", "threshold_px", threshold_px)) return rc;
     if (max_iters < 1 || max_iters > 100) return rpe_invalid(h, "rpe_link_bundles", "max_iters must be 1 ... 100");
     if ((R0 == nullptr) != (t0 == nullptr) || (L > 0 && !R0)) return rpe_invalid(h, "rpe_link_bundles", "R0 and t0 must both be given");
     const size_t n = (size_t)std::max(L, 0);
@@ -1210,40 +1247,18 @@ extern "C" int rpe_bundle_three_view(rpe_handle *h, int B, const int32_t *n, con
 }
 
 // ---- multi-view tracks (rpe_build_tracks / rpe_tracks_from_matches)
-// A buffer that grows: the old one leaves the handle's record and is freed (every track call ends in a wait on the stream,
-// so nothing is in flight on it)
-template <typename T>
-static int tracks_regrow(rpe_handle *h, T **p, size_t n)
-{
-    if (*p) {
-        h->dev_allocs.erase(std::remove(h->dev_allocs.begin(), h->dev_allocs.end(), (void *)*p), h->dev_allocs.end());
-        HIPCHK(h, hipFree(*p));
-        *p = nullptr;
-    }
-    return dmalloc(h, p, n);
-}
-
-// the buffers of both forms: per match slot on first use, per node and per frame grown to n_frames
+// the buffers of both forms: per match slot, then per node and per frame of this call's n_frames
 static int tracks_alloc(rpe_handle *h, int n_frames)
 {
     const size_t MB = (size_t)h->cfg.max_batch, cap = MB * h->cfg.max_matches;
-    DM_ONCE(h, h->d_tk_eflag, cap); DM_ONCE(h, h->d_tk_edge, cap); DM_ONCE(h, h->d_tk_use, MB);
-    DM_ONCE(h, h->d_tk_mtrack, cap); DM_ONCE(h, h->d_tk_q, cap); DM_ONCE(h, h->d_tk_t, cap); DM_ONCE(h, h->d_tk_m, MB);
-    DM_ONCE(h, h->d_tk_counts, 8); DM_ONCE(h, h->d_tk_tstart, cap + 1); DM_ONCE(h, h->d_tk_oframe, 2 * cap); DM_ONCE(h, h->d_tk_okp, 2 * cap);
-    DM_ONCE(h, h->d_tk_oxy, 2 * cap); DM_ONCE(h, h->d_tk_pts1, cap); DM_ONCE(h, h->d_tk_pts2, cap); DM_ONCE(h, h->d_tk_frames, MB);
     const int N = n_frames * h->lay.kcap;
-    if (N > h->tk_nodes) {
-        h->tk_nodes = 0;
-        if (int rc = tracks_regrow(h, &h->d_tk_node, (size_t)RPE_TRACK_NODE_WORDS * N)) return rc;
-        if (int rc = tracks_regrow(h, &h->d_tk_partial, (size_t)rpe_track_scan_blocks(N))) return rc;
-        h->tk_nodes = N;
-    }
-    if (n_frames > h->tk_frames) {
-        h->tk_frames = 0;
-        if (int rc = tracks_regrow(h, &h->d_tk_seen, (size_t)n_frames)) return rc;
-        h->tk_frames = n_frames;
-    }
-    return RPE_OK;
+    return rpe_bufset_fit(h, h->set_tracks,
+                          {buf_piece(h->d_tk_eflag, cap), buf_piece(h->d_tk_edge, cap), buf_piece(h->d_tk_use, MB),
+                           buf_piece(h->d_tk_mtrack, cap), buf_piece(h->d_tk_q, cap), buf_piece(h->d_tk_t, cap), buf_piece(h->d_tk_m, MB),
+                           buf_piece(h->d_tk_counts, 8), buf_piece(h->d_tk_tstart, cap + 1), buf_piece(h->d_tk_oframe, 2 * cap), buf_piece(h->d_tk_okp, 2 * cap),
+                           buf_piece(h->d_tk_oxy, 2 * cap), buf_piece(h->d_tk_pts1, cap), buf_piece(h->d_tk_pts2, cap), buf_piece(h->d_tk_frames, MB),
+                           buf_piece(h->d_tk_node, (size_t)RPE_TRACK_NODE_WORDS * N), buf_piece(h->d_tk_partial, (size_t)rpe_track_scan_blocks(N)),
+                           buf_piece(h->d_tk_seen, (size_t)n_frames)});
 }
 
 // min_len, and the node ids and edge ids of n_frames frames must fit an int.  frames_what: the refusal in the caller's terms
@@ -1359,10 +1374,9 @@ extern "C" int rpe_tracks_from_matches(rpe_handle *h, int P, int n_frames, const
 static int refine_alloc(rpe_handle *h)
 {
     const size_t MB = (size_t)h->cfg.max_batch;
-    DM_ONCE(h, h->d_ref_R, MB * 9); DM_ONCE(h, h->d_ref_t, MB * 3); DM_ONCE(h, h->d_ref_rms, MB * 2);
-    DM_ONCE(h, h->d_ref_R0, MB * 9); DM_ONCE(h, h->d_ref_t0, MB * 3);
-    DM_ONCE(h, h->d_ref_inl, MB); DM_ONCE(h, h->d_ref_info, MB * 4);
-    return RPE_OK;
+    return rpe_bufset_fit(h, h->set_refine,
+                          {buf_piece(h->d_ref_R, MB * 9), buf_piece(h->d_ref_t, MB * 3), buf_piece(h->d_ref_rms, MB * 2),
+                           buf_piece(h->d_ref_R0, MB * 9), buf_piece(h->d_ref_t0, MB * 3), buf_piece(h->d_ref_inl, MB), buf_piece(h->d_ref_info, MB * 4)});
 }
 
 static int refine_run(rpe_handle *h, const RpeRun &r, int max_iters, bool from_batch, double *R, double *t, int32_t *inliers,
@@ -1379,7 +1393,7 @@ extern "C" int rpe_refine_poses(rpe_handle *h, int B, int max_iters, double *R, 
                                 int32_t *info, double *rms)
 {
     if (!h || B < 1 || B > h->cfg.max_batch) return rpe_invalid(h, "rpe_refine_poses");
-    if (max_iters < 1 || max_iters > 100) { h->err = "rpe_refine_poses: max_iters must be 1 ... 100"; return RPE_ERR_INVALID; }
+    if (max_iters < 1 || max_iters > 100) return rpe_invalid(h, "rpe_refine_poses", "max_iters must be 1 ... 100");
     int rc = last_run_gate(h, "rpe_refine_poses", B, NEED_UNCHUNKED | NEED_PER_MATCH | NEED_COUNT);
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -1400,29 +1414,23 @@ static int guided_check(rpe_handle *h, const char *who, int norm, int B, const d
         h->err = w + (l2 ? ": L2 handles only (RPE_NORM_L2: SIFT, or ORB bytes under L2)" : ": Hamming handles only (ORB with RPE_NORM_HAMMING)");
         return RPE_ERR_INVALID;
     }
-    if (!std::isfinite(gate_px) || !(gate_px > 0.)) { h->err = w + ": gate_px must be finite and > 0"; return RPE_ERR_INVALID; }
+    if (int rc = check_positive(h, who, "gate_px", gate_px)) return rc;
     if (l2 ? !(max_distance >= 0.) : (max_distance < 0 || max_distance > 256)) {
         h->err = w + (l2 ? ": max_distance must be >= 0 (+inf: no bound)" : ": max_distance must be 0 ... 256");
         return RPE_ERR_INVALID;
     }
     if ((R == nullptr) != (t == nullptr)) { h->err = w + ": R and t must both be given or both be NULL"; return RPE_ERR_INVALID; }
-    if (R) {
-        bool fin = true;
-        for (int i = 0; i < 9 * B; ++i) fin = fin && std::isfinite(R[i]);
-        for (int i = 0; i < 3 * B; ++i) fin = fin && std::isfinite(t[i]);
-        if (!fin) { h->err = w + ": a pose has a non-finite entry"; return RPE_ERR_INVALID; }
-    }
+    if (R && (!all_finite(R, (size_t)9 * B) || !all_finite(t, (size_t)3 * B))) { h->err = w + ": a pose has a non-finite entry"; return RPE_ERR_INVALID; }
     return RPE_OK;
 }
 
 static int guided_alloc(rpe_handle *h)
 {
     const size_t MB = (size_t)h->cfg.max_batch, cap = MB * h->cfg.max_matches;
-    DM_ONCE(h, h->d_gm_q, cap); DM_ONCE(h, h->d_gm_t, cap); DM_ONCE(h, h->d_gm_d, cap); DM_ONCE(h, h->d_gm_n, MB);
-    DM_ONCE(h, h->d_gm_pts1, cap); DM_ONCE(h, h->d_gm_pts2, cap);
-    DM_ONCE(h, h->d_gm_R, MB * 9); DM_ONCE(h, h->d_gm_tr, MB * 3); DM_ONCE(h, h->d_gm_thr2, MB);
-    DM_ONCE(h, h->d_gm_rec, MB * 2 * h->lay.kcap);
-    return RPE_OK;
+    return rpe_bufset_fit(h, h->set_guided,
+                          {buf_piece(h->d_gm_q, cap), buf_piece(h->d_gm_t, cap), buf_piece(h->d_gm_d, cap), buf_piece(h->d_gm_n, MB),
+                           buf_piece(h->d_gm_pts1, cap), buf_piece(h->d_gm_pts2, cap), buf_piece(h->d_gm_R, MB * 9), buf_piece(h->d_gm_tr, MB * 3), buf_piece(h->d_gm_thr2, MB),
+                           buf_piece(h->d_gm_rec, MB * 2 * h->lay.kcap)});
 }
 
 // poses up (R == nullptr: the run's own, and its status words), launch, fetch
@@ -1533,10 +1541,9 @@ extern "C" int rpe_match_l2_guided(rpe_handle *h, const float *h_desc1, const fl
 static int homography_alloc(rpe_handle *h)
 {
     const size_t MB = (size_t)h->cfg.max_batch;
-    DM_ONCE(h, h->d_hg_H, MB * 9); DM_ONCE(h, h->d_hg_R, MB * 9);
-    DM_ONCE(h, h->d_hg_counts, MB * 3); DM_ONCE(h, h->d_hg_info, MB * 4);
-    DM_ONCE(h, h->d_hg_mask, MB * h->cfg.max_matches);
-    return RPE_OK;
+    return rpe_bufset_fit(h, h->set_homography,
+                          {buf_piece(h->d_hg_H, MB * 9), buf_piece(h->d_hg_R, MB * 9), buf_piece(h->d_hg_counts, MB * 3), buf_piece(h->d_hg_info, MB * 4),
+                           buf_piece(h->d_hg_mask, MB * h->cfg.max_matches)});
 }
 
 static int homography_run(rpe_handle *h, const RpeRun &r, int iters, double threshold_px, bool from_batch, double *H, double *R_rot,
@@ -2086,40 +2093,14 @@ extern "C" int rpe_undistort_points(rpe_handle *h, const float *h_pts, int n, co
 }
 
 // ---------------------------------------------------------------- track points (rpe_triangulate_tracks)
-// the buffers of one call, each grown to the largest call seen (tracks_regrow: every call ends in a wait on the stream)
+// the buffers of one call: per track, per observation, per frame
 static int track_points_alloc(rpe_handle *h, size_t n_tracks, size_t n_obs, size_t n_frames)
 {
-    int rc = RPE_OK;
-    if (n_tracks > h->tp_cap_tracks) {
-        h->tp_cap_tracks = 0;
-        if (!rc) rc = tracks_regrow(h, &h->d_tp_tstart, n_tracks + 1);
-        if (!rc) rc = tracks_regrow(h, &h->d_tp_points, 3 * n_tracks);
-        if (!rc) rc = tracks_regrow(h, &h->d_tp_info, 4 * n_tracks);
-        if (!rc) rc = tracks_regrow(h, &h->d_tp_rms, n_tracks);
-        if (!rc) rc = tracks_regrow(h, &h->d_tp_mincos, n_tracks);
-        if (rc) return rc;
-        h->tp_cap_tracks = n_tracks;
-    }
-    if (n_obs > h->tp_cap_obs) {
-        h->tp_cap_obs = 0;
-        if (!rc) rc = tracks_regrow(h, &h->d_tp_oframe, n_obs);
-        if (!rc) rc = tracks_regrow(h, &h->d_tp_oxy, n_obs);
-        if (!rc) rc = tracks_regrow(h, &h->d_tp_obs, 5 * n_obs);
-        if (!rc) rc = tracks_regrow(h, &h->d_tp_oflag, n_obs);
-        if (!rc) rc = tracks_regrow(h, &h->d_tp_oerr, n_obs);
-        if (rc) return rc;
-        h->tp_cap_obs = n_obs;
-    }
-    if (n_frames > h->tp_cap_frames) {
-        h->tp_cap_frames = 0;
-        if (!rc) rc = tracks_regrow(h, &h->d_tp_R, 9 * n_frames);
-        if (!rc) rc = tracks_regrow(h, &h->d_tp_T, 3 * n_frames);
-        if (!rc) rc = tracks_regrow(h, &h->d_tp_group, n_frames);
-        if (!rc) rc = tracks_regrow(h, &h->d_tp_cams, n_frames);
-        if (rc) return rc;
-        h->tp_cap_frames = n_frames;
-    }
-    return RPE_OK;
+    return rpe_bufset_fit(h, h->set_track_points,
+                          {buf_piece(h->d_tp_tstart, n_tracks + 1), buf_piece(h->d_tp_points, 3 * n_tracks), buf_piece(h->d_tp_info, 4 * n_tracks),
+                           buf_piece(h->d_tp_rms, n_tracks), buf_piece(h->d_tp_mincos, n_tracks),
+                           buf_piece(h->d_tp_oframe, n_obs), buf_piece(h->d_tp_oxy, n_obs), buf_piece(h->d_tp_obs, 5 * n_obs), buf_piece(h->d_tp_oflag, n_obs), buf_piece(h->d_tp_oerr, n_obs),
+                           buf_piece(h->d_tp_R, 9 * n_frames), buf_piece(h->d_tp_T, 3 * n_frames), buf_piece(h->d_tp_group, n_frames), buf_piece(h->d_tp_cams, n_frames)});
 }
 
 // Every check on the host first, the buffers, the uploads, the two kernels, the fetch.  Neither the workspace nor the record
@@ -2134,7 +2115,7 @@ extern "C" int rpe_triangulate_tracks(rpe_handle *h, int n_tracks, const int32_t
     if (n_tracks < 0) return rpe_invalid(h, who, "n_tracks must be >= 0");
     if (n_frames < 1) return rpe_invalid(h, who, "n_frames must be >= 1");
     if ((K == nullptr) == (cams == nullptr)) return rpe_invalid(h, who, "exactly one of K and cams must be given");
-    if (!std::isfinite(threshold_px) || !(threshold_px > 0.)) return rpe_invalid(h, who, "threshold_px must be finite and > 0");
+    if (int rc = check_positive(h, who, "threshold_px", threshold_px)) return rc;
     if (min_views < 2) return rpe_invalid(h, who, "min_views must be >= 2");
     if (!(max_cos > -1. && max_cos <= 1.)) return rpe_invalid(h, who, "max_cos must lie in (-1, 1]");
     if (max_iters < 0 || max_iters > 100) return rpe_invalid(h, who, "max_iters must be 0 ... 100");
@@ -2153,10 +2134,7 @@ extern "C" int rpe_triangulate_tracks(rpe_handle *h, int n_tracks, const int32_t
         if (obs_frame[o] < 0 || obs_frame[o] >= n_frames) return rpe_invalid(h, who, "a frame index outside 0 ... n_frames - 1");
     for (size_t f = 0; f < nf; ++f) {
         if (frame_group && frame_group[f] < 0) continue;
-        bool fin = true;
-        for (int k = 0; k < 9; ++k) fin = fin && std::isfinite(R_abs[f * 9 + k]);
-        for (int k = 0; k < 3; ++k) fin = fin && std::isfinite(T_abs[f * 3 + k]);
-        if (!fin) return rpe_invalid(h, who, "a non-finite pose of a frame that has a group");
+        if (!all_finite(R_abs + f * 9, 9) || !all_finite(T_abs + f * 3, 3)) return rpe_invalid(h, who, "a non-finite pose of a frame that has a group");
     }
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (int rc = track_points_alloc(h, nt, std::max(no, (size_t)1), nf)) return rc;
@@ -2302,7 +2280,7 @@ extern "C" int rpe_refine_pose_points(rpe_handle *h, const double *h_R0, const d
 {
     if (!h || !h_R0 || !h_t0 || !h_pts1 || !h_pts2 || !h_mask || !m || !K || B < 1) return rpe_invalid(h, "rpe_refine_pose_points");
     if (int rc = check_batch(h, B)) return rc;      // in front of max_iters, as ever
-    if (max_iters < 1 || max_iters > 100) { h->err = "rpe_refine_pose_points: max_iters must be 1 ... 100"; return RPE_ERR_INVALID; }
+    if (max_iters < 1 || max_iters > 100) return rpe_invalid(h, "rpe_refine_pose_points", "max_iters must be 1 ... 100");
     return stage_refine(h, "rpe_refine_pose_points", h_R0, h_t0, h_pts1, h_pts2, h_mask, m, B, K, nullptr, nullptr, max_iters, R, t, inliers, info, rms);
 }
 
@@ -2312,7 +2290,7 @@ extern "C" int rpe_refine_pose_points_cameras(rpe_handle *h, const double *h_R0,
                                               int32_t *inliers, int32_t *info, double *rms)
 {
     if (!h || !h_R0 || !h_t0 || !h_pts1 || !h_pts2 || !h_mask || !m || !cam1 || !cam2 || B < 1) return rpe_invalid(h, "rpe_refine_pose_points_cameras");
-    if (max_iters < 1 || max_iters > 100) { h->err = "rpe_refine_pose_points_cameras: max_iters must be 1 ... 100"; return RPE_ERR_INVALID; }
+    if (max_iters < 1 || max_iters > 100) return rpe_invalid(h, "rpe_refine_pose_points_cameras", "max_iters must be 1 ... 100");
     return stage_refine(h, "rpe_refine_pose_points_cameras", h_R0, h_t0, h_pts1, h_pts2, h_mask, m, B, nullptr, cam1, cam2, max_iters, R, t, inliers, info, rms);
 }
 

@@ -6,9 +6,11 @@
 #include <stdint.h>
 #include <stdio.h>
 #include <algorithm>
+#include <initializer_list>
 #include <string>
 #include <vector>
 #include "../../include/rpe_amd.h"
+#include "buf_layout.h"
 
 #define RPE_NLEVELS RPE_ORB_LEVELS
 #define RPE_EDGE 31            // ORB edgeThreshold (cv2 default; pose_estimator.py:85-91 leaves it)
@@ -354,6 +356,9 @@ struct RpeLinkSrc {
     int max_matches, kcap;
 };
 
+// The device buffers of one first-use feature: one hipMalloc, carved into the feature's d_* fields by rpe_bufset_fit (below)
+struct RpeBufSet { uint8_t *block = nullptr; size_t bytes = 0; };
+
 struct rpe_handle {
     rpe_config cfg;
     RpeSiftState *sift = nullptr;             // SIFT workspace (feature_method == RPE_FEATURE_SIFT)
@@ -420,59 +425,58 @@ struct rpe_handle {
     uint8_t *d_mask = nullptr;            // [pair][max_matches]
     uint8_t *d_pose_mask = nullptr;       // [pair][max_matches] rpe_fetch_structure only (created on first use)
     double *d_points = nullptr;           // [pair][max_matches][3] rpe_fetch_structure only (created on first use)
-    // rpe_refine_poses / rpe_refine_pose_points only (created on first use): refined pose, cheirality count, info[4], rms[2]
-    // per pair; start pose of the stage form
+    // rpe_refine_poses / rpe_refine_pose_points only (set_refine, fitted on first use): refined pose, cheirality count,
+    // info[4], rms[2] per pair; start pose of the stage form
     double *d_ref_R = nullptr, *d_ref_t = nullptr, *d_ref_rms = nullptr, *d_ref_R0 = nullptr, *d_ref_t0 = nullptr;
-    int *d_ref_inl = nullptr, *d_ref_info = nullptr;
-    // rpe_scale_links only (created on first use): link table and outputs, 4*max_batch links
+    int *d_ref_inl = nullptr, *d_ref_info = nullptr; RpeBufSet set_refine;
+    // the link calls' table (created on first use) and rpe_scale_links' outputs (set_links, fitted on first use), 4*max_batch links
     RpeLink *d_links = nullptr;
     std::vector<RpeLink> link_tab;        // host side of d_links: the table of the last link call, source of its upload
     double *d_link_stats = nullptr;       // [link][3] lower quartile, median, upper quartile
-    int *d_link_n = nullptr, *d_link_code = nullptr;
+    int *d_link_n = nullptr, *d_link_code = nullptr; RpeBufSet set_links;
     // the guided matchers of either norm only (rpe_guided_matches[_l2], rpe_match_hamming_guided, rpe_match_l2_guided;
-    // created on first use): match lists of their own, shaped like the run's d_m_* / d_pts* (d_gm_d: int32 Hamming
+    // set_guided, fitted on first use): match lists of their own, shaped like the run's d_m_* / d_pts* (d_gm_d: int32 Hamming
     // distances, or f32 L2 distances in the same four bytes); the poses gated with when the caller supplies them; per pair and image one 32-byte record per
     // keypoint [pair][2][kcap] and the squared threshold (see guided_records_kernel)
     int *d_gm_q = nullptr, *d_gm_t = nullptr, *d_gm_d = nullptr, *d_gm_n = nullptr;
     float2 *d_gm_pts1 = nullptr, *d_gm_pts2 = nullptr;
     double *d_gm_R = nullptr, *d_gm_tr = nullptr, *d_gm_thr2 = nullptr;
-    double4 *d_gm_rec = nullptr;
-    // rpe_pair_homographies / rpe_find_homography only (created on first use): H, R_rot, {n_H, n_rot, n_E} and info[4] per
-    // pair, the winner's inlier mask [pair][max_matches]
+    double4 *d_gm_rec = nullptr; RpeBufSet set_guided;
+    // rpe_pair_homographies / rpe_find_homography only (set_homography, fitted on first use): H, R_rot, {n_H, n_rot, n_E}
+    // and info[4] per pair, the winner's inlier mask [pair][max_matches]
     double *d_hg_H = nullptr, *d_hg_R = nullptr;
     int *d_hg_counts = nullptr, *d_hg_info = nullptr;
-    uint8_t *d_hg_mask = nullptr;
-    // rpe_link_poses only (created on first use): per link the pose, {n, inliers}, info[4], rms[2] and the inlier mask
-    // [link][max_matches], 4*max_batch links (the link table is rpe_scale_links' d_links); d_lp_corr [link][5 * max_matches]
-    // holds the correspondence lists of handles above the kernel's LDS cut only
+    uint8_t *d_hg_mask = nullptr; RpeBufSet set_homography;
+    // rpe_link_poses only (set_link_poses, fitted on first use): per link the pose, {n, inliers}, info[4], rms[2] and the
+    // inlier mask [link][max_matches], 4*max_batch links (the link table is d_links); d_lp_corr [link][5 * max_matches]
+    // holds the correspondence lists of handles above the kernel's LDS cut only (a piece of 0 bytes, null, on the others)
     double *d_lp_R = nullptr, *d_lp_t = nullptr, *d_lp_rms = nullptr, *d_lp_corr = nullptr;
     int *d_lp_counts = nullptr, *d_lp_info = nullptr;
-    uint8_t *d_lp_mask = nullptr;
-    // rpe_link_bundles / rpe_bundle_three_view only (created on first use), 4*max_batch problems.  The problems' arrays,
+    uint8_t *d_lp_mask = nullptr; RpeBufSet set_link_poses;
+    // rpe_link_bundles / rpe_bundle_three_view only (set_bundles, fitted on first use), 4*max_batch problems.  The problems' arrays,
     // indexed by pair a's match index (stage form: point number): view code [prob][max_matches], observations
     // [prob][max_matches][6] (S, A, C), points [prob][max_matches][3] (start points in, results out); per problem the scan
     // length, the code decided before the bundle, the start poses in the solved form [24] and the focal scales [2]; the
     // callers' poses of pair b; the results; d_ba_state [prob][6 * max_matches] holds the point state of handles above
-    // the kernel's LDS cut only
-    uint8_t *d_ba_views = nullptr;
+    // the kernel's LDS cut only (a piece of 0 bytes, null, on the others)
+    uint8_t *d_ba_views = nullptr; RpeBufSet set_bundles;
     double *d_ba_obs = nullptr, *d_ba_points = nullptr, *d_ba_pose0 = nullptr, *d_ba_focal = nullptr, *d_ba_state = nullptr;
     double *d_ba_Rin = nullptr, *d_ba_tin = nullptr;
     int *d_ba_n = nullptr, *d_ba_pre = nullptr, *d_ba_counts = nullptr, *d_ba_info = nullptr;
     double *d_ba_Ra = nullptr, *d_ba_ta = nullptr, *d_ba_Rb = nullptr, *d_ba_tb = nullptr, *d_ba_rms = nullptr;
-    // rpe_build_tracks / rpe_tracks_from_matches only (created on first use).  Per match slot [max_batch * max_matches]: the
+    // rpe_build_tracks / rpe_tracks_from_matches only (set_tracks, fitted to every call's n_frames).  Per match slot [max_batch * max_matches]: the
     // edge flag and match_track; the stage form's uploaded lists (d_tk_q / _t / _edge / _pts1 / _pts2) and per pair its match
     // count; per pair of either form the frame pair and use_pair.  Outputs: counts[8], track_start [slots + 1], observations
-    // [2 * slots].  Per node: d_tk_node, RPE_TRACK_NODE_WORDS arrays of tk_nodes words, with d_tk_partial (one int2 per scan
-    // workgroup) grown when a larger n_frames * kcap arrives; d_tk_seen [tk_frames] likewise
+    // [2 * slots].  Per node (n_frames * kcap of them): d_tk_node, RPE_TRACK_NODE_WORDS arrays of one word each, with
+    // d_tk_partial (one int2 per scan workgroup); d_tk_seen [n_frames]: the set's last pieces, so n_frames moves no other
     uint8_t *d_tk_eflag = nullptr, *d_tk_edge = nullptr, *d_tk_use = nullptr;
     int *d_tk_mtrack = nullptr, *d_tk_q = nullptr, *d_tk_t = nullptr, *d_tk_m = nullptr, *d_tk_counts = nullptr;
     int *d_tk_tstart = nullptr, *d_tk_oframe = nullptr, *d_tk_okp = nullptr;
     float2 *d_tk_oxy = nullptr, *d_tk_pts1 = nullptr, *d_tk_pts2 = nullptr;
     int2 *d_tk_frames = nullptr, *d_tk_partial = nullptr;
-    int *d_tk_node = nullptr, *d_tk_seen = nullptr;
-    int tk_nodes = 0, tk_frames = 0;
+    int *d_tk_node = nullptr, *d_tk_seen = nullptr; RpeBufSet set_tracks;
     std::vector<int> tk_frame_tab;        // host side of d_tk_frames: source of its upload
-    // rpe_triangulate_tracks only (created on first use, each grown to the largest call: tp_cap_*).  Per track: the CSR
+    // rpe_triangulate_tracks only (set_track_points, fitted to every call's tracks, observations and frames).  Per track: the CSR
     // offsets in, point, info[4], rms, min_cos out.  Per observation: frame and pixel in, the 80-byte record between the two
     // kernels, flag and error out.  Per frame: R, T, group, camera (tp_cam_k: the host side of the one record K becomes)
     int *d_tp_tstart = nullptr, *d_tp_oframe = nullptr, *d_tp_group = nullptr, *d_tp_info = nullptr;
@@ -481,8 +485,7 @@ struct rpe_handle {
     double *d_tp_R = nullptr, *d_tp_T = nullptr, *d_tp_points = nullptr, *d_tp_rms = nullptr, *d_tp_mincos = nullptr, *d_tp_oerr = nullptr;
     uint8_t *d_tp_oflag = nullptr;
     rpe_camera *d_tp_cams = nullptr;
-    rpe_camera tp_cam_k{};
-    size_t tp_cap_tracks = 0, tp_cap_obs = 0, tp_cap_frames = 0;
+    rpe_camera tp_cam_k{}; RpeBufSet set_track_points;
     // the kernels of geom_kernels.hip and link_kernels.hip whose dynamic-LDS limit a launch of this handle has raised
     // (raise_lds_limit, geom_device.h): the attribute is per device, so the record is per handle
     std::vector<const void *> lds_raised;
@@ -534,8 +537,25 @@ static int dmalloc(rpe_handle *h, T **p, size_t n)
     return RPE_OK;
 }
 #define DM(h, p, n) do { int r_ = dmalloc(h, &(p), (size_t)(n)); if (r_) return r_; } while (0)
-// a buffer created on first use
+// a single buffer created on first use
 #define DM_ONCE(h, p, n) do { if (!(p)) DM(h, p, n); } while (0)
+
+// The buffers a feature creates on first use are ONE set of the handle and ONE piece list -- its d_* fields with the sizes
+// THIS call needs -- given to rpe_bufset_fit behind the host-side checks and hipSetDevice, before the first upload:
+//   layout   piece i sits at the running sum of the 256-byte-aligned sizes of the pieces before it; the total is that sum,
+//            and at least 256 (buf_layout.h).  A piece of 0 bytes gets nullptr.
+//   growth   total > set.bytes: wait on the handle's stream if there is a block (growth is rare, and a call that returned
+//            early behind a launch may have left work in flight), take the block out of dev_allocs and free it, empty the
+//            set and null every piece, allocate exactly `total`: freed first, so a growth never holds both blocks.  A
+//            failure returns RPE_ERR_HIP with the set empty and the pointers null: the next call tries again.  No shrinking.
+//   carving  every call assigns every piece from its own sizes: a smaller call is carved smaller inside the same block; sizes
+//            of the configuration alone give a constant total, so those pointers never move after the first call.
+// Nothing in a set outlives its call (inputs are uploaded or written by the call's own kernels, outputs fetched before it
+// returns; d_pose_mask and d_points do persist and stay DM_ONCE buffers), and none is part of a captured graph.
+struct RpeBufPiece { void **p; size_t bytes; };
+template <typename T>
+static inline RpeBufPiece buf_piece(T *&p, size_t n) { return {(void **)&p, n * sizeof(T)}; }
+int rpe_bufset_fit(rpe_handle *h, RpeBufSet &s, std::initializer_list<RpeBufPiece> pieces);   // rpe_api.hip
 
 // A failed HIP call ends the entry point: the text goes to the handle, or (rpe_create, no handle yet) to the create-time string
 extern std::string g_create_err;

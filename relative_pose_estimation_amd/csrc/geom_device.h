@@ -1,12 +1,10 @@
 // geom_device.h -- what geom_kernels.hip (pairs) and link_kernels.hip (links) both use, and nothing else: the polynomial
 // root chain, the deterministic f64 sums and the ordered compaction, the small 3-vector algebra, the Levenberg-Marquardt
-// loop with its parts, and the two host helpers of their launchers.  A helper one file uses lives in that file.
+// loop with its parts, and the host helper of their launchers.  A helper one file uses lives in that file.
 // All f64 arithmetic keeps the oracle's operation order (compiled with -ffp-contract=off).
 #pragma once
 #include "rpe_internal.h"
 #include <float.h>
-#include <algorithm>
-#include <initializer_list>
 
 // ------------------------------------------------------------ polynomial root chain
 // Fixed Estrin scheme for degree <= 10 (dependency depth 7 instead of Horner's 20; the root finder is latency bound), the
@@ -290,26 +288,11 @@ __device__ __forceinline__ void hg_cross(const double (&a)[3], const double (&b)
 }
 __device__ __forceinline__ bool hg_finite(double v) { return fabs(v) <= DBL_MAX; }
 
-// ------------------------------------------------------------ host: the launchers' helpers
+// ------------------------------------------------------------ host: the launchers' helper
 // Launches the camera instance of a kernel when the run carries a camera source, the shared-K instance otherwise (the
 // single-K paths launch CAM = false only): the two instances share one signature
 template <typename Kernel, typename... Args>
 static void launch_cam(const RpeRun &r, Kernel with_cameras, Kernel with_K, dim3 grid, dim3 block, size_t lds, hipStream_t stream, Args... args)
 {
     hipLaunchKernelGGL(r.cam.cams ? with_cameras : with_K, grid, block, lds, stream, args...);
-}
-
-// A launch with more than 64 KB of dynamic LDS needs the kernels' limit raised first, once per device: the launchers of
-// scale links, homographies and link poses call this when their handle asks for that much.  The limit belongs to the
-// kernel, not to the handle, so lds_max is the most any legal handle asks of these kernels; the handle records the
-// kernels it has raised.  Never inside a graph capture: rpe_scale_links, rpe_pair_homographies / rpe_find_homography and
-// rpe_link_poses alone come here.
-static int raise_lds_limit(rpe_handle *h, std::initializer_list<const void *> kernels, size_t lds_max)
-{
-    for (const void *k : kernels) {
-        if (std::find(h->lds_raised.begin(), h->lds_raised.end(), k) != h->lds_raised.end()) continue;
-        if (hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_max) != hipSuccess) return RPE_ERR_HIP;
-        h->lds_raised.push_back(k);
-    }
-    return RPE_OK;
 }

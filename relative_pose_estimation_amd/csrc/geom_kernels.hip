@@ -793,7 +793,9 @@ void rpe_launch_ransac(rpe_handle *h, const RpeRun &r, bool want_mask)
     //   64,64,128,256,512: 1.58 ms   32,32,64,128,256,512: 1.43   32,32,64,384,512: 1.29   32,96,384,512: 1.20
     //   32,480,512: 1.23   64,448,512: 1.26   96,416,512: 1.40   (results identical: the replay in ransac_update_kernel
     //   is exact for any chunking).
-    const int use_lds = mm <= 2048;
+    constexpr int lds_matches = 2048;
+    static_assert(sizeof(double2) * 2 * lds_matches <= RPE_LDS_DEFAULT_BYTES, "the points of the cut fit the default dynamic LDS");
+    const int use_lds = mm <= lds_matches;
     const size_t lds = use_lds ? sizeof(double2) * 2 * (size_t)mm : 0;
     static_assert(RPE_RANSAC_FIRST_CHUNK % POLY_LANES == 0 && RPE_RANSAC_FIRST_CHUNK % SCORE_GROUP == 0 && (RPE_RANSAC_FIRST_CHUNK * RG) % 256 == 0, "chunk granularity");
     static const int kSchedule[] = {RPE_RANSAC_FIRST_CHUNK, 96, 384, RPE_RANSAC_MAXCHUNK};      // the last entry repeats
@@ -1209,6 +1211,8 @@ void rpe_launch_refine(rpe_handle *h, const RpeRun &r, int max_iters, bool from_
     const int *status = from_batch ? h->d_status : nullptr, *inl = from_batch ? h->d_inliers : nullptr;
     // the inliers staged in LDS, or, above the cut, as 16-bit indices
     const bool lds = mm <= REFINE_LDS_MATCHES;
+    static_assert(sizeof(double2) * 2 * REFINE_LDS_MATCHES <= RPE_LDS_DEFAULT_BYTES && sizeof(unsigned short) * RPE_MAX_MATCHES_LIMIT <= RPE_LDS_DEFAULT_BYTES,
+                  "either form fits the default dynamic LDS");
     launch_cam(r, lds ? pose_refine_kernel<true, true> : pose_refine_kernel<false, true>,
                lds ? pose_refine_kernel<true, false> : pose_refine_kernel<false, false>, dim3(B), dim3(256),
                lds ? sizeof(double2) * 2 * (size_t)mm : sizeof(unsigned short) * (size_t)mm, h->stream,
@@ -1231,10 +1235,15 @@ void rpe_launch_refine(rpe_handle *h, const RpeRun &r, int max_iters, bool from_
 //            mask, the bearing sums C (block_sum_f64: lane partials in strided order, xor butterfly, waves in wave
 //            order), recoverPose's 3x3 Jacobi on every lane (identical operands), and n_rot
 // Dynamic LDS (base 16-byte aligned): [HG_ROUND][18] f64 models = 36 KB, then [2][max_matches] double2 points: 52 KB at
-// the default 500 matches, 100 KB at the cut -- above the 64 KB a kernel gets without the function attribute.
+// the default 500 matches, 100 KB at the cut (hg_lds_bytes; the most: rpe_geom_lds_ceilings).
 #define HG_ROUND 256
 #define HG_MODEL_DOUBLES 18
 #define HG_LDS_MATCHES 2048
+constexpr size_t hg_lds_bytes(int max_matches)
+{
+    return sizeof(double) * HG_ROUND * HG_MODEL_DOUBLES + (max_matches <= HG_LDS_MATCHES ? sizeof(double2) * 2 * (size_t)max_matches : 0);
+}
+static_assert(hg_lds_bytes(HG_LDS_MATCHES) <= RPE_CU_LDS_BYTES, "the models and the points of the cut fit a CU's LDS");
 
 // adj(A), A row-major: rows cross(c1, c2), cross(c2, c0), cross(c0, c1) of A's columns
 __device__ __forceinline__ void hg_adj(const double (&A)[9], double (&J)[9])
@@ -1472,20 +1481,22 @@ __global__ __launch_bounds__(256) void homography_kernel(const double2 *__restri
 
 // d_n1 / d_n2 (the run's, or rpe_launch_normalise's in the stage form) -> d_hg_*.  from_batch: the run's d_status and
 // d_rstate gate the pairs and supply n_E.
-int rpe_launch_homography(rpe_handle *h, const RpeRun &r, int iters, double threshold_px, bool from_batch)
+void rpe_launch_homography(rpe_handle *h, const RpeRun &r, int iters, double threshold_px, bool from_batch)
 {
     const int mm = h->cfg.max_matches;
     const int use_lds = mm <= HG_LDS_MATCHES;
-    const size_t lds = sizeof(double) * HG_ROUND * HG_MODEL_DOUBLES + (use_lds ? sizeof(double2) * 2 * (size_t)mm : 0);
-    // the most: the points of the cut
-    const size_t lds_max = sizeof(double) * HG_ROUND * HG_MODEL_DOUBLES + sizeof(double2) * 2 * HG_LDS_MATCHES;
-    if (lds > 65536 && raise_lds_limit(h, {(const void *)homography_kernel<true>, (const void *)homography_kernel<false>}, lds_max) != RPE_OK)
-        return RPE_ERR_HIP;
-    launch_cam(r, homography_kernel<true>, homography_kernel<false>, dim3(r.pairs), dim3(256), lds, h->stream,
+    launch_cam(r, homography_kernel<true>, homography_kernel<false>, dim3(r.pairs), dim3(256), hg_lds_bytes(mm), h->stream,
                (const double2 *)h->d_n1, (const double2 *)h->d_n2, (const int *)h->d_m_n,
                from_batch ? (const int *)h->d_status : (const int *)nullptr,
                from_batch ? (const RpeRansacState *)h->d_rstate : (const RpeRansacState *)nullptr,
                (const unsigned short *)h->d_subsets, (const double *)h->d_K, r.cam, threshold_px, iters, h->cfg.ransac_max_iters,
                mm, use_lds, h->d_hg_H, h->d_hg_R, h->d_hg_mask, h->d_hg_counts, h->d_hg_info);
-    return RPE_OK;
+}
+
+// The kernels of this file that launch above the default dynamic LDS.  ransac_score_kernel and pose_refine_kernel stay at
+// it: both stage 32 B per match up to a cut of 2048 matches, exactly 64 KB (the static_asserts in their launchers).
+std::vector<RpeLdsCeiling> rpe_geom_lds_ceilings()
+{
+    return {{(const void *)homography_kernel<true>, "homography_kernel<true>", hg_lds_bytes(HG_LDS_MATCHES)},
+            {(const void *)homography_kernel<false>, "homography_kernel<false>", hg_lds_bytes(HG_LDS_MATCHES)}};
 }

@@ -23,11 +23,9 @@
 //           array, so they are bit-deterministic whatever order pass 3 left (ties are equal values)
 // Dynamic LDS (all of the kernel's LDS, base 16-byte aligned; ScaleLinksLds states it for kernel and launcher): [sort_cap
 // f64 ratios][kcap u32 table][fill count], sort_cap = next power of two >= max_matches.  Defaults (500 matches, 4064
-// keypoints): 4 + 15.9 KB; uncapped SIFT (8064 matches, 16384 keypoints): 64 + 64 KB, above the 64 KB a kernel gets
-// without the function attribute.
+// keypoints): 4 + 15.9 KB; uncapped SIFT (8064 matches, 16384 keypoints): 64 + 64 KB, the most (rpe_link_lds_ceilings).
 // The link, the two pairs' status, match counts, R and t come from blockIdx-indexed reads: uniform, scalar loads.
 #define LINK_NONE 0xFFFFu
-#define LINK_MAX_KCAP (RPE_SIFT_UNCAPPED_CAPACITY + 64)   // the largest keypoint capacity of a handle: uncapped SIFT's
 static_assert(RPE_MAX_MATCHES_LIMIT < LINK_NONE, "a match index fits half a table word beside the empty value");
 
 // the triangulated point P of a pair with pose (R, t) in the shared frame's coordinates: P itself when the shared frame is
@@ -157,7 +155,8 @@ struct ScaleLinksLds {
         total = fill + 16;
     }
 };
-static_assert(ScaleLinksLds(RPE_MAX_MATCHES_LIMIT, LINK_MAX_KCAP).total <= RPE_CU_LDS_BYTES, "the largest handle's ratios and table fit a CU's LDS");
+constexpr size_t SCALE_LINKS_LDS_MAX = ScaleLinksLds(RPE_MAX_MATCHES_LIMIT, RPE_MAX_KCAP).total;   // the largest max_matches over uncapped SIFT's keypoints
+static_assert(SCALE_LINKS_LDS_MAX <= RPE_CU_LDS_BYTES, "the largest handle's ratios and table fit a CU's LDS");
 
 __global__ __launch_bounds__(256) void scale_links_kernel(const RpeLinkSrc src, int min_shared, double *__restrict__ stats,
                                                            int *__restrict__ n_shared, int *__restrict__ code)
@@ -211,15 +210,11 @@ __global__ __launch_bounds__(256) void scale_links_kernel(const RpeLinkSrc src, 
 
 // the last run's d_status / d_m_n / d_R / d_t, its match indices and the structure buffers -> d_link_stats / _n / _code of
 // the L links in d_links
-int rpe_launch_scale_links(rpe_handle *h, int L, int min_shared)
+void rpe_launch_scale_links(rpe_handle *h, int L, int min_shared)
 {
     const RpeLinkSrc src = rpe_link_src(h);
     const size_t lds = ScaleLinksLds(src.max_matches, src.kcap).total;
-    // the most: the largest max_matches over uncapped SIFT's keypoints
-    if (lds > 65536 && raise_lds_limit(h, {(const void *)scale_links_kernel}, ScaleLinksLds(RPE_MAX_MATCHES_LIMIT, LINK_MAX_KCAP).total) != RPE_OK)
-        return RPE_ERR_HIP;
     hipLaunchKernelGGL(scale_links_kernel, dim3(L), dim3(256), lds, h->stream, src, min_shared, h->d_link_stats, h->d_link_n, h->d_link_code);
-    return RPE_OK;
 }
 
 // ------------------------------------------------------------ link poses
@@ -444,9 +439,12 @@ struct LinkPoseLds {
         total = ints + sizeof(int) * 32;
     }
 };
-static_assert(LinkPoseLds(LP_LDS_MATCHES, 0).total <= RPE_CU_LDS_BYTES && LinkPoseLds(RPE_MAX_MATCHES_LIMIT, 0).total <= RPE_CU_LDS_BYTES,
-              "the layout at the cut and at the largest max_matches fits a CU's LDS");
-static_assert(sizeof(unsigned) * LINK_MAX_KCAP <= LP_MODEL_BYTES, "no table is larger than the candidates it shares region A with");
+// the most: the cut, or the largest max_matches (the size grows with max_matches on either side of the cut, and no table
+// adds to it)
+constexpr size_t LINK_POSE_LDS_MAX = LinkPoseLds(LP_LDS_MATCHES, 0).total > LinkPoseLds(RPE_MAX_MATCHES_LIMIT, 0).total
+                                         ? LinkPoseLds(LP_LDS_MATCHES, 0).total : LinkPoseLds(RPE_MAX_MATCHES_LIMIT, 0).total;
+static_assert(LINK_POSE_LDS_MAX <= RPE_CU_LDS_BYTES, "the layout at the cut and at the largest max_matches fits a CU's LDS");
+static_assert(sizeof(unsigned) * RPE_MAX_KCAP <= LP_MODEL_BYTES, "no table is larger than the candidates it shares region A with");
 
 template <bool CAM>
 __global__ __launch_bounds__(256) void link_pose_kernel(const RpeLinkSrc src, const unsigned short *__restrict__ subsets,
@@ -664,20 +662,15 @@ bool rpe_link_poses_in_lds(const rpe_handle *h) { return LinkPoseLds(h->cfg.max_
 
 // the links in d_links over the last run r (its d_status / d_m_n / d_R / d_t, match indices, d_n1 / d_n2 and the structure
 // buffers) -> d_lp_*.  Above LP_LDS_MATCHES the lists go to d_lp_corr, which the caller has allocated.
-int rpe_launch_link_poses(rpe_handle *h, const RpeRun &r, int L, int iters, double threshold_px, int min_shared, int refine_iters)
+void rpe_launch_link_poses(rpe_handle *h, const RpeRun &r, int L, int iters, double threshold_px, int min_shared, int refine_iters)
 {
     const RpeLinkSrc src = rpe_link_src(h);
     const LinkPoseLds lay(src.max_matches, src.kcap);
-    // the most: the cut, or the largest max_matches (the static_asserts at the layout: both fit, and no table adds to them)
-    const size_t lds_max = std::max(LinkPoseLds(LP_LDS_MATCHES, 0).total, LinkPoseLds(RPE_MAX_MATCHES_LIMIT, 0).total);
-    if (lay.total > lds_max) return RPE_ERR_HIP;
-    if (lay.total > 65536 && raise_lds_limit(h, {(const void *)link_pose_kernel<true>, (const void *)link_pose_kernel<false>}, lds_max) != RPE_OK)
-        return RPE_ERR_HIP;
+    assert(lay.total <= LINK_POSE_LDS_MAX);
     launch_cam(r, link_pose_kernel<true>, link_pose_kernel<false>, dim3(L), dim3(256), lay.total, h->stream, src,
                (const unsigned short *)h->d_subsets, (const double *)h->d_K, r.cam, threshold_px, iters, h->cfg.ransac_max_iters,
                min_shared, refine_iters, lay.corr_in_lds ? (double *)nullptr : h->d_lp_corr,
                h->d_lp_R, h->d_lp_t, h->d_lp_mask, h->d_lp_counts, h->d_lp_info, h->d_lp_rms);
-    return RPE_OK;
 }
 
 // ------------------------------------------------------------ link bundles
@@ -873,6 +866,8 @@ struct BundleLds {
         total = idx + sizeof(unsigned short) * (size_t)((max_matches + 7) & ~7);
     }
 };
+static_assert(BundleLds(BA_LDS_MATCHES).total <= RPE_LDS_DEFAULT_BYTES && BundleLds(RPE_MAX_MATCHES_LIMIT).total <= RPE_LDS_DEFAULT_BYTES,
+              "the layout at the cut and at the largest max_matches fits the default dynamic LDS");
 
 // links == nullptr: the stage form, results in the solved form and in S's frame.  Otherwise the results go back into the
 // two pairs' own conventions and pair a's camera-1 frame, and a rejected bundle returns the run's own poses and points
@@ -1136,15 +1131,22 @@ void rpe_launch_bundle(rpe_handle *h, int n, int min_shared, int max_iters, bool
 }
 
 // the links in d_links over the last run r, the callers' poses of pair b in d_ba_Rin / d_ba_tin -> the problems' arrays
-int rpe_launch_bundle_gather(rpe_handle *h, const RpeRun &r, int L, double threshold_px)
+void rpe_launch_bundle_gather(rpe_handle *h, const RpeRun &r, int L, double threshold_px)
 {
     const RpeLinkSrc src = rpe_link_src(h);
+    // the table is all of the kernel's LDS: the largest (RPE_MAX_KCAP = 16384 entries) is exactly the default dynamic LDS
+    static_assert(sizeof(unsigned) * RPE_MAX_KCAP <= RPE_LDS_DEFAULT_BYTES, "the largest table needs no raised limit");
     const size_t lds = sizeof(unsigned) * (size_t)src.kcap;
-    // the table is all of the kernel's LDS: the largest (LINK_MAX_KCAP = 16384 entries) is exactly the 64 KB a kernel gets
-    // without the function attribute
-    if (lds > 65536) return RPE_ERR_HIP;
     launch_cam(r, bundle_gather_kernel<true>, bundle_gather_kernel<false>, dim3(L), dim3(256), lds, h->stream, src,
                (const double *)h->d_K, r.cam, (const double *)h->d_ba_Rin, (const double *)h->d_ba_tin, threshold_px,
                h->d_ba_views, h->d_ba_obs, h->d_ba_points, h->d_ba_pose0, h->d_ba_focal, h->d_ba_pre, h->d_ba_n);
-    return RPE_OK;
+}
+
+// The kernels of this file that launch above the default dynamic LDS.  bundle_gather_kernel and bundle_kernel stay at or
+// below it (the static_asserts at the launcher and at BundleLds).
+std::vector<RpeLdsCeiling> rpe_link_lds_ceilings()
+{
+    return {{(const void *)scale_links_kernel, "scale_links_kernel", SCALE_LINKS_LDS_MAX},
+            {(const void *)link_pose_kernel<true>, "link_pose_kernel<true>", LINK_POSE_LDS_MAX},
+            {(const void *)link_pose_kernel<false>, "link_pose_kernel<false>", LINK_POSE_LDS_MAX}};
 }

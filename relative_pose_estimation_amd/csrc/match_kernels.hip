@@ -433,7 +433,7 @@ RpeHammingPlan rpe_hamming_plan(int kcap, int B, int extra_uint4)
     const int rounds = ((kcap + 31) / 32 + 7) / 8;
     p.split = B <= RPE_MATCH_SPLIT_PAIRS ? std::min(rounds, std::max(1, 256 / B)) : 1;
     const size_t fused = (size_t)p.region0 * 16 + (size_t)kcap * 8;
-    p.hbm = p.split > 1 || fused > 65536;
+    p.hbm = p.split > 1 || fused > RPE_LDS_DEFAULT_BYTES;
     p.lds_tile = p.hbm ? (size_t)p.region0 * 16 : fused;
     p.lds_select = (size_t)p.sortP * 4;
     return p;
@@ -1118,19 +1118,37 @@ __global__ __launch_bounds__(256) void match_l2_select_kernel(const unsigned lon
         [&](int r, int i, unsigned long long key) { out.put(r, i, (int)(bp[i] & 0x3FFFF), __uint_as_float((unsigned)(key >> 16))); });
 }
 
+// match_l2_select_kernel's dynamic LDS: one 64-bit key per element of the sort size, the power of two >= max(kcap, 64).
+// More than 8128 keypoints per image pass the default; the most is uncapped SIFT's 16384 keys, 128 KB of the CU's 160
+constexpr size_t l2_select_lds_bytes(int kcap)
+{
+    int sortP = 64;
+    while (sortP < kcap) sortP <<= 1;
+    return sizeof(unsigned long long) * (size_t)sortP;
+}
+static_assert(l2_select_lds_bytes(RPE_MAX_KCAP) <= RPE_CU_LDS_BYTES, "the largest handle's sort keys fit a CU's LDS");
+
 // The launch of match_l2_select_kernel over the words in d_m_best2 (and nn_q, see there) into the lists o (o.d holds f32)
 static void launch_l2_select(rpe_handle *h, const RpeRun &r, const unsigned long long *nn_q, const MatchBufs &o)
 {
     const int kcap = h->lay.kcap;
     const RpeFeatSrc &f = r.feat;
-    int sortP = 64;
-    while (sortP < kcap) sortP <<= 1;
-    if (sizeof(unsigned long long) * (size_t)sortP > 65536)   // more than 8128 keypoints per image: up to 128 KB of the CU's 160 KB
-        hipFuncSetAttribute(f.tab ? (const void *)match_l2_select_kernel<true> : (const void *)match_l2_select_kernel<false>,
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)(sizeof(unsigned long long) * (size_t)sortP));
-    launch_tab(f.tab, match_l2_select_kernel<true>, match_l2_select_kernel<false>, dim3(r.pairs), dim3(256), sizeof(unsigned long long) * (size_t)sortP, h->stream,
+    launch_tab(f.tab, match_l2_select_kernel<true>, match_l2_select_kernel<false>, dim3(r.pairs), dim3(256), l2_select_lds_bytes(kcap), h->stream,
                        (const unsigned long long *)h->d_m_best2, nn_q, f.count, f.pt, f.img2_base, f.tab, kcap, h->cfg.max_matches,
                        o.q, o.t, (float *)o.d, o.n, o.p1, o.p2);
+}
+
+// The kernels of this file that launch above the default dynamic LDS.  The Hamming matchers serve ORB handles only
+// (kcap <= RPE_ORB_MAX_FEATURES + 64 = 8064) and stay at or below it: the fused tile kernel by rpe_hamming_plan's rule, the
+// HBM form's tile and select kernels with 35 KB and 32 KB, the ratio kernel with QTILE * 32 + kcap * 4 = 63.5 KB.
+std::vector<RpeLdsCeiling> rpe_match_lds_ceilings()
+{
+    constexpr size_t kcap = RPE_ORB_MAX_FEATURES + 64;
+    static_assert((size_t)QTILE * 32 + kcap * 4 <= RPE_LDS_DEFAULT_BYTES, "the ratio kernel needs no raised limit");
+    static_assert((MM_STAGE + RPE_GUIDED_LDS_UINT4) * 16 + kcap * 2 + 15 <= RPE_LDS_DEFAULT_BYTES && l2_select_lds_bytes(kcap) / 2 <= RPE_LDS_DEFAULT_BYTES,
+                  "region0 of the HBM form (staging + scanned words, or the 4-byte sort keys) and the select kernel's keys need none");
+    return {{(const void *)match_l2_select_kernel<true>, "match_l2_select_kernel<true>", l2_select_lds_bytes(RPE_MAX_KCAP)},
+            {(const void *)match_l2_select_kernel<false>, "match_l2_select_kernel<false>", l2_select_lds_bytes(RPE_MAX_KCAP)}};
 }
 
 // The split of the matrix-core L2 tile kernels for B pairs: owner chunks of 128, the scanned tiles dealt over gridDim.y

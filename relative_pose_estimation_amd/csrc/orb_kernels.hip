@@ -785,29 +785,40 @@ __global__ __launch_bounds__(64 * RPE_RETAIN_FAST_WAVES) void retain_fast_kernel
 }
 
 #define RPE_RETAIN_TIER 2048         // list length served by the small-LDS launch of the two retain kernels
+// The longest lists of the two retain kernels fit the default dynamic LDS: a corner list (ccap), and the candidates of level
+// 0, kcap2 = 4 quota + 256 with quota = nfeatures (1 - f) / (1 - f^12) < nfeatures / 7 for orb.cpp's f = 1 / 1.1
+constexpr int RETAIN_HARRIS_CAP_MAX = 4 * (RPE_ORB_MAX_FEATURES / 7 + 1) + 256;
+static_assert(rpe_retain_lds(0, rpe_corner_cap(RPE_MAX_IMAGE_DIM, RPE_MAX_IMAGE_DIM)) <= RPE_LDS_DEFAULT_BYTES &&
+              rpe_retain_lds(1, RETAIN_HARRIS_CAP_MAX) <= RPE_LDS_DEFAULT_BYTES, "the retain kernels need no raised limit");
+
+// raster_corners_kernel's dynamic LDS over a handle's levels: row starts + fill counters + staged entries (raster_key_cap:
+// the largest ccap + one full row of keypoints) + tile prefix.  Every term grows with the level's size and level 0 is the
+// image itself, so the most is the largest image rpe_create accepts (images beyond ~3000 px pass the default)
+constexpr int raster_key_cap(int ccap_max, int wmax) { return ccap_max + wmax / 2 + 64; }
+constexpr size_t raster_lds_bytes(int rows_cap, int key_cap, int nt_max) { return sizeof(unsigned) * ((size_t)rows_cap + 1 + rows_cap + key_cap + nt_max + 1); }
+constexpr size_t RASTER_LDS_MAX = raster_lds_bytes(RPE_MAX_IMAGE_DIM, raster_key_cap(rpe_corner_cap(RPE_MAX_IMAGE_DIM, RPE_MAX_IMAGE_DIM), RPE_MAX_IMAGE_DIM),
+                                                   rpe_fast_tiles(RPE_MAX_IMAGE_DIM, RPE_MAX_IMAGE_DIM));
+static_assert(RASTER_LDS_MAX <= RPE_CU_LDS_BYTES, "the largest image's rows, entries and tiles fit a CU's LDS");
 
 void rpe_launch_raster_retain(rpe_handle *h, int n_img)
 {
-    // LDS: row starts + fill counters + staged entries (capacity: largest ccap + one full row of keypoints) + tile prefix
     int rows_cap = 0, ccap_max = 0, nt_max = 0, wmax = 0, nlev_big = 0;
     for (int l = 0; l < RPE_NLEVELS; ++l) {
         rows_cap = std::max(rows_cap, h->lay.lv[l].h); ccap_max = std::max(ccap_max, h->lay.lv[l].ccap);
         nt_max = std::max(nt_max, h->lay.lv[l].ntile); wmax = std::max(wmax, h->lay.lv[l].w);
         if (h->lay.lv[l].ccap > RPE_RETAIN_TIER) nlev_big = l + 1;       // capacities shrink with the level
     }
-    const int key_cap = ccap_max + wmax / 2 + 64;
-    const size_t lds = sizeof(unsigned) * ((size_t)rows_cap + 1 + rows_cap + key_cap + nt_max + 1);
-    // images beyond ~3000 px need more than the default 64 KB of dynamic LDS per workgroup (gfx950 has 160 KB per CU)
-    if (lds > 65536) hipFuncSetAttribute((const void *)raster_corners_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    const int key_cap = raster_key_cap(ccap_max, wmax);
+    const size_t lds = raster_lds_bytes(rows_cap, key_cap, nt_max);
+    assert(lds <= RASTER_LDS_MAX);
     hipLaunchKernelGGL(raster_corners_kernel, dim3(RPE_NLEVELS, n_img), dim3(256), lds, h->stream,
                        (const unsigned *)h->d_tile_list, (const int *)h->d_tile_cnt,
                        h->d_corner, h->d_corner_count, h->d_ovf, h->lay, h->n_tiles_fast, rows_cap, key_cap);
-    auto lds_of = [](int cap) { return sizeof(unsigned) * (size_t)cap + sizeof(unsigned short) * ((size_t)cap + 4); };
-    hipLaunchKernelGGL(retain_fast_kernel, dim3(RPE_NLEVELS, n_img), dim3(64 * RPE_RETAIN_FAST_WAVES), lds_of(std::min(ccap_max, RPE_RETAIN_TIER)), h->stream,
+    hipLaunchKernelGGL(retain_fast_kernel, dim3(RPE_NLEVELS, n_img), dim3(64 * RPE_RETAIN_FAST_WAVES), rpe_retain_lds(0, std::min(ccap_max, RPE_RETAIN_TIER)), h->stream,
                        (const unsigned *)h->d_corner, (const int *)h->d_corner_count, h->d_cand_xy, h->d_cand_count, h->d_ovf, h->lay,
                        0, std::min(ccap_max, RPE_RETAIN_TIER), n_img);
     if (nlev_big > 0)
-        hipLaunchKernelGGL(retain_fast_kernel, dim3(nlev_big, std::min(n_img, 512)), dim3(64 * RPE_RETAIN_FAST_WAVES), lds_of(ccap_max), h->stream,
+        hipLaunchKernelGGL(retain_fast_kernel, dim3(nlev_big, std::min(n_img, 512)), dim3(64 * RPE_RETAIN_FAST_WAVES), rpe_retain_lds(0, ccap_max), h->stream,
                            (const unsigned *)h->d_corner, (const int *)h->d_corner_count, h->d_cand_xy, h->d_cand_count, h->d_ovf, h->lay,
                            RPE_RETAIN_TIER, ccap_max, n_img);
 }
@@ -933,11 +944,9 @@ __global__ __launch_bounds__(64 * NW) void retain_debug_kernel(E *__restrict__ e
     if (tid == 0) out_len[blockIdx.x] = n1;
 }
 
-size_t rpe_debug_retain_lds(int kind, int cap) { return (kind ? sizeof(unsigned long long) : sizeof(unsigned)) * (size_t)cap + sizeof(unsigned short) * ((size_t)cap + 4); }
-
 void rpe_launch_debug_retain(rpe_handle *h, int kind, int stl, void *d_elems, const int *d_len, const int *d_n_points, int *d_out_len, int n_lists, int cap)
 {
-    const size_t lds = rpe_debug_retain_lds(kind, cap);
+    const size_t lds = rpe_retain_lds(kind, cap);
     if (kind == 0)
         hipLaunchKernelGGL((retain_debug_kernel<RPE_RETAIN_FAST_WAVES, unsigned, FastScoreGT, FastScoreGE>), dim3(n_lists), dim3(64 * RPE_RETAIN_FAST_WAVES), lds, h->stream,
                            (unsigned *)d_elems, d_len, d_n_points, d_out_len, cap, stl);
@@ -987,15 +996,22 @@ void rpe_launch_keypoints(rpe_handle *h, int n_img)
         if (h->lay.lv[l].kcap2 > RPE_RETAIN_TIER / 2) nlev_big = l + 1;
     }
     const int tier = std::min(kcap2_max, RPE_RETAIN_TIER / 2);
-    auto lds_of = [](int cap) { return sizeof(unsigned long long) * (size_t)cap + sizeof(unsigned short) * ((size_t)cap + 4); };
-    hipLaunchKernelGGL(retain_harris_kernel, dim3(RPE_NLEVELS, n_img), dim3(64 * RPE_RETAIN_HARRIS_WAVES), lds_of(tier), h->stream,
+    assert(kcap2_max <= RETAIN_HARRIS_CAP_MAX);
+    hipLaunchKernelGGL(retain_harris_kernel, dim3(RPE_NLEVELS, n_img), dim3(64 * RPE_RETAIN_HARRIS_WAVES), rpe_retain_lds(1, tier), h->stream,
                        h->d_cand_xy, h->d_cand_resp, (const int *)h->d_cand_count, h->d_kp_lvl_count, h->lay, 0, tier);
     if (nlev_big > 0)
-        hipLaunchKernelGGL(retain_harris_kernel, dim3(nlev_big, n_img), dim3(64 * RPE_RETAIN_HARRIS_WAVES), lds_of(kcap2_max), h->stream,
+        hipLaunchKernelGGL(retain_harris_kernel, dim3(nlev_big, n_img), dim3(64 * RPE_RETAIN_HARRIS_WAVES), rpe_retain_lds(1, kcap2_max), h->stream,
                            h->d_cand_xy, h->d_cand_resp, (const int *)h->d_cand_count, h->d_kp_lvl_count, h->lay, RPE_RETAIN_TIER / 2, kcap2_max);
     hipLaunchKernelGGL(compact_keypoints_kernel, dim3(n_img), dim3(256), 0, h->stream,
                        (const unsigned *)h->d_cand_xy, (const float *)h->d_cand_resp, (const int *)h->d_kp_lvl_count,
                        h->d_kp_xy, h->d_kp_resp, h->d_kp_pt, h->d_kp_count, h->d_ovf, h->lay);
+}
+
+// The kernel of this file that launches above the default dynamic LDS.  The retain kernels stay below it (the
+// static_assert at RPE_RETAIN_TIER: 48 KB and 47 KB), and rpe_orb_debug_retain refuses a list above it.
+std::vector<RpeLdsCeiling> rpe_orb_lds_ceilings()
+{
+    return {{(const void *)raster_corners_kernel, "raster_corners_kernel", RASTER_LDS_MAX}};
 }
 
 // ------------------------------------------------- orientation + descriptor

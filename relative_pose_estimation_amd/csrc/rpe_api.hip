@@ -167,9 +167,7 @@ static void build_layout(rpe_handle *h)
     L.lv[RPE_NLEVELS - 1].quota = nf - sum > 0 ? nf - sum : 0;
     int corner = 0;
     for (int l = 0; l < RPE_NLEVELS; ++l) {
-        // raster corner list: clamp(w h / 64, 1024, 8192) entries (the oracle mirrors this rule: orc_orb_corner_cap)
-        const long long c64 = (long long)L.lv[l].w * L.lv[l].h / 64;
-        L.lv[l].ccap = (int)(c64 < 1024 ? 1024 : c64 > 8192 ? 8192 : c64);
+        L.lv[l].ccap = rpe_corner_cap(L.lv[l].w, L.lv[l].h);     // raster corner list: clamp(w h / 64, 1024, 8192) entries
         L.lv[l].corner_off = corner;
         corner += L.lv[l].ccap;
         L.lv[l].kcap2 = 4 * L.lv[l].quota + 256;
@@ -220,6 +218,7 @@ static int build_tables(rpe_handle *h)
             for (int y = RPE_EDGE; y < v.h - RPE_EDGE; y += FAST_TH)
                 for (int x = FAST_TILE_X0; x < v.w - RPE_EDGE; x += 64) fast.push_back({(short)l, (short)x, (short)y, 0});
         h->lay.lv[l].ntile = (int)fast.size() - h->lay.lv[l].tile0;
+        assert(h->lay.lv[l].ntile == rpe_fast_tiles(v.w, v.h));
     }
     // fast_nms_kernel loads pixels from (tx - 4, ty - 4) on and clamps only against the level's far edges
     for (const RpeTile &t : fast)
@@ -436,6 +435,21 @@ static int alloc_workspace(rpe_handle *h)
     return RPE_OK;
 }
 
+// Every kernel that some legal handle launches with more than RPE_LDS_DEFAULT_BYTES of dynamic LDS gets its limit raised to
+// its ceiling (the kernel files' lists) on the current device, before any launch or capture exists
+static int raise_lds_limits(rpe_handle *h)
+{
+    for (auto list : {rpe_orb_lds_ceilings, rpe_match_lds_ceilings, rpe_geom_lds_ceilings, rpe_link_lds_ceilings})
+        for (const RpeLdsCeiling &c : list()) {
+            const hipError_t e = hipFuncSetAttribute(c.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.bytes);
+            if (e != hipSuccess) {
+                h->err = std::string("raising the dynamic LDS limit of ") + c.name + " to " + std::to_string(c.bytes) + " bytes failed: " + hipGetErrorString(e);
+                return RPE_ERR_HIP;
+            }
+        }
+    return RPE_OK;
+}
+
 extern "C" int rpe_create(const rpe_config *cfg, rpe_handle **out)
 {
     if (!cfg || !out) { g_create_err = "null argument"; return RPE_ERR_INVALID; }
@@ -458,8 +472,8 @@ extern "C" int rpe_create(const rpe_config *cfg, rpe_handle **out)
     if (is_sift && (cfg->nfeatures > RPE_SIFT_UNCAPPED_CAPACITY || cfg->nfeatures < 0 || cfg->width > 4000 || cfg->height > 4000)) {
         g_create_err = "SIFT: nfeatures must be 0 (no cap: cv2's SIFT_create()) or a cap <= 16320, and the image <= 4000 px"; return RPE_ERR_INVALID;
     }
-    if (cfg->width < 96 || cfg->height < 96 || cfg->width > 4095 || cfg->height > 4095 || cfg->max_batch < 1 ||
-        (!is_sift && (cfg->nfeatures < 1 || cfg->nfeatures > 8000)) || cfg->max_matches < 5 || cfg->max_matches > RPE_MAX_MATCHES_LIMIT ||
+    if (cfg->width < 96 || cfg->height < 96 || cfg->width > RPE_MAX_IMAGE_DIM || cfg->height > RPE_MAX_IMAGE_DIM || cfg->max_batch < 1 ||
+        (!is_sift && (cfg->nfeatures < 1 || cfg->nfeatures > RPE_ORB_MAX_FEATURES)) || cfg->max_matches < 5 || cfg->max_matches > RPE_MAX_MATCHES_LIMIT ||
         cfg->ransac_max_iters < 1 || cfg->ransac_max_iters > 4096 || cfg->fast_threshold < 1 || cfg->fast_threshold > 254) {
         g_create_err = "configuration out of supported range"; return RPE_ERR_INVALID;
     }
@@ -475,6 +489,7 @@ extern "C" int rpe_create(const rpe_config *cfg, rpe_handle **out)
     int rc = RPE_OK;
     do {
         if (hipSetDevice(cfg->device) != hipSuccess) { h->err = "hipSetDevice failed"; rc = RPE_ERR_HIP; break; }
+        if ((rc = raise_lds_limits(h)) != RPE_OK) break;
         if (hipStreamCreate(&h->stream) != hipSuccess) { h->err = "hipStreamCreate failed"; rc = RPE_ERR_HIP; break; }
         build_layout(h);
         if ((rc = build_tables(h)) != RPE_OK) break;
@@ -1117,7 +1132,7 @@ extern "C" int rpe_scale_links(rpe_handle *h, int L, const int32_t *pair_a, cons
     int rc = links_begin(h, "rpe_scale_links", L, pair_a, pair_b, side, min_shared);
     if (rc != RPE_OK || L == 0) return rc;
     if ((rc = scale_links_alloc(h)) != RPE_OK) return rc;
-    if ((rc = rpe_launch_scale_links(h, L, min_shared)) != RPE_OK) return rpe_lds_unsized(h, "rpe_scale_links", rc);
+    rpe_launch_scale_links(h, L, min_shared);
     HIPCHK(h, hipGetLastError());
     return fetch(h, {{stats, h->d_link_stats, sizeof(double) * 3 * (size_t)L}, {n_shared, h->d_link_n, sizeof(int) * (size_t)L},
                      {code, h->d_link_code, sizeof(int) * (size_t)L}});
@@ -1146,7 +1161,7 @@ extern "C" int rpe_link_poses(rpe_handle *h, int L, const int32_t *pair_a, const
     rc = links_begin(h, "rpe_link_poses", L, pair_a, pair_b, side, min_shared);
     if (rc != RPE_OK || L == 0) return rc;
     if ((rc = link_poses_alloc(h)) != RPE_OK) return rc;
-    if ((rc = rpe_launch_link_poses(h, h->last.run, L, iters, threshold_px, min_shared, refine_iters)) != RPE_OK) return rpe_lds_unsized(h, "rpe_link_poses", rc);
+    rpe_launch_link_poses(h, h->last.run, L, iters, threshold_px, min_shared, refine_iters);
     HIPCHK(h, hipGetLastError());
     const size_t n = (size_t)L, mm = (size_t)h->cfg.max_matches;
     return fetch(h, {{R, h->d_lp_R, sizeof(double) * 9 * n}, {t, h->d_lp_t, sizeof(double) * 3 * n}, {mask, h->d_lp_mask, n * mm},
@@ -1193,7 +1208,7 @@ extern "C" int rpe_link_bundles(rpe_handle *h, int L, const int32_t *pair_a, con
     if ((rc = bundle_alloc(h)) != RPE_OK) return rc;
     HIPCHK(h, hipMemcpyAsync(h->d_ba_Rin, R0, sizeof(double) * 9 * n, hipMemcpyHostToDevice, h->stream));
     HIPCHK(h, hipMemcpyAsync(h->d_ba_tin, t0, sizeof(double) * 3 * n, hipMemcpyHostToDevice, h->stream));
-    if ((rc = rpe_launch_bundle_gather(h, h->last.run, L, threshold_px)) != RPE_OK) return rpe_lds_unsized(h, "rpe_link_bundles", rc);
+    rpe_launch_bundle_gather(h, h->last.run, L, threshold_px);
     rpe_launch_bundle(h, L, min_shared, max_iters, true);
     HIPCHK(h, hipGetLastError());
     // the wait also covers the upload: the poses have left the caller's arrays
@@ -1550,7 +1565,7 @@ static int homography_run(rpe_handle *h, const RpeRun &r, int iters, double thre
                           uint8_t *mask, int32_t *counts, int32_t *info)
 {
     const size_t B = (size_t)r.pairs;
-    if (int rc = rpe_launch_homography(h, r, iters, threshold_px, from_batch)) return rpe_lds_unsized(h, "homography", rc);
+    rpe_launch_homography(h, r, iters, threshold_px, from_batch);
     HIPCHK(h, hipGetLastError());
     return fetch(h, {{H, h->d_hg_H, sizeof(double) * 9 * B}, {R_rot, h->d_hg_R, sizeof(double) * 9 * B}, {mask, h->d_hg_mask, B * h->cfg.max_matches},
                      {counts, h->d_hg_counts, sizeof(int) * 3 * B}, {info, h->d_hg_info, sizeof(int) * 4 * B}});
@@ -1897,7 +1912,7 @@ extern "C" int rpe_orb_debug_retain(rpe_handle *h, int kind, int stl_runtime, vo
     if (kind != 0 && kind != 1) return rpe_invalid(h, "rpe_orb_debug_retain", "kind must be 0 (u32 FAST entries) or 1 (u64 Harris entries)");
     if (stl_runtime != RPE_STL_LIBSTDCXX && stl_runtime != RPE_STL_MSVC) return rpe_invalid(h, "rpe_orb_debug_retain", "unknown stl_runtime");
     // positions travel as u16 and the list, with its stopper positions, must fit the default dynamic LDS of a workgroup
-    if (cap > 8192 || rpe_debug_retain_lds(kind, cap) > 65536) return rpe_invalid(h, "rpe_orb_debug_retain", "cap too large for one workgroup's LDS");
+    if (cap > 8192 || rpe_retain_lds(kind, cap) > RPE_LDS_DEFAULT_BYTES) return rpe_invalid(h, "rpe_orb_debug_retain", "cap too large for one workgroup's LDS");
     for (int i = 0; i < n_lists; ++i)
         if (len[i] < 0 || len[i] > cap) return rpe_invalid(h, "rpe_orb_debug_retain", "a list is longer than the capacity the launch is sized for");
     HIPCHK(h, hipSetDevice(h->cfg.device));

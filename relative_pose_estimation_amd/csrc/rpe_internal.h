@@ -2,6 +2,7 @@
 // Host handle, HBM workspace layout and kernel-launcher prototypes.
 #pragma once
 #include <hip/hip_runtime.h>
+#include <assert.h>
 #include <math.h>
 #include <stdint.h>
 #include <stdio.h>
@@ -23,7 +24,20 @@
 #define RPE_GUIDED_LDS_UINT4 128    // the guided matcher's part of the first LDS region: 2 x 32 scanned records of 32 bytes
 #define RPE_TAB_RING 4            // pinned pieces the slot tables of rpe_frames_put* / rpe_enqueue_pairs rotate through
 #define RPE_MAX_MATCHES_LIMIT 8064   // the largest cfg.max_matches rpe_create accepts: the most any kernel's LDS is sized for
+#define RPE_MAX_IMAGE_DIM 4095       // the largest cfg.width / cfg.height rpe_create accepts
+#define RPE_ORB_MAX_FEATURES 8000    // the largest cfg.nfeatures of an ORB handle
+#define RPE_MAX_KCAP (RPE_SIFT_UNCAPPED_CAPACITY + 64)   // the largest keypoint capacity of a handle: uncapped SIFT's
 #define RPE_CU_LDS_BYTES (160 * 1024)   // LDS of one gfx950 CU: the most a workgroup can ask for
+#define RPE_LDS_DEFAULT_BYTES 65536     // the dynamic LDS a kernel may be launched with before its limit is raised
+// A kernel that some handle rpe_create accepts launches with more than RPE_LDS_DEFAULT_BYTES, and the most any such handle
+// asks of it.  Each kernel file lists its own, every launched template instance included, next to the layouts the
+// ceilings come from (each static_asserted <= RPE_CU_LDS_BYTES); rpe_create raises them all, so no launcher touches the
+// attribute.  The limit is per kernel and device and the ceilings depend on the build alone: repeating it is harmless.
+struct RpeLdsCeiling { const void *kernel; const char *name; size_t bytes; };
+std::vector<RpeLdsCeiling> rpe_orb_lds_ceilings();     // orb_kernels.hip
+std::vector<RpeLdsCeiling> rpe_match_lds_ceilings();   // match_kernels.hip
+std::vector<RpeLdsCeiling> rpe_geom_lds_ceilings();    // geom_kernels.hip
+std::vector<RpeLdsCeiling> rpe_link_lds_ceilings();    // link_kernels.hip
 // one pair's results, section by section of the result block (d_resblk): R, t, inliers, status, n_matches
 #define RPE_RESULT_SECTIONS 5
 static const size_t kRpeResultElem[RPE_RESULT_SECTIONS] = {9 * sizeof(double), 3 * sizeof(double), sizeof(int), sizeof(int), sizeof(int)};
@@ -38,6 +52,17 @@ constexpr int FAST_TH = 64;
 constexpr int FAST_TILE_X0 = RPE_EDGE & ~3;
 static_assert(FAST_TILE_X0 >= 4 && RPE_EDGE >= 4, "the FAST tile loads do not clamp x0 - 4 and y0 - 4 at 0");
 constexpr int RPE_FAST_TILE_CAP = 1024;   // entries of one FAST tile list: the most strict 3x3 maxima a 64 x 64 tile can hold (32 x 32)
+// The FAST tiles of a w x h level (build_tables lays them out), and the entries of its raster corner list (build_layout;
+// the oracle mirrors this rule: orc_orb_corner_cap)
+constexpr int rpe_fast_tiles(int w, int h)
+{
+    return w > 2 * RPE_EDGE && h > 2 * RPE_EDGE ? ((h - 2 * RPE_EDGE + FAST_TH - 1) / FAST_TH) * ((w - RPE_EDGE - FAST_TILE_X0 + 63) / 64) : 0;
+}
+constexpr int rpe_corner_cap(int w, int h)
+{
+    const long long c64 = (long long)w * h / 64;
+    return (int)(c64 < 1024 ? 1024 : c64 > 8192 ? 8192 : c64);
+}
 // Resize tile = PYR_TW x PYR_TH destination pixels, one wave; its source window in the level below is PYR_ROWS rows of
 // PYR_DW dwords (336 B = 21 16-byte loads, origin aligned down to 16 B).  build_tables checks every tile of a handle
 // against the window at create time.  Why this shape: see pyr_resize_kernel.
@@ -486,9 +511,6 @@ struct rpe_handle {
     uint8_t *d_tp_oflag = nullptr;
     rpe_camera *d_tp_cams = nullptr;
     rpe_camera tp_cam_k{}; RpeBufSet set_track_points;
-    // the kernels of geom_kernels.hip and link_kernels.hip whose dynamic-LDS limit a launch of this handle has raised
-    // (raise_lds_limit, geom_device.h): the attribute is per device, so the record is per handle
-    std::vector<const void *> lds_raised;
     // results
     double *d_R = nullptr, *d_t = nullptr, *d_E = nullptr;
     int *d_inliers = nullptr, *d_status = nullptr;
@@ -580,13 +602,6 @@ static inline int rpe_invalid(rpe_handle *h, const char *who, const char *what =
     return RPE_ERR_INVALID;
 }
 
-// The refusal of a launcher that could not raise or fit its kernel's dynamic LDS (rc: what it returned)
-static inline int rpe_lds_unsized(rpe_handle *h, const char *who, int rc)
-{
-    h->err = std::string(who) + ": could not size the kernel's LDS";
-    return rc;
-}
-
 // The runs.  `cam` defaults to the shared K; a camera source must address its records as the run addresses its images.
 static inline RpeRun rpe_run_rule(const rpe_handle *h, int pairs, int img2_base, RpeCamSrc cam)
 {
@@ -619,7 +634,9 @@ void rpe_launch_harris(rpe_handle *h, int n_img);
 void rpe_launch_keypoints(rpe_handle *h, int n_img);
 void rpe_launch_orient_describe(rpe_handle *h, int n_img);
 void rpe_launch_debug_blur(rpe_handle *h, int img);
-size_t rpe_debug_retain_lds(int kind, int cap);
+// dynamic LDS of the retain kernels for a list of `cap` elements (kind 0: 4-byte FAST entries, 1: 8-byte Harris entries)
+// and its [cap + 4] u16 stopper positions
+constexpr size_t rpe_retain_lds(int kind, int cap) { return (kind ? sizeof(unsigned long long) : sizeof(unsigned)) * (size_t)cap + sizeof(unsigned short) * ((size_t)cap + 4); }
 void rpe_launch_debug_retain(rpe_handle *h, int kind, int stl, void *d_elems, const int *d_len, const int *d_n_points, int *d_out_len, int n_lists, int cap);
 // How the matrix-core Hamming matchers (crossCheck: extra_uint4 = 0, guided: RPE_GUIDED_LDS_UINT4) run B pairs of capacity
 // kcap; the rule is rpe_hamming_plan's alone (match_kernels.hip)
@@ -646,16 +663,16 @@ void rpe_launch_ransac(rpe_handle *h, const RpeRun &r, bool want_mask);
 void rpe_launch_pose(rpe_handle *h, const RpeRun &r, bool set_status);
 void rpe_launch_structure(rpe_handle *h, const RpeRun &r);
 void rpe_launch_refine(rpe_handle *h, const RpeRun &r, int max_iters, bool from_batch);
-int rpe_launch_scale_links(rpe_handle *h, int L, int min_shared);
-int rpe_launch_link_poses(rpe_handle *h, const RpeRun &r, int L, int iters, double threshold_px, int min_shared, int refine_iters);
+void rpe_launch_scale_links(rpe_handle *h, int L, int min_shared);
+void rpe_launch_link_poses(rpe_handle *h, const RpeRun &r, int L, int iters, double threshold_px, int min_shared, int refine_iters);
 bool rpe_link_poses_in_lds(const rpe_handle *h);
-int rpe_launch_bundle_gather(rpe_handle *h, const RpeRun &r, int L, double threshold_px);
+void rpe_launch_bundle_gather(rpe_handle *h, const RpeRun &r, int L, double threshold_px);
 void rpe_launch_bundle(rpe_handle *h, int n, int min_shared, int max_iters, bool links);
 bool rpe_bundles_in_lds(const rpe_handle *h);
 void rpe_launch_tracks(rpe_handle *h, const RpeTrackJob &job);
 void rpe_launch_track_points(rpe_handle *h, const RpeTrackPointJob &job);
 void rpe_launch_normalise(rpe_handle *h, const RpeRun &r);
-int rpe_launch_homography(rpe_handle *h, const RpeRun &r, int iters, double threshold_px, bool from_batch);
+void rpe_launch_homography(rpe_handle *h, const RpeRun &r, int iters, double threshold_px, bool from_batch);
 void rpe_launch_undistort(rpe_handle *h, const float2 *d_pts, int n, const rpe_camera *d_cam, double2 *d_out);
 
 // per-stage hipEvents on the handle's stream (rpe_set_profiling / rpe_get_stage_ms)

@@ -149,6 +149,18 @@ def test_lds_above_64_kb(capi, oracle, K_vga):
     e.close()
 
 
+def test_lds_at_the_2048_match_cut(capi, oracle, K_vga):
+    """max_matches = 2048, the largest count that stages the points in LDS: 36 KB of models + 64 KB of points = 102400 bytes,
+    the ceiling rpe_create raises homography_kernel<false> to (the launch asks for it whatever a pair holds)"""
+    e = capi.Engine(640, 480, max_batch=2, nfeatures=2000, max_matches=2048)
+    assert 256 * 18 * 8 + 32 * e.max_matches == 102400
+    big = [("rotation-2048",) + hc.scene_points("rotation", 2048, K_vga, 2, noise=hc.STAGE_NOISE_PX)[:2],
+           ("plane-1000",) + hc.scene_points("plane", 1000, K_vga, 2, noise=hc.STAGE_NOISE_PX)[:2]]
+    angles = run_stage(e, big, K_vga, oracle, 300)
+    assert len(angles) == 2 and max(angles) <= ROT_BOUND_DEG, angles
+    e.close()
+
+
 def test_points_read_from_hbm_above_2048_matches(capi, oracle, K_vga):
     """max_matches > 2048: the points no longer fit LDS beside the models"""
     e = capi.Engine(640, 480, max_batch=2, nfeatures=2100, max_matches=2112)
@@ -254,6 +266,21 @@ def test_cameras(capi, oracle, physics):
     # a camera batch
     e.estimate_batch_cameras(frames[:2], frames[1:3], [capi.Camera(K), capi.Camera(K, dist)], [capi.Camera(K, dist), capi.Camera(K2)])
     check_run(e, 2, oracle, cams=cams, pairs=[(0, 1), (1, 2)])
+    e.close()
+
+
+def test_camera_batch_at_the_2048_match_cut(capi, oracle, physics):
+    """homography_kernel<true> at its ceiling of 102400 bytes: the camera batch of test_cameras on a handle with
+    max_matches = 2048"""
+    frames, K = physics
+    K2 = K.copy(); K2[0, 0] *= 1.02; K2[1, 1] *= 1.02
+    dist = [-0.08, 0.02, 0.001, -0.0005]
+    cams = [cm.Cam(K), cm.Cam(K, dist), cm.Cam(K2)]
+    e = capi.Engine(640, 480, max_batch=2, nfeatures=2000, max_matches=2048)
+    res = e.estimate_batch_cameras(frames[:2], frames[1:3], [capi.Camera(K), capi.Camera(K, dist)], [capi.Camera(K, dist), capi.Camera(K2)])
+    assert not res[4].any(), res[4]
+    got, _ = check_run(e, 2, oracle, cams=cams, pairs=[(0, 1), (1, 2)])
+    assert (got[4][:, 0] == hm.HOMOGRAPHY_OK).all()
     e.close()
 
 

@@ -803,6 +803,12 @@ int rpe_orb_detect_and_compute(rpe_handle *h, const uint8_t *h_imgs, int n_image
  * fused kernel; which = 1 is rejected.)  ORB handles only. */
 int rpe_orb_debug_fetch(rpe_handle *h, int index, int which, uint8_t *h_out);
 int64_t rpe_orb_pyramid_pixels(const rpe_handle *h);
+/* The smallest number of images of one ORB extraction (2 B of a batch, the frames of a stream, n_images here) that runs
+ * detection in level groups: FAST per group of pyramid levels, that of the first group on a second stream beside the
+ * resize of the levels above it, the keypoint selection of a finished group on that stream beside FAST of the next.
+ * Smaller extractions launch one kernel after the other.  Both schedules give the
+ * same bits; only the count decides, and batches small enough to be replayed as a graph are always below it. */
+int rpe_orb_group_min_images(void);
 /* KeyPointsFilter::retainBest as retain_fast / retain_harris replay it, on n_lists caller-supplied lists in one launch
  * (one workgroup per list, the kernels' own device routine).  kind 0: u32 FAST entries, compared on bits 24..31 (the
  * score); kind 1: u64 Harris entries, compared on the f32 in bits 32..63.  elems[n_lists*cap]: list i at elems + i*cap
@@ -876,7 +882,12 @@ int rpe_refine_pose_points(rpe_handle *h, const double *h_R0, const double *h_t0
 
 /* ------------------------------------------------------------ profiling */
 /* Per-stage device time of the last hot-path call, from hipEvents recorded
- * on the handle's stream around each kernel group. */
+ * on the handle's stream around each kernel group.  The stages partition the call: their sum is the span from the first
+ * event to the last.  An ORB extraction of rpe_orb_group_min_images() images or more also runs kernels on a second stream
+ * beside those of the handle's stream, and a stage then covers what ran in its span on either: `pyramid` the resize
+ * launches with FAST of the first level group beside the later ones, `fast` the other groups' FAST with the selection
+ * of finished groups beside it, `select`, `harris` and `keypoints` the last group's selection, `keypoints` also the wait
+ * for the second stream.  Such a stage time is a share of the step, not the cost of its kernels run alone. */
 enum {
     RPE_STAGE_PYRAMID = 0, RPE_STAGE_FAST, RPE_STAGE_NMS, RPE_STAGE_SELECT, RPE_STAGE_HARRIS,
     RPE_STAGE_KEYPOINTS, RPE_STAGE_ANGLE, RPE_STAGE_BLUR, RPE_STAGE_DESCRIBE, RPE_STAGE_MATCH,

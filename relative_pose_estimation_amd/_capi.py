@@ -67,6 +67,7 @@ _SIGNATURES = {
     "rpe_guided_matches_l2": "i:pippddpppppp",
     "rpe_pair_homographies": "i:piidppppp", "rpe_find_homography": "i:ppppipidppppp",
     "rpe_orb_detect_and_compute": "i:ppippp", "rpe_orb_debug_fetch": "i:piip", "rpe_orb_pyramid_pixels": "l:p",
+    "rpe_orb_group_min_images": "i:",
     "rpe_orb_debug_retain": "i:piipppiip",
     "rpe_match_hamming": "i:pppppipppp", "rpe_match_hamming_guided": "i:pppppppipppdipppp",
     "rpe_sift_detect_and_compute": "i:ppippp", "rpe_sift_debug_gauss": "l:pip", "rpe_match_l2": "i:pppppipppp",

@@ -260,9 +260,9 @@ __global__ __launch_bounds__(PYR_THREADS) void pyr_resize_kernel(uint8_t *pyr, R
     }
 }
 
-void rpe_launch_pyramid(rpe_handle *h, int n_img)
+void rpe_launch_pyramid(rpe_handle *h, int n_img, int l0, int l1)
 {
-    for (int l = 1; l < RPE_NLEVELS; ++l) {
+    for (int l = std::max(l0, 1); l < l1; ++l) {
         const int nt = h->pyr_tile_cnt[l];
         hipLaunchKernelGGL(pyr_resize_kernel, dim3((nt + 7) / 8 * 8, n_img), dim3(PYR_THREADS), 0, h->stream, h->d_pyr, h->lay, h->d_coef,
                            (const RpePyrTile *)(h->d_pyr_tiles + h->pyr_tile_off[l]), nt, l);
@@ -319,7 +319,7 @@ static_assert((FAST_PROWS * 18 + FS_ROWS * 18) * 4 + FAST_NCAND * 2 + 8 == 19448
 // order inside a tile depends on wave timing, which nothing downstream reads (select ranks by (y, x)).
 __global__ __launch_bounds__(FAST_THREADS) void fast_nms_kernel(const uint8_t *__restrict__ pyr, unsigned *__restrict__ tile_list,
                                                         int *__restrict__ tile_cnt, RpeDeviceLayout lay,
-                                                        const RpeTile *__restrict__ tiles, int ntiles)
+                                                        const RpeTile *__restrict__ tiles, int ntiles, int t0, int nt)
 {
     // 19448 B of LDS per workgroup = 8 workgroups (32 waves) per CU: the pixel tile is dead after phase 2, so the keypoint
     // list of phase 3 lives in its place (4096 <= 5184 bytes); with a list of its own (24.5 KB) only 6 workgroups fitted
@@ -329,8 +329,11 @@ __global__ __launch_bounds__(FAST_THREADS) void fast_nms_kernel(const uint8_t *_
     __shared__ unsigned short s_cand[FAST_NCAND];
     __shared__ int s_ncand, s_nout;
     const int tid = threadIdx.x, lane = tid & 63;
-    const int ti = xcd_tile(blockIdx.x, ntiles);
-    if (ti >= ntiles) return;
+    // this launch's run [t0, t0 + nt) of the tile table (a level group, orb_groups.h, or all of it); the slots keep the
+    // table's stride ntiles
+    const int tr = xcd_tile(blockIdx.x, nt);
+    if (tr >= nt) return;
+    const int ti = t0 + tr;
     const RpeTile t = tiles[ti];
     const RpeLevel &L = lay.lv[t.level];
     const int w = L.w, hgt = L.h, pitch = L.pitch, thr = lay.fast_thr;
@@ -592,12 +595,12 @@ __global__ __launch_bounds__(FAST_THREADS) void fast_nms_kernel(const uint8_t *_
     if (tid == 0) tile_cnt[tslot] = nout;
 }
 
-void rpe_launch_fast(rpe_handle *h, int n_img)
+void rpe_launch_fast(rpe_handle *h, int n_img, int t0, int nt, hipStream_t stream)
 {
     // tiles cover the border-filtered region only
-    if (h->n_tiles_fast == 0) return;
-    hipLaunchKernelGGL(fast_nms_kernel, dim3((h->n_tiles_fast + 7) / 8 * 8, n_img), dim3(FAST_THREADS), 0, h->stream,
-                       h->d_pyr, h->d_tile_list, h->d_tile_cnt, h->lay, h->d_tiles_fast, h->n_tiles_fast);
+    if (nt == 0) return;
+    hipLaunchKernelGGL(fast_nms_kernel, dim3((nt + 7) / 8 * 8, n_img), dim3(FAST_THREADS), 0, stream,
+                       h->d_pyr, h->d_tile_list, h->d_tile_cnt, h->lay, h->d_tiles_fast, h->n_tiles_fast, t0, nt);
 }
 
 // ----------------------------------------------------------------- select
@@ -621,7 +624,7 @@ void rpe_launch_fast(rpe_handle *h, int n_img)
 // Arrival order inside a row depends on wave timing; the final position does not.
 __global__ __launch_bounds__(256) void raster_corners_kernel(const unsigned *__restrict__ tile_list, const int *__restrict__ tile_cnt,
                                                               unsigned *__restrict__ corner, int *__restrict__ corner_count,
-                                                              unsigned *__restrict__ ovf, RpeDeviceLayout lay, int ntiles, int rows_cap, int key_cap)
+                                                              unsigned *__restrict__ ovf, RpeDeviceLayout lay, int ntiles, int rows_cap, int key_cap, int l0)
 {
     extern __shared__ unsigned s_dyn[];
     unsigned *s_rs = s_dyn;                          // [rows_cap + 1] per-row counts, then exclusive row starts
@@ -630,7 +633,7 @@ __global__ __launch_bounds__(256) void raster_corners_kernel(const unsigned *__r
     unsigned *s_toff = s_key + key_cap;              // [level tiles + 1] exclusive prefix of the tile counts
     __shared__ int s_wave[5];
     __shared__ int s_live;
-    const int tid = threadIdx.x, l = blockIdx.x, img = blockIdx.y;
+    const int tid = threadIdx.x, l = l0 + blockIdx.x, img = blockIdx.y;
     const RpeLevel &L = lay.lv[l];
     if (tid == 64) s_live = 0x7FFFFFFF;
     const int nrows = L.h, nt = L.ntile, ccap = L.ccap;
@@ -748,11 +751,11 @@ struct FastScoreGE { __device__ __forceinline__ bool operator()(unsigned a, unsi
 
 __global__ __launch_bounds__(64 * RPE_RETAIN_FAST_WAVES) void retain_fast_kernel(const unsigned *__restrict__ corner, const int *__restrict__ corner_count,
                                                           unsigned *__restrict__ cand_xy, int *__restrict__ cand_count,
-                                                          unsigned *__restrict__ ovf, RpeDeviceLayout lay, int lo, int cap, int n_img)
+                                                          unsigned *__restrict__ ovf, RpeDeviceLayout lay, int lo, int cap, int n_img, int l0)
 {
     extern __shared__ unsigned s_a[];                          // [cap] elements, then [cap + 2] u16 stopper positions (block_pair_swap)
     __shared__ int s_ctl[3 * RPE_RETAIN_FAST_WAVES];
-    const int tid = threadIdx.x, l = blockIdx.x;
+    const int tid = threadIdx.x, l = l0 + blockIdx.x;
     const RpeLevel &L = lay.lv[l];
     // the long-list launch runs a small grid whose workgroups walk over the images: on ordinary images it has nothing to do,
     // and 10 000 empty workgroups that each reserve 26 KB of LDS took 64 us
@@ -800,8 +803,12 @@ constexpr size_t RASTER_LDS_MAX = raster_lds_bytes(RPE_MAX_IMAGE_DIM, raster_key
                                                    rpe_fast_tiles(RPE_MAX_IMAGE_DIM, RPE_MAX_IMAGE_DIM));
 static_assert(RASTER_LDS_MAX <= RPE_CU_LDS_BYTES, "the largest image's rows, entries and tiles fit a CU's LDS");
 
-void rpe_launch_raster_retain(rpe_handle *h, int n_img)
+// The three launchers of the selection chain take the levels [l0, l1) they run (a level group, orb_groups.h, or all
+// twelve) and the stream they run on.  LDS sizes and list tiers stay those of the handle's largest level whatever the
+// range, so a level's workgroup is launched the same way in every range; an empty grid is not launched.
+void rpe_launch_raster_retain(rpe_handle *h, int n_img, int l0, int l1, hipStream_t stream)
 {
+    if (l1 <= l0) return;
     int rows_cap = 0, ccap_max = 0, nt_max = 0, wmax = 0, nlev_big = 0;
     for (int l = 0; l < RPE_NLEVELS; ++l) {
         rows_cap = std::max(rows_cap, h->lay.lv[l].h); ccap_max = std::max(ccap_max, h->lay.lv[l].ccap);
@@ -811,32 +818,34 @@ void rpe_launch_raster_retain(rpe_handle *h, int n_img)
     const int key_cap = raster_key_cap(ccap_max, wmax);
     const size_t lds = raster_lds_bytes(rows_cap, key_cap, nt_max);
     assert(lds <= RASTER_LDS_MAX);
-    hipLaunchKernelGGL(raster_corners_kernel, dim3(RPE_NLEVELS, n_img), dim3(256), lds, h->stream,
+    hipLaunchKernelGGL(raster_corners_kernel, dim3(l1 - l0, n_img), dim3(256), lds, stream,
                        (const unsigned *)h->d_tile_list, (const int *)h->d_tile_cnt,
-                       h->d_corner, h->d_corner_count, h->d_ovf, h->lay, h->n_tiles_fast, rows_cap, key_cap);
-    hipLaunchKernelGGL(retain_fast_kernel, dim3(RPE_NLEVELS, n_img), dim3(64 * RPE_RETAIN_FAST_WAVES), rpe_retain_lds(0, std::min(ccap_max, RPE_RETAIN_TIER)), h->stream,
+                       h->d_corner, h->d_corner_count, h->d_ovf, h->lay, h->n_tiles_fast, rows_cap, key_cap, l0);
+    hipLaunchKernelGGL(retain_fast_kernel, dim3(l1 - l0, n_img), dim3(64 * RPE_RETAIN_FAST_WAVES), rpe_retain_lds(0, std::min(ccap_max, RPE_RETAIN_TIER)), stream,
                        (const unsigned *)h->d_corner, (const int *)h->d_corner_count, h->d_cand_xy, h->d_cand_count, h->d_ovf, h->lay,
-                       0, std::min(ccap_max, RPE_RETAIN_TIER), n_img);
-    if (nlev_big > 0)
-        hipLaunchKernelGGL(retain_fast_kernel, dim3(nlev_big, std::min(n_img, 512)), dim3(64 * RPE_RETAIN_FAST_WAVES), rpe_retain_lds(0, ccap_max), h->stream,
+                       0, std::min(ccap_max, RPE_RETAIN_TIER), n_img, l0);
+    if (std::min(nlev_big, l1) > l0)       // the levels with long lists are [0, nlev_big): those of them in the range
+        hipLaunchKernelGGL(retain_fast_kernel, dim3(std::min(nlev_big, l1) - l0, std::min(n_img, 512)), dim3(64 * RPE_RETAIN_FAST_WAVES), rpe_retain_lds(0, ccap_max), stream,
                            (const unsigned *)h->d_corner, (const int *)h->d_corner_count, h->d_cand_xy, h->d_cand_count, h->d_ovf, h->lay,
-                           RPE_RETAIN_TIER, ccap_max, n_img);
+                           RPE_RETAIN_TIER, ccap_max, n_img, l0);
 }
 
 // ----------------------------------------------------------------- harris
 // orb.cpp HarrisResponses: 7x7 block of 3x3 Sobel-like derivatives, f32 response.
 __global__ __launch_bounds__(256) void harris_kernel(const uint8_t *__restrict__ pyr, const unsigned *__restrict__ cand_xy,
                                                       const int *__restrict__ cand_count, float *__restrict__ cand_resp,
-                                                      RpeDeviceLayout lay, int nb, int n_img)
+                                                      RpeDeviceLayout lay, int nb, int n_img, int l0, int l1)
 {
     // dense lane -> candidate mapping over the per-level counts: the slot arrays are sized 4*quota + 256 per level but
-    // hold ~2*quota entries, so slot-indexed lanes were two thirds idle
+    // hold ~2*quota entries, so slot-indexed lanes were two thirds idle.  The walk covers the launch's levels [l0, l1)
+    // and reads no other level's count: retain_fast of another level group may be writing it on another stream
     int img, blk;
     if (!xcd_image_block(nb, n_img, img, blk)) return;
     const int dsel = blk * 256 + threadIdx.x;
     int l = -1, ci = 0, acc = 0;
 #pragma unroll
     for (int k = 0; k < RPE_NLEVELS; ++k) {
+        if (k < l0 || k >= l1) continue;                     // uniform
         const int n = cand_count[img * RPE_NLEVELS + k];
         if (l < 0 && dsel < acc + n) { l = k; ci = dsel - acc; }
         acc += n;
@@ -889,11 +898,13 @@ __global__ __launch_bounds__(256) void harris_kernel(const uint8_t *__restrict__
     cand_resp[(long long)img * lay.cand_total + c] = (t3 - t4) * scale_sq_sq;
 }
 
-void rpe_launch_harris(rpe_handle *h, int n_img)
+void rpe_launch_harris(rpe_handle *h, int n_img, int l0, int l1, hipStream_t stream)
 {
-    const int nb = (h->lay.cand_total + 255) / 256;
-    hipLaunchKernelGGL(harris_kernel, dim3(xcd_image_grid(nb, n_img)), dim3(256), 0, h->stream,
-                       h->d_pyr, h->d_cand_xy, h->d_cand_count, h->d_cand_resp, h->lay, nb, n_img);
+    if (l1 <= l0) return;
+    // workgroups per image: the candidate capacity of the range's levels (cand_total when it is all of them)
+    const int nb = (h->lay.lv[l1 - 1].cand_off + h->lay.lv[l1 - 1].kcap2 - h->lay.lv[l0].cand_off + 255) / 256;
+    hipLaunchKernelGGL(harris_kernel, dim3(xcd_image_grid(nb, n_img)), dim3(256), 0, stream,
+                       h->d_pyr, h->d_cand_xy, h->d_cand_count, h->d_cand_resp, h->lay, nb, n_img, l0, l1);
 }
 
 // -------------------------------------------------------------- keypoints
@@ -906,11 +917,11 @@ struct HarrisGE { __device__ __forceinline__ bool operator()(unsigned long long 
 
 __global__ __launch_bounds__(64 * RPE_RETAIN_HARRIS_WAVES) void retain_harris_kernel(unsigned *__restrict__ cand_xy, float *__restrict__ cand_resp,
                                                             const int *__restrict__ cand_count, int *__restrict__ kp_lvl_count,
-                                                            RpeDeviceLayout lay, int lo, int cap)
+                                                            RpeDeviceLayout lay, int lo, int cap, int l0)
 {
     extern __shared__ unsigned long long s_e[];               // [cap] elements, then [cap + 2] u16 stopper positions
     __shared__ int s_ctl[3 * RPE_RETAIN_HARRIS_WAVES];
-    const int tid = threadIdx.x, l = blockIdx.x, img = blockIdx.y;
+    const int tid = threadIdx.x, l = l0 + blockIdx.x, img = blockIdx.y;
     const RpeLevel &L = lay.lv[l];
     const int n1 = cand_count[img * RPE_NLEVELS + l];
     const int q = L.quota;
@@ -988,8 +999,9 @@ __global__ __launch_bounds__(256) void compact_keypoints_kernel(const unsigned *
     }
 }
 
-void rpe_launch_keypoints(rpe_handle *h, int n_img)
+void rpe_launch_retain_harris(rpe_handle *h, int n_img, int l0, int l1, hipStream_t stream)
 {
+    if (l1 <= l0) return;
     int kcap2_max = 0, nlev_big = 0;
     for (int l = 0; l < RPE_NLEVELS; ++l) {
         kcap2_max = std::max(kcap2_max, h->lay.lv[l].kcap2);
@@ -997,11 +1009,16 @@ void rpe_launch_keypoints(rpe_handle *h, int n_img)
     }
     const int tier = std::min(kcap2_max, RPE_RETAIN_TIER / 2);
     assert(kcap2_max <= RETAIN_HARRIS_CAP_MAX);
-    hipLaunchKernelGGL(retain_harris_kernel, dim3(RPE_NLEVELS, n_img), dim3(64 * RPE_RETAIN_HARRIS_WAVES), rpe_retain_lds(1, tier), h->stream,
-                       h->d_cand_xy, h->d_cand_resp, (const int *)h->d_cand_count, h->d_kp_lvl_count, h->lay, 0, tier);
-    if (nlev_big > 0)
-        hipLaunchKernelGGL(retain_harris_kernel, dim3(nlev_big, n_img), dim3(64 * RPE_RETAIN_HARRIS_WAVES), rpe_retain_lds(1, kcap2_max), h->stream,
-                           h->d_cand_xy, h->d_cand_resp, (const int *)h->d_cand_count, h->d_kp_lvl_count, h->lay, RPE_RETAIN_TIER / 2, kcap2_max);
+    hipLaunchKernelGGL(retain_harris_kernel, dim3(l1 - l0, n_img), dim3(64 * RPE_RETAIN_HARRIS_WAVES), rpe_retain_lds(1, tier), stream,
+                       h->d_cand_xy, h->d_cand_resp, (const int *)h->d_cand_count, h->d_kp_lvl_count, h->lay, 0, tier, l0);
+    if (std::min(nlev_big, l1) > l0)
+        hipLaunchKernelGGL(retain_harris_kernel, dim3(std::min(nlev_big, l1) - l0, n_img), dim3(64 * RPE_RETAIN_HARRIS_WAVES), rpe_retain_lds(1, kcap2_max), stream,
+                           h->d_cand_xy, h->d_cand_resp, (const int *)h->d_cand_count, h->d_kp_lvl_count, h->lay, RPE_RETAIN_TIER / 2, kcap2_max, l0);
+}
+
+// every level's retain_harris has run: the level-major concatenation, on the handle's stream
+void rpe_launch_keypoints(rpe_handle *h, int n_img)
+{
     hipLaunchKernelGGL(compact_keypoints_kernel, dim3(n_img), dim3(256), 0, h->stream,
                        (const unsigned *)h->d_cand_xy, (const float *)h->d_cand_resp, (const int *)h->d_kp_lvl_count,
                        h->d_kp_xy, h->d_kp_resp, h->d_kp_pt, h->d_kp_count, h->d_ovf, h->lay);

@@ -224,6 +224,11 @@ static int build_tables(rpe_handle *h)
     for (const RpeTile &t : fast)
         if (t.tx < 4 || t.ty < 4) { h->err = "FAST tile origin below 4: the tile loads would start outside the level"; return RPE_ERR_INVALID; }
     h->n_tiles_full = (int)full.size(); h->n_tiles_fast = (int)fast.size();
+    {
+        int ntile[RPE_NLEVELS];
+        for (int l = 0; l < RPE_NLEVELS; ++l) ntile[l] = L.lv[l].ntile;
+        rpe_orb_groups(ntile, RPE_NLEVELS, RPE_ORB_GROUPS, h->orb_group);
+    }
     DM(h, h->d_tiles_full, full.size());
     DM(h, h->d_tiles_fast, fast.size() ? fast.size() : 1);
     HIPCHK(h, hipMemcpy(h->d_tiles_full, full.data(), full.size() * sizeof(RpeTile), hipMemcpyHostToDevice));
@@ -497,6 +502,12 @@ extern "C" int rpe_create(const rpe_config *cfg, rpe_handle **out)
         if (is_sift && (rc = rpe_sift_create(h)) != RPE_OK) break;
         for (int i = 0; i <= RPE_STAGE_COUNT; ++i)
             if (hipEventCreate(&h->ev[i]) != hipSuccess) { h->err = "hipEventCreate failed"; rc = RPE_ERR_HIP; break; }
+        if (rc != RPE_OK || is_sift) break;
+        // the grouped schedule of run_orb: its side stream orders itself against the handle's stream through the events alone
+        if (hipStreamCreateWithFlags(&h->side_stream, hipStreamNonBlocking) != hipSuccess) { h->err = "hipStreamCreateWithFlags failed"; rc = RPE_ERR_HIP; break; }
+        bool ev_ok = hipEventCreateWithFlags(&h->ev_join, hipEventDisableTiming) == hipSuccess;
+        for (int g = 0; g < RPE_ORB_GROUPS && ev_ok; ++g) ev_ok = hipEventCreateWithFlags(&h->ev_fork[g], hipEventDisableTiming) == hipSuccess;
+        if (!ev_ok) { h->err = "hipEventCreateWithFlags failed"; rc = RPE_ERR_HIP; break; }
     } while (0);
     if (rc != RPE_OK) { g_create_err = h->err; rpe_destroy(h); return rc; }
     *out = h;
@@ -515,6 +526,9 @@ extern "C" void rpe_destroy(rpe_handle *h)
     if (!h) return;
     hipSetDevice(h->cfg.device);
     if (h->stream) hipStreamSynchronize(h->stream);
+    if (h->side_stream) { hipStreamSynchronize(h->side_stream); hipStreamDestroy(h->side_stream); }
+    for (int g = 0; g < RPE_ORB_GROUPS; ++g) if (h->ev_fork[g]) hipEventDestroy(h->ev_fork[g]);
+    if (h->ev_join) hipEventDestroy(h->ev_join);
     rpe_sift_destroy(h);
     for (auto &g : h->graphs) { hipGraphExecDestroy(g.exec); hipGraphDestroy(g.graph); }
     for (void *p : h->dev_allocs) hipFree(p);
@@ -639,12 +653,51 @@ static int run_orb(rpe_handle *h, const uint8_t *d_a, const uint8_t *d_b, int na
         int rc = load_level0(h, d_a, d_b, na, nb);
         if (rc) return rc;
     }
-    rpe_launch_pyramid(h, n);
-    MARK(h, RPE_STAGE_FAST);      rpe_launch_fast(h, n);
+    // The selection chain of a level reads only what FAST wrote for that level, and FAST of a level only that level.  Small
+    // batches (every captured one among them) build the pyramid, then run FAST and the chain once over all levels, one
+    // kernel after the other.  From RPE_ORB_GROUP_MIN_IMAGES images on, the work is cut into level groups, largest levels
+    // first (orb_groups.h), and the side stream takes what is bound by something else than its neighbour on the handle's
+    // stream: FAST of group 0 (vector issue) as soon as the levels it reads exist, beside the resize of the levels above
+    // them (HBM and latency); behind it the chain of group 0 and, behind each group's event, the chains of the groups
+    // whose FAST runs on the handle's stream (latency), beside FAST of the groups after them.  The last group's chain
+    // follows its FAST on the handle's stream, which then waits for the side stream.  The stage events stay on the handle's
+    // stream and partition the step as before: `pyramid` spans the resize launches with FAST of group 0 beside the later
+    // ones, `fast` the other groups' FAST and what the side stream ran beside them, `select`, `harris` and `keypoints` the
+    // last group's chain, `keypoints` also the wait for the side stream and compact.
+    const bool grouped = n >= RPE_ORB_GROUP_MIN_IMAGES;
+    const int last = grouped ? RPE_ORB_GROUPS - 1 : 0;
+    const RpeOrbGroup all = {0, RPE_NLEVELS, 0, h->n_tiles_fast};
+    const int pyr_split = grouped ? std::max(h->orb_group[0].l1, 1) : RPE_NLEVELS;   // grouped: the levels group 0 reads come first
+    hipError_t fe = hipSuccess;                   // the first failed fork / join call: what follows it stays on the handle's stream
+    bool forked = false;
+    rpe_launch_pyramid(h, n, 1, pyr_split);
+    if (!grouped) MARK(h, RPE_STAGE_FAST);
+    for (int g = 0; g < last; ++g) {
+        const RpeOrbGroup &G = h->orb_group[g];
+        if (g > 0) rpe_launch_fast(h, n, G.t0, G.nt, h->stream);
+        hipStream_t s = h->stream;
+        if (fe == hipSuccess) fe = hipEventRecord(h->ev_fork[g], h->stream);
+        if (fe == hipSuccess) fe = hipStreamWaitEvent(h->side_stream, h->ev_fork[g], 0);
+        if (fe == hipSuccess) { s = h->side_stream; forked = true; }
+        if (g == 0) rpe_launch_fast(h, n, G.t0, G.nt, s);
+        rpe_launch_raster_retain(h, n, G.l0, G.l1, s);
+        rpe_launch_harris(h, n, G.l0, G.l1, s);
+        rpe_launch_retain_harris(h, n, G.l0, G.l1, s);
+        if (g == 0) { rpe_launch_pyramid(h, n, pyr_split, RPE_NLEVELS); MARK(h, RPE_STAGE_FAST); }
+    }
+    const RpeOrbGroup &G = grouped ? h->orb_group[last] : all;
+    rpe_launch_fast(h, n, G.t0, G.nt, h->stream);
     MARK(h, RPE_STAGE_NMS);       // fused into fast_nms_kernel
-    MARK(h, RPE_STAGE_SELECT);    rpe_launch_raster_retain(h, n);
-    MARK(h, RPE_STAGE_HARRIS);    rpe_launch_harris(h, n);
-    MARK(h, RPE_STAGE_KEYPOINTS); rpe_launch_keypoints(h, n);
+    MARK(h, RPE_STAGE_SELECT);    rpe_launch_raster_retain(h, n, G.l0, G.l1, h->stream);
+    MARK(h, RPE_STAGE_HARRIS);    rpe_launch_harris(h, n, G.l0, G.l1, h->stream);
+    MARK(h, RPE_STAGE_KEYPOINTS); rpe_launch_retain_harris(h, n, G.l0, G.l1, h->stream);
+    if (forked) {                 // whatever failed above, the side stream's work is joined before anything reads it
+        hipError_t je = hipEventRecord(h->ev_join, h->side_stream);
+        if (je == hipSuccess) je = hipStreamWaitEvent(h->stream, h->ev_join, 0);
+        if (je != hipSuccess) { hipStreamSynchronize(h->side_stream); if (fe == hipSuccess) fe = je; }
+    }
+    HIPCHK(h, fe);
+    rpe_launch_keypoints(h, n);
     MARK(h, RPE_STAGE_ANGLE);     rpe_launch_orient_describe(h, n);
     MARK(h, RPE_STAGE_BLUR);      // both fused into orient_describe_kernel (the whole-level blur runs on demand in rpe_orb_debug_fetch)
     MARK(h, RPE_STAGE_DESCRIBE);
@@ -1855,6 +1908,8 @@ extern "C" int64_t rpe_orb_pyramid_pixels(const rpe_handle *h)
     for (int l = 0; l < RPE_NLEVELS; ++l) n += (int64_t)h->lay.lv[l].w * h->lay.lv[l].h;
     return n;
 }
+
+extern "C" int rpe_orb_group_min_images(void) { return RPE_ORB_GROUP_MIN_IMAGES; }
 
 extern "C" int rpe_orb_debug_fetch(rpe_handle *h, int index, int which, uint8_t *h_out)
 {

@@ -12,6 +12,7 @@
 #include <vector>
 #include "../../include/rpe_amd.h"
 #include "buf_layout.h"
+#include "orb_groups.h"
 
 #define RPE_NLEVELS RPE_ORB_LEVELS
 #define RPE_EDGE 31            // ORB edgeThreshold (cv2 default; pose_estimator.py:85-91 leaves it)
@@ -20,6 +21,14 @@
 #define RPE_RANSAC_MAXCHUNK 512 // largest number of iterations evaluated per launch group (8 waves per pair)
 #define RPE_MAX_MODELS 10
 #define RPE_GRAPH_MAX_PAIRS 16    // batches up to this many pairs are replayed as a captured hipGraph
+// ORB detection over this many images and more runs in RPE_ORB_GROUPS level groups (orb_groups.h) on two streams: FAST of
+// the first group beside the resize of the levels above it, the selection chain of a group beside FAST of the next
+// (run_orb, rpe_api.hip).  The choice is by image count alone.  A captured batch is at most 2 * RPE_GRAPH_MAX_PAIRS
+// images, so no hipGraph ever holds a fork: the captured sequences stay linear.
+#define RPE_ORB_GROUP_MIN_IMAGES 33
+#define RPE_ORB_GROUPS 2          // measured 2 / 3 / 4, either group order, either side-stream priority: DESIGN.md section 4, round 20
+static_assert(RPE_ORB_GROUP_MIN_IMAGES > 2 * RPE_GRAPH_MAX_PAIRS, "a captured batch takes the linear schedule");
+static_assert(RPE_ORB_GROUPS >= 2 && RPE_ORB_GROUPS <= RPE_ORB_GROUP_MAX, "rpe_orb_groups cuts at most RPE_ORB_GROUP_MAX groups");
 #define RPE_MATCH_SPLIT_PAIRS 64   // batches up to this many pairs split a pair's Hamming matching over several workgroups
 #define RPE_GUIDED_LDS_UINT4 128    // the guided matcher's part of the first LDS region: 2 x 32 scanned records of 32 bytes
 #define RPE_TAB_RING 4            // pinned pieces the slot tables of rpe_frames_put* / rpe_enqueue_pairs rotate through
@@ -405,6 +414,12 @@ struct rpe_handle {
     int *d_coef = nullptr;            // resize coefficient tables
     RpePyrTile *d_pyr_tiles = nullptr;  // resize tiles of levels 1..11, level l at pyr_tile_off[l], raster order
     int pyr_tile_off[RPE_NLEVELS] = {}, pyr_tile_cnt[RPE_NLEVELS] = {};
+    // the grouped detection schedule of batches of RPE_ORB_GROUP_MIN_IMAGES images and more (run_orb): the level groups
+    // (build_tables), the stream that FAST of group 0 and the chains of all groups but the last run on, one event per
+    // group ('what group g's side-stream work reads is written') and the 'side stream is done' event; the events carry no timing
+    RpeOrbGroup orb_group[RPE_ORB_GROUPS] = {};
+    hipStream_t side_stream = nullptr;
+    hipEvent_t ev_fork[RPE_ORB_GROUPS] = {}, ev_join = nullptr;
     // image-shaped buffers
     uint8_t *d_pyr = nullptr;
     unsigned *d_tile_list = nullptr;  // [img][n_tiles_fast][RPE_FAST_TILE_CAP] score << 24 | y << 12 | x
@@ -627,10 +642,14 @@ static inline RpeLinkSrc rpe_link_src(const rpe_handle *h)
 }
 
 // ---- kernel launchers (defined in the .hip files) --------------------------
-void rpe_launch_pyramid(rpe_handle *h, int n_img);
-void rpe_launch_fast(rpe_handle *h, int n_img);
-void rpe_launch_raster_retain(rpe_handle *h, int n_img);
-void rpe_launch_harris(rpe_handle *h, int n_img);
+void rpe_launch_pyramid(rpe_handle *h, int n_img, int l0, int l1);   // levels [max(l0, 1), l1) from the level below each, in order
+// FAST over the tiles [t0, t0 + nt) of d_tiles_fast and the selection chain (raster + retain_fast, harris, retain_harris)
+// over the levels [l0, l1), on `stream`: a level group of orb_groups.h or everything.  compact (rpe_launch_keypoints) reads
+// every level.
+void rpe_launch_fast(rpe_handle *h, int n_img, int t0, int nt, hipStream_t stream);
+void rpe_launch_raster_retain(rpe_handle *h, int n_img, int l0, int l1, hipStream_t stream);
+void rpe_launch_harris(rpe_handle *h, int n_img, int l0, int l1, hipStream_t stream);
+void rpe_launch_retain_harris(rpe_handle *h, int n_img, int l0, int l1, hipStream_t stream);
 void rpe_launch_keypoints(rpe_handle *h, int n_img);
 void rpe_launch_orient_describe(rpe_handle *h, int n_img);
 void rpe_launch_debug_blur(rpe_handle *h, int img);

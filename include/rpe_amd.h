@@ -790,6 +790,89 @@ int rpe_triangulate_tracks(rpe_handle *h, int n_tracks, const int32_t *track_sta
                            const rpe_camera *cams, double threshold_px, int min_views, double max_cos, int max_iters,
                            double *points, int32_t *info, double *rms, double *min_cos, uint8_t *obs_flag, double *obs_err);
 
+/* --------------------------------------------------------- window bundles */
+/* Bundle adjustment of windows of 2 .. RPE_WINDOW_MAX_VIEWS frames (NOT in the reference): the poses of a window's frames
+ * and the points of the tracks they see are refined together on one reprojection cost.  A stage-form call over the caller's
+ * arrays: tracks, poses and one K or cams exactly as rpe_triangulate_tracks takes them; points0[3 * n_tracks]: a start point
+ * per track in the frame of the poses (what rpe_triangulate_tracks returns); point_use[n_tracks] (NULL: every track; a
+ * track is used when its byte is not 0); obs_use[n_obs] (NULL: every observation; an observation is selected when its
+ * byte is exactly 1, so rpe_triangulate_tracks' obs_flag can be passed as it is); windows in CSR form: window w is the
+ * frames win_frame[win_start[w] .. win_start[w + 1]), W of them, distinct, in any order; windows may overlap, each is
+ * solved on its own from the caller's poses and points.
+ * The rule, for one window with frames F_0 .. F_(W-1) ("position" p = 0 .. W-1).  All arithmetic f64, + - * / sqrt only
+ * (sin for a rotation increment, as rpe_refine_poses), no contraction; a comparison with a NaN is false; finite(v) =
+ * fabs(v) <= DBL_MAX; a 3-vector dot product is (a0*b0 + a1*b1) + a2*b2.
+ *  Per observation: (x, y) = the normalised, undistorted point and f = (fx + fy) / 2 of its frame's camera, as in "track
+ *   points".
+ *  Points: track k's observation at position p is the lowest o in its segment with obs_frame[o] == F_p that is selected.
+ *   A used track with observations at two or more positions is a candidate.  Candidates are numbered j = 0, 1, .. in
+ *   ascending track order; the first max_points are the window's points, the rest are dropped and counted.  The sets
+ *   are fixed for the whole optimisation; there is no robust kernel.
+ *  Gauge: with (R_p, T_p) the caller's pose of F_p, the pose of position p relative to position 0 is
+ *   Q_p[r][c] = (R_p[r][0]*R_0[c][0] + R_p[r][1]*R_0[c][1]) + R_p[r][2]*R_0[c][2],
+ *   s_p[r] = T_p[r] - ((Q_p[r][0]*T_0[0] + Q_p[r][1]*T_0[1]) + Q_p[r][2]*T_0[2]);  n_p = s_p . s_p is the squared distance
+ *   of the two centres.  The anchor A is the position >= 1 with the largest n_p (a later position wins only when strictly
+ *   larger); l = sqrt(n_A) is the unit of scale.  The problem is solved in position 0's coordinates scaled by 1 / l:
+ *   t_p[r] = s_p[r] / l and, per point, X[r] = (((R_0[r][0]*P0 + R_0[r][1]*P1) + R_0[r][2]*P2) + T_0[r]) / l with P the start
+ *   point.  Position 0 is the identity and never moves; t_A moves on the unit sphere only.
+ *  Codes, tested in this order: l not > 0 or not finite: RPE_WINDOW_NO_BASELINE.  A position p >= 1 with fewer than
+ *   max(min_obs, 6) observations of points: RPE_WINDOW_TOO_FEW.  After the loop RPE_WINDOW_REJECTED or RPE_WINDOW_OK (Result).
+ *  Parameters: position p >= 1 has the block (w[3], d[3]), the anchor (w[3], a[2]); the blocks follow each other in
+ *   ascending position: 6 W - 7 camera parameters.  Q_p <- exp([w]x) Q_p; t_p <- t_p + d; t_A <- normalise((t_A + a0*b1) +
+ *   a1*b2) with (b1, b2) the tangent basis of rpe_refine_poses at t_A;  X_j <- X_j + dp_j, three parameters per point.
+ *  Rows of a view, in pixels: at position 0, y = X; else a = Q_p X (each row (q0*X0 + q1*X1) + q2*X2), y = a + t_p.
+ *   u = y0/y2, v = y1/y2, e0 = f*(u - x), e1 = f*(v - y), s = f/y2.  Derivatives as in "link bundles": by w as in "link
+ *   poses" polish; Jt = (s, 0, -s*u) / (0, s, -s*v) by t; (Jt . b1, Jt . b2) by the tangent step; by X: Jt Q_p (column k:
+ *   (Jt0*Q[0][k] + Jt1*Q[1][k]) + Jt2*Q[2][k]), at position 0 Jt itself.  A point's cost is the sum over its views in
+ *   ascending position, from 0, of (e0*e0 + e1*e1); cost = the sum over the points.
+ *  The step at damping lambda solves (J'J + lambda diag J'J) step = -J'r exactly by eliminating the points.  Per point,
+ *   over its views in ascending position, x row before y row: V = Jp'Jp (upper triangle), g_p = Jp'e; V_ii <- V_ii +
+ *   lambda*V_ii; its inverse by the adjugate divided by det = (v00*c00 + v01*c01) + v02*c02 as in "link bundles"; det > 0
+ *   and finite, else the step is rejected.  Per view at p >= 1: W_p[k][i] = Jc0[k]*Jx0[i] + Jc1[k]*Jx1[i] (k: the
+ *   block's parameters, Jc the two rows by them, Jx by the point), Y_p[k][i] = (Vi[i][0]*W_p[k][0] + Vi[i][1]*W_p[k][1]) +
+ *   Vi[i][2]*W_p[k][2].  Over the points: U_p[k][m] = sum (Jc0[k]*Jc0[m] + Jc1[k]*Jc1[m]), g_c,p[k] = sum (Jc0[k]*e0 +
+ *   Jc1[k]*e1), v_p[k] = sum Y_p[k] . g_p over the points position p sees; S_pq[k][m] = sum Y_p[k] . W_q[m] over the
+ *   points positions p <= q both see.  H = (U + lambda diag U) - S with U block diagonal (0 - S elsewhere), g = g_c - v;
+ *   H step_c = -g by the Cholesky of rpe_refine_poses at lambda = 0 (not positive definite: rejected);
+ *   dp = -Vi (g_p + W' step_c): u_i = g_p[i], then u_i <- u_i + W_p[k][i]*step_c[block p, k] over the point's views in
+ *   ascending position and k ascending; dp_i = -((Vi[i][0]*u0 + Vi[i][1]*u1) + Vi[i][2]*u2).
+ *  Sums over points: U, g_c, v, S of one pair of positions: lane l of 64 adds its points j = l, l + 64, .. in ascending
+ *   order, then the butterfly (partner lane ^ 32, 16, .. 1).  The cost: lane l of 256 likewise, the butterfly, then the
+ *   four wave totals ((w0 + w1) + w2) + w3.  No atomics decide a value: bit-deterministic run to run.
+ *  LM: the conventions of rpe_refine_poses: lambda0 = 1e-3; at most max_iters iterations, each building the step at the
+ *   current state; a rejected step or a trial whose cost is not finite or not strictly lower: lambda * 10; an accepted
+ *   one: lambda / 10, and the loop ends when it lowered the cost by no more than 1e-6 of it or the length of step_c (its
+ *   squares added in ascending order) is <= 1e-9.  A start cost that is not finite runs no iteration.
+ *  Result: the bundled state is returned (RPE_WINDOW_OK) only if a step was accepted, every pose entry and point
+ *   coordinate is finite and every point has y2 > 0 in every view that observes it; otherwise RPE_WINDOW_REJECTED.  Back to
+ *   the caller's frame: R_out[r][c] = (Q_p[r][0]*R_0[0][c] + Q_p[r][1]*R_0[1][c]) + Q_p[r][2]*R_0[2][c], T_out[r] =
+ *   l*t_p[r] + ((Q_p[r][0]*T_0[0] + Q_p[r][1]*T_0[1]) + Q_p[r][2]*T_0[2]); point: m_r = l*X[r] - T_0[r], P_out[c] =
+ *   (R_0[0][c]*m0 + R_0[1][c]*m1) + R_0[2][c]*m2.  Position 0 returns its input bits.  For every code but OK all poses and
+ *   points are the input bits.
+ *  Outputs (host, any may be NULL): R_out[9 * n], T_out[3 * n] with n = win_start[n_win], laid out like win_frame;
+ *   points[n_win * max_points * 3] (zeros past the count); point_track[n_win * max_points]: the track of point j, -1 past
+ *   the count; counts[n_win * 4] = {W, points, observations of points, candidates dropped by max_points};
+ *   info[n_win * 4] = {RPE_WINDOW_* code, iterations begun, steps accepted, anchor position}; rms[n_win * 2] = sqrt(cost /
+ *   observations) of the input state and of the returned state (both 0 for NO_BASELINE and TOO_FEW).
+ * The call uses device buffers of its own, created on the first call and grown to the largest call; neither the workspace
+ * nor the record of the last run is touched: every fetch of the run and every call behind it returns the same bits.
+ * RPE_ERR_INVALID: the refusals of rpe_triangulate_tracks on the shared arguments (n_tracks, track_start, obs_frame, obs_xy,
+ * n_frames, R_abs, T_abs, K / cams); n_win < 0; a NULL win_start or win_frame with n_win > 0; win_start[0] != 0 or
+ * decreasing; a window of fewer than 2 or more than RPE_WINDOW_MAX_VIEWS frames; a frame index outside 0 .. n_frames - 1 or
+ * repeated inside a window; a non-finite pose of a frame some window names; points0 NULL with n_tracks > 0, or a non-finite
+ * start point of a used track; max_points < 1; min_obs < 0; max_iters outside 1 .. 100.  RPE_ERR_CAPACITY: max_points >
+ * RPE_WINDOW_MAX_POINTS.  All checks are host-side; nothing is launched and the handle stays usable after a refusal.
+ * n_win == 0 passes the scalar checks, succeeds and writes nothing. */
+#define RPE_WINDOW_MAX_VIEWS 8
+#define RPE_WINDOW_MAX_POINTS 16384
+enum { RPE_WINDOW_OK = 0, RPE_WINDOW_NO_BASELINE = 1, RPE_WINDOW_TOO_FEW = 2, RPE_WINDOW_REJECTED = 3 };
+int rpe_bundle_windows(rpe_handle *h, int n_tracks, const int32_t *track_start, const int32_t *obs_frame, const float *obs_xy,
+                       const double *points0, const uint8_t *point_use, const uint8_t *obs_use,
+                       int n_frames, const double *R_abs, const double *T_abs, const double *K, const rpe_camera *cams,
+                       int n_win, const int32_t *win_start, const int32_t *win_frame, int max_points, int min_obs, int max_iters,
+                       double *R_out, double *T_out, double *points, int32_t *point_track, int32_t *counts, int32_t *info,
+                       double *rms);
+
 /* ---------------------------------------------------------- stage entry */
 /* replaces extractor.detectAndCompute(image, None) (pose_estimator.py:108)
  * for n_images images (n_images <= 2*max_batch).  kps[n_images*cap],

@@ -36,6 +36,10 @@ TRACK_COUNTS = ("n_tracks", "n_obs", "n_edges", "dropped_conflict", "dropped_sho
 # info[:, 0] / 'code' of triangulate_tracks (RPE_TRACKPT_*)
 TRACKPT_OK, TRACKPT_TOO_FEW, TRACKPT_DEGENERATE, TRACKPT_BEHIND, TRACKPT_OUTLIERS, TRACKPT_LOW_PARALLAX = 0, 1, 2, 3, 4, 5
 TRACKPT_NAMES = ("OK", "TOO_FEW", "DEGENERATE", "BEHIND", "OUTLIERS", "LOW_PARALLAX")
+# info[:, 0] / 'code' of bundle_windows (RPE_WINDOW_*)
+WINDOW_OK, WINDOW_NO_BASELINE, WINDOW_TOO_FEW, WINDOW_REJECTED = 0, 1, 2, 3
+WINDOW_NAMES = ("OK", "NO_BASELINE", "TOO_FEW", "REJECTED")
+WINDOW_MAX_VIEWS, WINDOW_MAX_POINTS = 8, 16384   # RPE_WINDOW_MAX_VIEWS, RPE_WINDOW_MAX_POINTS
 UNDISTORT_ITERS = 5               # RPE_UNDISTORT_ITERS: fixed-point rounds of the camera path's undistortion
 
 # The binding, one entry per function of include/rpe_amd.h: "<return>:<one letter per parameter>".  Parameters: p pointer or
@@ -63,6 +67,7 @@ _SIGNATURES = {
     "rpe_link_bundles": "i:pipppppdiippppppppp", "rpe_bundle_three_view": "i:pippppppppppddippppppppp",
     "rpe_last_run_pairs": "i:p", "rpe_build_tracks": "i:ppiipppppp", "rpe_tracks_from_matches": "i:piippppppppipppppp",
     "rpe_triangulate_tracks": "i:pipppipppppdidipppppp",
+    "rpe_bundle_windows": "i:pippppppippppippiiippppppp",
     "rpe_guided_matches": "i:pippdipppppp",
     "rpe_guided_matches_l2": "i:pippddpppppp",
     "rpe_pair_homographies": "i:piidppppp", "rpe_find_homography": "i:ppppipidppppp",
@@ -571,6 +576,55 @@ class Engine:
                                                   _p(pts), _p(info), _p(rms), _p(mc), _p(flag), _p(err)))
         return {'points': pts, 'code': info[:, 0].copy(), 'n_used': info[:, 1].copy(), 'n_inliers': info[:, 2].copy(),
                 'iterations': info[:, 3].copy(), 'rms': rms, 'min_cos': mc, 'obs_flag': flag, 'obs_err': err}
+
+    # ---- window bundles (rpe_bundle_windows; not in the reference)
+    def bundle_windows(self, tracks, points, R_abs, T_abs, windows, K=None, cameras=None, obs_use=None, point_use=None,
+                       max_points=4096, min_obs=8, max_iters=10):
+        """Bundle adjustment of windows of 2 .. 8 frames over a run's tracks (rpe_bundle_windows).  tracks: the dict
+        build_tracks returns; points f64[n, 3]: a start point per track in the frame of the poses (triangulate_tracks'
+        'points'); R_abs [F, 3, 3], T_abs [F, 3]: world-to-camera poses; windows: a list of lists of distinct frames, the
+        first of each is its gauge; exactly one of K and cameras; obs_use u8[n_obs]: an observation is selected where the
+        byte is 1 (triangulate_tracks' 'obs_flag' passes as it is), point_use u8[n]: a track is used where it is not 0;
+        None selects all.  Each window is solved on its own from these inputs.  Returns a dict: 'R', 'T': lists, one
+        [W, 3, 3] / [W, 3] array per window, in the caller's frame; 'points': a list of f64[n_w, 3]; 'point_track': a list
+        of i32[n_w]; 'code' (WINDOW_*), 'views', 'n_points', 'n_obs', 'dropped', 'iterations', 'accepted', 'anchor'
+        i32[n_win]; 'rms' f64[n_win, 2] (px, before and after).  For every code but WINDOW_OK the inputs come back.  The
+        last run stays fetchable."""
+        ts, of = _i32(tracks['track_start']), _i32(tracks['obs_frame'])
+        xy = np.ascontiguousarray(tracks['obs_xy'], np.float32).reshape(-1, 2)
+        R = np.ascontiguousarray(np.asarray(R_abs, np.float64).reshape(-1, 9))
+        T = np.ascontiguousarray(np.asarray(T_abs, np.float64).reshape(-1, 3))
+        p0 = np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 3))
+        F, n = R.shape[0], ts.size - 1
+        if n < 0 or T.shape[0] != F or of.size != xy.shape[0] or int(ts[-1]) != of.size or p0.shape[0] != n:
+            raise ValueError("bundle_windows: track_start must end at the number of observations, points hold one row per track, and R_abs and T_abs one pose per frame")
+        if (K is None) == (cameras is None):
+            raise ValueError("bundle_windows: exactly one of K and cameras must be given")
+        ou = None if obs_use is None else np.ascontiguousarray(obs_use, np.uint8).reshape(-1)
+        pu = None if point_use is None else np.ascontiguousarray(point_use, np.uint8).reshape(-1)
+        if (ou is not None and ou.size != of.size) or (pu is not None and pu.size != n):
+            raise ValueError("bundle_windows: obs_use has one byte per observation and point_use one per track")
+        wl = [_i32(w) for w in windows]
+        nw = len(wl)
+        wstart = np.zeros(nw + 1, np.int32)
+        wstart[1:] = np.cumsum([w.size for w in wl])
+        wframe = _i32(np.concatenate(wl)) if nw else np.zeros(0, np.int32)
+        k = None if K is None else _f64(K).reshape(9)
+        cams = None if cameras is None else camera_records(cameras, F)
+        mp, nwf = int(max_points), int(wstart[-1])
+        slots = nw * max(mp, 0) if mp <= WINDOW_MAX_POINTS else 0
+        Ro = np.zeros((nwf, 3, 3)); To = np.zeros((nwf, 3)); pts = np.zeros((slots, 3)); ptk = np.zeros(slots, np.int32)
+        counts = np.zeros((nw, 4), np.int32); info = np.zeros((nw, 4), np.int32); rms = np.zeros((nw, 2))
+        self._chk(self.lib.rpe_bundle_windows(self.h, n, _p(ts), _p(of), _p(xy), _p(p0), _opt(pu), _opt(ou), F, _p(R), _p(T), _opt(k),
+                                              _opt(cams), nw, _p(wstart), _p(wframe), mp, int(min_obs), int(max_iters),
+                                              _p(Ro), _p(To), _p(pts), _p(ptk), _p(counts), _p(info), _p(rms)))
+        cnt = counts[:, 1]
+        return {'R': [Ro[wstart[w]:wstart[w + 1]].copy() for w in range(nw)], 'T': [To[wstart[w]:wstart[w + 1]].copy() for w in range(nw)],
+                'points': [pts[w * mp:w * mp + cnt[w]].copy() for w in range(nw)],
+                'point_track': [ptk[w * mp:w * mp + cnt[w]].copy() for w in range(nw)],
+                'code': info[:, 0].copy(), 'views': counts[:, 0].copy(), 'n_points': cnt.copy(), 'n_obs': counts[:, 2].copy(),
+                'dropped': counts[:, 3].copy(), 'iterations': info[:, 1].copy(), 'accepted': info[:, 2].copy(),
+                'anchor': info[:, 3].copy(), 'rms': rms}
 
     # ---- guided matching (rpe_guided_matches / rpe_match_hamming_guided; not in the reference)
     def _poses(self, B, R, t):

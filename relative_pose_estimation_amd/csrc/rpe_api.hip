@@ -2229,6 +2229,102 @@ extern "C" int rpe_triangulate_tracks(rpe_handle *h, int n_tracks, const int32_t
                      {obs_flag, h->d_tp_oflag, no}, {obs_err, h->d_tp_oerr, sizeof(double) * no}});
 }
 
+// ---------------------------------------------------------------- window bundles (rpe_bundle_windows)
+// the buffers of one call: per track, per observation, per frame, per window frame, per window, per window and point slot
+static int windows_alloc(rpe_handle *h, size_t n_tracks, size_t n_obs, size_t n_frames, size_t n_wf, size_t n_win, size_t slots)
+{
+    return rpe_bufset_fit(h, h->set_windows,
+                          {buf_piece(h->d_wb_tstart, n_tracks + 1), buf_piece(h->d_wb_points0, 3 * n_tracks), buf_piece(h->d_wb_puse, n_tracks),
+                           buf_piece(h->d_wb_oframe, n_obs), buf_piece(h->d_wb_oxy, n_obs), buf_piece(h->d_wb_obs, n_obs), buf_piece(h->d_wb_ouse, n_obs),
+                           buf_piece(h->d_wb_R, 9 * n_frames), buf_piece(h->d_wb_T, 3 * n_frames), buf_piece(h->d_wb_cams, n_frames),
+                           buf_piece(h->d_wb_wstart, n_win + 1), buf_piece(h->d_wb_wframe, n_wf), buf_piece(h->d_wb_Rout, 9 * n_wf), buf_piece(h->d_wb_Tout, 3 * n_wf),
+                           buf_piece(h->d_wb_counts, 4 * n_win), buf_piece(h->d_wb_info, 4 * n_win), buf_piece(h->d_wb_rms, 2 * n_win),
+                           buf_piece(h->d_wb_fcnt, RPE_WINDOW_MAX_VIEWS * n_win),
+                           buf_piece(h->d_wb_ptrack, slots), buf_piece(h->d_wb_pobs, RPE_WINDOW_MAX_VIEWS * slots),
+                           buf_piece(h->d_wb_state, 6 * slots), buf_piece(h->d_wb_points, 3 * slots)});
+}
+
+// Every check on the host first, the buffers, the uploads, the three kernels, the fetch.  Neither the workspace nor the record
+// of the last run is touched.
+extern "C" int rpe_bundle_windows(rpe_handle *h, int n_tracks, const int32_t *track_start, const int32_t *obs_frame, const float *obs_xy,
+                                  const double *points0, const uint8_t *point_use, const uint8_t *obs_use,
+                                  int n_frames, const double *R_abs, const double *T_abs, const double *K, const rpe_camera *cams,
+                                  int n_win, const int32_t *win_start, const int32_t *win_frame, int max_points, int min_obs, int max_iters,
+                                  double *R_out, double *T_out, double *points, int32_t *point_track, int32_t *counts, int32_t *info,
+                                  double *rms)
+{
+    const char *who = "rpe_bundle_windows";
+    if (!h) return rpe_invalid(h, who);
+    if (n_tracks < 0) return rpe_invalid(h, who, "n_tracks must be >= 0");
+    if (n_frames < 1) return rpe_invalid(h, who, "n_frames must be >= 1");
+    if (n_win < 0) return rpe_invalid(h, who, "n_win must be >= 0");
+    if ((K == nullptr) == (cams == nullptr)) return rpe_invalid(h, who, "exactly one of K and cams must be given");
+    if (max_points < 1) return rpe_invalid(h, who, "max_points must be >= 1");
+    if (max_points > RPE_WINDOW_MAX_POINTS) { h->err = std::string(who) + ": max_points exceeds RPE_WINDOW_MAX_POINTS"; return RPE_ERR_CAPACITY; }
+    if (min_obs < 0) return rpe_invalid(h, who, "min_obs must be >= 0");
+    if (max_iters < 1 || max_iters > 100) return rpe_invalid(h, who, "max_iters must be 1 ... 100");
+    if (K) h->wb_cam_k = rpe_camera{K[0], K[4], K[2], K[5], {0., 0., 0., 0., 0., 0., 0., 0.}};
+    if (int rc = K ? check_cameras(h, &h->wb_cam_k, 1, who) : check_cameras(h, cams, n_frames, who)) return rc;
+    if (track_start) {
+        if (track_start[0] != 0) return rpe_invalid(h, who, "track_start[0] must be 0");
+        for (int k = 0; k < n_tracks; ++k)
+            if (track_start[k + 1] < track_start[k]) return rpe_invalid(h, who, "track_start must not decrease");
+    }
+    if (n_win == 0) return RPE_OK;
+    if (!win_start || !win_frame || !R_abs || !T_abs) return rpe_invalid(h, who);
+    if (n_tracks > 0 && (!track_start || !points0)) return rpe_invalid(h, who);
+    const size_t nt = (size_t)n_tracks, no = n_tracks > 0 ? (size_t)track_start[n_tracks] : 0, nf = (size_t)n_frames, nw = (size_t)n_win;
+    if (no > 0 && (!obs_frame || !obs_xy)) return rpe_invalid(h, who);
+    for (size_t o = 0; o < no; ++o)
+        if (obs_frame[o] < 0 || obs_frame[o] >= n_frames) return rpe_invalid(h, who, "a frame index outside 0 ... n_frames - 1");
+    if (win_start[0] != 0) return rpe_invalid(h, who, "win_start[0] must be 0");
+    for (int w = 0; w < n_win; ++w) {
+        const int W = win_start[w + 1] - win_start[w];
+        if (W < 0) return rpe_invalid(h, who, "win_start must not decrease");
+        if (W < 2 || W > RPE_WINDOW_MAX_VIEWS) return rpe_invalid(h, who, "a window must have 2 ... RPE_WINDOW_MAX_VIEWS frames");
+        const int32_t *f = win_frame + win_start[w];
+        for (int p = 0; p < W; ++p) {
+            if (f[p] < 0 || f[p] >= n_frames) return rpe_invalid(h, who, "a window frame outside 0 ... n_frames - 1");
+            for (int q = 0; q < p; ++q)
+                if (f[q] == f[p]) return rpe_invalid(h, who, "a frame repeated inside a window");
+            if (!all_finite(R_abs + (size_t)f[p] * 9, 9) || !all_finite(T_abs + (size_t)f[p] * 3, 3))
+                return rpe_invalid(h, who, "a non-finite pose of a frame that a window names");
+        }
+    }
+    for (size_t t = 0; t < nt; ++t)
+        if ((!point_use || point_use[t]) && !all_finite(points0 + 3 * t, 3)) return rpe_invalid(h, who, "a non-finite start point of a used track");
+    const size_t nwf = (size_t)win_start[n_win], slots = nw * (size_t)max_points;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (int rc = windows_alloc(h, nt, no, nf, nwf, nw, slots)) return rc;
+    const hipStream_t s = h->stream;
+    if (nt > 0) {
+        HIPCHK(h, hipMemcpyAsync(h->d_wb_tstart, track_start, sizeof(int) * (nt + 1), hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipMemcpyAsync(h->d_wb_points0, points0, sizeof(double) * 3 * nt, hipMemcpyHostToDevice, s));
+        if (point_use) HIPCHK(h, hipMemcpyAsync(h->d_wb_puse, point_use, nt, hipMemcpyHostToDevice, s));
+    }
+    if (no > 0) {
+        HIPCHK(h, hipMemcpyAsync(h->d_wb_oframe, obs_frame, sizeof(int) * no, hipMemcpyHostToDevice, s));
+        HIPCHK(h, hipMemcpyAsync(h->d_wb_oxy, obs_xy, sizeof(float2) * no, hipMemcpyHostToDevice, s));
+        if (obs_use) HIPCHK(h, hipMemcpyAsync(h->d_wb_ouse, obs_use, no, hipMemcpyHostToDevice, s));
+    }
+    HIPCHK(h, hipMemcpyAsync(h->d_wb_R, R_abs, sizeof(double) * 9 * nf, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(h->d_wb_T, T_abs, sizeof(double) * 3 * nf, hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(h->d_wb_cams, K ? &h->wb_cam_k : cams, sizeof(rpe_camera) * (K ? 1 : nf), hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(h->d_wb_wstart, win_start, sizeof(int) * (nw + 1), hipMemcpyHostToDevice, s));
+    HIPCHK(h, hipMemcpyAsync(h->d_wb_wframe, win_frame, sizeof(int) * nwf, hipMemcpyHostToDevice, s));
+    const RpeWindowJob job = {n_tracks, (int)no, n_win, max_points, min_obs, max_iters, K ? 0 : 1,
+                              h->d_wb_tstart, h->d_wb_oframe, h->d_wb_oxy, h->d_wb_points0,
+                              point_use && nt > 0 ? h->d_wb_puse : nullptr, obs_use && no > 0 ? h->d_wb_ouse : nullptr,
+                              h->d_wb_R, h->d_wb_T, h->d_wb_cams, h->d_wb_wstart, h->d_wb_wframe};
+    rpe_launch_windows(h, job);
+    HIPCHK(h, hipGetLastError());
+    // the wait also covers the uploads: the inputs have left the caller's arrays
+    return fetch(h, {{R_out, h->d_wb_Rout, sizeof(double) * 9 * nwf}, {T_out, h->d_wb_Tout, sizeof(double) * 3 * nwf},
+                     {points, h->d_wb_points, sizeof(double) * 3 * slots}, {point_track, h->d_wb_ptrack, sizeof(int) * slots},
+                     {counts, h->d_wb_counts, sizeof(int) * 4 * nw}, {info, h->d_wb_info, sizeof(int) * 4 * nw},
+                     {rms, h->d_wb_rms, sizeof(double) * 2 * nw}});
+}
+
 // ---------------------------------------------------------------- stage API: geometry
 // findEssentialMat, recoverPose and the refinement over uploaded points, each on one K (rpe_*) or on a camera per side and
 // pair (rpe_*_cameras, K == nullptr here).  Head of the three: capacity, cameras, points and intrinsics resident; `run`

@@ -375,6 +375,19 @@ struct RpeTrackPointJob {
     const rpe_camera *cams;
 };
 
+// One job of the window-bundle kernels (window_kernels.hip): the uploaded tracks, start points, masks (null: all set), poses,
+// cameras (cam_stride as above) and windows
+struct RpeWindowJob {
+    int n_tracks, n_obs, n_win, max_points, min_obs, max_iters, cam_stride;
+    const int *track_start, *obs_frame;
+    const float2 *obs_xy;
+    const double *points0;
+    const uint8_t *point_use, *obs_use;
+    const double *R, *T;
+    const rpe_camera *cams;
+    const int *win_start, *win_frame;
+};
+
 // One rpe_scale_links link on the device: pairs a and b of the last run, side bit 0 / 1 = the shared frame is image 2 of a / of b
 struct RpeLink { int a, b, side, pad; };
 // What the link kernels (link_kernels.hip) read of the last run, by value (rpe_link_src fills it from the handle): the link
@@ -526,6 +539,19 @@ struct rpe_handle {
     uint8_t *d_tp_oflag = nullptr;
     rpe_camera *d_tp_cams = nullptr;
     rpe_camera tp_cam_k{}; RpeBufSet set_track_points;
+
+    // rpe_bundle_windows only (set_windows, fitted to every call's tracks, observations, frames and windows).  The uploads; per
+    // observation the 32-byte record of wb_prepare; per window and point slot [n_win * max_points]: the track, the observation of
+    // each window position (8 ints), the state X and the trial X (6 f64) and the output point; per window frame the output pose
+    int *d_wb_tstart = nullptr, *d_wb_oframe = nullptr, *d_wb_wstart = nullptr, *d_wb_wframe = nullptr;
+    int *d_wb_ptrack = nullptr, *d_wb_pobs = nullptr, *d_wb_counts = nullptr, *d_wb_info = nullptr, *d_wb_fcnt = nullptr;
+    float2 *d_wb_oxy = nullptr;
+    double4 *d_wb_obs = nullptr;
+    double *d_wb_points0 = nullptr, *d_wb_R = nullptr, *d_wb_T = nullptr, *d_wb_state = nullptr, *d_wb_points = nullptr;
+    double *d_wb_Rout = nullptr, *d_wb_Tout = nullptr, *d_wb_rms = nullptr;
+    uint8_t *d_wb_puse = nullptr, *d_wb_ouse = nullptr;
+    rpe_camera *d_wb_cams = nullptr;
+    rpe_camera wb_cam_k{}; RpeBufSet set_windows;
     // results
     double *d_R = nullptr, *d_t = nullptr, *d_E = nullptr;
     int *d_inliers = nullptr, *d_status = nullptr;
@@ -690,6 +716,7 @@ void rpe_launch_bundle(rpe_handle *h, int n, int min_shared, int max_iters, bool
 bool rpe_bundles_in_lds(const rpe_handle *h);
 void rpe_launch_tracks(rpe_handle *h, const RpeTrackJob &job);
 void rpe_launch_track_points(rpe_handle *h, const RpeTrackPointJob &job);
+void rpe_launch_windows(rpe_handle *h, const RpeWindowJob &job);
 void rpe_launch_normalise(rpe_handle *h, const RpeRun &r);
 void rpe_launch_homography(rpe_handle *h, const RpeRun &r, int iters, double threshold_px, bool from_batch);
 void rpe_launch_undistort(rpe_handle *h, const float2 *d_pts, int n, const rpe_camera *d_cam, double2 *d_out);

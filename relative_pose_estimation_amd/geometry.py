@@ -134,6 +134,68 @@ def frame_groups(status, segment):
     return g
 
 
+def windows_of_groups(frame_group, size=8, overlap=2):
+    """Sliding windows of frames for _capi.Engine.bundle_windows: inside every run of consecutive frames that share one
+    group >= 0 (frame_groups), windows of `size` frames (2 .. 8) that start every size - overlap frames; the last window of
+    a run ends at the run's last frame and may be shorter, but never shorter than two frames nor contained in the window
+    before it.  No window crosses a group boundary; a run of one frame gives none.  Returns a list of lists of frames."""
+    g = np.asarray(frame_group).reshape(-1)
+    if not (2 <= size <= 8) or not (0 <= overlap < size):
+        raise ValueError(f"windows_of_groups: size must be 2 ... 8 and 0 <= overlap < size, got {size} and {overlap}")
+    out = []
+    a = 0
+    while a < g.size:
+        b = a + 1
+        while b < g.size and g[b] == g[a]:
+            b += 1
+        if g[a] >= 0:
+            s = a
+            while b - s >= 2:
+                e = min(s + size, b)
+                out.append(list(range(s, e)))
+                if e == b:
+                    break
+                s += size - overlap
+        a = b
+    return out
+
+
+def chain_windows(windows, R_win, T_win, code, R_abs, T_abs):
+    """Fuses the windows bundle_windows returned with code 0 (WINDOW_OK), in order, into one chain (pure host code).  Starts
+    from copies of the input chain R_abs [F, 3, 3], T_abs [F, 3] with no frame placed.  An OK window w with frames
+    f_0, f_1, .. and poses (R_win[w], T_win[w]) is aligned by a similarity onto the chain built so far: the chain's pose of
+    f_0 fixes rotation and translation; the scale is the chain's centre distance f_0 -- f_1 over the window's, where an
+    earlier window placed f_1 (and both distances are > 0), else 1.  The window then places its frames that no earlier
+    window placed (f_0 too, at the pose it already has).  Frames of windows that are not OK, and frames in no window, keep
+    the input chain's poses.  Returns (R [F, 3, 3], T [F, 3], centers [F, 3], placed bool[F])."""
+    R = np.array(R_abs, np.float64).reshape(-1, 3, 3); T = np.array(T_abs, np.float64).reshape(-1, 3)
+    placed = np.zeros(len(R), bool)
+    for w, frames in enumerate(windows):
+        if int(code[w]) != 0:
+            continue
+        Rw = np.asarray(R_win[w], np.float64).reshape(-1, 3, 3); Tw = np.asarray(T_win[w], np.float64).reshape(-1, 3)
+        f0 = int(frames[0])
+        # relative to the window's first frame: x_p = Q_p x_0 + s_p
+        Q = [Rw[p] @ Rw[0].T for p in range(len(frames))]
+        s = [Tw[p] - Q[p] @ Tw[0] for p in range(len(frames))]
+        scale = 1.0
+        f1 = int(frames[1])
+        if placed[f1] and placed[f0]:
+            have = float(np.linalg.norm(-R[f1].T @ T[f1] + R[f0].T @ T[f0])); own = float(np.linalg.norm(s[1]))
+            if have > 0 and own > 0:
+                scale = have / own
+        for p, f in enumerate(frames):
+            f = int(f)
+            if placed[f]:
+                continue
+            if p:
+                R[f] = Q[p] @ R[f0]
+                T[f] = Q[p] @ T[f0] + scale * s[p]
+            placed[f] = True
+    centers = -np.einsum("fji,fj->fi", R, T)
+    return R, T, centers, placed
+
+
 def registered_chain_inputs(R_rel, t_rel, status, ratio, code, R_link, t_link, link_pose_code):
     """chain_trajectory's five inputs with pair i + 1 taken from link pose i (_capi.Engine.link_poses over the links
     (i, i + 1, 1)) where link_pose_code[i] is 0 (LINKPOSE_OK): R_link[i], t_link[i] / |t_link[i]| (zero when the link pose

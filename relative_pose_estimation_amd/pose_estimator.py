@@ -406,7 +406,28 @@ class PoseEstimator:
         cam = {'cameras': self._camera} if self._camera is not None else {'K': self.K}
         return self._last_engine.triangulate_tracks(tracks, R_abs, T_abs, frame_group=frame_group, **cam, **gates)
 
-    def estimate_trajectory(self, frames, min_shared=8, register=False, bundle=False, tracks=False, points=False):
+    def last_window_bundles(self, R_abs, T_abs, points=None, tracks=None, size=8, overlap=2, **kw):
+        """Bundle adjustment of sliding windows over the tracks of the last sequence under the absolute poses R_abs
+        [F, 3, 3], T_abs [F, 3] (not in the reference; _capi.Engine.bundle_windows, whose dict it returns with 'windows', the
+        list of frame lists, added).  points: a dict of last_track_points over the same poses (its 'points' are the start
+        points, its 'obs_flag' selects the observations, its codes TRACKPT_OK the tracks, its 'frame_group' if present the
+        groups); None = last_track_points(R_abs, T_abs, tracks=tracks) with its defaults, all frames in one group.  The
+        windows are geometry.windows_of_groups(frame_group, size, overlap).  kw: max_points, min_obs, max_iters of
+        bundle_windows.  The camera is the estimator's, as in last_track_points."""
+        if tracks is None:
+            tracks = self.last_tracks()
+        if points is None:
+            points = self.last_track_points(R_abs, T_abs, tracks=tracks)
+        F = np.asarray(R_abs).reshape(-1, 9).shape[0]
+        group = points.get('frame_group')
+        windows = geometry.windows_of_groups(np.zeros(F, np.int32) if group is None else group, size, overlap)
+        cam = {'cameras': self._camera} if self._camera is not None else {'K': self.K}
+        out = self._last_engine.bundle_windows(tracks, points['points'], R_abs, T_abs, windows, obs_use=points['obs_flag'],
+                                               point_use=(np.asarray(points['code']) == _capi.TRACKPT_OK).astype(np.uint8), **cam, **kw)
+        out['windows'] = windows
+        return out
+
+    def estimate_trajectory(self, frames, min_shared=8, register=False, bundle=False, tracks=False, points=False, window=0):
         """estimate_sequence plus what relates its poses (not in the reference): the scale link of every two consecutive
         pairs and the chained trajectory (geometry.chain_trajectory).  Returns a dict: 'R', 't', 'inliers', 'status' of
         the F - 1 pairs; 'ratio_stats' [F-2, 3], 'n_shared' [F-2], 'link_code' [F-2] of the links; 'R_abs' [F, 3, 3],
@@ -425,7 +446,10 @@ class PoseEstimator:
         points=True implies tracks and adds 'points': the dict of last_track_points (its defaults) over those tracks under
         the best chain built, plus 'chain', the key of that chain's rotations ('R_abs_ba' with bundle, else 'R_abs_reg'
         with register, else 'R_abs'), and the 'T_abs' [F, 3] and 'frame_group' [F] (geometry.frame_groups of that chain)
-        it was run with.  Points of different groups are on unrelated scales."""
+        it was run with.  Points of different groups are on unrelated scales.
+        window=W (2 .. 8) implies points and adds 'window': the dict of last_window_bundles over those points and that chain
+        with windows of W frames (overlap min(2, W - 1)), and the chain the OK windows fuse into
+        (geometry.chain_windows): 'R_abs_win' [F, 3, 3], 'T_abs_win' [F, 3], 'centers_win' [F, 3]."""
         if self._camera is not None:
             raise ValueError("estimate_trajectory: the camera path has no stream form; use estimate_pairs and last_scale_links")
         R, t, inl, st = self.estimate_sequence(frames)
@@ -453,12 +477,16 @@ class PoseEstimator:
             out.update({'R_bundle': ba[2], 't_bundle': ba[3], 'bundle_code': ba[7][:, 0], 'bundle_counts': ba[6],
                         'R_abs_ba': chain[0], 'centers_ba': chain[2]})
             best = ('R_abs_ba', chain[1], ba_in[2], chain[4])
-        if tracks or points:
+        if tracks or points or window:
             out['tracks'] = self._last_engine.build_tracks()
-        if points:
+        if points or window:
             group = geometry.frame_groups(best[2], best[3])
             out['points'] = self.last_track_points(out[best[0]], best[1], group, out['tracks'])
             out['points'].update({'chain': best[0], 'T_abs': best[1], 'frame_group': group})
+        if window:
+            win = self.last_window_bundles(out[best[0]], best[1], out['points'], out['tracks'], size=window, overlap=min(2, window - 1))
+            fused = geometry.chain_windows(win['windows'], win['R'], win['T'], win['code'], out[best[0]], best[1])
+            out.update({'window': win, 'R_abs_win': fused[0], 'T_abs_win': fused[1], 'centers_win': fused[2]})
         return out
 
     def estimate_sequence(self, frames):

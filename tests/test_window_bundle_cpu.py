@@ -1,0 +1,214 @@
+"""The float64 model of the window bundles (tests/window_bundle_model.py) checked on its own, without a GPU: its derivatives
+against finite differences, its Schur step against a dense solve, exact data, the accuracy table of the noisy cases (whose
+worst values are the constants the GPU bands come from), the two-frame cost against the track-point model, the tie cap of the
+case set, and the two host helpers geometry.windows_of_groups / chain_windows."""
+import math
+
+import numpy as np
+import pytest
+
+from relative_pose_estimation_amd import geometry
+from tests import link_pose_model as lp
+from tests import track_point_model as tpm
+from tests import window_bundle_cases as wc
+from tests import window_bundle_model as wm
+
+
+@pytest.fixture(scope="module")
+def models():
+    return {c['name']: (c, wm.model_case(c), wm.model_case(c, "reversed")) for c in wc.cases()}
+
+
+def _state(case, w=0):
+    """the scaled problem of window w of a case at its input state"""
+    xy, f = wm.observations(case['tracks'], case['cams'])
+    frames = case['windows'][w]
+    ptrack, pobs, _ = wm.window_points(case['tracks'], frames, case['obs_use'], case['point_use'], case['max_points'])
+    R = case['R_abs'][frames]; T = case['T_abs'][frames]
+    Q, s, n2, A = wm.gauge(R, T)
+    l = math.sqrt(n2[A])
+    P0 = case['points0'][ptrack]
+    X = np.stack([(R[0, r] @ P0.T + T[0, r]) / l for r in range(3)], 1)
+    seen = pobs >= 0
+    x = np.zeros(seen.shape + (2,)); fo = np.ones(seen.shape)
+    x[seen] = xy[pobs[seen]]; fo[seen] = f[pobs[seen]]
+    return wm.State(Q, s / l, X, seen, x, fo, A)
+
+
+def _residual_vector(st, Q, t, X):
+    out = []
+    for p in range(st.W):
+        e, _ = wm.view_rows(p, Q[p], t[p], X, st.x[:, p], st.f[:, p], jac=False)
+        out.append(np.where(st.seen[:, p, None], e, 0.0))
+    return np.stack(out, 1)                                              # (n, W, 2)
+
+
+@pytest.mark.parametrize("name", ["noisy_w3", "anchor_first", "mixed_views", "lens"])
+def test_derivatives_against_finite_differences(name):
+    st = _state({c['name']: c for c in wc.cases()}[name])
+    rows = wm.linearise(st)
+    h = 1e-6
+    r0 = _residual_vector(st, st.Q, st.t, st.X)
+    scale = max(np.abs(J).max() for _, J, _ in rows[1:])
+    for k in range(st.N):                                                # the camera parameters
+        d = np.zeros(st.N); d[k] = h
+        Qp, tp, _ = wm.apply_step(st, d, np.zeros_like(st.X))
+        d[k] = -h
+        Qm, tm_, _ = wm.apply_step(st, d, np.zeros_like(st.X))
+        num = (_residual_vector(st, Qp, tp, st.X) - _residual_vector(st, Qm, tm_, st.X)) / (2 * h)
+        p = next(q for q in range(1, st.W) if st.off[q] <= k < st.off[q] + st.np_[q])
+        ana = np.zeros_like(num)
+        ana[:, p] = np.where(st.seen[:, p, None], rows[p][1][:, :, k - st.off[p]], 0.0)
+        assert np.abs(num - ana).max() <= 1e-6 * scale, (name, k, np.abs(num - ana).max(), scale)
+    for i in range(3):                                                   # the points
+        dX = np.zeros_like(st.X); dX[:, i] = h
+        num = (_residual_vector(st, st.Q, st.t, st.X + dX) - _residual_vector(st, st.Q, st.t, st.X - dX)) / (2 * h)
+        ana = np.stack([np.where(st.seen[:, p, None], rows[p][2][:, :, i], 0.0) for p in range(st.W)], 1)
+        assert np.abs(num - ana).max() <= 1e-6 * np.abs(ana).max(), (name, i)
+    assert r0.shape == (len(st.X), st.W, 2)
+
+
+@pytest.mark.parametrize("name", ["noisy_w2", "noisy_w3", "noisy_w8", "mixed_views", "anchor_first"])
+@pytest.mark.parametrize("lam", [1e-3, 1.0])
+def test_schur_step_equals_the_dense_solve(name, lam):
+    st = _state({c['name']: c for c in wc.cases()}[name])
+    rows = wm.linearise(st)
+    d, dp = wm.schur_step(st, rows, lam, lp.SUMS["forward"])
+    dd, ddp = wm.dense_step(st, rows, lam)
+    assert len(d) == 6 * st.W - 7
+    assert np.abs(d - dd).max() <= 1e-7 * max(np.abs(dd).max(), 1e-12), (np.abs(d - dd).max(), np.abs(dd).max())
+    assert np.abs(dp - ddp).max() <= 1e-7 * max(np.abs(ddp).max(), 1e-12)
+
+
+def test_exact_data_stays_put(models):
+    """true poses and points, pixels rounded to f32: the start rms is that rounding, and whatever steps the loop accepts
+    leave poses and points where they were"""
+    for name in ("exact_w2", "exact_w3", "exact_w5", "exact_w8", "exact_lens"):
+        case, fw, _ = models[name]
+        r = fw[0]
+        assert r['code'] in (wm.WINDOW_OK, wm.WINDOW_REJECTED)
+        assert r['rms'][0] < 1e-4 and r['rms'][1] <= r['rms'][0], (name, r['rms'])
+        rot, cen = wm.pose_errors(r['R'], r['T'], case['R_true'], case['T_true'])
+        assert rot.max() < 1e-4 and cen.max() < 1e-5, (name, rot, cen)
+        assert np.abs(r['points'] - case['X_true'][r['point_track']]).max() < 1e-4, name
+
+
+def test_codes_and_counts_of_the_special_cases(models):
+    want = {"no_baseline": wm.WINDOW_NO_BASELINE, "too_few": wm.WINDOW_TOO_FEW, "too_few_min_obs": wm.WINDOW_TOO_FEW,
+            "rejected": wm.WINDOW_REJECTED}
+    for name, code in want.items():
+        case, fw, _ = models[name]
+        r = fw[0]
+        assert r['code'] == code and r['info'][1:3] == (0, 0), (name, r['info'])
+        assert np.array_equal(r['R'], case['R_abs'][case['windows'][0]]) and np.array_equal(r['points'], case['points0'][r['point_track']])
+    assert models["too_few"][1][0]['counts'] == (3, 20, 45, 0)
+    assert models["capped"][1][0]['counts'][1::2] == (64, 6) and models["capped"][1][0]['point_track'][-1] == 63
+    assert models["anchor_first"][1][0]['info'][3] == 1 and models["noisy_w5"][1][0]['info'][3] == 4
+    m = models["masked"][1][0]
+    assert not (m['point_track'] % 3 == 0).any() and m['counts'][2] < 4 * m['counts'][1]
+    assert not np.isfinite(models["rejected"][1][0]['rms'][0])
+    b = models["behind_view"][1][0]                                      # rejected at the end of the loop: a point behind its views
+    assert b['code'] == wm.WINDOW_REJECTED and b['info'][1] > 0 and b['info'][2] > 0 and b['rms'][0] == b['rms'][1], b['info']
+    assert np.array_equal(b['R'], models["behind_view"][0]['R_abs']) and np.array_equal(b['points'], models["behind_view"][0]['points0'][b['point_track']])
+
+
+def test_ties_stay_within_the_cap(models):
+    """a case whose forward and reversed models differ in a decision is skipped on the GPU: at most a quarter may"""
+    fwd = [r for _, f, _ in models.values() for r in f]; rev = [r for _, _, v in models.values() for r in v]
+    ties, d = wm.reduction_margin(fwd, rev)
+    print("windows %d ties %s forward / reversed %s" % (len(fwd), ties, d))
+    assert len(ties) * 4 <= len(fwd) and (d > 0).all()
+
+
+def _noisy(models):
+    return [n for n in models if n.startswith(("noisy_", "count_")) or n in ("mixed_views", "outside", "anchor_first", "overlapping",
+                                                                              "lens", "no_masks", "masked", "capped")]
+
+
+def test_accuracy_table(models):
+    """every noisy window lowers the rms, and the median rotation error (degrees) and the median centre error (in units of
+    the window's largest centre distance l) against the truth are below the input state's: per window wherever the window
+    has three frames or more and at least 30 points, and pooled over the non-first frames of all windows.  Two kinds of
+    window are held to the pooled bound only, because the data cannot promise more: a two-frame window (noisy_w2, the last
+    of overlapping) trades rotation against the direction of translation, and 60 points under 0.3 px at depth 4 .. 8 over a
+    baseline of 0.25 do not hold the 0.3 .. 0.5 degrees it starts from; count_6 and count_7 are the lane-stride shapes,
+    with 36 and 42 residuals for 29 and 32 unknowns.  The worst window medians after the bundle are the constants of
+    window_bundle_model."""
+    rin, rout, cin, cout, wr, wc_ = [], [], [], [], 0.0, 0.0
+    for name in _noisy(models):
+        case, fw, _ = models[name]
+        for w, r in enumerate(fw):
+            fr = case['windows'][w]
+            assert r['code'] == wm.WINDOW_OK and r['rms'][1] < r['rms'][0], (name, w, r['info'], r['rms'])
+            a, b = wm.pose_errors(case['R_abs'][fr], case['T_abs'][fr], case['R_true'][fr], case['T_true'][fr])
+            c, d = wm.pose_errors(r['R'], r['T'], case['R_true'][fr], case['T_true'][fr])
+            print("%-14s W %d points %3d rms %.3f -> %.3f px  rot median %.4f -> %.4f deg  centre median %.4f -> %.4f l" %
+                  (name, len(fr), r['counts'][1], r['rms'][0], r['rms'][1], np.median(a), np.median(c), np.median(b), np.median(d)))
+            if len(fr) >= 3 and r['counts'][1] >= 30:
+                assert np.median(c) < np.median(a) and np.median(d) < np.median(b), (name, w)
+            rin += list(a); rout += list(c); cin += list(b); cout += list(d)
+            wr = max(wr, float(np.median(c))); wc_ = max(wc_, float(np.median(d)))
+    print("pooled over %d frames: rot median %.4f -> %.4f deg, centre median %.4f -> %.4f l; worst window median after: rot %.5f deg, centre %.5f l"
+          % (len(rin), np.median(rin), np.median(rout), np.median(cin), np.median(cout), wr, wc_))
+    assert np.median(rout) < np.median(rin) and np.median(cout) < np.median(cin)
+    assert wr <= wm.WINDOW_ROT_WORST_DEG and wc_ <= wm.WINDOW_CENTRE_WORST
+    assert wr > 0.98 * wm.WINDOW_ROT_WORST_DEG and wc_ > 0.98 * wm.WINDOW_CENTRE_WORST     # the constants are the measured values
+
+
+def test_two_frame_cost_equals_the_track_point_errors(models):
+    """W = 2 at the input state: the cost is the sum of squares of track_point_model's obs_err over the used observations
+    (the same residual, f * (y / y2 - x), in another gauge: equal to rounding)"""
+    for name in ("noisy_w2", "exact_w2"):
+        case, fw, _ = models[name]
+        tp = tpm.triangulate_tracks(case['tracks'], case['R_abs'], case['T_abs'], case['cams'], threshold_px=wc.START_GATE_PX,
+                                    min_views=2, max_cos=1.0, max_iters=10)
+        if case['obs_use'] is None:
+            case = dict(case, points0=tp['points'], obs_use=tp['obs_flag'], point_use=(tp['code'] == tpm.OK).astype(np.uint8))
+        r = wm.model_case(case)[0]
+        sel = (case['obs_use'] == 1) & np.repeat(case['point_use'] != 0, np.diff(case['tracks']['track_start']))
+        want = float((tp['obs_err'][sel] ** 2).sum())
+        got = r['rms'][0] ** 2 * r['counts'][2]
+        assert r['counts'][2] == int(sel.sum())
+        assert abs(got - want) <= 1e-9 * want, (name, got, want)
+
+
+# ------------------------------------------------------------------ the host helpers
+def test_windows_of_groups():
+    g = np.array([0] * 20 + [-1] + [1] * 3 + [2] + [3] * 9)
+    w = geometry.windows_of_groups(g, size=8, overlap=2)
+    assert w[0] == list(range(8)) and w[1] == list(range(6, 14)) and w[2] == list(range(12, 20))
+    assert w[3] == [21, 22, 23] and w[4] == list(range(25, 33)) and w[5] == list(range(31, 34)) and len(w) == 6
+    for x in w:
+        assert 2 <= len(x) <= 8 and len(set(g[x])) == 1 and g[x[0]] >= 0                 # a group boundary is never crossed
+    assert geometry.windows_of_groups(np.zeros(6, int), size=4, overlap=2) == [[0, 1, 2, 3], [2, 3, 4, 5]]
+    assert geometry.windows_of_groups(np.zeros(5, int), size=4, overlap=2) == [[0, 1, 2, 3], [2, 3, 4]]
+    assert geometry.windows_of_groups(np.zeros(1, int)) == [] and geometry.windows_of_groups(np.full(5, -1)) == []
+    for bad in (dict(size=1), dict(size=9), dict(size=4, overlap=4)):
+        with pytest.raises(ValueError):
+            geometry.windows_of_groups(g, **bad)
+
+
+def test_chain_windows():
+    rng = np.random.default_rng(7)
+    R, T, c = wc.tc.walk(rng, 12)
+    windows = geometry.windows_of_groups(np.zeros(12, int), size=5, overlap=2)
+    # exact windows, each in a gauge and on a scale of its own, reproduce the input chain
+    Rw, Tw = [], []
+    for k, w in enumerate(windows):
+        G = wc.tc._rodrigues(rng.uniform(-0.3, 0.3, 3)); s = 1.0 + 0.5 * k; g = rng.standard_normal(3)
+        Rw.append(np.stack([R[f] @ G.T for f in w])); Tw.append(np.stack([s * (T[f] - R[f] @ G.T @ g) for f in w]))
+    Rf, Tf, cf, placed = geometry.chain_windows(windows, Rw, Tw, np.zeros(len(windows), int), R, T)
+    assert placed.all()
+    assert np.abs(Rf - R).max() <= 1e-12 and np.abs(Tf - T).max() <= 1e-12 and np.abs(cf - c).max() <= 1e-12
+    # a window that is not OK changes nothing, whatever it holds
+    junk = [np.zeros_like(x) for x in Rw], [np.full_like(x, 9.0) for x in Tw]
+    Rn, Tn, _, placed = geometry.chain_windows(windows, junk[0], junk[1], np.full(len(windows), 3), R, T)
+    assert np.array_equal(Rn, R) and np.array_equal(Tn, T) and not placed.any()
+    # one window of the four not OK: the window behind it finds neither of its first two frames placed, starts from the
+    # input chain's pose of its first frame and keeps its own scale -- the input chain's, as rpe_bundle_windows returns it
+    code = np.zeros(len(windows), int); code[1] = 2
+    Ru = [np.stack([R[f] for f in w]) for w in windows]; Tu = [np.stack([T[f] for f in w]) for w in windows]
+    Ru[1] = junk[0][1]; Tu[1] = junk[1][1]
+    Rm, Tm, _, placed = geometry.chain_windows(windows, Ru, Tu, code, R, T)
+    assert np.abs(Rm - R).max() <= 1e-12 and np.abs(Tm - T).max() <= 1e-12
+    assert placed.tolist() == [f not in (5,) for f in range(12)]

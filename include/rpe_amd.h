@@ -196,8 +196,8 @@ int rpe_enqueue_stream_device(rpe_handle *h, const uint8_t *d_frames, int F, con
 /* Extraction separated from pairing (NOT in the reference, whose only shapes are the pair and the consecutive-frame
  * sequence): per-frame features -- keypoint points, count, descriptors, the L2 matcher's norm words, RPE_OVF_* flags --
  * stay resident in HBM slots across calls, and a pair list names two slots per pair.  Windowed matching (frame i
- * against i+1 .. i+k), loop-closure candidates and online use (put the new frame, pair it with the ring of the last k)
- * extract every frame once.  The store is created on demand and survives every other call on the handle (batch,
+ * against i+1 .. i+k), loop-closure candidates (rpe_frames_similar below proposes them) and online use (put the new
+ * frame, pair it with the ring of the last k) extract every frame once.  The store is created on demand and survives every other call on the handle (batch,
  * stream, stage API, refinement); rpe_destroy frees it.  Bytes per slot:
  * (nfeatures + 64) * (descriptor bytes + 8 + N) + 8, descriptor bytes = 32 (ORB) or 128 (SIFT), N = 8 for NORM_L2 handles
  * of either match mode (the crossCheck matcher and rpe_guided_matches_l2 read the norm words) and 0 for Hamming handles,
@@ -872,6 +872,53 @@ int rpe_bundle_windows(rpe_handle *h, int n_tracks, const int32_t *track_start, 
                        int n_win, const int32_t *win_start, const int32_t *win_frame, int max_points, int min_obs, int max_iters,
                        double *R_out, double *T_out, double *points, int32_t *point_track, int32_t *counts, int32_t *info,
                        double *rms);
+
+/* --------------------------------------------------------- pair proposals */
+/* Which frames see the same place (NOT in the reference): an exact similarity score between stored frames and a top-k
+ * candidate selection, both on the GPU, so that a pair list for rpe_enqueue_pairs (loop closures, windows of far-apart
+ * frames) can come from the library itself.  Hamming handles only (ORB + RPE_NORM_HAMMING).
+ *
+ * The score.  The SAMPLE of a frame with n keypoints under a stride step >= 1 is its descriptors 0, step, 2 step, ...:
+ * M = ceil(n / step) of them, sample index k being keypoint k * step.  score(a, b) is the number of mutual nearest
+ * neighbours between the two samples whose Hamming distance is <= max_distance (0 .. 256); "mutual nearest" is cv2's
+ * crossCheck rule, both argmins taking the lowest index among equal distances (the rule of rpe_match_hamming, without its
+ * max_matches cut).  The mutual set of (a, b) is the transpose of that of (b, a), so the score is symmetric; an empty
+ * sample gives 0; a self pair is computed like any other.  Exact integers: scores[r * nt + c] = score(frame of query
+ * position r, frame of target position c).
+ *
+ * The candidates.  Column c is eligible for row r iff the two slots differ, |q_time[r] - t_time[c]| > exclude when
+ * exclude >= 0, and the score is >= min_score.  A row's candidates are its eligible columns by score descending, then
+ * column position ascending, the first k of them: cand[r * k + m] is a column POSITION (an index into t_slots), and
+ * cand_score[r * k + m] its score; both are -1 for m >= n_cand[r], the row's count.  A NULL time array means
+ * time = slot number (stage form: frame index), which suits callers that put frame f into slot f; callers with a ring
+ * pass frame numbers.
+ *
+ * rpe_frames_similar: over the frame store.  q_slots[nq] / t_slots[nt] are host arrays of filled slots; repeats are
+ * allowed within a list, the lists may be as long as the store and may be the same list (identical lists are computed
+ * as one triangle and mirrored).  scores may be NULL, and so may cand / cand_score / n_cand (all three or none; k = 0
+ * with the three NULL is allowed); at least one output must be asked for.  The call reads the store, writes buffers of
+ * its own (created on first use, grown to the largest call) and synchronises the handle's stream; the last run and
+ * everything fetched from it afterwards are untouched.
+ * rpe_similarity_hamming: the stage form, on the caller's own descriptors h_desc [F][cap][32] (cap =
+ * rpe_keypoint_capacity()) with counts n[F], F <= 2*max_batch; q_idx / t_idx index the frames 0 .. F-1 and take the
+ * place of the slots.  Like every stage call it overwrites the extraction workspace: the calls behind the last run are
+ * refused until the next batch, stream or pair list.
+ * RPE_ERR_INVALID, with nothing launched and the handle still usable: a NULL handle or list; no store; a slot outside
+ * the store or an empty slot (stage form: F < 1, a count outside 0 .. cap, an index outside 0 .. F-1); step < 1;
+ * max_distance outside 0 .. 256; k outside 0 .. RPE_SIMILAR_MAX_K; nq < 1 or nt < 1; no output, or only part of the
+ * candidate trio; an L2 or SIFT handle.  RPE_ERR_CAPACITY: nq * nt > 2^31 - 1, F > 2*max_batch.  RPE_ERR_HIP: the
+ * device cannot hold the call's buffers (nq * nt scores and the tables); the buffer set is then empty and the next call
+ * tries again. */
+#define RPE_SIMILAR_MAX_K 32
+int rpe_frames_similar(rpe_handle *h, int nq, const int32_t *q_slots, int nt, const int32_t *t_slots,
+                       int step, int max_distance, const int32_t *q_time, const int32_t *t_time,
+                       int exclude, int min_score, int k,
+                       int32_t *scores, int32_t *cand, int32_t *cand_score, int32_t *n_cand);
+int rpe_similarity_hamming(rpe_handle *h, const uint8_t *h_desc, const int32_t *n, int F,
+                           int nq, const int32_t *q_idx, int nt, const int32_t *t_idx,
+                           int step, int max_distance, const int32_t *q_time, const int32_t *t_time,
+                           int exclude, int min_score, int k,
+                           int32_t *scores, int32_t *cand, int32_t *cand_score, int32_t *n_cand);
 
 /* ---------------------------------------------------------- stage entry */
 /* replaces extractor.detectAndCompute(image, None) (pose_estimator.py:108)

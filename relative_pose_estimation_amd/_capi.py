@@ -40,6 +40,7 @@ TRACKPT_NAMES = ("OK", "TOO_FEW", "DEGENERATE", "BEHIND", "OUTLIERS", "LOW_PARAL
 WINDOW_OK, WINDOW_NO_BASELINE, WINDOW_TOO_FEW, WINDOW_REJECTED = 0, 1, 2, 3
 WINDOW_NAMES = ("OK", "NO_BASELINE", "TOO_FEW", "REJECTED")
 WINDOW_MAX_VIEWS, WINDOW_MAX_POINTS = 8, 16384   # RPE_WINDOW_MAX_VIEWS, RPE_WINDOW_MAX_POINTS
+SIMILAR_MAX_K = 32                # RPE_SIMILAR_MAX_K: the most candidates per query row of the similarity calls
 UNDISTORT_ITERS = 5               # RPE_UNDISTORT_ITERS: fixed-point rounds of the camera path's undistortion
 
 # The binding, one entry per function of include/rpe_amd.h: "<return>:<one letter per parameter>".  Parameters: p pointer or
@@ -68,6 +69,7 @@ _SIGNATURES = {
     "rpe_last_run_pairs": "i:p", "rpe_build_tracks": "i:ppiipppppp", "rpe_tracks_from_matches": "i:piippppppppipppppp",
     "rpe_triangulate_tracks": "i:pipppipppppdidipppppp",
     "rpe_bundle_windows": "i:pippppppippppippiiippppppp",
+    "rpe_frames_similar": "i:pipipiippiiipppp", "rpe_similarity_hamming": "i:pppiipipiippiiipppp",
     "rpe_guided_matches": "i:pippdipppppp",
     "rpe_guided_matches_l2": "i:pippddpppppp",
     "rpe_pair_homographies": "i:piidppppp", "rpe_find_homography": "i:ppppipidppppp",
@@ -777,6 +779,43 @@ class Engine:
         s1, s2 = _slot_pairs(slot1, slot2)
         K = _f64(K)
         return self._estimate(self.lib.rpe_estimate_pairs, s1.size, _p(s1), _p(s2), s1.size, _p(K))
+
+    # ---- pair proposals (rpe_frames_similar / rpe_similarity_hamming; not in the reference)
+    def _similar(self, call, q, t, step, max_distance, q_time, t_time, exclude, min_score, k, want_scores):
+        """the shared tail of the two forms: {"scores" [nq, nt] or None, "cand" / "cand_score" [nq, k] and "n_cand" [nq], or
+        None without candidates (k = 0)}.  cand holds POSITIONS in the target list, -1 past a row's count."""
+        q, t = _i32(q), _i32(t)
+        q_time = None if q_time is None else _i32(q_time)
+        t_time = None if t_time is None else _i32(t_time)
+        assert (q_time is None or q_time.size == q.size) and (t_time is None or t_time.size == t.size)
+        k = int(k)
+        scores = np.zeros((q.size, t.size), np.int32) if want_scores else None
+        cand = cscore = ncand = None
+        if k > 0:
+            cand = np.full((q.size, k), -1, np.int32); cscore = np.full((q.size, k), -1, np.int32); ncand = np.zeros(q.size, np.int32)
+        self._chk(call(q.size, _p(q), t.size, _p(t), int(step), int(max_distance), _opt(q_time), _opt(t_time), int(exclude), int(min_score), k,
+                       _opt(scores), _opt(cand), _opt(cscore), _opt(ncand)))
+        return {"scores": scores, "cand": cand, "cand_score": cscore, "n_cand": ncand}
+
+    def frames_similar(self, q_slots, t_slots, step=1, max_distance=48, q_time=None, t_time=None, exclude=-1, min_score=0, k=0,
+                       want_scores=True):
+        """Similarity of stored frames: scores[r, c] = crossCheck matches within max_distance between every step-th
+        descriptor of slot q_slots[r] and of slot t_slots[c]; with k > 0 the k best eligible columns per row (slots
+        differ, |q_time - t_time| > exclude when exclude >= 0, score >= min_score; times default to the slot numbers)."""
+        return self._similar(lambda *a: self.lib.rpe_frames_similar(self.h, *a), q_slots, t_slots, step, max_distance, q_time, t_time,
+                             exclude, min_score, k, want_scores)
+
+    def similarity_hamming(self, desc, n, q_idx, t_idx, step=1, max_distance=48, q_time=None, t_time=None, exclude=-1, min_score=0, k=0,
+                           want_scores=True):
+        """The stage form: desc is a list of F uint8 [n_f, 32] descriptor arrays (or one [F, kcap, 32] array with counts n);
+        q_idx / t_idx index the frames."""
+        if n is None:
+            n = np.array([len(d) for d in desc], np.int32)
+            desc = self._pack_features(desc, n, (32,), np.uint8)
+        desc = np.ascontiguousarray(desc, np.uint8); n = _i32(n)
+        assert desc.shape == (n.size, self.kcap, 32), desc.shape
+        return self._similar(lambda *a: self.lib.rpe_similarity_hamming(self.h, _p(desc), _p(n), n.size, *a), q_idx, t_idx, step, max_distance,
+                             q_time, t_time, exclude, min_score, k, want_scores)
 
     # ---- camera models (rpe_*_cameras; not in the reference): one Camera, or one per frame
     def frames_set_cameras(self, slots, cameras):

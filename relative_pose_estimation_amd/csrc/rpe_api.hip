@@ -444,7 +444,7 @@ static int alloc_workspace(rpe_handle *h)
 // its ceiling (the kernel files' lists) on the current device, before any launch or capture exists
 static int raise_lds_limits(rpe_handle *h)
 {
-    for (auto list : {rpe_orb_lds_ceilings, rpe_match_lds_ceilings, rpe_geom_lds_ceilings, rpe_link_lds_ceilings})
+    for (auto list : {rpe_orb_lds_ceilings, rpe_match_lds_ceilings, rpe_similar_lds_ceilings, rpe_geom_lds_ceilings, rpe_link_lds_ceilings})
         for (const RpeLdsCeiling &c : list()) {
             const hipError_t e = hipFuncSetAttribute(c.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)c.bytes);
             if (e != hipSuccess) {
@@ -1865,6 +1865,109 @@ extern "C" int rpe_estimate_pairs(rpe_handle *h, const int32_t *slot1, const int
     int rc = rpe_enqueue_pairs(h, slot1, slot2, P, K);
     if (rc) return rc;
     return rpe_fetch_results(h, P, R, t, inliers, n_matches, status);
+}
+
+// ---- pair proposals (rpe_frames_similar / rpe_similarity_hamming; NOT in the reference): similarity scores between frames
+// and a top-k candidate selection (the definitions: include/rpe_amd.h; the kernels: similar_kernels.hip).
+// The checks the two forms share, host side, in front of any device call.  n_frames: the store's slots or the stage call's
+// frames; filled: the store's flags, or null
+static int similar_check(rpe_handle *h, const char *who, int n_frames, const uint8_t *filled, int nq, const int32_t *q, int nt, const int32_t *t,
+                         int step, int max_distance, int k, const int32_t *scores, const int32_t *cand, const int32_t *cand_score, const int32_t *n_cand)
+{
+    if (!q || !t || nq < 1 || nt < 1) return rpe_invalid(h, who, "a null list, or nq < 1 or nt < 1");
+    if (step < 1) return rpe_invalid(h, who, "step must be >= 1");
+    if (max_distance < 0 || max_distance > 256) return rpe_invalid(h, who, "max_distance must be 0 ... 256");
+    if (k < 0 || k > RPE_SIMILAR_MAX_K) return rpe_invalid(h, who, "k must be 0 ... RPE_SIMILAR_MAX_K");
+    const int trio = (cand != nullptr) + (cand_score != nullptr) + (n_cand != nullptr);
+    if (trio != 0 && trio != 3) return rpe_invalid(h, who, "cand, cand_score and n_cand must all be given or all be NULL");
+    if (!scores && !trio) return rpe_invalid(h, who, "no output asked for");
+    for (int s = 0; s < 2; ++s) {
+        const int32_t *l = s ? t : q;
+        for (int i = 0, n = s ? nt : nq; i < n; ++i) {
+            if (l[i] < 0 || l[i] >= n_frames) return rpe_invalid(h, who, filled ? "slot outside the store" : "frame index outside 0 ... F-1");
+            if (filled && !filled[(size_t)l[i]]) return rpe_invalid(h, who, "a list names an empty slot");
+        }
+    }
+    if ((long long)nq * nt > 0x7FFFFFFFLL) { h->err = std::string(who) + ": nq * nt exceeds 2^31 - 1"; return RPE_ERR_CAPACITY; }
+    return RPE_OK;
+}
+
+// Behind the checks and hipSetDevice: the buffer set, the tables, the launches over the features (desc, count), the fetch
+static int similar_run(rpe_handle *h, const uint8_t *desc, const int *count, int nq, const int32_t *q, int nt, const int32_t *t,
+                       int step, int max_distance, const int32_t *q_time, const int32_t *t_time, int exclude, int min_score, int k,
+                       int32_t *scores, int32_t *cand, int32_t *cand_score, int32_t *n_cand)
+{
+    const size_t NQ = (size_t)nq, NT = (size_t)nt, ck = cand ? NQ * (size_t)k : 0;
+    if (int rc = rpe_bufset_fit(h, h->set_similar,
+                                {buf_piece(h->d_sim_q, NQ), buf_piece(h->d_sim_t, NT), buf_piece(h->d_sim_qtime, q_time ? NQ : 0),
+                                 buf_piece(h->d_sim_ttime, t_time ? NT : 0), buf_piece(h->d_sim_scores, NQ * NT), buf_piece(h->d_sim_cand, ck),
+                                 buf_piece(h->d_sim_cscore, ck), buf_piece(h->d_sim_ncand, cand ? NQ : 0)})) return rc;
+    HIPCHK(h, hipMemcpyAsync(h->d_sim_q, q, sizeof(int) * NQ, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_sim_t, t, sizeof(int) * NT, hipMemcpyHostToDevice, h->stream));
+    if (q_time) HIPCHK(h, hipMemcpyAsync(h->d_sim_qtime, q_time, sizeof(int) * NQ, hipMemcpyHostToDevice, h->stream));
+    if (t_time) HIPCHK(h, hipMemcpyAsync(h->d_sim_ttime, t_time, sizeof(int) * NT, hipMemcpyHostToDevice, h->stream));
+    RpeSimilarJob job;
+    job.desc = desc; job.count = count;
+    job.nq = nq; job.nt = nt; job.q = h->d_sim_q; job.t = h->d_sim_t;
+    job.step = std::min(step, std::max(h->lay.kcap, 1));       // a stride of the capacity or more samples descriptor 0 alone
+    job.max_distance = max_distance;
+    job.same = nq == nt && memcmp(q, t, sizeof(int32_t) * NQ) == 0;
+    job.q_time = q_time ? h->d_sim_qtime : h->d_sim_q; job.t_time = t_time ? h->d_sim_ttime : h->d_sim_t;      // no times: the slot numbers
+    job.exclude = exclude; job.min_score = min_score; job.k = k;
+    job.scores = h->d_sim_scores;
+    // k == 0 selects nothing: every row's count is 0, written below without a launch
+    const bool select = cand && k > 0;
+    job.cand = select ? h->d_sim_cand : nullptr; job.cand_score = h->d_sim_cscore; job.n_cand = h->d_sim_ncand;
+    rpe_launch_similar(h, job);
+    HIPCHK(h, hipGetLastError());
+    if (cand && !select) memset(n_cand, 0, sizeof(int32_t) * NQ);
+    // the wait also covers the uploads: the lists and times have left the caller's arrays
+    return fetch(h, {{scores, h->d_sim_scores, sizeof(int) * NQ * NT}, {select ? cand : nullptr, h->d_sim_cand, sizeof(int) * ck},
+                     {select ? cand_score : nullptr, h->d_sim_cscore, sizeof(int) * ck}, {select ? n_cand : nullptr, h->d_sim_ncand, sizeof(int) * NQ}});
+}
+
+static int similar_hamming_only(rpe_handle *h, const char *who)
+{
+    if (h->cfg.feature_method == RPE_FEATURE_SIFT || h->cfg.norm_type != RPE_NORM_HAMMING)
+        return rpe_invalid(h, who, "Hamming handles only (ORB with RPE_NORM_HAMMING)");
+    return RPE_OK;
+}
+
+extern "C" int rpe_frames_similar(rpe_handle *h, int nq, const int32_t *q_slots, int nt, const int32_t *t_slots,
+                                  int step, int max_distance, const int32_t *q_time, const int32_t *t_time,
+                                  int exclude, int min_score, int k,
+                                  int32_t *scores, int32_t *cand, int32_t *cand_score, int32_t *n_cand)
+{
+    const char *who = "rpe_frames_similar";
+    if (!h) return rpe_invalid(h, who);
+    if (int rc = similar_hamming_only(h, who)) return rc;
+    if (h->fs.cap == 0) return rpe_invalid(h, who, "no frame store (rpe_frames_reserve)");
+    if (int rc = similar_check(h, who, h->fs.cap, h->fs.filled.data(), nq, q_slots, nt, t_slots, step, max_distance, k, scores, cand, cand_score, n_cand)) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    // reads the store, writes set_similar: the last run and what is fetched from it stay as they are
+    return similar_run(h, h->fs.d_desc, h->fs.d_count, nq, q_slots, nt, t_slots, step, max_distance, q_time, t_time, exclude, min_score, k,
+                       scores, cand, cand_score, n_cand);
+}
+
+extern "C" int rpe_similarity_hamming(rpe_handle *h, const uint8_t *h_desc, const int32_t *n, int F,
+                                      int nq, const int32_t *q_idx, int nt, const int32_t *t_idx,
+                                      int step, int max_distance, const int32_t *q_time, const int32_t *t_time,
+                                      int exclude, int min_score, int k,
+                                      int32_t *scores, int32_t *cand, int32_t *cand_score, int32_t *n_cand)
+{
+    const char *who = "rpe_similarity_hamming";
+    if (!h || !h_desc || !n || F < 1) return rpe_invalid(h, who);
+    if (int rc = similar_hamming_only(h, who)) return rc;
+    if (F > h->n_img_cap) { h->err = std::string(who) + ": more than 2*max_batch frames"; return RPE_ERR_CAPACITY; }
+    if (int rc = check_desc_counts(h, n, F)) return rc;
+    if (int rc = similar_check(h, who, F, nullptr, nq, q_idx, nt, t_idx, step, max_distance, k, scores, cand, cand_score, n_cand)) return rc;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    last_run_end(h);                            // overwrites the workspace's features
+    // frame f on the workspace slot f
+    HIPCHK(h, hipMemcpyAsync(h->d_desc, h_desc, (size_t)h->lay.kcap * 32 * F, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h, hipMemcpyAsync(h->d_kp_count, n, sizeof(int) * (size_t)F, hipMemcpyHostToDevice, h->stream));
+    return similar_run(h, h->d_desc, h->d_kp_count, nq, q_idx, nt, t_idx, step, max_distance, q_time, t_time, exclude, min_score, k,
+                       scores, cand, cand_score, n_cand);
 }
 
 // ---------------------------------------------------------------- stage API

@@ -47,6 +47,7 @@ std::vector<RpeLdsCeiling> rpe_orb_lds_ceilings();     // orb_kernels.hip
 std::vector<RpeLdsCeiling> rpe_match_lds_ceilings();   // match_kernels.hip
 std::vector<RpeLdsCeiling> rpe_geom_lds_ceilings();    // geom_kernels.hip
 std::vector<RpeLdsCeiling> rpe_link_lds_ceilings();    // link_kernels.hip
+std::vector<RpeLdsCeiling> rpe_similar_lds_ceilings(); // similar_kernels.hip
 // one pair's results, section by section of the result block (d_resblk): R, t, inliers, status, n_matches
 #define RPE_RESULT_SECTIONS 5
 static const size_t kRpeResultElem[RPE_RESULT_SECTIONS] = {9 * sizeof(double), 3 * sizeof(double), sizeof(int), sizeof(int), sizeof(int)};
@@ -388,6 +389,21 @@ struct RpeWindowJob {
     const int *win_start, *win_frame;
 };
 
+// One job of the similarity kernels (similar_kernels.hip): the features (the frame store's, or the workspace's of the stage
+// form), the two device tables of slots, the times (the tables themselves when the caller gave none) and where the results go.
+// same: the two lists are identical, the triangle is computed and mirrored.  cand == null: no selection
+struct RpeSimilarJob {
+    const uint8_t *desc;
+    const int *count;
+    int nq, nt;
+    const int *q, *t;
+    int step, max_distance;
+    bool same;
+    const int *q_time, *t_time;
+    int exclude, min_score, k;
+    int *scores, *cand, *cand_score, *n_cand;
+};
+
 // One rpe_scale_links link on the device: pairs a and b of the last run, side bit 0 / 1 = the shared frame is image 2 of a / of b
 struct RpeLink { int a, b, side, pad; };
 // What the link kernels (link_kernels.hip) read of the last run, by value (rpe_link_src fills it from the handle): the link
@@ -552,6 +568,11 @@ struct rpe_handle {
     uint8_t *d_wb_puse = nullptr, *d_wb_ouse = nullptr;
     rpe_camera *d_wb_cams = nullptr;
     rpe_camera wb_cam_k{}; RpeBufSet set_windows;
+    // rpe_frames_similar / rpe_similarity_hamming only (set_similar, fitted to every call's lists): the two slot tables (not
+    // d_pairtab, which holds 2*max_batch entries: a list here may be as long as the store), the times the caller gave, the
+    // nq * nt scores, and per query row its k candidates, their scores and their count
+    int *d_sim_q = nullptr, *d_sim_t = nullptr, *d_sim_qtime = nullptr, *d_sim_ttime = nullptr;
+    int *d_sim_scores = nullptr, *d_sim_cand = nullptr, *d_sim_cscore = nullptr, *d_sim_ncand = nullptr; RpeBufSet set_similar;
     // results
     double *d_R = nullptr, *d_t = nullptr, *d_E = nullptr;
     int *d_inliers = nullptr, *d_status = nullptr;
@@ -717,6 +738,7 @@ bool rpe_bundles_in_lds(const rpe_handle *h);
 void rpe_launch_tracks(rpe_handle *h, const RpeTrackJob &job);
 void rpe_launch_track_points(rpe_handle *h, const RpeTrackPointJob &job);
 void rpe_launch_windows(rpe_handle *h, const RpeWindowJob &job);
+void rpe_launch_similar(rpe_handle *h, const RpeSimilarJob &job);
 void rpe_launch_normalise(rpe_handle *h, const RpeRun &r);
 void rpe_launch_homography(rpe_handle *h, const RpeRun &r, int iters, double threshold_px, bool from_batch);
 void rpe_launch_undistort(rpe_handle *h, const float2 *d_pts, int n, const rpe_camera *d_cam, double2 *d_out);

@@ -265,3 +265,27 @@ def tracks_of_frames(tracks, frames):
         obs[track_of_obs[hit], c] = hit
     keep = (obs >= 0).all(axis=1) if frames.size else np.zeros(n_tracks, bool)
     return np.nonzero(keep)[0].astype(np.int32), obs[keep].astype(np.int32)
+
+
+def pairs_of_candidates(q_ids, t_ids, cand, cand_score):
+    """The pair list of a candidate table (_capi.Engine.frames_similar / similarity_hamming with k > 0), a pure function:
+    (pairs i32[P, 2], scores i32[P]).  q_ids[r] / t_ids[c] are the frames (store slots) of query row r and target column c;
+    cand[r, m] is a column position or -1, cand_score[r, m] its score.  Every candidate (r, c) becomes the unordered pair
+    (min, max) of its two frames; a pair proposed from both sides, or by repeated rows, appears once, with its largest
+    score (the score is symmetric, so the sides agree).  Order: score descending, then the pair ascending."""
+    q_ids = np.asarray(q_ids, np.int64).reshape(-1); t_ids = np.asarray(t_ids, np.int64).reshape(-1)
+    cand = np.asarray(cand, np.int64); cand_score = np.asarray(cand_score, np.int64)
+    if cand.ndim != 2 or cand.shape != cand_score.shape or cand.shape[0] != q_ids.size:
+        raise ValueError(f"pairs_of_candidates: cand and cand_score must both be [len(q_ids), k], got {cand.shape}, {cand_score.shape}")
+    if (cand >= t_ids.size).any():
+        raise ValueError("pairs_of_candidates: a candidate is no position of t_ids")
+    r, m = np.nonzero(cand >= 0)
+    a, b = q_ids[r], t_ids[cand[r, m]]
+    if (a == b).any():
+        raise ValueError("pairs_of_candidates: a candidate pairs a frame with itself")
+    lo, hi, sc = np.minimum(a, b), np.maximum(a, b), cand_score[r, m]
+    o = np.lexsort((hi, lo, -sc))                      # score descending, then the pair: the first of equal pairs has its largest score
+    lo, hi, sc = lo[o], hi[o], sc[o]
+    _, first = np.unique(np.stack([lo, hi], 1), axis=0, return_index=True) if lo.size else (None, np.zeros(0, np.int64))
+    first = np.sort(first)
+    return np.stack([lo[first], hi[first]], 1).astype(np.int32).reshape(-1, 2), sc[first].astype(np.int32)

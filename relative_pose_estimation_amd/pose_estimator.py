@@ -112,6 +112,51 @@ class FrameStore:
         eng = self._engine((self._eng.height, self._eng.width))
         return self._est._run_pair_list(eng, pairs, cameras=bool(named.all()))
 
+    def _filled(self):
+        if self._eng is None:
+            raise _capi.RpeError("FrameStore: nothing has been put yet")
+        cnt, _ = self.info(np.arange(self.capacity))
+        return np.nonzero(cnt >= 0)[0].astype(np.int32)
+
+    def _slot_list(self, slots, what):
+        if slots is None:
+            return self._filled()
+        a = np.asarray(slots)
+        if a.ndim != 1 or a.size == 0 or a.dtype.kind not in "iu" or (a < 0).any() or (a >= self.capacity).any():
+            raise ValueError(f"{what}: expected integers inside [0, {self.capacity})")
+        return np.ascontiguousarray(a, np.int32)
+
+    def similar(self, queries=None, targets=None, step=1, max_distance=48, times=None, exclude=-1, min_score=0, k=0, want_scores=True):
+        """Similarity of stored frames (ORB + Hamming estimators): a dict with "queries" / "targets" (the slot lists; None
+        = all filled slots), "scores" [nq, nt] -- crossCheck matches within max_distance between every step-th descriptor
+        of the two frames -- and, with k > 0, "cand" [nq, k] (positions in targets, -1 past "n_cand"), "cand_score",
+        "n_cand": the k best targets of a query among those in another slot, more than `exclude` apart in time when
+        exclude >= 0, and scoring at least min_score.  times: one time per store slot (frame numbers of a ring); None =
+        the slot numbers.  want_scores=False leaves "scores" None (the matrix stays on the GPU)."""
+        q, t = self._slot_list(queries, "queries"), self._slot_list(targets, "targets")
+        eng = self._engine((self._eng.height, self._eng.width))
+        q_time = t_time = None
+        if times is not None:
+            times = np.asarray(times)
+            if times.shape != (self.capacity,) or times.dtype.kind not in "iu":
+                raise ValueError(f"times: expected {self.capacity} integers, one per slot")
+            q_time, t_time = times[q], times[t]
+        out = eng.frames_similar(q, t, step=step, max_distance=max_distance, q_time=q_time, t_time=t_time, exclude=exclude,
+                                 min_score=min_score, k=k, want_scores=want_scores)
+        out["queries"], out["targets"] = q, t
+        return out
+
+    def propose_pairs(self, k=3, exclude=-1, min_score=0, step=1, max_distance=48, queries=None, targets=None, times=None):
+        """(pairs i32[P, 2], scores i32[P]): the slot pairs worth estimating -- every query's k most similar targets (see
+        similar), each unordered pair once as (min, max), score descending then pair ascending: a pair list for
+        estimate.  max_distance = 48 is what the synthetic loop scene supports, not a value tuned on real
+        imagery."""
+        if int(k) < 1:
+            raise ValueError("propose_pairs: k must be >= 1")
+        s = self.similar(queries, targets, step=step, max_distance=max_distance, times=times, exclude=exclude, min_score=min_score, k=k,
+                         want_scores=False)
+        return geometry.pairs_of_candidates(s["queries"], s["targets"], s["cand"], s["cand_score"])
+
     def info(self, slots):
         """(keypoint counts, OVF_* flags) of the slots; count -1 = never filled"""
         slots = np.asarray(slots)

@@ -205,6 +205,22 @@ def _slot_pairs(slot1, slot2):
     return s1, s2
 
 
+def _scene_args(who, tracks, R_abs, T_abs, K, cameras):
+    """The track scene of triangulate_tracks and bundle_windows as the library reads it: track_start i32[n + 1],
+    obs_frame i32[n_obs], obs_xy f32[n_obs, 2], R f64[F, 9], T f64[F, 3], then F, n, K f64[9] or None and the F camera
+    records or None"""
+    ts, of = _i32(tracks['track_start']), _i32(tracks['obs_frame'])
+    xy = np.ascontiguousarray(tracks['obs_xy'], np.float32).reshape(-1, 2)
+    R = np.ascontiguousarray(np.asarray(R_abs, np.float64).reshape(-1, 9))
+    T = np.ascontiguousarray(np.asarray(T_abs, np.float64).reshape(-1, 3))
+    F, n = R.shape[0], ts.size - 1
+    if n < 0 or T.shape[0] != F or of.size != xy.shape[0] or int(ts[-1]) != of.size:
+        raise ValueError(f"{who}: track_start must end at the number of observations, and R_abs and T_abs hold one pose per frame")
+    if (K is None) == (cameras is None):
+        raise ValueError(f"{who}: exactly one of K and cameras must be given")
+    return ts, of, xy, R, T, F, n, None if K is None else _f64(K).reshape(9), None if cameras is None else camera_records(cameras, F)
+
+
 def lsd_detect(gray, capacity=8192):
     """cv2.createLineSegmentDetector(LSD_REFINE_STD).detect(gray)[0] restated: (N, 4) float64 segments
     (pose_estimator.py:160-175).  Host code inside librpe_amd.so; needs no GPU handle."""
@@ -557,20 +573,10 @@ class Engine:
         i32[n], 'rms' f64[n] (px, over the inliers), 'min_cos' f64[n] (smallest cosine between the rays of two inlier
         views; above max_cos the code is TRACKPT_LOW_PARALLAX), 'obs_flag' u8[n_obs] (0 not used, 1 inlier, 2 outlier),
         'obs_err' f64[n_obs] (px; -1 behind the camera).  The last run stays fetchable."""
-        ts, of = _i32(tracks['track_start']), _i32(tracks['obs_frame'])
-        xy = np.ascontiguousarray(tracks['obs_xy'], np.float32).reshape(-1, 2)
-        R = np.ascontiguousarray(np.asarray(R_abs, np.float64).reshape(-1, 9))
-        T = np.ascontiguousarray(np.asarray(T_abs, np.float64).reshape(-1, 3))
-        F, n = R.shape[0], ts.size - 1
-        if n < 0 or T.shape[0] != F or of.size != xy.shape[0] or (n >= 0 and ts.size and int(ts[-1]) != of.size):
-            raise ValueError("triangulate_tracks: track_start must end at the number of observations, and R_abs and T_abs hold one pose per frame")
-        if (K is None) == (cameras is None):
-            raise ValueError("triangulate_tracks: exactly one of K and cameras must be given")
+        ts, of, xy, R, T, F, n, k, cams = _scene_args("triangulate_tracks", tracks, R_abs, T_abs, K, cameras)
         g = None if frame_group is None else _i32(frame_group)
         if g is not None and g.size != F:
             raise ValueError(f"triangulate_tracks: frame_group must have one entry per frame ({F}), got {g.size}")
-        k = None if K is None else _f64(K).reshape(9)
-        cams = None if cameras is None else camera_records(cameras, F)
         pts = np.zeros((n, 3)); info = np.zeros((n, 4), np.int32); rms = np.zeros(n); mc = np.zeros(n)
         flag = np.zeros(of.size, np.uint8); err = np.zeros(of.size)
         self._chk(self.lib.rpe_triangulate_tracks(self.h, n, _p(ts), _p(of), _p(xy), F, _p(R), _p(T), _opt(g), _opt(k), _opt(cams),
@@ -592,16 +598,10 @@ class Engine:
         of i32[n_w]; 'code' (WINDOW_*), 'views', 'n_points', 'n_obs', 'dropped', 'iterations', 'accepted', 'anchor'
         i32[n_win]; 'rms' f64[n_win, 2] (px, before and after).  For every code but WINDOW_OK the inputs come back.  The
         last run stays fetchable."""
-        ts, of = _i32(tracks['track_start']), _i32(tracks['obs_frame'])
-        xy = np.ascontiguousarray(tracks['obs_xy'], np.float32).reshape(-1, 2)
-        R = np.ascontiguousarray(np.asarray(R_abs, np.float64).reshape(-1, 9))
-        T = np.ascontiguousarray(np.asarray(T_abs, np.float64).reshape(-1, 3))
+        ts, of, xy, R, T, F, n, k, cams = _scene_args("bundle_windows", tracks, R_abs, T_abs, K, cameras)
         p0 = np.ascontiguousarray(np.asarray(points, np.float64).reshape(-1, 3))
-        F, n = R.shape[0], ts.size - 1
-        if n < 0 or T.shape[0] != F or of.size != xy.shape[0] or int(ts[-1]) != of.size or p0.shape[0] != n:
-            raise ValueError("bundle_windows: track_start must end at the number of observations, points hold one row per track, and R_abs and T_abs one pose per frame")
-        if (K is None) == (cameras is None):
-            raise ValueError("bundle_windows: exactly one of K and cameras must be given")
+        if p0.shape[0] != n:
+            raise ValueError("bundle_windows: points hold one row per track")
         ou = None if obs_use is None else np.ascontiguousarray(obs_use, np.uint8).reshape(-1)
         pu = None if point_use is None else np.ascontiguousarray(point_use, np.uint8).reshape(-1)
         if (ou is not None and ou.size != of.size) or (pu is not None and pu.size != n):
@@ -611,8 +611,6 @@ class Engine:
         wstart = np.zeros(nw + 1, np.int32)
         wstart[1:] = np.cumsum([w.size for w in wl])
         wframe = _i32(np.concatenate(wl)) if nw else np.zeros(0, np.int32)
-        k = None if K is None else _f64(K).reshape(9)
-        cams = None if cameras is None else camera_records(cameras, F)
         mp, nwf = int(max_points), int(wstart[-1])
         slots = nw * max(mp, 0) if mp <= WINDOW_MAX_POINTS else 0
         Ro = np.zeros((nwf, 3, 3)); To = np.zeros((nwf, 3)); pts = np.zeros((slots, 3)); ptk = np.zeros(slots, np.int32)

@@ -56,13 +56,31 @@ static int check_match_counts(rpe_handle *h, const int32_t *m, int B)
 }
 
 // ---- the fetch: a device-to-host copy on the handle's stream for every piece the caller wants (dst != NULL), one wait
-struct Fetch { void *dst; const void *src; size_t bytes; };
-static int fetch(rpe_handle *h, std::initializer_list<Fetch> pieces)
+struct Copy { void *dst; const void *src; size_t bytes; };
+static int fetch(rpe_handle *h, std::initializer_list<Copy> pieces)
 {
-    for (const Fetch &f : pieces)
+    for (const Copy &f : pieces)
         if (f.dst) HIPCHK(h, hipMemcpyAsync(f.dst, f.src, f.bytes, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return RPE_OK;
+}
+
+// ---- the upload: a host-to-device copy on the handle's stream for every piece the caller gave (src != NULL) that has bytes; no wait
+static int upload(rpe_handle *h, std::initializer_list<Copy> pieces)
+{
+    for (const Copy &u : pieces)
+        if (u.src && u.bytes > 0) HIPCHK(h, hipMemcpyAsync(u.dst, u.src, u.bytes, hipMemcpyHostToDevice, h->stream));
+    return RPE_OK;
+}
+// Both sides of the B pairs of a stage call, pair p on the workspace slots (p, B + p): the keypoint counts, the 32-byte descriptors
+static int upload_counts(rpe_handle *h, const int32_t *n1, const int32_t *n2, int B)
+{
+    return upload(h, {{h->d_kp_count, n1, sizeof(int) * B}, {h->d_kp_count + B, n2, sizeof(int) * B}});
+}
+static int upload_descriptors(rpe_handle *h, const uint8_t *h_desc1, const uint8_t *h_desc2, int B)
+{
+    const size_t side = (size_t)h->lay.kcap * 32 * B;
+    return upload(h, {{h->d_desc, h_desc1, side}, {h->d_desc + side, h_desc2, side}});
 }
 
 // ---- the buffer set of a first-use feature, fitted to one call (the rule: rpe_internal.h)
@@ -712,7 +730,7 @@ static int set_K(rpe_handle *h, const double K[9])
     if (h->K_valid && memcmp(h->K_last, K, sizeof(double) * 9) == 0) return RPE_OK;      // same camera as the last batch: already resident
     memcpy(h->K_last, K, sizeof(double) * 9);
     h->K_valid = false;
-    HIPCHK(h, hipMemcpyAsync(h->d_K, h->K_last, sizeof(double) * 9, hipMemcpyHostToDevice, h->stream));
+    if (int rc = upload(h, {{h->d_K, h->K_last, sizeof(double) * 9}})) return rc;
     h->K_valid = true;
     return RPE_OK;
 }
@@ -896,8 +914,8 @@ extern "C" int rpe_estimate_stream(rpe_handle *h, const uint8_t *h_frames, int F
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const size_t img = (size_t)h->cfg.width * h->cfg.height;
     // d_stage1 holds max_batch + 1 frames: every legal stream fits the persistent staging buffer
-    HIPCHK(h, hipMemcpyAsync(h->d_stage1, h_frames, img * F, hipMemcpyHostToDevice, h->stream));
-    int rc = rpe_enqueue_stream_device(h, h->d_stage1, F, K);
+    int rc = upload(h, {{h->d_stage1, h_frames, img * F}});
+    if (!rc) rc = rpe_enqueue_stream_device(h, h->d_stage1, F, K);
     if (rc) return rc;
     return rpe_fetch_results(h, F - 1, R, t, inliers, n_matches, status);
 }
@@ -1028,9 +1046,7 @@ static int stage_images(rpe_handle *h, const uint8_t *h_imgs, int n, int &na, in
 {
     const size_t img = (size_t)h->cfg.width * h->cfg.height;
     na = n < h->cfg.max_batch ? n : h->cfg.max_batch; nb = n - na;
-    HIPCHK(h, hipMemcpyAsync(h->d_stage1, h_imgs, img * na, hipMemcpyHostToDevice, h->stream));
-    if (nb) HIPCHK(h, hipMemcpyAsync(h->d_stage2, h_imgs + img * na, img * nb, hipMemcpyHostToDevice, h->stream));
-    return RPE_OK;
+    return upload(h, {{h->d_stage1, h_imgs, img * na}, {h->d_stage2, h_imgs + img * na, img * nb}});
 }
 
 extern "C" int rpe_estimate_batch(rpe_handle *h, const uint8_t *h_imgs1, const uint8_t *h_imgs2, int B, const double K[9],
@@ -1045,8 +1061,7 @@ extern "C" int rpe_estimate_batch(rpe_handle *h, const uint8_t *h_imgs1, const u
     // (1024 VGA pairs: 629 MB = 12 ms of copy in front of 16 ms of kernels when done in one piece).
     const int nchunks = batch_is_chunked(h, B) ? 4 : 1;    // 2/3/4/6/8 chunks measured: 23.1/22.4/22.1/24.1/26.7 ms
     if (nchunks == 1) {
-        HIPCHK(h, hipMemcpyAsync(h->d_stage1, h_imgs1, img * B, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->d_stage2, h_imgs2, img * B, hipMemcpyHostToDevice, h->stream));
+        if (int rc = upload(h, {{h->d_stage1, h_imgs1, img * B}, {h->d_stage2, h_imgs2, img * B}})) return rc;
         return rpe_estimate_batch_device(h, h->d_stage1, h->d_stage2, B, K, R, t, inliers, n_matches, status);
     }
     if (!h->copy_stream) {
@@ -1055,7 +1070,7 @@ extern "C" int rpe_estimate_batch(rpe_handle *h, const uint8_t *h_imgs1, const u
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));                 // the staging buffers are free again
     const int per = (B + nchunks - 1) / nchunks;
-    auto upload = [&](int c) -> int {
+    auto upload_chunk = [&](int c) -> int {
         const int off = c * per, n = B - off < per ? B - off : per;
         if (n <= 0) return RPE_OK;
         HIPCHK(h, hipMemcpyAsync(h->d_stage1 + (size_t)off * img, h_imgs1 + (size_t)off * img, img * n, hipMemcpyHostToDevice, h->copy_stream));
@@ -1072,7 +1087,7 @@ extern "C" int rpe_estimate_batch(rpe_handle *h, const uint8_t *h_imgs1, const u
     const ResultBlock rb(h);
     DM_ONCE(h, h->d_resall, rb.bytes);
     DM_ONCE(h, h->d_ovfall, MB * 2);
-    int rc = upload(0);
+    int rc = upload_chunk(0);
     if (rc) return rc;
     for (int c = 0; c < nchunks; ++c) {
         const int off = c * per, n = B - off < per ? B - off : per;
@@ -1084,7 +1099,7 @@ extern "C" int rpe_estimate_batch(rpe_handle *h, const uint8_t *h_imgs1, const u
         // the chunk's capacity flags (image slots p and n + p of this launch), before the next chunk overwrites them
         HIPCHK(h, hipMemcpyAsync(h->d_ovfall + off, h->d_ovf, sizeof(unsigned) * (size_t)n, hipMemcpyDeviceToDevice, h->stream));
         HIPCHK(h, hipMemcpyAsync(h->d_ovfall + MB + off, h->d_ovf + n, sizeof(unsigned) * (size_t)n, hipMemcpyDeviceToDevice, h->stream));
-        if (c + 1 < nchunks && (rc = upload(c + 1)) != RPE_OK) return rc;
+        if (c + 1 < nchunks && (rc = upload_chunk(c + 1)) != RPE_OK) return rc;
     }
     std::vector<unsigned> ov(2 * MB);
     HIPCHK(h, hipMemcpyAsync(h->h_resblk, h->d_resall, rb.bytes, hipMemcpyDeviceToHost, h->stream));
@@ -1168,8 +1183,7 @@ static int links_begin(rpe_handle *h, const char *who, int L, const int32_t *pai
     HIPCHK(h, hipSetDevice(h->cfg.device));
     DM_ONCE(h, h->d_links, (size_t)rpe_link_capacity(h));
     if ((rc = last_run_structure(h, l.pairs, false)) != RPE_OK) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_links, tbl.data(), sizeof(RpeLink) * (size_t)L, hipMemcpyHostToDevice, h->stream));
-    return RPE_OK;
+    return upload(h, {{h->d_links, tbl.data(), sizeof(RpeLink) * (size_t)L}});
 }
 
 static int scale_links_alloc(rpe_handle *h)
@@ -1259,8 +1273,7 @@ extern "C" int rpe_link_bundles(rpe_handle *h, int L, const int32_t *pair_a, con
     int rc = links_begin(h, "rpe_link_bundles", L, pair_a, pair_b, side, min_shared);
     if (rc != RPE_OK || L == 0) return rc;
     if ((rc = bundle_alloc(h)) != RPE_OK) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_ba_Rin, R0, sizeof(double) * 9 * n, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_ba_tin, t0, sizeof(double) * 3 * n, hipMemcpyHostToDevice, h->stream));
+    if ((rc = upload(h, {{h->d_ba_Rin, R0, sizeof(double) * 9 * n}, {h->d_ba_tin, t0, sizeof(double) * 3 * n}})) != RPE_OK) return rc;
     rpe_launch_bundle_gather(h, h->last.run, L, threshold_px);
     rpe_launch_bundle(h, L, min_shared, max_iters, true);
     HIPCHK(h, hipGetLastError());
@@ -1301,13 +1314,10 @@ extern "C" int rpe_bundle_three_view(rpe_handle *h, int B, const int32_t *n, con
     }
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if ((rc = bundle_alloc(h)) != RPE_OK) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_ba_views, vw.data(), vw.size(), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_ba_obs, ob.data(), sizeof(double) * ob.size(), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_ba_points, x0.data(), sizeof(double) * x0.size(), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_ba_pose0, pose.data(), sizeof(double) * pose.size(), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_ba_focal, foc.data(), sizeof(double) * foc.size(), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_ba_pre, pre.data(), sizeof(int) * nb, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_ba_n, n, sizeof(int) * nb, hipMemcpyHostToDevice, h->stream));
+    if ((rc = upload(h, {{h->d_ba_views, vw.data(), vw.size()}, {h->d_ba_obs, ob.data(), sizeof(double) * ob.size()},
+                         {h->d_ba_points, x0.data(), sizeof(double) * x0.size()}, {h->d_ba_pose0, pose.data(), sizeof(double) * pose.size()},
+                         {h->d_ba_focal, foc.data(), sizeof(double) * foc.size()}, {h->d_ba_pre, pre.data(), sizeof(int) * nb},
+                         {h->d_ba_n, n, sizeof(int) * nb}})) != RPE_OK) return rc;
     rpe_launch_bundle(h, B, 1, max_iters, false);
     HIPCHK(h, hipGetLastError());
     // the wait also covers the uploads: the staging vectors live until it returns
@@ -1343,13 +1353,12 @@ static int tracks_run(rpe_handle *h, RpeTrackJob job, int32_t *counts, int32_t *
                       float *obs_xy, int32_t *match_track)
 {
     const size_t P = (size_t)job.P;
-    HIPCHK(h, hipMemcpyAsync(h->d_tk_frames, h->tk_frame_tab.data(), sizeof(int2) * P, hipMemcpyHostToDevice, h->stream));
+    if (int rc = upload(h, {{h->d_tk_frames, h->tk_frame_tab.data(), sizeof(int2) * P}})) return rc;
     job.frames = h->d_tk_frames;
     rpe_launch_tracks(h, job);
     HIPCHK(h, hipGetLastError());
     int32_t c[6];
-    int rc = fetch(h, {{c, h->d_tk_counts, sizeof(c)}});
-    if (rc) return rc;
+    if (int rc = fetch(h, {{c, h->d_tk_counts, sizeof(c)}})) return rc;
     if (counts) memcpy(counts, c, sizeof(c));
     const size_t nt = (size_t)c[0], no = (size_t)c[1];
     return fetch(h, {{track_start, h->d_tk_tstart, sizeof(int) * (nt + 1)}, {obs_frame, h->d_tk_oframe, sizeof(int) * no},
@@ -1384,7 +1393,7 @@ extern "C" int rpe_build_tracks(rpe_handle *h, const uint8_t *use_pair, int edge
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if ((rc = tracks_alloc(h, n_frames)) != RPE_OK) return rc;
     if (edge_rule != RPE_TRACK_EDGES_ALL && (rc = last_run_structure(h, P, false)) != RPE_OK) return rc;
-    if (use_pair) HIPCHK(h, hipMemcpyAsync(h->d_tk_use, use_pair, (size_t)P, hipMemcpyHostToDevice, h->stream));
+    if ((rc = upload(h, {{h->d_tk_use, use_pair, (size_t)P}})) != RPE_OK) return rc;
     const RpeTrackJob job = {P, n_frames, edge_rule, min_len, nullptr, h->d_m_n, h->d_m_q, h->d_m_t, use_pair ? h->d_tk_use : nullptr, nullptr,
                              h->d_status, h->d_mask, h->d_pose_mask, h->d_pts1, h->d_pts2};
     // the first wait also covers the uploads: use_pair has left the caller's array
@@ -1424,14 +1433,8 @@ extern "C" int rpe_tracks_from_matches(rpe_handle *h, int P, int n_frames, const
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if ((rc = tracks_alloc(h, n_frames)) != RPE_OK) return rc;
     const size_t n = (size_t)P * mm;
-    HIPCHK(h, hipMemcpyAsync(h->d_tk_m, m, sizeof(int) * (size_t)P, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_tk_q, qidx, sizeof(int) * n, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_tk_t, tidx, sizeof(int) * n, hipMemcpyHostToDevice, h->stream));
-    if (edge) HIPCHK(h, hipMemcpyAsync(h->d_tk_edge, edge, n, hipMemcpyHostToDevice, h->stream));
-    if (pts1) {
-        HIPCHK(h, hipMemcpyAsync(h->d_tk_pts1, pts1, sizeof(float2) * n, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->d_tk_pts2, pts2, sizeof(float2) * n, hipMemcpyHostToDevice, h->stream));
-    }
+    if ((rc = upload(h, {{h->d_tk_m, m, sizeof(int) * (size_t)P}, {h->d_tk_q, qidx, sizeof(int) * n}, {h->d_tk_t, tidx, sizeof(int) * n},
+                         {h->d_tk_edge, edge, n}, {h->d_tk_pts1, pts1, sizeof(float2) * n}, {h->d_tk_pts2, pts2, sizeof(float2) * n}})) != RPE_OK) return rc;
     const RpeTrackJob job = {P, n_frames, RPE_TRACK_EDGES_ALL, min_len, nullptr, h->d_tk_m, h->d_tk_q, h->d_tk_t, nullptr, edge ? h->d_tk_edge : nullptr,
                              nullptr, nullptr, nullptr, pts1 ? h->d_tk_pts1 : nullptr, pts1 ? h->d_tk_pts2 : nullptr};
     // the first wait also covers the uploads: the lists have left the caller's arrays
@@ -1506,10 +1509,7 @@ static int guided_run(rpe_handle *h, const RpeRun &r, const double *R, const dou
                       int32_t *qidx, int32_t *tidx, void *dist, float *pts1, float *pts2, int32_t *n_matches)
 {
     const size_t B = (size_t)r.pairs, n = B * h->cfg.max_matches;
-    if (R) {
-        HIPCHK(h, hipMemcpyAsync(h->d_gm_R, R, sizeof(double) * 9 * B, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(h, hipMemcpyAsync(h->d_gm_tr, t, sizeof(double) * 3 * B, hipMemcpyHostToDevice, h->stream));
-    }
+    if (int rc = upload(h, {{h->d_gm_R, R, sizeof(double) * 9 * B}, {h->d_gm_tr, t, sizeof(double) * 3 * B}})) return rc;
     const double *d_R = R ? h->d_gm_R : h->d_R, *d_t = R ? h->d_gm_tr : h->d_t;
     const int *d_status = R ? (const int *)nullptr : (const int *)h->d_status;
     if (h->cfg.norm_type == RPE_NORM_L2) rpe_launch_guided_l2(h, r, d_R, d_t, d_status, gate_px, max_distance);
@@ -1555,10 +1555,8 @@ static int guided_stage_run(rpe_handle *h, const float *h_pts1, const int32_t *n
                             int32_t *qidx, int32_t *tidx, void *dist, int32_t *n_matches)
 {
     const size_t kcap = (size_t)h->lay.kcap;
-    HIPCHK(h, hipMemcpyAsync(h->d_kp_pt, h_pts1, sizeof(float2) * kcap * B, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_kp_pt + kcap * B, h_pts2, sizeof(float2) * kcap * B, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_kp_count, n1, sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_kp_count + B, n2, sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
+    if (int rc = upload(h, {{h->d_kp_pt, h_pts1, sizeof(float2) * kcap * B}, {h->d_kp_pt + kcap * B, h_pts2, sizeof(float2) * kcap * B}})) return rc;
+    if (int rc = upload_counts(h, n1, n2, B)) return rc;
     return guided_run(h, rpe_run_batch(h, B), R, t, gate_px, max_distance, qidx, tidx, dist, nullptr, nullptr, n_matches);
 }
 
@@ -1571,15 +1569,13 @@ extern "C" int rpe_match_hamming_guided(rpe_handle *h, const uint8_t *h_desc1, c
     if (int rc = check_batch(h, B)) return rc;
     int rc = guided_check(h, "rpe_match_hamming_guided", RPE_NORM_HAMMING, B, R, t, gate_px, max_distance);
     if (rc) return rc;
-    const size_t kcap = (size_t)h->lay.kcap;
     if ((rc = check_desc_counts(h, n1, B)) != RPE_OK || (rc = check_desc_counts(h, n2, B)) != RPE_OK) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if ((rc = guided_alloc(h)) != RPE_OK) return rc;
     last_run_end(h);                            // overwrites the workspace's features
     if ((rc = set_K(h, K)) != RPE_OK) return rc;
     // pair p on the workspace slots (p, B + p), like every stage call
-    HIPCHK(h, hipMemcpyAsync(h->d_desc, h_desc1, kcap * 32 * B, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_desc + kcap * 32 * B, h_desc2, kcap * 32 * B, hipMemcpyHostToDevice, h->stream));
+    if ((rc = upload_descriptors(h, h_desc1, h_desc2, B)) != RPE_OK) return rc;
     return guided_stage_run(h, h_pts1, n1, h_pts2, n2, B, R, t, gate_px, max_distance, qidx, tidx, dist, n_matches);
 }
 
@@ -1598,7 +1594,7 @@ extern "C" int rpe_match_l2_guided(rpe_handle *h, const float *h_desc1, const fl
     if ((rc = guided_alloc(h)) != RPE_OK) return rc;
     last_run_end(h);                            // overwrites the workspace's features
     if ((rc = set_K(h, K)) != RPE_OK) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_desc, u.data(), u.size(), hipMemcpyHostToDevice, h->stream));
+    if ((rc = upload(h, {{h->d_desc, u.data(), u.size()}})) != RPE_OK) return rc;
     return guided_stage_run(h, h_pts1, n1, h_pts2, n2, B, R, t, gate_px, max_distance, qidx, tidx, dist, n_matches);   // waits: u is read by then
 }
 
@@ -1750,7 +1746,7 @@ static int upload_table(rpe_handle *h, const int32_t *a, const int32_t *b, int n
     int *dst = h->h_pairtab + (size_t)r * per;
     if (b) for (int i = 0; i < n; ++i) { dst[2 * i] = a[i]; dst[2 * i + 1] = b[i]; }
     else memcpy(dst, a, sizeof(int) * (size_t)n);
-    HIPCHK(h, hipMemcpyAsync(h->d_pairtab, dst, sizeof(int) * (size_t)(b ? 2 * n : n), hipMemcpyHostToDevice, h->stream));
+    if (int rc = upload(h, {{h->d_pairtab, dst, sizeof(int) * (size_t)(b ? 2 * n : n)}})) return rc;
     HIPCHK(h, hipEventRecord(h->ev_tab[r], h->stream));
     return RPE_OK;
 }
@@ -1902,10 +1898,8 @@ static int similar_run(rpe_handle *h, const uint8_t *desc, const int *count, int
                                 {buf_piece(h->d_sim_q, NQ), buf_piece(h->d_sim_t, NT), buf_piece(h->d_sim_qtime, q_time ? NQ : 0),
                                  buf_piece(h->d_sim_ttime, t_time ? NT : 0), buf_piece(h->d_sim_scores, NQ * NT), buf_piece(h->d_sim_cand, ck),
                                  buf_piece(h->d_sim_cscore, ck), buf_piece(h->d_sim_ncand, cand ? NQ : 0)})) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_sim_q, q, sizeof(int) * NQ, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_sim_t, t, sizeof(int) * NT, hipMemcpyHostToDevice, h->stream));
-    if (q_time) HIPCHK(h, hipMemcpyAsync(h->d_sim_qtime, q_time, sizeof(int) * NQ, hipMemcpyHostToDevice, h->stream));
-    if (t_time) HIPCHK(h, hipMemcpyAsync(h->d_sim_ttime, t_time, sizeof(int) * NT, hipMemcpyHostToDevice, h->stream));
+    if (int rc = upload(h, {{h->d_sim_q, q, sizeof(int) * NQ}, {h->d_sim_t, t, sizeof(int) * NT},
+                            {h->d_sim_qtime, q_time, sizeof(int) * NQ}, {h->d_sim_ttime, t_time, sizeof(int) * NT}})) return rc;
     RpeSimilarJob job;
     job.desc = desc; job.count = count;
     job.nq = nq; job.nt = nt; job.q = h->d_sim_q; job.t = h->d_sim_t;
@@ -1964,8 +1958,7 @@ extern "C" int rpe_similarity_hamming(rpe_handle *h, const uint8_t *h_desc, cons
     HIPCHK(h, hipSetDevice(h->cfg.device));
     last_run_end(h);                            // overwrites the workspace's features
     // frame f on the workspace slot f
-    HIPCHK(h, hipMemcpyAsync(h->d_desc, h_desc, (size_t)h->lay.kcap * 32 * F, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_kp_count, n, sizeof(int) * (size_t)F, hipMemcpyHostToDevice, h->stream));
+    if (int rc = upload(h, {{h->d_desc, h_desc, (size_t)h->lay.kcap * 32 * F}, {h->d_kp_count, n, sizeof(int) * (size_t)F}})) return rc;
     return similar_run(h, h->d_desc, h->d_kp_count, nq, q_idx, nt, t_idx, step, max_distance, q_time, t_time, exclude, min_score, k,
                        scores, cand, cand_score, n_cand);
 }
@@ -2099,8 +2092,7 @@ static int stage_match_run(rpe_handle *h, bool l2, const int32_t *n1, const int3
                            void *dist, int32_t *n_matches)
 {
     const size_t mm = h->cfg.max_matches;
-    HIPCHK(h, hipMemcpyAsync(h->d_kp_count, n1, sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_kp_count + B, n2, sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
+    if (int rc = upload_counts(h, n1, n2, B)) return rc;
     if (l2) rpe_launch_match_l2(h, rpe_run_batch(h, B));
     else rpe_launch_match(h, rpe_run_batch(h, B));
     HIPCHK(h, hipGetLastError());
@@ -2115,11 +2107,9 @@ extern "C" int rpe_match_hamming(rpe_handle *h, const uint8_t *h_desc1, const in
     if (int rc = check_batch(h, B)) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     last_run_end(h);                            // overwrites buffers rpe_fetch_structure reads
-    const size_t per = (size_t)h->lay.kcap * 32;
     if (int rc = check_desc_counts(h, n1, B)) return rc;
     if (int rc = check_desc_counts(h, n2, B)) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_desc, h_desc1, per * B, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_desc + per * B, h_desc2, per * B, hipMemcpyHostToDevice, h->stream));
+    if (int rc = upload_descriptors(h, h_desc1, h_desc2, B)) return rc;
     return stage_match_run(h, false, n1, n2, B, qidx, tidx, dist, n_matches);
 }
 
@@ -2127,10 +2117,7 @@ static int upload_points(rpe_handle *h, const float *p1, const float *p2, const 
 {
     const size_t mm = h->cfg.max_matches;
     if (int rc = check_match_counts(h, m, B)) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_pts1, p1, sizeof(float2) * mm * B, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_pts2, p2, sizeof(float2) * mm * B, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_m_n, m, sizeof(int) * B, hipMemcpyHostToDevice, h->stream));
-    return RPE_OK;
+    return upload(h, {{h->d_pts1, p1, sizeof(float2) * mm * B}, {h->d_pts2, p2, sizeof(float2) * mm * B}, {h->d_m_n, m, sizeof(int) * B}});
 }
 
 // ---------------------------------------------------------------- camera models
@@ -2161,8 +2148,7 @@ static int upload_batch_cameras(rpe_handle *h, const rpe_camera *cam1, const rpe
     HIPCHK(h, hipStreamSynchronize(h->stream));      // nothing in flight reads the records or their staging
     memcpy(h->h_batch_cams.data(), cam1, sizeof(rpe_camera) * (size_t)B);
     memcpy(h->h_batch_cams.data() + B, cam2, sizeof(rpe_camera) * (size_t)B);
-    HIPCHK(h, hipMemcpyAsync(h->d_batch_cams, h->h_batch_cams.data(), sizeof(rpe_camera) * 2 * (size_t)B, hipMemcpyHostToDevice, h->stream));
-    return RPE_OK;
+    return upload(h, {{h->d_batch_cams, h->h_batch_cams.data(), sizeof(rpe_camera) * 2 * (size_t)B}});
 }
 
 extern "C" int rpe_frames_set_cameras(rpe_handle *h, int n, const int32_t *slots, const rpe_camera *cams)
@@ -2179,7 +2165,7 @@ extern "C" int rpe_frames_set_cameras(rpe_handle *h, int n, const int32_t *slots
         const size_t s = (size_t)slots[i];
         h->fs.h_cam[s] = cams[i];
         h->fs.has_cam[s] = 1;
-        HIPCHK(h, hipMemcpyAsync(h->fs.d_cam + s, &h->fs.h_cam[s], sizeof(rpe_camera), hipMemcpyHostToDevice, h->stream));
+        if ((rc = upload(h, {{h->fs.d_cam + s, &h->fs.h_cam[s], sizeof(rpe_camera)}})) != RPE_OK) return rc;
     }
     HIPCHK(h, hipStreamSynchronize(h->stream));
     return RPE_OK;
@@ -2237,8 +2223,7 @@ extern "C" int rpe_estimate_batch_cameras(rpe_handle *h, const uint8_t *h_imgs1,
     if (!rc) rc = check_cameras(h, cam2, B, "rpe_estimate_batch_cameras");
     if (rc) return rc;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, hipMemcpyAsync(h->d_stage1, h_imgs1, img * B, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_stage2, h_imgs2, img * B, hipMemcpyHostToDevice, h->stream));
+    if ((rc = upload(h, {{h->d_stage1, h_imgs1, img * B}, {h->d_stage2, h_imgs2, img * B}})) != RPE_OK) return rc;
     return rpe_estimate_batch_cameras_device(h, h->d_stage1, h->d_stage2, B, cam1, cam2, R, t, inliers, n_matches, status);
 }
 
@@ -2265,17 +2250,30 @@ extern "C" int rpe_undistort_points(rpe_handle *h, const float *h_pts, int n, co
     return RPE_OK;
 }
 
-// ---------------------------------------------------------------- track points (rpe_triangulate_tracks)
-// the buffers of one call: per track, per observation, per frame
-static int track_points_alloc(rpe_handle *h, size_t n_tracks, size_t n_obs, size_t n_frames)
+// ---------------------------------------------------------------- the track scene (track_scene.h)
+// What rpe_triangulate_tracks and rpe_bundle_windows share.  Phase 1 of its check, in front of the empty-call return: the
+// scalars and the CSR shape, then the cameras (K as the one pinhole record it becomes)
+static int scene_check_shape(rpe_handle *h, const char *who, const RpeSceneArgs &a)
 {
-    return rpe_bufset_fit(h, h->set_track_points,
-                          {buf_piece(h->d_tp_tstart, n_tracks + 1), buf_piece(h->d_tp_points, 3 * n_tracks), buf_piece(h->d_tp_info, 4 * n_tracks),
-                           buf_piece(h->d_tp_rms, n_tracks), buf_piece(h->d_tp_mincos, n_tracks),
-                           buf_piece(h->d_tp_oframe, n_obs), buf_piece(h->d_tp_oxy, n_obs), buf_piece(h->d_tp_obs, 5 * n_obs), buf_piece(h->d_tp_oflag, n_obs), buf_piece(h->d_tp_oerr, n_obs),
-                           buf_piece(h->d_tp_R, 9 * n_frames), buf_piece(h->d_tp_T, 3 * n_frames), buf_piece(h->d_tp_group, n_frames), buf_piece(h->d_tp_cams, n_frames)});
+    if (const char *what = rpe_scene_check_shape(a)) return rpe_invalid(h, who, what);
+    if (a.K) h->scene.cam_k = rpe_camera{a.K[0], a.K[4], a.K[2], a.K[5], {0., 0., 0., 0., 0., 0., 0., 0.}};
+    return a.K ? check_cameras(h, &h->scene.cam_k, 1, who) : check_cameras(h, a.cams, a.n_frames, who);
+}
+// Behind phase 2 (rpe_scene_check_arrays: n_obs) and hipSetDevice: the scene buffers fitted to this call, the uploads, the device view
+static int scene_upload(rpe_handle *h, const RpeSceneArgs &a, size_t n_obs, RpeTrackScene *sc)
+{
+    rpe_handle::Scene &b = h->scene;
+    const size_t nt = (size_t)a.n_tracks, nf = (size_t)a.n_frames, nc = a.K ? 1 : nf;
+    if (int rc = rpe_bufset_fit(h, b.set, {buf_piece(b.d_tstart, nt + 1), buf_piece(b.d_oframe, n_obs), buf_piece(b.d_oxy, n_obs),
+                                           buf_piece(b.d_R, 9 * nf), buf_piece(b.d_T, 3 * nf), buf_piece(b.d_cams, nc)})) return rc;
+    if (int rc = upload(h, {{b.d_tstart, a.track_start, sizeof(int) * (nt + 1)}, {b.d_oframe, a.obs_frame, sizeof(int) * n_obs},
+                            {b.d_oxy, a.obs_xy, sizeof(float2) * n_obs}, {b.d_R, a.R_abs, sizeof(double) * 9 * nf},
+                            {b.d_T, a.T_abs, sizeof(double) * 3 * nf}, {b.d_cams, a.K ? &b.cam_k : a.cams, sizeof(rpe_camera) * nc}})) return rc;
+    *sc = {a.n_tracks, (int)n_obs, a.K ? 0 : 1, b.d_tstart, b.d_oframe, b.d_oxy, b.d_R, b.d_T, b.d_cams};
+    return RPE_OK;
 }
 
+// ---------------------------------------------------------------- track points (rpe_triangulate_tracks)
 // Every check on the host first, the buffers, the uploads, the two kernels, the fetch.  Neither the workspace nor the record
 // of the last run is touched.
 extern "C" int rpe_triangulate_tracks(rpe_handle *h, int n_tracks, const int32_t *track_start, const int32_t *obs_frame, const float *obs_xy,
@@ -2285,45 +2283,29 @@ extern "C" int rpe_triangulate_tracks(rpe_handle *h, int n_tracks, const int32_t
 {
     const char *who = "rpe_triangulate_tracks";
     if (!h) return rpe_invalid(h, who);
-    if (n_tracks < 0) return rpe_invalid(h, who, "n_tracks must be >= 0");
-    if (n_frames < 1) return rpe_invalid(h, who, "n_frames must be >= 1");
-    if ((K == nullptr) == (cams == nullptr)) return rpe_invalid(h, who, "exactly one of K and cams must be given");
+    const RpeSceneArgs scene = {n_tracks, track_start, obs_frame, obs_xy, n_frames, R_abs, T_abs, K, cams};
     if (int rc = check_positive(h, who, "threshold_px", threshold_px)) return rc;
     if (min_views < 2) return rpe_invalid(h, who, "min_views must be >= 2");
     if (!(max_cos > -1. && max_cos <= 1.)) return rpe_invalid(h, who, "max_cos must lie in (-1, 1]");
     if (max_iters < 0 || max_iters > 100) return rpe_invalid(h, who, "max_iters must be 0 ... 100");
-    if (K) h->tp_cam_k = rpe_camera{K[0], K[4], K[2], K[5], {0., 0., 0., 0., 0., 0., 0., 0.}};
-    if (int rc = K ? check_cameras(h, &h->tp_cam_k, 1, who) : check_cameras(h, cams, n_frames, who)) return rc;
-    if (track_start) {
-        if (track_start[0] != 0) return rpe_invalid(h, who, "track_start[0] must be 0");
-        for (int k = 0; k < n_tracks; ++k)
-            if (track_start[k + 1] < track_start[k]) return rpe_invalid(h, who, "track_start must not decrease");
-    }
+    if (int rc = scene_check_shape(h, who, scene)) return rc;
     if (n_tracks == 0) return RPE_OK;
-    if (!track_start || !R_abs || !T_abs) return rpe_invalid(h, who);
-    const size_t nt = (size_t)n_tracks, no = (size_t)track_start[n_tracks], nf = (size_t)n_frames;
-    if (no > 0 && (!obs_frame || !obs_xy)) return rpe_invalid(h, who);
-    for (size_t o = 0; o < no; ++o)
-        if (obs_frame[o] < 0 || obs_frame[o] >= n_frames) return rpe_invalid(h, who, "a frame index outside 0 ... n_frames - 1");
+    size_t no;
+    if (const char *what = rpe_scene_check_arrays(scene, &no)) return rpe_invalid(h, who, what);
+    const size_t nt = (size_t)n_tracks, nf = (size_t)n_frames;
     for (size_t f = 0; f < nf; ++f) {
         if (frame_group && frame_group[f] < 0) continue;
         if (!all_finite(R_abs + f * 9, 9) || !all_finite(T_abs + f * 3, 3)) return rpe_invalid(h, who, "a non-finite pose of a frame that has a group");
     }
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (int rc = track_points_alloc(h, nt, std::max(no, (size_t)1), nf)) return rc;
-    const hipStream_t s = h->stream;
-    HIPCHK(h, hipMemcpyAsync(h->d_tp_tstart, track_start, sizeof(int) * (nt + 1), hipMemcpyHostToDevice, s));
-    if (no > 0) {
-        HIPCHK(h, hipMemcpyAsync(h->d_tp_oframe, obs_frame, sizeof(int) * no, hipMemcpyHostToDevice, s));
-        HIPCHK(h, hipMemcpyAsync(h->d_tp_oxy, obs_xy, sizeof(float2) * no, hipMemcpyHostToDevice, s));
-    }
-    HIPCHK(h, hipMemcpyAsync(h->d_tp_R, R_abs, sizeof(double) * 9 * nf, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(h->d_tp_T, T_abs, sizeof(double) * 3 * nf, hipMemcpyHostToDevice, s));
-    if (frame_group) HIPCHK(h, hipMemcpyAsync(h->d_tp_group, frame_group, sizeof(int) * nf, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(h->d_tp_cams, K ? &h->tp_cam_k : cams, sizeof(rpe_camera) * (K ? 1 : nf), hipMemcpyHostToDevice, s));
-    const RpeTrackPointJob job = {n_tracks, (int)no, min_views, max_iters, K ? 0 : 1, threshold_px, max_cos,
-                                  h->d_tp_tstart, h->d_tp_oframe, frame_group ? h->d_tp_group : nullptr, h->d_tp_oxy,
-                                  h->d_tp_R, h->d_tp_T, h->d_tp_cams};
+    const size_t no1 = std::max(no, (size_t)1);
+    // the buffers of the call beside the scene: per track, per observation, per frame
+    if (int rc = rpe_bufset_fit(h, h->set_track_points,
+                                {buf_piece(h->d_tp_points, 3 * nt), buf_piece(h->d_tp_info, 4 * nt), buf_piece(h->d_tp_rms, nt), buf_piece(h->d_tp_mincos, nt),
+                                 buf_piece(h->d_tp_obs, 5 * no1), buf_piece(h->d_tp_oflag, no1), buf_piece(h->d_tp_oerr, no1), buf_piece(h->d_tp_group, nf)})) return rc;
+    RpeTrackPointJob job = {{}, min_views, max_iters, threshold_px, max_cos, frame_group ? h->d_tp_group : nullptr};
+    if (int rc = scene_upload(h, scene, no, &job.scene)) return rc;
+    if (int rc = upload(h, {{h->d_tp_group, frame_group, sizeof(int) * nf}})) return rc;
     rpe_launch_track_points(h, job);
     HIPCHK(h, hipGetLastError());
     // the wait also covers the uploads: the inputs have left the caller's arrays
@@ -2333,20 +2315,6 @@ extern "C" int rpe_triangulate_tracks(rpe_handle *h, int n_tracks, const int32_t
 }
 
 // ---------------------------------------------------------------- window bundles (rpe_bundle_windows)
-// the buffers of one call: per track, per observation, per frame, per window frame, per window, per window and point slot
-static int windows_alloc(rpe_handle *h, size_t n_tracks, size_t n_obs, size_t n_frames, size_t n_wf, size_t n_win, size_t slots)
-{
-    return rpe_bufset_fit(h, h->set_windows,
-                          {buf_piece(h->d_wb_tstart, n_tracks + 1), buf_piece(h->d_wb_points0, 3 * n_tracks), buf_piece(h->d_wb_puse, n_tracks),
-                           buf_piece(h->d_wb_oframe, n_obs), buf_piece(h->d_wb_oxy, n_obs), buf_piece(h->d_wb_obs, n_obs), buf_piece(h->d_wb_ouse, n_obs),
-                           buf_piece(h->d_wb_R, 9 * n_frames), buf_piece(h->d_wb_T, 3 * n_frames), buf_piece(h->d_wb_cams, n_frames),
-                           buf_piece(h->d_wb_wstart, n_win + 1), buf_piece(h->d_wb_wframe, n_wf), buf_piece(h->d_wb_Rout, 9 * n_wf), buf_piece(h->d_wb_Tout, 3 * n_wf),
-                           buf_piece(h->d_wb_counts, 4 * n_win), buf_piece(h->d_wb_info, 4 * n_win), buf_piece(h->d_wb_rms, 2 * n_win),
-                           buf_piece(h->d_wb_fcnt, RPE_WINDOW_MAX_VIEWS * n_win),
-                           buf_piece(h->d_wb_ptrack, slots), buf_piece(h->d_wb_pobs, RPE_WINDOW_MAX_VIEWS * slots),
-                           buf_piece(h->d_wb_state, 6 * slots), buf_piece(h->d_wb_points, 3 * slots)});
-}
-
 // Every check on the host first, the buffers, the uploads, the three kernels, the fetch.  Neither the workspace nor the record
 // of the last run is touched.
 extern "C" int rpe_bundle_windows(rpe_handle *h, int n_tracks, const int32_t *track_start, const int32_t *obs_frame, const float *obs_xy,
@@ -2358,28 +2326,18 @@ extern "C" int rpe_bundle_windows(rpe_handle *h, int n_tracks, const int32_t *tr
 {
     const char *who = "rpe_bundle_windows";
     if (!h) return rpe_invalid(h, who);
-    if (n_tracks < 0) return rpe_invalid(h, who, "n_tracks must be >= 0");
-    if (n_frames < 1) return rpe_invalid(h, who, "n_frames must be >= 1");
+    const RpeSceneArgs scene = {n_tracks, track_start, obs_frame, obs_xy, n_frames, R_abs, T_abs, K, cams};
     if (n_win < 0) return rpe_invalid(h, who, "n_win must be >= 0");
-    if ((K == nullptr) == (cams == nullptr)) return rpe_invalid(h, who, "exactly one of K and cams must be given");
     if (max_points < 1) return rpe_invalid(h, who, "max_points must be >= 1");
     if (max_points > RPE_WINDOW_MAX_POINTS) { h->err = std::string(who) + ": max_points exceeds RPE_WINDOW_MAX_POINTS"; return RPE_ERR_CAPACITY; }
     if (min_obs < 0) return rpe_invalid(h, who, "min_obs must be >= 0");
     if (max_iters < 1 || max_iters > 100) return rpe_invalid(h, who, "max_iters must be 1 ... 100");
-    if (K) h->wb_cam_k = rpe_camera{K[0], K[4], K[2], K[5], {0., 0., 0., 0., 0., 0., 0., 0.}};
-    if (int rc = K ? check_cameras(h, &h->wb_cam_k, 1, who) : check_cameras(h, cams, n_frames, who)) return rc;
-    if (track_start) {
-        if (track_start[0] != 0) return rpe_invalid(h, who, "track_start[0] must be 0");
-        for (int k = 0; k < n_tracks; ++k)
-            if (track_start[k + 1] < track_start[k]) return rpe_invalid(h, who, "track_start must not decrease");
-    }
+    if (int rc = scene_check_shape(h, who, scene)) return rc;
     if (n_win == 0) return RPE_OK;
-    if (!win_start || !win_frame || !R_abs || !T_abs) return rpe_invalid(h, who);
-    if (n_tracks > 0 && (!track_start || !points0)) return rpe_invalid(h, who);
-    const size_t nt = (size_t)n_tracks, no = n_tracks > 0 ? (size_t)track_start[n_tracks] : 0, nf = (size_t)n_frames, nw = (size_t)n_win;
-    if (no > 0 && (!obs_frame || !obs_xy)) return rpe_invalid(h, who);
-    for (size_t o = 0; o < no; ++o)
-        if (obs_frame[o] < 0 || obs_frame[o] >= n_frames) return rpe_invalid(h, who, "a frame index outside 0 ... n_frames - 1");
+    if (!win_start || !win_frame || (n_tracks > 0 && !points0)) return rpe_invalid(h, who);
+    size_t no;
+    if (const char *what = rpe_scene_check_arrays(scene, &no)) return rpe_invalid(h, who, what);
+    const size_t nt = (size_t)n_tracks, nw = (size_t)n_win;
     if (win_start[0] != 0) return rpe_invalid(h, who, "win_start[0] must be 0");
     for (int w = 0; w < n_win; ++w) {
         const int W = win_start[w + 1] - win_start[w];
@@ -2398,27 +2356,18 @@ extern "C" int rpe_bundle_windows(rpe_handle *h, int n_tracks, const int32_t *tr
         if ((!point_use || point_use[t]) && !all_finite(points0 + 3 * t, 3)) return rpe_invalid(h, who, "a non-finite start point of a used track");
     const size_t nwf = (size_t)win_start[n_win], slots = nw * (size_t)max_points;
     HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (int rc = windows_alloc(h, nt, no, nf, nwf, nw, slots)) return rc;
-    const hipStream_t s = h->stream;
-    if (nt > 0) {
-        HIPCHK(h, hipMemcpyAsync(h->d_wb_tstart, track_start, sizeof(int) * (nt + 1), hipMemcpyHostToDevice, s));
-        HIPCHK(h, hipMemcpyAsync(h->d_wb_points0, points0, sizeof(double) * 3 * nt, hipMemcpyHostToDevice, s));
-        if (point_use) HIPCHK(h, hipMemcpyAsync(h->d_wb_puse, point_use, nt, hipMemcpyHostToDevice, s));
-    }
-    if (no > 0) {
-        HIPCHK(h, hipMemcpyAsync(h->d_wb_oframe, obs_frame, sizeof(int) * no, hipMemcpyHostToDevice, s));
-        HIPCHK(h, hipMemcpyAsync(h->d_wb_oxy, obs_xy, sizeof(float2) * no, hipMemcpyHostToDevice, s));
-        if (obs_use) HIPCHK(h, hipMemcpyAsync(h->d_wb_ouse, obs_use, no, hipMemcpyHostToDevice, s));
-    }
-    HIPCHK(h, hipMemcpyAsync(h->d_wb_R, R_abs, sizeof(double) * 9 * nf, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(h->d_wb_T, T_abs, sizeof(double) * 3 * nf, hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(h->d_wb_cams, K ? &h->wb_cam_k : cams, sizeof(rpe_camera) * (K ? 1 : nf), hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(h->d_wb_wstart, win_start, sizeof(int) * (nw + 1), hipMemcpyHostToDevice, s));
-    HIPCHK(h, hipMemcpyAsync(h->d_wb_wframe, win_frame, sizeof(int) * nwf, hipMemcpyHostToDevice, s));
-    const RpeWindowJob job = {n_tracks, (int)no, n_win, max_points, min_obs, max_iters, K ? 0 : 1,
-                              h->d_wb_tstart, h->d_wb_oframe, h->d_wb_oxy, h->d_wb_points0,
-                              point_use && nt > 0 ? h->d_wb_puse : nullptr, obs_use && no > 0 ? h->d_wb_ouse : nullptr,
-                              h->d_wb_R, h->d_wb_T, h->d_wb_cams, h->d_wb_wstart, h->d_wb_wframe};
+    // the buffers of the call beside the scene: per track, per observation, per window frame, per window, per window and point slot
+    if (int rc = rpe_bufset_fit(h, h->set_windows,
+                                {buf_piece(h->d_wb_points0, 3 * nt), buf_piece(h->d_wb_puse, nt), buf_piece(h->d_wb_obs, no), buf_piece(h->d_wb_ouse, no),
+                                 buf_piece(h->d_wb_wstart, nw + 1), buf_piece(h->d_wb_wframe, nwf), buf_piece(h->d_wb_Rout, 9 * nwf), buf_piece(h->d_wb_Tout, 3 * nwf),
+                                 buf_piece(h->d_wb_counts, 4 * nw), buf_piece(h->d_wb_info, 4 * nw), buf_piece(h->d_wb_rms, 2 * nw), buf_piece(h->d_wb_fcnt, RPE_WINDOW_MAX_VIEWS * nw),
+                                 buf_piece(h->d_wb_ptrack, slots), buf_piece(h->d_wb_pobs, RPE_WINDOW_MAX_VIEWS * slots),
+                                 buf_piece(h->d_wb_state, 6 * slots), buf_piece(h->d_wb_points, 3 * slots)})) return rc;
+    RpeWindowJob job = {{}, n_win, max_points, min_obs, max_iters, h->d_wb_points0, point_use ? h->d_wb_puse : nullptr,
+                        obs_use ? h->d_wb_ouse : nullptr, h->d_wb_wstart, h->d_wb_wframe};
+    if (int rc = scene_upload(h, scene, no, &job.scene)) return rc;
+    if (int rc = upload(h, {{h->d_wb_points0, points0, sizeof(double) * 3 * nt}, {h->d_wb_puse, point_use, nt}, {h->d_wb_ouse, obs_use, no},
+                            {h->d_wb_wstart, win_start, sizeof(int) * (nw + 1)}, {h->d_wb_wframe, win_frame, sizeof(int) * nwf}})) return rc;
     rpe_launch_windows(h, job);
     HIPCHK(h, hipGetLastError());
     // the wait also covers the uploads: the inputs have left the caller's arrays
@@ -2475,7 +2424,7 @@ static int stage_recover_pose(rpe_handle *h, const char *who, const double *h_E,
     RpeRun run;
     int rc = stage_begin(h, who, h_pts1, h_pts2, m, B, K, cam1, cam2, run);
     if (rc) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_E, h_E, sizeof(double) * 9 * B, hipMemcpyHostToDevice, h->stream));
+    if ((rc = upload(h, {{h->d_E, h_E, sizeof(double) * 9 * B}})) != RPE_OK) return rc;
     if (run.cam.cams) rpe_launch_normalise(h, run);             // recover_pose_kernel's camera instances read d_n1 / d_n2
     rpe_launch_pose(h, run, false);
     HIPCHK(h, hipGetLastError());
@@ -2491,9 +2440,8 @@ static int stage_refine(rpe_handle *h, const char *who, const double *h_R0, cons
     int rc = stage_begin(h, who, h_pts1, h_pts2, m, B, K, cam1, cam2, run);
     if (rc) return rc;
     if ((rc = refine_alloc(h)) != RPE_OK) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_mask, h_mask, (size_t)h->cfg.max_matches * B, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_ref_R0, h_R0, sizeof(double) * 9 * B, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(h, hipMemcpyAsync(h->d_ref_t0, h_t0, sizeof(double) * 3 * B, hipMemcpyHostToDevice, h->stream));
+    if ((rc = upload(h, {{h->d_mask, h_mask, (size_t)h->cfg.max_matches * B}, {h->d_ref_R0, h_R0, sizeof(double) * 9 * B},
+                         {h->d_ref_t0, h_t0, sizeof(double) * 3 * B}})) != RPE_OK) return rc;
     return refine_run(h, run, max_iters, false, R, t, inliers, info, rms);
 }
 
@@ -2638,6 +2586,6 @@ extern "C" int rpe_match_l2(rpe_handle *h, const float *h_desc1, const int32_t *
     last_run_end(h);                            // overwrites buffers rpe_fetch_structure reads
     std::vector<uint8_t> u;
     if (int rc = l2_desc_bytes(h, h_desc1, n1, h_desc2, n2, B, u)) return rc;
-    HIPCHK(h, hipMemcpyAsync(h->d_desc, u.data(), u.size(), hipMemcpyHostToDevice, h->stream));
+    if (int rc = upload(h, {{h->d_desc, u.data(), u.size()}})) return rc;
     return stage_match_run(h, true, n1, n2, B, qidx, tidx, dist, n_matches);
 }

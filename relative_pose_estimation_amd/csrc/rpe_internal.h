@@ -13,6 +13,7 @@
 #include "../../include/rpe_amd.h"
 #include "buf_layout.h"
 #include "orb_groups.h"
+#include "track_scene.h"
 
 #define RPE_NLEVELS RPE_ORB_LEVELS
 #define RPE_EDGE 31            // ORB edgeThreshold (cv2 default; pose_estimator.py:85-91 leaves it)
@@ -365,27 +366,29 @@ struct RpeTrackJob {
 #define RPE_TRACK_NODE_WORDS 11   // int arrays of one word per node in d_tk_node
 static inline int rpe_track_scan_blocks(int N) { return (int)(((long long)N + 2047) / 2048); }   // workgroups of the track scans (2048 nodes each)
 
-// One job of the track-point kernels (track_point_kernels.hip): the uploaded tracks, poses, groups (null: all 0) and cameras
+// The track scene (track_scene.h) on the device, as scene_upload (rpe_api.hip) left it: the tracks, the poses and the cameras
 // (cam_stride 1: one per frame; 0: the one record K became)
-struct RpeTrackPointJob {
-    int n_tracks, n_obs, min_views, max_iters, cam_stride;
-    double threshold_px, max_cos;
-    const int *track_start, *obs_frame, *group;
-    const float2 *obs_xy;
-    const double *R, *T;
-    const rpe_camera *cams;
+struct RpeTrackScene {
+    int n_tracks, n_obs, cam_stride;
+    const int *track_start, *obs_frame; const float2 *obs_xy;
+    const double *R, *T; const rpe_camera *cams;
 };
 
-// One job of the window-bundle kernels (window_kernels.hip): the uploaded tracks, start points, masks (null: all set), poses,
-// cameras (cam_stride as above) and windows
+// One job of the track-point kernels (track_point_kernels.hip): the scene and the uploaded groups (null: all 0)
+struct RpeTrackPointJob {
+    RpeTrackScene scene;
+    int min_views, max_iters;
+    double threshold_px, max_cos;
+    const int *group;
+};
+
+// One job of the window-bundle kernels (window_kernels.hip): the scene and the uploaded start points, masks (null: all set)
+// and windows
 struct RpeWindowJob {
-    int n_tracks, n_obs, n_win, max_points, min_obs, max_iters, cam_stride;
-    const int *track_start, *obs_frame;
-    const float2 *obs_xy;
+    RpeTrackScene scene;
+    int n_win, max_points, min_obs, max_iters;
     const double *points0;
     const uint8_t *point_use, *obs_use;
-    const double *R, *T;
-    const rpe_camera *cams;
     const int *win_start, *win_frame;
 };
 
@@ -545,29 +548,31 @@ struct rpe_handle {
     int2 *d_tk_frames = nullptr, *d_tk_partial = nullptr;
     int *d_tk_node = nullptr, *d_tk_seen = nullptr; RpeBufSet set_tracks;
     std::vector<int> tk_frame_tab;        // host side of d_tk_frames: source of its upload
-    // rpe_triangulate_tracks only (set_track_points, fitted to every call's tracks, observations and frames).  Per track: the CSR
-    // offsets in, point, info[4], rms, min_cos out.  Per observation: frame and pixel in, the 80-byte record between the two
-    // kernels, flag and error out.  Per frame: R, T, group, camera (tp_cam_k: the host side of the one record K becomes)
-    int *d_tp_tstart = nullptr, *d_tp_oframe = nullptr, *d_tp_group = nullptr, *d_tp_info = nullptr;
-    float2 *d_tp_oxy = nullptr;
+    // The track scene of rpe_triangulate_tracks and rpe_bundle_windows (scene.set, fitted to every call's tracks, observations
+    // and frames by scene_upload; either call uploads its own scene, none is kept).  Per track the CSR offsets, per observation
+    // frame and pixel, per frame R, T and camera (cam_k: the host side of the one record K becomes)
+    struct Scene {
+        int *d_tstart = nullptr, *d_oframe = nullptr; float2 *d_oxy = nullptr;
+        double *d_R = nullptr, *d_T = nullptr; rpe_camera *d_cams = nullptr;
+        rpe_camera cam_k{}; RpeBufSet set;
+    } scene;
+    // rpe_triangulate_tracks only (set_track_points, fitted to every call's tracks, observations and frames), beside the scene.
+    // Per track: point, info[4], rms, min_cos out.  Per observation: the 80-byte record between the two kernels, flag and
+    // error out.  Per frame: group
+    int *d_tp_group = nullptr, *d_tp_info = nullptr;
     double2 *d_tp_obs = nullptr;          // [5 * n_obs]: one 80-byte record per observation
-    double *d_tp_R = nullptr, *d_tp_T = nullptr, *d_tp_points = nullptr, *d_tp_rms = nullptr, *d_tp_mincos = nullptr, *d_tp_oerr = nullptr;
-    uint8_t *d_tp_oflag = nullptr;
-    rpe_camera *d_tp_cams = nullptr;
-    rpe_camera tp_cam_k{}; RpeBufSet set_track_points;
-
-    // rpe_bundle_windows only (set_windows, fitted to every call's tracks, observations, frames and windows).  The uploads; per
-    // observation the 32-byte record of wb_prepare; per window and point slot [n_win * max_points]: the track, the observation of
-    // each window position (8 ints), the state X and the trial X (6 f64) and the output point; per window frame the output pose
-    int *d_wb_tstart = nullptr, *d_wb_oframe = nullptr, *d_wb_wstart = nullptr, *d_wb_wframe = nullptr;
+    double *d_tp_points = nullptr, *d_tp_rms = nullptr, *d_tp_mincos = nullptr, *d_tp_oerr = nullptr;
+    uint8_t *d_tp_oflag = nullptr; RpeBufSet set_track_points;
+    // rpe_bundle_windows only (set_windows, fitted to every call's tracks, observations and windows), beside the scene.  The
+    // uploads of its own (start points, masks, windows); per observation the 32-byte record of wb_prepare; per window and point
+    // slot [n_win * max_points]: the track, the observation of each window position (8 ints), the state X and the trial X
+    // (6 f64) and the output point; per window frame the output pose
+    int *d_wb_wstart = nullptr, *d_wb_wframe = nullptr;
     int *d_wb_ptrack = nullptr, *d_wb_pobs = nullptr, *d_wb_counts = nullptr, *d_wb_info = nullptr, *d_wb_fcnt = nullptr;
-    float2 *d_wb_oxy = nullptr;
     double4 *d_wb_obs = nullptr;
-    double *d_wb_points0 = nullptr, *d_wb_R = nullptr, *d_wb_T = nullptr, *d_wb_state = nullptr, *d_wb_points = nullptr;
+    double *d_wb_points0 = nullptr, *d_wb_state = nullptr, *d_wb_points = nullptr;
     double *d_wb_Rout = nullptr, *d_wb_Tout = nullptr, *d_wb_rms = nullptr;
-    uint8_t *d_wb_puse = nullptr, *d_wb_ouse = nullptr;
-    rpe_camera *d_wb_cams = nullptr;
-    rpe_camera wb_cam_k{}; RpeBufSet set_windows;
+    uint8_t *d_wb_puse = nullptr, *d_wb_ouse = nullptr; RpeBufSet set_windows;
     // rpe_frames_similar / rpe_similarity_hamming only (set_similar, fitted to every call's lists): the two slot tables (not
     // d_pairtab, which holds 2*max_batch entries: a list here may be as long as the store), the times the caller gave, the
     // nq * nt scores, and per query row its k candidates, their scores and their count
@@ -635,7 +640,8 @@ static int dmalloc(rpe_handle *h, T **p, size_t n)
 //   carving  every call assigns every piece from its own sizes: a smaller call is carved smaller inside the same block; sizes
 //            of the configuration alone give a constant total, so those pointers never move after the first call.
 // Nothing in a set outlives its call (inputs are uploaded or written by the call's own kernels, outputs fetched before it
-// returns; d_pose_mask and d_points do persist and stay DM_ONCE buffers), and none is part of a captured graph.
+// returns; d_pose_mask and d_points do persist and stay DM_ONCE buffers), and none is part of a captured graph.  That is
+// also why two features may share a set: scene.set serves the track points and the window bundles, each beside its own.
 struct RpeBufPiece { void **p; size_t bytes; };
 template <typename T>
 static inline RpeBufPiece buf_piece(T *&p, size_t n) { return {(void **)&p, n * sizeof(T)}; }
@@ -658,7 +664,7 @@ extern std::string g_create_err;
 static inline int cv_round(double v) { return (int)lrint(v); }
 
 // The refusal of an argument head: every failed call leaves a text of its own for rpe_last_error (h == NULL: nowhere to)
-static inline int rpe_invalid(rpe_handle *h, const char *who, const char *what = "a null argument or a count out of range")
+static inline int rpe_invalid(rpe_handle *h, const char *who, const char *what = RPE_NULL_ARGUMENT_TEXT)
 {
     if (h) h->err = std::string(who) + ": " + what;
     return RPE_ERR_INVALID;

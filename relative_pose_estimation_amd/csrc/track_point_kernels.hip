@@ -23,13 +23,13 @@ struct TpArgs {
 
 __global__ __launch_bounds__(256) void tp_prepare_kernel(const TpArgs a)
 {
-    const int o = tk_thread_index(a.job.n_obs);
+    const int o = tk_thread_index(a.job.scene.n_obs);
     if (o < 0) return;
     const RpeTrackPointJob &j = a.job;
-    const int fr = j.obs_frame[o];
-    const rpe_camera *cam = j.cams + (size_t)fr * j.cam_stride;
-    const double2 n = rpe_camera_normalise(cam, rpe_camera_has_lens(cam), j.obs_xy[o]);
-    const double *R = j.R + (size_t)fr * 9, *T = j.T + (size_t)fr * 3;
+    const int fr = j.scene.obs_frame[o];
+    const rpe_camera *cam = j.scene.cams + (size_t)fr * j.scene.cam_stride;
+    const double2 n = rpe_camera_normalise(cam, rpe_camera_has_lens(cam), j.scene.obs_xy[o]);
+    const double *R = j.scene.R + (size_t)fr * 9, *T = j.scene.T + (size_t)fr * 3;
     TpObs ob;
     ob.x = n.x; ob.y = n.y;
     double v[3];
@@ -80,9 +80,9 @@ __device__ __forceinline__ bool tp_linearise(const TpArgs &a, int s, int e, int 
     for (int o = s; o < e; ++o) {
         const TpObs ob = a.obs[o];
         if (!tp_selected(a, o, ob, G, inliers)) continue;
-        const double *R = a.job.R + (size_t)ob.frame * 9;
+        const double *R = a.job.scene.R + (size_t)ob.frame * 9;
         TpView v;
-        front = tp_view(ob, R, a.job.T + (size_t)ob.frame * 3, X, v) && front;
+        front = tp_view(ob, R, a.job.scene.T + (size_t)ob.frame * 3, X, v) && front;
         cost = cost + (v.e0 * v.e0 + v.e1 * v.e1);
         const double q = ob.f / v.y2, qa = q * v.u, qb = q * v.w;
         double J0[3], J1[3];
@@ -101,10 +101,10 @@ __device__ __forceinline__ bool tp_linearise(const TpArgs &a, int s, int e, int 
 
 __global__ __launch_bounds__(256) void tp_solve_kernel(const TpArgs a)
 {
-    const int t = tk_thread_index(a.job.n_tracks);
+    const int t = tk_thread_index(a.job.scene.n_tracks);
     if (t < 0) return;
     const RpeTrackPointJob &j = a.job;
-    const int s = j.track_start[t], e = j.track_start[t + 1];
+    const int s = j.scene.track_start[t], e = j.scene.track_start[t + 1];
     // 1: the group and the used set; the flags double as this thread's per-observation state, so they start at zero
     int G = -1, nU = 0;
     for (int o = s; o < e; ++o) {
@@ -169,7 +169,7 @@ __global__ __launch_bounds__(256) void tp_solve_kernel(const TpArgs a)
             TpView v;
             double err = -1.;
             bool in = false;
-            if (tp_view(ob, j.R + (size_t)ob.frame * 9, j.T + (size_t)ob.frame * 3, X, v)) {
+            if (tp_view(ob, j.scene.R + (size_t)ob.frame * 9, j.scene.T + (size_t)ob.frame * 3, X, v)) {
                 const double e2 = v.e0 * v.e0 + v.e1 * v.e1;
                 err = sqrt(e2);
                 in = err <= j.threshold_px;
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(256) void tp_solve_kernel(const TpArgs a)
     a.rms[t] = rms; a.min_cos[t] = mc;
 }
 
-// The two launches of one job.  The buffers are the caller's business (rpe_api.hip, track_points_alloc)
+// The two launches of one job.  The buffers are the caller's business (rpe_triangulate_tracks, rpe_api.hip)
 void rpe_launch_track_points(rpe_handle *h, const RpeTrackPointJob &job)
 {
     TpArgs a{};
@@ -222,6 +222,6 @@ void rpe_launch_track_points(rpe_handle *h, const RpeTrackPointJob &job)
     a.points = h->d_tp_points; a.rms = h->d_tp_rms; a.min_cos = h->d_tp_mincos; a.obs_err = h->d_tp_oerr;
     a.info = h->d_tp_info; a.obs_flag = h->d_tp_oflag;
     const dim3 blk(256);
-    if (job.n_obs > 0) hipLaunchKernelGGL(tp_prepare_kernel, dim3((unsigned)(((long long)job.n_obs + 255) / 256)), blk, 0, h->stream, a);
-    hipLaunchKernelGGL(tp_solve_kernel, dim3((unsigned)(((long long)job.n_tracks + 255) / 256)), blk, 0, h->stream, a);
+    if (job.scene.n_obs > 0) hipLaunchKernelGGL(tp_prepare_kernel, dim3((unsigned)(((long long)job.scene.n_obs + 255) / 256)), blk, 0, h->stream, a);
+    hipLaunchKernelGGL(tp_solve_kernel, dim3((unsigned)(((long long)job.scene.n_tracks + 255) / 256)), blk, 0, h->stream, a);
 }

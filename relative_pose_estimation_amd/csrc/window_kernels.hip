@@ -43,11 +43,11 @@ struct WbArgs {
 
 __global__ __launch_bounds__(256) void wb_prepare_kernel(const WbArgs a)
 {
-    const int o = tk_thread_index(a.job.n_obs);
+    const int o = tk_thread_index(a.job.scene.n_obs);
     if (o < 0) return;
     const RpeWindowJob &j = a.job;
-    const rpe_camera *cam = j.cams + (size_t)j.obs_frame[o] * j.cam_stride;
-    const double2 n = rpe_camera_normalise(cam, rpe_camera_has_lens(cam), j.obs_xy[o]);
+    const rpe_camera *cam = j.scene.cams + (size_t)j.scene.obs_frame[o] * j.scene.cam_stride;
+    const double2 n = rpe_camera_normalise(cam, rpe_camera_has_lens(cam), j.scene.obs_xy[o]);
     WbObs ob;
     ob.x = n.x; ob.y = n.y; ob.f = (cam->fx + cam->fy) / 2; ob.pad = 0.;
     a.obs[o] = ob;
@@ -63,15 +63,15 @@ __global__ __launch_bounds__(256) void wb_gather_kernel(const WbArgs a)
     __syncthreads();
     const size_t pm = (size_t)w * j.max_points;
     int n = 0;                                                               // candidates so far
-    for (int t0 = 0; t0 < j.n_tracks; t0 += 256) {
+    for (int t0 = 0; t0 < j.scene.n_tracks; t0 += 256) {
         const int t = t0 + tid;
         unsigned seen = 0;
         int s = 0, e = 0;
-        if (t < j.n_tracks && (!j.point_use || j.point_use[t])) {
-            s = j.track_start[t]; e = j.track_start[t + 1];
+        if (t < j.scene.n_tracks && (!j.point_use || j.point_use[t])) {
+            s = j.scene.track_start[t]; e = j.scene.track_start[t + 1];
             for (int o = s; o < e; ++o) {
                 if (j.obs_use && j.obs_use[o] != 1) continue;
-                const int fr = j.obs_frame[o];
+                const int fr = j.scene.obs_frame[o];
                 for (int p = 0; p < W; ++p) if (s_fr[p] == fr) seen |= 1u << p;
             }
         }
@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void wb_gather_kernel(const WbArgs a)
             unsigned done = 0;                                               // the lowest observation of a position wins
             for (int o = s; o < e; ++o) {
                 if (j.obs_use && j.obs_use[o] != 1) continue;
-                const int fr = j.obs_frame[o];
+                const int fr = j.scene.obs_frame[o];
                 for (int p = 0; p < W; ++p)
                     if (s_fr[p] == fr && !((done >> p) & 1u)) { po[p] = o; done |= 1u << p; }
             }
@@ -214,7 +214,7 @@ __global__ __launch_bounds__(256) void wb_solve_kernel(const WbArgs a)
     // ---- the gauge: every position relative to position 0
     if (tid < WB_V) s_fr[tid] = tid < W ? jb.win_frame[ws + tid] : 0;
     __syncthreads();
-    const double *R0 = jb.R + (size_t)s_fr[0] * 9, *T0 = jb.T + (size_t)s_fr[0] * 3;
+    const double *R0 = jb.scene.R + (size_t)s_fr[0] * 9, *T0 = jb.scene.T + (size_t)s_fr[0] * 3;
     if (tid < W) {
         const int p = tid;
         if (p == 0) {
@@ -224,7 +224,7 @@ __global__ __launch_bounds__(256) void wb_solve_kernel(const WbArgs a)
             for (int e = 0; e < 3; ++e) { s_t[e] = 0.; s_tn[e] = 0.; }
             s_n2[0] = 0.;
         } else {
-            const double *Rp = jb.R + (size_t)s_fr[p] * 9, *Tp = jb.T + (size_t)s_fr[p] * 3;
+            const double *Rp = jb.scene.R + (size_t)s_fr[p] * 9, *Tp = jb.scene.T + (size_t)s_fr[p] * 3;
             double Q[9], s[3];
 #pragma unroll
             for (int r = 0; r < 3; ++r)
@@ -253,7 +253,7 @@ __global__ __launch_bounds__(256) void wb_solve_kernel(const WbArgs a)
     // the input state as the output: poses and points, zeros past the points
     auto return_input = [&]() {
         if (tid < W) {
-            const double *Rp = jb.R + (size_t)s_fr[tid] * 9, *Tp = jb.T + (size_t)s_fr[tid] * 3;
+            const double *Rp = jb.scene.R + (size_t)s_fr[tid] * 9, *Tp = jb.scene.T + (size_t)s_fr[tid] * 3;
 #pragma unroll
             for (int e = 0; e < 9; ++e) a.Rout[(size_t)(ws + tid) * 9 + e] = Rp[e];
 #pragma unroll
@@ -574,7 +574,7 @@ __global__ __launch_bounds__(256) void wb_solve_kernel(const WbArgs a)
     }
 }
 
-// The three launches of one job.  The buffers are the caller's business (rpe_api.hip, windows_alloc)
+// The three launches of one job.  The buffers are the caller's business (rpe_bundle_windows, rpe_api.hip)
 void rpe_launch_windows(rpe_handle *h, const RpeWindowJob &job)
 {
     WbArgs a{};
@@ -583,7 +583,7 @@ void rpe_launch_windows(rpe_handle *h, const RpeWindowJob &job)
     a.ptrack = h->d_wb_ptrack; a.pobs = h->d_wb_pobs; a.fcnt = h->d_wb_fcnt; a.counts = h->d_wb_counts; a.info = h->d_wb_info;
     a.state = h->d_wb_state; a.points = h->d_wb_points; a.Rout = h->d_wb_Rout; a.Tout = h->d_wb_Tout; a.rms = h->d_wb_rms;
     const dim3 blk(256);
-    if (job.n_obs > 0) hipLaunchKernelGGL(wb_prepare_kernel, dim3((unsigned)(((long long)job.n_obs + 255) / 256)), blk, 0, h->stream, a);
+    if (job.scene.n_obs > 0) hipLaunchKernelGGL(wb_prepare_kernel, dim3((unsigned)(((long long)job.scene.n_obs + 255) / 256)), blk, 0, h->stream, a);
     hipLaunchKernelGGL(wb_gather_kernel, dim3(job.n_win), blk, 0, h->stream, a);
     hipLaunchKernelGGL(wb_solve_kernel, dim3(job.n_win), blk, 0, h->stream, a);
 }

@@ -135,3 +135,34 @@ def test_constructor_mirrors_reference():
         PoseEstimator._raise_for(2, 3)
     with pytest.raises(RuntimeError, match="Could not estimate Essential matrix."):   # :529-530
         PoseEstimator._raise_for(3, 9)
+
+
+def test_scene_args_prepare_and_refuse_the_track_scene():
+    """_capi._scene_args, the head of Engine.triangulate_tracks and Engine.bundle_windows, needs no library: C-contiguous
+    i32 / f32 / f64 arrays of the documented shapes, and a ValueError carrying the caller's name for a pose-count
+    mismatch, a track_start that does not end at the number of observations, an empty track_start, both K and cameras,
+    neither K nor cameras"""
+    from relative_pose_estimation_amd import _capi
+    tracks = {'track_start': [0, 2, 4, 7], 'obs_frame': np.arange(7, dtype=np.int64) % 3,
+              'obs_xy': np.arange(28, dtype=np.float64).reshape(7, 4)[:, ::2]}         # neither the dtype nor the layout wanted
+    R = np.tile(np.eye(3, dtype=np.float32), (3, 1, 1))
+    T = np.zeros((3, 3))
+    K = np.array([[500., 0., 320.], [0., 500., 240.], [0., 0., 1.]]).T.copy().T        # not C-contiguous
+    cam = _capi.Camera(K)
+    ts, of, xy, Rc, Tc, F, n, k, cams = _capi._scene_args("who", tracks, R, T, K, None)
+    assert (F, n, cams) == (3, 3, None)
+    for a, dtype, shape in ((ts, np.int32, (4,)), (of, np.int32, (7,)), (xy, np.float32, (7, 2)), (Rc, np.float64, (3, 9)),
+                            (Tc, np.float64, (3, 3)), (k, np.float64, (9,))):
+        assert a.dtype == dtype and a.shape == shape and a.flags['C_CONTIGUOUS'], (a.dtype, a.shape)
+    assert ts.tolist() == [0, 2, 4, 7] and np.array_equal(xy, np.asarray(tracks['obs_xy'], np.float32))
+    assert np.array_equal(Rc, R.reshape(3, 9)) and k.tolist() == K.reshape(9).tolist()
+    k, cams = _capi._scene_args("who", tracks, R, T, None, cam)[-2:]
+    assert k is None and cams.dtype == _capi.CAMERA_DTYPE and cams.shape == (3,) and cams.flags['C_CONTIGUOUS']
+    for who in ("triangulate_tracks", "bundle_windows"):
+        for bad, K_, cam_, what in ((dict(R_abs=R[:2]), K, None, "one pose per frame"),
+                                    (dict(tracks=dict(tracks, track_start=[0, 2, 4, 6])), K, None, "must end at the number of observations"),
+                                    (dict(tracks=dict(tracks, track_start=[])), K, None, "must end at the number of observations"),
+                                    ({}, K, cam, "exactly one of K and cameras"), ({}, None, None, "exactly one of K and cameras")):
+            args = dict(dict(tracks=tracks, R_abs=R, T_abs=T), **bad)
+            with pytest.raises(ValueError, match=who + ": .*" + what):
+                _capi._scene_args(who, args['tracks'], args['R_abs'], args['T_abs'], K_, cam_)

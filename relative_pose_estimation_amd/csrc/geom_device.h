@@ -1,10 +1,11 @@
 // geom_device.h -- what geom_kernels.hip (pairs) and link_kernels.hip (links) both use, and nothing else: the polynomial
 // root chain, the deterministic f64 sums and the ordered compaction, the small 3-vector algebra, the Levenberg-Marquardt
-// loop with its parts, and the host helper of their launchers.  A helper one file uses lives in that file.
+// loop with its parts, and the host helper of their launchers.  A helper one file uses lives in that file; what needs nothing
+// of the device (a view's rows, the point block, the rule of the loop) is in bundle_math.h, which the host tests compile too.
 // All f64 arithmetic keeps the oracle's operation order (compiled with -ffp-contract=off).
 #pragma once
 #include "rpe_internal.h"
-#include <float.h>
+#include "bundle_math.h"
 
 // ------------------------------------------------------------ polynomial root chain
 // Fixed Estrin scheme for degree <= 10 (dependency depth 7 instead of Horner's 20; the root finder is latency bound), the
@@ -139,12 +140,7 @@ __device__ __forceinline__ void cross3(const double *a, const double *b, double 
     c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
 }
 
-// ------------------------------------------------------------ Levenberg-Marquardt (refine_lm and its parts)
-#define REFINE_LAMBDA0 1e-3          // initial damping
-#define REFINE_REL_TOL 1e-6          // stop when an accepted step lowers the cost by no more than this fraction
-#define REFINE_STEP_TOL 1e-9         // ... or its 5-vector is no longer than this
-#define REFINE_SMALL_ANGLE 1e-4      // Rodrigues: series for sin(th)/th and (1 - cos th)/th^2 below this angle
-
+// ------------------------------------------------------------ Levenberg-Marquardt (refine_lm and its parts; lm_loop: bundle_math.h)
 // tangent basis of the unit sphere at t: b1 = normalise(t x e_k), k = axis of smallest |t_k| (lowest on ties), b2 = t x b1
 __device__ __forceinline__ void refine_basis(const double *t, double *b1, double *b2)
 {
@@ -230,16 +226,14 @@ __device__ __forceinline__ bool refine_solve(const double *H, const double *g, d
 }
 
 // The Levenberg-Marquardt loop over N parameters, shared by pose_refine_kernel, link_pose_kernel and bundle_kernel; all 256
-// threads call it with identical operands.
+// threads call it with identical operands.  lm_loop's rule, arranged for a workgroup whose state is a pose in registers:
 //   linearise()        the normal equations at the caller's state, summed over the workgroup (block_sum_f64)
 //   solve(lambda, d)   the damped step d from them; false when there is none (a matrix that is not positive definite).
 //                      RefineNormalSolve is the plain form: s holds the upper triangle of J'J, then J'r, then r'r
 //   trial(d, Rn, tn)   the pose (Rn, tn) that step d leads to from (R, t), and this thread's part of its cost
 //   commit()           an accepted step: whatever state the caller keeps outside (R, t) moves with it
-// A failed solve or a step that does not strictly lower the cost multiplies lambda by 10; an accepted step divides it by
-// 10, moves (R, t, cost) and stops the loop when it lowered the cost by no more than REFINE_REL_TOL of it or is no longer
-// than REFINE_STEP_TOL.  The state is linearised again only when another iteration follows an accepted step.  iters counts
-// the iterations begun, acc the steps accepted.
+// The state is linearised again only when another iteration follows an accepted step (the step hook); the trial hook sums
+// the threads' parts, the accept hook moves (R, t) and calls commit().  iters: the iterations begun, acc: the steps accepted.
 template <int N>
 struct RefineNormalSolve {
     const double *s;
@@ -251,33 +245,18 @@ template <int N, class Linearise, class Solve, class Trial, class Commit>
 __device__ __forceinline__ void refine_lm(double (&R)[9], double (&t)[3], double &cost, int max_iters, double *s_red,
                                           Linearise linearise, Solve solve, Trial trial, Commit commit, int &iters, int &acc)
 {
-    double lambda = REFINE_LAMBDA0;
     bool need_lin = false;
-    for (int it = 0; it < max_iters; ++it) {
-        if (need_lin) { linearise(); need_lin = false; }
-        ++iters;
-        double d[N];
-        if (!solve(lambda, d)) { lambda = lambda * 10.; continue; }
-        double Rn[9], tn[3];
-        double c1[1] = {trial(d, Rn, tn)};
-        block_sum_f64<1>(c1, s_red, threadIdx.x);
-        if (isfinite(c1[0]) && c1[0] < cost) {
-            const double dec = cost - c1[0], prev = cost;
-            double dn = d[0] * d[0];
+    double d[N], Rn[9], tn[3];
+    auto step = [&](double lambda) { if (need_lin) { linearise(); need_lin = false; } return solve(lambda, d); };
+    auto summed_trial = [&](double) { double c1[1] = {trial(d, Rn, tn)}; block_sum_f64<1>(c1, s_red, threadIdx.x); return c1[0]; };
+    auto accept = [&]() {
 #pragma unroll
-            for (int k = 1; k < N; ++k) dn = dn + d[k] * d[k];
-            dn = sqrt(dn);
+        for (int e = 0; e < 9; ++e) R[e] = Rn[e];
 #pragma unroll
-            for (int e = 0; e < 9; ++e) R[e] = Rn[e];
-#pragma unroll
-            for (int e = 0; e < 3; ++e) t[e] = tn[e];
-            commit();
-            cost = c1[0]; lambda = lambda / 10.; ++acc; need_lin = true;
-            if (dec <= REFINE_REL_TOL * prev || dn <= REFINE_STEP_TOL) break;
-        } else {
-            lambda = lambda * 10.;
-        }
-    }
+        for (int e = 0; e < 3; ++e) t[e] = tn[e];
+        commit(); need_lin = true;
+    };
+    lm_loop(cost, max_iters, step, summed_trial, [&]() { return lm_step_norm(d, N); }, accept, iters, acc);
 }
 
 // ------------------------------------------------------------ 3-vectors by reference
@@ -286,7 +265,7 @@ __device__ __forceinline__ void hg_cross(const double (&a)[3], const double (&b)
 {
     c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
 }
-__device__ __forceinline__ bool hg_finite(double v) { return fabs(v) <= DBL_MAX; }
+__device__ __forceinline__ bool hg_finite(double v) { return bm_finite(v); }
 
 // ------------------------------------------------------------ host: the launchers' helper
 // Launches the camera instance of a kernel when the run carries a camera source, the shared-K instance otherwise (the

@@ -4,7 +4,8 @@
 //   link poses    : P3P RANSAC of pair b's other frame against the points pair a triangulated, polished by refine_lm<6>
 //   link bundles  : bundle adjustment of the link's three views (gather + bundle, refine_lm<11> on the reduced system)
 // One 256-thread workgroup per link, f64 throughout; what the pair kernels of geom_kernels.hip use as well is in
-// geom_device.h.  All f64 arithmetic keeps the oracle's operation order (compiled with -ffp-contract=off).
+// geom_device.h.  The reprojection view (bm_view), the rows by the point, the point block with its adjugate inverse and the
+// rule under refine_lm (lm_loop) are bundle_math.h's, shared with the track points and the window bundles.  All f64 arithmetic keeps the oracle's operation order (compiled with -ffp-contract=off).
 #include "rpe_internal.h"
 #include "geom_device.h"
 #include <algorithm>
@@ -405,23 +406,6 @@ __device__ __forceinline__ void lp_sample(const unsigned short *__restrict__ sub
     }
 }
 
-// the two reprojection residuals of one correspondence in pixels; optionally their derivatives by (w0 w1 w2 | d0 d1 d2)
-template <bool JAC>
-__device__ __forceinline__ void lp_residual(const double *R, const double *t, double scale, const double *X, const double *q,
-                                            double &rx, double &ry, double *Jx, double *Jy)
-{
-    const double a0 = (R[0] * X[0] + R[1] * X[1]) + R[2] * X[2], a1 = (R[3] * X[0] + R[4] * X[1]) + R[5] * X[2];
-    const double a2 = (R[6] * X[0] + R[7] * X[1]) + R[8] * X[2];
-    const double y0 = a0 + t[0], y1 = a1 + t[1], y2 = a2 + t[2];
-    const double ux = y0 / y2, uy = y1 / y2;
-    rx = scale * (ux - q[0]); ry = scale * (uy - q[1]);
-    if (JAC) {                                            // d y / d w_k = e_k x (R X), d y / d d = I
-        const double s = scale / y2;
-        Jx[0] = -s * (ux * a1); Jx[1] = s * (a2 + ux * a0); Jx[2] = -s * a1; Jx[3] = s; Jx[4] = 0.; Jx[5] = -s * ux;
-        Jy[0] = -s * (a2 + uy * a1); Jy[1] = s * (uy * a0); Jy[2] = s * a0; Jy[3] = 0.; Jy[4] = s; Jy[5] = -s * uy;
-    }
-}
-
 // The kernel's dynamic LDS (the list of the header), for the kernel's carve-up and the launcher's size: region A at 0, the
 // byte offsets of what follows it, the size.  corr_in_lds: X and q are staged here, else they are in d_lp_corr
 struct LinkPoseLds {
@@ -584,7 +568,7 @@ __global__ __launch_bounds__(256) void link_pose_kernel(const RpeLinkSrc src, co
         for (int c = tid; c < n; c += 256) {
             if (!s_in[c]) continue;
             double rx, ry, Jx[6], Jy[6];
-            lp_residual<true>(R, t, scale, cX + 3 * c, cq + 2 * c, rx, ry, Jx, Jy);
+            bm_view<true>(R, t, scale, cX + 3 * c, cq[2 * c], cq[2 * c + 1], rx, ry, Jx, Jy);
             int q = 0;
 #pragma unroll
             for (int u = 0; u < 6; ++u)
@@ -605,7 +589,7 @@ __global__ __launch_bounds__(256) void link_pose_kernel(const RpeLinkSrc src, co
         for (int c = tid; c < n; c += 256) {
             if (!s_in[c]) continue;
             double rx, ry;
-            lp_residual<false>(Rn, tn, scale, cX + 3 * c, cq + 2 * c, rx, ry, nullptr, nullptr);
+            bm_view<false>(Rn, tn, scale, cX + 3 * c, cq[2 * c], cq[2 * c + 1], rx, ry, nullptr, nullptr);
             cs += rx * rx + ry * ry;
         }
         return cs;
@@ -717,24 +701,15 @@ __device__ __forceinline__ void ba_point(const double (&RA)[9], const double (&t
         p.JX[1][0] = 0.; p.JX[1][1] = s; p.JX[1][2] = -s * uy;
     }
     double Jx[6], Jy[6];
-    lp_residual<true>(RA, tA, fa, X, q + 2, p.e[2], p.e[3], Jx, Jy);
+    bm_view<true>(RA, tA, fa, X, q[2], q[3], p.e[2], p.e[3], Jx, Jy);
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
-        p.JA[0][k] = Jx[k]; p.JA[1][k] = Jy[k];
-        p.JX[2][k] = (Jx[3] * RA[k] + Jx[4] * RA[3 + k]) + Jx[5] * RA[6 + k];
-        p.JX[3][k] = (Jy[3] * RA[k] + Jy[4] * RA[3 + k]) + Jy[5] * RA[6 + k];
-    }
+    for (int k = 0; k < 3; ++k) { p.JA[0][k] = Jx[k]; p.JA[1][k] = Jy[k]; }
+    bm_point_rows(Jx, Jy, RA, p.JX[2], p.JX[3]);
     p.JA[0][3] = (Jx[3] * b1[0] + Jx[4] * b1[1]) + Jx[5] * b1[2]; p.JA[0][4] = (Jx[3] * b2[0] + Jx[4] * b2[1]) + Jx[5] * b2[2];
     p.JA[1][3] = (Jy[3] * b1[0] + Jy[4] * b1[1]) + Jy[5] * b1[2]; p.JA[1][4] = (Jy[3] * b2[0] + Jy[4] * b2[1]) + Jy[5] * b2[2];
     if (hc) {
-        lp_residual<true>(RC, tC, fc, X, q + 4, p.e[4], p.e[5], Jx, Jy);
-#pragma unroll
-        for (int k = 0; k < 6; ++k) { p.JC[0][k] = Jx[k]; p.JC[1][k] = Jy[k]; }
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            p.JX[4][k] = (Jx[3] * RC[k] + Jx[4] * RC[3 + k]) + Jx[5] * RC[6 + k];
-            p.JX[5][k] = (Jy[3] * RC[k] + Jy[4] * RC[3 + k]) + Jy[5] * RC[6 + k];
-        }
+        bm_view<true>(RC, tC, fc, X, q[4], q[5], p.e[4], p.e[5], p.JC[0], p.JC[1]);
+        bm_point_rows(p.JC[0], p.JC[1], RC, p.JX[4], p.JX[5]);
     } else {
         p.e[4] = 0.; p.e[5] = 0.;
 #pragma unroll
@@ -748,24 +723,15 @@ __device__ __forceinline__ void ba_point(const double (&RA)[9], const double (&t
 __device__ __forceinline__ double ba_cost(const double (&e)[6]) { return ((e[0] * e[0] + e[1] * e[1]) + (e[2] * e[2] + e[3] * e[3])) + (e[4] * e[4] + e[5] * e[5]); }
 
 // The point block of p under damping lambda: Vi = (Jp'Jp + lambda diag)^-1 by the adjugate (upper triangle 00 01 02 11 12
-// 22), g_p = Jp'r and W = Jc'Jp (rows 0..4: A, 5..10: C).  False when V is singular.
+// 22; bm_block_row over the six rows in ascending order), g_p = Jp'r and W = Jc'Jp (rows 0..4: A, 5..10: C).  False when V
+// is singular.  The inverse stands before W: behind it, bundle_kernel took 113 more vector instructions and 4 % more time.
 __device__ __forceinline__ bool ba_block(const BaPoint &p, double lambda, double (&Vi)[6], double (&gp)[3], double (&W)[11][3])
 {
     double v[6] = {0., 0., 0., 0., 0., 0.};
+    gp[0] = 0.; gp[1] = 0.; gp[2] = 0.;
 #pragma unroll
-    for (int i = 0; i < 3; ++i) gp[i] = 0.;
-#pragma unroll
-    for (int r = 0; r < 6; ++r) {
-        v[0] += p.JX[r][0] * p.JX[r][0]; v[1] += p.JX[r][0] * p.JX[r][1]; v[2] += p.JX[r][0] * p.JX[r][2];
-        v[3] += p.JX[r][1] * p.JX[r][1]; v[4] += p.JX[r][1] * p.JX[r][2]; v[5] += p.JX[r][2] * p.JX[r][2];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) gp[i] += p.JX[r][i] * p.e[r];
-    }
-    v[0] = v[0] + lambda * v[0]; v[3] = v[3] + lambda * v[3]; v[5] = v[5] + lambda * v[5];
-    const double c00 = v[3] * v[5] - v[4] * v[4], c01 = v[2] * v[4] - v[1] * v[5], c02 = v[1] * v[4] - v[2] * v[3];
-    const double c11 = v[0] * v[5] - v[2] * v[2], c12 = v[1] * v[2] - v[0] * v[4], c22 = v[0] * v[3] - v[1] * v[1];
-    const double det = (v[0] * c00 + v[1] * c01) + v[2] * c02;
-    Vi[0] = c00 / det; Vi[1] = c01 / det; Vi[2] = c02 / det; Vi[3] = c11 / det; Vi[4] = c12 / det; Vi[5] = c22 / det;
+    for (int r = 0; r < 6; ++r) bm_block_row(p.JX[r], p.e[r], v, gp);
+    const bool regular = bm_damped_inverse(v, lambda, Vi);
 #pragma unroll
     for (int i = 0; i < 3; ++i) {
 #pragma unroll
@@ -773,15 +739,7 @@ __device__ __forceinline__ bool ba_block(const BaPoint &p, double lambda, double
 #pragma unroll
         for (int k = 0; k < 6; ++k) W[5 + k][i] = p.JC[0][k] * p.JX[4][i] + p.JC[1][k] * p.JX[5][i];
     }
-    return det > 0. && hg_finite(det);
-}
-
-// row i of the symmetric 3 x 3 held as its upper triangle, times u
-__device__ __forceinline__ double ba_sym_row(const double (&S)[6], int i, const double (&u)[3])
-{
-    const double a = i == 0 ? S[0] : (i == 1 ? S[1] : S[2]), b = i == 0 ? S[1] : (i == 1 ? S[3] : S[4]);
-    const double c = i == 0 ? S[2] : (i == 1 ? S[4] : S[5]);
-    return (a * u[0] + b * u[1]) + c * u[2];
+    return regular;
 }
 
 template <bool CAM>
@@ -981,7 +939,7 @@ __global__ __launch_bounds__(256) void bundle_kernel(const int *__restrict__ n_i
             int q = 0;
 #pragma unroll
             for (int k = 0; k < 11; ++k) {
-                const double Y[3] = {ba_sym_row(Vi, 0, W[k]), ba_sym_row(Vi, 1, W[k]), ba_sym_row(Vi, 2, W[k])};
+                const double Y[3] = {bm_sym_row(Vi, 0, W[k]), bm_sym_row(Vi, 1, W[k]), bm_sym_row(Vi, 2, W[k])};
 #pragma unroll
                 for (int l = k; l < 11; ++l, ++q) r[q] += (Y[0] * W[l][0] + Y[1] * W[l][1]) + Y[2] * W[l][2];
                 r[66 + k] += (Y[0] * gp[0] + Y[1] * gp[1]) + Y[2] * gp[2];
@@ -1031,13 +989,13 @@ __global__ __launch_bounds__(256) void bundle_kernel(const int *__restrict__ n_i
             }
             double Xn[3];
 #pragma unroll
-            for (int i = 0; i < 3; ++i) { Xn[i] = sX[3 * j + i] - ba_sym_row(Vi, i, u); sXn[3 * j + i] = Xn[i]; }
+            for (int i = 0; i < 3; ++i) { Xn[i] = sX[3 * j + i] - bm_sym_row(Vi, i, u); sXn[3 * j + i] = Xn[i]; }
             const double *q = ob + 6 * s_idx[j];
             double e[6];
             e[0] = fa * (Xn[0] / Xn[2] - q[0]); e[1] = fa * (Xn[1] / Xn[2] - q[1]);
-            lp_residual<false>(RAn, tAn, fa, Xn, q + 2, e[2], e[3], nullptr, nullptr);
+            bm_view<false>(RAn, tAn, fa, Xn, q[2], q[3], e[2], e[3], nullptr, nullptr);
             e[4] = 0.; e[5] = 0.;
-            if (vw[s_idx[j]] == 3) lp_residual<false>(RCn, tCn, fc, Xn, q + 4, e[4], e[5], nullptr, nullptr);
+            if (vw[s_idx[j]] == 3) bm_view<false>(RCn, tCn, fc, Xn, q[4], q[5], e[4], e[5], nullptr, nullptr);
             c += ba_cost(e);
         }
         return c;

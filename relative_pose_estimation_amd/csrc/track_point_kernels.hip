@@ -8,6 +8,7 @@
 //   tp_solve     one thread per track, walking its CSR segment in ascending order: that IS the header's summation order, so
 //                there is no reduction tree, no barrier and no atomic.  The per-observation state of a track of any length
 //                (its verdict) lives in the obs_flag output itself, which the thread reads back in the reselection round
+// A view (bm_view) and the rule of the refinement (lm_loop, here for one thread) are bundle_math.h's, as in the link kernels
 #include "geom_device.h"
 
 struct alignas(16) TpObs { double x, y, d[3], c[3], f; int group, frame; };
@@ -47,16 +48,14 @@ __global__ __launch_bounds__(256) void tp_prepare_kernel(const TpArgs a)
     a.obs[o] = ob;
 }
 
-// One view of X: depth y2 (the return value says y2 > 0), the projection (u, w) and the pixel residual (e0, e1)
+// One view of X (bm_view): depth y2 (the return value says y2 > 0), the projection (u, w) and the pixel residual (e0, e1)
 struct TpView { double y2, u, w, e0, e1; };
 __device__ __forceinline__ bool tp_view(const TpObs &ob, const double *__restrict__ R, const double *__restrict__ T,
                                         const double (&X)[3], TpView &v)
 {
-    const double y0 = ((R[0] * X[0] + R[1] * X[1]) + R[2] * X[2]) + T[0];
-    const double y1 = ((R[3] * X[0] + R[4] * X[1]) + R[5] * X[2]) + T[1];
-    v.y2 = ((R[6] * X[0] + R[7] * X[1]) + R[8] * X[2]) + T[2];
-    v.u = y0 / v.y2; v.w = y1 / v.y2;
-    v.e0 = ob.f * (v.u - ob.x); v.e1 = ob.f * (v.w - ob.y);
+    double yu[3];
+    bm_view<false>(R, T, ob.f, X, ob.x, ob.y, v.e0, v.e1, nullptr, nullptr, yu);
+    v.y2 = yu[0]; v.u = yu[1]; v.w = yu[2];
     return v.y2 > 0.;
 }
 
@@ -113,7 +112,7 @@ __global__ __launch_bounds__(256) void tp_solve_kernel(const TpArgs a)
         nU += G >= 0 && g == G;
         a.obs_flag[o] = 0; a.obs_err[o] = 0.;
     }
-    int code = -1, nin = 0, iters = 0;
+    int code = -1, nin = 0, iters = 0, acc = 0;             // acc: lm_loop counts the accepted steps, nothing here reads them
     double X[3] = {0., 0., 0.}, rms = 0., mc = 0.;
     if (nU < j.min_views) code = RPE_TRACKPT_TOO_FEW;
     for (int round = 0; code < 0; ++round) {
@@ -138,28 +137,22 @@ __global__ __launch_bounds__(256) void tp_solve_kernel(const TpArgs a)
         if (!refine_solve<3>(A, nb, 0., X)) { code = RPE_TRACKPT_DEGENERATE; break; }
         double cost, H[6], g[3];
         if (!tp_linearise(a, s, e, G, inl, X, cost, H, g)) { code = RPE_TRACKPT_BEHIND; break; }
-        // 3: refine_lm's loop for one thread.  A trial is linearised as it is costed, so an accepted one needs no second pass
-        double lambda = REFINE_LAMBDA0;
-        for (int it = 0; it < j.max_iters; ++it) {
-            ++iters;
-            double d[3];
-            if (!refine_solve<3>(H, g, lambda, d)) { lambda = lambda * 10.; continue; }
-            const double Xn[3] = {X[0] + d[0], X[1] + d[1], X[2] + d[2]};
-            double c1, Hn[6], gn[3];
-            const bool front = tp_linearise(a, s, e, G, inl, Xn, c1, Hn, gn);
-            if (front && hg_finite(c1) && c1 < cost) {
-                const double dec = cost - c1, prev = cost;
-                const double dn = sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]);
+        // 3: lm_loop for one thread.  A trial is linearised as it is costed, so an accepted one needs no second pass; a trial
+        // with a selected view behind is vetoed
+        double d[3], Xn[3], Hn[6], gn[3];
+        auto trial = [&](double) {
+            double c1;
+            Xn[0] = X[0] + d[0]; Xn[1] = X[1] + d[1]; Xn[2] = X[2] + d[2];
+            return tp_linearise(a, s, e, G, inl, Xn, c1, Hn, gn) ? c1 : (double)INFINITY;
+        };
+        auto accept = [&]() {
 #pragma unroll
-                for (int k = 0; k < 3; ++k) { X[k] = Xn[k]; g[k] = gn[k]; }
+            for (int k = 0; k < 3; ++k) { X[k] = Xn[k]; g[k] = gn[k]; }
 #pragma unroll
-                for (int k = 0; k < 6; ++k) H[k] = Hn[k];
-                cost = c1; lambda = lambda / 10.;
-                if (dec <= REFINE_REL_TOL * prev || dn <= REFINE_STEP_TOL) break;
-            } else {
-                lambda = lambda * 10.;
-            }
-        }
+            for (int k = 0; k < 6; ++k) H[k] = Hn[k];
+        };
+        auto step = [&](double lambda) { return refine_solve<3>(H, g, lambda, d); };
+        lm_loop(cost, j.max_iters, step, trial, [&]() { return lm_step_norm(d, 3); }, accept, iters, acc);
         // 4: every used view judged at X
         double ss = 0.;
         nin = 0;

@@ -21,6 +21,7 @@
 //                               per column
 //                  trial        per point (lane stride 256) dp = -V^-1 (g_p + W' step), the trial X and its cost
 // A point's Jacobians are formed again in every pass: arithmetic is small next to storing 288 B per observation.
+// A view with its rows, the point block with its inverse and the rule of the loop are bundle_math.h's, as in the link kernels.
 #include "geom_device.h"
 
 #define WB_V RPE_WINDOW_MAX_VIEWS
@@ -103,28 +104,14 @@ __global__ __launch_bounds__(256) void wb_gather_kernel(const WbArgs a)
     }
 }
 
-// The two residuals of one view of X in pixels and its depth; with JAC the rows' derivatives by (w0 w1 w2 | d0 d1 d2) and
-// by the point.  Position 0 comes through here as (I, 0): a = X and Jt Q = Jt to the bit
+// The two residuals of one view of X in pixels; with JAC the rows' derivatives by (w0 w1 w2 | d0 d1 d2) and by the point
+// (bm_view, bm_point_rows).  Position 0 comes through here as (I, 0): a = X and Jt Q = Jt to the bit
 template <bool JAC>
-__device__ __forceinline__ void wb_view(const double *Q, const double *t, const WbObs &ob, const double *X, double (&e)[2], double &y2,
+__device__ __forceinline__ void wb_view(const double *Q, const double *t, const WbObs &ob, const double *X, double (&e)[2],
                                         double (&Jx)[6], double (&Jy)[6], double (&JX)[2][3])
 {
-    const double a0 = (Q[0] * X[0] + Q[1] * X[1]) + Q[2] * X[2], a1 = (Q[3] * X[0] + Q[4] * X[1]) + Q[5] * X[2];
-    const double a2 = (Q[6] * X[0] + Q[7] * X[1]) + Q[8] * X[2];
-    const double y0 = a0 + t[0], y1 = a1 + t[1];
-    y2 = a2 + t[2];
-    const double ux = y0 / y2, uy = y1 / y2;
-    e[0] = ob.f * (ux - ob.x); e[1] = ob.f * (uy - ob.y);
-    if (JAC) {
-        const double s = ob.f / y2;
-        Jx[0] = -s * (ux * a1); Jx[1] = s * (a2 + ux * a0); Jx[2] = -s * a1; Jx[3] = s; Jx[4] = 0.; Jx[5] = -s * ux;
-        Jy[0] = -s * (a2 + uy * a1); Jy[1] = s * (uy * a0); Jy[2] = s * a0; Jy[3] = 0.; Jy[4] = s; Jy[5] = -s * uy;
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            JX[0][k] = (Jx[3] * Q[k] + Jx[4] * Q[3 + k]) + Jx[5] * Q[6 + k];
-            JX[1][k] = (Jy[3] * Q[k] + Jy[4] * Q[3 + k]) + Jy[5] * Q[6 + k];
-        }
-    }
+    bm_view<JAC>(Q, t, ob.f, X, ob.x, ob.y, e[0], e[1], Jx, Jy);
+    if (JAC) bm_point_rows(Jx, Jy, Q, JX[0], JX[1]);
 }
 
 // the anchor's block: (w | tangent step); its sixth column is unused and zero
@@ -132,14 +119,6 @@ __device__ __forceinline__ void wb_anchor_cols(const double *b, double (&J)[6])
 {
     const double c3 = (J[3] * b[0] + J[4] * b[1]) + J[5] * b[2], c4 = (J[3] * b[3] + J[4] * b[4]) + J[5] * b[5];
     J[3] = c3; J[4] = c4; J[5] = 0.;
-}
-
-// row i of the symmetric 3 x 3 held as its upper triangle (00 01 02 11 12 22), times u
-__device__ __forceinline__ double wb_sym_row(const double (&S)[6], int i, const double (&u)[3])
-{
-    const double a = i == 0 ? S[0] : (i == 1 ? S[1] : S[2]), b = i == 0 ? S[1] : (i == 1 ? S[3] : S[4]);
-    const double c = i == 0 ? S[2] : (i == 1 ? S[4] : S[5]);
-    return (a * u[0] + b * u[1]) + c * u[2];
 }
 
 // What a pass over the points reads: the window's size, the cameras (LDS), the tangent basis at the anchor's t (LDS), the
@@ -153,41 +132,30 @@ struct WbState {
 };
 
 // The point block of point j under damping lambda: Vi = (Jp'Jp + lambda diag)^-1 by the adjugate and g_p = Jp'e, over the
-// point's views in ascending position, x row before y row.  False when V is singular.
+// point's views in ascending position, x row before y row (bm_block_row).  False when V is singular.
 __device__ __forceinline__ bool wb_block(const WbState &c, int j, double lambda, double (&Vi)[6], double (&gp)[3])
 {
     double v[6] = {0., 0., 0., 0., 0., 0.};
-#pragma unroll
-    for (int i = 0; i < 3; ++i) gp[i] = 0.;
+    gp[0] = 0.; gp[1] = 0.; gp[2] = 0.;
     const int *po = c.pobs + (size_t)j * WB_V;
     const double *X = c.X + 3 * (size_t)j;
     for (int p = 0; p < c.W; ++p) {
         const int o = po[p];
         if (o < 0) continue;
-        double e[2], y2, Jx[6], Jy[6], JX[2][3];
-        wb_view<true>(c.Q + 9 * p, c.t + 3 * p, c.obs[o], X, e, y2, Jx, Jy, JX);
-#pragma unroll
-        for (int r = 0; r < 2; ++r) {
-            v[0] += JX[r][0] * JX[r][0]; v[1] += JX[r][0] * JX[r][1]; v[2] += JX[r][0] * JX[r][2];
-            v[3] += JX[r][1] * JX[r][1]; v[4] += JX[r][1] * JX[r][2]; v[5] += JX[r][2] * JX[r][2];
-#pragma unroll
-            for (int i = 0; i < 3; ++i) gp[i] += JX[r][i] * e[r];
-        }
+        double e[2], Jx[6], Jy[6], JX[2][3];
+        wb_view<true>(c.Q + 9 * p, c.t + 3 * p, c.obs[o], X, e, Jx, Jy, JX);
+        bm_block_row(JX[0], e[0], v, gp);
+        bm_block_row(JX[1], e[1], v, gp);
     }
-    v[0] = v[0] + lambda * v[0]; v[3] = v[3] + lambda * v[3]; v[5] = v[5] + lambda * v[5];
-    const double c00 = v[3] * v[5] - v[4] * v[4], c01 = v[2] * v[4] - v[1] * v[5], c02 = v[1] * v[4] - v[2] * v[3];
-    const double c11 = v[0] * v[5] - v[2] * v[2], c12 = v[1] * v[2] - v[0] * v[4], c22 = v[0] * v[3] - v[1] * v[1];
-    const double det = (v[0] * c00 + v[1] * c01) + v[2] * c02;
-    Vi[0] = c00 / det; Vi[1] = c01 / det; Vi[2] = c02 / det; Vi[3] = c11 / det; Vi[4] = c12 / det; Vi[5] = c22 / det;
-    return det > 0. && hg_finite(det);
+    return bm_damped_inverse(v, lambda, Vi);
 }
 
 // The view of point j at position p >= 1 (observation o): its residuals, the rows by the block's parameters and W = Jc'Jp
 __device__ __forceinline__ void wb_cam_view(const WbState &c, int j, int p, int o, double (&e)[2], double (&Jx)[6], double (&Jy)[6],
                                             double (&Wm)[6][3])
 {
-    double y2, JX[2][3];
-    wb_view<true>(c.Q + 9 * p, c.t + 3 * p, c.obs[o], c.X + 3 * (size_t)j, e, y2, Jx, Jy, JX);
+    double JX[2][3];
+    wb_view<true>(c.Q + 9 * p, c.t + 3 * p, c.obs[o], c.X + 3 * (size_t)j, e, Jx, Jy, JX);
     if (p == c.A) { wb_anchor_cols(c.b, Jx); wb_anchor_cols(c.b, Jy); }
 #pragma unroll
     for (int k = 0; k < 6; ++k)
@@ -311,8 +279,8 @@ __global__ __launch_bounds__(256) void wb_solve_kernel(const WbArgs a)
             for (int p = 0; p < W; ++p) {
                 const int o = po[p];
                 if (o < 0) continue;
-                double e[2], y2, Jx[6], Jy[6], JX[2][3];
-                wb_view<false>(Q + 9 * p, t + 3 * p, a.obs[o], Xs + 3 * (size_t)j, e, y2, Jx, Jy, JX);
+                double e[2], Jx[6], Jy[6], JX[2][3];
+                wb_view<false>(Q + 9 * p, t + 3 * p, a.obs[o], Xs + 3 * (size_t)j, e, Jx, Jy, JX);
                 pc = pc + (e[0] * e[0] + e[1] * e[1]);
             }
             c[0] += pc;
@@ -358,7 +326,7 @@ __global__ __launch_bounds__(256) void wb_solve_kernel(const WbArgs a)
                 }
 #pragma unroll
                 for (int k = 0; k < 6; ++k) {
-                    const double Y[3] = {wb_sym_row(Vi, 0, Wp[k]), wb_sym_row(Vi, 1, Wp[k]), wb_sym_row(Vi, 2, Wp[k])};
+                    const double Y[3] = {bm_sym_row(Vi, 0, Wp[k]), bm_sym_row(Vi, 1, Wp[k]), bm_sym_row(Vi, 2, Wp[k])};
 #pragma unroll
                     for (int m = 0; m < 6; ++m) S[k * 6 + m] += (Y[0] * Wq[m][0] + Y[1] * Wq[m][1]) + Y[2] * Wq[m][2];
                     if (diag) vv[k] += (Y[0] * gp[0] + Y[1] * gp[1]) + Y[2] * gp[2];
@@ -476,41 +444,27 @@ __global__ __launch_bounds__(256) void wb_solve_kernel(const WbArgs a)
                 }
             }
 #pragma unroll
-            for (int i = 0; i < 3; ++i) sXn[3 * (size_t)j + i] = sX[3 * (size_t)j + i] - wb_sym_row(Vi, i, u);
+            for (int i = 0; i < 3; ++i) sXn[3 * (size_t)j + i] = sX[3 * (size_t)j + i] - bm_sym_row(Vi, i, u);
         }
         __syncthreads();                                                     // the trial cameras; a thread reads its own trial points
         return cost_of(s_Qn, s_tn, sXn);
     };
-    // ---- the loop of refine_lm over this state
+    // ---- lm_loop over this state
     const double cost0 = cost_of(s_Q, s_t, sX);
-    double cost = cost0, lambda = REFINE_LAMBDA0;
+    double cost = cost0;
     int iters = 0, acc = 0;
-    if (hg_finite(cost0)) {
-        for (int it = 0; it < jb.max_iters; ++it) {
-            ++iters;
-            if (!solve(lambda)) { lambda = lambda * 10.; continue; }
-            const double c1 = trial(lambda);
-            if (hg_finite(c1) && c1 < cost) {
-                const double dec = cost - c1, prev = cost;
-                double dn = s_d[0] * s_d[0];
-                for (int k = 1; k < N; ++k) dn = dn + s_d[k] * s_d[k];
-                dn = sqrt(dn);
-                __syncthreads();                                             // every reader of the old state and of s_d is done
-                if (tid < W * 9) s_Q[tid] = s_Qn[tid];
-                if (tid < W * 3) s_t[tid] = s_tn[tid];
-                for (int j = tid; j < n; j += 256) {
+    auto accept = [&]() {
+        __syncthreads();                                                     // every reader of the old state and of s_d is done
+        if (tid < W * 9) s_Q[tid] = s_Qn[tid];
+        if (tid < W * 3) s_t[tid] = s_tn[tid];
+        for (int j = tid; j < n; j += 256) {
 #pragma unroll
-                    for (int e = 0; e < 3; ++e) sX[3 * (size_t)j + e] = sXn[3 * (size_t)j + e];
-                }
-                __syncthreads();                                             // the passes of solve() walk the points in another order
-                basis();
-                cost = c1; lambda = lambda / 10.; ++acc;
-                if (dec <= REFINE_REL_TOL * prev || dn <= REFINE_STEP_TOL) break;
-            } else {
-                lambda = lambda * 10.;
-            }
+            for (int e = 0; e < 3; ++e) sX[3 * (size_t)j + e] = sXn[3 * (size_t)j + e];
         }
-    }
+        __syncthreads();                                                     // the passes of solve() walk the points in another order
+        basis();
+    };
+    if (hg_finite(cost0)) lm_loop(cost, jb.max_iters, solve, trial, [&]() { return lm_step_norm(s_d, N); }, accept, iters, acc);
     // ---- the bundled state is returned only if a step was accepted, it is finite and every point lies in front of its views
     double bad[1] = {0.};
     if (acc > 0) {

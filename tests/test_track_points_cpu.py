@@ -157,9 +157,13 @@ def test_capi_surface():
     assert _capi.TRACKPT_NAMES == tuple(k[len("RPE_TRACKPT_"):] for k in sorted(vals, key=vals.get))
     assert "rpe_triangulate_tracks" in _capi.EXPORTS
     assert (tm.LAMBDA0, tm.REL_TOL, tm.STEP_TOL) == (1e-3, 1e-6, 1e-9)
-    dev = open(os.path.join(ROOT, "relative_pose_estimation_amd", "csrc", "geom_device.h")).read()
+    csrc = os.path.join(ROOT, "relative_pose_estimation_amd", "csrc")
+    dev = open(os.path.join(csrc, "bundle_math.h")).read()             # the constants live with lm_loop, once
+    assert '#include "bundle_math.h"' in open(os.path.join(csrc, "geom_device.h")).read()
     for name, v in (("REFINE_LAMBDA0", "1e-3"), ("REFINE_REL_TOL", "1e-6"), ("REFINE_STEP_TOL", "1e-9")):
         assert re.search(rf"#define {name} {v}\b", dev), name
+        assert sum(len(re.findall(rf"#define {name}\b", open(os.path.join(csrc, f)).read())) for f in os.listdir(csrc)
+                   if f.endswith((".h", ".hip"))) == 1, name
 
 
 ACCURACY_VIEWS = (2, 3, 5, 8)

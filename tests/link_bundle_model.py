@@ -9,12 +9,11 @@ import math
 
 import numpy as np
 
+from tests import bundle_math_model as mm
 from tests import link_pose_model as lp
-from tests import refine_model as rf
 from tests import scale_model as sc
 
 BUNDLE_OK, BUNDLE_PAIR_FAILED, BUNDLE_TOO_FEW, BUNDLE_SKIPPED, BUNDLE_REJECTED = 0, 1, 2, 3, 4
-LAMBDA0, REL_TOL, STEP_TOL = lp.LAMBDA0, lp.REL_TOL, lp.STEP_TOL
 NCAM = 11
 
 
@@ -31,7 +30,7 @@ def rows(P, X):
         u = X[:, :2] / X[:, 2:3]; s = fa / X[:, 2]
         e[:, 0:2] = fa * (u - q[:, 0:2])
         JX[:, 0, 0] = s; JX[:, 0, 2] = -s * u[:, 0]; JX[:, 1, 1] = s; JX[:, 1, 2] = -s * u[:, 1]
-        b1, b2 = rf.tangent_basis(tA)
+        b1, b2 = mm.tangent_basis(tA)
         r, J = lp.residuals(RA, tA, X, q[:, 2:4], fa, True)
         e[:, 2:4] = r
         JC[:, 2:4, 0:3] = J[:, :, 0:3]
@@ -71,15 +70,7 @@ def blocks(e, JX, JC, lam):
     for r in range(6):                                        # rows added in order
         V += JX[:, r, :, None] * JX[:, r, None, :]
         gp += JX[:, r, :] * e[:, r, None]
-    for i in range(3):
-        V[:, i, i] = V[:, i, i] + lam * V[:, i, i]
-    v00, v01, v02, v11, v12, v22 = V[:, 0, 0], V[:, 0, 1], V[:, 0, 2], V[:, 1, 1], V[:, 1, 2], V[:, 2, 2]
-    c00 = v11 * v22 - v12 * v12; c01 = v02 * v12 - v01 * v22; c02 = v01 * v12 - v02 * v11
-    c11 = v00 * v22 - v02 * v02; c12 = v01 * v02 - v00 * v12; c22 = v00 * v11 - v01 * v01
-    det = (v00 * c00 + v01 * c01) + v02 * c02
-    with np.errstate(all="ignore"):
-        Vi = np.stack([np.stack([c00, c01, c02], 1), np.stack([c01, c11, c12], 1), np.stack([c02, c12, c22], 1)], 1) / det[:, None, None]
-    ok = (det > 0.0) & (np.abs(det) <= lp.DBL_MAX)
+    Vi, ok = mm.damped_inverse(V, lam)
     W = JC[:, 2, :, None] * JX[:, 2, None, :] + JC[:, 3, :, None] * JX[:, 3, None, :]
     W[:, 5:] = (JC[:, 4, :, None] * JX[:, 4, None, :] + JC[:, 5, :, None] * JX[:, 5, None, :])[:, 5:]
     return Vi, ok, gp, W
@@ -111,7 +102,7 @@ def schur_step(e, JX, JC, U, gc, lam, S):
     for k in range(NCAM):
         H[k, k] = (U[k, k] + lam * U[k, k]) - SW[k, k]
     H = np.triu(H) + np.triu(H, 1).T
-    d = lp.solve(H, gc - v, 0.0)
+    d = mm.solve(H, gc - v, 0.0)
     if d is None:
         return None
     u = gp.copy()
@@ -135,10 +126,10 @@ def dense_step(e, JX, JC, lam):
 
 
 def apply_step(P, X, d, dp):
-    b1, b2 = rf.tangent_basis(P["tA"])
+    b1, b2 = mm.tangent_basis(P["tA"])
     tA = (P["tA"] + d[3] * b1) + d[4] * b2
     tA = tA / math.sqrt((tA[0] * tA[0] + tA[1] * tA[1]) + tA[2] * tA[2])
-    return dict(RA=lp.rotate(d[0:3], P["RA"]), tA=tA, RC=lp.rotate(d[5:8], P["RC"]), tC=P["tC"] + d[8:11]), X + dp
+    return dict(RA=mm.rotate(d[0:3], P["RA"]), tA=tA, RC=mm.rotate(d[5:8], P["RC"]), tC=P["tC"] + d[8:11]), X + dp
 
 
 # ---------------------------------------------------------------- the problem (stage form)
@@ -151,7 +142,7 @@ def problem(obs, hc, X0, RA, tA, RC, tC, fa, fc):
 def bundle(P, max_iters=10, min_shared=1, order="forward"):
     """one problem as rpe_bundle_three_view returns it (solved form, S's frame): dict code, RA, tA, RC, tC, X (n, 3), counts,
     info, rms, decisions"""
-    S = lp.SUMS[order]
+    S = mm.SUMS[order]
     n, n3 = len(P["X0"]), int(P["hc"].sum())
     res = dict(code=BUNDLE_OK, RA=np.zeros((3, 3)), tA=np.zeros(3), RC=np.zeros((3, 3)), tC=np.zeros(3), X=np.zeros((n, 3)),
                counts=(n, n3), info=(BUNDLE_TOO_FEW, 0, 0, 0), rms=(0.0, 0.0), decisions=[], taken=False)
@@ -161,39 +152,29 @@ def bundle(P, max_iters=10, min_shared=1, order="forward"):
     cur = dict(P); X = P["X0"].copy()
     e, JX, JC = rows(cur, X)
     U, gc, cost0 = normal_sums(e, JC, S)
-    cost = cost0
-    iters = acc = 0
-    dec = []
+    lin = (e, JX, JC, U, gc)                                  # of the state; None once the state has moved
+    cost, iters, acc, dec = cost0, 0, 0, []
+    st = new = None                                           # the step (d_c, d_p) and the trial state (poses, X)
+
+    def step(lam):
+        nonlocal lin, st
+        if lin is None:
+            e, JX, JC = rows(cur, X)
+            lin = (e, JX, JC) + normal_sums(e, JC, S)[:2]
+        st = schur_step(*lin, lam, S)
+        return st is not None
+
+    def trial(lam):
+        nonlocal new
+        new = apply_step(cur, X, *st)
+        return float(S(point_costs(residuals_only(cur, *new))))
+
+    def accept():
+        nonlocal X, lin
+        cur.update(new[0]); X, lin = new[1], None
+
     if np.isfinite(cost0):
-        lam = LAMBDA0
-        need_lin = False
-        for _ in range(max_iters):
-            if need_lin:
-                e, JX, JC = rows(cur, X)
-                U, gc, _ = normal_sums(e, JC, S)
-                need_lin = False
-            iters += 1
-            st = schur_step(e, JX, JC, U, gc, lam, S)
-            ok = st is not None
-            if ok:
-                d, dp = st
-                poses, Xn = apply_step(cur, X, d, dp)
-                c1 = float(S(point_costs(residuals_only(cur, poses, Xn))))
-                ok = bool(np.isfinite(c1) and c1 < cost)
-            dec.append(ok)
-            if not ok:
-                lam = lam * 10.0
-                continue
-            drop, prev = cost - c1, cost
-            cur.update(poses); X = Xn; cost = c1
-            lam = lam / 10.0
-            acc += 1
-            need_lin = True
-            dn = d[0] * d[0]
-            for k in range(1, NCAM):
-                dn = dn + d[k] * d[k]
-            if drop <= REL_TOL * prev or math.sqrt(dn) <= STEP_TOL:
-                break
+        cost, iters, acc, dec = mm.lm_loop(cost0, max_iters, step, trial, lambda: mm.step_norm(st[0]), accept)
     take = acc > 0
     if take:
         fin = all(np.isfinite(cur[k]).all() for k in ("RA", "tA", "RC", "tC")) and np.isfinite(X).all()
@@ -293,7 +274,7 @@ def reduction_margin(results_fwd, results_rev):
             continue
         ka, kb, kp = ("RA", "RC", "X") if "RA" in f else ("R_a", "R_b", "points")
         ta, tb = ("tA", "tC") if "RA" in f else ("t_a", "t_b")
-        d = np.maximum(d, [abs(f["rms"][1] - r["rms"][1]), max(lp.rot_angle_deg(f[ka], r[ka]), lp.rot_angle_deg(f[kb], r[kb])),
+        d = np.maximum(d, [abs(f["rms"][1] - r["rms"][1]), max(mm.rot_angle_deg(f[ka], r[ka]), mm.rot_angle_deg(f[kb], r[kb])),
                            max(np.abs(f[ta] - r[ta]).max(), np.abs(f[tb] - r[tb]).max()), np.abs(f[kp] - r[kp]).max(),
                            abs(f["rms"][0] - r["rms"][0])])
     return ties, d

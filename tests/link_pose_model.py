@@ -15,10 +15,10 @@ import numpy as np
 from tests import camera_model as cm
 from tests import scale_model as sc
 from tests import structure_model as sm
+from tests.bundle_math_model import SUMS, lm_loop, rodrigues, rot_angle_deg, rotate, solve, step_norm  # noqa: F401
+from tests.bundle_math_model import dot3 as _dot, fdiv as _div, finite as _finite, fsqrt as _sqrt
 
 LINKPOSE_OK, LINKPOSE_PAIR_FAILED, LINKPOSE_TOO_FEW, LINKPOSE_NONE = 0, 1, 2, 3
-LAMBDA0, REL_TOL, STEP_TOL, SMALL_ANGLE = 1e-3, 1e-6, 1e-9, 1e-4      # rpe_refine_poses' conventions
-DBL_MAX = float(np.finfo(np.float64).max)
 
 
 # ---------------------------------------------------------------- real roots (the library's derivative chain)
@@ -107,28 +107,12 @@ def real_roots(c):
 
 
 # ---------------------------------------------------------------- the minimal solver
-def _dot(a, b):
-    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
-
-
 def _cross(a, b):
     return (a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0])
 
 
 def _sub(a, b):
     return (a[0] - b[0], a[1] - b[1], a[2] - b[2])
-
-
-def _sqrt(v):
-    return math.sqrt(v) if v >= 0.0 else math.nan
-
-
-def _div(a, b):
-    if b == 0.0:
-        if a == 0.0 or a != a:
-            return math.nan
-        return math.copysign(math.inf, a) * math.copysign(1.0, b)
-    return a / b
 
 
 def _frame(A1, A2, A3):
@@ -139,10 +123,6 @@ def _frame(A1, A2, A3):
     nc = _sqrt(_dot(c, c))
     e3 = tuple(_div(v, nc) for v in c)
     return e1, _cross(e3, e1), e3
-
-
-def _finite(v):
-    return abs(v) <= DBL_MAX
 
 
 def quartic(P, q):
@@ -208,81 +188,6 @@ def inlier_mask(R, t, X, q, thr2):
 
 
 # ---------------------------------------------------------------- polish
-def _fsum(a):
-    return np.sum(a, axis=0)
-
-
-def _rsum(a):
-    return np.sum(np.flip(a, axis=0), axis=0)
-
-
-SUMS = {"forward": _fsum, "reversed": _rsum}
-
-
-def rodrigues(w):
-    w = np.asarray(w, np.float64).reshape(3)
-    th2 = float(w @ w); th = np.sqrt(th2)
-    if th < SMALL_ANGLE:
-        A = 1.0 - th2 / 6.0; B = 0.5 - th2 / 24.0
-    else:
-        A = np.sin(th) / th; B = 2.0 * np.sin(0.5 * th) ** 2 / th2
-    W = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
-    return np.eye(3) + A * W + B * (np.outer(w, w) - th2 * np.eye(3))
-
-
-def rotate(w, R):
-    """exp([w]x) R as rpe_refine_poses forms it: I + A [w]x + B ([w][w]' - th2 I) entry by entry, then the row sums"""
-    w = [float(v) for v in w]
-    th2 = (w[0] * w[0] + w[1] * w[1]) + w[2] * w[2]; th = math.sqrt(th2)
-    if th < SMALL_ANGLE:
-        A = 1.0 - th2 / 6.0; B = 0.5 - th2 / 24.0
-    else:
-        sh = math.sin(0.5 * th); A = math.sin(th) / th; B = 2.0 * (sh * sh) / th2
-    E = [[B * (w[i] * w[j]) + (1.0 - B * th2 if i == j else 0.0) for j in range(3)] for i in range(3)]
-    E[0][1] -= A * w[2]; E[0][2] += A * w[1]
-    E[1][0] += A * w[2]; E[1][2] -= A * w[0]
-    E[2][0] -= A * w[1]; E[2][1] += A * w[0]
-    R = np.asarray(R, np.float64)
-    return np.array([[(E[i][0] * float(R[0, j]) + E[i][1] * float(R[1, j])) + E[i][2] * float(R[2, j]) for j in range(3)] for i in range(3)])
-
-
-def solve(H, g, lam):
-    """(H + lam diag H) d = -g by the library's Cholesky (rpe_refine_poses' solver for N parameters), or None when the
-    matrix is not positive definite"""
-    N = len(g)
-    L = [[float(H[i][j]) for j in range(N)] for i in range(N)]
-    for i in range(N):
-        L[i][i] = L[i][i] + lam * L[i][i]
-    ok = True
-    for j in range(N):
-        sj = L[j][j]
-        for k in range(j):
-            sj -= L[j][k] * L[j][k]
-        if not (sj > 0.0) or not math.isfinite(sj):
-            ok = False
-        dj = _sqrt(sj)
-        L[j][j] = dj
-        for i in range(j + 1, N):
-            v = L[i][j]
-            for k in range(j):
-                v -= L[i][k] * L[j][k]
-            L[i][j] = _div(v, dj)
-    if not ok:
-        return None
-    y = [0.0] * N; d = [0.0] * N
-    for i in range(N):
-        v = -float(g[i])
-        for k in range(i):
-            v -= L[i][k] * y[k]
-        y[i] = _div(v, L[i][i])
-    for i in range(N - 1, -1, -1):
-        v = y[i]
-        for k in range(i + 1, N):
-            v -= L[k][i] * d[k]
-        d[i] = _div(v, L[i][i])
-    return np.array(d)
-
-
 def residuals(R, t, X, q, scale, jac=False):
     """r (m, 2) in pixels and, with jac, J (m, 2, 6): columns w0 w1 w2 (R <- exp([w]x) R), d0 d1 d2 (t <- t + d)"""
     a = np.stack([(R[k, 0] * X[:, 0] + R[k, 1] * X[:, 1]) + R[k, 2] * X[:, 2] for k in range(3)], 1)   # the score's row order
@@ -306,42 +211,37 @@ def lm(R0, t0, X, q, scale, max_iters, order="forward"):
     """the iteration over the fixed set (X, q): dict R, t, cost0, cost, iters, accepted, decisions"""
     S = SUMS[order]
     R = np.array(R0, np.float64); t = np.array(t0, np.float64)
-    r, J = residuals(R, t, X, q, scale, True)
-    cost0 = cost = float(S((r * r).sum(1)))
-    out = dict(R=R, t=t, cost0=cost0, cost=cost, iters=0, accepted=0, decisions=[])
+    lin = residuals(R, t, X, q, scale, True)           # (r, J) of the state; None once the state has moved
+    cost0 = float(S((lin[0] * lin[0]).sum(1)))
+    out = dict(R=R, t=t, cost0=cost0, cost=cost0, iters=0, accepted=0, decisions=[])
     if not np.isfinite(cost0):
         return out
-    lam = LAMBDA0
-    need_lin = False
     iu = np.triu_indices(6)
-    for _ in range(max_iters):
-        if need_lin:
-            r, J = residuals(R, t, X, q, scale, True)
-            need_lin = False
-        out["iters"] += 1
+    d = new = None
+
+    def step(lam):
+        nonlocal lin, d
+        if lin is None:
+            lin = residuals(R, t, X, q, scale, True)
+        r, J = lin
         H = np.zeros((6, 6))
         H[iu] = S((J[:, :, iu[0]] * J[:, :, iu[1]]).sum(1))
         H = np.triu(H) + np.triu(H, 1).T
-        g = S((J * r[:, :, None]).sum(1))
-        d = solve(H, g, lam)
-        ok = d is not None
-        if ok:
-            Rn = rotate(d[:3], R); tn = t + d[3:]
-            rn = residuals(Rn, tn, X, q, scale)
-            c1 = float(S((rn * rn).sum(1)))
-            ok = bool(np.isfinite(c1) and c1 < cost)
-        out["decisions"].append(ok)
-        if not ok:
-            lam = lam * 10.0
-            continue
-        dec, prev = cost - c1, cost
-        R, t, cost = Rn, tn, c1
-        lam = lam / 10.0
-        out["accepted"] += 1
-        need_lin = True
-        if dec <= REL_TOL * prev or math.sqrt(((((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2]) + d[3] * d[3]) + d[4] * d[4]) + d[5] * d[5]) <= STEP_TOL:
-            break
-    out.update(R=R, t=t, cost=cost)
+        d = solve(H, S((J * r[:, :, None]).sum(1)), lam)
+        return d is not None
+
+    def trial(lam):
+        nonlocal new
+        new = (rotate(d[:3], R), t + d[3:])
+        rn = residuals(new[0], new[1], X, q, scale)
+        return float(S((rn * rn).sum(1)))
+
+    def accept():
+        nonlocal R, t, lin
+        (R, t), lin = new, None
+
+    cost, iters, acc, dec = lm_loop(cost0, max_iters, step, trial, lambda: step_norm(d), accept)
+    out.update(R=R, t=t, cost=cost, iters=iters, accepted=acc, decisions=dec)
     return out
 
 
@@ -469,13 +369,6 @@ def reduction_margin(run, x1, x2, focal, links, subsets, **kw):
         d_rms = max(d_rms, abs(f["rms"][1] - r["rms"][1])); d_rms0 = max(d_rms0, abs(f["rms"][0] - r["rms"][0]))
         d_R = max(d_R, rot_angle_deg(f["R"], r["R"])); d_t = max(d_t, float(np.abs(f["t"] - r["t"]).max()))
     return fwd, ties, d_rms, d_R, d_t, d_rms0
-
-
-def rot_angle_deg(Ra, Rb):
-    """angle between two rotations, accurate for tiny angles (from the antisymmetric part)"""
-    M = np.asarray(Ra, np.float64).reshape(3, 3).T @ np.asarray(Rb, np.float64).reshape(3, 3)
-    v = 0.5 * np.array([M[2, 1] - M[1, 2], M[0, 2] - M[2, 0], M[1, 0] - M[0, 1]])
-    return float(np.degrees(np.arctan2(np.sqrt(v @ v), 0.5 * (np.trace(M) - 1.0))))
 
 
 # ---------------------------------------------------------------- physics bands

@@ -16,54 +16,16 @@ np.linalg.solve; used by test_refine_cpu.py and test_gpu_refine.py.
 import numpy as np
 
 from tests import structure_model as sm
+from tests.bundle_math_model import REL_TOL, STEP_TOL, SUMS, lm_loop, step_norm
+from tests.bundle_math_model import rodrigues, rot_angle_deg, rotate_np, tangent_basis, vec_angle_deg
 
-LAMBDA0 = 1e-3
-REL_TOL = 1e-6
-STEP_TOL = 1e-9
-SMALL_ANGLE = 1e-4
 MIN_RESIDUALS = 6
 REFINE_OK, REFINE_SKIPPED, REFINE_REJECTED = 0, 1, 2
 
 
-def _fsum(a, axis=0):
-    return np.sum(a, axis=axis)
-
-
-def _rsum(a, axis=0):
-    """the same sum with the terms in reversed order (np.sum's pairwise tree then pairs different neighbours)"""
-    return np.sum(np.flip(a, axis=axis), axis=axis)
-
-
-def _lsum(a, axis=0):
-    return np.sum(np.asarray(a, np.longdouble), axis=axis).astype(np.float64)
-
-
-SUMS = {"forward": _fsum, "reversed": _rsum, "longdouble": _lsum}
-
-
-def tangent_basis(t):
-    t = np.asarray(t, np.float64).reshape(3)
-    k = int(np.argmin(np.abs(t)))                      # first index of the minimum
-    e = np.zeros(3); e[k] = 1.0
-    b1 = np.cross(t, e)
-    b1 = b1 / np.sqrt(b1 @ b1)
-    return b1, np.cross(t, b1)
-
-
-def rodrigues(w):
-    w = np.asarray(w, np.float64).reshape(3)
-    th2 = float(w @ w); th = np.sqrt(th2)
-    if th < SMALL_ANGLE:
-        A = 1.0 - th2 / 6.0; B = 0.5 - th2 / 24.0
-    else:
-        A = np.sin(th) / th; B = 2.0 * np.sin(0.5 * th) ** 2 / th2
-    W = np.array([[0, -w[2], w[1]], [w[2], 0, -w[0]], [-w[1], w[0], 0]])
-    return np.eye(3) + A * W + B * (np.outer(w, w) - th2 * np.eye(3))
-
-
 def apply_step(R, t, d, basis=None):
     b1, b2 = basis if basis is not None else tangent_basis(t)
-    Rn = rodrigues(d[:3]) @ R
+    Rn = rotate_np(d[:3], R)
     tn = t + d[3] * b1 + d[4] * b2
     return Rn, tn / np.sqrt(tn @ tn)
 
@@ -107,21 +69,25 @@ def lm(R0, t0, x1, x2, scale, max_iters, order="forward", rel_tol=REL_TOL, step_
     iters, accepted, history (cost after every iteration), decisions (True = accepted, per iteration)."""
     S = SUMS[order]
     R = np.asarray(R0, np.float64).reshape(3, 3).copy(); t = np.asarray(t0, np.float64).reshape(3).copy()
-    basis = tangent_basis(t)
-    r, J = residuals(R, t, x1, x2, scale, True, basis)
-    cost0 = cost = float(S(r * r))
-    out = dict(R=R, t=t, cost0=cost0, cost=cost, iters=0, accepted=0, history=[cost0], decisions=[])
+    iu = np.triu_indices(5)
+
+    def linearise():
+        basis = tangent_basis(t)
+        return (basis,) + residuals(R, t, x1, x2, scale, True, basis)
+
+    lin = linearise()                                  # (basis, r, J) of the state; None once the state has moved
+    cost0 = float(S(lin[1] * lin[1]))
+    out = dict(R=R, t=t, cost0=cost0, cost=cost0, iters=0, accepted=0, history=[cost0], decisions=[])
     if not np.isfinite(cost0):
         return out
-    lam = LAMBDA0
-    need_lin = False
-    iu = np.triu_indices(5)
-    for _ in range(max_iters):
-        if need_lin:
-            basis = tangent_basis(t)
-            r, J = residuals(R, t, x1, x2, scale, True, basis)
-            need_lin = False
-        out["iters"] += 1
+    d = new = None
+    taken = []                                         # the cost of every accepted trial
+
+    def step(lam):
+        nonlocal lin, d
+        if lin is None:
+            lin = linearise()
+        _, r, J = lin
         H = np.zeros((5, 5))
         H[iu] = S(J[:, iu[0]] * J[:, iu[1]])
         H = np.triu(H) + np.triu(H, 1).T
@@ -130,28 +96,26 @@ def lm(R0, t0, x1, x2, scale, max_iters, order="forward", rel_tol=REL_TOL, step_
         try:
             np.linalg.cholesky(A)
             d = np.linalg.solve(A, -g)
-            ok = bool(np.isfinite(d).all())
+            return bool(np.isfinite(d).all())
         except np.linalg.LinAlgError:
-            ok = False
-        if ok:
-            Rn, tn = apply_step(R, t, d, basis)
-            rn = residuals(Rn, tn, x1, x2, scale)
-            c1 = float(S(rn * rn))
-            ok = bool(np.isfinite(c1) and c1 < cost)
-        out["decisions"].append(ok)
-        if not ok:
-            lam = lam * 10.0
-            out["history"].append(cost)
-            continue
-        dec, prev = cost - c1, cost
-        R, t, cost = Rn, tn, c1
-        lam = lam / 10.0
-        out["accepted"] += 1
-        need_lin = True
-        out["history"].append(cost)
-        if dec <= rel_tol * prev or np.sqrt(d @ d) <= step_tol:
-            break
-    out.update(R=R, t=t, cost=cost)
+            return False
+
+    def trial(lam):
+        nonlocal new
+        Rn, tn = apply_step(R, t, d, lin[0])
+        rn = residuals(Rn, tn, x1, x2, scale)
+        new = (Rn, tn, float(S(rn * rn)))
+        return new[2]
+
+    def accept():
+        nonlocal R, t, lin
+        R, t, lin = new[0], new[1], None
+        taken.append(new[2])
+
+    cost, iters, acc, dec = lm_loop(cost0, max_iters, step, trial, lambda: step_norm(d), accept, rel_tol, step_tol)
+    for ok in dec:
+        out["history"].append(taken.pop(0) if ok else out["history"][-1])
+    out.update(R=R, t=t, cost=cost, iters=iters, accepted=acc, decisions=dec)
     return out
 
 
@@ -192,19 +156,6 @@ def converge(R, t, x1, x2, scale=1.0):
     return lm(R, t, x1, x2, scale, 200, rel_tol=np.finfo(np.float64).eps, step_tol=np.finfo(np.float64).eps)
 
 
-def rot_angle_deg(Ra, Rb):
-    """angle between two rotations, accurate for tiny angles (from the antisymmetric part, not from arccos of the trace)"""
-    M = np.asarray(Ra, np.float64).reshape(3, 3).T @ np.asarray(Rb, np.float64).reshape(3, 3)
-    v = 0.5 * np.array([M[2, 1] - M[1, 2], M[0, 2] - M[2, 0], M[1, 0] - M[0, 1]])
-    return float(np.degrees(np.arctan2(np.sqrt(v @ v), 0.5 * (np.trace(M) - 1.0))))
-
-
-def vec_angle_deg(a, b):
-    a = np.asarray(a, np.float64).reshape(3); b = np.asarray(b, np.float64).reshape(3)
-    c = np.cross(a, b)
-    return float(np.degrees(np.arctan2(np.sqrt(c @ c), a @ b)))
-
-
 # ---- scenes and the reduction-order margin shared by test_refine_cpu.py and test_gpu_refine.py
 ACCURACY_PAIRS, ACCURACY_CFG = 48, 8         # synthetic.make_batch(ACCURACY_PAIRS, K_vga, cfg=ACCURACY_CFG)
 NOISY_SEED = 2024
@@ -234,7 +185,8 @@ def noisy_scenes(K, B=16, n=300, sigma=0.5, outlier_frac=0.2, seed=NOISY_SEED):
         ax = rng.normal(size=3); ax /= np.linalg.norm(ax)
         ang = np.radians(rng.uniform(0.5, 2.0))
         R0 = rodrigues(ang * ax) @ R
-        b1, b2 = tangent_basis(t)
+        e = np.zeros(3); e[np.argmin(np.abs(t))] = 1.0                  # a tangent pair at t, in the numpy form the scenes
+        b1 = np.cross(t, e); b1 = b1 / np.sqrt(b1 @ b1); b2 = np.cross(t, b1)   # were drawn with: they stay what they were
         ph = rng.uniform(0, 2 * np.pi)
         t0 = np.cos(ang) * t + np.sin(ang) * (np.cos(ph) * b1 + np.sin(ph) * b2)
         out.append(dict(R_true=R, t_true=t, R0=R0, t0=t0 / np.linalg.norm(t0), pts1=p1.astype(np.float32),

@@ -7,8 +7,9 @@ plain and with the host sanitizers.
 Every comparison is bit for bit (the float64 words as integers); two NaNs count as equal whatever their payload.
 
 References: window_bundle_model.view_rows and point_blocks (every case), link_bundle_model.rows and blocks (the cases in
-front of the camera, three views: elsewhere that model differs in the sign of a zero, as its docstring says), and for the
-loop a restatement of the rule from the comment above refine_lm (geom_device.h)."""
+front of the camera, three views: elsewhere that model differs in the sign of a zero, as its docstring says), and
+tests/bundle_math_model.py, the header's Python twin: its damped_inverse, and for the loop its lm_loop, the one the five
+models run."""
 import math
 import os
 import struct
@@ -18,9 +19,8 @@ import types
 import numpy as np
 import pytest
 
+from tests import bundle_math_model as mm
 from tests import link_bundle_model as lb
-from tests import link_pose_model as lp
-from tests import refine_model as rf
 from tests import window_bundle_model as wb
 
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -64,12 +64,12 @@ def _views():
     for i in range(n):
         ax = rng.normal(size=3); ax /= np.linalg.norm(ax)
         ang = rng.uniform(-1.0, 1.0) * 10.0 ** rng.uniform(-7.0, -1.0) if i % 3 == 0 else rng.uniform(-3.1, 3.1)
-        R[i] = rf.rodrigues(ang * ax)
+        R[i] = mm.rodrigues(ang * ax)
     depth = rng.uniform(2.0, 20.0, n)
     y = np.stack([depth * rng.uniform(-0.5, 0.5, n), depth * rng.uniform(-0.5, 0.5, n), depth], 1)
     X = np.einsum("nji,nj->ni", R, y - t)                                   # R'(y - t): depth 2 .. 20 up to rounding
     q = rng.uniform(-0.5, 0.5, (n, 2)); scale = rng.uniform(400.0, 1200.0, n)
-    I = np.eye(3); Rc = rf.rodrigues([0.3, -0.2, 0.1])
+    I = np.eye(3); Rc = mm.rodrigues([0.3, -0.2, 0.1])
     crafted = [
         (I, np.zeros(3), np.array([0.7, -0.4, 5.0]), 800.0, np.array([0.1, -0.1])),          # the window's position 0
         (I, np.zeros(3), np.array([0.0, 0.0, 3.0]), 600.0, np.array([0.02, -0.01])),         # on the optical axis
@@ -226,31 +226,48 @@ def test_block_equals_the_link_model(block_out):
         assert _same(got[:, 6:9], gp).all() and (got[:, 15] == ok).all() and _same(got[:, 9:15], _tri(Vi)).all(), l
 
 
+def test_damped_inverse_equals_the_program(block_out):
+    """bundle_math_model.damped_inverse, which both bundle models call, on the program's own V of every case: the Vi and
+    the verdict of bm_damped_inverse, the singular block and the one with an infinite entry included"""
+    lam = BLOCKS[2]
+    for l in LAMBDAS:
+        idx = np.flatnonzero(lam == l)
+        assert len(idx)
+        v = block_out[idx, 0:6]
+        V = np.stack([v[:, [0, 1, 2]], v[:, [1, 3, 4]], v[:, [2, 4, 5]]], 1)
+        Vi, ok = mm.damped_inverse(V, l)
+        assert (block_out[idx, 15] == ok).all() and _same(block_out[idx, 9:15], _tri(Vi)).all(), l
+    assert lam[0] == 0.0 and lam[1] == 0.0                                  # the two crafted blocks were among them
+
+
 # ---------------------------------------------------------------- the loop
 def lm_reference(max_iters, cost, script):
-    """The rule as the comment above refine_lm states it: a missing step or a trial that does not strictly lower the cost
-    multiplies lambda by 10; an accepted step divides it by 10, moves the cost and stops the loop on either tolerance; the
-    state is linearised again only when another iteration follows an accepted step.  Returns (iters, acc, cost, accepts,
-    the calls in order)"""
-    lam, iters, acc, calls, need_lin = lp.LAMBDA0, 0, 0, [], False
-    for it in range(max_iters):
-        has_step, c1, dn = script[it]
-        if need_lin:
-            calls.append(("L", None)); need_lin = False
-        iters += 1
+    """bundle_math_model.lm_loop, the loop the five models run, over hooks that read the script and record their calls in
+    the program's arrangement (refine_lm's: the state is linearised again in the step hook that follows an accepted step).
+    Returns (iters, acc, cost, accepts, the calls in order)"""
+    calls, it, moved = [], -1, False
+
+    def step(lam):
+        nonlocal it, moved
+        it += 1
+        if moved:
+            calls.append(("L", None)); moved = False
         calls.append(("S", lam))
-        if not has_step:
-            lam = lam * 10.0
-            continue
+        return bool(script[it][0])
+
+    def trial(lam):
         calls.append(("T", lam))
-        if math.isfinite(c1) and c1 < cost:
-            calls += [("N", None), ("A", None)]
-            dec, prev = cost - c1, cost
-            cost = c1; lam = lam / 10.0; acc += 1; need_lin = True
-            if dec <= lp.REL_TOL * prev or dn <= lp.STEP_TOL:
-                break
-        else:
-            lam = lam * 10.0
+        return script[it][1]
+
+    def step_norm():
+        calls.append(("N", None))
+        return script[it][2]
+
+    def accept():
+        nonlocal moved
+        calls.append(("A", None)); moved = True
+
+    cost, iters, acc, _ = mm.lm_loop(cost, max_iters, step, trial, step_norm, accept)
     return iters, acc, cost, sum(c[0] == "A" for c in calls), calls
 
 

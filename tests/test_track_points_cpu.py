@@ -8,6 +8,7 @@ import re
 import numpy as np
 import pytest
 
+from tests import bundle_math_model as mm
 from tests import camera_model as cm
 from tests import track_point_cases as tc
 from tests import track_point_model as tm
@@ -156,11 +157,12 @@ def test_capi_surface():
         assert getattr(_capi, name[4:]) == v == getattr(tm, name[len("RPE_TRACKPT_"):])
     assert _capi.TRACKPT_NAMES == tuple(k[len("RPE_TRACKPT_"):] for k in sorted(vals, key=vals.get))
     assert "rpe_triangulate_tracks" in _capi.EXPORTS
-    assert (tm.LAMBDA0, tm.REL_TOL, tm.STEP_TOL) == (1e-3, 1e-6, 1e-9)
     csrc = os.path.join(ROOT, "relative_pose_estimation_amd", "csrc")
-    dev = open(os.path.join(csrc, "bundle_math.h")).read()             # the constants live with lm_loop, once
+    dev = open(os.path.join(csrc, "bundle_math.h")).read()             # the constants live with lm_loop, once on either side
     assert '#include "bundle_math.h"' in open(os.path.join(csrc, "geom_device.h")).read()
-    for name, v in (("REFINE_LAMBDA0", "1e-3"), ("REFINE_REL_TOL", "1e-6"), ("REFINE_STEP_TOL", "1e-9")):
+    for name, v, model in (("REFINE_LAMBDA0", "1e-3", mm.LAMBDA0), ("REFINE_REL_TOL", "1e-6", mm.REL_TOL),
+                           ("REFINE_STEP_TOL", "1e-9", mm.STEP_TOL)):
+        assert model == float(v), name
         assert re.search(rf"#define {name} {v}\b", dev), name
         assert sum(len(re.findall(rf"#define {name}\b", open(os.path.join(csrc, f)).read())) for f in os.listdir(csrc)
                    if f.endswith((".h", ".hip"))) == 1, name

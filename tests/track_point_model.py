@@ -8,51 +8,16 @@ import math
 import numpy as np
 
 from tests import camera_model as cm
+from tests.bundle_math_model import dot3, lm_loop, solve, step_norm
 
 OK, TOO_FEW, DEGENERATE, BEHIND, OUTLIERS, LOW_PARALLAX = range(6)
-LAMBDA0, REL_TOL, STEP_TOL = 1e-3, 1e-6, 1e-9          # rpe_refine_poses' (REFINE_LAMBDA0, REFINE_REL_TOL, REFINE_STEP_TOL)
-
-
-def dot3(a, b):
-    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
 
 
 def solve3(H, g, lam):
-    """(H + lam diag H) d = -g, H the upper triangle (6 entries, row-major): the Cholesky of rpe_refine_poses.  None when
-    not positive definite"""
-    L = [[0.0] * 3 for _ in range(3)]
-    q = 0
-    for i in range(3):
-        for j in range(i, 3):
-            L[i][j] = H[q]; L[j][i] = H[q]; q += 1
-    for i in range(3):
-        L[i][i] = L[i][i] + lam * L[i][i]
-    for j in range(3):
-        s = L[j][j]
-        for k in range(j):
-            s -= L[j][k] * L[j][k]
-        if not (s > 0.0) or not math.isfinite(s):
-            return None
-        dj = math.sqrt(s)
-        L[j][j] = dj
-        for i in range(j + 1, 3):
-            v = L[i][j]
-            for k in range(j):
-                v -= L[i][k] * L[j][k]
-            L[i][j] = v / dj
-    y = [0.0] * 3
-    for i in range(3):
-        v = -g[i]
-        for k in range(i):
-            v -= L[i][k] * y[k]
-        y[i] = v / L[i][i]
-    d = [0.0] * 3
-    for i in (2, 1, 0):
-        v = y[i]
-        for k in range(i + 1, 3):
-            v -= L[k][i] * d[k]
-        d[i] = v / L[i][i]
-    return d
+    """(H + lam diag H) d = -g, H the upper triangle (6 entries, row-major): the Cholesky of rpe_refine_poses (the shared
+    scalar solve).  None when not positive definite"""
+    d = solve([[H[0], H[1], H[2]], [H[1], H[3], H[4]], [H[2], H[4], H[5]]], g, lam)
+    return None if d is None else d.tolist()
 
 
 class View:
@@ -122,26 +87,24 @@ def solve_round(views, max_iters):
     if lin is None:
         return BEHIND, X, 0
     cost, H, g = lin
-    lam = LAMBDA0
-    iters = 0
-    for _ in range(max_iters):
-        iters += 1
+    d = new = None                                          # the step and the trial (point, its linearisation)
+
+    def step(lam):
+        nonlocal d
         d = solve3(H, g, lam)
-        if d is None:
-            lam = lam * 10.0
-            continue
+        return d is not None
+
+    def trial(lam):                                         # linearised as it is costed: an accepted one needs no second pass
+        nonlocal new
         Xn = [X[0] + d[0], X[1] + d[1], X[2] + d[2]]
-        trial = linearise(views, Xn)
-        if trial is not None and math.isfinite(trial[0]) and trial[0] < cost:
-            dec = cost - trial[0]; prev = cost
-            dn = math.sqrt((d[0] * d[0] + d[1] * d[1]) + d[2] * d[2])
-            X = Xn
-            cost, H, g = trial
-            lam = lam / 10.0
-            if dec <= REL_TOL * prev or dn <= STEP_TOL:
-                break
-        else:
-            lam = lam * 10.0
+        new = (Xn, linearise(views, Xn))
+        return math.inf if new[1] is None else new[1][0]    # a view without positive depth vetoes the trial
+
+    def accept():
+        nonlocal X, H, g
+        X, (_, H, g) = new
+
+    iters = lm_loop(cost, max_iters, step, trial, lambda: step_norm(d), accept)[1]
     return None, X, iters
 
 

@@ -10,32 +10,11 @@ import math
 
 import numpy as np
 
+from tests import bundle_math_model as mm
 from tests import camera_model as cm
-from tests import link_pose_model as lp
 
 WINDOW_OK, WINDOW_NO_BASELINE, WINDOW_TOO_FEW, WINDOW_REJECTED = 0, 1, 2, 3
 MAX_VIEWS = 8
-LAMBDA0, REL_TOL, STEP_TOL = lp.LAMBDA0, lp.REL_TOL, lp.STEP_TOL
-
-
-def dot3(a, b):
-    return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]
-
-
-def tangent_basis(t):
-    """refine_basis of rpe_refine_poses: b1 = normalise(t x e_k), k the axis of smallest |t_k| (lowest on ties), b2 = t x b1"""
-    t = [float(v) for v in t]
-    k, m = 0, abs(t[0])
-    if abs(t[1]) < m:
-        k, m = 1, abs(t[1])
-    if abs(t[2]) < m:
-        k = 2
-    e = [1.0 if i == k else 0.0 for i in range(3)]
-    cross = lambda a, b: [a[1] * b[2] - a[2] * b[1], a[2] * b[0] - a[0] * b[2], a[0] * b[1] - a[1] * b[0]]
-    b1 = cross(t, e)
-    n = math.sqrt((b1[0] * b1[0] + b1[1] * b1[1]) + b1[2] * b1[2])
-    b1 = [v / n for v in b1]
-    return np.array(b1), np.array(cross(t, b1))
 
 
 # ---------------------------------------------------------------- the points of a window
@@ -125,7 +104,7 @@ class State:
 def linearise(st):
     """per position: e (n, 2), Jc (n, 2, 6) (the anchor's in its own parameters), JX (n, 2, 3); rows of points that do not see
     the position are not to be used"""
-    b1, b2 = tangent_basis(st.t[st.A])
+    b1, b2 = mm.tangent_basis(st.t[st.A])
     rows = []
     for p in range(st.W):
         e, _, J, JX = view_rows(p, st.Q[p], st.t[p], st.X, st.x[:, p], st.f[:, p])
@@ -159,14 +138,7 @@ def point_blocks(st, rows, lam):
                 gp[m] += JX[m, r, :] * e[m, r, None]
             if p:
                 Wm[p] = J[:, 0, :, None] * JX[:, 0, None, :] + J[:, 1, :, None] * JX[:, 1, None, :]
-        for i in range(3):
-            V[:, i, i] = V[:, i, i] + lam * V[:, i, i]
-        v00, v01, v02, v11, v12, v22 = V[:, 0, 0], V[:, 0, 1], V[:, 0, 2], V[:, 1, 1], V[:, 1, 2], V[:, 2, 2]
-        c00 = v11 * v22 - v12 * v12; c01 = v02 * v12 - v01 * v22; c02 = v01 * v12 - v02 * v11
-        c11 = v00 * v22 - v02 * v02; c12 = v01 * v02 - v00 * v12; c22 = v00 * v11 - v01 * v01
-        det = (v00 * c00 + v01 * c01) + v02 * c02
-        Vi = np.stack([np.stack([c00, c01, c02], 1), np.stack([c01, c11, c12], 1), np.stack([c02, c12, c22], 1)], 1) / det[:, None, None]
-    ok = (det > 0.0) & (np.abs(det) <= lp.DBL_MAX)
+    Vi, ok = mm.damped_inverse(V, lam)
     return Vi, ok, gp, Wm
 
 
@@ -208,7 +180,7 @@ def schur_step(st, rows, lam, S):
     if not ok.all():
         return None
     H, g = reduced_system(st, rows, Vi, gp, Wm, lam, S)
-    d = lp.solve(H, g, 0.0)
+    d = mm.solve(H, g, 0.0)
     if d is None:
         return None
     u = gp.copy()
@@ -244,10 +216,10 @@ def dense_step(st, rows, lam):
 
 def apply_step(st, d, dp):
     Q = st.Q.copy(); t = st.t.copy()
-    b1, b2 = tangent_basis(st.t[st.A])
+    b1, b2 = mm.tangent_basis(st.t[st.A])
     for p in range(1, st.W):
         o = st.off[p]
-        Q[p] = lp.rotate(d[o:o + 3], st.Q[p])
+        Q[p] = mm.rotate(d[o:o + 3], st.Q[p])
         if p == st.A:
             tn = (st.t[p] + d[o + 3] * b1) + d[o + 4] * b2
             t[p] = tn / math.sqrt((tn[0] * tn[0] + tn[1] * tn[1]) + tn[2] * tn[2])
@@ -269,7 +241,7 @@ def gauge(R, T):
                     Q[p, r, c] = (R[p, r, 0] * R[0, c, 0] + R[p, r, 1] * R[0, c, 1]) + R[p, r, 2] * R[0, c, 2]
             for r in range(3):
                 s[p, r] = T[p, r] - ((Q[p, r, 0] * T[0, 0] + Q[p, r, 1] * T[0, 1]) + Q[p, r, 2] * T[0, 2])
-            n2[p] = dot3(s[p], s[p])
+            n2[p] = mm.dot3(s[p], s[p])
     A, best = 1, n2[1]
     for p in range(2, W):
         if n2[p] > best:
@@ -281,7 +253,7 @@ def bundle_window(tracks, obs_xy_n, obs_f, points0, R_abs, T_abs, frames, obs_us
                   min_obs=8, max_iters=10, order="forward"):
     """one window as rpe_bundle_windows returns it: dict code, R (W, 3, 3), T (W, 3), points (n, 3), point_track, counts, info,
     rms, decisions"""
-    S = lp.SUMS[order]
+    S = mm.SUMS[order]
     frames = [int(f) for f in frames]
     W = len(frames)
     R = np.asarray(R_abs, np.float64).reshape(-1, 3, 3)[frames]; T = np.asarray(T_abs, np.float64).reshape(-1, 3)[frames]
@@ -311,34 +283,25 @@ def bundle_window(tracks, obs_xy_n, obs_f, points0, R_abs, T_abs, frames, obs_us
     st = State(Q, t, X, seen, x, f, A)
     with np.errstate(all="ignore"):
         cost0 = float(S(point_costs(st)))
-    cost = cost0
-    iters = acc = 0
-    dec = []
+    cost, iters, acc, dec = cost0, 0, 0, []
+    sol = new = None                                                  # the step (d_c, d_p) and the trial state (Q, t, X)
+
+    def step(lam):                                                    # linearised in every iteration, moved or not
+        nonlocal sol
+        sol = schur_step(st, linearise(st), lam, S)
+        return sol is not None
+
+    def trial(lam):
+        nonlocal new
+        new = apply_step(st, *sol)
+        with np.errstate(all="ignore"):
+            return float(S(point_costs(st, *new)))
+
+    def accept():
+        st.Q, st.t, st.X = new
+
     if math.isfinite(cost0):
-        lam = LAMBDA0
-        for _ in range(max_iters):
-            iters += 1
-            rows = linearise(st)
-            step = schur_step(st, rows, lam, S)
-            ok = step is not None
-            if ok:
-                d, dp = step
-                Qn, tn, Xn = apply_step(st, d, dp)
-                with np.errstate(all="ignore"):
-                    c1 = float(S(point_costs(st, Qn, tn, Xn)))
-                ok = bool(math.isfinite(c1) and c1 < cost)
-            dec.append(ok)
-            if not ok:
-                lam = lam * 10.0
-                continue
-            drop, prev = cost - c1, cost
-            st.Q, st.t, st.X = Qn, tn, Xn
-            cost = c1; lam = lam / 10.0; acc += 1
-            dn = d[0] * d[0]
-            for k in range(1, st.N):
-                dn = dn + d[k] * d[k]
-            if drop <= REL_TOL * prev or math.sqrt(dn) <= STEP_TOL:
-                break
+        cost, iters, acc, dec = mm.lm_loop(cost0, max_iters, step, trial, lambda: mm.step_norm(sol[0]), accept)
     take = acc > 0
     if take:
         fin = bool(np.isfinite(st.Q).all() and np.isfinite(st.t).all() and np.isfinite(st.X).all())
@@ -385,7 +348,7 @@ def tied(f, r):
 
 def differences(a, b):
     """[rms_after px, rotation degrees, translation, point coordinate, rms_before px] between two results of one window"""
-    rot = max([lp.rot_angle_deg(x, y) for x, y in zip(a["R"], b["R"])])
+    rot = max([mm.rot_angle_deg(x, y) for x, y in zip(a["R"], b["R"])])
     dp = np.abs(np.asarray(a["points"]) - np.asarray(b["points"])).max() if len(a["points"]) else 0.0
     return np.array([abs(a["rms"][1] - b["rms"][1]), rot, np.abs(np.asarray(a["T"]) - np.asarray(b["T"])).max(), dp,
                      abs(a["rms"][0] - b["rms"][0])])
@@ -410,7 +373,7 @@ def pose_errors(R, T, R_true, T_true):
     l, lt = math.sqrt(n2[At]), math.sqrt(n2t[At])
     rot, cen = [], []
     for p in range(1, len(Q)):
-        rot.append(lp.rot_angle_deg(Q[p], Qt[p]))
+        rot.append(mm.rot_angle_deg(Q[p], Qt[p]))
         c = -Q[p].T @ s[p] / l; ct = -Qt[p].T @ st_[p] / lt
         cen.append(float(np.linalg.norm(c - ct)))
     return np.array(rot), np.array(cen)

@@ -873,6 +873,100 @@ int rpe_bundle_windows(rpe_handle *h, int n_tracks, const int32_t *track_start, 
                        double *R_out, double *T_out, double *points, int32_t *point_track, int32_t *counts, int32_t *info,
                        double *rms);
 
+/* ------------------------------------------------------------ pose graphs */
+/* Pose-graph optimisation (NOT in the reference): the poses of a chain are moved onto relative-pose measurements between
+ * its frames, so that a revisit (a loop edge) takes out the drift the chain has integrated.  A stage-form call over the
+ * caller's arrays: n_frames poses R_abs[9 * n_frames], T_abs[3 * n_frames] in the convention of the chain, X_f = R_f X +
+ * T_f; graphs in CSR form: graph g is the frames graph_frame[graph_start[g] .. graph_start[g + 1]), F of them, distinct;
+ * graphs may share frames, each is solved on its own from the caller's poses; fixed[graph_start[n_graphs]] bytes laid out
+ * like graph_frame (NULL: none; not 0: the frame does not move; position 0 of every graph is fixed whatever its byte);
+ * edges in CSR form: graph g owns the edges edge_start[g] .. edge_start[g + 1); edge e joins the frames edge_i[e] and
+ * edge_j[e] (frame indices; both frames of its graph, different) with the measurement X_j = M X_i + m, M = edge_R[9 e ..],
+ * m = edge_t[3 e ..], the weights (w_rot, w_trans) = edge_w[2 e ..] and edge_kind[e]: RPE_EDGE_METRIC (m on the graph's
+ * scale) or RPE_EDGE_DIRECTION (only the direction of m is measured).
+ * The rule, for one graph.  All arithmetic f64, + - * / sqrt only -- no sin or cos anywhere: the rotation update is the
+ * Cayley map -- no contraction; a comparison with a NaN is false; finite(v) = fabs(v) <= DBL_MAX; a 3-vector dot product is
+ * (a0*b0 + a1*b1) + a2*b2; EVERY other sum starts at +0.0 and adds its terms in ascending order ("sum").  The GPU result
+ * equals a scalar evaluation of this rule bit for bit on every output.
+ *  Active set (host): a frame is fixed at position 0 or where its byte is set.  A frame is active when a path of the graph's
+ *   edges joins it to a fixed frame (a fixed frame is active); it is free when it is active and not fixed.  An edge is used
+ *   when both ends are active and at least one is free.  Free frames are numbered k = 0, 1, .. in ascending graph position,
+ *   used edges u = 0, 1, .. in ascending position in the graph's edge list.  A frame that is not free returns its input bits.
+ *  Codes, tested in this order: no used edge: RPE_GRAPH_NO_EDGES.  A free frame none of whose used edges has w_trans > 0:
+ *   RPE_GRAPH_UNDERDETERMINED.  After the loop RPE_GRAPH_REJECTED or RPE_GRAPH_OK (Result).
+ *  Rows of an edge (12) at the state (R, T): Q[r][c] = R_j[r] . R_i[c] (rows), q[r] = Q[r] . T_i, p[r] = T_j[r] - q[r],
+ *   D[r][c] = Q[r] . M[c] (rows: D = Q M'), a = w_rot / sqrt(2).  Rotation rows 3 k + r = a * (D[r][k] - (r == k ? 1 : 0)),
+ *   k = 0 .. 2: the columns of D - I, the chordal distance, monotone up to 180 degrees.  Translation rows 9 + r, metric:
+ *   w_trans * (p[r] - m[r]); direction: n = sqrt(p . p); where n is not > 0 the three rows and their derivatives are +0;
+ *   else u = p / n, w_trans * (u[r] - m[r] / sqrt(m . m)).
+ *  Parameters of a free frame: (w[3], d[3]): R <- C(w) R, T <- T + d, with the Cayley map C(w): a = w / 2 (each
+ *   component), n2 = a . a, f = 2 / (1 + n2), C[r][r] = 1 + f*(a_r*a_r - n2), C[0][1] = f*(a0*a1 - a2), C[0][2] = f*(a0*a2 +
+ *   a1), C[1][0] = f*(a1*a0 + a2), C[1][2] = f*(a1*a2 - a0), C[2][0] = f*(a2*a0 - a1), C[2][1] = f*(a2*a1 + a0); (C R)[r][c]
+ *   = (C[r][0]*R[0][c] + C[r][1]*R[1][c]) + C[r][2]*R[2][c].  C is a rotation for every w and agrees with exp to second order.
+ *  Derivatives.  Rotation rows by d: structurally zero, not part of any sum.  Rotation row 3 k + r by w_j: with v = a *
+ *   (column k of D): (0, v2, -v1), (-v2, 0, v0), (v1, -v0, 0) for r = 0, 1, 2; by w_i, column c: a * (D[r][k2]*M[k1][c] -
+ *   D[r][k1]*M[k2][c]) with k1 = (k + 1) % 3, k2 = (k + 2) % 3 (that is a D [e_k]x M).  p by w_j: Pj = [q]x = (0, -q2, q1),
+ *   (q2, 0, -q0), (-q1, q0, 0); by w_i: Pi[r] = (Q[r][2]*Ti1 - Q[r][1]*Ti2, Q[r][0]*Ti2 - Q[r][2]*Ti0, Q[r][1]*Ti0 -
+ *   Q[r][0]*Ti1) (that is -Q [T_i]x); by d_j: I; by d_i: -Q.  Metric rows: w_trans * Pj[r][c], w_trans * Pi[r][c], by d_j
+ *   (r == c ? w_trans : 0), by d_i -(w_trans * Q[r][c]).  Direction rows: N[r][c] = ((r == c ? 1 : 0) - u[r]*u[c]) / n;
+ *   w_trans * (N[r] . column c of Pj), w_trans * (N[r] . column c of Pi), by d_j w_trans * N[r][c], by d_i
+ *   -(w_trans * (N[r] . column c of Q)).
+ *  Huber: s2 = sum of the 12 squared rows, s = sqrt(s2).  huber == 0 or s <= huber: weight h = 1, cost term s2; else
+ *   h = huber / s, cost term (2*huber)*s - huber*huber.  Weights are recomputed at every linearisation; the trial cost uses
+ *   the same terms.  cost = the reduction (below) of the used edges' terms.
+ *  Normal equations, formed explicitly.  Per used edge, with J = (the three w columns | the three d columns): entry [a][b]
+ *   of h Ji'Ji, h Jj'Jj, h Ji'Jj = h * sum over the rows of Ja[row]*Jb[row] -- all 12 rows when a and b are both w
+ *   columns, rows 9 .. 11 otherwise -- and entry a of h Ji'r, h Jj'r = h * sum of J[row][a]*r[row] likewise.  Per free
+ *   frame: its 6 x 6 block H_kk and gradient g_k = the sums over its used edges in ascending used-edge number of the
+ *   edge's block and gradient of the frame's side (a gather per frame: no atomics decide a value).  Damping: H_kk[a][a] <-
+ *   H_kk[a][a] + lambda*H_kk[a][a].
+ *  Preconditioner: the Cholesky factor of each damped H_kk by columns, L[c][c] = sqrt(H[c][c] - L[c][0]^2 - .. ), L[r][c]
+ *   = (H[r][c] - L[r][0]*L[c][0] - ..) / L[c][c], every product subtracted serially in ascending k; a pivot that is not
+ *   > 0 or not finite rejects the step.  z = M^-1 r: y_i = (r_i - L[i][0]*y_0 - ..) / L[i][i] ascending, then z_i = (y_i -
+ *   L[i+1][i]*z_(i+1) - ..) / L[i][i] descending, the products of a row subtracted in ascending k.
+ *  Step: preconditioned conjugate gradients on H x = -g.  x = 0, r_k = -g_k, z = M^-1 r, p = z, rz = rz0 = r.z.  At most
+ *   cg_iters times: (H p)_k[a] = sum_b H_kk[a][b]*p_k[b]; then over the frame's used edges in ascending number whose other
+ *   end o is free, (H p)_k[a] <- (H p)_k[a] + sum_b A[a][b]*p_o[b] where the frame is the edge's i, + sum_b A[b][a]*p_o[b]
+ *   where it is its j, A = h Ji'Jj.  pHp = p.Hp; not > 0: stop (before the first update: the step is rejected).  alpha = rz
+ *   / pHp; x <- x + alpha*p; r <- r - alpha*Hp; z = M^-1 r; rzn = r.z: one PCG iteration is counted; rzn <= (cg_tol*cg_tol)
+ *   * rz0: stop; beta = rzn / rz; p <- z + beta*p; rz = rzn.  A dot product of two 6-vectors is the sum of the six products.
+ *  Reductions: p.Hp, r.z, the squared step length x.x (items: the free frames, each item the dot product of its 6-vectors)
+ *   and the cost (items: the used edges): lane l of 256 adds its items l, l + 256, .. in ascending order, then the
+ *   butterfly (partner lane ^ 32, 16, .. 1 inside each wave of 64), then the four wave totals ((w0 + w1) + w2) + w3.
+ *  Trial: every free frame R <- C(x[0..2]) R, T <- T + x[3..5]; its cost as above.
+ *  LM: the conventions of rpe_refine_poses: lambda0 = 1e-3; at most max_iters iterations, each building the step at the
+ *   current state; a rejected step or a trial whose cost is not finite or not strictly lower: lambda * 10; an accepted one:
+ *   lambda / 10, and the loop ends when it lowered the cost by no more than 1e-6 of it or the step length sqrt(x.x) is <=
+ *   1e-9.  A start cost that is not finite runs no iteration.
+ *  Result: the optimised state is returned (RPE_GRAPH_OK) only if a step was accepted and every entry of every free frame's
+ *   pose is finite; otherwise RPE_GRAPH_REJECTED.  For every code but OK all poses are the input bits.
+ *  Outputs (host, any may be NULL): R_out[9 * n], T_out[3 * n] with n = graph_start[n_graphs], laid out like graph_frame;
+ *   counts[n_graphs * 4] = {frames, free frames, used edges, unused edges}; info[n_graphs * 4] = {RPE_GRAPH_* code,
+ *   iterations begun, steps accepted, PCG iterations in total}; cost[n_graphs * 2]: of the input state and of the returned
+ *   state; edge_chi[2 * n_edges]: the length s of each used edge's rows at the input state and at the returned state, 0 for
+ *   an unused edge -- how a caller finds the loop edge to drop; edge_used[n_edges] bytes.
+ * The call uses device buffers of its own, created on the first call and grown to the largest call; neither the workspace
+ * nor the record of the last run is touched: every fetch of the run and every call behind it returns the same bits.
+ * RPE_ERR_INVALID: a NULL handle; n_frames < 1; n_graphs < 0; huber negative or not finite; max_iters outside 1 .. 100;
+ * cg_iters outside 1 .. 1000; cg_tol outside [0, 1); with n_graphs > 0: a NULL R_abs, T_abs, graph_start, graph_frame or
+ * edge_start, or a NULL edge array with edges; a CSR array not starting at 0 or decreasing; a graph of fewer than 2 frames;
+ * a frame index outside 0 .. n_frames - 1 or repeated inside a graph; an edge end that is no frame of its graph; i == j; a
+ * non-finite pose of a frame some graph names; a non-finite measurement or weight; w_rot not > 0 or w_trans < 0; an edge_R
+ * whose M M' differs from I by more than 1e-6 in an entry; an unknown kind; a direction edge with m = 0.  RPE_ERR_CAPACITY:
+ * a graph of more than RPE_GRAPH_MAX_FRAMES frames or RPE_GRAPH_MAX_EDGES edges.  All checks are host-side; nothing is
+ * launched and the handle stays usable after a refusal.  n_graphs == 0 passes the scalar checks, succeeds and writes nothing. */
+#define RPE_GRAPH_MAX_FRAMES 4096
+#define RPE_GRAPH_MAX_EDGES 65536
+enum { RPE_EDGE_METRIC = 0, RPE_EDGE_DIRECTION = 1 };
+enum { RPE_GRAPH_OK = 0, RPE_GRAPH_NO_EDGES = 1, RPE_GRAPH_UNDERDETERMINED = 2, RPE_GRAPH_REJECTED = 3 };
+int rpe_optimise_graphs(rpe_handle *h, int n_frames, const double *R_abs, const double *T_abs,
+                        int n_graphs, const int32_t *graph_start, const int32_t *graph_frame, const uint8_t *fixed,
+                        const int32_t *edge_start, const int32_t *edge_i, const int32_t *edge_j, const double *edge_R,
+                        const double *edge_t, const double *edge_w, const int32_t *edge_kind,
+                        double huber, int max_iters, int cg_iters, double cg_tol,
+                        double *R_out, double *T_out, int32_t *counts, int32_t *info, double *cost, double *edge_chi,
+                        uint8_t *edge_used);
+
 /* --------------------------------------------------------- pair proposals */
 /* Which frames see the same place (NOT in the reference): an exact similarity score between stored frames and a top-k
  * candidate selection, both on the GPU, so that a pair list for rpe_enqueue_pairs (loop closures, windows of far-apart

@@ -40,7 +40,12 @@ TRACKPT_NAMES = ("OK", "TOO_FEW", "DEGENERATE", "BEHIND", "OUTLIERS", "LOW_PARAL
 WINDOW_OK, WINDOW_NO_BASELINE, WINDOW_TOO_FEW, WINDOW_REJECTED = 0, 1, 2, 3
 WINDOW_NAMES = ("OK", "NO_BASELINE", "TOO_FEW", "REJECTED")
 WINDOW_MAX_VIEWS, WINDOW_MAX_POINTS = 8, 16384   # RPE_WINDOW_MAX_VIEWS, RPE_WINDOW_MAX_POINTS
-SIMILAR_MAX_K = 32                # RPE_SIMILAR_MAX_K: the most candidates per query row of the similarity calls
+# info[:, 0] / 'code' of optimise_graphs (RPE_GRAPH_*), the kinds of its edges (RPE_EDGE_*) and its capacities
+GRAPH_OK, GRAPH_NO_EDGES, GRAPH_UNDERDETERMINED, GRAPH_REJECTED = 0, 1, 2, 3
+GRAPH_NAMES = ("OK", "NO_EDGES", "UNDERDETERMINED", "REJECTED")
+EDGE_METRIC, EDGE_DIRECTION = 0, 1
+GRAPH_MAX_FRAMES, GRAPH_MAX_EDGES = 4096, 65536   # RPE_GRAPH_MAX_FRAMES, RPE_GRAPH_MAX_EDGES
+SIMILAR_MAX_K = 32             # RPE_SIMILAR_MAX_K: the most candidates per query row of the similarity calls
 UNDISTORT_ITERS = 5               # RPE_UNDISTORT_ITERS: fixed-point rounds of the camera path's undistortion
 
 # The binding, one entry per function of include/rpe_amd.h: "<return>:<one letter per parameter>".  Parameters: p pointer or
@@ -69,6 +74,7 @@ _SIGNATURES = {
     "rpe_last_run_pairs": "i:p", "rpe_build_tracks": "i:ppiipppppp", "rpe_tracks_from_matches": "i:piippppppppipppppp",
     "rpe_triangulate_tracks": "i:pipppipppppdidipppppp",
     "rpe_bundle_windows": "i:pippppppippppippiiippppppp",
+    "rpe_optimise_graphs": "i:pippipppppppppp" "diid" "ppppppp",
     "rpe_frames_similar": "i:pipipiippiiipppp", "rpe_similarity_hamming": "i:pppiipipiippiiipppp",
     "rpe_guided_matches": "i:pippdipppppp",
     "rpe_guided_matches_l2": "i:pippddpppppp",
@@ -625,6 +631,65 @@ class Engine:
                 'code': info[:, 0].copy(), 'views': counts[:, 0].copy(), 'n_points': cnt.copy(), 'n_obs': counts[:, 2].copy(),
                 'dropped': counts[:, 3].copy(), 'iterations': info[:, 1].copy(), 'accepted': info[:, 2].copy(),
                 'anchor': info[:, 3].copy(), 'rms': rms}
+
+    # ---- pose graphs (rpe_optimise_graphs; not in the reference)
+    def optimise_graphs(self, R_abs, T_abs, graphs, edges, fixed=None, huber=0.0, max_iters=20, cg_iters=32, cg_tol=1e-3):
+        """Pose-graph optimisation of a chain's poses over relative-pose edges (rpe_optimise_graphs; the rule is in
+        include/rpe_amd.h, "pose graphs").  R_abs [F, 3, 3], T_abs [F, 3]: world-to-camera poses; graphs: a list of lists of
+        distinct frames, the first of each is fixed; edges: one dict per graph of 'i', 'j' (frame indices), 'R' [E, 3, 3],
+        't' [E, 3] (X_j = R X_i + t), 'w' [E, 2] (w_rot, w_trans) and 'kind' [E] (EDGE_METRIC / EDGE_DIRECTION) --
+        geometry.chain_edges and loop_edges build them; fixed: None or one byte array per graph (or None), laid out like the
+        graph's frames.  Each graph is solved on its own from these poses.  Returns a dict: 'R', 'T': lists, one [n, 3, 3] /
+        [n, 3] array per graph; 'code' (GRAPH_*), 'frames', 'free', 'used_edges', 'unused_edges', 'iterations', 'accepted',
+        'pcg_iterations' i32[n_graphs]; 'cost' f64[n_graphs, 2] (before and after); 'edge_chi': a list of f64[E, 2], the length
+        of each used edge's rows before and after (0 for unused edges); 'edge_used': a list of u8[E].  For every code but
+        GRAPH_OK the inputs come back.  The last run stays fetchable."""
+        R = np.ascontiguousarray(np.asarray(R_abs, np.float64).reshape(-1, 9))
+        T = np.ascontiguousarray(np.asarray(T_abs, np.float64).reshape(-1, 3))
+        if T.shape[0] != R.shape[0]:
+            raise ValueError("optimise_graphs: R_abs and T_abs hold one pose per frame")
+        gl = [_i32(g) for g in graphs]
+        ng = len(gl)
+        if len(edges) != ng or (fixed is not None and len(fixed) != ng):
+            raise ValueError("optimise_graphs: edges (and fixed) hold one entry per graph")
+        gstart = np.zeros(ng + 1, np.int32); estart = np.zeros(ng + 1, np.int32)
+        gstart[1:] = np.cumsum([g.size for g in gl])
+        el = []
+        for e in edges:
+            i, j = _i32(e['i']), _i32(e['j'])
+            n = i.size
+            M = np.asarray(e['R'], np.float64).reshape(-1, 9); m = np.asarray(e['t'], np.float64).reshape(-1, 3)
+            w = np.asarray(e['w'], np.float64).reshape(-1, 2); k = _i32(e['kind'])
+            if not (j.size == M.shape[0] == m.shape[0] == w.shape[0] == k.size == n):
+                raise ValueError("optimise_graphs: the arrays of a graph's edges hold one row per edge")
+            el.append((i, j, M, m, w, k))
+        estart[1:] = np.cumsum([e[0].size for e in el])
+        cat = lambda k, dtype, shape: np.ascontiguousarray(np.concatenate([e[k] for e in el]) if el else np.zeros(shape, dtype), dtype)
+        gframe = np.ascontiguousarray(np.concatenate(gl) if ng else np.zeros(0, np.int32), np.int32)
+        ei, ej, eM, em, ew, ek = (cat(0, np.int32, 0), cat(1, np.int32, 0), cat(2, np.float64, (0, 9)), cat(3, np.float64, (0, 3)),
+                                  cat(4, np.float64, (0, 2)), cat(5, np.int32, 0))
+        fx = None
+        if fixed is not None:
+            fx = np.zeros(gframe.size, np.uint8)
+            for g, f in enumerate(fixed):
+                if f is not None:
+                    f = np.asarray(f).reshape(-1)
+                    if f.size != gl[g].size:
+                        raise ValueError("optimise_graphs: fixed holds one byte per frame of its graph")
+                    fx[gstart[g]:gstart[g + 1]] = f != 0
+        nf, ne = int(gstart[-1]), int(estart[-1])
+        Ro = np.zeros((nf, 3, 3)); To = np.zeros((nf, 3)); counts = np.zeros((ng, 4), np.int32); info = np.zeros((ng, 4), np.int32)
+        cost = np.zeros((ng, 2)); chi = np.zeros((ne, 2)); used = np.zeros(ne, np.uint8)
+        self._chk(self.lib.rpe_optimise_graphs(self.h, R.shape[0], _p(R), _p(T), ng, _p(gstart), _p(gframe), _opt(fx), _p(estart),
+                                               _p(ei), _p(ej), _p(eM), _p(em), _p(ew), _p(ek), float(huber), int(max_iters),
+                                               int(cg_iters), float(cg_tol), _p(Ro), _p(To), _p(counts), _p(info), _p(cost),
+                                               _p(chi), _p(used)))
+        per_g = lambda a: [a[gstart[g]:gstart[g + 1]].copy() for g in range(ng)]
+        per_e = lambda a: [a[estart[g]:estart[g + 1]].copy() for g in range(ng)]
+        return {'R': per_g(Ro), 'T': per_g(To), 'code': info[:, 0].copy(), 'iterations': info[:, 1].copy(),
+                'accepted': info[:, 2].copy(), 'pcg_iterations': info[:, 3].copy(), 'frames': counts[:, 0].copy(),
+                'free': counts[:, 1].copy(), 'used_edges': counts[:, 2].copy(), 'unused_edges': counts[:, 3].copy(),
+                'cost': cost, 'edge_chi': per_e(chi), 'edge_used': per_e(used)}
 
     # ---- guided matching (rpe_guided_matches / rpe_match_hamming_guided; not in the reference)
     def _poses(self, B, R, t):

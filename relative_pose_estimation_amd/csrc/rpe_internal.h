@@ -392,6 +392,20 @@ struct RpeWindowJob {
     const int *win_start, *win_frame;
 };
 
+// One job of the pose-graph kernel (graph_kernels.hip): the caller's poses and measurements as uploaded, the graphs in CSR
+// form, and what the host made of them (rpe_optimise_graphs): per graph the offsets of its free frames and used edges and
+// the code it already has (-1: solve); per free frame its graph position and its adjacency (adj_start, global offsets into
+// adj: x = used edge of the graph << 1 | side, side 1 = the frame is the edge's j; y = free index of the other end or -1),
+// per used edge its position in the graph's edge list, per edge the graph positions of its ends
+struct RpeGraphJob {
+    int n_graphs, max_iters, cg_iters;
+    double huber, cg_tol;
+    const double *R_abs, *T_abs, *edge_R, *edge_t, *edge_w;
+    const int *graph_start, *graph_frame, *edge_start, *free_start, *used_start, *precode;
+    const int *free_pos, *adj_start, *used_edge, *edge_i, *edge_j, *edge_kind;
+    const int2 *adj;
+};
+
 // One job of the similarity kernels (similar_kernels.hip): the features (the frame store's, or the workspace's of the stage
 // form), the two device tables of slots, the times (the tables themselves when the caller gave none) and where the results go.
 // same: the two lists are identical, the triangle is computed and mirrored.  cand == null: no selection
@@ -573,6 +587,17 @@ struct rpe_handle {
     double *d_wb_points0 = nullptr, *d_wb_state = nullptr, *d_wb_points = nullptr;
     double *d_wb_Rout = nullptr, *d_wb_Tout = nullptr, *d_wb_rms = nullptr;
     uint8_t *d_wb_puse = nullptr, *d_wb_ouse = nullptr; RpeBufSet set_windows;
+    // rpe_optimise_graphs only (set_graphs, fitted to every call's frames, graphs and edges).  The uploads: the caller's poses
+    // and measurements, the CSR arrays and the host's tables (RpeGraphJob); per graph position the state (the output) and the
+    // trial state; per used edge the 120 f64 of its blocks, per free frame the 87 f64 of its block, factor and PCG vectors
+    // (graph_kernels.hip); per edge the two chi, per graph cost and info
+    double *d_pg_Rabs = nullptr, *d_pg_Tabs = nullptr, *d_pg_eR = nullptr, *d_pg_et = nullptr, *d_pg_ew = nullptr;
+    int *d_pg_gstart = nullptr, *d_pg_gframe = nullptr, *d_pg_estart = nullptr, *d_pg_fstart = nullptr, *d_pg_ustart = nullptr;
+    int *d_pg_precode = nullptr, *d_pg_fpos = nullptr, *d_pg_astart = nullptr, *d_pg_uedge = nullptr;
+    int *d_pg_ei = nullptr, *d_pg_ej = nullptr, *d_pg_ekind = nullptr, *d_pg_info = nullptr;
+    int2 *d_pg_adj = nullptr;
+    double *d_pg_Rout = nullptr, *d_pg_Tout = nullptr, *d_pg_Rn = nullptr, *d_pg_Tn = nullptr;
+    double *d_pg_eb = nullptr, *d_pg_fb = nullptr, *d_pg_chi = nullptr, *d_pg_cost = nullptr; RpeBufSet set_graphs;
     // rpe_frames_similar / rpe_similarity_hamming only (set_similar, fitted to every call's lists): the two slot tables (not
     // d_pairtab, which holds 2*max_batch entries: a list here may be as long as the store), the times the caller gave, the
     // nq * nt scores, and per query row its k candidates, their scores and their count
@@ -744,6 +769,7 @@ bool rpe_bundles_in_lds(const rpe_handle *h);
 void rpe_launch_tracks(rpe_handle *h, const RpeTrackJob &job);
 void rpe_launch_track_points(rpe_handle *h, const RpeTrackPointJob &job);
 void rpe_launch_windows(rpe_handle *h, const RpeWindowJob &job);
+void rpe_launch_graphs(rpe_handle *h, const RpeGraphJob &job);
 void rpe_launch_similar(rpe_handle *h, const RpeSimilarJob &job);
 void rpe_launch_normalise(rpe_handle *h, const RpeRun &r);
 void rpe_launch_homography(rpe_handle *h, const RpeRun &r, int iters, double threshold_px, bool from_batch);

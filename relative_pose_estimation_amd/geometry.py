@@ -218,6 +218,102 @@ def registered_chain_inputs(R_rel, t_rel, status, ratio, code, R_link, t_link, l
     return R, t, status, ratio, code
 
 
+# ---- pose graphs over a chain (not in the reference) -------------
+EDGE_METRIC, EDGE_DIRECTION = 0, 1        # RPE_EDGE_*: the kinds of _capi.Engine.optimise_graphs' edges
+
+
+def _edge_dict(i, j, R, t, w, kind):
+    return {'i': np.asarray(i, np.int32).reshape(-1), 'j': np.asarray(j, np.int32).reshape(-1),
+            'R': np.asarray(R, np.float64).reshape(-1, 3, 3), 't': np.asarray(t, np.float64).reshape(-1, 3),
+            'w': np.asarray(w, np.float64).reshape(-1, 2), 'kind': np.asarray(kind, np.int32).reshape(-1)}
+
+
+def chain_edges(R_abs, T_abs, frame_group, sigma_rot_deg=0.5, sigma_dir_deg=2.0):
+    """The chain as edges of a pose graph (pure host code): one metric edge (f, f + 1) between consecutive frames that share
+    one group >= 0 (frame_groups), carrying the chain's own relative pose M = R_(f+1) R_f', m = T_(f+1) - M T_f, so the
+    chain has zero residual at the start and only the loop edges pull.  Weights: w_rot = 1 / rad(sigma_rot_deg), w_trans =
+    1 / (rad(sigma_dir_deg) * max(|m|, the group's median |m|)): a direction error of sigma_dir on a step of the usual
+    length, and never a larger weight on a step that happens to be short.  The sigmas are caller policy: 0.5 degrees is
+    the median five-point rotation error this project measures; 2 degrees for the direction is NOT
+    measured anywhere in the project.  Returns the dict of edges optimise_graphs takes ('i', 'j', 'R', 't', 'w', 'kind'),
+    in ascending f."""
+    R_abs = np.asarray(R_abs, np.float64).reshape(-1, 3, 3); T_abs = np.asarray(T_abs, np.float64).reshape(-1, 3)
+    g = np.asarray(frame_group).reshape(-1)
+    if not (g.size == R_abs.shape[0] == T_abs.shape[0]):
+        raise ValueError("chain_edges: R_abs, T_abs and frame_group hold one entry per frame")
+    if not (sigma_rot_deg > 0 and sigma_dir_deg > 0):
+        raise ValueError("chain_edges: the sigmas must be > 0")
+    f = np.flatnonzero((g[:-1] == g[1:]) & (g[:-1] >= 0)) if g.size > 1 else np.zeros(0, int)
+    M = np.einsum("fab,fcb->fac", R_abs[f + 1], R_abs[f])
+    m = T_abs[f + 1] - np.einsum("fab,fb->fa", M, T_abs[f])
+    length = np.sqrt((m * m).sum(1))
+    floor = np.zeros(len(f))
+    for grp in np.unique(g[f]):
+        sel = g[f] == grp
+        floor[sel] = np.median(length[sel])
+    w = np.zeros((len(f), 2))
+    w[:, 0] = 1.0 / np.deg2rad(sigma_rot_deg)
+    scale = np.deg2rad(sigma_dir_deg) * np.maximum(length, floor)
+    w[:, 1] = np.divide(1.0, scale, out=np.zeros(len(f)), where=scale > 0)      # a group that never moves: rotation only
+    return _edge_dict(f, f + 1, M, m, w, np.full(len(f), EDGE_METRIC))
+
+
+def loop_edges(pairs, R, t, status, frame_group, min_inliers=0, inliers=None, sigma_rot_deg=0.5, sigma_dir_deg=2.0):
+    """Loop closures as edges of a pose graph (pure host code): one direction edge per pair (i, j) of pairs[P, 2] whose pose
+    X_j = R[p] X_i + t[p] is OK (status[p] == 0, a finite t that is not zero, inliers[p] >= min_inliers where inliers is
+    given) and whose two frames share one group >= 0.  Pairs across groups are dropped: the scales of different groups are
+    unrelated and the graph has no scale variable.  Weights: w_rot = 1 / rad(sigma_rot_deg), w_trans = 1 /
+    rad(sigma_dir_deg) (the rows are a difference of unit vectors); the sigmas as in chain_edges -- the 2 degrees are not
+    measured.  Returns (the dict of edges, in the order of the kept pairs; the indices of the pairs it dropped)."""
+    pairs = np.asarray(pairs, np.int64).reshape(-1, 2)
+    P = pairs.shape[0]
+    R = np.asarray(R, np.float64).reshape(-1, 3, 3); t = np.asarray(t, np.float64).reshape(-1, 3)
+    status = np.asarray(status).reshape(-1)
+    g = np.asarray(frame_group).reshape(-1)
+    if not (R.shape[0] == t.shape[0] == status.size == P) or (inliers is not None and np.asarray(inliers).size != P):
+        raise ValueError("loop_edges: R, t, status (and inliers) hold one entry per pair")
+    if P and (pairs.min() < 0 or pairs.max() >= g.size):
+        raise ValueError("loop_edges: a pair names a frame outside frame_group")
+    if not (sigma_rot_deg > 0 and sigma_dir_deg > 0):
+        raise ValueError("loop_edges: the sigmas must be > 0")
+    keep = (status == 0) & (pairs[:, 0] != pairs[:, 1]) & np.isfinite(R).all((1, 2)) & np.isfinite(t).all(1) & ((t != 0).any(1))
+    keep &= (g[pairs[:, 0]] == g[pairs[:, 1]]) & (g[pairs[:, 0]] >= 0)
+    if inliers is not None:
+        keep &= np.asarray(inliers).reshape(-1) >= min_inliers
+    k = np.flatnonzero(keep)
+    w = np.tile([1.0 / np.deg2rad(sigma_rot_deg), 1.0 / np.deg2rad(sigma_dir_deg)], (len(k), 1))
+    return _edge_dict(pairs[k, 0], pairs[k, 1], R[k], t[k], w, np.full(len(k), EDGE_DIRECTION)), np.flatnonzero(~keep).astype(np.int32)
+
+
+def graphs_of_groups(frame_group):
+    """One graph per group >= 0 of two or more frames (frame_groups), in the order of the groups' first frames; a graph's
+    frames ascend, so the group's first frame is at position 0, the one optimise_graphs keeps fixed.  A list of lists."""
+    g = np.asarray(frame_group).reshape(-1)
+    out, seen = [], set()
+    for f in range(g.size):
+        if g[f] >= 0 and int(g[f]) not in seen:
+            seen.add(int(g[f]))
+            frames = np.flatnonzero(g == g[f])
+            if frames.size >= 2:
+                out.append([int(x) for x in frames])
+    return out
+
+
+def edges_of_graphs(graphs, *edge_dicts):
+    """The edges of chain_edges / loop_edges dealt to the graphs of graphs_of_groups: per graph one dict, holding the edges
+    whose two frames are both in the graph, the first dict's before the second's.  Edges in no graph are left out."""
+    out = []
+    for frames in graphs:
+        s = np.asarray(frames).reshape(-1)
+        part = []
+        for e in edge_dicts:
+            k = np.flatnonzero(np.isin(e['i'], s) & np.isin(e['j'], s))
+            part.append({key: e[key][k] for key in ('i', 'j', 'R', 't', 'w', 'kind')})
+        out.append({key: np.concatenate([p[key] for p in part]) for key in ('i', 'j', 'R', 't', 'w', 'kind')} if part
+                   else _edge_dict([], [], np.zeros((0, 3, 3)), np.zeros((0, 3)), np.zeros((0, 2)), []))
+    return out
+
+
 # ---- which model a pair obeys (not in the reference) -------------
 def classify_pair(n_matches, n_E, n_H, n_rot, rotation_ratio=0.7, planar_ratio=0.8):
     """Names the geometric model a pair obeys from the inlier counts of PoseEstimator.last_homographies /

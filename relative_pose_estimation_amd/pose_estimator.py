@@ -337,15 +337,25 @@ class PoseEstimator:
         at most max_batch (plan_pairs); last_structure(), last_refined() and last_overflow() describe the LAST chunk of
         pairs, as they do for estimate_batch.  Needs F store slots of GPU memory, which stay with the engine and are reused by the next call
         (INTEGRATION.md section 7)."""
+        frames = self._check_frames(frames)
+        pairs = _check_pairs(pairs, frames.shape[0], "frame")
+        eng = self._fill_store(frames, pairs.shape[0])
+        return self._run_pair_list(eng, pairs, cameras=self._camera is not None)
+
+    @staticmethod
+    def _check_frames(frames):
         frames = np.asarray(frames)
         if frames.dtype != np.uint8 or frames.ndim not in (3, 4) or (frames.ndim == 4 and frames.shape[-1] != 3) or frames.shape[0] < 1:
             raise ValueError(f"frames: expected uint8 [F, H, W] or [F, H, W, 3], got {frames.dtype} {frames.shape}")
+        return frames
+
+    def _fill_store(self, frames, n_pairs):
+        """estimate_pairs' store: frame f extracted into slot f of the engine of the frames' size, which is returned"""
         F, H, W = frames.shape[:3]
-        pairs = _check_pairs(pairs, F, "frame")
         eng = self._engine(H, W, 1)
         if getattr(eng, "_store_owner", None) is not None:
             raise _capi.RpeError("the engine of this image size serves a FrameStore: use its estimate(), or close it first")
-        puts, _ = plan_pairs(F, pairs.shape[0], eng.max_batch)
+        puts, _ = plan_pairs(F, n_pairs, eng.max_batch)
         if eng.frames_capacity() < F:         # a store left by an earlier call is reused when it is large enough
             eng.frames_reserve(0)
             eng.frames_reserve(F)
@@ -355,7 +365,55 @@ class PoseEstimator:
             eng.frames_put(gray, np.arange(a, b, dtype=np.int32))
         if self._camera is not None:
             eng.frames_set_cameras(np.arange(F, dtype=np.int32), self._camera)
-        return self._run_pair_list(eng, pairs, cameras=self._camera is not None)
+        return eng
+
+    def close_loops(self, frames, R_abs, T_abs, frame_group, loop_pairs=None, k=3, exclude=8, min_score=0, huber=2.0, **solver):
+        """Loop closure over a chain (not in the reference): the poses of the loop pairs, the pose graph of the chain with
+        those pairs as loop edges, and its optimisation on the GPU (_capi.Engine.optimise_graphs).  frames as in
+        estimate_pairs; R_abs [F, 3, 3], T_abs [F, 3], frame_group [F]: a chain and its scale groups, as estimate_trajectory
+        and geometry.frame_groups give them (estimate_trajectory itself is unchanged: its result feeds this call).
+        loop_pairs [P, 2]: the frame pairs that see the same place again; None: proposed from the frames themselves --
+        every frame's k most similar frames more than `exclude` frames away scoring at least min_score (frames_similar
+        over the store estimate_pairs fills, frame f in slot f, time = frame) -- which needs an ORB + Hamming estimator:
+        others raise ValueError without the list.  The graph: geometry.chain_edges, loop_edges and graphs_of_groups with
+        their default sigmas; loop pairs across groups are dropped.  huber and solver (max_iters, cg_iters, cg_tol) go to
+        optimise_graphs; the default bound of 2 keeps a wrong loop edge from bending the chain.
+        Returns a dict: 'R_abs_graph' [F, 3, 3], 'T_abs_graph' [F, 3], 'centers_graph' [F, 3]: the chain with the frames
+        of every graph whose code is GRAPH_OK replaced; 'graph': the solver's dict with 'graphs' and 'edges' (what it was
+        given) and 'dropped' (indices of loop pairs that became no edge) added; 'loop_pairs' [P, 2]; and the pair results
+        'R', 't', 'inliers', 'n_matches', 'status' of the loop pairs."""
+        frames = self._check_frames(frames)
+        F = frames.shape[0]
+        R_abs = np.asarray(R_abs, np.float64).reshape(-1, 3, 3); T_abs = np.asarray(T_abs, np.float64).reshape(-1, 3)
+        group = np.asarray(frame_group).reshape(-1)
+        if not (R_abs.shape[0] == T_abs.shape[0] == group.size == F):
+            raise ValueError("close_loops: R_abs, T_abs and frame_group hold one entry per frame")
+        if loop_pairs is None and (self._feature, self._norm) != (_capi.FEATURE_ORB, _capi.NORM_HAMMING):
+            raise ValueError("close_loops: pairs are proposed on ORB + Hamming estimators only; pass loop_pairs")
+        if loop_pairs is not None:
+            loop_pairs = _check_pairs(loop_pairs, F, "frame")
+        eng = self._fill_store(frames, F if loop_pairs is None else loop_pairs.shape[0])
+        if loop_pairs is None:
+            every = np.arange(F, dtype=np.int32)
+            s = eng.frames_similar(every, every, exclude=exclude, min_score=min_score, k=k, want_scores=False)
+            loop_pairs, _ = geometry.pairs_of_candidates(every, every, s["cand"], s["cand_score"])
+        if loop_pairs.shape[0]:
+            R, t, inl, nm, st = self._run_pair_list(eng, loop_pairs, cameras=self._camera is not None)
+        else:
+            R, t = np.zeros((0, 3, 3)), np.zeros((0, 3, 1))
+            inl = nm = st = np.zeros(0, np.int32)
+        chain = geometry.chain_edges(R_abs, T_abs, group)
+        loops, dropped = geometry.loop_edges(loop_pairs, R, t, st, group)
+        graphs = geometry.graphs_of_groups(group)
+        edges = geometry.edges_of_graphs(graphs, chain, loops)
+        res = eng.optimise_graphs(R_abs, T_abs, graphs, edges, huber=huber, **solver)
+        Rg, Tg = R_abs.copy(), T_abs.copy()
+        for g, fr in enumerate(graphs):
+            if res['code'][g] == _capi.GRAPH_OK:
+                Rg[fr] = res['R'][g]; Tg[fr] = res['T'][g]
+        res.update({'graphs': graphs, 'edges': edges, 'dropped': dropped})
+        return {'R_abs_graph': Rg, 'T_abs_graph': Tg, 'centers_graph': -np.einsum("fji,fj->fi", Rg, Tg), 'graph': res,
+                'loop_pairs': loop_pairs, 'R': R, 't': t, 'inliers': inl, 'n_matches': nm, 'status': st}
 
     def frame_store(self, capacity):
         """A FrameStore of `capacity` slots on this estimator's engine (created for the size of the first frame put)."""

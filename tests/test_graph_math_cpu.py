@@ -1,0 +1,181 @@
+"""relative_pose_estimation_amd/csrc/graph_math.h on the host: the rows of a pose-graph edge with their two Jacobians, the Huber
+weight, the edge's blocks of the normal equations, the 6 x 6 Cholesky factor and solve and the Cayley update, which
+pg_solve_kernel runs on a GPU lane.  tests/native/graph_math_host.cpp runs the header's statements on seeded and crafted
+cases; it is built without floating-point contraction (the device build's setting), plain and with the host sanitizers.
+
+Every comparison is with tests/pose_graph_model.py, bit for bit (the float64 words as integers); two NaNs count as equal."""
+import os
+import subprocess
+
+import numpy as np
+import pytest
+
+from tests import bundle_math_model as mm
+from tests import pose_graph_model as pg
+
+HERE = os.path.dirname(os.path.abspath(__file__))
+SRC = os.path.join(HERE, "native", "graph_math_host.cpp")
+BUILD = os.path.join(HERE, "native", "build")
+
+FLAVOURS = {
+    "nocontract": ["-O2", "-ffp-contract=off"],
+    "sanitized": ["-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all"],
+}
+N_RANDOM = 2000
+
+
+@pytest.fixture(scope="module", params=list(FLAVOURS))
+def exe(request):
+    os.makedirs(BUILD, exist_ok=True)
+    out = os.path.join(BUILD, "graph_math_host_" + request.param)
+    subprocess.check_call(["g++", "-std=c++17"] + FLAVOURS[request.param] + ["-o", out, SRC])
+    return out
+
+
+def _run(exe, mode, doubles):
+    data = np.ascontiguousarray(doubles, np.float64).tobytes()
+    return subprocess.run([exe, mode], input=data, capture_output=True, check=True).stdout
+
+
+def _same(a, b):
+    a = np.ascontiguousarray(a, np.float64); b = np.ascontiguousarray(b, np.float64)
+    assert a.shape == b.shape, (a.shape, b.shape)
+    return (a.view(np.uint64) == b.view(np.uint64)) | (np.isnan(a) & np.isnan(b))
+
+
+def _rot(rng, big=True):
+    ax = rng.normal(size=3); ax /= np.linalg.norm(ax)
+    return mm.rodrigues(ax * (rng.uniform(-3.1, 3.1) if big else rng.uniform(-0.05, 0.05)))
+
+
+def _edges():
+    """the seeded edges, the crafted ones first: an exact identity edge (all rows zero), coincident centres under a
+    direction edge (the zero rows), a rotation 180 degrees wrong, an edge with s far above the Huber bound, a NaN pose"""
+    rng = np.random.default_rng(20251021)
+    I = np.eye(3)
+    Rz = np.diag([-1.0, -1.0, 1.0])
+    crafted = [
+        (I, [1.0, 2.0, 3.0], I, [2.0, 4.0, 3.0], I, [1.0, 2.0, 0.0], 100.0, 10.0, 0, 2.0),
+        (_rot(rng), [0.0, 0.0, 0.0], I, [0.0, 0.0, 0.0], _rot(rng), [0.0, 0.0, 1.0], 50.0, 5.0, 1, 0.0),
+        (I, [0.0, 0.0, 0.0], Rz, [1.0, 0.0, 0.0], I, [1.0, 0.0, 0.0], 100.0, 10.0, 1, 0.0),
+        (_rot(rng), [3.0, 1.0, 2.0], _rot(rng), [-4.0, 0.0, 9.0], _rot(rng), [0.1, 0.2, 0.3], 115.0, 30.0, 0, 2.0),
+        (I * np.nan, [0.0, 0.0, 0.0], I, [1.0, 0.0, 0.0], I, [1.0, 0.0, 0.0], 100.0, 10.0, 1, 2.0),
+    ]
+    rec = [np.concatenate([np.ravel(c[0]), c[1], np.ravel(c[2]), c[3], np.ravel(c[4]), c[5], c[6:]]) for c in crafted]
+    for k in range(N_RANDOM):
+        Ri, Rj = _rot(rng), _rot(rng)
+        Ti, Tj = rng.uniform(-10, 10, 3), rng.uniform(-10, 10, 3)
+        Q = Rj @ Ri.T
+        M = _rot(rng, big=False) @ Q if k % 2 else _rot(rng)
+        m = (Tj - Q @ Ti) + rng.normal(size=3) * 0.1
+        rec.append(np.concatenate([Ri.ravel(), Ti, Rj.ravel(), Tj, M.ravel(), m,
+                                   [rng.uniform(10, 200), [0.0, rng.uniform(0.1, 50)][k % 5 != 0], k % 3 != 0, [0.0, 2.0, 30.0][k % 3]]]))
+    return np.stack(rec)
+
+
+EDGES = _edges()
+N_CRAFTED = len(EDGES) - N_RANDOM
+
+
+def _edge_reference():
+    e = EDGES
+    Ri, Ti, Rj, Tj = e[:, 0:9].reshape(-1, 3, 3), e[:, 9:12], e[:, 12:21].reshape(-1, 3, 3), e[:, 21:24]
+    M, m, wr, wt, kind, hub = e[:, 24:33].reshape(-1, 3, 3), e[:, 33:36], e[:, 36], e[:, 37], e[:, 38].astype(int), e[:, 39]
+    r0 = pg.edge_rows(Ri, Ti, Rj, Tj, M, m, wr, wt, kind, jac=False)
+    r, JiW, JjW, JiD, JjD = pg.edge_rows(Ri, Ti, Rj, Tj, M, m, wr, wt, kind)
+    ref = np.zeros((len(e), 237))
+    ref[:, 0:12] = r0; ref[:, 12:24] = r
+    ref[:, 24:60] = JiW.reshape(-1, 36); ref[:, 60:96] = JjW.reshape(-1, 36)
+    ref[:, 96:105] = JiD.reshape(-1, 9); ref[:, 105:114] = JjD.reshape(-1, 9)
+    for hv in np.unique(hub):
+        i = np.flatnonzero(hub == hv)
+        s, h, c = pg.huber_terms(r[i], float(hv))
+        ref[i, 114] = s; ref[i, 115] = h; ref[i, 116] = c
+        ref[i, 117:153] = pg.block(h, JiW[i], JiD[i], JiW[i], JiD[i]).reshape(-1, 36)
+        ref[i, 153:189] = pg.block(h, JjW[i], JjD[i], JjW[i], JjD[i]).reshape(-1, 36)
+        ref[i, 189:225] = pg.block(h, JiW[i], JiD[i], JjW[i], JjD[i]).reshape(-1, 36)
+        ref[i, 225:231] = pg.grad(h, JiW[i], JiD[i], r[i]); ref[i, 231:237] = pg.grad(h, JjW[i], JjD[i], r[i])
+    return ref
+
+
+EDGE_REF = _edge_reference()
+
+
+@pytest.fixture(scope="module")
+def edge_out(exe):
+    return np.frombuffer(_run(exe, "edge", EDGES), np.float64).reshape(-1, 237)
+
+
+def test_edge_rows_blocks_and_huber_equal_the_model(edge_out):
+    assert edge_out.shape == EDGE_REF.shape
+    ok = _same(edge_out, EDGE_REF)
+    assert ok.all(), np.argwhere(~ok)[:10]
+    assert _same(edge_out[:, 0:12], edge_out[:, 12:24]).all()               # the rows do not depend on JAC
+
+
+def test_crafted_edges_are_what_they_were_meant_to_be(edge_out):
+    assert (edge_out[0, 12:24] == 0.0).all() and edge_out[0, 114] == 0.0 and edge_out[0, 115] == 1.0
+    assert (edge_out[1, 21:24] == 0.0).all() and (edge_out[1, 96:114] == 0.0).all()      # the zero rows, their d columns
+    assert (edge_out[1, 24 + 27:24 + 36] == 0.0).all() and (edge_out[1, 60 + 27:60 + 36] == 0.0).all()
+    # 180 degrees wrong: the chordal rows see it at full length, sqrt(8) w_rot / sqrt(2) = 2 w_rot (the sine form gives 0)
+    assert abs(edge_out[2, 114] - 200.0) < 1e-9
+    assert edge_out[3, 114] > 2.0 and 0.0 < edge_out[3, 115] < 1.0
+    s, h, c = edge_out[3, 114:117]
+    assert h == 2.0 / s and c == (2.0 * 2.0) * s - 2.0 * 2.0
+    assert np.isnan(edge_out[4, 114]) and np.isnan(edge_out[4, 116])
+    kinds = EDGES[N_CRAFTED:, 38]
+    assert (kinds == 0).sum() > 500 and (kinds == 1).sum() > 500
+    assert (edge_out[N_CRAFTED:, 115] < 1.0).sum() > 300 and (edge_out[N_CRAFTED:, 115] == 1.0).sum() > 300
+
+
+def _blocks():
+    """damped sums of the edge blocks above (positive definite), then crafted ones: a zero block, a negative pivot, an
+    infinite entry, an indefinite block whose first pivots pass"""
+    rng = np.random.default_rng(5)
+    ref = EDGE_REF[N_CRAFTED:]
+    H = []
+    for k in range(1500):
+        i = rng.integers(0, len(ref), 1 + k % 4)
+        B = ref[i, 117:153].sum(0).reshape(6, 6) + ref[i, 153:189].sum(0).reshape(6, 6)
+        B[np.arange(6), np.arange(6)] *= 1.0 + [1e-3, 1e-1, 10.0][k % 3]
+        H.append(B)
+    Z = np.zeros((6, 6)); neg = np.eye(6); neg[3, 3] = -1.0; inf = np.eye(6); inf[2, 2] = np.inf
+    ind = np.eye(6); ind[4, 5] = ind[5, 4] = 2.0
+    H += [Z, neg, inf, ind]
+    H = np.stack(H)
+    r = rng.normal(size=(len(H), 6)) * 10.0 ** rng.uniform(-3, 3, (len(H), 1))
+    return H, r
+
+
+BLOCKS = _blocks()
+
+
+def test_cholesky_factor_and_solve_equal_the_model(exe):
+    H, r = BLOCKS
+    out = np.frombuffer(_run(exe, "block", np.concatenate([H.reshape(-1, 36), r], 1)), np.float64).reshape(-1, 41)
+    L, ok = pg.chol6(H)
+    assert (out[:, 0] == ok).all()
+    assert (~ok[-4:]).all() and ok[:-4].sum() > 1000       # most sums are regular (a lone edge of w_trans 0 is rank deficient)
+    g = np.flatnonzero(ok)
+    tri = np.stack([L[:, i, k] for i in range(6) for k in range(i + 1)], 1)
+    assert _same(out[g, 1:22], tri[g]).all()
+    assert _same(out[g, 22:28], pg.chol6_solve(L[g], r[g])).all()
+    assert _same(out[:, 28:34], pg._matvec6(H, r)).all()
+    assert _same(out[:, 34:40], pg._matvec6(np.transpose(H, (0, 2, 1)), r)).all()
+    assert _same(out[:, 40], pg._dot6(r, r)).all()
+    # and the solve solves: against numpy on the well-conditioned blocks
+    z = out[g, 22:28]
+    res = np.einsum("nab,nb->na", H[g], z) - r[g]
+    cond = np.linalg.cond(H[g])
+    assert (np.abs(res).max(1) <= 1e-10 * cond * np.abs(r[g]).max(1)).all()
+
+
+def test_cayley_update_equals_the_model(exe):
+    rng = np.random.default_rng(11)
+    n = 2000
+    w = rng.normal(size=(n, 3)) * 10.0 ** rng.uniform(-9, 1, (n, 1))
+    w[0] = 0.0; w[1] = [1e300, 0.0, 0.0]; w[2] = [np.nan, 0.0, 0.0]
+    R = np.stack([_rot(rng) for _ in range(n)])
+    out = np.frombuffer(_run(exe, "cayley", np.concatenate([w, R.reshape(-1, 9)], 1)), np.float64).reshape(-1, 3, 3)
+    assert _same(out, pg.cayley(w, R)).all()
+    assert _same(out[0], R[0]).all()                                        # w = 0 returns R's bits

@@ -1,7 +1,10 @@
-// bundle_math.h -- the f64 mathematics that pose refinement, link poses, link bundles, track points and window bundles share,
-// written so that a GPU lane and the host (tests/native/bundle_math_host.cpp) run the same statements: nothing of HIP or the
-// handle, no barrier, no thread index, no intrinsic.  Every caller is built with -ffp-contract=off and compared with a Python
-// model bit for bit: the association of every expression is the contract; the order of a caller's rows, views, points is its own.
+// bundle_math.h -- the f64 mathematics that pose refinement, link poses, link bundles, track points, window bundles and pose
+// graphs share: a view's rows, the point block, the scalar Cholesky factor and solve (bm_chol, bm_chol_solve, and refine_solve
+// over them: the only ones of the per-lane code) and the rule of the Levenberg-Marquardt loop.  Written so that a GPU lane and
+// the host (tests/native/bundle_math_host.cpp) run the same statements: nothing of HIP or the handle, no barrier, no thread
+// index, no intrinsic.  Every caller is built with -ffp-contract=off and compared with a Python model
+// (tests/bundle_math_model.py is this header's twin) bit for bit: the association of every expression is the contract; the
+// order of a caller's rows, views, points is its own.
 #pragma once
 #include <float.h>
 #include <math.h>
@@ -75,6 +78,83 @@ BM_INLINE double bm_sym_row(const double (&S)[6], int i, const double (&u)[3])
     const double a = i == 0 ? S[0] : (i == 1 ? S[1] : S[2]), b = i == 0 ? S[1] : (i == 1 ? S[3] : S[4]);
     const double c = i == 0 ? S[2] : (i == 1 ? S[4] : S[5]);
     return (a * u[0] + b * u[1]) + c * u[2];
+}
+
+// ---------------------------------------------------------------- the Cholesky solve, the only one of the scalar code
+// A symmetric N x N matrix travels as its lower triangle, packed by rows: N (N + 1) / 2 entries, entry (i, k) at bm_tri(i, k)
+BM_INLINE constexpr int bm_tri(int i, int k) { return i * (i + 1) / 2 + k; }   // k <= i
+
+// H = L L' by columns, in place: L holds H's lower triangle on entry and the factor on return.  The pivot of column c is
+// H(c, c) minus L(c, k)^2 for k = 0 .. c - 1, each subtracted serially in ascending k, then its square root; the entry
+// (r, c) below it is H(r, c) minus L(r, k) L(c, k), subtracted the same way, divided by the pivot's root.  False when a
+// pivot is not > 0 or not finite (bm_finite); L is then not to be used.  The factorisation carries on behind such a pivot
+// instead of returning: a return inside the unrolled columns keeps every later column's operands alive across the branch
+// (pose_refine_kernel 167 -> 231 / 255 VGPRs, tp_solve_kernel 126 -> 154: profiles/r25_kernel_resources.md).
+template <int N>
+BM_INLINE bool bm_chol(double (&L)[N * (N + 1) / 2])
+{
+    bool ok = true;
+#pragma unroll
+    for (int c = 0; c < N; ++c) {
+        double s = L[bm_tri(c, c)];
+#pragma unroll
+        for (int k = 0; k < c; ++k) s = s - L[bm_tri(c, k)] * L[bm_tri(c, k)];
+        if (!(s > 0.) || !bm_finite(s)) ok = false;
+        const double d = sqrt(s);
+        L[bm_tri(c, c)] = d;
+#pragma unroll
+        for (int r = c + 1; r < N; ++r) {
+            double v = L[bm_tri(r, c)];
+#pragma unroll
+            for (int k = 0; k < c; ++k) v = v - L[bm_tri(r, k)] * L[bm_tri(c, k)];
+            L[bm_tri(r, c)] = v / d;
+        }
+    }
+    return ok;
+}
+
+// z = (L L')^-1 r: forward (y_i = (r_i - sum_{k < i} L(i, k) y_k) / L(i, i), i ascending), then back (z_i = (y_i -
+// sum_{k > i} L(k, i) z_k) / L(i, i), i descending), each inner sum subtracted serially in ascending k
+template <int N>
+BM_INLINE void bm_chol_solve(const double (&L)[N * (N + 1) / 2], const double (&r)[N], double (&z)[N])
+{
+    double y[N];
+#pragma unroll
+    for (int i = 0; i < N; ++i) {
+        double v = r[i];
+#pragma unroll
+        for (int k = 0; k < i; ++k) v = v - L[bm_tri(i, k)] * y[k];
+        y[i] = v / L[bm_tri(i, i)];
+    }
+#pragma unroll
+    for (int i = N - 1; i >= 0; --i) {
+        double v = y[i];
+#pragma unroll
+        for (int k = i + 1; k < N; ++k) v = v - L[bm_tri(k, i)] * z[k];
+        z[i] = v / L[bm_tri(i, i)];
+    }
+}
+
+// (H + lambda diag H) d = -g for N parameters, H given as its upper triangle (row-major, N (N + 1) / 2 entries), the
+// diagonal damped as h + lambda * h, by bm_chol and bm_chol_solve with the right-hand side -g; false when the damped matrix
+// is not positive definite (d is then not to be used).  Serves pose_refine_kernel (N = 5), link_pose_kernel (6),
+// bundle_kernel (11) and tp_solve_kernel (3)
+template <int N>
+BM_INLINE bool refine_solve(const double *H, const double *g, double lambda, double *d)
+{
+    double L[N * (N + 1) / 2], r[N], z[N];
+    int q = 0;
+#pragma unroll
+    for (int i = 0; i < N; ++i)
+#pragma unroll
+        for (int j = i; j < N; ++j, ++q) L[bm_tri(j, i)] = H[q];
+#pragma unroll
+    for (int i = 0; i < N; ++i) { L[bm_tri(i, i)] = L[bm_tri(i, i)] + lambda * L[bm_tri(i, i)]; r[i] = -g[i]; }
+    const bool ok = bm_chol<N>(L);
+    bm_chol_solve<N>(L, r, z);
+#pragma unroll
+    for (int i = 0; i < N; ++i) d[i] = z[i];
+    return ok;
 }
 
 // the length of a step of n parameters: d[0]^2 first, then ascending adds (d: anything indexable)

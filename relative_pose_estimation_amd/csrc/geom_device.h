@@ -1,7 +1,8 @@
 // geom_device.h -- what geom_kernels.hip (pairs) and link_kernels.hip (links) both use, and nothing else: the polynomial
 // root chain, the deterministic f64 sums and the ordered compaction, the small 3-vector algebra, the Levenberg-Marquardt
 // loop with its parts, and the host helper of their launchers.  A helper one file uses lives in that file; what needs nothing
-// of the device (a view's rows, the point block, the rule of the loop) is in bundle_math.h, which the host tests compile too.
+// of the device (a view's rows, the point block, the Cholesky solve refine_solve, the rule of the loop) is in bundle_math.h,
+// which the host tests compile too.
 // All f64 arithmetic keeps the oracle's operation order (compiled with -ffp-contract=off).
 #pragma once
 #include "rpe_internal.h"
@@ -140,7 +141,7 @@ __device__ __forceinline__ void cross3(const double *a, const double *b, double 
     c[0] = a[1] * b[2] - a[2] * b[1]; c[1] = a[2] * b[0] - a[0] * b[2]; c[2] = a[0] * b[1] - a[1] * b[0];
 }
 
-// ------------------------------------------------------------ Levenberg-Marquardt (refine_lm and its parts; lm_loop: bundle_math.h)
+// ------------------------------------------------------------ Levenberg-Marquardt (refine_lm and its parts; lm_loop, refine_solve: bundle_math.h)
 // tangent basis of the unit sphere at t: b1 = normalise(t x e_k), k = axis of smallest |t_k| (lowest on ties), b2 = t x b1
 __device__ __forceinline__ void refine_basis(const double *t, double *b1, double *b2)
 {
@@ -175,54 +176,6 @@ __device__ __forceinline__ void refine_rotate(const double *w, const double *R, 
     for (int i = 0; i < 3; ++i)
 #pragma unroll
         for (int j = 0; j < 3; ++j) Rn[i * 3 + j] = (X[i * 3] * R[j] + X[i * 3 + 1] * R[3 + j]) + X[i * 3 + 2] * R[6 + j];
-}
-
-// (H + lambda diag H) d = -g for N parameters, H given as its upper triangle (row-major, N (N + 1) / 2 entries); false when
-// not positive definite
-template <int N>
-__device__ __forceinline__ bool refine_solve(const double *H, const double *g, double lambda, double *d)
-{
-    double L[N][N];
-    int q = 0;
-#pragma unroll
-    for (int i = 0; i < N; ++i)
-#pragma unroll
-        for (int j = i; j < N; ++j, ++q) { L[i][j] = H[q]; L[j][i] = H[q]; }
-#pragma unroll
-    for (int i = 0; i < N; ++i) L[i][i] = L[i][i] + lambda * L[i][i];
-    bool ok = true;
-#pragma unroll
-    for (int j = 0; j < N; ++j) {
-        double s = L[j][j];
-#pragma unroll
-        for (int k = 0; k < j; ++k) s -= L[j][k] * L[j][k];
-        if (!(s > 0.) || !isfinite(s)) ok = false;
-        const double dj = sqrt(s);
-        L[j][j] = dj;
-#pragma unroll
-        for (int i = j + 1; i < N; ++i) {
-            double v = L[i][j];
-#pragma unroll
-            for (int k = 0; k < j; ++k) v -= L[i][k] * L[j][k];
-            L[i][j] = v / dj;
-        }
-    }
-    double y[N];
-#pragma unroll
-    for (int i = 0; i < N; ++i) {
-        double v = -g[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) v -= L[i][k] * y[k];
-        y[i] = v / L[i][i];
-    }
-#pragma unroll
-    for (int i = N - 1; i >= 0; --i) {
-        double v = y[i];
-#pragma unroll
-        for (int k = i + 1; k < N; ++k) v -= L[k][i] * d[k];
-        d[i] = v / L[i][i];
-    }
-    return ok;
 }
 
 // The Levenberg-Marquardt loop over N parameters, shared by pose_refine_kernel, link_pose_kernel and bundle_kernel; all 256

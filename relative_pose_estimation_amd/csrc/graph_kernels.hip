@@ -1,9 +1,10 @@
 // graph_kernels.hip -- pose graphs (include/rpe_amd.h, "pose graphs"): the poses of a graph's free frames moved onto the
 // relative-pose measurements of its edges.  All f64, + - * / sqrt only, in the header's operation order.
 //
-// One launch on the handle's stream, one workgroup of 256 lanes per graph.  The host (rpe_optimise_graphs, rpe_api.hip) has
-// built the active set: the free frames, the used edges, the adjacency of every free frame (its used edges in ascending
-// position, one side bit, the free index of the other end) and the codes that need no arithmetic.  Everything of a graph
+// One launch on the handle's stream, one workgroup of 256 lanes per graph.  The host (rpe_optimise_graphs, rpe_api.hip, by
+// graph_plan.h) has built the active set: the free frames, the used edges, the adjacency of every free frame (its used edges
+// in ascending position, one side bit, the free index of the other end) and the codes that need no arithmetic; the kernel
+// indexes with these tables without a check of its own, the host tests of graph_plan.h are their check.  Everything of a graph
 // lives in the call's device buffers, one path for every size; LDS holds the four wave totals of a reduction only.
 //   state        R, T and the trial Rn, Tn per graph position (the state arrays are the output arrays)
 //   edge blocks  per used edge 120 f64, component-major ([component][used edge]: lanes of consecutive edges coalesce):
@@ -16,7 +17,8 @@
 //           three block reductions per iteration (p.Hp, r.z; the step length once per accepted step)
 //   trial   the Cayley update of every free frame, then the cost over the used edges
 // A barrier separates the phases; every decision is taken on a block-reduced value, so the control flow is uniform.
-// What a lane computes is graph_math.h's; the rule of the loop is bundle_math.h's lm_loop.
+// What a lane computes is graph_math.h's; the block's Cholesky (bm_chol<6>, bm_chol_solve<6>) and the rule of the loop
+// (lm_loop) are bundle_math.h's.
 #include "geom_device.h"
 #include "graph_math.h"
 
@@ -167,8 +169,9 @@ __global__ __launch_bounds__(256) void pg_solve_kernel(const PgArgs a)
             }
 #pragma unroll
             for (int c = 0; c < 6; ++c) { H[c * 7] = H[c * 7] + lambda * H[c * 7]; r[c] = -gr[c]; }
-            const bool ok = gm_chol6(H, L);
-            if (ok) gm_chol6_solve(L, r, z); else v[0] = v[0] + 1.;
+            gm_lower6(H, L);
+            const bool ok = bm_chol<6>(L);
+            if (ok) bm_chol_solve<6>(L, r, z); else v[0] = v[0] + 1.;
 #pragma unroll
             for (int c = 0; c < 36; ++c) fb[c * nfs + k] = H[c];
 #pragma unroll
@@ -216,7 +219,7 @@ __global__ __launch_bounds__(256) void pg_solve_kernel(const PgArgs a)
                 for (int c = 0; c < 21; ++c) L[c] = fb[(PG_FB_L + c) * nfs + k];
 #pragma unroll
                 for (int c = 0; c < 6; ++c) { x[c] = x[c] + alpha * p[c]; r[c] = r[c] - alpha * hp[c]; }
-                gm_chol6_solve(L, r, z);
+                bm_chol_solve<6>(L, r, z);
                 pg_store6(fb, PG_FB_X, nfs, k, x); pg_store6(fb, PG_FB_R, nfs, k, r); pg_store6(fb, PG_FB_Z, nfs, k, z);
                 return gm_dot6(r, z);
             });

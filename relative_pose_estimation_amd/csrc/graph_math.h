@@ -3,7 +3,8 @@
 // index, no intrinsic.  The rule is include/rpe_amd.h, "pose graphs"; every caller is built with -ffp-contract=off and compared
 // with tests/pose_graph_model.py bit for bit, so the association of every expression here is the contract.  All f64,
 // + - * / sqrt only.  Every sum starts at +0.0 and adds its terms in ascending order; a 3-vector dot product is
-// (a0*b0 + a1*b1) + a2*b2.
+// (a0*b0 + a1*b1) + a2*b2.  The factor and the solve of a frame's 6 x 6 block are bundle_math.h's bm_chol<6> and
+// bm_chol_solve<6>, with their order of operations.
 #pragma once
 #include "bundle_math.h"
 
@@ -180,49 +181,14 @@ BM_INLINE double gm_dot6(const double (&a)[6], const double (&b)[6])
     return s;
 }
 
-BM_INLINE int gm_tri(int i, int k) { return i * (i + 1) / 2 + k; }           // k <= i < 6
-
-// H = L L' by columns, L's lower triangle in 21 entries; each inner sum is subtracted serially in ascending k.  False when a
-// pivot is not > 0 or not finite (L is then not to be used)
-BM_INLINE bool gm_chol6(const double (&H)[36], double (&L)[21])
+// The lower triangle of a 6 x 6 block (row-major) as bm_chol<6> takes it (bundle_math.h: the factor and the solve of a
+// frame's block are the shared ones)
+BM_INLINE void gm_lower6(const double (&H)[36], double (&L)[21])
 {
 #pragma unroll
-    for (int c = 0; c < 6; ++c) {
-        double s = H[c * 6 + c];
+    for (int i = 0; i < 6; ++i)
 #pragma unroll
-        for (int k = 0; k < c; ++k) s = s - L[gm_tri(c, k)] * L[gm_tri(c, k)];
-        if (!(s > 0.) || !bm_finite(s)) return false;
-        const double d = sqrt(s);
-        L[gm_tri(c, c)] = d;
-#pragma unroll
-        for (int r = c + 1; r < 6; ++r) {
-            double v = H[r * 6 + c];
-#pragma unroll
-            for (int k = 0; k < c; ++k) v = v - L[gm_tri(r, k)] * L[gm_tri(c, k)];
-            L[gm_tri(r, c)] = v / d;
-        }
-    }
-    return true;
-}
-
-// z = (L L')^-1 r: forward, then back, each inner sum subtracted serially in ascending k
-BM_INLINE void gm_chol6_solve(const double (&L)[21], const double (&r)[6], double (&z)[6])
-{
-    double y[6];
-#pragma unroll
-    for (int i = 0; i < 6; ++i) {
-        double v = r[i];
-#pragma unroll
-        for (int k = 0; k < i; ++k) v = v - L[gm_tri(i, k)] * y[k];
-        y[i] = v / L[gm_tri(i, i)];
-    }
-#pragma unroll
-    for (int i = 5; i >= 0; --i) {
-        double v = y[i];
-#pragma unroll
-        for (int k = i + 1; k < 6; ++k) v = v - L[gm_tri(k, i)] * z[k];
-        z[i] = v / L[gm_tri(i, i)];
-    }
+        for (int k = 0; k <= i; ++k) L[bm_tri(i, k)] = H[i * 6 + k];
 }
 
 // Rn = C(w) R with the Cayley map C = I + (2 / (1 + a.a)) ([a]x + [a]x [a]x), a = w / 2: a rotation for every w

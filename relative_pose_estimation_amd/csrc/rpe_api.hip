@@ -2,6 +2,7 @@
 // HBM workspace, host-built tables (pyramid geometry, resize coefficients,
 // RANSAC subset stream and niters table) and stage orchestration on one HIP stream.
 #include "rpe_internal.h"
+#include "graph_plan.h"
 #include <math.h>
 #include <float.h>
 #include <string.h>
@@ -2378,8 +2379,8 @@ extern "C" int rpe_bundle_windows(rpe_handle *h, int n_tracks, const int32_t *tr
 }
 
 // ---------------------------------------------------------------- pose graphs (rpe_optimise_graphs)
-// Every check on the host first, then the active set and the tables of the kernel (RpeGraphJob), the buffers, the uploads,
-// the kernel, the fetch.  Neither the workspace nor the record of the last run is touched.
+// Every check on the host first, then the active set and the tables of the kernel (graph_plan.h, which the host tests run),
+// the buffers, the uploads, the kernel, the fetch.  Neither the workspace nor the record of the last run is touched.
 extern "C" int rpe_optimise_graphs(rpe_handle *h, int n_frames, const double *R_abs, const double *T_abs,
                                    int n_graphs, const int32_t *graph_start, const int32_t *graph_frame, const uint8_t *fixed,
                                    const int32_t *edge_start, const int32_t *edge_i, const int32_t *edge_j, const double *edge_R,
@@ -2390,96 +2391,16 @@ extern "C" int rpe_optimise_graphs(rpe_handle *h, int n_frames, const double *R_
 {
     const char *who = "rpe_optimise_graphs";
     if (!h) return rpe_invalid(h, who);
-    if (n_frames < 1) return rpe_invalid(h, who, "n_frames must be >= 1");
-    if (n_graphs < 0) return rpe_invalid(h, who, "n_graphs must be >= 0");
-    if (!(std::isfinite(huber) && huber >= 0.)) return rpe_invalid(h, who, "huber must be finite and >= 0");
-    if (max_iters < 1 || max_iters > 100) return rpe_invalid(h, who, "max_iters must be 1 ... 100");
-    if (cg_iters < 1 || cg_iters > 1000) return rpe_invalid(h, who, "cg_iters must be 1 ... 1000");
-    if (!(cg_tol >= 0. && cg_tol < 1.)) return rpe_invalid(h, who, "cg_tol must lie in [0, 1)");
+    const RpeGraphArgs args = {n_frames, R_abs, T_abs, n_graphs, graph_start, graph_frame, fixed, edge_start, edge_i, edge_j,
+                               edge_R, edge_t, edge_w, edge_kind, huber, max_iters, cg_iters, cg_tol};
+    RpeGraphPlan plan;
+    const RpeGraphRefusal no = rpe_graph_check(args, plan);
+    if (no.code) { h->err = std::string(who) + ": " + (no.text ? no.text : RPE_NULL_ARGUMENT_TEXT); return no.code; }
     if (n_graphs == 0) return RPE_OK;
-    if (!R_abs || !T_abs || !graph_start || !graph_frame || !edge_start) return rpe_invalid(h, who);
-    if (graph_start[0] != 0 || edge_start[0] != 0) return rpe_invalid(h, who, "graph_start[0] and edge_start[0] must be 0");
-    for (int g = 0; g < n_graphs; ++g) {
-        const int F = graph_start[g + 1] - graph_start[g], E = edge_start[g + 1] - edge_start[g];
-        if (F < 0 || E < 0) return rpe_invalid(h, who, "graph_start and edge_start must not decrease");
-        if (F < 2) return rpe_invalid(h, who, "a graph must have at least 2 frames");
-        if (F > RPE_GRAPH_MAX_FRAMES) { h->err = std::string(who) + ": a graph exceeds RPE_GRAPH_MAX_FRAMES"; return RPE_ERR_CAPACITY; }
-        if (E > RPE_GRAPH_MAX_EDGES) { h->err = std::string(who) + ": a graph exceeds RPE_GRAPH_MAX_EDGES"; return RPE_ERR_CAPACITY; }
-    }
+    rpe_graph_build(args, plan);
+    const std::vector<int> &ei = plan.ei, &ej = plan.ej, &free_start = plan.free_start, &used_start = plan.used_start, &precode = plan.precode;
+    const std::vector<int> &free_pos = plan.free_pos, &used_edge = plan.used_edge, &adj_start = plan.adj_start, &adj = plan.adj;
     const size_t ng = (size_t)n_graphs, nf = (size_t)graph_start[n_graphs], ne = (size_t)edge_start[n_graphs];
-    if (ne > 0 && (!edge_i || !edge_j || !edge_R || !edge_t || !edge_w || !edge_kind)) return rpe_invalid(h, who);
-    // the tables of the kernel, graph by graph
-    std::vector<int> pos_of((size_t)n_frames, -1), ei(ne), ej(ne), free_start(ng + 1, 0), used_start(ng + 1, 0), precode(ng, -1);
-    std::vector<int> free_pos, used_edge, adj_start(1, 0), adj, cnt(4 * ng), fidx, comp, stack;
-    std::vector<uint8_t> used(ne, 0);
-    std::vector<std::vector<int>> nb;
-    for (int g = 0; g < n_graphs; ++g) {
-        const int gs = graph_start[g], F = graph_start[g + 1] - gs, es = edge_start[g], E = edge_start[g + 1] - es;
-        const int32_t *f = graph_frame + gs;
-        int rc = RPE_OK;
-        for (int p = 0; p < F && !rc; ++p) {
-            if (f[p] < 0 || f[p] >= n_frames) rc = rpe_invalid(h, who, "a graph frame outside 0 ... n_frames - 1");
-            else if (pos_of[f[p]] >= 0) rc = rpe_invalid(h, who, "a frame repeated inside a graph");
-            else if (!all_finite(R_abs + (size_t)f[p] * 9, 9) || !all_finite(T_abs + (size_t)f[p] * 3, 3))
-                rc = rpe_invalid(h, who, "a non-finite pose of a frame that a graph names");
-            else pos_of[f[p]] = p;
-        }
-        for (int k = 0; k < E && !rc; ++k) {
-            const size_t e = (size_t)es + k;
-            const double *M = edge_R + 9 * e, *m = edge_t + 3 * e, *w = edge_w + 2 * e;
-            if (edge_i[e] < 0 || edge_i[e] >= n_frames || edge_j[e] < 0 || edge_j[e] >= n_frames || pos_of[edge_i[e]] < 0 || pos_of[edge_j[e]] < 0)
-                rc = rpe_invalid(h, who, "an edge end that is no frame of its graph");
-            else if (edge_i[e] == edge_j[e]) rc = rpe_invalid(h, who, "an edge from a frame to itself");
-            else if (!all_finite(M, 9) || !all_finite(m, 3) || !all_finite(w, 2)) rc = rpe_invalid(h, who, "a non-finite measurement or weight");
-            else if (!(w[0] > 0.) || !(w[1] >= 0.)) rc = rpe_invalid(h, who, "edge_w must hold w_rot > 0 and w_trans >= 0");
-            else if (edge_kind[e] != RPE_EDGE_METRIC && edge_kind[e] != RPE_EDGE_DIRECTION) rc = rpe_invalid(h, who, "an unknown edge kind");
-            else if (edge_kind[e] == RPE_EDGE_DIRECTION && m[0] == 0. && m[1] == 0. && m[2] == 0.) rc = rpe_invalid(h, who, "a direction edge with a zero direction");
-            for (int r = 0; r < 3 && !rc; ++r)
-                for (int c = 0; c < 3 && !rc; ++c) {
-                    const double d = (M[r * 3] * M[c * 3] + M[r * 3 + 1] * M[c * 3 + 1]) + M[r * 3 + 2] * M[c * 3 + 2];
-                    if (!(fabs(d - (r == c ? 1. : 0.)) <= 1e-6)) rc = rpe_invalid(h, who, "an edge_R that is not orthonormal to 1e-6");
-                }
-            if (!rc) { ei[e] = pos_of[edge_i[e]]; ej[e] = pos_of[edge_j[e]]; }
-        }
-        for (int p = 0; p < F; ++p) if (f[p] >= 0 && f[p] < n_frames && pos_of[f[p]] == p) pos_of[f[p]] = -1;   // the map serves the next graph
-        if (rc) return rc;
-        // active: joined to a fixed frame by a path of edges
-        nb.assign(F, {});
-        for (int k = 0; k < E; ++k) { nb[ei[es + k]].push_back(ej[es + k]); nb[ej[es + k]].push_back(ei[es + k]); }
-        comp.assign(F, 0);                                                  // 1: active
-        stack.clear();
-        auto is_fixed = [&](int p) { return p == 0 || (fixed && fixed[gs + p]); };
-        for (int p = 0; p < F; ++p) if (is_fixed(p)) { comp[p] = 1; stack.push_back(p); }
-        while (!stack.empty()) {
-            const int p = stack.back(); stack.pop_back();
-            for (int q : nb[p]) if (!comp[q]) { comp[q] = 1; stack.push_back(q); }
-        }
-        fidx.assign(F, -1);
-        int nfree = 0;
-        for (int p = 0; p < F; ++p) if (comp[p] && !is_fixed(p)) { fidx[p] = nfree++; free_pos.push_back(p); }
-        // used edges, and per free frame its adjacency in ascending used-edge number
-        std::vector<std::vector<int>> &inc = nb;                            // reused: per free frame (x, y) pairs
-        inc.assign(nfree, {});
-        std::vector<uint8_t> has_trans(nfree, 0);
-        int nused = 0;
-        for (int k = 0; k < E; ++k) {
-            const size_t e = (size_t)es + k;
-            const int pi = ei[e], pj = ej[e];
-            if (!comp[pi] || !comp[pj] || (fidx[pi] < 0 && fidx[pj] < 0)) continue;
-            used[e] = 1; used_edge.push_back(k);
-            if (fidx[pi] >= 0) { inc[fidx[pi]].push_back(nused << 1); inc[fidx[pi]].push_back(fidx[pj]); if (edge_w[2 * e + 1] > 0.) has_trans[fidx[pi]] = 1; }
-            if (fidx[pj] >= 0) { inc[fidx[pj]].push_back(nused << 1 | 1); inc[fidx[pj]].push_back(fidx[pi]); if (edge_w[2 * e + 1] > 0.) has_trans[fidx[pj]] = 1; }
-            ++nused;
-        }
-        for (int k = 0; k < nfree; ++k) {
-            adj.insert(adj.end(), inc[k].begin(), inc[k].end());
-            adj_start.push_back((int)(adj.size() / 2));
-        }
-        free_start[g + 1] = free_start[g] + nfree; used_start[g + 1] = used_start[g] + nused;
-        if (nused == 0) precode[g] = RPE_GRAPH_NO_EDGES;
-        else for (int k = 0; k < nfree; ++k) if (!has_trans[k]) precode[g] = RPE_GRAPH_UNDERDETERMINED;
-        cnt[4 * g] = F; cnt[4 * g + 1] = nfree; cnt[4 * g + 2] = nused; cnt[4 * g + 3] = E - nused;
-    }
     const size_t nfr = free_pos.size(), nus = used_edge.size(), nadj = adj.size() / 2, nF = (size_t)n_frames;
     HIPCHK(h, hipSetDevice(h->cfg.device));
     if (int rc = rpe_bufset_fit(h, h->set_graphs,
@@ -2508,8 +2429,8 @@ extern "C" int rpe_optimise_graphs(rpe_handle *h, int n_frames, const double *R_
     if (int rc = fetch(h, {{R_out, h->d_pg_Rout, sizeof(double) * 9 * nf}, {T_out, h->d_pg_Tout, sizeof(double) * 3 * nf},
                            {info, h->d_pg_info, sizeof(int) * 4 * ng}, {cost, h->d_pg_cost, sizeof(double) * 2 * ng},
                            {edge_chi, h->d_pg_chi, sizeof(double) * 2 * ne}})) return rc;
-    if (counts) memcpy(counts, cnt.data(), sizeof(int) * 4 * ng);
-    if (edge_used && ne > 0) memcpy(edge_used, used.data(), ne);
+    if (counts) memcpy(counts, plan.counts.data(), sizeof(int) * 4 * ng);
+    if (edge_used && ne > 0) memcpy(edge_used, plan.used.data(), ne);
     return RPE_OK;
 }
 

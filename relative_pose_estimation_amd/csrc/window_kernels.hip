@@ -16,9 +16,9 @@
 //                               waves round robin, so there is no barrier between passes and nothing per point is stored
 //                  reduce       the (6 W - 7)-square system and its right-hand side in LDS, a Cholesky by columns: every
 //                               thread forms the pivot, thread i the entry of row i, each inner sum serially in ascending
-//                               k, so it equals the scalar Cholesky of refine_solve bit for bit; the right-hand side rides
-//                               along as one more row (the forward substitution), thread 0 substitutes back; one barrier
-//                               per column
+//                               k, so it equals the scalar Cholesky of bm_chol (bundle_math.h) bit for bit; the right-hand
+//                               side rides along as one more row (the forward substitution), thread 0 substitutes back;
+//                               one barrier per column
 //                  trial        per point (lane stride 256) dp = -V^-1 (g_p + W' step), the trial X and its cost
 // A point's Jacobians are formed again in every pass: arithmetic is small next to storing 288 B per observation.
 // A view with its rows, the point block with its inverse and the rule of the loop are bundle_math.h's, as in the link kernels.

@@ -2,8 +2,8 @@
 poses, link bundles, track points and window bundles share -- the constants, the Levenberg-Marquardt acceptance rule, the
 Cholesky solve, the damped inverse of a point block, the rotation update and the tangent basis -- stated once.  Plain
 Python floats and numpy; it imports none of the models, they import it.  The scalar functions keep the library's operation
-order (one rounding per operation); tests/test_bundle_math_cpu.py compares lm_loop and damped_inverse with the header's own
-statements run on the host, bit for bit."""
+order (one rounding per operation); tests/test_bundle_math_cpu.py compares lm_loop, damped_inverse and solve with the
+header's own statements run on the host, bit for bit."""
 import math
 
 import numpy as np
@@ -60,41 +60,82 @@ def step_norm(d):
 
 
 # ---------------------------------------------------------------- the two solvers
-def solve(H, g, lam):
-    """(H + lam diag H) d = -g by the library's Cholesky (rpe_refine_poses' solver for N parameters), or None when the
-    matrix is not positive definite"""
-    N = len(g)
-    L = [[float(H[i][j]) for j in range(N)] for i in range(N)]
-    for i in range(N):
-        L[i][i] = L[i][i] + lam * L[i][i]
+def _elements(A, axes):
+    """the entries of A over its last axes as nested lists: Python floats for one system, arrays over the leading axes for
+    many -- the loops below are the same for both, and every entry keeps its own order of operations"""
+    if A.ndim == axes:
+        return A.tolist()
+    if axes == 1:
+        return [A[..., i] for i in range(A.shape[-1])]
+    return [[A[..., i, j] for j in range(A.shape[-1])] for i in range(A.shape[-2])]
+
+
+def cholesky(H):
+    """bm_chol over systems of any leading shape, H (..., N, N) symmetric (its lower triangle is read): (L, ok) with
+    H = L L', L (..., N, N) lower, and ok (...) False where a pivot is not > 0 or not finite (L is then not to be used).
+    By columns; the pivot of column c is H(c, c) minus L(c, k)^2 for k = 0 .. c - 1, each subtracted serially in ascending
+    k, then its square root; the entry (r, c) below it is H(r, c) minus L(r, k) L(c, k), subtracted the same way, divided
+    by the pivot's root"""
+    H = np.asarray(H, np.float64)
+    N = H.shape[-1]
+    a = _elements(H, 2)
+    L = [[0.0] * N for _ in range(N)]
     ok = True
-    for j in range(N):
-        sj = L[j][j]
-        for k in range(j):
-            sj -= L[j][k] * L[j][k]
-        if not (sj > 0.0) or not math.isfinite(sj):
-            ok = False
-        dj = fsqrt(sj)
-        L[j][j] = dj
-        for i in range(j + 1, N):
-            v = L[i][j]
-            for k in range(j):
-                v -= L[i][k] * L[j][k]
-            L[i][j] = fdiv(v, dj)
+    with np.errstate(all="ignore"):
+        for c in range(N):
+            s = a[c][c]
+            for k in range(c):
+                s = s - L[c][k] * L[c][k]
+            ok = ok & ((s > 0.0) & (abs(s) <= DBL_MAX))
+            d = np.sqrt(s)
+            L[c][c] = d
+            for r in range(c + 1, N):
+                v = a[r][c]
+                for k in range(c):
+                    v = v - L[r][k] * L[c][k]
+                L[r][c] = v / d
+    if H.ndim == 2:
+        return np.array(L), ok
+    out = np.zeros(H.shape)
+    for r in range(N):
+        for c in range(r + 1):
+            out[..., r, c] = L[r][c]
+    return out, ok
+
+
+def cholesky_solve(L, r):
+    """bm_chol_solve: z = (L L')^-1 r over any leading shape, L (..., N, N), r (..., N): forward, then back, each inner sum
+    subtracted serially in ascending k"""
+    L = np.asarray(L, np.float64); r = np.asarray(r, np.float64)
+    N = L.shape[-1]
+    a, b = _elements(L, 2), _elements(r, 1)
+    y, z = [0.0] * N, [0.0] * N
+    with np.errstate(all="ignore"):
+        one = np.float64(1.0)                                   # divisions as C has them, also between two Python floats
+        for i in range(N):
+            v = b[i]
+            for k in range(i):
+                v = v - a[i][k] * y[k]
+            y[i] = v * one / a[i][i]
+        for i in range(N - 1, -1, -1):
+            v = y[i]
+            for k in range(i + 1, N):
+                v = v - a[k][i] * z[k]
+            z[i] = v * one / a[i][i]
+    return np.array(z) if r.ndim == 1 else np.stack(z, -1)
+
+
+def solve(H, g, lam):
+    """refine_solve: (H + lam diag H) d = -g by the library's Cholesky (rpe_refine_poses' solver for N parameters), or None
+    when the matrix is not positive definite"""
+    A = np.array(H, np.float64)
+    i = np.arange(len(g))
+    with np.errstate(all="ignore"):
+        A[i, i] = A[i, i] + lam * A[i, i]
+    L, ok = cholesky(A)
     if not ok:
         return None
-    y = [0.0] * N; d = [0.0] * N
-    for i in range(N):
-        v = -float(g[i])
-        for k in range(i):
-            v -= L[i][k] * y[k]
-        y[i] = fdiv(v, L[i][i])
-    for i in range(N - 1, -1, -1):
-        v = y[i]
-        for k in range(i + 1, N):
-            v -= L[k][i] * d[k]
-        d[i] = fdiv(v, L[i][i])
-    return np.array(d)
+    return cholesky_solve(L, -np.asarray(g, np.float64))
 
 
 def damped_inverse(V, lam):

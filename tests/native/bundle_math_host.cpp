@@ -12,6 +12,9 @@
 //                             the step's length), one per iteration
 //                             stdout: per script one line: iters acc cost accepts, then the hooks' calls in order: L (the
 //                             state is linearised: the arrangement of refine_lm, geom_device.h), S:lambda, T:lambda, N, A
+//   bundle_math_host solve    stdin: records of 2 + N (N + 1) / 2 + N doubles: N (3, 5, 6 or 11), lambda, H's upper triangle
+//                             (row-major), g
+//                             stdout: per record 1 + N doubles: refine_solve<N>'s verdict and d (zeros when it refused)
 // Doubles travel as raw bytes, in the lm lines as hex floats.
 #include <stdio.h>
 #include <stdlib.h>
@@ -30,9 +33,19 @@ static std::vector<double> read_all()
     return v;
 }
 
+template <int N>
+static void solve_record(const double *rec)
+{
+    double out[1 + N], d[N];
+    const bool ok = refine_solve<N>(rec + 2, rec + 2 + N * (N + 1) / 2, rec[1], d);
+    out[0] = ok ? 1. : 0.;
+    for (int i = 0; i < N; ++i) out[1 + i] = ok ? d[i] : 0.;
+    fwrite(out, sizeof(double), 1 + N, stdout);
+}
+
 int main(int argc, char **argv)
 {
-    if (argc != 2) { fprintf(stderr, "usage: %s view | block | lm  (cases on stdin)\n", argv[0]); return 2; }
+    if (argc != 2) { fprintf(stderr, "usage: %s view | block | lm | solve  (cases on stdin)\n", argv[0]); return 2; }
     const std::vector<double> in = read_all();
     if (!strcmp(argv[1], "view")) {
         const size_t REC = 18;
@@ -67,6 +80,23 @@ int main(int argc, char **argv)
             memcpy(out + 9, Vi, sizeof Vi);
             for (int i = 0; i < 3; ++i) out[16 + i] = bm_sym_row(Vi, i, gp);
             fwrite(out, sizeof(double), 19, stdout);
+        }
+        return 0;
+    }
+    if (!strcmp(argv[1], "solve")) {
+        size_t o = 0;
+        while (o < in.size()) {
+            const int N = (int)in[o];
+            if (N != 3 && N != 5 && N != 6 && N != 11) return 2;
+            const size_t rec = 2 + (size_t)N * (N + 1) / 2 + N;
+            if (o + rec > in.size()) return 2;
+            // a block of the record's own length: a read past the triangle or g is a sanitizer error
+            const std::vector<double> r(in.begin() + o, in.begin() + o + rec);
+            if (N == 3) solve_record<3>(r.data());
+            else if (N == 5) solve_record<5>(r.data());
+            else if (N == 6) solve_record<6>(r.data());
+            else solve_record<11>(r.data());
+            o += rec;
         }
         return 0;
     }

@@ -8,8 +8,8 @@
 //                            JjW[36], JiD[9], JjD[9]; gm_huber's s, h, cost; h Ji'Ji[36], h Jj'Jj[36], h Ji'Jj[36], h Ji'r[6],
 //                            h Jj'r[6]
 //   graph_math_host block    stdin: records of 42 doubles H[36] r[6]
-//                            stdout: per record 41 doubles: gm_chol6's verdict and L[21] (zeros when it failed), gm_chol6_solve's
-//                            z[6] (zeros when it failed), gm_row6(H, a, r) and gm_col6(H, a, r) for a = 0 .. 5, gm_dot6(r, r)
+//                            stdout: per record 41 doubles: bm_chol<6>'s verdict on gm_lower6(H) and L[21] (zeros when it
+//                            failed), bm_chol_solve<6>'s z[6] (zeros when it failed), gm_row6(H, a, r) and gm_col6(H, a, r) for a = 0 .. 5, gm_dot6(r, r)
 //   graph_math_host cayley   stdin: records of 12 doubles w[3] R[9];  stdout: per record gm_cayley's Rn[9]
 // Doubles travel as raw bytes.
 #include <stdio.h>
@@ -69,8 +69,9 @@ int main(int argc, char **argv)
         for (size_t o = 0; o < in.size(); o += REC) {
             double H[36], r[6], L[21], z[6] = {0., 0., 0., 0., 0., 0.}, out[41];
             memcpy(H, in.data() + o, sizeof H); memcpy(r, in.data() + o + 36, sizeof r);
-            const bool ok = gm_chol6(H, L);
-            if (ok) gm_chol6_solve(L, r, z); else memset(L, 0, sizeof L);
+            gm_lower6(H, L);
+            const bool ok = bm_chol<6>(L);
+            if (ok) bm_chol_solve<6>(L, r, z); else memset(L, 0, sizeof L);
             out[0] = ok ? 1. : 0.;
             memcpy(out + 1, L, sizeof L); memcpy(out + 22, z, sizeof z);
             for (int a = 0; a < 6; ++a) { out[28 + a] = gm_row6(H, a, r); out[34 + a] = gm_col6(H, a, r); }

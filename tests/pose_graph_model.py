@@ -160,43 +160,6 @@ def grad(h, W, D, res):
     return out
 
 
-def chol6(H):
-    """the factor L (n, 6, 6; lower) of n blocks by columns and ok (n,): every pivot > 0 and finite"""
-    n = len(H)
-    L = np.zeros((n, 6, 6)); ok = np.ones(n, bool)
-    with np.errstate(all="ignore"):
-        for c in range(6):
-            s = H[:, c, c].copy()
-            for k in range(c):
-                s = s - L[:, c, k] * L[:, c, k]
-            ok &= (s > 0.0) & (np.abs(s) <= mm.DBL_MAX)
-            d = np.sqrt(s)
-            L[:, c, c] = d
-            for r in range(c + 1, 6):
-                v = H[:, r, c].copy()
-                for k in range(c):
-                    v = v - L[:, r, k] * L[:, c, k]
-                L[:, r, c] = v / d
-    return L, ok
-
-
-def chol6_solve(L, r):
-    n = len(L)
-    y = np.zeros((n, 6)); z = np.zeros((n, 6))
-    with np.errstate(all="ignore"):
-        for i in range(6):
-            v = r[:, i].copy()
-            for k in range(i):
-                v = v - L[:, i, k] * y[:, k]
-            y[:, i] = v / L[:, i, i]
-        for i in range(5, -1, -1):
-            v = y[:, i].copy()
-            for k in range(i + 1, 6):
-                v = v - L[:, k, i] * z[:, k]
-            z[:, i] = v / L[:, i, i]
-    return z
-
-
 def _dot6(a, b):
     with np.errstate(all="ignore"):
         return _sum([a[:, k] * b[:, k] for k in range(6)])
@@ -309,11 +272,11 @@ def solve_graph(R0, T0, fixed, ei, ej, M, m, w, kind, huber=0.0, max_iters=20, c
             H = H0.copy()
             for a in range(6):
                 H[:, a, a] = H[:, a, a] + lam * H[:, a, a]
-            L, ok = chol6(H)
+            L, ok = mm.cholesky(H)
             if not ok.all():
                 return False
             r = -g
-            z = chol6_solve(L, r)
+            z = mm.cholesky_solve(L, r)
             p = z.copy(); x = np.zeros((nf, 6))
             rz = reduce256(_dot6(r, z)); rz0 = rz
             tol2 = cg_tol * cg_tol
@@ -332,7 +295,7 @@ def solve_graph(R0, T0, fixed, ei, ej, M, m, w, kind, huber=0.0, max_iters=20, c
                     break
                 alpha = np.float64(rz) / np.float64(pHp)
                 x = x + alpha * p; r = r - alpha * hp
-                z = chol6_solve(L, r)
+                z = mm.cholesky_solve(L, r)
                 rzn = reduce256(_dot6(r, z))
                 moved = True; st['npcg'] += 1
                 if rzn <= tol2 * rz0:

@@ -1,6 +1,6 @@
 """relative_pose_estimation_amd/csrc/bundle_math.h on the host: the view of a point with its Jacobian rows, the point block
-with its damped adjugate inverse and the Levenberg-Marquardt acceptance rule, which pose_refine_kernel, link_pose_kernel,
-bundle_kernel, tp_solve_kernel and wb_solve_kernel all run.  tests/native/bundle_math_host.cpp runs the header's statements
+with its damped adjugate inverse, the damped Cholesky solve and the Levenberg-Marquardt acceptance rule, which
+pose_refine_kernel, link_pose_kernel, bundle_kernel, tp_solve_kernel and wb_solve_kernel all run.  tests/native/bundle_math_host.cpp runs the header's statements
 on seeded cases; it is built without floating-point contraction (the device build's setting: these results do depend on it),
 plain and with the host sanitizers.
 
@@ -8,8 +8,8 @@ Every comparison is bit for bit (the float64 words as integers); two NaNs count 
 
 References: window_bundle_model.view_rows and point_blocks (every case), link_bundle_model.rows and blocks (the cases in
 front of the camera, three views: elsewhere that model differs in the sign of a zero, as its docstring says), and
-tests/bundle_math_model.py, the header's Python twin: its damped_inverse, and for the loop its lm_loop, the one the five
-models run."""
+tests/bundle_math_model.py, the header's Python twin: its damped_inverse, its solve, and for the loop its lm_loop, the one
+the five models run."""
 import math
 import os
 import struct
@@ -238,6 +238,65 @@ def test_damped_inverse_equals_the_program(block_out):
         Vi, ok = mm.damped_inverse(V, l)
         assert (block_out[idx, 15] == ok).all() and _same(block_out[idx, 9:15], _tri(Vi)).all(), l
     assert lam[0] == 0.0 and lam[1] == 0.0                                  # the two crafted blocks were among them
+
+
+# ---------------------------------------------------------------- the solve
+SOLVE_SIZES = (3, 5, 6, 11)                      # tp_solve_kernel, pose_refine_kernel, link_pose_kernel, bundle_kernel
+
+
+def _solve_cases():
+    """(N, lambda, H (N, N), g (N,), name or None): seeded J'J systems of every size at the three dampings, J with N + 4 rows
+    (regular) or N - 1 rows (rank deficient up to rounding: either verdict, and the same one), then the crafted blocks of
+    every size: a zero block, a negative pivot, an infinite entry, an NaN entry, and an indefinite block whose first pivots
+    pass"""
+    rng = np.random.default_rng(20251104)
+    out = []
+    for N in SOLVE_SIZES:
+        for k in range(240):
+            rows = N - 1 if k % 8 == 7 else N + 4
+            J = rng.normal(size=(rows, N)) * 10.0 ** rng.uniform(-2.0, 2.0, (1, N))
+            H = J.T @ J
+            out.append((N, LAMBDAS[k % 3], (H + H.T) / 2.0, J.T @ rng.normal(size=rows), None))
+    for N in SOLVE_SIZES:
+        g = np.arange(1.0, N + 1.0)
+        neg = np.eye(N); neg[N // 2, N // 2] = -1.0
+        inf = np.eye(N); inf[1, 1] = np.inf
+        nan = np.eye(N); nan[2, 0] = nan[0, 2] = np.nan
+        ind = np.eye(N); ind[N - 2, N - 1] = ind[N - 1, N - 2] = 2.0
+        for name, H in (("zero", np.zeros((N, N))), ("negative pivot", neg), ("infinite entry", inf), ("NaN entry", nan), ("indefinite", ind)):
+            for lam in (0.0, 1e-3):
+                out.append((N, lam, H, g, name))
+    return out
+
+
+SOLVES = _solve_cases()
+
+
+def test_solve_equals_the_model(exe):
+    """refine_solve<N>, the solver under five kernels, against bundle_math_model.solve: the verdict, and d bit for bit where
+    there is one"""
+    rec = np.concatenate([np.concatenate([[float(N), lam], H[np.triu_indices(N)], g]) for N, lam, H, g, _ in SOLVES])
+    out = np.frombuffer(_run(exe, "solve", rec), np.float64)
+    assert len(out) == sum(1 + c[0] for c in SOLVES)
+    o, regular = 0, {N: 0 for N in SOLVE_SIZES}
+    for i, (N, lam, H, g, name) in enumerate(SOLVES):
+        verdict, d = out[o], out[o + 1:o + 1 + N]
+        o += 1 + N
+        ref = mm.solve(H, g, lam)
+        assert (verdict == 1.0) == (ref is not None), (i, N, lam, name)
+        if ref is None:
+            assert verdict == 0.0
+            continue
+        assert _same(d, ref).all(), (i, N, lam, name)
+        assert name is None, (N, name)                                     # every crafted block is refused
+        regular[N] += 1
+        # and the solve solves: against the damped matrix, on the well-conditioned systems
+        A = H + lam * np.diag(np.diag(H))
+        cond = np.linalg.cond(A)
+        if cond < 1e10:
+            assert np.abs(A @ d + g).max() <= 1e-10 * cond * np.abs(g).max(), (i, N, lam)
+    assert all(regular[N] >= 200 for N in SOLVE_SIZES), regular
+    assert any(c[1] == 0.0 and c[4] is None for c in SOLVES)
 
 
 # ---------------------------------------------------------------- the loop

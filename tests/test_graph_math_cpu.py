@@ -3,7 +3,8 @@ weight, the edge's blocks of the normal equations, the 6 x 6 Cholesky factor and
 pg_solve_kernel runs on a GPU lane.  tests/native/graph_math_host.cpp runs the header's statements on seeded and crafted
 cases; it is built without floating-point contraction (the device build's setting), plain and with the host sanitizers.
 
-Every comparison is with tests/pose_graph_model.py, bit for bit (the float64 words as integers); two NaNs count as equal."""
+Every comparison is with tests/pose_graph_model.py (the factor and the solve: tests/bundle_math_model.py, which that model
+calls), bit for bit (the float64 words as integers); two NaNs count as equal."""
 import os
 import subprocess
 
@@ -153,13 +154,13 @@ BLOCKS = _blocks()
 def test_cholesky_factor_and_solve_equal_the_model(exe):
     H, r = BLOCKS
     out = np.frombuffer(_run(exe, "block", np.concatenate([H.reshape(-1, 36), r], 1)), np.float64).reshape(-1, 41)
-    L, ok = pg.chol6(H)
+    L, ok = mm.cholesky(H)
     assert (out[:, 0] == ok).all()
     assert (~ok[-4:]).all() and ok[:-4].sum() > 1000       # most sums are regular (a lone edge of w_trans 0 is rank deficient)
     g = np.flatnonzero(ok)
     tri = np.stack([L[:, i, k] for i in range(6) for k in range(i + 1)], 1)
     assert _same(out[g, 1:22], tri[g]).all()
-    assert _same(out[g, 22:28], pg.chol6_solve(L[g], r[g])).all()
+    assert _same(out[g, 22:28], mm.cholesky_solve(L[g], r[g])).all()
     assert _same(out[:, 28:34], pg._matvec6(H, r)).all()
     assert _same(out[:, 34:40], pg._matvec6(np.transpose(H, (0, 2, 1)), r)).all()
     assert _same(out[:, 40], pg._dot6(r, r)).all()

@@ -1201,13 +1201,13 @@ void rpe_launch_undistort(rpe_handle *h, const float2 *d_pts, int n, const rpe_c
 }
 
 // after a batch / stream (from_batch): inliers = ransac_mask_kernel's mask of the winning model, start = d_R / d_t.
-// stage form: d_mask, d_ref_R0 / d_ref_t0 and d_pts* were uploaded by the caller.
+// stage form: d_mask, ref.R0 / ref.t0 and d_pts* were uploaded by the caller.
 void rpe_launch_refine(rpe_handle *h, const RpeRun &r, int max_iters, bool from_batch)
 {
     const int mm = h->cfg.max_matches, B = r.pairs;
     if (from_batch) launch_mask(h, r, (const int *)h->d_status);
     else rpe_launch_normalise(h, r);
-    const double *Rin = from_batch ? h->d_R : h->d_ref_R0, *tin = from_batch ? h->d_t : h->d_ref_t0;
+    const double *Rin = from_batch ? h->d_R : h->ref.R0, *tin = from_batch ? h->d_t : h->ref.t0;
     const int *status = from_batch ? h->d_status : nullptr, *inl = from_batch ? h->d_inliers : nullptr;
     // the inliers staged in LDS, or, above the cut, as 16-bit indices
     const bool lds = mm <= REFINE_LDS_MATCHES;
@@ -1217,7 +1217,7 @@ void rpe_launch_refine(rpe_handle *h, const RpeRun &r, int max_iters, bool from_
                lds ? pose_refine_kernel<true, false> : pose_refine_kernel<false, false>, dim3(B), dim3(256),
                lds ? sizeof(double2) * 2 * (size_t)mm : sizeof(unsigned short) * (size_t)mm, h->stream,
                h->d_n1, h->d_n2, h->d_mask, h->d_m_n, status, inl, h->d_K, r.cam, Rin, tin,
-               h->d_ref_R, h->d_ref_t, h->d_ref_inl, h->d_ref_info, h->d_ref_rms, mm, max_iters);
+               h->ref.R, h->ref.t, h->ref.inl, h->ref.info, h->ref.rms, mm, max_iters);
 }
 
 // ------------------------------------------------------------ homography / rotation-only
@@ -1479,7 +1479,7 @@ __global__ __launch_bounds__(256) void homography_kernel(const double2 *__restri
     }
 }
 
-// d_n1 / d_n2 (the run's, or rpe_launch_normalise's in the stage form) -> d_hg_*.  from_batch: the run's d_status and
+// d_n1 / d_n2 (the run's, or rpe_launch_normalise's in the stage form) -> hg.*.  from_batch: the run's d_status and
 // d_rstate gate the pairs and supply n_E.
 void rpe_launch_homography(rpe_handle *h, const RpeRun &r, int iters, double threshold_px, bool from_batch)
 {
@@ -1490,7 +1490,7 @@ void rpe_launch_homography(rpe_handle *h, const RpeRun &r, int iters, double thr
                from_batch ? (const int *)h->d_status : (const int *)nullptr,
                from_batch ? (const RpeRansacState *)h->d_rstate : (const RpeRansacState *)nullptr,
                (const unsigned short *)h->d_subsets, (const double *)h->d_K, r.cam, threshold_px, iters, h->cfg.ransac_max_iters,
-               mm, use_lds, h->d_hg_H, h->d_hg_R, h->d_hg_mask, h->d_hg_counts, h->d_hg_info);
+               mm, use_lds, h->hg.H, h->hg.R, h->hg.mask, h->hg.counts, h->hg.info);
 }
 
 // The kernels of this file that launch above the default dynamic LDS.  ransac_score_kernel and pose_refine_kernel stay at

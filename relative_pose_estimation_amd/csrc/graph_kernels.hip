@@ -1,7 +1,7 @@
 // graph_kernels.hip -- pose graphs (include/rpe_amd.h, "pose graphs"): the poses of a graph's free frames moved onto the
 // relative-pose measurements of its edges.  All f64, + - * / sqrt only, in the header's operation order.
 //
-// One launch on the handle's stream, one workgroup of 256 lanes per graph.  The host (rpe_optimise_graphs, rpe_api.hip, by
+// One launch on the handle's stream, one workgroup of 256 lanes per graph.  The host (rpe_optimise_graphs, rpe_features.hip, by
 // graph_plan.h) has built the active set: the free frames, the used edges, the adjacency of every free frame (its used edges
 // in ascending position, one side bit, the free index of the other end) and the codes that need no arithmetic; the kernel
 // indexes with these tables without a check of its own, the host tests of graph_plan.h are their check.  Everything of a graph
@@ -34,6 +34,8 @@
 #define PG_FB_P 69
 #define PG_FB_X 75
 #define PG_FB_HP 81
+static_assert(PG_EB == RPE_GRAPH_EDGE_DOUBLES && PG_EB_GJ + 6 == PG_EB, "pg.eb holds one edge block per used edge");
+static_assert(PG_FB == RPE_GRAPH_FRAME_DOUBLES && PG_FB_HP + 6 == PG_FB, "pg.fb holds one frame block per free frame");
 
 struct PgArgs {
     RpeGraphJob job;
@@ -291,12 +293,12 @@ __global__ __launch_bounds__(256) void pg_solve_kernel(const PgArgs a)
     }
 }
 
-// The launch of one job.  The buffers are the caller's business (rpe_optimise_graphs, rpe_api.hip)
+// The launch of one job.  The buffers are the caller's business (rpe_optimise_graphs, rpe_features.hip)
 void rpe_launch_graphs(rpe_handle *h, const RpeGraphJob &job)
 {
     PgArgs a{};
     a.job = job;
-    a.R = h->d_pg_Rout; a.T = h->d_pg_Tout; a.Rn = h->d_pg_Rn; a.Tn = h->d_pg_Tn;
-    a.eb = h->d_pg_eb; a.fb = h->d_pg_fb; a.chi = h->d_pg_chi; a.cost = h->d_pg_cost; a.info = h->d_pg_info;
+    a.R = h->pg.Rout; a.T = h->pg.Tout; a.Rn = h->pg.Rn; a.Tn = h->pg.Tn;
+    a.eb = h->pg.eb; a.fb = h->pg.fb; a.chi = h->pg.chi; a.cost = h->pg.cost; a.info = h->pg.info;
     hipLaunchKernelGGL(pg_solve_kernel, dim3(job.n_graphs), dim3(256), 0, h->stream, a);
 }

@@ -209,13 +209,13 @@ __global__ __launch_bounds__(256) void scale_links_kernel(const RpeLinkSrc src, 
     if (tid == 0) { n_shared[link] = n; code[link] = ok ? RPE_LINK_OK : RPE_LINK_TOO_FEW; }
 }
 
-// the last run's d_status / d_m_n / d_R / d_t, its match indices and the structure buffers -> d_link_stats / _n / _code of
-// the L links in d_links
+// the last run's d_status / d_m_n / d_R / d_t, its match indices and the structure buffers -> link.stats / n / code of
+// the L links in link.links
 void rpe_launch_scale_links(rpe_handle *h, int L, int min_shared)
 {
     const RpeLinkSrc src = rpe_link_src(h);
     const size_t lds = ScaleLinksLds(src.max_matches, src.kcap).total;
-    hipLaunchKernelGGL(scale_links_kernel, dim3(L), dim3(256), lds, h->stream, src, min_shared, h->d_link_stats, h->d_link_n, h->d_link_code);
+    hipLaunchKernelGGL(scale_links_kernel, dim3(L), dim3(256), lds, h->stream, src, min_shared, h->link.stats, h->link.n, h->link.code);
 }
 
 // ------------------------------------------------------------ link poses
@@ -226,7 +226,7 @@ void rpe_launch_scale_links(rpe_handle *h, int L, int min_shared)
 //            of b takes part).  The winners of b are then compacted in match order by ordered_slot (ballot / popcount):
 //            correspondence c = the c-th winner, so no atomic decides an order.
 //   list     per correspondence X (3 f64, link_point: in S's frame), q (2 f64) and b's match index (u16).  X and q live in
-//            LDS up to LP_LDS_MATCHES matches (40 B each: 20 KB at the default 500) and in d_lp_corr above it; both forms
+//            LDS up to LP_LDS_MATCHES matches (40 B each: 20 KB at the default 500) and in lp.corr above it; both forms
 //            are walked through the same pointers in the same order.  The indices are always in LDS.
 //   rounds   as the homography's: LP_ROUND = 256 samples at a time, thread j solves sample j in registers (quartic, the
 //            derivative chain with static indices, up to four poses) and parks its candidates at slot 4 j + root; the
@@ -241,7 +241,7 @@ void rpe_launch_scale_links(rpe_handle *h, int L, int min_shared)
 //   [A] max(kcap u32 table, LP_ROUND * 4 poses of 12 f64 = 96 KB): the table is dead once the list is built, the poses
 //       once the election is over (the winner's inlier flags then live there)
 //   [s_red 4 * 28 f64][X, q: 40 B * max_matches when in LDS][dense list 1024 u16][match indices max_matches u16][32 ints]
-// 120 KB at the defaults (one workgroup per CU), 141 KB at the cut, 115 KB for uncapped SIFT (8064 matches in d_lp_corr).
+// 120 KB at the defaults (one workgroup per CU), 141 KB at the cut, 115 KB for uncapped SIFT (8064 matches in lp.corr).
 #define LP_ROUND 256
 #define LP_POSE_DOUBLES 12
 #define LP_MODEL_BYTES (sizeof(double) * LP_ROUND * 4 * LP_POSE_DOUBLES)   // a round's candidates: up to four poses per sample
@@ -407,7 +407,7 @@ __device__ __forceinline__ void lp_sample(const unsigned short *__restrict__ sub
 }
 
 // The kernel's dynamic LDS (the list of the header), for the kernel's carve-up and the launcher's size: region A at 0, the
-// byte offsets of what follows it, the size.  corr_in_lds: X and q are staged here, else they are in d_lp_corr
+// byte offsets of what follows it, the size.  corr_in_lds: X and q are staged here, else they are in lp.corr
 struct LinkPoseLds {
     bool corr_in_lds = false;
     size_t red = 0, corr = 0, list = 0, idx = 0, ints = 0, total = 0;
@@ -417,7 +417,7 @@ struct LinkPoseLds {
         corr_in_lds = max_matches <= LP_LDS_MATCHES;
         red = ((bytesT > LP_MODEL_BYTES ? bytesT : LP_MODEL_BYTES) + 15) & ~(size_t)15;                   // [4 * LP_NSUM] f64
         corr = red + sizeof(double) * 4 * LP_NSUM;                                                    // [5 * max_matches] f64 when corr_in_lds
-        list = corr + (corr_in_lds ? sizeof(double) * 5 * (size_t)max_matches : 0);                   // [LP_ROUND * 4] u16
+        list = corr + (corr_in_lds ? sizeof(double) * RPE_LINK_POSE_CORR_DOUBLES * (size_t)max_matches : 0);                   // [LP_ROUND * 4] u16
         idx = list + sizeof(unsigned short) * LP_ROUND * 4;                                           // [max_matches rounded up to 8] u16
         ints = idx + sizeof(unsigned short) * (size_t)((max_matches + 7) & ~7);                       // [32] ints
         total = ints + sizeof(int) * 32;
@@ -453,7 +453,7 @@ __global__ __launch_bounds__(256) void link_pose_kernel(const RpeLinkSrc src, co
     const long long om = (long long)link * max_matches;
     int code = src.status[lv.lk.a] == RPE_PAIR_OK ? RPE_LINKPOSE_OK : RPE_LINKPOSE_PAIR_FAILED;
     int n = 0;
-    double *cX = lay.corr_in_lds ? s_corr : corr + (long long)link * 5 * max_matches, *cq = cX + 3 * (size_t)max_matches;
+    double *cX = lay.corr_in_lds ? s_corr : corr + (long long)link * RPE_LINK_POSE_CORR_DOUBLES * max_matches, *cq = cX + 3 * (size_t)max_matches;
     if (code == RPE_LINKPOSE_OK) {                                           // workgroup-uniform
         // ---- join and ordered list
         const double2 *obs = (lv.b2 ? src.n1 : src.n2) + lv.ob;                // b's point on C, its frame that is not shared
@@ -641,11 +641,11 @@ __global__ __launch_bounds__(256) void link_pose_kernel(const RpeLinkSrc src, co
     }
 }
 
-// the correspondence lists of this handle fit the kernel's LDS (else rpe_link_poses creates d_lp_corr)
+// the correspondence lists of this handle fit the kernel's LDS (else rpe_link_poses creates lp.corr)
 bool rpe_link_poses_in_lds(const rpe_handle *h) { return LinkPoseLds(h->cfg.max_matches, h->lay.kcap).corr_in_lds; }
 
-// the links in d_links over the last run r (its d_status / d_m_n / d_R / d_t, match indices, d_n1 / d_n2 and the structure
-// buffers) -> d_lp_*.  Above LP_LDS_MATCHES the lists go to d_lp_corr, which the caller has allocated.
+// the links in link.links over the last run r (its d_status / d_m_n / d_R / d_t, match indices, d_n1 / d_n2 and the structure
+// buffers) -> lp.*.  Above LP_LDS_MATCHES the lists go to lp.corr, which the caller has allocated.
 void rpe_launch_link_poses(rpe_handle *h, const RpeRun &r, int L, int iters, double threshold_px, int min_shared, int refine_iters)
 {
     const RpeLinkSrc src = rpe_link_src(h);
@@ -653,8 +653,8 @@ void rpe_launch_link_poses(rpe_handle *h, const RpeRun &r, int L, int iters, dou
     assert(lay.total <= LINK_POSE_LDS_MAX);
     launch_cam(r, link_pose_kernel<true>, link_pose_kernel<false>, dim3(L), dim3(256), lay.total, h->stream, src,
                (const unsigned short *)h->d_subsets, (const double *)h->d_K, r.cam, threshold_px, iters, h->cfg.ransac_max_iters,
-               min_shared, refine_iters, lay.corr_in_lds ? (double *)nullptr : h->d_lp_corr,
-               h->d_lp_R, h->d_lp_t, h->d_lp_mask, h->d_lp_counts, h->d_lp_info, h->d_lp_rms);
+               min_shared, refine_iters, lay.corr_in_lds ? (double *)nullptr : h->lp.corr,
+               h->lp.R, h->lp.t, h->lp.mask, h->lp.counts, h->lp.info, h->lp.rms);
 }
 
 // ------------------------------------------------------------ link bundles
@@ -667,7 +667,7 @@ void rpe_launch_link_poses(rpe_handle *h, const RpeRun &r, int L, int iters, dou
 //            the solved form (S -> A, S -> C) and the two focal scales.  The stage form uploads the same arrays.
 //   bundle   bundle_kernel, one workgroup per problem, whichever form filled the arrays: the points are compacted in index
 //            order (ordered_slot), their state (X and the trial X, 48 B per point) lives in LDS up to BA_LDS_MATCHES matches
-//            and in d_ba_state above it, walked through the same pointers in the same order; the observations are read
+//            and in ba.state above it, walked through the same pointers in the same order; the observations are read
 //            where the gather left them.  refine_lm<11> with a solve policy of its own:
 //              linearise  U (block diagonal: 15 + 21), g_c (11) and the cost: 48 sums, parked in LDS between the trials
 //              solve      per point V = Jp'Jp + lambda diag, its adjugate inverse, W (11 x 3): 66 sums of W V^-1 W', 11 of
@@ -765,7 +765,7 @@ __global__ __launch_bounds__(256) void bundle_gather_kernel(const RpeLinkSrc src
             views[om + i] = 0;
             X0[(om + i) * 3] = 0.; X0[(om + i) * 3 + 1] = 0.; X0[(om + i) * 3 + 2] = 0.;
         }
-        if (tid < 24) pose0[link * 24 + tid] = 0.;
+        if (tid < RPE_BUNDLE_POSE_DOUBLES) pose0[link * RPE_BUNDLE_POSE_DOUBLES + tid] = 0.;
         if (tid < 2) focal[link * 2 + tid] = 0.;
         if (tid == 0) { pre[link] = code; n_in[link] = 0; }
         return;
@@ -786,7 +786,7 @@ __global__ __launch_bounds__(256) void bundle_gather_kernel(const RpeLinkSrc src
             if (link_a_won(e, i)) {
                 v = 1;
                 link_point(src.points + (lv.oa + i) * 3, Ra, ta, lv.a2, X[0], X[1], X[2]);
-                double *o = obs + (om + i) * 6;
+                double *o = obs + (om + i) * RPE_BUNDLE_OBS_DOUBLES;
                 const double2 s = oS[i], a = oA[i];
                 o[0] = s.x; o[1] = s.y; o[2] = a.x; o[3] = a.y;
                 if ((e & 0xFFFFu) != LINK_NONE) {
@@ -803,7 +803,7 @@ __global__ __launch_bounds__(256) void bundle_gather_kernel(const RpeLinkSrc src
     if (tid == 0) {
         double RA[9], tA[3];
         rigid_convention(lv.a2, Ra, ta, RA, tA);                             // the solved form of A: S -> A
-        double *o = pose0 + link * 24;
+        double *o = pose0 + link * RPE_BUNDLE_POSE_DOUBLES;
         pose_store(o, o + 9, RA, tA);
         pose_store(o + 12, o + 21, RC, tC);
         focal[link * 2] = fa; focal[link * 2 + 1] = fc;
@@ -812,7 +812,7 @@ __global__ __launch_bounds__(256) void bundle_gather_kernel(const RpeLinkSrc src
 }
 
 // The kernel's dynamic LDS, for the kernel's carve-up and the launcher's size: the point state (X and the trial X, 6 f64 per
-// point) at 0 when state_in_lds, else it is in d_ba_state; the byte offset of the index list [max_matches rounded up to 8]
+// point) at 0 when state_in_lds, else it is in ba.state; the byte offset of the index list [max_matches rounded up to 8]
 // u16; the size
 struct BundleLds {
     bool state_in_lds = false;
@@ -820,7 +820,7 @@ struct BundleLds {
     __host__ __device__ constexpr BundleLds(int max_matches)
     {
         state_in_lds = max_matches <= BA_LDS_MATCHES;
-        idx = state_in_lds ? sizeof(double) * 6 * (size_t)max_matches : 0;
+        idx = state_in_lds ? sizeof(double) * RPE_BUNDLE_STATE_DOUBLES * (size_t)max_matches : 0;
         total = idx + sizeof(unsigned short) * (size_t)((max_matches + 7) & ~7);
     }
 };
@@ -847,12 +847,12 @@ __global__ __launch_bounds__(256) void bundle_kernel(const int *__restrict__ n_i
     const int prob = blockIdx.x, tid = threadIdx.x;
     const long long om = (long long)prob * max_matches;
     const BundleLds lay(max_matches);
-    double *sX = state ? state + om * 6 : (double *)s_ba, *sXn = sX + 3 * (size_t)max_matches;     // [n][3] each
+    double *sX = state ? state + om * RPE_BUNDLE_STATE_DOUBLES : (double *)s_ba, *sXn = sX + 3 * (size_t)max_matches;     // [n][3] each
     unsigned short *s_idx = (unsigned short *)(s_ba + lay.idx);
     const int M = min(max(n_in[prob], 0), max_matches);
     uint8_t *vw = views + om;
     double *pts = points + om * 3;
-    const double *ob = obs + om * 6;
+    const double *ob = obs + om * RPE_BUNDLE_OBS_DOUBLES;
     // ---- the points in index order, their state, the counts
     int n = 0, n3 = 0;
     for (int i0 = 0; i0 < M; i0 += 256) {
@@ -880,18 +880,18 @@ __global__ __launch_bounds__(256) void bundle_kernel(const int *__restrict__ n_i
         return;
     }
     double RA[9], tA[3], RC[9], tC[3], RCn[9], tCn[3], b1[3], b2[3];
-    const double *p0 = pose0 + prob * 24;                                    // the start poses: S -> A, S -> C
+    const double *p0 = pose0 + prob * RPE_BUNDLE_POSE_DOUBLES;                                    // the start poses: S -> A, S -> C
     // not two pose_load: with the two poses loaded one after the other instead of element by element, this kernel (500 of
     // 512 VGPRs) spilled 80 of them in the loop below (profiles/r14_kernel_resources.md)
 #pragma unroll
-    for (int e = 0; e < 9; ++e) { RA[e] = pose0[prob * 24 + e]; RC[e] = pose0[prob * 24 + 12 + e]; }
+    for (int e = 0; e < 9; ++e) { RA[e] = pose0[prob * RPE_BUNDLE_POSE_DOUBLES + e]; RC[e] = pose0[prob * RPE_BUNDLE_POSE_DOUBLES + 12 + e]; }
 #pragma unroll
-    for (int e = 0; e < 3; ++e) { tA[e] = pose0[prob * 24 + 9 + e]; tC[e] = pose0[prob * 24 + 21 + e]; }
+    for (int e = 0; e < 3; ++e) { tA[e] = pose0[prob * RPE_BUNDLE_POSE_DOUBLES + 9 + e]; tC[e] = pose0[prob * RPE_BUNDLE_POSE_DOUBLES + 21 + e]; }
     const double fa = focal[prob * 2], fc = focal[prob * 2 + 1];
     double lam = 0.;                                                         // the damping solve() met last: trial() builds the same blocks
     auto point = [&](int j, BaPoint &p) {
         const int i = s_idx[j];
-        ba_point(RA, tA, b1, b2, RC, tC, fa, fc, sX + 3 * j, ob + 6 * i, vw[i] == 3, p);
+        ba_point(RA, tA, b1, b2, RC, tC, fa, fc, sX + 3 * j, ob + RPE_BUNDLE_OBS_DOUBLES * i, vw[i] == 3, p);
     };
     // also leaves the tangent basis at tA in (b1, b2)
     auto linearise = [&]() {
@@ -990,7 +990,7 @@ __global__ __launch_bounds__(256) void bundle_kernel(const int *__restrict__ n_i
             double Xn[3];
 #pragma unroll
             for (int i = 0; i < 3; ++i) { Xn[i] = sX[3 * j + i] - bm_sym_row(Vi, i, u); sXn[3 * j + i] = Xn[i]; }
-            const double *q = ob + 6 * s_idx[j];
+            const double *q = ob + RPE_BUNDLE_OBS_DOUBLES * s_idx[j];
             double e[6];
             e[0] = fa * (Xn[0] / Xn[2] - q[0]); e[1] = fa * (Xn[1] / Xn[2] - q[1]);
             bm_view<false>(RAn, tAn, fa, Xn, q[2], q[3], e[2], e[3], nullptr, nullptr);
@@ -1072,23 +1072,23 @@ __global__ __launch_bounds__(256) void bundle_kernel(const int *__restrict__ n_i
     }
 }
 
-// the point state of this handle fits the kernel's LDS (else the callers create d_ba_state)
+// the point state of this handle fits the kernel's LDS (else the callers create ba.state)
 bool rpe_bundles_in_lds(const rpe_handle *h) { return BundleLds(h->cfg.max_matches).state_in_lds; }
 
-// n problems whose arrays are in d_ba_* (the stage form uploaded them, or the gather below wrote them) -> d_ba_* results
+// n problems whose arrays are in ba.* (the stage form uploaded them, or the gather below wrote them) -> ba.* results
 void rpe_launch_bundle(rpe_handle *h, int n, int min_shared, int max_iters, bool links)
 {
     const RpeLinkSrc src = rpe_link_src(h);
     const BundleLds lay(src.max_matches);
-    hipLaunchKernelGGL(bundle_kernel, dim3(n), dim3(256), lay.total, h->stream, (const int *)h->d_ba_n, (const int *)h->d_ba_pre,
-                       h->d_ba_views, (const double *)h->d_ba_obs, h->d_ba_points, (const double *)h->d_ba_pose0, (const double *)h->d_ba_focal,
-                       min_shared, max_iters, src.max_matches, lay.state_in_lds ? (double *)nullptr : h->d_ba_state,
+    hipLaunchKernelGGL(bundle_kernel, dim3(n), dim3(256), lay.total, h->stream, (const int *)h->ba.n, (const int *)h->ba.pre,
+                       h->ba.views, (const double *)h->ba.obs, h->ba.points, (const double *)h->ba.pose0, (const double *)h->ba.focal,
+                       min_shared, max_iters, src.max_matches, lay.state_in_lds ? (double *)nullptr : h->ba.state,
                        links ? src.links : (const RpeLink *)nullptr, src.points, src.R, src.t,
-                       (const double *)h->d_ba_Rin, (const double *)h->d_ba_tin,
-                       h->d_ba_Ra, h->d_ba_ta, h->d_ba_Rb, h->d_ba_tb, h->d_ba_counts, h->d_ba_info, h->d_ba_rms);
+                       (const double *)h->ba.Rin, (const double *)h->ba.tin,
+                       h->ba.Ra, h->ba.ta, h->ba.Rb, h->ba.tb, h->ba.counts, h->ba.info, h->ba.rms);
 }
 
-// the links in d_links over the last run r, the callers' poses of pair b in d_ba_Rin / d_ba_tin -> the problems' arrays
+// the links in link.links over the last run r, the callers' poses of pair b in ba.Rin / ba.tin -> the problems' arrays
 void rpe_launch_bundle_gather(rpe_handle *h, const RpeRun &r, int L, double threshold_px)
 {
     const RpeLinkSrc src = rpe_link_src(h);
@@ -1096,8 +1096,8 @@ void rpe_launch_bundle_gather(rpe_handle *h, const RpeRun &r, int L, double thre
     static_assert(sizeof(unsigned) * RPE_MAX_KCAP <= RPE_LDS_DEFAULT_BYTES, "the largest table needs no raised limit");
     const size_t lds = sizeof(unsigned) * (size_t)src.kcap;
     launch_cam(r, bundle_gather_kernel<true>, bundle_gather_kernel<false>, dim3(L), dim3(256), lds, h->stream, src,
-               (const double *)h->d_K, r.cam, (const double *)h->d_ba_Rin, (const double *)h->d_ba_tin, threshold_px,
-               h->d_ba_views, h->d_ba_obs, h->d_ba_points, h->d_ba_pose0, h->d_ba_focal, h->d_ba_pre, h->d_ba_n);
+               (const double *)h->d_K, r.cam, (const double *)h->ba.Rin, (const double *)h->ba.tin, threshold_px,
+               h->ba.views, h->ba.obs, h->ba.points, h->ba.pose0, h->ba.focal, h->ba.pre, h->ba.n);
 }
 
 // The kernels of this file that launch above the default dynamic LDS.  bundle_gather_kernel and bundle_kernel stay at or

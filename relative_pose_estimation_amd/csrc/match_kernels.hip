@@ -469,7 +469,7 @@ __global__ __launch_bounds__(256) void guided_records_kernel(const int *__restri
         const double m0 = (E[0][0] * x + E[1][0] * y) + E[2][0], m1 = (E[0][1] * x + E[1][1] * y) + E[2][1];
         o = make_double4(x, y, m0 * m0 + m1 * m1, 0.);
     }
-    rec[((long long)pair * 2 + side) * kcap + k] = o;
+    rec[((long long)pair * RPE_GUIDED_SIDES + side) * kcap + k] = o;
 }
 
 // The tile loop of match_hamming_mfma_kernel (same MFMA tile, key packing and SPLIT form; still one pass per crossCheck
@@ -515,8 +515,8 @@ __global__ __launch_bounds__(MM_NT) void match_guided_mfma_kernel(const uint8_t 
     const int n_own = pass ? n1 : n2, n_scan = pass ? n2 : n1;
     const unsigned *q32 = (const unsigned *)(desc + (long long)(pass ? img2 : img1) * kcap * 32);      // scanned: 8 dwords per descriptor
     const uint4 *d2 = (const uint4 *)(desc + (long long)(pass ? img1 : img2) * kcap * 32);             // owners
-    const double2 *rec_scan = (const double2 *)(g_rec + ((long long)pair * 2 + (pass ? 1 : 0)) * kcap);
-    const double4 *rec_own = g_rec + ((long long)pair * 2 + (pass ? 0 : 1)) * kcap;
+    const double2 *rec_scan = (const double2 *)(g_rec + ((long long)pair * RPE_GUIDED_SIDES + (pass ? 1 : 0)) * kcap);
+    const double4 *rec_own = g_rec + ((long long)pair * RPE_GUIDED_SIDES + (pass ? 0 : 1)) * kcap;
     __syncthreads();                                           // the previous pass is done with s_qpop
     fill_qpop(s_qpop, (const uint4 *)q32, n_scan);
     const int ntq = (n_scan + 31) >> 5, ntt = (n_own + 31) >> 5;
@@ -605,27 +605,27 @@ __global__ __launch_bounds__(MM_NT) void match_guided_mfma_kernel(const uint8_t 
         [&](int r, int i, unsigned key) { out.put(r, i, s_best[i] & 0x3FFFF, (int)(key >> 16)); });
 }
 
-// What both norms' guided launchers open with: the d_gm_* lists cleared and the records of the run under the poses
+// What both norms' guided launchers open with: the gm.* lists cleared and the records of the run under the poses
 static void launch_guided_records(rpe_handle *h, const RpeRun &r, const double *d_R, const double *d_t, const int *d_status, double gate_px)
 {
     const int kcap = h->lay.kcap, B = r.pairs, mm = h->cfg.max_matches;
     const RpeFeatSrc &f = r.feat;
     // -1 / zero past n_matches (an L2 distance of all-ones bits)
-    hipMemsetAsync(h->d_gm_q, 0xFF, sizeof(int) * (size_t)B * mm, h->stream);
-    hipMemsetAsync(h->d_gm_t, 0xFF, sizeof(int) * (size_t)B * mm, h->stream);
-    hipMemsetAsync(h->d_gm_d, 0xFF, sizeof(int) * (size_t)B * mm, h->stream);
-    hipMemsetAsync(h->d_gm_pts1, 0, sizeof(float2) * (size_t)B * mm, h->stream);
-    hipMemsetAsync(h->d_gm_pts2, 0, sizeof(float2) * (size_t)B * mm, h->stream);
+    hipMemsetAsync(h->gm.q, 0xFF, sizeof(int) * (size_t)B * mm, h->stream);
+    hipMemsetAsync(h->gm.t, 0xFF, sizeof(int) * (size_t)B * mm, h->stream);
+    hipMemsetAsync(h->gm.d, 0xFF, sizeof(int) * (size_t)B * mm, h->stream);
+    hipMemsetAsync(h->gm.pts1, 0, sizeof(float2) * (size_t)B * mm, h->stream);
+    hipMemsetAsync(h->gm.pts2, 0, sizeof(float2) * (size_t)B * mm, h->stream);
     const bool cam = r.cam.cams != nullptr;
     auto records = f.tab ? (cam ? guided_records_kernel<true, true> : guided_records_kernel<true, false>)
                          : (cam ? guided_records_kernel<false, true> : guided_records_kernel<false, false>);
     hipLaunchKernelGGL(records, dim3((kcap + 255) / 256, 2, B), dim3(256), 0, h->stream,
                        f.count, f.pt, f.img2_base, f.tab, kcap, (const double *)h->d_K, r.cam, d_R, d_t, d_status, gate_px,
-                       h->d_gm_rec, h->d_gm_thr2);
+                       h->gm.rec, h->gm.thr2);
 }
 
 // Guided matches of run r under the poses d_R / d_t (d_status: the run's own poses, pairs that are not OK are skipped; nullptr:
-// every pair) into the d_gm_* buffers.  The election words of the HBM form are the crossCheck matcher's d_hm_*, scratch of one
+// every pair) into the gm.* buffers.  The election words of the HBM form are the crossCheck matcher's d_hm_*, scratch of one
 // launch sequence there as here.
 void rpe_launch_guided(rpe_handle *h, const RpeRun &r, const double *d_R, const double *d_t, const int *d_status, double gate_px, int max_distance)
 {
@@ -635,8 +635,8 @@ void rpe_launch_guided(rpe_handle *h, const RpeRun &r, const double *d_R, const 
     const RpeHammingPlan p = rpe_hamming_plan(kcap, B, RPE_GUIDED_LDS_UINT4);
     launch_hamming_plan(h, r, p, match_guided_mfma_kernel<true, true>, match_guided_mfma_kernel<true, false>,
                         match_guided_mfma_kernel<false, true>, match_guided_mfma_kernel<false, false>, (const uint8_t *)nullptr,
-                        MatchBufs{h->d_gm_q, h->d_gm_t, h->d_gm_d, h->d_gm_n, h->d_gm_pts1, h->d_gm_pts2},
-                        max_distance, p.region0, (const double4 *)h->d_gm_rec, (const double *)h->d_gm_thr2);
+                        MatchBufs{h->gm.q, h->gm.t, h->gm.d, h->gm.n, h->gm.pts1, h->gm.pts2},
+                        max_distance, p.region0, (const double4 *)h->gm.rec, (const double *)h->gm.thr2);
 }
 
 // ===================================================================== L2 (SIFT)
@@ -920,8 +920,8 @@ __global__ __launch_bounds__(256) void match_l2_guided_mfma_kernel(const uint8_t
     const uint4 *d_scan = (const uint4 *)(desc + (long long)img_scan * kcap * DIM);
     const int2 *nrm_scan = norms + (long long)img_scan * kcap;
     // records: side 0 the queries' (l_0, l_1, l_2, s1), side 1 the trains' (x2, y2, s2, 0)
-    const double4 *rec_own = g_rec + ((long long)pair * 2 + pass) * kcap;
-    const double2 *rec_scan = (const double2 *)(g_rec + ((long long)pair * 2 + (pass ^ 1)) * kcap);
+    const double4 *rec_own = g_rec + ((long long)pair * RPE_GUIDED_SIDES + pass) * kcap;
+    const double2 *rec_scan = (const double2 *)(g_rec + ((long long)pair * RPE_GUIDED_SIDES + (pass ^ 1)) * kcap);
     const int j = (blockIdx.x * 4 + wv) * 32 + col;
     const bool valid_own = j < n_own;
     v4i_t bop[KS];
@@ -1128,7 +1128,7 @@ void rpe_launch_match_l2(rpe_handle *h, const RpeRun &r)
                      MatchBufs{h->d_m_q, h->d_m_t, h->d_m_d, h->d_m_n, h->d_pts1, h->d_pts2});
 }
 
-// Guided matches of run r for an L2 handle, into the d_gm_* buffers (d_gm_d read as f32); poses and d_status as in
+// Guided matches of run r for an L2 handle, into the gm.* buffers (gm.d read as f32); poses and d_status as in
 // rpe_launch_guided.  Served for both match modes: the guided rule is the mutual one, and the matrix-core form needs the norm
 // words, which a ratio-mode run of the workspace never wrote (the kernel is idempotent and O(N); the frame
 // store of every NORM_L2 handle, ratio mode included, holds its slots' words from the put).  d_m_best2 / d_m_best are scratch of one matcher launch sequence -- nothing reads
@@ -1144,9 +1144,9 @@ void rpe_launch_guided_l2(rpe_handle *h, const RpeRun &r, const double *d_R, con
     const dim3 grid = l2_mfma_grid(kcap, B);
     if (h->desc_bytes == 128)
         launch_tab(f.tab, match_l2_guided_mfma_kernel<4, true>, match_l2_guided_mfma_kernel<4, false>, grid, dim3(256), 0, h->stream,
-                   f.desc, f.norm, f.count, f.img2_base, f.tab, kcap, (const double4 *)h->d_gm_rec, (const double *)h->d_gm_thr2, max_distance, h->d_m_best2, h->d_m_best);
+                   f.desc, f.norm, f.count, f.img2_base, f.tab, kcap, (const double4 *)h->gm.rec, (const double *)h->gm.thr2, max_distance, h->d_m_best2, h->d_m_best);
     else
         launch_tab(f.tab, match_l2_guided_mfma_kernel<1, true>, match_l2_guided_mfma_kernel<1, false>, grid, dim3(256), 0, h->stream,
-                   f.desc, f.norm, f.count, f.img2_base, f.tab, kcap, (const double4 *)h->d_gm_rec, (const double *)h->d_gm_thr2, max_distance, h->d_m_best2, h->d_m_best);
-    launch_l2_select(h, r, (const unsigned long long *)h->d_m_best, MatchBufs{h->d_gm_q, h->d_gm_t, h->d_gm_d, h->d_gm_n, h->d_gm_pts1, h->d_gm_pts2});
+                   f.desc, f.norm, f.count, f.img2_base, f.tab, kcap, (const double4 *)h->gm.rec, (const double *)h->gm.thr2, max_distance, h->d_m_best2, h->d_m_best);
+    launch_l2_select(h, r, (const unsigned long long *)h->d_m_best, MatchBufs{h->gm.q, h->gm.t, h->gm.d, h->gm.n, h->gm.pts1, h->gm.pts2});
 }

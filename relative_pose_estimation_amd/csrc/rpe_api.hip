@@ -2,20 +2,17 @@
 // HBM workspace, host-built tables (pyramid geometry, resize coefficients,
 // RANSAC subset stream and niters table) and stage orchestration on one HIP stream.
 #include "rpe_internal.h"
-#include "graph_plan.h"
-#include <math.h>
+#include "rpe_host.h"
 #include <float.h>
 #include <string.h>
-#include <stdio.h>
 #include <stdlib.h>
-#include <algorithm>
 
 void rpe_orb_upload_constants(const signed char *disc, int n);
 
 std::string g_create_err;       // what rpe_last_error(NULL) returns: the failure of the last rpe_create
 
 // ---- argument heads: the checks several entry points share, each with its one message
-static int check_batch(rpe_handle *h, int B)
+int check_batch(rpe_handle *h, int B)
 {
     if (B > h->cfg.max_batch) { h->err = "batch exceeds max_batch"; return RPE_ERR_CAPACITY; }
     return RPE_OK;
@@ -25,14 +22,14 @@ static int check_stream(rpe_handle *h, int F)
     if (F > h->n_img_cap || F - 1 > h->cfg.max_batch) { h->err = "stream longer than the handle capacity (frames <= 2*max_batch, pairs <= max_batch)"; return RPE_ERR_CAPACITY; }
     return RPE_OK;
 }
-static int check_desc_counts(rpe_handle *h, const int32_t *n, int B)
+int check_desc_counts(rpe_handle *h, const int32_t *n, int B)
 {
     for (int i = 0; i < B; ++i) if (n[i] < 0 || n[i] > h->lay.kcap) { h->err = "descriptor count exceeds keypoint capacity"; return RPE_ERR_INVALID; }
     return RPE_OK;
 }
 // The byte-valued f32 descriptors of the L2 stage calls as the workspace holds them: u8 rows, the B sets of side 1 and then
 // those of side 2, each of keypoint capacity; the counts are checked on the way
-static int l2_desc_bytes(rpe_handle *h, const float *h_desc1, const int32_t *n1, const float *h_desc2, const int32_t *n2, int B, std::vector<uint8_t> &u)
+int l2_desc_bytes(rpe_handle *h, const float *h_desc1, const int32_t *n1, const float *h_desc2, const int32_t *n2, int B, std::vector<uint8_t> &u)
 {
     const size_t dim = (size_t)h->desc_bytes;               // 128 (SIFT) or 32 (ORB descriptors under NORM_L2)
     const size_t per = (size_t)h->lay.kcap * dim;
@@ -50,15 +47,14 @@ static int l2_desc_bytes(rpe_handle *h, const float *h_desc1, const int32_t *n1,
     }
     return RPE_OK;
 }
-static int check_match_counts(rpe_handle *h, const int32_t *m, int B)
+int check_match_counts(rpe_handle *h, const int32_t *m, int B)
 {
     for (int i = 0; i < B; ++i) if (m[i] < 0 || m[i] > h->cfg.max_matches) { h->err = "match count exceeds max_matches"; return RPE_ERR_INVALID; }
     return RPE_OK;
 }
 
 // ---- the fetch: a device-to-host copy on the handle's stream for every piece the caller wants (dst != NULL), one wait
-struct Copy { void *dst; const void *src; size_t bytes; };
-static int fetch(rpe_handle *h, std::initializer_list<Copy> pieces)
+int fetch(rpe_handle *h, std::initializer_list<Copy> pieces)
 {
     for (const Copy &f : pieces)
         if (f.dst) HIPCHK(h, hipMemcpyAsync(f.dst, f.src, f.bytes, hipMemcpyDeviceToHost, h->stream));
@@ -67,18 +63,18 @@ static int fetch(rpe_handle *h, std::initializer_list<Copy> pieces)
 }
 
 // ---- the upload: a host-to-device copy on the handle's stream for every piece the caller gave (src != NULL) that has bytes; no wait
-static int upload(rpe_handle *h, std::initializer_list<Copy> pieces)
+int upload(rpe_handle *h, std::initializer_list<Copy> pieces)
 {
     for (const Copy &u : pieces)
         if (u.src && u.bytes > 0) HIPCHK(h, hipMemcpyAsync(u.dst, u.src, u.bytes, hipMemcpyHostToDevice, h->stream));
     return RPE_OK;
 }
 // Both sides of the B pairs of a stage call, pair p on the workspace slots (p, B + p): the keypoint counts, the 32-byte descriptors
-static int upload_counts(rpe_handle *h, const int32_t *n1, const int32_t *n2, int B)
+int upload_counts(rpe_handle *h, const int32_t *n1, const int32_t *n2, int B)
 {
     return upload(h, {{h->d_kp_count, n1, sizeof(int) * B}, {h->d_kp_count + B, n2, sizeof(int) * B}});
 }
-static int upload_descriptors(rpe_handle *h, const uint8_t *h_desc1, const uint8_t *h_desc2, int B)
+int upload_descriptors(rpe_handle *h, const uint8_t *h_desc1, const uint8_t *h_desc2, int B)
 {
     const size_t side = (size_t)h->lay.kcap * 32 * B;
     return upload(h, {{h->d_desc, h_desc1, side}, {h->d_desc + side, h_desc2, side}});
@@ -107,12 +103,19 @@ int rpe_bufset_fit(rpe_handle *h, RpeBufSet &s, std::initializer_list<RpeBufPiec
     return RPE_OK;
 }
 
+int rpe_bufset_upload(rpe_handle *h, std::initializer_list<RpeBufPiece> pieces)
+{
+    for (const RpeBufPiece &pc : pieces)
+        if (pc.src && pc.bytes > 0) HIPCHK(h, hipMemcpyAsync(*pc.p, pc.src, pc.bytes, hipMemcpyHostToDevice, h->stream));
+    return RPE_OK;
+}
+
 // ---- argument heads of the calls behind a run: a parameter that must be finite and > 0, an array that must be finite
-static int check_positive(rpe_handle *h, const char *who, const char *name, double v)
+int check_positive(rpe_handle *h, const char *who, const char *name, double v)
 {
     return std::isfinite(v) && v > 0. ? RPE_OK : rpe_invalid(h, who, (std::string(name) + " must be finite and > 0").c_str());
 }
-static bool all_finite(const double *v, size_t n)
+bool all_finite(const double *v, size_t n)
 {
     bool fin = true;
     for (size_t i = 0; i < n; ++i) fin = fin && std::isfinite(v[i]);
@@ -726,7 +729,7 @@ static int run_orb(rpe_handle *h, const uint8_t *d_a, const uint8_t *d_b, int na
 }
 
 // keeps d_K current (re-uploaded only when the camera matrix changes)
-static int set_K(rpe_handle *h, const double K[9])
+int set_K(rpe_handle *h, const double K[9])
 {
     if (h->K_valid && memcmp(h->K_last, K, sizeof(double) * 9) == 0) return RPE_OK;      // same camera as the last batch: already resident
     memcpy(h->K_last, K, sizeof(double) * 9);
@@ -756,7 +759,7 @@ static void last_run_begin(rpe_handle *h, RpeLastRun::Kind kind, const RpeRun &r
 
 // The last run's claim on the per-match buffers ends (a stage call overwrites them, a failed launch sequence never filled
 // them); images_too: on the per-image arrays and the device pair table as well (rpe_frames_put*), nothing is left to fetch
-static void last_run_end(rpe_handle *h, bool images_too = false)
+void last_run_end(rpe_handle *h, bool images_too)
 {
     h->last.per_match = false;
     h->last.structure = 0;
@@ -773,7 +776,7 @@ static void last_run_store_changed(rpe_handle *h, bool resized)
 }
 
 // the first B pairs of the last run: what the calls behind it launch on
-static RpeRun last_run_first(const rpe_handle *h, int B)
+RpeRun last_run_first(const rpe_handle *h, int B)
 {
     RpeRun r = h->last.run;
     r.pairs = B;
@@ -782,7 +785,7 @@ static RpeRun last_run_first(const rpe_handle *h, int B)
 
 // Makes d_mask (status form), d_pose_mask and d_points current for the first B pairs of the last run: the two buffers on
 // first use, the structure kernels (again: always; otherwise only when the run is not covered that far), the record
-static int last_run_structure(rpe_handle *h, int B, bool always)
+int last_run_structure(rpe_handle *h, int B, bool always)
 {
     const size_t cap = (size_t)h->cfg.max_batch * h->cfg.max_matches;
     DM_ONCE(h, h->d_pose_mask, cap);
@@ -807,8 +810,7 @@ static int last_run_structure(rpe_handle *h, int B, bool always)
 //
 // Tested in this order, so a state gives one message whatever the call.  Two tests stay with their callers:
 // the link calls' and rpe_build_tracks' "the pairs of a batch share no frame" and rpe_fetch_overflow's slot range.
-enum : unsigned { NEED_UNCHUNKED = 1, NEED_PER_MATCH = 2, NEED_COUNT = 4, NEED_TABLE = 8 };
-static int last_run_gate(rpe_handle *h, const char *who, int n, unsigned needs)
+int last_run_gate(rpe_handle *h, const char *who, int n, unsigned needs)
 {
     const RpeLastRun &l = h->last;
     const char *why = nullptr;
@@ -820,6 +822,8 @@ static int last_run_gate(rpe_handle *h, const char *who, int n, unsigned needs)
     if (why) { h->err = std::string(who) + why; return RPE_ERR_INVALID; }
     return RPE_OK;
 }
+
+extern "C" int rpe_last_run_pairs(const rpe_handle *h) { return h ? h->last.pairs : 0; }
 
 // match -> RANSAC -> pose of run r: the tail of the image paths and the whole of a pair list
 static int run_tail(rpe_handle *h, const RpeRun &r)
@@ -1147,494 +1151,6 @@ extern "C" int rpe_fetch_match_indices(rpe_handle *h, int B, int32_t *qidx, int3
     return RPE_OK;
 }
 
-// iters and threshold_px of the calls that run a RANSAC of their own behind the last run (homography, link poses)
-static int homography_check(rpe_handle *h, const char *who, int iters, double threshold_px)
-{
-    if (iters < 1 || iters > h->cfg.ransac_max_iters) return rpe_invalid(h, who, "iters must be 1 ... ransac_max_iters");
-    return check_positive(h, who, "threshold_px", threshold_px);
-}
-
-// The argument head of the calls over links (rpe_scale_links, rpe_link_poses, rpe_link_bundles): every check on the host first (the kept
-// pair table of a list, the rule of a stream), then the structure kernels when the per-match buffers do not hold their
-// results for the whole run, and the link table on its way to d_links.  L == 0 passes the checks and does nothing more.
-static int links_begin(rpe_handle *h, const char *who, int L, const int32_t *pair_a, const int32_t *pair_b, const int32_t *side, int min_shared)
-{
-    const std::string w(who);
-    if (L < 0 || min_shared < 1 || (L > 0 && (!pair_a || !pair_b || !side))) { h->err = w + ": L < 0, min_shared < 1 or a null link array"; return RPE_ERR_INVALID; }
-    int rc = last_run_gate(h, who, h->last.pairs, NEED_UNCHUNKED | NEED_PER_MATCH | NEED_TABLE);
-    if (rc) return rc;
-    const RpeLastRun &l = h->last;
-    const bool list = l.kind == RpeLastRun::LIST;
-    if (!list && l.run.feat.img2_base != 1) { h->err = w + ": the pairs of a batch share no frame (links join the pairs of a stream or of a pair list)"; return RPE_ERR_INVALID; }
-    if (L > rpe_link_capacity(h)) { h->err = w + ": more than 4*max_batch links in one call"; return RPE_ERR_CAPACITY; }
-    std::vector<RpeLink> &tbl = h->link_tab;                // outlives the call: the upload below is asynchronous
-    tbl.assign((size_t)L, RpeLink{0, 0, 0, 0});
-    for (int i = 0; i < L; ++i) {
-        const int a = pair_a[i], b = pair_b[i], s = side[i];
-        const char *bad = nullptr;
-        if (a < 0 || a >= l.pairs || b < 0 || b >= l.pairs) bad = ": pair index outside the last run";
-        else if (a == b) bad = ": a link joins two different pairs";
-        else if (s < 0 || s > 3) bad = ": side must be 0 ... 3";
-        else if (list ? l.tab[(size_t)2 * a + (s & 1)] != l.tab[(size_t)2 * b + (s >> 1)] : a + (s & 1) != b + (s >> 1))
-            bad = ": the two pairs do not share the frame the link names";
-        if (bad) { h->err = w + bad; return RPE_ERR_INVALID; }
-        tbl[(size_t)i] = {a, b, s, 0};
-    }
-    if (L == 0) return RPE_OK;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    DM_ONCE(h, h->d_links, (size_t)rpe_link_capacity(h));
-    if ((rc = last_run_structure(h, l.pairs, false)) != RPE_OK) return rc;
-    return upload(h, {{h->d_links, tbl.data(), sizeof(RpeLink) * (size_t)L}});
-}
-
-static int scale_links_alloc(rpe_handle *h)
-{
-    const size_t lcap = (size_t)rpe_link_capacity(h);
-    return rpe_bufset_fit(h, h->set_links, {buf_piece(h->d_link_stats, lcap * 3), buf_piece(h->d_link_n, lcap), buf_piece(h->d_link_code, lcap)});
-}
-
-extern "C" int rpe_scale_links(rpe_handle *h, int L, const int32_t *pair_a, const int32_t *pair_b, const int32_t *side,
-                               int min_shared, double *stats, int32_t *n_shared, int32_t *code)
-{
-    if (!h) return rpe_invalid(h, "rpe_scale_links");
-    int rc = links_begin(h, "rpe_scale_links", L, pair_a, pair_b, side, min_shared);
-    if (rc != RPE_OK || L == 0) return rc;
-    if ((rc = scale_links_alloc(h)) != RPE_OK) return rc;
-    rpe_launch_scale_links(h, L, min_shared);
-    HIPCHK(h, hipGetLastError());
-    return fetch(h, {{stats, h->d_link_stats, sizeof(double) * 3 * (size_t)L}, {n_shared, h->d_link_n, sizeof(int) * (size_t)L},
-                     {code, h->d_link_code, sizeof(int) * (size_t)L}});
-}
-
-// d_lp_corr: 0 bytes, so null, on handles whose kernel keeps the correspondence lists in LDS
-static int link_poses_alloc(rpe_handle *h)
-{
-    const size_t lcap = (size_t)rpe_link_capacity(h), mm = (size_t)h->cfg.max_matches;
-    return rpe_bufset_fit(h, h->set_link_poses,
-                          {buf_piece(h->d_lp_R, lcap * 9), buf_piece(h->d_lp_t, lcap * 3), buf_piece(h->d_lp_rms, lcap * 2),
-                           buf_piece(h->d_lp_counts, lcap * 2), buf_piece(h->d_lp_info, lcap * 4), buf_piece(h->d_lp_mask, lcap * mm),
-                           buf_piece(h->d_lp_corr, rpe_link_poses_in_lds(h) ? 0 : lcap * 5 * mm)});
-}
-
-// rpe_link_poses: the links' argument head, its own three checks (all before anything is launched), the buffers on first
-// use, one kernel, one fetch.  Nothing of the run is written.
-extern "C" int rpe_link_poses(rpe_handle *h, int L, const int32_t *pair_a, const int32_t *pair_b, const int32_t *side,
-                              int iters, double threshold_px, int min_shared, int refine_iters,
-                              double *R, double *t, uint8_t *mask, int32_t *counts, int32_t *info, double *rms)
-{
-    if (!h) return rpe_invalid(h, "rpe_link_poses");
-    int rc = homography_check(h, "rpe_link_poses", iters, threshold_px);
-    if (rc) return rc;
-    if (refine_iters < 0 || refine_iters > 100) return rpe_invalid(h, "rpe_link_poses", "refine_iters must be 0 ... 100");
-    rc = links_begin(h, "rpe_link_poses", L, pair_a, pair_b, side, min_shared);
-    if (rc != RPE_OK || L == 0) return rc;
-    if ((rc = link_poses_alloc(h)) != RPE_OK) return rc;
-    rpe_launch_link_poses(h, h->last.run, L, iters, threshold_px, min_shared, refine_iters);
-    HIPCHK(h, hipGetLastError());
-    const size_t n = (size_t)L, mm = (size_t)h->cfg.max_matches;
-    return fetch(h, {{R, h->d_lp_R, sizeof(double) * 9 * n}, {t, h->d_lp_t, sizeof(double) * 3 * n}, {mask, h->d_lp_mask, n * mm},
-                     {counts, h->d_lp_counts, sizeof(int) * 2 * n}, {info, h->d_lp_info, sizeof(int) * 4 * n}, {rms, h->d_lp_rms, sizeof(double) * 2 * n}});
-}
-
-// link bundles: the buffers of both forms; d_ba_state: 0 bytes, so null, on handles whose kernel keeps the point state in LDS
-static int bundle_alloc(rpe_handle *h)
-{
-    const size_t lcap = (size_t)rpe_link_capacity(h), mm = (size_t)h->cfg.max_matches;
-    return rpe_bufset_fit(h, h->set_bundles,
-                          {buf_piece(h->d_ba_views, lcap * mm), buf_piece(h->d_ba_obs, lcap * mm * 6), buf_piece(h->d_ba_points, lcap * mm * 3),
-                           buf_piece(h->d_ba_pose0, lcap * 24), buf_piece(h->d_ba_focal, lcap * 2), buf_piece(h->d_ba_n, lcap), buf_piece(h->d_ba_pre, lcap),
-                           buf_piece(h->d_ba_Rin, lcap * 9), buf_piece(h->d_ba_tin, lcap * 3),
-                           buf_piece(h->d_ba_Ra, lcap * 9), buf_piece(h->d_ba_ta, lcap * 3), buf_piece(h->d_ba_Rb, lcap * 9), buf_piece(h->d_ba_tb, lcap * 3),
-                           buf_piece(h->d_ba_counts, lcap * 2), buf_piece(h->d_ba_info, lcap * 4), buf_piece(h->d_ba_rms, lcap * 2),
-                           buf_piece(h->d_ba_state, rpe_bundles_in_lds(h) ? 0 : lcap * mm * 6)});
-}
-
-static int bundle_fetch(rpe_handle *h, size_t n, double *R_a, double *t_a, double *R_b, double *t_b, double *points, uint8_t *views,
-                        int32_t *counts, int32_t *info, double *rms)
-{
-    const size_t mm = (size_t)h->cfg.max_matches;
-    return fetch(h, {{R_a, h->d_ba_Ra, sizeof(double) * 9 * n}, {t_a, h->d_ba_ta, sizeof(double) * 3 * n}, {R_b, h->d_ba_Rb, sizeof(double) * 9 * n},
-                     {t_b, h->d_ba_tb, sizeof(double) * 3 * n}, {points, h->d_ba_points, sizeof(double) * 3 * n * mm}, {views, h->d_ba_views, n * mm},
-                     {counts, h->d_ba_counts, sizeof(int) * 2 * n}, {info, h->d_ba_info, sizeof(int) * 4 * n}, {rms, h->d_ba_rms, sizeof(double) * 2 * n}});
-}
-
-// rpe_link_bundles: its own checks and the links' argument head (all before anything is launched), the buffers on first
-// use, the poses of pair b up, two kernels, one fetch.  Nothing of the run is written.
-extern "C" int rpe_link_bundles(rpe_handle *h, int L, const int32_t *pair_a, const int32_t *pair_b, const int32_t *side,
-                                const double *R0, const double *t0, double threshold_px, int min_shared, int max_iters,
-                                double *R_a, double *t_a, double *R_b, double *t_b, double *points, uint8_t *views,
-                                int32_t *counts, int32_t *info, double *rms)
-{
-    if (!h) return rpe_invalid(h, "rpe_link_bundles");
-    if (int rc = check_positive(h, "rpe_link_bundles", "threshold_px", threshold_px)) return rc;
-    if (max_iters < 1 || max_iters > 100) return rpe_invalid(h, "rpe_link_bundles", "max_iters must be 1 ... 100");
-    if ((R0 == nullptr) != (t0 == nullptr) || (L > 0 && !R0)) return rpe_invalid(h, "rpe_link_bundles", "R0 and t0 must both be given");
-    const size_t n = (size_t)std::max(L, 0);
-    if (R0 && (!all_finite(R0, 9 * n) || !all_finite(t0, 3 * n))) return rpe_invalid(h, "rpe_link_bundles", "a pose has a non-finite entry");
-    int rc = links_begin(h, "rpe_link_bundles", L, pair_a, pair_b, side, min_shared);
-    if (rc != RPE_OK || L == 0) return rc;
-    if ((rc = bundle_alloc(h)) != RPE_OK) return rc;
-    if ((rc = upload(h, {{h->d_ba_Rin, R0, sizeof(double) * 9 * n}, {h->d_ba_tin, t0, sizeof(double) * 3 * n}})) != RPE_OK) return rc;
-    rpe_launch_bundle_gather(h, h->last.run, L, threshold_px);
-    rpe_launch_bundle(h, L, min_shared, max_iters, true);
-    HIPCHK(h, hipGetLastError());
-    // the wait also covers the upload: the poses have left the caller's arrays
-    return bundle_fetch(h, n, R_a, t_a, R_b, t_b, points, views, counts, info, rms);
-}
-
-// rpe_bundle_three_view: the problems' arrays packed on the host as the gather kernel leaves them, one kernel, one fetch
-extern "C" int rpe_bundle_three_view(rpe_handle *h, int B, const int32_t *n, const double *obs_s, const double *obs_a,
-                                     const double *obs_c, const uint8_t *has_c, const double *X0, const double *Ra0, const double *ta0,
-                                     const double *Rc0, const double *tc0, double f_a, double f_c, int max_iters,
-                                     double *R_a, double *t_a, double *R_c, double *t_c, double *points, uint8_t *views,
-                                     int32_t *counts, int32_t *info, double *rms)
-{
-    if (!h || !n || !obs_s || !obs_a || !obs_c || !has_c || !X0 || !Ra0 || !ta0 || !Rc0 || !tc0 || B < 1) return rpe_invalid(h, "rpe_bundle_three_view");
-    if (int rc = check_batch(h, B)) return rc;
-    if (max_iters < 1 || max_iters > 100) return rpe_invalid(h, "rpe_bundle_three_view", "max_iters must be 1 ... 100");
-    if (!std::isfinite(f_a) || !(f_a > 0.) || !std::isfinite(f_c) || !(f_c > 0.)) return rpe_invalid(h, "rpe_bundle_three_view", "f_a and f_c must be finite and > 0");
-    int rc = check_match_counts(h, n, B);
-    if (rc) return rc;
-    const size_t nb = (size_t)B, mm = (size_t)h->cfg.max_matches;
-    if (!all_finite(Ra0, 9 * nb) || !all_finite(ta0, 3 * nb) || !all_finite(Rc0, 9 * nb) || !all_finite(tc0, 3 * nb))
-        return rpe_invalid(h, "rpe_bundle_three_view", "a pose has a non-finite entry");
-    std::vector<uint8_t> vw(nb * mm, 0);
-    std::vector<double> ob(nb * mm * 6, 0.), x0(nb * mm * 3, 0.), pose(nb * 24), foc(nb * 2);
-    std::vector<int> pre(nb, RPE_BUNDLE_OK);
-    for (size_t p = 0; p < nb; ++p) {
-        for (size_t i = 0; i < (size_t)n[p]; ++i) {
-            const size_t k = p * mm + i;
-            vw[k] = has_c[k] ? 3 : 1;
-            ob[k * 6] = obs_s[k * 2]; ob[k * 6 + 1] = obs_s[k * 2 + 1]; ob[k * 6 + 2] = obs_a[k * 2]; ob[k * 6 + 3] = obs_a[k * 2 + 1];
-            if (has_c[k]) { ob[k * 6 + 4] = obs_c[k * 2]; ob[k * 6 + 5] = obs_c[k * 2 + 1]; }
-            for (int e = 0; e < 3; ++e) x0[k * 3 + e] = X0[k * 3 + e];
-        }
-        for (int e = 0; e < 9; ++e) { pose[p * 24 + e] = Ra0[p * 9 + e]; pose[p * 24 + 12 + e] = Rc0[p * 9 + e]; }
-        for (int e = 0; e < 3; ++e) { pose[p * 24 + 9 + e] = ta0[p * 3 + e]; pose[p * 24 + 21 + e] = tc0[p * 3 + e]; }
-        foc[p * 2] = f_a; foc[p * 2 + 1] = f_c;
-    }
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    if ((rc = bundle_alloc(h)) != RPE_OK) return rc;
-    if ((rc = upload(h, {{h->d_ba_views, vw.data(), vw.size()}, {h->d_ba_obs, ob.data(), sizeof(double) * ob.size()},
-                         {h->d_ba_points, x0.data(), sizeof(double) * x0.size()}, {h->d_ba_pose0, pose.data(), sizeof(double) * pose.size()},
-                         {h->d_ba_focal, foc.data(), sizeof(double) * foc.size()}, {h->d_ba_pre, pre.data(), sizeof(int) * nb},
-                         {h->d_ba_n, n, sizeof(int) * nb}})) != RPE_OK) return rc;
-    rpe_launch_bundle(h, B, 1, max_iters, false);
-    HIPCHK(h, hipGetLastError());
-    // the wait also covers the uploads: the staging vectors live until it returns
-    return bundle_fetch(h, nb, R_a, t_a, R_c, t_c, points, views, counts, info, rms);
-}
-
-// ---- multi-view tracks (rpe_build_tracks / rpe_tracks_from_matches)
-// the buffers of both forms: per match slot, then per node and per frame of this call's n_frames
-static int tracks_alloc(rpe_handle *h, int n_frames)
-{
-    const size_t MB = (size_t)h->cfg.max_batch, cap = MB * h->cfg.max_matches;
-    const int N = n_frames * h->lay.kcap;
-    return rpe_bufset_fit(h, h->set_tracks,
-                          {buf_piece(h->d_tk_eflag, cap), buf_piece(h->d_tk_edge, cap), buf_piece(h->d_tk_use, MB),
-                           buf_piece(h->d_tk_mtrack, cap), buf_piece(h->d_tk_q, cap), buf_piece(h->d_tk_t, cap), buf_piece(h->d_tk_m, MB),
-                           buf_piece(h->d_tk_counts, 8), buf_piece(h->d_tk_tstart, cap + 1), buf_piece(h->d_tk_oframe, 2 * cap), buf_piece(h->d_tk_okp, 2 * cap),
-                           buf_piece(h->d_tk_oxy, 2 * cap), buf_piece(h->d_tk_pts1, cap), buf_piece(h->d_tk_pts2, cap), buf_piece(h->d_tk_frames, MB),
-                           buf_piece(h->d_tk_node, (size_t)RPE_TRACK_NODE_WORDS * N), buf_piece(h->d_tk_partial, (size_t)rpe_track_scan_blocks(N)),
-                           buf_piece(h->d_tk_seen, (size_t)n_frames)});
-}
-
-// min_len, and the node ids and edge ids of n_frames frames must fit an int.  frames_what: the refusal in the caller's terms
-static int tracks_check(rpe_handle *h, const char *who, int n_frames, int min_len, const char *frames_what)
-{
-    if (min_len < 2) return rpe_invalid(h, who, "min_len must be >= 2");
-    if (n_frames < 1 || (long long)n_frames * h->lay.kcap >= (1LL << 31)) return rpe_invalid(h, who, frames_what);
-    if ((long long)h->cfg.max_batch * h->cfg.max_matches >= (1LL << 30)) return rpe_invalid(h, who, "max_batch * max_matches must be < 2^30");
-    return RPE_OK;
-}
-
-// the frame table up, the kernels, counts first and then the used prefixes
-static int tracks_run(rpe_handle *h, RpeTrackJob job, int32_t *counts, int32_t *track_start, int32_t *obs_frame, int32_t *obs_kp,
-                      float *obs_xy, int32_t *match_track)
-{
-    const size_t P = (size_t)job.P;
-    if (int rc = upload(h, {{h->d_tk_frames, h->tk_frame_tab.data(), sizeof(int2) * P}})) return rc;
-    job.frames = h->d_tk_frames;
-    rpe_launch_tracks(h, job);
-    HIPCHK(h, hipGetLastError());
-    int32_t c[6];
-    if (int rc = fetch(h, {{c, h->d_tk_counts, sizeof(c)}})) return rc;
-    if (counts) memcpy(counts, c, sizeof(c));
-    const size_t nt = (size_t)c[0], no = (size_t)c[1];
-    return fetch(h, {{track_start, h->d_tk_tstart, sizeof(int) * (nt + 1)}, {obs_frame, h->d_tk_oframe, sizeof(int) * no},
-                     {obs_kp, h->d_tk_okp, sizeof(int) * no}, {obs_xy, h->d_tk_oxy, sizeof(float2) * no},
-                     {match_track, h->d_tk_mtrack, sizeof(int) * P * h->cfg.max_matches}});
-}
-
-extern "C" int rpe_last_run_pairs(const rpe_handle *h) { return h ? h->last.pairs : 0; }
-
-// rpe_build_tracks: every check on the host first, the buffers, the structure kernels when the rule reads masks that are
-// not current, the kernels, the fetch.  Nothing of the run is written.
-extern "C" int rpe_build_tracks(rpe_handle *h, const uint8_t *use_pair, int edge_rule, int min_len,
-                                int32_t *counts, int32_t *track_start, int32_t *obs_frame, int32_t *obs_kp, float *obs_xy,
-                                int32_t *match_track)
-{
-    if (!h) return rpe_invalid(h, "rpe_build_tracks");
-    if (edge_rule < RPE_TRACK_EDGES_USABLE || edge_rule > RPE_TRACK_EDGES_ALL) return rpe_invalid(h, "rpe_build_tracks", "edge_rule must be 0 ... 2");
-    int rc = last_run_gate(h, "rpe_build_tracks", h->last.pairs, NEED_UNCHUNKED | NEED_PER_MATCH | NEED_TABLE);
-    if (rc) return rc;
-    const RpeLastRun &l = h->last;
-    const bool list = l.kind == RpeLastRun::LIST;
-    // a batch of one pair has img2_base == 1 like a stream of two frames: it is served as that stream (the header says so)
-    if (!list && l.run.feat.img2_base != 1) return rpe_invalid(h, "rpe_build_tracks", "the pairs of a batch share no frame (links join the pairs of a stream or of a pair list)");
-    const int P = l.pairs, n_frames = list ? h->fs.cap : P + 1;
-    if ((rc = tracks_check(h, "rpe_build_tracks", n_frames, min_len,
-                           "the frames of the run (a pair list: the store's capacity) times the keypoint capacity must be < 2^31")) != RPE_OK) return rc;
-    h->tk_frame_tab.resize((size_t)2 * P);
-    for (int p = 0; p < P; ++p) {
-        h->tk_frame_tab[(size_t)2 * p] = list ? l.tab[(size_t)2 * p] : p;
-        h->tk_frame_tab[(size_t)2 * p + 1] = list ? l.tab[(size_t)2 * p + 1] : p + 1;
-    }
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    if ((rc = tracks_alloc(h, n_frames)) != RPE_OK) return rc;
-    if (edge_rule != RPE_TRACK_EDGES_ALL && (rc = last_run_structure(h, P, false)) != RPE_OK) return rc;
-    if ((rc = upload(h, {{h->d_tk_use, use_pair, (size_t)P}})) != RPE_OK) return rc;
-    const RpeTrackJob job = {P, n_frames, edge_rule, min_len, nullptr, h->d_m_n, h->d_m_q, h->d_m_t, use_pair ? h->d_tk_use : nullptr, nullptr,
-                             h->d_status, h->d_mask, h->d_pose_mask, h->d_pts1, h->d_pts2};
-    // the first wait also covers the uploads: use_pair has left the caller's array
-    return tracks_run(h, job, counts, track_start, obs_frame, obs_kp, obs_xy, match_track);
-}
-
-// rpe_tracks_from_matches: the caller's lists into the track buffers, the same kernels under RPE_TRACK_EDGES_ALL.  Neither
-// the workspace nor the record of the last run is touched.
-extern "C" int rpe_tracks_from_matches(rpe_handle *h, int P, int n_frames, const int32_t *frame1, const int32_t *frame2, const int32_t *m,
-                                       const int32_t *qidx, const int32_t *tidx, const uint8_t *edge, const float *pts1, const float *pts2,
-                                       int min_len, int32_t *counts, int32_t *track_start, int32_t *obs_frame, int32_t *obs_kp,
-                                       float *obs_xy, int32_t *match_track)
-{
-    const char *who = "rpe_tracks_from_matches";
-    if (!h || P < 0 || (P > 0 && (!frame1 || !frame2 || !m || !qidx || !tidx))) return rpe_invalid(h, who);
-    if (int rc = check_batch(h, P)) return rc;
-    int rc = tracks_check(h, who, n_frames, min_len, "n_frames must be >= 1 and n_frames * keypoint capacity < 2^31");
-    if (rc) return rc;
-    if ((pts1 == nullptr) != (pts2 == nullptr)) return rpe_invalid(h, who, "pts1 and pts2 must both be given or both be NULL");
-    if ((rc = check_match_counts(h, m, P)) != RPE_OK) return rc;
-    const size_t mm = (size_t)h->cfg.max_matches;
-    const int KC = h->lay.kcap;
-    for (int p = 0; p < P; ++p) {
-        if (frame1[p] < 0 || frame1[p] >= n_frames || frame2[p] < 0 || frame2[p] >= n_frames) return rpe_invalid(h, who, "a frame index outside 0 ... n_frames - 1");
-        for (size_t i = 0; i < (size_t)m[p]; ++i) {
-            const int q = qidx[p * mm + i], t = tidx[p * mm + i];
-            if (q < 0 || q >= KC || t < 0 || t >= KC) return rpe_invalid(h, who, "a keypoint index outside 0 ... keypoint capacity - 1");
-        }
-    }
-    if (P == 0) {
-        if (counts) memset(counts, 0, sizeof(int32_t) * 6);
-        if (track_start) track_start[0] = 0;
-        return RPE_OK;
-    }
-    h->tk_frame_tab.resize((size_t)2 * P);
-    for (int p = 0; p < P; ++p) { h->tk_frame_tab[(size_t)2 * p] = frame1[p]; h->tk_frame_tab[(size_t)2 * p + 1] = frame2[p]; }
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    if ((rc = tracks_alloc(h, n_frames)) != RPE_OK) return rc;
-    const size_t n = (size_t)P * mm;
-    if ((rc = upload(h, {{h->d_tk_m, m, sizeof(int) * (size_t)P}, {h->d_tk_q, qidx, sizeof(int) * n}, {h->d_tk_t, tidx, sizeof(int) * n},
-                         {h->d_tk_edge, edge, n}, {h->d_tk_pts1, pts1, sizeof(float2) * n}, {h->d_tk_pts2, pts2, sizeof(float2) * n}})) != RPE_OK) return rc;
-    const RpeTrackJob job = {P, n_frames, RPE_TRACK_EDGES_ALL, min_len, nullptr, h->d_tk_m, h->d_tk_q, h->d_tk_t, nullptr, edge ? h->d_tk_edge : nullptr,
-                             nullptr, nullptr, nullptr, pts1 ? h->d_tk_pts1 : nullptr, pts1 ? h->d_tk_pts2 : nullptr};
-    // the first wait also covers the uploads: the lists have left the caller's arrays
-    return tracks_run(h, job, counts, track_start, obs_frame, obs_kp, obs_xy, match_track);
-}
-
-// refined poses: device buffers on first use, launch, fetch
-static int refine_alloc(rpe_handle *h)
-{
-    const size_t MB = (size_t)h->cfg.max_batch;
-    return rpe_bufset_fit(h, h->set_refine,
-                          {buf_piece(h->d_ref_R, MB * 9), buf_piece(h->d_ref_t, MB * 3), buf_piece(h->d_ref_rms, MB * 2),
-                           buf_piece(h->d_ref_R0, MB * 9), buf_piece(h->d_ref_t0, MB * 3), buf_piece(h->d_ref_inl, MB), buf_piece(h->d_ref_info, MB * 4)});
-}
-
-static int refine_run(rpe_handle *h, const RpeRun &r, int max_iters, bool from_batch, double *R, double *t, int32_t *inliers,
-                      int32_t *info, double *rms)
-{
-    const int B = r.pairs;
-    rpe_launch_refine(h, r, max_iters, from_batch);
-    HIPCHK(h, hipGetLastError());
-    return fetch(h, {{R, h->d_ref_R, sizeof(double) * 9 * B}, {t, h->d_ref_t, sizeof(double) * 3 * B}, {inliers, h->d_ref_inl, sizeof(int) * B},
-                     {info, h->d_ref_info, sizeof(int) * 4 * B}, {rms, h->d_ref_rms, sizeof(double) * 2 * B}});
-}
-
-extern "C" int rpe_refine_poses(rpe_handle *h, int B, int max_iters, double *R, double *t, int32_t *inliers,
-                                int32_t *info, double *rms)
-{
-    if (!h || B < 1 || B > h->cfg.max_batch) return rpe_invalid(h, "rpe_refine_poses");
-    if (max_iters < 1 || max_iters > 100) return rpe_invalid(h, "rpe_refine_poses", "max_iters must be 1 ... 100");
-    int rc = last_run_gate(h, "rpe_refine_poses", B, NEED_UNCHUNKED | NEED_PER_MATCH | NEED_COUNT);
-    if (rc) return rc;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    if ((rc = refine_alloc(h)) != RPE_OK) return rc;
-    return refine_run(h, last_run_first(h, B), max_iters, true, R, t, inliers, info, rms);
-}
-
-// ---------------------------------------------------------------- guided matching
-// rpe_guided_matches / rpe_match_hamming_guided and their L2 forms rpe_guided_matches_l2 / rpe_match_l2_guided (NOT in the
-// reference): the mutual-nearest-neighbour match again, among the keypoint pairs that pass the Sampson gate of a pose.
-// Results go to the d_gm_* buffers (d_gm_d: int32 Hamming or f32 L2 distances); nothing of the run's results is written.
-// norm: the norm the entry point serves; max_distance: an integer 0 ... 256 for Hamming, >= 0 or +inf for L2.
-static int guided_check(rpe_handle *h, const char *who, int norm, int B, const double *R, const double *t, double gate_px, double max_distance)
-{
-    const std::string w(who);
-    const bool l2 = norm == RPE_NORM_L2;
-    if (h->cfg.norm_type != norm) {
-        h->err = w + (l2 ? ": L2 handles only (RPE_NORM_L2: SIFT, or ORB bytes under L2)" : ": Hamming handles only (ORB with RPE_NORM_HAMMING)");
-        return RPE_ERR_INVALID;
-    }
-    if (int rc = check_positive(h, who, "gate_px", gate_px)) return rc;
-    if (l2 ? !(max_distance >= 0.) : (max_distance < 0 || max_distance > 256)) {
-        h->err = w + (l2 ? ": max_distance must be >= 0 (+inf: no bound)" : ": max_distance must be 0 ... 256");
-        return RPE_ERR_INVALID;
-    }
-    if ((R == nullptr) != (t == nullptr)) { h->err = w + ": R and t must both be given or both be NULL"; return RPE_ERR_INVALID; }
-    if (R && (!all_finite(R, (size_t)9 * B) || !all_finite(t, (size_t)3 * B))) { h->err = w + ": a pose has a non-finite entry"; return RPE_ERR_INVALID; }
-    return RPE_OK;
-}
-
-static int guided_alloc(rpe_handle *h)
-{
-    const size_t MB = (size_t)h->cfg.max_batch, cap = MB * h->cfg.max_matches;
-    return rpe_bufset_fit(h, h->set_guided,
-                          {buf_piece(h->d_gm_q, cap), buf_piece(h->d_gm_t, cap), buf_piece(h->d_gm_d, cap), buf_piece(h->d_gm_n, MB),
-                           buf_piece(h->d_gm_pts1, cap), buf_piece(h->d_gm_pts2, cap), buf_piece(h->d_gm_R, MB * 9), buf_piece(h->d_gm_tr, MB * 3), buf_piece(h->d_gm_thr2, MB),
-                           buf_piece(h->d_gm_rec, MB * 2 * h->lay.kcap)});
-}
-
-// poses up (R == nullptr: the run's own, and its status words), launch, fetch
-static int guided_run(rpe_handle *h, const RpeRun &r, const double *R, const double *t, double gate_px, double max_distance,
-                      int32_t *qidx, int32_t *tidx, void *dist, float *pts1, float *pts2, int32_t *n_matches)
-{
-    const size_t B = (size_t)r.pairs, n = B * h->cfg.max_matches;
-    if (int rc = upload(h, {{h->d_gm_R, R, sizeof(double) * 9 * B}, {h->d_gm_tr, t, sizeof(double) * 3 * B}})) return rc;
-    const double *d_R = R ? h->d_gm_R : h->d_R, *d_t = R ? h->d_gm_tr : h->d_t;
-    const int *d_status = R ? (const int *)nullptr : (const int *)h->d_status;
-    if (h->cfg.norm_type == RPE_NORM_L2) rpe_launch_guided_l2(h, r, d_R, d_t, d_status, gate_px, max_distance);
-    else rpe_launch_guided(h, r, d_R, d_t, d_status, gate_px, (int)max_distance);
-    HIPCHK(h, hipGetLastError());
-    // the wait also covers the upload: the poses have left the caller's arrays
-    return fetch(h, {{qidx, h->d_gm_q, sizeof(int) * n}, {tidx, h->d_gm_t, sizeof(int) * n}, {dist, h->d_gm_d, sizeof(int) * n},
-                     {pts1, h->d_gm_pts1, sizeof(float2) * n}, {pts2, h->d_gm_pts2, sizeof(float2) * n}, {n_matches, h->d_gm_n, sizeof(int) * B}});
-}
-
-// the run form of either norm: over the first B pairs of the last run
-static int guided_last_run(rpe_handle *h, const char *who, int norm, int B, const double *R, const double *t, double gate_px, double max_distance,
-                           int32_t *qidx, int32_t *tidx, void *dist, float *pts1, float *pts2, int32_t *n_matches)
-{
-    int rc = guided_check(h, who, norm, B, R, t, gate_px, max_distance);
-    if (rc) return rc;
-    // the features of the run must still be where it read them (a stage call or a put overwrote the workspace's) and, under
-    // the run's own poses, d_R / d_t / d_status its results
-    rc = last_run_gate(h, who, B, NEED_UNCHUNKED | NEED_PER_MATCH | NEED_COUNT | NEED_TABLE);
-    if (rc) return rc;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    if ((rc = guided_alloc(h)) != RPE_OK) return rc;
-    return guided_run(h, last_run_first(h, B), R, t, gate_px, max_distance, qidx, tidx, dist, pts1, pts2, n_matches);
-}
-
-extern "C" int rpe_guided_matches(rpe_handle *h, int B, const double *R, const double *t, double gate_px, int max_distance,
-                                  int32_t *qidx, int32_t *tidx, int32_t *dist, float *pts1, float *pts2, int32_t *n_matches)
-{
-    if (!h || B < 1 || B > h->cfg.max_batch) return rpe_invalid(h, "rpe_guided_matches");
-    return guided_last_run(h, "rpe_guided_matches", RPE_NORM_HAMMING, B, R, t, gate_px, max_distance, qidx, tidx, dist, pts1, pts2, n_matches);
-}
-
-extern "C" int rpe_guided_matches_l2(rpe_handle *h, int B, const double *R, const double *t, double gate_px, double max_distance,
-                                     int32_t *qidx, int32_t *tidx, float *dist, float *pts1, float *pts2, int32_t *n_matches)
-{
-    if (!h || B < 1 || B > h->cfg.max_batch) return rpe_invalid(h, "rpe_guided_matches_l2");
-    return guided_last_run(h, "rpe_guided_matches_l2", RPE_NORM_L2, B, R, t, gate_px, max_distance, qidx, tidx, dist, pts1, pts2, n_matches);
-}
-
-// tail of the stage forms (descriptors of pair p uploaded to workspace slots p and B + p): points, counts, match, fetch
-static int guided_stage_run(rpe_handle *h, const float *h_pts1, const int32_t *n1, const float *h_pts2, const int32_t *n2, int B,
-                            const double *R, const double *t, double gate_px, double max_distance,
-                            int32_t *qidx, int32_t *tidx, void *dist, int32_t *n_matches)
-{
-    const size_t kcap = (size_t)h->lay.kcap;
-    if (int rc = upload(h, {{h->d_kp_pt, h_pts1, sizeof(float2) * kcap * B}, {h->d_kp_pt + kcap * B, h_pts2, sizeof(float2) * kcap * B}})) return rc;
-    if (int rc = upload_counts(h, n1, n2, B)) return rc;
-    return guided_run(h, rpe_run_batch(h, B), R, t, gate_px, max_distance, qidx, tidx, dist, nullptr, nullptr, n_matches);
-}
-
-extern "C" int rpe_match_hamming_guided(rpe_handle *h, const uint8_t *h_desc1, const float *h_pts1, const int32_t *n1,
-                                        const uint8_t *h_desc2, const float *h_pts2, const int32_t *n2, int B,
-                                        const double K[9], const double *R, const double *t, double gate_px, int max_distance,
-                                        int32_t *qidx, int32_t *tidx, int32_t *dist, int32_t *n_matches)
-{
-    if (!h || !h_desc1 || !h_pts1 || !n1 || !h_desc2 || !h_pts2 || !n2 || !K || !R || !t || B < 1) return rpe_invalid(h, "rpe_match_hamming_guided");
-    if (int rc = check_batch(h, B)) return rc;
-    int rc = guided_check(h, "rpe_match_hamming_guided", RPE_NORM_HAMMING, B, R, t, gate_px, max_distance);
-    if (rc) return rc;
-    if ((rc = check_desc_counts(h, n1, B)) != RPE_OK || (rc = check_desc_counts(h, n2, B)) != RPE_OK) return rc;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    if ((rc = guided_alloc(h)) != RPE_OK) return rc;
-    last_run_end(h);                            // overwrites the workspace's features
-    if ((rc = set_K(h, K)) != RPE_OK) return rc;
-    // pair p on the workspace slots (p, B + p), like every stage call
-    if ((rc = upload_descriptors(h, h_desc1, h_desc2, B)) != RPE_OK) return rc;
-    return guided_stage_run(h, h_pts1, n1, h_pts2, n2, B, R, t, gate_px, max_distance, qidx, tidx, dist, n_matches);
-}
-
-extern "C" int rpe_match_l2_guided(rpe_handle *h, const float *h_desc1, const float *h_pts1, const int32_t *n1,
-                                   const float *h_desc2, const float *h_pts2, const int32_t *n2, int B,
-                                   const double K[9], const double *R, const double *t, double gate_px, double max_distance,
-                                   int32_t *qidx, int32_t *tidx, float *dist, int32_t *n_matches)
-{
-    if (!h || !h_desc1 || !h_pts1 || !n1 || !h_desc2 || !h_pts2 || !n2 || !K || !R || !t || B < 1) return rpe_invalid(h, "rpe_match_l2_guided");
-    if (int rc = check_batch(h, B)) return rc;
-    int rc = guided_check(h, "rpe_match_l2_guided", RPE_NORM_L2, B, R, t, gate_px, max_distance);
-    if (rc) return rc;
-    std::vector<uint8_t> u;
-    if ((rc = l2_desc_bytes(h, h_desc1, n1, h_desc2, n2, B, u)) != RPE_OK) return rc;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    if ((rc = guided_alloc(h)) != RPE_OK) return rc;
-    last_run_end(h);                            // overwrites the workspace's features
-    if ((rc = set_K(h, K)) != RPE_OK) return rc;
-    if ((rc = upload(h, {{h->d_desc, u.data(), u.size()}})) != RPE_OK) return rc;
-    return guided_stage_run(h, h_pts1, n1, h_pts2, n2, B, R, t, gate_px, max_distance, qidx, tidx, dist, n_matches);   // waits: u is read by then
-}
-
-// ---------------------------------------------------------------- homography / rotation-only
-// rpe_pair_homographies / rpe_find_homography (NOT in the reference): a homography by RANSAC over the matches of a pair,
-// the rotation fitted to its inliers and the three inlier counts.  Results go to the d_hg_* buffers; nothing of the run
-// is written.
-static int homography_alloc(rpe_handle *h)
-{
-    const size_t MB = (size_t)h->cfg.max_batch;
-    return rpe_bufset_fit(h, h->set_homography,
-                          {buf_piece(h->d_hg_H, MB * 9), buf_piece(h->d_hg_R, MB * 9), buf_piece(h->d_hg_counts, MB * 3), buf_piece(h->d_hg_info, MB * 4),
-                           buf_piece(h->d_hg_mask, MB * h->cfg.max_matches)});
-}
-
-static int homography_run(rpe_handle *h, const RpeRun &r, int iters, double threshold_px, bool from_batch, double *H, double *R_rot,
-                          uint8_t *mask, int32_t *counts, int32_t *info)
-{
-    const size_t B = (size_t)r.pairs;
-    rpe_launch_homography(h, r, iters, threshold_px, from_batch);
-    HIPCHK(h, hipGetLastError());
-    return fetch(h, {{H, h->d_hg_H, sizeof(double) * 9 * B}, {R_rot, h->d_hg_R, sizeof(double) * 9 * B}, {mask, h->d_hg_mask, B * h->cfg.max_matches},
-                     {counts, h->d_hg_counts, sizeof(int) * 3 * B}, {info, h->d_hg_info, sizeof(int) * 4 * B}});
-}
-
-extern "C" int rpe_pair_homographies(rpe_handle *h, int B, int iters, double threshold_px, double *H, double *R_rot,
-                                     uint8_t *mask, int32_t *counts, int32_t *info)
-{
-    if (!h || B < 1 || B > h->cfg.max_batch) return rpe_invalid(h, "rpe_pair_homographies");
-    int rc = homography_check(h, "rpe_pair_homographies", iters, threshold_px);
-    if (rc) return rc;
-    // d_n1 / d_n2, d_rstate and d_status must still hold the run's (a stage call or a put overwrote them)
-    rc = last_run_gate(h, "rpe_pair_homographies", B, NEED_UNCHUNKED | NEED_PER_MATCH | NEED_COUNT | NEED_TABLE);
-    if (rc) return rc;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    if ((rc = homography_alloc(h)) != RPE_OK) return rc;
-    return homography_run(h, last_run_first(h, B), iters, threshold_px, true, H, R_rot, mask, counts, info);
-}
-
 // ---------------------------------------------------------------- frame store
 // rpe_frames_* / rpe_enqueue_pairs (NOT in the reference): extraction separated from pairing.  A put extracts n frames in
 // the workspace slots [0, n) exactly as a stream does and one scatter kernel moves what the matchers and the status test
@@ -1864,106 +1380,6 @@ extern "C" int rpe_estimate_pairs(rpe_handle *h, const int32_t *slot1, const int
     return rpe_fetch_results(h, P, R, t, inliers, n_matches, status);
 }
 
-// ---- pair proposals (rpe_frames_similar / rpe_similarity_hamming; NOT in the reference): similarity scores between frames
-// and a top-k candidate selection (the definitions: include/rpe_amd.h; the kernels: similar_kernels.hip).
-// The checks the two forms share, host side, in front of any device call.  n_frames: the store's slots or the stage call's
-// frames; filled: the store's flags, or null
-static int similar_check(rpe_handle *h, const char *who, int n_frames, const uint8_t *filled, int nq, const int32_t *q, int nt, const int32_t *t,
-                         int step, int max_distance, int k, const int32_t *scores, const int32_t *cand, const int32_t *cand_score, const int32_t *n_cand)
-{
-    if (!q || !t || nq < 1 || nt < 1) return rpe_invalid(h, who, "a null list, or nq < 1 or nt < 1");
-    if (step < 1) return rpe_invalid(h, who, "step must be >= 1");
-    if (max_distance < 0 || max_distance > 256) return rpe_invalid(h, who, "max_distance must be 0 ... 256");
-    if (k < 0 || k > RPE_SIMILAR_MAX_K) return rpe_invalid(h, who, "k must be 0 ... RPE_SIMILAR_MAX_K");
-    const int trio = (cand != nullptr) + (cand_score != nullptr) + (n_cand != nullptr);
-    if (trio != 0 && trio != 3) return rpe_invalid(h, who, "cand, cand_score and n_cand must all be given or all be NULL");
-    if (!scores && !trio) return rpe_invalid(h, who, "no output asked for");
-    for (int s = 0; s < 2; ++s) {
-        const int32_t *l = s ? t : q;
-        for (int i = 0, n = s ? nt : nq; i < n; ++i) {
-            if (l[i] < 0 || l[i] >= n_frames) return rpe_invalid(h, who, filled ? "slot outside the store" : "frame index outside 0 ... F-1");
-            if (filled && !filled[(size_t)l[i]]) return rpe_invalid(h, who, "a list names an empty slot");
-        }
-    }
-    if ((long long)nq * nt > 0x7FFFFFFFLL) { h->err = std::string(who) + ": nq * nt exceeds 2^31 - 1"; return RPE_ERR_CAPACITY; }
-    return RPE_OK;
-}
-
-// Behind the checks and hipSetDevice: the buffer set, the tables, the launches over the features (desc, count), the fetch
-static int similar_run(rpe_handle *h, const uint8_t *desc, const int *count, int nq, const int32_t *q, int nt, const int32_t *t,
-                       int step, int max_distance, const int32_t *q_time, const int32_t *t_time, int exclude, int min_score, int k,
-                       int32_t *scores, int32_t *cand, int32_t *cand_score, int32_t *n_cand)
-{
-    const size_t NQ = (size_t)nq, NT = (size_t)nt, ck = cand ? NQ * (size_t)k : 0;
-    if (int rc = rpe_bufset_fit(h, h->set_similar,
-                                {buf_piece(h->d_sim_q, NQ), buf_piece(h->d_sim_t, NT), buf_piece(h->d_sim_qtime, q_time ? NQ : 0),
-                                 buf_piece(h->d_sim_ttime, t_time ? NT : 0), buf_piece(h->d_sim_scores, NQ * NT), buf_piece(h->d_sim_cand, ck),
-                                 buf_piece(h->d_sim_cscore, ck), buf_piece(h->d_sim_ncand, cand ? NQ : 0)})) return rc;
-    if (int rc = upload(h, {{h->d_sim_q, q, sizeof(int) * NQ}, {h->d_sim_t, t, sizeof(int) * NT},
-                            {h->d_sim_qtime, q_time, sizeof(int) * NQ}, {h->d_sim_ttime, t_time, sizeof(int) * NT}})) return rc;
-    RpeSimilarJob job;
-    job.desc = desc; job.count = count;
-    job.nq = nq; job.nt = nt; job.q = h->d_sim_q; job.t = h->d_sim_t;
-    job.step = std::min(step, std::max(h->lay.kcap, 1));       // a stride of the capacity or more samples descriptor 0 alone
-    job.max_distance = max_distance;
-    job.same = nq == nt && memcmp(q, t, sizeof(int32_t) * NQ) == 0;
-    job.q_time = q_time ? h->d_sim_qtime : h->d_sim_q; job.t_time = t_time ? h->d_sim_ttime : h->d_sim_t;      // no times: the slot numbers
-    job.exclude = exclude; job.min_score = min_score; job.k = k;
-    job.scores = h->d_sim_scores;
-    // k == 0 selects nothing: every row's count is 0, written below without a launch
-    const bool select = cand && k > 0;
-    job.cand = select ? h->d_sim_cand : nullptr; job.cand_score = h->d_sim_cscore; job.n_cand = h->d_sim_ncand;
-    rpe_launch_similar(h, job);
-    HIPCHK(h, hipGetLastError());
-    if (cand && !select) memset(n_cand, 0, sizeof(int32_t) * NQ);
-    // the wait also covers the uploads: the lists and times have left the caller's arrays
-    return fetch(h, {{scores, h->d_sim_scores, sizeof(int) * NQ * NT}, {select ? cand : nullptr, h->d_sim_cand, sizeof(int) * ck},
-                     {select ? cand_score : nullptr, h->d_sim_cscore, sizeof(int) * ck}, {select ? n_cand : nullptr, h->d_sim_ncand, sizeof(int) * NQ}});
-}
-
-static int similar_hamming_only(rpe_handle *h, const char *who)
-{
-    if (h->cfg.feature_method == RPE_FEATURE_SIFT || h->cfg.norm_type != RPE_NORM_HAMMING)
-        return rpe_invalid(h, who, "Hamming handles only (ORB with RPE_NORM_HAMMING)");
-    return RPE_OK;
-}
-
-extern "C" int rpe_frames_similar(rpe_handle *h, int nq, const int32_t *q_slots, int nt, const int32_t *t_slots,
-                                  int step, int max_distance, const int32_t *q_time, const int32_t *t_time,
-                                  int exclude, int min_score, int k,
-                                  int32_t *scores, int32_t *cand, int32_t *cand_score, int32_t *n_cand)
-{
-    const char *who = "rpe_frames_similar";
-    if (!h) return rpe_invalid(h, who);
-    if (int rc = similar_hamming_only(h, who)) return rc;
-    if (h->fs.cap == 0) return rpe_invalid(h, who, "no frame store (rpe_frames_reserve)");
-    if (int rc = similar_check(h, who, h->fs.cap, h->fs.filled.data(), nq, q_slots, nt, t_slots, step, max_distance, k, scores, cand, cand_score, n_cand)) return rc;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    // reads the store, writes set_similar: the last run and what is fetched from it stay as they are
-    return similar_run(h, h->fs.d_desc, h->fs.d_count, nq, q_slots, nt, t_slots, step, max_distance, q_time, t_time, exclude, min_score, k,
-                       scores, cand, cand_score, n_cand);
-}
-
-extern "C" int rpe_similarity_hamming(rpe_handle *h, const uint8_t *h_desc, const int32_t *n, int F,
-                                      int nq, const int32_t *q_idx, int nt, const int32_t *t_idx,
-                                      int step, int max_distance, const int32_t *q_time, const int32_t *t_time,
-                                      int exclude, int min_score, int k,
-                                      int32_t *scores, int32_t *cand, int32_t *cand_score, int32_t *n_cand)
-{
-    const char *who = "rpe_similarity_hamming";
-    if (!h || !h_desc || !n || F < 1) return rpe_invalid(h, who);
-    if (int rc = similar_hamming_only(h, who)) return rc;
-    if (F > h->n_img_cap) { h->err = std::string(who) + ": more than 2*max_batch frames"; return RPE_ERR_CAPACITY; }
-    if (int rc = check_desc_counts(h, n, F)) return rc;
-    if (int rc = similar_check(h, who, F, nullptr, nq, q_idx, nt, t_idx, step, max_distance, k, scores, cand, cand_score, n_cand)) return rc;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    last_run_end(h);                            // overwrites the workspace's features
-    // frame f on the workspace slot f
-    if (int rc = upload(h, {{h->d_desc, h_desc, (size_t)h->lay.kcap * 32 * F}, {h->d_kp_count, n, sizeof(int) * (size_t)F}})) return rc;
-    return similar_run(h, h->d_desc, h->d_kp_count, nq, q_idx, nt, t_idx, step, max_distance, q_time, t_time, exclude, min_score, k,
-                       scores, cand, cand_score, n_cand);
-}
-
 // ---------------------------------------------------------------- stage API
 extern "C" int rpe_orb_detect_and_compute(rpe_handle *h, const uint8_t *h_imgs, int n_images,
                                           rpe_keypoint *kps, uint8_t *desc, int32_t *counts)
@@ -2126,7 +1542,7 @@ static int upload_points(rpe_handle *h, const float *p1, const float *p2, const 
 // the camera records where the kernels find them -- 2 B records per batch / stage call in d_batch_cams, one record per
 // frame-store slot in fs.d_cam -- and name them in the camera source of the run they launch, which makes the launchers of
 // geom_kernels.hip and link_kernels.hip take the camera instances (launch_cam, geom_device.h).
-static int check_cameras(rpe_handle *h, const rpe_camera *c, int n, const char *who)
+int check_cameras(rpe_handle *h, const rpe_camera *c, int n, const char *who)
 {
     for (int i = 0; i < n; ++i) {
         const double *f = &c[i].fx;                     // fx fy cx cy dist[8]: twelve doubles
@@ -2251,194 +1667,11 @@ extern "C" int rpe_undistort_points(rpe_handle *h, const float *h_pts, int n, co
     return RPE_OK;
 }
 
-// ---------------------------------------------------------------- the track scene (track_scene.h)
-// What rpe_triangulate_tracks and rpe_bundle_windows share.  Phase 1 of its check, in front of the empty-call return: the
-// scalars and the CSR shape, then the cameras (K as the one pinhole record it becomes)
-static int scene_check_shape(rpe_handle *h, const char *who, const RpeSceneArgs &a)
-{
-    if (const char *what = rpe_scene_check_shape(a)) return rpe_invalid(h, who, what);
-    if (a.K) h->scene.cam_k = rpe_camera{a.K[0], a.K[4], a.K[2], a.K[5], {0., 0., 0., 0., 0., 0., 0., 0.}};
-    return a.K ? check_cameras(h, &h->scene.cam_k, 1, who) : check_cameras(h, a.cams, a.n_frames, who);
-}
-// Behind phase 2 (rpe_scene_check_arrays: n_obs) and hipSetDevice: the scene buffers fitted to this call, the uploads, the device view
-static int scene_upload(rpe_handle *h, const RpeSceneArgs &a, size_t n_obs, RpeTrackScene *sc)
-{
-    rpe_handle::Scene &b = h->scene;
-    const size_t nt = (size_t)a.n_tracks, nf = (size_t)a.n_frames, nc = a.K ? 1 : nf;
-    if (int rc = rpe_bufset_fit(h, b.set, {buf_piece(b.d_tstart, nt + 1), buf_piece(b.d_oframe, n_obs), buf_piece(b.d_oxy, n_obs),
-                                           buf_piece(b.d_R, 9 * nf), buf_piece(b.d_T, 3 * nf), buf_piece(b.d_cams, nc)})) return rc;
-    if (int rc = upload(h, {{b.d_tstart, a.track_start, sizeof(int) * (nt + 1)}, {b.d_oframe, a.obs_frame, sizeof(int) * n_obs},
-                            {b.d_oxy, a.obs_xy, sizeof(float2) * n_obs}, {b.d_R, a.R_abs, sizeof(double) * 9 * nf},
-                            {b.d_T, a.T_abs, sizeof(double) * 3 * nf}, {b.d_cams, a.K ? &b.cam_k : a.cams, sizeof(rpe_camera) * nc}})) return rc;
-    *sc = {a.n_tracks, (int)n_obs, a.K ? 0 : 1, b.d_tstart, b.d_oframe, b.d_oxy, b.d_R, b.d_T, b.d_cams};
-    return RPE_OK;
-}
-
-// ---------------------------------------------------------------- track points (rpe_triangulate_tracks)
-// Every check on the host first, the buffers, the uploads, the two kernels, the fetch.  Neither the workspace nor the record
-// of the last run is touched.
-extern "C" int rpe_triangulate_tracks(rpe_handle *h, int n_tracks, const int32_t *track_start, const int32_t *obs_frame, const float *obs_xy,
-                                      int n_frames, const double *R_abs, const double *T_abs, const int32_t *frame_group, const double *K,
-                                      const rpe_camera *cams, double threshold_px, int min_views, double max_cos, int max_iters,
-                                      double *points, int32_t *info, double *rms, double *min_cos, uint8_t *obs_flag, double *obs_err)
-{
-    const char *who = "rpe_triangulate_tracks";
-    if (!h) return rpe_invalid(h, who);
-    const RpeSceneArgs scene = {n_tracks, track_start, obs_frame, obs_xy, n_frames, R_abs, T_abs, K, cams};
-    if (int rc = check_positive(h, who, "threshold_px", threshold_px)) return rc;
-    if (min_views < 2) return rpe_invalid(h, who, "min_views must be >= 2");
-    if (!(max_cos > -1. && max_cos <= 1.)) return rpe_invalid(h, who, "max_cos must lie in (-1, 1]");
-    if (max_iters < 0 || max_iters > 100) return rpe_invalid(h, who, "max_iters must be 0 ... 100");
-    if (int rc = scene_check_shape(h, who, scene)) return rc;
-    if (n_tracks == 0) return RPE_OK;
-    size_t no;
-    if (const char *what = rpe_scene_check_arrays(scene, &no)) return rpe_invalid(h, who, what);
-    const size_t nt = (size_t)n_tracks, nf = (size_t)n_frames;
-    for (size_t f = 0; f < nf; ++f) {
-        if (frame_group && frame_group[f] < 0) continue;
-        if (!all_finite(R_abs + f * 9, 9) || !all_finite(T_abs + f * 3, 3)) return rpe_invalid(h, who, "a non-finite pose of a frame that has a group");
-    }
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    const size_t no1 = std::max(no, (size_t)1);
-    // the buffers of the call beside the scene: per track, per observation, per frame
-    if (int rc = rpe_bufset_fit(h, h->set_track_points,
-                                {buf_piece(h->d_tp_points, 3 * nt), buf_piece(h->d_tp_info, 4 * nt), buf_piece(h->d_tp_rms, nt), buf_piece(h->d_tp_mincos, nt),
-                                 buf_piece(h->d_tp_obs, 5 * no1), buf_piece(h->d_tp_oflag, no1), buf_piece(h->d_tp_oerr, no1), buf_piece(h->d_tp_group, nf)})) return rc;
-    RpeTrackPointJob job = {{}, min_views, max_iters, threshold_px, max_cos, frame_group ? h->d_tp_group : nullptr};
-    if (int rc = scene_upload(h, scene, no, &job.scene)) return rc;
-    if (int rc = upload(h, {{h->d_tp_group, frame_group, sizeof(int) * nf}})) return rc;
-    rpe_launch_track_points(h, job);
-    HIPCHK(h, hipGetLastError());
-    // the wait also covers the uploads: the inputs have left the caller's arrays
-    return fetch(h, {{points, h->d_tp_points, sizeof(double) * 3 * nt}, {info, h->d_tp_info, sizeof(int) * 4 * nt},
-                     {rms, h->d_tp_rms, sizeof(double) * nt}, {min_cos, h->d_tp_mincos, sizeof(double) * nt},
-                     {obs_flag, h->d_tp_oflag, no}, {obs_err, h->d_tp_oerr, sizeof(double) * no}});
-}
-
-// ---------------------------------------------------------------- window bundles (rpe_bundle_windows)
-// Every check on the host first, the buffers, the uploads, the three kernels, the fetch.  Neither the workspace nor the record
-// of the last run is touched.
-extern "C" int rpe_bundle_windows(rpe_handle *h, int n_tracks, const int32_t *track_start, const int32_t *obs_frame, const float *obs_xy,
-                                  const double *points0, const uint8_t *point_use, const uint8_t *obs_use,
-                                  int n_frames, const double *R_abs, const double *T_abs, const double *K, const rpe_camera *cams,
-                                  int n_win, const int32_t *win_start, const int32_t *win_frame, int max_points, int min_obs, int max_iters,
-                                  double *R_out, double *T_out, double *points, int32_t *point_track, int32_t *counts, int32_t *info,
-                                  double *rms)
-{
-    const char *who = "rpe_bundle_windows";
-    if (!h) return rpe_invalid(h, who);
-    const RpeSceneArgs scene = {n_tracks, track_start, obs_frame, obs_xy, n_frames, R_abs, T_abs, K, cams};
-    if (n_win < 0) return rpe_invalid(h, who, "n_win must be >= 0");
-    if (max_points < 1) return rpe_invalid(h, who, "max_points must be >= 1");
-    if (max_points > RPE_WINDOW_MAX_POINTS) { h->err = std::string(who) + ": max_points exceeds RPE_WINDOW_MAX_POINTS"; return RPE_ERR_CAPACITY; }
-    if (min_obs < 0) return rpe_invalid(h, who, "min_obs must be >= 0");
-    if (max_iters < 1 || max_iters > 100) return rpe_invalid(h, who, "max_iters must be 1 ... 100");
-    if (int rc = scene_check_shape(h, who, scene)) return rc;
-    if (n_win == 0) return RPE_OK;
-    if (!win_start || !win_frame || (n_tracks > 0 && !points0)) return rpe_invalid(h, who);
-    size_t no;
-    if (const char *what = rpe_scene_check_arrays(scene, &no)) return rpe_invalid(h, who, what);
-    const size_t nt = (size_t)n_tracks, nw = (size_t)n_win;
-    if (win_start[0] != 0) return rpe_invalid(h, who, "win_start[0] must be 0");
-    for (int w = 0; w < n_win; ++w) {
-        const int W = win_start[w + 1] - win_start[w];
-        if (W < 0) return rpe_invalid(h, who, "win_start must not decrease");
-        if (W < 2 || W > RPE_WINDOW_MAX_VIEWS) return rpe_invalid(h, who, "a window must have 2 ... RPE_WINDOW_MAX_VIEWS frames");
-        const int32_t *f = win_frame + win_start[w];
-        for (int p = 0; p < W; ++p) {
-            if (f[p] < 0 || f[p] >= n_frames) return rpe_invalid(h, who, "a window frame outside 0 ... n_frames - 1");
-            for (int q = 0; q < p; ++q)
-                if (f[q] == f[p]) return rpe_invalid(h, who, "a frame repeated inside a window");
-            if (!all_finite(R_abs + (size_t)f[p] * 9, 9) || !all_finite(T_abs + (size_t)f[p] * 3, 3))
-                return rpe_invalid(h, who, "a non-finite pose of a frame that a window names");
-        }
-    }
-    for (size_t t = 0; t < nt; ++t)
-        if ((!point_use || point_use[t]) && !all_finite(points0 + 3 * t, 3)) return rpe_invalid(h, who, "a non-finite start point of a used track");
-    const size_t nwf = (size_t)win_start[n_win], slots = nw * (size_t)max_points;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    // the buffers of the call beside the scene: per track, per observation, per window frame, per window, per window and point slot
-    if (int rc = rpe_bufset_fit(h, h->set_windows,
-                                {buf_piece(h->d_wb_points0, 3 * nt), buf_piece(h->d_wb_puse, nt), buf_piece(h->d_wb_obs, no), buf_piece(h->d_wb_ouse, no),
-                                 buf_piece(h->d_wb_wstart, nw + 1), buf_piece(h->d_wb_wframe, nwf), buf_piece(h->d_wb_Rout, 9 * nwf), buf_piece(h->d_wb_Tout, 3 * nwf),
-                                 buf_piece(h->d_wb_counts, 4 * nw), buf_piece(h->d_wb_info, 4 * nw), buf_piece(h->d_wb_rms, 2 * nw), buf_piece(h->d_wb_fcnt, RPE_WINDOW_MAX_VIEWS * nw),
-                                 buf_piece(h->d_wb_ptrack, slots), buf_piece(h->d_wb_pobs, RPE_WINDOW_MAX_VIEWS * slots),
-                                 buf_piece(h->d_wb_state, 6 * slots), buf_piece(h->d_wb_points, 3 * slots)})) return rc;
-    RpeWindowJob job = {{}, n_win, max_points, min_obs, max_iters, h->d_wb_points0, point_use ? h->d_wb_puse : nullptr,
-                        obs_use ? h->d_wb_ouse : nullptr, h->d_wb_wstart, h->d_wb_wframe};
-    if (int rc = scene_upload(h, scene, no, &job.scene)) return rc;
-    if (int rc = upload(h, {{h->d_wb_points0, points0, sizeof(double) * 3 * nt}, {h->d_wb_puse, point_use, nt}, {h->d_wb_ouse, obs_use, no},
-                            {h->d_wb_wstart, win_start, sizeof(int) * (nw + 1)}, {h->d_wb_wframe, win_frame, sizeof(int) * nwf}})) return rc;
-    rpe_launch_windows(h, job);
-    HIPCHK(h, hipGetLastError());
-    // the wait also covers the uploads: the inputs have left the caller's arrays
-    return fetch(h, {{R_out, h->d_wb_Rout, sizeof(double) * 9 * nwf}, {T_out, h->d_wb_Tout, sizeof(double) * 3 * nwf},
-                     {points, h->d_wb_points, sizeof(double) * 3 * slots}, {point_track, h->d_wb_ptrack, sizeof(int) * slots},
-                     {counts, h->d_wb_counts, sizeof(int) * 4 * nw}, {info, h->d_wb_info, sizeof(int) * 4 * nw},
-                     {rms, h->d_wb_rms, sizeof(double) * 2 * nw}});
-}
-
-// ---------------------------------------------------------------- pose graphs (rpe_optimise_graphs)
-// Every check on the host first, then the active set and the tables of the kernel (graph_plan.h, which the host tests run),
-// the buffers, the uploads, the kernel, the fetch.  Neither the workspace nor the record of the last run is touched.
-extern "C" int rpe_optimise_graphs(rpe_handle *h, int n_frames, const double *R_abs, const double *T_abs,
-                                   int n_graphs, const int32_t *graph_start, const int32_t *graph_frame, const uint8_t *fixed,
-                                   const int32_t *edge_start, const int32_t *edge_i, const int32_t *edge_j, const double *edge_R,
-                                   const double *edge_t, const double *edge_w, const int32_t *edge_kind,
-                                   double huber, int max_iters, int cg_iters, double cg_tol,
-                                   double *R_out, double *T_out, int32_t *counts, int32_t *info, double *cost, double *edge_chi,
-                                   uint8_t *edge_used)
-{
-    const char *who = "rpe_optimise_graphs";
-    if (!h) return rpe_invalid(h, who);
-    const RpeGraphArgs args = {n_frames, R_abs, T_abs, n_graphs, graph_start, graph_frame, fixed, edge_start, edge_i, edge_j,
-                               edge_R, edge_t, edge_w, edge_kind, huber, max_iters, cg_iters, cg_tol};
-    RpeGraphPlan plan;
-    const RpeGraphRefusal no = rpe_graph_check(args, plan);
-    if (no.code) { h->err = std::string(who) + ": " + (no.text ? no.text : RPE_NULL_ARGUMENT_TEXT); return no.code; }
-    if (n_graphs == 0) return RPE_OK;
-    rpe_graph_build(args, plan);
-    const std::vector<int> &ei = plan.ei, &ej = plan.ej, &free_start = plan.free_start, &used_start = plan.used_start, &precode = plan.precode;
-    const std::vector<int> &free_pos = plan.free_pos, &used_edge = plan.used_edge, &adj_start = plan.adj_start, &adj = plan.adj;
-    const size_t ng = (size_t)n_graphs, nf = (size_t)graph_start[n_graphs], ne = (size_t)edge_start[n_graphs];
-    const size_t nfr = free_pos.size(), nus = used_edge.size(), nadj = adj.size() / 2, nF = (size_t)n_frames;
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    if (int rc = rpe_bufset_fit(h, h->set_graphs,
-                                {buf_piece(h->d_pg_Rabs, 9 * nF), buf_piece(h->d_pg_Tabs, 3 * nF), buf_piece(h->d_pg_eR, 9 * ne), buf_piece(h->d_pg_et, 3 * ne),
-                                 buf_piece(h->d_pg_ew, 2 * ne), buf_piece(h->d_pg_gstart, ng + 1), buf_piece(h->d_pg_gframe, nf), buf_piece(h->d_pg_estart, ng + 1),
-                                 buf_piece(h->d_pg_fstart, ng + 1), buf_piece(h->d_pg_ustart, ng + 1), buf_piece(h->d_pg_precode, ng), buf_piece(h->d_pg_fpos, nfr),
-                                 buf_piece(h->d_pg_astart, nfr + 1), buf_piece(h->d_pg_uedge, nus), buf_piece(h->d_pg_ei, ne), buf_piece(h->d_pg_ej, ne),
-                                 buf_piece(h->d_pg_ekind, ne), buf_piece(h->d_pg_info, 4 * ng), buf_piece(h->d_pg_adj, nadj),
-                                 buf_piece(h->d_pg_Rout, 9 * nf), buf_piece(h->d_pg_Tout, 3 * nf), buf_piece(h->d_pg_Rn, 9 * nf), buf_piece(h->d_pg_Tn, 3 * nf),
-                                 buf_piece(h->d_pg_eb, 120 * nus), buf_piece(h->d_pg_fb, 87 * nfr), buf_piece(h->d_pg_chi, 2 * std::max(ne, (size_t)1)), buf_piece(h->d_pg_cost, 2 * ng)})) return rc;
-    if (int rc = upload(h, {{h->d_pg_Rabs, R_abs, sizeof(double) * 9 * nF}, {h->d_pg_Tabs, T_abs, sizeof(double) * 3 * nF},
-                            {h->d_pg_eR, edge_R, sizeof(double) * 9 * ne}, {h->d_pg_et, edge_t, sizeof(double) * 3 * ne}, {h->d_pg_ew, edge_w, sizeof(double) * 2 * ne},
-                            {h->d_pg_gstart, graph_start, sizeof(int) * (ng + 1)}, {h->d_pg_gframe, graph_frame, sizeof(int) * nf},
-                            {h->d_pg_estart, edge_start, sizeof(int) * (ng + 1)}, {h->d_pg_fstart, free_start.data(), sizeof(int) * (ng + 1)},
-                            {h->d_pg_ustart, used_start.data(), sizeof(int) * (ng + 1)}, {h->d_pg_precode, precode.data(), sizeof(int) * ng},
-                            {h->d_pg_fpos, free_pos.data(), sizeof(int) * nfr}, {h->d_pg_astart, adj_start.data(), sizeof(int) * (nfr + 1)},
-                            {h->d_pg_uedge, used_edge.data(), sizeof(int) * nus}, {h->d_pg_ei, ei.data(), sizeof(int) * ne}, {h->d_pg_ej, ej.data(), sizeof(int) * ne},
-                            {h->d_pg_ekind, edge_kind, sizeof(int) * ne}, {h->d_pg_adj, adj.data(), sizeof(int2) * nadj}})) return rc;
-    if (ne > 0) HIPCHK(h, hipMemsetAsync(h->d_pg_chi, 0, sizeof(double) * 2 * ne, h->stream));
-    const RpeGraphJob job = {n_graphs, max_iters, cg_iters, huber, cg_tol, h->d_pg_Rabs, h->d_pg_Tabs, h->d_pg_eR, h->d_pg_et, h->d_pg_ew,
-                             h->d_pg_gstart, h->d_pg_gframe, h->d_pg_estart, h->d_pg_fstart, h->d_pg_ustart, h->d_pg_precode,
-                             h->d_pg_fpos, h->d_pg_astart, h->d_pg_uedge, h->d_pg_ei, h->d_pg_ej, h->d_pg_ekind, h->d_pg_adj};
-    rpe_launch_graphs(h, job);
-    HIPCHK(h, hipGetLastError());
-    // the wait also covers the uploads: the host tables above and the caller's arrays have been read
-    if (int rc = fetch(h, {{R_out, h->d_pg_Rout, sizeof(double) * 9 * nf}, {T_out, h->d_pg_Tout, sizeof(double) * 3 * nf},
-                           {info, h->d_pg_info, sizeof(int) * 4 * ng}, {cost, h->d_pg_cost, sizeof(double) * 2 * ng},
-                           {edge_chi, h->d_pg_chi, sizeof(double) * 2 * ne}})) return rc;
-    if (counts) memcpy(counts, plan.counts.data(), sizeof(int) * 4 * ng);
-    if (edge_used && ne > 0) memcpy(edge_used, plan.used.data(), ne);
-    return RPE_OK;
-}
-
 // ---------------------------------------------------------------- stage API: geometry
 // findEssentialMat, recoverPose and the refinement over uploaded points, each on one K (rpe_*) or on a camera per side and
 // pair (rpe_*_cameras, K == nullptr here).  Head of the three: capacity, cameras, points and intrinsics resident; `run`
 // is the stage run over the B uploaded pairs.
-static int stage_begin(rpe_handle *h, const char *who, const float *p1, const float *p2, const int32_t *m, int B,
+int stage_begin(rpe_handle *h, const char *who, const float *p1, const float *p2, const int32_t *m, int B,
                        const double *K, const rpe_camera *cam1, const rpe_camera *cam2, RpeRun &run)
 {
     if (int rc = check_batch(h, B)) return rc;
@@ -2488,20 +1721,6 @@ static int stage_recover_pose(rpe_handle *h, const char *who, const double *h_E,
     return rpe_fetch_results(h, B, R, t, inliers, nullptr, nullptr);
 }
 
-static int stage_refine(rpe_handle *h, const char *who, const double *h_R0, const double *h_t0, const float *h_pts1,
-                        const float *h_pts2, const uint8_t *h_mask, const int32_t *m, int B, const double *K,
-                        const rpe_camera *cam1, const rpe_camera *cam2, int max_iters, double *R, double *t, int32_t *inliers,
-                        int32_t *info, double *rms)
-{
-    RpeRun run;
-    int rc = stage_begin(h, who, h_pts1, h_pts2, m, B, K, cam1, cam2, run);
-    if (rc) return rc;
-    if ((rc = refine_alloc(h)) != RPE_OK) return rc;
-    if ((rc = upload(h, {{h->d_mask, h_mask, (size_t)h->cfg.max_matches * B}, {h->d_ref_R0, h_R0, sizeof(double) * 9 * B},
-                         {h->d_ref_t0, h_t0, sizeof(double) * 3 * B}})) != RPE_OK) return rc;
-    return refine_run(h, run, max_iters, false, R, t, inliers, info, rms);
-}
-
 extern "C" int rpe_find_essential(rpe_handle *h, const float *h_pts1, const float *h_pts2, const int32_t *m, int B,
                                   const double K[9], double *E, uint8_t *mask, int32_t *found, int32_t *info)
 {
@@ -2517,22 +1736,6 @@ extern "C" int rpe_find_essential_cameras(rpe_handle *h, const float *h_pts1, co
     return stage_find_essential(h, "rpe_find_essential_cameras", h_pts1, h_pts2, m, B, nullptr, cam1, cam2, E, mask, found, info);
 }
 
-extern "C" int rpe_find_homography(rpe_handle *h, const float *h_pts1, const float *h_pts2, const int32_t *m, int B,
-                                   const double K[9], int iters, double threshold_px, double *H, double *R_rot, uint8_t *mask,
-                                   int32_t *counts, int32_t *info)
-{
-    if (!h || !h_pts1 || !h_pts2 || !m || !K || B < 1) return rpe_invalid(h, "rpe_find_homography");
-    if (int rc = check_batch(h, B)) return rc;
-    int rc = homography_check(h, "rpe_find_homography", iters, threshold_px);
-    if (rc) return rc;
-    if ((rc = check_match_counts(h, m, B)) != RPE_OK) return rc;
-    RpeRun run;
-    if ((rc = stage_begin(h, "rpe_find_homography", h_pts1, h_pts2, m, B, K, nullptr, nullptr, run)) != RPE_OK) return rc;
-    if ((rc = homography_alloc(h)) != RPE_OK) return rc;
-    rpe_launch_normalise(h, run);
-    return homography_run(h, run, iters, threshold_px, false, H, R_rot, mask, counts, info);
-}
-
 extern "C" int rpe_recover_pose(rpe_handle *h, const double *h_E, const float *h_pts1, const float *h_pts2, const int32_t *m,
                                 int B, const double K[9], double *R, double *t, int32_t *inliers)
 {
@@ -2546,26 +1749,6 @@ extern "C" int rpe_recover_pose_cameras(rpe_handle *h, const double *h_E, const 
 {
     if (!h || !h_E || !h_pts1 || !h_pts2 || !m || !cam1 || !cam2 || B < 1) return rpe_invalid(h, "rpe_recover_pose_cameras");
     return stage_recover_pose(h, "rpe_recover_pose_cameras", h_E, h_pts1, h_pts2, m, B, nullptr, cam1, cam2, R, t, inliers);
-}
-
-extern "C" int rpe_refine_pose_points(rpe_handle *h, const double *h_R0, const double *h_t0, const float *h_pts1,
-                                      const float *h_pts2, const uint8_t *h_mask, const int32_t *m, int B, const double K[9],
-                                      int max_iters, double *R, double *t, int32_t *inliers, int32_t *info, double *rms)
-{
-    if (!h || !h_R0 || !h_t0 || !h_pts1 || !h_pts2 || !h_mask || !m || !K || B < 1) return rpe_invalid(h, "rpe_refine_pose_points");
-    if (int rc = check_batch(h, B)) return rc;      // in front of max_iters, as ever
-    if (max_iters < 1 || max_iters > 100) return rpe_invalid(h, "rpe_refine_pose_points", "max_iters must be 1 ... 100");
-    return stage_refine(h, "rpe_refine_pose_points", h_R0, h_t0, h_pts1, h_pts2, h_mask, m, B, K, nullptr, nullptr, max_iters, R, t, inliers, info, rms);
-}
-
-extern "C" int rpe_refine_pose_points_cameras(rpe_handle *h, const double *h_R0, const double *h_t0, const float *h_pts1,
-                                              const float *h_pts2, const uint8_t *h_mask, const int32_t *m, int B,
-                                              const rpe_camera *cam1, const rpe_camera *cam2, int max_iters, double *R, double *t,
-                                              int32_t *inliers, int32_t *info, double *rms)
-{
-    if (!h || !h_R0 || !h_t0 || !h_pts1 || !h_pts2 || !h_mask || !m || !cam1 || !cam2 || B < 1) return rpe_invalid(h, "rpe_refine_pose_points_cameras");
-    if (max_iters < 1 || max_iters > 100) return rpe_invalid(h, "rpe_refine_pose_points_cameras", "max_iters must be 1 ... 100");
-    return stage_refine(h, "rpe_refine_pose_points_cameras", h_R0, h_t0, h_pts1, h_pts2, h_mask, m, B, nullptr, cam1, cam2, max_iters, R, t, inliers, info, rms);
 }
 
 // ---------------------------------------------------------------- profiling

@@ -350,6 +350,9 @@ struct RpeLastRun {
     int structure = 0;                // pairs [0, structure) of the run have d_mask (status form), d_pose_mask and d_points filled
 };
 
+// The device buffers of one first-use feature: one hipMalloc, carved into the fields of the feature's record by rpe_bufset_fit (below)
+struct RpeBufSet { uint8_t *block = nullptr; size_t bytes = 0; };
+
 // One job of the track kernels (track_kernels.hip): P pairs over n_frames frames, pair p between frames[p].x and frames[p].y,
 // its matches at p * max_matches.  Run form: the run's own match lists, status and masks (rmask / pmask read only under the
 // rules that name them), use_pair or null, edge null.  Stage form: the uploaded lists, rule ALL, edge or null.  pts1 == null:
@@ -363,10 +366,24 @@ struct RpeTrackJob {
     const uint8_t *rmask, *pmask;
     const float2 *pts1, *pts2;
 };
-#define RPE_TRACK_NODE_WORDS 11   // int arrays of one word per node in d_tk_node
+#define RPE_TRACK_NODE_WORDS 11   // int arrays of one word per node in RpeTrackBufs::node
 static inline int rpe_track_scan_blocks(int N) { return (int)(((long long)N + 2047) / 2048); }   // workgroups of the track scans (2048 nodes each)
+// rpe_build_tracks / rpe_tracks_from_matches only (set, fitted to every call's n_frames).  Per match slot [max_batch * max_matches]: the
+// edge flag and match_track; the stage form's uploaded lists (q / t / edge / pts1 / pts2) and per pair its match
+// count; per pair of either form the frame pair and use_pair.  Outputs: counts[8], track_start [slots + 1], observations
+// [2 * slots].  Per node (n_frames * kcap of them): node, RPE_TRACK_NODE_WORDS arrays of one word each, with
+// partial (one int2 per scan workgroup); seen [n_frames]: the set's last pieces, so n_frames moves no other
+struct RpeTrackBufs {
+    uint8_t *eflag = nullptr, *edge = nullptr, *use = nullptr;
+    int *mtrack = nullptr, *q = nullptr, *t = nullptr, *m = nullptr, *counts = nullptr;
+    int *tstart = nullptr, *oframe = nullptr, *okp = nullptr;
+    float2 *oxy = nullptr, *pts1 = nullptr, *pts2 = nullptr;
+    int2 *frames = nullptr, *partial = nullptr;
+    int *node = nullptr, *seen = nullptr; RpeBufSet set;
+    std::vector<int> frame_tab;           // host side of frames: source of its upload
+};
 
-// The track scene (track_scene.h) on the device, as scene_upload (rpe_api.hip) left it: the tracks, the poses and the cameras
+// The track scene (track_scene.h) on the device, as scene_upload (rpe_features.hip) left it: the tracks, the poses and the cameras
 // (cam_stride 1: one per frame; 0: the one record K became)
 struct RpeTrackScene {
     int n_tracks, n_obs, cam_stride;
@@ -382,6 +399,17 @@ struct RpeTrackPointJob {
     const int *group;
 };
 
+// rpe_triangulate_tracks only (set, fitted to every call's tracks, observations and frames), beside the scene.
+// Per track: point, info[4], rms, min_cos out.  Per observation: the record between the two kernels (TpObs,
+// track_point_kernels.hip), flag and error out.  Per frame: group
+#define RPE_TRACK_POINT_OBS_BYTES 80   // one TpObs
+struct RpeTrackPointBufs {
+    int *group = nullptr, *info = nullptr;
+    uint8_t *obs = nullptr;               // [n_obs] records of RPE_TRACK_POINT_OBS_BYTES
+    double *points = nullptr, *rms = nullptr, *mincos = nullptr, *oerr = nullptr;
+    uint8_t *oflag = nullptr; RpeBufSet set;
+};
+
 // One job of the window-bundle kernels (window_kernels.hip): the scene and the uploaded start points, masks (null: all set)
 // and windows
 struct RpeWindowJob {
@@ -390,6 +418,22 @@ struct RpeWindowJob {
     const double *points0;
     const uint8_t *point_use, *obs_use;
     const int *win_start, *win_frame;
+};
+
+// rpe_bundle_windows only (set, fitted to every call's tracks, observations and windows), beside the scene.  The
+// uploads of its own (start points, masks, windows); per observation the record of wb_prepare (WbObs, window_kernels.hip);
+// per window and point slot [n_win * max_points]: the track, the observation of each window position, the state (X and
+// the trial X) and the output point; per window frame the output pose
+#define RPE_WINDOW_OBS_BYTES 32       // one WbObs
+#define RPE_WINDOW_SLOT_OBS RPE_WINDOW_MAX_VIEWS   // ints of a point slot's observation list: one per window position
+#define RPE_WINDOW_STATE_DOUBLES 6    // f64 of a point slot's state: X, then the trial X
+struct RpeWindowBufs {
+    int *wstart = nullptr, *wframe = nullptr;
+    int *ptrack = nullptr, *pobs = nullptr, *counts = nullptr, *info = nullptr, *fcnt = nullptr;
+    uint8_t *obs = nullptr;               // [n_obs] records of RPE_WINDOW_OBS_BYTES
+    double *points0 = nullptr, *state = nullptr, *points = nullptr;
+    double *Rout = nullptr, *Tout = nullptr, *rms = nullptr;
+    uint8_t *puse = nullptr, *ouse = nullptr; RpeBufSet set;
 };
 
 // One job of the pose-graph kernel (graph_kernels.hip): the caller's poses and measurements as uploaded, the graphs in CSR
@@ -404,6 +448,22 @@ struct RpeGraphJob {
     const int *graph_start, *graph_frame, *edge_start, *free_start, *used_start, *precode;
     const int *free_pos, *adj_start, *used_edge, *edge_i, *edge_j, *edge_kind;
     const int2 *adj;
+};
+
+// rpe_optimise_graphs only (set, fitted to every call's frames, graphs and edges).  The uploads: the caller's poses
+// and measurements, the CSR arrays and the host's tables (RpeGraphJob); per graph position the state (the output) and the
+// trial state; per used edge its blocks, per free frame its block, factor and PCG vectors (the layouts: graph_kernels.hip);
+// per edge the two chi, per graph cost and info
+#define RPE_GRAPH_EDGE_DOUBLES 120    // f64 of a used edge's blocks (PG_EB)
+#define RPE_GRAPH_FRAME_DOUBLES 87    // f64 of a free frame's block, factor and PCG vectors (PG_FB)
+struct RpeGraphBufs {
+    double *Rabs = nullptr, *Tabs = nullptr, *eR = nullptr, *et = nullptr, *ew = nullptr;
+    int *gstart = nullptr, *gframe = nullptr, *estart = nullptr, *fstart = nullptr, *ustart = nullptr;
+    int *precode = nullptr, *fpos = nullptr, *astart = nullptr, *uedge = nullptr;
+    int *ei = nullptr, *ej = nullptr, *ekind = nullptr, *info = nullptr;
+    int2 *adj = nullptr;
+    double *Rout = nullptr, *Tout = nullptr, *Rn = nullptr, *Tn = nullptr;
+    double *eb = nullptr, *fb = nullptr, *chi = nullptr, *cost = nullptr; RpeBufSet set;
 };
 
 // One job of the similarity kernels (similar_kernels.hip): the features (the frame store's, or the workspace's of the stage
@@ -421,6 +481,14 @@ struct RpeSimilarJob {
     int *scores, *cand, *cand_score, *n_cand;
 };
 
+// rpe_frames_similar / rpe_similarity_hamming only (set, fitted to every call's lists): the two slot tables (not
+// d_pairtab, which holds 2*max_batch entries: a list here may be as long as the store), the times the caller gave, the
+// nq * nt scores, and per query row its k candidates, their scores and their count
+struct RpeSimilarBufs {
+    int *q = nullptr, *t = nullptr, *qtime = nullptr, *ttime = nullptr;
+    int *scores = nullptr, *cand = nullptr, *cscore = nullptr, *ncand = nullptr; RpeBufSet set;
+};
+
 // One rpe_scale_links link on the device: pairs a and b of the last run, side bit 0 / 1 = the shared frame is image 2 of a / of b
 struct RpeLink { int a, b, side, pad; };
 // What the link kernels (link_kernels.hip) read of the last run, by value (rpe_link_src fills it from the handle): the link
@@ -436,8 +504,77 @@ struct RpeLinkSrc {
     int max_matches, kcap;
 };
 
-// The device buffers of one first-use feature: one hipMalloc, carved into the feature's d_* fields by rpe_bufset_fit (below)
-struct RpeBufSet { uint8_t *block = nullptr; size_t bytes = 0; };
+// The link calls' table (links, created on first use, 4*max_batch links; tab: its host side, the table of the last link
+// call and the source of its upload) and rpe_scale_links' outputs (set, fitted on first use)
+struct RpeLinkBufs {
+    RpeLink *links = nullptr;
+    std::vector<RpeLink> tab;
+    double *stats = nullptr;              // [link][3] lower quartile, median, upper quartile
+    int *n = nullptr, *code = nullptr; RpeBufSet set;
+};
+
+// rpe_link_poses only (set, fitted on first use): per link the pose, {n, inliers}, info[4], rms[2] and the inlier mask
+// [link][max_matches], 4*max_batch links (the link table is RpeLinkBufs::links); corr [link][RPE_LINK_POSE_CORR_DOUBLES *
+// max_matches] holds the correspondence lists of handles above the kernel's LDS cut only (a piece of 0 bytes, null, on the others)
+#define RPE_LINK_POSE_CORR_DOUBLES 5  // f64 of one correspondence: X[3], then q[2]
+struct RpeLinkPoseBufs {
+    double *R = nullptr, *t = nullptr, *rms = nullptr, *corr = nullptr;
+    int *counts = nullptr, *info = nullptr;
+    uint8_t *mask = nullptr; RpeBufSet set;
+};
+
+// rpe_link_bundles / rpe_bundle_three_view only (set, fitted on first use), 4*max_batch problems.  The problems' arrays,
+// indexed by pair a's match index (stage form: point number): view code [prob][max_matches], observations
+// [prob][max_matches][RPE_BUNDLE_OBS_DOUBLES] (S, A, C), points [prob][max_matches][3] (start points in, results out); per
+// problem the scan length, the code decided before the bundle, the start poses in the solved form [RPE_BUNDLE_POSE_DOUBLES]
+// and the focal scales [2]; the callers' poses of pair b; the results; state [prob][RPE_BUNDLE_STATE_DOUBLES * max_matches]
+// holds the point state of handles above the kernel's LDS cut only (a piece of 0 bytes, null, on the others)
+#define RPE_BUNDLE_OBS_DOUBLES 6      // f64 of a point's observations: S x, y, A x, y, C x, y
+#define RPE_BUNDLE_POSE_DOUBLES 24    // f64 of a problem's start poses: R, t of S -> A, then of S -> C
+#define RPE_BUNDLE_STATE_DOUBLES 6    // f64 of a point's state: X, then the trial X
+struct RpeBundleBufs {
+    uint8_t *views = nullptr; RpeBufSet set;
+    double *obs = nullptr, *points = nullptr, *pose0 = nullptr, *focal = nullptr, *state = nullptr;
+    double *Rin = nullptr, *tin = nullptr;
+    int *n = nullptr, *pre = nullptr, *counts = nullptr, *info = nullptr;
+    double *Ra = nullptr, *ta = nullptr, *Rb = nullptr, *tb = nullptr, *rms = nullptr;
+};
+
+// rpe_refine_poses / rpe_refine_pose_points only (set, fitted on first use): refined pose, cheirality count, info[4],
+// rms[2] per pair; start pose of the stage form
+struct RpeRefineBufs {
+    double *R = nullptr, *t = nullptr, *rms = nullptr, *R0 = nullptr, *t0 = nullptr;
+    int *inl = nullptr, *info = nullptr; RpeBufSet set;
+};
+
+// The guided matchers of either norm only (rpe_guided_matches[_l2], rpe_match_hamming_guided, rpe_match_l2_guided; set,
+// fitted on first use): match lists of their own, shaped like the run's d_m_* / d_pts* (d: int32 Hamming distances, or f32
+// L2 distances in the same four bytes); the poses gated with when the caller supplies them; per pair and image one 32-byte
+// record per keypoint [pair][RPE_GUIDED_SIDES][kcap] and the squared threshold (see guided_records_kernel)
+#define RPE_GUIDED_SIDES 2            // record lists of a pair: one per image
+struct RpeGuidedBufs {
+    int *q = nullptr, *t = nullptr, *d = nullptr, *n = nullptr;
+    float2 *pts1 = nullptr, *pts2 = nullptr;
+    double *R = nullptr, *tr = nullptr, *thr2 = nullptr;
+    double4 *rec = nullptr; RpeBufSet set;
+};
+
+// rpe_pair_homographies / rpe_find_homography only (set, fitted on first use): H, R_rot, {n_H, n_rot, n_E} and info[4]
+// per pair, the winner's inlier mask [pair][max_matches]
+struct RpeHomographyBufs {
+    double *H = nullptr, *R = nullptr;
+    int *counts = nullptr, *info = nullptr;
+    uint8_t *mask = nullptr; RpeBufSet set;
+};
+
+// The track scene of rpe_triangulate_tracks and rpe_bundle_windows (set, fitted to every call's tracks, observations and
+// frames by scene_upload; either call uploads its own scene, none is kept).  Per track the CSR offsets, per observation
+// frame and pixel, per frame R, T and camera (cam_k: the host side of the one record K becomes)
+struct RpeSceneBufs {
+    int *tstart = nullptr, *oframe = nullptr; float2 *oxy = nullptr;
+    double *R = nullptr, *T = nullptr; rpe_camera *cams = nullptr;
+    rpe_camera cam_k{}; RpeBufSet set;
+};
 
 struct rpe_handle {
     rpe_config cfg;
@@ -511,98 +648,9 @@ struct rpe_handle {
     uint8_t *d_mask = nullptr;            // [pair][max_matches]
     uint8_t *d_pose_mask = nullptr;       // [pair][max_matches] rpe_fetch_structure only (created on first use)
     double *d_points = nullptr;           // [pair][max_matches][3] rpe_fetch_structure only (created on first use)
-    // rpe_refine_poses / rpe_refine_pose_points only (set_refine, fitted on first use): refined pose, cheirality count,
-    // info[4], rms[2] per pair; start pose of the stage form
-    double *d_ref_R = nullptr, *d_ref_t = nullptr, *d_ref_rms = nullptr, *d_ref_R0 = nullptr, *d_ref_t0 = nullptr;
-    int *d_ref_inl = nullptr, *d_ref_info = nullptr; RpeBufSet set_refine;
-    // the link calls' table (created on first use) and rpe_scale_links' outputs (set_links, fitted on first use), 4*max_batch links
-    RpeLink *d_links = nullptr;
-    std::vector<RpeLink> link_tab;        // host side of d_links: the table of the last link call, source of its upload
-    double *d_link_stats = nullptr;       // [link][3] lower quartile, median, upper quartile
-    int *d_link_n = nullptr, *d_link_code = nullptr; RpeBufSet set_links;
-    // the guided matchers of either norm only (rpe_guided_matches[_l2], rpe_match_hamming_guided, rpe_match_l2_guided;
-    // set_guided, fitted on first use): match lists of their own, shaped like the run's d_m_* / d_pts* (d_gm_d: int32 Hamming
-    // distances, or f32 L2 distances in the same four bytes); the poses gated with when the caller supplies them; per pair and image one 32-byte record per
-    // keypoint [pair][2][kcap] and the squared threshold (see guided_records_kernel)
-    int *d_gm_q = nullptr, *d_gm_t = nullptr, *d_gm_d = nullptr, *d_gm_n = nullptr;
-    float2 *d_gm_pts1 = nullptr, *d_gm_pts2 = nullptr;
-    double *d_gm_R = nullptr, *d_gm_tr = nullptr, *d_gm_thr2 = nullptr;
-    double4 *d_gm_rec = nullptr; RpeBufSet set_guided;
-    // rpe_pair_homographies / rpe_find_homography only (set_homography, fitted on first use): H, R_rot, {n_H, n_rot, n_E}
-    // and info[4] per pair, the winner's inlier mask [pair][max_matches]
-    double *d_hg_H = nullptr, *d_hg_R = nullptr;
-    int *d_hg_counts = nullptr, *d_hg_info = nullptr;
-    uint8_t *d_hg_mask = nullptr; RpeBufSet set_homography;
-    // rpe_link_poses only (set_link_poses, fitted on first use): per link the pose, {n, inliers}, info[4], rms[2] and the
-    // inlier mask [link][max_matches], 4*max_batch links (the link table is d_links); d_lp_corr [link][5 * max_matches]
-    // holds the correspondence lists of handles above the kernel's LDS cut only (a piece of 0 bytes, null, on the others)
-    double *d_lp_R = nullptr, *d_lp_t = nullptr, *d_lp_rms = nullptr, *d_lp_corr = nullptr;
-    int *d_lp_counts = nullptr, *d_lp_info = nullptr;
-    uint8_t *d_lp_mask = nullptr; RpeBufSet set_link_poses;
-    // rpe_link_bundles / rpe_bundle_three_view only (set_bundles, fitted on first use), 4*max_batch problems.  The problems' arrays,
-    // indexed by pair a's match index (stage form: point number): view code [prob][max_matches], observations
-    // [prob][max_matches][6] (S, A, C), points [prob][max_matches][3] (start points in, results out); per problem the scan
-    // length, the code decided before the bundle, the start poses in the solved form [24] and the focal scales [2]; the
-    // callers' poses of pair b; the results; d_ba_state [prob][6 * max_matches] holds the point state of handles above
-    // the kernel's LDS cut only (a piece of 0 bytes, null, on the others)
-    uint8_t *d_ba_views = nullptr; RpeBufSet set_bundles;
-    double *d_ba_obs = nullptr, *d_ba_points = nullptr, *d_ba_pose0 = nullptr, *d_ba_focal = nullptr, *d_ba_state = nullptr;
-    double *d_ba_Rin = nullptr, *d_ba_tin = nullptr;
-    int *d_ba_n = nullptr, *d_ba_pre = nullptr, *d_ba_counts = nullptr, *d_ba_info = nullptr;
-    double *d_ba_Ra = nullptr, *d_ba_ta = nullptr, *d_ba_Rb = nullptr, *d_ba_tb = nullptr, *d_ba_rms = nullptr;
-    // rpe_build_tracks / rpe_tracks_from_matches only (set_tracks, fitted to every call's n_frames).  Per match slot [max_batch * max_matches]: the
-    // edge flag and match_track; the stage form's uploaded lists (d_tk_q / _t / _edge / _pts1 / _pts2) and per pair its match
-    // count; per pair of either form the frame pair and use_pair.  Outputs: counts[8], track_start [slots + 1], observations
-    // [2 * slots].  Per node (n_frames * kcap of them): d_tk_node, RPE_TRACK_NODE_WORDS arrays of one word each, with
-    // d_tk_partial (one int2 per scan workgroup); d_tk_seen [n_frames]: the set's last pieces, so n_frames moves no other
-    uint8_t *d_tk_eflag = nullptr, *d_tk_edge = nullptr, *d_tk_use = nullptr;
-    int *d_tk_mtrack = nullptr, *d_tk_q = nullptr, *d_tk_t = nullptr, *d_tk_m = nullptr, *d_tk_counts = nullptr;
-    int *d_tk_tstart = nullptr, *d_tk_oframe = nullptr, *d_tk_okp = nullptr;
-    float2 *d_tk_oxy = nullptr, *d_tk_pts1 = nullptr, *d_tk_pts2 = nullptr;
-    int2 *d_tk_frames = nullptr, *d_tk_partial = nullptr;
-    int *d_tk_node = nullptr, *d_tk_seen = nullptr; RpeBufSet set_tracks;
-    std::vector<int> tk_frame_tab;        // host side of d_tk_frames: source of its upload
-    // The track scene of rpe_triangulate_tracks and rpe_bundle_windows (scene.set, fitted to every call's tracks, observations
-    // and frames by scene_upload; either call uploads its own scene, none is kept).  Per track the CSR offsets, per observation
-    // frame and pixel, per frame R, T and camera (cam_k: the host side of the one record K becomes)
-    struct Scene {
-        int *d_tstart = nullptr, *d_oframe = nullptr; float2 *d_oxy = nullptr;
-        double *d_R = nullptr, *d_T = nullptr; rpe_camera *d_cams = nullptr;
-        rpe_camera cam_k{}; RpeBufSet set;
-    } scene;
-    // rpe_triangulate_tracks only (set_track_points, fitted to every call's tracks, observations and frames), beside the scene.
-    // Per track: point, info[4], rms, min_cos out.  Per observation: the 80-byte record between the two kernels, flag and
-    // error out.  Per frame: group
-    int *d_tp_group = nullptr, *d_tp_info = nullptr;
-    double2 *d_tp_obs = nullptr;          // [5 * n_obs]: one 80-byte record per observation
-    double *d_tp_points = nullptr, *d_tp_rms = nullptr, *d_tp_mincos = nullptr, *d_tp_oerr = nullptr;
-    uint8_t *d_tp_oflag = nullptr; RpeBufSet set_track_points;
-    // rpe_bundle_windows only (set_windows, fitted to every call's tracks, observations and windows), beside the scene.  The
-    // uploads of its own (start points, masks, windows); per observation the 32-byte record of wb_prepare; per window and point
-    // slot [n_win * max_points]: the track, the observation of each window position (8 ints), the state X and the trial X
-    // (6 f64) and the output point; per window frame the output pose
-    int *d_wb_wstart = nullptr, *d_wb_wframe = nullptr;
-    int *d_wb_ptrack = nullptr, *d_wb_pobs = nullptr, *d_wb_counts = nullptr, *d_wb_info = nullptr, *d_wb_fcnt = nullptr;
-    double4 *d_wb_obs = nullptr;
-    double *d_wb_points0 = nullptr, *d_wb_state = nullptr, *d_wb_points = nullptr;
-    double *d_wb_Rout = nullptr, *d_wb_Tout = nullptr, *d_wb_rms = nullptr;
-    uint8_t *d_wb_puse = nullptr, *d_wb_ouse = nullptr; RpeBufSet set_windows;
-    // rpe_optimise_graphs only (set_graphs, fitted to every call's frames, graphs and edges).  The uploads: the caller's poses
-    // and measurements, the CSR arrays and the host's tables (RpeGraphJob); per graph position the state (the output) and the
-    // trial state; per used edge the 120 f64 of its blocks, per free frame the 87 f64 of its block, factor and PCG vectors
-    // (graph_kernels.hip); per edge the two chi, per graph cost and info
-    double *d_pg_Rabs = nullptr, *d_pg_Tabs = nullptr, *d_pg_eR = nullptr, *d_pg_et = nullptr, *d_pg_ew = nullptr;
-    int *d_pg_gstart = nullptr, *d_pg_gframe = nullptr, *d_pg_estart = nullptr, *d_pg_fstart = nullptr, *d_pg_ustart = nullptr;
-    int *d_pg_precode = nullptr, *d_pg_fpos = nullptr, *d_pg_astart = nullptr, *d_pg_uedge = nullptr;
-    int *d_pg_ei = nullptr, *d_pg_ej = nullptr, *d_pg_ekind = nullptr, *d_pg_info = nullptr;
-    int2 *d_pg_adj = nullptr;
-    double *d_pg_Rout = nullptr, *d_pg_Tout = nullptr, *d_pg_Rn = nullptr, *d_pg_Tn = nullptr;
-    double *d_pg_eb = nullptr, *d_pg_fb = nullptr, *d_pg_chi = nullptr, *d_pg_cost = nullptr; RpeBufSet set_graphs;
-    // rpe_frames_similar / rpe_similarity_hamming only (set_similar, fitted to every call's lists): the two slot tables (not
-    // d_pairtab, which holds 2*max_batch entries: a list here may be as long as the store), the times the caller gave, the
-    // nq * nt scores, and per query row its k candidates, their scores and their count
-    int *d_sim_q = nullptr, *d_sim_t = nullptr, *d_sim_qtime = nullptr, *d_sim_ttime = nullptr;
-    int *d_sim_scores = nullptr, *d_sim_cand = nullptr, *d_sim_cscore = nullptr, *d_sim_ncand = nullptr; RpeBufSet set_similar;
+    // the first-use features: one record each (above, beside the feature's job)
+    RpeRefineBufs ref; RpeLinkBufs link; RpeLinkPoseBufs lp; RpeBundleBufs ba; RpeGuidedBufs gm; RpeHomographyBufs hg;
+    RpeTrackBufs tk; RpeSceneBufs scene; RpeTrackPointBufs tp; RpeWindowBufs wb; RpeGraphBufs pg; RpeSimilarBufs sim;
     // results
     double *d_R = nullptr, *d_t = nullptr, *d_E = nullptr;
     int *d_inliers = nullptr, *d_status = nullptr;
@@ -654,8 +702,8 @@ static int dmalloc(rpe_handle *h, T **p, size_t n)
 // a single buffer created on first use
 #define DM_ONCE(h, p, n) do { if (!(p)) DM(h, p, n); } while (0)
 
-// The buffers a feature creates on first use are ONE set of the handle and ONE piece list -- its d_* fields with the sizes
-// THIS call needs -- given to rpe_bufset_fit behind the host-side checks and hipSetDevice, before the first upload:
+// The buffers a feature creates on first use are ONE set of its record and ONE piece list -- the record's fields with the
+// sizes THIS call needs -- given to rpe_bufset_fit behind the host-side checks and hipSetDevice, before the first upload:
 //   layout   piece i sits at the running sum of the 256-byte-aligned sizes of the pieces before it; the total is that sum,
 //            and at least 256 (buf_layout.h).  A piece of 0 bytes gets nullptr.
 //   growth   total > set.bytes: wait on the handle's stream if there is a block (growth is rare, and a call that returned
@@ -667,10 +715,14 @@ static int dmalloc(rpe_handle *h, T **p, size_t n)
 // Nothing in a set outlives its call (inputs are uploaded or written by the call's own kernels, outputs fetched before it
 // returns; d_pose_mask and d_points do persist and stay DM_ONCE buffers), and none is part of a captured graph.  That is
 // also why two features may share a set: scene.set serves the track points and the window bundles, each beside its own.
-struct RpeBufPiece { void **p; size_t bytes; };
+// A set fitted to the call's own sizes names, with each piece, the host array the call uploads into it (src, or null):
+// the one list is fitted and then walked by rpe_bufset_upload, so a copy is exactly as long as its piece.
+struct RpeBufPiece { void **p; size_t bytes; const void *src; };
 template <typename T>
-static inline RpeBufPiece buf_piece(T *&p, size_t n) { return {(void **)&p, n * sizeof(T)}; }
+static inline RpeBufPiece buf_piece(T *&p, size_t n, const void *src = nullptr) { return {(void **)&p, n * sizeof(T), src}; }
 int rpe_bufset_fit(rpe_handle *h, RpeBufSet &s, std::initializer_list<RpeBufPiece> pieces);   // rpe_api.hip
+// the upload rule (rpe_host.h) over a fitted list: every piece that has a source and bytes, on the handle's stream, no wait
+int rpe_bufset_upload(rpe_handle *h, std::initializer_list<RpeBufPiece> pieces);              // rpe_api.hip
 
 // A failed HIP call ends the entry point: the text goes to the handle, or (rpe_create, no handle yet) to the create-time string
 extern std::string g_create_err;
@@ -710,12 +762,12 @@ static inline RpeRun rpe_run_list(const rpe_handle *h, int P, RpeCamSrc cam = {n
     return {P, {h->fs.d_desc, h->fs.d_count, h->fs.d_kp_pt, h->fs.d_norm, (const int2 *)h->d_pairtab, 0}, cam};
 }
 
-// The links one call may carry, and the entries of d_links and of every per-link buffer
+// The links one call may carry, and the entries of link.links and of every per-link buffer
 static inline int rpe_link_capacity(const rpe_handle *h) { return 4 * h->cfg.max_batch; }
-// The link kernels' source: the table in d_links over the last run's buffers
+// The link kernels' source: the table in link.links over the last run's buffers
 static inline RpeLinkSrc rpe_link_src(const rpe_handle *h)
 {
-    return {h->d_links, h->d_m_q, h->d_m_t, h->d_m_n, h->d_status, h->d_mask, h->d_pose_mask, h->d_points, h->d_R, h->d_t,
+    return {h->link.links, h->d_m_q, h->d_m_t, h->d_m_n, h->d_status, h->d_mask, h->d_pose_mask, h->d_points, h->d_R, h->d_t,
             h->d_n1, h->d_n2, h->cfg.max_matches, h->lay.kcap};
 }
 

@@ -259,17 +259,17 @@ __global__ __launch_bounds__(256) void tk_finish_kernel(const TkArgs a)
     if (threadIdx.x == 0) { a.counts[5] = n; a.o_tstart[a.counts[0]] = a.counts[1]; }
 }
 
-// The whole sequence for one job.  The buffers are the caller's business (rpe_api.hip, tracks_alloc): the node block holds
+// The whole sequence for one job.  The buffers are the caller's business (rpe_features.hip, tracks_alloc): the node block holds
 // RPE_TRACK_NODE_WORDS arrays of N words
 void rpe_launch_tracks(rpe_handle *h, const RpeTrackJob &job)
 {
     TkArgs a{};
     a.job = job; a.mm = h->cfg.max_matches; a.KC = h->lay.kcap; a.N = job.n_frames * a.KC;
-    int *w = h->d_tk_node;
+    int *w = h->tk.node;
     int **arr[RPE_TRACK_NODE_WORDS] = {&a.parent, &a.first, &a.size, &a.label, &a.segstart, &a.cursor, &a.rank, &a.tidx, &a.tstart, &a.conflict, &a.members};
     for (int k = 0; k < RPE_TRACK_NODE_WORDS; ++k) *arr[k] = w + (size_t)k * a.N;
-    a.frame_seen = h->d_tk_seen; a.partial = h->d_tk_partial; a.eflag = h->d_tk_eflag; a.mtrack = h->d_tk_mtrack; a.counts = h->d_tk_counts;
-    a.o_tstart = h->d_tk_tstart; a.o_frame = h->d_tk_oframe; a.o_kp = h->d_tk_okp; a.o_xy = h->d_tk_oxy;
+    a.frame_seen = h->tk.seen; a.partial = h->tk.partial; a.eflag = h->tk.eflag; a.mtrack = h->tk.mtrack; a.counts = h->tk.counts;
+    a.o_tstart = h->tk.tstart; a.o_frame = h->tk.oframe; a.o_kp = h->tk.okp; a.o_xy = h->tk.oxy;
     const hipStream_t s = h->stream;
     const long long slots = (long long)job.P * a.mm;
     const dim3 blk(256), gn((unsigned)(((long long)std::max(a.N, 8) + 255) / 256)), gm((unsigned)((slots + 255) / 256));

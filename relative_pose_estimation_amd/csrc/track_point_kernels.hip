@@ -12,7 +12,7 @@
 #include "geom_device.h"
 
 struct alignas(16) TpObs { double x, y, d[3], c[3], f; int group, frame; };
-static_assert(sizeof(TpObs) == 80, "five 16-byte loads per observation");
+static_assert(sizeof(TpObs) == RPE_TRACK_POINT_OBS_BYTES, "five 16-byte loads per observation");
 
 struct TpArgs {
     RpeTrackPointJob job;
@@ -206,14 +206,14 @@ __global__ __launch_bounds__(256) void tp_solve_kernel(const TpArgs a)
     a.rms[t] = rms; a.min_cos[t] = mc;
 }
 
-// The two launches of one job.  The buffers are the caller's business (rpe_triangulate_tracks, rpe_api.hip)
+// The two launches of one job.  The buffers are the caller's business (rpe_triangulate_tracks, rpe_features.hip)
 void rpe_launch_track_points(rpe_handle *h, const RpeTrackPointJob &job)
 {
     TpArgs a{};
     a.job = job;
-    a.obs = (TpObs *)h->d_tp_obs;
-    a.points = h->d_tp_points; a.rms = h->d_tp_rms; a.min_cos = h->d_tp_mincos; a.obs_err = h->d_tp_oerr;
-    a.info = h->d_tp_info; a.obs_flag = h->d_tp_oflag;
+    a.obs = (TpObs *)h->tp.obs;
+    a.points = h->tp.points; a.rms = h->tp.rms; a.min_cos = h->tp.mincos; a.obs_err = h->tp.oerr;
+    a.info = h->tp.info; a.obs_flag = h->tp.oflag;
     const dim3 blk(256);
     if (job.scene.n_obs > 0) hipLaunchKernelGGL(tp_prepare_kernel, dim3((unsigned)(((long long)job.scene.n_obs + 255) / 256)), blk, 0, h->stream, a);
     hipLaunchKernelGGL(tp_solve_kernel, dim3((unsigned)(((long long)job.scene.n_tracks + 255) / 256)), blk, 0, h->stream, a);

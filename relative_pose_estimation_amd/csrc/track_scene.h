@@ -16,7 +16,7 @@ struct RpeSceneArgs {
 };
 
 // Phase 1, in front of the empty-call return: the scalars and the CSR shape of track_start (when given; n_tracks + 1 entries
-// are read, behind the test of n_tracks).  The cameras are the caller's to check (check_cameras, rpe_api.hip).
+// are read, behind the test of n_tracks).  The cameras are the caller's to check (check_cameras, rpe_host.h).
 static inline const char *rpe_scene_check_shape(const RpeSceneArgs &a)
 {
     if (a.n_tracks < 0) return "n_tracks must be >= 0";

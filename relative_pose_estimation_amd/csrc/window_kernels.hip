@@ -25,11 +25,12 @@
 #include "geom_device.h"
 
 #define WB_V RPE_WINDOW_MAX_VIEWS
+static_assert(WB_V == RPE_WINDOW_SLOT_OBS, "wb.pobs holds one observation per window position and point slot");
 #define WB_NS (6 * WB_V - 7)                   // most camera parameters: 41
 #define WB_PAIRS ((WB_V - 1) * WB_V / 2)       // most pairs (p <= q) of free positions: 28
 
 struct alignas(16) WbObs { double x, y, f, pad; };
-static_assert(sizeof(WbObs) == sizeof(double4), "d_wb_obs holds one double4 per observation");
+static_assert(sizeof(WbObs) == RPE_WINDOW_OBS_BYTES, "wb.obs holds one record per observation");
 
 struct WbArgs {
     RpeWindowJob job;
@@ -177,7 +178,7 @@ __global__ __launch_bounds__(256) void wb_solve_kernel(const WbArgs a)
     const int n = a.counts[w * 4 + 1], nobs = a.counts[w * 4 + 2];
     const size_t pm = (size_t)w * jb.max_points;
     const int *ptrack = a.ptrack + pm, *pobs = a.pobs + pm * WB_V;
-    double *sX = a.state + pm * 6, *sXn = sX + 3 * (size_t)jb.max_points;
+    double *sX = a.state + pm * RPE_WINDOW_STATE_DOUBLES, *sXn = sX + 3 * (size_t)jb.max_points;
     double *pts = a.points + pm * 3;
     // ---- the gauge: every position relative to position 0
     if (tid < WB_V) s_fr[tid] = tid < W ? jb.win_frame[ws + tid] : 0;
@@ -528,14 +529,14 @@ __global__ __launch_bounds__(256) void wb_solve_kernel(const WbArgs a)
     }
 }
 
-// The three launches of one job.  The buffers are the caller's business (rpe_bundle_windows, rpe_api.hip)
+// The three launches of one job.  The buffers are the caller's business (rpe_bundle_windows, rpe_features.hip)
 void rpe_launch_windows(rpe_handle *h, const RpeWindowJob &job)
 {
     WbArgs a{};
     a.job = job;
-    a.obs = (WbObs *)h->d_wb_obs;
-    a.ptrack = h->d_wb_ptrack; a.pobs = h->d_wb_pobs; a.fcnt = h->d_wb_fcnt; a.counts = h->d_wb_counts; a.info = h->d_wb_info;
-    a.state = h->d_wb_state; a.points = h->d_wb_points; a.Rout = h->d_wb_Rout; a.Tout = h->d_wb_Tout; a.rms = h->d_wb_rms;
+    a.obs = (WbObs *)h->wb.obs;
+    a.ptrack = h->wb.ptrack; a.pobs = h->wb.pobs; a.fcnt = h->wb.fcnt; a.counts = h->wb.counts; a.info = h->wb.info;
+    a.state = h->wb.state; a.points = h->wb.points; a.Rout = h->wb.Rout; a.Tout = h->wb.Tout; a.rms = h->wb.rms;
     const dim3 blk(256);
     if (job.scene.n_obs > 0) hipLaunchKernelGGL(wb_prepare_kernel, dim3((unsigned)(((long long)job.scene.n_obs + 255) / 256)), blk, 0, h->stream, a);
     hipLaunchKernelGGL(wb_gather_kernel, dim3(job.n_win), blk, 0, h->stream, a);
